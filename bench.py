@@ -2,6 +2,15 @@
 """bench.py -- SA neighbour-cost evaluations per second on MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W        (N=1: plain python; N>1: torchrun)
+          [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, the workload, the
+state after the timed steps ("final") and the set-up ("prepare", "whole_run").  Everything below that takes work
+of its own -- the exchange, `roofline`, `default_mode`, `cpu_baseline`, the young-slab rate and the `gates` -- is
+measured with `--full` only.  `--dump-outputs DIR` writes what the timed steps left rank 0's chain with, after them:
+counters.npy (steps, evaluations, accepted moves), costs.npy (current and best perplexity), current_packets.npy and
+best_packets.npy ((position, type, dist, len) per packet on the walk; above 2^19 packets a fixed, seeded sample),
+all float64.  The inputs are seeded: two builds given the same arguments can be compared file for file.
 
 One "step" = one pass of the hot path over one batch: K_nb candidate neighbours of the current slab
 generated and costed exactly (each cost = the u64 perplexity of one complete parse of the input), one
@@ -11,8 +20,8 @@ Workload.  N = 1: BASELINE configs[2], the largest single-GPU configuration -- d
 (synthetic, seeded: no corpora exist offline), 16 384 neighbours/step, lc=lp=pb=0, top-K 20.  N > 1:
 configs[3], one independent chain per GPU on an enwik8-shaped 100 000 000 B input, 16 384 neighbours/step
 (weak scaling, no data-path collective).  The per-epoch best-slab exchange (one 8-byte RCCL all-reduce + one
-broadcast of the packed slab, from the C library: configs[3] runs it every 10 000 steps) is run once, right after
-the timed steps, and timed on its own ("exchange"): it is not a step.  `--config` selects another workload.
+broadcast of the packed slab, from the C library: configs[3] runs it every 10 000 steps) is run once with `--full`,
+right after the timed steps, and timed on its own ("exchange"): it is not a step.  `--config` selects another workload.
 
 State measured.  The configs are long runs (10^5 .. 10^6 steps); what such a run does almost all of the time is
 step an *evolved* slab.  So the set-up phase first runs `--prepare-steps` search steps from the all-literal slab
@@ -152,6 +161,40 @@ def load_pmc(cfg):
         return json.load(f), path
 
 
+DUMP_PACKETS = 1 << 19  # --dump-outputs: packets per parse at most (2 parses x 4 float64 columns = 32 MB)
+
+
+def walk_packets(slab):
+    """(position, type, dist, len) of the packets on a slab's walk, float64 (every field is exact there); above
+    DUMP_PACKETS of them a fixed, seeded sample, in walk order."""
+    import numpy as np
+
+    lens, n = slab["len"].tolist(), len(slab)
+    pos, walk = 0, []
+    while pos < n:
+        walk.append(pos)
+        pos += max(1, lens[pos])
+    p = np.asarray(walk, dtype=np.int64)
+    if len(p) > DUMP_PACKETS:
+        p = p[np.sort(np.random.default_rng(1673551).choice(len(p), DUMP_PACKETS, replace=False))]
+    return np.stack([p, slab["type"][p], slab["dist"][p], slab["len"][p]], axis=1).astype(np.float64)
+
+
+def dump_outputs(out_dir, sa, st):
+    """What a caller of the timed path (SA.run) receives from it: the run's counters that do not depend on time, the
+    current and the best parse and their costs (exact u64 perplexities, < 2^53)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    cur, cur_cost = sa.current()
+    best, best_cost = sa.best()
+    arrays = {"counters": np.array([st["steps"], st["evaluations"], st["accepted"]], dtype=np.float64),
+              "costs": np.array([cur_cost, best_cost], dtype=np.float64),
+              "current_packets": walk_packets(cur), "best_packets": walk_packets(best)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 CONFIG_ITERS = {"c1": 1000, "c2": 100000, "c3": 1000000}  # BASELINE.json configs: SA iterations named per config
 
 
@@ -279,9 +322,14 @@ def main():
     ap.add_argument("--accept", default=None, choices=["auto", "single", "bulk"],
                     help="accept mode of the warm-up and timed steps (default: single; the set-up phase always runs in auto)")
     ap.add_argument("--greedy-seed", type=int, default=-1, help="set-up from the greedy seed with this many candidates (default: 64 above 32 MB, else off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the exchange (N > 1), roofline, default accept "
+                         "mode, correctness gates, CPU baselines, young-slab rate and size gates")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the chain's state they left (rank 0) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the young-slab rate and the size gates")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the young-slab rate and the size gates")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -403,8 +451,10 @@ def main():
     st = sa.run(args.steps)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sa, st)
     exchange = None
-    if dist is not None:
+    if dist is not None and args.full:
         t1 = time.perf_counter()
         if comm is not None:
             winner, wcost = multi_gpu.exchange_best_native(sa, comm)
@@ -421,7 +471,7 @@ def main():
     # the dominant kernel's algorithmic bytes, counted by the kernel itself (k_sim<true>: every chain position / event /
     # list entry its loads ask for) over a few more steps of the same state, outside the timed region
     counted = None
-    if rank == 0 and st.get("sim_launches"):
+    if rank == 0 and args.full and st.get("sim_launches"):
         sa.debug_set(4, 1)
         for _ in range(4):  # (the device now and then tries the one-kernel form for a few steps: no k_sim launches in those)
             cs = sa.run(8)
@@ -434,7 +484,7 @@ def main():
     # the same state in the library's default accept mode (auto: steps take every compatible improving neighbour and patch
     # them in at once, or rebuild when they are many), for the same number of steps: what a user of the defaults gets
     default_mode = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sa.set_accept_mode("auto")
         sa.run(4)
         ba0 = sa.batch_counters()
@@ -458,67 +508,69 @@ def main():
         elapsed, evals, walked = float(tmax[0]), float(t[1]), float(t[2])
 
     if rank == 0:
-        P = st["packets"]
-        b_eval = n + 12 * P  # every input byte once + one 12-byte packet record per packet of the parse
         launches = max(1, st["neighbour_launches"])
-        nbr_ms = st["gpu_ms_neighbours"] / launches  # all neighbour kernels of a step, HIP events on the library's streams
-        evals_per_step = st["evaluations"] / max(1, st["steps"])
-        pmc, pmc_path = load_pmc(cfg)
-        sim_ms = st["gpu_ms_sim"] / st["sim_launches"] if st.get("sim_launches") else None  # HIP events on the streams k_sim runs on
-        roof = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
-                "kernel": "k_sim (chain re-simulation), the dominant kernel: one launch per slice of the step's neighbours + one over the second "
-                          "pass's list; per touched probability context a lane follows the base chain from the first change until the "
-                          "perturbed probability re-joins the base trajectory",
-                "avg_launch_ms": sim_ms, "launches_timed": st.get("sim_launches", 0),
-                "definition": "achieved = the kernel's ALGORITHMIC bytes per launch (chain positions and events and change-list entries its loads ask "
-                              "for, counted by the kernel itself in a few extra steps after the timed region) / its average launch duration measured "
-                              "live with HIP events on its streams; traffic = HBM bytes per launch from rocprofv3 FETCH_SIZE + WRITE_SIZE (raw) of "
-                              "the stored profile, null when that profile was taken of other kernel sources than the ones running",
-                "algorithmic_equiv_gbs": evals_per_step * b_eval / (nbr_ms * 1e-3) / 1e9 if nbr_ms > 0 else None,
-                "algorithmic_note": "SURVEY 8d's figure -- evaluations/step x (N + 12 P) / time of all neighbour kernels: what a streaming evaluator "
-                                    "would move; the incremental kernels price only the changed window, so this is not a fraction of anything",
-                "b_eval_bytes": b_eval, "packets_on_walk": P, "packets_walked_per_eval": walked / max(1.0, evals)}
-        if counted and sim_ms:
-            per_launch = counted["bytes"] / counted["launches"]
-            roof["algorithmic_bytes_per_launch"] = per_launch
-            # per evaluation: over the steps that ran the split form (k_sim launches per such step: one per slice of the step's
-            # neighbours -- two above 1 MiB -- and one over the second pass's list; steps of a trial of the one-kernel form launch none)
-            per_step = 3 if n > (1 << 20) else 2
-            roof["algorithmic_bytes_per_evaluation"] = per_launch * per_step / max(1.0, counted["evaluations"] / max(1, counted["steps"]))
-            roof["counted_over"] = (f"{counted['launches'] // per_step} of {counted['steps']} steps after the timed region "
-                                    f"({counted['launches']} launches, kernel's own byte counters on)")
-            roof["achieved"] = per_launch / (sim_ms * 1e-3) / 1e9
-            roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
-        nk = {"avg_ms_per_step_live": nbr_ms, "launches_timed": launches}  # all neighbour kernels of a step together
-        if pmc:
-            ks = pmc["kernels"]
-            fresh = pmc.get("source_hash") == source_hash()
-            dom = {k: v for k, v in ks.items() if any(k.startswith(d) for d in DOMINANT)}
-            sim = [v for k, v in ks.items() if k.startswith(SIM)]
-            roof["traffic_source"] = os.path.relpath(pmc_path, ROOT)
-            roof["traffic_profile_matches_build"] = fresh
-            if fresh and sim:
-                roof["traffic"] = sum(v.get("hbm_bytes_raw_per_launch", 0.0) * v["launches_per_step"] for v in sim) / sum(v["launches_per_step"] for v in sim)
-                roof["traffic_upper_gfx950_fetch_x2"] = sum(v.get("hbm_bytes_upper_per_launch", 0.0) * v["launches_per_step"] for v in sim) / sum(v["launches_per_step"] for v in sim)
-                roof["profile_avg_launch_ms"] = sum(v["us_per_step"] for v in sim) / sum(v["launches_per_step"] for v in sim) / 1e3
-                if sim_ms:
-                    roof["hbm_frac_raw_counters"] = roof["traffic"] / (sim_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-            elif not fresh:
-                roof["traffic_note"] = "the stored profile was taken of other kernel sources (source_hash differs): no counter figure is claimed for this build"
-            if fresh:
-                raw = sum(v.get("hbm_bytes_raw_per_launch", 0.0) * v["launches_per_step"] for v in dom.values())
-                upper = sum(v.get("hbm_bytes_upper_per_launch", 0.0) * v["launches_per_step"] for v in dom.values())
-                if raw and nbr_ms > 0:
-                    nk.update(hbm_bytes_raw_per_step=raw, hbm_bytes_upper_per_step=upper, frac_raw_counters=raw / (nbr_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              frac_upper_gfx950_fetch_x2=upper / (nbr_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              profile_us_per_step=sum(v["us_per_step"] for v in dom.values()))
-                roof["limiter"] = {"kind": "latency / issue (dependent L2 + LDS accesses at 3-16 wavefronts per CU), not HBM",
-                                   "per_kernel": {k: {c: v[c] for c in ("avg_us", "launches_per_step", "vgpr", "lds", "SQ_WAVES", "SQ_WAVE_CYCLES",
-                                                                        "SQ_BUSY_CYCLES", "wait_any_frac", "issue_stall_frac", "SQ_INSTS_VALU",
-                                                                        "SQ_INSTS_SALU", "hbm_gbs_raw") if c in v} for k, v in dom.items()}}
-        else:
-            roof["traffic_source"] = f"missing: {os.path.relpath(pmc_path, ROOT)} (tools/collect_roofline.sh {cfg})"
-        roof["neighbour_kernels"] = nk
+        roof = None
+        if args.full:
+            P = st["packets"]
+            b_eval = n + 12 * P  # every input byte once + one 12-byte packet record per packet of the parse
+            nbr_ms = st["gpu_ms_neighbours"] / launches  # all neighbour kernels of a step, HIP events on the library's streams
+            evals_per_step = st["evaluations"] / max(1, st["steps"])
+            pmc, pmc_path = load_pmc(cfg)
+            sim_ms = st["gpu_ms_sim"] / st["sim_launches"] if st.get("sim_launches") else None  # HIP events on the streams k_sim runs on
+            roof = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
+                    "kernel": "k_sim (chain re-simulation), the dominant kernel: one launch per slice of the step's neighbours + one over the second "
+                              "pass's list; per touched probability context a lane follows the base chain from the first change until the "
+                              "perturbed probability re-joins the base trajectory",
+                    "avg_launch_ms": sim_ms, "launches_timed": st.get("sim_launches", 0),
+                    "definition": "achieved = the kernel's ALGORITHMIC bytes per launch (chain positions and events and change-list entries its loads ask "
+                                  "for, counted by the kernel itself in a few extra steps after the timed region) / its average launch duration measured "
+                                  "live with HIP events on its streams; traffic = HBM bytes per launch from rocprofv3 FETCH_SIZE + WRITE_SIZE (raw) of "
+                                  "the stored profile, null when that profile was taken of other kernel sources than the ones running",
+                    "algorithmic_equiv_gbs": evals_per_step * b_eval / (nbr_ms * 1e-3) / 1e9 if nbr_ms > 0 else None,
+                    "algorithmic_note": "SURVEY 8d's figure -- evaluations/step x (N + 12 P) / time of all neighbour kernels: what a streaming evaluator "
+                                        "would move; the incremental kernels price only the changed window, so this is not a fraction of anything",
+                    "b_eval_bytes": b_eval, "packets_on_walk": P, "packets_walked_per_eval": walked / max(1.0, evals)}
+            if counted and sim_ms:
+                per_launch = counted["bytes"] / counted["launches"]
+                roof["algorithmic_bytes_per_launch"] = per_launch
+                # per evaluation: over the steps that ran the split form (k_sim launches per such step: one per slice of the step's
+                # neighbours -- two above 1 MiB -- and one over the second pass's list; steps of a trial of the one-kernel form launch none)
+                per_step = 3 if n > (1 << 20) else 2
+                roof["algorithmic_bytes_per_evaluation"] = per_launch * per_step / max(1.0, counted["evaluations"] / max(1, counted["steps"]))
+                roof["counted_over"] = (f"{counted['launches'] // per_step} of {counted['steps']} steps after the timed region "
+                                        f"({counted['launches']} launches, kernel's own byte counters on)")
+                roof["achieved"] = per_launch / (sim_ms * 1e-3) / 1e9
+                roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
+            nk = {"avg_ms_per_step_live": nbr_ms, "launches_timed": launches}  # all neighbour kernels of a step together
+            if pmc:
+                ks = pmc["kernels"]
+                fresh = pmc.get("source_hash") == source_hash()
+                dom = {k: v for k, v in ks.items() if any(k.startswith(d) for d in DOMINANT)}
+                sim = [v for k, v in ks.items() if k.startswith(SIM)]
+                roof["traffic_source"] = os.path.relpath(pmc_path, ROOT)
+                roof["traffic_profile_matches_build"] = fresh
+                if fresh and sim:
+                    roof["traffic"] = sum(v.get("hbm_bytes_raw_per_launch", 0.0) * v["launches_per_step"] for v in sim) / sum(v["launches_per_step"] for v in sim)
+                    roof["traffic_upper_gfx950_fetch_x2"] = sum(v.get("hbm_bytes_upper_per_launch", 0.0) * v["launches_per_step"] for v in sim) / sum(v["launches_per_step"] for v in sim)
+                    roof["profile_avg_launch_ms"] = sum(v["us_per_step"] for v in sim) / sum(v["launches_per_step"] for v in sim) / 1e3
+                    if sim_ms:
+                        roof["hbm_frac_raw_counters"] = roof["traffic"] / (sim_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                elif not fresh:
+                    roof["traffic_note"] = "the stored profile was taken of other kernel sources (source_hash differs): no counter figure is claimed for this build"
+                if fresh:
+                    raw = sum(v.get("hbm_bytes_raw_per_launch", 0.0) * v["launches_per_step"] for v in dom.values())
+                    upper = sum(v.get("hbm_bytes_upper_per_launch", 0.0) * v["launches_per_step"] for v in dom.values())
+                    if raw and nbr_ms > 0:
+                        nk.update(hbm_bytes_raw_per_step=raw, hbm_bytes_upper_per_step=upper, frac_raw_counters=raw / (nbr_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                  frac_upper_gfx950_fetch_x2=upper / (nbr_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                  profile_us_per_step=sum(v["us_per_step"] for v in dom.values()))
+                    roof["limiter"] = {"kind": "latency / issue (dependent L2 + LDS accesses at 3-16 wavefronts per CU), not HBM",
+                                       "per_kernel": {k: {c: v[c] for c in ("avg_us", "launches_per_step", "vgpr", "lds", "SQ_WAVES", "SQ_WAVE_CYCLES",
+                                                                            "SQ_BUSY_CYCLES", "wait_any_frac", "issue_stall_frac", "SQ_INSTS_VALU",
+                                                                            "SQ_INSTS_SALU", "hbm_gbs_raw") if c in v} for k, v in dom.items()}}
+            else:
+                roof["traffic_source"] = f"missing: {os.path.relpath(pmc_path, ROOT)} (tools/collect_roofline.sh {cfg})"
+            roof["neighbour_kernels"] = nk
         lcpb = f"{props.get('lc', 0)}/{props.get('lp', 0)}/{props.get('pb', 0)}"
         out = {
             "metric": "SA neighbour-cost evals/s",
@@ -539,7 +591,6 @@ def main():
                                       f"; slab state: after {prepare} search steps from the all-literal slab (accept mode auto); timed steps in accept mode {accept}"),
                        "chains": n_gpus, "parallelism": f"{n_gpus} independent chain(s), " + ("ALL ON ONE GPU (rehearsal of the N > 1 path, not a scaling figure)" if shared_gpu else "1 per GPU")
                                    + (", best-slab exchange timed separately" if n_gpus > 1 else "")},
-            "roofline": roof,
             "final": {"current_cost": st["current_cost"], "best_cost": st["best_cost"],
                       "est_bytes_best": 18 + st["best_cost"] / 16384, "accepted": st["accepted"],
                       "bulk_steps_timed": st["bulk_steps"], "improving_neighbours": st["improving_neighbours"],
@@ -549,6 +600,8 @@ def main():
                       "fallback_neighbours": st["fallback_neighbours"],
                       "second_pass_neighbours": st["second_pass_neighbours"]},
         }
+        if roof:
+            out["roofline"] = roof
         if default_mode:
             out["default_mode"] = default_mode
         if exchange:
@@ -567,7 +620,7 @@ def main():
                                 "note": "set-up search (accept mode auto, from the all-literal slab) + timed steps; `value` is the steady state "
                                         "of a long run (single steps on the evolved slab)"}
         gates = {}
-        if n <= (16 << 20):
+        if args.full and n <= (16 << 20):
             # correctness gates reported with the number, after the timed region: the best slab's cost
             # re-derived by the device's independent full walk, and its stream through liblzma
             import lzma
@@ -581,7 +634,7 @@ def main():
             gates.update(best_cost_equals_full_walk=sa.cost_slab(best, want_cum=False)["total"] == best_cost,
                          lzma_roundtrip=ok, stream_bytes=len(stream))
         sa.close()
-        if n_gpus == 1 and not args.no_cpu:
+        if args.full and n_gpus == 1 and not args.no_cpu:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import build_oracle
             build_oracle.build_oracle()
@@ -590,7 +643,7 @@ def main():
             out["vs_cpu_reference_1_thread"] = out["value"] / out["cpu_baseline"]["value"]
         else:
             out["cpu_baseline"] = None
-        if n_gpus == 1 and not args.no_secondary:
+        if args.full and n_gpus == 1 and not args.no_secondary:
             # the rate on the young slab (what round 1 reported) and the size comparison with the reference path
             y = binding.SA(data, neighbours_per_step=K, seed=1673551, iters_per_epoch=n, timing=True, accept="single", **props)
             y.run(5)

@@ -2,6 +2,7 @@
 fixtures, and the C-ABI library's load/export contract.  No compute entry point of
 libmegalania_hip.so is called here."""
 import ctypes as C
+import json
 import lzma
 import os
 import re
@@ -57,16 +58,13 @@ def test_rng_matches_oracle():
 
 def test_bit_cost_table_is_the_reference_table():
     """csrc/mgl_cost_table.inc (exact integer arithmetic) == the oracle's libm table == the
-    reference's perplexity_table.h (checked directly where /root/reference exists)."""
+    reference's perplexity_table.h (its hash, recorded in tests/golden/oracle_vs_ref.json)."""
     txt = open(os.path.join(ROOT, "megalania_amd", "csrc", "mgl_cost_table.inc")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     mine = np.array([int(x) for x in re.findall(r"\d+", txt)], dtype=np.uint16)
     assert len(mine) == 2048 and (mine == Oracle.cost_table()).all()
-    ref = "/root/reference/src/perplexity_table.h"
-    if os.path.exists(ref):
-        body = open(ref).read().split("{", 1)[1]
-        theirs = np.array([int(x) for x in re.findall(r"\d+", body)], dtype=np.uint16)
-        assert (mine == theirs).all()
+    with open(os.path.join(ROOT, "tests", "golden", "oracle_vs_ref.json")) as f:
+        assert sha(mine) == json.load(f)["perplexity_table_sha256"]
 
 
 def test_host_emission_matches_reference_streams(golden, golden_input):

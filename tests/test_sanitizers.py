@@ -22,7 +22,7 @@ def test_golden_walks_under_asan_and_ubsan():
         pytest.skip("gcc's sanitizer runtimes are not installed")
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "sanitizers"], stdout=sys.stderr)
     env = dict(os.environ,
-               LD_PRELOAD=asan + ":" + ubsan,
+               LD_PRELOAD=":".join(p for p in (asan, ubsan, os.environ.get("LD_PRELOAD")) if p),  # the runtimes first
                ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=1",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                MGL_ORACLE_SO=os.path.join(ROOT, "oracle", "_build", "liboracle_asan.so"),
