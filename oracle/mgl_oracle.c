@@ -76,12 +76,15 @@ struct orc_ctx {
 	uint32_t* bucket_pos; /* n-1 positions, ascending inside a bucket */
 	uint64_t temperature; /* 0 = the reference's accept rule; else the opt-in Metropolis rule of orc_sa_batched */
 	uint32_t max_bucket_scan; /* 0 = every hit (the reference); else only the nearest M hits of the window */
+	uint32_t top_k;           /* candidates a neighbour's pick draws from (main.c:49: 20); mirrors mgl_sa_config.top_k */
 	uint32_t strata;          /* batched mode: 0 = the target comes from position draws; K = neighbour j takes a packet of the j-th
 	                           * of K equal slices of the walk's packets (the device's default, mgl_device.h:stratified_target) */
 };
 
 void orc_set_temperature(orc_ctx* c, uint64_t temperature) { c->temperature = temperature; }
 void orc_set_max_bucket_scan(orc_ctx* c, uint32_t m) { c->max_bucket_scan = m; }
+#define ORC_MAX_K 64
+void orc_set_top_k(orc_ctx* c, uint32_t k) { c->top_k = k == 0 ? 20 : k > ORC_MAX_K ? ORC_MAX_K : k; }
 void orc_set_strata(orc_ctx* c, uint32_t K) { c->strata = K; }
 
 size_t orc_num_probs(const orc_ctx* c) { return c->L.total; }
@@ -334,6 +337,7 @@ orc_ctx* orc_new(const uint8_t* data, size_t n, int lc, int lp, int pb, uint32_t
 	if (!c) return NULL;
 	c->data = data; c->n = n; c->lc = lc; c->lp = lp; c->pb = pb;
 	c->dict_limit = dict_limit ? dict_limit : 0xFFFFFFFFu;
+	c->top_k = 20;
 	c->L.lit = 0;
 	c->L.len = 0x300u << (lc + lp);
 	c->L.rep_len = c->L.len + LEN_SIZE;
@@ -439,7 +443,6 @@ size_t orc_substrings(orc_ctx* c, size_t pos, size_t max_len, uint32_t* offs, ui
 }
 
 /* ---------------------------------------------------------------- top-K */
-#define ORC_MAX_K 64
 typedef struct { orc_packet pk; uint32_t cost; uint64_t seq; } topk_entry;
 typedef struct {
 	const orc_ctx* c;
@@ -655,7 +658,7 @@ static size_t rand_max_of(gen_env* g, size_t count, size_t num)
 static int pick_from_top_k(gen_env* g, const orc_state* st, orc_packet* slab, int best)
 {
 	topk t;
-	topk_find(&t, g->c, st, slab, g->topk_mode, 20, g->scratch);
+	topk_find(&t, g->c, st, slab, g->topk_mode, g->c->top_k, g->scratch);
 	size_t count = t.count;
 	if (count == 0) return 0;
 	size_t choice = rand_max_of(g, count, 8);

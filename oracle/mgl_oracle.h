@@ -104,6 +104,8 @@ int orc_sa_batched(orc_ctx* c, orc_packet* slab_io, orc_packet* best_io, uint64_
 void orc_set_strata(orc_ctx* c, uint32_t K);
 /* cap on the match-index hits a top-K query enumerates (nearest first); mirrors mgl_sa_config.max_bucket_scan */
 void orc_set_max_bucket_scan(orc_ctx* c, uint32_t m);
+/* size of the top-K list a neighbour's pick draws from (default 20, main.c:49; 0 = 20; at most 64); mirrors mgl_sa_config.top_k */
+void orc_set_top_k(orc_ctx* c, uint32_t k);
 
 /* Opt-in Metropolis rule for orc_sa_batched (0 = the reference's rule); mirrors mgl_sa_set_temperature. */
 void orc_set_temperature(orc_ctx* c, uint64_t temperature);

@@ -112,6 +112,7 @@ class Oracle:
             L.orc_neighbour_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
             L.orc_set_max_bucket_scan.argtypes = [C.c_void_p, C.c_uint32]
+            L.orc_set_top_k.argtypes = [C.c_void_p, C.c_uint32]
             L.orc_set_strata.argtypes = [C.c_void_p, C.c_uint32]
             L.orc_set_temperature.argtypes = [C.c_void_p, C.c_uint64]
             L.orc_emit.restype = C.c_size_t
@@ -119,8 +120,9 @@ class Oracle:
             cls._lib = L
         return cls._lib
 
-    def __init__(self, data: bytes, lc=0, lp=0, pb=0, dict_limit=0, max_bucket_scan=0, position_targets=False):
-        """position_targets: the batched mode draws targets as positions (mgl_sa_config.flags & MGL_F_POSITION_TARGETS) instead of
+    def __init__(self, data: bytes, lc=0, lp=0, pb=0, dict_limit=0, max_bucket_scan=0, position_targets=False, top_k=20):
+        """top_k: size of the list a neighbour's pick draws from (mgl_sa_config.top_k; top_k() takes its own k).
+        position_targets: the batched mode draws targets as positions (mgl_sa_config.flags & MGL_F_POSITION_TARGETS) instead of
         the device's default, stratified by packet ordinal over the K neighbours of a step (then neighbour() needs K)."""
         self.stratified = not position_targets
         self.L = self.lib()
@@ -130,6 +132,7 @@ class Oracle:
         self.nprobs = self.L.orc_num_probs(self.h)
         if max_bucket_scan:
             self.L.orc_set_max_bucket_scan(self.h, max_bucket_scan)
+        self.L.orc_set_top_k(self.h, top_k)
 
     def __del__(self):
         if getattr(self, "h", None):

@@ -60,7 +60,7 @@ def as_list(slab):
     return [(int(t), int(d), int(l)) for t, d, l in zip(slab["type"], slab["dist"], slab["len"])]
 
 
-@pytest.mark.parametrize("name,data,cand", [
+GREEDY_INPUTS = pytest.mark.parametrize("name,data,cand", [
     ("lorem", corpus.lorem(4096), 8),
     ("enwik", corpus.enwik_like(20000, 0x31), 4),
     ("enwik_wide", corpus.enwik_like(6000, 0x32), 256),
@@ -69,17 +69,33 @@ def as_list(slab):
     ("n2", b"ab", 16),
     ("n1", b"x", 16),
 ])
-def test_greedy_slab_matches_the_rule(name, data, cand):
-    sa = binding.SA(data, accept="single", neighbours_per_step=16)
+
+
+def _check_greedy(name, data, cand, dict_limit=0x400000):
+    sa = binding.SA(data, accept="single", neighbours_per_step=16, dict_limit=dict_limit)
     sa.seed_greedy(cand)
     cur, cost = sa.current()
-    assert as_list(cur) == greedy_rule(data, cand), name
+    assert as_list(cur) == greedy_rule(data, cand, dict_limit), name
     # the slab is a valid parse with exactly the cost the oracle gives it, and it decodes
-    o = Oracle(data, dict_limit=0x400000)
+    o = Oracle(data, dict_limit=dict_limit)
     slab = np.ascontiguousarray(cur).astype(literal_slab(1).dtype)
     assert cost == o.cost_slab(slab)["total"]
     assert lzma.decompress(binding.emit_stream(data, cur), format=lzma.FORMAT_ALONE) == data
     sa.close()
+    return cur
+
+
+@GREEDY_INPUTS
+def test_greedy_slab_matches_the_rule(name, data, cand):
+    _check_greedy(name, data, cand)
+
+
+@pytest.mark.parametrize("dict_limit", [64, 4096])
+@GREEDY_INPUTS
+def test_greedy_slab_matches_the_rule_under_a_window(name, data, cand, dict_limit):
+    """the same under a dictionary window that cuts through the input (mgl_kernels.hip's greedy window check)"""
+    cur = _check_greedy(name, data, cand, dict_limit)
+    assert all(t != MATCH or d < dict_limit for t, d, _ in as_list(cur))
 
 
 def test_greedy_tail_entries_with_short_lookahead():

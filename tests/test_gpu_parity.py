@@ -452,7 +452,7 @@ def test_match_index_built_on_device(cfg, size):
     sa.close()
 
 
-@pytest.mark.parametrize("lc,lp,pb", [(3, 0, 2), (0, 2, 0), (1, 1, 1), (4, 0, 0)])
+@pytest.mark.parametrize("lc,lp,pb", [(3, 0, 2), (0, 2, 0), (1, 1, 1), (4, 0, 0), (0, 4, 4), (2, 2, 3), (0, 0, 3), (1, 3, 4)])
 def test_literal_context_and_position_bits(lc, lp, pb):
     """lc / lp / pb beyond the reference's hard-coded 0/0/0 (main.c:45; xz's default is
     3/0/2).  No reference implementation exists for these (parity unpinned): the device must equal
