@@ -40,12 +40,18 @@ HIP_SYMBOLS = [
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
     "mgl_range_encoder_new", "mgl_range_encoder_free", "mgl_perplexity_encoder_new", "mgl_file_output_new",
-    "mgl_memory_output_new", "mgl_emit_stream",
+    "mgl_memory_output_new", "mgl_emit_stream", "mgl_stream_info_read", "mgl_stream_import",
 ]
+IMPORT_CLIP_WINDOW = 1
+CONTAINER_LZMA, CONTAINER_XZ = 1, 2
 
 
 class MglError(RuntimeError):
-    pass
+    """rc: the MGL_E* code where one is known; error / error_pos: a stream import's first problem."""
+
+    def __init__(self, msg, rc=None, error=None, error_pos=None):
+        super().__init__(msg)
+        self.rc, self.error, self.error_pos = rc, error, error_pos
 
 
 class Properties(C.Structure):
@@ -70,6 +76,16 @@ class Stats(C.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class StreamInfo(C.Structure):
+    _fields_ = [("container", C.c_int), ("props", Properties), ("dict_size", C.c_uint32), ("declared_size", C.c_uint64)]
+
+
+class ImportStats(C.Structure):
+    _fields_ = [("packets", C.c_uint64), ("literals", C.c_uint64), ("matches", C.c_uint64), ("short_reps", C.c_uint64),
+                ("long_reps", C.c_uint64 * 4), ("reexpressed", C.c_uint64), ("clipped", C.c_uint64),
+                ("props_changes", C.c_uint64), ("error_pos", C.c_uint64), ("error", C.c_char_p)]
 
 
 class MemorySink(C.Structure):
@@ -142,6 +158,9 @@ def host_lib():
         L.mgl_emit_stream.restype = C.c_bool
         L.mgl_emit_stream.argtypes = [C.c_void_p, C.c_size_t, Properties, C.c_void_p, C.POINTER(OutputInterface)]
         L.mgl_memory_output_new.argtypes = [C.POINTER(OutputInterface), C.POINTER(MemorySink)]
+        L.mgl_stream_info_read.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(StreamInfo)]
+        L.mgl_stream_import.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.POINTER(ImportStats)]
         _host = L
     return _host
 
@@ -171,6 +190,38 @@ def emit_stream(data: bytes, slab: np.ndarray, lc=0, lp=0, pb=0) -> bytes:
         raise MglError("mgl_emit_stream failed (invalid slab?)")
     assert sink.len <= cap
     return out[: sink.len].tobytes()
+
+
+def stream_info(stream: bytes) -> dict:
+    """Container, lc/lp/pb, dictionary and declared size of an LZMA-alone or .xz stream
+    (declared_size None = unknown, the stream ends with an end marker)."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+    info = StreamInfo()
+    rc = L.mgl_stream_info_read(_ptr(buf), len(buf), C.byref(info))
+    if rc != 0:
+        raise MglError(f"rc={rc}: not an LZMA-alone or .xz stream", rc=rc)
+    return dict(container=info.container, lc=info.props.lc, lp=info.props.lp, pb=info.props.pb,
+                dict_size=info.dict_size, declared_size=None if info.declared_size == (1 << 64) - 1 else info.declared_size)
+
+
+def stream_import(stream: bytes, data: bytes, window: int = 0x400000, clip: bool = False):
+    """The parse inside an LZMA-alone / .xz stream of `data` as a position-indexed slab (host C, mgl_stream_import),
+    re-expressed for one LZMA1 stream.  Returns (slab, stats dict); raises MglError (rc, error, error_pos)."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+    dat = np.frombuffer(bytes(data), dtype=np.uint8)
+    slab = np.zeros(len(dat), dtype=PACKET)
+    st = ImportStats()
+    rc = L.mgl_stream_import(_ptr(buf), len(buf), _ptr(dat), len(dat), window, IMPORT_CLIP_WINDOW if clip else 0,
+                             _ptr(slab), C.byref(st))
+    err = st.error.decode() if st.error else None
+    if rc != 0:
+        raise MglError(f"rc={rc}: stream import failed at input position {st.error_pos}: {err}", rc=rc, error=err,
+                       error_pos=st.error_pos)
+    stats = {k: getattr(st, k) for k, _ in ImportStats._fields_ if k not in ("error", "error_pos", "long_reps")}
+    stats["long_reps"] = list(st.long_reps)
+    return slab, stats
 
 
 class SA:
@@ -230,6 +281,15 @@ class SA:
     def seed_greedy(self, candidates: int = 256):
         """Current slab := greedy LZ parse made on the device (opt-in starting point)."""
         self._chk(self.L.mgl_sa_seed_greedy(self.h, candidates))
+
+    def seed_stream(self, stream: bytes, clip: bool = False) -> int:
+        """Best slab := the parse inside an existing .lzma / .xz stream of this input (stream_import, window =
+        the handle's dict_limit), costed on the device; returns that cost.  begin_epoch(.., from_best=True) then
+        searches from it."""
+        slab, _ = stream_import(stream, self.data.tobytes(), window=self.cfg.dict_limit or 0x400000, clip=clip)
+        cost = self.cost_slab(slab, want_cum=False)["total"]
+        self.set_best(slab, cost)
+        return cost
 
     def set_temperature(self, temperature: int):
         """Opt-in Metropolis accept rule, temperature in cost units (16384 per byte); 0 = reference rule."""

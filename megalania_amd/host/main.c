@@ -28,12 +28,17 @@ static void usage(const char* argv0)
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
 	        "          [--lc N --lp N --pb N] [--device D] [--max-scan M]\n"
 	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--temperature B]\n"
+	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
 	        "  --save-slab  after every epoch, write the best packet slab (resumable checkpoint)\n"
 	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb)\n"
 	        "  --greedy-seed C  epochs that the reference starts from the all-literal slab start from a greedy\n"
 	        "               parse instead (longest of the C nearest candidates per position; e.g. 256)\n"
+	        "  --seed-stream F  start from the parse inside an existing .lzma / .xz stream of this input (e.g. xz -9e's):\n"
+	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's\n"
+	        "  --clip-window    with --seed-stream: copies from beyond the dictionary window become literals instead\n"
+	        "               of an error\n"
 	        "  --temperature B  Metropolis accept rule instead of the reference's: B = e-folding slack in output\n"
 	        "               bytes at the start of an epoch, cooled linearly to 0 (e.g. 2; 0 = reference rule)\n"
 	        "  --chains N --rank R --comm-file PATH  one of N independent chains, one process per GPU (device = R unless\n"
@@ -58,7 +63,8 @@ int main(int argc, char** argv)
 	unsigned epochs = 200, phases = 3;  /* main.c:66,69 */
 	unsigned long long steps_override = 0;
 	const char* filename = NULL;
-	const char *out_path = NULL, *save_path = NULL, *load_path = NULL;
+	const char *out_path = NULL, *save_path = NULL, *load_path = NULL, *seed_stream_path = NULL;
+	int clip_window = 0, props_given = 0;
 	uint32_t greedy = 0;
 	double temperature_bytes = 0;
 	int accept_mode = MGL_ACCEPT_AUTO;
@@ -70,15 +76,16 @@ int main(int argc, char** argv)
 		const char* a = argv[i];
 		const char* v = i + 1 < argc ? argv[i + 1] : NULL;
 		if (a[0] != '-') { filename = a; continue; }
+		if (!strcmp(a, "--clip-window")) { clip_window = 1; continue; }
 		if (!v) { usage(argv[0]); return -1; }
 		if (!strcmp(a, "--neighbours")) cfg.neighbours_per_step = (uint32_t)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--epochs")) epochs = (unsigned)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--phases")) phases = (unsigned)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--steps")) steps_override = strtoull(v, NULL, 0);
 		else if (!strcmp(a, "--seed")) cfg.seed = strtoull(v, NULL, 0);
-		else if (!strcmp(a, "--lc")) props.lc = (uint8_t)strtoul(v, NULL, 0);
-		else if (!strcmp(a, "--lp")) props.lp = (uint8_t)strtoul(v, NULL, 0);
-		else if (!strcmp(a, "--pb")) props.pb = (uint8_t)strtoul(v, NULL, 0);
+		else if (!strcmp(a, "--lc")) { props.lc = (uint8_t)strtoul(v, NULL, 0); props_given = 1; }
+		else if (!strcmp(a, "--lp")) { props.lp = (uint8_t)strtoul(v, NULL, 0); props_given = 1; }
+		else if (!strcmp(a, "--pb")) { props.pb = (uint8_t)strtoul(v, NULL, 0); props_given = 1; }
 		else if (!strcmp(a, "--device")) { cfg.device = (int32_t)strtol(v, NULL, 0); device_given = 1; }
 		else if (!strcmp(a, "--chains")) chains = (int)strtol(v, NULL, 0);
 		else if (!strcmp(a, "--rank")) rank = (int)strtol(v, NULL, 0);
@@ -93,6 +100,7 @@ int main(int argc, char** argv)
 		else if (!strcmp(a, "--save-slab")) save_path = v;
 		else if (!strcmp(a, "--load-slab")) load_path = v;
 		else if (!strcmp(a, "--greedy-seed")) greedy = (uint32_t)strtoul(v, NULL, 0);
+		else if (!strcmp(a, "--seed-stream")) seed_stream_path = v;
 		else if (!strcmp(a, "--temperature")) temperature_bytes = strtod(v, NULL);
 		else if (!strcmp(a, "--accept")) {
 			if (!strcmp(v, "auto")) accept_mode = MGL_ACCEPT_AUTO;
@@ -104,6 +112,12 @@ int main(int argc, char** argv)
 		i++;
 	}
 	if (!filename) { usage(argv[0]); return -1; }
+	if (seed_stream_path && (load_path || greedy)) {
+		fprintf(stderr, "Error: --seed-stream cannot be combined with --load-slab or --greedy-seed\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (clip_window && !seed_stream_path) { usage(argv[0]); return -1; }
 	if (chains < 1 || rank < 0 || rank >= chains || (chains > 1 && !comm_path)) { usage(argv[0]); return -1; }
 	if (chains > 1) {
 		if (!device_given) cfg.device = rank;
@@ -123,6 +137,27 @@ int main(int argc, char** argv)
 	if (mgl_device_count() < 1) {
 		fprintf(stderr, "Error: no HIP device found; this program has no CPU search path\n");
 		return -1;
+	}
+	/* --seed-stream: the stream's properties unless --lc/--lp/--pb say otherwise (a parse is valid under any) */
+	uint8_t* seed_stream = NULL;
+	size_t seed_stream_len = 0;
+	if (seed_stream_path) {
+		FILE* f = fopen(seed_stream_path, "rb");
+		long sz = -1;
+		if (f && fseek(f, 0, SEEK_END) == 0) sz = ftell(f);
+		if (sz > 0 && fseek(f, 0, SEEK_SET) == 0 && (seed_stream = (uint8_t*)malloc((size_t)sz)) != NULL &&
+		    fread(seed_stream, 1, (size_t)sz, f) == (size_t)sz)
+			seed_stream_len = (size_t)sz;
+		if (f) fclose(f);
+		mgl_stream_info info;
+		if (!seed_stream_len || mgl_stream_info_read(seed_stream, seed_stream_len, &info) != MGL_OK) {
+			fprintf(stderr, "Error: %s is not an LZMA-alone or .xz stream\n", seed_stream_path);
+			return -1;
+		}
+		if (!props_given) props = info.props;
+		else if (props.lc != info.props.lc || props.lp != info.props.lp || props.pb != info.props.pb)
+			fprintf(stderr, "note: %s was coded with lc/lp/pb %u/%u/%u; searching with the given %u/%u/%u\n", seed_stream_path,
+			        info.props.lc, info.props.lp, info.props.pb, props.lc, props.lp, props.pb);
 	}
 	cfg.iters_per_epoch = file_size;
 	mgl_sa* sa = mgl_sa_create(file_data, file_size, props, &cfg);
@@ -185,6 +220,28 @@ int main(int argc, char** argv)
 		fclose(f);
 		/* the library re-costs the slab and refuses it unless the perplexity matches */
 		if (mgl_sa_set_best(sa, packets_best, hdr[1]) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+		resumed = true;
+	}
+	if (seed_stream) {
+		/* the stream's parse, re-expressed for one LZMA1 stream, becomes the best slab (re-costed and checked by
+		 * the library like a --load-slab one); every epoch then starts from the best slab */
+		mgl_import_stats ist;
+		const int irc = mgl_stream_import(seed_stream, seed_stream_len, file_data, file_size, cfg.dict_limit,
+		                                  clip_window ? MGL_IMPORT_CLIP_WINDOW : 0, packets_best, &ist);
+		if (irc != MGL_OK) {
+			fprintf(stderr, "Error: %s: %s at input position %llu%s\n", seed_stream_path, ist.error ? ist.error : "import failed",
+			        (unsigned long long)ist.error_pos, irc == MGL_ERANGE ? " (--clip-window turns such copies into literals)" : "");
+			return -1;
+		}
+		uint64_t cost = 0;
+		size_t npk = 0;
+		if (mgl_cost_slab(sa, packets_best, &cost, NULL, &npk) != MGL_OK || mgl_sa_set_best(sa, packets_best, cost) != MGL_OK) {
+			fprintf(stderr, "Error: %s\n", mgl_last_error());
+			return -1;
+		}
+		fprintf(stderr, "seed stream: %zu packets, estimate %f bytes, stream %zu bytes, %llu re-expressed, %llu clipped\n", npk,
+		        18 + cost / 16384.f, seed_stream_len, (unsigned long long)ist.reexpressed, (unsigned long long)ist.clipped);
+		free(seed_stream);
 		resumed = true;
 	}
 

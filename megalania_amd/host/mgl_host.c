@@ -277,3 +277,579 @@ bool mgl_emit_stream(const uint8_t* data, size_t n, mgl_properties props, const 
 	mgl_lzma_state_free(&st);
 	return true;
 }
+
+/* ------------------------------------------------------------------ stream import
+ *
+ * Reads the parse out of an existing LZMA-alone or .xz stream of `data`.  Nothing is
+ * materialised: every decoded byte is compared with the input, which therefore also serves as
+ * the dictionary.  The contexts are the encoder's (mgl_model.h), so the decoder below is the
+ * exact mirror of mgl_plan_packet / mgl_plan_event.  Every read is bounded; a short or corrupt
+ * stream is an error, never an out-of-bounds access. */
+
+typedef struct {
+	/* what is being checked and written */
+	const uint8_t* data;
+	size_t n;
+	uint32_t window;
+	uint32_t flags;
+	mgl_packet* slab;
+	mgl_import_stats* st;
+	/* the stream's model: layout, probabilities, walk state (ctx_state, reps) */
+	mgl_properties props;
+	bool have_props;
+	mgl_layout L;
+	Prob* probs;
+	uint32_t probs_cap;
+	mgl_wstate sw;
+	size_t dict_start; /* input position of the last dictionary reset */
+	/* the output walk, whose rep stack the packets are re-expressed against */
+	mgl_wstate ow;
+	size_t pos;
+	/* range decoder over [in, in_end) */
+	const uint8_t* in;
+	const uint8_t* in_end;
+	uint32_t range, code;
+	bool overrun;
+	/* first problem */
+	const char* error;
+	size_t error_pos;
+	int rc;
+} mgl_imp;
+
+static int imp_fail(mgl_imp* im, int rc, const char* why)
+{
+	if (!im->error) {
+		im->error = why;
+		im->error_pos = im->pos;
+		im->rc = rc;
+	}
+	return rc;
+}
+
+static uint8_t rd_byte(mgl_imp* im)
+{
+	if (im->in < im->in_end) return *im->in++;
+	im->overrun = true;
+	return 0;
+}
+
+/* normalisation right after every bit, like the encoder's: a well-formed stream is then
+ * consumed exactly (5 initial bytes + one per shift) */
+static void rd_normalize(mgl_imp* im)
+{
+	while (im->range < MGL_RC_TOP) {
+		im->range <<= 8;
+		im->code = (im->code << 8) | rd_byte(im);
+	}
+}
+
+static bool rd_init(mgl_imp* im, const uint8_t* p, const uint8_t* end)
+{
+	im->in = p;
+	im->in_end = end;
+	im->overrun = false;
+	im->range = 0xFFFFFFFFu;
+	im->code = 0;
+	if (rd_byte(im) != 0) return false; /* the encoder's first byte is its initial cache, always 0 */
+	for (int i = 0; i < 4; i++) im->code = (im->code << 8) | rd_byte(im);
+	return !im->overrun && im->code != 0xFFFFFFFFu;
+}
+
+static uint32_t rd_bit(mgl_imp* im, uint32_t ctx)
+{
+	Prob* p = &im->probs[ctx];
+	const uint32_t bound = (im->range >> MGL_NUM_BIT_MODEL_TOTAL_BITS) * *p;
+	uint32_t bit;
+	if (im->code < bound) {
+		im->range = bound;
+		bit = 0;
+	} else {
+		im->code -= bound;
+		im->range -= bound;
+		bit = 1;
+	}
+	*p = (Prob)mgl_prob_update(*p, bit);
+	rd_normalize(im);
+	return bit;
+}
+
+static uint32_t rd_direct(mgl_imp* im, uint32_t nbits)
+{
+	uint32_t v = 0;
+	while (nbits--) {
+		im->range >>= 1;
+		uint32_t bit = im->code >= im->range;
+		if (bit) im->code -= im->range;
+		v = (v << 1) | bit;
+		rd_normalize(im);
+	}
+	return v;
+}
+
+/* bit tree, most significant bit first: contexts 1, 1b, 1bb, ... */
+static uint32_t rd_tree(mgl_imp* im, uint32_t base, uint32_t nbits)
+{
+	uint32_t m = 1;
+	for (uint32_t i = 0; i < nbits; i++) m = (m << 1) | rd_bit(im, base + m);
+	return m - (1u << nbits);
+}
+
+/* reverse bit tree (probability_model.c:34-44), least significant bit first */
+static uint32_t rd_tree_rev(mgl_imp* im, uint32_t base, uint32_t nbits)
+{
+	uint32_t m = 1, v = 0;
+	for (uint32_t e = 0; e < nbits; e++) {
+		const uint32_t bit = rd_bit(im, base + m);
+		m = (m << 1) | bit;
+		v |= bit << e;
+	}
+	return v;
+}
+
+/* mgl_plan_length in reverse */
+static uint32_t rd_length(mgl_imp* im, uint32_t base, uint32_t pos_state)
+{
+	if (!rd_bit(im, base)) return MGL_MIN_MATCH + rd_tree(im, base + MGL_LEN_LOW + pos_state * 8, 3);
+	if (!rd_bit(im, base + 1)) return MGL_MIN_MATCH + 8 + rd_tree(im, base + MGL_LEN_MID + pos_state * 8, 3);
+	return MGL_MIN_MATCH + 16 + rd_tree(im, base + MGL_LEN_HIGH, 8);
+}
+
+static bool imp_set_props(mgl_imp* im, uint8_t b)
+{
+	if (b >= 9 * 5 * 5) return false;
+	mgl_properties p = { (uint8_t)(b % 9), (uint8_t)((b / 9) % 5), (uint8_t)(b / 45) };
+	im->L = mgl_make_layout(p.lc, p.lp, p.pb);
+	if (im->L.total > im->probs_cap) {
+		Prob* np = (Prob*)realloc(im->probs, sizeof(Prob) * im->L.total);
+		if (!np) return false;
+		im->probs = np;
+		im->probs_cap = im->L.total;
+	}
+	if (im->have_props && (p.lc != im->props.lc || p.lp != im->props.lp || p.pb != im->props.pb) && im->st) im->st->props_changes++;
+	if (!im->have_props) im->props = p;
+	im->have_props = true;
+	return true;
+}
+
+/* LZMA state reset: fresh probabilities, ctx_state 0, reps 0 (the output walk keeps its own) */
+static void imp_reset_state(mgl_imp* im)
+{
+	for (uint32_t i = 0; i < im->L.total; i++) im->probs[i] = MGL_PROB_INIT_VAL;
+	const uint32_t pos = im->sw.pos;
+	memset(&im->sw, 0, sizeof im->sw);
+	im->sw.pos = pos;
+}
+
+/* one literal of the output walk (the slab entry keeps its all-literal default) */
+static void imp_put_literal(mgl_imp* im)
+{
+	mgl_advance(&im->ow, MGL_LITERAL, 0, 1);
+	im->pos++;
+}
+
+static void imp_put(mgl_imp* im, uint32_t type, uint32_t dist, uint32_t len)
+{
+	if (im->slab) {
+		mgl_packet* e = &im->slab[im->pos];
+		e->type = (uint8_t)type;
+		e->dist = dist;
+		e->len = (uint16_t)len;
+	}
+	mgl_advance(&im->ow, type, dist, len);
+	im->pos += len;
+}
+
+/* A copy of `len` bytes from 0-based distance `d` that the stream coded as `type` / `idx`
+ * (MATCH: idx unused; LONG_REP: rep index; SHORT_REP).  Checks it against the input and
+ * emits it in the output walk's terms. */
+static int imp_copy(mgl_imp* im, uint32_t type, uint32_t idx, uint32_t d, uint32_t len)
+{
+	const size_t pos = im->pos;
+	if (len > im->n - pos) return imp_fail(im, MGL_EINVAL, "stream continues past the end of the input");
+	if ((size_t)d >= pos - im->dict_start) return imp_fail(im, MGL_EINVAL, "copy reaches before the start of the dictionary");
+	const uint8_t* a = im->data + pos - d - 1;
+	const uint8_t* b = im->data + pos;
+	for (uint32_t i = 0; i < len; i++)
+		if (a[i] != b[i]) {
+			im->pos = pos + i;
+			return imp_fail(im, MGL_EINVAL, "decoded byte differs from the input");
+		}
+	if (d >= im->window) {
+		if (!(im->flags & MGL_IMPORT_CLIP_WINDOW)) return imp_fail(im, MGL_ERANGE, "copy distance outside the window");
+		for (uint32_t i = 0; i < len; i++) imp_put_literal(im);
+		if (im->st) im->st->clipped++;
+		return MGL_OK;
+	}
+	uint32_t otype = MGL_MATCH, odist = d;
+	if (type != MGL_MATCH) {
+		/* the stream's own index first: that keeps an unchanged rep stack the identity */
+		int j = mgl_dist_at(&im->ow, idx) == d ? (int)idx : -1;
+		for (uint32_t k = 0; k < 4 && j < 0; k++) if (im->ow.dists[k] == d) j = (int)k;
+		if (len == 1) {
+			if (j == 0) { otype = MGL_SHORT_REP; odist = 0; }
+			else otype = MGL_LITERAL;
+		} else if (j >= 0) { otype = MGL_LONG_REP; odist = (uint32_t)j; }
+		if (im->st && (otype != type || (otype == MGL_LONG_REP && odist != idx))) im->st->reexpressed++;
+	}
+	if (otype == MGL_LITERAL) imp_put_literal(im);
+	else imp_put(im, otype, odist, len);
+	if (im->st) {
+		if (type == MGL_MATCH) im->st->matches++;
+		else if (type == MGL_SHORT_REP) im->st->short_reps++;
+		else im->st->long_reps[idx]++;
+	}
+	return MGL_OK;
+}
+
+/* Decode packets until the input position reaches `limit`, or an end marker when `limit` is
+ * unknown (SIZE_MAX).  *ended = an end marker was met. */
+static int imp_decode(mgl_imp* im, size_t limit, bool* ended)
+{
+	*ended = false;
+	const uint32_t pb_mask = (1u << im->L.pb) - 1u, lp_mask = (1u << im->L.lp) - 1u;
+	while (im->pos < limit || limit == SIZE_MAX) {
+		if (im->overrun) return imp_fail(im, MGL_EINVAL, "stream is truncated");
+		const size_t rel = im->pos - im->dict_start;
+		const uint32_t state = im->sw.ctx_state;
+		const uint32_t pos_state = (uint32_t)rel & pb_mask;
+		const uint32_t sp = (state << 4) + pos_state;
+		if (!rd_bit(im, MGL_CS_IS_MATCH + sp)) {
+			/* literal, mgl_plan_packet / mgl_plan_event */
+			if (im->pos >= im->n) return imp_fail(im, MGL_EINVAL, "stream continues past the end of the input");
+			const uint32_t prev = rel ? im->data[im->pos - 1] : 0;
+			const uint32_t lit_ctx = (((uint32_t)rel & lp_mask) << im->L.lc) + (prev >> (8u - im->L.lc));
+			const uint32_t base = MGL_OFF_LIT + 0x300u * lit_ctx;
+			uint32_t match_byte = 0, matched = state >= 7;
+			if (matched) {
+				if ((size_t)im->sw.dists[0] >= rel) return imp_fail(im, MGL_EINVAL, "copy reaches before the start of the dictionary");
+				match_byte = im->data[im->pos - im->sw.dists[0] - 1];
+			}
+			uint32_t sym = 1;
+			for (int i = 7; i >= 0; i--) {
+				const uint32_t mbit = (match_byte >> i) & 1u;
+				const uint32_t bit = rd_bit(im, base + sym + (matched ? (1u + mbit) << 8 : 0));
+				sym = (sym << 1) | bit;
+				if (matched && bit != mbit) matched = 0;
+			}
+			if ((sym & 0xFFu) != im->data[im->pos]) return imp_fail(im, MGL_EINVAL, "decoded byte differs from the input");
+			mgl_advance(&im->sw, MGL_LITERAL, 0, 1);
+			imp_put_literal(im);
+			if (im->st) im->st->literals++;
+		} else if (!rd_bit(im, MGL_CS_IS_REP + state)) {
+			/* match: length, distance slot, then the reverse tree or direct bits + align */
+			const uint32_t len = rd_length(im, MGL_OFF_LEN, pos_state);
+			const uint32_t len_ctx = len - 2 < 3 ? len - 2 : 3;
+			const uint32_t slot = rd_tree(im, MGL_OFF_DIST + len_ctx * 64, 6);
+			uint32_t d = slot;
+			if (slot >= 4) {
+				const uint32_t nlow = (slot >> 1) - 1;
+				d = (2u | (slot & 1u)) << nlow;
+				if (slot < 14) d += rd_tree_rev(im, MGL_OFF_DIST + MGL_DIST_POS + d - slot, nlow);
+				else {
+					d += rd_direct(im, nlow - 4) << 4;
+					d += rd_tree_rev(im, MGL_OFF_DIST + MGL_DIST_ALIGN, 4);
+				}
+			}
+			if (d == 0xFFFFFFFFu) {
+				if (im->overrun) return imp_fail(im, MGL_EINVAL, "stream is truncated");
+				*ended = true;
+				return MGL_OK;
+			}
+			if (len > limit - im->pos && limit != SIZE_MAX) return imp_fail(im, MGL_EINVAL, "copy crosses the end of the chunk");
+			int rc = imp_copy(im, MGL_MATCH, 0, d, len);
+			if (rc) return rc;
+			mgl_advance(&im->sw, MGL_MATCH, d, len);
+		} else {
+			uint32_t type = MGL_LONG_REP, idx = 0, len;
+			if (!rd_bit(im, MGL_CS_G0 + state)) {
+				if (!rd_bit(im, MGL_CS_REP0_LONG + sp)) type = MGL_SHORT_REP;
+			} else if (!rd_bit(im, MGL_CS_G1 + state)) idx = 1;
+			else idx = rd_bit(im, MGL_CS_G2 + state) ? 3 : 2;
+			len = type == MGL_SHORT_REP ? 1 : rd_length(im, MGL_OFF_REP_LEN, pos_state);
+			if (len > limit - im->pos && limit != SIZE_MAX) return imp_fail(im, MGL_EINVAL, "copy crosses the end of the chunk");
+			int rc = imp_copy(im, type, idx, mgl_dist_at(&im->sw, idx), len);
+			if (rc) return rc;
+			mgl_advance(&im->sw, type, idx, len);
+		}
+		if (im->st) im->st->packets++;
+	}
+	return MGL_OK;
+}
+
+/* the range decoder has consumed its input exactly and ends at zero (as liblzma requires) */
+static int imp_finish_rc(mgl_imp* im, bool exact)
+{
+	if (im->overrun) return imp_fail(im, MGL_EINVAL, "stream is truncated");
+	if (im->code != 0) return imp_fail(im, MGL_EINVAL, "range decoder does not end at zero");
+	if (exact && im->in != im->in_end) return imp_fail(im, MGL_EINVAL, "LZMA2 chunk has bytes left over");
+	return MGL_OK;
+}
+
+static uint64_t le_read(const uint8_t* p, int nbytes)
+{
+	uint64_t v = 0;
+	for (int i = nbytes - 1; i >= 0; i--) v = (v << 8) | p[i];
+	return v;
+}
+
+static const uint8_t k_xz_magic[6] = { 0xFD, '7', 'z', 'X', 'Z', 0x00 };
+
+/* .xz multibyte integer (at most 9 bytes); false on a truncated or overlong one */
+static bool xz_varint(const uint8_t* s, size_t len, size_t* at, uint64_t* out)
+{
+	uint64_t v = 0;
+	for (int i = 0; i < 9; i++) {
+		if (*at >= len) return false;
+		const uint8_t b = s[(*at)++];
+		v |= (uint64_t)(b & 0x7F) << (7 * i);
+		if (!(b & 0x80)) { *out = v; return b != 0 || i == 0; }
+	}
+	return false;
+}
+
+static const char* xz_filter_name(uint64_t id)
+{
+	switch (id) {
+	case 0x03: return "filter chain holds the delta filter; only a single LZMA2 filter is supported";
+	case 0x04: return "filter chain holds the x86 BCJ filter; only a single LZMA2 filter is supported";
+	case 0x05: return "filter chain holds the PowerPC BCJ filter; only a single LZMA2 filter is supported";
+	case 0x06: return "filter chain holds the IA-64 BCJ filter; only a single LZMA2 filter is supported";
+	case 0x07: return "filter chain holds the ARM BCJ filter; only a single LZMA2 filter is supported";
+	case 0x08: return "filter chain holds the ARM-Thumb BCJ filter; only a single LZMA2 filter is supported";
+	case 0x09: return "filter chain holds the SPARC BCJ filter; only a single LZMA2 filter is supported";
+	case 0x0A: return "filter chain holds the ARM64 BCJ filter; only a single LZMA2 filter is supported";
+	case 0x21: return "filter chain holds LZMA2 together with other filters; only a single LZMA2 filter is supported";
+	default: return "filter chain holds an unknown filter; only a single LZMA2 filter is supported";
+	}
+}
+
+/* Walk a .xz file: streams, blocks, LZMA2 chunks, index, footers, padding.  With im->data set
+ * the LZMA chunks are decoded against it; otherwise only their headers are read (for
+ * mgl_stream_info_read: props, dictionary, total size). */
+static int xz_walk(mgl_imp* im, const uint8_t* s, size_t len, uint32_t* dict_size, uint64_t* total)
+{
+	const bool decode = im->data != NULL;
+	size_t at = 0;
+	uint64_t upos = 0; /* uncompressed bytes so far */
+	int nstreams = 0;
+	*dict_size = 0;
+	for (;;) {
+		/* stream padding between streams: zero bytes, a multiple of four */
+		if (nstreams) {
+			size_t z = at;
+			while (z < len && s[z] == 0) z++;
+			if (z + 6 > len || memcmp(s + z, k_xz_magic, 6) != 0) break; /* trailing bytes are ignored */
+			if ((z - at) % 4) return imp_fail(im, MGL_EINVAL, ".xz stream padding is not a multiple of four bytes");
+			at = z;
+		}
+		if (len - at < 12 || memcmp(s + at, k_xz_magic, 6) != 0) return imp_fail(im, MGL_EINVAL, "not an .xz stream header");
+		if (s[at + 6] != 0 || s[at + 7] > 0x0F) return imp_fail(im, MGL_EINVAL, "unsupported .xz stream flags");
+		static const uint8_t k_check_size[16] = { 0, 4, 4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64 };
+		const uint8_t check_id = s[at + 7];
+		const size_t check_size = k_check_size[check_id];
+		at += 12;
+		nstreams++;
+		/* blocks */
+		while (at < len && s[at] != 0) {
+			const size_t bstart = at;
+			const size_t hsize = ((size_t)s[at] + 1) * 4;
+			if (hsize > len - at) return imp_fail(im, MGL_EINVAL, ".xz block header is truncated");
+			const uint8_t* h = s + at;
+			const uint8_t bflags = h[1];
+			if (bflags & 0x3C) return imp_fail(im, MGL_EINVAL, "unsupported .xz block flags");
+			const unsigned nfilters = (bflags & 3u) + 1;
+			size_t hp = 2;
+			uint64_t v;
+			const size_t hend = hsize - 4; /* CRC32 at the end (not verified) */
+			if ((bflags & 0x40) && !xz_varint(h, hend, &hp, &v)) return imp_fail(im, MGL_EINVAL, "bad .xz block header");
+			if ((bflags & 0x80) && !xz_varint(h, hend, &hp, &v)) return imp_fail(im, MGL_EINVAL, "bad .xz block header");
+			uint64_t ids[4], psize = 0;
+			uint8_t dict_byte = 0;
+			for (unsigned f = 0; f < nfilters; f++) {
+				if (!xz_varint(h, hend, &hp, &ids[f]) || !xz_varint(h, hend, &hp, &psize) || psize > hend - hp)
+					return imp_fail(im, MGL_EINVAL, "bad .xz block header");
+				if (ids[f] == 0x21 && psize == 1) dict_byte = h[hp];
+				hp += (size_t)psize;
+			}
+			if (nfilters != 1 || ids[0] != 0x21) {
+				for (unsigned f = 0; f < nfilters; f++)
+					if (ids[f] != 0x21) return imp_fail(im, MGL_EINVAL, xz_filter_name(ids[f]));
+				return imp_fail(im, MGL_EINVAL, xz_filter_name(0x21));
+			}
+			if (psize != 1 || dict_byte > 40) return imp_fail(im, MGL_EINVAL, "bad LZMA2 filter properties");
+			if (!*dict_size)
+				*dict_size = dict_byte == 40 ? 0xFFFFFFFFu : (2u | (dict_byte & 1u)) << (dict_byte / 2 + 11);
+			at += hsize;
+			/* LZMA2 chunks; every block starts a fresh decoder, which needs a dictionary reset first */
+			bool need_dict_reset = true, need_props = true;
+			for (;;) {
+				if (at >= len) return imp_fail(im, MGL_EINVAL, "LZMA2 data is truncated");
+				const uint8_t c = s[at];
+				if (c == 0x00) { at++; break; }
+				if (c == 0x01 || c >= 0xE0) {
+					need_dict_reset = false;
+					if (decode) im->dict_start = im->pos;
+				} else if (need_dict_reset) return imp_fail(im, MGL_EINVAL, "LZMA2 chunk without the dictionary reset a block starts with");
+				if (c < 0x80) {
+					/* uncompressed chunk: its bytes are literals; the LZMA state carries over */
+					if (c > 0x02) return imp_fail(im, MGL_EINVAL, "bad LZMA2 control byte");
+					if (len - at < 3) return imp_fail(im, MGL_EINVAL, "LZMA2 data is truncated");
+					const size_t usize = ((size_t)s[at + 1] << 8 | s[at + 2]) + 1;
+					at += 3;
+					if (usize > len - at) return imp_fail(im, MGL_EINVAL, "LZMA2 data is truncated");
+					if (c == 0x01) need_props = true;
+					if (decode) {
+						if (usize > im->n - im->pos) return imp_fail(im, MGL_EINVAL, "stream continues past the end of the input");
+						for (size_t i = 0; i < usize; i++) {
+							if (s[at + i] != im->data[im->pos]) return imp_fail(im, MGL_EINVAL, "decoded byte differs from the input");
+							imp_put_literal(im);
+						}
+						im->sw.pos += (uint32_t)usize;
+						if (im->st) { im->st->packets += usize; im->st->literals += usize; }
+					}
+					upos += usize;
+					at += usize;
+					continue;
+				}
+				const int reset = (c >> 5) & 3; /* 0 none, 1 state, 2 state + props, 3 + dictionary */
+				if (len - at < 5 + (reset >= 2)) return imp_fail(im, MGL_EINVAL, "LZMA2 data is truncated");
+				const size_t usize = ((size_t)(c & 0x1F) << 16 | (size_t)s[at + 1] << 8 | s[at + 2]) + 1;
+				const size_t csize = ((size_t)s[at + 3] << 8 | s[at + 4]) + 1;
+				at += 5;
+				if (reset >= 2) {
+					const uint8_t pbyte = s[at++];
+					if (pbyte >= 225 || pbyte % 9 + (pbyte / 9) % 5 > 4) return imp_fail(im, MGL_EINVAL, "bad LZMA2 properties");
+					if (!imp_set_props(im, pbyte)) return imp_fail(im, MGL_ENOMEM, "out of memory");
+					need_props = false;
+				} else if (need_props) return imp_fail(im, MGL_EINVAL, "LZMA2 chunk without the properties it needs");
+				if (csize > len - at) return imp_fail(im, MGL_EINVAL, "LZMA2 data is truncated");
+				if (decode) {
+					if (reset >= 1) imp_reset_state(im);
+					if (!rd_init(im, s + at, s + at + csize)) return imp_fail(im, MGL_EINVAL, "bad range coder start");
+					if (usize > im->n - im->pos) return imp_fail(im, MGL_EINVAL, "stream continues past the end of the input");
+					bool ended;
+					int rc = imp_decode(im, im->pos + usize, &ended);
+					if (!rc && ended) rc = imp_fail(im, MGL_EINVAL, "end marker inside an LZMA2 chunk");
+					if (!rc) rc = imp_finish_rc(im, true);
+					if (rc) return rc;
+				}
+				upos += usize;
+				at += csize;
+			}
+			/* block padding to a multiple of four, then the check (not verified: the bytes were) */
+			while ((at - bstart) % 4) {
+				if (at >= len || s[at] != 0) return imp_fail(im, MGL_EINVAL, "bad .xz block padding");
+				at++;
+			}
+			if (check_size > len - at) return imp_fail(im, MGL_EINVAL, ".xz block check is truncated");
+			at += check_size;
+		}
+		/* index: indicator, record count, (unpadded, uncompressed) pairs, padding, CRC32 */
+		if (at >= len) return imp_fail(im, MGL_EINVAL, ".xz index is missing");
+		const size_t istart = at++;
+		uint64_t nrec, v;
+		if (!xz_varint(s, len, &at, &nrec)) return imp_fail(im, MGL_EINVAL, "bad .xz index");
+		for (uint64_t r = 0; r < nrec; r++)
+			if (!xz_varint(s, len, &at, &v) || !xz_varint(s, len, &at, &v)) return imp_fail(im, MGL_EINVAL, "bad .xz index");
+		while ((at - istart) % 4) {
+			if (at >= len || s[at] != 0) return imp_fail(im, MGL_EINVAL, "bad .xz index padding");
+			at++;
+		}
+		if (len - at < 4 + 12) return imp_fail(im, MGL_EINVAL, ".xz stream footer is truncated");
+		at += 4;
+		const uint8_t* f = s + at;
+		if (f[10] != 'Y' || f[11] != 'Z' || f[8] != 0 || f[9] != check_id) return imp_fail(im, MGL_EINVAL, "bad .xz stream footer");
+		if (le_read(f + 4, 4) * 4 + 4 != at - istart) return imp_fail(im, MGL_EINVAL, ".xz stream footer does not match the index");
+		at += 12;
+	}
+	if (!im->have_props) return imp_fail(im, MGL_EINVAL, ".xz stream holds no LZMA chunk");
+	*total = upos;
+	return MGL_OK;
+}
+
+static bool is_xz(const uint8_t* s, size_t len)
+{
+	return len >= 6 && memcmp(s, k_xz_magic, 6) == 0;
+}
+
+int mgl_stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out)
+{
+	if (!stream || !out) return MGL_EINVAL;
+	memset(out, 0, sizeof *out);
+	if (is_xz(stream, len)) {
+		mgl_imp im;
+		memset(&im, 0, sizeof im);
+		uint32_t dict = 0;
+		uint64_t total = 0;
+		const int rc = xz_walk(&im, stream, len, &dict, &total);
+		free(im.probs);
+		if (rc) return rc;
+		out->container = 2;
+		out->props = im.props;
+		out->dict_size = dict;
+		out->declared_size = total;
+		return MGL_OK;
+	}
+	if (len < 13 || stream[0] >= 225) return MGL_EINVAL;
+	out->container = 1;
+	out->props.lc = (uint8_t)(stream[0] % 9);
+	out->props.lp = (uint8_t)((stream[0] / 9) % 5);
+	out->props.pb = (uint8_t)(stream[0] / 45);
+	out->dict_size = (uint32_t)le_read(stream + 1, 4);
+	out->declared_size = le_read(stream + 5, 8);
+	return MGL_OK;
+}
+
+int mgl_stream_import(const uint8_t* stream, size_t len, const uint8_t* data, size_t n, uint32_t window, uint32_t flags,
+                      mgl_packet* slab_out, mgl_import_stats* st)
+{
+	if (st) memset(st, 0, sizeof *st);
+	if (!stream || (!data && n)) {
+		if (st) st->error = "null argument";
+		return MGL_EINVAL;
+	}
+	static const uint8_t k_empty = 0;
+	mgl_imp im;
+	memset(&im, 0, sizeof im);
+	im.data = data ? data : &k_empty; /* non-NULL: xz_walk decodes */
+	im.n = n;
+	im.window = window ? window : 0x400000u; /* 0 = the dictionary mgl_emit_stream declares */
+	im.flags = flags;
+	im.slab = slab_out;
+	im.st = st;
+	if (slab_out) {
+		/* the all-literal slab (padding bytes zero, like binding.literal_slab) */
+		memset(slab_out, 0, sizeof(mgl_packet) * n);
+		for (size_t i = 0; i < n; i++) { slab_out[i].type = MGL_LITERAL; slab_out[i].len = 1; }
+	}
+	int rc = MGL_OK;
+	if (is_xz(stream, len)) {
+		uint32_t dict;
+		uint64_t total;
+		rc = xz_walk(&im, stream, len, &dict, &total);
+		if (!rc && im.pos != n) rc = imp_fail(&im, MGL_EINVAL, "stream ends before the end of the input");
+	} else if (len < 13) {
+		rc = imp_fail(&im, MGL_EINVAL, "stream is shorter than an LZMA header");
+	} else {
+		const uint64_t declared = le_read(stream + 5, 8);
+		if (stream[0] >= 225) rc = imp_fail(&im, MGL_EINVAL, "bad LZMA properties byte");
+		else if (!imp_set_props(&im, stream[0])) rc = imp_fail(&im, MGL_ENOMEM, "out of memory");
+		else if (declared != UINT64_MAX && declared != n) rc = imp_fail(&im, MGL_EINVAL, "declared size differs from the input");
+		if (!rc) {
+			imp_reset_state(&im);
+			if (!rd_init(&im, stream + 13, stream + len)) rc = imp_fail(&im, MGL_EINVAL, "bad range coder start");
+		}
+		if (!rc) {
+			bool ended = false;
+			rc = imp_decode(&im, declared == UINT64_MAX ? SIZE_MAX : n, &ended);
+			if (!rc && im.pos != n) rc = imp_fail(&im, MGL_EINVAL, "stream ends before the end of the input");
+			if (!rc) rc = imp_finish_rc(&im, false);
+		}
+	}
+	free(im.probs);
+	if (rc && st) {
+		st->error = im.error;
+		st->error_pos = im.error_pos;
+	}
+	return rc;
+}

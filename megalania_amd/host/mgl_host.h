@@ -13,6 +13,26 @@
  *   mgl_file_output_new               file_output.c:9-13
  *   mgl_memory_output_new             (no reference equivalent: OutputInterface over a buffer)
  *   mgl_emit_stream                   main.c:110-119 as one call
+ *   mgl_stream_info_read / _import    (no reference equivalent: the reference has no decoder)
+ *
+ * Stream import reads the parse out of an existing LZMA-alone (.lzma) or .xz stream of the same
+ * input, as a starting slab for the search (the best known parse of a file is usually the one
+ * xz already wrote).  Range decoder + LZMA packet decoder over the encoder's own contexts
+ * (csrc/mgl_model.h); no output is materialised: each decoded byte is compared with `data`,
+ * which also serves as the dictionary, whatever size the header declares.  .xz: streams
+ * (concatenated ones too), blocks with any check, index, padding, and LZMA2 chunks of every
+ * kind; a filter chain other than a single LZMA2 filter is refused.  Checks are not verified
+ * (the byte comparison covers the content).  The slab is position-indexed like every slab here
+ * (walked packets at their start, all-literal elsewhere); every packet is resolved to its
+ * concrete distance under the stream's own rep stack and re-expressed against the output
+ * walk's (LZMA2 state resets and clipped copies make them differ): MATCH stays MATCH; a rep
+ * becomes LONG_REP(j) / SHORT_REP (j = 0, length 1) where that distance sits at index j of the
+ * output stack, else MATCH, or a literal when its length is 1.  For an LZMA-alone stream with
+ * nothing clipped this is the identity.  A copy whose 0-based distance is >= `window` (0 = 4 MiB,
+ * the dictionary mgl_emit_stream declares) is MGL_ERANGE, or `len` literals under
+ * MGL_IMPORT_CLIP_WINDOW.  Truncated / corrupt streams, a byte that differs from the input, a
+ * declared size other than n and a stream that ends early are MGL_EINVAL; bytes after the end
+ * marker or the declared size are ignored.
  *
  * Error conventions follow the reference: constructors that allocate return false/NULL and
  * print to stderr; a failed OutputInterface.write is only logged (range_encoder.c:29-31).
@@ -54,6 +74,28 @@ void mgl_memory_output_new(OutputInterface* output, mgl_memory_sink* sink);
 
 /* header + every packet on the slab's walk through a fresh range coder; false on bad input */
 bool mgl_emit_stream(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, OutputInterface* output);
+
+typedef struct {
+	int container;            /* 1 LZMA-alone (.lzma), 2 .xz */
+	mgl_properties props;     /* .lzma: the header byte; .xz: the first LZMA2 chunk that carries props */
+	uint32_t dict_size;       /* as declared (.xz: the first block's LZMA2 filter) */
+	uint64_t declared_size;   /* UINT64_MAX = unknown (end marker expected); .xz: the sum of its chunks */
+} mgl_stream_info;
+/* MGL_OK, or MGL_EINVAL when `stream` is neither container (or a malformed .xz) */
+int mgl_stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out);
+
+#define MGL_IMPORT_CLIP_WINDOW 1u /* copies from beyond the window become literals instead of an error */
+typedef struct {
+	uint64_t packets, literals, matches, short_reps, long_reps[4]; /* as the stream coded them */
+	uint64_t reexpressed;     /* packets whose type or rep index had to change */
+	uint64_t clipped;         /* copies turned into literals under MGL_IMPORT_CLIP_WINDOW */
+	uint64_t props_changes;   /* LZMA2 chunks that set props other than the first ones */
+	uint64_t error_pos;       /* input position of the first problem (valid when the call fails) */
+	const char* error;        /* static text of the first problem, NULL on success */
+} mgl_import_stats;
+/* slab_out (nullable: validate only): n entries.  st (nullable).  0 or a negative MGL_E* code. */
+int mgl_stream_import(const uint8_t* stream, size_t len, const uint8_t* data, size_t n,
+                      uint32_t window, uint32_t flags, mgl_packet* slab_out, mgl_import_stats* st);
 
 #ifdef __cplusplus
 }
