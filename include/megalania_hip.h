@@ -162,6 +162,35 @@ int mgl_sa_set_slab(mgl_sa* sa, const mgl_packet* packets);
  * among equals; len 2 only up to distance 128, len 3 up to 2^14; dropped when the next position
  * would take a longer one), or a literal; the slab walk picks the parse out of them.  Same effect on the handle as mgl_sa_set_slab. */
 int mgl_sa_seed_greedy(mgl_sa* sa, uint32_t candidates);
+/* Optimal-parse seed (not in the reference; DESIGN.md section 10, megalania_amd/csrc/mgl_optimal.hip).  Pass p runs
+ * a forward shortest path over every chunk of `chunk` bytes under static bit prices, then resolves the concatenated
+ * parse against the true rep stack; pass 0 takes its prices from the greedy seed's parse (`cand` candidates), pass
+ * p > 0 from pass p - 1's resolved parse, whose walk states also start pass p's chunks.  Every resolved parse is
+ * costed exactly; the cheapest becomes the current slab, with the same effect on the handle as mgl_sa_seed_greedy.
+ * Fields left 0 take the defaults; cand is at most 30 (MATCH candidates per order, as in mgl_sa_seed_greedy). */
+#define MGL_OPT_MAX_PASSES 16
+typedef struct {
+	uint32_t passes; /* default 3, at most MGL_OPT_MAX_PASSES */
+	uint32_t cand;   /* default 16 */
+	uint32_t chunk;  /* bytes per DP chunk, default 4096, at least 512 */
+} mgl_optimal_config;
+typedef struct {
+	uint32_t passes;     /* passes run */
+	uint32_t best_pass;  /* the one whose parse became the current slab */
+	uint64_t greedy_cost; /* exact cost of the greedy parse the first prices came from */
+	uint64_t cost[MGL_OPT_MAX_PASSES];      /* exact cost of each resolved parse */
+	uint64_t objective[MGL_OPT_MAX_PASSES]; /* sum of the DP's static prices over the chunks */
+	double ms[MGL_OPT_MAX_PASSES];          /* device time of each pass: DP, resolution, costing, next prices */
+} mgl_optimal_stats;
+int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mgl_optimal_stats* stats);
+/* Parity hook: one DP pass under explicit `prices` (nprices = 2 x number of probabilities, price of (slot, bit) at
+ * 2 * slot + bit, cost units) with the LZMA initial state at every chunk start.  packets_out (n entries) is the
+ * concatenated, unresolved parse: copies carry their type in the DP (LONG_REP, SHORT_REP, MATCH) and their absolute
+ * distance (>= 1), positions off the parse hold literals; *objective = sum of its prices.  The SA state is untouched. */
+int mgl_optimal_pass(mgl_sa* sa, const uint32_t* prices, size_t nprices, uint32_t cand, uint32_t chunk,
+                     mgl_packet* packets_out, uint64_t* objective);
+/* The prices mgl_sa_seed_optimal derives from a (valid) slab: 2 x number of probabilities u32. */
+int mgl_optimal_prices(mgl_sa* sa, const mgl_packet* packets, uint32_t* prices_out, size_t nprices);
 /* Opt-in Metropolis accept rule (not in the reference, whose rule ignores the cost difference,
  * main.c:86).  temperature = 0 (default): the reference's rule.  temperature > 0, in
  * cost units (16384 per output byte, main.c:97): when the step's best neighbour does not improve,

@@ -32,7 +32,7 @@ ACCEPT_AUTO, ACCEPT_SINGLE, ACCEPT_BULK = 0, 1, 2
 
 HIP_SYMBOLS = [
     "mgl_version", "mgl_last_error", "mgl_device_count", "mgl_sa_create", "mgl_sa_destroy", "mgl_sa_begin_epoch",
-    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
+    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
     "mgl_substrings", "mgl_neighbours", "mgl_rng_draw_at", "mgl_debug_dump", "mgl_debug_set",
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed",
@@ -78,6 +78,19 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+OPT_MAX_PASSES = 16
+
+
+class OptimalConfig(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("cand", C.c_uint32), ("chunk", C.c_uint32)]
+
+
+class OptimalStats(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("best_pass", C.c_uint32), ("greedy_cost", C.c_uint64),
+                ("cost", C.c_uint64 * OPT_MAX_PASSES), ("objective", C.c_uint64 * OPT_MAX_PASSES),
+                ("ms", C.c_double * OPT_MAX_PASSES)]
+
+
 class StreamInfo(C.Structure):
     _fields_ = [("container", C.c_int), ("props", Properties), ("dict_size", C.c_uint32), ("declared_size", C.c_uint64)]
 
@@ -118,6 +131,10 @@ def hip_lib():
         L.mgl_sa_begin_epoch.argtypes = [C.c_void_p, C.c_uint, C.c_int]
         L.mgl_sa_set_slab.argtypes = [C.c_void_p, C.c_void_p]
         L.mgl_sa_seed_greedy.argtypes = [C.c_void_p, C.c_uint32]
+        L.mgl_sa_seed_optimal.argtypes = [C.c_void_p, C.POINTER(OptimalConfig), C.POINTER(OptimalStats)]
+        L.mgl_optimal_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                       C.POINTER(C.c_uint64)]
+        L.mgl_optimal_prices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.mgl_sa_set_temperature.argtypes = [C.c_void_p, C.c_uint64]
         L.mgl_sa_set_best.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.mgl_sa_set_accept_mode.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
@@ -281,6 +298,31 @@ class SA:
     def seed_greedy(self, candidates: int = 256):
         """Current slab := greedy LZ parse made on the device (opt-in starting point)."""
         self._chk(self.L.mgl_sa_seed_greedy(self.h, candidates))
+
+    def seed_optimal(self, passes: int = 0, cand: int = 0, chunk: int = 0) -> dict:
+        """Current slab := the best of `passes` price-driven optimal parses made on the device (mgl_sa_seed_optimal;
+        0 = the library's defaults).  Returns the per-pass stats: exact cost, DP objective and device ms per pass."""
+        st = OptimalStats()
+        self._chk(self.L.mgl_sa_seed_optimal(self.h, C.byref(OptimalConfig(passes, cand, chunk)), C.byref(st)))
+        k = st.passes
+        return dict(passes=k, best_pass=st.best_pass, greedy_cost=st.greedy_cost, cost=list(st.cost[:k]),
+                    objective=list(st.objective[:k]), ms=list(st.ms[:k]))
+
+    def optimal_prices(self, slab) -> np.ndarray:
+        """The static prices (u32 per (slot, bit), index 2 * slot + bit) that the optimal seed derives from `slab`."""
+        slab = np.ascontiguousarray(slab, dtype=PACKET)
+        out = np.zeros(2 * self.nprobs, dtype=np.uint32)
+        self._chk(self.L.mgl_optimal_prices(self.h, _ptr(slab), _ptr(out), len(out)))
+        return out
+
+    def optimal_pass(self, prices, cand: int, chunk: int):
+        """One DP pass under explicit prices, LZMA initial state at every chunk start (parity hook, SA state untouched).
+        Returns (unresolved slab with absolute distances, objective)."""
+        prices = np.ascontiguousarray(prices, dtype=np.uint32)
+        out = np.zeros(self.n, dtype=PACKET)
+        obj = C.c_uint64(0)
+        self._chk(self.L.mgl_optimal_pass(self.h, _ptr(prices), len(prices), cand, chunk, _ptr(out), C.byref(obj)))
+        return out, obj.value
 
     def seed_stream(self, stream: bytes, clip: bool = False) -> int:
         """Best slab := the parse inside an existing .lzma / .xz stream of this input (stream_import, window =

@@ -9,6 +9,7 @@
 #include "mgl_kernels5.hip"
 #include "mgl_pbuild.hip"
 #include "mgl_index.hip"
+#include "mgl_optimal.hip"
 #include "../../include/megalania_hip.h"
 
 #include <math.h>
@@ -1363,6 +1364,176 @@ extern "C" int mgl_sa_seed_greedy(mgl_sa* sa, uint32_t candidates)
 	if ((rc = rebuild_base(sa, 0))) return rc;
 	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
 	if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_greedy: the seeded slab failed the walk check");
+	return MGL_OK;
+}
+
+/* ---- optimal-parse seed (mgl_optimal.hip) */
+static int scratch_walk(mgl_sa* sa, const mgl_packet* packets, bool want_cum, bool want_probs, Control* out);
+#define MGL_OPT_DEF_PASSES 3u
+#define MGL_OPT_DEF_CAND 16u
+#define MGL_OPT_DEF_CHUNK 4096u
+struct OptBufs {
+	uint32_t *counts = nullptr, *prices = nullptr, *entry = nullptr;
+	mgl_pk *back = nullptr, *dp = nullptr, *res = nullptr, *keep = nullptr;
+	unsigned long long* obj = nullptr;
+	~OptBufs() { dfree(counts); dfree(prices); dfree(entry); dfree(back); dfree(dp); dfree(res); dfree(keep); dfree(obj); }
+};
+static int opt_alloc(mgl_sa* sa, OptBufs& o, uint32_t chunk, bool seed)
+{
+	const size_t n = sa->n, total = sa->ctx.L.total, nch = (n + chunk - 1) / chunk;
+	HIPCHK(hipMalloc(&o.counts, sizeof(uint32_t) * 2 * total));
+	HIPCHK(hipMalloc(&o.prices, sizeof(uint32_t) * 2 * total));
+	HIPCHK(hipMalloc(&o.back, sizeof(mgl_pk) * (n + 1)));
+	HIPCHK(hipMalloc(&o.dp, sizeof(mgl_pk) * n));
+	HIPCHK(hipMalloc(&o.obj, sizeof(unsigned long long)));
+	if (seed) {
+		HIPCHK(hipMalloc(&o.entry, sizeof(uint32_t) * 5 * nch));
+		HIPCHK(hipMalloc(&o.res, sizeof(mgl_pk) * n));
+		HIPCHK(hipMalloc(&o.keep, sizeof(mgl_pk) * n));
+	}
+	return MGL_OK;
+}
+/* prices of the parse on `slab` (a valid parse) */
+static int opt_prices(mgl_sa* sa, OptBufs& o, const mgl_pk* slab)
+{
+	const uint32_t total = sa->ctx.L.total;
+	HIPCHK(hipMemsetAsync(o.counts, 0, sizeof(uint32_t) * 2 * total, sa->stream));
+	hipLaunchKernelGGL(k_opt_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, slab, (mgl_pk*)nullptr, o.counts, 0, 1u, (uint32_t*)nullptr);
+	hipLaunchKernelGGL(k_opt_prices, dim3((total + 255) / 256), dim3(256), 0, sa->stream, (const uint32_t*)o.counts, sa->ctx.cost_tbl, total, o.prices);
+	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+/* one DP pass into o.dp (entry == nullptr: the LZMA initial state at every chunk start) */
+static int opt_dp(mgl_sa* sa, OptBufs& o, const uint32_t* entry, uint32_t cand, uint32_t chunk)
+{
+	const uint32_t nch = (uint32_t)((sa->n + chunk - 1) / chunk);
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.dp, (uint32_t)sa->n);
+	HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long), sa->stream));
+	hipLaunchKernelGGL(k_opt_dp, dim3(nch), dim3(64), 0, sa->stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj);
+	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+static int opt_args(uint32_t cand, uint32_t chunk)
+{
+	if (cand == 0 || cand > MGL_OPT_MAX_CAND) return fail(MGL_EINVAL, "optimal parse: cand must be 1..30");
+	if (chunk < MGL_OPT_MIN_CHUNK) return fail(MGL_EINVAL, "optimal parse: chunk must be at least 512 bytes");
+	return MGL_OK;
+}
+
+extern "C" int mgl_optimal_pass(mgl_sa* sa, const uint32_t* prices, size_t nprices, uint32_t cand, uint32_t chunk,
+                                mgl_packet* packets_out, uint64_t* objective)
+{
+	if (!sa || !prices || !packets_out) return fail(MGL_EINVAL, "null argument");
+	int rc = opt_args(cand, chunk);
+	if (rc) return rc;
+	if (nprices != 2 * (size_t)sa->ctx.L.total) return fail(MGL_EINVAL, "mgl_optimal_pass: nprices must be 2 x the number of probabilities");
+	for (size_t k = 0; k < nprices; k++)
+		if (prices[k] > 0xFFFFu) return fail(MGL_EINVAL, "mgl_optimal_pass: a price is above 65535 cost units");
+	HIPCHK(hipSetDevice(sa->device));
+	OptBufs o;
+	if ((rc = opt_alloc(sa, o, chunk, false))) return rc;
+	HIPCHK(hipMemcpyAsync(o.prices, prices, sizeof(uint32_t) * nprices, hipMemcpyHostToDevice, sa->stream));
+	if ((rc = opt_dp(sa, o, nullptr, cand, chunk))) return rc;
+	unsigned long long obj = 0;
+	HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
+	if ((rc = export_slab(sa, o.dp, packets_out))) return rc;
+	if (objective) *objective = obj;
+	return MGL_OK;
+}
+
+extern "C" int mgl_optimal_prices(mgl_sa* sa, const mgl_packet* packets, uint32_t* prices_out, size_t nprices)
+{
+	if (!sa || !packets || !prices_out) return fail(MGL_EINVAL, "null argument");
+	if (nprices < 2 * (size_t)sa->ctx.L.total) return fail(MGL_ERANGE, "prices_out too small");
+	HIPCHK(hipSetDevice(sa->device));
+	Control c;
+	int rc = scratch_walk(sa, packets, false, false, &c); /* validates the slab */
+	if (rc) return rc;
+	OptBufs o;
+	if ((rc = opt_alloc(sa, o, MGL_OPT_DEF_CHUNK, false))) return rc;
+	if ((rc = opt_prices(sa, o, sa->scratch.v.slab))) return rc;
+	HIPCHK(hipMemcpyAsync(prices_out, o.prices, sizeof(uint32_t) * 2 * sa->ctx.L.total, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	return MGL_OK;
+}
+
+/* current slab := the parse on `slab` (device); returns its exact cost through the base's rebuild */
+static int opt_make_current(mgl_sa* sa, const mgl_pk* slab, uint64_t* cost)
+{
+	Control c;
+	int rc = read_ctl(sa, sa->base, &c);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(sa->base.v.slab, slab, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->stream));
+	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
+	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
+	if ((rc = rebuild_base(sa, 0))) return rc;
+	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+	if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_optimal: a resolved parse failed the walk check");
+	*cost = c.rebuild_cost;
+	return MGL_OK;
+}
+
+extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mgl_optimal_stats* stats)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	const uint32_t passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
+	const uint32_t cand = cfg && cfg->cand ? cfg->cand : MGL_OPT_DEF_CAND;
+	const uint32_t chunk = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
+	int rc = opt_args(cand, chunk);
+	if (rc) return rc;
+	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "mgl_sa_seed_optimal: at most 16 passes");
+	HIPCHK(hipSetDevice(sa->device));
+	mgl_optimal_stats st;
+	memset(&st, 0, sizeof st);
+	Control c;
+	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+	if ((rc = keep_best_before_overwrite(sa, c))) return rc;
+	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
+	sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
+	OptBufs o;
+	if ((rc = opt_alloc(sa, o, chunk, true))) return rc;
+	const uint32_t n = (uint32_t)sa->n;
+	/* pass 0's prices: the greedy parse */
+	hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.res, cand);
+	HIPCHK(hipGetLastError());
+	if ((rc = opt_make_current(sa, o.res, &st.greedy_cost))) return rc;
+	if ((rc = opt_prices(sa, o, o.res))) return rc;
+	hipEvent_t t0, t1;
+	HIPCHK(hipEventCreate(&t0));
+	HIPCHK(hipEventCreate(&t1));
+	uint64_t best = ~0ull;
+	for (uint32_t p = 0; p < passes && rc == MGL_OK; p++) {
+		if (hipEventRecord(t0, sa->stream) != hipSuccess) { rc = fail(MGL_EDEVICE, "hipEventRecord"); break; }
+		if ((rc = opt_dp(sa, o, p ? o.entry : nullptr, cand, chunk))) break;
+		hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.res, n);
+		HIPCHK(hipMemsetAsync(o.counts, 0, sizeof(uint32_t) * 2 * sa->ctx.L.total, sa->stream));
+		hipLaunchKernelGGL(k_opt_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, (const mgl_pk*)o.dp, o.res, o.counts, 1, chunk, o.entry);
+		hipLaunchKernelGGL(k_opt_prices, dim3((sa->ctx.L.total + 255) / 256), dim3(256), 0, sa->stream, (const uint32_t*)o.counts, sa->ctx.cost_tbl,
+		                   sa->ctx.L.total, o.prices);
+		if ((rc = opt_make_current(sa, o.res, &st.cost[p]))) break;
+		unsigned long long obj = 0;
+		HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
+		float ms = 0;
+		HIPCHK(hipEventRecord(t1, sa->stream));
+		HIPCHK(hipEventSynchronize(t1));
+		st.objective[p] = obj;
+		HIPCHK(hipEventElapsedTime(&ms, t0, t1));
+		st.ms[p] = ms;
+		st.passes = p + 1;
+		if (st.cost[p] < best) {
+			best = st.cost[p]; st.best_pass = p;
+			HIPCHK(hipMemcpyAsync(o.keep, o.res, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
+		}
+	}
+	(void)hipEventDestroy(t0);
+	(void)hipEventDestroy(t1);
+	if (rc) return rc;
+	if (st.best_pass + 1 != st.passes && (rc = opt_make_current(sa, o.keep, &best))) return rc;
+	if ((rc = launch_validate(sa))) return rc;
+	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+	if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_optimal: the seeded slab failed the walk check");
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	if (stats) *stats = st;
 	return MGL_OK;
 }
 

@@ -27,7 +27,7 @@ static void usage(const char* argv0)
 	fprintf(stderr,
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
 	        "          [--lc N --lp N --pb N] [--device D] [--max-scan M]\n"
-	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--temperature B]\n"
+	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
@@ -35,6 +35,9 @@ static void usage(const char* argv0)
 	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb)\n"
 	        "  --greedy-seed C  epochs that the reference starts from the all-literal slab start from a greedy\n"
 	        "               parse instead (longest of the C nearest candidates per position; e.g. 256)\n"
+	        "  --optimal-seed P  epochs that the reference starts from the all-literal slab start from the best of P\n"
+	        "               price-driven optimal parses made on the device (e.g. 3); not with --greedy-seed,\n"
+	        "               --seed-stream or --load-slab\n"
 	        "  --seed-stream F  start from the parse inside an existing .lzma / .xz stream of this input (e.g. xz -9e's):\n"
 	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's\n"
 	        "  --clip-window    with --seed-stream: copies from beyond the dictionary window become literals instead\n"
@@ -65,7 +68,8 @@ int main(int argc, char** argv)
 	const char* filename = NULL;
 	const char *out_path = NULL, *save_path = NULL, *load_path = NULL, *seed_stream_path = NULL;
 	int clip_window = 0, props_given = 0;
-	uint32_t greedy = 0;
+	uint32_t greedy = 0, optimal = 0;
+	mgl_packet* optimal_slab = NULL;
 	double temperature_bytes = 0;
 	int accept_mode = MGL_ACCEPT_AUTO;
 	int chains = 1, rank = 0, device_given = 0;
@@ -100,6 +104,7 @@ int main(int argc, char** argv)
 		else if (!strcmp(a, "--save-slab")) save_path = v;
 		else if (!strcmp(a, "--load-slab")) load_path = v;
 		else if (!strcmp(a, "--greedy-seed")) greedy = (uint32_t)strtoul(v, NULL, 0);
+		else if (!strcmp(a, "--optimal-seed")) { optimal = (uint32_t)strtoul(v, NULL, 0); if (!optimal) { usage(argv[0]); return -1; } }
 		else if (!strcmp(a, "--seed-stream")) seed_stream_path = v;
 		else if (!strcmp(a, "--temperature")) temperature_bytes = strtod(v, NULL);
 		else if (!strcmp(a, "--accept")) {
@@ -114,6 +119,11 @@ int main(int argc, char** argv)
 	if (!filename) { usage(argv[0]); return -1; }
 	if (seed_stream_path && (load_path || greedy)) {
 		fprintf(stderr, "Error: --seed-stream cannot be combined with --load-slab or --greedy-seed\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (optimal && (greedy || seed_stream_path || load_path)) {
+		fprintf(stderr, "Error: --optimal-seed cannot be combined with --greedy-seed, --seed-stream or --load-slab\n");
 		usage(argv[0]);
 		return -1;
 	}
@@ -245,12 +255,29 @@ int main(int argc, char** argv)
 		resumed = true;
 	}
 
+	if (optimal) {
+		/* made once; every epoch that would start from the all-literal slab starts from it */
+		mgl_optimal_config oc = { optimal, 0, 0 };
+		mgl_optimal_stats os;
+		uint64_t cost = 0;
+		optimal_slab = (mgl_packet*)malloc(sizeof(mgl_packet) * (file_size ? file_size : 1));
+		if (!optimal_slab || mgl_sa_seed_optimal(sa, &oc, &os) != MGL_OK || mgl_sa_current(sa, optimal_slab, &cost) != MGL_OK) {
+			fprintf(stderr, "Error: %s\n", optimal_slab ? mgl_last_error() : "out of memory");
+			return -1;
+		}
+		double ms = 0;
+		for (uint32_t p = 0; p < os.passes; p++) ms += os.ms[p];
+		fprintf(stderr, "optimal seed: %u passes in %.1f ms, estimate %f bytes (greedy parse %f)\n", os.passes, ms,
+		        18 + cost / 16384.f, 18 + os.greedy_cost / 16384.f);
+	}
+
 	unsigned long long steps_per_epoch = (file_size + cfg.neighbours_per_step - 1) / cfg.neighbours_per_step;
 	if (steps_override) steps_per_epoch = steps_override;
 	for (unsigned phase = 0; phase < phases; phase++) {
 		for (unsigned epoch = 0; epoch < epochs; epoch++) {
 			if (mgl_sa_begin_epoch(sa, phase, phase != 0 || resumed) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			if (greedy && phase == 0 && !resumed && mgl_sa_seed_greedy(sa, greedy) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+			if (optimal && phase == 0 && mgl_sa_set_slab(sa, optimal_slab) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			mgl_sa_stats st;
 			if (mgl_sa_run(sa, steps_per_epoch, &st) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			/* main.c:97-99: 18 = 13 header bytes + 5 flush bytes, 16384 = 2048 * 8 */
@@ -294,6 +321,7 @@ int main(int argc, char** argv)
 	mgl_file_output_new(&output, out);
 	if (!mgl_emit_stream(file_data, file_size, props, packets_best, &output)) return -1;
 	if (out_path ? fclose(out) != 0 : fflush(stdout) != 0) { fprintf(stderr, "Error: could not write the stream\n"); return -1; }
+	free(optimal_slab);
 	free(packets_best);
 	munmap((void*)file_data, file_size);
 	close(fd);
