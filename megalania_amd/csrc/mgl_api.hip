@@ -37,11 +37,6 @@ static int fail(int code, const std::string& msg)
 			return fail(MGL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
 	} while (0)
 
-/* Look-ahead (opt-in, MGL_LOOKAHEAD=1) keeps five streams busy -- the step's own chain, the second slice, the re-simulations,
- * two speculative slices -- and streams that share a hardware queue run one behind the other: more queues than the runtime's
- * default of four, set before the runtime initialises (its first call) and only if the user has not set the variable. */
-__attribute__((constructor)) static void mgl_more_hw_queues(void) { if (getenv("MGL_LOOKAHEAD")) setenv("GPU_MAX_HW_QUEUES", "8", 0); }
-
 extern "C" const char* mgl_version(void) { return "megalania-hip 0.1 (gfx950)"; }
 extern "C" const char* mgl_last_error(void) { return g_err.c_str(); }
 extern "C" int mgl_device_count(void)
@@ -154,9 +149,6 @@ struct mgl_sa {
 	uint32_t force_rollbacks = 0;  /* diagnostic: treat the next so many bulk steps that took moves as failed validations */
 	uint64_t bulk_rollbacks = 0;   /* bulk steps whose combined parse failed validation and was taken back (never seen) */
 	bool best_unverified = false;  /* packets_best came from another chain: checked when an epoch starts from it */
-	/* look-ahead (k_la_check): the next step's pick + window walk run beside this step's tail into the other buffer set */
-	struct NbrSet { NbrOut nbr; uint4* pickrec; uint4* pickstate; uint4* sim_hdr; uint16_t* sim_keys; uint32_t* sim_pos; uint32_t* todo; uint32_t* counts; };
-	NbrSet alt = {};
 	uint32_t sim_waves = MGL_SIM_WAVES; /* wavefronts per neighbour in the regular re-simulation launch (MGL_SIMW: 1, 2, 4, 8) */
 	/* the re-simulation kernel measured on its own (it is the path's dominant kernel): HIP events around its launches on the
 	 * streams they run on (MGL_F_TIMING), and -- when switched on, mgl_debug_set key 4 -- the bytes of chain data it reads */
@@ -164,15 +156,8 @@ struct mgl_sa {
 	int64_t time_sim_step = -1;     /* >= 0: the step whose k_sim launches are bracketed by events */
 	bool count_traffic = false;
 	unsigned long long* d_traffic = nullptr; /* [0] bytes [1] spare */
-	bool la_enabled = false, la_ready = false;
-	hipGraph_t nbr_graph = nullptr; hipGraphExec_t nbr_graph_exec = nullptr; uint64_t nbr_graph_key = 0; bool graph_ok = false; /* a step's neighbour launches, captured */
 	uint32_t short_looks = 0;      /* blocks of at most four steps still to come after a switch of the launch form */
-	uint8_t* d_la_mark = nullptr;
-	uint32_t* d_la_list = nullptr;
-	uint32_t* d_la_hdr = nullptr;  /* [0] neighbours to evaluate again, [1] second-pass entries of the speculative launch */
-	hipStream_t stream5 = nullptr, stream6 = nullptr;
 	hipEvent_t ev_val = nullptr; /* a bulk step's validation beside its build */
-	hipEvent_t ev_la_check = nullptr, ev_la_zero = nullptr, ev_redo = nullptr, ev_spec[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 };
 
 static uint64_t ceil_sqrt_u64(uint64_t x)
@@ -383,60 +368,10 @@ static hipEvent_t sim_event(mgl_sa* sa, size_t i)
 	}
 	return sa->ev_sim_pool[i];
 }
-static mgl_sa::NbrSet cur_set(const mgl_sa* sa)
-{
-	mgl_sa::NbrSet t = { sa->nbr, sa->d_pickrec, sa->d_pickstate, sa->big.sim_hdr, sa->big.sim_keys, sa->big.sim_pos, sa->d_todo, sa->d_counts };
-	return t;
-}
-static void use_set(mgl_sa* sa, const mgl_sa::NbrSet& t)
-{
-	sa->nbr = t.nbr; sa->d_pickrec = t.pickrec; sa->d_pickstate = t.pickstate;
-	sa->big.sim_hdr = t.sim_hdr; sa->big.sim_keys = t.sim_keys; sa->big.sim_pos = t.sim_pos;
-	sa->d_todo = t.todo; sa->d_counts = t.counts;
-	sa->big.todo_in = t.todo; sa->big.todo_in_count = t.counts; sa->big.spill_ctr = t.counts + 2;
-}
 static uint32_t nbr_slices(const mgl_sa* sa)
 {
 	const uint32_t K = sa->cfg.neighbours_per_step;
 	return (sa->halves >= 2 && K >= 1024) ? sa->halves : 1u;
-}
-/* the first two thirds of the split form -- pick, then window walk -- of every slice of a step into the buffer set `t`;
- * slices alternate between the two streams, done[h] is recorded behind slice h's walk */
-static int launch_pick_rest(mgl_sa* sa, const mgl_sa::NbrSet& t, uint64_t step_override, hipStream_t s_even, hipStream_t s_odd, hipEvent_t* done)
-{
-	const uint32_t K = sa->cfg.neighbours_per_step, slices = nbr_slices(sa);
-	BigScratch g = sa->big;
-	g.sim_hdr = t.sim_hdr; g.sim_keys = t.sim_keys; g.sim_pos = t.sim_pos;
-	g.todo_in = t.todo; g.todo_in_count = t.counts; g.spill_ctr = t.counts + 2;
-	for (uint32_t h = 0; h < slices; h++) {
-		const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
-		hipStream_t st = (h & 1u) ? s_odd : s_even;
-		hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_PICK>), dim3((j1 - j0 + sa->pick_waves - 1) / sa->pick_waves), dim3(64 * sa->pick_waves),
-		                   (MGL_PICK_T_GLOBAL ? 0u : 4096u) + sa->pick_waves * sa->per_wave_pick, st, sa->ctx,
-		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, t.nbr, sa->per_wave_pick, t.todo, t.counts,
-		                   (unsigned long long*)nullptr, g, t.pickrec, j0, j1, t.pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICK>");
-		hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_REST>), dim3(j1 - j0), dim3(64), sa->per_wave_rest, st, sa->ctx,
-		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, t.nbr, sa->per_wave_rest, t.todo, t.counts,
-		                   g_prof_big ? (unsigned long long*)nullptr : sa->d_prof, g, t.pickrec, j0, j1, t.pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_REST>");
-		HIPCHK(hipEventRecord(done[h], st));
-	}
-	HIPCHK(hipGetLastError());
-	return MGL_OK;
-}
-/* look-ahead: the NEXT step's pick + window walk, speculatively, into the other buffer set; they start once this step's own
- * walks are through (after_check: once k_la_check has run) and the accept waits for them (launch_apply's caller) */
-static int launch_lookahead(mgl_sa* sa, uint64_t gstep_next, bool after_check)
-{
-	const uint32_t slices = nbr_slices(sa);
-	if (after_check) HIPCHK(hipStreamWaitEvent(sa->stream5, sa->ev_la_check, 0));
-	else for (uint32_t h = 0; h < slices; h++) HIPCHK(hipStreamWaitEvent(sa->stream5, sa->ev_rest[h], 0));
-	HIPCHK(hipMemsetAsync(sa->alt.counts, 0, 8 * sizeof(uint32_t), sa->stream5));
-	HIPCHK(hipEventRecord(sa->ev_la_zero, sa->stream5));
-	HIPCHK(hipStreamWaitEvent(sa->stream6, sa->ev_la_zero, 0));
-	int rc = launch_pick_rest(sa, sa->alt, gstep_next, sa->stream5, sa->stream6, sa->ev_spec);
-	if (rc) return rc;
-	sa->la_ready = true;
-	return MGL_OK;
 }
 /* stratified targets of a step: packets before every block of 4 096 positions of the current walk, their
  * prefix sums, then one wavefront per neighbour turns its ordinal into a position */
@@ -463,12 +398,25 @@ static int launch_targets_ahead(mgl_sa* sa, uint64_t next_gstep)
 	sa->tgt_ahead = 1;
 	return MGL_OK;
 }
-static uint64_t graph_key(const mgl_sa* sa);
-/* the launches of a step's neighbour evaluation on the incremental engine: pick / walk slices on two streams, re-simulations on a
- * third, second pass, last resort (what launch_neighbours queues behind its targets) */
-static int launch_neighbours_body(mgl_sa* sa, uint64_t step_override, bool from_lookahead)
+/* a step's neighbour evaluation: its targets, then on the incremental engine pick / walk slices on two streams, re-simulations
+ * on a third, second pass, last resort */
+static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_counts = true)
 {
 	const uint32_t K = sa->cfg.neighbours_per_step;
+	if (sa->d_strat_pre) {
+		if (sa->tgt_ahead) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_tgt, 0)); /* made beside the previous step's accept (or at least out of the buffers' way) */
+		if (sa->tgt_ahead != 1) launch_targets(sa, sa->stream, step_override);
+		sa->tgt_ahead = 0;
+	}
+	if (!sa->incremental) {
+		const uint32_t blocks = (K + sa->waves_per_block - 1) / sa->waves_per_block;
+		hipLaunchKernelGGL(k_neighbours, dim3(blocks), dim3(64 * sa->waves_per_block), sa->nbr_lds, sa->stream, sa->ctx, sa->base.v,
+		                   (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_bytes,
+		                   (const uint32_t*)nullptr, (const uint32_t*)nullptr); NBR_TRACE("k_neighbours");
+		HIPCHK(hipGetLastError());
+		return MGL_OK;
+	}
+	if (zero_counts) HIPCHK(hipMemsetAsync(sa->d_counts, 0, 8 * sizeof(uint32_t), sa->stream)); /* todo counts + spill slots; k_step_end clears them between steps */
 	const uint32_t blocks2 = (K + sa->waves_per_block2 - 1) / sa->waves_per_block2;
 	const bool split_now = sa->split_nbr && !sa->form_single;
 	const uint32_t sim_lds_regular = ((((sa->ctx.L.total + 31u) >> 5) + 3u) & ~3u) * 4u + sa->chg_cap * 16u;
@@ -477,27 +425,29 @@ static int launch_neighbours_body(mgl_sa* sa, uint64_t step_override, bool from_
 		 * the other slice's kernels keep the CUs busy.  The re-simulation kernels run on a third stream: the second
 		 * pass below needs the walks, not the re-simulations, and its few long-running wavefronts overlap with them. */
 		const uint32_t slices = nbr_slices(sa);
-		if (!from_lookahead) {
-			HIPCHK(hipEventRecord(sa->ev_fork, sa->stream));
-			if (slices >= 2) HIPCHK(hipStreamWaitEvent(sa->stream2, sa->ev_fork, 0));
-			HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_fork, 0));
-			int rc = launch_pick_rest(sa, cur_set(sa), step_override, sa->stream, sa->stream2, sa->ev_rest);
-			if (rc) return rc;
-		} else {
-			/* pick + walk of this step ran ahead, beside the previous step's tail (launch_lookahead): keep what the accepted
-			 * move cannot have touched, evaluate the others again in the one-kernel form (a list, usually short) */
-			HIPCHK(hipMemsetAsync(sa->d_la_hdr, 0, 2 * sizeof(uint32_t), sa->stream));
-			hipLaunchKernelGGL(k_la_check, dim3((K + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, sa->b2, (const Control*)sa->base.ctl, sa->nbr,
-			                   (const uint4*)sa->d_pickstate, sa->big.sim_hdr, (const uint32_t*)sa->d_counts, sa->d_la_mark, sa->d_la_list, sa->d_la_hdr, sa->cfg.seed, K); NBR_TRACE("k_la_check");
-			HIPCHK(hipEventRecord(sa->ev_la_check, sa->stream));
-			HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_la_check, 0));
-			HIPCHK(hipStreamWaitEvent(sa->stream2, sa->ev_la_check, 0));
+		HIPCHK(hipEventRecord(sa->ev_fork, sa->stream));
+		if (slices >= 2) HIPCHK(hipStreamWaitEvent(sa->stream2, sa->ev_fork, 0));
+		HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_fork, 0));
+		/* the first two thirds of the split form -- pick, then window walk -- of every slice; slices alternate between the two
+		 * streams, ev_rest[h] is recorded behind slice h's walk */
+		for (uint32_t h = 0; h < slices; h++) {
+			const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
+			hipStream_t st = (h & 1u) ? sa->stream2 : sa->stream;
+			hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_PICK>), dim3((j1 - j0 + sa->pick_waves - 1) / sa->pick_waves), dim3(64 * sa->pick_waves),
+			                   (MGL_PICK_T_GLOBAL ? 0u : 4096u) + sa->pick_waves * sa->per_wave_pick, st, sa->ctx,
+			                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_pick, sa->d_todo, sa->d_counts,
+			                   (unsigned long long*)nullptr, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICK>");
+			hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_REST>), dim3(j1 - j0), dim3(64), sa->per_wave_rest, st, sa->ctx,
+			                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_rest, sa->d_todo, sa->d_counts,
+			                   g_prof_big ? (unsigned long long*)nullptr : sa->d_prof, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_REST>");
+			HIPCHK(hipEventRecord(sa->ev_rest[h], st));
 		}
+		HIPCHK(hipGetLastError());
 		for (uint32_t h = 0; h < slices; h++) {
 			const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
 			/* the second half's re-simulation, several wavefronts per neighbour; a neighbour with more touched contexts
 			 * than its list holds goes straight to the last resort's list (the second pass may be running by then) */
-			if (!from_lookahead) HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_rest[h], 0));
+			HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_rest[h], 0));
 			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 6 * (size_t)sa->time_sim_step + 2 * h), sa->stream3));
 			if (sa->count_traffic)
 				hipLaunchKernelGGL(k_sim<true>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, sa->stream3, sa->ctx, sa->b2, sa->base.ctl,
@@ -509,18 +459,7 @@ static int launch_neighbours_body(mgl_sa* sa, uint64_t step_override, bool from_
 			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 6 * (size_t)sa->time_sim_step + 2 * h + 1), sa->stream3));
 		}
 		HIPCHK(hipEventRecord(sa->ev_sim, sa->stream3));
-		if (!from_lookahead) {
-			for (uint32_t h = 1; h < slices; h += 2) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_rest[h], 0)); /* the walks of the other stream's slices */
-		} else {
-			BigScratch g = sa->big;
-			g.la_list = sa->d_la_list; g.la_count = sa->d_la_hdr;
-			const uint32_t grid = blocks2 < 4096u ? blocks2 : 4096u; /* strides over the list */
-			/* on the second stream, beside the second pass over the speculative launch's entries; its own entries get a second pass of their own below */
-			hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_FULL, true>), dim3(grid), dim3(64 * sa->waves_per_block2), sa->nbr2_lds, sa->stream2, sa->ctx,
-			                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo, sa->d_counts,
-			                   sa->d_prof, g, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_FULL, true>");
-			HIPCHK(hipEventRecord(sa->ev_redo, sa->stream2));
-		}
+		for (uint32_t h = 1; h < slices; h += 2) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_rest[h], 0)); /* the walks of the other stream's slices */
 	}
 	if (!sa->split_nbr || sa->form_single) { /* the one-kernel form */
 		hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_FULL>), dim3(blocks2), dim3(64 * sa->waves_per_block2), sa->nbr2_lds, sa->stream, sa->ctx,
@@ -535,35 +474,9 @@ static int launch_neighbours_body(mgl_sa* sa, uint64_t step_override, bool from_
 	big_now.lds_cache = 1u;
 	const uint32_t big_lds = sa->nbr2_lds + 12u * MGL_BIG_CAP; /* + a copy of both lists for the re-simulations */
 	if (!split_now || g_big_inline_sim) big_now.sim_hdr2 = nullptr; /* the one-kernel form has no k_sim launch to hand over to */
-	const bool la_step = from_lookahead && split_now;
-	if (la_step) {
-		/* the list-mode instances dereference these unconditionally or behind a test of their partner pointer only (a launch
-		 * of k_neighbours2<true, FULL, true> once faulted on a null address, cause never pinned down: DESIGN.md section 10) */
-		if (!sa->d_la_mark || !sa->d_la_hdr || !sa->d_la_list || !sa->d_todo || !sa->d_todo2 || !sa->d_pickrec || !sa->d_pickstate || !sa->big.ins_key || !sa->big.sim_slot2)
-			return fail(MGL_EDEVICE, "launch_neighbours: look-ahead step without its buffers");
-		/* first the entries the speculative launch made (their count is fixed since k_la_check; the ones evaluated again are passed by) ... */
-		big_now.la_mark = sa->d_la_mark; big_now.la_spec_count = sa->d_la_hdr + 1;
-		big_now.todo_in_count = sa->d_la_hdr + 1;
-	}
-	if (la_step) {
-		hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL, true>), dim3(bigblocks), dim3(64 * sa->waves_per_block2), big_lds, sa->stream, sa->ctx,
-		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
-		                   (unsigned long long*)nullptr, big_now, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL, true>");
-	} else {
-		hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks), dim3(64 * sa->waves_per_block2), big_lds, sa->stream, sa->ctx,
-		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
-		                   g_prof_big ? sa->d_prof : (unsigned long long*)nullptr, big_now, (sa->split_nbr && !sa->form_single) ? sa->d_pickrec : (uint4*)nullptr, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
-	}
-	if (la_step) {
-		/* ... then, once the fresh evaluations are through, the entries they added */
-		HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_redo, 0));
-		big_now.todo_in_count = sa->d_counts;
-		big_now.todo_first = sa->d_la_hdr + 1;
-		hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL, true>), dim3(bigblocks < 256u ? bigblocks : 256u), dim3(64 * sa->waves_per_block2), big_lds, sa->stream, sa->ctx,
-		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
-		                   (unsigned long long*)nullptr, big_now, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL, true>");
-		big_now.todo_first = nullptr;
-	}
+	hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks), dim3(64 * sa->waves_per_block2), big_lds, sa->stream, sa->ctx,
+	                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
+	                   g_prof_big ? sa->d_prof : (unsigned long long*)nullptr, big_now, (sa->split_nbr && !sa->form_single) ? sa->d_pickrec : (uint4*)nullptr, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
 	if (split_now) {
 		/* the second pass handed its final re-simulations to k_sim as well (headers in sim_hdr2): a small grid over its list */
 		const uint32_t sim_lds = ((((sa->ctx.L.total + 31u) >> 5) + 3u) & ~3u) * 4u + MGL_SIM2_CAP * 16u;
@@ -592,59 +505,6 @@ static int launch_neighbours_body(mgl_sa* sa, uint64_t step_override, bool from_
 	                   (const uint32_t*)sa->d_todo2, (const uint32_t*)(sa->d_counts + 1)); NBR_TRACE("k_neighbours");
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
-}
-
-static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_counts = true, bool from_lookahead = false)
-{
-	const uint32_t K = sa->cfg.neighbours_per_step;
-	if (sa->d_strat_pre) {
-		if (sa->tgt_ahead) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_tgt, 0)); /* made beside the previous step's accept (or at least out of the buffers' way) */
-		if (sa->tgt_ahead != 1) launch_targets(sa, sa->stream, step_override);
-		sa->tgt_ahead = 0;
-	}
-	if (!sa->incremental) {
-		const uint32_t blocks = (K + sa->waves_per_block - 1) / sa->waves_per_block;
-		hipLaunchKernelGGL(k_neighbours, dim3(blocks), dim3(64 * sa->waves_per_block), sa->nbr_lds, sa->stream, sa->ctx, sa->base.v,
-		                   (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_bytes,
-		                   (const uint32_t*)nullptr, (const uint32_t*)nullptr); NBR_TRACE("k_neighbours");
-		HIPCHK(hipGetLastError());
-		return MGL_OK;
-	}
-	if (zero_counts) HIPCHK(hipMemsetAsync(sa->d_counts, 0, 8 * sizeof(uint32_t), sa->stream)); /* todo counts + spill slots; k_step_end clears them between steps */
-	/* The launches of a step are the same from step to step (the kernels read the step's number from the control block): captured
-	 * once as a graph -- three streams, their events -- and replayed, unless something about them changed (the launch form, a
-	 * buffer, a diagnostic) or the step is a timed or traced one. */
-	if (sa->graph_ok && step_override == ~0ull && !from_lookahead && !sa->la_enabled && sa->time_sim_step < 0 && !sa->count_traffic && !g_trace && !g_prof_big && sa->d_prof == nullptr) {
-		const uint64_t key = graph_key(sa);
-		if (sa->nbr_graph_exec == nullptr || key != sa->nbr_graph_key) {
-			if (sa->nbr_graph_exec) { (void)hipGraphExecDestroy(sa->nbr_graph_exec); sa->nbr_graph_exec = nullptr; }
-			if (sa->nbr_graph) { (void)hipGraphDestroy(sa->nbr_graph); sa->nbr_graph = nullptr; }
-			HIPCHK(hipStreamBeginCapture(sa->stream, hipStreamCaptureModeRelaxed));
-			const int rc = launch_neighbours_body(sa, ~0ull, false);
-			const hipError_t ec = hipStreamEndCapture(sa->stream, &sa->nbr_graph);
-			if (rc) return rc;
-			if (ec != hipSuccess || sa->nbr_graph == nullptr) return fail(MGL_EDEVICE, "launch_neighbours: graph capture failed");
-			HIPCHK(hipGraphInstantiate(&sa->nbr_graph_exec, sa->nbr_graph, nullptr, nullptr, 0));
-			sa->nbr_graph_key = key;
-		}
-		HIPCHK(hipGraphLaunch(sa->nbr_graph_exec, sa->stream));
-		return MGL_OK;
-	}
-	return launch_neighbours_body(sa, step_override, from_lookahead);
-}
-
-/* everything a step's neighbour launches are made of: a captured graph is good while this stays what it was */
-static uint64_t graph_key(const mgl_sa* sa)
-{
-	uint64_t h = 1469598103934665603ull;
-	auto mix = [&](const void* p, size_t n) { const unsigned char* c = (const unsigned char*)p; for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ull; } };
-	mix(&sa->ctx, sizeof sa->ctx); mix(&sa->b2, sizeof sa->b2); mix(&sa->base, sizeof sa->base); mix(&sa->nbr, sizeof sa->nbr); mix(&sa->big, sizeof sa->big);
-	const uint64_t w[] = { sa->cfg.neighbours_per_step, sa->cfg.seed, (uint64_t)sa->form_single, (uint64_t)sa->split_nbr, sa->halves, sa->waves_per_block, sa->waves_per_block2,
-	                       sa->pick_waves, sa->per_wave_pick, sa->per_wave_rest, sa->per_wave2, sa->per_wave_bytes, sa->nbr_lds, sa->nbr2_lds, sa->chg_cap, sa->sim_waves,
-	                       (uint64_t)(uintptr_t)sa->d_todo, (uint64_t)(uintptr_t)sa->d_todo2, (uint64_t)(uintptr_t)sa->d_todo3, (uint64_t)(uintptr_t)sa->d_counts,
-	                       (uint64_t)(uintptr_t)sa->d_pickrec, (uint64_t)(uintptr_t)sa->d_pickstate, (uint64_t)g_big_inline_sim };
-	mix(w, sizeof w);
-	return h;
 }
 
 static int import_slab(mgl_sa* sa, const mgl_packet* packets, mgl_pk* d_slab)
@@ -682,18 +542,6 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 	free_b2(sa->snap_lit, true); free_b2(sa->snap_best, true); dfree(sa->d_snap_meta);
 	dfree(sa->pb.exits); dfree(sa->pb.entry); dfree(sa->pb.gexits); dfree(sa->pb.gentry); dfree(sa->pb.gsum); dfree(sa->pb.ch_map); dfree(sa->pb.ch_vs); dfree(sa->pb.ch_pk); dfree(sa->pb.ch_state); dfree(sa->pb.tf_ctx); dfree(sa->pb.tf_dist); dfree(sa->pb.tf_pk);
 	dfree(sa->pb.st_in); dfree(sa->pb.hist); dfree(sa->pb.stage); dfree(sa->pb.stage_n); dfree(sa->pb.stage_over); dfree(sa->pb.acc); dfree(sa->pb.seg_off); dfree(sa->pb.unres);
-	{
-		mgl_sa::NbrSet& t = sa->alt;
-		dfree(t.nbr.cost); dfree(t.nbr.ndiffs); dfree(t.nbr.walked); dfree(t.nbr.win); dfree(t.nbr.win2); dfree(t.nbr.dpos); dfree(t.nbr.dold); dfree(t.nbr.dnew);
-		dfree(t.pickrec); dfree(t.pickstate); dfree(t.sim_hdr); dfree(t.sim_keys); dfree(t.sim_pos); dfree(t.todo); dfree(t.counts);
-		dfree(sa->d_la_mark); dfree(sa->d_la_list); dfree(sa->d_la_hdr);
-		if (sa->stream5) (void)hipStreamDestroy(sa->stream5);
-		if (sa->stream6) (void)hipStreamDestroy(sa->stream6);
-		if (sa->ev_la_check) (void)hipEventDestroy(sa->ev_la_check);
-		if (sa->ev_la_zero) (void)hipEventDestroy(sa->ev_la_zero);
-		if (sa->ev_redo) (void)hipEventDestroy(sa->ev_redo);
-		for (int i = 0; i < 8; i++) if (sa->ev_spec[i]) (void)hipEventDestroy(sa->ev_spec[i]);
-	}
 	dfree(sa->d_todo); dfree(sa->d_prof);
 	dfree(sa->big.sim_hdr); dfree(sa->big.sim_keys); dfree(sa->big.sim_pos);
 	dfree(sa->big.ins_key); dfree(sa->big.rem_key); dfree(sa->big.ins_pos); dfree(sa->big.rem_pos); dfree(sa->big.uctx);
@@ -721,8 +569,6 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 	for (auto& e : sa->ev_rest) if (e) (void)hipEventDestroy(e);
 	if (sa->ev_sim) (void)hipEventDestroy(sa->ev_sim);
 	if (sa->ev_val) (void)hipEventDestroy(sa->ev_val);
-	if (sa->nbr_graph_exec) (void)hipGraphExecDestroy(sa->nbr_graph_exec);
-	if (sa->nbr_graph) (void)hipGraphDestroy(sa->nbr_graph);
 	if (sa->ev_fork) (void)hipEventDestroy(sa->ev_fork);
 	if (sa->ev_tgt) (void)hipEventDestroy(sa->ev_tgt);
 	if (sa->ev_tgt_go) (void)hipEventDestroy(sa->ev_tgt_go);
@@ -745,7 +591,6 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 	HIPCHK(hipEventCreateWithFlags(&sa->ev_sim, hipEventDisableTiming));
 	HIPCHK(hipEventCreateWithFlags(&sa->ev_val, hipEventDisableTiming));
 	/* measured: + 8 % on the 10 MB input, nothing on the 100 KB one (its kernels are too short to overlap) */
-	sa->graph_ok = getenv("MGL_GRAPH") != nullptr;
 	sa->halves = getenv("MGL_HALVES") ? (uint32_t)atoi(getenv("MGL_HALVES")) : (n > (1u << 20) ? 2u : 1u);
 	if (sa->halves < 1 || sa->halves > 8) sa->halves = 1;
 	HIPCHK(hipEventCreate(&sa->ev_begin));
@@ -1084,11 +929,9 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		HIPCHK(hipMemset(sa->d_todo3, 0, sizeof(uint32_t) * (K + 1)));
 		sa->big.todo_in = sa->d_todo; sa->big.todo_in_count = sa->d_counts; sa->big.spill_ctr = sa->d_counts + 2;
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_REST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sa->nbr2_lds + 12u * MGL_BIG_CAP)));
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sa->nbr2_lds + 12u * MGL_BIG_CAP)));
 		HIPCHK(hipMalloc(&sa->d_pickrec, sizeof(uint4) * K));
 		HIPCHK(hipMalloc(&sa->d_pickstate, sizeof(uint4) * 2 * K));
 		sa->split_nbr = getenv("MGL_NO_SPLIT") == nullptr;
@@ -1102,52 +945,10 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 			HIPCHK(hipMalloc(&g.sim_hdr2, sizeof(uint4) * (size_t)K));
 			HIPCHK(hipMalloc(&g.sim_slot2, sizeof(uint32_t) * (size_t)K));
 			HIPCHK(hipMemset(g.sim_hdr2, 0xFF, sizeof(uint4) * (size_t)K));
-			/* continuation records: the second half saves a walk that stops at a repair pick, the second pass resumes it
-			 * (not beside the look-ahead, whose speculative launch would write the slots the running second pass reads) */
-			if (getenv("MGL_NO_CONT") == nullptr && getenv("MGL_LOOKAHEAD") == nullptr) {
+			/* continuation records: the second half saves a walk that stops at a repair pick, the second pass resumes it */
+			if (getenv("MGL_NO_CONT") == nullptr) {
 				HIPCHK(hipMalloc(&g.cont, sizeof(uint32_t) * MGL_CONT_WORDS * (size_t)g.slots));
 				HIPCHK(hipMemset(g.cont, 0, sizeof(uint32_t) * MGL_CONT_WORDS * (size_t)g.slots));
-			}
-			/* look-ahead: a second set of everything pick + walk write, the check's list and marks, two more streams */
-			/* Opt-in (MGL_LOOKAHEAD=1): exact (tests/test_gpu_parity.py runs it against the plain order), but slower on MI355X as
-			 * measured (c3: 1.58 ms per step against 1.37, profiles/r02_lookahead_c3.txt): the pick kernel is bound by LDS capacity
-			 * and the re-simulations by the memory system, so kernels running beside each other take their time from each other. */
-			sa->la_enabled = sa->incremental_apply && getenv("MGL_LOOKAHEAD") != nullptr;
-			if (sa->la_enabled) {
-				mgl_sa::NbrSet& t = sa->alt;
-				HIPCHK(hipMalloc(&t.nbr.cost, sizeof(uint64_t) * K));
-				HIPCHK(hipMalloc(&t.nbr.ndiffs, sizeof(uint32_t) * K));
-				HIPCHK(hipMalloc(&t.nbr.walked, sizeof(uint32_t) * K));
-				HIPCHK(hipMalloc(&t.nbr.win, sizeof(uint32_t) * 2 * K));
-				HIPCHK(hipMemset(t.nbr.win, 0xFF, sizeof(uint32_t) * 2 * K));
-				HIPCHK(hipMalloc(&t.nbr.win2, sizeof(uint32_t) * K));
-				HIPCHK(hipMemset(t.nbr.win2, 0xFF, sizeof(uint32_t) * K));
-				HIPCHK(hipMalloc(&t.nbr.dpos, sizeof(uint32_t) * K * MGL_MAX_DIFFS));
-				HIPCHK(hipMalloc(&t.nbr.dold, sizeof(mgl_pk) * K * MGL_MAX_DIFFS));
-				HIPCHK(hipMalloc(&t.nbr.dnew, sizeof(mgl_pk) * K * MGL_MAX_DIFFS));
-				HIPCHK(hipMalloc(&t.pickrec, sizeof(uint4) * K));
-				HIPCHK(hipMalloc(&t.pickstate, sizeof(uint4) * 2 * K));
-				HIPCHK(hipMalloc(&t.sim_hdr, sizeof(uint4) * (size_t)K));
-				HIPCHK(hipMemset(t.sim_hdr, 0xFF, sizeof(uint4) * (size_t)K));
-				HIPCHK(hipMalloc(&t.sim_keys, sizeof(uint16_t) * 2u * sa->chg_cap * (size_t)K));
-				HIPCHK(hipMalloc(&t.sim_pos, sizeof(uint32_t) * 2u * sa->chg_cap * (size_t)K));
-				HIPCHK(hipMalloc(&t.todo, sizeof(uint32_t) * (K + 1)));
-				HIPCHK(hipMemset(t.todo, 0, sizeof(uint32_t) * (K + 1)));
-				HIPCHK(hipMalloc(&t.counts, sizeof(uint32_t) * 16));
-				HIPCHK(hipMemset(t.counts, 0, sizeof(uint32_t) * 16));
-				HIPCHK(hipMalloc(&sa->d_la_mark, K));
-				HIPCHK(hipMemset(sa->d_la_mark, 0, K));
-				HIPCHK(hipMalloc(&sa->d_la_list, sizeof(uint32_t) * K));
-				HIPCHK(hipMalloc(&sa->d_la_hdr, sizeof(uint32_t) * 2));
-				HIPCHK(hipMemset(sa->d_la_hdr, 0, sizeof(uint32_t) * 2));
-				int plo = 0, phi = 0;
-				HIPCHK(hipDeviceGetStreamPriorityRange(&plo, &phi));
-				HIPCHK(hipStreamCreateWithPriority(&sa->stream5, hipStreamDefault, plo));
-				HIPCHK(hipStreamCreateWithPriority(&sa->stream6, hipStreamDefault, plo));
-				HIPCHK(hipEventCreateWithFlags(&sa->ev_redo, hipEventDisableTiming));
-				HIPCHK(hipEventCreateWithFlags(&sa->ev_la_check, hipEventDisableTiming));
-				HIPCHK(hipEventCreateWithFlags(&sa->ev_la_zero, hipEventDisableTiming));
-				for (int i = 0; i < 8; i++) HIPCHK(hipEventCreateWithFlags(&sa->ev_spec[i], hipEventDisableTiming));
 			}
 		}
 		if (getenv("MGL_SIMW")) { const int w = atoi(getenv("MGL_SIMW")); if (w == 1 || w == 2 || w == 4 || w == 8) sa->sim_waves = (uint32_t)w; }
@@ -1180,9 +981,8 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		HIPCHK(hipFuncSetAttribute((const void*)k_build_end, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->build_lds));
 	}
 
-	/* targets: stratified by packet ordinal (default), or position draws (MGL_F_POSITION_TARGETS; the look-ahead needs them:
-	 * it keeps speculative results whose target draw lands on the same position after the accept) */
-	if (!(sa->cfg.flags & MGL_F_POSITION_TARGETS) && !sa->la_enabled && getenv("MGL_POSITION_TARGETS") == nullptr) { /* (the environment switch: A/B runs) */
+	/* targets: stratified by packet ordinal (default), or position draws (MGL_F_POSITION_TARGETS) */
+	if (!(sa->cfg.flags & MGL_F_POSITION_TARGETS)) {
 		sa->ctx.strat_nblk = (uint32_t)((n + 4095u) / 4096u);
 		HIPCHK(hipMalloc(&sa->d_strat_pre, sizeof(uint32_t) * (sa->ctx.strat_nblk + 2u)));
 		HIPCHK(hipMemset(sa->d_strat_pre, 0, sizeof(uint32_t) * (sa->ctx.strat_nblk + 2u)));
@@ -1712,9 +1512,7 @@ extern "C" int mgl_sa_run(mgl_sa* sa, uint64_t steps, mgl_sa_stats* stats)
 	const DecideArgs dargs = decide_args(sa);
 	const int mode = (sa->incremental && sa->parallel_build) ? sa->accept_mode : MGL_ACCEPT_SINGLE; /* bulk steps rebuild with the parallel builder */
 	sa->mode_log.clear();
-	sa->la_ready = false;
 	if (sa->tgt_ahead) sa->tgt_ahead = 2; /* (only behind a run that ended early: whatever was queued is not trusted) */
-	const bool la_ok = sa->la_enabled && inc_apply && sa->split_nbr && sa->ctx.diag_stop == 0;
 	const uint64_t rollbacks_before = sa->bulk_rollbacks;
 	std::vector<uint8_t> sim_timed; /* per timed step: how many of the regular k_sim launches carry events (0: none, the one-kernel form ran) */
 	unsigned long long traffic_before[2] = { 0, 0 };
@@ -1736,20 +1534,11 @@ extern "C" int mgl_sa_run(mgl_sa* sa, uint64_t steps, mgl_sa_stats* stats)
 			const uint64_t ti = s / t_stride; /* the step's place among the timed ones */
 			if (sa->mode_log.size() < (1u << 20)) sa->mode_log.push_back(bulk ? 1 : 0);
 			if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 0), sa->stream));
-			/* look-ahead: this step's pick + walk may have run beside the previous step's tail, into the other buffer set */
-			const bool from_la = sa->la_ready;
-			if (from_la) {
-				const mgl_sa::NbrSet now = cur_set(sa);
-				use_set(sa, sa->alt);
-				sa->alt = now;
-				sa->la_ready = false;
-			}
-			sa->time_sim_step = (t && sa->split_nbr && !sa->form_single && !from_la) ? (int64_t)ti : -1;
+			sa->time_sim_step = (t && sa->split_nbr && !sa->form_single) ? (int64_t)ti : -1;
 			if (t) sim_timed.push_back(sa->time_sim_step >= 0 ? (nbr_slices(sa) < 2u ? 1 : 2) : 0);
-			rc = launch_neighbours(sa, ~0ull, (s == 0 && !from_la) || !inc_apply, from_la);
+			rc = launch_neighbours(sa, ~0ull, s == 0 || !inc_apply);
 			sa->time_sim_step = -1;
 			if (rc) return rc;
-			if (la_ok && !bulk && !sa->form_single && s + 1 < e && (rc = launch_lookahead(sa, before.gstep + s + 1, from_la))) return rc;
 			if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 1), sa->stream));
 			if (bulk) {
 				if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 2), sa->stream));
@@ -1761,8 +1550,6 @@ extern "C" int mgl_sa_run(mgl_sa* sa, uint64_t steps, mgl_sa_stats* stats)
 			HIPCHK(hipGetLastError());
 			if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 2), sa->stream));
 			if (inc_apply) {
-				/* the accept changes the base: the speculative pick + walk of the next step read it until they are through */
-				if (sa->la_ready) for (uint32_t h = 0; h < nbr_slices(sa); h++) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_spec[h], 0));
 				if ((rc = launch_apply(sa, s + 1 < steps ? before.gstep + s + 1 : ~0ull))) return rc;
 			} else {
 				hipLaunchKernelGGL(k_copy_best, dim3(256), dim3(256), 0, sa->stream, (const Control*)sa->base.ctl,

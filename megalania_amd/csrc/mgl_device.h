@@ -108,8 +108,6 @@ struct Control {
 	uint32_t taken;          /* neighbours the last step took */
 	uint32_t bulk_was_best;  /* bulk step: the base held the best slab's structures when the step began */
 	uint32_t bulk_need_undo; /* bulk step: the best slab has to be restored from the new one + the undo log */
-	uint32_t la_lo, la_end;  /* window of the move the last step accepted (la_lo = MGL_POS_INF: none) */
-	uint32_t mod_lo, mod_hi; /* the last accepted move changed some context's probability before positions in (mod_lo, mod_hi] (MGL_POS_INF: to the end) */
 	uint64_t bulk_overlaps;  /* slab entries two taken journals of one bulk step both wanted to change (k_bulk_round; such a step is taken back) */
 };
 #define MGL_ERR_REBUILD_MISMATCH 1u

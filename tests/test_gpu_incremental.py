@@ -375,32 +375,6 @@ def test_parallel_build_serial_segment_path():
     a.close()
 
 
-def test_graph_replay_gives_the_same_trajectory(monkeypatch):
-    """MGL_GRAPH=1 (opt-in): a step's neighbour launches -- three streams, their events -- are captured once as a HIP graph
-    and replayed while nothing about them changes (launch form, buffers): same trajectory as the eager launches, in single
-    and in bulk steps, through switches of the launch form (c2's early repair bursts) and across mgl_sa_run calls."""
-    data, _ = corpus.config_input("c2")
-    K = 4096
-    monkeypatch.delenv("MGL_GRAPH", raising=False)
-    eager = binding.SA(data, accept="auto", neighbours_per_step=K, seed=31)
-    monkeypatch.setenv("MGL_GRAPH", "1")
-    graph = binding.SA(data, accept="auto", neighbours_per_step=K, seed=31)
-    monkeypatch.delenv("MGL_GRAPH")
-    for chunk in (1, 7, 40, 64, 3, 90):
-        a, b = eager.run(chunk), graph.run(chunk)
-        for k in ("evaluations", "accepted", "current_cost", "best_cost", "packets", "failed", "bulk_steps"):
-            assert a[k] == b[k], (chunk, k)
-    for x in (eager, graph):
-        x.set_accept_mode("single")
-    for chunk in (5, 70, 20):
-        a, b = eager.run(chunk), graph.run(chunk)
-        for k in ("evaluations", "accepted", "current_cost", "best_cost", "packets", "failed"):
-            assert a[k] == b[k], (chunk, k)
-    ca, cb = eager.current(), graph.current()
-    assert ca[1] == cb[1] and (ca[0] == cb[0]).all()
-    eager.close(); graph.close()
-
-
 def test_launch_forms_give_one_trajectory(monkeypatch):
     """The neighbour evaluation runs as two launches (pick + rest, with a second pass), as one kernel,
     or switches between them on the device (k_step_end): same costs for every neighbour, same
@@ -431,40 +405,6 @@ def test_launch_forms_give_one_trajectory(monkeypatch):
     assert (a == c).all() and (b == c).all()
     for x in (adaptive, split, single):
         x.close()
-
-
-@pytest.mark.parametrize("name,size,K,cap", [("lorem", 4096, 64, 0), ("enwik", 200000, 2048, 0), ("enwik_small_lists", 60000, 1024, 16)])
-def test_look_ahead_gives_the_same_trajectory(monkeypatch, name, size, K, cap):
-    """MGL_LOOKAHEAD=1 (opt-in): the next step's pick + window walk run beside this step's tail on the base as it is before
-    the accept; k_la_check keeps what the accepted move cannot have touched and has the rest evaluated again.  Whatever is
-    kept or redone, the chain must be the one the plain order produces: same statistics block by block (look-ahead works
-    inside a mgl_sa_run call), same slab -- also with the first-pass lists shrunk so that the second pass sees entries from
-    both the speculative launch and the fresh evaluations."""
-    data = corpus.lorem(size) if name == "lorem" else corpus.enwik_like(size, 0x4C41)
-    monkeypatch.setenv("MGL_NO_ADAPT", "1")  # the split form throughout: look-ahead only exists there
-    monkeypatch.delenv("MGL_LOOKAHEAD", raising=False)
-    # (the look-ahead draws targets as positions -- it keeps the speculative results whose draw lands on the same position after
-    # the accept --, so the plain chain it is compared with is given the same rule)
-    plain = binding.SA(data, accept="single", neighbours_per_step=K, seed=77, iters_per_epoch=10**7, flags=binding.F_POSITION_TARGETS)
-    monkeypatch.setenv("MGL_LOOKAHEAD", "1")
-    ahead = binding.SA(data, accept="single", neighbours_per_step=K, seed=77, iters_per_epoch=10**7)
-    monkeypatch.delenv("MGL_LOOKAHEAD")
-    if cap:
-        for x in (plain, ahead):
-            assert x.L.mgl_debug_set(x.h, 2, cap) == 0
-    accepted = 0
-    for chunk in (1, 2, 3, 8, 30, 64, 70):
-        a, b = plain.run(chunk), ahead.run(chunk)
-        for k in ("evaluations", "accepted", "improved", "current_cost", "best_cost", "packets", "failed", "dropped_neighbours"):
-            assert a[k] == b[k], (chunk, k)
-        accepted += a["accepted"]
-    ca, _ = plain.current()
-    cb, _ = ahead.current()
-    assert (ca == cb).all() and accepted > 20
-    o = Oracle(data, dict_limit=0x400000)
-    assert ahead.current()[1] == o.cost_slab(cb.astype(literal_slab(1).dtype))["total"]
-    plain.close()
-    ahead.close()
 
 
 def test_second_pass_takes_what_overflows_small_lists():

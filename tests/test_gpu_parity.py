@@ -134,19 +134,22 @@ def test_neighbours_bit_exact_vs_oracle(name, fullwalk, golden, golden_input):
             _check_neighbours(sa, o, base, seed, step, K)
 
 
-@pytest.mark.parametrize("fullwalk,accept", [(False, "single"), (True, "single"), (False, "bulk"), (False, "auto")],
-                         ids=["incremental-single", "fullwalk-single", "bulk", "auto"])
-def test_sa_run_trajectory_vs_oracle(fullwalk, accept):
+@pytest.mark.parametrize("fullwalk,accept,positions", [(False, "single", False), (True, "single", False), (False, "bulk", False), (False, "auto", False),
+                                                       (False, "single", True), (False, "bulk", True)],
+                         ids=["incremental-single", "fullwalk-single", "bulk", "auto", "incremental-single-positions", "bulk-positions"])
+def test_sa_run_trajectory_vs_oracle(fullwalk, accept, positions):
     """mgl_sa_run against orc_sa_batched: same accept decisions, same current/best cost every step, same
     final slabs; the stream decodes.  Single steps take the best acceptable neighbour, bulk steps every
     acceptable neighbour that is the best of its window; "auto" is a run of both, replayed in the oracle
-    with the modes the library chose."""
+    with the modes the library chose.  The "positions" cases draw targets as positions
+    (MGL_F_POSITION_TARGETS) instead of stratified by packet ordinal, on both sides."""
     data = corpus.lorem(1800)
     n = len(data)
     K, seed, steps = 48, 1673551, 60
     ipe = steps * K  # evaluations per epoch: neighbour j of in-epoch step s is the reference's iteration s K + j
-    sa = binding.SA(data, accept=accept, bulk_threshold=6, neighbours_per_step=K, seed=seed, iters_per_epoch=ipe, fullwalk=fullwalk)
-    o = Oracle(data, dict_limit=0x400000)
+    sa = binding.SA(data, accept=accept, bulk_threshold=6, neighbours_per_step=K, seed=seed, iters_per_epoch=ipe, fullwalk=fullwalk,
+                    flags=binding.F_POSITION_TARGETS if positions else 0)
+    o = Oracle(data, dict_limit=0x400000, position_targets=positions)
     slab, best = literal_slab(n), literal_slab(n)
     evals = dropped = 0
     if accept == "auto":
