@@ -23,6 +23,8 @@
  *   mgl_top_k         top_k_packet_finder_find/pop (top_k_packet_finder.c:120-138)
  *   mgl_substrings    substring_enumerator_for_each (substring_enumerator.c:85-105)
  *   mgl_sa_destroy    main.c:107-108,121 the matching frees
+ *   mgl_props_sweep   no reference counterpart (lc = lp = pb = 0 are fixed there, main.c:45): one parse costed
+ *                                    under every supported lc/lp/pb at once
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -253,6 +255,14 @@ int mgl_sa_best(mgl_sa* sa, mgl_packet* packets_out, uint64_t* perplexity_out);
  * total per walked packet; npackets (nullable) their number. */
 int mgl_cost_slab(mgl_sa* sa, const mgl_packet* packets, uint64_t* total,
                   uint64_t* per_packet_cumulative, size_t* npackets);
+/* Exact cost of one parse under every supported lc/lp/pb (no reference counterpart; DESIGN.md section 10,
+ * megalania_amd/csrc/mgl_props.hip): the triples mgl_sa_create accepts, lc + lp <= 4 and pb <= 4, in the canonical
+ * order `for lc in 0..4: for lp in 0..4-lc: for pb in 0..4`.  out[t].cost is what mgl_cost_slab returns for the same
+ * slab on a handle created with out[t].props, and the call refuses exactly the slabs mgl_cost_slab refuses.
+ * packets == NULL: the current slab.  cap < 75: MGL_ERANGE, *count = 75.  gpu_ms (nullable): device time of the sweep. */
+#define MGL_PROPS_TRIPLES 75
+typedef struct { mgl_properties props; uint64_t cost; } mgl_props_cost;
+int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_cost* out, size_t cap, size_t* count, double* gpu_ms);
 /* Final model state after costing `packets`: probabilities in the reference's struct order
  * (lzma_state.h:47-53: lit | len | rep_len | dist | ctx_state), ctx_state, rep distances. */
 int mgl_final_state(mgl_sa* sa, const mgl_packet* packets, uint16_t* probs_out, size_t probs_cap,

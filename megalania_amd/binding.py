@@ -35,7 +35,7 @@ HIP_SYMBOLS = [
     "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
     "mgl_substrings", "mgl_neighbours", "mgl_rng_draw_at", "mgl_debug_dump", "mgl_debug_set",
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
-    "mgl_sa_best_packed", "mgl_sa_adopt_best_packed",
+    "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep",
 ]
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
@@ -43,6 +43,15 @@ HOST_SYMBOLS = [
     "mgl_memory_output_new", "mgl_emit_stream", "mgl_stream_info_read", "mgl_stream_import",
 ]
 IMPORT_CLIP_WINDOW = 1
+# the lc/lp/pb triples mgl_sa_create accepts, in the order mgl_props_sweep reports them
+PROPS_TRIPLES = [(lc, lp, pb) for lc in range(5) for lp in range(5 - lc) for pb in range(5)]
+
+
+def best_props(costs):
+    """The cheapest triple of a props_sweep table; among equals the first in canonical order (0/0/0 beats 1/0/0 on text)."""
+    costs = [int(c) for c in costs]
+    assert len(costs) == len(PROPS_TRIPLES)
+    return PROPS_TRIPLES[costs.index(min(costs))]
 CONTAINER_LZMA, CONTAINER_XZ = 1, 2
 
 
@@ -89,6 +98,10 @@ class OptimalStats(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("best_pass", C.c_uint32), ("greedy_cost", C.c_uint64),
                 ("cost", C.c_uint64 * OPT_MAX_PASSES), ("objective", C.c_uint64 * OPT_MAX_PASSES),
                 ("ms", C.c_double * OPT_MAX_PASSES)]
+
+
+class PropsCost(C.Structure):
+    _fields_ = [("props", Properties), ("cost", C.c_uint64)]
 
 
 class StreamInfo(C.Structure):
@@ -143,6 +156,8 @@ def hip_lib():
         L.mgl_sa_current.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.mgl_sa_best.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.mgl_cost_slab.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_size_t)]
+        L.mgl_props_sweep.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PropsCost), C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_double)]
         L.mgl_final_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_void_p]
         L.mgl_top_k.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
         L.mgl_substrings.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -286,7 +301,7 @@ class SA:
 
     def _chk(self, rc):
         if rc != 0:
-            raise MglError(f"rc={rc}: {self.L.mgl_last_error().decode()}")
+            raise MglError(f"rc={rc}: {self.L.mgl_last_error().decode()}", rc=rc)
 
     def begin_epoch(self, phase=0, from_best=False):
         self._chk(self.L.mgl_sa_begin_epoch(self.h, phase, int(from_best)))
@@ -387,6 +402,18 @@ class SA:
         cum = np.zeros(self.n, dtype=np.uint64) if want_cum else None
         self._chk(self.L.mgl_cost_slab(self.h, _ptr(slab), C.byref(total), _ptr(cum), C.byref(npk)))
         return dict(total=total.value, npackets=npk.value, cum=None if cum is None else cum[: npk.value].copy())
+
+    def props_sweep(self, slab=None):
+        """Exact cost of `slab` (None: the current slab) under every triple of PROPS_TRIPLES, whatever the handle's own
+        (mgl_props_sweep; SA state untouched).  Returns (75 uint64 costs in canonical order, device ms of the sweep)."""
+        if slab is not None:
+            slab = np.ascontiguousarray(slab, dtype=PACKET)
+        out = (PropsCost * len(PROPS_TRIPLES))()
+        cnt, ms = C.c_size_t(0), C.c_double(0)
+        self._chk(self.L.mgl_props_sweep(self.h, _ptr(slab), out, len(out), C.byref(cnt), C.byref(ms)))
+        assert cnt.value == len(PROPS_TRIPLES)
+        assert [(e.props.lc, e.props.lp, e.props.pb) for e in out] == PROPS_TRIPLES
+        return np.array([e.cost for e in out], dtype=np.uint64), ms.value
 
     def final_state(self, slab):
         slab = np.ascontiguousarray(slab, dtype=PACKET)

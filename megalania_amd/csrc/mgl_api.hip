@@ -10,6 +10,7 @@
 #include "mgl_pbuild.hip"
 #include "mgl_index.hip"
 #include "mgl_optimal.hip"
+#include "mgl_props.hip"
 #include "../../include/megalania_hip.h"
 
 #include <math.h>
@@ -1693,6 +1694,48 @@ extern "C" int mgl_cost_slab(mgl_sa* sa, const mgl_packet* packets, uint64_t* to
 	if (npackets) *npackets = (size_t)c.packets;
 	if (per_packet_cumulative)
 		HIPCHK(hipMemcpy(per_packet_cumulative, sa->d_cum, sizeof(uint64_t) * (size_t)c.packets, hipMemcpyDeviceToHost));
+	return MGL_OK;
+}
+
+/* The exact cost of one parse under every supported lc/lp/pb (mgl_props.hip).  Validity is decided here, once, by the walk
+ * mgl_cost_slab uses; the current slab (packets == NULL) is a valid parse by construction and is read where it lies. */
+extern "C" int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_cost* out, size_t cap, size_t* count, double* gpu_ms)
+{
+	static_assert(MGL_PROPS_TRIPLES == MGL_PROPS_NTRIPLES, "header and kernel disagree on the number of triples");
+	if (!sa || !out) return fail(MGL_EINVAL, "null argument");
+	if (count) *count = MGL_PROPS_TRIPLES;
+	if (cap < MGL_PROPS_TRIPLES) return fail(MGL_ERANGE, "mgl_props_sweep: out holds fewer than 75 entries");
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* slab = sa->base.v.slab;
+	if (packets) {
+		Control c;
+		int rc = scratch_walk(sa, packets, false, false, &c);
+		if (rc) return rc;
+		slab = sa->scratch.v.slab;
+	}
+	struct Tmp {
+		uint64_t* d = nullptr;
+		hipEvent_t t0 = nullptr, t1 = nullptr;
+		~Tmp() { dfree(d); if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
+	} tmp;
+	HIPCHK(hipMalloc(&tmp.d, sizeof(uint64_t) * MGL_PROPS_TRIPLES));
+	HIPCHK(hipEventCreate(&tmp.t0));
+	HIPCHK(hipEventCreate(&tmp.t1));
+	HIPCHK(hipEventRecord(tmp.t0, sa->stream));
+	hipLaunchKernelGGL(k_props_sweep, dim3(MGL_PROPS_TRIPLES), dim3(64), 0, sa->stream, sa->ctx, slab, tmp.d);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(tmp.t1, sa->stream));
+	uint64_t costs[MGL_PROPS_TRIPLES];
+	HIPCHK(hipMemcpyAsync(costs, tmp.d, sizeof costs, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, tmp.t0, tmp.t1));
+	if (gpu_ms) *gpu_ms = ms;
+	for (uint32_t t = 0; t < MGL_PROPS_TRIPLES; t++) {
+		const mgl_layout L = mgl_props_triple(t);
+		out[t].props.lc = (uint8_t)L.lc; out[t].props.lp = (uint8_t)L.lp; out[t].props.pb = (uint8_t)L.pb;
+		out[t].cost = costs[t];
+	}
 	return MGL_OK;
 }
 

@@ -26,7 +26,7 @@ static void usage(const char* argv0)
 {
 	fprintf(stderr,
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
-	        "          [--lc N --lp N --pb N] [--device D] [--max-scan M]\n"
+	        "          [--lc N --lp N --pb N | --props auto [--props-rounds R] [--props-table]] [--device D] [--max-scan M]\n"
 	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]] filename\n"
@@ -42,6 +42,10 @@ static void usage(const char* argv0)
 	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's\n"
 	        "  --clip-window    with --seed-stream: copies from beyond the dictionary window become literals instead\n"
 	        "               of an error\n"
+	        "  --props auto     choose lc/lp/pb before the search: the parse of the seed option (without one, an optimal parse made\n"
+	        "               for this only) is costed under all 75 supported triples at once and the search runs under the\n"
+	        "               cheapest; a seed that depends on the triple is made again under it, up to R sweeps (default 3).\n"
+	        "               Not with --lc/--lp/--pb or --chains above 1.  --props-table prints the last sweep's 75 costs\n"
 	        "  --temperature B  Metropolis accept rule instead of the reference's: B = e-folding slack in output\n"
 	        "               bytes at the start of an epoch, cooled linearly to 0 (e.g. 2; 0 = reference rule)\n"
 	        "  --chains N --rank R --comm-file PATH  one of N independent chains, one process per GPU (device = R unless\n"
@@ -53,6 +57,78 @@ static void usage(const char* argv0)
 	        "               for chains that share one GPU.  --save-slab: chain R > 0 writes to <file>.rankR\n"
 	        "  --accept     what a step of K neighbours takes: the best acceptable one (single), every one that is\n"
 	        "               the best of its own window (bulk), or whichever pays (auto, default)\n", argv0);
+}
+
+static bool same_props(mgl_properties a, mgl_properties b) { return a.lc == b.lc && a.lp == b.lp && a.pb == b.pb; }
+
+/* slab file: "MGLSLAB1", u64 size, u64 perplexity, size x 12-byte packets (lzma_packet.h:13-17) */
+static bool read_slab_file(const char* path, size_t file_size, mgl_packet* packets, uint64_t* perplexity)
+{
+	FILE* f = fopen(path, "rb");
+	char magic[8];
+	uint64_t hdr[2] = { 0, 0 };
+	const bool ok = f && fread(magic, 8, 1, f) == 1 && memcmp(magic, "MGLSLAB1", 8) == 0 && fread(hdr, 8, 2, f) == 2 &&
+	                hdr[0] == file_size && fread(packets, sizeof(mgl_packet), file_size, f) == file_size;
+	if (f) fclose(f);
+	*perplexity = hdr[1];
+	return ok;
+}
+
+/* --props auto.  `sa` is a handle at *props that nothing has been done to yet.  Each round costs
+ * one parse under all 75 triples (mgl_props_sweep) and moves to a fresh handle at the cheapest, until that is the
+ * handle's own or `rounds` sweeps are done.  parse_fixed: `parse` holds a parse that does not depend on the triple (a
+ * stream's, a loaded slab's, the greedy one); otherwise every round makes an optimal seed under the handle's triple
+ * into it.  Of all (triple, parse) pairs seen the cheapest wins: *props becomes its triple, `kept` its parse (only
+ * when the parse is not fixed), and the handle returned is an untouched one at that triple.  NULL after an error
+ * (already reported). */
+static mgl_sa* choose_props(mgl_sa* sa, const uint8_t* data, size_t n, const mgl_sa_config* cfg, mgl_properties* props,
+                            mgl_packet* parse, bool parse_fixed, uint32_t optimal_passes, unsigned rounds, bool print_table,
+                            mgl_packet* kept)
+{
+	mgl_props_cost tab[MGL_PROPS_TRIPLES];
+	uint64_t best_cost = UINT64_MAX, best_at0 = 0;
+	mgl_properties best = *props;
+	unsigned done = 0;
+	bool touched = false;
+	for (;;) {
+		if (!parse_fixed) {
+			mgl_optimal_config oc = { optimal_passes, 0, 0 };
+			mgl_optimal_stats os;
+			uint64_t cost = 0;
+			if (mgl_sa_seed_optimal(sa, &oc, &os) != MGL_OK || mgl_sa_current(sa, parse, &cost) != MGL_OK) goto fail;
+			touched = true;
+		}
+		size_t count = 0;
+		if (mgl_props_sweep(sa, parse, tab, MGL_PROPS_TRIPLES, &count, NULL) != MGL_OK) goto fail;
+		done++;
+		size_t arg = 0; /* the cheapest, ties to the first in canonical order */
+		for (size_t t = 1; t < MGL_PROPS_TRIPLES; t++)
+			if (tab[t].cost < tab[arg].cost) arg = t;
+		if (tab[arg].cost < best_cost) {
+			best_cost = tab[arg].cost; best = tab[arg].props; best_at0 = tab[0].cost;
+			if (!parse_fixed) memcpy(kept, parse, sizeof(mgl_packet) * n);
+		}
+		if (same_props(tab[arg].props, *props) || done >= rounds) break;
+		mgl_sa_destroy(sa);
+		*props = tab[arg].props;
+		touched = false;
+		if ((sa = mgl_sa_create(data, n, *props, cfg)) == NULL) goto fail;
+	}
+	if (touched || !same_props(best, *props)) {
+		mgl_sa_destroy(sa);
+		*props = best;
+		if ((sa = mgl_sa_create(data, n, *props, cfg)) == NULL) goto fail;
+	}
+	fprintf(stderr, "props: lc=%u lp=%u pb=%u, sweep %llu B, at 0/0/0 %llu B, %u rounds\n", best.lc, best.lp, best.pb,
+	        (unsigned long long)((best_cost + 16383) / 16384), (unsigned long long)((best_at0 + 16383) / 16384), done);
+	if (print_table)
+		for (size_t t = 0; t < MGL_PROPS_TRIPLES; t++)
+			fprintf(stderr, "props-table: lc=%u lp=%u pb=%u cost %llu (%llu B)\n", tab[t].props.lc, tab[t].props.lp, tab[t].props.pb,
+			        (unsigned long long)tab[t].cost, (unsigned long long)((tab[t].cost + 16383) / 16384));
+	return sa;
+fail:
+	fprintf(stderr, "Error: %s\n", mgl_last_error());
+	return NULL;
 }
 
 int main(int argc, char** argv)
@@ -68,6 +144,8 @@ int main(int argc, char** argv)
 	const char* filename = NULL;
 	const char *out_path = NULL, *save_path = NULL, *load_path = NULL, *seed_stream_path = NULL;
 	int clip_window = 0, props_given = 0;
+	bool props_auto = false, props_table = false;
+	unsigned props_rounds = 3;
 	uint32_t greedy = 0, optimal = 0;
 	mgl_packet* optimal_slab = NULL;
 	double temperature_bytes = 0;
@@ -81,6 +159,7 @@ int main(int argc, char** argv)
 		const char* v = i + 1 < argc ? argv[i + 1] : NULL;
 		if (a[0] != '-') { filename = a; continue; }
 		if (!strcmp(a, "--clip-window")) { clip_window = 1; continue; }
+		if (!strcmp(a, "--props-table")) { props_table = true; continue; }
 		if (!v) { usage(argv[0]); return -1; }
 		if (!strcmp(a, "--neighbours")) cfg.neighbours_per_step = (uint32_t)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--epochs")) epochs = (unsigned)strtoul(v, NULL, 0);
@@ -90,6 +169,11 @@ int main(int argc, char** argv)
 		else if (!strcmp(a, "--lc")) { props.lc = (uint8_t)strtoul(v, NULL, 0); props_given = 1; }
 		else if (!strcmp(a, "--lp")) { props.lp = (uint8_t)strtoul(v, NULL, 0); props_given = 1; }
 		else if (!strcmp(a, "--pb")) { props.pb = (uint8_t)strtoul(v, NULL, 0); props_given = 1; }
+		else if (!strcmp(a, "--props")) {
+			if (strcmp(v, "auto") != 0) { usage(argv[0]); return -1; }
+			props_auto = true;
+		}
+		else if (!strcmp(a, "--props-rounds")) { props_rounds = (unsigned)strtoul(v, NULL, 0); if (!props_rounds) { usage(argv[0]); return -1; } }
 		else if (!strcmp(a, "--device")) { cfg.device = (int32_t)strtol(v, NULL, 0); device_given = 1; }
 		else if (!strcmp(a, "--chains")) chains = (int)strtol(v, NULL, 0);
 		else if (!strcmp(a, "--rank")) rank = (int)strtol(v, NULL, 0);
@@ -128,6 +212,12 @@ int main(int argc, char** argv)
 		return -1;
 	}
 	if (clip_window && !seed_stream_path) { usage(argv[0]); return -1; }
+	if (props_auto && (props_given || chains > 1)) {
+		fprintf(stderr, "Error: --props auto cannot be combined with --lc/--lp/--pb or with --chains above 1\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (props_table && !props_auto) { usage(argv[0]); return -1; }
 	if (chains < 1 || rank < 0 || rank >= chains || (chains > 1 && !comm_path)) { usage(argv[0]); return -1; }
 	if (chains > 1) {
 		if (!device_given) cfg.device = rank;
@@ -172,6 +262,35 @@ int main(int argc, char** argv)
 	cfg.iters_per_epoch = file_size;
 	mgl_sa* sa = mgl_sa_create(file_data, file_size, props, &cfg);
 	if (sa == NULL) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+	if (props_auto) {
+		/* the parse to look at: the seed the user asked for; without one an optimal seed at its defaults, for the sweep only */
+		mgl_packet* parse = (mgl_packet*)malloc(sizeof(mgl_packet) * file_size);
+		bool fixed = true;
+		uint64_t unused = 0;
+		if (!parse) { fprintf(stderr, "Error: out of memory\n"); return -1; }
+		if (seed_stream) {
+			mgl_import_stats ist;
+			if (mgl_stream_import(seed_stream, seed_stream_len, file_data, file_size, cfg.dict_limit, clip_window ? MGL_IMPORT_CLIP_WINDOW : 0,
+			                      parse, &ist) != MGL_OK) {
+				fprintf(stderr, "Error: %s: %s at input position %llu\n", seed_stream_path, ist.error ? ist.error : "import failed",
+				        (unsigned long long)ist.error_pos);
+				return -1;
+			}
+		} else if (load_path) {
+			if (!read_slab_file(load_path, file_size, parse, &unused)) { fprintf(stderr, "Error: %s is not a slab for this input\n", load_path); return -1; }
+		} else if (greedy) {
+			/* the greedy parse does not look at the properties: made once, on a handle that is then replaced */
+			if (mgl_sa_seed_greedy(sa, greedy) != MGL_OK || mgl_sa_current(sa, parse, &unused) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+			mgl_sa_destroy(sa);
+			if ((sa = mgl_sa_create(file_data, file_size, props, &cfg)) == NULL) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+		} else {
+			fixed = false;
+			if ((optimal_slab = (mgl_packet*)malloc(sizeof(mgl_packet) * file_size)) == NULL) { fprintf(stderr, "Error: out of memory\n"); return -1; }
+		}
+		if ((sa = choose_props(sa, file_data, file_size, &cfg, &props, parse, fixed, optimal, props_rounds, props_table, optimal_slab)) == NULL) return -1;
+		free(parse);
+		if (!optimal) { free(optimal_slab); optimal_slab = NULL; } /* no seed option: the search starts from the all-literal slab */
+	}
 
 	if (temperature_bytes > 0 && mgl_sa_set_temperature(sa, (uint64_t)(temperature_bytes * 16384.0)) != MGL_OK) {
 		fprintf(stderr, "Error: %s\n", mgl_last_error());
@@ -218,18 +337,15 @@ int main(int argc, char** argv)
 	if (packets_best == NULL) { fprintf(stderr, "Error: out of memory\n"); return -1; }
 	bool resumed = false;
 	if (load_path) {
-		/* slab file: "MGLSLAB1", u64 size, u64 perplexity, size x 12-byte packets (lzma_packet.h:13-17) */
-		FILE* f = fopen(load_path, "rb");
-		char magic[8];
-		uint64_t hdr[2] = { 0, 0 };
-		if (!f || fread(magic, 8, 1, f) != 1 || memcmp(magic, "MGLSLAB1", 8) != 0 || fread(hdr, 8, 2, f) != 2 ||
-		    hdr[0] != file_size || fread(packets_best, sizeof(mgl_packet), file_size, f) != file_size) {
+		uint64_t perplexity = 0;
+		if (!read_slab_file(load_path, file_size, packets_best, &perplexity)) {
 			fprintf(stderr, "Error: %s is not a slab for this input\n", load_path);
 			return -1;
 		}
-		fclose(f);
+		/* --props auto: the file's perplexity belongs to the triple it was saved under; the slab is costed under the chosen one */
+		if (props_auto && mgl_cost_slab(sa, packets_best, &perplexity, NULL, NULL) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 		/* the library re-costs the slab and refuses it unless the perplexity matches */
-		if (mgl_sa_set_best(sa, packets_best, hdr[1]) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+		if (mgl_sa_set_best(sa, packets_best, perplexity) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 		resumed = true;
 	}
 	if (seed_stream) {
@@ -255,7 +371,7 @@ int main(int argc, char** argv)
 		resumed = true;
 	}
 
-	if (optimal) {
+	if (optimal && !props_auto) { /* --props auto kept the parse of its cheapest (triple, parse) pair in optimal_slab */
 		/* made once; every epoch that would start from the all-literal slab starts from it */
 		mgl_optimal_config oc = { optimal, 0, 0 };
 		mgl_optimal_stats os;
