@@ -287,8 +287,12 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * 11 parallel-builder totals, 12 / 13 match index (bucket offsets / positions), 14 accept-path
  * counters, 15 pick records, 16 the control block, 21 the windows (target, end) of the last costed neighbours, 22 their soft ends | dep << 31,
  * 30-35 / 40-45 / 50-55 / 60-65 positions / ranks / run starts / next byte of the exact-length orders D = 2..7,
- * 70-73 and 74-77 positions, ranks, run starts, next eight bytes of the 8- and 16-byte orders, 80 two u64 host counters: bulk
- * steps whose moves were patched into the base structures at once (batch accept), and those that began so and fell back to the rebuild.
+ * 70-73 and 74-77 positions, ranks, run starts, next eight bytes of the 8- and 16-byte orders, 80 three u64 host counters: bulk
+ * steps whose moves were patched into the base structures at once (batch accept), those that began so and fell back to the
+ * rebuild behind their commit (status 1), and those that left the step to the rebuild before anything was touched because the
+ * clusters or a walk gave up (status 2 with a failure seen), 81 / 82 the batch accept's header and totals, 83 the chain index,
+ * selector 84 one u32: the give-up sites of the in-place accepts seen since the last dump (MGL_GU_* bits of csrc/mgl_base2.h;
+ * cleared by the dump and by key 6), 85 one u32: the chain pool's top.
  * mgl_debug_set: key 0 = stop the neighbour kernels after a phase (tools/phase_cost.py), 50 =
  * stage timing in the accept path; key 1 = make the parallel builder redo every chain segment
  * serially (exercises its fallback); key 2 = shrink the first-pass change lists (a multiple of 8,
@@ -296,7 +300,21 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * next so many bulk steps that took moves as failed validations (exercises the rollback); key 4 = 1 / 0: the
  * re-simulation kernel adds up the bytes it reads (mgl_sa_stats.sim_bytes_counted; a few percent slower); key 5 = n: the next
  * n batch accepts (bulk steps that patch few moves into the base structures) give up after they have written their journals
- * and bitmaps (exercises the fallback to the rebuild from there). */
+ * and bitmaps (exercises the fallback to the rebuild from there): at the top of the chain kernel, before any chain is touched.
+ * Second form, value >> 32 = m > 0: the give-up comes once the m-th touched context has rewritten its chain's descriptors,
+ * taken its pool space and queued its copy jobs -- behind a partial rewrite by other workgroups (a low word of 0 then counts as 1).
+ * Every batch accept the hook is applied to counts against the low word, also one that goes through because fewer than m
+ * contexts got that far (nothing gives up then); steps that take nothing or too many moves do not count.
+ * key 6 = id | value << 8: limit `id` of the in-place accepts := value, so that a give-up's real comparison fires on an
+ * ordinary input; a value above the compiled / allocated one is refused (MGL_EINVAL); id 0 with value 0 restores every default.
+ * Single accept (mgl_kernels3.hip): 1 = inserted / removed events of the accepted neighbour, 2 = iterations of its walk,
+ * 3 = events of one context, 4 = rewritten chain entries of one context, 5 = pieces / checkpoint segments of one context,
+ * 6 = entries a chain's tail may shift by in place.  Both accepts: 7 = chain pool entries (a chain that outgrows its slot
+ * finds the pool exhausted), 8 = copy jobs per list, 9 = span area entries, 10 = save area entries.  Batch accept
+ * (mgl_kernels5.hip): 11 = journal entries of one cluster, 12 = staged events of one cluster, 13 = bitmap / state-record ops
+ * of one cluster, 14 = iterations of a cluster's walk, 15 = events of one kind per context, 16 = entries a stretch may shift
+ * by in place, 17 = runs on the checkpoint list, 18 = 1 / 0: clusters are split at the members' soft window ends instead of
+ * their hard ends (a wrong rule on purpose: the boundary guard of the cluster walks must then send the step to the rebuild). */
 int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes);
 int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value);
 /* draw n of neighbour j at global step `step` (31-bit, like rand()); j = 0xFFFFFFFF is the

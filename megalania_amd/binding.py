@@ -444,6 +444,19 @@ class SA:
         v = self.debug_dump(80, np.uint64)
         return int(v[0]), int(v[1])
 
+    def batch_giveups(self) -> int:
+        """bulk steps that began a batch accept and left the step to the rebuild before anything was touched (a cluster's journal
+        or a walk gave up: status 2 with a failure seen)"""
+        return int(self.debug_dump(80, np.uint64)[2])
+
+    def giveup_sites(self) -> int:
+        """give-up sites of the in-place accepts seen since the last call (MGL_GU_* bits, csrc/mgl_base2.h); reading clears"""
+        return int(self.debug_dump(84, np.uint32)[0])
+
+    def set_limit(self, limit_id: int, value: int):
+        """mgl_debug_set key 6: lower limit `limit_id` of the in-place accepts; set_limit(0, 0) restores every default"""
+        self.debug_set(6, limit_id | (value << 8))
+
     def debug_set(self, key: int, value: int):
         self._chk(self.L.mgl_debug_set(self.h, key, value))
 

@@ -145,6 +145,9 @@ struct mgl_sa {
 	uint32_t* h_bstat = nullptr;   /* pinned: the batch accept's status words, read back once per bulk step */
 	hipEvent_t ev_bstat = nullptr; /* behind that read-back's copy */
 	uint32_t force_batch_fail = 0; /* diagnostic (mgl_debug_set key 5): the next so many batch accepts give up behind their commit */
+	uint32_t force_batch_late = 0; /* ... 0: before any chain is touched; n: once the n-th touched context has rewritten its chain's descriptors */
+	AcceptLimits lim, lim_max;     /* what the in-place accepts compare against (mgl_debug_set key 6 lowers them) and the compiled / allocated values */
+	uint64_t batch_early_giveups = 0; /* bulk steps that began a batch accept and left it before anything was touched (clusters or a walk gave up) */
 	uint64_t batch_accepts = 0, batch_fallbacks = 0; /* bulk steps whose moves were patched in / that went to the rebuild although a batch accept began */
 	std::vector<uint8_t> mode_log; /* per step of the last mgl_sa_run: 0 single, 1 bulk */
 	uint32_t force_rollbacks = 0;  /* diagnostic: treat the next so many bulk steps that took moves as failed validations */
@@ -333,6 +336,30 @@ static int launch_validate(mgl_sa* sa)
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
+/* the structs the accept kernels get: the handle's, with the capacities a test may have lowered (mgl_debug_set key 6) */
+static Base2 accept_b2(const mgl_sa* sa) { Base2 b = sa->b2; b.pool_cap = sa->lim.v[MGL_LIM_POOL]; return b; }
+static ApplyBuf accept_ab(const mgl_sa* sa)
+{
+	ApplyBuf ab = sa->ab;
+	ab.job_cap = sa->lim.v[MGL_LIM_JOBS]; ab.span_cap = sa->lim.v[MGL_LIM_SPAN_AREA]; ab.scratch_cap = sa->lim.v[MGL_LIM_SCRATCH];
+	return ab;
+}
+static BatchBuf accept_bt(const mgl_sa* sa) { BatchBuf bt = sa->batch; bt.runs_cap = sa->lim.v[MGL_LIM_BATCH_RUNS]; return bt; }
+static void accept_limits_init(mgl_sa* sa, uint32_t* why)
+{
+	AcceptLimits& m = sa->lim_max;
+	memset(&m, 0, sizeof m);
+	m.v[MGL_LIM_APPLY_EVENTS] = MGL_APPLY_CAP; m.v[MGL_LIM_APPLY_GUARD] = 1u << 20; m.v[MGL_LIM_APPLY_SUB] = MGL_SUB_CAP;
+	m.v[MGL_LIM_APPLY_SPAN] = MGL_SPAN_CAP; m.v[MGL_LIM_APPLY_PIECES] = MGL_PIECE_CAP; m.v[MGL_LIM_APPLY_SHIFT] = MGL_SUB_CAP;
+	m.v[MGL_LIM_POOL] = sa->b2.pool_cap; m.v[MGL_LIM_JOBS] = sa->ab.job_cap; m.v[MGL_LIM_SPAN_AREA] = sa->ab.span_cap;
+	m.v[MGL_LIM_SCRATCH] = sa->ab.scratch_cap;
+	m.v[MGL_LIM_BATCH_JOURNAL] = MGL_BATCH_JCAP; m.v[MGL_LIM_BATCH_EVENTS] = MGL_BATCH_EVCAP; m.v[MGL_LIM_BATCH_OPS] = MGL_BATCH_OPCAP;
+	m.v[MGL_LIM_BATCH_GUARD] = 1u << 18; m.v[MGL_LIM_BATCH_SUB] = MGL_BATCH_SUB; m.v[MGL_LIM_BATCH_SHIFT] = 2047u;
+	m.v[MGL_LIM_BATCH_RUNS] = sa->batch.runs_cap; m.v[MGL_LIM_SOFT_REACH] = 1u;
+	m.why = why;
+	sa->lim = m;
+	sa->lim.v[MGL_LIM_SOFT_REACH] = 0u;
+}
 /* incremental engine, after k_decide: fold the winner into the base structures */
 static int launch_targets_ahead(mgl_sa* sa, uint64_t next_gstep);
 static int launch_apply(mgl_sa* sa, uint64_t next_gstep = ~0ull)
@@ -343,12 +370,12 @@ static int launch_apply(mgl_sa* sa, uint64_t next_gstep = ~0ull)
 		int rc = launch_snapshot(sa, sa->snap_best, 1, 0, 2);
 		if (rc) return rc;
 	}
-	hipLaunchKernelGGL(k_apply_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->nbr, sa->ab);
+	hipLaunchKernelGGL(k_apply_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->nbr, sa->ab, sa->lim);
 	if (next_gstep != ~0ull) { int rc = launch_targets_ahead(sa, next_gstep); if (rc) return rc; } /* the bitmap is final from here on */
 	if (!sa->snapshots)
 		hipLaunchKernelGGL(k_copy_best, dim3(256), dim3(256), 0, sa->stream, (const Control*)sa->base.ctl,
 		                   (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n);
-	hipLaunchKernelGGL(k_apply_chains, dim3(sa->apply_blocks), dim3(MGL_APPLY_THREADS), 0, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->ab);
+	hipLaunchKernelGGL(k_apply_chains, dim3(sa->apply_blocks), dim3(MGL_APPLY_THREADS), 0, sa->stream, sa->ctx, accept_b2(sa), sa->base.ctl, accept_ab(sa), sa->lim);
 	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)nullptr);
 	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)nullptr);
 	hipLaunchKernelGGL(k_build_end, dim3(1), dim3(64), sa->build_lds, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->snapshots ? 1 : 0, sa->d_counts, sa->adaptive ? 1 : 0, sa->form_single ? 1 : 0);
@@ -558,7 +585,7 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 	}
 	for (hipEvent_t e : sa->ev_sim_pool) if (e) (void)hipEventDestroy(e);
 	dfree(sa->d_todo2); dfree(sa->d_todo3); dfree(sa->d_counts); dfree(sa->big.sim_hdr2); dfree(sa->big.sim_slot2); dfree(sa->d_pickrec); dfree(sa->d_pickstate);
-	dfree(sa->ab.hdr); dfree(sa->ab.ins_key); dfree(sa->ab.rem_key); dfree(sa->ab.ins_pos); dfree(sa->ab.rem_pos);
+	dfree(sa->lim.why); dfree(sa->ab.hdr); dfree(sa->ab.ins_key); dfree(sa->ab.rem_key); dfree(sa->ab.ins_pos); dfree(sa->ab.rem_pos);
 	dfree(sa->ab.tctx); dfree(sa->ab.scratch_pos); dfree(sa->ab.scratch_ev);
 	dfree(sa->ab.span_pos); dfree(sa->ab.span_ev); dfree(sa->ab.jobs_b); dfree(sa->ab.jobs_c);
 	dfree(sa->d_topk_pk); dfree(sa->d_topk_cost); dfree(sa->d_small); dfree(sa->d_sub_offs); dfree(sa->d_sub_lens);
@@ -882,6 +909,10 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 			HIPCHK(hipHostMalloc((void**)&sa->h_bstat, sizeof(uint32_t) * 16, hipHostMallocDefault));
 			HIPCHK(hipEventCreateWithFlags(&sa->ev_bstat, hipEventDisableTiming));
 			sa->batch_ok = sa->incremental_apply && getenv("MGL_NO_BATCH") == nullptr;
+			uint32_t* why = nullptr;
+			HIPCHK(hipMalloc(&why, sizeof(uint32_t)));
+			HIPCHK(hipMemset(why, 0, sizeof(uint32_t)));
+			accept_limits_init(sa, why);
 
 		}
 		{
@@ -1430,9 +1461,15 @@ static int launch_bulk_tail(mgl_sa* sa, uint64_t next_gstep)
 	bool closed = false; /* the closing kernels are queued (behind the batch accept's gate) and the gate is open */
 	if (sa->batch_ok && !sa->force_rollbacks) { /* (the rollback net hangs under the rebuild: while a test forces it, steps go that way) */
 		Base2& b = sa->b2;
-		if (sa->force_batch_fail) { const uint32_t one = 1u; HIPCHK(hipMemcpyAsync(sa->batch.hdr + 9, &one, sizeof one, hipMemcpyHostToDevice, sa->stream)); }
-		hipLaunchKernelGGL(k_batch_clusters, dim3(1), dim3(1024), 0, sa->stream, sa->ctx, (const Control*)sa->base.ctl, sa->nbr, sa->bulk, sa->batch);
-		hipLaunchKernelGGL(k_batch_walk, dim3(MGL_BATCH_MAX), dim3(64), 0, sa->stream, sa->ctx, b, sa->batch);
+		if (sa->force_batch_fail) { /* hdr[9]: give up at the top of k_batch_chains; hdr[13] = n: behind the n-th context's rewrite */
+			const uint32_t early = sa->force_batch_late ? 0u : 1u, late = sa->force_batch_late;
+			HIPCHK(hipMemcpyAsync(sa->batch.hdr + 9, &early, sizeof early, hipMemcpyHostToDevice, sa->stream));
+			HIPCHK(hipMemcpyAsync(sa->batch.hdr + 13, &late, sizeof late, hipMemcpyHostToDevice, sa->stream));
+		}
+		const BatchBuf bt = accept_bt(sa);
+		const ApplyBuf ab = accept_ab(sa);
+		hipLaunchKernelGGL(k_batch_clusters, dim3(1), dim3(1024), 0, sa->stream, sa->ctx, (const Control*)sa->base.ctl, sa->nbr, sa->bulk, sa->batch, sa->lim);
+		hipLaunchKernelGGL(k_batch_walk, dim3(MGL_BATCH_MAX), dim3(64), 0, sa->stream, sa->ctx, b, sa->batch, sa->lim);
 		hipLaunchKernelGGL(k_batch_commit, dim3(MGL_BATCH_MAX), dim3(256), 0, sa->stream, sa->ctx, b, sa->base.ctl, sa->batch, sa->ab);
 		hipLaunchKernelGGL(pb_levels, dim3((b.nw0 + 255) / 256), dim3(256), 0, sa->stream, (const uint64_t*)b.sp0, b.sp1, b.nw0, b.nw1);
 		hipLaunchKernelGGL(pb_levels, dim3((b.nw1 + 255) / 256), dim3(256), 0, sa->stream, (const uint64_t*)b.sp1, b.sp2, b.nw1, b.nw2);
@@ -1440,8 +1477,8 @@ static int launch_bulk_tail(mgl_sa* sa, uint64_t next_gstep)
 		if (next_gstep != ~0ull && (rc = launch_targets_ahead(sa, next_gstep))) return rc;
 		hipLaunchKernelGGL(k_batch_scan, dim3(1), dim3(1024), 0, sa->stream, sa->batch, sa->ab);
 		hipLaunchKernelGGL(k_batch_fill, dim3(256), dim3(256), 0, sa->stream, sa->batch, sa->ab);
-		hipLaunchKernelGGL(k_batch_chains, dim3(MGL_BATCH_GRID), dim3(MGL_BATCH_THREADS), 0, sa->stream, sa->ctx, b, sa->base.ctl, sa->batch, sa->ab);
-		hipLaunchKernelGGL(k_batch_ckpt, dim3(1024, 8), dim3(256), 0, sa->stream, b, (const Control*)sa->base.ctl, sa->batch, sa->ab);
+		hipLaunchKernelGGL(k_batch_chains, dim3(MGL_BATCH_GRID), dim3(MGL_BATCH_THREADS), 0, sa->stream, sa->ctx, accept_b2(sa), sa->base.ctl, bt, ab, sa->lim);
+		hipLaunchKernelGGL(k_batch_ckpt, dim3(1024, 8), dim3(256), 0, sa->stream, b, (const Control*)sa->base.ctl, bt, ab);
 		hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, b, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)sa->batch.hdr);
 		hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, b, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)sa->batch.hdr);
 		hipLaunchKernelGGL(k_batch_end, dim3(1), dim3(64), 0, sa->stream, sa->base.ctl, sa->batch);
@@ -1457,7 +1494,11 @@ static int launch_bulk_tail(mgl_sa* sa, uint64_t next_gstep)
 		if (sa->force_batch_fail) {
 			const uint32_t zero = 0u;
 			HIPCHK(hipMemcpy(sa->batch.hdr + 9, &zero, sizeof zero, hipMemcpyHostToDevice));
-			if (bstat[0] == 1u) sa->force_batch_fail--; /* (a step that took nothing, or went to the rebuild anyway, does not count) */
+			HIPCHK(hipMemcpy(sa->batch.hdr + 13, &zero, sizeof zero, hipMemcpyHostToDevice));
+			/* a step that took nothing, or went to the rebuild anyway, does not count; a batch accept the hook was applied to does,
+			 * whether it gave up or (late form with n above the contexts that got that far) went through: the hook never stays
+			 * armed with a stale n */
+			if ((bstat[0] == 1u || bstat[0] == 3u) && --sa->force_batch_fail == 0) sa->force_batch_late = 0;
 		}
 	}
 	if (sa->batch_ok) sa->select_small = bstat[7] <= 512u; /* this step's acceptable neighbours size the next step's selection */
@@ -1469,6 +1510,7 @@ static int launch_bulk_tail(mgl_sa* sa, uint64_t next_gstep)
 		 * the new parse against the input; a parse that fails is taken back as a whole.  One small read-back per bulk
 		 * step (a bulk step of this kind is a rebuild: milliseconds) */
 		if (sa->batch_ok && bstat[0] == 1u) sa->batch_fallbacks++;
+		if (sa->batch_ok && bstat[0] == 2u && bstat[4]) sa->batch_early_giveups++; /* (status 2 without it: more moves than a batch accept handles) */
 		if (bstat[0] != 1u)
 			hipLaunchKernelGGL(k_bulk_write, dim3(64), dim3(256), 0, sa->stream, sa->base.ctl, sa->nbr, sa->bulk, sa->base.v.slab);
 		HIPCHK(hipGetLastError());
@@ -1869,12 +1911,15 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 7: src = b.ck_probs; sz = sizeof(uint16_t) * (size_t)b.nck * b.ck_elems; break;
 	case 8: src = b.ch_cap; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
 	case 9: src = sa->d_prof; sz = sa->d_prof ? sizeof(unsigned long long) * (32 + sa->cfg.neighbours_per_step) : 0; break;
-	case 80: { /* host counters: batch accepts, batch accepts that fell back to the rebuild */
-		const uint64_t v[2] = { sa->batch_accepts, sa->batch_fallbacks };
+	case 80: { /* host counters: batch accepts, batch accepts that fell back to the rebuild behind their commit, and those that left the
+	            * step to the rebuild before anything was touched */
+		const uint64_t v[3] = { sa->batch_accepts, sa->batch_fallbacks, sa->batch_early_giveups };
 		*bytes = sizeof v;
 		if (cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
 		return MGL_OK;
 	}
+	case 84: src = sa->lim.why; sz = sizeof(uint32_t); break; /* give-up sites seen since the last dump (cleared below) */
+	case 85: src = b.pool_top; sz = sizeof(uint32_t); break;
 	case 83: src = b.ch_sb; sz = sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride; break; /* the chain index, row per context, sb_stride words each */
 	case 81: src = sa->batch.hdr; sz = sizeof(uint32_t) * 16; break;
 	case 82: src = sa->batch.acc; sz = sizeof(long long) * 4; break;
@@ -1906,13 +1951,35 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	*bytes = sz;
 	if (sz > cap_bytes) return fail(MGL_ERANGE, "mgl_debug_dump: buffer too small");
 	HIPCHK(hipMemcpy(out, src, sz, hipMemcpyDeviceToHost));
+	if (what == 84) HIPCHK(hipMemset(sa->lim.why, 0, sizeof(uint32_t)));
 	return MGL_OK;
 }
 
 /* diagnostic knobs (tools/, tests/): key 0 = stop the neighbour kernel after phase `value`; key 1 = see below */
 extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 {
-	if (sa && key == 5) { sa->force_batch_fail = (uint32_t)value; return MGL_OK; } /* the next `value` batch accepts give up behind their commit (exercises the fallback to the rebuild) */
+	if (sa && key == 5) { /* the next (low word) batch accepts give up behind their commit; high word 0: before a chain is touched, n: behind the n-th context's rewrite */
+		sa->force_batch_late = (uint32_t)(value >> 32);
+		sa->force_batch_fail = (uint32_t)value;
+		if (sa->force_batch_late && !sa->force_batch_fail) sa->force_batch_fail = 1;
+		return MGL_OK;
+	}
+	if (sa && key == 6) { /* limit `id` of the in-place accepts := value (at most the compiled / allocated one); 0: all back to their defaults */
+		const uint32_t id = (uint32_t)(value & 0xFFu);
+		const uint64_t v = value >> 8;
+		if (!sa->incremental || !sa->lim.why) return fail(MGL_EINVAL, "mgl_debug_set: no in-place accept on this handle");
+		HIPCHK(hipSetDevice(sa->device));
+		HIPCHK(hipStreamSynchronize(sa->stream));
+		if (id == 0) {
+			if (v) return fail(MGL_EINVAL, "mgl_debug_set: limit id 0 takes value 0 (restore the defaults)");
+			for (uint32_t i = 1; i < MGL_LIM_COUNT; i++) sa->lim.v[i] = i == MGL_LIM_SOFT_REACH ? 0u : sa->lim_max.v[i];
+		} else {
+			if (id >= MGL_LIM_COUNT || v > sa->lim_max.v[id]) return fail(MGL_EINVAL, "mgl_debug_set: unknown limit, or a value above the compiled / allocated one");
+			sa->lim.v[id] = (uint32_t)v;
+		}
+		HIPCHK(hipMemset(sa->lim.why, 0, sizeof(uint32_t)));
+		return MGL_OK;
+	}
 	if (sa && key == 4) { /* count the bytes of chain data the re-simulation kernel reads (mgl_sa_stats.sim_bytes_counted) */
 		if (!sa->d_traffic) return fail(MGL_EINVAL, "mgl_debug_set: no split neighbour evaluation on this handle");
 		sa->count_traffic = value != 0;

@@ -13,7 +13,11 @@
  *                   trajectory.
  * Anything that does not fit (event lists, span buffers, chain capacity) raises
  * Control::apply_failed and the same step falls back to k_build, which rebuilds everything
- * from the slab; both routes produce identical structures (tests/test_gpu_incremental.py).
+ * from the slab; both routes produce identical structures
+ * (tests/test_gpu_accept_giveups.py:test_single_accept_that_gives_up_equals_the_rebuild takes the
+ * fallback at every give-up site below -- what a site compares against comes in AcceptLimits, which
+ * a test lowers -- and compares with a rebuild; tests/test_gpu_incremental.py covers the route that
+ * does not give up).  Every give-up ORs its site's bit (MGL_GU_*) into *AcceptLimits::why.
  */
 #include "mgl_base2.h"
 
@@ -80,7 +84,7 @@ __device__ __forceinline__ void special_write(const Base2& b, uint32_t pos, bool
 	b.sp2[x] = nv1 ? (v2 | m2) : (v2 & ~m2);
 }
 
-__global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* ctl, NbrOut out, ApplyBuf ab)
+__global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* ctl, NbrOut out, ApplyBuf ab, AcceptLimits lim)
 {
 	__shared__ uint32_t s_jpos[MGL_MAX_DIFFS];
 	__shared__ mgl_pk s_jnew[MGL_MAX_DIFFS];
@@ -105,11 +109,11 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 	Win win; win.base = 0xFFFFFFFFu; win.pk = 0; win.byte = 0;
 	uint32_t n_ins = 0, n_rem = 0;
 	int32_t dpackets = 0;
-	bool failed = false;
+	uint32_t failed = 0; /* the give-up site's bit */
 	uint32_t ji = 0; /* next journal entry (positions ascending) */
 	uint32_t guard = 0;
 	while (nb.pos < c.n || bs.pos < c.n) {
-		if (++guard > (1u << 20)) { failed = true; break; }
+		if (++guard > lim.v[MGL_LIM_APPLY_GUARD]) { failed = MGL_GU_APPLY_GUARD; break; }
 		if (nb.pos == bs.pos) {
 			const bool same_ctx = nb.ctx_state == bs.ctx_state;
 			const bool same_d = nb.dists[0] == bs.dists[0] && nb.dists[1] == bs.dists[1] && nb.dists[2] == bs.dists[2] &&
@@ -164,7 +168,7 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 				b.sp_state[(size_t)p * 8 + lane] = v;
 			}
 			if (!cancelled) {
-				if (n_ins + npl.nev > MGL_APPLY_CAP || (paired && n_rem + bpl.nev > MGL_APPLY_CAP)) { failed = true; break; }
+				if (n_ins + npl.nev > lim.v[MGL_LIM_APPLY_EVENTS] || (paired && n_rem + bpl.nev > lim.v[MGL_LIM_APPLY_EVENTS])) { failed = MGL_GU_APPLY_EVENTS; break; }
 				if (lane < npl.nev) {
 					uint32_t ctx, bit;
 					mgl_plan_event(&npl, lane, &ctx, &bit);
@@ -201,7 +205,7 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 				run = run < limit ? run : limit;
 				if (run >= 2u) {
 					const uint32_t take = run < 7u ? run : 7u;
-					if (n_rem + 9u * take > MGL_APPLY_CAP) { failed = true; break; }
+					if (n_rem + 9u * take > lim.v[MGL_LIM_APPLY_EVENTS]) { failed = MGL_GU_APPLY_EVENTS; break; }
 					const uint32_t i = lane / 9u, slot = lane - i * 9u, p = q + i;
 					const bool active = i < take;
 					const uint32_t byte = (uint32_t)__shfl((int)win.byte, (int)((p - win.base) & 63u), 64);
@@ -234,7 +238,7 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 			const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
 			mgl_plan bpl;
 			plan_at(c, bs, btype, bdist, blen, win_byte(win, q), bpl);
-			if (n_rem + bpl.nev > MGL_APPLY_CAP) { failed = true; break; }
+			if (n_rem + bpl.nev > lim.v[MGL_LIM_APPLY_EVENTS]) { failed = MGL_GU_APPLY_EVENTS; break; }
 			if (lane < bpl.nev) {
 				uint32_t ctx, bit;
 				mgl_plan_event(&bpl, lane, &ctx, &bit);
@@ -281,7 +285,7 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 		}
 		ctl->packets = (uint64_t)((int64_t)ctl->packets + dpackets);
 		ctl->rebuild_cost = ctl->cur_cost; /* exact cost of the new base */
-		if (failed) ctl->apply_failed = 1;
+		if (failed) { ctl->apply_failed = 1; atomicOr(lim.why, failed); }
 	}
 }
 
@@ -306,7 +310,7 @@ struct Piece {
 	uint32_t from_span;
 };
 
-__global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Control* ctl, ApplyBuf ab)
+__global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Control* ctl, ApplyBuf ab, AcceptLimits lim)
 {
 	__shared__ uint32_t s_ipos[MGL_SUB_CAP];
 	__shared__ uint16_t s_ibit[MGL_SUB_CAP];
@@ -354,10 +358,10 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 				for (uint32_t w = 0; w < wid; w++) before += s_wcount[w];
 				const uint32_t idx = before + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
 				if (hit) {
-					if (idx < MGL_SUB_CAP) {
+					if (idx < lim.v[MGL_LIM_APPLY_SUB]) {
 						if (pass == 0) { s_ipos[idx] = pos; s_ibit[idx] = (uint16_t)(key >> 15); }
 						else s_rpos[idx] = pos;
-					} else s_fail = 1;
+					} else s_fail = MGL_GU_APPLY_SUB;
 				}
 				__syncthreads();
 				if (tid == 0) {
@@ -368,7 +372,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 				__syncthreads();
 			}
 		}
-		if (s_fail) { if (tid == 0) ctl->apply_failed = 1; continue; }
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } continue; }
 		APPLY_STAGE(0)
 
 		const uint32_t off = b.ch_off[cx], len = b.ch_len[cx], cap = b.ch_cap[cx];
@@ -425,7 +429,8 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 #define CPOS(k_) (((k_) - k0) < MGL_APPLY_WIN ? s_win_pos[(k_) - k0] : cpos[(k_)])
 #define CEV(k_) (((k_) - k0) < MGL_APPLY_WIN ? (uint32_t)s_win_ev[(k_) - k0] : (uint32_t)cev[(k_)])
 			uint32_t k = k0, dst = 0;
-			bool fail = false;
+			uint32_t fail = 0; /* the give-up site's bit */
+			const uint32_t span_cap = lim.v[MGL_LIM_APPLY_SPAN], piece_cap = lim.v[MGL_LIM_APPLY_PIECES];
 			uint32_t seg_first = 0, seg_lo = x0;
 			bool in_seg = true; /* a segment = a stretch where the new trajectory differs / entries change */
 			/* everything the loop compares lives in registers and is reloaded only when its cursor
@@ -443,9 +448,9 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 					bool moved_on = false;
 					for (;;) {
 						const uint32_t rel = k - k0;
-						if (rel >= MGL_APPLY_WIN || ns >= MGL_SPAN_CAP) break;
+						if (rel >= MGL_APPLY_WIN || ns >= span_cap) break;
 						uint32_t avail = MGL_APPLY_WIN - rel;
-						avail = avail < MGL_SPAN_CAP - ns ? avail : MGL_SPAN_CAP - ns;
+						avail = avail < span_cap - ns ? avail : span_cap - ns;
 						avail = avail < 64u ? avail : 64u;
 						const uint32_t my_pos = lane < avail ? s_win_pos[rel + lane] : MGL_POS_INF;
 						const uint32_t my_ev = lane < avail ? (uint32_t)s_win_ev[rel + lane] : 0u;
@@ -475,7 +480,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 					}
 				}
 				if (ipos < bpos) {
-					if (ns >= MGL_SPAN_CAP) { fail = true; break; }
+					if (ns >= span_cap) { fail = MGL_GU_APPLY_SPAN; break; }
 					s_span_pos[ns] = ipos; s_span_ev[ns] = (uint16_t)((ibit << 15) | p); ns++;
 					p = mgl_prob_update(p, ibit);
 					ii++;
@@ -487,7 +492,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 				const uint32_t nxt = ipos < rposn ? ipos : rposn;
 				if (p == bp && (!pending || nxt > bpos)) {
 					/* re-coupled at old entry k (which itself stays): close the segment */
-					if (nseg >= MGL_PIECE_CAP || np + 2 > MGL_PIECE_CAP) { fail = true; break; }
+					if (nseg >= piece_cap || np + 2 > piece_cap) { fail = MGL_GU_APPLY_PIECES; break; }
 					s_seg_lo[nseg] = seg_lo; s_seg_hi[nseg] = bpos; s_seg_first[nseg] = seg_first; s_seg_last[nseg] = ns;
 					s_seg_endp[nseg] = (uint16_t)p; nseg++;
 					s_piece[np].dst = dst; s_piece[np].src = seg_first; s_piece[np].count = ns - seg_first; s_piece[np].from_span = 1; np++;
@@ -509,7 +514,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 					ri++;
 					rposn = ri < nr ? s_rpos[ri] : MGL_POS_INF;
 				} else {
-					if (ns >= MGL_SPAN_CAP) { fail = true; break; }
+					if (ns >= span_cap) { fail = MGL_GU_APPLY_SPAN; break; }
 					s_span_pos[ns] = bpos; s_span_ev[ns] = (uint16_t)((bb << 15) | p); ns++;
 					p = mgl_prob_update(p, bb);
 				}
@@ -519,7 +524,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 			}
 			if (!fail && in_seg) {
 				/* ran into the sentinel un-coupled: the last segment reaches the end of the file */
-				if (nseg >= MGL_PIECE_CAP || np + 1 > MGL_PIECE_CAP) fail = true;
+				if (nseg >= piece_cap || np + 1 > piece_cap) fail = MGL_GU_APPLY_PIECES;
 				else {
 					s_seg_lo[nseg] = seg_lo; s_seg_hi[nseg] = MGL_POS_INF; s_seg_first[nseg] = seg_first; s_seg_last[nseg] = ns;
 					s_seg_endp[nseg] = (uint16_t)p; nseg++;
@@ -537,21 +542,21 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 				newoff = 0;
 				if (lane == 0) newoff = atomicAdd(b.pool_top, newcap);
 				newoff = uni(newoff);
-				if (newoff + newcap > b.pool_cap) fail = true; /* pool exhausted: k_build compacts */
+				if (newoff + newcap > b.pool_cap) fail = MGL_GU_APPLY_POOL; /* pool exhausted: k_build compacts */
 			}
 			s_newoff = newoff; s_newcap = newcap;
 			if (!fail) {
 				s_piece[np].dst = dst; s_piece[np].src = k - k0; s_piece[np].count = tail; s_piece[np].from_span = 0; np++;
 				/* an un-coupled end changes the context's final probability: the sentinel */
 			}
-			s_npiece = np; s_nseg = nseg; s_k0 = k0; s_oldlen = len; s_newlen = newlen; s_fail = fail ? 1u : 0u;
+			s_npiece = np; s_nseg = nseg; s_k0 = k0; s_oldlen = len; s_newlen = newlen; s_fail = fail;
 			s_k = k; s_ns = ns;
 			s_newtail = (CPOS(k) == MGL_POS_INF && in_seg) ? (p | 0x10000u) : 0u; /* new sentinel value if un-coupled */
 #undef CPOS
 #undef CEV
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) ctl->apply_failed = 1; continue; }
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } continue; }
 		APPLY_STAGE(2)
 		const uint32_t k0 = s_k0, oldlen = s_oldlen, newlen = s_newlen, kk = s_k, ns = s_ns, np = s_npiece;
 		/* ---- 3. the rewrite as copy jobs.  Pass B saves the old entries [k0, len] (only [k0, k) when the
@@ -589,12 +594,13 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 			s_job_c = atomicAdd(&ab.hdr[5], n_small + n_tail + (new_sentinel ? 1u : 0u));
 			s_span_base = atomicAdd(&ab.hdr[6], ns + 1u);
 			s_scr_base = atomicAdd(&ab.hdr[7], scratch_need);
-			if (s_job_b + n_save + n_prefix + n_sliver > ab.job_cap || s_job_c + n_small + n_tail + 1u > ab.job_cap ||
-			    s_span_base + ns + 1u > ab.span_cap || s_scr_base + scratch_need > ab.scratch_cap || (shift && ad > MGL_SUB_CAP))
-				s_fail = 1;
+			if (s_job_b + n_save + n_prefix + n_sliver > ab.job_cap || s_job_c + n_small + n_tail + 1u > ab.job_cap) s_fail |= MGL_GU_APPLY_JOBS;
+			if (s_span_base + ns + 1u > ab.span_cap) s_fail |= MGL_GU_APPLY_SPAN_AREA;
+			if (s_scr_base + scratch_need > ab.scratch_cap) s_fail |= MGL_GU_APPLY_SCRATCH;
+			if (shift && ad > lim.v[MGL_LIM_APPLY_SHIFT]) s_fail |= MGL_GU_APPLY_SHIFT;
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) ctl->apply_failed = 1; continue; }
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } continue; }
 		const uint32_t jb = s_job_b, jc = s_job_c, spb = s_span_base, scb = s_scr_base, noff = s_newoff;
 		for (uint32_t i = tid; i < ns; i += MGL_APPLY_THREADS) { ab.span_pos[spb + i] = s_span_pos[i]; ab.span_ev[spb + i] = s_span_ev[i]; }
 		if (tid == 0 && new_sentinel) { ab.span_pos[spb + ns] = MGL_POS_INF; ab.span_ev[spb + ns] = (uint16_t)(s_newtail & 0x7FFu); }

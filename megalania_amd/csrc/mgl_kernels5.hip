@@ -31,8 +31,14 @@
  *   k_apply_jobs      (mgl_kernels3.hip) carries out the job lists.
  *   k_batch_end       totals into Control.
  *
- * Anything that does not fit (more than MGL_BATCH_MAX moves, list / journal / span capacities, an invalid rep packet)
- * leaves the step to the full rebuild: both routes produce identical structures (tests/test_gpu_incremental.py).
+ * Anything that does not fit (more than MGL_BATCH_MAX moves, list / journal / span capacities, an invalid rep packet, a
+ * cluster's walk that has not re-joined the base at the next cluster's first journal entry) leaves the step to the full
+ * rebuild -- before anything is touched (clusters, walks: status 2) or behind the commit, while other workgroups have already
+ * rewritten their chains' descriptors (k_batch_chains: status 1): both routes produce identical structures
+ * (tests/test_gpu_accept_giveups.py takes every give-up site that a capacity reaches, the boundary guard and the forced
+ * give-up behind a partial rewrite, and compares with a rebuild; tests/test_gpu_incremental.py covers the route that does not
+ * give up).  What a site compares against comes in AcceptLimits (mgl_base2.h), which a test lowers; every give-up ORs its
+ * site's bit (MGL_GU_*) into *AcceptLimits::why.
  */
 #include "mgl_base2.h"
 
@@ -50,8 +56,10 @@
 
 struct BatchBuf {
 	uint32_t* hdr;      /* [0] status: 0 nothing to do, 1 batch accept, 2 left to the rebuild; [1] clusters; [2] inserted events,
-	                     * [3] removed events (combined lists); [4] failure seen by a kernel; [5] journal entries; [6] touched contexts */
-	uint32_t* cl;       /* per cluster, 8 words: first journal entry, journal entries, staged inserted, staged removed, ops, first target, - , - */
+	                     * [3] removed events (combined lists); [4] failure seen by a kernel (1 a walk gave up, 2 a walk met an invalid packet,
+	                     * 4 the clusters gave up); [5] journal entries; [6] touched contexts; [9] / [13] / [12] test hook (mgl_debug_set key 5):
+	                     * give up at the top of k_batch_chains / behind the [13]-th context's rewrite / contexts that got that far */
+	uint32_t* cl;       /* per cluster, 8 words: first journal entry, journal entries, staged inserted, staged removed, ops, -, -, - */
 	uint32_t* jpos;     /* merged journals, cluster after cluster */
 	mgl_pk* jnew;
 	mgl_pk* jold;
@@ -78,7 +86,7 @@ struct BatchBuf {
 #define MGL_OP_PLAIN 8u  /* position is a literal of the new walk: special bit off */
 
 /* ------------------------------------------------------------------ clusters */
-__global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control* ctl, NbrOut out, BulkBuf bb, BatchBuf bt)
+__global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control* ctl, NbrOut out, BulkBuf bb, BatchBuf bt, AcceptLimits lim)
 {
 	__shared__ uint32_t s_j[MGL_BATCH_MAX], s_t[MGL_BATCH_MAX], s_e[MGL_BATCH_MAX], s_nd[MGL_BATCH_MAX], s_ord[MGL_BATCH_MAX];
 	__shared__ uint32_t s_joff[MGL_BATCH_MAX + 1], s_cl[MGL_BATCH_MAX * 2];
@@ -89,7 +97,7 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 		s_bad = 0; s_ncl = 0;
 		bt.hdr[0] = m == 0 ? 0u : (m > MGL_BATCH_MAX ? 2u : 1u);
 		bt.hdr[1] = 0; bt.hdr[2] = 0; bt.hdr[3] = 0; bt.hdr[4] = 0; bt.hdr[5] = 0; bt.hdr[6] = 0;
-		bt.hdr[8] = 0;
+		bt.hdr[8] = 0; bt.hdr[12] = 0;
 		bt.hdr[7] = (uint32_t)bb.hdr[0]; /* acceptable neighbours of this step: the host sizes the next step's selection by it */
 		bt.acc[0] = 0; bt.acc[1] = 0; bt.acc[2] = 0;
 	}
@@ -98,7 +106,7 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 	(void)ctl; (void)c;
 	if (tid < m) {
 		const uint32_t j = bb.taken[tid];
-		s_j[tid] = j; s_t[tid] = out.win[2u * j]; s_e[tid] = out.win[2u * j + 1u]; s_nd[tid] = out.ndiffs[j];
+		s_j[tid] = j; s_t[tid] = out.win[2u * j]; s_e[tid] = lim.v[MGL_LIM_SOFT_REACH] ? (out.win2[j] & 0x7FFFFFFFu) : out.win[2u * j + 1u]; s_nd[tid] = out.ndiffs[j];
 	}
 	__syncthreads();
 	/* position order (targets are distinct: two neighbours with one target conflict) */
@@ -125,7 +133,7 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 		s_joff[m] = joff;
 		if (ncl) s_cl[(ncl - 1u) * 2u + 1u] = joff - s_cl[(ncl - 1u) * 2u];
 		s_ncl = ncl;
-		for (uint32_t q = 0; q < ncl; q++) if (s_cl[q * 2u + 1u] > MGL_BATCH_JCAP) s_bad = 1;
+		for (uint32_t q = 0; q < ncl; q++) if (s_cl[q * 2u + 1u] > lim.v[MGL_LIM_BATCH_JOURNAL]) s_bad = MGL_GU_CL_JOURNAL;
 	}
 	__syncthreads();
 	if (tid < s_ncl) { bt.cl[tid * 8u] = s_cl[tid * 2u]; bt.cl[tid * 8u + 1u] = s_cl[tid * 2u + 1u]; }
@@ -157,20 +165,20 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 			while (r2 < m && s_nd[s_ord[r2]] == 0) r2++;
 			nxt = r2 < m ? out.dpos[(size_t)s_j[s_ord[r2]] * MGL_MAX_DIFFS] : 0xFFFFFFFFu;
 		}
-		if (out.dpos[k] >= nxt) s_bad = 1;
+		if (out.dpos[k] >= nxt) atomicOr(&s_bad, MGL_GU_CL_ORDER);
 	}
 	__syncthreads();
 	if (tid == 0) {
 		bt.hdr[1] = s_ncl; bt.hdr[5] = tot;
-		if (s_bad) bt.hdr[0] = 2u;
+		if (s_bad) { bt.hdr[0] = 2u; bt.hdr[4] = 4u; atomicOr(lim.why, s_bad); } /* nothing has been touched: the rebuild takes the step */
 	}
 }
 
 /* ------------------------------------------------------------------ the walks (read-only on the base) */
-__device__ __forceinline__ void batch_op(const BatchBuf& bt, uint32_t cl, uint32_t& nops, bool& failed, uint32_t pos, uint32_t flags, uint32_t count,
+__device__ __forceinline__ void batch_op(const BatchBuf& bt, uint32_t cl, uint32_t& nops, uint32_t opcap, uint32_t& failed, uint32_t pos, uint32_t flags, uint32_t count,
                                          const mgl_wstate& st, uint32_t lane)
 {
-	if (nops >= MGL_BATCH_OPCAP) { failed = true; return; }
+	if (nops >= opcap) { failed |= MGL_GU_WALK_OPS; return; }
 	if (lane == 0) {
 		uint4* o = bt.ops + ((size_t)cl * MGL_BATCH_OPCAP + nops) * 2u;
 		o[0] = make_uint4(pos, flags | (count << 8), st.ctx_state, st.dists[0]);
@@ -188,7 +196,7 @@ __device__ __forceinline__ bool batch_rep_ok(const DevCtx& c, uint32_t p, uint32
 	return __ballot(bad) == 0;
 }
 
-__global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf bt)
+__global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf bt, AcceptLimits lim)
 {
 	__shared__ uint32_t s_jpos[MGL_BATCH_JCAP];
 	__shared__ mgl_pk s_jnew[MGL_BATCH_JCAP];
@@ -199,6 +207,10 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 	for (uint32_t i = lane; i < nd; i += 64) { s_jpos[i] = bt.jpos[j0 + i]; s_jnew[i] = bt.jnew[j0 + i]; }
 	wave_sync();
 	const uint32_t t = s_jpos[0], last_j = s_jpos[nd - 1];
+	/* the next cluster's walk starts at its first journal entry, from the OLD base's state there: this walk has to have re-joined
+	 * the base by then, and may not touch a packet of either walk at or behind it */
+	const uint32_t next_first = cl + 1u < bt.hdr[1] ? bt.jpos[j0 + nd] : MGL_POS_INF;
+	const uint32_t evcap = lim.v[MGL_LIM_BATCH_EVENTS], opcap = lim.v[MGL_LIM_BATCH_OPS];
 	uint16_t* ikey = bt.st_ikey + (size_t)cl * MGL_BATCH_EVCAP; uint32_t* ipos = bt.st_ipos + (size_t)cl * MGL_BATCH_EVCAP;
 	uint16_t* rkey = bt.st_rkey + (size_t)cl * MGL_BATCH_EVCAP; uint32_t* rpos = bt.st_rpos + (size_t)cl * MGL_BATCH_EVCAP;
 
@@ -208,19 +220,22 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 	uint32_t n_ins = 0, n_rem = 0, nops = 0;
 	int32_t dpackets = 0;
 	long long ddirect = 0;
-	bool failed = false, invalid = false;
+	uint32_t failed = 0; /* the give-up sites' bits */
+	bool invalid = false;
 	uint32_t ji = 0, guard = 0;
 	while (nb.pos < c.n || bs.pos < c.n) {
-		if (failed || ++guard > (1u << 18)) { failed = true; break; }
+		if (failed) break;
+		if (++guard > lim.v[MGL_LIM_BATCH_GUARD]) { failed = MGL_GU_WALK_GUARD; break; }
 		if (nb.pos == bs.pos) {
 			const bool same_ctx = nb.ctx_state == bs.ctx_state;
 			const bool same_d = nb.dists[0] == bs.dists[0] && nb.dists[1] == bs.dists[1] && nb.dists[2] == bs.dists[2] && nb.dists[3] == bs.dists[3];
-			if (same_ctx && same_d && nb.pos > last_j) break;
-			if (same_ctx && nb.ctx_state < 7) {
+			if (same_ctx && same_d && nb.pos > last_j) break; /* (exactly at next_first: the normal end of a cluster that has a neighbour) */
+			if (same_ctx && nb.ctx_state < 7 && nb.pos < next_first) {
 				uint32_t s = uni(sp_find_next(b, nb.pos));
 				if (s == MGL_POS_INF || s > c.n) s = c.n;
 				while (ji < nd && s_jpos[ji] < nb.pos) ji++;
 				if (ji < nd && s_jpos[ji] < s) s = s_jpos[ji];
+				if (next_first < s) s = next_first; /* (a jump may not carry the walk across the boundary unseen) */
 				if (s > nb.pos) {
 					const uint32_t cs = lit_steps(nb.ctx_state, s - nb.pos);
 					nb.pos = bs.pos = s; nb.ctx_state = bs.ctx_state = cs;
@@ -228,6 +243,9 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 				}
 			}
 		}
+		/* not re-joined, and the next packet of one of the walks lies in the next cluster's range: that cluster reads it with the old
+		 * packets and the old state, so the two would disagree about it -- the step is the rebuild's (nothing has been touched) */
+		if ((nb.pos < bs.pos ? nb.pos : bs.pos) >= next_first) { failed = MGL_GU_WALK_OVERRUN; break; }
 		if (nb.pos <= bs.pos && nb.pos < c.n) {
 			const uint32_t p = nb.pos;
 			win_cover(win, c, b.slab, p, lane);
@@ -258,9 +276,9 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 				if (paired) plan_at(c, bs, btype, bdist, blen, win_byte(win, p), bpl);
 			}
 			/* p is on the new walk; special iff not a literal, with the state before it */
-			batch_op(bt, cl, nops, failed, p, (paired ? 0u : MGL_OP_ON) | (ntype != MGL_LITERAL ? MGL_OP_SPEC : MGL_OP_PLAIN), 1u, nb, lane);
+			batch_op(bt, cl, nops, opcap, failed, p, (paired ? 0u : MGL_OP_ON) | (ntype != MGL_LITERAL ? MGL_OP_SPEC : MGL_OP_PLAIN), 1u, nb, lane);
 			if (!cancelled) {
-				if (n_ins + npl.nev > MGL_BATCH_EVCAP || (paired && n_rem + bpl.nev > MGL_BATCH_EVCAP)) { failed = true; break; }
+				if (n_ins + npl.nev > evcap || (paired && n_rem + bpl.nev > evcap)) { failed = MGL_GU_WALK_EVENTS; break; }
 				if (lane < npl.nev) {
 					uint32_t ctx, bit;
 					mgl_plan_event(&npl, lane, &ctx, &bit);
@@ -291,12 +309,13 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 				const uint32_t o = q - win.base;
 				const unsigned long long lit = __ballot(mgl_pk_type(win.pk) == MGL_LITERAL) >> o;
 				uint32_t run = ~lit == 0ull ? 64u : (uint32_t)__ffsll((long long)~lit) - 1u;
-				const uint32_t limit = (nb.pos < c.n ? nb.pos : c.n) - q;
+				uint32_t limit = nb.pos < c.n ? nb.pos : c.n;
+				limit = (limit < next_first ? limit : next_first) - q;
 				run = run < 64u - o ? run : 64u - o;
 				run = run < limit ? run : limit;
 				if (run >= 2u) {
 					const uint32_t take = run < 7u ? run : 7u;
-					if (n_rem + 9u * take > MGL_BATCH_EVCAP) { failed = true; break; }
+					if (n_rem + 9u * take > evcap) { failed = MGL_GU_WALK_EVENTS; break; }
 					const uint32_t i = lane / 9u, slot = lane - i * 9u, p = q + i;
 					const bool active = i < take;
 					const uint32_t byte = (uint32_t)__shfl((int)win.byte, (int)((p - win.base) & 63u), 64);
@@ -317,7 +336,7 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 							rpos[n_rem + i * 9u + slot] = p;
 								}
 						n_rem += 9u * take;
-						batch_op(bt, cl, nops, failed, q, MGL_OP_OFF, take, bs, lane);
+						batch_op(bt, cl, nops, opcap, failed, q, MGL_OP_OFF, take, bs, lane);
 						dpackets -= (int32_t)take;
 						bs.pos += take; bs.ctx_state = lit_steps(bs.ctx_state, take);
 						continue;
@@ -328,7 +347,7 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 			const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
 			mgl_plan bpl;
 			plan_at(c, bs, btype, bdist, blen, win_byte(win, q), bpl);
-			if (n_rem + bpl.nev > MGL_BATCH_EVCAP) { failed = true; break; }
+			if (n_rem + bpl.nev > evcap) { failed = MGL_GU_WALK_EVENTS; break; }
 			if (lane < bpl.nev) {
 				uint32_t ctx, bit;
 				mgl_plan_event(&bpl, lane, &ctx, &bit);
@@ -337,7 +356,7 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 			}
 			n_rem += bpl.nev;
 			ddirect -= (long long)((uint64_t)bpl.ndirect << 11);
-			batch_op(bt, cl, nops, failed, q, MGL_OP_OFF, 1u, bs, lane);
+			batch_op(bt, cl, nops, opcap, failed, q, MGL_OP_OFF, 1u, bs, lane);
 			dpackets -= 1;
 			mgl_advance(&bs, btype, bdist, blen);
 		}
@@ -345,7 +364,7 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 	wave_sync();
 	if (lane == 0) {
 		bt.cl[cl * 8u + 2u] = n_ins; bt.cl[cl * 8u + 3u] = n_rem; bt.cl[cl * 8u + 4u] = nops;
-		if (failed || invalid) atomicOr(&bt.hdr[4], invalid ? 2u : 1u);
+		if (failed || invalid) { atomicOr(&bt.hdr[4], invalid ? 2u : 1u); atomicOr(lim.why, failed | (invalid ? MGL_GU_WALK_INVALID : 0u)); }
 		atomicAdd((unsigned long long*)&bt.acc[1], (unsigned long long)ddirect);
 		atomicAdd((unsigned long long*)&bt.acc[2], (unsigned long long)(long long)dpackets);
 	}
@@ -713,7 +732,7 @@ __device__ __forceinline__ RunOut batch_run_wave(const uint32_t* cpos, const uin
 	return r;
 }
 
-__global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Base2 b, Control* ctl, BatchBuf bt, ApplyBuf ab)
+__global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Base2 b, Control* ctl, BatchBuf bt, ApplyBuf ab, AcceptLimits lim)
 {
 	__shared__ __attribute__((aligned(16))) uint16_t T[2048];
 	__shared__ uint32_t s_ipos[MGL_BATCH_SUB], s_rpos[MGL_BATCH_SUB], s_upos[MGL_BATCH_SUB];
@@ -727,7 +746,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 	__shared__ int32_t s_hdelta[MGL_BATCH_MAX + 1]; /* length change accumulated up to and including head h */
 	__shared__ uint32_t s_ng, s_nh, s_fail, s_scr_base, s_job_b, s_job_c, s_newoff, s_newcap, s_newlen, s_maxd;
 	if (bt.hdr[0] != 1u || bt.hdr[4]) return;
-	if (bt.hdr[9]) { if (blockIdx.x == 0 && threadIdx.x == 0) ctl->apply_failed = 1; return; } /* test hook (mgl_debug_set key 5): give up behind the commit */
+	if (bt.hdr[9]) { if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->apply_failed = 1; atomicOr(lim.why, MGL_GU_FORCED_EARLY); } return; } /* test hook (mgl_debug_set key 5): give up behind the commit */
 	/* one workgroup per touched context (k_batch_scan lists them: a tenth of the contexts on a step of fifteen moves), the
 	 * grid strides over the list */
 	const uint32_t ntouched = bt.hdr[10];
@@ -737,7 +756,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 	for (uint32_t w = blockIdx.x; w < ntouched; w += gridDim.x) {
 		const uint32_t cx = bt.touched[w];
 		const uint32_t ni = bt.cnt_i[cx], nr = bt.cnt_r[cx];
-		if (ni > MGL_BATCH_SUB || nr > MGL_BATCH_SUB) { if (tid == 0) ctl->apply_failed = 1; return; }
+		if (ni > lim.v[MGL_LIM_BATCH_SUB] || nr > lim.v[MGL_LIM_BATCH_SUB]) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, MGL_GU_CH_SUB); } return; }
 		long long my_cost = 0; /* thread 0 sums the context's runs */
 		__syncthreads(); /* (the shared arrays are the previous context's until here) */
 		if (tid == 0) s_fail = 0;
@@ -798,18 +817,18 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 				if (lane == 0) at = atomicAdd(&ab.hdr[6], res + 8u);
 				at = uni(at);
 				if (lane == 0) s_gat[g] = at;
-				if (at + res + 8u > ab.span_cap) { s_fail = 1; continue; }
+				if (at + res + 8u > ab.span_cap) { s_fail = MGL_GU_CH_SPAN_AREA; continue; }
 				const RunOut rr = batch_run_wave<true>(cpos, cev, len, T, s_ipos, s_ibit, s_icl, ni, s_rpos, s_rcl, nr, s_gi[g], s_gr[g], s_gcl, g, ab.span_pos, ab.span_ev, at, res, sb_row, sb_info, lane);
 				if (lane == 0) s_run[g] = rr;
 			}
 		} else if (tid < ng) {
 			const uint32_t at = atomicAdd(&ab.hdr[6], res + 8u); /* (+ the spare entry the tail loop writes to instead of branching) */
 			s_gat[tid] = at;
-			if (at + res + 8u > ab.span_cap) s_fail = 1;
+			if (at + res + 8u > ab.span_cap) s_fail = MGL_GU_CH_SPAN_AREA;
 			else s_run[tid] = batch_run<true>(cpos, cev, len, T, s_ipos, s_ibit, s_icl, ni, s_rpos, s_rcl, nr, s_gi[tid], s_gr[tid], s_gcl, tid, ab.span_pos, ab.span_ev, at, res, sb_row, sb_info);
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) ctl->apply_failed = 1; return; }
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
 		/* ---- 4. ... the ones that count begin where the previous one ended */
 		if (tid == 0) {
 			uint32_t nh = 0, maxd = 0;
@@ -829,17 +848,17 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			const uint32_t newlen = (uint32_t)((int32_t)len + d); /* (a run that ends at the sentinel un-coupled replaces everything up to it, and writes a new one) */
 			s_newlen = newlen;
 			uint32_t newoff = off, newcap = cap;
-			bool fail = maxd > 2047u;
+			uint32_t fail = maxd > lim.v[MGL_LIM_BATCH_SHIFT] ? MGL_GU_CH_SHIFT : 0u;
 			if (!fail && newlen + 1u > cap) { /* the chain outgrew its slot: fresh space at the top of the pool */
 				newcap = (2u * (newlen + 1u) + 256u + 7u) & ~7u;
 				newoff = atomicAdd(b.pool_top, newcap);
-				if (newoff + newcap > b.pool_cap) fail = true;
+				if (newoff + newcap > b.pool_cap) fail = MGL_GU_CH_POOL;
 			}
 			s_newoff = newoff; s_newcap = newcap;
-			s_fail = fail ? 1u : 0u;
+			s_fail = fail;
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) ctl->apply_failed = 1; return; }
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
 		const uint32_t nh = s_nh, noff = s_newoff, maxd = s_maxd;
 		const bool moved = noff != off;
 		/* ---- 5. a run that counts and did not fit its place: again, into one of its size; the new sentinel behind a run that
@@ -854,7 +873,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 					at = 0;
 					if (lane == 0) at = atomicAdd(&ab.hdr[6], spn + 1u);
 					at = uni(at);
-					if (at + spn + 1u > ab.span_cap) { s_fail = 1; continue; }
+					if (at + spn + 1u > ab.span_cap) { s_fail = MGL_GU_CH_SPAN_RERUN; continue; }
 					if (lane == 0) s_hspan[h] = at;
 					(void)batch_run_wave<true>(cpos, cev, len, T, s_ipos, s_ibit, s_icl, ni, s_rpos, s_rcl, nr, s_gi[g], s_gr[g], s_gcl, g, ab.span_pos, ab.span_ev, at, spn, sb_row, sb_info, lane);
 				}
@@ -867,7 +886,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			uint32_t at = s_hspan[tid];
 			if (at == 0xFFFFFFFFu) {
 				at = atomicAdd(&ab.hdr[6], spn + 1u);
-				if (at + spn + 1u > ab.span_cap) s_fail = 1;
+				if (at + spn + 1u > ab.span_cap) s_fail = MGL_GU_CH_SPAN_RERUN;
 				else {
 					s_hspan[tid] = at;
 					(void)batch_run<true>(cpos, cev, len, T, s_ipos, s_ibit, s_icl, ni, s_rpos, s_rcl, nr, s_gi[g], s_gr[g], s_gcl, g, ab.span_pos, ab.span_ev, at, spn, sb_row, sb_info);
@@ -876,7 +895,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			if (!s_fail && r0.uncoupled) { ab.span_pos[at + r0.ns] = MGL_POS_INF; ab.span_ev[at + r0.ns] = (uint16_t)r0.end_p; }
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) ctl->apply_failed = 1; return; }
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
 		/* ---- 6. the rewrite as copy jobs.  Pieces in chain order: [prefix] run 0, stretch 0, run 1, stretch 1, ... ; stretch h
 		 * = old entries [k_end(h), k_start(h + 1)) (the last one runs to the sentinel, included) and moves by the length change
 		 * accumulated up to run h.  In place: a stretch that does not move is left alone; one that moves goes in chunks that
@@ -903,10 +922,11 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			s_job_b = atomicAdd(&ab.hdr[4], jb);
 			s_job_c = atomicAdd(&ab.hdr[5], jc);
 			s_scr_base = atomicAdd(&ab.hdr[7], scr);
-			if (s_job_b + jb > ab.job_cap || s_job_c + jc > ab.job_cap || s_scr_base + scr > ab.scratch_cap) s_fail = 1;
+			if (s_job_b + jb > ab.job_cap || s_job_c + jc > ab.job_cap) s_fail |= MGL_GU_CH_JOBS;
+			if (s_scr_base + scr > ab.scratch_cap) s_fail |= MGL_GU_CH_SCRATCH;
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) ctl->apply_failed = 1; return; }
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
 		{
 			const uint32_t jb0 = s_job_b, jc0 = s_job_c, scr0 = s_scr_base;
 			const uint32_t pre = moved ? (s_run[s_hlist[0]].k_start + MGL_JOB_CHUNK - 1u) / MGL_JOB_CHUNK : 0u; /* the prefix's jobs lead pass B's list */
@@ -949,10 +969,15 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			if (tid == 0) {
 				b.ch_len[cx] = s_newlen;
 				if (moved) { b.ch_off[cx] = noff; b.ch_cap[cx] = s_newcap; }
+				/* test hook (mgl_debug_set key 5, high word = n): the n-th context to get this far gives up -- a give-up behind a
+				 * partial rewrite: other workgroups have rewritten their chains' descriptors, taken pool space, patched index rows
+				 * and queued jobs, and go on doing so */
+				if (bt.hdr[13] && atomicAdd(&bt.hdr[12], 1u) + 1u == bt.hdr[13]) s_fail = MGL_GU_FORCED_LATE;
 			}
 		}
 		/* ---- 6b. the chain index of this context (nothing searches the old chain any more) */
 		__syncthreads();
+		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
 		{
 			const uint32_t first = ((ni ? s_ipos[0] : MGL_POS_INF) < (nr ? s_rpos[0] : MGL_POS_INF)) ? s_ipos[0] : s_rpos[0];
 			for (uint32_t blk = (first >> b.sb_shift) + 1u + tid; blk <= b.nsb; blk += blockDim.x) {
@@ -974,7 +999,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			if (at < bt.runs_cap) {
 				bt.runs[2u * at] = make_uint4(cx, r.lo, r.hi, s_hspan[tid]);
 				bt.runs[2u * at + 1u] = make_uint4(r.ns, r.end_p, 0u, 0u);
-			} else ctl->apply_failed = 1;
+			} else { ctl->apply_failed = 1; atomicOr(lim.why, MGL_GU_CH_RUNS); }
 		}
 		if (tid == 0 && my_cost) atomicAdd((unsigned long long*)&bt.acc[0], (unsigned long long)my_cost);
 	}

@@ -1113,6 +1113,102 @@ uint64_t orc_bulk_rollbacks(void) { return g_bulk_rollbacks; }
 static uint64_t g_bulk_overlaps;
 uint64_t orc_bulk_overlaps(void) { return g_bulk_overlaps; }
 
+/* The device's batch accept (mgl_kernels5.hip) restated: the taken moves of a bulk step in target order form clusters -- a new
+ * one where a move's target lies at or behind `reach`, the largest hard window end so far -- and every cluster's merged journal
+ * is walked against the old slab from its first entry until position, ctx_state and the four rep distances agree again behind
+ * its last entry.  The device starts the next cluster's walk from the OLD state at that cluster's first entry, so a walk that
+ * has not re-joined by then would make the two disagree (the device's walk gives the step to the rebuild there).  Counted:
+ * clusters whose re-join point lies behind the next cluster's first entry.  The table of the last bulk step that took moves
+ * stays readable (orc_bulk_cluster_table). */
+static uint64_t g_bulk_cluster_overruns;
+uint64_t orc_bulk_cluster_overruns(void) { return g_bulk_cluster_overruns; }
+/* the same count under the device's test knob (mgl_debug_set key 6, limit 18: clusters split at the members' SOFT ends, a wrong
+ * rule on purpose): the steps on which the device's boundary guard has to fire when a test switches the knob on */
+static uint64_t g_bulk_soft_overruns;
+uint64_t orc_bulk_soft_overruns(void) { return g_bulk_soft_overruns; }
+#define ORC_CL_WORDS 6u  /* first entry, last entry, re-join point, next cluster's first entry (~0: none), members, first member */
+#define ORC_CLM_WORDS 5u /* neighbour, target, end, soft end, dep */
+static uint32_t* g_cl_tab; static size_t g_cl_count, g_cl_cap;
+static uint32_t* g_clm_tab; static size_t g_clm_count, g_clm_cap;
+/* clusters / members of the last bulk step that took moves: up to cap_* rows are copied, the counts are returned */
+size_t orc_bulk_cluster_table(uint32_t* clusters, size_t cap_clusters, uint32_t* members, size_t cap_members, size_t* nmembers)
+{
+	const size_t nc = g_cl_count < cap_clusters ? g_cl_count : cap_clusters, nm = g_clm_count < cap_members ? g_clm_count : cap_members;
+	if (clusters && nc) memcpy(clusters, g_cl_tab, sizeof(uint32_t) * ORC_CL_WORDS * nc);
+	if (members && nm) memcpy(members, g_clm_tab, sizeof(uint32_t) * ORC_CLM_WORDS * nm);
+	if (nmembers) *nmembers = g_clm_count;
+	return g_cl_count;
+}
+typedef struct { uint32_t target, j; } cl_order;
+static int cl_order_cmp(const void* a, const void* b)
+{
+	const cl_order* x = (const cl_order*)a; const cl_order* y = (const cl_order*)b;
+	return x->target < y->target ? -1 : x->target > y->target ? 1 : (x->j < y->j ? -1 : x->j > y->j);
+}
+/* old: the slab before the step; diffs / nd / win / take as in orc_sa_batched; soft_reach: the device's test knob (clusters split
+ * at the soft ends).  Fills the table; returns the clusters that overran. */
+static size_t bulk_clusters(const orc_ctx* c, const orc_packet* old, const orc_diff* diffs, const size_t* nd, const uint32_t* win,
+                            const uint8_t* take, uint32_t K, int soft_reach)
+{
+	cl_order* ord = (cl_order*)malloc(sizeof(cl_order) * (K ? K : 1));
+	size_t m = 0;
+	for (uint32_t j = 0; j < K; j++) if (take[j] && nd[j]) { ord[m].target = win[4 * (size_t)j]; ord[m].j = j; m++; }
+	qsort(ord, m, sizeof *ord, cl_order_cmp);
+	if (m > g_clm_cap) { g_clm_cap = m; g_clm_tab = (uint32_t*)realloc(g_clm_tab, sizeof(uint32_t) * ORC_CLM_WORDS * m); g_cl_cap = m; g_cl_tab = (uint32_t*)realloc(g_cl_tab, sizeof(uint32_t) * ORC_CL_WORDS * m); }
+	g_cl_count = 0; g_clm_count = m;
+	uint32_t reach = 0;
+	for (size_t r = 0; r < m; r++) {
+		const uint32_t j = ord[r].j;
+		const uint32_t* w = win + 4 * (size_t)j;
+		uint32_t lo = ~0u, hi = 0;
+		for (size_t e = 0; e < nd[j]; e++) {
+			const uint32_t p = diffs[(size_t)j * ORC_MAX_JOURNAL + e].position;
+			lo = p < lo ? p : lo; hi = p > hi ? p : hi;
+		}
+		if (g_cl_count == 0 || w[0] >= reach) {
+			uint32_t* row = g_cl_tab + ORC_CL_WORDS * g_cl_count++;
+			row[0] = lo; row[1] = hi; row[2] = 0; row[3] = ~0u; row[4] = 0; row[5] = (uint32_t)r;
+		}
+		uint32_t* row = g_cl_tab + ORC_CL_WORDS * (g_cl_count - 1);
+		row[0] = lo < row[0] ? lo : row[0]; row[1] = hi > row[1] ? hi : row[1]; row[4]++;
+		uint32_t* mr = g_clm_tab + ORC_CLM_WORDS * r;
+		mr[0] = j; mr[1] = w[0]; mr[2] = w[1]; mr[3] = w[2]; mr[4] = w[3];
+		const uint32_t e_ = soft_reach ? w[2] : w[1];
+		reach = e_ > reach ? e_ : reach;
+	}
+	/* the walks: old slab against old slab + this cluster's journals */
+	orc_packet* nw = (orc_packet*)malloc(sizeof(orc_packet) * c->n);
+	memcpy(nw, old, sizeof(orc_packet) * c->n);
+	wstate w0; memset(&w0, 0, sizeof w0); /* the old walk's state, carried from cluster to cluster */
+	size_t over = 0;
+	for (size_t q = 0; q < g_cl_count; q++) {
+		uint32_t* row = g_cl_tab + ORC_CL_WORDS * q;
+		if (q + 1 < g_cl_count) row[3] = row[ORC_CL_WORDS];
+		for (size_t r = row[5]; r < row[5] + row[4]; r++) {
+			const uint32_t j = g_clm_tab[ORC_CLM_WORDS * r];
+			for (size_t e = 0; e < nd[j]; e++) nw[diffs[(size_t)j * ORC_MAX_JOURNAL + e].position] = diffs[(size_t)j * ORC_MAX_JOURNAL + e].new_packet;
+		}
+		while (w0.pos < row[0]) wstate_advance(&w0, old[w0.pos]);
+		wstate nb = w0, bs = w0; /* (w0.pos == row[0]: a cluster's first entry is a packet of the old walk) */
+		while (nb.pos < c->n || bs.pos < c->n) {
+			if (nb.pos == bs.pos && wstate_same(&nb, &bs) && nb.pos > row[1]) break;
+			if (nb.pos <= bs.pos && nb.pos < c->n) {
+				const int paired = bs.pos == nb.pos;
+				if (paired) wstate_advance(&bs, old[bs.pos]);
+				wstate_advance(&nb, nw[nb.pos]);
+			} else wstate_advance(&bs, old[bs.pos]);
+		}
+		row[2] = (uint32_t)(nb.pos > bs.pos ? nb.pos : bs.pos);
+		if (w0.pos != row[0] || row[2] > row[3]) over++;
+		for (size_t r = row[5]; r < row[5] + row[4]; r++) {
+			const uint32_t j = g_clm_tab[ORC_CLM_WORDS * r];
+			for (size_t e = 0; e < nd[j]; e++) nw[diffs[(size_t)j * ORC_MAX_JOURNAL + e].position] = old[diffs[(size_t)j * ORC_MAX_JOURNAL + e].position];
+		}
+	}
+	free(nw); free(ord);
+	return over;
+}
+
 static int windows_conflict(const uint32_t* x, const uint32_t* y)
 {
 	const uint32_t* a = x[0] <= y[0] ? x : y;
@@ -1219,6 +1315,10 @@ int orc_sa_batched(orc_ctx* c, orc_packet* slab, orc_packet* best, uint64_t* cur
 			for (uint32_t j = 0; j < K; j++)
 				if (keys[j] != ~0ull && fin[j] == 1) { take[j] = 1; ntaken++; }
 			free(st);
+		}
+		if (bulk && ntaken) { /* (the slab is still the old one; the table that stays is the real rule's) */
+			g_bulk_soft_overruns += bulk_clusters(c, slab, diffs, nd, win, take, K, 1) ? 1u : 0u;
+			g_bulk_cluster_overruns += bulk_clusters(c, slab, diffs, nd, win, take, K, 0);
 		}
 		for (uint32_t j = 0; j < K; j++) {
 			if (!take[j]) continue;

@@ -61,6 +61,56 @@ def walk(slab: np.ndarray):
     return out
 
 
+def canonical_base(sa, slab):
+    """The incremental engine's base structures (a megalania_amd.binding.SA handle) in an offset-independent form."""
+    n, total = sa.n, sa.nprobs
+    off = sa.debug_dump(0, np.uint32)
+    ln = sa.debug_dump(1, np.uint32)
+    cap = sa.debug_dump(8, np.uint32)
+    cpos = sa.debug_dump(2, np.uint32)
+    cev = sa.debug_dump(3, np.uint16)
+    chains = []
+    for c in range(total):
+        k, m = int(off[c]), int(ln[c])
+        assert m + 1 <= cap[c], c
+        chains.append((cpos[k:k + m + 1].copy(), cev[k:k + m + 1].copy()))
+    # every chain has its slot to itself, below the pool's top: a give-up that leaks or double-books pool space would pass every
+    # comparison of contents until a later step writes through it
+    top = int(sa.debug_dump(85, np.uint32)[0])
+    by_off = np.argsort(off[:total].astype(np.int64), kind="stable")
+    o64, c64 = off[:total].astype(np.int64)[by_off], cap[:total].astype(np.int64)[by_off]
+    clash = np.nonzero(o64[:-1] + c64[:-1] > o64[1:])[0]
+    assert len(clash) == 0, ("chain slots overlap", [(int(by_off[i]), int(by_off[i + 1])) for i in clash[:5]])
+    assert int((o64 + c64).max()) <= top, ("chain slot above the pool top", int(by_off[np.argmax(o64 + c64)]), top)
+    on = np.unpackbits(sa.debug_dump(4, np.uint64).view(np.uint8), bitorder="little")[:n].astype(bool)
+    sp = np.unpackbits(sa.debug_dump(5, np.uint64).view(np.uint8), bitorder="little")[:n].astype(bool)
+    st = sa.debug_dump(6, np.uint32).reshape(n, 8)[:, :5]
+    ck = sa.debug_dump(7, np.uint16).reshape(-1, (total + 7) // 8 * 8)[:, :total]
+    # the chain index is checked against the chains it indexes, here, whoever built or patched it: entry [c][b] = entries of
+    # context c's chain with a position below b << shift (the last column: the chain's length)
+    shift = 8 if n <= (1 << 20) else 9 if n <= (1 << 23) else 10
+    nsb = (n + (1 << shift) - 1) >> shift
+    stride = (nsb + 2 + 3) & ~3
+    idx = sa.debug_dump(83, np.uint32).reshape(-1, stride)
+    bounds = (np.arange(nsb + 1, dtype=np.int64) << shift)
+    for c in range(total):
+        pos = chains[c][0][:-1].astype(np.int64)
+        want = np.searchsorted(pos, bounds, side="left")
+        want[nsb] = len(pos)
+        assert (idx[c, : nsb + 1] == want).all(), ("chain index", c, np.nonzero(idx[c, : nsb + 1] != want)[0][:5])
+    return dict(chains=chains, on=on, sp=sp, st=st[sp], ck=ck)
+
+
+def assert_same_base(a, b, what):
+    assert (a["on"] == b["on"]).all(), what
+    assert (a["sp"] == b["sp"]).all(), what
+    assert (a["st"] == b["st"]).all(), (what, np.nonzero((a["st"] != b["st"]).any(axis=1))[0][:5])
+    for c, (x, y) in enumerate(zip(a["chains"], b["chains"])):
+        assert len(x[0]) == len(y[0]) and (x[0] == y[0]).all() and (x[1] == y[1]).all(), (what, "chain", c)
+    bad = np.nonzero((a["ck"] != b["ck"]).any(axis=1))[0]
+    assert len(bad) == 0, (what, "checkpoints", bad[:5], np.nonzero(a["ck"][bad[0]] != b["ck"][bad[0]])[0][:5])
+
+
 def _build_oracle():
     if not os.path.exists(ORACLE_SO) or os.path.getmtime(ORACLE_SO) < os.path.getmtime(
         os.path.join(ROOT, "oracle", "mgl_oracle.c")
@@ -108,6 +158,12 @@ class Oracle:
             L.orc_bulk_rollbacks.argtypes = []
             L.orc_bulk_overlaps.restype = C.c_uint64
             L.orc_bulk_overlaps.argtypes = []
+            L.orc_bulk_cluster_overruns.restype = C.c_uint64
+            L.orc_bulk_cluster_overruns.argtypes = []
+            L.orc_bulk_soft_overruns.restype = C.c_uint64
+            L.orc_bulk_soft_overruns.argtypes = []
+            L.orc_bulk_cluster_table.restype = C.c_size_t
+            L.orc_bulk_cluster_table.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
             L.orc_neighbour_ex.restype = C.c_int
             L.orc_neighbour_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -248,6 +304,27 @@ class Oracle:
     def bulk_overlaps(self) -> int:
         """slab entries that two taken journals of one bulk step both wrote, since the library was loaded"""
         return int(self.L.orc_bulk_overlaps())
+
+    def bulk_cluster_overruns(self) -> int:
+        """clusters of bulk steps (the device's batch accept restated: a new cluster where a taken move's target lies at or behind
+        the largest hard end so far) whose merged walk had not re-joined the old slab at the next cluster's first journal entry,
+        since the library was loaded"""
+        return int(self.L.orc_bulk_cluster_overruns())
+
+    def bulk_soft_overruns(self) -> int:
+        """bulk steps with such a cluster when clusters are split at the SOFT ends (the device's test knob, limit 18)"""
+        return int(self.L.orc_bulk_soft_overruns())
+
+    def bulk_cluster_table(self):
+        """the last bulk step that took moves: clusters as dicts (first / last journal entry, re-join point, the next cluster's
+        first entry or None, members) with members as (neighbour, target, end, soft end, dep), in target order"""
+        cl = np.zeros((4096, 6), dtype=np.uint32)
+        mb = np.zeros((4096, 5), dtype=np.uint32)
+        nm = C.c_size_t(0)
+        nc = self.L.orc_bulk_cluster_table(ptr(cl), len(cl), ptr(mb), len(mb), C.addressof(nm))
+        assert nc <= len(cl) and nm.value <= len(mb)
+        return [dict(first=int(r[0]), last=int(r[1]), rejoin=int(r[2]), next_first=None if r[3] == 0xFFFFFFFF else int(r[3]),
+                     members=[tuple(int(x) for x in mb[k]) for k in range(int(r[5]), int(r[5]) + int(r[4]))]) for r in cl[:nc]]
 
     def emit(self, slab) -> bytes:
         cap = 2 * self.n + 1024

@@ -6,7 +6,7 @@ import lzma
 import numpy as np
 import pytest
 
-from _libs import Oracle, literal_slab, walk
+from _libs import Oracle, assert_same_base, canonical_base, literal_slab, walk
 from conftest import slab_from_rle
 from megalania_amd import binding, corpus
 
@@ -134,48 +134,6 @@ def test_engines_agree_on_c2_neighbours():
     full.close()
 
 
-def canonical_base(sa, slab):
-    """The incremental engine's base structures in an offset-independent form."""
-    n, total = sa.n, sa.nprobs
-    off = sa.debug_dump(0, np.uint32)
-    ln = sa.debug_dump(1, np.uint32)
-    cap = sa.debug_dump(8, np.uint32)
-    cpos = sa.debug_dump(2, np.uint32)
-    cev = sa.debug_dump(3, np.uint16)
-    chains = []
-    for c in range(total):
-        k, m = int(off[c]), int(ln[c])
-        assert m + 1 <= cap[c], c
-        chains.append((cpos[k:k + m + 1].copy(), cev[k:k + m + 1].copy()))
-    on = np.unpackbits(sa.debug_dump(4, np.uint64).view(np.uint8), bitorder="little")[:n].astype(bool)
-    sp = np.unpackbits(sa.debug_dump(5, np.uint64).view(np.uint8), bitorder="little")[:n].astype(bool)
-    st = sa.debug_dump(6, np.uint32).reshape(n, 8)[:, :5]
-    ck = sa.debug_dump(7, np.uint16).reshape(-1, (total + 7) // 8 * 8)[:, :total]
-    # the chain index is checked against the chains it indexes, here, whoever built or patched it: entry [c][b] = entries of
-    # context c's chain with a position below b << shift (the last column: the chain's length)
-    shift = 8 if n <= (1 << 20) else 9 if n <= (1 << 23) else 10
-    nsb = (n + (1 << shift) - 1) >> shift
-    stride = (nsb + 2 + 3) & ~3
-    idx = sa.debug_dump(83, np.uint32).reshape(-1, stride)
-    bounds = (np.arange(nsb + 1, dtype=np.int64) << shift)
-    for c in range(total):
-        pos = chains[c][0][:-1].astype(np.int64)
-        want = np.searchsorted(pos, bounds, side="left")
-        want[nsb] = len(pos)
-        assert (idx[c, : nsb + 1] == want).all(), ("chain index", c, np.nonzero(idx[c, : nsb + 1] != want)[0][:5])
-    return dict(chains=chains, on=on, sp=sp, st=st[sp], ck=ck)
-
-
-def assert_same_base(a, b, what):
-    assert (a["on"] == b["on"]).all(), what
-    assert (a["sp"] == b["sp"]).all(), what
-    assert (a["st"] == b["st"]).all(), (what, np.nonzero((a["st"] != b["st"]).any(axis=1))[0][:5])
-    for c, (x, y) in enumerate(zip(a["chains"], b["chains"])):
-        assert len(x[0]) == len(y[0]) and (x[0] == y[0]).all() and (x[1] == y[1]).all(), (what, "chain", c)
-    bad = np.nonzero((a["ck"] != b["ck"]).any(axis=1))[0]
-    assert len(bad) == 0, (what, "checkpoints", bad[:5], np.nonzero(a["ck"][bad[0]] != b["ck"][bad[0]])[0][:5])
-
-
 @pytest.mark.parametrize("name,K,steps", [("lorem4k", 64, 120), ("enwik3k", 96, 150), ("reps", 48, 120), ("zeros600", 32, 60)])
 def test_incremental_accept_equals_rebuild(name, K, steps, golden, golden_input):
     """After every accepted step the incrementally maintained base (bitmaps, special-state
@@ -237,7 +195,8 @@ def test_batch_accept_equals_rebuild(name, K, steps, lcpb, golden, golden_input,
 
 def test_batch_accept_that_gives_up_falls_back_to_the_rebuild(monkeypatch):
     """The batch accept's own fallback -- it has written journals and bitmaps, then a capacity is exceeded while the chains are
-    rewritten -- has never been taken by a real step; mgl_debug_set key 5 forces it.  The step must end exactly where the
+    rewritten -- is rare in real steps (tests/test_gpu_accept_giveups.py meets one, and takes every site of it with lowered
+    capacities); mgl_debug_set key 5 forces it, here in its first form, at the top of the chain kernel.  The step must end exactly where the
     chain without the batch path ends (rebuild from the slab the commit left), and the next steps go on patching in place."""
     data = corpus.enwik_like(30000, 0x5151)
     a = binding.SA(data, accept="bulk", neighbours_per_step=256, seed=9, iters_per_epoch=10**7)

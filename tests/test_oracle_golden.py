@@ -177,6 +177,7 @@ def test_bulk_steps_on_the_oracle_never_need_the_rollback(name, seed):
     o = Oracle(data)
     slab, best = literal_slab(n), literal_slab(n)
     before, over_before = o.bulk_rollbacks(), o.bulk_overlaps()
+    overruns_before = o.bulk_cluster_overruns()
     K, steps = (96, 60) if name == "doubled" else (48, 36)
     cur = best_cost = 0
     taken = 0
@@ -190,4 +191,7 @@ def test_bulk_steps_on_the_oracle_never_need_the_rollback(name, seed):
         assert lzma.decompress(o.emit(slab), format=lzma.FORMAT_ALONE) == data
     assert o.bulk_rollbacks() == before
     assert o.bulk_overlaps() == over_before  # no slab entry written by two taken journals (the device writes them in parallel)
+    # every cluster of taken moves (the device's batch accept, restated in the oracle) re-joins the old walk before the next cluster's
+    # first journal entry: a change of the window rule that lets a merged walk run on is seen here, on the CPU
+    assert o.bulk_cluster_overruns() == overruns_before
     assert taken >= 12  # the steps did take moves (several per step on the text-like inputs)
