@@ -193,6 +193,29 @@ int mgl_optimal_pass(mgl_sa* sa, const uint32_t* prices, size_t nprices, uint32_
                      mgl_packet* packets_out, uint64_t* objective);
 /* The prices mgl_sa_seed_optimal derives from a (valid) slab: 2 x number of probabilities u32. */
 int mgl_optimal_prices(mgl_sa* sa, const mgl_packet* packets, uint32_t* prices_out, size_t nprices);
+/* Adaptive-price optimal parse (not in the reference; DESIGN.md section 10, megalania_amd/csrc/mgl_adaptive.hip).  As
+ * mgl_sa_seed_optimal, but a chunk's shortest path runs in segments under the live probability model: a chunk starts from
+ * the walk state and the model that the previous parse's walk leaves there, each segment's DP looks `ahead` bytes past its
+ * commit horizon of `segment` bytes, and the model is refreshed with the events of the packets a segment commits.  Pass 0
+ * takes its chunk starts from the greedy parse (`cand` candidates), or with from_current from the current slab; pass p > 0
+ * from pass p - 1's resolved parse.  Every resolved parse is costed exactly; the cheapest becomes the current slab, with
+ * mgl_sa_seed_optimal's effect on the handle.  With from_current the current slab competes too (the re-parse: a caller may
+ * alternate it with mgl_sa_run): if no pass beats it the handle is left untouched, stats->best_pass is UINT32_MAX, and
+ * stats->greedy_cost holds the current slab's cost.  Fields left 0 take the defaults (segment 0: both segment and ahead). */
+typedef struct {
+	uint32_t passes;   /* default 3, at most MGL_OPT_MAX_PASSES */
+	uint32_t cand;     /* default 16, at most 30 */
+	uint32_t chunk;    /* default 4096, at least 512 */
+	uint32_t segment;  /* commit distance, 0 = default (64, with ahead 128) */
+	uint32_t ahead;    /* look-ahead past the commit horizon, at most 273 */
+	uint32_t from_current; /* 0: pass 0 starts from the greedy parse; 1: from the current slab */
+} mgl_adaptive_config;
+int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, mgl_optimal_stats* stats);
+/* Parity hook: one pass from the chunk starts of `parse_in` (n entries; MGL_ERANGE unless a valid parse).  packets_out
+ * (n entries) is the concatenated, unresolved parse in mgl_optimal_pass's form; *objective = the sum over the segments of
+ * the prices of what each committed.  segment 0 takes the default commit distance.  The SA state is untouched. */
+int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead,
+                      mgl_packet* packets_out, uint64_t* objective);
 /* Opt-in Metropolis accept rule (not in the reference, whose rule ignores the cost difference,
  * main.c:86).  temperature = 0 (default): the reference's rule.  temperature > 0, in
  * cost units (16384 per output byte, main.c:97): when the step's best neighbour does not improve,

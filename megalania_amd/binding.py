@@ -32,7 +32,7 @@ ACCEPT_AUTO, ACCEPT_SINGLE, ACCEPT_BULK = 0, 1, 2
 
 HIP_SYMBOLS = [
     "mgl_version", "mgl_last_error", "mgl_device_count", "mgl_sa_create", "mgl_sa_destroy", "mgl_sa_begin_epoch",
-    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
+    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_seed_adaptive", "mgl_adaptive_pass", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
     "mgl_substrings", "mgl_neighbours", "mgl_rng_draw_at", "mgl_debug_dump", "mgl_debug_set",
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep",
@@ -100,6 +100,11 @@ class OptimalStats(C.Structure):
                 ("ms", C.c_double * OPT_MAX_PASSES)]
 
 
+class AdaptiveConfig(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("cand", C.c_uint32), ("chunk", C.c_uint32), ("segment", C.c_uint32),
+                ("ahead", C.c_uint32), ("from_current", C.c_uint32)]
+
+
 class PropsCost(C.Structure):
     _fields_ = [("props", Properties), ("cost", C.c_uint64)]
 
@@ -148,6 +153,9 @@ def hip_lib():
         L.mgl_optimal_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
                                        C.POINTER(C.c_uint64)]
         L.mgl_optimal_prices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.mgl_sa_seed_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveConfig), C.POINTER(OptimalStats)]
+        L.mgl_adaptive_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                        C.POINTER(C.c_uint64)]
         L.mgl_sa_set_temperature.argtypes = [C.c_void_p, C.c_uint64]
         L.mgl_sa_set_best.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.mgl_sa_set_accept_mode.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
@@ -337,6 +345,29 @@ class SA:
         out = np.zeros(self.n, dtype=PACKET)
         obj = C.c_uint64(0)
         self._chk(self.L.mgl_optimal_pass(self.h, _ptr(prices), len(prices), cand, chunk, _ptr(out), C.byref(obj)))
+        return out, obj.value
+
+    def seed_adaptive(self, passes: int = 0, cand: int = 0, chunk: int = 0, segment: int = 0, ahead: int = 0,
+                      from_current: bool = False) -> dict:
+        """Current slab := the best of `passes` optimal parses under adaptive prices (mgl_sa_seed_adaptive; 0 = the
+        library's defaults).  from_current: the re-parse -- pass 0 starts from the current slab, which stays if no pass
+        beats it (best_pass is then None and greedy_cost its cost).  Returns the per-pass stats as seed_optimal does."""
+        st = OptimalStats()
+        cfg = AdaptiveConfig(passes, cand, chunk, segment, ahead, int(from_current))
+        self._chk(self.L.mgl_sa_seed_adaptive(self.h, C.byref(cfg), C.byref(st)))
+        k = st.passes
+        return dict(passes=k, best_pass=None if st.best_pass == 0xFFFFFFFF else st.best_pass, greedy_cost=st.greedy_cost,
+                    cost=list(st.cost[:k]), objective=list(st.objective[:k]), ms=list(st.ms[:k]))
+
+    def adaptive_pass(self, parse_in, cand: int, chunk: int, segment: int, ahead: int):
+        """One adaptive-price pass from the chunk starts of the valid slab `parse_in` (parity hook, SA state untouched).
+        Returns (unresolved slab with absolute distances, objective)."""
+        parse_in = np.ascontiguousarray(parse_in, dtype=PACKET)
+        if len(parse_in) != self.n:
+            raise MglError("adaptive_pass: parse_in must have one entry per input byte")
+        out = np.zeros(self.n, dtype=PACKET)
+        obj = C.c_uint64(0)
+        self._chk(self.L.mgl_adaptive_pass(self.h, _ptr(parse_in), cand, chunk, segment, ahead, _ptr(out), C.byref(obj)))
         return out, obj.value
 
     def seed_stream(self, stream: bytes, clip: bool = False) -> int:

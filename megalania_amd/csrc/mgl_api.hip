@@ -10,6 +10,7 @@
 #include "mgl_pbuild.hip"
 #include "mgl_index.hip"
 #include "mgl_optimal.hip"
+#include "mgl_adaptive.hip"
 #include "mgl_props.hip"
 #include "../../include/megalania_hip.h"
 
@@ -1364,6 +1365,162 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 	if ((rc = launch_validate(sa))) return rc;
 	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
 	if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_optimal: the seeded slab failed the walk check");
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	if (stats) *stats = st;
+	return MGL_OK;
+}
+
+/* ---- adaptive-price optimal parse (mgl_adaptive.hip) */
+#define MGL_ADP_DEF_SEGMENT 64u
+#define MGL_ADP_DEF_AHEAD 128u
+struct AdpBufs {
+	uint16_t* snaps = nullptr;
+	uint32_t* entry = nullptr;
+	mgl_pk *back = nullptr, *dp = nullptr, *res = nullptr, *keep = nullptr;
+	unsigned long long* obj = nullptr;
+	uint64_t* cost = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	~AdpBufs()
+	{
+		dfree(snaps); dfree(entry); dfree(back); dfree(dp); dfree(res); dfree(keep); dfree(obj); dfree(cost);
+		if (t0) (void)hipEventDestroy(t0);
+		if (t1) (void)hipEventDestroy(t1);
+	}
+};
+/* checks and defaults; a chunk or a segment longer than the input acts like one of its length */
+static int adp_args(const mgl_sa* sa, uint32_t cand, uint32_t& chunk, uint32_t& segment, uint32_t& ahead, bool ahead_given)
+{
+	int rc = opt_args(cand, chunk);
+	if (rc) return rc;
+	if (ahead > MGL_MAX_MATCH) return fail(MGL_EINVAL, "adaptive parse: ahead must be at most 273");
+	if (segment == 0) { segment = MGL_ADP_DEF_SEGMENT; if (!ahead_given) ahead = MGL_ADP_DEF_AHEAD; }
+	const uint32_t n = (uint32_t)sa->n;
+	if (chunk > n) chunk = n > MGL_OPT_MIN_CHUNK ? n : MGL_OPT_MIN_CHUNK;
+	if (segment > chunk) segment = chunk;
+	return MGL_OK;
+}
+static int adp_alloc(mgl_sa* sa, AdpBufs& o, uint32_t chunk, bool seed)
+{
+	const size_t n = sa->n, nch = (n + chunk - 1) / chunk;
+	HIPCHK(hipMalloc(&o.snaps, sizeof(uint16_t) * adp_stride(sa->ctx.L) * nch));
+	HIPCHK(hipMalloc(&o.entry, sizeof(uint32_t) * 5 * nch));
+	HIPCHK(hipMalloc(&o.back, sizeof(mgl_pk) * (n + 1)));
+	HIPCHK(hipMalloc(&o.dp, sizeof(mgl_pk) * n));
+	HIPCHK(hipMalloc(&o.obj, sizeof(unsigned long long)));
+	HIPCHK(hipMalloc(&o.cost, sizeof(uint64_t)));
+	if (seed) {
+		HIPCHK(hipMalloc(&o.res, sizeof(mgl_pk) * n));
+		HIPCHK(hipMalloc(&o.keep, sizeof(mgl_pk) * n));
+		HIPCHK(hipEventCreate(&o.t0));
+		HIPCHK(hipEventCreate(&o.t1));
+	}
+	return MGL_OK;
+}
+/* the serial walk: chunk starts of `in` (snaps), its exact cost, and with `out` the resolution of the DP's copies */
+static int adp_snap(mgl_sa* sa, AdpBufs& o, const mgl_pk* in, mgl_pk* out, uint32_t chunk, bool snaps)
+{
+	if (out) hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, out, (uint32_t)sa->n);
+	hipLaunchKernelGGL(k_adp_snap, dim3(1), dim3(64), 0, sa->stream, sa->ctx, in, out, out ? 1 : 0, chunk, o.entry,
+	                   snaps ? o.snaps : (uint16_t*)nullptr, o.cost);
+	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+/* one DP pass from the chunk starts in o.snaps / o.entry into o.dp */
+static int adp_dp(mgl_sa* sa, AdpBufs& o, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead)
+{
+	const uint32_t nch = (uint32_t)((sa->n + chunk - 1) / chunk);
+	const uint32_t lds = adp_stride(sa->ctx.L) * (uint32_t)sizeof(uint16_t);
+	HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.dp, (uint32_t)sa->n);
+	HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long), sa->stream));
+	hipLaunchKernelGGL(k_adp_dp, dim3(nch), dim3(64), lds, sa->stream, sa->ctx, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, cand,
+	                   segment, ahead, o.back, o.dp, o.obj);
+	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+
+extern "C" int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead,
+                                 mgl_packet* packets_out, uint64_t* objective)
+{
+	if (!sa || !parse_in || !packets_out) return fail(MGL_EINVAL, "null argument");
+	int rc = adp_args(sa, cand, chunk, segment, ahead, true);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(sa->device));
+	Control c;
+	if (scratch_walk(sa, parse_in, false, false, &c)) return fail(MGL_ERANGE, "mgl_adaptive_pass: parse_in is not a valid parse of the input");
+	AdpBufs o;
+	if ((rc = adp_alloc(sa, o, chunk, false))) return rc;
+	if ((rc = adp_snap(sa, o, sa->scratch.v.slab, nullptr, chunk, true))) return rc;
+	if ((rc = adp_dp(sa, o, cand, chunk, segment, ahead))) return rc;
+	unsigned long long obj = 0;
+	HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
+	if ((rc = export_slab(sa, o.dp, packets_out))) return rc;
+	if (objective) *objective = obj;
+	return MGL_OK;
+}
+
+extern "C" int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, mgl_optimal_stats* stats)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	const uint32_t passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
+	const uint32_t cand = cfg && cfg->cand ? cfg->cand : MGL_OPT_DEF_CAND;
+	uint32_t chunk = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
+	uint32_t segment = cfg ? cfg->segment : 0u, ahead = cfg ? cfg->ahead : 0u;
+	const bool from_current = cfg && cfg->from_current;
+	int rc = adp_args(sa, cand, chunk, segment, ahead, false);
+	if (rc) return rc;
+	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "mgl_sa_seed_adaptive: at most 16 passes");
+	HIPCHK(hipSetDevice(sa->device));
+	mgl_optimal_stats st;
+	memset(&st, 0, sizeof st);
+	AdpBufs o;
+	if ((rc = adp_alloc(sa, o, chunk, true))) return rc;
+	const uint32_t n = (uint32_t)sa->n;
+	/* pass 0's chunk starts: the greedy parse, or the current slab (which then has to be beaten) */
+	const mgl_pk* first = sa->base.v.slab;
+	if (!from_current) {
+		hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.res, cand);
+		HIPCHK(hipGetLastError());
+		first = o.res;
+	}
+	if ((rc = adp_snap(sa, o, first, nullptr, chunk, true))) return rc;
+	HIPCHK(hipMemcpyAsync(&st.greedy_cost, o.cost, sizeof(uint64_t), hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	uint64_t best = from_current ? st.greedy_cost : ~0ull;
+	st.best_pass = UINT32_MAX;
+	for (uint32_t p = 0; p < passes; p++) {
+		HIPCHK(hipEventRecord(o.t0, sa->stream));
+		if ((rc = adp_dp(sa, o, cand, chunk, segment, ahead))) return rc;
+		if ((rc = adp_snap(sa, o, o.dp, o.res, chunk, p + 1 < passes))) return rc;
+		unsigned long long obj = 0;
+		HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
+		HIPCHK(hipMemcpyAsync(&st.cost[p], o.cost, sizeof(uint64_t), hipMemcpyDeviceToHost, sa->stream));
+		HIPCHK(hipEventRecord(o.t1, sa->stream));
+		HIPCHK(hipEventSynchronize(o.t1));
+		float ms = 0;
+		HIPCHK(hipEventElapsedTime(&ms, o.t0, o.t1));
+		st.objective[p] = obj;
+		st.ms[p] = ms;
+		st.passes = p + 1;
+		if (st.cost[p] < best) {
+			best = st.cost[p]; st.best_pass = p;
+			HIPCHK(hipMemcpyAsync(o.keep, o.res, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
+		}
+	}
+	if (st.best_pass != UINT32_MAX) {
+		/* the cheapest parse becomes the current slab, as in mgl_sa_seed_optimal */
+		Control c;
+		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+		if ((rc = keep_best_before_overwrite(sa, c))) return rc;
+		if ((rc = write_ctl(sa, sa->base, &c))) return rc;
+		sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
+		uint64_t built = 0;
+		if ((rc = opt_make_current(sa, o.keep, &built))) return rc;
+		if ((rc = launch_validate(sa))) return rc;
+		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+		if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_adaptive: the seeded slab failed the walk check");
+		if (built != best) return fail(MGL_EDEVICE, "mgl_sa_seed_adaptive: the walk's cost of the seeded slab differs from the rebuild's");
+	}
 	HIPCHK(hipStreamSynchronize(sa->stream));
 	if (stats) *stats = st;
 	return MGL_OK;

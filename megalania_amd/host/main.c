@@ -27,7 +27,8 @@ static void usage(const char* argv0)
 	fprintf(stderr,
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
 	        "          [--lc N --lp N --pb N | --props auto [--props-rounds R] [--props-table]] [--device D] [--max-scan M]\n"
-	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P] [--temperature B]\n"
+	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P | --adaptive-seed P]\n"
+	        "          [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
@@ -37,6 +38,9 @@ static void usage(const char* argv0)
 	        "               parse instead (longest of the C nearest candidates per position; e.g. 256)\n"
 	        "  --optimal-seed P  epochs that the reference starts from the all-literal slab start from the best of P\n"
 	        "               price-driven optimal parses made on the device (e.g. 3); not with --greedy-seed,\n"
+	        "               --seed-stream or --load-slab\n"
+	        "  --adaptive-seed P  as --optimal-seed, but the parses are priced from the live probability model, refreshed as\n"
+	        "               each segment of a chunk is committed (e.g. 3); not with --optimal-seed, --greedy-seed,\n"
 	        "               --seed-stream or --load-slab\n"
 	        "  --seed-stream F  start from the parse inside an existing .lzma / .xz stream of this input (e.g. xz -9e's):\n"
 	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's\n"
@@ -59,6 +63,18 @@ static void usage(const char* argv0)
 	        "               the best of its own window (bulk), or whichever pays (auto, default)\n", argv0);
 }
 
+/* the seed made on the device: the best of `passes` optimal parses, under static prices or (adaptive) the live model's */
+typedef struct { uint32_t passes; bool adaptive; } seed_spec;
+static int make_seed(mgl_sa* sa, seed_spec seed, mgl_optimal_stats* os)
+{
+	if (seed.adaptive) {
+		mgl_adaptive_config ac = { seed.passes, 0, 0, 0, 0, 0 };
+		return mgl_sa_seed_adaptive(sa, &ac, os);
+	}
+	mgl_optimal_config oc = { seed.passes, 0, 0 };
+	return mgl_sa_seed_optimal(sa, &oc, os);
+}
+
 static bool same_props(mgl_properties a, mgl_properties b) { return a.lc == b.lc && a.lp == b.lp && a.pb == b.pb; }
 
 /* slab file: "MGLSLAB1", u64 size, u64 perplexity, size x 12-byte packets (lzma_packet.h:13-17) */
@@ -77,12 +93,12 @@ static bool read_slab_file(const char* path, size_t file_size, mgl_packet* packe
 /* --props auto.  `sa` is a handle at *props that nothing has been done to yet.  Each round costs
  * one parse under all 75 triples (mgl_props_sweep) and moves to a fresh handle at the cheapest, until that is the
  * handle's own or `rounds` sweeps are done.  parse_fixed: `parse` holds a parse that does not depend on the triple (a
- * stream's, a loaded slab's, the greedy one); otherwise every round makes an optimal seed under the handle's triple
+ * stream's, a loaded slab's, the greedy one); otherwise every round makes the seed `seed` under the handle's triple
  * into it.  Of all (triple, parse) pairs seen the cheapest wins: *props becomes its triple, `kept` its parse (only
  * when the parse is not fixed), and the handle returned is an untouched one at that triple.  NULL after an error
  * (already reported). */
 static mgl_sa* choose_props(mgl_sa* sa, const uint8_t* data, size_t n, const mgl_sa_config* cfg, mgl_properties* props,
-                            mgl_packet* parse, bool parse_fixed, uint32_t optimal_passes, unsigned rounds, bool print_table,
+                            mgl_packet* parse, bool parse_fixed, seed_spec seed, unsigned rounds, bool print_table,
                             mgl_packet* kept)
 {
 	mgl_props_cost tab[MGL_PROPS_TRIPLES];
@@ -92,10 +108,9 @@ static mgl_sa* choose_props(mgl_sa* sa, const uint8_t* data, size_t n, const mgl
 	bool touched = false;
 	for (;;) {
 		if (!parse_fixed) {
-			mgl_optimal_config oc = { optimal_passes, 0, 0 };
 			mgl_optimal_stats os;
 			uint64_t cost = 0;
-			if (mgl_sa_seed_optimal(sa, &oc, &os) != MGL_OK || mgl_sa_current(sa, parse, &cost) != MGL_OK) goto fail;
+			if (make_seed(sa, seed, &os) != MGL_OK || mgl_sa_current(sa, parse, &cost) != MGL_OK) goto fail;
 			touched = true;
 		}
 		size_t count = 0;
@@ -146,7 +161,7 @@ int main(int argc, char** argv)
 	int clip_window = 0, props_given = 0;
 	bool props_auto = false, props_table = false;
 	unsigned props_rounds = 3;
-	uint32_t greedy = 0, optimal = 0;
+	uint32_t greedy = 0, optimal = 0, adaptive = 0;
 	mgl_packet* optimal_slab = NULL;
 	double temperature_bytes = 0;
 	int accept_mode = MGL_ACCEPT_AUTO;
@@ -189,6 +204,7 @@ int main(int argc, char** argv)
 		else if (!strcmp(a, "--load-slab")) load_path = v;
 		else if (!strcmp(a, "--greedy-seed")) greedy = (uint32_t)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--optimal-seed")) { optimal = (uint32_t)strtoul(v, NULL, 0); if (!optimal) { usage(argv[0]); return -1; } }
+		else if (!strcmp(a, "--adaptive-seed")) { adaptive = (uint32_t)strtoul(v, NULL, 0); if (!adaptive) { usage(argv[0]); return -1; } }
 		else if (!strcmp(a, "--seed-stream")) seed_stream_path = v;
 		else if (!strcmp(a, "--temperature")) temperature_bytes = strtod(v, NULL);
 		else if (!strcmp(a, "--accept")) {
@@ -211,6 +227,12 @@ int main(int argc, char** argv)
 		usage(argv[0]);
 		return -1;
 	}
+	if (adaptive && (optimal || greedy || seed_stream_path || load_path)) {
+		fprintf(stderr, "Error: --adaptive-seed cannot be combined with --optimal-seed, --greedy-seed, --seed-stream or --load-slab\n");
+		usage(argv[0]);
+		return -1;
+	}
+	const seed_spec seed = { adaptive ? adaptive : optimal, adaptive != 0 }; /* passes 0: no seed of this kind */
 	if (clip_window && !seed_stream_path) { usage(argv[0]); return -1; }
 	if (props_auto && (props_given || chains > 1)) {
 		fprintf(stderr, "Error: --props auto cannot be combined with --lc/--lp/--pb or with --chains above 1\n");
@@ -287,9 +309,9 @@ int main(int argc, char** argv)
 			fixed = false;
 			if ((optimal_slab = (mgl_packet*)malloc(sizeof(mgl_packet) * file_size)) == NULL) { fprintf(stderr, "Error: out of memory\n"); return -1; }
 		}
-		if ((sa = choose_props(sa, file_data, file_size, &cfg, &props, parse, fixed, optimal, props_rounds, props_table, optimal_slab)) == NULL) return -1;
+		if ((sa = choose_props(sa, file_data, file_size, &cfg, &props, parse, fixed, seed, props_rounds, props_table, optimal_slab)) == NULL) return -1;
 		free(parse);
-		if (!optimal) { free(optimal_slab); optimal_slab = NULL; } /* no seed option: the search starts from the all-literal slab */
+		if (!seed.passes) { free(optimal_slab); optimal_slab = NULL; } /* no seed option: the search starts from the all-literal slab */
 	}
 
 	if (temperature_bytes > 0 && mgl_sa_set_temperature(sa, (uint64_t)(temperature_bytes * 16384.0)) != MGL_OK) {
@@ -371,19 +393,18 @@ int main(int argc, char** argv)
 		resumed = true;
 	}
 
-	if (optimal && !props_auto) { /* --props auto kept the parse of its cheapest (triple, parse) pair in optimal_slab */
+	if (seed.passes && !props_auto) { /* --props auto kept the parse of its cheapest (triple, parse) pair in optimal_slab */
 		/* made once; every epoch that would start from the all-literal slab starts from it */
-		mgl_optimal_config oc = { optimal, 0, 0 };
 		mgl_optimal_stats os;
 		uint64_t cost = 0;
 		optimal_slab = (mgl_packet*)malloc(sizeof(mgl_packet) * (file_size ? file_size : 1));
-		if (!optimal_slab || mgl_sa_seed_optimal(sa, &oc, &os) != MGL_OK || mgl_sa_current(sa, optimal_slab, &cost) != MGL_OK) {
+		if (!optimal_slab || make_seed(sa, seed, &os) != MGL_OK || mgl_sa_current(sa, optimal_slab, &cost) != MGL_OK) {
 			fprintf(stderr, "Error: %s\n", optimal_slab ? mgl_last_error() : "out of memory");
 			return -1;
 		}
 		double ms = 0;
 		for (uint32_t p = 0; p < os.passes; p++) ms += os.ms[p];
-		fprintf(stderr, "optimal seed: %u passes in %.1f ms, estimate %f bytes (greedy parse %f)\n", os.passes, ms,
+		fprintf(stderr, "%s seed: %u passes in %.1f ms, estimate %f bytes (greedy parse %f)\n", seed.adaptive ? "adaptive" : "optimal", os.passes, ms,
 		        18 + cost / 16384.f, 18 + os.greedy_cost / 16384.f);
 	}
 
@@ -393,7 +414,7 @@ int main(int argc, char** argv)
 		for (unsigned epoch = 0; epoch < epochs; epoch++) {
 			if (mgl_sa_begin_epoch(sa, phase, phase != 0 || resumed) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			if (greedy && phase == 0 && !resumed && mgl_sa_seed_greedy(sa, greedy) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
-			if (optimal && phase == 0 && mgl_sa_set_slab(sa, optimal_slab) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+			if (seed.passes && phase == 0 && mgl_sa_set_slab(sa, optimal_slab) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			mgl_sa_stats st;
 			if (mgl_sa_run(sa, steps_per_epoch, &st) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			/* main.c:97-99: 18 = 13 header bytes + 5 flush bytes, 16384 = 2048 * 8 */
