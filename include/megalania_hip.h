@@ -216,6 +216,26 @@ int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, mgl_optimal
  * the prices of what each committed.  segment 0 takes the default commit distance.  The SA state is untouched. */
 int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead,
                       mgl_packet* packets_out, uint64_t* objective);
+/* The match finder of the parses above (not in the reference; DESIGN.md section 10, megalania_amd/csrc/mgl_matchfinder.hip):
+ * where a node of the shortest path takes its MATCH sources from.  MGL_MF_NEAREST (default): the `cand` nearest earlier
+ * positions with the same two bytes and the `cand` nearest with the same four.  MGL_MF_FRONTIER: for every achievable
+ * length the nearest earlier position that reaches it -- the list an LZ optimiser gets from a binary-tree match finder
+ * -- at most 60 entries per position, inside the handle's dictionary window.  Lengths 2..8 and 16 are one index look-up
+ * each; a longer match is looked for among the positions that share 8 (16) bytes, nearest first, and `depth` bounds how
+ * many of those are examined per position over all lengths (0 = default 64, at most 4096; with enough depth the list is
+ * exact).  Applies to every later mgl_sa_seed_optimal, mgl_optimal_pass, mgl_sa_seed_adaptive and mgl_adaptive_pass on the
+ * handle; `cand` then only shapes the greedy parse that pass 0 starts from.  The lists are made on the first such call
+ * and kept (made again when the depth changes).  MGL_EINVAL: unknown finder, depth above 4096. */
+#define MGL_MF_NEAREST 0
+#define MGL_MF_FRONTIER 1
+int mgl_sa_set_match_finder(mgl_sa* sa, int finder, uint32_t depth);
+/* Parity hook: the MGL_MF_FRONTIER lists at `depth` (0 = default).  off_out (n + 1 entries, nullable): position i's
+ * entries are [off[i], off[i + 1]); src_out / len_out (cap entries each, nullable): source position and match length
+ * (capped at 273 and at the end of the input), lengths and distances rising along a list.  *count = off[n];
+ * cap < *count: MGL_ERANGE with *count set.  gpu_ms (nullable): device time of the build that made the lists the handle
+ * holds.  The SA state is untouched. */
+int mgl_match_frontier(mgl_sa* sa, uint32_t depth, uint32_t* off_out, uint32_t* src_out, uint16_t* len_out, size_t cap,
+                       size_t* count, double* gpu_ms);
 /* Opt-in Metropolis accept rule (not in the reference, whose rule ignores the cost difference,
  * main.c:86).  temperature = 0 (default): the reference's rule.  temperature > 0, in
  * cost units (16384 per output byte, main.c:97): when the step's best neighbour does not improve,

@@ -29,10 +29,11 @@ F_NO_SNAPSHOTS = 8
 F_SERIAL_BUILD = 16
 F_POSITION_TARGETS = 32
 ACCEPT_AUTO, ACCEPT_SINGLE, ACCEPT_BULK = 0, 1, 2
+MF_NEAREST, MF_FRONTIER = 0, 1
 
 HIP_SYMBOLS = [
     "mgl_version", "mgl_last_error", "mgl_device_count", "mgl_sa_create", "mgl_sa_destroy", "mgl_sa_begin_epoch",
-    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_seed_adaptive", "mgl_adaptive_pass", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
+    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_seed_adaptive", "mgl_adaptive_pass", "mgl_sa_set_match_finder", "mgl_match_frontier", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
     "mgl_substrings", "mgl_neighbours", "mgl_rng_draw_at", "mgl_debug_dump", "mgl_debug_set",
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep",
@@ -156,6 +157,9 @@ def hip_lib():
         L.mgl_sa_seed_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveConfig), C.POINTER(OptimalStats)]
         L.mgl_adaptive_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.POINTER(C.c_uint64)]
+        L.mgl_sa_set_match_finder.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+        L.mgl_match_frontier.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
         L.mgl_sa_set_temperature.argtypes = [C.c_void_p, C.c_uint64]
         L.mgl_sa_set_best.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.mgl_sa_set_accept_mode.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
@@ -369,6 +373,28 @@ class SA:
         obj = C.c_uint64(0)
         self._chk(self.L.mgl_adaptive_pass(self.h, _ptr(parse_in), cand, chunk, segment, ahead, _ptr(out), C.byref(obj)))
         return out, obj.value
+
+    def set_match_finder(self, finder, depth: int = 0):
+        """Where the optimal / adaptive parses take a node's MATCH sources from: MF_NEAREST (default; "nearest") or
+        MF_FRONTIER ("frontier": the nearest source of every achievable length, `depth` run entries examined per position,
+        0 = the library's default)."""
+        finder = {"nearest": MF_NEAREST, "frontier": MF_FRONTIER}.get(finder, finder)
+        self._chk(self.L.mgl_sa_set_match_finder(self.h, finder, depth))
+
+    def match_frontier(self, depth: int = 0, cap=None):
+        """The MF_FRONTIER lists (parity hook, SA state untouched): (off[n + 1], src, len, device ms of their build).
+        cap: the room offered for the entries (default: as many as there are)."""
+        cnt, ms = C.c_size_t(0), C.c_double(0)
+        if cap is None:
+            rc = self.L.mgl_match_frontier(self.h, depth, None, None, None, 0, C.byref(cnt), C.byref(ms))
+            if rc != 0 and rc != -4:  # MGL_ERANGE: cnt holds the number of entries
+                self._chk(rc)
+            cap = cnt.value
+        off = np.zeros(self.n + 1, dtype=np.uint32)
+        src = np.zeros(max(1, cap), dtype=np.uint32)
+        ln = np.zeros(max(1, cap), dtype=np.uint16)
+        self._chk(self.L.mgl_match_frontier(self.h, depth, _ptr(off), _ptr(src), _ptr(ln), cap, C.byref(cnt), C.byref(ms)))
+        return off, src[: cnt.value].copy(), ln[: cnt.value].copy(), ms.value
 
     def seed_stream(self, stream: bytes, clip: bool = False) -> int:
         """Best slab := the parse inside an existing .lzma / .xz stream of this input (stream_import, window =

@@ -8,7 +8,8 @@
  *   k_adp_snap  one wavefront, the model in LDS (as k_props_sweep holds it): walks a slab from the LZMA initial
  *               state, costs it exactly, and leaves the walk state and a copy of the model at every chunk start;
  *               when resolving it re-expresses the DP's copies against the true rep stack on the way (k_opt_walk)
- *   k_adp_dp    one workgroup (one wavefront) per chunk: k_opt_dp's forward shortest path, segment by segment
+ *   k_adp_dp    one workgroup (one wavefront) per chunk: k_opt_dp's forward shortest path, segment by segment (the
+ *               instance <true> reads its MATCH sources from the lists of mgl_matchfinder.hip, as k_opt_dp<true>)
  *
  * The rule is restated in plain Python in tests/test_adaptive_rule_cpu.py.
  */
@@ -119,8 +120,10 @@ extern __shared__ __align__(4) uint16_t adp_model[]; /* the chunk's model: adp_s
  * of each to M, under the exact state of the path.  Where that walk ends is the next anchor.
  *
  * back[] and out[] are read and written by lane 0 alone (what the other lanes need of an entry is broadcast). */
+template <bool MF>
 __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, const uint16_t* snaps, uint32_t chunk, uint32_t cand,
-                                               uint32_t segment, uint32_t ahead, mgl_pk* back, mgl_pk* out, unsigned long long* objective)
+                                               uint32_t segment, uint32_t ahead, mgl_pk* back, mgl_pk* out, unsigned long long* objective,
+                                               MfLists mf)
 {
 	__shared__ uint64_t r_tot[MGL_OPT_RING];
 	__shared__ uint64_t r_edge[MGL_OPT_RING];
@@ -203,9 +206,12 @@ __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, 
 			const uint32_t ps = i & (nps - 1u);
 			if (lane == 0 && i + MGL_MAX_MATCH <= end) r_tot[(i + MGL_MAX_MATCH) % MGL_OPT_RING] = ~0ull; /* slot of the node that enters the window */
 
-			/* one source per lane: lanes 0..3 rep r, 4 .. 4 + cand - 1 the 2-byte order, then the 4-byte order */
+			/* one source per lane: lanes 0..3 rep r, 4 .. 4 + cand - 1 the 2-byte order, then the 4-byte order; MF: lane
+			 * 4 + k takes entry k of the node's match list, cut to this segment's cap */
 			uint32_t slen = 0, sb0 = 0, sb1 = 0, sb2 = 0, sb3 = 0;
 			uint64_t skey = 0;
+			uint32_t f0 = 0, fcnt = 0;
+			if (MF) { f0 = mf.off[i]; fcnt = mf.off[i + 1u] - f0; }
 			if (lane < 4u) {
 				const uint32_t D = mgl_dist_at(&W, lane) + 1u;
 				if (D <= i && cap >= 2u) {
@@ -217,6 +223,20 @@ __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, 
 					} else slen = 0;
 				}
 				skey = lane;
+			} else if (MF) {
+				if (lane - 4u < fcnt && cap >= 2u) {
+					const uint32_t fl = mf.len[f0 + lane - 4u], D = i - mf.src[f0 + lane - 4u];
+					slen = fl < cap ? fl : cap;
+					mgl_plan pl;
+					uint32_t b[4];
+					for (uint32_t lc4 = 0; lc4 < 4u; lc4++) {
+						mgl_plan_packet(&L, &W, MGL_MATCH, D - 1u, 2u + lc4, 0u, 0u, 0u, &pl);
+						const uint32_t from = pl.nhdr + pl.len_nchoice + pl.len_tbits;
+						b[lc4] = adp_events(pl, M, T, 0, pl.nhdr) + adp_events(pl, M, T, from, pl.nev) + (pl.ndirect << 11);
+					}
+					sb0 = b[0]; sb1 = b[1]; sb2 = b[2]; sb3 = b[3];
+					skey = 5ull + D;
+				}
 			} else if (lane < 4u + 2u * cand && cap >= 2u && i + 1u < c.n) {
 				const uint32_t src = lane < 4u + cand ? 0u : 1u, k = lane - 4u - src * cand;
 				const uint32_t bigram = ((uint32_t)d[i] << 8) | d[i + 1];
@@ -255,7 +275,7 @@ __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, 
 			for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)maxl, o, 64); maxl = t > maxl ? t : maxl; }
 			__syncthreads();
 
-			const uint32_t nsrc = 4u + 2u * cand;
+			const uint32_t nsrc = MF ? 4u + fcnt : 4u + 2u * cand;
 			for (uint32_t l = 1u + lane; l <= (maxl > 1u ? maxl : 1u); l += 64u) {
 				uint64_t best = ~0ull, bkey = ~0ull;
 				uint32_t btype = 0, bx = 0;

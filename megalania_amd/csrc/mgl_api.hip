@@ -9,6 +9,7 @@
 #include "mgl_kernels5.hip"
 #include "mgl_pbuild.hip"
 #include "mgl_index.hip"
+#include "mgl_matchfinder.hip"
 #include "mgl_optimal.hip"
 #include "mgl_adaptive.hip"
 #include "mgl_props.hip"
@@ -163,6 +164,16 @@ struct mgl_sa {
 	unsigned long long* d_traffic = nullptr; /* [0] bytes [1] spare */
 	uint32_t short_looks = 0;      /* blocks of at most four steps still to come after a switch of the launch form */
 	hipEvent_t ev_val = nullptr; /* a bulk step's validation beside its build */
+	/* the parses' match finder (mgl_sa_set_match_finder) and the lists of mgl_matchfinder.hip: made on first use, kept with
+	 * the depth they were made at, made again when another depth is asked for */
+	int mf_finder = MGL_MF_NEAREST;
+	uint32_t mf_depth = MGL_MF_DEF_DEPTH;
+	uint32_t mf_built = 0;         /* depth of the lists held, 0 = none */
+	uint32_t* d_mf_off = nullptr;
+	uint32_t* d_mf_src = nullptr;
+	uint16_t* d_mf_len = nullptr;
+	size_t mf_total = 0;
+	double mf_ms = 0;              /* device time of the build that made them */
 };
 
 static uint64_t ceil_sqrt_u64(uint64_t x)
@@ -589,6 +600,7 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 	dfree(sa->lim.why); dfree(sa->ab.hdr); dfree(sa->ab.ins_key); dfree(sa->ab.rem_key); dfree(sa->ab.ins_pos); dfree(sa->ab.rem_pos);
 	dfree(sa->ab.tctx); dfree(sa->ab.scratch_pos); dfree(sa->ab.scratch_ev);
 	dfree(sa->ab.span_pos); dfree(sa->ab.span_ev); dfree(sa->ab.jobs_b); dfree(sa->ab.jobs_c);
+	dfree(sa->d_mf_off); dfree(sa->d_mf_src); dfree(sa->d_mf_len);
 	dfree(sa->d_topk_pk); dfree(sa->d_topk_cost); dfree(sa->d_small); dfree(sa->d_sub_offs); dfree(sa->d_sub_lens);
 	for (hipEvent_t e : sa->ev_pool) (void)hipEventDestroy(e);
 	if (sa->ev_begin) (void)hipEventDestroy(sa->ev_begin);
@@ -1236,13 +1248,101 @@ static int opt_prices(mgl_sa* sa, OptBufs& o, const mgl_pk* slab)
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
+/* ---- the parses' match lists (mgl_matchfinder.hip) */
+struct MfTmp {
+	uint4* queue = nullptr;
+	uint32_t* qcount = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	~MfTmp()
+	{
+		dfree(queue); dfree(qcount);
+		if (t0) (void)hipEventDestroy(t0);
+		if (t1) (void)hipEventDestroy(t1);
+	}
+};
+/* the handle holds the lists of depth `depth` afterwards */
+static int mf_ensure(mgl_sa* sa, uint32_t depth)
+{
+	if (sa->mf_built == depth) return MGL_OK;
+	const uint32_t n = (uint32_t)sa->n;
+	dfree(sa->d_mf_off); dfree(sa->d_mf_src); dfree(sa->d_mf_len);
+	sa->d_mf_off = nullptr; sa->d_mf_src = nullptr; sa->d_mf_len = nullptr;
+	sa->mf_built = 0; sa->mf_total = 0;
+	MfTmp t;
+	HIPCHK(hipMalloc(&sa->d_mf_off, sizeof(uint32_t) * ((size_t)n + 1)));
+	HIPCHK(hipMalloc(&t.queue, sizeof(uint4) * (size_t)n));
+	HIPCHK(hipMalloc(&t.qcount, sizeof(uint32_t)));
+	HIPCHK(hipEventCreate(&t.t0));
+	HIPCHK(hipEventCreate(&t.t1));
+	const dim3 g_direct(n / 256u + 1u); /* n + 1 lanes: off[n] */
+	HIPCHK(hipEventRecord(t.t0, sa->stream));
+	HIPCHK(hipMemsetAsync(t.qcount, 0, sizeof(uint32_t), sa->stream));
+	hipLaunchKernelGGL(k_mf_direct<false>, g_direct, dim3(256), 0, sa->stream, sa->ctx, sa->d_mf_off, (uint32_t*)nullptr, (uint16_t*)nullptr, t.queue, t.qcount);
+	uint32_t queued = 0;
+	HIPCHK(hipMemcpyAsync(&queued, t.qcount, sizeof queued, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	if (queued > n) return fail(MGL_EDEVICE, "match finder: the scan queue overran");
+	const dim3 g_scan((queued + 3u) / 4u);
+	if (queued) hipLaunchKernelGGL(k_mf_scan<false>, g_scan, dim3(256), 0, sa->stream, sa->ctx, depth, sa->d_mf_off, (uint32_t*)nullptr, (uint16_t*)nullptr,
+	                               (const uint4*)t.queue, (const uint32_t*)t.qcount);
+	hipLaunchKernelGGL(ix_scan, dim3(1), dim3(1024), 0, sa->stream, sa->d_mf_off, n + 1u);
+	uint32_t total = 0;
+	HIPCHK(hipMemcpyAsync(&total, sa->d_mf_off + n, sizeof total, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	if ((uint64_t)total > (uint64_t)MGL_MF_MAX_ENTRIES * n) return fail(MGL_EDEVICE, "match finder: the list lengths do not add up");
+	HIPCHK(hipMalloc(&sa->d_mf_src, sizeof(uint32_t) * ((size_t)total + 1)));
+	HIPCHK(hipMalloc(&sa->d_mf_len, sizeof(uint16_t) * ((size_t)total + 1)));
+	hipLaunchKernelGGL(k_mf_direct<true>, g_direct, dim3(256), 0, sa->stream, sa->ctx, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len, t.queue, t.qcount);
+	if (queued) hipLaunchKernelGGL(k_mf_scan<true>, g_scan, dim3(256), 0, sa->stream, sa->ctx, depth, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len,
+	                               (const uint4*)t.queue, (const uint32_t*)t.qcount);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(t.t1, sa->stream));
+	HIPCHK(hipEventSynchronize(t.t1));
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, t.t0, t.t1));
+	sa->mf_ms = ms; sa->mf_total = total; sa->mf_built = depth;
+	return MGL_OK;
+}
+static MfLists mf_lists(const mgl_sa* sa) { return MfLists{ sa->d_mf_off, sa->d_mf_src, sa->d_mf_len }; }
+
+extern "C" int mgl_sa_set_match_finder(mgl_sa* sa, int finder, uint32_t depth)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	if (finder != MGL_MF_NEAREST && finder != MGL_MF_FRONTIER) return fail(MGL_EINVAL, "mgl_sa_set_match_finder: unknown finder");
+	if (depth > MGL_MF_MAX_DEPTH) return fail(MGL_EINVAL, "mgl_sa_set_match_finder: depth must be at most 4096");
+	sa->mf_finder = finder;
+	sa->mf_depth = depth ? depth : MGL_MF_DEF_DEPTH;
+	return MGL_OK;
+}
+
+extern "C" int mgl_match_frontier(mgl_sa* sa, uint32_t depth, uint32_t* off_out, uint32_t* src_out, uint16_t* len_out, size_t cap,
+                                  size_t* count, double* gpu_ms)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	if (depth > MGL_MF_MAX_DEPTH) return fail(MGL_EINVAL, "mgl_match_frontier: depth must be at most 4096");
+	HIPCHK(hipSetDevice(sa->device));
+	int rc = mf_ensure(sa, depth ? depth : MGL_MF_DEF_DEPTH);
+	if (rc) return rc;
+	if (count) *count = sa->mf_total;
+	if (gpu_ms) *gpu_ms = sa->mf_ms;
+	if (cap < sa->mf_total) return fail(MGL_ERANGE, "mgl_match_frontier: cap is below the number of entries");
+	if (off_out) HIPCHK(hipMemcpyAsync(off_out, sa->d_mf_off, sizeof(uint32_t) * ((size_t)sa->n + 1), hipMemcpyDeviceToHost, sa->stream));
+	if (src_out && sa->mf_total) HIPCHK(hipMemcpyAsync(src_out, sa->d_mf_src, sizeof(uint32_t) * sa->mf_total, hipMemcpyDeviceToHost, sa->stream));
+	if (len_out && sa->mf_total) HIPCHK(hipMemcpyAsync(len_out, sa->d_mf_len, sizeof(uint16_t) * sa->mf_total, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	return MGL_OK;
+}
+
 /* one DP pass into o.dp (entry == nullptr: the LZMA initial state at every chunk start) */
 static int opt_dp(mgl_sa* sa, OptBufs& o, const uint32_t* entry, uint32_t cand, uint32_t chunk)
 {
 	const uint32_t nch = (uint32_t)((sa->n + chunk - 1) / chunk);
+	const bool mf = sa->mf_finder == MGL_MF_FRONTIER;
+	if (mf) { int rc = mf_ensure(sa, sa->mf_depth); if (rc) return rc; }
 	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.dp, (uint32_t)sa->n);
 	HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long), sa->stream));
-	hipLaunchKernelGGL(k_opt_dp, dim3(nch), dim3(64), 0, sa->stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj);
+	if (mf) hipLaunchKernelGGL(k_opt_dp<true>, dim3(nch), dim3(64), 0, sa->stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj, mf_lists(sa));
+	else hipLaunchKernelGGL(k_opt_dp<false>, dim3(nch), dim3(64), 0, sa->stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj, MfLists{});
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -1430,11 +1530,15 @@ static int adp_dp(mgl_sa* sa, AdpBufs& o, uint32_t cand, uint32_t chunk, uint32_
 {
 	const uint32_t nch = (uint32_t)((sa->n + chunk - 1) / chunk);
 	const uint32_t lds = adp_stride(sa->ctx.L) * (uint32_t)sizeof(uint16_t);
-	HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	const bool mf = sa->mf_finder == MGL_MF_FRONTIER;
+	if (mf) { int rc = mf_ensure(sa, sa->mf_depth); if (rc) return rc; }
+	HIPCHK(hipFuncSetAttribute(mf ? (const void*)k_adp_dp<true> : (const void*)k_adp_dp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.dp, (uint32_t)sa->n);
 	HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long), sa->stream));
-	hipLaunchKernelGGL(k_adp_dp, dim3(nch), dim3(64), lds, sa->stream, sa->ctx, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, cand,
-	                   segment, ahead, o.back, o.dp, o.obj);
+	if (mf) hipLaunchKernelGGL(k_adp_dp<true>, dim3(nch), dim3(64), lds, sa->stream, sa->ctx, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, cand,
+	                           segment, ahead, o.back, o.dp, o.obj, mf_lists(sa));
+	else hipLaunchKernelGGL(k_adp_dp<false>, dim3(nch), dim3(64), lds, sa->stream, sa->ctx, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, cand,
+	                        segment, ahead, o.back, o.dp, o.obj, MfLists{});
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }

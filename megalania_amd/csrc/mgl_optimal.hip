@@ -9,7 +9,8 @@
  *                 ones every probability slot sees and, when resolving, re-expresses the DP's
  *                 copies (absolute distances) against the true rep stack
  *   k_opt_prices  counts -> one price per (slot, bit), in cost units (2048 per bit)
- *   k_opt_dp      one workgroup per chunk [s, e): forward shortest path over the nodes s..e
+ *   k_opt_dp      one workgroup per chunk [s, e): forward shortest path over the nodes s..e; the instance <true>
+ *                 takes a node's MATCH sources from the lists of mgl_matchfinder.hip instead of searching for them
  *
  * Prices: p0 = clamp(floor(2048 (n0 + 1) / (n0 + n1 + 2)), 1, 2047), price0 = T[p0], price1 =
  * T[2048 - p0]; direct bits cost 2048 as on the costing path.  The rule of k_opt_dp is restated
@@ -107,8 +108,9 @@ __device__ __forceinline__ uint32_t opt_events(const mgl_plan& pl, const uint32_
  *
  * back[j] (global, n + 1 entries) = the winning edge into node j as (type, absolute distance, len); the chunk's parse
  * is read off it from e backwards into out[] (position-indexed; positions off the path keep their literal). */
+template <bool MF>
 __global__ void __launch_bounds__(64) k_opt_dp(DevCtx c, const uint32_t* prices, const uint32_t* entry, uint32_t chunk,
-                                               uint32_t cand, mgl_pk* back, mgl_pk* out, unsigned long long* objective)
+                                               uint32_t cand, mgl_pk* back, mgl_pk* out, unsigned long long* objective, MfLists mf)
 {
 	__shared__ uint64_t r_tot[MGL_OPT_RING];
 	__shared__ uint64_t r_edge[MGL_OPT_RING];
@@ -172,9 +174,12 @@ __global__ void __launch_bounds__(64) k_opt_dp(DevCtx c, const uint32_t* prices,
 		const uint32_t ps = i & (nps - 1u);
 		if (lane == 0 && i + MGL_MAX_MATCH <= e) r_tot[(i + MGL_MAX_MATCH) % MGL_OPT_RING] = ~0ull; /* slot of the node that enters the window */
 
-		/* one source per lane: lanes 0..3 rep r, 4 .. 4 + cand - 1 the 2-byte order, then the 4-byte order */
+		/* one source per lane: lanes 0..3 rep r, 4 .. 4 + cand - 1 the 2-byte order, then the 4-byte order; MF: lane 4 + k
+		 * takes entry k of the node's match list, whose length is known (no bytes are compared) */
 		uint32_t slen = 0, sb0 = 0, sb1 = 0, sb2 = 0, sb3 = 0;
 		uint64_t skey = 0;
+		uint32_t f0 = 0, fcnt = 0;
+		if (MF) { f0 = mf.off[i]; fcnt = mf.off[i + 1u] - f0; }
 		if (lane < 4u) {
 			const uint32_t D = mgl_dist_at(&W, lane) + 1u;
 			if (D <= i && cap >= 2u) {
@@ -186,6 +191,20 @@ __global__ void __launch_bounds__(64) k_opt_dp(DevCtx c, const uint32_t* prices,
 				} else slen = 0;
 			}
 			skey = lane;
+		} else if (MF) {
+			if (lane - 4u < fcnt && cap >= 2u) {
+				const uint32_t fl = mf.len[f0 + lane - 4u], D = i - mf.src[f0 + lane - 4u];
+				slen = fl < cap ? fl : cap;
+				mgl_plan pl;
+				uint32_t b[4];
+				for (uint32_t lc4 = 0; lc4 < 4u; lc4++) {
+					mgl_plan_packet(&L, &W, MGL_MATCH, D - 1u, 2u + lc4, 0u, 0u, 0u, &pl);
+					const uint32_t from = pl.nhdr + pl.len_nchoice + pl.len_tbits;
+					b[lc4] = opt_events(pl, prices, 0, pl.nhdr) + opt_events(pl, prices, from, pl.nev) + (pl.ndirect << 11);
+				}
+				sb0 = b[0]; sb1 = b[1]; sb2 = b[2]; sb3 = b[3];
+				skey = 5ull + D;
+			}
 		} else if (lane < 4u + 2u * cand && cap >= 2u && i + 1u < c.n) {
 			const uint32_t src = lane < 4u + cand ? 0u : 1u, k = lane - 4u - src * cand;
 			const uint32_t bigram = ((uint32_t)d[i] << 8) | d[i + 1];
@@ -224,7 +243,7 @@ __global__ void __launch_bounds__(64) k_opt_dp(DevCtx c, const uint32_t* prices,
 		for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)maxl, o, 64); maxl = t > maxl ? t : maxl; }
 		__syncthreads();
 
-		const uint32_t nsrc = 4u + 2u * cand;
+		const uint32_t nsrc = MF ? 4u + fcnt : 4u + 2u * cand;
 		for (uint32_t l = 1u + lane; l <= (maxl > 1u ? maxl : 1u); l += 64u) {
 			uint64_t best = ~0ull, bkey = ~0ull;
 			uint32_t btype = 0, bx = 0;

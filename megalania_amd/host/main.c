@@ -28,7 +28,7 @@ static void usage(const char* argv0)
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
 	        "          [--lc N --lp N --pb N | --props auto [--props-rounds R] [--props-table]] [--device D] [--max-scan M]\n"
 	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P | --adaptive-seed P]\n"
-	        "          [--temperature B]\n"
+	        "          [--match-finder nearest|frontier [--mf-depth N]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
@@ -42,7 +42,11 @@ static void usage(const char* argv0)
 	        "  --adaptive-seed P  as --optimal-seed, but the parses are priced from the live probability model, refreshed as\n"
 	        "               each segment of a chunk is committed (e.g. 3); not with --optimal-seed, --greedy-seed,\n"
 	        "               --seed-stream or --load-slab\n"
-	        "  --seed-stream F  start from the parse inside an existing .lzma / .xz stream of this input (e.g. xz -9e's):\n"
+	        "  --match-finder F  where --optimal-seed / --adaptive-seed / --props auto take a node's match sources from: the\n"
+        "               nearest candidates of the two- and four-byte orders (nearest, default) or the nearest source of every\n"
+        "               achievable length (frontier); --mf-depth N bounds the run entries the frontier examines per position\n"
+        "               (default 64, at most 4096)\n"
+        "  --seed-stream F  start from the parse inside an existing .lzma / .xz stream of this input (e.g. xz -9e's):\n"
 	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's\n"
 	        "  --clip-window    with --seed-stream: copies from beyond the dictionary window become literals instead\n"
 	        "               of an error\n"
@@ -64,9 +68,12 @@ static void usage(const char* argv0)
 }
 
 /* the seed made on the device: the best of `passes` optimal parses, under static prices or (adaptive) the live model's */
-typedef struct { uint32_t passes; bool adaptive; } seed_spec;
+typedef struct { uint32_t passes; bool adaptive; int finder; uint32_t mf_depth; } seed_spec;
 static int make_seed(mgl_sa* sa, seed_spec seed, mgl_optimal_stats* os)
 {
+	/* set on every handle a seed is made on: --props auto makes fresh ones */
+	int rc = mgl_sa_set_match_finder(sa, seed.finder, seed.mf_depth);
+	if (rc != MGL_OK) return rc;
 	if (seed.adaptive) {
 		mgl_adaptive_config ac = { seed.passes, 0, 0, 0, 0, 0 };
 		return mgl_sa_seed_adaptive(sa, &ac, os);
@@ -161,7 +168,9 @@ int main(int argc, char** argv)
 	int clip_window = 0, props_given = 0;
 	bool props_auto = false, props_table = false;
 	unsigned props_rounds = 3;
-	uint32_t greedy = 0, optimal = 0, adaptive = 0;
+	uint32_t greedy = 0, optimal = 0, adaptive = 0, mf_depth = 0;
+	int finder = MGL_MF_NEAREST;
+	bool finder_given = false;
 	mgl_packet* optimal_slab = NULL;
 	double temperature_bytes = 0;
 	int accept_mode = MGL_ACCEPT_AUTO;
@@ -205,6 +214,13 @@ int main(int argc, char** argv)
 		else if (!strcmp(a, "--greedy-seed")) greedy = (uint32_t)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--optimal-seed")) { optimal = (uint32_t)strtoul(v, NULL, 0); if (!optimal) { usage(argv[0]); return -1; } }
 		else if (!strcmp(a, "--adaptive-seed")) { adaptive = (uint32_t)strtoul(v, NULL, 0); if (!adaptive) { usage(argv[0]); return -1; } }
+		else if (!strcmp(a, "--match-finder")) {
+			if (!strcmp(v, "nearest")) finder = MGL_MF_NEAREST;
+			else if (!strcmp(v, "frontier")) finder = MGL_MF_FRONTIER;
+			else { usage(argv[0]); return -1; }
+			finder_given = true;
+		}
+		else if (!strcmp(a, "--mf-depth")) { mf_depth = (uint32_t)strtoul(v, NULL, 0); if (!mf_depth || mf_depth > 4096) { usage(argv[0]); return -1; } }
 		else if (!strcmp(a, "--seed-stream")) seed_stream_path = v;
 		else if (!strcmp(a, "--temperature")) temperature_bytes = strtod(v, NULL);
 		else if (!strcmp(a, "--accept")) {
@@ -232,7 +248,13 @@ int main(int argc, char** argv)
 		usage(argv[0]);
 		return -1;
 	}
-	const seed_spec seed = { adaptive ? adaptive : optimal, adaptive != 0 }; /* passes 0: no seed of this kind */
+	if ((finder_given || mf_depth) && !(optimal || adaptive || props_auto)) {
+		fprintf(stderr, "Error: --match-finder / --mf-depth need --optimal-seed, --adaptive-seed or --props auto\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (mf_depth && finder != MGL_MF_FRONTIER) { usage(argv[0]); return -1; }
+	const seed_spec seed = { adaptive ? adaptive : optimal, adaptive != 0, finder, mf_depth }; /* passes 0: no seed of this kind */
 	if (clip_window && !seed_stream_path) { usage(argv[0]); return -1; }
 	if (props_auto && (props_given || chains > 1)) {
 		fprintf(stderr, "Error: --props auto cannot be combined with --lc/--lp/--pb or with --chains above 1\n");
@@ -404,8 +426,16 @@ int main(int argc, char** argv)
 		}
 		double ms = 0;
 		for (uint32_t p = 0; p < os.passes; p++) ms += os.ms[p];
-		fprintf(stderr, "%s seed: %u passes in %.1f ms, estimate %f bytes (greedy parse %f)\n", seed.adaptive ? "adaptive" : "optimal", os.passes, ms,
-		        18 + cost / 16384.f, 18 + os.greedy_cost / 16384.f);
+		char mf[96] = "nearest";
+		if (seed.finder == MGL_MF_FRONTIER) {
+			/* the lists the seed used are still in the handle: only their count and build time are asked for */
+			size_t entries = 0;
+			double build_ms = 0;
+			if (mgl_match_frontier(sa, seed.mf_depth, NULL, NULL, NULL, (size_t)-1, &entries, &build_ms) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+			snprintf(mf, sizeof mf, "frontier, %zu entries built in %.2f ms", entries, build_ms);
+		}
+		fprintf(stderr, "%s seed: %u passes in %.1f ms, estimate %f bytes (greedy parse %f), match finder %s\n", seed.adaptive ? "adaptive" : "optimal", os.passes, ms,
+		        18 + cost / 16384.f, 18 + os.greedy_cost / 16384.f, mf);
 	}
 
 	unsigned long long steps_per_epoch = (file_size + cfg.neighbours_per_step - 1) / cfg.neighbours_per_step;
