@@ -216,6 +216,33 @@ int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, mgl_optimal
  * the prices of what each committed.  segment 0 takes the default commit distance.  The SA state is untouched. */
 int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead,
                       mgl_packet* packets_out, uint64_t* objective);
+/* The adaptive parse under several settings at once.  Variant v is the parse that
+ * mgl_sa_seed_adaptive({passes, cand, chunk, segment, ahead, from_current}) makes on a handle set to
+ * mgl_sa_set_match_finder(finder, depth); all variants run through one launch of each stage, and results[v] (nvariants
+ * entries, nullable) holds that call's passes, best_pass, greedy_cost, cost[] and objective[].  results[v].ms[p] is the
+ * device time of pass p of the whole batch, *gpu_ms (nullable) that of the whole call.  The cheapest cost[p] over all
+ * (variant, pass) -- ties to the lower variant, then to the lower pass -- becomes the current slab, with
+ * mgl_sa_seed_adaptive's effect on the handle, and *best_variant (nullable) names its variant.  With from_current the
+ * current slab competes: if nothing beats it the handle is left untouched and *best_variant is UINT32_MAX.  The handle's
+ * own match-finder selection stays; the frontier's lists are made (or reused) at `depth` only if a variant asks for them.
+ * MGL_EINVAL: no or more than MGL_SWEEP_MAX variants, an unknown finder, cand above 30, ahead above 273, chunk below 512,
+ * more than 16 passes, depth above 4096.  MGL_ENOMEM: the per-variant buffers (about 26 bytes per input byte and variant)
+ * do not fit; the handle stays usable. */
+#define MGL_SWEEP_MAX 64
+typedef struct {
+	uint32_t finder;   /* MGL_MF_NEAREST | MGL_MF_FRONTIER */
+	uint32_t cand;     /* 0 = default 16, at most 30 */
+	uint32_t segment;  /* 0 = default (64, with ahead 128), as in mgl_adaptive_config */
+	uint32_t ahead;    /* at most 273 */
+} mgl_parse_variant;
+typedef struct {
+	uint32_t passes;       /* default 3, at most MGL_OPT_MAX_PASSES */
+	uint32_t chunk;        /* default 4096, at least 512; common to all variants */
+	uint32_t depth;        /* frontier scan budget; 0 = the handle's (default 64), at most 4096 */
+	uint32_t from_current; /* as in mgl_adaptive_config */
+} mgl_parse_sweep_config;
+int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, size_t nvariants,
+                      mgl_optimal_stats* results /* nvariants entries */, uint32_t* best_variant, double* gpu_ms);
 /* The match finder of the parses above (not in the reference; DESIGN.md section 10, megalania_amd/csrc/mgl_matchfinder.hip):
  * where a node of the shortest path takes its MATCH sources from.  MGL_MF_NEAREST (default): the `cand` nearest earlier
  * positions with the same two bytes and the `cand` nearest with the same four.  MGL_MF_FRONTIER: for every achievable

@@ -33,7 +33,7 @@ MF_NEAREST, MF_FRONTIER = 0, 1
 
 HIP_SYMBOLS = [
     "mgl_version", "mgl_last_error", "mgl_device_count", "mgl_sa_create", "mgl_sa_destroy", "mgl_sa_begin_epoch",
-    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_seed_adaptive", "mgl_adaptive_pass", "mgl_sa_set_match_finder", "mgl_match_frontier", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
+    "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_seed_adaptive", "mgl_adaptive_pass", "mgl_sa_seed_sweep", "mgl_sa_set_match_finder", "mgl_match_frontier", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
     "mgl_substrings", "mgl_neighbours", "mgl_rng_draw_at", "mgl_debug_dump", "mgl_debug_set",
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep",
@@ -106,6 +106,18 @@ class AdaptiveConfig(C.Structure):
                 ("ahead", C.c_uint32), ("from_current", C.c_uint32)]
 
 
+class ParseVariant(C.Structure):
+    _fields_ = [("finder", C.c_uint32), ("cand", C.c_uint32), ("segment", C.c_uint32), ("ahead", C.c_uint32)]
+
+
+class ParseSweepConfig(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("chunk", C.c_uint32), ("depth", C.c_uint32), ("from_current", C.c_uint32)]
+
+
+# the CLI's --parse-sweep grid (host/main.c: sweep_grid), (finder, cand, segment, ahead); index 0 is the library's default
+DEFAULT_SWEEP = [(f, 16, s, a) for f in (MF_NEAREST, MF_FRONTIER) for s in (64, 32, 128, 256) for a in (128, 273)]
+
+
 class PropsCost(C.Structure):
     _fields_ = [("props", Properties), ("cost", C.c_uint64)]
 
@@ -157,6 +169,8 @@ def hip_lib():
         L.mgl_sa_seed_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveConfig), C.POINTER(OptimalStats)]
         L.mgl_adaptive_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.POINTER(C.c_uint64)]
+        L.mgl_sa_seed_sweep.argtypes = [C.c_void_p, C.POINTER(ParseSweepConfig), C.POINTER(ParseVariant), C.c_size_t,
+                                        C.POINTER(OptimalStats), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         L.mgl_sa_set_match_finder.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
         L.mgl_match_frontier.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
@@ -362,6 +376,23 @@ class SA:
         k = st.passes
         return dict(passes=k, best_pass=None if st.best_pass == 0xFFFFFFFF else st.best_pass, greedy_cost=st.greedy_cost,
                     cost=list(st.cost[:k]), objective=list(st.objective[:k]), ms=list(st.ms[:k]))
+
+    def seed_sweep(self, variants, passes: int = 0, chunk: int = 0, depth: int = 0, from_current: bool = False) -> dict:
+        """Current slab := the cheapest parse of a batch of adaptive parses (mgl_sa_seed_sweep).  variants: a list of
+        (finder, cand, segment, ahead), finder MF_NEAREST / MF_FRONTIER or their names; each is the parse seed_adaptive
+        makes under that finder, all run through the same launches.  Returns results (per variant, the dict seed_adaptive
+        returns; ms is the batch's), best_variant (None: from_current, and nothing beat the current slab) and gpu_ms."""
+        names = {"nearest": MF_NEAREST, "frontier": MF_FRONTIER}
+        nv = len(variants)
+        arr = (ParseVariant * max(1, nv))(*[ParseVariant(names.get(f, f), c, s, a) for f, c, s, a in variants])
+        st = (OptimalStats * max(1, nv))()
+        best, ms = C.c_uint32(0), C.c_double(0)
+        cfg = ParseSweepConfig(passes, chunk, depth, int(from_current))
+        self._chk(self.L.mgl_sa_seed_sweep(self.h, C.byref(cfg), arr, nv, st, C.byref(best), C.byref(ms)))
+        results = [dict(passes=r.passes, best_pass=None if r.best_pass == 0xFFFFFFFF else r.best_pass, greedy_cost=r.greedy_cost,
+                        cost=list(r.cost[:r.passes]), objective=list(r.objective[:r.passes]), ms=list(r.ms[:r.passes]))
+                   for r in st[:nv]]
+        return dict(results=results, best_variant=None if best.value == 0xFFFFFFFF else best.value, gpu_ms=ms.value)
 
     def adaptive_pass(self, parse_in, cand: int, chunk: int, segment: int, ahead: int):
         """One adaptive-price pass from the chunk starts of the valid slab `parse_in` (parity hook, SA state untouched).

@@ -11,6 +11,9 @@
  *   k_adp_dp    one workgroup (one wavefront) per chunk: k_opt_dp's forward shortest path, segment by segment (the
  *               instance <true> reads its MATCH sources from the lists of mgl_matchfinder.hip, as k_opt_dp<true>)
  *
+ * k_adp_snap_sweep and k_adp_dp_sweep run the same two bodies for several variants of the settings at once (one wavefront
+ * per variant, one workgroup per chunk and variant): mgl_sa_seed_sweep.
+ *
  * The rule is restated in plain Python in tests/test_adaptive_rule_cpu.py.
  */
 #include "mgl_device.h"
@@ -25,8 +28,8 @@ __host__ __device__ static inline uint32_t adp_stride(const mgl_layout& L) { ret
  * the four rep distances, and snaps[m x stride ..] = the model, both as they stand before the packet that starts there.
  * A chunk start inside a packet takes the LZMA initial state and the model before that packet.  snaps == nullptr: none
  * are written.  *cost_out = the exact cost of the (resolved) parse. */
-__global__ void __launch_bounds__(64) k_adp_snap(DevCtx c, const mgl_pk* in, mgl_pk* out, int resolve, uint32_t chunk,
-                                                 uint32_t* entry, uint16_t* snaps, uint64_t* cost_out)
+__device__ __forceinline__ void adp_snap_walk(const DevCtx& c, const mgl_pk* in, mgl_pk* out, int resolve, uint32_t chunk,
+                                              uint32_t* entry, uint16_t* snaps, uint64_t* cost_out)
 {
 	__shared__ uint16_t T[2048];
 	__shared__ __align__(4) uint16_t probs[MGL_ADP_MAX_PROBS];
@@ -97,6 +100,29 @@ __global__ void __launch_bounds__(64) k_adp_snap(DevCtx c, const mgl_pk* in, mgl
 	if (lane == 0) *cost_out = total;
 }
 
+__global__ void __launch_bounds__(64) k_adp_snap(DevCtx c, const mgl_pk* in, mgl_pk* out, int resolve, uint32_t chunk,
+                                                 uint32_t* entry, uint16_t* snaps, uint64_t* cost_out)
+{
+	adp_snap_walk(c, in, out, resolve, chunk, entry, snaps, cost_out);
+}
+
+__global__ void k_fill_literal_sweep(mgl_pk* slabs, size_t count)
+{
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) slabs[i] = MGL_PK_LITERAL;
+}
+
+/* The sweep (mgl_sa_seed_sweep): one wavefront per variant, each walking its own parse.  Variant v reads slab
+ * in_idx[v] of `in` (in_idx == nullptr: slab v; pass 0's starts are shared by the variants of one `cand`) and writes
+ * slab v of `out`, its own nch chunk starts and cost[v]. */
+__global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const mgl_pk* in, const uint32_t* in_idx, mgl_pk* out, int resolve,
+                                                       uint32_t chunk, uint32_t nch, uint32_t* entry, uint16_t* snaps, uint64_t* cost)
+{
+	const uint32_t v = blockIdx.x;
+	const size_t n = c.n;
+	adp_snap_walk(c, in + (in_idx ? in_idx[v] : v) * n, out ? out + v * n : nullptr, resolve, chunk, entry + (size_t)v * 5u * nch,
+	              snaps ? snaps + (size_t)v * nch * adp_stride(c.L) : nullptr, cost + v);
+}
+
 /* price of events [from, to) of a planned packet under the model M */
 __device__ __forceinline__ uint32_t adp_events(const mgl_plan& pl, const uint16_t* M, const uint16_t* T, uint32_t from, uint32_t to)
 {
@@ -121,9 +147,9 @@ extern __shared__ __align__(4) uint16_t adp_model[]; /* the chunk's model: adp_s
  *
  * back[] and out[] are read and written by lane 0 alone (what the other lanes need of an entry is broadcast). */
 template <bool MF>
-__global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, const uint16_t* snaps, uint32_t chunk, uint32_t cand,
-                                               uint32_t segment, uint32_t ahead, mgl_pk* back, mgl_pk* out, unsigned long long* objective,
-                                               MfLists mf)
+__device__ __forceinline__ void adp_dp_chunk(const DevCtx& c, const uint32_t m, const uint32_t* entry, const uint16_t* snaps, uint32_t chunk,
+                                             uint32_t cand, uint32_t segment, uint32_t ahead, mgl_pk* back, mgl_pk* out,
+                                             unsigned long long* objective, const MfLists& mf)
 {
 	__shared__ uint64_t r_tot[MGL_OPT_RING];
 	__shared__ uint64_t r_edge[MGL_OPT_RING];
@@ -137,7 +163,7 @@ __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, 
 	uint16_t* M = adp_model;
 
 	const uint32_t lane = threadIdx.x;
-	const uint32_t s = blockIdx.x * chunk;
+	const uint32_t s = m * chunk;
 	const uint32_t e = (s + chunk) < c.n ? (s + chunk) : c.n;
 	const uint32_t nps = 1u << c.L.pb;
 	const mgl_layout L = c.L;
@@ -146,15 +172,15 @@ __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, 
 
 	for (uint32_t k = lane; k < 2048u; k += 64u) T[k] = c.cost_tbl[k];
 	{
-		const uint32_t* src = (const uint32_t*)(snaps + (size_t)blockIdx.x * stride);
+		const uint32_t* src = (const uint32_t*)(snaps + (size_t)m * stride);
 		uint32_t* dst = (uint32_t*)M;
 		for (uint32_t k = lane; k < stride / 2u; k += 64u) dst[k] = src[k];
 	}
 	/* the anchor: position a, its exact walk state A (uniform) */
 	mgl_wstate A;
-	A.pos = s; A.ctx_state = entry[5u * blockIdx.x];
-	A.dists[0] = entry[5u * blockIdx.x + 1u]; A.dists[1] = entry[5u * blockIdx.x + 2u];
-	A.dists[2] = entry[5u * blockIdx.x + 3u]; A.dists[3] = entry[5u * blockIdx.x + 4u];
+	A.pos = s; A.ctx_state = entry[5u * m];
+	A.dists[0] = entry[5u * m + 1u]; A.dists[1] = entry[5u * m + 2u];
+	A.dists[2] = entry[5u * m + 3u]; A.dists[3] = entry[5u * m + 4u];
 	uint64_t obj = 0;
 	__syncthreads();
 
@@ -360,4 +386,27 @@ __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, 
 		__syncthreads();
 	}
 	if (lane == 0) atomicAdd(objective, (unsigned long long)obj);
+}
+
+template <bool MF>
+__global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, const uint16_t* snaps, uint32_t chunk, uint32_t cand,
+                                               uint32_t segment, uint32_t ahead, mgl_pk* back, mgl_pk* out, unsigned long long* objective,
+                                               MfLists mf)
+{
+	adp_dp_chunk<MF>(c, blockIdx.x, entry, snaps, chunk, cand, segment, ahead, back, out, objective, mf);
+}
+
+/* The sweep: workgroup (m, y) runs chunk m of variant v = list[y], one of the variants of this instance's finder, with
+ * that variant's settings from `tab` and on its slice of entry, snaps, back, out and objective. */
+struct AdpVariant { uint32_t cand, segment, ahead, pad; };
+template <bool MF>
+__global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant* tab, const uint32_t* list, uint32_t nch, const uint32_t* entry,
+                                                     const uint16_t* snaps, uint32_t chunk, mgl_pk* back, mgl_pk* out,
+                                                     unsigned long long* objective, MfLists mf)
+{
+	const uint32_t v = list[blockIdx.y];
+	const AdpVariant t = tab[v];
+	const size_t n = c.n;
+	adp_dp_chunk<MF>(c, blockIdx.x, entry + (size_t)v * 5u * nch, snaps + (size_t)v * nch * adp_stride(c.L), chunk, t.cand, t.segment, t.ahead,
+	                 back + v * (n + 1u), out + v * n, objective + v, mf);
 }

@@ -1630,6 +1630,176 @@ extern "C" int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, 
 	return MGL_OK;
 }
 
+/* ---- the sweep: several variants of the adaptive parse through one launch per stage, the cheapest parse kept */
+struct SweepBufs {
+	uint16_t* snaps = nullptr;
+	uint32_t *entry = nullptr, *lists = nullptr, *start_idx = nullptr;
+	mgl_pk *back = nullptr, *dp = nullptr, *res = nullptr, *keep = nullptr, *starts = nullptr;
+	unsigned long long* obj = nullptr;
+	uint64_t* cost = nullptr;
+	AdpVariant* tab = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr, call0 = nullptr, call1 = nullptr, fork = nullptr, join = nullptr;
+	~SweepBufs()
+	{
+		dfree(snaps); dfree(entry); dfree(lists); dfree(start_idx); dfree(back); dfree(dp); dfree(res); dfree(keep); dfree(starts);
+		dfree(obj); dfree(cost); dfree(tab);
+		for (hipEvent_t e : { t0, t1, call0, call1, fork, join })
+			if (e) (void)hipEventDestroy(e);
+	}
+};
+/* an allocation of the sweep that does not fit is MGL_ENOMEM, and leaves no error behind for the next launch check */
+#define SWEEP_ALLOC(ptr, bytes)                                                                          \
+	do {                                                                                                 \
+		if (hipMalloc(&(ptr), (bytes)) != hipSuccess) {                                                  \
+			(void)hipGetLastError();                                                                     \
+			return fail(MGL_ENOMEM, "mgl_sa_seed_sweep: the per-variant buffers do not fit the device"); \
+		}                                                                                                \
+	} while (0)
+
+extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, size_t nvariants,
+                                 mgl_optimal_stats* results, uint32_t* best_variant, double* gpu_ms)
+{
+	if (!sa || !variants) return fail(MGL_EINVAL, "null argument");
+	if (nvariants == 0 || nvariants > MGL_SWEEP_MAX) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: 1 to 64 variants");
+	const uint32_t passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
+	uint32_t chunk = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
+	const uint32_t depth = cfg && cfg->depth ? cfg->depth : sa->mf_depth;
+	const bool from_current = cfg && cfg->from_current;
+	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: at most 16 passes");
+	if (depth > MGL_MF_MAX_DEPTH) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: depth must be at most 4096");
+	const uint32_t nv = (uint32_t)nvariants, n = (uint32_t)sa->n;
+	/* per variant: its settings after the defaults and clamps of mgl_sa_seed_adaptive; the greedy parse of its cand */
+	AdpVariant tab[MGL_SWEEP_MAX];
+	uint32_t lists[MGL_SWEEP_MAX], start_idx[MGL_SWEEP_MAX], cands[MGL_SWEEP_MAX], ncand = 0, nnear = 0;
+	for (uint32_t v = 0; v < nv; v++) {
+		if (variants[v].finder != MGL_MF_NEAREST && variants[v].finder != MGL_MF_FRONTIER) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: unknown finder");
+		uint32_t ch = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
+		tab[v].cand = variants[v].cand ? variants[v].cand : MGL_OPT_DEF_CAND;
+		tab[v].segment = variants[v].segment; tab[v].ahead = variants[v].ahead; tab[v].pad = 0;
+		int rc = adp_args(sa, tab[v].cand, ch, tab[v].segment, tab[v].ahead, false);
+		if (rc) return rc;
+		chunk = ch; /* the same for every variant */
+		uint32_t k = 0;
+		while (k < ncand && cands[k] != tab[v].cand) k++;
+		if (k == ncand) cands[ncand++] = tab[v].cand;
+		start_idx[v] = from_current ? 0u : k;
+		if (variants[v].finder == MGL_MF_NEAREST) lists[nnear++] = v;
+	}
+	const uint32_t nfront = nv - nnear;
+	for (uint32_t v = 0, k = nnear; v < nv; v++)
+		if (variants[v].finder == MGL_MF_FRONTIER) lists[k++] = v;
+	HIPCHK(hipSetDevice(sa->device));
+	if (nfront) { int rc = mf_ensure(sa, depth); if (rc) return rc; }
+	const size_t nch = ((size_t)n + chunk - 1) / chunk, stride = adp_stride(sa->ctx.L);
+	SweepBufs o;
+	SWEEP_ALLOC(o.snaps, sizeof(uint16_t) * stride * nch * nv);
+	SWEEP_ALLOC(o.entry, sizeof(uint32_t) * 5 * nch * nv);
+	SWEEP_ALLOC(o.back, sizeof(mgl_pk) * ((size_t)n + 1) * nv);
+	SWEEP_ALLOC(o.dp, sizeof(mgl_pk) * (size_t)n * nv);
+	SWEEP_ALLOC(o.res, sizeof(mgl_pk) * (size_t)n * nv);
+	SWEEP_ALLOC(o.keep, sizeof(mgl_pk) * (size_t)n);
+	if (!from_current) SWEEP_ALLOC(o.starts, sizeof(mgl_pk) * (size_t)n * ncand);
+	SWEEP_ALLOC(o.obj, sizeof(unsigned long long) * nv);
+	SWEEP_ALLOC(o.cost, sizeof(uint64_t) * nv);
+	SWEEP_ALLOC(o.tab, sizeof(AdpVariant) * nv);
+	SWEEP_ALLOC(o.lists, sizeof(uint32_t) * nv);
+	SWEEP_ALLOC(o.start_idx, sizeof(uint32_t) * nv);
+	for (hipEvent_t* e : { &o.t0, &o.t1, &o.call0, &o.call1, &o.fork, &o.join }) HIPCHK(hipEventCreate(e));
+	const uint32_t lds = (uint32_t)stride * (uint32_t)sizeof(uint16_t);
+	if (nnear) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	if (nfront) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	HIPCHK(hipEventRecord(o.call0, sa->stream));
+	HIPCHK(hipMemcpyAsync(o.tab, tab, sizeof(AdpVariant) * nv, hipMemcpyHostToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(o.lists, lists, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(o.start_idx, start_idx, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
+	/* pass 0's chunk starts: one greedy parse per distinct cand, or the current slab (which then has to be beaten) */
+	const mgl_pk* first = sa->base.v.slab;
+	if (!from_current) {
+		for (uint32_t k = 0; k < ncand; k++)
+			hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.starts + (size_t)k * n, cands[k]);
+		first = o.starts;
+	}
+	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, first, (const uint32_t*)o.start_idx, (mgl_pk*)nullptr, 0, chunk,
+	                   (uint32_t)nch, o.entry, o.snaps, o.cost);
+	HIPCHK(hipGetLastError());
+	std::vector<mgl_optimal_stats> st(nv);
+	memset(st.data(), 0, sizeof(mgl_optimal_stats) * nv);
+	uint64_t h_cost[MGL_SWEEP_MAX];
+	unsigned long long h_obj[MGL_SWEEP_MAX];
+	HIPCHK(hipMemcpyAsync(h_cost, o.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	uint64_t vbest[MGL_SWEEP_MAX]; /* what variant v would have to beat on a handle of its own */
+	for (uint32_t v = 0; v < nv; v++) {
+		st[v].greedy_cost = h_cost[v];
+		st[v].best_pass = UINT32_MAX;
+		vbest[v] = from_current ? h_cost[v] : ~0ull;
+	}
+	/* the cheapest (variant, pass): ties to the lower variant, then to the lower pass; with from_current the current slab
+	 * holds every tie */
+	uint64_t best = from_current ? h_cost[0] : ~0ull;
+	uint32_t best_v = UINT32_MAX;
+	for (uint32_t p = 0; p < passes; p++) {
+		HIPCHK(hipEventRecord(o.t0, sa->stream));
+		hipLaunchKernelGGL(k_fill_literal_sweep, dim3(1024), dim3(256), 0, sa->stream, o.dp, (size_t)n * nv);
+		hipLaunchKernelGGL(k_fill_literal_sweep, dim3(1024), dim3(256), 0, sa->stream, o.res, (size_t)n * nv);
+		HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long) * nv, sa->stream));
+		if (nfront) {
+			/* the two instances side by side: the frontier's on the handle's second stream */
+			HIPCHK(hipEventRecord(o.fork, sa->stream));
+			HIPCHK(hipStreamWaitEvent(sa->stream2, o.fork, 0));
+			hipLaunchKernelGGL(k_adp_dp_sweep<true>, dim3((uint32_t)nch, nfront), dim3(64), lds, sa->stream2, sa->ctx, (const AdpVariant*)o.tab,
+			                   (const uint32_t*)o.lists + nnear, (uint32_t)nch, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, o.back, o.dp, o.obj,
+			                   mf_lists(sa));
+			HIPCHK(hipEventRecord(o.join, sa->stream2));
+		}
+		if (nnear)
+			hipLaunchKernelGGL(k_adp_dp_sweep<false>, dim3((uint32_t)nch, nnear), dim3(64), lds, sa->stream, sa->ctx, (const AdpVariant*)o.tab,
+			                   (const uint32_t*)o.lists, (uint32_t)nch, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, o.back, o.dp, o.obj,
+			                   MfLists{});
+		if (nfront) HIPCHK(hipStreamWaitEvent(sa->stream, o.join, 0));
+		hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const mgl_pk*)o.dp, (const uint32_t*)nullptr, o.res, 1, chunk,
+		                   (uint32_t)nch, o.entry, p + 1 < passes ? o.snaps : (uint16_t*)nullptr, o.cost);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(h_obj, o.obj, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, sa->stream));
+		HIPCHK(hipMemcpyAsync(h_cost, o.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->stream));
+		HIPCHK(hipEventRecord(o.t1, sa->stream));
+		HIPCHK(hipEventSynchronize(o.t1));
+		float ms = 0;
+		HIPCHK(hipEventElapsedTime(&ms, o.t0, o.t1));
+		uint32_t keep_v = UINT32_MAX;
+		for (uint32_t v = 0; v < nv; v++) {
+			st[v].cost[p] = h_cost[v]; st[v].objective[p] = h_obj[v]; st[v].ms[p] = ms; st[v].passes = p + 1;
+			if (h_cost[v] < vbest[v]) { vbest[v] = h_cost[v]; st[v].best_pass = p; }
+			if (h_cost[v] < best || (h_cost[v] == best && best_v != UINT32_MAX && v < best_v)) { best = h_cost[v]; best_v = keep_v = v; }
+		}
+		if (keep_v != UINT32_MAX)
+			HIPCHK(hipMemcpyAsync(o.keep, o.res + (size_t)keep_v * n, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
+	}
+	if (best_v != UINT32_MAX) {
+		/* the cheapest parse becomes the current slab, as in mgl_sa_seed_adaptive */
+		Control c;
+		int rc;
+		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+		if ((rc = keep_best_before_overwrite(sa, c))) return rc;
+		if ((rc = write_ctl(sa, sa->base, &c))) return rc;
+		sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
+		uint64_t built = 0;
+		if ((rc = opt_make_current(sa, o.keep, &built))) return rc;
+		if ((rc = launch_validate(sa))) return rc;
+		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+		if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_sweep: the seeded slab failed the walk check");
+		if (built != best) return fail(MGL_EDEVICE, "mgl_sa_seed_sweep: the walk's cost of the seeded slab differs from the rebuild's");
+	}
+	HIPCHK(hipEventRecord(o.call1, sa->stream));
+	HIPCHK(hipEventSynchronize(o.call1));
+	float call_ms = 0;
+	HIPCHK(hipEventElapsedTime(&call_ms, o.call0, o.call1));
+	if (results) memcpy(results, st.data(), sizeof(mgl_optimal_stats) * nv);
+	if (best_variant) *best_variant = best_v;
+	if (gpu_ms) *gpu_ms = call_ms;
+	return MGL_OK;
+}
+
 static hipEvent_t pool_event(mgl_sa* sa, size_t i)
 {
 	while (sa->ev_pool.size() <= i) {

@@ -28,7 +28,7 @@ static void usage(const char* argv0)
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
 	        "          [--lc N --lp N --pb N | --props auto [--props-rounds R] [--props-table]] [--device D] [--max-scan M]\n"
 	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P | --adaptive-seed P]\n"
-	        "          [--match-finder nearest|frontier [--mf-depth N]] [--temperature B]\n"
+	        "          [--match-finder nearest|frontier [--mf-depth N]] [--parse-sweep [--parse-sweep-table]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
@@ -46,6 +46,10 @@ static void usage(const char* argv0)
         "               nearest candidates of the two- and four-byte orders (nearest, default) or the nearest source of every\n"
         "               achievable length (frontier); --mf-depth N bounds the run entries the frontier examines per position\n"
         "               (default 64, at most 4096)\n"
+	        "  --parse-sweep    with --adaptive-seed P: the seed is made under 16 settings at once (both match finders, commit\n"
+	        "               distances 64, 32, 128, 256, look-ahead 128 and 273) and the cheapest parse is kept; --mf-depth N\n"
+	        "               applies to the frontier's variants; not with --match-finder.  --parse-sweep-table prints every\n"
+	        "               variant's per-pass sizes\n"
         "  --seed-stream F  start from the parse inside an existing .lzma / .xz stream of this input (e.g. xz -9e's):\n"
 	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's\n"
 	        "  --clip-window    with --seed-stream: copies from beyond the dictionary window become literals instead\n"
@@ -68,9 +72,44 @@ static void usage(const char* argv0)
 }
 
 /* the seed made on the device: the best of `passes` optimal parses, under static prices or (adaptive) the live model's */
-typedef struct { uint32_t passes; bool adaptive; int finder; uint32_t mf_depth; } seed_spec;
+typedef struct { uint32_t passes; bool adaptive; int finder; uint32_t mf_depth; bool sweep, sweep_table; } seed_spec;
+
+/* --parse-sweep's grid (mirrored by binding.DEFAULT_SWEEP): index 0 is the library's default, which therefore holds a tie */
+#define SWEEP_GRID 16
+static const mgl_parse_variant sweep_grid[SWEEP_GRID] = {
+	{ MGL_MF_NEAREST, 16, 64, 128 },   { MGL_MF_NEAREST, 16, 64, 273 },   { MGL_MF_NEAREST, 16, 32, 128 },   { MGL_MF_NEAREST, 16, 32, 273 },
+	{ MGL_MF_NEAREST, 16, 128, 128 },  { MGL_MF_NEAREST, 16, 128, 273 },  { MGL_MF_NEAREST, 16, 256, 128 },  { MGL_MF_NEAREST, 16, 256, 273 },
+	{ MGL_MF_FRONTIER, 16, 64, 128 },  { MGL_MF_FRONTIER, 16, 64, 273 },  { MGL_MF_FRONTIER, 16, 32, 128 },  { MGL_MF_FRONTIER, 16, 32, 273 },
+	{ MGL_MF_FRONTIER, 16, 128, 128 }, { MGL_MF_FRONTIER, 16, 128, 273 }, { MGL_MF_FRONTIER, 16, 256, 128 }, { MGL_MF_FRONTIER, 16, 256, 273 },
+};
+
+/* the adaptive seed under every variant of the grid at once; *os = the winner's stats */
+static int make_sweep_seed(mgl_sa* sa, seed_spec seed, mgl_optimal_stats* os)
+{
+	mgl_optimal_stats res[SWEEP_GRID];
+	const mgl_parse_sweep_config sc = { seed.passes, 0, seed.mf_depth, 0 };
+	uint32_t best = 0;
+	double ms = 0;
+	int rc = mgl_sa_seed_sweep(sa, &sc, sweep_grid, SWEEP_GRID, res, &best, &ms);
+	if (rc != MGL_OK) return rc;
+	if (best >= SWEEP_GRID) return MGL_EDEVICE; /* without from_current some variant always wins */
+	if (seed.sweep_table)
+		for (uint32_t v = 0; v < SWEEP_GRID; v++) {
+			fprintf(stderr, "parse-sweep-table: %s cand %u segment %u ahead %u:", sweep_grid[v].finder == MGL_MF_FRONTIER ? "frontier" : "nearest",
+			        sweep_grid[v].cand, sweep_grid[v].segment, sweep_grid[v].ahead);
+			for (uint32_t p = 0; p < res[v].passes; p++) fprintf(stderr, " %.1f", 18 + res[v].cost[p] / 16384.0);
+			fprintf(stderr, " B%s\n", v == best ? " *" : "");
+		}
+	fprintf(stderr, "parse sweep: variant %u (%s, cand %u, segment %u, ahead %u), pass %u, %.1f B; %u variants in %.1f ms\n", best,
+	        sweep_grid[best].finder == MGL_MF_FRONTIER ? "frontier" : "nearest", sweep_grid[best].cand, sweep_grid[best].segment,
+	        sweep_grid[best].ahead, res[best].best_pass, 18 + res[best].cost[res[best].best_pass] / 16384.0, SWEEP_GRID, ms);
+	*os = res[best];
+	return MGL_OK;
+}
+
 static int make_seed(mgl_sa* sa, seed_spec seed, mgl_optimal_stats* os)
 {
+	if (seed.sweep) return make_sweep_seed(sa, seed, os);
 	/* set on every handle a seed is made on: --props auto makes fresh ones */
 	int rc = mgl_sa_set_match_finder(sa, seed.finder, seed.mf_depth);
 	if (rc != MGL_OK) return rc;
@@ -170,7 +209,7 @@ int main(int argc, char** argv)
 	unsigned props_rounds = 3;
 	uint32_t greedy = 0, optimal = 0, adaptive = 0, mf_depth = 0;
 	int finder = MGL_MF_NEAREST;
-	bool finder_given = false;
+	bool finder_given = false, parse_sweep = false, parse_sweep_table = false;
 	mgl_packet* optimal_slab = NULL;
 	double temperature_bytes = 0;
 	int accept_mode = MGL_ACCEPT_AUTO;
@@ -184,6 +223,8 @@ int main(int argc, char** argv)
 		if (a[0] != '-') { filename = a; continue; }
 		if (!strcmp(a, "--clip-window")) { clip_window = 1; continue; }
 		if (!strcmp(a, "--props-table")) { props_table = true; continue; }
+		if (!strcmp(a, "--parse-sweep")) { parse_sweep = true; continue; }
+		if (!strcmp(a, "--parse-sweep-table")) { parse_sweep_table = true; continue; }
 		if (!v) { usage(argv[0]); return -1; }
 		if (!strcmp(a, "--neighbours")) cfg.neighbours_per_step = (uint32_t)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--epochs")) epochs = (unsigned)strtoul(v, NULL, 0);
@@ -253,8 +294,14 @@ int main(int argc, char** argv)
 		usage(argv[0]);
 		return -1;
 	}
-	if (mf_depth && finder != MGL_MF_FRONTIER) { usage(argv[0]); return -1; }
-	const seed_spec seed = { adaptive ? adaptive : optimal, adaptive != 0, finder, mf_depth }; /* passes 0: no seed of this kind */
+	if ((parse_sweep && !adaptive) || (parse_sweep_table && !parse_sweep)) { usage(argv[0]); return -1; }
+	if (parse_sweep && finder_given) {
+		fprintf(stderr, "Error: --parse-sweep runs both match finders; --match-finder cannot be combined with it\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (mf_depth && finder != MGL_MF_FRONTIER && !parse_sweep) { usage(argv[0]); return -1; }
+	const seed_spec seed = { adaptive ? adaptive : optimal, adaptive != 0, finder, mf_depth, parse_sweep, parse_sweep_table }; /* passes 0: no seed of this kind */
 	if (clip_window && !seed_stream_path) { usage(argv[0]); return -1; }
 	if (props_auto && (props_given || chains > 1)) {
 		fprintf(stderr, "Error: --props auto cannot be combined with --lc/--lp/--pb or with --chains above 1\n");
@@ -427,7 +474,8 @@ int main(int argc, char** argv)
 		double ms = 0;
 		for (uint32_t p = 0; p < os.passes; p++) ms += os.ms[p];
 		char mf[96] = "nearest";
-		if (seed.finder == MGL_MF_FRONTIER) {
+		if (seed.sweep) snprintf(mf, sizeof mf, "chosen by the parse sweep");
+		else if (seed.finder == MGL_MF_FRONTIER) {
 			/* the lists the seed used are still in the handle: only their count and build time are asked for */
 			size_t entries = 0;
 			double build_ms = 0;
