@@ -243,6 +243,24 @@ typedef struct {
 } mgl_parse_sweep_config;
 int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, size_t nvariants,
                       mgl_optimal_stats* results /* nvariants entries */, uint32_t* best_variant, double* gpu_ms);
+/* The same batch with a triple per variant: variant v is, integer for integer, the parse that
+ * mgl_sa_seed_adaptive({passes, cand, chunk, segment, ahead, from_current = 0}) makes on a fresh handle created with
+ * props[v] (same data, dict_limit and max_bucket_scan) and set to mgl_sa_set_match_finder(variants[v].finder, depth);
+ * results[v] (nvariants entries, nullable) holds that call's passes, best_pass, greedy_cost, cost[] and objective[], every
+ * cost exact under props[v], and ms[p] the batch's pass p.  The handle's own triple plays no part in any number.  The
+ * cheapest cost[p] over all (variant, pass) wins -- costs under different triples compared as they are, ties to the lower
+ * variant, then to the lower pass: *best_variant (nullable) names its variant and packets_out (n entries, nullable)
+ * receives its resolved parse, entry for entry what mgl_sa_current returns on that fresh handle after its
+ * mgl_sa_seed_adaptive.  The search state is untouched, as by the parity hooks (only the frontier's lists are made or
+ * reused at `depth` if a variant asks for them): the handle cannot cost a slab under a foreign triple, so the winner is
+ * not made current -- create a handle at the winning triple and give it the parse through mgl_sa_set_slab.
+ * MGL_EINVAL: whatever mgl_sa_seed_sweep refuses, props == NULL, a triple mgl_sa_create refuses (lc + lp > 4 or pb > 4),
+ * cfg->from_current != 0 (a current slab has a cost under one triple only).  MGL_ENOMEM as in mgl_sa_seed_sweep; a
+ * variant's snapshots take ceil(n / chunk) models of its own triple's size. */
+int mgl_parse_sweep_props(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants,
+                          const mgl_properties* props /* nvariants entries */, size_t nvariants,
+                          mgl_optimal_stats* results /* nvariants entries */, uint32_t* best_variant, mgl_packet* packets_out,
+                          double* gpu_ms);
 /* The match finder of the parses above (not in the reference; DESIGN.md section 10, megalania_amd/csrc/mgl_matchfinder.hip):
  * where a node of the shortest path takes its MATCH sources from.  MGL_MF_NEAREST (default): the `cand` nearest earlier
  * positions with the same two bytes and the `cand` nearest with the same four.  MGL_MF_FRONTIER: for every achievable

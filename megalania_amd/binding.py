@@ -36,7 +36,7 @@ HIP_SYMBOLS = [
     "mgl_sa_set_slab", "mgl_sa_seed_greedy", "mgl_sa_seed_optimal", "mgl_optimal_pass", "mgl_optimal_prices", "mgl_sa_seed_adaptive", "mgl_adaptive_pass", "mgl_sa_seed_sweep", "mgl_sa_set_match_finder", "mgl_match_frontier", "mgl_sa_set_temperature", "mgl_sa_set_accept_mode", "mgl_sa_step_modes", "mgl_sa_set_best", "mgl_sa_run", "mgl_sa_current", "mgl_sa_best", "mgl_cost_slab", "mgl_final_state", "mgl_top_k",
     "mgl_substrings", "mgl_neighbours", "mgl_rng_draw_at", "mgl_debug_dump", "mgl_debug_set",
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
-    "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep",
+    "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep", "mgl_parse_sweep_props",
 ]
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
@@ -171,6 +171,9 @@ def hip_lib():
                                         C.POINTER(C.c_uint64)]
         L.mgl_sa_seed_sweep.argtypes = [C.c_void_p, C.POINTER(ParseSweepConfig), C.POINTER(ParseVariant), C.c_size_t,
                                         C.POINTER(OptimalStats), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+        L.mgl_parse_sweep_props.argtypes = [C.c_void_p, C.POINTER(ParseSweepConfig), C.POINTER(ParseVariant),
+                                            C.POINTER(Properties), C.c_size_t, C.POINTER(OptimalStats), C.POINTER(C.c_uint32),
+                                            C.c_void_p, C.POINTER(C.c_double)]
         L.mgl_sa_set_match_finder.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
         L.mgl_match_frontier.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
@@ -393,6 +396,27 @@ class SA:
                         cost=list(r.cost[:r.passes]), objective=list(r.objective[:r.passes]), ms=list(r.ms[:r.passes]))
                    for r in st[:nv]]
         return dict(results=results, best_variant=None if best.value == 0xFFFFFFFF else best.value, gpu_ms=ms.value)
+
+    def parse_sweep_props(self, variants, props, passes: int = 0, chunk: int = 0, depth: int = 0, from_current: bool = False) -> dict:
+        """The batch of seed_sweep with a triple per variant (mgl_parse_sweep_props; SA state untouched).  variants as in
+        seed_sweep, props one (lc, lp, pb) per variant: each is the parse seed_adaptive makes on a fresh handle at its
+        triple, whatever this handle's own.  Returns results (per variant, costs exact under its triple), best_variant,
+        slab (the cheapest parse, as current() returns one) and gpu_ms."""
+        names = {"nearest": MF_NEAREST, "frontier": MF_FRONTIER}
+        nv = len(variants)
+        if len(props) != nv:
+            raise MglError("parse_sweep_props: one (lc, lp, pb) per variant", rc=-1)
+        arr = (ParseVariant * max(1, nv))(*[ParseVariant(names.get(f, f), c, s, a) for f, c, s, a in variants])
+        pr = (Properties * max(1, nv))(*[Properties(*t) for t in props])
+        st = (OptimalStats * max(1, nv))()
+        best, ms = C.c_uint32(0), C.c_double(0)
+        slab = np.zeros(self.n, dtype=PACKET)
+        cfg = ParseSweepConfig(passes, chunk, depth, int(from_current))
+        self._chk(self.L.mgl_parse_sweep_props(self.h, C.byref(cfg), arr, pr, nv, st, C.byref(best), _ptr(slab), C.byref(ms)))
+        results = [dict(passes=r.passes, best_pass=None if r.best_pass == 0xFFFFFFFF else r.best_pass, greedy_cost=r.greedy_cost,
+                        cost=list(r.cost[:r.passes]), objective=list(r.objective[:r.passes]), ms=list(r.ms[:r.passes]))
+                   for r in st[:nv]]
+        return dict(results=results, best_variant=best.value, slab=slab, gpu_ms=ms.value)
 
     def adaptive_pass(self, parse_in, cand: int, chunk: int, segment: int, ahead: int):
         """One adaptive-price pass from the chunk starts of the valid slab `parse_in` (parity hook, SA state untouched).

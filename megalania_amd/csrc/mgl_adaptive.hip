@@ -12,7 +12,8 @@
  *               instance <true> reads its MATCH sources from the lists of mgl_matchfinder.hip, as k_opt_dp<true>)
  *
  * k_adp_snap_sweep and k_adp_dp_sweep run the same two bodies for several variants of the settings at once (one wavefront
- * per variant, one workgroup per chunk and variant): mgl_sa_seed_sweep.
+ * per variant, one workgroup per chunk and variant): mgl_sa_seed_sweep.  A variant carries its own lc/lp/pb there
+ * (mgl_parse_sweep_props): the bodies take the probability layout as an argument, nothing else of a parse depends on it.
  *
  * The rule is restated in plain Python in tests/test_adaptive_rule_cpu.py.
  */
@@ -24,17 +25,16 @@
 /* u16 per snapshot: the model, padded to whole u32 words */
 __host__ __device__ static inline uint32_t adp_stride(const mgl_layout& L) { return (L.total + 1u) & ~1u; }
 
-/* One wavefront walks `in` with the live model.  Chunk start m (position m x chunk) gets entry[5 m ..] = ctx_state and
+/* One wavefront walks `in` with the live model laid out by L.  Chunk start m (position m x chunk) gets entry[5 m ..] = ctx_state and
  * the four rep distances, and snaps[m x stride ..] = the model, both as they stand before the packet that starts there.
  * A chunk start inside a packet takes the LZMA initial state and the model before that packet.  snaps == nullptr: none
  * are written.  *cost_out = the exact cost of the (resolved) parse. */
-__device__ __forceinline__ void adp_snap_walk(const DevCtx& c, const mgl_pk* in, mgl_pk* out, int resolve, uint32_t chunk,
+__device__ __forceinline__ void adp_snap_walk(const DevCtx& c, const mgl_layout L, const mgl_pk* in, mgl_pk* out, int resolve, uint32_t chunk,
                                               uint32_t* entry, uint16_t* snaps, uint64_t* cost_out)
 {
 	__shared__ uint16_t T[2048];
 	__shared__ __align__(4) uint16_t probs[MGL_ADP_MAX_PROBS];
 	const uint32_t lane = threadIdx.x;
-	const mgl_layout L = c.L;
 	const uint32_t stride = adp_stride(L);
 	for (uint32_t i = lane; i < 2048u; i += 64u) T[i] = c.cost_tbl[i];
 	for (uint32_t i = lane; i < stride; i += 64u) probs[i] = MGL_PROB_INIT;
@@ -103,7 +103,7 @@ __device__ __forceinline__ void adp_snap_walk(const DevCtx& c, const mgl_pk* in,
 __global__ void __launch_bounds__(64) k_adp_snap(DevCtx c, const mgl_pk* in, mgl_pk* out, int resolve, uint32_t chunk,
                                                  uint32_t* entry, uint16_t* snaps, uint64_t* cost_out)
 {
-	adp_snap_walk(c, in, out, resolve, chunk, entry, snaps, cost_out);
+	adp_snap_walk(c, c.L, in, out, resolve, chunk, entry, snaps, cost_out);
 }
 
 __global__ void k_fill_literal_sweep(mgl_pk* slabs, size_t count)
@@ -111,16 +111,26 @@ __global__ void k_fill_literal_sweep(mgl_pk* slabs, size_t count)
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) slabs[i] = MGL_PK_LITERAL;
 }
 
-/* The sweep (mgl_sa_seed_sweep): one wavefront per variant, each walking its own parse.  Variant v reads slab
- * in_idx[v] of `in` (in_idx == nullptr: slab v; pass 0's starts are shared by the variants of one `cand`) and writes
- * slab v of `out`, its own nch chunk starts and cost[v]. */
-__global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const mgl_pk* in, const uint32_t* in_idx, mgl_pk* out, int resolve,
-                                                       uint32_t chunk, uint32_t nch, uint32_t* entry, uint16_t* snaps, uint64_t* cost)
+/* A variant of the sweeps: its settings, its lc/lp/pb and where its nch snapshots start in `snaps` (in u16; the strides
+ * differ from variant to variant, so the offsets are a prefix sum made on the host). */
+struct AdpVariant { uint32_t cand, segment, ahead, props; uint64_t snap_off; };
+__host__ __device__ static inline uint32_t adp_pack_props(uint32_t lc, uint32_t lp, uint32_t pb) { return lc | (lp << 8) | (pb << 16); }
+__device__ __forceinline__ mgl_layout adp_variant_layout(const AdpVariant& t)
+{
+	return mgl_make_layout(t.props & 0xFFu, (t.props >> 8) & 0xFFu, (t.props >> 16) & 0xFFu);
+}
+
+/* The sweep (mgl_sa_seed_sweep, mgl_parse_sweep_props): one wavefront per variant, each walking its own parse under its
+ * own layout.  Variant v reads slab in_idx[v] of `in` (in_idx == nullptr: slab v; pass 0's starts are shared by the
+ * variants of one `cand`) and writes slab v of `out`, its own nch chunk starts and cost[v]. */
+__global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const AdpVariant* tab, const mgl_pk* in, const uint32_t* in_idx, mgl_pk* out,
+                                                       int resolve, uint32_t chunk, uint32_t nch, uint32_t* entry, uint16_t* snaps, uint64_t* cost)
 {
 	const uint32_t v = blockIdx.x;
+	const AdpVariant t = tab[v];
 	const size_t n = c.n;
-	adp_snap_walk(c, in + (in_idx ? in_idx[v] : v) * n, out ? out + v * n : nullptr, resolve, chunk, entry + (size_t)v * 5u * nch,
-	              snaps ? snaps + (size_t)v * nch * adp_stride(c.L) : nullptr, cost + v);
+	adp_snap_walk(c, adp_variant_layout(t), in + (in_idx ? in_idx[v] : v) * n, out ? out + v * n : nullptr, resolve, chunk,
+	              entry + (size_t)v * 5u * nch, snaps ? snaps + t.snap_off : nullptr, cost + v);
 }
 
 /* price of events [from, to) of a planned packet under the model M */
@@ -136,7 +146,7 @@ __device__ __forceinline__ uint32_t adp_events(const mgl_plan& pl, const uint16_
 	return s;
 }
 
-extern __shared__ __align__(4) uint16_t adp_model[]; /* the chunk's model: adp_stride(L) u16, sized at launch */
+extern __shared__ __align__(4) uint16_t adp_model[]; /* the chunk's model: adp_stride(L) u16, sized at launch (a sweep: its largest) */
 
 /* One workgroup (one wavefront) per chunk [s, e).  The node loop is k_opt_dp's (same sources per lane, tie order,
  * SHORT_REP before LITERAL, states carried along winning edges, same LDS ring and the bounds stated there), run over the
@@ -147,7 +157,7 @@ extern __shared__ __align__(4) uint16_t adp_model[]; /* the chunk's model: adp_s
  *
  * back[] and out[] are read and written by lane 0 alone (what the other lanes need of an entry is broadcast). */
 template <bool MF>
-__device__ __forceinline__ void adp_dp_chunk(const DevCtx& c, const uint32_t m, const uint32_t* entry, const uint16_t* snaps, uint32_t chunk,
+__device__ __forceinline__ void adp_dp_chunk(const DevCtx& c, const mgl_layout L, const uint32_t m, const uint32_t* entry, const uint16_t* snaps, uint32_t chunk,
                                              uint32_t cand, uint32_t segment, uint32_t ahead, mgl_pk* back, mgl_pk* out,
                                              unsigned long long* objective, const MfLists& mf)
 {
@@ -165,8 +175,7 @@ __device__ __forceinline__ void adp_dp_chunk(const DevCtx& c, const uint32_t m, 
 	const uint32_t lane = threadIdx.x;
 	const uint32_t s = m * chunk;
 	const uint32_t e = (s + chunk) < c.n ? (s + chunk) : c.n;
-	const uint32_t nps = 1u << c.L.pb;
-	const mgl_layout L = c.L;
+	const uint32_t nps = 1u << L.pb;
 	const uint8_t* d = c.data;
 	const uint32_t stride = adp_stride(L);
 
@@ -393,12 +402,11 @@ __global__ void __launch_bounds__(64) k_adp_dp(DevCtx c, const uint32_t* entry, 
                                                uint32_t segment, uint32_t ahead, mgl_pk* back, mgl_pk* out, unsigned long long* objective,
                                                MfLists mf)
 {
-	adp_dp_chunk<MF>(c, blockIdx.x, entry, snaps, chunk, cand, segment, ahead, back, out, objective, mf);
+	adp_dp_chunk<MF>(c, c.L, blockIdx.x, entry, snaps, chunk, cand, segment, ahead, back, out, objective, mf);
 }
 
 /* The sweep: workgroup (m, y) runs chunk m of variant v = list[y], one of the variants of this instance's finder, with
- * that variant's settings from `tab` and on its slice of entry, snaps, back, out and objective. */
-struct AdpVariant { uint32_t cand, segment, ahead, pad; };
+ * that variant's settings and layout from `tab` and on its slice of entry, snaps, back, out and objective. */
 template <bool MF>
 __global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant* tab, const uint32_t* list, uint32_t nch, const uint32_t* entry,
                                                      const uint16_t* snaps, uint32_t chunk, mgl_pk* back, mgl_pk* out,
@@ -407,6 +415,6 @@ __global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant*
 	const uint32_t v = list[blockIdx.y];
 	const AdpVariant t = tab[v];
 	const size_t n = c.n;
-	adp_dp_chunk<MF>(c, blockIdx.x, entry + (size_t)v * 5u * nch, snaps + (size_t)v * nch * adp_stride(c.L), chunk, t.cand, t.segment, t.ahead,
+	adp_dp_chunk<MF>(c, adp_variant_layout(t), blockIdx.x, entry + (size_t)v * 5u * nch, snaps + t.snap_off, chunk, t.cand, t.segment, t.ahead,
 	                 back + v * (n + 1u), out + v * n, objective + v, mf);
 }

@@ -1630,7 +1630,8 @@ extern "C" int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, 
 	return MGL_OK;
 }
 
-/* ---- the sweep: several variants of the adaptive parse through one launch per stage, the cheapest parse kept */
+/* ---- the sweeps: several variants of the adaptive parse through one launch per stage.  mgl_sa_seed_sweep keeps the cheapest
+ * parse as the current slab; mgl_parse_sweep_props gives every variant a triple of its own and hands the cheapest parse out */
 struct SweepBufs {
 	uint16_t* snaps = nullptr;
 	uint32_t *entry = nullptr, *lists = nullptr, *start_idx = nullptr;
@@ -1652,30 +1653,36 @@ struct SweepBufs {
 	do {                                                                                                 \
 		if (hipMalloc(&(ptr), (bytes)) != hipSuccess) {                                                  \
 			(void)hipGetLastError();                                                                     \
-			return fail(MGL_ENOMEM, "mgl_sa_seed_sweep: the per-variant buffers do not fit the device"); \
+			return fail(MGL_ENOMEM, "parse sweep: the per-variant buffers do not fit the device"); \
 		}                                                                                                \
 	} while (0)
 
-extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, size_t nvariants,
-                                 mgl_optimal_stats* results, uint32_t* best_variant, double* gpu_ms)
+/* props == nullptr: every variant under the handle's triple, and the winner becomes the current slab (mgl_sa_seed_sweep).
+ * Otherwise variant v under props[v]; nothing of the search state is touched and the winner goes to packets_out. */
+static int sweep_run(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, const mgl_properties* props,
+                     size_t nvariants, mgl_optimal_stats* results, uint32_t* best_variant, mgl_packet* packets_out, double* gpu_ms)
 {
-	if (!sa || !variants) return fail(MGL_EINVAL, "null argument");
-	if (nvariants == 0 || nvariants > MGL_SWEEP_MAX) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: 1 to 64 variants");
+	if (nvariants == 0 || nvariants > MGL_SWEEP_MAX) return fail(MGL_EINVAL, "parse sweep: 1 to 64 variants");
 	const uint32_t passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
 	uint32_t chunk = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
 	const uint32_t depth = cfg && cfg->depth ? cfg->depth : sa->mf_depth;
 	const bool from_current = cfg && cfg->from_current;
-	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: at most 16 passes");
-	if (depth > MGL_MF_MAX_DEPTH) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: depth must be at most 4096");
+	if (props && from_current) return fail(MGL_EINVAL, "mgl_parse_sweep_props: a current slab has a cost under one triple only; from_current must be 0");
+	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "parse sweep: at most 16 passes");
+	if (depth > MGL_MF_MAX_DEPTH) return fail(MGL_EINVAL, "parse sweep: depth must be at most 4096");
 	const uint32_t nv = (uint32_t)nvariants, n = (uint32_t)sa->n;
 	/* per variant: its settings after the defaults and clamps of mgl_sa_seed_adaptive; the greedy parse of its cand */
 	AdpVariant tab[MGL_SWEEP_MAX];
 	uint32_t lists[MGL_SWEEP_MAX], start_idx[MGL_SWEEP_MAX], cands[MGL_SWEEP_MAX], ncand = 0, nnear = 0;
 	for (uint32_t v = 0; v < nv; v++) {
-		if (variants[v].finder != MGL_MF_NEAREST && variants[v].finder != MGL_MF_FRONTIER) return fail(MGL_EINVAL, "mgl_sa_seed_sweep: unknown finder");
+		if (variants[v].finder != MGL_MF_NEAREST && variants[v].finder != MGL_MF_FRONTIER) return fail(MGL_EINVAL, "parse sweep: unknown finder");
+		if (props && ((uint32_t)props[v].lc + props[v].lp > 4u || props[v].pb > 4u))
+			return fail(MGL_EINVAL, "mgl_parse_sweep_props: supported properties are lc + lp <= 4, pb <= 4");
 		uint32_t ch = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
 		tab[v].cand = variants[v].cand ? variants[v].cand : MGL_OPT_DEF_CAND;
-		tab[v].segment = variants[v].segment; tab[v].ahead = variants[v].ahead; tab[v].pad = 0;
+		tab[v].segment = variants[v].segment; tab[v].ahead = variants[v].ahead;
+		tab[v].props = props ? adp_pack_props(props[v].lc, props[v].lp, props[v].pb) : adp_pack_props(sa->ctx.L.lc, sa->ctx.L.lp, sa->ctx.L.pb);
+		tab[v].snap_off = 0;
 		int rc = adp_args(sa, tab[v].cand, ch, tab[v].segment, tab[v].ahead, false);
 		if (rc) return rc;
 		chunk = ch; /* the same for every variant */
@@ -1690,9 +1697,19 @@ extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, 
 		if (variants[v].finder == MGL_MF_FRONTIER) lists[k++] = v;
 	HIPCHK(hipSetDevice(sa->device));
 	if (nfront) { int rc = mf_ensure(sa, depth); if (rc) return rc; }
-	const size_t nch = ((size_t)n + chunk - 1) / chunk, stride = adp_stride(sa->ctx.L);
+	/* a variant's snapshots: nch models of its own layout; a launch's dynamic LDS: the largest model among its variants */
+	const size_t nch = ((size_t)n + chunk - 1) / chunk;
+	size_t snap_total = 0;
+	uint32_t lds_near = 0, lds_front = 0;
+	for (uint32_t v = 0; v < nv; v++) {
+		const uint32_t stride = adp_stride(mgl_make_layout(tab[v].props & 0xFFu, (tab[v].props >> 8) & 0xFFu, (tab[v].props >> 16) & 0xFFu));
+		tab[v].snap_off = snap_total;
+		snap_total += nch * stride;
+		uint32_t& lds = variants[v].finder == MGL_MF_FRONTIER ? lds_front : lds_near;
+		if (stride * (uint32_t)sizeof(uint16_t) > lds) lds = stride * (uint32_t)sizeof(uint16_t);
+	}
 	SweepBufs o;
-	SWEEP_ALLOC(o.snaps, sizeof(uint16_t) * stride * nch * nv);
+	SWEEP_ALLOC(o.snaps, sizeof(uint16_t) * snap_total);
 	SWEEP_ALLOC(o.entry, sizeof(uint32_t) * 5 * nch * nv);
 	SWEEP_ALLOC(o.back, sizeof(mgl_pk) * ((size_t)n + 1) * nv);
 	SWEEP_ALLOC(o.dp, sizeof(mgl_pk) * (size_t)n * nv);
@@ -1705,9 +1722,8 @@ extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, 
 	SWEEP_ALLOC(o.lists, sizeof(uint32_t) * nv);
 	SWEEP_ALLOC(o.start_idx, sizeof(uint32_t) * nv);
 	for (hipEvent_t* e : { &o.t0, &o.t1, &o.call0, &o.call1, &o.fork, &o.join }) HIPCHK(hipEventCreate(e));
-	const uint32_t lds = (uint32_t)stride * (uint32_t)sizeof(uint16_t);
-	if (nnear) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	if (nfront) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	if (nnear) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_near));
+	if (nfront) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_front));
 	HIPCHK(hipEventRecord(o.call0, sa->stream));
 	HIPCHK(hipMemcpyAsync(o.tab, tab, sizeof(AdpVariant) * nv, hipMemcpyHostToDevice, sa->stream));
 	HIPCHK(hipMemcpyAsync(o.lists, lists, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
@@ -1719,8 +1735,8 @@ extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, 
 			hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.starts + (size_t)k * n, cands[k]);
 		first = o.starts;
 	}
-	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, first, (const uint32_t*)o.start_idx, (mgl_pk*)nullptr, 0, chunk,
-	                   (uint32_t)nch, o.entry, o.snaps, o.cost);
+	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)o.tab, first, (const uint32_t*)o.start_idx,
+	                   (mgl_pk*)nullptr, 0, chunk, (uint32_t)nch, o.entry, o.snaps, o.cost);
 	HIPCHK(hipGetLastError());
 	std::vector<mgl_optimal_stats> st(nv);
 	memset(st.data(), 0, sizeof(mgl_optimal_stats) * nv);
@@ -1747,18 +1763,18 @@ extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, 
 			/* the two instances side by side: the frontier's on the handle's second stream */
 			HIPCHK(hipEventRecord(o.fork, sa->stream));
 			HIPCHK(hipStreamWaitEvent(sa->stream2, o.fork, 0));
-			hipLaunchKernelGGL(k_adp_dp_sweep<true>, dim3((uint32_t)nch, nfront), dim3(64), lds, sa->stream2, sa->ctx, (const AdpVariant*)o.tab,
+			hipLaunchKernelGGL(k_adp_dp_sweep<true>, dim3((uint32_t)nch, nfront), dim3(64), lds_front, sa->stream2, sa->ctx, (const AdpVariant*)o.tab,
 			                   (const uint32_t*)o.lists + nnear, (uint32_t)nch, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, o.back, o.dp, o.obj,
 			                   mf_lists(sa));
 			HIPCHK(hipEventRecord(o.join, sa->stream2));
 		}
 		if (nnear)
-			hipLaunchKernelGGL(k_adp_dp_sweep<false>, dim3((uint32_t)nch, nnear), dim3(64), lds, sa->stream, sa->ctx, (const AdpVariant*)o.tab,
+			hipLaunchKernelGGL(k_adp_dp_sweep<false>, dim3((uint32_t)nch, nnear), dim3(64), lds_near, sa->stream, sa->ctx, (const AdpVariant*)o.tab,
 			                   (const uint32_t*)o.lists, (uint32_t)nch, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, o.back, o.dp, o.obj,
 			                   MfLists{});
 		if (nfront) HIPCHK(hipStreamWaitEvent(sa->stream, o.join, 0));
-		hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const mgl_pk*)o.dp, (const uint32_t*)nullptr, o.res, 1, chunk,
-		                   (uint32_t)nch, o.entry, p + 1 < passes ? o.snaps : (uint16_t*)nullptr, o.cost);
+		hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)o.tab, (const mgl_pk*)o.dp,
+		                   (const uint32_t*)nullptr, o.res, 1, chunk, (uint32_t)nch, o.entry, p + 1 < passes ? o.snaps : (uint16_t*)nullptr, o.cost);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipMemcpyAsync(h_obj, o.obj, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, sa->stream));
 		HIPCHK(hipMemcpyAsync(h_cost, o.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->stream));
@@ -1775,7 +1791,10 @@ extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, 
 		if (keep_v != UINT32_MAX)
 			HIPCHK(hipMemcpyAsync(o.keep, o.res + (size_t)keep_v * n, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
 	}
-	if (best_v != UINT32_MAX) {
+	if (props) {
+		/* the handle cannot cost a slab under a foreign triple: the winner is handed out, not made current */
+		if (packets_out) { int rc = export_slab(sa, o.keep, packets_out); if (rc) return rc; }
+	} else if (best_v != UINT32_MAX) {
 		/* the cheapest parse becomes the current slab, as in mgl_sa_seed_adaptive */
 		Control c;
 		int rc;
@@ -1798,6 +1817,20 @@ extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, 
 	if (best_variant) *best_variant = best_v;
 	if (gpu_ms) *gpu_ms = call_ms;
 	return MGL_OK;
+}
+
+extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, size_t nvariants,
+                                 mgl_optimal_stats* results, uint32_t* best_variant, double* gpu_ms)
+{
+	if (!sa || !variants) return fail(MGL_EINVAL, "null argument");
+	return sweep_run(sa, cfg, variants, nullptr, nvariants, results, best_variant, nullptr, gpu_ms);
+}
+
+extern "C" int mgl_parse_sweep_props(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, const mgl_properties* props,
+                                     size_t nvariants, mgl_optimal_stats* results, uint32_t* best_variant, mgl_packet* packets_out, double* gpu_ms)
+{
+	if (!sa || !variants || !props) return fail(MGL_EINVAL, "null argument");
+	return sweep_run(sa, cfg, variants, props, nvariants, results, best_variant, packets_out, gpu_ms);
 }
 
 static hipEvent_t pool_event(mgl_sa* sa, size_t i)

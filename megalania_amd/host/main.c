@@ -26,7 +26,7 @@ static void usage(const char* argv0)
 {
 	fprintf(stderr,
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
-	        "          [--lc N --lp N --pb N | --props auto [--props-rounds R] [--props-table]] [--device D] [--max-scan M]\n"
+	        "          [--lc N --lp N --pb N | --props auto [--props-rounds R] [--props-table] [--props-joint T]] [--device D] [--max-scan M]\n"
 	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P | --adaptive-seed P]\n"
 	        "          [--match-finder nearest|frontier [--mf-depth N]] [--parse-sweep [--parse-sweep-table]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
@@ -58,6 +58,11 @@ static void usage(const char* argv0)
 	        "               for this only) is costed under all 75 supported triples at once and the search runs under the\n"
 	        "               cheapest; a seed that depends on the triple is made again under it, up to R sweeps (default 3).\n"
 	        "               Not with --lc/--lp/--pb or --chains above 1.  --props-table prints the last sweep's 75 costs\n"
+	        "  --props-joint T  with --props auto --adaptive-seed P --parse-sweep: instead of the rounds, the parse sweep is made at\n"
+	        "               0/0/0, its winner is costed under all 75 triples, and one more batch makes the 16 settings under each of\n"
+	        "               the T cheapest other triples (1..4) on the same handle; the cheapest (triple, parse) of both stages wins.\n"
+	        "               At most two handles are created.  Not with --seed-stream, --load-slab, --greedy-seed, --lc/--lp/--pb or\n"
+	        "               --chains above 1\n"
 	        "  --temperature B  Metropolis accept rule instead of the reference's: B = e-folding slack in output\n"
 	        "               bytes at the start of an epoch, cooled linearly to 0 (e.g. 2; 0 = reference rule)\n"
 	        "  --chains N --rank R --comm-file PATH  one of N independent chains, one process per GPU (device = R unless\n"
@@ -192,6 +197,101 @@ fail:
 	return NULL;
 }
 
+/* --props-joint T.  `sa` is an untouched handle at *props = 0/0/0.  Stage A: the grid at 0/0/0
+ * (parse W_A, cost c_A).  W_A is costed under all 75 triples; t* is the cheapest, the candidates C the T cheapest other than
+ * 0/0/0.  Stage B: one batch of 16 x T variants, grid entry g under C[k] at 16 k + g (parse W_B at cost c_B under C[k_B]).
+ * The cheapest of (0/0/0, W_A, c_A), (t*, W_A, table[t*]), (C[k_B], W_B, c_B) wins, ties in this order; `kept` receives
+ * its parse and *props its triple.  Returns a handle at that triple on which the parse costs what the pair said. */
+#define JOINT_MAX 4
+static void print_sweep_rows(mgl_properties pr, const mgl_optimal_stats* res, uint32_t star)
+{
+	for (uint32_t g = 0; g < SWEEP_GRID; g++) {
+		fprintf(stderr, "parse-sweep-table: lc=%u lp=%u pb=%u %s cand %u segment %u ahead %u:", pr.lc, pr.lp, pr.pb,
+		        sweep_grid[g].finder == MGL_MF_FRONTIER ? "frontier" : "nearest", sweep_grid[g].cand, sweep_grid[g].segment, sweep_grid[g].ahead);
+		for (uint32_t p = 0; p < res[g].passes; p++) fprintf(stderr, " %.1f", 18 + res[g].cost[p] / 16384.0);
+		fprintf(stderr, " B%s\n", g == star ? " *" : "");
+	}
+}
+static mgl_sa* choose_props_joint(mgl_sa* sa, const uint8_t* data, size_t n, const mgl_sa_config* cfg, mgl_properties* props, seed_spec seed,
+                                  unsigned T, bool print_table, mgl_packet* kept)
+{
+	static mgl_optimal_stats res_a[SWEEP_GRID], res_b[SWEEP_GRID * JOINT_MAX];
+	mgl_parse_variant var_b[SWEEP_GRID * JOINT_MAX];
+	mgl_properties pr_a[SWEEP_GRID], pr_b[SWEEP_GRID * JOINT_MAX], cand[JOINT_MAX];
+	mgl_props_cost tab[MGL_PROPS_TRIPLES];
+	const mgl_parse_sweep_config sc = { seed.passes, 0, seed.mf_depth, 0 };
+	const mgl_properties s0 = *props;
+	mgl_packet* w_b = (mgl_packet*)malloc(sizeof(mgl_packet) * n);
+	uint32_t best_a = 0, best_b = 0;
+	double ms_a = 0, ms_b = 0;
+	size_t count = 0;
+	if (!w_b) { fprintf(stderr, "Error: out of memory\n"); return NULL; }
+	for (uint32_t g = 0; g < SWEEP_GRID; g++) pr_a[g] = s0;
+	if (mgl_parse_sweep_props(sa, &sc, sweep_grid, pr_a, SWEEP_GRID, res_a, &best_a, kept, &ms_a) != MGL_OK) goto fail;
+	if (best_a >= SWEEP_GRID) { mgl_sa_destroy(sa); free(w_b); fprintf(stderr, "Error: the parse sweep named no variant\n"); return NULL; }
+	const uint64_t c_a = res_a[best_a].cost[res_a[best_a].best_pass];
+	if (mgl_props_sweep(sa, kept, tab, MGL_PROPS_TRIPLES, &count, NULL) != MGL_OK) goto fail;
+	size_t t_star = 0; /* the cheapest, ties to the first in canonical order */
+	for (size_t t = 1; t < MGL_PROPS_TRIPLES; t++)
+		if (tab[t].cost < tab[t_star].cost) t_star = t;
+	/* the T cheapest triples other than the start, by cost, ties in canonical order */
+	bool taken[MGL_PROPS_TRIPLES] = { false };
+	for (unsigned k = 0; k < T; k++) {
+		size_t arg = MGL_PROPS_TRIPLES;
+		for (size_t t = 0; t < MGL_PROPS_TRIPLES; t++)
+			if (!taken[t] && !same_props(tab[t].props, s0) && (arg == MGL_PROPS_TRIPLES || tab[t].cost < tab[arg].cost)) arg = t;
+		taken[arg] = true;
+		cand[k] = tab[arg].props;
+		for (uint32_t g = 0; g < SWEEP_GRID; g++) { var_b[SWEEP_GRID * k + g] = sweep_grid[g]; pr_b[SWEEP_GRID * k + g] = cand[k]; }
+	}
+	if (mgl_parse_sweep_props(sa, &sc, var_b, pr_b, (size_t)SWEEP_GRID * T, res_b, &best_b, w_b, &ms_b) != MGL_OK) goto fail;
+	if (best_b >= SWEEP_GRID * T) { mgl_sa_destroy(sa); free(w_b); fprintf(stderr, "Error: the parse sweep named no variant\n"); return NULL; }
+	const uint64_t c_b = res_b[best_b].cost[res_b[best_b].best_pass];
+	/* the decision */
+	const char* stage = "A";
+	mgl_properties win = s0;
+	uint64_t cost = c_a;
+	uint32_t variant = best_a, pass = res_a[best_a].best_pass;
+	if (tab[t_star].cost < cost) { stage = "A-recosted"; win = tab[t_star].props; cost = tab[t_star].cost; }
+	if (c_b < cost) {
+		stage = "B"; win = pr_b[best_b]; cost = c_b; variant = best_b % SWEEP_GRID; pass = res_b[best_b].best_pass;
+		memcpy(kept, w_b, sizeof(mgl_packet) * n);
+	}
+	free(w_b);
+	w_b = NULL;
+	if (!same_props(win, s0)) {
+		mgl_sa_destroy(sa);
+		*props = win;
+		if ((sa = mgl_sa_create(data, n, *props, cfg)) == NULL) goto fail;
+	}
+	uint64_t check = 0;
+	if (mgl_sa_set_slab(sa, kept) != MGL_OK || mgl_sa_current(sa, NULL, &check) != MGL_OK) goto fail;
+	if (check != cost) {
+		fprintf(stderr, "Error: the joint choice's parse costs %llu on a handle at its triple, not %llu\n", (unsigned long long)check, (unsigned long long)cost);
+		mgl_sa_destroy(sa);
+		return NULL;
+	}
+	fprintf(stderr, "props: lc=%u lp=%u pb=%u, sweep %llu B, at 0/0/0 %llu B, joint with %u candidates in %.1f + %.1f ms\n", win.lc, win.lp, win.pb,
+	        (unsigned long long)((cost + 16383) / 16384), (unsigned long long)((c_a + 16383) / 16384), T, ms_a, ms_b);
+	fprintf(stderr, "props joint: lc=%u lp=%u pb=%u stage %s variant %u pass %u cost %llu; stage A cost %llu; candidates", win.lc, win.lp, win.pb, stage,
+	        variant, pass, (unsigned long long)cost, (unsigned long long)c_a);
+	for (unsigned k = 0; k < T; k++) fprintf(stderr, " %u/%u/%u", cand[k].lc, cand[k].lp, cand[k].pb);
+	fprintf(stderr, "\n");
+	if (seed.sweep_table) {
+		print_sweep_rows(s0, res_a, !strcmp(stage, "B") ? SWEEP_GRID : best_a);
+		for (unsigned k = 0; k < T; k++) print_sweep_rows(cand[k], res_b + SWEEP_GRID * k, !strcmp(stage, "B") && best_b / SWEEP_GRID == k ? variant : SWEEP_GRID);
+	}
+	if (print_table)
+		for (size_t t = 0; t < MGL_PROPS_TRIPLES; t++)
+			fprintf(stderr, "props-table: lc=%u lp=%u pb=%u cost %llu (%llu B)\n", tab[t].props.lc, tab[t].props.lp, tab[t].props.pb,
+			        (unsigned long long)tab[t].cost, (unsigned long long)((tab[t].cost + 16383) / 16384));
+	return sa;
+fail:
+	free(w_b);
+	fprintf(stderr, "Error: %s\n", mgl_last_error());
+	return NULL;
+}
+
 int main(int argc, char** argv)
 {
 	mgl_sa_config cfg;
@@ -206,7 +306,7 @@ int main(int argc, char** argv)
 	const char *out_path = NULL, *save_path = NULL, *load_path = NULL, *seed_stream_path = NULL;
 	int clip_window = 0, props_given = 0;
 	bool props_auto = false, props_table = false;
-	unsigned props_rounds = 3;
+	unsigned props_rounds = 3, props_joint = 0;
 	uint32_t greedy = 0, optimal = 0, adaptive = 0, mf_depth = 0;
 	int finder = MGL_MF_NEAREST;
 	bool finder_given = false, parse_sweep = false, parse_sweep_table = false;
@@ -239,6 +339,7 @@ int main(int argc, char** argv)
 			props_auto = true;
 		}
 		else if (!strcmp(a, "--props-rounds")) { props_rounds = (unsigned)strtoul(v, NULL, 0); if (!props_rounds) { usage(argv[0]); return -1; } }
+		else if (!strcmp(a, "--props-joint")) { props_joint = (unsigned)strtoul(v, NULL, 0); if (!props_joint || props_joint > JOINT_MAX) { usage(argv[0]); return -1; } }
 		else if (!strcmp(a, "--device")) { cfg.device = (int32_t)strtol(v, NULL, 0); device_given = 1; }
 		else if (!strcmp(a, "--chains")) chains = (int)strtol(v, NULL, 0);
 		else if (!strcmp(a, "--rank")) rank = (int)strtol(v, NULL, 0);
@@ -309,6 +410,11 @@ int main(int argc, char** argv)
 		return -1;
 	}
 	if (props_table && !props_auto) { usage(argv[0]); return -1; }
+	if (props_joint && !(props_auto && adaptive && parse_sweep)) {
+		fprintf(stderr, "Error: --props-joint needs --props auto --adaptive-seed P --parse-sweep\n");
+		usage(argv[0]);
+		return -1;
+	}
 	if (chains < 1 || rank < 0 || rank >= chains || (chains > 1 && !comm_path)) { usage(argv[0]); return -1; }
 	if (chains > 1) {
 		if (!device_given) cfg.device = rank;
@@ -378,7 +484,9 @@ int main(int argc, char** argv)
 			fixed = false;
 			if ((optimal_slab = (mgl_packet*)malloc(sizeof(mgl_packet) * file_size)) == NULL) { fprintf(stderr, "Error: out of memory\n"); return -1; }
 		}
-		if ((sa = choose_props(sa, file_data, file_size, &cfg, &props, parse, fixed, seed, props_rounds, props_table, optimal_slab)) == NULL) return -1;
+		if (props_joint) sa = choose_props_joint(sa, file_data, file_size, &cfg, &props, seed, props_joint, props_table, optimal_slab);
+		else sa = choose_props(sa, file_data, file_size, &cfg, &props, parse, fixed, seed, props_rounds, props_table, optimal_slab);
+		if (sa == NULL) return -1;
 		free(parse);
 		if (!seed.passes) { free(optimal_slab); optimal_slab = NULL; } /* no seed option: the search starts from the all-literal slab */
 	}
