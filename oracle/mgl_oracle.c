@@ -977,6 +977,11 @@ static window_info window_end(const orc_ctx* c, const orc_packet* slab, const jo
 	if (wi.soft_end == (size_t)-1 || wi.soft_end > wi.end) wi.soft_end = wi.end;
 	return wi;
 }
+/* why the last orc_neighbour_ex returned -1 (process-wide, like the bulk counters): a set of ORC_DROP_* bits, 0 when it did not.  The
+ * journal and repair-pick rules are tested together, the walk-length and event-list rules only on a neighbour that passed both
+ * (its window is not walked otherwise). */
+static unsigned g_last_drop_reason;
+unsigned orc_last_drop_reason(void) { return g_last_drop_reason; }
 /* status: 1 = ok, 0 = no candidate at the target (main.c:81-84 retries those), -1 = dropped because
  * its journal needs more than ORC_MAX_JOURNAL distinct positions (the device's journal capacity) */
 int orc_neighbour_ex(orc_ctx* c, orc_packet* slab, uint64_t seed, uint64_t step, uint32_t j,
@@ -1017,6 +1022,7 @@ int orc_neighbour_ex(orc_ctx* c, orc_packet* slab, uint64_t seed, uint64_t step,
 	}
 	free(on);
 	uint64_t total = 0;
+	unsigned reason = 0;
 	int ok = generate_at(&g, slab, target, 0, 0, &jn, &total, probs);
 	/* the device journal holds ORC_MAX_JOURNAL distinct positions; a neighbour that needs
 	 * more is dropped as a failed generate */
@@ -1027,8 +1033,8 @@ int orc_neighbour_ex(orc_ctx* c, orc_packet* slab, uint64_t seed, uint64_t step,
 			for (size_t q = 0; q < i && !seen; q++) seen = jn.d[q].position == jn.d[i].position;
 			distinct += !seen;
 		}
-		if (distinct > ORC_MAX_JOURNAL) ok = -1;
-		if (g.repair_picks > ORC_MAX_REPAIR_PICKS) ok = -1; /* the device gives such a neighbour up */
+		if (distinct > ORC_MAX_JOURNAL) { ok = -1; reason |= ORC_DROP_JOURNAL; }
+		if (g.repair_picks > ORC_MAX_REPAIR_PICKS) { ok = -1; reason |= ORC_DROP_REPAIR_PICKS; } /* the device gives such a neighbour up */
 	}
 	uint32_t wv[4] = { (uint32_t)target, 0xFFFFFFFFu, 0xFFFFFFFFu, 0 };
 	if (ok == 1) {
@@ -1037,8 +1043,11 @@ int orc_neighbour_ex(orc_ctx* c, orc_packet* slab, uint64_t seed, uint64_t step,
 		/* the device keeps at most ORC_MAX_EVENTS inserted and as many removed events per neighbour (its second
 		 * pass's lists) and visits at most ORC_MAX_WALK of its packets: a neighbour that changes more of the coding than
 		 * that, or whose walk stays apart from the base's for longer, is dropped, like one with too long a journal */
-		if (wi.n_ins > ORC_MAX_EVENTS || wi.n_rem > ORC_MAX_EVENTS || wi.walked > ORC_MAX_WALK) { ok = -1; wv[1] = wv[2] = 0xFFFFFFFFu; wv[3] = 0; }
+		if (wi.walked > ORC_MAX_WALK) reason |= ORC_DROP_WALK;
+		if (wi.n_ins > ORC_MAX_EVENTS || wi.n_rem > ORC_MAX_EVENTS) reason |= ORC_DROP_EVENTS;
+		if (reason) { ok = -1; wv[1] = wv[2] = 0xFFFFFFFFu; wv[3] = 0; }
 	}
+	g_last_drop_reason = reason;
 	if (cost) *cost = ok == 1 ? total : ~0ull;
 	if (window) memcpy(window, wv, sizeof wv);
 	/* compact the journal: first old value per position + final value, drop no-ops */

@@ -88,6 +88,10 @@ int orc_neighbour(orc_ctx* c, orc_packet* slab, uint64_t seed, uint64_t step, ui
  * inside the window reads a rep distance from before the window */
 int orc_neighbour_ex(orc_ctx* c, orc_packet* slab, uint64_t seed, uint64_t step, uint32_t j,
                      int keep, uint64_t* cost, orc_diff* diffs, size_t* ndiffs, size_t cap, uint32_t* window);
+/* why the last orc_neighbour_ex returned -1 (0 when it did not): the device's capacities it ran over.  Journal and repair
+ * picks are tested together; the walk length and the event lists only on a neighbour that passed both. */
+enum { ORC_DROP_JOURNAL = 1, ORC_DROP_REPAIR_PICKS = 2, ORC_DROP_WALK = 4, ORC_DROP_EVENTS = 8 };
+unsigned orc_last_drop_reason(void);
 /* Run batched steps [step_begin, step_end) of K neighbours; mirrors mgl_sa_run.  iter0 = evaluations
  * already made in this epoch (the reference's i); modes (nullable = all 0): per step 0 = take the
  * best acceptable neighbour, 1 = take every acceptable neighbour that is the best of its window.

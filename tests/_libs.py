@@ -19,6 +19,8 @@ DIFF = np.dtype([("position", "u4"), ("old", PACKET), ("new", PACKET)], align=Tr
 assert DIFF.itemsize == 28
 
 LITERAL, MATCH, SHORT_REP, LONG_REP = 1, 2, 3, 4
+# orc_last_drop_reason: the journal's 64 positions, the 8 repair picks, the 2 048 walked packets, the 4 096-event lists
+DROP_JOURNAL, DROP_REPAIR_PICKS, DROP_WALK, DROP_EVENTS = 1, 2, 4, 8
 
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
@@ -167,6 +169,8 @@ class Oracle:
             L.orc_neighbour_ex.restype = C.c_int
             L.orc_neighbour_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.orc_last_drop_reason.restype = C.c_uint
+            L.orc_last_drop_reason.argtypes = []
             L.orc_set_max_bucket_scan.argtypes = [C.c_void_p, C.c_uint32]
             L.orc_set_top_k.argtypes = [C.c_void_p, C.c_uint32]
             L.orc_set_strata.argtypes = [C.c_void_p, C.c_uint32]
@@ -267,16 +271,18 @@ class Oracle:
         assert nd.value <= cap
         return bool(ok), cost.value, diffs[: nd.value].copy()
 
-    def neighbour_ex(self, slab, seed, step, j, keep=False, cap=4096, K=None):
+    def neighbour_ex(self, slab, seed, step, j, keep=False, cap=4096, K=None, reason=False):
+        """status (1 ok / 0 no candidate / -1 dropped by a capacity of the device), cost, diffs, (target, end, soft end, dep);
+        reason=True: and the DROP_* bits of the capacities a dropped neighbour ran over (0 unless the status is -1)"""
         self._strata(K)
-        """status (1 ok / 0 no candidate / -1 dropped by the journal capacity), cost, diffs, (target, end, soft end, dep)"""
         cost = C.c_uint64(0)
         nd = C.c_size_t(0)
         diffs = np.zeros(cap, dtype=DIFF)
         win = np.zeros(4, dtype=np.uint32)
         st = self.L.orc_neighbour_ex(self.h, ptr(slab), seed, step, j, int(keep), C.addressof(cost), ptr(diffs),
                                      C.addressof(nd), cap, ptr(win))
-        return st, cost.value, diffs[: min(nd.value, cap)].copy(), tuple(int(x) for x in win)
+        out = (st, cost.value, diffs[: min(nd.value, cap)].copy(), tuple(int(x) for x in win))
+        return out + (int(self.L.orc_last_drop_reason()),) if reason else out
 
     def set_temperature(self, temperature: int):
         self.L.orc_set_temperature(self.h, temperature)

@@ -36,7 +36,8 @@ def check_base(sa, o, slab, data):
     n = len(data)
     tr = o.trace_events(slab)
     total = sa.nprobs
-    ctx = ref_to_product_ctx(tr["ctx"], 0x300)
+    lit = total - 1847  # the literal coder: 0x300 << (lc + lp) probabilities, first in the reference's order, last in the product's
+    ctx = ref_to_product_ctx(tr["ctx"], lit)
     off = sa.debug_dump(0, np.uint32)
     ln = sa.debug_dump(1, np.uint32)
     cap = sa.debug_dump(8, np.uint32)
@@ -45,7 +46,7 @@ def check_base(sa, o, slab, data):
     ev = (tr["bit"].astype(np.uint16) << 15) | tr["prob"]
     fin = o.cost_slab(slab, want_probs=True)["probs"]
     fin_prod = np.empty(total, dtype=np.uint16)
-    fin_prod[ref_to_product_ctx(np.arange(total), 0x300)] = fin
+    fin_prod[ref_to_product_ctx(np.arange(total), lit)] = fin
     assert int(ln.sum()) == len(ctx)
     order = np.argsort(ctx, kind="stable")
     sctx, spos, sev = ctx[order], tr["pos"][order], ev[order]

@@ -433,7 +433,9 @@ def test_match_index_built_on_device(cfg, size):
     # the deeper orders top-K scans by length (mgl_index.hip): positions by their first D bytes, then by position;
     # rank = inverse permutation; run start = first entry with the same D bytes; the byte(s) behind the prefix
     dp = np.concatenate([d, np.zeros(32, dtype=np.uint32)]).astype(np.uint8)
-    for D, sel in ((3, (31, 41, 51, 61)), (5, (33, 43, 53, 63)), (7, (35, 45, 55, 65)), (8, (70, 71, 72, 73)), (16, (74, 75, 76, 77))):
+    # (D = 4 again, through the selectors top-K and the match finder read it by: its rank, run starts and next byte as well)
+    for D, sel in ((3, (31, 41, 51, 61)), (4, (32, 42, 52, 62)), (5, (33, 43, 53, 63)), (6, (34, 44, 54, 64)), (7, (35, 45, 55, 65)),
+                   (8, (70, 71, 72, 73)), (16, (74, 75, 76, 77))):
         cols = np.stack([dp[idx + k] for k in range(D)])           # D x m
         want = np.lexsort(cols[::-1]).astype(np.uint32)            # stable: ties keep position order
         got = sa.debug_dump(sel[0], np.uint32)

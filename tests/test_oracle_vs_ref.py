@@ -4,6 +4,10 @@ trajectories under glibc rand() -- is recorded in tests/golden/oracle_vs_ref.jso
 against that record everywhere.  Where the reference is built, it is checked against the same record too, so a
 record that no longer matches the reference fails here.
 
+The `random_starts` section does the same from seeded random parses with stale entries (tests/_random_parse.py): starts
+that no search of the reference would reach, with matches, long reps and short reps under the packets of the walk, which the
+reference's repair reads when a move uncovers them.
+
 Re-record (where the reference is built): python tests/test_oracle_vs_ref.py REFERENCE_CHECKOUT"""
 import json
 import os
@@ -14,8 +18,9 @@ import numpy as np
 import pytest
 
 from _libs import PACKET, Oracle, Ref, literal_slab, walk
-from conftest import ROOT, rand_bytes, sha, sha_slab, slab_from_rle
+from conftest import ROOT, rand_bytes, sha, sha_slab, slab_from_rle  # (puts the repository on sys.path when run as a script)
 from megalania_amd import corpus
+import _random_parse as rp
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "oracle_vs_ref.json")
 
@@ -57,6 +62,27 @@ CASES = [
     ("one", b"x", 0),
 ]
 TRAJECTORY_DATA = corpus.enwik_like(1500, 0x99)
+
+
+# name: (data, weights, len_mode); each under two generator seeds
+RANDOM_STARTS = {
+    "enwik2k": (lambda: corpus.enwik_like(2000, 0x42), rp.TEXT, "any"),
+    "lorem2k": (lambda: corpus.lorem(2000), rp.TEXT, "any"),
+    "doubled2k": (lambda: rp.doubled_letters(1, 2000), rp.REPS, "any"),
+    "two_periods2k": (lambda: rp.two_periods(3), rp.REPS, "short"),
+}
+RANDOM_CASES = [(name, seed) for name in RANDOM_STARTS for seed in (1, 2)]
+
+
+def _random_start(name, seed):
+    make, weights, len_mode = RANDOM_STARTS[name]
+    data = make()
+    return data, rp.random_parse(data, seed, weights, len_mode)
+
+
+def random_start_record(make_eng, seed_fn, data, start):
+    return dict(walk=walk_record(make_eng(data), data, start),
+                trajectories={str(step): trajectory_record(make_eng(data), seed_fn, start, step) for step in (0, 2)})
 
 
 def _layout(L):
@@ -119,6 +145,20 @@ def test_sa_trajectory(step):
         assert trajectory_record(Ref(TRAJECTORY_DATA), Ref.lib().ref_srand, start, step) == rec
 
 
+@pytest.mark.parametrize("name,seed", RANDOM_CASES, ids=[f"{n}-{s}" for n, s in RANDOM_CASES])
+def test_random_starts(name, seed):
+    """From a random parse with stale matches, long reps and short reps: the walk's figures, and 500 SA iterations in phase 0
+    and in phase 2 (costs, accept decisions, undo-stack counts, final slabs with whatever the moves left off the walk)."""
+    data, start = _random_start(name, seed)
+    rec = _fixture()["random_starts"][f"{name}-{seed}"]
+    assert sha_slab(start) == rec["start"]
+    assert not rp.on_walk(start).all() and (start["type"][~rp.on_walk(start)] != 1).any()
+    want = dict(walk=rec["walk"], trajectories=rec["trajectories"])
+    assert random_start_record(Oracle, Oracle.lib().orc_srand, data, start) == want
+    if Ref.available():
+        assert random_start_record(Ref, Ref.lib().ref_srand, data, start) == want
+
+
 def _record(reference_checkout):
     """Every expected value from the compiled reference; the reference's own perplexity_table.h for the bit-cost
     table that tests/test_host.py pins."""
@@ -132,13 +172,17 @@ def _record(reference_checkout):
     starts = {name: pk_list(_evolve(data, iters, 1234)) for name, data, iters in CASES if iters}
     starts["trajectory"] = pk_list(_evolve(TRAJECTORY_DATA, 200, 42))
     out = dict(made_by="python tests/test_oracle_vs_ref.py: the compiled reference (oracle/_ref/libmegalania_ref.so)",
-               layout=_layout(Ref.lib()), perplexity_table_sha256=sha(table), starts=starts, walks={}, trajectories=[])
+               layout=_layout(Ref.lib()), perplexity_table_sha256=sha(table), starts=starts, walks={}, trajectories=[],
+               random_starts={})
     for name, data, iters in CASES:
         slab = slab_from_rle(len(data), starts[name]) if iters else literal_slab(len(data))
         out["walks"][name] = walk_record(Ref(data), data, slab)
     for step in (0, 1, 2):
         start = slab_from_rle(len(TRAJECTORY_DATA), starts["trajectory"]) if step else literal_slab(len(TRAJECTORY_DATA))
         out["trajectories"].append(trajectory_record(Ref(TRAJECTORY_DATA), Ref.lib().ref_srand, start, step))
+    for name, seed in RANDOM_CASES:
+        data, start = _random_start(name, seed)
+        out["random_starts"][f"{name}-{seed}"] = dict(start=sha_slab(start), **random_start_record(Ref, Ref.lib().ref_srand, data, start))
     return out
 
 
