@@ -116,7 +116,7 @@ typedef struct {
 	                               * by entry with a compare-and-swap; such a step is taken back, so it also counts above) */
 	double gpu_ms_sim;            /* sum over launches of the chain re-simulation kernel k_sim, the path's dominant kernel, each
 	                               * bracketed by HIP events on the stream it runs on (MGL_F_TIMING; split launch form only) */
-	uint64_t sim_launches;        /* the launches summed in gpu_ms_sim */
+	uint64_t sim_launches;        /* the launches summed in gpu_ms_sim: one per slice of a step (the second pass re-simulates in place) */
 	uint64_t sim_bytes_counted;   /* bytes of chain data (positions, events) and change lists k_sim's loads asked for, counted by
 	                               * the kernel itself while mgl_debug_set key 4 is on (its algorithmic bytes; 0 otherwise) */
 } mgl_sa_stats;
@@ -402,7 +402,9 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * (mgl_kernels5.hip): 11 = journal entries of one cluster, 12 = staged events of one cluster, 13 = bitmap / state-record ops
  * of one cluster, 14 = iterations of a cluster's walk, 15 = events of one kind per context, 16 = entries a stretch may shift
  * by in place, 17 = runs on the checkpoint list, 18 = 1 / 0: clusters are split at the members' soft window ends instead of
- * their hard ends (a wrong rule on purpose: the boundary guard of the cluster walks must then send the step to the rebuild). */
+ * their hard ends (a wrong rule on purpose: the boundary guard of the cluster walks must then send the step to the rebuild).
+ * key 7 = 1, 2 or the compiled MGL_BIG_WAVES (anything else: MGL_EINVAL): the wavefronts of a second-pass workgroup, which
+ * share a neighbour's re-simulations; with 1 or 2 a neighbour's contexts take several trips (exercises that path). */
 int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes);
 int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value);
 /* draw n of neighbour j at global step `step` (31-bit, like rand()); j = 0xFFFFFFFF is the

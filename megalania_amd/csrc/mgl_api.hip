@@ -108,6 +108,7 @@ struct mgl_sa {
 	unsigned long long* d_prof; /* 16 u64: per-phase cycles + counts, only with MGL_F_PROFILE */
 	uint32_t* d_todo;       /* [0] = count, [1..K] = neighbour indices for the full-walk fallback */
 	uint32_t per_wave2, waves_per_block2, nbr2_lds, build_lds;
+	uint32_t big_waves = MGL_BIG_WAVES; /* wavefronts of a second-pass workgroup (mgl_debug_set key 7 lowers it for tests) */
 	uint32_t chg_cap = MGL_CHG_CAP; /* events per first-pass list */
 	uint32_t per_wave_pick, per_wave_rest, pick_waves; /* LDS per wavefront of the two halves of the split launch */
 	size_t b2_bytes;
@@ -397,7 +398,7 @@ static int launch_apply(mgl_sa* sa, uint64_t next_gstep = ~0ull)
 /* diagnostic (MGL_TRACE=1): name every launch of the neighbour evaluation on stderr and wait for the device after it, so that a
  * faulting kernel is the last one named */
 /* diagnostic switches of the launch path, read once */
-static const bool g_trace = getenv("MGL_TRACE") != nullptr, g_prof_big = getenv("MGL_PROF_BIG") != nullptr, g_big_inline_sim = getenv("MGL_BIG_INLINE_SIM") != nullptr;
+static const bool g_trace = getenv("MGL_TRACE") != nullptr, g_prof_big = getenv("MGL_PROF_BIG") != nullptr;
 #define NBR_TRACE(name) do { if (g_trace) { fprintf(stderr, "[mgl] %s\n", name); hipError_t e_ = hipDeviceSynchronize(); if (e_ != hipSuccess) fprintf(stderr, "[mgl] %s -> %s\n", name, hipGetErrorString(e_)); } } while (0)
 static hipEvent_t sim_event(mgl_sa* sa, size_t i)
 {
@@ -488,15 +489,15 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 			/* the second half's re-simulation, several wavefronts per neighbour; a neighbour with more touched contexts
 			 * than its list holds goes straight to the last resort's list (the second pass may be running by then) */
 			HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_rest[h], 0));
-			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 6 * (size_t)sa->time_sim_step + 2 * h), sa->stream3));
+			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 4 * (size_t)sa->time_sim_step + 2 * h), sa->stream3));
 			if (sa->count_traffic)
 				hipLaunchKernelGGL(k_sim<true>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, sa->stream3, sa->ctx, sa->b2, sa->base.ctl,
-				                   sa->nbr, sa->big, j0, j1, sa->d_todo3, sa->d_counts + 4, (const uint32_t*)nullptr, (const uint32_t*)nullptr, sa->d_traffic);
+				                   sa->nbr, sa->big, j0, j1, sa->d_todo3, sa->d_counts + 4, sa->d_traffic);
 			else
 				hipLaunchKernelGGL(k_sim<false>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, sa->stream3, sa->ctx, sa->b2, sa->base.ctl,
-				                   sa->nbr, sa->big, j0, j1, sa->d_todo3, sa->d_counts + 4, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (unsigned long long*)nullptr);
+				                   sa->nbr, sa->big, j0, j1, sa->d_todo3, sa->d_counts + 4, (unsigned long long*)nullptr);
 			NBR_TRACE("k_sim");
-			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 6 * (size_t)sa->time_sim_step + 2 * h + 1), sa->stream3));
+			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 4 * (size_t)sa->time_sim_step + 2 * h + 1), sa->stream3));
 		}
 		HIPCHK(hipEventRecord(sa->ev_sim, sa->stream3));
 		for (uint32_t h = 1; h < slices; h += 2) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_rest[h], 0)); /* the walks of the other stream's slices */
@@ -506,35 +507,20 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo, sa->d_counts,
 		                   sa->d_prof, sa->big, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_FULL>");
 	}
-	/* the few whose change lists overflowed LDS (or that need a second top-K pick): the whole
-	 * evaluation in one kernel, lists in global scratch */
-	const uint32_t bigneed = (sa->big.slots + sa->waves_per_block2 - 1) / sa->waves_per_block2; /* a slot per neighbour: none is dropped */
-	const uint32_t bigblocks = bigneed < 1024u ? bigneed : 1024u; /* the kernel strides over its list */
-	BigScratch big_now = sa->big;
-	big_now.lds_cache = 1u;
-	const uint32_t big_lds = sa->nbr2_lds + 12u * MGL_BIG_CAP; /* + a copy of both lists for the re-simulations */
-	if (!split_now || g_big_inline_sim) big_now.sim_hdr2 = nullptr; /* the one-kernel form has no k_sim launch to hand over to */
-	hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks), dim3(64 * sa->waves_per_block2), big_lds, sa->stream, sa->ctx,
+	/* the few whose change lists overflowed LDS (or that need a second top-K pick): the whole evaluation in one kernel,
+	 * lists in global scratch, a workgroup per neighbour -- one wavefront evaluates it, the others share its re-simulations */
+	const uint32_t bigblocks = sa->big.slots < 1024u ? sa->big.slots : 1024u; /* the kernel strides over its list: none is dropped */
+	const uint32_t big_lds = 4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES; /* + a copy of both lists for the re-simulations, + the workgroup's command */
+	hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks), dim3(64 * sa->big_waves), big_lds, sa->stream, sa->ctx,
 	                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
-	                   g_prof_big ? sa->d_prof : (unsigned long long*)nullptr, big_now, (sa->split_nbr && !sa->form_single) ? sa->d_pickrec : (uint4*)nullptr, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
+	                   g_prof_big ? sa->d_prof : (unsigned long long*)nullptr, sa->big, split_now ? sa->d_pickrec : (uint4*)nullptr, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
 	if (split_now) {
-		/* the second pass handed its final re-simulations to k_sim as well (headers in sim_hdr2): a small grid over its list */
-		const uint32_t sim_lds = ((((sa->ctx.L.total + 31u) >> 5) + 3u) & ~3u) * 4u + MGL_SIM2_CAP * 16u;
-		if (sa->time_sim_step >= 0) HIPCHK(hipEventRecord(sim_event(sa, 6 * (size_t)sa->time_sim_step + 4), sa->stream));
-		if (sa->count_traffic)
-			hipLaunchKernelGGL(k_sim<true>, dim3(256), dim3(64 * MGL_SIM_WAVES_LIST), sim_lds, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->nbr, big_now, 0u, K,
-			                   sa->d_todo3, sa->d_counts + 4, (const uint32_t*)sa->d_todo, (const uint32_t*)sa->d_counts, sa->d_traffic);
-		else
-			hipLaunchKernelGGL(k_sim<false>, dim3(256), dim3(64 * MGL_SIM_WAVES_LIST), sim_lds, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->nbr, big_now, 0u, K,
-			                   sa->d_todo3, sa->d_counts + 4, (const uint32_t*)sa->d_todo, (const uint32_t*)sa->d_counts, (unsigned long long*)nullptr);
-		NBR_TRACE("k_sim");
-		if (sa->time_sim_step >= 0) HIPCHK(hipEventRecord(sim_event(sa, 6 * (size_t)sa->time_sim_step + 5), sa->stream));
-		/* what k_sim (either launch) could not take: a late second pass that re-simulates inline */
+		/* what k_sim could not take (more touched contexts than its list holds): a late second pass */
 		HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_sim, 0));
 		BigScratch late = sa->big;
-		late.todo_in = sa->d_todo3; late.todo_in_count = sa->d_counts + 4; late.sim_hdr2 = nullptr; late.lds_cache = 1u;
+		late.todo_in = sa->d_todo3; late.todo_in_count = sa->d_counts + 4;
 		late.cont = nullptr; /* its list is another one: the slots' saved walks belong to the second pass proper */
-		hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks < 64u ? bigblocks : 64u), dim3(64 * sa->waves_per_block2), big_lds, sa->stream, sa->ctx,
+		hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks < 64u ? bigblocks : 64u), dim3(64 * sa->big_waves), big_lds, sa->stream, sa->ctx,
 		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
 		                   (unsigned long long*)nullptr, late, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
 	}
@@ -596,7 +582,7 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 		dfree(bt.bk_ipos); dfree(bt.bk_rpos); dfree(bt.bk_ibit); dfree(bt.bk_icl); dfree(bt.bk_rcl);
 	}
 	for (hipEvent_t e : sa->ev_sim_pool) if (e) (void)hipEventDestroy(e);
-	dfree(sa->d_todo2); dfree(sa->d_todo3); dfree(sa->d_counts); dfree(sa->big.sim_hdr2); dfree(sa->big.sim_slot2); dfree(sa->d_pickrec); dfree(sa->d_pickstate);
+	dfree(sa->d_todo2); dfree(sa->d_todo3); dfree(sa->d_counts); dfree(sa->d_pickrec); dfree(sa->d_pickstate);
 	dfree(sa->lim.why); dfree(sa->ab.hdr); dfree(sa->ab.ins_key); dfree(sa->ab.rem_key); dfree(sa->ab.ins_pos); dfree(sa->ab.rem_pos);
 	dfree(sa->ab.tctx); dfree(sa->ab.scratch_pos); dfree(sa->ab.scratch_ev);
 	dfree(sa->ab.span_pos); dfree(sa->ab.span_ev); dfree(sa->ab.jobs_b); dfree(sa->ab.jobs_c);
@@ -976,7 +962,7 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_REST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sa->nbr2_lds + 12u * MGL_BIG_CAP)));
+		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES)));
 		HIPCHK(hipMalloc(&sa->d_pickrec, sizeof(uint4) * K));
 		HIPCHK(hipMalloc(&sa->d_pickstate, sizeof(uint4) * 2 * K));
 		sa->split_nbr = getenv("MGL_NO_SPLIT") == nullptr;
@@ -987,9 +973,6 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 			HIPCHK(hipMalloc(&g.sim_keys, sizeof(uint16_t) * 2u * sa->chg_cap * (size_t)K));
 			HIPCHK(hipMalloc(&g.sim_pos, sizeof(uint32_t) * 2u * sa->chg_cap * (size_t)K));
 			HIPCHK(hipMemset(g.sim_hdr, 0xFF, sizeof(uint4) * (size_t)K));
-			HIPCHK(hipMalloc(&g.sim_hdr2, sizeof(uint4) * (size_t)K));
-			HIPCHK(hipMalloc(&g.sim_slot2, sizeof(uint32_t) * (size_t)K));
-			HIPCHK(hipMemset(g.sim_hdr2, 0xFF, sizeof(uint4) * (size_t)K));
 			/* continuation records: the second half saves a walk that stops at a repair pick, the second pass resumes it */
 			if (getenv("MGL_NO_CONT") == nullptr) {
 				HIPCHK(hipMalloc(&g.cont, sizeof(uint32_t) * MGL_CONT_WORDS * (size_t)g.slots));
@@ -2108,9 +2091,8 @@ extern "C" int mgl_sa_run(mgl_sa* sa, uint64_t steps, mgl_sa_stats* stats)
 		stats->neighbour_launches = timed_steps;
 		for (uint64_t s = 0; s < timed_steps && s < sim_timed.size(); s++) {
 			if (!sim_timed[s]) continue;
-			for (uint32_t h = 0; h < 3; h++) { /* the regular launches (one per slice, at most two timed) and the second pass's list */
-				if (h < 2 && h >= sim_timed[s]) continue;
-				HIPCHK(hipEventElapsedTime(&ms, sa->ev_sim_pool[6 * s + 2 * h], sa->ev_sim_pool[6 * s + 2 * h + 1]));
+			for (uint32_t h = 0; h < sim_timed[s]; h++) { /* the regular launches: one per slice, at most two timed */
+				HIPCHK(hipEventElapsedTime(&ms, sa->ev_sim_pool[4 * s + 2 * h], sa->ev_sim_pool[4 * s + 2 * h + 1]));
 				stats->gpu_ms_sim += ms;
 				stats->sim_launches++;
 			}
@@ -2455,6 +2437,11 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 	if (key == 2) { /* first-pass list capacity, below what was allocated: pushes neighbours into the second pass */
 		if (value < 8 || value > sa->chg_cap || (value & 7u)) return fail(MGL_EINVAL, "mgl_debug_set: list capacity must be a multiple of 8 within the allocated one");
 		sa->big.chg_cap = (uint32_t)value;
+		return MGL_OK;
+	}
+	if (key == 7) { /* wavefronts that share a second-pass neighbour's re-simulations: the block size of that launch and nothing else */
+		if (value != 1 && value != 2 && value != MGL_BIG_WAVES) return fail(MGL_EINVAL, "mgl_debug_set: 1, 2 or MGL_BIG_WAVES wavefronts");
+		sa->big_waves = (uint32_t)value;
 		return MGL_OK;
 	}
 	if (key == 3) { sa->force_rollbacks = (uint32_t)value; return MGL_OK; } /* the next `value` bulk steps that take moves are taken back as if their parse had failed validation */

@@ -677,9 +677,6 @@ struct BigScratch {
 	 * {n_ins, n_rem, direct lo, direct hi} (n_ins = ~0: nothing to do) and the two change lists */
 	uint32_t chg_cap; /* events per first-pass list (MGL_CHG_CAP, more when a step has few neighbours and LDS to spare) */
 	uint4* sim_hdr;
-	uint4* sim_hdr2; /* the same for the second pass's neighbours (k_sim's second launch); nullptr: the second pass re-simulates inline */
-	uint32_t* sim_slot2; /* per neighbour: the scratch slot its lists sit in */
-	uint32_t lds_cache; /* second pass: 12 * MGL_BIG_CAP bytes of LDS behind the wavefront's area hold a copy of the lists during a re-simulation */
 	uint16_t* sim_keys; /* per neighbour: ins_key[chg_cap] | rem_key[chg_cap] */
 	uint32_t* sim_pos;  /* per neighbour: ins_pos[chg_cap] | rem_pos[chg_cap] */
 	/* continuation records, one per scratch slot (MGL_CONT_WORDS u32 each): a second-half wavefront whose repair needs a top-K pick
@@ -704,10 +701,100 @@ struct BigScratch {
 #ifndef MGL_REST_WAVES_PER_SIMD
 #define MGL_REST_WAVES_PER_SIMD 4
 #endif
-#define MGL_SIM2_CAP 4096u /* events per list k_sim's second launch takes (the second pass's neighbours) */
 #define MGL_NBR_FULL 0
 #define MGL_NBR_PICK 1
 #define MGL_NBR_REST 2
+/* ---- the second pass's re-simulations, by the whole workgroup
+ *
+ * A second-pass workgroup is MGL_BIG_WAVES wavefronts on one neighbour.  Wavefront 0 evaluates the neighbour (nbr2_one);
+ * the others wait in coop_helpers and take part in its re-simulations only -- the overlay at a repair pick and the final
+ * one -- the way k_sim's wavefronts share a regular neighbour's contexts.  Wavefront 0 lists the distinct contexts, posts a
+ * command in LDS and then runs the same three barriers as the helpers (coop_share):
+ *     A   the command is posted              -> everyone copies its share of the two lists into LDS
+ *     B   the lists are in LDS               -> everyone re-simulates contexts wid * 64 + lane, + blockDim.x, ...
+ *     C   sums (and overlay values) are in   -> wavefront 0 adds the sums up and walks on
+ * Wavefront 0 reaches barrier A only in coop_sim and once more, with EXIT, behind its loop over the units (every return
+ * of nbr2_one leads there); a helper leaves at A on EXIT or when the generation has not advanced.  No barrier sits in
+ * divergent code, nothing spins. */
+#ifndef MGL_BIG_WAVES
+#define MGL_BIG_WAVES 4u /* one per SIMD: the instance keeps its 256 VGPRs + AGPRs at one wavefront per SIMD */
+#endif
+#define MGL_COOP_SIM 1u
+#define MGL_COOP_EXIT 2u
+#define MGL_COOP_BYTES 128u /* LDS the command takes, behind the copy of the lists */
+struct CoopCmd {
+	uint32_t gen;     /* advanced by wavefront 0 with every command */
+	uint32_t op;
+	uint32_t slot;    /* the neighbour's scratch slot: lists and context list */
+	uint32_t n_ins, n_rem, nu, limit;
+	uint32_t overlay; /* byte offset of wavefront 0's model in the workgroup's LDS; 0: no overlay */
+	unsigned long long sum[MGL_BIG_WAVES];
+};
+static_assert(sizeof(CoopCmd) <= MGL_COOP_BYTES, "CoopCmd outgrew its LDS");
+__device__ __forceinline__ CoopCmd* coop_cmd(unsigned char* smem, uint32_t per_wave_bytes)
+{
+	return (CoopCmd*)(smem + 4096u + per_wave_bytes + 12u * MGL_BIG_CAP);
+}
+/* every wavefront of the workgroup, behind barrier A: barriers B and C are in here */
+__device__ __forceinline__ void coop_share(const DevCtx& c, const Base2& b, const BigScratch& big, unsigned long long* dbg, unsigned char* smem,
+                                           uint32_t per_wave_bytes, const uint16_t* T, CoopCmd* cmd, uint32_t lane, uint32_t wid)
+{
+	const uint32_t slot = uni(cmd->slot), overlay = uni(cmd->overlay);
+	Changes cl;
+	cl.n_ins = uni(cmd->n_ins); cl.n_rem = uni(cmd->n_rem);
+	/* the lists sit in the slot's global scratch; a re-simulation scans them once per touched context, so it works on a copy
+	 * in LDS (behind wavefront 0's area: the second pass's launch reserves it) */
+	uint32_t* cp = (uint32_t*)(smem + 4096u + per_wave_bytes);
+	cl.ins_pos = cp; cl.rem_pos = cp + MGL_BIG_CAP;
+	cl.ins_key = (uint16_t*)(cp + 2u * MGL_BIG_CAP); cl.rem_key = cl.ins_key + MGL_BIG_CAP;
+	cl.uctx = big.uctx + (size_t)slot * big.uctx_cap; cl.ctxbits = nullptr;
+	cl.cap = MGL_BIG_CAP; cl.uctx_cap = big.uctx_cap; cl.nbitwords = 0;
+	cl.direct = 0; cl.dbg = dbg; cl.diag = c.diag_stop; cl.overflow = false; cl.list_full = false;
+	const uint16_t* gik = big.ins_key + (size_t)slot * big.cap; const uint32_t* gip = big.ins_pos + (size_t)slot * big.cap;
+	const uint16_t* grk = big.rem_key + (size_t)slot * big.cap; const uint32_t* grp = big.rem_pos + (size_t)slot * big.cap;
+	for (uint32_t e = threadIdx.x; e < cl.n_ins; e += blockDim.x) { cl.ins_pos[e] = gip[e]; cl.ins_key[e] = gik[e]; }
+	for (uint32_t e = threadIdx.x; e < cl.n_rem; e += blockDim.x) { cl.rem_pos[e] = grp[e]; cl.rem_key[e] = grk[e]; }
+	__syncthreads(); /* B */
+	const int64_t mine = chain_sim_contexts(b, cl, T, uni(cmd->limit), overlay ? (uint16_t*)(smem + overlay) : nullptr, lane, wid * 64u, blockDim.x, uni(cmd->nu));
+	const uint64_t u = wave_sum64((uint64_t)mine);
+	if (lane == 0) cmd->sum[wid] = u;
+	__syncthreads(); /* C */
+}
+/* wavefront 0, at either re-simulation site of the second pass: chain_sim with the workgroup's help */
+__device__ __forceinline__ int64_t coop_sim(const DevCtx& c, const Base2& b, const BigScratch& big, unsigned long long* dbg, unsigned char* smem,
+                                            uint32_t per_wave_bytes, const uint16_t* T, Changes& ch, uint32_t slot, uint32_t limit, uint16_t* overlay,
+                                            uint32_t lane, bool* too_many)
+{
+	const uint32_t nu = chain_list(ch, lane, too_many); /* from the lists in global memory: one pass over the keys */
+	if (*too_many) return 0;
+	if (ch.diag == 41) return (int64_t)nu;
+	CoopCmd* cmd = coop_cmd(smem, per_wave_bytes);
+	if (lane == 0) {
+		cmd->op = MGL_COOP_SIM; cmd->slot = slot; cmd->n_ins = ch.n_ins; cmd->n_rem = ch.n_rem; cmd->nu = nu; cmd->limit = limit;
+		cmd->overlay = overlay ? (uint32_t)((unsigned char*)overlay - smem) : 0u;
+		cmd->gen = cmd->gen + 1u;
+	}
+	__syncthreads(); /* A */
+	coop_share(c, b, big, dbg, smem, per_wave_bytes, T, cmd, lane, 0u);
+	uint64_t d = 0;
+	for (uint32_t w = 0; w < (blockDim.x >> 6); w++) d += cmd->sum[w];
+	wave_sync();
+	return (int64_t)d;
+}
+/* wavefronts 1 .. of a second-pass workgroup */
+__device__ __forceinline__ void coop_helpers(const DevCtx& c, const Base2& b, const BigScratch& big, unsigned long long* dbg, unsigned char* smem,
+                                             uint32_t per_wave_bytes, const uint16_t* T, uint32_t lane, uint32_t wid)
+{
+	CoopCmd* cmd = coop_cmd(smem, per_wave_bytes);
+	uint32_t seen = 0;
+	for (;;) {
+		__syncthreads(); /* A */
+		const uint32_t gen = uni(cmd->gen);
+		if (uni(cmd->op) == MGL_COOP_EXIT || gen == seen) return;
+		seen = gen;
+		coop_share(c, b, big, dbg, smem, per_wave_bytes, T, cmd, lane, wid);
+	}
+}
 /* one neighbour, by the wavefront `wid` of its workgroup; `unit` = the neighbour's index in this launch's slice
  * (regular launch) or its slot in the second pass's list (BIG) */
 template <bool BIG, int MODE>
@@ -765,7 +852,6 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	ch.n_ins = ch.n_rem = 0; ch.direct = 0; ch.overflow = false; ch.list_full = false;
 	bool too_many = false;
 	bool spilled = BIG;
-	const bool spilled_lds = false; /* BIG: the lists live in this neighbour's global scratch slot from the start */
 
 	const uint64_t gstep = step_override != ~0ull ? step_override : ctl->gstep;
 	NbrRng rng; rng.key = mgl_rng_key(seed, gstep, j); rng.n = 0;
@@ -779,7 +865,6 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	uint32_t target;
 	mgl_wstate nb; /* neighbour's walk state */
 	if (MODE == MGL_NBR_REST && lane == 0) big.sim_hdr[j] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
-	if (BIG && big.sim_hdr2 != nullptr && lane == 0) big.sim_hdr2[j] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
 	if (MODE == MGL_NBR_REST) {
 		const uint4 s0 = pickstate[2u * j], s1 = pickstate[2u * j + 1u];
 		target = s0.x; rng.n = s0.y;
@@ -952,18 +1037,6 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 			if ((ch.n_ins + ch.n_rem) != 0) { sim_limit = pick_pos; sim_overlay = true; phase = P_SIM; }
 			else phase = P_TOPK;
 		}
-		if (BIG && big.sim_hdr2 != nullptr && !sim_overlay && !spilled_lds && ch.n_ins <= MGL_SIM2_CAP && ch.n_rem <= MGL_SIM2_CAP && phase == P_SIM) {
-			/* the second pass hands over its FINAL re-simulation too: k_sim's second launch reads the lists straight from this
-			 * neighbour's scratch slot into LDS and puts two wavefronts on them (here they sit in global memory in front of one
-			 * wavefront: the long-list neighbours were the slowest of the pass) */
-			if (lane == 0) {
-				big.sim_slot2[j] = slot;
-				big.sim_hdr2[j] = make_uint4(ch.n_ins, ch.n_rem, (uint32_t)(uint64_t)ch.direct, (uint32_t)((uint64_t)ch.direct >> 32));
-			}
-			sim_deferred = true;
-			phase = P_OUT;
-			continue;
-		}
 		if (MODE == MGL_NBR_REST && phase == P_SIM) {
 			/* the second half ends here (always: it holds no re-simulation code of its own): the lists go to k_sim, which puts several wavefronts on the
 			 * contexts of one neighbour and writes the cost; journal and counters are written below */
@@ -979,20 +1052,8 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		}
 		if (MODE == MGL_NBR_FULL && phase == P_SIM) {
 			int64_t r;
-			if (BIG && big.lds_cache && ch.n_ins <= MGL_BIG_CAP && ch.n_rem <= MGL_BIG_CAP) {
-				/* the second pass keeps its lists in global memory; a re-simulation scans them once per touched context,
-				 * so it works on a copy in LDS (behind this wavefront's regular area: the second pass's launch reserves it) */
-				uint32_t* cp = (uint32_t*)(mine + per_wave_bytes);
-				Changes cl = ch;
-				cl.ins_pos = cp; cl.rem_pos = cp + MGL_BIG_CAP;
-				cl.ins_key = (uint16_t*)(cp + 2u * MGL_BIG_CAP); cl.rem_key = cl.ins_key + MGL_BIG_CAP;
-				for (uint32_t e = lane; e < ch.n_ins; e += 64) { cl.ins_pos[e] = ch.ins_pos[e]; cl.ins_key[e] = ch.ins_key[e]; }
-				for (uint32_t e = lane; e < ch.n_rem; e += 64) { cl.rem_pos[e] = ch.rem_pos[e]; cl.rem_key[e] = ch.rem_key[e]; }
-				wave_sync();
-				r = chain_sim(b, cl, T, sim_limit, sim_overlay ? probs : nullptr, lane, &too_many);
-			} else {
-				r = chain_sim(b, ch, T, sim_limit, (MODE != MGL_NBR_REST && sim_overlay) ? probs : nullptr, lane, &too_many);
-			}
+			if (BIG) r = coop_sim(c, b, big, prof_acc, smem, per_wave_bytes, T, ch, slot, sim_limit, sim_overlay ? probs : nullptr, lane, &too_many);
+			else r = chain_sim(b, ch, T, sim_limit, sim_overlay ? probs : nullptr, lane, &too_many);
 			wave_sync();
 			if (too_many) { phase = P_OUT; continue; }
 			if (sim_overlay) { prof_mark(prof, 6, lane); phase = P_TOPK; } /* repair: model overridden by the re-simulated values */
@@ -1244,7 +1305,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 }
 
 template <bool BIG, int MODE>
-__global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : 64), (MODE == MGL_NBR_FULL ? (BIG ? 1 : MGL_NBR_WAVES_PER_SIMD) : (MODE == MGL_NBR_REST ? MGL_REST_WAVES_PER_SIMD : 4))) k_neighbours2(DevCtx c, Base2 b, Control* ctl, uint64_t seed,
+__global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_BIG_WAVES : 64)), (MODE == MGL_NBR_FULL ? (BIG ? 1 : MGL_NBR_WAVES_PER_SIMD) : (MODE == MGL_NBR_REST ? MGL_REST_WAVES_PER_SIMD : 4))) k_neighbours2(DevCtx c, Base2 b, Control* ctl, uint64_t seed,
                                                      uint64_t step_override, uint32_t K, NbrOut out, uint32_t per_wave_bytes,
                                                      uint32_t* todo, uint32_t* todo_count, unsigned long long* prof_acc,
                                                      BigScratch big, uint4* pickrec, uint32_t j_base, uint32_t j_end, uint4* pickstate)
@@ -1252,11 +1313,13 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : 64), (MODE == MG
 	/* Which form of the regular launch runs (split: pick + rest + k_sim, or the one-kernel form) is the host's
 	 * choice per block of steps (mgl_sa_run reads the device's recommendation, Control::nbr_single): only the
 	 * chosen form is launched.  The second pass is launched with a small grid whatever its list holds -- the
-	 * host does not know the count -- and strides over it; with an empty list a workgroup costs one load. */
+	 * host does not know the count -- and strides over it, a workgroup per neighbour; with an empty list a
+	 * workgroup costs one load. */
 	const uint32_t waves = blockDim.x >> 6;
-	if (BIG && blockIdx.x * waves >= *big.todo_in_count) return;
+	if (BIG && blockIdx.x >= *big.todo_in_count) return; /* uniform over the workgroup */
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	uint16_t* T = (uint16_t*)smem;
+	if (BIG && threadIdx.x == 0) { CoopCmd* cmd = coop_cmd(smem, per_wave_bytes); cmd->gen = 0; cmd->op = MGL_COOP_SIM; }
 	/* 4 KiB as 256 16-byte units (the table is hipMalloc-aligned, T sits at the start of the LDS block); the second
 	 * half of the split form prices nothing (its re-simulation is k_sim's) and has no table: 4 KiB less per workgroup */
 	if (MODE == MGL_NBR_PICK && MGL_PICK_T_GLOBAL) {
@@ -1267,9 +1330,13 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : 64), (MODE == MG
 	}
 	const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
 	if (BIG) {
+		/* wavefront 0 takes the workgroup's neighbours one at a time; the others help with their re-simulations */
+		if (wid != 0) { coop_helpers(c, b, big, prof_acc, smem, per_wave_bytes, T, lane, wid); return; }
 		const uint32_t n = *big.todo_in_count;
-		for (uint32_t unit = blockIdx.x * waves + wid; unit < n; unit += gridDim.x * waves)
-			nbr2_one<BIG, MODE>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T, unit, lane, wid);
+		for (uint32_t unit = blockIdx.x; unit < n; unit += gridDim.x)
+			nbr2_one<BIG, MODE>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T, unit, lane, 0u);
+		if (lane == 0) { CoopCmd* cmd = coop_cmd(smem, per_wave_bytes); cmd->op = MGL_COOP_EXIT; cmd->gen = cmd->gen + 1u; }
+		__syncthreads(); /* A, for the last time: the helpers leave */
 	} else {
 		nbr2_one<BIG, MODE>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T,
 		                    blockIdx.x * waves + wid, lane, wid);
@@ -1287,9 +1354,6 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : 64), (MODE == MG
 #ifndef MGL_SIM_WAVES
 #define MGL_SIM_WAVES 2u   /* the regular launch: thousands of neighbours, a hundred contexts each */
 #endif
-#ifndef MGL_SIM_WAVES_LIST
-#define MGL_SIM_WAVES_LIST 8u /* the second pass's few neighbours (long lists, hundreds of contexts): one trip over the contexts */
-#endif
 #define MGL_SIM_WAVES_MAX 8u
 struct SimShared {
 	uint16_t* T;
@@ -1297,14 +1361,13 @@ struct SimShared {
 	unsigned long long* sum;
 	uint32_t* nu_many; /* [0] distinct contexts, [1] too many */
 };
-template <bool FROM_BIG, bool COUNT>
+template <bool COUNT>
 __device__ __forceinline__ void sim_one(const DevCtx& c, const Base2& b, Control* ctl, const NbrOut& out, const BigScratch& big, const uint4* hdrs,
                                         uint32_t j, uint32_t* todo, uint32_t* todo_count, const SimShared& sh, unsigned long long* traffic_ctr)
 {
 	const uint4 hdr = hdrs[j];
 	if (hdr.x == 0xFFFFFFFFu) return; /* failed, dropped or handed on: its cost is written (uniform over the workgroup) */
-	const uint32_t cap = FROM_BIG ? MGL_SIM2_CAP : big.chg_cap;
-	const uint32_t slot = FROM_BIG ? big.sim_slot2[j] : 0u;
+	const uint32_t cap = big.chg_cap;
 	uint32_t* s_bits = sh.dyn;
 	uint32_t* s_pos = sh.dyn + ((((c.L.total + 31u) >> 5) + 3u) & ~3u);
 	uint16_t* s_key = (uint16_t*)(s_pos + 2u * cap);
@@ -1318,18 +1381,10 @@ __device__ __forceinline__ void sim_one(const DevCtx& c, const Base2& b, Control
 	ch.cap = cap; ch.uctx_cap = 2 * cap;
 	ch.nbitwords = (c.L.total + 31u) >> 5;
 	ch.direct = 0; ch.dbg = nullptr; ch.diag = c.diag_stop; ch.overflow = false; ch.list_full = false;
-	__syncthreads(); /* the previous neighbour of a striding workgroup is done with the LDS */
-	if (FROM_BIG) {
-		const uint16_t* ik = big.ins_key + (size_t)slot * big.cap; const uint32_t* ip = big.ins_pos + (size_t)slot * big.cap;
-		const uint16_t* rk = big.rem_key + (size_t)slot * big.cap; const uint32_t* rp = big.rem_pos + (size_t)slot * big.cap;
-		for (uint32_t e = threadIdx.x; e < ch.n_ins; e += blockDim.x) { s_key[e] = ik[e]; s_pos[e] = ip[e]; }
-		for (uint32_t e = threadIdx.x; e < ch.n_rem; e += blockDim.x) { s_key[cap + e] = rk[e]; s_pos[cap + e] = rp[e]; }
-	} else {
-		const uint16_t* gk = big.sim_keys + (size_t)j * (2u * cap);
-		const uint32_t* gp = big.sim_pos + (size_t)j * (2u * cap);
-		for (uint32_t e = threadIdx.x; e < ch.n_ins; e += blockDim.x) { s_key[e] = gk[e]; s_pos[e] = gp[e]; }
-		for (uint32_t e = threadIdx.x; e < ch.n_rem; e += blockDim.x) { s_key[cap + e] = gk[cap + e]; s_pos[cap + e] = gp[cap + e]; }
-	}
+	const uint16_t* gk = big.sim_keys + (size_t)j * (2u * cap);
+	const uint32_t* gp = big.sim_pos + (size_t)j * (2u * cap);
+	for (uint32_t e = threadIdx.x; e < ch.n_ins; e += blockDim.x) { s_key[e] = gk[e]; s_pos[e] = gp[e]; }
+	for (uint32_t e = threadIdx.x; e < ch.n_rem; e += blockDim.x) { s_key[cap + e] = gk[cap + e]; s_pos[cap + e] = gp[cap + e]; }
 	__syncthreads();
 	if (wid == 0) {
 		bool too_many = false;
@@ -1363,32 +1418,24 @@ __device__ __forceinline__ void sim_one(const DevCtx& c, const Base2& b, Control
 		out.cost[j] = (uint64_t)((int64_t)ctl->rebuild_cost + (int64_t)d + direct);
 	}
 }
-/* list == nullptr: the regular launch, workgroup x = neighbour j_base + x with header sim_hdr.  list != nullptr: the
- * second pass's neighbours (headers in sim_hdr2), a small grid striding over the list. */
+/* workgroup x = neighbour j_base + x with header sim_hdr */
 /* COUNT: the same kernel adding up the bytes of chain data and change lists it reads (traffic_ctr[0]) and its launches that had
  * work (traffic_ctr[1]); bench.py runs a few steps with it after its timed region */
 template <bool COUNT>
 __global__ void __launch_bounds__(64 * MGL_SIM_WAVES_MAX, 8) k_sim(DevCtx c, Base2 b, Control* ctl, NbrOut out, BigScratch big, uint32_t j_base, uint32_t j_end,
-                                                           uint32_t* todo, uint32_t* todo_count, const uint32_t* list, const uint32_t* list_count,
-                                                           unsigned long long* traffic_ctr)
+                                                           uint32_t* todo, uint32_t* todo_count, unsigned long long* traffic_ctr)
 {
-	if (list ? blockIdx.x >= *list_count : j_base + blockIdx.x >= j_end) return;
+	if (j_base + blockIdx.x >= j_end) return;
 	__shared__ __attribute__((aligned(16))) uint16_t T[2048];
 	/* sized by the launch: one bit per context, then the two lists (positions, keys) and the context list */
 	extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
 	__shared__ unsigned long long s_sum[MGL_SIM_WAVES_MAX];
 	__shared__ uint32_t s_nm[2];
-	if (!list && big.sim_hdr[j_base + blockIdx.x].x == 0xFFFFFFFFu) return; /* before the table load: most launches of a bulk-free step's tail */
+	if (big.sim_hdr[j_base + blockIdx.x].x == 0xFFFFFFFFu) return; /* before the table load: most launches of a bulk-free step's tail */
 	for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) reinterpret_cast<uint4*>(T)[i] = reinterpret_cast<const uint4*>(c.cost_tbl)[i];
 	SimShared sh;
 	sh.T = T; sh.dyn = s_dyn; sh.sum = s_sum; sh.nu_many = s_nm;
-	if (list) {
-		const uint32_t n = *list_count;
-		for (uint32_t i = blockIdx.x; i < n; i += gridDim.x)
-			sim_one<true, COUNT>(c, b, ctl, out, big, big.sim_hdr2, list[i], todo, todo_count, sh, traffic_ctr);
-	} else {
-		sim_one<false, COUNT>(c, b, ctl, out, big, big.sim_hdr, j_base + blockIdx.x, todo, todo_count, sh, traffic_ctr);
-	}
+	sim_one<COUNT>(c, b, ctl, out, big, big.sim_hdr, j_base + blockIdx.x, todo, todo_count, sh, traffic_ctr);
 }
 
 
