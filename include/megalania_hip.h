@@ -201,7 +201,9 @@ int mgl_optimal_prices(mgl_sa* sa, const mgl_packet* packets, uint32_t* prices_o
  * from pass p - 1's resolved parse.  Every resolved parse is costed exactly; the cheapest becomes the current slab, with
  * mgl_sa_seed_optimal's effect on the handle.  With from_current the current slab competes too (the re-parse: a caller may
  * alternate it with mgl_sa_run): if no pass beats it the handle is left untouched, stats->best_pass is UINT32_MAX, and
- * stats->greedy_cost holds the current slab's cost.  Fields left 0 take the defaults (segment 0: both segment and ahead). */
+ * stats->greedy_cost holds the current slab's cost.  Fields left 0 take the defaults (segment 0: both segment and ahead).
+ * The call is mgl_sa_seed_sweep with one variant, under the handle's finder and depth: MGL_ENOMEM, with the handle left
+ * usable, where its buffers (about 34 bytes per input byte) do not fit the device. */
 typedef struct {
 	uint32_t passes;   /* default 3, at most MGL_OPT_MAX_PASSES */
 	uint32_t cand;     /* default 16, at most 30 */
@@ -213,7 +215,8 @@ typedef struct {
 int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, mgl_optimal_stats* stats);
 /* Parity hook: one pass from the chunk starts of `parse_in` (n entries; MGL_ERANGE unless a valid parse).  packets_out
  * (n entries) is the concatenated, unresolved parse in mgl_optimal_pass's form; *objective = the sum over the segments of
- * the prices of what each committed.  segment 0 takes the default commit distance.  The SA state is untouched. */
+ * the prices of what each committed.  segment 0 takes the default commit distance.  The SA state is untouched.
+ * MGL_ENOMEM as for mgl_sa_seed_adaptive (about 18 bytes per input byte here). */
 int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead,
                       mgl_packet* packets_out, uint64_t* objective);
 /* The adaptive parse under several settings at once.  Variant v is the parse that
@@ -226,8 +229,8 @@ int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uin
  * current slab competes: if nothing beats it the handle is left untouched and *best_variant is UINT32_MAX.  The handle's
  * own match-finder selection stays; the frontier's lists are made (or reused) at `depth` only if a variant asks for them.
  * MGL_EINVAL: no or more than MGL_SWEEP_MAX variants, an unknown finder, cand above 30, ahead above 273, chunk below 512,
- * more than 16 passes, depth above 4096.  MGL_ENOMEM: the per-variant buffers (about 26 bytes per input byte and variant)
- * do not fit; the handle stays usable. */
+ * more than 16 passes, depth above 4096.  MGL_ENOMEM: the buffers (about 26 bytes per input byte and variant, pass 0's
+ * greedy parses included, and 8 per input byte for the kept parse) do not fit; the handle stays usable. */
 #define MGL_SWEEP_MAX 64
 typedef struct {
 	uint32_t finder;   /* MGL_MF_NEAREST | MGL_MF_FRONTIER */

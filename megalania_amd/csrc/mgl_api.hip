@@ -1095,6 +1095,48 @@ static int keep_best_before_overwrite(mgl_sa* sa, Control& c)
 	return MGL_OK;
 }
 
+/* MGL_ACCEPT_AUTO starts over: a fresh block, bulk steps first (a new slab says nothing about the old one's windows) */
+static void auto_reset(mgl_sa* sa) { sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; }
+
+/* The base has just been rebuilt on a new current slab: the walk's verdict on it, after checking every packet against the
+ * input too if `validate`.  A slab that fails is `bad` in the name of `who`; *cost (nullable) = its exact cost. */
+static int check_current(mgl_sa* sa, bool validate, int bad, const char* who, uint64_t* cost)
+{
+	int rc;
+	Control c;
+	if (validate && (rc = launch_validate(sa))) return rc;
+	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+	if (c.error_flags) return fail(bad, std::string(who) + ": the new current slab is not a valid parse of the input");
+	if (cost) *cost = c.rebuild_cost;
+	return MGL_OK;
+}
+
+/* The current slab is replaced by what `put` leaves in base.v.slab (an import, a kernel launch, a device copy): the best
+ * slab's structures are saved if the base is their only holder, MGL_ACCEPT_AUTO starts over, the current cost and the
+ * flags are cleared and the base is rebuilt; then check_current. */
+template <class Put>
+static int replace_current(mgl_sa* sa, Put put, bool validate, int bad, const char* who, uint64_t* cost = nullptr)
+{
+	Control c;
+	int rc = read_ctl(sa, sa->base, &c);
+	if (rc) return rc;
+	if ((rc = keep_best_before_overwrite(sa, c))) return rc;
+	auto_reset(sa);
+	if ((rc = put())) return rc;
+	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
+	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
+	if ((rc = rebuild_base(sa, 0))) return rc;
+	return check_current(sa, validate, bad, who, cost);
+}
+/* put: a copy of a slab on the device */
+static auto put_slab(mgl_sa* sa, const mgl_pk* slab)
+{
+	return [=]() -> int {
+		HIPCHK(hipMemcpyAsync(sa->base.v.slab, slab, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->stream));
+		return MGL_OK;
+	};
+}
+
 extern "C" int mgl_sa_begin_epoch(mgl_sa* sa, unsigned phase, int from_best)
 {
 	if (!sa) return fail(MGL_EINVAL, "null handle");
@@ -1110,7 +1152,8 @@ extern "C" int mgl_sa_begin_epoch(mgl_sa* sa, unsigned phase, int from_best)
 	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
 	/* MGL_ACCEPT_AUTO starts every epoch the same way, whatever the previous one left behind: a fresh block, bulk steps
 	 * first from the all-literal slab (thousands of improving neighbours), single steps first from the best slab */
-	sa->bulk_now = !from_best; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false;
+	auto_reset(sa);
+	sa->bulk_now = !from_best;
 	if (from_best && base_is_best) return MGL_OK; /* main.c:73-76 would copy packets_best over itself */
 	if (snaps) {
 		SnapMeta meta[2];
@@ -1152,19 +1195,7 @@ extern "C" int mgl_sa_set_slab(mgl_sa* sa, const mgl_packet* packets)
 {
 	if (!sa || !packets) return fail(MGL_EINVAL, "null argument");
 	HIPCHK(hipSetDevice(sa->device));
-	Control c;
-	int rc = read_ctl(sa, sa->base, &c);
-	if (rc) return rc;
-	if ((rc = keep_best_before_overwrite(sa, c))) return rc;
-	sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
-	if ((rc = import_slab(sa, packets, sa->base.v.slab))) return rc;
-	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
-	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
-	if ((rc = rebuild_base(sa, 0))) return rc;
-	if ((rc = launch_validate(sa))) return rc;
-	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-	if (c.error_flags) return fail(MGL_EINVAL, "mgl_sa_set_slab: slab is not a valid parse of the input");
-	return MGL_OK;
+	return replace_current(sa, [=] { return import_slab(sa, packets, sa->base.v.slab); }, true, MGL_EINVAL, "mgl_sa_set_slab");
 }
 
 extern "C" int mgl_sa_set_temperature(mgl_sa* sa, uint64_t temperature)
@@ -1180,19 +1211,12 @@ extern "C" int mgl_sa_seed_greedy(mgl_sa* sa, uint32_t candidates)
 	if (!sa) return fail(MGL_EINVAL, "null handle");
 	if (candidates == 0) return fail(MGL_EINVAL, "mgl_sa_seed_greedy: candidates must be > 0");
 	HIPCHK(hipSetDevice(sa->device));
-	Control c;
-	int rc = read_ctl(sa, sa->base, &c);
-	if (rc) return rc;
-	if ((rc = keep_best_before_overwrite(sa, c))) return rc;
-	sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
-	hipLaunchKernelGGL(k_greedy_seed, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, sa->base.v.slab, candidates);
-	HIPCHK(hipGetLastError());
-	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
-	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
-	if ((rc = rebuild_base(sa, 0))) return rc;
-	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-	if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_greedy: the seeded slab failed the walk check");
-	return MGL_OK;
+	const auto put = [=]() -> int {
+		hipLaunchKernelGGL(k_greedy_seed, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, sa->base.v.slab, candidates);
+		HIPCHK(hipGetLastError());
+		return MGL_OK;
+	};
+	return replace_current(sa, put, false, MGL_EDEVICE, "mgl_sa_seed_greedy");
 }
 
 /* ---- optimal-parse seed (mgl_optimal.hip) */
@@ -1373,24 +1397,9 @@ extern "C" int mgl_optimal_prices(mgl_sa* sa, const mgl_packet* packets, uint32_
 	return MGL_OK;
 }
 
-/* current slab := the parse on `slab` (device); returns its exact cost through the base's rebuild */
-static int opt_make_current(mgl_sa* sa, const mgl_pk* slab, uint64_t* cost)
-{
-	Control c;
-	int rc = read_ctl(sa, sa->base, &c);
-	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(sa->base.v.slab, slab, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->stream));
-	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
-	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
-	if ((rc = rebuild_base(sa, 0))) return rc;
-	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-	if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_optimal: a resolved parse failed the walk check");
-	*cost = c.rebuild_cost;
-	return MGL_OK;
-}
-
 extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mgl_optimal_stats* stats)
 {
+	static const char* who = "mgl_sa_seed_optimal";
 	if (!sa) return fail(MGL_EINVAL, "null handle");
 	const uint32_t passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
 	const uint32_t cand = cfg && cfg->cand ? cfg->cand : MGL_OPT_DEF_CAND;
@@ -1401,18 +1410,14 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 	HIPCHK(hipSetDevice(sa->device));
 	mgl_optimal_stats st;
 	memset(&st, 0, sizeof st);
-	Control c;
-	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-	if ((rc = keep_best_before_overwrite(sa, c))) return rc;
-	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
-	sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
 	OptBufs o;
 	if ((rc = opt_alloc(sa, o, chunk, true))) return rc;
 	const uint32_t n = (uint32_t)sa->n;
-	/* pass 0's prices: the greedy parse */
+	/* pass 0's prices: the greedy parse.  It and every pass's parse become the current slab in turn: the base's rebuild is
+	 * what costs them */
 	hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.res, cand);
 	HIPCHK(hipGetLastError());
-	if ((rc = opt_make_current(sa, o.res, &st.greedy_cost))) return rc;
+	if ((rc = replace_current(sa, put_slab(sa, o.res), false, MGL_EDEVICE, who, &st.greedy_cost))) return rc;
 	if ((rc = opt_prices(sa, o, o.res))) return rc;
 	hipEvent_t t0, t1;
 	HIPCHK(hipEventCreate(&t0));
@@ -1426,7 +1431,7 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 		hipLaunchKernelGGL(k_opt_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, (const mgl_pk*)o.dp, o.res, o.counts, 1, chunk, o.entry);
 		hipLaunchKernelGGL(k_opt_prices, dim3((sa->ctx.L.total + 255) / 256), dim3(256), 0, sa->stream, (const uint32_t*)o.counts, sa->ctx.cost_tbl,
 		                   sa->ctx.L.total, o.prices);
-		if ((rc = opt_make_current(sa, o.res, &st.cost[p]))) break;
+		if ((rc = replace_current(sa, put_slab(sa, o.res), false, MGL_EDEVICE, who, &st.cost[p]))) break;
 		unsigned long long obj = 0;
 		HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
 		float ms = 0;
@@ -1444,32 +1449,51 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 	(void)hipEventDestroy(t0);
 	(void)hipEventDestroy(t1);
 	if (rc) return rc;
-	if (st.best_pass + 1 != st.passes && (rc = opt_make_current(sa, o.keep, &best))) return rc;
-	if ((rc = launch_validate(sa))) return rc;
-	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-	if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_optimal: the seeded slab failed the walk check");
+	/* the cheapest pass stays current (the last one already is), validated */
+	if (st.best_pass + 1 != st.passes) rc = replace_current(sa, put_slab(sa, o.keep), true, MGL_EDEVICE, who, &best);
+	else rc = check_current(sa, true, MGL_EDEVICE, who, nullptr);
+	if (rc) return rc;
 	HIPCHK(hipStreamSynchronize(sa->stream));
 	if (stats) *stats = st;
 	return MGL_OK;
 }
 
-/* ---- adaptive-price optimal parse (mgl_adaptive.hip) */
+/* ---- adaptive-price optimal parse (mgl_adaptive.hip): a batch of variants of the settings through one launch per stage.
+ * mgl_sa_seed_sweep keeps the cheapest parse as the current slab; mgl_parse_sweep_props gives every variant a triple of its
+ * own and hands the cheapest parse out; mgl_sa_seed_adaptive and mgl_adaptive_pass are a batch of one.  The stages below work
+ * on one Parse each, in the order they stand in. */
 #define MGL_ADP_DEF_SEGMENT 64u
 #define MGL_ADP_DEF_AHEAD 128u
-struct AdpBufs {
+struct Parse {
+	/* settings (parse_args) */
+	uint32_t nv = 0, passes = 0, chunk = 0, depth = 0, nch = 0, ncand = 0, nnear = 0, nfront = 0, lds_near = 0, lds_front = 0;
+	bool from_current = false;
+	size_t snap_total = 0;
+	AdpVariant h_tab[MGL_SWEEP_MAX];
+	uint32_t h_lists[MGL_SWEEP_MAX], cand_idx[MGL_SWEEP_MAX], cands[MGL_SWEEP_MAX]; /* variants by finder; a variant's cand among the distinct ones */
+	/* device buffers and events (parse_alloc) */
 	uint16_t* snaps = nullptr;
-	uint32_t* entry = nullptr;
+	uint32_t *entry = nullptr, *lists = nullptr, *start_idx = nullptr;
 	mgl_pk *back = nullptr, *dp = nullptr, *res = nullptr, *keep = nullptr;
 	unsigned long long* obj = nullptr;
 	uint64_t* cost = nullptr;
-	hipEvent_t t0 = nullptr, t1 = nullptr;
-	~AdpBufs()
+	AdpVariant* tab = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr, call0 = nullptr, fork = nullptr, join = nullptr;
+	/* results: the last walk's costs and the last DP's objectives, per variant; the stats; the best parse so far */
+	uint64_t h_cost[MGL_SWEEP_MAX], vbest[MGL_SWEEP_MAX], best = ~0ull;
+	unsigned long long h_obj[MGL_SWEEP_MAX];
+	float ms = 0;
+	uint32_t best_v = UINT32_MAX;
+	std::vector<mgl_optimal_stats> st;
+	~Parse()
 	{
-		dfree(snaps); dfree(entry); dfree(back); dfree(dp); dfree(res); dfree(keep); dfree(obj); dfree(cost);
-		if (t0) (void)hipEventDestroy(t0);
-		if (t1) (void)hipEventDestroy(t1);
+		dfree(snaps); dfree(entry); dfree(lists); dfree(start_idx); dfree(back); dfree(dp); dfree(res); dfree(keep);
+		dfree(obj); dfree(cost); dfree(tab);
+		for (hipEvent_t e : { t0, t1, call0, fork, join })
+			if (e) (void)hipEventDestroy(e);
 	}
 };
+
 /* checks and defaults; a chunk or a segment longer than the input acts like one of its length */
 static int adp_args(const mgl_sa* sa, uint32_t cand, uint32_t& chunk, uint32_t& segment, uint32_t& ahead, bool ahead_given)
 {
@@ -1482,322 +1506,208 @@ static int adp_args(const mgl_sa* sa, uint32_t cand, uint32_t& chunk, uint32_t& 
 	if (segment > chunk) segment = chunk;
 	return MGL_OK;
 }
-static int adp_alloc(mgl_sa* sa, AdpBufs& o, uint32_t chunk, bool seed)
-{
-	const size_t n = sa->n, nch = (n + chunk - 1) / chunk;
-	HIPCHK(hipMalloc(&o.snaps, sizeof(uint16_t) * adp_stride(sa->ctx.L) * nch));
-	HIPCHK(hipMalloc(&o.entry, sizeof(uint32_t) * 5 * nch));
-	HIPCHK(hipMalloc(&o.back, sizeof(mgl_pk) * (n + 1)));
-	HIPCHK(hipMalloc(&o.dp, sizeof(mgl_pk) * n));
-	HIPCHK(hipMalloc(&o.obj, sizeof(unsigned long long)));
-	HIPCHK(hipMalloc(&o.cost, sizeof(uint64_t)));
-	if (seed) {
-		HIPCHK(hipMalloc(&o.res, sizeof(mgl_pk) * n));
-		HIPCHK(hipMalloc(&o.keep, sizeof(mgl_pk) * n));
-		HIPCHK(hipEventCreate(&o.t0));
-		HIPCHK(hipEventCreate(&o.t1));
-	}
-	return MGL_OK;
-}
-/* the serial walk: chunk starts of `in` (snaps), its exact cost, and with `out` the resolution of the DP's copies */
-static int adp_snap(mgl_sa* sa, AdpBufs& o, const mgl_pk* in, mgl_pk* out, uint32_t chunk, bool snaps)
-{
-	if (out) hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, out, (uint32_t)sa->n);
-	hipLaunchKernelGGL(k_adp_snap, dim3(1), dim3(64), 0, sa->stream, sa->ctx, in, out, out ? 1 : 0, chunk, o.entry,
-	                   snaps ? o.snaps : (uint16_t*)nullptr, o.cost);
-	HIPCHK(hipGetLastError());
-	return MGL_OK;
-}
-/* one DP pass from the chunk starts in o.snaps / o.entry into o.dp */
-static int adp_dp(mgl_sa* sa, AdpBufs& o, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead)
-{
-	const uint32_t nch = (uint32_t)((sa->n + chunk - 1) / chunk);
-	const uint32_t lds = adp_stride(sa->ctx.L) * (uint32_t)sizeof(uint16_t);
-	const bool mf = sa->mf_finder == MGL_MF_FRONTIER;
-	if (mf) { int rc = mf_ensure(sa, sa->mf_depth); if (rc) return rc; }
-	HIPCHK(hipFuncSetAttribute(mf ? (const void*)k_adp_dp<true> : (const void*)k_adp_dp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.dp, (uint32_t)sa->n);
-	HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long), sa->stream));
-	if (mf) hipLaunchKernelGGL(k_adp_dp<true>, dim3(nch), dim3(64), lds, sa->stream, sa->ctx, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, cand,
-	                           segment, ahead, o.back, o.dp, o.obj, mf_lists(sa));
-	else hipLaunchKernelGGL(k_adp_dp<false>, dim3(nch), dim3(64), lds, sa->stream, sa->ctx, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, cand,
-	                        segment, ahead, o.back, o.dp, o.obj, MfLists{});
-	HIPCHK(hipGetLastError());
-	return MGL_OK;
-}
 
-extern "C" int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead,
-                                 mgl_packet* packets_out, uint64_t* objective)
-{
-	if (!sa || !parse_in || !packets_out) return fail(MGL_EINVAL, "null argument");
-	int rc = adp_args(sa, cand, chunk, segment, ahead, true);
-	if (rc) return rc;
-	HIPCHK(hipSetDevice(sa->device));
-	Control c;
-	if (scratch_walk(sa, parse_in, false, false, &c)) return fail(MGL_ERANGE, "mgl_adaptive_pass: parse_in is not a valid parse of the input");
-	AdpBufs o;
-	if ((rc = adp_alloc(sa, o, chunk, false))) return rc;
-	if ((rc = adp_snap(sa, o, sa->scratch.v.slab, nullptr, chunk, true))) return rc;
-	if ((rc = adp_dp(sa, o, cand, chunk, segment, ahead))) return rc;
-	unsigned long long obj = 0;
-	HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
-	if ((rc = export_slab(sa, o.dp, packets_out))) return rc;
-	if (objective) *objective = obj;
-	return MGL_OK;
-}
-
-extern "C" int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, mgl_optimal_stats* stats)
-{
-	if (!sa) return fail(MGL_EINVAL, "null handle");
-	const uint32_t passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
-	const uint32_t cand = cfg && cfg->cand ? cfg->cand : MGL_OPT_DEF_CAND;
-	uint32_t chunk = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
-	uint32_t segment = cfg ? cfg->segment : 0u, ahead = cfg ? cfg->ahead : 0u;
-	const bool from_current = cfg && cfg->from_current;
-	int rc = adp_args(sa, cand, chunk, segment, ahead, false);
-	if (rc) return rc;
-	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "mgl_sa_seed_adaptive: at most 16 passes");
-	HIPCHK(hipSetDevice(sa->device));
-	mgl_optimal_stats st;
-	memset(&st, 0, sizeof st);
-	AdpBufs o;
-	if ((rc = adp_alloc(sa, o, chunk, true))) return rc;
-	const uint32_t n = (uint32_t)sa->n;
-	/* pass 0's chunk starts: the greedy parse, or the current slab (which then has to be beaten) */
-	const mgl_pk* first = sa->base.v.slab;
-	if (!from_current) {
-		hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.res, cand);
-		HIPCHK(hipGetLastError());
-		first = o.res;
-	}
-	if ((rc = adp_snap(sa, o, first, nullptr, chunk, true))) return rc;
-	HIPCHK(hipMemcpyAsync(&st.greedy_cost, o.cost, sizeof(uint64_t), hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
-	uint64_t best = from_current ? st.greedy_cost : ~0ull;
-	st.best_pass = UINT32_MAX;
-	for (uint32_t p = 0; p < passes; p++) {
-		HIPCHK(hipEventRecord(o.t0, sa->stream));
-		if ((rc = adp_dp(sa, o, cand, chunk, segment, ahead))) return rc;
-		if ((rc = adp_snap(sa, o, o.dp, o.res, chunk, p + 1 < passes))) return rc;
-		unsigned long long obj = 0;
-		HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipMemcpyAsync(&st.cost[p], o.cost, sizeof(uint64_t), hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipEventRecord(o.t1, sa->stream));
-		HIPCHK(hipEventSynchronize(o.t1));
-		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, o.t0, o.t1));
-		st.objective[p] = obj;
-		st.ms[p] = ms;
-		st.passes = p + 1;
-		if (st.cost[p] < best) {
-			best = st.cost[p]; st.best_pass = p;
-			HIPCHK(hipMemcpyAsync(o.keep, o.res, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
-		}
-	}
-	if (st.best_pass != UINT32_MAX) {
-		/* the cheapest parse becomes the current slab, as in mgl_sa_seed_optimal */
-		Control c;
-		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-		if ((rc = keep_best_before_overwrite(sa, c))) return rc;
-		if ((rc = write_ctl(sa, sa->base, &c))) return rc;
-		sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
-		uint64_t built = 0;
-		if ((rc = opt_make_current(sa, o.keep, &built))) return rc;
-		if ((rc = launch_validate(sa))) return rc;
-		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-		if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_adaptive: the seeded slab failed the walk check");
-		if (built != best) return fail(MGL_EDEVICE, "mgl_sa_seed_adaptive: the walk's cost of the seeded slab differs from the rebuild's");
-	}
-	HIPCHK(hipStreamSynchronize(sa->stream));
-	if (stats) *stats = st;
-	return MGL_OK;
-}
-
-/* ---- the sweeps: several variants of the adaptive parse through one launch per stage.  mgl_sa_seed_sweep keeps the cheapest
- * parse as the current slab; mgl_parse_sweep_props gives every variant a triple of its own and hands the cheapest parse out */
-struct SweepBufs {
-	uint16_t* snaps = nullptr;
-	uint32_t *entry = nullptr, *lists = nullptr, *start_idx = nullptr;
-	mgl_pk *back = nullptr, *dp = nullptr, *res = nullptr, *keep = nullptr, *starts = nullptr;
-	unsigned long long* obj = nullptr;
-	uint64_t* cost = nullptr;
-	AdpVariant* tab = nullptr;
-	hipEvent_t t0 = nullptr, t1 = nullptr, call0 = nullptr, call1 = nullptr, fork = nullptr, join = nullptr;
-	~SweepBufs()
-	{
-		dfree(snaps); dfree(entry); dfree(lists); dfree(start_idx); dfree(back); dfree(dp); dfree(res); dfree(keep); dfree(starts);
-		dfree(obj); dfree(cost); dfree(tab);
-		for (hipEvent_t e : { t0, t1, call0, call1, fork, join })
-			if (e) (void)hipEventDestroy(e);
-	}
-};
-/* an allocation of the sweep that does not fit is MGL_ENOMEM, and leaves no error behind for the next launch check */
-#define SWEEP_ALLOC(ptr, bytes)                                                                          \
-	do {                                                                                                 \
-		if (hipMalloc(&(ptr), (bytes)) != hipSuccess) {                                                  \
-			(void)hipGetLastError();                                                                     \
-			return fail(MGL_ENOMEM, "parse sweep: the per-variant buffers do not fit the device"); \
-		}                                                                                                \
-	} while (0)
-
-/* props == nullptr: every variant under the handle's triple, and the winner becomes the current slab (mgl_sa_seed_sweep).
- * Otherwise variant v under props[v]; nothing of the search state is touched and the winner goes to packets_out. */
-static int sweep_run(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, const mgl_properties* props,
-                     size_t nvariants, mgl_optimal_stats* results, uint32_t* best_variant, mgl_packet* packets_out, double* gpu_ms)
+/* Argument checks and the variant table: per variant its settings after the defaults and clamps, its triple (props[v], or the
+ * handle's) and where its snapshots lie; the variants listed by finder; the distinct cands. */
+static int parse_args(const mgl_sa* sa, Parse& P, uint32_t passes, uint32_t chunk, uint32_t depth, bool from_current, bool ahead_given,
+                      const mgl_parse_variant* variants, const mgl_properties* props, size_t nvariants)
 {
 	if (nvariants == 0 || nvariants > MGL_SWEEP_MAX) return fail(MGL_EINVAL, "parse sweep: 1 to 64 variants");
-	const uint32_t passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
-	uint32_t chunk = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
-	const uint32_t depth = cfg && cfg->depth ? cfg->depth : sa->mf_depth;
-	const bool from_current = cfg && cfg->from_current;
 	if (props && from_current) return fail(MGL_EINVAL, "mgl_parse_sweep_props: a current slab has a cost under one triple only; from_current must be 0");
-	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "parse sweep: at most 16 passes");
+	if (passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "adaptive parse: at most 16 passes");
 	if (depth > MGL_MF_MAX_DEPTH) return fail(MGL_EINVAL, "parse sweep: depth must be at most 4096");
-	const uint32_t nv = (uint32_t)nvariants, n = (uint32_t)sa->n;
-	/* per variant: its settings after the defaults and clamps of mgl_sa_seed_adaptive; the greedy parse of its cand */
-	AdpVariant tab[MGL_SWEEP_MAX];
-	uint32_t lists[MGL_SWEEP_MAX], start_idx[MGL_SWEEP_MAX], cands[MGL_SWEEP_MAX], ncand = 0, nnear = 0;
-	for (uint32_t v = 0; v < nv; v++) {
+	P.nv = (uint32_t)nvariants; P.passes = passes; P.depth = depth; P.from_current = from_current;
+	for (uint32_t v = 0; v < P.nv; v++) {
 		if (variants[v].finder != MGL_MF_NEAREST && variants[v].finder != MGL_MF_FRONTIER) return fail(MGL_EINVAL, "parse sweep: unknown finder");
 		if (props && ((uint32_t)props[v].lc + props[v].lp > 4u || props[v].pb > 4u))
 			return fail(MGL_EINVAL, "mgl_parse_sweep_props: supported properties are lc + lp <= 4, pb <= 4");
-		uint32_t ch = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
-		tab[v].cand = variants[v].cand ? variants[v].cand : MGL_OPT_DEF_CAND;
-		tab[v].segment = variants[v].segment; tab[v].ahead = variants[v].ahead;
-		tab[v].props = props ? adp_pack_props(props[v].lc, props[v].lp, props[v].pb) : adp_pack_props(sa->ctx.L.lc, sa->ctx.L.lp, sa->ctx.L.pb);
-		tab[v].snap_off = 0;
-		int rc = adp_args(sa, tab[v].cand, ch, tab[v].segment, tab[v].ahead, false);
+		AdpVariant& t = P.h_tab[v];
+		t.cand = variants[v].cand ? variants[v].cand : MGL_OPT_DEF_CAND;
+		t.segment = variants[v].segment; t.ahead = variants[v].ahead;
+		t.props = props ? adp_pack_props(props[v].lc, props[v].lp, props[v].pb) : adp_pack_props(sa->ctx.L.lc, sa->ctx.L.lp, sa->ctx.L.pb);
+		P.chunk = chunk; /* clamped the same way for every variant */
+		int rc = adp_args(sa, t.cand, P.chunk, t.segment, t.ahead, ahead_given);
 		if (rc) return rc;
-		chunk = ch; /* the same for every variant */
 		uint32_t k = 0;
-		while (k < ncand && cands[k] != tab[v].cand) k++;
-		if (k == ncand) cands[ncand++] = tab[v].cand;
-		start_idx[v] = from_current ? 0u : k;
-		if (variants[v].finder == MGL_MF_NEAREST) lists[nnear++] = v;
+		while (k < P.ncand && P.cands[k] != t.cand) k++;
+		if (k == P.ncand) P.cands[P.ncand++] = t.cand;
+		P.cand_idx[v] = k;
+		if (variants[v].finder == MGL_MF_NEAREST) P.h_lists[P.nnear++] = v;
 	}
-	const uint32_t nfront = nv - nnear;
-	for (uint32_t v = 0, k = nnear; v < nv; v++)
-		if (variants[v].finder == MGL_MF_FRONTIER) lists[k++] = v;
-	HIPCHK(hipSetDevice(sa->device));
-	if (nfront) { int rc = mf_ensure(sa, depth); if (rc) return rc; }
+	P.nfront = P.nv - P.nnear;
+	for (uint32_t v = 0, k = P.nnear; v < P.nv; v++)
+		if (variants[v].finder == MGL_MF_FRONTIER) P.h_lists[k++] = v;
 	/* a variant's snapshots: nch models of its own layout; a launch's dynamic LDS: the largest model among its variants */
-	const size_t nch = ((size_t)n + chunk - 1) / chunk;
-	size_t snap_total = 0;
-	uint32_t lds_near = 0, lds_front = 0;
-	for (uint32_t v = 0; v < nv; v++) {
-		const uint32_t stride = adp_stride(mgl_make_layout(tab[v].props & 0xFFu, (tab[v].props >> 8) & 0xFFu, (tab[v].props >> 16) & 0xFFu));
-		tab[v].snap_off = snap_total;
-		snap_total += nch * stride;
-		uint32_t& lds = variants[v].finder == MGL_MF_FRONTIER ? lds_front : lds_near;
+	P.nch = (uint32_t)(((size_t)sa->n + P.chunk - 1) / P.chunk);
+	for (uint32_t v = 0; v < P.nv; v++) {
+		AdpVariant& t = P.h_tab[v];
+		const uint32_t stride = adp_stride(mgl_make_layout(t.props & 0xFFu, (t.props >> 8) & 0xFFu, (t.props >> 16) & 0xFFu));
+		t.snap_off = P.snap_total;
+		P.snap_total += (size_t)P.nch * stride;
+		uint32_t& lds = variants[v].finder == MGL_MF_FRONTIER ? P.lds_front : P.lds_near;
 		if (stride * (uint32_t)sizeof(uint16_t) > lds) lds = stride * (uint32_t)sizeof(uint16_t);
 	}
-	SweepBufs o;
-	SWEEP_ALLOC(o.snaps, sizeof(uint16_t) * snap_total);
-	SWEEP_ALLOC(o.entry, sizeof(uint32_t) * 5 * nch * nv);
-	SWEEP_ALLOC(o.back, sizeof(mgl_pk) * ((size_t)n + 1) * nv);
-	SWEEP_ALLOC(o.dp, sizeof(mgl_pk) * (size_t)n * nv);
-	SWEEP_ALLOC(o.res, sizeof(mgl_pk) * (size_t)n * nv);
-	SWEEP_ALLOC(o.keep, sizeof(mgl_pk) * (size_t)n);
-	if (!from_current) SWEEP_ALLOC(o.starts, sizeof(mgl_pk) * (size_t)n * ncand);
-	SWEEP_ALLOC(o.obj, sizeof(unsigned long long) * nv);
-	SWEEP_ALLOC(o.cost, sizeof(uint64_t) * nv);
-	SWEEP_ALLOC(o.tab, sizeof(AdpVariant) * nv);
-	SWEEP_ALLOC(o.lists, sizeof(uint32_t) * nv);
-	SWEEP_ALLOC(o.start_idx, sizeof(uint32_t) * nv);
-	for (hipEvent_t* e : { &o.t0, &o.t1, &o.call0, &o.call1, &o.fork, &o.join }) HIPCHK(hipEventCreate(e));
-	if (nnear) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_near));
-	if (nfront) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_front));
-	HIPCHK(hipEventRecord(o.call0, sa->stream));
-	HIPCHK(hipMemcpyAsync(o.tab, tab, sizeof(AdpVariant) * nv, hipMemcpyHostToDevice, sa->stream));
-	HIPCHK(hipMemcpyAsync(o.lists, lists, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
-	HIPCHK(hipMemcpyAsync(o.start_idx, start_idx, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
-	/* pass 0's chunk starts: one greedy parse per distinct cand, or the current slab (which then has to be beaten) */
-	const mgl_pk* first = sa->base.v.slab;
-	if (!from_current) {
-		for (uint32_t k = 0; k < ncand; k++)
-			hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.starts + (size_t)k * n, cands[k]);
-		first = o.starts;
+	return MGL_OK;
+}
+
+/* an allocation that does not fit is MGL_ENOMEM, and leaves no error behind for the next launch check */
+#define PARSE_ALLOC(ptr, bytes)                                                                              \
+	do {                                                                                                     \
+		if (hipMalloc(&(ptr), (bytes)) != hipSuccess) {                                                      \
+			(void)hipGetLastError();                                                                         \
+			return fail(MGL_ENOMEM, "adaptive parse: the per-variant buffers do not fit the device"); \
+		}                                                                                                    \
+	} while (0)
+
+/* The buffers, the frontier's lists if a variant asks for them, the tables on the device.  resolved: the passes' parses are
+ * resolved (res; pass 0's greedy parses lie there first) and the best is kept (keep). */
+static int parse_alloc(mgl_sa* sa, Parse& P, bool resolved)
+{
+	const size_t n = sa->n, nv = P.nv;
+	if (P.nfront) { int rc = mf_ensure(sa, P.depth); if (rc) return rc; }
+	PARSE_ALLOC(P.snaps, sizeof(uint16_t) * P.snap_total);
+	PARSE_ALLOC(P.entry, sizeof(uint32_t) * 5 * P.nch * nv);
+	PARSE_ALLOC(P.back, sizeof(mgl_pk) * (n + 1) * nv);
+	PARSE_ALLOC(P.dp, sizeof(mgl_pk) * n * nv);
+	if (resolved) {
+		PARSE_ALLOC(P.res, sizeof(mgl_pk) * n * nv);
+		PARSE_ALLOC(P.keep, sizeof(mgl_pk) * n);
 	}
-	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)o.tab, first, (const uint32_t*)o.start_idx,
-	                   (mgl_pk*)nullptr, 0, chunk, (uint32_t)nch, o.entry, o.snaps, o.cost);
+	PARSE_ALLOC(P.obj, sizeof(unsigned long long) * nv);
+	PARSE_ALLOC(P.cost, sizeof(uint64_t) * nv);
+	PARSE_ALLOC(P.tab, sizeof(AdpVariant) * nv);
+	PARSE_ALLOC(P.lists, sizeof(uint32_t) * nv);
+	PARSE_ALLOC(P.start_idx, sizeof(uint32_t) * nv);
+	for (hipEvent_t* e : { &P.t0, &P.t1, &P.call0, &P.fork, &P.join }) HIPCHK(hipEventCreate(e));
+	if (P.nnear) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_near));
+	if (P.nfront) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_front));
+	HIPCHK(hipEventRecord(P.call0, sa->stream));
+	HIPCHK(hipMemcpyAsync(P.tab, P.h_tab, sizeof(AdpVariant) * nv, hipMemcpyHostToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(P.lists, P.h_lists, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
+	return MGL_OK;
+}
+
+/* Pass 0's chunk starts and model snapshots, from the walk of `given` (a valid parse on the device) for every variant, or
+ * (nullptr) of one greedy parse per distinct cand.  The walk's cost is the variant's greedy_cost; with from_current it is
+ * what the variant, and the batch, have to beat. */
+static int parse_starts(mgl_sa* sa, Parse& P, const mgl_pk* given)
+{
+	const uint32_t n = (uint32_t)sa->n, nv = P.nv;
+	uint32_t idx[MGL_SWEEP_MAX];
+	for (uint32_t v = 0; v < nv; v++) idx[v] = given ? 0u : P.cand_idx[v];
+	HIPCHK(hipMemcpyAsync(P.start_idx, idx, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
+	if (!given) {
+		for (uint32_t k = 0; k < P.ncand; k++) /* ncand <= nv slabs of res, which no pass has written yet */
+			hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, P.res + (size_t)k * n, P.cands[k]);
+		given = P.res;
+	}
+	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)P.tab, given, (const uint32_t*)P.start_idx,
+	                   (mgl_pk*)nullptr, 0, P.chunk, P.nch, P.entry, P.snaps, P.cost);
 	HIPCHK(hipGetLastError());
-	std::vector<mgl_optimal_stats> st(nv);
-	memset(st.data(), 0, sizeof(mgl_optimal_stats) * nv);
-	uint64_t h_cost[MGL_SWEEP_MAX];
-	unsigned long long h_obj[MGL_SWEEP_MAX];
-	HIPCHK(hipMemcpyAsync(h_cost, o.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->stream));
 	HIPCHK(hipStreamSynchronize(sa->stream));
-	uint64_t vbest[MGL_SWEEP_MAX]; /* what variant v would have to beat on a handle of its own */
+	P.st.assign(nv, mgl_optimal_stats{});
 	for (uint32_t v = 0; v < nv; v++) {
-		st[v].greedy_cost = h_cost[v];
-		st[v].best_pass = UINT32_MAX;
-		vbest[v] = from_current ? h_cost[v] : ~0ull;
+		P.st[v].greedy_cost = P.h_cost[v];
+		P.st[v].best_pass = UINT32_MAX;
+		P.vbest[v] = P.from_current ? P.h_cost[v] : ~0ull;
 	}
-	/* the cheapest (variant, pass): ties to the lower variant, then to the lower pass; with from_current the current slab
-	 * holds every tie */
-	uint64_t best = from_current ? h_cost[0] : ~0ull;
-	uint32_t best_v = UINT32_MAX;
-	for (uint32_t p = 0; p < passes; p++) {
-		HIPCHK(hipEventRecord(o.t0, sa->stream));
-		hipLaunchKernelGGL(k_fill_literal_sweep, dim3(1024), dim3(256), 0, sa->stream, o.dp, (size_t)n * nv);
-		hipLaunchKernelGGL(k_fill_literal_sweep, dim3(1024), dim3(256), 0, sa->stream, o.res, (size_t)n * nv);
-		HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long) * nv, sa->stream));
-		if (nfront) {
-			/* the two instances side by side: the frontier's on the handle's second stream */
-			HIPCHK(hipEventRecord(o.fork, sa->stream));
-			HIPCHK(hipStreamWaitEvent(sa->stream2, o.fork, 0));
-			hipLaunchKernelGGL(k_adp_dp_sweep<true>, dim3((uint32_t)nch, nfront), dim3(64), lds_front, sa->stream2, sa->ctx, (const AdpVariant*)o.tab,
-			                   (const uint32_t*)o.lists + nnear, (uint32_t)nch, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, o.back, o.dp, o.obj,
-			                   mf_lists(sa));
-			HIPCHK(hipEventRecord(o.join, sa->stream2));
-		}
-		if (nnear)
-			hipLaunchKernelGGL(k_adp_dp_sweep<false>, dim3((uint32_t)nch, nnear), dim3(64), lds_near, sa->stream, sa->ctx, (const AdpVariant*)o.tab,
-			                   (const uint32_t*)o.lists, (uint32_t)nch, (const uint32_t*)o.entry, (const uint16_t*)o.snaps, chunk, o.back, o.dp, o.obj,
-			                   MfLists{});
-		if (nfront) HIPCHK(hipStreamWaitEvent(sa->stream, o.join, 0));
-		hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)o.tab, (const mgl_pk*)o.dp,
-		                   (const uint32_t*)nullptr, o.res, 1, chunk, (uint32_t)nch, o.entry, p + 1 < passes ? o.snaps : (uint16_t*)nullptr, o.cost);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(h_obj, o.obj, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipMemcpyAsync(h_cost, o.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipEventRecord(o.t1, sa->stream));
-		HIPCHK(hipEventSynchronize(o.t1));
-		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, o.t0, o.t1));
-		uint32_t keep_v = UINT32_MAX;
-		for (uint32_t v = 0; v < nv; v++) {
-			st[v].cost[p] = h_cost[v]; st[v].objective[p] = h_obj[v]; st[v].ms[p] = ms; st[v].passes = p + 1;
-			if (h_cost[v] < vbest[v]) { vbest[v] = h_cost[v]; st[v].best_pass = p; }
-			if (h_cost[v] < best || (h_cost[v] == best && best_v != UINT32_MAX && v < best_v)) { best = h_cost[v]; best_v = keep_v = v; }
-		}
-		if (keep_v != UINT32_MAX)
-			HIPCHK(hipMemcpyAsync(o.keep, o.res + (size_t)keep_v * n, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
+	P.best = P.from_current ? P.h_cost[0] : ~0ull;
+	return MGL_OK;
+}
+
+/* One DP pass from the chunk starts in entry / snaps into dp: one launch, or with both finders present two side by side,
+ * the frontier's on the handle's second stream */
+static int parse_dp(mgl_sa* sa, Parse& P)
+{
+	const size_t n = sa->n;
+	const bool both = P.nnear && P.nfront;
+	HIPCHK(hipEventRecord(P.t0, sa->stream));
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, P.dp, n * P.nv);
+	HIPCHK(hipMemsetAsync(P.obj, 0, sizeof(unsigned long long) * P.nv, sa->stream));
+	if (both) {
+		HIPCHK(hipEventRecord(P.fork, sa->stream));
+		HIPCHK(hipStreamWaitEvent(sa->stream2, P.fork, 0));
+	}
+	if (P.nfront)
+		hipLaunchKernelGGL(k_adp_dp_sweep<true>, dim3(P.nch, P.nfront), dim3(64), P.lds_front, both ? sa->stream2 : sa->stream, sa->ctx,
+		                   (const AdpVariant*)P.tab, (const uint32_t*)P.lists + P.nnear, P.nch, (const uint32_t*)P.entry, (const uint16_t*)P.snaps, P.chunk,
+		                   P.back, P.dp, P.obj, mf_lists(sa));
+	if (both) HIPCHK(hipEventRecord(P.join, sa->stream2));
+	if (P.nnear)
+		hipLaunchKernelGGL(k_adp_dp_sweep<false>, dim3(P.nch, P.nnear), dim3(64), P.lds_near, sa->stream, sa->ctx, (const AdpVariant*)P.tab,
+		                   (const uint32_t*)P.lists, P.nch, (const uint32_t*)P.entry, (const uint16_t*)P.snaps, P.chunk, P.back, P.dp, P.obj, MfLists{});
+	if (both) HIPCHK(hipStreamWaitEvent(sa->stream, P.join, 0));
+	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+
+/* Resolve and cost: the serial walk of every variant's dp into res, exactly costed, leaving the next pass's chunk starts
+ * (`snaps`: and its model snapshots).  h_cost, h_obj and ms hold the pass afterwards. */
+static int parse_resolve(mgl_sa* sa, Parse& P, bool snaps)
+{
+	const size_t n = sa->n;
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, P.res, n * P.nv);
+	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(P.nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)P.tab, (const mgl_pk*)P.dp,
+	                   (const uint32_t*)nullptr, P.res, 1, P.chunk, P.nch, P.entry, snaps ? P.snaps : (uint16_t*)nullptr, P.cost);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(P.h_obj, P.obj, sizeof(unsigned long long) * P.nv, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * P.nv, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipEventRecord(P.t1, sa->stream));
+	HIPCHK(hipEventSynchronize(P.t1));
+	HIPCHK(hipEventElapsedTime(&P.ms, P.t0, P.t1));
+	return MGL_OK;
+}
+
+/* Pass p's figures into the stats, and the cheapest (variant, pass) so far into keep: ties to the lower variant, then to
+ * the lower pass; with from_current the current slab holds every tie */
+static int parse_keep(mgl_sa* sa, Parse& P, uint32_t p)
+{
+	uint32_t keep_v = UINT32_MAX;
+	for (uint32_t v = 0; v < P.nv; v++) {
+		mgl_optimal_stats& s = P.st[v];
+		const uint64_t cost = P.h_cost[v];
+		s.cost[p] = cost; s.objective[p] = P.h_obj[v]; s.ms[p] = P.ms; s.passes = p + 1;
+		if (cost < P.vbest[v]) { P.vbest[v] = cost; s.best_pass = p; }
+		if (cost < P.best || (cost == P.best && P.best_v != UINT32_MAX && v < P.best_v)) { P.best = cost; P.best_v = keep_v = v; }
+	}
+	if (keep_v != UINT32_MAX)
+		HIPCHK(hipMemcpyAsync(P.keep, P.res + (size_t)keep_v * sa->n, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->stream));
+	return MGL_OK;
+}
+
+/* props == nullptr: every variant under the handle's triple, and the winner becomes the current slab (unless, with
+ * from_current, nothing beat it: the handle is left as it is).  Otherwise variant v under props[v]; nothing of the search
+ * state is touched and the winner goes to packets_out. */
+static int sweep_run(mgl_sa* sa, const char* who, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, const mgl_properties* props,
+                     size_t nvariants, mgl_optimal_stats* results, uint32_t* best_variant, mgl_packet* packets_out, double* gpu_ms)
+{
+	Parse P;
+	int rc = parse_args(sa, P, cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES, cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK,
+	                    cfg && cfg->depth ? cfg->depth : sa->mf_depth, cfg && cfg->from_current, false, variants, props, nvariants);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(sa->device));
+	if ((rc = parse_alloc(sa, P, true))) return rc;
+	if ((rc = parse_starts(sa, P, P.from_current ? sa->base.v.slab : nullptr))) return rc;
+	for (uint32_t p = 0; p < P.passes; p++) {
+		if ((rc = parse_dp(sa, P))) return rc;
+		if ((rc = parse_resolve(sa, P, p + 1 < P.passes))) return rc;
+		if ((rc = parse_keep(sa, P, p))) return rc;
 	}
 	if (props) {
 		/* the handle cannot cost a slab under a foreign triple: the winner is handed out, not made current */
-		if (packets_out) { int rc = export_slab(sa, o.keep, packets_out); if (rc) return rc; }
-	} else if (best_v != UINT32_MAX) {
-		/* the cheapest parse becomes the current slab, as in mgl_sa_seed_adaptive */
-		Control c;
-		int rc;
-		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-		if ((rc = keep_best_before_overwrite(sa, c))) return rc;
-		if ((rc = write_ctl(sa, sa->base, &c))) return rc;
-		sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; /* MGL_ACCEPT_AUTO starts over on a new slab */
+		if (packets_out && (rc = export_slab(sa, P.keep, packets_out))) return rc;
+	} else if (P.best_v != UINT32_MAX) {
 		uint64_t built = 0;
-		if ((rc = opt_make_current(sa, o.keep, &built))) return rc;
-		if ((rc = launch_validate(sa))) return rc;
-		if ((rc = read_ctl(sa, sa->base, &c))) return rc;
-		if (c.error_flags) return fail(MGL_EDEVICE, "mgl_sa_seed_sweep: the seeded slab failed the walk check");
-		if (built != best) return fail(MGL_EDEVICE, "mgl_sa_seed_sweep: the walk's cost of the seeded slab differs from the rebuild's");
+		if ((rc = replace_current(sa, put_slab(sa, P.keep), true, MGL_EDEVICE, who, &built))) return rc;
+		if (built != P.best) return fail(MGL_EDEVICE, std::string(who) + ": the walk's cost of the seeded slab differs from the rebuild's");
 	}
-	HIPCHK(hipEventRecord(o.call1, sa->stream));
-	HIPCHK(hipEventSynchronize(o.call1));
+	HIPCHK(hipEventRecord(P.t1, sa->stream));
+	HIPCHK(hipEventSynchronize(P.t1));
 	float call_ms = 0;
-	HIPCHK(hipEventElapsedTime(&call_ms, o.call0, o.call1));
-	if (results) memcpy(results, st.data(), sizeof(mgl_optimal_stats) * nv);
-	if (best_variant) *best_variant = best_v;
+	HIPCHK(hipEventElapsedTime(&call_ms, P.call0, P.t1));
+	if (results) memcpy(results, P.st.data(), sizeof(mgl_optimal_stats) * P.nv);
+	if (best_variant) *best_variant = P.best_v;
 	if (gpu_ms) *gpu_ms = call_ms;
 	return MGL_OK;
 }
@@ -1806,14 +1716,45 @@ extern "C" int mgl_sa_seed_sweep(mgl_sa* sa, const mgl_parse_sweep_config* cfg, 
                                  mgl_optimal_stats* results, uint32_t* best_variant, double* gpu_ms)
 {
 	if (!sa || !variants) return fail(MGL_EINVAL, "null argument");
-	return sweep_run(sa, cfg, variants, nullptr, nvariants, results, best_variant, nullptr, gpu_ms);
+	return sweep_run(sa, "mgl_sa_seed_sweep", cfg, variants, nullptr, nvariants, results, best_variant, nullptr, gpu_ms);
 }
 
 extern "C" int mgl_parse_sweep_props(mgl_sa* sa, const mgl_parse_sweep_config* cfg, const mgl_parse_variant* variants, const mgl_properties* props,
                                      size_t nvariants, mgl_optimal_stats* results, uint32_t* best_variant, mgl_packet* packets_out, double* gpu_ms)
 {
 	if (!sa || !variants || !props) return fail(MGL_EINVAL, "null argument");
-	return sweep_run(sa, cfg, variants, props, nvariants, results, best_variant, packets_out, gpu_ms);
+	return sweep_run(sa, "mgl_parse_sweep_props", cfg, variants, props, nvariants, results, best_variant, packets_out, gpu_ms);
+}
+
+/* one variant, with the handle's finder and depth */
+extern "C" int mgl_sa_seed_adaptive(mgl_sa* sa, const mgl_adaptive_config* cfg, mgl_optimal_stats* stats)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	const mgl_parse_sweep_config sc = { cfg ? cfg->passes : 0u, cfg ? cfg->chunk : 0u, sa->mf_depth, cfg ? cfg->from_current : 0u };
+	const mgl_parse_variant var = { (uint32_t)sa->mf_finder, cfg ? cfg->cand : 0u, cfg ? cfg->segment : 0u, cfg ? cfg->ahead : 0u };
+	return sweep_run(sa, "mgl_sa_seed_adaptive", &sc, &var, nullptr, 1, stats, nullptr, nullptr, nullptr);
+}
+
+/* one variant and one DP from the starts of the validated scratch slab: neither resolved nor kept */
+extern "C" int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_t cand, uint32_t chunk, uint32_t segment, uint32_t ahead,
+                                 mgl_packet* packets_out, uint64_t* objective)
+{
+	if (!sa || !parse_in || !packets_out) return fail(MGL_EINVAL, "null argument");
+	if (cand == 0) return fail(MGL_EINVAL, "optimal parse: cand must be 1..30");
+	const mgl_parse_variant var = { (uint32_t)sa->mf_finder, cand, segment, ahead };
+	Parse P;
+	int rc = parse_args(sa, P, 1, chunk, sa->mf_depth, false, true, &var, nullptr, 1);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(sa->device));
+	Control c;
+	if (scratch_walk(sa, parse_in, false, false, &c)) return fail(MGL_ERANGE, "mgl_adaptive_pass: parse_in is not a valid parse of the input");
+	if ((rc = parse_alloc(sa, P, false))) return rc;
+	if ((rc = parse_starts(sa, P, sa->scratch.v.slab))) return rc;
+	if ((rc = parse_dp(sa, P))) return rc;
+	HIPCHK(hipMemcpyAsync(P.h_obj, P.obj, sizeof(unsigned long long), hipMemcpyDeviceToHost, sa->stream));
+	if ((rc = export_slab(sa, P.dp, packets_out))) return rc;
+	if (objective) *objective = P.h_obj[0];
+	return MGL_OK;
 }
 
 static hipEvent_t pool_event(mgl_sa* sa, size_t i)
@@ -1826,8 +1767,6 @@ static hipEvent_t pool_event(mgl_sa* sa, size_t i)
 	return sa->ev_pool[i];
 }
 
-/* MGL_ACCEPT_AUTO starts over: a fresh block, bulk steps first (a new slab says nothing about the old one's windows) */
-static void auto_reset(mgl_sa* sa) { sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; }
 extern "C" int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_threshold)
 {
 	if (!sa) return fail(MGL_EINVAL, "null handle");

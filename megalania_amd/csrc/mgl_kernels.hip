@@ -1078,9 +1078,10 @@ __global__ void k_export(const mgl_pk* slab, uint32_t* aos, uint32_t n)
 		aos[3 * i] = mgl_pk_type(p); aos[3 * i + 1] = mgl_pk_dist(p); aos[3 * i + 2] = mgl_pk_len(p);
 	}
 }
-__global__ void k_fill_literal(mgl_pk* slab, uint32_t n)
+/* count: one slab, or the parses' several side by side (above 2^32 entries then) */
+__global__ void k_fill_literal(mgl_pk* slab, size_t count)
 {
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) slab[i] = MGL_PK_LITERAL;
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) slab[i] = MGL_PK_LITERAL;
 }
 
 /* top-K at an arbitrary on-walk position of a (scratch) base; list written worst first */
