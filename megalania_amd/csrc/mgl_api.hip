@@ -105,7 +105,7 @@ struct mgl_sa {
 	/* incremental path (mgl_kernels2.hip) */
 	bool incremental;
 	Base2 b2;
-	unsigned long long* d_prof; /* 16 u64: per-phase cycles + counts, only with MGL_F_PROFILE */
+	unsigned long long* d_prof; /* only with MGL_F_PROFILE: 32 u64 per-phase cycles + counts | K second-half lifetimes | 32 pick stages | K pick lifetimes */
 	uint32_t* d_todo;       /* [0] = count, [1..K] = neighbour indices for the full-walk fallback */
 	uint32_t per_wave2, waves_per_block2, nbr2_lds, build_lds;
 	uint32_t big_waves = MGL_BIG_WAVES; /* wavefronts of a second-pass workgroup (mgl_debug_set key 7 lowers it for tests) */
@@ -474,10 +474,11 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 		for (uint32_t h = 0; h < slices; h++) {
 			const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
 			hipStream_t st = (h & 1u) ? sa->stream2 : sa->stream;
-			hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_PICK>), dim3((j1 - j0 + sa->pick_waves - 1) / sa->pick_waves), dim3(64 * sa->pick_waves),
+			/* under MGL_F_PROFILE the instance that carries the stage marks (tools/pick_waves.py); normal runs hold none of them */
+			hipLaunchKernelGGL((sa->d_prof ? k_neighbours2<false, MGL_NBR_PICK, true> : k_neighbours2<false, MGL_NBR_PICK>), dim3((j1 - j0 + sa->pick_waves - 1) / sa->pick_waves), dim3(64 * sa->pick_waves),
 			                   (MGL_PICK_T_GLOBAL ? 0u : 4096u) + sa->pick_waves * sa->per_wave_pick, st, sa->ctx,
 			                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_pick, sa->d_todo, sa->d_counts,
-			                   (unsigned long long*)nullptr, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICK>");
+			                   sa->d_prof, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICK>");
 			hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_REST>), dim3(j1 - j0), dim3(64), sa->per_wave_rest, st, sa->ctx,
 			                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_rest, sa->d_todo, sa->d_counts,
 			                   g_prof_big ? (unsigned long long*)nullptr : sa->d_prof, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_REST>");
@@ -848,8 +849,8 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 			sa->d_best = sa->snap_best.slab; /* packets_best lives in the best snapshot */
 		}
 		if (sa->cfg.flags & MGL_F_PROFILE) {
-			HIPCHK(hipMalloc(&sa->d_prof, sizeof(unsigned long long) * (32 + K)));
-			HIPCHK(hipMemset(sa->d_prof, 0, sizeof(unsigned long long) * (32 + K)));
+			HIPCHK(hipMalloc(&sa->d_prof, sizeof(unsigned long long) * (64 + 2 * (size_t)K)));
+			HIPCHK(hipMemset(sa->d_prof, 0, sizeof(unsigned long long) * (64 + 2 * (size_t)K)));
 		}
 		HIPCHK(hipMalloc(&sa->d_todo, sizeof(uint32_t) * (K + 1)));
 		HIPCHK(hipMemset(sa->d_todo, 0, sizeof(uint32_t) * (K + 1)));
@@ -961,6 +962,7 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		sa->big.todo_in = sa->d_todo; sa->big.todo_in_count = sa->d_counts; sa->big.spill_ctr = sa->d_counts + 2;
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_REST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES)));
 		HIPCHK(hipMalloc(&sa->d_pickrec, sizeof(uint4) * K));
@@ -2295,7 +2297,7 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 6: src = b.sp_state; sz = sizeof(uint32_t) * 8 * (size_t)sa->n; break;
 	case 7: src = b.ck_probs; sz = sizeof(uint16_t) * (size_t)b.nck * b.ck_elems; break;
 	case 8: src = b.ch_cap; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
-	case 9: src = sa->d_prof; sz = sa->d_prof ? sizeof(unsigned long long) * (32 + sa->cfg.neighbours_per_step) : 0; break;
+	case 9: src = sa->d_prof; sz = sa->d_prof ? sizeof(unsigned long long) * (64 + 2 * (size_t)sa->cfg.neighbours_per_step) : 0; break;
 	case 80: { /* host counters: batch accepts, batch accepts that fell back to the rebuild behind their commit, and those that left the
 	            * step to the rebuild before anything was touched */
 		const uint64_t v[3] = { sa->batch_accepts, sa->batch_fallbacks, sa->batch_early_giveups };

@@ -160,16 +160,160 @@ __device__ __forceinline__ uint32_t nx_lower_bound(const uint16_t* a, uint32_t l
 	return lo;
 }
 
+/* stage clock of the pick half's profile (MGL_F_PROFILE; acc == nullptr in normal runs): cycles and visits per stage, summed
+ * over the picking wavefronts of a launch.  Stages: 0 target, state, mutate decision; 1 the plan (batched set-up); 2 model
+ * load and replay; 3 price tables, literal, short rep; 4 set-up done in place (bounds, ranks, runs, searches, up to each
+ * source's first trip); 5 rep pass; 6, 7 sixteen- and eight-byte scans; 8..13 scans of D = 7..2; 14 draw and record. */
+#define MGL_PICK_STAGES 16u
+struct PickProf {
+	unsigned long long* acc;
+	unsigned long long t;
+};
+__device__ __forceinline__ void pick_prof_mark(PickProf* p, uint32_t stage, uint32_t lane)
+{
+	if (!p || !p->acc) return;
+	const unsigned long long now = __builtin_readcyclecounter();
+	if (lane == 0) { atomicAdd(&p->acc[stage], now - p->t); atomicAdd(&p->acc[MGL_PICK_STAGES + stage], 1ull); }
+	p->t = __builtin_readcyclecounter();
+}
+
+/* ---- the batched set-up of topk_find's sources.
+ * Where a source's entries start and end is a chain of reads of the immutable index: rank[pos] -> run[rank] -> a 64-ary
+ * lower bound over the run, nine such chains per query, and none reads what another found.  Done in place, one behind the
+ * other, they are about forty dependent round trips to memory.  The plan does them level by level -- every chain's loads
+ * of one level are issued together and waited for once -- from the position and the rep distances alone: no model, no price.
+ * So the pick half makes it before it loads the model, and its handful of round trips stand in front of the checkpoint
+ * copy, not behind it.  All fields are wave-uniform (they live in SGPRs). */
+#ifndef MGL_PICK_BATCH
+#define MGL_PICK_BATCH 1 /* 0: the pick half and the probe set their sources up in place, as the one-kernel form does (A/B) */
+#endif
+struct TopkPlan {
+	uint32_t lo, hi;          /* the bigram bucket's entries inside the scan window */
+	uint32_t wmin;            /* a hit lies at a position >= wmin (below) */
+	uint32_t r16, l16, r8, l8; /* own rank and first entry inside the window: sixteen- and eight-byte orders */
+	uint32_t top[5], low[5];  /* the same for the exact-length orders D = 3..7 (index D - 3) */
+	uint32_t rep;             /* byte k: bytes (of the first 64, capped by the longest match) the source of rep distance k shares with the target */
+	uint64_t x0, x8, x16;     /* the target's bytes 0..23 */
+};
+/* Window floor.  The scan window is the bucket's entries [lo, hi): those at positions in [pos - dict_limit, pos), of which a
+ * scan cap (max_scan) keeps the nearest.  An entry q < pos of a D-byte run (or a rep source that carries the bigram) is a
+ * bucket entry, and the bucket ascends, so q >= bucket_pos[lo] <=> q >= pos - dict_limit as long as no cap cuts: the runs'
+ * searches then need no bucket_pos[lo] and go in lock step with the bucket's.  With a cap they wait for it (second pass). */
+__device__ __forceinline__ void topk_plan_make(TopkPlan& p, const DevCtx& c, const mgl_wstate& st, uint32_t lane)
+{
+	const uint32_t pos = st.pos;
+	p.lo = p.hi = p.wmin = p.r16 = p.l16 = p.r8 = p.l8 = p.rep = 0;
+#pragma unroll
+	for (uint32_t i = 0; i < 5; i++) p.top[i] = p.low[i] = 0;
+	p.x0 = p.x8 = p.x16 = 0;
+	if (pos == 0 || pos >= c.n - 1) return; /* no match starts here: topk_find returns before it looks */
+	const uint32_t maxlen = (c.n - pos) < MGL_MAX_MATCH ? (c.n - pos) : MGL_MAX_MATCH;
+	/* level 0: the target's bytes, the first 64 bytes of the four rep sources, and the seven ranks (a lane per table) */
+	const uint32_t* rt = lane == 0 ? c.oct_rank : lane == 1 ? c.hex_rank : lane == 2 ? c.xrank[1] : lane == 3 ? c.xrank[2] :
+	                     lane == 4 ? c.xrank[3] : lane == 5 ? c.xrank[4] : c.xrank[5];
+	uint32_t rk = 0;
+	if (lane < 7) rk = rt[pos];
+	uint64_t xw = 0;
+	if (lane < 3) __builtin_memcpy(&xw, c.data + pos + 8u * lane, 8); /* the input has 64 bytes of zero padding */
+	const uint32_t pv = c.data[pos + lane];
+	uint32_t qv[4];
+#pragma unroll
+	for (uint32_t k = 0; k < 4; k++) {
+		const uint32_t dk = mgl_dist_at(&st, k);
+		qv[k] = dk < pos ? (uint32_t)c.data[pos - dk - 1u + lane] : 0x100u;
+	}
+#pragma unroll
+	for (uint32_t k = 0; k < 4; k++) {
+		if (mgl_dist_at(&st, k) >= pos) continue;
+		const unsigned long long m = __ballot(lane >= maxlen || qv[k] != pv);
+		p.rep |= (m ? (uint32_t)__ffsll((long long)m) - 1u : 64u) << (8u * k);
+	}
+	p.x0 = rdlane64(xw, 0); p.x8 = rdlane64(xw, 1); p.x16 = rdlane64(xw, 2);
+	p.r8 = rdlane(rk, 0); p.r16 = rdlane(rk, 1);
+#pragma unroll
+	for (uint32_t i = 0; i < 5; i++) p.top[i] = rdlane(rk, 2u + i);
+	/* level 1: the bucket's bounds and the seven run starts */
+	const uint32_t bigram = (((uint32_t)p.x0 & 0xFFu) << 8) | (((uint32_t)p.x0 >> 8) & 0xFFu);
+	const uint32_t* st1 = lane < 2 ? c.bucket_off : lane == 2 ? c.oct_run : lane == 3 ? c.hex_run : lane == 4 ? c.xrun[1] :
+	                      lane == 5 ? c.xrun[2] : lane == 6 ? c.xrun[3] : lane == 7 ? c.xrun[4] : c.xrun[5];
+	const uint32_t i1 = lane < 2 ? bigram + lane : lane == 2 ? p.r8 : lane == 3 ? p.r16 : lane == 4 ? p.top[0] :
+	                    lane == 5 ? p.top[1] : lane == 6 ? p.top[2] : lane == 7 ? p.top[3] : p.top[4];
+	uint32_t s1 = 0;
+	if (lane < 9) s1 = st1[i1];
+	const uint32_t off0 = rdlane(s1, 0), off1 = rdlane(s1, 1);
+	/* levels 2..: nine lower bounds in lock step.  0: the bucket's end (entries < pos); 1: its start (entries >= the floor; the
+	 * same index over [off0, off1) as over [off0, end), the floor being below pos); 2, 3: eight- and sixteen-byte runs; 4..8: D = 3..7 */
+	const uint32_t floor = pos > c.dict_limit ? pos - c.dict_limit : 0u;
+	const uint32_t* const tab[9] = { c.bucket_pos, c.bucket_pos, c.oct_pos, c.hex_pos, c.xpos[1], c.xpos[2], c.xpos[3], c.xpos[4], c.xpos[5] };
+	uint32_t a[9], b[9];
+	a[0] = a[1] = off0; b[0] = b[1] = off1;
+	a[2] = rdlane(s1, 2); b[2] = p.r8;
+	a[3] = rdlane(s1, 3); b[3] = p.r16;
+#pragma unroll
+	for (uint32_t i = 0; i < 5; i++) { a[4u + i] = rdlane(s1, 4u + i); b[4u + i] = p.top[i]; }
+	const bool capped = c.max_scan != 0;
+	uint32_t xlow = floor;
+	/* a floor of 0 admits every entry: those searches have their answer */
+	uint32_t on = capped ? 0x003u : (floor != 0 ? 0x1FFu : 0x001u);
+	if (floor == 0) on &= ~2u;
+#pragma nounroll
+	for (uint32_t pass = 0; pass < 2; pass++) {
+		if (pass == 1) {
+			if (!capped) break;
+			/* the cap cuts inside the window: the runs are searched for the first position the cap leaves */
+			p.hi = a[0]; p.lo = floor != 0 ? a[1] : off0;
+			if (p.hi - p.lo > c.max_scan) p.lo = p.hi - c.max_scan;
+			if (p.hi == p.lo) return; /* no hit: topk_find returns before it looks at the rest */
+			xlow = uni(c.bucket_pos[p.lo]);
+			on = 0x1FCu;
+		}
+		for (;;) {
+			uint32_t v[9];
+			bool any = false;
+#pragma unroll
+			for (uint32_t s = 0; s < 9; s++) {
+				v[s] = 0xFFFFFFFFu;
+				if (!((on >> s) & 1u) || b[s] <= a[s]) continue;
+				any = true;
+				const uint32_t idx = a[s] + lane * ((b[s] - a[s] + 63u) / 64u);
+				if (idx < b[s]) v[s] = tab[s][idx];
+			}
+			if (!any) break;
+#pragma unroll
+			for (uint32_t s = 0; s < 9; s++) {
+				if (!((on >> s) & 1u) || b[s] <= a[s]) continue;
+				const uint32_t step = (b[s] - a[s] + 63u) / 64u;
+				const unsigned long long m = __ballot(v[s] >= (s == 0 ? pos : xlow)); /* a probe past the end holds ~0 */
+				const int f = m ? __ffsll((long long)m) - 1 : 64;
+				if (f == 0) { b[s] = a[s]; continue; } /* the answer is a */
+				const uint32_t na = a[s] + (uint32_t)(f - 1) * step + 1u;
+				uint32_t nb = a[s] + (uint32_t)f * step;
+				if (nb > b[s]) nb = b[s];
+				a[s] = na; b[s] = nb;
+			}
+		}
+	}
+	if (!capped) { p.hi = a[0]; p.lo = floor != 0 ? a[1] : off0; }
+	p.wmin = xlow;
+	p.l8 = a[2]; p.l16 = a[3];
+#pragma unroll
+	for (uint32_t i = 0; i < 5; i++) p.low[i] = a[4u + i];
+}
+
 /* top_k_packet_finder_find (top_k_packet_finder.c:120-125): enumerate every legal next
  * packet at the walk's state, cost each from the adapted model (cost = perplexity/length,
  * :115-116), keep the k best.  Order-independent ("canonical") selection: better = lower
  * cost, then later in the reference's enumeration order (the reference's `<=`, :89).
  * lencost: LDS scratch, 2 x 272 u32.
  * W: entries a lane takes per trip through the exact-length sources (4 where registers allow: the pick kernel; 1 in the
- * one-kernel form, which has none to spare). */
-template <int W>
+ * one-kernel form, which has none to spare).
+ * BATCH: the sources' bounds come from `plan` (topk_plan_make at this position and these rep distances) instead of being
+ * searched for in place; the kernels that run at 256 VGPRs keep the in-place form, a plan held across their model load
+ * would only add to their spills.
+ * PROF: the stage marks of the pick half's profile are compiled in (`pp`: its clock); the kernels of normal runs hold none. */
+template <int W, bool BATCH = false, bool PROF = false>
 __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_t* probs, const uint16_t* T,
-                          uint32_t* lencost, mgl_pk incumbent, uint32_t lane)
+                          uint32_t* lencost, mgl_pk incumbent, uint32_t lane, const TopkPlan* plan = nullptr, PickProf* pp = nullptr)
 {
 	const uint32_t pos = w.st.pos;
 	const uint32_t state = w.st.ctx_state;
@@ -270,16 +414,23 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 	if (c.diag_stop == 32) return;
 	/* substring_enumerator.c:85-105: nothing at the first and the last byte */
 	if (pos == 0 || pos >= c.n - 1) return;
-	const uint32_t bigram = ((uint32_t)walk_byte_at(w, pos) << 8) | c.data[pos + 1];
-	uint32_t lo = c.bucket_off[bigram];
-	const uint32_t end = c.bucket_off[bigram + 1];
-	const uint32_t hi = bucket_lower_bound(c.bucket_pos, lo, end, pos, lane); /* hits are < pos */
-	if (pos > c.dict_limit) lo = bucket_lower_bound(c.bucket_pos, lo, hi, pos - c.dict_limit, lane);
-	if (c.max_scan && hi - lo > c.max_scan) lo = hi - c.max_scan;
+	if (PROF) pick_prof_mark(pp, 3, lane); /* price tables, literal, short rep */
+	uint32_t lo, hi, bigram = 0;
+	if (BATCH) { lo = plan->lo; hi = plan->hi; }
+	else {
+		bigram = ((uint32_t)walk_byte_at(w, pos) << 8) | c.data[pos + 1];
+		lo = c.bucket_off[bigram];
+		const uint32_t end = c.bucket_off[bigram + 1];
+		hi = bucket_lower_bound(c.bucket_pos, lo, end, pos, lane); /* hits are < pos */
+		if (pos > c.dict_limit) lo = bucket_lower_bound(c.bucket_pos, lo, hi, pos - c.dict_limit, lane);
+		if (c.max_scan && hi - lo > c.max_scan) lo = hi - c.max_scan;
+	}
 	const uint32_t nhits = hi - lo;
-	if (c.diag_stop == 33) { t.count += nhits & 1u; return; }
+	if (c.diag_stop == 33) { t.count += nhits & 1u; return; } /* with a plan, stops 33 and 34 fall inside the batch: "set-up done" */
 	if (nhits == 0) return;
-	const uint32_t wpos = c.bucket_pos[lo]; /* the scan window: hits at positions [wpos, pos) */
+	/* the scan window: hits at positions [wpos, pos) (with a plan: its floor, which admits the same entries) */
+	const uint32_t wpos = BATCH ? plan->wmin : c.bucket_pos[lo];
+	if (PROF) pick_prof_mark(pp, 4, lane); /* set-up */
 	const uint32_t maxlen = (c.n - pos) < MGL_MAX_MATCH ? (c.n - pos) : MGL_MAX_MATCH;
 	const uint32_t inc_type = mgl_pk_type(incumbent), inc_len = mgl_pk_len(incumbent), inc_dist = mgl_pk_dist(incumbent);
 
@@ -313,10 +464,12 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 			const uint32_t dk = mgl_dist_at(&w.st, k);
 			if (dk >= pos) continue;
 			const uint32_t q = pos - dk - 1u;
-			if (q < wpos || c.data[q] != b0 || c.data[q + 1] != b1) continue;
+			/* with a plan the first 64 bytes of all four are compared already (they carry the bigram when two or more agree) */
+			const uint32_t L0 = BATCH ? (plan->rep >> (8u * k)) & 0xFFu : 0u;
+			if (BATCH ? (q < wpos || L0 < 2u) : (q < wpos || c.data[q] != b0 || c.data[q + 1] != b1)) continue;
 			/* match length, substring_enumerator.c:99-103: 64 bytes per trip */
-			uint32_t L = maxlen;
-			for (uint32_t base = 0; base < maxlen; base += 64) {
+			uint32_t L = (BATCH && L0 < 64u) ? L0 : maxlen;
+			for (uint32_t base = BATCH ? (L0 < 64u ? maxlen : 64u) : 0u; base < maxlen; base += 64) {
 				const uint32_t i = base + lane;
 				const bool stop = i >= maxlen || c.data[q + i] != c.data[pos + i];
 				const unsigned long long m = __ballot(stop);
@@ -355,13 +508,19 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 	 * Inside a source the price only grows with the distance slot, and the lengths are capped by the next source's
 	 * prefix: a scan stops at the first batch whose nearest entry cannot reach the K-th best any more even at the
 	 * cheapest length up to that cap and the cheapest slot from there on (a true lower bound: the selection stays exact). */
+	if (PROF) pick_prof_mark(pp, 5, lane); /* rep pass */
 	uint64_t x8, x16, x0;
-	__builtin_memcpy(&x0, c.data + pos, 8); /* bytes 0..7: byte D is what separates source D from source D + 1 */
-	__builtin_memcpy(&x8, c.data + pos + 8, 8);
-	__builtin_memcpy(&x16, c.data + pos + 16, 8);
-	const uint32_t r8 = c.oct_rank[pos], r16 = c.hex_rank[pos];
-	const uint32_t l8 = bucket_lower_bound(c.oct_pos, c.oct_run[r8], r8, wpos, lane);
-	const uint32_t l16 = bucket_lower_bound(c.hex_pos, c.hex_run[r16], r16, wpos, lane);
+	uint32_t r8, r16, l8, l16;
+	if (BATCH) { x0 = plan->x0; x8 = plan->x8; x16 = plan->x16; r8 = plan->r8; r16 = plan->r16; l8 = plan->l8; l16 = plan->l16; }
+	else {
+		__builtin_memcpy(&x0, c.data + pos, 8); /* bytes 0..7: byte D is what separates source D from source D + 1 */
+		__builtin_memcpy(&x8, c.data + pos + 8, 8);
+		__builtin_memcpy(&x16, c.data + pos + 16, 8);
+		r8 = c.oct_rank[pos]; r16 = c.hex_rank[pos];
+		l8 = bucket_lower_bound(c.oct_pos, c.oct_run[r8], r8, wpos, lane);
+		l16 = bucket_lower_bound(c.hex_pos, c.hex_run[r16], r16, wpos, lane);
+	}
+	if (PROF) pick_prof_mark(pp, 4, lane); /* set-up */
 	if (c.diag_stop == 35) return; /* diagnostic stops: 34 = before the rep pass (below), 35 = after it, 36..38 = after source 0..2 */
 	/* cheapest match-length price up to the eight-byte source's cap (lengths 2..17 are priced by now) */
 	uint32_t min15;
@@ -476,6 +635,7 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 			}
 			price_hits(cq, L, have);
 		}
+		if (PROF) pick_prof_mark(pp, 6 + ph, lane); /* scan of the sixteen- / eight-byte source */
 	}
 	if (c.diag_stop == 36 || c.diag_stop == 37) return;
 
@@ -494,11 +654,16 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 		const uint8_t* snxb = c.xnxb[li];
 		uint32_t top, low;
 		if (D == 2) { top = hi; low = lo; }
-		else {
+		else if (BATCH) {
+			/* plan->top[D - 3] without indexing the plan by a variable (it lives in registers) */
+			top = D == 7 ? plan->top[4] : D == 6 ? plan->top[3] : D == 5 ? plan->top[2] : D == 4 ? plan->top[1] : plan->top[0];
+			low = D == 7 ? plan->low[4] : D == 6 ? plan->low[3] : D == 5 ? plan->low[2] : D == 4 ? plan->low[1] : plan->low[0];
+		} else {
 			top = c.xrank[li][pos];
 			low = bucket_lower_bound(spos, c.xrun[li][top], top, wpos, lane);
 		}
 		const uint32_t cnt = top - low;
+		if (PROF && cnt == 0) pick_prof_mark(pp, 4, lane); /* set-up */
 		if (cnt == 0) continue;
 		const uint32_t xb = (uint32_t)(x0 >> (8u * D)) & 0xFFu; /* our byte D (D = 7: byte 7 is the top byte of x0) */
 		const uint32_t hitlen = D < maxlen ? D : maxlen;
@@ -548,6 +713,7 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 		uint32_t qa[W], qb[W], ya, yb = 0;
 #pragma unroll
 		for (uint32_t r = 0; r < (uint32_t)W; r++) qb[r] = 0;
+		if (PROF) pick_prof_mark(pp, 4, lane); /* set-up: up to this source's first trip */
 		loadw(0, qa, ya);
 		for (uint32_t hb = 0; hb < cnt; hb += 64u * W) {
 			if (hb + 64u * W < cnt) loadw(hb + 64u * W, qb, yb); /* the next trip, in flight */
@@ -577,6 +743,7 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 			for (uint32_t r = 0; r < (uint32_t)W; r++) qa[r] = qb[r];
 			ya = yb;
 		}
+		if (PROF) pick_prof_mark(pp, 6u + (9u - D), lane); /* scans of D = 7..2: stages 8..13 */
 	}
 }
 
@@ -734,12 +901,13 @@ struct NbrRng { uint64_t key; uint32_t n; };
 __device__ __forceinline__ uint32_t nbr_draw(NbrRng& r) { return mgl_rng_draw(r.key, r.n++); }
 
 /* packet_slab_neighbour.c:56-72 with the canonical top-K order */
-template <int W>
+template <int W, bool BATCH = false, bool PROF = false>
 __device__ bool pick_from_top_k(const DevCtx& c, const Walk& w, const uint16_t* probs, const uint16_t* T, uint32_t* lencost,
-                                mgl_pk incumbent, bool best, NbrRng& rng, uint32_t lane, mgl_pk* picked)
+                                mgl_pk incumbent, bool best, NbrRng& rng, uint32_t lane, mgl_pk* picked,
+                                const TopkPlan* plan = nullptr, PickProf* pp = nullptr)
 {
 	TopK t;
-	topk_find<W>(t, c, w, probs, T, lencost, incumbent, lane);
+	topk_find<W, BATCH, PROF>(t, c, w, probs, T, lencost, incumbent, lane, plan, pp);
 	const uint32_t count = t.count;
 	if (count == 0) return false;
 	uint32_t choice = nbr_draw(rng) % count; /* :48-54 max of 8 draws */
@@ -1108,7 +1276,9 @@ __global__ void __launch_bounds__(64) k_topk_probe(DevCtx c, BaseView b, uint32_
 	}
 	walk_window(w, c, b.slab, lane);
 	TopK t;
-	topk_find<4>(t, c, w, probs, T, lencost, walk_slab_at(w, position), lane);
+	TopkPlan plan;
+	if (MGL_PICK_BATCH) topk_plan_make(plan, c, w.st, lane);
+	topk_find<4, MGL_PICK_BATCH != 0>(t, c, w, probs, T, lencost, walk_slab_at(w, position), lane, &plan);
 	if (lane < t.count) {
 		const uint32_t o = t.count - 1 - lane; /* worst first */
 		out_pk[o] = topk_packet(t.key, position);

@@ -797,7 +797,7 @@ __device__ __forceinline__ void coop_helpers(const DevCtx& c, const Base2& b, co
 }
 /* one neighbour, by the wavefront `wid` of its workgroup; `unit` = the neighbour's index in this launch's slice
  * (regular launch) or its slot in the second pass's list (BIG) */
-template <bool BIG, int MODE>
+template <bool BIG, int MODE, bool PROF = false>
 __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Control* ctl, uint64_t seed,
                                          uint64_t step_override, uint32_t K, const NbrOut& out, uint32_t per_wave_bytes,
                                          uint32_t* todo, uint32_t* todo_count, unsigned long long* prof_acc,
@@ -904,9 +904,13 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 			pickstate[2u * j + 1u] = make_uint4(nb.dists[1], nb.dists[2], nb.dists[3], 0u);
 		}
 	}
+	/* the pick half keeps its own stage clock (PickProf: stages behind the second half's lifetimes in the profile buffer) */
 	Prof prof;
-	prof_start(prof, prof_acc);
-	ch.dbg = prof_acc;
+	prof_start(prof, MODE == MGL_NBR_PICK ? nullptr : prof_acc);
+	ch.dbg = MODE == MGL_NBR_PICK ? nullptr : prof_acc;
+	PickProf pp; /* PROF: the pick half's profiled instance, launched only under MGL_F_PROFILE */
+	pp.acc = PROF ? prof_acc + 32u + K : nullptr;
+	pp.t = t_begin;
 	ch.diag = c.diag_stop;
 	const uint32_t pos = target;
 	mgl_wstate bs = nb;                               /* base's walk state */
@@ -945,6 +949,14 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	enum { P_MODEL, P_SIM, P_TOPK, P_WALK, P_OUT };
 	uint32_t phase = mutated ? P_WALK : P_MODEL;
 	if (MODE == MGL_NBR_PICK && mutated) return; /* nothing to pick: the second half redoes the grow/shrink itself */
+	/* where the pick's sources start and end depends on the target and the rep distances alone: searched for here, all
+	 * sources level by level, in front of the model load instead of source by source behind it */
+	TopkPlan plan;
+	if (MODE == MGL_NBR_PICK) {
+		if (PROF) pick_prof_mark(&pp, 0, lane);
+		if (MGL_PICK_BATCH) topk_plan_make(plan, c, nb, lane);
+		if (PROF) pick_prof_mark(&pp, 1, lane);
+	}
 	if (MODE == MGL_NBR_REST && c.diag_stop != 0 && c.diag_stop != 4 && c.diag_stop < 40) return; /* diagnostic stops of the first half */
 	/* pending top-K request */
 	bool pick_is_mutation = !mutated;
@@ -1028,6 +1040,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 				spilled = true;
 			}
 			model_load(c, b, probs, T, pick_pos, lane);
+			if (PROF) pick_prof_mark(&pp, 2, lane);
 			if (!pick_is_mutation) prof_mark(prof, 5, lane); /* repair: base model at the pick position */
 			if (pick_is_mutation) {
 				prof_mark(prof, 1, lane); /* model at target */
@@ -1063,9 +1076,13 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 			walk_from_state(tw, nb);
 			walk_window(tw, c, b.slab, lane);
 			mgl_pk picked;
-			const bool ok = pick_from_top_k<(MODE == MGL_NBR_PICK ? 4 : 1)>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked);
+			bool ok;
+			if constexpr (MODE == MGL_NBR_PICK) ok = pick_from_top_k<4, MGL_PICK_BATCH != 0, PROF>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked, &plan, &pp);
+			else ok = pick_from_top_k<1>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked);
 			if (MODE == MGL_NBR_PICK) {
 				if (lane == 0) pickrec[j] = make_uint4((uint32_t)picked, (uint32_t)(picked >> 32), rng.n, ok ? 1u : 0u);
+				if (PROF) pick_prof_mark(&pp, 14, lane);
+				if (PROF && pp.acc && lane == 0) pp.acc[2u * MGL_PICK_STAGES + j] = __builtin_readcyclecounter() - t_begin; /* a picking wavefront's lifetime */
 				return;
 			}
 			if (pick_is_mutation) {
@@ -1304,7 +1321,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		                   ((unsigned long long)((ch.n_ins + ch.n_rem) & 0xFFFu) << 40) | ((unsigned long long)(walked & 0xFFFu) << 52);
 }
 
-template <bool BIG, int MODE>
+template <bool BIG, int MODE, bool PROF = false>
 __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_BIG_WAVES : 64)), (MODE == MGL_NBR_FULL ? (BIG ? 1 : MGL_NBR_WAVES_PER_SIMD) : (MODE == MGL_NBR_REST ? MGL_REST_WAVES_PER_SIMD : 4))) k_neighbours2(DevCtx c, Base2 b, Control* ctl, uint64_t seed,
                                                      uint64_t step_override, uint32_t K, NbrOut out, uint32_t per_wave_bytes,
                                                      uint32_t* todo, uint32_t* todo_count, unsigned long long* prof_acc,
@@ -1334,11 +1351,11 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_
 		if (wid != 0) { coop_helpers(c, b, big, prof_acc, smem, per_wave_bytes, T, lane, wid); return; }
 		const uint32_t n = *big.todo_in_count;
 		for (uint32_t unit = blockIdx.x; unit < n; unit += gridDim.x)
-			nbr2_one<BIG, MODE>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T, unit, lane, 0u);
+			nbr2_one<BIG, MODE, PROF>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T, unit, lane, 0u);
 		if (lane == 0) { CoopCmd* cmd = coop_cmd(smem, per_wave_bytes); cmd->op = MGL_COOP_EXIT; cmd->gen = cmd->gen + 1u; }
 		__syncthreads(); /* A, for the last time: the helpers leave */
 	} else {
-		nbr2_one<BIG, MODE>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T,
+		nbr2_one<BIG, MODE, PROF>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T,
 		                    blockIdx.x * waves + wid, lane, wid);
 	}
 }
