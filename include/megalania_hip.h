@@ -25,6 +25,9 @@
  *   mgl_sa_destroy    main.c:107-108,121 the matching frees
  *   mgl_props_sweep   no reference counterpart (lc = lp = pb = 0 are fixed there, main.c:45): one parse costed
  *                                    under every supported lc/lp/pb at once
+ *   mgl_crossover, mgl_sa_cross_best, mgl_sa_exchange_cross
+ *                     no reference counterpart (the reference runs one chain): several valid parses recombined region
+ *                                    by region between the positions where their walks agree
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -329,6 +332,42 @@ int mgl_comm_world(const mgl_comm* comm);
  * winner_rank / winner_cost (nullable) receive the outcome; cost 0 = no chain has a best slab yet.
  * Collective: every rank of the communicator must call it. */
 int mgl_sa_exchange_best(mgl_sa* sa, mgl_comm* comm, int* winner_rank, uint64_t* winner_cost);
+/* Crossover of parses (no reference counterpart; DESIGN.md section 10, megalania_amd/csrc/mgl_crossover.hip).  Every parent
+ * (n entries, position-indexed, a valid parse) is walked from position 0 with the LZMA initial state and a fresh model under
+ * the handle's lc/lp/pb.  A position q is a joint if q = 0, q = n, or every parent starts a packet at q in the same walk state
+ * (ctx_state and the four rep distances).  Boundaries: with grain <= 1 every joint; with grain g > 1 the joints that are the
+ * first joint >= m g for some m >= 0, and n (a set: no boundary depends on an earlier one).  Between consecutive boundaries
+ * b < b' the child takes, entry for entry (stale off-walk entries included), the parent whose packets starting in [b, b')
+ * cost least along its own walk, ties to the lowest parent.  The child is a valid parse by construction; it can cost more
+ * than its best parent, so it is costed exactly.  grain 0 = 64.
+ * MGL_EINVAL: a null handle, parents or parent, fewer than 2 or more than MGL_XO_MAX_PARENTS parents; a parent that
+ * mgl_cost_slab refuses is refused with mgl_cost_slab's code.  MGL_ENOMEM, with the handle left usable: the call's buffers
+ * (about 36 bytes per input byte and parent, allocated per call and freed) do not fit the device. */
+#define MGL_XO_MAX_PARENTS 8
+typedef struct {
+	uint32_t parents, grain;            /* as used (grain 0 -> 64) */
+	uint64_t parent_cost[MGL_XO_MAX_PARENTS]; /* exact cost of each parent */
+	uint64_t child_cost;                /* exact cost of the child */
+	uint64_t predicted;                 /* sum over the regions of the winner's cost there (diagnostic: the child's model adapts
+	                                     * along a mixed history, so its real cost differs) */
+	uint64_t boundaries;                /* boundaries, 0 and n included: one more than there are regions */
+	uint64_t regions_from[MGL_XO_MAX_PARENTS]; /* regions taken from each parent */
+	uint32_t adopted;                   /* mgl_sa_cross_best / exchange: 0 own best kept, 1 the other slab adopted, 2 the child adopted */
+	double gpu_ms;                      /* device time: walks, joints, boundaries, winners, scatter, the child's walk */
+} mgl_cross_stats;
+/* parity hook: SA state untouched; child_out (n entries) nullable */
+int mgl_crossover(mgl_sa* sa, const mgl_packet* const* parents, size_t nparents, uint32_t grain, mgl_packet* child_out,
+                  mgl_cross_stats* stats);
+/* parents = (the handle's best slab, other).  Child strictly cheaper than both: it becomes the best slab at its exact cost (verified,
+ * not "unverified");  else other strictly cheaper than the best: adopted as mgl_sa_set_best does;  else nothing changes.  No best slab
+ * yet: other is adopted (stats: parents 0, nothing was crossed; parent_cost[1] its cost).  The current slab and the run state are untouched
+ * (mgl_sa_begin_epoch(.., from_best) continues from the new best slab). */
+int mgl_sa_cross_best(mgl_sa* sa, const mgl_packet* other, uint32_t grain, mgl_cross_stats* stats);
+/* mgl_sa_exchange_best's two collectives (min of cost << 8 | rank, broadcast of the winner's packed slab), then on every rank but the
+ * winner mgl_sa_cross_best against the received slab, device to device.  Ranks may hold different best slabs afterwards, each no
+ * dearer than the winner's.  What a rank adopts here came from a peer and is checked against the input when an epoch first starts
+ * from it, as after mgl_sa_exchange_best.  stats (nullable): this rank's crossing; all zero on the winner.  Collective. */
+int mgl_sa_exchange_cross(mgl_sa* sa, mgl_comm* comm, uint32_t grain, int* winner_rank, uint64_t* winner_cost, mgl_cross_stats* stats);
 /* The same hand-over through host memory in the packed device form (dist | len << 32 | type << 48, 8 bytes
  * per position), for transports other than RCCL.  Adopting does not verify; see mgl_sa_exchange_best. */
 int mgl_sa_best_packed(mgl_sa* sa, uint64_t* packed_out, uint64_t* perplexity_out);

@@ -37,6 +37,7 @@ HIP_SYMBOLS = [
     "mgl_substrings", "mgl_neighbours", "mgl_rng_draw_at", "mgl_debug_dump", "mgl_debug_set",
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep", "mgl_parse_sweep_props",
+    "mgl_crossover", "mgl_sa_cross_best", "mgl_sa_exchange_cross",
 ]
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
@@ -122,6 +123,21 @@ class PropsCost(C.Structure):
     _fields_ = [("props", Properties), ("cost", C.c_uint64)]
 
 
+XO_MAX_PARENTS = 8
+
+
+class CrossStats(C.Structure):
+    _fields_ = [("parents", C.c_uint32), ("grain", C.c_uint32), ("parent_cost", C.c_uint64 * XO_MAX_PARENTS),
+                ("child_cost", C.c_uint64), ("predicted", C.c_uint64), ("boundaries", C.c_uint64),
+                ("regions_from", C.c_uint64 * XO_MAX_PARENTS), ("adopted", C.c_uint32), ("gpu_ms", C.c_double)]
+
+    def asdict(self):
+        k = self.parents
+        return dict(parents=k, grain=self.grain, parent_cost=list(self.parent_cost[:max(k, 2)]), child_cost=self.child_cost,
+                    predicted=self.predicted, boundaries=self.boundaries, regions_from=list(self.regions_from[:max(k, 2)]),
+                    adopted=self.adopted, gpu_ms=self.gpu_ms)
+
+
 class StreamInfo(C.Structure):
     _fields_ = [("container", C.c_int), ("props", Properties), ("dict_size", C.c_uint32), ("declared_size", C.c_uint64)]
 
@@ -204,6 +220,10 @@ def hip_lib():
         L.mgl_sa_exchange_best.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
         L.mgl_sa_best_packed.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.mgl_sa_adopt_best_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mgl_crossover.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(CrossStats)]
+        L.mgl_sa_cross_best.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(CrossStats)]
+        L.mgl_sa_exchange_cross.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint64),
+                                            C.POINTER(CrossStats)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -490,6 +510,38 @@ class SA:
         w, c = C.c_int(-1), C.c_uint64(0)
         self._chk(self.L.mgl_sa_exchange_best(self.h, comm.h, C.byref(w), C.byref(c)))
         return w.value, c.value
+
+    def crossover(self, parents, grain: int = 0):
+        """The child of 2..8 valid parses (mgl_crossover; parity hook, SA state untouched): between the positions where all
+        the walks agree (about one cut per `grain` bytes, 0 = 64, 1 = every joint) the entries of whichever parent codes the
+        stretch most cheaply.  Returns (child slab, stats dict: parent_cost, child_cost, predicted, boundaries, regions_from,
+        gpu_ms)."""
+        keep = [np.ascontiguousarray(p, dtype=PACKET) for p in parents]
+        if any(len(p) != self.n for p in keep):
+            raise MglError("crossover: every parent must have one entry per input byte", rc=-1)
+        arr = (C.c_void_p * max(1, len(keep)))(*[p.ctypes.data for p in keep])
+        child = np.zeros(self.n, dtype=PACKET)
+        st = CrossStats()
+        self._chk(self.L.mgl_crossover(self.h, arr, len(keep), grain, _ptr(child), C.byref(st)))
+        return child, st.asdict()
+
+    def cross_best(self, slab, grain: int = 0) -> dict:
+        """Cross the best slab with `slab` (mgl_sa_cross_best): the child becomes the best slab if it is cheaper than both,
+        else `slab` if it is cheaper than the best; stats["adopted"] = 0 own best kept, 1 `slab`, 2 the child."""
+        slab = np.ascontiguousarray(slab, dtype=PACKET)
+        if len(slab) != self.n:
+            raise MglError("cross_best: the slab must have one entry per input byte", rc=-1)
+        st = CrossStats()
+        self._chk(self.L.mgl_sa_cross_best(self.h, _ptr(slab), grain, C.byref(st)))
+        return st.asdict()
+
+    def exchange_cross(self, comm: "Comm", grain: int = 0):
+        """exchange_best's collectives, then every rank but the winner crosses its best slab with the winner's
+        (mgl_sa_exchange_cross; collective).  Returns (winner rank, winner cost, this rank's stats dict)."""
+        w, c = C.c_int(-1), C.c_uint64(0)
+        st = CrossStats()
+        self._chk(self.L.mgl_sa_exchange_cross(self.h, comm.h, grain, C.byref(w), C.byref(c), C.byref(st)))
+        return w.value, c.value, st.asdict()
 
     def run(self, steps: int) -> dict:
         st = Stats()

@@ -13,6 +13,7 @@
 #include "mgl_optimal.hip"
 #include "mgl_adaptive.hip"
 #include "mgl_props.hip"
+#include "mgl_crossover.hip"
 #include "../../include/megalania_hip.h"
 
 #include <math.h>
@@ -2165,6 +2166,119 @@ extern "C" int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_
 		out[t].props.lc = (uint8_t)L.lc; out[t].props.lp = (uint8_t)L.lp; out[t].props.pb = (uint8_t)L.pb;
 		out[t].cost = costs[t];
 	}
+	return MGL_OK;
+}
+
+/* ---- crossover of parses (mgl_crossover.hip) */
+#define MGL_XO_DEF_GRAIN 64u
+struct XoBufs {
+	mgl_pk *slabs = nullptr, *child = nullptr;
+	uint64_t *cost = nullptr, *onwalk = nullptr, *joint = nullptr, *bound = nullptr;
+	uint32_t *state = nullptr, *last = nullptr;
+	uint8_t* winner = nullptr;
+	XoCounters* cnt = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	~XoBufs()
+	{
+		dfree(slabs); dfree(child); dfree(cost); dfree(onwalk); dfree(joint); dfree(bound); dfree(state); dfree(last); dfree(winner); dfree(cnt);
+		if (t0) (void)hipEventDestroy(t0);
+		if (t1) (void)hipEventDestroy(t1);
+	}
+};
+#define XO_ALLOC(ptr, bytes)                                                                      \
+	do {                                                                                          \
+		if (hipMalloc(&(ptr), (bytes)) != hipSuccess) {                                           \
+			(void)hipGetLastError();                                                              \
+			return fail(MGL_ENOMEM, "crossover: the per-parent buffers do not fit the device"); \
+		}                                                                                         \
+	} while (0)
+static int xo_alloc(mgl_sa* sa, XoBufs& x, uint32_t P)
+{
+	const size_t n = sa->n, nw = n / 64 + 1;
+	XO_ALLOC(x.slabs, sizeof(mgl_pk) * n * P);
+	XO_ALLOC(x.cost, sizeof(uint64_t) * (n + 1) * P);
+	XO_ALLOC(x.state, sizeof(uint32_t) * 5 * n * P);
+	XO_ALLOC(x.onwalk, sizeof(uint64_t) * nw * P);
+	XO_ALLOC(x.child, sizeof(mgl_pk) * n);
+	XO_ALLOC(x.joint, sizeof(uint64_t) * nw);
+	XO_ALLOC(x.bound, sizeof(uint64_t) * nw);
+	XO_ALLOC(x.last, sizeof(uint32_t) * nw);
+	XO_ALLOC(x.winner, n + 1);
+	XO_ALLOC(x.cnt, sizeof(XoCounters));
+	HIPCHK(hipEventCreate(&x.t0));
+	HIPCHK(hipEventCreate(&x.t1));
+	return MGL_OK;
+}
+/* The P parents lie packed in x.slabs: walk them, cut, pick, scatter into x.child and cost the child.  A parent the walk
+ * refuses is MGL_EINVAL, as from scratch_walk.  *st is filled except `adopted`. */
+static int xo_run(mgl_sa* sa, XoBufs& x, uint32_t P, uint32_t grain, mgl_cross_stats* st)
+{
+	const uint32_t n = sa->n, nw = n / 64u + 1u, nblk = (n + 1u + 255u) / 256u;
+	if (grain == 0) grain = MGL_XO_DEF_GRAIN;
+	hipStream_t s = sa->stream;
+	XoView v;
+	v.slab = x.slabs; v.cost = x.cost; v.state = x.state; v.onwalk = x.onwalk; v.nw = nw;
+	HIPCHK(hipEventRecord(x.t0, s));
+	HIPCHK(hipMemsetAsync(x.onwalk, 0, sizeof(uint64_t) * (size_t)nw * P, s));
+	HIPCHK(hipMemsetAsync(x.cnt, 0, sizeof(XoCounters), s));
+	HIPCHK(hipMemsetAsync(x.winner, 0xFF, (size_t)n + 1, s));
+	hipLaunchKernelGGL(k_xo_walk, dim3(P), dim3(64), 0, s, sa->ctx, v, x.cnt);
+	HIPCHK(hipGetLastError());
+	XoCounters h;
+	HIPCHK(hipMemcpyAsync(&h, x.cnt, sizeof h, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	memset(st, 0, sizeof *st);
+	st->parents = P; st->grain = grain;
+	for (uint32_t p = 0; p < P; p++) {
+		if (h.err[p]) return fail(MGL_EINVAL, "slab is not a valid parse of the input");
+		st->parent_cost[p] = h.total[p];
+	}
+	hipLaunchKernelGGL(k_xo_joints, dim3(nblk), dim3(256), 0, s, n, P, v, x.joint);
+	hipLaunchKernelGGL(k_xo_lastnz, dim3(1), dim3(1024), 0, s, (const uint64_t*)x.joint, nw, x.last);
+	hipLaunchKernelGGL(k_xo_bounds, dim3(nblk), dim3(256), 0, s, n, nw, grain, (const uint64_t*)x.joint, (const uint32_t*)x.last, x.bound, x.cnt);
+	hipLaunchKernelGGL(k_xo_lastnz, dim3(1), dim3(1024), 0, s, (const uint64_t*)x.bound, nw, x.last);
+	hipLaunchKernelGGL(k_xo_winner, dim3(nblk), dim3(256), 0, s, n, P, (const uint64_t*)x.cost, (const uint64_t*)x.bound, (const uint32_t*)x.last,
+	                   x.winner, x.cnt);
+	hipLaunchKernelGGL(k_xo_scatter, dim3((n + 255u) / 256u), dim3(256), 0, s, n, P, (const mgl_pk*)x.slabs, (const uint64_t*)x.bound,
+	                   (const uint32_t*)x.last, (const uint8_t*)x.winner, x.child);
+	HIPCHK(hipGetLastError());
+	/* the child: a batch of one, over parent 0's arrays (the winners are chosen) */
+	v.slab = x.child;
+	hipLaunchKernelGGL(k_xo_walk, dim3(1), dim3(64), 0, s, sa->ctx, v, x.cnt);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(x.t1, s));
+	HIPCHK(hipMemcpyAsync(&h, x.cnt, sizeof h, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (h.err[0]) return fail(MGL_EDEVICE, "crossover: the child is not a valid parse (device consistency check)");
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, x.t0, x.t1));
+	st->gpu_ms = ms;
+	st->child_cost = h.total[0];
+	st->predicted = h.predicted;
+	st->boundaries = h.boundaries;
+	for (uint32_t p = 0; p < P; p++) st->regions_from[p] = h.regions_from[p];
+	return MGL_OK;
+}
+
+extern "C" int mgl_crossover(mgl_sa* sa, const mgl_packet* const* parents, size_t nparents, uint32_t grain, mgl_packet* child_out,
+                             mgl_cross_stats* stats)
+{
+	static_assert(MGL_XO_MAX_PARENTS == MGL_XO_PARENTS, "header and kernels disagree on the number of parents");
+	if (!sa || !parents) return fail(MGL_EINVAL, "null argument");
+	if (nparents < 2 || nparents > MGL_XO_MAX_PARENTS) return fail(MGL_EINVAL, "mgl_crossover: 2 to 8 parents");
+	for (size_t p = 0; p < nparents; p++) if (!parents[p]) return fail(MGL_EINVAL, "mgl_crossover: null parent");
+	HIPCHK(hipSetDevice(sa->device));
+	XoBufs x;
+	int rc = xo_alloc(sa, x, (uint32_t)nparents);
+	if (rc) return rc;
+	for (size_t p = 0; p < nparents; p++) {
+		if ((rc = import_slab(sa, parents[p], x.slabs + p * (size_t)sa->n))) return rc;
+		HIPCHK(hipStreamSynchronize(sa->stream)); /* the staging area is reused */
+	}
+	mgl_cross_stats st;
+	if ((rc = xo_run(sa, x, (uint32_t)nparents, grain, &st))) return rc;
+	if (stats) *stats = st;
+	if (child_out) return export_slab(sa, x.child, child_out);
 	return MGL_OK;
 }
 

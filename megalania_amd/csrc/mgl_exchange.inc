@@ -367,3 +367,92 @@ extern "C" int mgl_sa_adopt_best_packed(mgl_sa* sa, const uint64_t* packed, uint
 	HIPCHK(hipMemcpyAsync(sa->scratch.v.slab, packed, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyHostToDevice, sa->stream));
 	return adopt_best_device(sa, sa->scratch.v.slab, perplexity, c);
 }
+
+/* ---- crossing exchange (mgl_crossover.hip): the loser recombines its own best slab with the winner's */
+/* packets_best := the packed slab at `src` (device) at its exact cost; `unverified`: checked when an epoch starts from it */
+static int xo_set_best(mgl_sa* sa, const mgl_pk* src, uint64_t cost, Control& c, bool unverified)
+{
+	HIPCHK(hipMemcpyAsync(sa->d_best, src, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
+	if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->stream));
+	c.best_cost = cost;
+	c.best_is_current = 0;
+	sa->best_unverified = unverified;
+	return write_ctl(sa, sa->base, &c);
+}
+/* mgl_sa_cross_best with `other` already in the scratch slab (an import, or the landing area of a broadcast) */
+static int cross_best_scratch(mgl_sa* sa, uint32_t grain, bool from_peer, mgl_cross_stats* st)
+{
+	Control c;
+	int rc = read_ctl(sa, sa->base, &c);
+	if (rc) return rc;
+	const mgl_pk* other = sa->scratch.v.slab;
+	memset(st, 0, sizeof *st);
+	if (c.best_cost == 0) {
+		/* no best slab yet: the walk mgl_sa_set_best uses says what `other` costs */
+		Control w;
+		HIPCHK(hipMemsetAsync(sa->scratch.ctl, 0, sizeof(Control), sa->stream));
+		if ((rc = launch_rebuild(sa, sa->scratch, 0, nullptr, nullptr))) return rc;
+		if ((rc = read_ctl(sa, sa->scratch, &w))) return rc;
+		if (w.error_flags) return fail(MGL_EINVAL, "slab is not a valid parse of the input");
+		st->grain = grain ? grain : MGL_XO_DEF_GRAIN;
+		st->parent_cost[1] = w.rebuild_cost;
+		st->adopted = 1;
+		return xo_set_best(sa, other, w.rebuild_cost, c, from_peer);
+	}
+	XoBufs x;
+	if ((rc = xo_alloc(sa, x, 2))) return rc;
+	HIPCHK(hipMemcpyAsync(x.slabs, best_slab_device(sa, c), sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(x.slabs + sa->n, other, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
+	if ((rc = xo_run(sa, x, 2, grain, st))) return rc;
+	const uint64_t own = st->parent_cost[0], oth = st->parent_cost[1];
+	if (st->child_cost < own && st->child_cost < oth) {
+		st->adopted = 2;
+		rc = xo_set_best(sa, x.child, st->child_cost, c, from_peer || sa->best_unverified);
+	} else if (oth < own) {
+		st->adopted = 1;
+		rc = xo_set_best(sa, other, oth, c, from_peer);
+	}
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(sa->stream)); /* the buffers go away with x */
+	return MGL_OK;
+}
+
+extern "C" int mgl_sa_cross_best(mgl_sa* sa, const mgl_packet* other, uint32_t grain, mgl_cross_stats* stats)
+{
+	if (!sa || !other) return fail(MGL_EINVAL, "null argument");
+	HIPCHK(hipSetDevice(sa->device));
+	int rc = import_slab(sa, other, sa->scratch.v.slab);
+	if (rc) return rc;
+	mgl_cross_stats st;
+	if ((rc = cross_best_scratch(sa, grain, false, &st))) return rc;
+	if (stats) *stats = st;
+	return MGL_OK;
+}
+
+extern "C" int mgl_sa_exchange_cross(mgl_sa* sa, mgl_comm* comm, uint32_t grain, int* winner_rank, uint64_t* winner_cost, mgl_cross_stats* stats)
+{
+	if (!sa || !comm) return fail(MGL_EINVAL, "null argument");
+	if (comm->device != sa->device) return fail(MGL_EINVAL, "mgl_sa_exchange_cross: communicator and chain live on different devices");
+	HIPCHK(hipSetDevice(sa->device));
+	if (stats) memset(stats, 0, sizeof *stats);
+	Control c;
+	int rc = read_ctl(sa, sa->base, &c);
+	if (rc) return rc;
+	/* the two collectives of mgl_sa_exchange_best */
+	const uint64_t mine = ((c.best_cost ? c.best_cost : MGL_KEY_NONE) << 8) | (uint64_t)(comm->rank & 0xFF);
+	uint64_t key = 0;
+	if ((rc = comm_min_u64(sa, comm, mine, &key)) != MGL_OK) return rc;
+	const int winner = (int)(key & 0xFF);
+	const uint64_t wcost = key >> 8;
+	if (winner_rank) *winner_rank = winner;
+	if (winner_cost) *winner_cost = wcost == MGL_KEY_NONE ? 0 : wcost;
+	if (wcost == MGL_KEY_NONE || comm->world == 1) return MGL_OK;
+	if ((rc = comm_broadcast_slab(sa, comm, best_slab_device(sa, c), sa->scratch.v.slab, (size_t)sa->n, winner)) != MGL_OK) return rc;
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	if (winner == comm->rank) return MGL_OK;
+	/* every other rank crosses its own best slab with the one that has just landed in the scratch slab */
+	mgl_cross_stats st;
+	if ((rc = cross_best_scratch(sa, grain, true, &st))) return rc;
+	if (stats) *stats = st;
+	return MGL_OK;
+}

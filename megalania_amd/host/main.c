@@ -30,7 +30,8 @@ static void usage(const char* argv0)
 	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P | --adaptive-seed P]\n"
 	        "          [--match-finder nearest|frontier [--mf-depth N]] [--parse-sweep [--parse-sweep-table]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
-	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]] filename\n"
+	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]\n"
+	        "          [--exchange best|cross [--cross-grain N]]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
 	        "  --save-slab  after every epoch, write the best packet slab (resumable checkpoint)\n"
 	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb)\n"
@@ -72,6 +73,11 @@ static void usage(const char* argv0)
 	        "               e.g. the launcher's pid: a file left by an earlier run is then never mistaken for this one's);\n"
 	        "               --transport shm stages the exchange through PATH itself (host shared memory) instead of RCCL:\n"
 	        "               for chains that share one GPU.  --save-slab: chain R > 0 writes to <file>.rankR\n"
+	        "  --exchange best|cross  what the chains do with the cheapest best slab after an epoch: every other chain adopts it\n"
+	        "               (best, default), or recombines it with its own best slab region by region between the positions where\n"
+	        "               the two walks agree and keeps the child if it is cheaper than both (cross; mgl_sa_exchange_cross);\n"
+	        "               one plain exchange follows the last epoch, so that rank 0 writes the overall best.  --cross-grain N:\n"
+	        "               about one cut per N input bytes (default 64; 1 = every joint); only with --exchange cross\n"
 	        "  --accept     what a step of K neighbours takes: the best acceptable one (single), every one that is\n"
 	        "               the best of its own window (bulk), or whichever pays (auto, default)\n", argv0);
 }
@@ -317,6 +323,8 @@ int main(int argc, char** argv)
 	const char* comm_path = NULL;
 	unsigned long long comm_nonce = 0;
 	int transport_shm = 0;
+	int exchange_cross = 0, cross_grain_given = 0;
+	uint32_t cross_grain = 0;
 	for (int i = 1; i < argc; i++) {
 		const char* a = argv[i];
 		const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -349,6 +357,11 @@ int main(int argc, char** argv)
 			if (!strcmp(v, "shm")) transport_shm = 1;
 			else if (strcmp(v, "rccl") != 0) { usage(argv[0]); return -1; }
 		}
+		else if (!strcmp(a, "--exchange")) {
+			if (!strcmp(v, "cross")) exchange_cross = 1;
+			else if (strcmp(v, "best") != 0) { usage(argv[0]); return -1; }
+		}
+		else if (!strcmp(a, "--cross-grain")) { cross_grain = (uint32_t)strtoul(v, NULL, 0); cross_grain_given = 1; }
 		else if (!strcmp(a, "--max-scan")) cfg.max_bucket_scan = (uint32_t)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "-o")) out_path = v;
 		else if (!strcmp(a, "--save-slab")) save_path = v;
@@ -412,6 +425,11 @@ int main(int argc, char** argv)
 	if (props_table && !props_auto) { usage(argv[0]); return -1; }
 	if (props_joint && !(props_auto && adaptive && parse_sweep)) {
 		fprintf(stderr, "Error: --props-joint needs --props auto --adaptive-seed P --parse-sweep\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (cross_grain_given && !exchange_cross) {
+		fprintf(stderr, "Error: --cross-grain needs --exchange cross\n");
 		usage(argv[0]);
 		return -1;
 	}
@@ -610,8 +628,18 @@ int main(int argc, char** argv)
 			if (comm) {
 				int winner = -1;
 				uint64_t wcost = 0;
-				if (mgl_sa_exchange_best(sa, comm, &winner, &wcost) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+				mgl_cross_stats xs;
+				if ((exchange_cross ? mgl_sa_exchange_cross(sa, comm, cross_grain, &winner, &wcost, &xs) : mgl_sa_exchange_best(sa, comm, &winner, &wcost)) != MGL_OK) {
+					fprintf(stderr, "Error: %s\n", mgl_last_error());
+					return -1;
+				}
 				fprintf(stderr, "exchange: chain %d holds the best slab, %f bytes\n", winner, 18 + wcost / 16384.f);
+				if (exchange_cross && xs.parents)
+					fprintf(stderr, "cross: chain %d: own %f, child %f of %llu regions (%llu own), %s (adopted %u), %.2f ms\n", rank, 18 + xs.parent_cost[0] / 16384.f,
+					        18 + xs.child_cost / 16384.f, (unsigned long long)(xs.boundaries - 1), (unsigned long long)xs.regions_from[0],
+					        xs.adopted == 2 ? "the child is the new best" : xs.adopted == 1 ? "the winner's slab adopted" : "own best kept", xs.adopted, xs.gpu_ms);
+				else if (exchange_cross)
+					fprintf(stderr, "cross: chain %d: nothing crossed (adopted %u)\n", rank, xs.adopted);
 			}
 			if (save_path && st.best_cost != 0) {
 				uint64_t hdr[2] = { file_size, 0 };
@@ -629,6 +657,13 @@ int main(int argc, char** argv)
 		}
 	}
 
+	if (comm && exchange_cross) {
+		/* the crossing exchanges leave every chain its own best slab: one plain exchange, so that rank 0 writes the overall best */
+		int winner = -1;
+		uint64_t wcost = 0;
+		if (mgl_sa_exchange_best(sa, comm, &winner, &wcost) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+		fprintf(stderr, "exchange: chain %d holds the best slab, %f bytes\n", winner, 18 + wcost / 16384.f);
+	}
 	uint64_t best = 0;
 	if (mgl_sa_best(sa, packets_best, &best) != MGL_OK) {
 		fprintf(stderr, "Error: could not fetch the best slab: %s\n", mgl_last_error());

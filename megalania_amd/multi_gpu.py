@@ -68,3 +68,11 @@ def exchange_best_native(chain, comm):
     """The north-star exchange, entirely inside the C library: 8-byte ncclAllReduce(min) + ncclBroadcast of
     the packed slab from the winner's HBM to the others'."""
     return chain.exchange_best(comm)
+
+
+def exchange_cross_native(chain, comm, grain: int = 0):
+    """The crossing exchange inside the C library (mgl_sa_exchange_cross): the same two collectives, then every chain but
+    the winner recombines its own best slab with the winner's region by region and keeps the child if it is cheaper than
+    both.  Chains may hold different best slabs afterwards; follow the last one with `exchange_best_native` where a
+    common slab is wanted.  Returns (winner rank, winner cost, this chain's crossover stats)."""
+    return chain.exchange_cross(comm, grain)
