@@ -27,6 +27,11 @@ static const uint16_t k_cost_table[2048] = {
 #include "mgl_cost_table.inc"
 };
 
+/* A/B switch of the step's serial tail; 0 builds the form before it */
+#ifndef MGL_TAIL_EARLY
+#define MGL_TAIL_EARLY 1 /* the last resort queued in front of the join with the re-simulations; no fork wait on the third stream */
+#endif
+
 #define MGL_MAX_INPUT 176000000ull
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg)
@@ -115,12 +120,11 @@ struct mgl_sa {
 	size_t b2_bytes;
 	BigScratch big;
 	uint32_t* d_todo2;
-	uint32_t* d_todo3 = nullptr; /* neighbours k_sim could not take (more touched contexts than its list holds): the late second pass */
 	uint4* d_pickstate;     /* 2 K: target, RNG position and walk state at the target (first half -> second half) */
 	uint4* d_pickrec;       /* K: picked packet, RNG position, ok flag (first half -> second half of the neighbour evaluation) */
 	bool split_nbr, adaptive; /* adaptive: the device recommends the split or the one-kernel form, the host adopts it block by block */
 	bool form_single = false; /* the form the regular launch runs as right now */
-	uint32_t* d_counts;     /* [0] first-pass overflow count, [1] second-pass overflow count, [2] spill slots used */
+	uint32_t* d_counts;     /* [0] first-pass overflow count, [1] second-pass overflow count, [2] spill slots used, [3] repair picks, [4] unused, always zero */
 	ApplyBuf ab;
 	uint32_t apply_blocks;
 	bool incremental_apply;
@@ -469,7 +473,11 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 		const uint32_t slices = nbr_slices(sa);
 		HIPCHK(hipEventRecord(sa->ev_fork, sa->stream));
 		if (slices >= 2) HIPCHK(hipStreamWaitEvent(sa->stream2, sa->ev_fork, 0));
+#if !MGL_TAIL_EARLY
 		HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_fork, 0));
+#endif
+		/* (the third stream needs no wait of its own for the fork: its first wait, ev_rest[0], is recorded on the main stream
+		 * behind the fork, for any number of slices) */
 		/* the first two thirds of the split form -- pick, then window walk -- of every slice; slices alternate between the two
 		 * streams, ev_rest[h] is recorded behind slice h's walk */
 		for (uint32_t h = 0; h < slices; h++) {
@@ -488,16 +496,15 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 		HIPCHK(hipGetLastError());
 		for (uint32_t h = 0; h < slices; h++) {
 			const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
-			/* the second half's re-simulation, several wavefronts per neighbour; a neighbour with more touched contexts
-			 * than its list holds goes straight to the last resort's list (the second pass may be running by then) */
+			/* the second half's re-simulation, several wavefronts per neighbour */
 			HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_rest[h], 0));
 			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 4 * (size_t)sa->time_sim_step + 2 * h), sa->stream3));
 			if (sa->count_traffic)
 				hipLaunchKernelGGL(k_sim<true>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, sa->stream3, sa->ctx, sa->b2, sa->base.ctl,
-				                   sa->nbr, sa->big, j0, j1, sa->d_todo3, sa->d_counts + 4, sa->d_traffic);
+				                   sa->nbr, sa->big, j0, j1, sa->d_traffic);
 			else
 				hipLaunchKernelGGL(k_sim<false>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, sa->stream3, sa->ctx, sa->b2, sa->base.ctl,
-				                   sa->nbr, sa->big, j0, j1, sa->d_todo3, sa->d_counts + 4, (unsigned long long*)nullptr);
+				                   sa->nbr, sa->big, j0, j1, (unsigned long long*)nullptr);
 			NBR_TRACE("k_sim");
 			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 4 * (size_t)sa->time_sim_step + 2 * h + 1), sa->stream3));
 		}
@@ -516,21 +523,19 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 	hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks), dim3(64 * sa->big_waves), big_lds, sa->stream, sa->ctx,
 	                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
 	                   g_prof_big ? sa->d_prof : (unsigned long long*)nullptr, sa->big, split_now ? sa->d_pickrec : (uint4*)nullptr, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
-	if (split_now) {
-		/* what k_sim could not take (more touched contexts than its list holds): a late second pass */
-		HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_sim, 0));
-		BigScratch late = sa->big;
-		late.todo_in = sa->d_todo3; late.todo_in_count = sa->d_counts + 4;
-		late.cont = nullptr; /* its list is another one: the slots' saved walks belong to the second pass proper */
-		hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks < 64u ? bigblocks : 64u), dim3(64 * sa->big_waves), big_lds, sa->stream, sa->ctx,
-		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
-		                   (unsigned long long*)nullptr, late, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
-	}
-	/* and whatever overflowed even that: exact full walk from byte 0 (a small grid strides over the list) */
+#if !MGL_TAIL_EARLY
+	if (split_now) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_sim, 0));
+#endif
+	/* and whatever overflowed even that: exact full walk from byte 0 (a small grid strides over the list).  It reads the second
+	 * pass's list and writes the outputs of its own neighbours only, which k_sim never costs (their headers stay 0xFFFFFFFF):
+	 * it is queued right behind the second pass, and the re-simulations join behind it */
 	const uint32_t blocks = (K + sa->waves_per_block - 1) / sa->waves_per_block;
 	hipLaunchKernelGGL(k_neighbours, dim3(blocks < 256u ? blocks : 256u), dim3(64 * sa->waves_per_block), sa->nbr_lds, sa->stream, sa->ctx, sa->base.v,
 	                   (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_bytes,
 	                   (const uint32_t*)sa->d_todo2, (const uint32_t*)(sa->d_counts + 1)); NBR_TRACE("k_neighbours");
+#if MGL_TAIL_EARLY
+	if (split_now) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_sim, 0));
+#endif
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -584,7 +589,7 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 		dfree(bt.bk_ipos); dfree(bt.bk_rpos); dfree(bt.bk_ibit); dfree(bt.bk_icl); dfree(bt.bk_rcl);
 	}
 	for (hipEvent_t e : sa->ev_sim_pool) if (e) (void)hipEventDestroy(e);
-	dfree(sa->d_todo2); dfree(sa->d_todo3); dfree(sa->d_counts); dfree(sa->d_pickrec); dfree(sa->d_pickstate);
+	dfree(sa->d_todo2); dfree(sa->d_counts); dfree(sa->d_pickrec); dfree(sa->d_pickstate);
 	dfree(sa->lim.why); dfree(sa->ab.hdr); dfree(sa->ab.ins_key); dfree(sa->ab.rem_key); dfree(sa->ab.ins_pos); dfree(sa->ab.rem_pos);
 	dfree(sa->ab.tctx); dfree(sa->ab.scratch_pos); dfree(sa->ab.scratch_ev);
 	dfree(sa->ab.span_pos); dfree(sa->ab.span_ev); dfree(sa->ab.jobs_b); dfree(sa->ab.jobs_c);
@@ -958,8 +963,6 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		sa->build_lds = 4096u + ckpt_elems * 2u + ckpt_elems * 8u;
 		HIPCHK(hipMalloc(&sa->d_counts, sizeof(uint32_t) * 16)); /* [0..7] live, [8..15] the last finished step's */
 		HIPCHK(hipMemset(sa->d_counts, 0, sizeof(uint32_t) * 16));
-		HIPCHK(hipMalloc(&sa->d_todo3, sizeof(uint32_t) * (K + 1)));
-		HIPCHK(hipMemset(sa->d_todo3, 0, sizeof(uint32_t) * (K + 1)));
 		sa->big.todo_in = sa->d_todo; sa->big.todo_in_count = sa->d_counts; sa->big.spill_ctr = sa->d_counts + 2;
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2424,7 +2427,15 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 83: src = b.ch_sb; sz = sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride; break; /* the chain index, row per context, sb_stride words each */
 	case 81: src = sa->batch.hdr; sz = sizeof(uint32_t) * 16; break;
 	case 82: src = sa->batch.acc; sz = sizeof(long long) * 4; break;
-	case 10: src = sa->d_counts + 8; sz = sizeof(uint32_t) * 4; break; /* of the last finished step / mgl_neighbours call */
+	case 10: { /* the per-step counters: [0..7] of the last finished step / mgl_neighbours call, [8..15] the live ones (zero between steps) */
+		uint32_t v[16];
+		*bytes = sizeof v;
+		if (cap_bytes < sizeof v) return fail(MGL_ERANGE, "mgl_debug_dump: buffer too small");
+		HIPCHK(hipMemcpy(v, sa->d_counts + 8, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(v + 8, sa->d_counts, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost));
+		memcpy(out, v, sizeof v);
+		return MGL_OK;
+	}
 	case 14: src = sa->ab.hdr; sz = sa->ab.hdr ? sizeof(uint32_t) * 16 : 0; break; /* apply counters / stage cycles */
 	case 16: src = sa->base.ctl; sz = sizeof(Control); break; /* raw control block */
 	case 15: src = sa->d_pickrec; sz = sa->d_pickrec ? sizeof(uint4) * sa->cfg.neighbours_per_step : 0; break;

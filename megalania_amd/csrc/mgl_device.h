@@ -113,6 +113,7 @@ struct Control {
 #define MGL_ERR_REBUILD_MISMATCH 1u
 #define MGL_ERR_WALK_OVERRUN 2u
 #define MGL_ERR_BAD_PACKET 4u /* a packet that does not reproduce the input (k_validate) */
+#define MGL_ERR_SIM_LIST 8u /* k_sim was handed more distinct contexts than its list holds: cannot happen (mgl_kernels2.hip:sim_one) */
 
 #define MGL_WIN_NONE 0xFFFFFFFFu    /* no cost: no candidate at the target / handed to a later pass */
 #define MGL_WIN_DROPPED 0xFFFFFFFEu /* no cost: the journal outgrew MGL_MAX_DIFFS */

@@ -1380,7 +1380,7 @@ struct SimShared {
 };
 template <bool COUNT>
 __device__ __forceinline__ void sim_one(const DevCtx& c, const Base2& b, Control* ctl, const NbrOut& out, const BigScratch& big, const uint4* hdrs,
-                                        uint32_t j, uint32_t* todo, uint32_t* todo_count, const SimShared& sh, unsigned long long* traffic_ctr)
+                                        uint32_t j, const SimShared& sh, unsigned long long* traffic_ctr)
 {
 	const uint4 hdr = hdrs[j];
 	if (hdr.x == 0xFFFFFFFFu) return; /* failed, dropped or handed on: its cost is written (uniform over the workgroup) */
@@ -1404,15 +1404,18 @@ __device__ __forceinline__ void sim_one(const DevCtx& c, const Base2& b, Control
 	for (uint32_t e = threadIdx.x; e < ch.n_rem; e += blockDim.x) { s_key[cap + e] = gk[cap + e]; s_pos[cap + e] = gp[cap + e]; }
 	__syncthreads();
 	if (wid == 0) {
+		/* The list cannot run out of room here.  Both change lists were filled by the walk half, where changes_add and the
+		 * literal-run path refuse an event beyond `cap` per list and raise list_full; such a neighbour goes to the second pass
+		 * and its header stays 0xFFFFFFFF, so it never gets here.  What does get here has n_ins <= cap and n_rem <= cap, hence
+		 * at most n_ins + n_rem <= 2 cap = uctx_cap distinct contexts, whatever chg_cap is set to (mgl_debug_set key 2). */
 		bool too_many = false;
 		const uint32_t nu = chain_list(ch, lane, &too_many);
 		if (lane == 0) { sh.nu_many[0] = nu; sh.nu_many[1] = too_many ? 1u : 0u; }
 	}
 	__syncthreads();
-	if (sh.nu_many[1]) { /* more distinct contexts than the list holds: the late second pass re-simulates it inline */
+	if (sh.nu_many[1]) { /* the invariant above is broken: no cost, and the run ends with an error instead of dropping the neighbour quietly */
 		if (threadIdx.x == 0) {
-			const uint32_t slot2 = atomicAdd(todo_count, 1u);
-			todo[slot2] = j;
+			atomicOr(&ctl->error_flags, MGL_ERR_SIM_LIST);
 			out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = 0; out.win[2u * j + 1u] = MGL_WIN_NONE;
 		}
 		return;
@@ -1440,7 +1443,7 @@ __device__ __forceinline__ void sim_one(const DevCtx& c, const Base2& b, Control
  * work (traffic_ctr[1]); bench.py runs a few steps with it after its timed region */
 template <bool COUNT>
 __global__ void __launch_bounds__(64 * MGL_SIM_WAVES_MAX, 8) k_sim(DevCtx c, Base2 b, Control* ctl, NbrOut out, BigScratch big, uint32_t j_base, uint32_t j_end,
-                                                           uint32_t* todo, uint32_t* todo_count, unsigned long long* traffic_ctr)
+                                                           unsigned long long* traffic_ctr)
 {
 	if (j_base + blockIdx.x >= j_end) return;
 	__shared__ __attribute__((aligned(16))) uint16_t T[2048];
@@ -1452,7 +1455,7 @@ __global__ void __launch_bounds__(64 * MGL_SIM_WAVES_MAX, 8) k_sim(DevCtx c, Bas
 	for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) reinterpret_cast<uint4*>(T)[i] = reinterpret_cast<const uint4*>(c.cost_tbl)[i];
 	SimShared sh;
 	sh.T = T; sh.dyn = s_dyn; sh.sum = s_sum; sh.nu_many = s_nm;
-	sim_one<COUNT>(c, b, ctl, out, big, big.sim_hdr, j_base + blockIdx.x, todo, todo_count, sh, traffic_ctr);
+	sim_one<COUNT>(c, b, ctl, out, big, big.sim_hdr, j_base + blockIdx.x, sh, traffic_ctr);
 }
 
 
