@@ -25,9 +25,10 @@
  *   mgl_sa_destroy    main.c:107-108,121 the matching frees
  *   mgl_props_sweep   no reference counterpart (lc = lp = pb = 0 are fixed there, main.c:45): one parse costed
  *                                    under every supported lc/lp/pb at once
- *   mgl_crossover, mgl_sa_cross_best, mgl_sa_exchange_cross
+ *   mgl_crossover, mgl_sa_cross_best, mgl_sa_exchange_cross, mgl_sa_exchange_cross_all
  *                     no reference counterpart (the reference runs one chain): several valid parses recombined region
- *                                    by region between the positions where their walks agree
+ *                                    by region between the positions where their walks agree; the last one crosses the
+ *                                    distinct best slabs of all chains (mgl_slab_hash, mgl_comm_allgather_u64 serve it)
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -322,6 +323,9 @@ int mgl_comm_init(mgl_comm** comm_out, const uint8_t id[128], int rank, int worl
 int mgl_comm_init_shm(mgl_comm** comm_out, const char* path, uint64_t nonce, int rank, int world, int device);
 /* host transport only, no device involved: the minimum over the ranks of one word each (the first half of an exchange) */
 int mgl_comm_min_u64(mgl_comm* comm, uint64_t mine, uint64_t* min_out);
+/* host transport only, no device involved: every rank's word in rank order (all_out: mgl_comm_world entries).  The collective
+ * by which mgl_sa_exchange_cross_all publishes keys and slab hashes; its RCCL form (ncclAllGather) runs inside that call. */
+int mgl_comm_allgather_u64(mgl_comm* comm, uint64_t mine, uint64_t* all_out);
 void mgl_comm_destroy(mgl_comm* comm);
 int mgl_comm_rank(const mgl_comm* comm);
 int mgl_comm_world(const mgl_comm* comm);
@@ -368,6 +372,37 @@ int mgl_sa_cross_best(mgl_sa* sa, const mgl_packet* other, uint32_t grain, mgl_c
  * dearer than the winner's.  What a rank adopts here came from a peer and is checked against the input when an epoch first starts
  * from it, as after mgl_sa_exchange_best.  stats (nullable): this rank's crossing; all zero on the winner.  Collective. */
 int mgl_sa_exchange_cross(mgl_sa* sa, mgl_comm* comm, uint32_t grain, int* winner_rank, uint64_t* winner_cost, mgl_cross_stats* stats);
+/* Parity hook (SA state untouched): the hash by which chains tell equal slabs from different ones without sending them.
+ * h = sum over x < n of fin(packed[x] + (x + 1) * 0x9E3779B97F4A7C15) mod 2^64, packed = dist | len << 32 | type << 48 (the 8-byte
+ * device form) and fin the splitmix64 finaliser, z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB,
+ * z ^= z >> 31.  Every entry counts, stale off-walk ones too (the crossover copies entries verbatim).  packets NULL = the best
+ * slab; MGL_EINVAL if there is none yet. */
+int mgl_slab_hash(mgl_sa* sa, const mgl_packet* packets, uint64_t* hash);
+/* The exchange that crosses the best slabs of all chains (collective; opt-in next to mgl_sa_exchange_best and
+ * mgl_sa_exchange_cross).
+ * (1) Every rank publishes key = (best_cost, or "none") << 8 | rank and mgl_slab_hash of its best slab: two all-gathers.
+ * (2) Every rank makes the same selection: the ranks that hold a best slab in ascending key order, skipping a rank whose
+ *     (cost, hash) an already selected rank has, at most MGL_XO_MAX_PARENTS of them.  D remain; parent p is the p-th, so the
+ *     crossover's ties go to the cheaper chain.  A hash collision between different slabs of one cost can only drop a parent.
+ * (3) D = 0: nothing happens.  D = 1: mgl_sa_exchange_best -- one broadcast, ranks with a dearer best slab or none adopt it
+ *     (cross.parents = 0, cross.adopted = 1 on those ranks, cross.parent_cost[0] its cost).  D >= 2: every rank allocates mgl_crossover's buffers and one min
+ *     of an ok flag follows; if any rank had no room all of them take the D = 1 path instead (fell_back = 1, still MGL_OK).
+ *     Otherwise parent p's owner broadcasts its best slab into slot p of the crossover's slab buffer, device to device (the
+ *     host transport stages through its file), and every rank runs mgl_crossover's kernels on the D parents.  A parent whose
+ *     walked cost is not the cost its rank published: MGL_EINVAL, nothing adopted.
+ * (4) The same on every rank: child_cost < parent_cost[0]: the child becomes the best slab (cross.adopted = 2);  else ranks
+ *     whose best is dearer than parent 0, or that have none, adopt parent 0 (1);  else nothing changes (0).
+ * What a rank adopts came from peers and is checked against the input when an epoch first starts from it, as after
+ * mgl_sa_exchange_best.  The current slab and the run state are untouched.  grain as in mgl_crossover.  stats nullable. */
+typedef struct {
+	uint32_t chains_with_best;               /* ranks that published a best slab */
+	uint32_t distinct;                       /* D: the parents */
+	uint32_t parent_rank[MGL_XO_MAX_PARENTS]; /* the rank that owns each parent */
+	uint32_t own_parent;                     /* this rank's parent index, UINT32_MAX if it is none */
+	uint32_t fell_back;                      /* 1: a rank could not allocate, everybody took the D = 1 path */
+	mgl_cross_stats cross;                   /* the crossing, the same on every rank but gpu_ms (nothing crossed: zero but `adopted` and parent_cost[0]) */
+} mgl_cross_all_stats;
+int mgl_sa_exchange_cross_all(mgl_sa* sa, mgl_comm* comm, uint32_t grain, mgl_cross_all_stats* stats);
 /* The same hand-over through host memory in the packed device form (dist | len << 32 | type << 48, 8 bytes
  * per position), for transports other than RCCL.  Adopting does not verify; see mgl_sa_exchange_best. */
 int mgl_sa_best_packed(mgl_sa* sa, uint64_t* packed_out, uint64_t* perplexity_out);
@@ -448,7 +483,9 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * by in place, 17 = runs on the checkpoint list, 18 = 1 / 0: clusters are split at the members' soft window ends instead of
  * their hard ends (a wrong rule on purpose: the boundary guard of the cluster walks must then send the step to the rebuild).
  * key 7 = 1, 2 or the compiled MGL_BIG_WAVES (anything else: MGL_EINVAL): the wavefronts of a second-pass workgroup, which
- * share a neighbour's re-simulations; with 1 or 2 a neighbour's contexts take several trips (exercises that path). */
+ * share a neighbour's re-simulations; with 1 or 2 a neighbour's contexts take several trips (exercises that path).
+ * key 8 = n: the next n crossovers (mgl_crossover, mgl_sa_cross_best and the crossing exchanges) find no room for their
+ * buffers (MGL_ENOMEM; exercises mgl_sa_exchange_cross_all's fall-back). */
 int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes);
 int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value);
 /* draw n of neighbour j at global step `step` (31-bit, like rand()); j = 0xFFFFFFFF is the

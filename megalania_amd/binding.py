@@ -38,6 +38,7 @@ HIP_SYMBOLS = [
     "mgl_comm_unique_id", "mgl_comm_init", "mgl_comm_init_shm", "mgl_comm_min_u64", "mgl_comm_destroy", "mgl_comm_rank", "mgl_comm_world", "mgl_sa_exchange_best",
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep", "mgl_parse_sweep_props",
     "mgl_crossover", "mgl_sa_cross_best", "mgl_sa_exchange_cross",
+    "mgl_comm_allgather_u64", "mgl_slab_hash", "mgl_sa_exchange_cross_all",
 ]
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
@@ -138,6 +139,16 @@ class CrossStats(C.Structure):
                     adopted=self.adopted, gpu_ms=self.gpu_ms)
 
 
+class CrossAllStats(C.Structure):
+    _fields_ = [("chains_with_best", C.c_uint32), ("distinct", C.c_uint32), ("parent_rank", C.c_uint32 * XO_MAX_PARENTS),
+                ("own_parent", C.c_uint32), ("fell_back", C.c_uint32), ("cross", CrossStats)]
+
+    def asdict(self):
+        own = self.own_parent
+        return dict(chains_with_best=self.chains_with_best, distinct=self.distinct, parent_rank=list(self.parent_rank[:self.distinct]),
+                    own_parent=None if own == 0xFFFFFFFF else own, fell_back=self.fell_back, cross=self.cross.asdict())
+
+
 class StreamInfo(C.Structure):
     _fields_ = [("container", C.c_int), ("props", Properties), ("dict_size", C.c_uint32), ("declared_size", C.c_uint64)]
 
@@ -224,6 +235,9 @@ def hip_lib():
         L.mgl_sa_cross_best.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(CrossStats)]
         L.mgl_sa_exchange_cross.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint64),
                                             C.POINTER(CrossStats)]
+        L.mgl_comm_allgather_u64.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.mgl_slab_hash.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.mgl_sa_exchange_cross_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(CrossAllStats)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -543,6 +557,25 @@ class SA:
         self._chk(self.L.mgl_sa_exchange_cross(self.h, comm.h, grain, C.byref(w), C.byref(c), C.byref(st)))
         return w.value, c.value, st.asdict()
 
+    def exchange_cross_all(self, comm: "Comm", grain: int = 0) -> dict:
+        """Cross the distinct best slabs of all chains, the 8 cheapest at most (mgl_sa_exchange_cross_all; collective): every
+        rank makes the same child and takes it if it is cheaper than the cheapest parent, which the dearer ranks adopt
+        otherwise.  Returns the stats dict: chains_with_best, distinct, parent_rank, own_parent (None: not a parent),
+        fell_back, cross (as from crossover, with adopted = 0 nothing, 1 the cheapest parent, 2 the child)."""
+        st = CrossAllStats()
+        self._chk(self.L.mgl_sa_exchange_cross_all(self.h, comm.h, grain, C.byref(st)))
+        return st.asdict()
+
+    def slab_hash(self, slab=None) -> int:
+        """mgl_slab_hash of `slab` (None: the best slab), stale entries included; parity hook, SA state untouched"""
+        if slab is not None:
+            slab = np.ascontiguousarray(slab, dtype=PACKET)
+            if len(slab) != self.n:
+                raise MglError("slab_hash: the slab must have one entry per input byte", rc=-1)
+        out = C.c_uint64(0)
+        self._chk(self.L.mgl_slab_hash(self.h, _ptr(slab), C.byref(out)))
+        return out.value
+
     def run(self, steps: int) -> dict:
         st = Stats()
         self._chk(self.L.mgl_sa_run(self.h, steps, C.byref(st)))
@@ -660,6 +693,13 @@ class Comm:
         if self.L.mgl_comm_min_u64(self.h, mine, C.byref(out)) != 0:
             raise MglError(self.L.mgl_last_error().decode())
         return out.value
+
+    def allgather_u64(self, mine: int) -> list:
+        """every rank's word in rank order (mgl_comm_allgather_u64: host transport only)"""
+        out = (C.c_uint64 * self.world)()
+        if self.L.mgl_comm_allgather_u64(self.h, mine, out) != 0:
+            raise MglError(self.L.mgl_last_error().decode())
+        return list(out)
 
     @staticmethod
     def unique_id() -> bytes:

@@ -152,6 +152,7 @@ struct mgl_sa {
 	bool select_small = false;    /* the previous bulk step had few acceptable neighbours: this one's selection runs as one launch */
 	uint32_t* h_bstat = nullptr;   /* pinned: the batch accept's status words, read back once per bulk step */
 	hipEvent_t ev_bstat = nullptr; /* behind that read-back's copy */
+	uint32_t force_xo_nomem = 0; /* diagnostic (mgl_debug_set key 8): the next so many crossovers find no room for their buffers */
 	uint32_t force_batch_fail = 0; /* diagnostic (mgl_debug_set key 5): the next so many batch accepts give up behind their commit */
 	uint32_t force_batch_late = 0; /* ... 0: before any chain is touched; n: once the n-th touched context has rewritten its chain's descriptors */
 	AcceptLimits lim, lim_max;     /* what the in-place accepts compare against (mgl_debug_set key 6 lowers them) and the compiled / allocated values */
@@ -2198,6 +2199,7 @@ struct XoBufs {
 static int xo_alloc(mgl_sa* sa, XoBufs& x, uint32_t P)
 {
 	const size_t n = sa->n, nw = n / 64 + 1;
+	if (sa->force_xo_nomem) { sa->force_xo_nomem--; return fail(MGL_ENOMEM, "crossover: the per-parent buffers do not fit the device"); }
 	XO_ALLOC(x.slabs, sizeof(mgl_pk) * n * P);
 	XO_ALLOC(x.cost, sizeof(uint64_t) * (n + 1) * P);
 	XO_ALLOC(x.state, sizeof(uint32_t) * 5 * n * P);
@@ -2282,6 +2284,18 @@ extern "C" int mgl_crossover(mgl_sa* sa, const mgl_packet* const* parents, size_
 	if ((rc = xo_run(sa, x, (uint32_t)nparents, grain, &st))) return rc;
 	if (stats) *stats = st;
 	if (child_out) return export_slab(sa, x.child, child_out);
+	return MGL_OK;
+}
+
+/* the hash of the n packed entries at `slab` (device); the first of the 64 words of top-K scratch takes the sum */
+static int slab_hash_device(mgl_sa* sa, const mgl_pk* slab, uint64_t* hash)
+{
+	unsigned long long* d_sum = (unsigned long long*)sa->d_topk_cost;
+	HIPCHK(hipMemsetAsync(d_sum, 0, sizeof *d_sum, sa->stream));
+	hipLaunchKernelGGL(k_slab_hash, dim3((sa->n + 255u) / 256u), dim3(256), 0, sa->stream, sa->n, slab, d_sum);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(hash, d_sum, sizeof *hash, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
 	return MGL_OK;
 }
 
@@ -2510,6 +2524,7 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 		sa->big_waves = (uint32_t)value;
 		return MGL_OK;
 	}
+	if (key == 8) { sa->force_xo_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` crossovers fail to allocate their buffers (MGL_ENOMEM) */
 	if (key == 3) { sa->force_rollbacks = (uint32_t)value; return MGL_OK; } /* the next `value` bulk steps that take moves are taken back as if their parse had failed validation */
 	return fail(MGL_EINVAL, "mgl_debug_set: unknown key");
 }

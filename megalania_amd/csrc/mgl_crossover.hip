@@ -21,9 +21,12 @@
  *   k_xo_winner   a lane per position: a boundary b' > 0 closes the region [b, b') behind the boundary before it; the
  *                 parent with the smallest cost[b'] - cost[b] wins it, ties to the lowest index.  winner[b] is its index.
  *   k_xo_scatter  a lane per position x < n: child[x] = the entry at x of the winner of the region x lies in.
+ *   k_slab_hash   a lane per position x < n: the sum mod 2^64 of the mixed (entry, position) words of a packed slab, the word
+ *                 by which the exchange of all chains' best slabs (mgl_sa_exchange_cross_all) tells equal slabs from
+ *                 different ones without sending them.
  *
- * Atomics: the count of boundaries, regions_from[] and the sum of the minima (one per wavefront each; u64 addition
- * commutes, so the sums are exact).  Every index is bounded by n (or the word count) before it is used.
+ * Atomics: the count of boundaries, regions_from[], the sum of the minima and the slab hash (one per wavefront each; u64
+ * addition commutes, so the sums are exact).  Every index is bounded by n (or the word count) before it is used.
  */
 #include "mgl_device.h"
 
@@ -200,4 +203,15 @@ __global__ void __launch_bounds__(256) k_xo_scatter(uint32_t n, uint32_t nparent
 	uint32_t w = winner[xo_last_le(bound, blast, x)];
 	if (w >= nparents) w = 0u; /* never: every region below n has a winner */
 	child[x] = slabs[(size_t)w * n + x];
+}
+
+/* *out += the sum over x < n of fin(slab[x] + (x + 1) * 0x9E3779B97F4A7C15) mod 2^64, fin = the splitmix64 finaliser: mgl_mix64
+ * adds the constant once more before it finalises, hence the x where the formula has x + 1.  Every entry counts, the stale
+ * ones off the walk too: the crossover copies entries verbatim, so two slabs are the same parent only if all of them agree. */
+__global__ void __launch_bounds__(256) k_slab_hash(uint32_t n, const mgl_pk* slab, unsigned long long* out)
+{
+	const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint64_t h = x < n ? mgl_mix64((uint64_t)slab[x] + (uint64_t)x * 0x9E3779B97F4A7C15ull) : 0ull;
+	const uint64_t sum = wave_sum64(h);
+	if ((threadIdx.x & 63u) == 0u) atomicAdd(out, (unsigned long long)sum);
 }

@@ -15,6 +15,9 @@
  *                              share one GPU (RCCL refuses two ranks per device) and for boxes without RCCL;
  *                              it is also how the two-rank protocol is tested on a one-GPU box.
  *
+ * Two more collectives serve the exchange that crosses every chain's best slab (mgl_sa_exchange_cross_all): an all-gather of
+ * one u64 per rank (ncclAllGather; the host form reads the keys the min already stages) and the broadcast again, once per parent.
+ *
  * An adopted slab becomes packets_best only; its cost is the sender's exact figure.  It is verified when
  * it is used: mgl_sa_begin_epoch(from_best) re-derives its structures with the parallel builder, checks
  * every packet against the input (k_validate) and the total against the claimed cost.
@@ -26,6 +29,9 @@
 #include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
+#include <algorithm>
+#include <type_traits>
+#include <utility>
 
 #if __has_include(<rccl/rccl.h>)
 #include <rccl/rccl.h>
@@ -34,6 +40,8 @@
 #define MGL_NCCL_MIN ((int)ncclMin)
 static_assert((int)ncclUint64 == 5 && (int)ncclMin == 3, "rccl.h: ncclUint64 / ncclMin are not the values this library was written against");
 static_assert(sizeof(ncclUniqueId) == 128, "rccl.h: ncclUniqueId is not 128 bytes (mgl_comm_unique_id's contract)");
+static_assert(std::is_same<decltype(&ncclAllGather), ncclResult_t (*)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t)>::value,
+              "rccl.h: ncclAllGather does not have the signature it is called with");
 #else
 #error "rccl/rccl.h not found: the RCCL enum values used by mgl_sa_exchange_best cannot be checked"
 #endif
@@ -53,6 +61,7 @@ typedef int (*pfn_ncclCommInitRank)(void**, int, /* ncclUniqueId by value: 128 b
 typedef int (*pfn_ncclCommDestroy)(void*);
 typedef int (*pfn_ncclAllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t);
 typedef int (*pfn_ncclBroadcast)(const void*, void*, size_t, int, int, void*, hipStream_t);
+typedef int (*pfn_ncclAllGather)(const void*, void*, size_t, int, void*, hipStream_t);
 typedef const char* (*pfn_ncclGetErrorString)(int);
 
 /* the shared-memory transport's file: one page of header, the slab area behind it */
@@ -79,6 +88,7 @@ struct mgl_comm {
 	pfn_ncclCommDestroy destroy;
 	pfn_ncclAllReduce all_reduce;
 	pfn_ncclBroadcast broadcast;
+	pfn_ncclAllGather all_gather;
 	pfn_ncclGetErrorString errstr;
 	/* shared-memory file */
 	int fd;
@@ -138,8 +148,9 @@ extern "C" int mgl_comm_init(mgl_comm** out, const uint8_t id[128], int rank, in
 	c->destroy = (pfn_ncclCommDestroy)dlsym(c->dl, "ncclCommDestroy");
 	c->all_reduce = (pfn_ncclAllReduce)dlsym(c->dl, "ncclAllReduce");
 	c->broadcast = (pfn_ncclBroadcast)dlsym(c->dl, "ncclBroadcast");
+	c->all_gather = (pfn_ncclAllGather)dlsym(c->dl, "ncclAllGather");
 	c->errstr = (pfn_ncclGetErrorString)dlsym(c->dl, "ncclGetErrorString");
-	if (!init || !c->destroy || !c->all_reduce || !c->broadcast) { delete c; return fail(MGL_EDEVICE, "mgl_comm_init: RCCL symbols missing"); }
+	if (!init || !c->destroy || !c->all_reduce || !c->broadcast || !c->all_gather) { delete c; return fail(MGL_EDEVICE, "mgl_comm_init: RCCL symbols missing"); }
 	mgl_nccl_id uid;
 	memcpy(uid.internal, id, 128);
 	c->rank = rank; c->world = world; c->device = device;
@@ -241,7 +252,7 @@ extern "C" void mgl_comm_destroy(mgl_comm* c)
 extern "C" int mgl_comm_rank(const mgl_comm* c) { return c ? c->rank : -1; }
 extern "C" int mgl_comm_world(const mgl_comm* c) { return c ? c->world : 0; }
 
-/* ---- the two collectives, by transport */
+/* ---- the collectives, by transport */
 /* min over the ranks of one u64 each (the packed key): every rank receives it.  `sa` lends a stream and 16 bytes of
  * device scratch to the RCCL form; the host form does not touch the device (sa may be null: mgl_comm_min_u64) */
 static int comm_min_u64(mgl_sa* sa, mgl_comm* comm, uint64_t mine, uint64_t* out)
@@ -262,6 +273,35 @@ static int comm_min_u64(mgl_sa* sa, mgl_comm* comm, uint64_t mine, uint64_t* out
 	const int nrc = comm->all_reduce(d_key, d_key + 1, 1, MGL_NCCL_UINT64, MGL_NCCL_MIN, comm->comm, sa->stream);
 	if (nrc != 0) return fail(MGL_EDEVICE, std::string("ncclAllReduce: ") + (comm->errstr ? comm->errstr(nrc) : "?"));
 	HIPCHK(hipMemcpyAsync(out, d_key + 1, sizeof *out, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	return MGL_OK;
+}
+/* one u64 of every rank, in rank order, to every rank (`all`: world entries).  The host form reads every key that comm_min_u64
+ * takes the minimum of, between the same two barriers; the RCCL form borrows the chain's stream and allocates world + 1 words for
+ * the call (the chain's own scratch holds 64, a communicator up to 256 ranks) */
+static int comm_allgather_u64(mgl_sa* sa, mgl_comm* comm, uint64_t mine, uint64_t* all)
+{
+	if (comm->kind == MGL_COMM_SHM) {
+		ShmHdr* h = (ShmHdr*)comm->map;
+		h->keys[comm->rank] = mine;
+		int rc = shm_barrier(comm);
+		if (rc) return rc;
+		for (int r = 0; r < comm->world; r++) all[r] = h->keys[r];
+		return shm_barrier(comm); /* nobody writes its next word before everybody has read these */
+	}
+	if (!sa) return fail(MGL_EINVAL, "an RCCL all-gather needs a chain (stream)");
+	struct Tmp {
+		uint64_t* d = nullptr;
+		~Tmp() { dfree(d); }
+	} tmp;
+	HIPCHK(hipMalloc(&tmp.d, sizeof(uint64_t) * ((size_t)comm->world + 1u)));
+	HIPCHK(hipMemcpyAsync(tmp.d, &mine, sizeof mine, hipMemcpyHostToDevice, sa->stream));
+	const int nrc = comm->all_gather(tmp.d, tmp.d + 1, 1, MGL_NCCL_UINT64, comm->comm, sa->stream);
+	if (nrc != 0) {
+		(void)hipStreamSynchronize(sa->stream); /* the copy above reads a local and writes what tmp frees */
+		return fail(MGL_EDEVICE, std::string("ncclAllGather: ") + (comm->errstr ? comm->errstr(nrc) : "?"));
+	}
+	HIPCHK(hipMemcpyAsync(all, tmp.d + 1, sizeof(uint64_t) * (size_t)comm->world, hipMemcpyDeviceToHost, sa->stream));
 	HIPCHK(hipStreamSynchronize(sa->stream));
 	return MGL_OK;
 }
@@ -300,6 +340,14 @@ extern "C" int mgl_comm_min_u64(mgl_comm* comm, uint64_t mine, uint64_t* out)
 	return comm_min_u64(nullptr, comm, mine, out);
 }
 
+/* the same for the all-gather: every rank's word in rank order (`all_out`: mgl_comm_world entries) */
+extern "C" int mgl_comm_allgather_u64(mgl_comm* comm, uint64_t mine, uint64_t* all_out)
+{
+	if (!comm || !all_out) return fail(MGL_EINVAL, "null argument");
+	if (comm->kind != MGL_COMM_SHM) return fail(MGL_EINVAL, "mgl_comm_allgather_u64: host transport only (the RCCL form needs a chain's stream)");
+	return comm_allgather_u64(nullptr, comm, mine, all_out);
+}
+
 /* the device buffer that holds packets_best right now */
 static const mgl_pk* best_slab_device(mgl_sa* sa, const Control& c)
 {
@@ -314,6 +362,23 @@ static int adopt_best_device(mgl_sa* sa, const mgl_pk* src, uint64_t cost, Contr
 	c.best_is_current = 0;
 	sa->best_unverified = true;
 	return write_ctl(sa, sa->base, &c);
+}
+
+/* the second half of mgl_sa_exchange_best: the winner's packed slab to everybody, 8 bytes per position (RCCL: HBM to HBM); a rank
+ * whose best is dearer, or that has none, adopts it (*adopted, nullable, says so).  `c`: the chain's control block as just read */
+static int broadcast_best_and_adopt(mgl_sa* sa, mgl_comm* comm, Control& c, int winner, uint64_t wcost, bool* adopted)
+{
+	if (adopted) *adopted = false;
+	const bool i_win = winner == comm->rank;
+	mgl_pk* recv = sa->scratch.v.slab; /* the parity hooks' scratch slab doubles as the landing area */
+	int rc;
+	if ((rc = comm_broadcast_slab(sa, comm, best_slab_device(sa, c), recv, (size_t)sa->n, winner)) != MGL_OK) return rc;
+	if (!i_win && (c.best_cost == 0 || wcost < c.best_cost)) {
+		if (adopted) *adopted = true;
+		return adopt_best_device(sa, recv, wcost, c);
+	}
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	return MGL_OK;
 }
 
 extern "C" int mgl_sa_exchange_best(mgl_sa* sa, mgl_comm* comm, int* winner_rank, uint64_t* winner_cost)
@@ -333,13 +398,8 @@ extern "C" int mgl_sa_exchange_best(mgl_sa* sa, mgl_comm* comm, int* winner_rank
 	if (winner_rank) *winner_rank = winner;
 	if (winner_cost) *winner_cost = wcost == MGL_KEY_NONE ? 0 : wcost;
 	if (wcost == MGL_KEY_NONE || comm->world == 1) return MGL_OK; /* nobody has a best slab yet / nobody to send it to */
-	/* (2) the winner's packed slab: 8 bytes per position (RCCL: HBM to HBM) */
-	const bool i_win = winner == comm->rank;
-	mgl_pk* recv = sa->scratch.v.slab; /* the parity hooks' scratch slab doubles as the landing area */
-	if ((rc = comm_broadcast_slab(sa, comm, best_slab_device(sa, c), recv, (size_t)sa->n, winner)) != MGL_OK) return rc;
-	if (!i_win && (c.best_cost == 0 || wcost < c.best_cost)) return adopt_best_device(sa, recv, wcost, c);
-	HIPCHK(hipStreamSynchronize(sa->stream));
-	return MGL_OK;
+	/* (2) the winner's packed slab */
+	return broadcast_best_and_adopt(sa, comm, c, winner, wcost, nullptr);
 }
 
 /* the same hand-over through host memory, for transports other than the library's own (tests use gloo) */
@@ -454,5 +514,120 @@ extern "C" int mgl_sa_exchange_cross(mgl_sa* sa, mgl_comm* comm, uint32_t grain,
 	mgl_cross_stats st;
 	if ((rc = cross_best_scratch(sa, grain, true, &st))) return rc;
 	if (stats) *stats = st;
+	return MGL_OK;
+}
+
+/* ---- crossing exchange of all chains: the parents are the distinct best slabs of every chain, up to MGL_XO_MAX_PARENTS */
+/* The selection every rank makes from the same gathered words: the ranks that hold a best slab in ascending key order (cost, then
+ * rank), skipping a rank whose (cost, hash) an already selected one has, until MGL_XO_MAX_PARENTS are chosen.  Equal hashes of
+ * equal-cost slabs are taken for equal slabs: a collision can only drop a parent, never cross a wrong one in.  Returns D. */
+static uint32_t cross_all_select(const uint64_t* keys, const uint64_t* hashes, int world, uint32_t parent_rank[MGL_XO_MAX_PARENTS], uint32_t* with_best)
+{
+	std::vector<std::pair<uint64_t, uint32_t>> order; /* (key, the rank it came from) */
+	for (int r = 0; r < world; r++)
+		if ((keys[r] >> 8) != MGL_KEY_NONE) order.push_back(std::make_pair(keys[r], (uint32_t)r));
+	std::sort(order.begin(), order.end());
+	*with_best = (uint32_t)order.size();
+	uint32_t D = 0;
+	for (size_t i = 0; i < order.size() && D < MGL_XO_MAX_PARENTS; i++) {
+		const uint32_t r = order[i].second;
+		bool seen = false;
+		for (uint32_t p = 0; p < D && !seen; p++) seen = (keys[parent_rank[p]] >> 8) == (keys[r] >> 8) && hashes[parent_rank[p]] == hashes[r];
+		if (!seen) parent_rank[D++] = r;
+	}
+	return D;
+}
+/* D >= 2 parents: their owners broadcast them into the slots of the crossover's slab buffer, every rank makes the same child and
+ * takes the same decision.  *fell_back: a rank could not allocate the buffers, so nothing was sent and nothing crossed */
+static int cross_all_parents(mgl_sa* sa, mgl_comm* comm, Control& c, uint32_t D, const uint32_t* parent_rank, const uint64_t* keys, uint32_t grain,
+                             mgl_cross_stats* st, bool* fell_back)
+{
+	const size_t n = sa->n;
+	XoBufs x;
+	/* a rank that cannot allocate must not leave the others waiting in a broadcast: everybody learns of it first */
+	const uint64_t ok = xo_alloc(sa, x, D) == MGL_OK ? 1u : 0u;
+	uint64_t all_ok = 0;
+	int rc = comm_min_u64(sa, comm, ok, &all_ok);
+	if (rc) return rc;
+	*fell_back = all_ok == 0;
+	if (*fell_back) return MGL_OK;
+	for (uint32_t p = 0; p < D; p++) {
+		mgl_pk* slot = x.slabs + (size_t)p * n;
+		const int owner = (int)parent_rank[p];
+		if (owner == comm->rank) HIPCHK(hipMemcpyAsync(slot, best_slab_device(sa, c), sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
+		if ((rc = comm_broadcast_slab(sa, comm, slot, slot, n, owner)) != MGL_OK) return rc;
+	}
+	if ((rc = xo_run(sa, x, D, grain, st))) return rc;
+	for (uint32_t p = 0; p < D; p++)
+		if (st->parent_cost[p] != keys[parent_rank[p]] >> 8)
+			return fail(MGL_EINVAL, "mgl_sa_exchange_cross_all: a chain's best slab does not cost what the chain published");
+	const uint64_t cheapest = st->parent_cost[0];
+	if (st->child_cost < cheapest) {
+		st->adopted = 2;
+		rc = xo_set_best(sa, x.child, st->child_cost, c, true);
+	} else if (c.best_cost == 0 || cheapest < c.best_cost) {
+		st->adopted = 1;
+		rc = xo_set_best(sa, x.slabs, cheapest, c, true);
+	}
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(sa->stream)); /* the buffers go away with x */
+	return MGL_OK;
+}
+
+extern "C" int mgl_slab_hash(mgl_sa* sa, const mgl_packet* packets, uint64_t* hash)
+{
+	if (!sa || !hash) return fail(MGL_EINVAL, "null argument");
+	HIPCHK(hipSetDevice(sa->device));
+	int rc;
+	if (packets) {
+		if ((rc = import_slab(sa, packets, sa->scratch.v.slab))) return rc;
+		return slab_hash_device(sa, sa->scratch.v.slab, hash);
+	}
+	Control c;
+	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
+	if (c.best_cost == 0) return fail(MGL_EINVAL, "mgl_slab_hash: the chain has no best slab yet");
+	return slab_hash_device(sa, best_slab_device(sa, c), hash);
+}
+
+extern "C" int mgl_sa_exchange_cross_all(mgl_sa* sa, mgl_comm* comm, uint32_t grain, mgl_cross_all_stats* stats)
+{
+	if (!sa || !comm) return fail(MGL_EINVAL, "null argument");
+	if (comm->device != sa->device) return fail(MGL_EINVAL, "mgl_sa_exchange_cross_all: communicator and chain live on different devices");
+	HIPCHK(hipSetDevice(sa->device));
+	mgl_cross_all_stats out;
+	memset(&out, 0, sizeof out);
+	out.own_parent = UINT32_MAX;
+	if (stats) *stats = out;
+	Control c;
+	int rc = read_ctl(sa, sa->base, &c);
+	if (rc) return rc;
+	/* (1) publish: the key of mgl_sa_exchange_best and the hash of the best slab, one all-gather each */
+	uint64_t hash = 0;
+	if (c.best_cost && (rc = slab_hash_device(sa, best_slab_device(sa, c), &hash))) return rc;
+	const uint64_t mine = ((c.best_cost ? c.best_cost : MGL_KEY_NONE) << 8) | (uint64_t)(comm->rank & 0xFF);
+	std::vector<uint64_t> keys((size_t)comm->world), hashes((size_t)comm->world);
+	if ((rc = comm_allgather_u64(sa, comm, mine, keys.data())) != MGL_OK) return rc;
+	if ((rc = comm_allgather_u64(sa, comm, hash, hashes.data())) != MGL_OK) return rc;
+	/* (2) select: the same parents, in the same order, on every rank */
+	const uint32_t D = cross_all_select(keys.data(), hashes.data(), comm->world, out.parent_rank, &out.chains_with_best);
+	out.distinct = D;
+	for (uint32_t p = 0; p < D; p++)
+		if ((int)out.parent_rank[p] == comm->rank) out.own_parent = p;
+	/* (3) act */
+	bool fell_back = false;
+	if (D >= 2) {
+		rc = cross_all_parents(sa, comm, c, D, out.parent_rank, keys.data(), grain, &out.cross, &fell_back);
+		out.fell_back = fell_back ? 1u : 0u;
+	}
+	if (rc == MGL_OK && (D == 1 || fell_back) && comm->world > 1) {
+		/* one slab is all there is (or all the devices have room for): mgl_sa_exchange_best's broadcast of the cheapest */
+		bool adopted = false;
+		memset(&out.cross, 0, sizeof out.cross);
+		rc = broadcast_best_and_adopt(sa, comm, c, (int)out.parent_rank[0], keys[out.parent_rank[0]] >> 8, &adopted);
+		out.cross.adopted = adopted ? 1u : 0u;
+	}
+	if (D == 1 || fell_back) out.cross.parent_cost[0] = keys[out.parent_rank[0]] >> 8; /* what every chain's best slab costs now */
+	if (rc) return rc;
+	if (stats) *stats = out;
 	return MGL_OK;
 }

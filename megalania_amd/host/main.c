@@ -31,7 +31,7 @@ static void usage(const char* argv0)
 	        "          [--match-finder nearest|frontier [--mf-depth N]] [--parse-sweep [--parse-sweep-table]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]\n"
-	        "          [--exchange best|cross [--cross-grain N]]] filename\n"
+	        "          [--exchange best|cross|cross-all [--cross-grain N]]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
 	        "  --save-slab  after every epoch, write the best packet slab (resumable checkpoint)\n"
 	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb)\n"
@@ -73,11 +73,15 @@ static void usage(const char* argv0)
 	        "               e.g. the launcher's pid: a file left by an earlier run is then never mistaken for this one's);\n"
 	        "               --transport shm stages the exchange through PATH itself (host shared memory) instead of RCCL:\n"
 	        "               for chains that share one GPU.  --save-slab: chain R > 0 writes to <file>.rankR\n"
-	        "  --exchange best|cross  what the chains do with the cheapest best slab after an epoch: every other chain adopts it\n"
+	        "  --exchange best|cross|cross-all  what the chains do with the cheapest best slab after an epoch: every other chain adopts it\n"
 	        "               (best, default), or recombines it with its own best slab region by region between the positions where\n"
 	        "               the two walks agree and keeps the child if it is cheaper than both (cross; mgl_sa_exchange_cross);\n"
 	        "               one plain exchange follows the last epoch, so that rank 0 writes the overall best.  --cross-grain N:\n"
-	        "               about one cut per N input bytes (default 64; 1 = every joint); only with --exchange cross\n"
+	        "               about one cut per N input bytes (default 64; 1 = every joint); only with --exchange cross or cross-all.\n"
+	        "               cross-all (mgl_sa_exchange_cross_all): the chains publish cost and hash of their best slabs, the distinct\n"
+	        "               ones (the 8 cheapest at most) travel to every chain and all chains make the same child of them; it\n"
+	        "               becomes every chain's best slab if it is cheaper than the cheapest parent, which the dearer chains adopt\n"
+	        "               otherwise.  Every chain then holds a best slab of the same cost: no plain exchange follows\n"
 	        "  --accept     what a step of K neighbours takes: the best acceptable one (single), every one that is\n"
 	        "               the best of its own window (bulk), or whichever pays (auto, default)\n", argv0);
 }
@@ -323,7 +327,7 @@ int main(int argc, char** argv)
 	const char* comm_path = NULL;
 	unsigned long long comm_nonce = 0;
 	int transport_shm = 0;
-	int exchange_cross = 0, cross_grain_given = 0;
+	int exchange_cross = 0, exchange_all = 0, cross_grain_given = 0;
 	uint32_t cross_grain = 0;
 	for (int i = 1; i < argc; i++) {
 		const char* a = argv[i];
@@ -358,7 +362,9 @@ int main(int argc, char** argv)
 			else if (strcmp(v, "rccl") != 0) { usage(argv[0]); return -1; }
 		}
 		else if (!strcmp(a, "--exchange")) {
+			exchange_cross = exchange_all = 0;
 			if (!strcmp(v, "cross")) exchange_cross = 1;
+			else if (!strcmp(v, "cross-all")) exchange_all = 1;
 			else if (strcmp(v, "best") != 0) { usage(argv[0]); return -1; }
 		}
 		else if (!strcmp(a, "--cross-grain")) { cross_grain = (uint32_t)strtoul(v, NULL, 0); cross_grain_given = 1; }
@@ -428,8 +434,8 @@ int main(int argc, char** argv)
 		usage(argv[0]);
 		return -1;
 	}
-	if (cross_grain_given && !exchange_cross) {
-		fprintf(stderr, "Error: --cross-grain needs --exchange cross\n");
+	if (cross_grain_given && !exchange_cross && !exchange_all) {
+		fprintf(stderr, "Error: --cross-grain needs --exchange cross or --exchange cross-all\n");
 		usage(argv[0]);
 		return -1;
 	}
@@ -625,7 +631,22 @@ int main(int argc, char** argv)
 			fprintf(stderr, "current file size: %f\tbest: %f\tstep: %u\tepoch: %04u\t%.0f evals/s\n",
 			        18 + st.current_cost / 16384.f, 18 + st.best_cost / 16384.f, phase + 1, epoch,
 			        st.gpu_ms_total > 0 ? st.evaluations / (st.gpu_ms_total * 1e-3) : 0.0);
-			if (comm) {
+			if (comm && exchange_all) {
+				mgl_cross_all_stats as;
+				if (mgl_sa_exchange_cross_all(sa, comm, cross_grain, &as) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+				char owners[8 * MGL_XO_MAX_PARENTS + 1] = "";
+				for (uint32_t p = 0; p < as.distinct; p++) snprintf(owners + strlen(owners), sizeof owners - strlen(owners), p ? " %u" : "%u", as.parent_rank[p]);
+				const uint64_t now = as.cross.adopted == 2 ? as.cross.child_cost : as.cross.parent_cost[0];
+				if (as.cross.parents)
+					fprintf(stderr, "exchange: cross-all: %u distinct of %u best slabs, parents from chains [%s], cheapest %f bytes, child %f bytes of %llu regions, "
+					        "adopted %u, best %f bytes, %.2f ms\n", as.distinct, as.chains_with_best, owners, 18 + as.cross.parent_cost[0] / 16384.f,
+					        18 + as.cross.child_cost / 16384.f, (unsigned long long)(as.cross.boundaries - 1), as.cross.adopted, 18 + now / 16384.f, as.cross.gpu_ms);
+				else if (as.distinct)
+					fprintf(stderr, "exchange: cross-all: %u distinct of %u best slabs, parents from chains [%s], nothing crossed%s, adopted %u, best %f bytes\n",
+					        as.distinct, as.chains_with_best, owners, as.fell_back ? " (a chain had no room for the buffers)" : "", as.cross.adopted, 18 + now / 16384.f);
+				else
+					fprintf(stderr, "exchange: cross-all: no chain has a best slab yet, adopted 0\n");
+			} else if (comm) {
 				int winner = -1;
 				uint64_t wcost = 0;
 				mgl_cross_stats xs;

@@ -76,3 +76,12 @@ def exchange_cross_native(chain, comm, grain: int = 0):
     both.  Chains may hold different best slabs afterwards; follow the last one with `exchange_best_native` where a
     common slab is wanted.  Returns (winner rank, winner cost, this chain's crossover stats)."""
     return chain.exchange_cross(comm, grain)
+
+
+def exchange_cross_all_native(chain, comm, grain: int = 0):
+    """The exchange that crosses every chain's best slab (mgl_sa_exchange_cross_all): keys and slab hashes are all-gathered,
+    the distinct best slabs (the 8 cheapest at most, cheapest first) are broadcast by their owners, and every chain makes the
+    same child of them.  It becomes every chain's best slab if it is cheaper than the cheapest parent; otherwise the dearer
+    chains adopt that parent.  Every chain holds a best slab of the same cost afterwards.  Returns the stats dict of
+    binding.SA.exchange_cross_all."""
+    return chain.exchange_cross_all(comm, grain)
