@@ -453,6 +453,7 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * call; then, as [8..15], the same eight slots live, which the end of a step leaves at zero),
  * 11 parallel-builder totals, 12 / 13 match index (bucket offsets / positions), 14 accept-path
  * counters, 15 pick records, 16 the control block, 21 the windows (target, end) of the last costed neighbours, 22 their soft ends | dep << 31,
+ * 23 / 24 / 25 their costs (u64), journal lengths and packets walked,
  * 30-35 / 40-45 / 50-55 / 60-65 positions / ranks / run starts / next byte of the exact-length orders D = 2..7,
  * 70-73 and 74-77 positions, ranks, run starts, next eight bytes of the 8- and 16-byte orders, 80 three u64 host counters: bulk
  * steps whose moves were patched into the base structures at once (batch accept), those that began so and fell back to the

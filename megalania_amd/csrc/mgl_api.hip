@@ -117,6 +117,8 @@ struct mgl_sa {
 	uint32_t big_waves = MGL_BIG_WAVES; /* wavefronts of a second-pass workgroup (mgl_debug_set key 7 lowers it for tests) */
 	uint32_t chg_cap = MGL_CHG_CAP; /* events per first-pass list */
 	uint32_t per_wave_pick, per_wave_rest, pick_waves; /* LDS per wavefront of the two halves of the split launch */
+	bool fuse;              /* the two halves as one launch (k_neighbours2<false, MGL_NBR_PICKWALK>); MGL_NO_FUSE=1: two launches */
+	uint32_t fused_lds;     /* its dynamic LDS: one wavefront, the larger of the two halves' areas */
 	size_t b2_bytes;
 	BigScratch big;
 	uint32_t* d_todo2;
@@ -479,11 +481,20 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 #endif
 		/* (the third stream needs no wait of its own for the fork: its first wait, ev_rest[0], is recorded on the main stream
 		 * behind the fork, for any number of slices) */
-		/* the first two thirds of the split form -- pick, then window walk -- of every slice; slices alternate between the two
-		 * streams, ev_rest[h] is recorded behind slice h's walk */
+		/* the first two thirds of the split form -- pick, then window walk -- of every slice, as one fused launch per slice (or as
+		 * two: MGL_NO_FUSE, MGL_F_PROFILE); slices alternate between the two streams, ev_rest[h] is recorded behind slice h's walk */
 		for (uint32_t h = 0; h < slices; h++) {
 			const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
 			hipStream_t st = (h & 1u) ? sa->stream2 : sa->stream;
+			if (sa->fuse && !sa->d_prof) {
+				/* pick and walk of a neighbour in one wavefront: no barrier on the slice's slowest pick in front of its walks.  Under
+				 * MGL_F_PROFILE the two halves run as two launches (below): the stage marks are the pick half's */
+				hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_PICKWALK>), dim3(j1 - j0), dim3(64), sa->fused_lds, st, sa->ctx,
+				                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->fused_lds, sa->d_todo, sa->d_counts,
+				                   (unsigned long long*)nullptr, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICKWALK>");
+				HIPCHK(hipEventRecord(sa->ev_rest[h], st));
+				continue;
+			}
 			/* under MGL_F_PROFILE the instance that carries the stage marks (tools/pick_waves.py); normal runs hold none of them */
 			hipLaunchKernelGGL((sa->d_prof ? k_neighbours2<false, MGL_NBR_PICK, true> : k_neighbours2<false, MGL_NBR_PICK>), dim3((j1 - j0 + sa->pick_waves - 1) / sa->pick_waves), dim3(64 * sa->pick_waves),
 			                   (MGL_PICK_T_GLOBAL ? 0u : 4096u) + sa->pick_waves * sa->per_wave_pick, st, sa->ctx,
@@ -970,6 +981,9 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_REST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES)));
+		sa->fuse = getenv("MGL_NO_FUSE") == nullptr;
+		sa->fused_lds = (MGL_PICK_T_GLOBAL ? 0u : 4096u) + (sa->per_wave_pick > sa->per_wave_rest ? sa->per_wave_pick : sa->per_wave_rest);
+		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICKWALK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->fused_lds));
 		HIPCHK(hipMalloc(&sa->d_pickrec, sizeof(uint4) * K));
 		HIPCHK(hipMalloc(&sa->d_pickstate, sizeof(uint4) * 2 * K));
 		sa->split_nbr = getenv("MGL_NO_SPLIT") == nullptr;
@@ -2469,6 +2483,9 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 75: src = sa->d_hex_rank; sz = sizeof(uint32_t) * (sa->n - 1); break;
 	case 76: src = sa->d_hex_run; sz = sizeof(uint32_t) * (sa->n - 1); break;
 	case 77: src = sa->d_hex_nx8; sz = sizeof(uint64_t) * (sa->n - 1); break;
+	case 23: src = sa->nbr.cost; sz = sizeof(uint64_t) * sa->cfg.neighbours_per_step; break;   /* costs, */
+	case 24: src = sa->nbr.ndiffs; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* journal lengths */
+	case 25: src = sa->nbr.walked; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* and packets walked of the last costed neighbours */
 	case 22: src = sa->nbr.win2; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* soft ends | dep << 31 */
 	case 21: src = sa->nbr.win; sz = sizeof(uint32_t) * 2 * sa->cfg.neighbours_per_step; break; /* windows of the last costed neighbours */
 	case 11: src = sa->pb.acc; sz = sa->pb.acc ? sizeof(unsigned long long) * 8 : 0; break; /* parallel builder totals */

@@ -587,8 +587,10 @@ __device__ __forceinline__ uint32_t literal_run_events(const DevCtx& c, Changes&
 }
 
 /* The base's adaptive model before the first base packet at or after y, into LDS: dense
- * checkpoint + replay of < 2^MGL_CK2_SHIFT bytes of base packets. */
-__device__ void model_load(const DevCtx& c, const Base2& b, uint16_t* probs, const uint16_t* T, uint32_t y, uint32_t lane)
+ * checkpoint + replay of < 2^MGL_CK2_SHIFT bytes of base packets.
+ * model_load_inl is the body, always inlined: the fused instance calls it directly -- left to the inliner it is a call there,
+ * and a call takes the kernel's DevCtx and Base2 arguments by reference, i.e. a copy of both in scratch (640 B/lane). */
+__device__ __forceinline__ void model_load_inl(const DevCtx& c, const Base2& b, uint16_t* probs, const uint16_t* T, uint32_t y, uint32_t lane)
 {
 	const uint32_t ck = y >> MGL_CK2_SHIFT;
 	/* 16 bytes per lane and four loads in flight per trip (rows are 16-byte multiples, 16-byte aligned on both sides):
@@ -656,6 +658,10 @@ __device__ void model_load(const DevCtx& c, const Base2& b, uint16_t* probs, con
 		wave_sync();
 	}
 }
+__device__ void model_load(const DevCtx& c, const Base2& b, uint16_t* probs, const uint16_t* T, uint32_t y, uint32_t lane)
+{
+	model_load_inl(c, b, probs, T, y, lane);
+}
 
 /* the Walk-based helpers of the full-walk path read the input through Walk's window */
 __device__ __forceinline__ void walk_from_state(Walk& w, const mgl_wstate& st)
@@ -694,7 +700,11 @@ struct BigScratch {
  *   MGL_NBR_REST  recomputes the cheap part, takes the pick from `pickrec`, then window walk and
  *                 chain re-simulation.  A repair that needs another top-K pick (rare) hands the
  *                 neighbour to the next pass;
- *   MGL_NBR_FULL  the whole thing in one kernel (the BIG second pass, which starts from scratch). */
+ *   MGL_NBR_FULL  the whole thing in one kernel (the BIG second pass, which starts from scratch);
+ *   MGL_NBR_PICKWALK  the two halves' bodies one behind the other in one wavefront (the split form's default launch): the
+ *                 same code on the same inputs, but no launch boundary -- and so no wait for the slice's slowest top-K
+ *                 query -- between a neighbour's pick and its walk.  Not the phase machine as one kernel (246 VGPRs):
+ *                 nothing but a handful of wave-uniform scalars (PickHand) lives across the top-K. */
 #ifndef MGL_PICK_T_GLOBAL
 #define MGL_PICK_T_GLOBAL 1 /* the pick half reads the 4 KiB cost table through the vector cache instead of keeping a copy in LDS: 16 instead of 11 wavefronts per CU at 10 MB (c3 neighbour kernels - 5 %), no change at 100 KB */
 #endif
@@ -704,6 +714,19 @@ struct BigScratch {
 #define MGL_NBR_FULL 0
 #define MGL_NBR_PICK 1
 #define MGL_NBR_REST 2
+#define MGL_NBR_PICKWALK 3
+/* what the pick body of the fused instance hands to its walk body, in place of `pickstate` and the read of `pickrec`: all
+ * wave-uniform, so scalar registers */
+struct PickHand {
+	uint32_t target, rng_n;      /* rng_n: the RNG position behind the grow/shrink draw, or behind the pick */
+	uint32_t ctx_state, dists[4]; /* walk state at the target */
+	mgl_pk first, second;        /* the base's packets at the target and behind it (second: only with HAND_SECOND) */
+	mgl_pk m_first, m_second;    /* the mutated packet(s): grow/shrink, or the top-K pick */
+	uint32_t flags;
+};
+#define MGL_HAND_MUTATED 1u /* grow/shrink: no pick */
+#define MGL_HAND_SECOND 2u  /* ... that rewrote the packet behind the target too */
+#define MGL_HAND_OK 4u      /* the top-K pick found a candidate */
 /* ---- the second pass's re-simulations, by the whole workgroup
  *
  * A second-pass workgroup is MGL_BIG_WAVES wavefronts on one neighbour.  Wavefront 0 evaluates the neighbour (nbr2_one);
@@ -797,13 +820,15 @@ __device__ __forceinline__ void coop_helpers(const DevCtx& c, const Base2& b, co
 }
 /* one neighbour, by the wavefront `wid` of its workgroup; `unit` = the neighbour's index in this launch's slice
  * (regular launch) or its slot in the second pass's list (BIG) */
-template <bool BIG, int MODE, bool PROF = false>
+template <bool BIG, int MODE, bool PROF = false, bool FUSED = false>
 __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Control* ctl, uint64_t seed,
                                          uint64_t step_override, uint32_t K, const NbrOut& out, uint32_t per_wave_bytes,
                                          uint32_t* todo, uint32_t* todo_count, unsigned long long* prof_acc,
                                          const BigScratch& big, uint4* pickrec, uint32_t j_base, uint32_t j_end, uint4* pickstate,
-                                         unsigned char* smem, const uint16_t* T, uint32_t unit, uint32_t lane, uint32_t wid)
+                                         unsigned char* smem, const uint16_t* T, uint32_t unit, uint32_t lane, uint32_t wid,
+                                         PickHand* hand = nullptr)
 {
+	static_assert(!FUSED || (!BIG && !PROF && (MODE == MGL_NBR_PICK || MODE == MGL_NBR_REST)), "the fused instance is the two halves of the regular launch");
 	uint32_t j = j_base + unit; /* [j_base, j_end): the slice of the step this launch covers */
 	uint32_t slot = 0;
 	const unsigned long long t_begin = prof_acc ? __builtin_readcyclecounter() : 0ull;
@@ -865,7 +890,11 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	uint32_t target;
 	mgl_wstate nb; /* neighbour's walk state */
 	if (MODE == MGL_NBR_REST && lane == 0) big.sim_hdr[j] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
-	if (MODE == MGL_NBR_REST) {
+	if (MODE == MGL_NBR_REST && FUSED) {
+		target = hand->target; rng.n = hand->rng_n;
+		nb.pos = target; nb.ctx_state = hand->ctx_state;
+		nb.dists[0] = hand->dists[0]; nb.dists[1] = hand->dists[1]; nb.dists[2] = hand->dists[2]; nb.dists[3] = hand->dists[3];
+	} else if (MODE == MGL_NBR_REST) {
 		const uint4 s0 = pickstate[2u * j], s1 = pickstate[2u * j + 1u];
 		target = s0.x; rng.n = s0.y;
 		nb.pos = target; nb.ctx_state = s0.z;
@@ -878,7 +907,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		target = uni(c.strat_tgt[j]); /* stratified_target(), worked out for the whole step by k_targets */
 		rng.n = 1;
 		nb = uni_state(base_state_at(b, target));
-		if (MODE == MGL_NBR_PICK && lane == 0) {
+		if (MODE == MGL_NBR_PICK && !FUSED && lane == 0) {
 			pickstate[2u * j] = make_uint4(target, rng.n, nb.ctx_state, nb.dists[0]);
 			pickstate[2u * j + 1u] = make_uint4(nb.dists[1], nb.dists[2], nb.dists[3], 0u);
 		}
@@ -899,10 +928,14 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 			target = uni(bits ? (wd << 6) + ctz64(bits) : 0u);
 		}
 		nb = uni_state(base_state_at(b, target));
-		if (MODE == MGL_NBR_PICK && lane == 0) {
+		if (MODE == MGL_NBR_PICK && !FUSED && lane == 0) {
 			pickstate[2u * j] = make_uint4(target, rng.n, nb.ctx_state, nb.dists[0]);
 			pickstate[2u * j + 1u] = make_uint4(nb.dists[1], nb.dists[2], nb.dists[3], 0u);
 		}
+	}
+	if (MODE == MGL_NBR_PICK && FUSED) {
+		hand->target = target; hand->ctx_state = nb.ctx_state;
+		hand->dists[0] = nb.dists[0]; hand->dists[1] = nb.dists[1]; hand->dists[2] = nb.dists[2]; hand->dists[3] = nb.dists[3];
 	}
 	/* the pick half keeps its own stage clock (PickProf: stages behind the second half's lifetimes in the profile buffer) */
 	Prof prof;
@@ -918,19 +951,30 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	Walk tw; /* scratch Walk for top-K (its window is the input window at the query position) */
 
 	/* ---- mutate, packet_slab_neighbour.c:119-152 */
-	win_cover(win, c, b.slab, pos, lane);
-	const mgl_pk first = win_pk(win, pos);
+	mgl_pk first;
+	if (MODE == MGL_NBR_REST && FUSED) first = hand->first; /* the walk covers its window itself */
+	else { win_cover(win, c, b.slab, pos, lane); first = win_pk(win, pos); }
+	if (MODE == MGL_NBR_PICK && FUSED) hand->first = uni64(first);
 	mgl_pk m_first = first, m_second = 0;
 	bool second_set = false, mutated = false;
 	prof_mark(prof, 0, lane); /* state at target */
 	if (c.diag_stop == 1) { if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = first; } return; }
-	if (!(BIG && resumed) && pos + 1 < c.n && (nbr_draw(rng) % 2u) == 0) {
+	if (MODE == MGL_NBR_REST && FUSED) {
+		/* the pick body's grow/shrink decision: journalled here, not made again */
+		mutated = (hand->flags & MGL_HAND_MUTATED) != 0; second_set = (hand->flags & MGL_HAND_SECOND) != 0;
+		if (mutated) {
+			m_first = hand->m_first; m_second = hand->m_second;
+			journal_set(jn, pos, first, m_first, lane);
+			if (second_set) journal_set(jn, pos + 1, hand->second, m_second, lane);
+		}
+	} else if (!(BIG && resumed) && pos + 1 < c.n && (nbr_draw(rng) % 2u) == 0) {
 		const mgl_pk second = uni64(b.slab[pos + 1]);
 		const uint32_t ft = mgl_pk_type(first), flen = mgl_pk_len(first);
 		const uint32_t st = mgl_pk_type(second), slen = mgl_pk_len(second), sdist = mgl_pk_dist(second);
 		if ((ft == MGL_LONG_REP || ft == MGL_MATCH) && flen > 2) {
 			m_second = mgl_pack(ft, mgl_pk_dist(first), flen - 1);
 			m_first = MGL_PK_LITERAL;
+			if (MODE == MGL_NBR_PICK && FUSED) hand->second = uni64(second);
 			if (MODE != MGL_NBR_PICK) { journal_set(jn, pos, first, m_first, lane); journal_set(jn, pos + 1, second, m_second, lane); }
 			second_set = true; mutated = true;
 		} else if ((ft == MGL_LITERAL || ft == MGL_SHORT_REP) && (st == MGL_MATCH || st == MGL_LONG_REP)) {
@@ -948,6 +992,10 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	 * position) and the final one.  Halves the code size and the register pressure. */
 	enum { P_MODEL, P_SIM, P_TOPK, P_WALK, P_OUT };
 	uint32_t phase = mutated ? P_WALK : P_MODEL;
+	if (MODE == MGL_NBR_PICK && FUSED) {
+		hand->m_first = uni64(m_first); hand->m_second = uni64(m_second); hand->rng_n = uni(rng.n);
+		hand->flags = (mutated ? MGL_HAND_MUTATED : 0u) | (second_set ? MGL_HAND_SECOND : 0u);
+	}
 	if (MODE == MGL_NBR_PICK && mutated) return; /* nothing to pick: the second half redoes the grow/shrink itself */
 	/* where the pick's sources start and end depends on the target and the rep distances alone: searched for here, all
 	 * sources level by level, in front of the model load instead of source by source behind it */
@@ -1005,7 +1053,8 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		phase = P_MODEL;
 	}
 	if ((MODE == MGL_NBR_REST || (BIG && pickrec != nullptr)) && !mutated) { /* the host passes the pick records only when the split form ran */
-		const uint4 rec = pickrec[j];
+		const uint4 rec = (MODE == MGL_NBR_REST && FUSED) ? make_uint4((uint32_t)hand->m_first, (uint32_t)(hand->m_first >> 32), hand->rng_n, (hand->flags & MGL_HAND_OK) ? 1u : 0u)
+		                                                   : pickrec[j];
 		if (!(rec.w & 1u)) { generate_failed = true; phase = P_OUT; }
 		else {
 			m_first = (mgl_pk)rec.x | ((mgl_pk)rec.y << 32);
@@ -1039,7 +1088,8 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 				ch.cap = big.cap; ch.uctx_cap = big.uctx_cap;
 				spilled = true;
 			}
-			model_load(c, b, probs, T, pick_pos, lane);
+			if constexpr (FUSED) model_load_inl(c, b, probs, T, pick_pos, lane);
+			else model_load(c, b, probs, T, pick_pos, lane);
 			if (PROF) pick_prof_mark(&pp, 2, lane);
 			if (!pick_is_mutation) prof_mark(prof, 5, lane); /* repair: base model at the pick position */
 			if (pick_is_mutation) {
@@ -1080,7 +1130,8 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 			if constexpr (MODE == MGL_NBR_PICK) ok = pick_from_top_k<4, MGL_PICK_BATCH != 0, PROF>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked, &plan, &pp);
 			else ok = pick_from_top_k<1>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked);
 			if (MODE == MGL_NBR_PICK) {
-				if (lane == 0) pickrec[j] = make_uint4((uint32_t)picked, (uint32_t)(picked >> 32), rng.n, ok ? 1u : 0u);
+				if (lane == 0) pickrec[j] = make_uint4((uint32_t)picked, (uint32_t)(picked >> 32), rng.n, ok ? 1u : 0u); /* fused, too: the second pass restarts from it */
+				if (FUSED) { hand->m_first = uni64(picked); hand->rng_n = uni(rng.n); if (ok) hand->flags |= MGL_HAND_OK; }
 				if (PROF) pick_prof_mark(&pp, 14, lane);
 				if (PROF && pp.acc && lane == 0) pp.acc[2u * MGL_PICK_STAGES + j] = __builtin_readcyclecounter() - t_begin; /* a picking wavefront's lifetime */
 				return;
@@ -1322,7 +1373,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 }
 
 template <bool BIG, int MODE, bool PROF = false>
-__global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_BIG_WAVES : 64)), (MODE == MGL_NBR_FULL ? (BIG ? 1 : MGL_NBR_WAVES_PER_SIMD) : (MODE == MGL_NBR_REST ? MGL_REST_WAVES_PER_SIMD : 4))) k_neighbours2(DevCtx c, Base2 b, Control* ctl, uint64_t seed,
+__global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_BIG_WAVES : 64)), (MODE == MGL_NBR_FULL ? (BIG ? 1 : MGL_NBR_WAVES_PER_SIMD) : (MODE == MGL_NBR_REST ? MGL_REST_WAVES_PER_SIMD : 4))) /* MGL_NBR_PICKWALK: (64, 4) */ k_neighbours2(DevCtx c, Base2 b, Control* ctl, uint64_t seed,
                                                      uint64_t step_override, uint32_t K, NbrOut out, uint32_t per_wave_bytes,
                                                      uint32_t* todo, uint32_t* todo_count, unsigned long long* prof_acc,
                                                      BigScratch big, uint4* pickrec, uint32_t j_base, uint32_t j_end, uint4* pickstate)
@@ -1339,14 +1390,27 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_
 	if (BIG && threadIdx.x == 0) { CoopCmd* cmd = coop_cmd(smem, per_wave_bytes); cmd->gen = 0; cmd->op = MGL_COOP_SIM; }
 	/* 4 KiB as 256 16-byte units (the table is hipMalloc-aligned, T sits at the start of the LDS block); the second
 	 * half of the split form prices nothing (its re-simulation is k_sim's) and has no table: 4 KiB less per workgroup */
-	if (MODE == MGL_NBR_PICK && MGL_PICK_T_GLOBAL) {
+	if ((MODE == MGL_NBR_PICK || MODE == MGL_NBR_PICKWALK) && MGL_PICK_T_GLOBAL) {
 		T = const_cast<uint16_t*>(c.cost_tbl); /* read through the vector cache: 4 KiB less LDS per pick workgroup */
 	} else if (MODE != MGL_NBR_REST) {
 		for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) reinterpret_cast<uint4*>(T)[i] = reinterpret_cast<const uint4*>(c.cost_tbl)[i];
 		__syncthreads();
 	}
 	const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-	if (BIG) {
+	if constexpr (MODE == MGL_NBR_PICKWALK) {
+		/* one wavefront per workgroup: the pick body, then the walk body on the same LDS area (the pick's model and price
+		 * tables are dead by then).  Each body's returns end that body alone: a neighbour whose pick body returned early
+		 * (grow/shrink, a diagnostic stop) still gets its walk body, which takes the same decision from the same values. */
+		static_assert(!BIG && !PROF, "the fused instance is a regular launch without stage marks");
+		PickHand hand;
+		hand.target = 0; hand.rng_n = 0; hand.ctx_state = 0; hand.dists[0] = hand.dists[1] = hand.dists[2] = hand.dists[3] = 0;
+		hand.first = hand.second = hand.m_first = hand.m_second = 0; hand.flags = 0;
+		nbr2_one<false, MGL_NBR_PICK, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, pickstate, smem, T,
+		                                           blockIdx.x, lane, 0u, &hand);
+		wave_sync(); /* the walk body's journal and lists overwrite what the pick body's lanes read */
+		nbr2_one<false, MGL_NBR_REST, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, pickstate, smem, T,
+		                                           blockIdx.x, lane, 0u, &hand);
+	} else if (BIG) {
 		/* wavefront 0 takes the workgroup's neighbours one at a time; the others help with their re-simulations */
 		if (wid != 0) { coop_helpers(c, b, big, prof_acc, smem, per_wave_bytes, T, lane, wid); return; }
 		const uint32_t n = *big.todo_in_count;
