@@ -44,8 +44,11 @@ HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
     "mgl_range_encoder_new", "mgl_range_encoder_free", "mgl_perplexity_encoder_new", "mgl_file_output_new",
     "mgl_memory_output_new", "mgl_emit_stream", "mgl_stream_info_read", "mgl_stream_import",
+    "mgl_emit_stream_dict", "mgl_bcj_x86", "mgl_emit_xz", "mgl_stream_info_read_x",
 ]
 IMPORT_CLIP_WINDOW = 1
+IMPORT_X86 = 2
+FILTER_NONE, FILTER_X86 = 0, 4
 # the lc/lp/pb triples mgl_sa_create accepts, in the order mgl_props_sweep reports them
 PROPS_TRIPLES = [(lc, lp, pb) for lc in range(5) for lp in range(5 - lc) for pb in range(5)]
 
@@ -159,6 +162,10 @@ class ImportStats(C.Structure):
                 ("props_changes", C.c_uint64), ("error_pos", C.c_uint64), ("error", C.c_char_p)]
 
 
+class XzOptions(C.Structure):
+    _fields_ = [("filter", C.c_uint32), ("dict_size", C.c_uint32), ("check", C.c_uint32)]
+
+
 class MemorySink(C.Structure):
     _fields_ = [("buf", C.c_void_p), ("cap", C.c_size_t), ("len", C.c_size_t)]
 
@@ -252,6 +259,14 @@ def host_lib():
         L = C.CDLL(HOST_SO)
         L.mgl_emit_stream.restype = C.c_bool
         L.mgl_emit_stream.argtypes = [C.c_void_p, C.c_size_t, Properties, C.c_void_p, C.POINTER(OutputInterface)]
+        L.mgl_emit_stream_dict.restype = C.c_bool
+        L.mgl_emit_stream_dict.argtypes = [C.c_void_p, C.c_size_t, Properties, C.c_void_p, C.c_uint32, C.POINTER(OutputInterface)]
+        L.mgl_emit_xz.restype = C.c_bool
+        L.mgl_emit_xz.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, Properties, C.c_void_p, C.POINTER(XzOptions),
+                                  C.POINTER(OutputInterface)]
+        L.mgl_bcj_x86.restype = None
+        L.mgl_bcj_x86.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+        L.mgl_stream_info_read_x.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(StreamInfo), C.POINTER(C.c_uint32)]
         L.mgl_memory_output_new.argtypes = [C.POINTER(OutputInterface), C.POINTER(MemorySink)]
         L.mgl_stream_info_read.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(StreamInfo)]
         L.mgl_stream_import.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
@@ -287,6 +302,53 @@ def emit_stream(data: bytes, slab: np.ndarray, lc=0, lp=0, pb=0) -> bytes:
     return out[: sink.len].tobytes()
 
 
+def emit_stream_dict(data: bytes, slab: np.ndarray, dict_size: int, lc=0, lp=0, pb=0) -> bytes:
+    """emit_stream with `dict_size` (0 = 4 MiB) as the header's dictionary and as the window the slab is checked against."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    cap = 2 * len(buf) + 1024
+    out = np.zeros(cap, dtype=np.uint8)
+    sink = MemorySink(out.ctypes.data, cap, 0)
+    oi = OutputInterface()
+    L.mgl_memory_output_new(C.byref(oi), C.byref(sink))
+    slab = np.ascontiguousarray(slab, dtype=PACKET)
+    if not L.mgl_emit_stream_dict(_ptr(buf), len(buf), Properties(lc, lp, pb), _ptr(slab), dict_size, C.byref(oi)):
+        raise MglError("mgl_emit_stream_dict failed (invalid slab?)")
+    assert sink.len <= cap
+    return out[: sink.len].tobytes()
+
+
+def bcj_x86(data: bytes, encode: bool = True) -> bytes:
+    """The .xz x86 branch/call/jump filter (id 0x04, start offset 0) over the whole of `data`; encode=False inverts it."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8).copy()
+    L.mgl_bcj_x86(_ptr(buf), len(buf), int(bool(encode)))
+    return buf.tobytes()
+
+
+def emit_xz(original: bytes, coded: bytes, slab: np.ndarray, lc=0, lp=0, pb=0, filter=0, dict_size=0, check=1) -> bytes:
+    """Host emission (C, mgl_emit_xz): one .xz stream of one block, [x86,] LZMA2 over the slab's walk.  `coded` is what the
+    LZMA layer sees (bcj_x86(original) when filter = 4, else original) and `slab` a parse of it."""
+    L = host_lib()
+    org = np.frombuffer(bytes(original), dtype=np.uint8)
+    cod = np.frombuffer(bytes(coded), dtype=np.uint8)
+    if len(org) != len(cod):
+        raise MglError("emit_xz: original and coded differ in length", rc=-1)
+    cap = 2 * len(org) + (len(org) >> 10) * 16 + 1024
+    out = np.zeros(cap, dtype=np.uint8)
+    sink = MemorySink(out.ctypes.data, cap, 0)
+    oi = OutputInterface()
+    L.mgl_memory_output_new(C.byref(oi), C.byref(sink))
+    slab = np.ascontiguousarray(slab, dtype=PACKET)
+    if len(slab) != len(org):
+        raise MglError("emit_xz: the slab must have one entry per input byte", rc=-1)
+    opt = XzOptions(filter, dict_size, check)
+    if not L.mgl_emit_xz(_ptr(org), _ptr(cod), len(org), Properties(lc, lp, pb), _ptr(slab), C.byref(opt), C.byref(oi)):
+        raise MglError("mgl_emit_xz failed (invalid slab or option?)")
+    assert sink.len <= cap
+    return out[: sink.len].tobytes()
+
+
 def stream_info(stream: bytes) -> dict:
     """Container, lc/lp/pb, dictionary and declared size of an LZMA-alone or .xz stream
     (declared_size None = unknown, the stream ends with an end marker)."""
@@ -300,16 +362,30 @@ def stream_info(stream: bytes) -> dict:
                 dict_size=info.dict_size, declared_size=None if info.declared_size == (1 << 64) - 1 else info.declared_size)
 
 
-def stream_import(stream: bytes, data: bytes, window: int = 0x400000, clip: bool = False):
+def stream_info_x(stream: bytes) -> dict:
+    """stream_info that also reads an .xz whose chain is [x86, LZMA2]: `filter` is 4 for it, else 0."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+    info = StreamInfo()
+    flt = C.c_uint32(0)
+    rc = L.mgl_stream_info_read_x(_ptr(buf), len(buf), C.byref(info), C.byref(flt))
+    if rc != 0:
+        raise MglError(f"rc={rc}: not an LZMA-alone or .xz stream", rc=rc)
+    return dict(container=info.container, lc=info.props.lc, lp=info.props.lp, pb=info.props.pb, dict_size=info.dict_size,
+                declared_size=None if info.declared_size == (1 << 64) - 1 else info.declared_size, filter=flt.value)
+
+
+def stream_import(stream: bytes, data: bytes, window: int = 0x400000, clip: bool = False, x86: bool = False):
     """The parse inside an LZMA-alone / .xz stream of `data` as a position-indexed slab (host C, mgl_stream_import),
-    re-expressed for one LZMA1 stream.  Returns (slab, stats dict); raises MglError (rc, error, error_pos)."""
+    re-expressed for one LZMA1 stream.  x86: an .xz chain [x86, LZMA2] is accepted, and `data` is then the filtered
+    input, bcj_x86(original).  Returns (slab, stats dict); raises MglError (rc, error, error_pos)."""
     L = host_lib()
     buf = np.frombuffer(bytes(stream), dtype=np.uint8)
     dat = np.frombuffer(bytes(data), dtype=np.uint8)
     slab = np.zeros(len(dat), dtype=PACKET)
     st = ImportStats()
-    rc = L.mgl_stream_import(_ptr(buf), len(buf), _ptr(dat), len(dat), window, IMPORT_CLIP_WINDOW if clip else 0,
-                             _ptr(slab), C.byref(st))
+    rc = L.mgl_stream_import(_ptr(buf), len(buf), _ptr(dat), len(dat), window,
+                             (IMPORT_CLIP_WINDOW if clip else 0) | (IMPORT_X86 if x86 else 0), _ptr(slab), C.byref(st))
     err = st.error.decode() if st.error else None
     if rc != 0:
         raise MglError(f"rc={rc}: stream import failed at input position {st.error_pos}: {err}", rc=rc, error=err,

@@ -1,7 +1,7 @@
 /*
  * megalania-hip -- command-line driver in C, the GPU-path counterpart of the reference's
- * main.c:28-128: `megalania-hip [options] <file>` writes an LZMA-alone stream to stdout and
- * progress to stderr.  Host code only calls the C ABI (include/megalania_hip.h) and emits
+ * main.c:28-128: `megalania-hip [options] <file>` writes an LZMA-alone stream (or, with
+ * --format xz, an .xz stream) to stdout and progress to stderr.  Host code only calls the C ABI (include/megalania_hip.h) and emits
  * the best slab through EncoderInterface / OutputInterface like main.c:110-119.
  *
  * Schedule (main.c:64-77): `phases` x `epochs` epochs; phase 0 epochs start from an
@@ -27,6 +27,7 @@ static void usage(const char* argv0)
 	fprintf(stderr,
 	        "usage: %s [--neighbours K] [--epochs E] [--phases P] [--steps S] [--seed N]\n"
 	        "          [--lc N --lp N --pb N | --props auto [--props-rounds R] [--props-table] [--props-joint T]] [--device D] [--max-scan M]\n"
+	        "          [--format lzma|xz] [--filter none|x86|auto] [--dict-size BYTES]\n"
 	        "          [-o out.lzma] [--save-slab file] [--load-slab file] [--greedy-seed C] [--optimal-seed P | --adaptive-seed P]\n"
 	        "          [--match-finder nearest|frontier [--mf-depth N]] [--parse-sweep [--parse-sweep-table]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
@@ -34,7 +35,14 @@ static void usage(const char* argv0)
 	        "          [--exchange best|cross|cross-all [--cross-grain N]]] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
 	        "  --save-slab  after every epoch, write the best packet slab (resumable checkpoint)\n"
-	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb)\n"
+	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb, same filter)\n"
+	        "  --format F   the container written: lzma (LZMA-alone, default) or xz (one stream, one block, CRC32 check)\n"
+	        "  --filter F   with --format xz: none (default), x86 (the input goes through the .xz x86 branch/call/jump filter before\n"
+	        "               anything else sees it, and the block declares it) or auto: the parse of the seed option (without one, an\n"
+	        "               optimal parse made for this only) is made over the plain and over the filtered bytes and the cheaper\n"
+	        "               exact cost wins, a tie goes to none.  auto: not with --seed-stream, --load-slab or --chains above 1\n"
+	        "  --dict-size BYTES  the dictionary: no copy reaches farther back, and the stream declares it (.xz: the next size\n"
+	        "               the format can name).  At least 4096; 0 or absent = 4 MiB\n"
 	        "  --greedy-seed C  epochs that the reference starts from the all-literal slab start from a greedy\n"
 	        "               parse instead (longest of the C nearest candidates per position; e.g. 256)\n"
 	        "  --optimal-seed P  epochs that the reference starts from the all-literal slab start from the best of P\n"
@@ -52,7 +60,8 @@ static void usage(const char* argv0)
 	        "               applies to the frontier's variants; not with --match-finder.  --parse-sweep-table prints every\n"
 	        "               variant's per-pass sizes\n"
         "  --seed-stream F  start from the parse inside an existing .lzma / .xz stream of this input (e.g. xz -9e's):\n"
-	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's\n"
+	        "               it becomes the best slab and every epoch starts from it; lc/lp/pb default to the stream's;\n"
+	        "               with --format xz, an .xz stream that declares the x86 filter selects --filter x86\n"
 	        "  --clip-window    with --seed-stream: copies from beyond the dictionary window become literals instead\n"
 	        "               of an error\n"
 	        "  --props auto     choose lc/lp/pb before the search: the parse of the seed option (without one, an optimal parse made\n"
@@ -302,6 +311,21 @@ fail:
 	return NULL;
 }
 
+/* --filter auto: the seed whose exact cost decides.  Greedy parse, the optimal / adaptive seed of the run, or an optimal
+ * parse at the library's defaults where the run has no seed option. */
+static int make_filter_seed(mgl_sa* sa, uint32_t greedy, seed_spec seed, mgl_packet* parse, uint64_t* cost)
+{
+	mgl_optimal_stats os;
+	int rc;
+	if (greedy) rc = mgl_sa_seed_greedy(sa, greedy);
+	else if (seed.passes) rc = make_seed(sa, seed, &os);
+	else {
+		mgl_optimal_config oc = { 0, 0, 0 };
+		rc = mgl_sa_seed_optimal(sa, &oc, &os);
+	}
+	return rc != MGL_OK ? rc : mgl_sa_current(sa, parse, cost);
+}
+
 int main(int argc, char** argv)
 {
 	mgl_sa_config cfg;
@@ -329,6 +353,9 @@ int main(int argc, char** argv)
 	int transport_shm = 0;
 	int exchange_cross = 0, exchange_all = 0, cross_grain_given = 0;
 	uint32_t cross_grain = 0;
+	bool format_xz = false, filter_given = false;
+	enum { FILTER_NONE, FILTER_X86, FILTER_AUTO } filter = FILTER_NONE;
+	uint32_t dict_size = 0;
 	for (int i = 1; i < argc; i++) {
 		const char* a = argv[i];
 		const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -369,6 +396,28 @@ int main(int argc, char** argv)
 		}
 		else if (!strcmp(a, "--cross-grain")) { cross_grain = (uint32_t)strtoul(v, NULL, 0); cross_grain_given = 1; }
 		else if (!strcmp(a, "--max-scan")) cfg.max_bucket_scan = (uint32_t)strtoul(v, NULL, 0);
+		else if (!strcmp(a, "--format")) {
+			if (!strcmp(v, "xz")) format_xz = true;
+			else if (!strcmp(v, "lzma")) format_xz = false;
+			else { usage(argv[0]); return -1; }
+		}
+		else if (!strcmp(a, "--filter")) {
+			if (!strcmp(v, "none")) filter = FILTER_NONE;
+			else if (!strcmp(v, "x86")) filter = FILTER_X86;
+			else if (!strcmp(v, "auto")) filter = FILTER_AUTO;
+			else { usage(argv[0]); return -1; }
+			filter_given = true;
+		}
+		else if (!strcmp(a, "--dict-size")) {
+			char* end = NULL;
+			const unsigned long long d = strtoull(v, &end, 0);
+			if (end == v || *end || (d && d < 4096) || d > 0xFFFFFFFFull) {
+				fprintf(stderr, "Error: --dict-size takes a number of bytes from 4096 to 4294967295 (0 = 4 MiB)\n");
+				usage(argv[0]);
+				return -1;
+			}
+			dict_size = (uint32_t)d;
+		}
 		else if (!strcmp(a, "-o")) out_path = v;
 		else if (!strcmp(a, "--save-slab")) save_path = v;
 		else if (!strcmp(a, "--load-slab")) load_path = v;
@@ -439,6 +488,17 @@ int main(int argc, char** argv)
 		usage(argv[0]);
 		return -1;
 	}
+	if (filter != FILTER_NONE && !format_xz) {
+		fprintf(stderr, "Error: --filter x86 / auto need --format xz: an .lzma stream has no place to declare a filter\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (filter == FILTER_AUTO && (seed_stream_path || load_path || chains > 1)) {
+		fprintf(stderr, "Error: --filter auto cannot be combined with --seed-stream, --load-slab or --chains above 1\n");
+		usage(argv[0]);
+		return -1;
+	}
+	cfg.dict_limit = dict_size; /* 0: the library's 4 MiB */
 	if (chains < 1 || rank < 0 || rank >= chains || (chains > 1 && !comm_path)) { usage(argv[0]); return -1; }
 	if (chains > 1) {
 		if (!device_given) cfg.device = rank;
@@ -452,8 +512,12 @@ int main(int argc, char** argv)
 	if (fstat(fd, &sb) < 0) { fprintf(stderr, "Error: could not stat %s\n", filename); close(fd); return -1; }
 	const size_t file_size = (size_t)sb.st_size;
 	if (file_size == 0) { close(fd); return 0; } /* main.c:40-42 */
-	const uint8_t* file_data = (const uint8_t*)mmap(NULL, file_size, PROT_READ, MAP_PRIVATE, fd, 0);
-	if (file_data == MAP_FAILED) { fprintf(stderr, "Error: could not map %s\n", filename); close(fd); return -1; }
+	/* orig_data: the file.  file_data: what the LZMA layer sees, the file itself or (--filter x86) its filtered copy; the
+	 * handle, the seeds, the slabs and the chains all work on file_data, and only the .xz writer looks at both */
+	const uint8_t* const orig_data = (const uint8_t*)mmap(NULL, file_size, PROT_READ, MAP_PRIVATE, fd, 0);
+	const uint8_t* file_data = orig_data;
+	uint8_t* filtered = NULL;
+	if (orig_data == MAP_FAILED) { fprintf(stderr, "Error: could not map %s\n", filename); close(fd); return -1; }
 
 	if (mgl_device_count() < 1) {
 		fprintf(stderr, "Error: no HIP device found; this program has no CPU search path\n");
@@ -471,9 +535,21 @@ int main(int argc, char** argv)
 			seed_stream_len = (size_t)sz;
 		if (f) fclose(f);
 		mgl_stream_info info;
-		if (!seed_stream_len || mgl_stream_info_read(seed_stream, seed_stream_len, &info) != MGL_OK) {
+		uint32_t stream_filter = 0;
+		if (!seed_stream_len || mgl_stream_info_read_x(seed_stream, seed_stream_len, &info, &stream_filter) != MGL_OK) {
 			fprintf(stderr, "Error: %s is not an LZMA-alone or .xz stream\n", seed_stream_path);
 			return -1;
+		}
+		if (stream_filter == 4) {
+			if (!format_xz) {
+				fprintf(stderr, "Error: %s declares the x86 BCJ filter, which an .lzma stream cannot declare: use --format xz\n", seed_stream_path);
+				return -1;
+			}
+			if (filter_given && filter == FILTER_NONE) {
+				fprintf(stderr, "Error: %s declares the x86 BCJ filter, so its parse is one of the filtered input: not with --filter none\n", seed_stream_path);
+				return -1;
+			}
+			filter = FILTER_X86;
 		}
 		if (!props_given) props = info.props;
 		else if (props.lc != info.props.lc || props.lp != info.props.lp || props.pb != info.props.pb)
@@ -481,8 +557,45 @@ int main(int argc, char** argv)
 			        info.props.lc, info.props.lp, info.props.pb, props.lc, props.lp, props.pb);
 	}
 	cfg.iters_per_epoch = file_size;
+	if (filter != FILTER_NONE) {
+		if ((filtered = (uint8_t*)malloc(file_size)) == NULL) { fprintf(stderr, "Error: out of memory\n"); return -1; }
+		memcpy(filtered, orig_data, file_size);
+		mgl_bcj_x86(filtered, file_size, 1);
+	}
+	if (filter == FILTER_X86) file_data = filtered;
 	mgl_sa* sa = mgl_sa_create(file_data, file_size, props, &cfg);
 	if (sa == NULL) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+	bool filter_seed_kept = false;
+	if (filter == FILTER_AUTO) {
+		/* The same seed over the plain bytes (on `sa`) and over the filtered ones, one handle after the other; the cheaper
+		 * exact cost wins and a tie goes to none.  Where the filter changes no byte the two parses are the same one. */
+		mgl_packet* parse[2] = { (mgl_packet*)malloc(sizeof(mgl_packet) * file_size), (mgl_packet*)malloc(sizeof(mgl_packet) * file_size) };
+		uint64_t cost[2] = { 0, 0 };
+		if (!parse[0] || !parse[1]) { fprintf(stderr, "Error: out of memory\n"); return -1; }
+		if (make_filter_seed(sa, greedy, seed, parse[0], &cost[0]) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+		const bool changed = memcmp(filtered, orig_data, file_size) != 0;
+		cost[1] = cost[0];
+		if (changed) {
+			mgl_sa_destroy(sa);
+			if ((sa = mgl_sa_create(filtered, file_size, props, &cfg)) == NULL || make_filter_seed(sa, greedy, seed, parse[1], &cost[1]) != MGL_OK) {
+				fprintf(stderr, "Error: %s\n", mgl_last_error());
+				return -1;
+			}
+		}
+		const int win = cost[1] < cost[0];
+		fprintf(stderr, "filter auto: none %llu x86 %llu -> %s (exact costs %llu %llu)\n", (unsigned long long)((cost[0] + 16383) / 16384),
+		        (unsigned long long)((cost[1] + 16383) / 16384), win ? "x86" : "none", (unsigned long long)cost[0], (unsigned long long)cost[1]);
+		filter = win ? FILTER_X86 : FILTER_NONE;
+		file_data = win ? filtered : orig_data;
+		/* the handle alive is the filtered bytes' when they were looked at; --props auto wants an untouched one */
+		if (changed ? (!win || props_auto) : props_auto) {
+			mgl_sa_destroy(sa);
+			if ((sa = mgl_sa_create(file_data, file_size, props, &cfg)) == NULL) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+		}
+		if (seed.passes && !props_auto) { optimal_slab = parse[win]; filter_seed_kept = true; }
+		else free(parse[win]);
+		free(parse[!win]);
+	}
 	if (props_auto) {
 		/* the parse to look at: the seed the user asked for; without one an optimal seed at its defaults, for the sweep only */
 		mgl_packet* parse = (mgl_packet*)malloc(sizeof(mgl_packet) * file_size);
@@ -491,7 +604,7 @@ int main(int argc, char** argv)
 		if (!parse) { fprintf(stderr, "Error: out of memory\n"); return -1; }
 		if (seed_stream) {
 			mgl_import_stats ist;
-			if (mgl_stream_import(seed_stream, seed_stream_len, file_data, file_size, cfg.dict_limit, clip_window ? MGL_IMPORT_CLIP_WINDOW : 0,
+			if (mgl_stream_import(seed_stream, seed_stream_len, file_data, file_size, cfg.dict_limit, (clip_window ? MGL_IMPORT_CLIP_WINDOW : 0) | (filter == FILTER_X86 ? MGL_IMPORT_X86 : 0),
 			                      parse, &ist) != MGL_OK) {
 				fprintf(stderr, "Error: %s: %s at input position %llu\n", seed_stream_path, ist.error ? ist.error : "import failed",
 				        (unsigned long long)ist.error_pos);
@@ -576,7 +689,7 @@ int main(int argc, char** argv)
 		 * the library like a --load-slab one); every epoch then starts from the best slab */
 		mgl_import_stats ist;
 		const int irc = mgl_stream_import(seed_stream, seed_stream_len, file_data, file_size, cfg.dict_limit,
-		                                  clip_window ? MGL_IMPORT_CLIP_WINDOW : 0, packets_best, &ist);
+		                                  (clip_window ? MGL_IMPORT_CLIP_WINDOW : 0) | (filter == FILTER_X86 ? MGL_IMPORT_X86 : 0), packets_best, &ist);
 		if (irc != MGL_OK) {
 			fprintf(stderr, "Error: %s: %s at input position %llu%s\n", seed_stream_path, ist.error ? ist.error : "import failed",
 			        (unsigned long long)ist.error_pos, irc == MGL_ERANGE ? " (--clip-window turns such copies into literals)" : "");
@@ -594,7 +707,7 @@ int main(int argc, char** argv)
 		resumed = true;
 	}
 
-	if (seed.passes && !props_auto) { /* --props auto kept the parse of its cheapest (triple, parse) pair in optimal_slab */
+	if (seed.passes && !props_auto && !filter_seed_kept) { /* --props auto kept the parse of its cheapest (triple, parse) pair in optimal_slab */
 		/* made once; every epoch that would start from the all-literal slab starts from it */
 		mgl_optimal_stats os;
 		uint64_t cost = 0;
@@ -698,11 +811,17 @@ int main(int argc, char** argv)
 	if (out_path && (out = fopen(out_path, "wb")) == NULL) { fprintf(stderr, "Error: could not open %s\n", out_path); return -1; }
 	OutputInterface output;
 	mgl_file_output_new(&output, out);
-	if (!mgl_emit_stream(file_data, file_size, props, packets_best, &output)) return -1;
+	if (format_xz) {
+		const mgl_xz_options xo = { filter == FILTER_X86 ? 4u : 0u, dict_size, 1 };
+		if (!mgl_emit_xz(orig_data, file_data, file_size, props, packets_best, &xo, &output)) return -1;
+	} else if (dict_size) {
+		if (!mgl_emit_stream_dict(file_data, file_size, props, packets_best, dict_size, &output)) return -1;
+	} else if (!mgl_emit_stream(file_data, file_size, props, packets_best, &output)) return -1;
 	if (out_path ? fclose(out) != 0 : fflush(stdout) != 0) { fprintf(stderr, "Error: could not write the stream\n"); return -1; }
 	free(optimal_slab);
 	free(packets_best);
-	munmap((void*)file_data, file_size);
+	free(filtered);
+	munmap((void*)orig_data, file_size);
 	close(fd);
 	return 0;
 }

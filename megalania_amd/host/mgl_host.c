@@ -56,18 +56,22 @@ void mgl_lzma_encode_packet(mgl_lzma_state* st, EncoderInterface* enc, mgl_packe
 	mgl_advance(&st->walk, packet.type, packet.dist, packet.len);
 }
 
-void mgl_lzma_encode_header(const mgl_lzma_state* st, OutputInterface* output)
+static void encode_header_dict(const mgl_lzma_state* st, uint32_t dict, OutputInterface* output)
 {
 	uint8_t hdr[13];
 	const mgl_properties* p = &st->properties;
 	hdr[0] = (uint8_t)((p->pb * 5 + p->lp) * 9 + p->lc);
-	const uint32_t dict = 0x400000; /* lzma_header_encoder.c:16 */
 	for (int i = 0; i < 4; i++) hdr[1 + i] = (uint8_t)(dict >> (8 * i));
 	const uint64_t size = (uint32_t)st->data_size; /* :19 goes through htole32 */
 	for (int i = 0; i < 8; i++) hdr[5 + i] = (uint8_t)(size >> (8 * i));
 	(*output->write)(output, &hdr[0], 1);
 	(*output->write)(output, &hdr[1], 4);
 	(*output->write)(output, &hdr[5], 8);
+}
+
+void mgl_lzma_encode_header(const mgl_lzma_state* st, OutputInterface* output)
+{
+	encode_header_dict(st, 0x400000, output); /* lzma_header_encoder.c:16 */
 }
 
 /* ------------------------------------------------------------------ range coder */
@@ -225,56 +229,299 @@ void mgl_memory_output_new(OutputInterface* output, mgl_memory_sink* sink)
 
 /* ------------------------------------------------------------------ main.c:110-119 */
 
-bool mgl_emit_stream(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, OutputInterface* output)
+#define MGL_DEFAULT_DICT 0x400000u
+static const uint8_t k_xz_magic[6] = { 0xFD, '7', 'z', 'X', 'Z', 0x00 };
+
+/* The reference's emitter codes whatever it is given (main.c:116-118) and reads data[pos - dists[0] - 1] unguarded; here
+ * a slab is refused unless its walk is a valid parse of the input that a dictionary of `window` bytes can decode: packet
+ * types and lengths, MATCH distances inside the window and the prefix, LONG_REP indices, and the copied bytes
+ * themselves.  false with a message on stderr. */
+static bool slab_is_valid(const uint8_t* data, size_t n, const mgl_packet* slab, uint32_t window)
 {
-	mgl_lzma_state st;
-	if (!mgl_lzma_state_init(&st, data, n, props)) return false;
-	/* the reference's emitter codes whatever it is given (main.c:116-118) and reads
-	 * data[pos - dists[0] - 1] unguarded; here a slab is refused unless its walk is a valid parse of
-	 * the input that the header's 4 MiB dictionary can decode: packet types and lengths, MATCH
-	 * distances inside the window and the prefix, LONG_REP indices, and the copied bytes themselves */
-	{
-		mgl_wstate w;
-		memset(&w, 0, sizeof w);
-		const char* why = NULL;
-		while (w.pos < n && !why) {
-			const mgl_packet* p = &slab[w.pos];
-			const size_t pos = w.pos;
-			uint32_t src_dist = 0;
-			if (p->type < MGL_LITERAL || p->type > MGL_LONG_REP || p->len == 0 || pos + p->len > n) why = "not a packet";
-			else if (p->type == MGL_LITERAL) { if (p->len != 1) why = "literal longer than one byte"; }
-			else if (p->type == MGL_SHORT_REP) {
-				if (p->len != 1) why = "short rep longer than one byte";
-				else if (w.dists[0] >= pos || data[pos] != data[pos - w.dists[0] - 1]) why = "short rep does not reproduce the input";
-			} else {
-				if (p->len < MGL_MIN_MATCH || p->len > MGL_MAX_MATCH) why = "match length outside 2..273";
-				else if (p->type == MGL_LONG_REP && p->dist > 3) why = "rep index above 3";
+	mgl_wstate w;
+	memset(&w, 0, sizeof w);
+	const char* why = NULL;
+	while (w.pos < n && !why) {
+		const mgl_packet* p = &slab[w.pos];
+		const size_t pos = w.pos;
+		uint32_t src_dist = 0;
+		if (p->type < MGL_LITERAL || p->type > MGL_LONG_REP || p->len == 0 || pos + p->len > n) why = "not a packet";
+		else if (p->type == MGL_LITERAL) { if (p->len != 1) why = "literal longer than one byte"; }
+		else if (p->type == MGL_SHORT_REP) {
+			if (p->len != 1) why = "short rep longer than one byte";
+			else if (w.dists[0] >= pos || data[pos] != data[pos - w.dists[0] - 1]) why = "short rep does not reproduce the input";
+		} else {
+			if (p->len < MGL_MIN_MATCH || p->len > MGL_MAX_MATCH) why = "match length outside 2..273";
+			else if (p->type == MGL_LONG_REP && p->dist > 3) why = "rep index above 3";
+			else {
+				src_dist = p->type == MGL_MATCH ? p->dist : mgl_dist_at(&w, p->dist);
+				if (src_dist >= pos) why = "distance reaches before the start of the input";
+				else if (src_dist >= window)
+					why = window == MGL_DEFAULT_DICT ? "distance outside the 4 MiB dictionary of the header" : "distance outside the declared dictionary";
 				else {
-					src_dist = p->type == MGL_MATCH ? p->dist : mgl_dist_at(&w, p->dist);
-					if (src_dist >= pos) why = "distance reaches before the start of the input";
-					else if (src_dist >= 0x400000u) why = "distance outside the 4 MiB dictionary of the header";
-					else {
-						/* overlapping copies are legal: compare byte by byte */
-						const uint8_t* a = data + pos - src_dist - 1;
-						const uint8_t* b = data + pos;
-						for (uint32_t i = 0; i < p->len; i++) if (a[i] != b[i]) { why = "match does not reproduce the input"; break; }
-					}
+					/* overlapping copies are legal: compare byte by byte */
+					const uint8_t* a = data + pos - src_dist - 1;
+					const uint8_t* b = data + pos;
+					for (uint32_t i = 0; i < p->len; i++) if (a[i] != b[i]) { why = "match does not reproduce the input"; break; }
 				}
 			}
-			if (why) {
-				fprintf(stderr, "Error: slab entry at %zu: %s\n", pos, why);
-				mgl_lzma_state_free(&st);
-				return false;
-			}
-			mgl_advance(&w, p->type, p->dist, p->len);
 		}
+		if (why) {
+			fprintf(stderr, "Error: slab entry at %zu: %s\n", pos, why);
+			return false;
+		}
+		mgl_advance(&w, p->type, p->dist, p->len);
 	}
-	mgl_lzma_encode_header(&st, output);
+	return true;
+}
+
+bool mgl_emit_stream_dict(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, uint32_t dict_size,
+                          OutputInterface* output)
+{
+	const uint32_t dict = dict_size ? dict_size : MGL_DEFAULT_DICT;
+	mgl_lzma_state st;
+	if (!mgl_lzma_state_init(&st, data, n, props)) return false;
+	if (!slab_is_valid(data, n, slab, dict)) { mgl_lzma_state_free(&st); return false; }
+	encode_header_dict(&st, dict, output);
 	EncoderInterface enc;
 	if (!mgl_range_encoder_new(&enc, output)) { mgl_lzma_state_free(&st); return false; }
 	while (st.walk.pos < n) mgl_lzma_encode_packet(&st, &enc, slab[st.walk.pos]);
 	mgl_range_encoder_free(&enc);
 	mgl_lzma_state_free(&st);
+	return true;
+}
+
+bool mgl_emit_stream(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, OutputInterface* output)
+{
+	return mgl_emit_stream_dict(data, n, props, slab, MGL_DEFAULT_DICT, output);
+}
+
+/* ------------------------------------------------------------------ x86 BCJ filter (.xz filter id 0x04)
+ *
+ * The relative 32-bit target behind an E8 (call) or E9 (jmp) opcode becomes an absolute one, so that calls of one
+ * function from many places repeat byte for byte.  Only targets whose top byte is 00 or FF (a plausible displacement)
+ * are converted; prev_mask remembers which of the last bytes looked like such a top byte or an opcode, so that an opcode
+ * byte inside another instruction's operand is not taken for one.  The decoder runs the same scan and subtracts. */
+
+static bool bcj_ms(uint8_t b) { return b == 0x00 || b == 0xFF; }
+
+void mgl_bcj_x86(uint8_t* buf, size_t n, int encode)
+{
+	static const uint8_t allowed[8] = { 1, 1, 1, 0, 1, 0, 0, 0 };
+	static const uint8_t bitno[8] = { 0, 1, 2, 2, 3, 3, 3, 3 };
+	if (n < 5) return;
+	uint32_t prev_mask = 0;
+	size_t prev_pos = (size_t)0 - 5; /* only its distance to p is used, modulo 2^32 */
+	size_t p = 0;
+	while (p <= n - 5) {
+		if (buf[p] != 0xE8 && buf[p] != 0xE9) { p++; continue; }
+		const uint32_t off = (uint32_t)(p - prev_pos);
+		prev_pos = p;
+		if (off > 5) prev_mask = 0;
+		else for (uint32_t i = 0; i < off; i++) { prev_mask &= 0x77; prev_mask <<= 1; }
+		uint8_t b = buf[p + 4];
+		if (bcj_ms(b) && allowed[(prev_mask >> 1) & 7] && (prev_mask >> 1) < 0x10) {
+			uint32_t src = (uint32_t)b << 24 | (uint32_t)buf[p + 3] << 16 | (uint32_t)buf[p + 2] << 8 | buf[p + 1];
+			uint32_t dest;
+			for (;;) {
+				dest = encode ? src + (uint32_t)(p + 5) : src - (uint32_t)(p + 5);
+				if (prev_mask == 0) break;
+				const uint32_t i = bitno[prev_mask >> 1];
+				b = (uint8_t)(dest >> (24 - 8 * i));
+				if (!bcj_ms(b)) break;
+				src = dest ^ ((1u << (32 - 8 * i)) - 1u);
+			}
+			buf[p + 4] = (uint8_t)~(((dest >> 24) & 1u) - 1u);
+			buf[p + 3] = (uint8_t)(dest >> 16);
+			buf[p + 2] = (uint8_t)(dest >> 8);
+			buf[p + 1] = (uint8_t)dest;
+			p += 5;
+			prev_mask = 0;
+		} else {
+			p++;
+			prev_mask |= 1;
+			if (bcj_ms(b)) prev_mask |= 0x10;
+		}
+	}
+}
+
+/* ------------------------------------------------------------------ .xz writer */
+
+static uint32_t crc32_ieee(uint32_t crc, const uint8_t* p, size_t n)
+{
+	static uint32_t table[256];
+	if (!table[1]) /* filled with the same values by whoever gets here first */
+		for (uint32_t i = 0; i < 256; i++) {
+			uint32_t c = i;
+			for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+			table[i] = c;
+		}
+	crc = ~crc;
+	for (size_t i = 0; i < n; i++) crc = table[(crc ^ p[i]) & 0xFF] ^ (crc >> 8);
+	return ~crc;
+}
+
+static void le32_put(uint8_t* p, uint32_t v)
+{
+	for (int i = 0; i < 4; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+
+static size_t xz_varint_put(uint8_t* p, uint64_t v)
+{
+	size_t k = 0;
+	while (v >= 0x80) { p[k++] = (uint8_t)(v | 0x80); v >>= 7; }
+	p[k++] = (uint8_t)v;
+	return k;
+}
+
+/* size that LZMA2 dictionary byte b declares: 2^n or 2^n + 2^(n-1), b = 40 the 4 GiB - 1 maximum */
+static uint64_t xz_dict_of_byte(uint32_t b) { return (uint64_t)(2u | (b & 1u)) << (b / 2 + 11); }
+
+/* A chunk is closed before a packet that could take its compressed size past 64 KiB.  The bytes a chunk has cost so far
+ * are exact: its encoder has shifted `emitted + pending - 1` bytes out of `low` and the flush shifts five more, each
+ * shift being one byte of output.  What one more packet can add is bounded by its events: a modelled bit leaves
+ * range >= 2^24 >> 11 = 2^13, so its normalisation shifts at most twice; a direct bit halves the range and shifts at most
+ * once.  The longest packet is a MATCH with is_match, is_rep, 10 length bits (two choices and the 8-bit tree), 6 slot
+ * bits and 4 align bits (22 modelled bits) and 26 direct bits: 2 * 22 + 26 = 70 bytes. */
+#define XZ_PACKET_MAX_BYTES 70u
+#define XZ_CHUNK_USIZE_MAX (1u << 21)
+#define XZ_CHUNK_CSIZE_MAX (1u << 16)
+
+static size_t rc_bytes_if_flushed(const EncoderInterface* enc, const mgl_memory_sink* sink)
+{
+	const mgl_rc* rc = (const mgl_rc*)enc->private_data;
+	return sink->len + rc->fill + (size_t)rc->pending - 1 + 5;
+}
+
+static bool xz_write(OutputInterface* output, const void* p, size_t n, bool* failed)
+{
+	if (n && !(*output->write)(output, p, n) && !*failed) {
+		fprintf(stderr, "could not write %zu bytes\n", n); /* logged only, like the range coder's sink */
+		*failed = true;
+	}
+	return true;
+}
+
+bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_properties props, const mgl_packet* slab,
+                 const mgl_xz_options* opt, OutputInterface* output)
+{
+	static const mgl_xz_options k_defaults = { 0, 0, 0 };
+	if (!opt) opt = &k_defaults;
+	if ((opt->filter != 0 && opt->filter != 4) || opt->check > 1) {
+		fprintf(stderr, "Error: mgl_emit_xz: filter must be 0 or 4 and check 0 or 1\n");
+		return false;
+	}
+	if (props.lc > 4 || props.lp > 4 || props.pb > 4 || props.lc + props.lp > 4) {
+		fprintf(stderr, "Error: mgl_emit_xz: LZMA2 needs lc + lp <= 4 and pb <= 4\n");
+		return false;
+	}
+	if (n && (!original || !coded || !slab)) {
+		fprintf(stderr, "Error: mgl_emit_xz: null argument\n");
+		return false;
+	}
+	if (opt->filter == 0 && coded != original && n && memcmp(coded, original, n) != 0) {
+		fprintf(stderr, "Error: mgl_emit_xz: without a filter the coded bytes are the original ones\n");
+		return false;
+	}
+	const uint32_t want = opt->dict_size ? opt->dict_size : MGL_DEFAULT_DICT;
+	uint32_t dict_byte = 0;
+	while (dict_byte < 40 && xz_dict_of_byte(dict_byte) < (want < 4096 ? 4096 : want)) dict_byte++;
+	const uint32_t window = dict_byte == 40 ? 0xFFFFFFFFu : (uint32_t)xz_dict_of_byte(dict_byte);
+	if (!slab_is_valid(coded, n, slab, window)) return false;
+
+	bool failed = false;
+	uint8_t hdr[32];
+	/* stream header: magic, flags (00, check id), CRC32 of the flags */
+	const uint8_t flags[2] = { 0, (uint8_t)opt->check };
+	memcpy(hdr, k_xz_magic, 6);
+	memcpy(hdr + 6, flags, 2);
+	le32_put(hdr + 8, crc32_ieee(0, flags, 2));
+	xz_write(output, hdr, 12, &failed);
+
+	uint64_t unpadded = 0;
+	if (n) {
+		/* block header: size byte, flags (number of filters - 1, no size fields), filter flags, zero padding, CRC32 */
+		size_t h = 2;
+		memset(hdr, 0, sizeof hdr);
+		if (opt->filter == 4) { hdr[h++] = 0x04; hdr[h++] = 0x00; }
+		hdr[h++] = 0x21; hdr[h++] = 0x01; hdr[h++] = (uint8_t)dict_byte;
+		const size_t hsize = (h + 3) / 4 * 4 + 4;
+		hdr[0] = (uint8_t)(hsize / 4 - 1);
+		hdr[1] = opt->filter == 4 ? 1 : 0;
+		le32_put(hdr + hsize - 4, crc32_ieee(0, hdr, hsize - 4));
+		xz_write(output, hdr, hsize, &failed);
+		unpadded = hsize;
+
+		mgl_lzma_state st;
+		if (!mgl_lzma_state_init(&st, coded, n, props)) return false;
+		uint8_t* cbuf = (uint8_t*)malloc(XZ_CHUNK_CSIZE_MAX);
+		if (!cbuf) { fprintf(stderr, "Error: could not allocate memory in mgl_emit_xz\n"); mgl_lzma_state_free(&st); return false; }
+		bool first = true;
+		while (st.walk.pos < n) {
+			/* one chunk: a fresh range coder over a memory sink; model and rep stack carry on */
+			mgl_memory_sink sink = { cbuf, XZ_CHUNK_CSIZE_MAX, 0 };
+			OutputInterface mem;
+			mgl_memory_output_new(&mem, &sink);
+			EncoderInterface enc;
+			if (!mgl_range_encoder_new(&enc, &mem)) { free(cbuf); mgl_lzma_state_free(&st); return false; }
+			const size_t start = st.walk.pos;
+			do {
+				/* the first packet of a chunk always fits: 5 + 70 bytes, at most 273 bytes of input */
+				mgl_lzma_encode_packet(&st, &enc, slab[st.walk.pos]);
+			} while (st.walk.pos < n && st.walk.pos - start + slab[st.walk.pos].len <= XZ_CHUNK_USIZE_MAX &&
+			         rc_bytes_if_flushed(&enc, &sink) + XZ_PACKET_MAX_BYTES <= XZ_CHUNK_CSIZE_MAX);
+			mgl_range_encoder_free(&enc);
+			const size_t usize = st.walk.pos - start, csize = sink.len;
+			if (csize > XZ_CHUNK_CSIZE_MAX || usize > XZ_CHUNK_USIZE_MAX) { /* the bound above rules this out */
+				fprintf(stderr, "Error: mgl_emit_xz: an LZMA2 chunk came out at %zu bytes for %zu\n", csize, usize);
+				free(cbuf);
+				mgl_lzma_state_free(&st);
+				return false;
+			}
+			size_t c = 0;
+			hdr[c++] = (uint8_t)((first ? 0xE0 : 0x80) | ((usize - 1) >> 16));
+			hdr[c++] = (uint8_t)((usize - 1) >> 8);
+			hdr[c++] = (uint8_t)(usize - 1);
+			hdr[c++] = (uint8_t)((csize - 1) >> 8);
+			hdr[c++] = (uint8_t)(csize - 1);
+			if (first) hdr[c++] = (uint8_t)((props.pb * 5 + props.lp) * 9 + props.lc);
+			xz_write(output, hdr, c, &failed);
+			xz_write(output, cbuf, csize, &failed);
+			unpadded += c + csize;
+			first = false;
+		}
+		free(cbuf);
+		mgl_lzma_state_free(&st);
+		/* end of the LZMA2 data, block padding, check */
+		memset(hdr, 0, 8);
+		size_t t = 1;
+		unpadded += 1;
+		while ((unpadded + (t - 1)) % 4) t++;
+		if (opt->check == 1) { le32_put(hdr + t, crc32_ieee(0, original, n)); t += 4; unpadded += 4; }
+		xz_write(output, hdr, t, &failed);
+	}
+
+	/* index: indicator, number of records, (unpadded size, uncompressed size), padding, CRC32 */
+	uint8_t idx[32];
+	size_t k = 0;
+	memset(idx, 0, sizeof idx);
+	idx[k++] = 0x00;
+	idx[k++] = n ? 1 : 0;
+	if (n) {
+		k += xz_varint_put(idx + k, unpadded);
+		k += xz_varint_put(idx + k, n);
+	}
+	k = (k + 3) / 4 * 4;
+	le32_put(idx + k, crc32_ieee(0, idx, k));
+	k += 4;
+	xz_write(output, idx, k, &failed);
+	/* footer: CRC32 of the next six bytes, backward size, flags, magic */
+	le32_put(hdr + 4, (uint32_t)(k / 4 - 1));
+	memcpy(hdr + 8, flags, 2);
+	le32_put(hdr, crc32_ieee(0, hdr + 4, 6));
+	hdr[10] = 'Y';
+	hdr[11] = 'Z';
+	xz_write(output, hdr, 12, &failed);
 	return true;
 }
 
@@ -302,6 +549,9 @@ typedef struct {
 	uint32_t probs_cap;
 	mgl_wstate sw;
 	size_t dict_start; /* input position of the last dictionary reset */
+	/* .xz filter chain: [x86, LZMA2] is read only when asked for; `filter` is what the blocks so far declared (0 none, 4 x86) */
+	bool accept_x86, have_chain;
+	uint32_t filter;
 	/* the output walk, whose rep stack the packets are re-expressed against */
 	mgl_wstate ow;
 	size_t pos;
@@ -592,8 +842,6 @@ static uint64_t le_read(const uint8_t* p, int nbytes)
 	return v;
 }
 
-static const uint8_t k_xz_magic[6] = { 0xFD, '7', 'z', 'X', 'Z', 0x00 };
-
 /* .xz multibyte integer (at most 9 bytes); false on a truncated or overlong one */
 static bool xz_varint(const uint8_t* s, size_t len, size_t* at, uint64_t* out)
 {
@@ -665,17 +913,27 @@ static int xz_walk(mgl_imp* im, const uint8_t* s, size_t len, uint32_t* dict_siz
 			if ((bflags & 0x80) && !xz_varint(h, hend, &hp, &v)) return imp_fail(im, MGL_EINVAL, "bad .xz block header");
 			uint64_t ids[4], psize = 0;
 			uint8_t dict_byte = 0;
+			bool x86_plain = false; /* the first filter is x86 without properties or with start offset 0 */
 			for (unsigned f = 0; f < nfilters; f++) {
 				if (!xz_varint(h, hend, &hp, &ids[f]) || !xz_varint(h, hend, &hp, &psize) || psize > hend - hp)
 					return imp_fail(im, MGL_EINVAL, "bad .xz block header");
 				if (ids[f] == 0x21 && psize == 1) dict_byte = h[hp];
+				if (f == 0 && ids[f] == 0x04) x86_plain = psize == 0 || (psize == 4 && le_read(h + hp, 4) == 0);
 				hp += (size_t)psize;
 			}
-			if (nfilters != 1 || ids[0] != 0x21) {
+			uint32_t chain = 0;
+			if (im->accept_x86 && nfilters == 2 && ids[0] == 0x04 && ids[1] == 0x21) {
+				if (!x86_plain) return imp_fail(im, MGL_EINVAL, "x86 BCJ filter with a start offset other than 0");
+				chain = 4;
+			} else if (nfilters != 1 || ids[0] != 0x21) {
 				for (unsigned f = 0; f < nfilters; f++)
 					if (ids[f] != 0x21) return imp_fail(im, MGL_EINVAL, xz_filter_name(ids[f]));
 				return imp_fail(im, MGL_EINVAL, xz_filter_name(0x21));
 			}
+			/* one filtered input serves the whole file: every block has to use the first one's chain */
+			if (im->have_chain && chain != im->filter) return imp_fail(im, MGL_EINVAL, "blocks with different filter chains");
+			im->have_chain = true;
+			im->filter = chain;
 			if (psize != 1 || dict_byte > 40) return imp_fail(im, MGL_EINVAL, "bad LZMA2 filter properties");
 			if (!*dict_size)
 				*dict_size = dict_byte == 40 ? 0xFFFFFFFFu : (2u | (dict_byte & 1u)) << (dict_byte / 2 + 11);
@@ -772,13 +1030,15 @@ static bool is_xz(const uint8_t* s, size_t len)
 	return len >= 6 && memcmp(s, k_xz_magic, 6) == 0;
 }
 
-int mgl_stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out)
+static int stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out, bool accept_x86, uint32_t* filter_out)
 {
+	if (filter_out) *filter_out = 0;
 	if (!stream || !out) return MGL_EINVAL;
 	memset(out, 0, sizeof *out);
 	if (is_xz(stream, len)) {
 		mgl_imp im;
 		memset(&im, 0, sizeof im);
+		im.accept_x86 = accept_x86;
 		uint32_t dict = 0;
 		uint64_t total = 0;
 		const int rc = xz_walk(&im, stream, len, &dict, &total);
@@ -788,6 +1048,7 @@ int mgl_stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out
 		out->props = im.props;
 		out->dict_size = dict;
 		out->declared_size = total;
+		if (filter_out) *filter_out = im.filter;
 		return MGL_OK;
 	}
 	if (len < 13 || stream[0] >= 225) return MGL_EINVAL;
@@ -798,6 +1059,16 @@ int mgl_stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out
 	out->dict_size = (uint32_t)le_read(stream + 1, 4);
 	out->declared_size = le_read(stream + 5, 8);
 	return MGL_OK;
+}
+
+int mgl_stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out)
+{
+	return stream_info_read(stream, len, out, false, NULL);
+}
+
+int mgl_stream_info_read_x(const uint8_t* stream, size_t len, mgl_stream_info* out, uint32_t* filter_out)
+{
+	return stream_info_read(stream, len, out, true, filter_out);
 }
 
 int mgl_stream_import(const uint8_t* stream, size_t len, const uint8_t* data, size_t n, uint32_t window, uint32_t flags,
@@ -815,6 +1086,7 @@ int mgl_stream_import(const uint8_t* stream, size_t len, const uint8_t* data, si
 	im.n = n;
 	im.window = window ? window : 0x400000u; /* 0 = the dictionary mgl_emit_stream declares */
 	im.flags = flags;
+	im.accept_x86 = (flags & MGL_IMPORT_X86) != 0;
 	im.slab = slab_out;
 	im.st = st;
 	if (slab_out) {

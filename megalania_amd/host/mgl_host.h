@@ -14,6 +14,8 @@
  *   mgl_memory_output_new             (no reference equivalent: OutputInterface over a buffer)
  *   mgl_emit_stream                   main.c:110-119 as one call
  *   mgl_stream_info_read / _import    (no reference equivalent: the reference has no decoder)
+ *   mgl_emit_stream_dict              mgl_emit_stream with the dictionary size as a parameter
+ *   mgl_bcj_x86 / mgl_emit_xz         (no reference equivalent: the .xz container and its x86 filter)
  *
  * Stream import reads the parse out of an existing LZMA-alone (.lzma) or .xz stream of the same
  * input, as a starting slab for the search (the best known parse of a file is usually the one
@@ -21,7 +23,8 @@
  * (csrc/mgl_model.h); no output is materialised: each decoded byte is compared with `data`,
  * which also serves as the dictionary, whatever size the header declares.  .xz: streams
  * (concatenated ones too), blocks with any check, index, padding, and LZMA2 chunks of every
- * kind; a filter chain other than a single LZMA2 filter is refused.  Checks are not verified
+ * kind; a filter chain other than a single LZMA2 filter is refused, except that MGL_IMPORT_X86 admits [x86, LZMA2], for
+ * which `data` is the filtered input.  Checks are not verified
  * (the byte comparison covers the content).  The slab is position-indexed like every slab here
  * (walked packets at their start, all-literal elsewhere); every packet is resolved to its
  * concrete distance under the stream's own rep stack and re-expressed against the output
@@ -74,6 +77,27 @@ void mgl_memory_output_new(OutputInterface* output, mgl_memory_sink* sink);
 
 /* header + every packet on the slab's walk through a fresh range coder; false on bad input */
 bool mgl_emit_stream(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, OutputInterface* output);
+/* the same stream with `dict_size` (0 = 0x400000) as the header's dictionary and as the window the slab is checked against */
+bool mgl_emit_stream_dict(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, uint32_t dict_size,
+                          OutputInterface* output);
+
+/* The .xz x86 branch/call/jump filter (filter id 0x04, start offset 0) over the whole buffer, in place: the relative
+ * targets of E8 / E9 become absolute ones (encode != 0) or relative ones again (encode == 0). */
+void mgl_bcj_x86(uint8_t* buf, size_t n, int encode);
+
+typedef struct {
+	uint32_t filter;    /* 0 none, 4 x86 */
+	uint32_t dict_size; /* 0 = 0x400000 */
+	uint32_t check;     /* 0 none, 1 CRC32 */
+} mgl_xz_options;
+/* One .xz stream of one block: [x86,] LZMA2 over the slab's walk.  `coded` is what the LZMA layer sees (the filtered
+ * input when filter = 4, else `original` itself), `slab` a parse of `coded`; the block check is over `original`.  The
+ * declared dictionary is the smallest one the format can name that holds max(dict_size, 4096), and the slab is checked
+ * against it.  One model and one rep stack run through all LZMA2 chunks: the first resets dictionary, state and
+ * properties, the later ones nothing.  n = 0 writes the empty stream (no block).  opt NULL = all defaults (check none).
+ * false (with a message on stderr) on a bad slab or option. */
+bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_properties props, const mgl_packet* slab,
+                 const mgl_xz_options* opt, OutputInterface* output);
 
 typedef struct {
 	int container;            /* 1 LZMA-alone (.lzma), 2 .xz */
@@ -83,8 +107,13 @@ typedef struct {
 } mgl_stream_info;
 /* MGL_OK, or MGL_EINVAL when `stream` is neither container (or a malformed .xz) */
 int mgl_stream_info_read(const uint8_t* stream, size_t len, mgl_stream_info* out);
+/* the same, except that an .xz whose blocks all use the chain [x86 (no properties, or start offset 0), LZMA2] is read too:
+ * *filter_out = 4 for it, 0 for a plain LZMA2 chain and for .lzma */
+int mgl_stream_info_read_x(const uint8_t* stream, size_t len, mgl_stream_info* out, uint32_t* filter_out);
 
 #define MGL_IMPORT_CLIP_WINDOW 1u /* copies from beyond the window become literals instead of an error */
+#define MGL_IMPORT_X86 2u         /* an .xz chain [x86 (no properties, or start offset 0), LZMA2] is accepted: `data` is then the
+                                     filtered input (mgl_bcj_x86), which the caller filters; every other chain is refused */
 typedef struct {
 	uint64_t packets, literals, matches, short_reps, long_reps[4]; /* as the stream coded them */
 	uint64_t reexpressed;     /* packets whose type or rep index had to change */
