@@ -449,7 +449,8 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * small.  Selectors: 0 chain offsets, 1 chain lengths, 2 chain positions, 3 chain events,
  * 4 on-walk bitmap, 5 special bitmap, 6 special-state records, 7 dense checkpoints, 8 chain
  * capacities, 9 phase-cycle counters (MGL_F_PROFILE), 10 per-step overflow / repair counters (sixteen u32: [0] second-pass list,
- * [1] last-resort list, [2] spill slots, [3] repair picks, [4..7] unused and zero, of the last finished step or mgl_neighbours
+ * [1] last-resort list, [2] spill slots, [3] repair picks, [4] unused and zero, [5] event pairs the window walks of the costed neighbours left out of their
+ * change lists (0 under MGL_NO_EVCANCEL=1), [6..7] unused and zero, of the last finished step or mgl_neighbours
  * call; then, as [8..15], the same eight slots live, which the end of a step leaves at zero),
  * 11 parallel-builder totals, 12 / 13 match index (bucket offsets / positions), 14 accept-path
  * counters, 15 pick records, 16 the control block, 21 the windows (target, end) of the last costed neighbours, 22 their soft ends | dep << 31,

@@ -126,7 +126,7 @@ struct mgl_sa {
 	uint4* d_pickrec;       /* K: picked packet, RNG position, ok flag (first half -> second half of the neighbour evaluation) */
 	bool split_nbr, adaptive; /* adaptive: the device recommends the split or the one-kernel form, the host adopts it block by block */
 	bool form_single = false; /* the form the regular launch runs as right now */
-	uint32_t* d_counts;     /* [0] first-pass overflow count, [1] second-pass overflow count, [2] spill slots used, [3] repair picks, [4] unused, always zero */
+	uint32_t* d_counts;     /* [0] first-pass overflow count, [1] second-pass overflow count, [2] spill slots used, [3] repair picks, [4] unused, always zero, [5] event pairs the window walks cancelled */
 	ApplyBuf ab;
 	uint32_t apply_blocks;
 	bool incremental_apply;
@@ -982,6 +982,7 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_REST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES)));
 		sa->fuse = getenv("MGL_NO_FUSE") == nullptr;
+		sa->big.evcancel = getenv("MGL_NO_EVCANCEL") == nullptr ? 1u : 0u; /* the window walk lists a re-coded packet's changed events only; MGL_NO_EVCANCEL=1: all of them */
 		sa->fused_lds = (MGL_PICK_T_GLOBAL ? 0u : 4096u) + (sa->per_wave_pick > sa->per_wave_rest ? sa->per_wave_pick : sa->per_wave_rest);
 		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICKWALK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->fused_lds));
 		HIPCHK(hipMalloc(&sa->d_pickrec, sizeof(uint4) * K));
@@ -2455,7 +2456,7 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 83: src = b.ch_sb; sz = sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride; break; /* the chain index, row per context, sb_stride words each */
 	case 81: src = sa->batch.hdr; sz = sizeof(uint32_t) * 16; break;
 	case 82: src = sa->batch.acc; sz = sizeof(long long) * 4; break;
-	case 10: { /* the per-step counters: [0..7] of the last finished step / mgl_neighbours call, [8..15] the live ones (zero between steps) */
+	case 10: { /* the per-step counters: [0..7] of the last finished step / mgl_neighbours call ([5]: event pairs the window walks of its costed neighbours left out of their change lists), [8..15] the live ones (zero between steps) */
 		uint32_t v[16];
 		*bytes = sizeof v;
 		if (cap_bytes < sizeof v) return fail(MGL_ERANGE, "mgl_debug_dump: buffer too small");

@@ -245,7 +245,10 @@ struct Changes {
 	uint32_t cap;       /* capacity of each list */
 	uint32_t uctx_cap;
 	uint32_t nbitwords;
-	uint32_t n_ins, n_rem; /* uniform */
+	uint32_t n_ins, n_rem; /* uniform: the stored lengths */
+	uint32_t n_cancel;     /* uniform: event pairs the paired site of the walk left out of both lists (changes_add_pair).  A pair is one
+	                        * inserted and one removed event, so the totals capacity rule (2) of DESIGN.md section 4 counts -- every event
+	                        * of every packet that does not cancel whole -- are n_ins + n_cancel and n_rem + n_cancel */
 	int64_t direct;        /* (inserted - removed) direct-bit cost, uniform */
 	unsigned long long* dbg; /* diagnostic counters (MGL_F_PROFILE), else nullptr */
 	uint32_t diag;
@@ -258,7 +261,7 @@ template <bool INS>
 __device__ __forceinline__ void changes_add(Changes& ch, const mgl_plan& pl, uint32_t pos, uint32_t lane)
 {
 	uint32_t& n = INS ? ch.n_ins : ch.n_rem;
-	if (n + pl.nev > ch.cap) { ch.overflow = true; ch.list_full = true; return; }
+	if (n + pl.nev > ch.cap || n + ch.n_cancel + pl.nev > MGL_BIG_CAP) { ch.overflow = true; ch.list_full = true; return; } /* room by the stored length, the rule by the counted one */
 	if (lane < pl.nev) {
 		uint32_t ctx, bit;
 		mgl_plan_event(&pl, lane, &ctx, &bit);
@@ -268,6 +271,37 @@ __device__ __forceinline__ void changes_add(Changes& ch, const mgl_plan& pl, uin
 	n += pl.nev;
 	const int64_t d = (int64_t)((uint64_t)pl.ndirect << 11);
 	ch.direct += INS ? d : -d;
+}
+
+/* The paired site of the window walk: a neighbour packet (planned, `npl`) and, where bnev != 0, the base packet that starts at
+ * the same position and does not cancel whole (its keys ctx | bit << 15 one per lane in `bkey`, its direct bits in `bndirect`).
+ * An event both plans hold in the same slot -- same context, same bit, same position -- is left out of both lists: a context
+ * occurs at most once in a packet's plan, so at that context and position the merged chain is the base chain, and the
+ * re-simulation computes the same probabilities and the same delta with the pair or without it.  Two plans of the same packet
+ * have the same slot structure, and so have the headers and length trees of different packets where they agree, so a lane
+ * compares the two keys of its own slot.  The survivors keep their order (the lists stay sorted by position). */
+__device__ __forceinline__ void changes_add_pair(Changes& ch, uint32_t bkey, uint32_t bnev, uint32_t bndirect, const mgl_plan& npl, uint32_t pos,
+                                                 uint32_t lane, bool evcancel)
+{
+	uint32_t nkey = 0;
+	if (lane < npl.nev) {
+		uint32_t ctx, bit;
+		mgl_plan_event(&npl, lane, &ctx, &bit);
+		nkey = ctx | (bit << 15);
+	}
+	const bool common = evcancel && lane < bnev && lane < npl.nev && bkey == nkey;
+	const unsigned long long cm = __ballot(common);
+	const uint32_t nc = (uint32_t)__popcll(cm);
+	/* the rule counts the packets' events, the room is the survivors' */
+	if (ch.n_rem + ch.n_cancel + bnev > MGL_BIG_CAP || ch.n_ins + ch.n_cancel + npl.nev > MGL_BIG_CAP ||
+	    ch.n_rem + bnev - nc > ch.cap || ch.n_ins + npl.nev - nc > ch.cap) { ch.overflow = true; ch.list_full = true; return; }
+	if (!common) {
+		const uint32_t at = lane - __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u)); /* cancelled slots below this one */
+		if (lane < bnev) { ch.rem_key[ch.n_rem + at] = (uint16_t)(bkey & 0x7FFFu); ch.rem_pos[ch.n_rem + at] = pos; }
+		if (lane < npl.nev) { ch.ins_key[ch.n_ins + at] = (uint16_t)nkey; ch.ins_pos[ch.n_ins + at] = pos; }
+	}
+	ch.n_rem += bnev - nc; ch.n_ins += npl.nev - nc; ch.n_cancel += nc;
+	ch.direct += (int64_t)((uint64_t)npl.ndirect << 11) - (int64_t)((uint64_t)bndirect << 11);
 }
 
 /* first index >= start (and < n) whose key, masked, equals cx; n if none.  Sixteen 16-bit keys
@@ -557,7 +591,7 @@ __device__ __forceinline__ uint32_t literal_run_events(const DevCtx& c, Changes&
 	if (run < 2u) return 0;
 	const uint32_t take = run < 7u ? run : 7u;
 	uint32_t& n = INS ? ch.n_ins : ch.n_rem;
-	if (n + 9u * take > ch.cap) { ch.overflow = true; ch.list_full = true; return take; }
+	if (n + 9u * take > ch.cap || n + ch.n_cancel + 9u * take > MGL_BIG_CAP) { ch.overflow = true; ch.list_full = true; return take; }
 	const uint32_t i = lane / 9u, slot = lane - i * 9u;
 	const uint32_t p = st.pos + i;
 	const bool active = i < take;
@@ -689,6 +723,7 @@ struct BigScratch {
 	 * saves its walk here (state, journal; its change lists go to the slot's list area) and the second pass resumes it at the
 	 * pick instead of evaluating the neighbour again from its target.  nullptr: no continuations (restart, as before) */
 	uint32_t* cont;
+	uint32_t evcancel; /* the paired site of the window walk leaves events common to both packets out of the lists; 0 (MGL_NO_EVCANCEL=1): packet-level lists */
 };
 #define MGL_CONT_WORDS 368u       /* 48 header words | 64 journal positions | 64 old packets | 64 new packets */
 #define MGL_CONT_MAGIC 0x434F4E54u
@@ -772,7 +807,7 @@ __device__ __forceinline__ void coop_share(const DevCtx& c, const Base2& b, cons
 	cl.ins_key = (uint16_t*)(cp + 2u * MGL_BIG_CAP); cl.rem_key = cl.ins_key + MGL_BIG_CAP;
 	cl.uctx = big.uctx + (size_t)slot * big.uctx_cap; cl.ctxbits = nullptr;
 	cl.cap = MGL_BIG_CAP; cl.uctx_cap = big.uctx_cap; cl.nbitwords = 0;
-	cl.direct = 0; cl.dbg = dbg; cl.diag = c.diag_stop; cl.overflow = false; cl.list_full = false;
+	cl.direct = 0; cl.n_cancel = 0; cl.dbg = dbg; cl.diag = c.diag_stop; cl.overflow = false; cl.list_full = false;
 	const uint16_t* gik = big.ins_key + (size_t)slot * big.cap; const uint32_t* gip = big.ins_pos + (size_t)slot * big.cap;
 	const uint16_t* grk = big.rem_key + (size_t)slot * big.cap; const uint32_t* grp = big.rem_pos + (size_t)slot * big.cap;
 	for (uint32_t e = threadIdx.x; e < cl.n_ins; e += blockDim.x) { cl.ins_pos[e] = gip[e]; cl.ins_key[e] = gik[e]; }
@@ -874,7 +909,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		ch.uctx = big.uctx + (size_t)slot * big.uctx_cap;
 		ch.cap = big.cap; ch.uctx_cap = big.uctx_cap;
 	}
-	ch.n_ins = ch.n_rem = 0; ch.direct = 0; ch.overflow = false; ch.list_full = false;
+	ch.n_ins = ch.n_rem = 0; ch.n_cancel = 0; ch.direct = 0; ch.overflow = false; ch.list_full = false;
 	bool too_many = false;
 	bool spilled = BIG;
 
@@ -1041,6 +1076,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		resume_old = (mgl_pk)uni(crec[30]) | ((mgl_pk)uni(crec[31]) << 32);
 		m_second = (mgl_pk)uni(crec[32]) | ((mgl_pk)uni(crec[33]) << 32);
 		ch.direct = (int64_t)((uint64_t)uni(crec[34]) | ((uint64_t)uni(crec[35]) << 32));
+		ch.n_cancel = uni(crec[36]); /* the resumed walk goes on counting events at packet level */
 		if (lane < jn.count) {
 			jn.pos[lane] = crec[48u + lane];
 			jn.old[lane] = reinterpret_cast<const mgl_pk*>(crec + 112u)[lane];
@@ -1249,6 +1285,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 											rec[30] = (uint32_t)old; rec[31] = (uint32_t)(old >> 32);     /* the packet the repair found at p */
 											rec[32] = (uint32_t)m_second; rec[33] = (uint32_t)(m_second >> 32);
 											rec[34] = (uint32_t)(uint64_t)ch.direct; rec[35] = (uint32_t)((uint64_t)ch.direct >> 32);
+											rec[36] = ch.n_cancel;
 											rec[0] = MGL_CONT_MAGIC; /* the reader is a later launch */
 										}
 									}
@@ -1295,17 +1332,24 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 					if (cancelled) {
 						mgl_advance(&bs, ntype, ndist, nlen);
 					} else {
+						/* of the base packet only a key per lane and two counts stay live while the neighbour's is planned */
+						uint32_t bkey = 0, bnev = 0, bndirect = 0;
 						if (bs.pos == p) {
 							const mgl_pk bpk = win_pk(win, p);
 							const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
 							mgl_plan bpl;
 							plan_at(c, bs, btype, bdist, blen, win_byte(win, p), bpl);
-							changes_add<false>(ch, bpl, p, lane);
+							bnev = bpl.nev; bndirect = bpl.ndirect;
+							if (lane < bnev) {
+								uint32_t cx, bt;
+								mgl_plan_event(&bpl, lane, &cx, &bt);
+								bkey = cx | (bt << 15);
+							}
 							mgl_advance(&bs, btype, bdist, blen);
 						}
 						mgl_plan npl;
 						plan_at(c, nb, ntype, ndist, nlen, win_byte(win, p), npl);
-						changes_add<true>(ch, npl, p, lane);
+						changes_add_pair(ch, bkey, bnev, bndirect, npl, p, lane, big.evcancel != 0);
 					}
 					mgl_advance(&nb, ntype, ndist, nlen);
 				} else {
@@ -1355,6 +1399,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		}
 		return;
 	}
+	if (lane == 0 && ch.n_cancel) atomicAdd(big.spill_ctr + 3, ch.n_cancel); /* event pairs cancelled in the neighbours this step finished */
 	const uint64_t total = (uint64_t)((int64_t)ctl->rebuild_cost + delta + ch.direct); /* rebuild_cost: exact cost of the base */
 	uint32_t nd = 0;
 	for (uint32_t i = 0; i < jn.count; i++) {
@@ -1461,7 +1506,7 @@ __device__ __forceinline__ void sim_one(const DevCtx& c, const Base2& b, Control
 	ch.uctx = s_uctx; ch.ctxbits = s_bits;
 	ch.cap = cap; ch.uctx_cap = 2 * cap;
 	ch.nbitwords = (c.L.total + 31u) >> 5;
-	ch.direct = 0; ch.dbg = nullptr; ch.diag = c.diag_stop; ch.overflow = false; ch.list_full = false;
+	ch.direct = 0; ch.n_cancel = 0; ch.dbg = nullptr; ch.diag = c.diag_stop; ch.overflow = false; ch.list_full = false;
 	const uint16_t* gk = big.sim_keys + (size_t)j * (2u * cap);
 	const uint32_t* gp = big.sim_pos + (size_t)j * (2u * cap);
 	for (uint32_t e = threadIdx.x; e < ch.n_ins; e += blockDim.x) { s_key[e] = gk[e]; s_pos[e] = gp[e]; }

@@ -713,7 +713,8 @@ __device__ void step_end_body(Control* ctl, int lazy_best, uint32_t* counts, int
 			else if (ctl->accepted_flag) ctl->best_is_current = 0;
 		}
 		ctl->accepted_flag = 0; ctl->apply_failed = 0;
-		/* the per-step counters ([0] second-pass list, [1] last-resort list, [2] spill slots, [3] repair picks, [4] unused, always zero):
+		/* the per-step counters ([0] second-pass list, [1] last-resort list, [2] spill slots, [3] repair picks, [4] unused, always zero,
+		 * [5] event pairs the window walks cancelled, [6..7] unused):
 		 * kept for diagnostics in [8..15], cleared for the next step (saves a memset launch) */
 		for (int i = 0; i < 8; i++) { counts[8 + i] = counts[i]; counts[i] = 0; }
 	}
