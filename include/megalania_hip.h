@@ -155,11 +155,31 @@ int mgl_device_count(void);
 mgl_sa* mgl_sa_create(const uint8_t* data, size_t n, mgl_properties props, const mgl_sa_config* cfg);
 void mgl_sa_destroy(mgl_sa* sa);
 
+/* Slabs from outside, and the state after a refusal.  A slab the search did not make itself is checked on the device
+ * before the search goes on from it: every entry on its walk is a packet (type 1..4; length 1 for LITERAL and SHORT_REP,
+ * 2..273 for MATCH and LONG_REP; a LONG_REP index of at most 3) that ends inside the input, and every copy has its source
+ * inside the input and the handle's dictionary window and reproduces the input byte for byte (rep packets by the rep
+ * distances of the slab's own walk).  Entries off the walk are not looked at and come back entry for entry
+ * (mgl_sa_current, mgl_sa_best, the crossover's child).  mgl_sa_run, however, re-joins the slab through entries that were
+ * off its walk and takes them as they are, like the reference (packet_slab_neighbour.c:82-117, where a stale entry once
+ * was a packet of a valid parse): a slab that a search is to start from must hold off its walk only what a search leaves
+ * there -- a MATCH that reproduces the input, a LONG_REP of any index or a SHORT_REP that stays inside the input, a
+ * literal.  mgl_sa_set_slab checks at once.  A best slab
+ * from outside (mgl_sa_set_best, mgl_sa_adopt_best_packed, mgl_sa_cross_best, the exchanges) is accepted on its walk and
+ * its cost -- which refuses what is no packet or does not fit -- and compared with the input bytes by the first
+ * mgl_sa_begin_epoch(.., from_best) that starts from it, together with its cost.  The parity hooks (mgl_cost_slab,
+ * mgl_props_sweep, mgl_final_state, mgl_crossover, ...) refuse an entry that is no packet or does not fit; whether they
+ * look at the sources of the copies is left open.
+ * After a refused mgl_sa_set_slab or a refused mgl_sa_begin_epoch(.., from_best) -- both MGL_EINVAL -- the handle is as
+ * after mgl_sa_begin_epoch(phase, 0): the current slab is the all-literal one at its exact cost, no error is pending and
+ * mgl_sa_run works.  mgl_sa_set_slab leaves the best slab and its cost untouched; mgl_sa_begin_epoch forgets the best slab
+ * it refused: mgl_sa_best reports cost 0 ("none", which is what the next exchange publishes) and all-literal entries. */
 /* Start an epoch (main.c:71-77): phase = the reference's `step` (0..2); from_best != 0 copies
  * the best slab into the current one, else the current slab becomes all-literal.  Resets the
- * within-epoch iteration counter and the current cost. */
+ * within-epoch iteration counter and the current cost.  MGL_EINVAL: the best slab came from outside and is not a valid
+ * parse of the input at the cost it came with (see above for the state this leaves). */
 int mgl_sa_begin_epoch(mgl_sa* sa, unsigned phase, int from_best);
-/* Replace the current slab (n entries, position-indexed).  Must be a valid parse. */
+/* Replace the current slab (n entries, position-indexed).  Must be a valid parse: MGL_EINVAL otherwise (see above). */
 int mgl_sa_set_slab(mgl_sa* sa, const mgl_packet* packets);
 /* Replace the current slab by a greedy LZ parse made on the device (not in the reference, whose
  * search always starts from the all-literal slab, main.c:71; SURVEY 8f-3 "greedy seeding"): every
@@ -305,7 +325,10 @@ int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_threshold);
  * in an epoch that starts from the best slab). */
 int mgl_sa_step_modes(mgl_sa* sa, uint8_t* modes_out, size_t cap, size_t* count);
 /* Adopt a best slab found elsewhere (another chain / GPU): replaces best slab and best cost.
- * `perplexity` must be the slab's exact cost (it is re-derived on the device and checked). */
+ * `perplexity` must be the slab's exact cost: the slab is walked on the device at once, which refuses (MGL_EINVAL, nothing
+ * adopted) an entry that is no packet or does not fit, and a cost other than `perplexity`.  That walk does not look at the
+ * bytes a copy copies: like a slab adopted from a peer, this one is compared with the input by the first
+ * mgl_sa_begin_epoch(.., from_best) that starts from it, which refuses it then. */
 int mgl_sa_set_best(mgl_sa* sa, const mgl_packet* packets, uint64_t perplexity);
 /* ---- chains on several GPUs (no reference counterpart: the reference is one process; main.c:75-77 is what
  * an exchange feeds).  One chain per GPU / process; mgl_comm wraps one RCCL communicator (librccl is loaded on
@@ -362,8 +385,9 @@ typedef struct {
 /* parity hook: SA state untouched; child_out (n entries) nullable */
 int mgl_crossover(mgl_sa* sa, const mgl_packet* const* parents, size_t nparents, uint32_t grain, mgl_packet* child_out,
                   mgl_cross_stats* stats);
-/* parents = (the handle's best slab, other).  Child strictly cheaper than both: it becomes the best slab at its exact cost (verified,
- * not "unverified");  else other strictly cheaper than the best: adopted as mgl_sa_set_best does;  else nothing changes.  No best slab
+/* parents = (the handle's best slab, other).  Child strictly cheaper than both: it becomes the best slab at its exact cost (the
+ * cost is verified; `other`'s copies, and so the child's, are compared with the input when an epoch first starts from it, as for
+ * mgl_sa_set_best);  else other strictly cheaper than the best: adopted as mgl_sa_set_best does;  else nothing changes.  No best slab
  * yet: other is adopted (stats: parents 0, nothing was crossed; parent_cost[1] its cost).  The current slab and the run state are untouched
  * (mgl_sa_begin_epoch(.., from_best) continues from the new best slab). */
 int mgl_sa_cross_best(mgl_sa* sa, const mgl_packet* other, uint32_t grain, mgl_cross_stats* stats);

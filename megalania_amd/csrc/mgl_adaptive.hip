@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const AdpVarian
 		walk_window(w, c, in, lane);
 		const mgl_pk pk = walk_slab_at(w, pos);
 		uint32_t type = mgl_pk_type(pk), dist = mgl_pk_dist(pk), len = mgl_pk_len(pk);
-		if (type < MGL_LITERAL || type > MGL_LONG_REP || len == 0 || len > c.n - pos) break; /* not a parse: the host validated it, never taken */
+		if (len == 0 || len > c.n - pos) break; /* leaves the input: never taken (see below) */
 		if (snaps) {
 			for (uint32_t m = (pos + chunk - 1u) / chunk; (uint64_t)m * chunk < (uint64_t)pos + len; m++) {
 				const bool here = m * chunk == pos;
@@ -82,6 +82,9 @@ __global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const AdpVarian
 			opt_resolve(st, type, dist, len);
 			if (lane == 0) out[pos] = mgl_pack(type, dist, len);
 		}
+		/* what is planned is a packet (mgl_model.h): a DP's copy is one once it is resolved (before that its distance is
+		 * absolute, whatever its type), a slab from outside has been through the walk of mgl_cost_slab.  Never taken. */
+		if (!mgl_pk_wellformed(type, dist, len)) break;
 		uint32_t match_byte = 0, prev_byte = 0;
 		if (type == MGL_LITERAL) {
 			if (st.ctx_state >= 7 && st.dists[0] < pos) match_byte = c.data[pos - st.dists[0] - 1];

@@ -1133,9 +1133,59 @@ static int check_current(mgl_sa* sa, bool validate, int bad, const char* who, ui
 	return MGL_OK;
 }
 
+/* The current slab becomes the all-literal one, with its base structures and its exact cost: from the kept copy where
+ * there is one, else filled, rebuilt and kept.  The control block's flags and counters are the caller's business. */
+static int current_to_literal(mgl_sa* sa)
+{
+	int rc;
+	const bool snaps = sa->incremental && sa->snapshots;
+	if (snaps) {
+		SnapMeta meta;
+		HIPCHK(hipMemcpyAsync(&meta, sa->d_snap_meta, sizeof meta, hipMemcpyDeviceToHost, sa->stream));
+		HIPCHK(hipStreamSynchronize(sa->stream));
+		if (meta.valid) {
+			if ((rc = launch_snapshot(sa, sa->snap_lit, 0u, 1, 0))) return rc;
+			HIPCHK(hipStreamSynchronize(sa->stream));
+			return MGL_OK;
+		}
+	}
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->base.v.slab, sa->ctx.n);
+	HIPCHK(hipGetLastError());
+	if ((rc = rebuild_base(sa, 0))) return rc;
+	if (snaps && (rc = launch_snapshot(sa, sa->snap_lit, 0u, 0, 0))) return rc;
+	HIPCHK(hipStreamSynchronize(sa->stream));
+	return MGL_OK;
+}
+
+/* A slab from outside has just been refused as the current one (megalania_hip.h, "after a refusal"): the handle goes on
+ * from the all-literal slab with clear flags, as after mgl_sa_begin_epoch(phase, 0) -- not from a slab that is no parse.
+ * forget_best: the refused slab was the best one, which is then none (cost 0, all-literal entries).  The refusal's text
+ * stays the last error. */
+static int recover_from_refusal(mgl_sa* sa, bool forget_best)
+{
+	const std::string keep = g_err;
+	Control c;
+	int rc = read_ctl(sa, sa->base, &c);
+	if (rc) return rc;
+	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
+	if (forget_best) {
+		c.best_cost = 0; c.best_is_current = 0;
+		sa->best_unverified = false;
+		hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->d_best, sa->ctx.n);
+		HIPCHK(hipGetLastError());
+		if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->stream));
+	}
+	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
+	auto_reset(sa);
+	if ((rc = current_to_literal(sa))) return rc;
+	g_err = keep;
+	return MGL_OK;
+}
+
 /* The current slab is replaced by what `put` leaves in base.v.slab (an import, a kernel launch, a device copy): the best
  * slab's structures are saved if the base is their only holder, MGL_ACCEPT_AUTO starts over, the current cost and the
- * flags are cleared and the base is rebuilt; then check_current. */
+ * flags are cleared and the base is rebuilt; then check_current.  A slab from outside (`validate`) that is refused does
+ * not stay: recover_from_refusal, and the best slab is as it was. */
 template <class Put>
 static int replace_current(mgl_sa* sa, Put put, bool validate, int bad, const char* who, uint64_t* cost = nullptr)
 {
@@ -1148,7 +1198,12 @@ static int replace_current(mgl_sa* sa, Put put, bool validate, int bad, const ch
 	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
 	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
 	if ((rc = rebuild_base(sa, 0))) return rc;
-	return check_current(sa, validate, bad, who, cost);
+	rc = check_current(sa, validate, bad, who, cost);
+	if (rc == bad && validate) {
+		const int rc2 = recover_from_refusal(sa, false);
+		if (rc2) return rc2;
+	}
+	return rc;
 }
 /* put: a copy of a slab on the device */
 static auto put_slab(mgl_sa* sa, const mgl_pk* slab)
@@ -1177,38 +1232,35 @@ extern "C" int mgl_sa_begin_epoch(mgl_sa* sa, unsigned phase, int from_best)
 	auto_reset(sa);
 	sa->bulk_now = !from_best;
 	if (from_best && base_is_best) return MGL_OK; /* main.c:73-76 would copy packets_best over itself */
+	if (!from_best) return current_to_literal(sa);
 	if (snaps) {
-		SnapMeta meta[2];
-		HIPCHK(hipMemcpyAsync(meta, sa->d_snap_meta, sizeof meta, hipMemcpyDeviceToHost, sa->stream));
+		SnapMeta meta;
+		HIPCHK(hipMemcpyAsync(&meta, sa->d_snap_meta + 1, sizeof meta, hipMemcpyDeviceToHost, sa->stream));
 		HIPCHK(hipStreamSynchronize(sa->stream));
-		const uint32_t which = from_best ? 1u : 0u;
-		if (meta[which].valid) {
-			if ((rc = launch_snapshot(sa, which ? sa->snap_best : sa->snap_lit, which, 1, 0))) return rc;
+		if (meta.valid) {
+			if ((rc = launch_snapshot(sa, sa->snap_best, 1u, 1, 0))) return rc;
 			HIPCHK(hipStreamSynchronize(sa->stream));
 			return MGL_OK;
 		}
 	}
-	if (from_best) HIPCHK(hipMemcpyAsync(sa->base.v.slab, sa->d_best, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
-	else {
-		hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->base.v.slab, sa->ctx.n);
-		HIPCHK(hipGetLastError());
-	}
+	HIPCHK(hipMemcpyAsync(sa->base.v.slab, sa->d_best, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
 	if ((rc = rebuild_base(sa, 0))) return rc;
-	if (from_best && sa->best_unverified) {
-		/* a slab adopted from another chain is checked here, where it first matters: every packet against
-		 * the input, and the total against the cost it came with */
+	if (sa->best_unverified) {
+		/* a best slab that came from outside (another chain, mgl_sa_set_best) is checked here, where it first matters:
+		 * every packet against the input, and the total against the cost it came with */
 		if ((rc = launch_validate(sa))) return rc;
 		Control v;
 		if ((rc = read_ctl(sa, sa->base, &v))) return rc;
 		if (v.error_flags || v.rebuild_cost != v.best_cost) {
-			v.error_flags = 0;
-			(void)write_ctl(sa, sa->base, &v);
-			return fail(MGL_EINVAL, "mgl_sa_begin_epoch: the adopted best slab is not a valid parse of the input at the cost it came with");
+			(void)fail(MGL_EINVAL, "mgl_sa_begin_epoch: the adopted best slab is not a valid parse of the input at the cost it came with");
+			if ((rc = recover_from_refusal(sa, true))) return rc;
+			sa->bulk_now = true; /* the epoch starts from the all-literal slab after all */
+			return MGL_EINVAL;
 		}
 		sa->best_unverified = false;
 	}
-	/* the base now is the best (or the literal) slab's: keep it for the next epoch */
-	if (snaps && (rc = launch_snapshot(sa, from_best ? sa->snap_best : sa->snap_lit, from_best ? 1u : 0u, 0, 0))) return rc;
+	/* the base now is the best slab's: keep it for the next epoch */
+	if (snaps && (rc = launch_snapshot(sa, sa->snap_best, 1u, 0, 0))) return rc;
 	HIPCHK(hipStreamSynchronize(sa->stream));
 	return MGL_OK;
 }
@@ -2128,6 +2180,7 @@ extern "C" int mgl_sa_set_best(mgl_sa* sa, const mgl_packet* packets, uint64_t p
 	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
 	c.best_cost = perplexity;
 	c.best_is_current = 0;
+	sa->best_unverified = true; /* the walk has no eye for the copied bytes: mgl_sa_begin_epoch(.., from_best) looks at them */
 	return write_ctl(sa, sa->base, &c);
 }
 

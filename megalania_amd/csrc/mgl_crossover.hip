@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(64) k_xo_walk(DevCtx c, XoView v, XoCounters* 
 		walk_window(w, c, slab, lane);
 		const mgl_pk pk = walk_slab_at(w, pos);
 		const uint32_t type = mgl_pk_type(pk), dist = mgl_pk_dist(pk), len = mgl_pk_len(pk);
-		if (type < MGL_LITERAL || type > MGL_LONG_REP || len == 0u || len > c.n - pos) { bad = true; break; }
+		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) { bad = true; break; }
 		const uint64_t before = wave_sum64(w.acc);
 		const uint32_t pw = pos >> 6;
 		if (pw != word) {

@@ -440,7 +440,7 @@ static int xo_set_best(mgl_sa* sa, const mgl_pk* src, uint64_t cost, Control& c,
 	return write_ctl(sa, sa->base, &c);
 }
 /* mgl_sa_cross_best with `other` already in the scratch slab (an import, or the landing area of a broadcast) */
-static int cross_best_scratch(mgl_sa* sa, uint32_t grain, bool from_peer, mgl_cross_stats* st)
+static int cross_best_scratch(mgl_sa* sa, uint32_t grain, bool from_peer /* or from the caller: not yet compared with the input */, mgl_cross_stats* st)
 {
 	Control c;
 	int rc = read_ctl(sa, sa->base, &c);
@@ -484,7 +484,7 @@ extern "C" int mgl_sa_cross_best(mgl_sa* sa, const mgl_packet* other, uint32_t g
 	int rc = import_slab(sa, other, sa->scratch.v.slab);
 	if (rc) return rc;
 	mgl_cross_stats st;
-	if ((rc = cross_best_scratch(sa, grain, false, &st))) return rc;
+	if ((rc = cross_best_scratch(sa, grain, true, &st))) return rc; /* `other` is as little checked as a peer's slab */
 	if (stats) *stats = st;
 	return MGL_OK;
 }

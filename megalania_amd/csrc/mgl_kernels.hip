@@ -845,7 +845,7 @@ __global__ void __launch_bounds__(64) k_rebuild(DevCtx c, BaseView b, Control* c
 		walk_window(w, c, b.slab, lane);
 		const mgl_pk pk = walk_slab_at(w, pos);
 		uint32_t type = mgl_pk_type(pk), len = mgl_pk_len(pk), dist = mgl_pk_dist(pk);
-		if (type < MGL_LITERAL || type > MGL_LONG_REP || len == 0 || pos + len > c.n) { /* corrupt entry: cost as literal */
+		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) { /* not a packet (mgl_model.h): cost as literal */
 			type = MGL_LITERAL; len = 1; dist = 0;
 			if (lane == 0) atomicOr(&ctl->error_flags, MGL_ERR_WALK_OVERRUN);
 		}

@@ -62,7 +62,7 @@ __device__ void build_body(const DevCtx& c, const Base2& b, Control* ctl, int ch
 		walk_window(w, c, b.slab, lane);
 		const mgl_pk pk = walk_slab_at(w, pos);
 		uint32_t type = mgl_pk_type(pk), len = mgl_pk_len(pk), dist = mgl_pk_dist(pk);
-		if (type < MGL_LITERAL || type > MGL_LONG_REP || len == 0 || pos + len > c.n) {
+		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) {
 			type = MGL_LITERAL; len = 1; dist = 0;
 			if (lane == 0) atomicOr(&ctl->error_flags, MGL_ERR_WALK_OVERRUN);
 		}
@@ -163,7 +163,7 @@ __device__ void build_body(const DevCtx& c, const Base2& b, Control* ctl, int ch
 		walk_window(w, c, b.slab, lane);
 		const mgl_pk pk = walk_slab_at(w, pos);
 		uint32_t type = mgl_pk_type(pk), len = mgl_pk_len(pk), dist = mgl_pk_dist(pk);
-		if (type < MGL_LITERAL || type > MGL_LONG_REP || len == 0 || pos + len > c.n) { type = MGL_LITERAL; len = 1; dist = 0; }
+		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) { type = MGL_LITERAL; len = 1; dist = 0; }
 		const uint32_t byte = walk_byte_at(w, pos);
 		uint32_t match_byte = 0, prev_byte = 0;
 		if (type == MGL_LITERAL) {

@@ -885,24 +885,17 @@ __global__ void __launch_bounds__(256) k_validate(DevCtx c, Base2 b, Control* ct
 	if (!((b.onwalk[p >> 6] >> (p & 63u)) & 1ull)) return;
 	const mgl_pk pk = b.slab[p];
 	const uint32_t type = mgl_pk_type(pk), len = mgl_pk_len(pk), dist = mgl_pk_dist(pk);
-	bool bad = type < MGL_LITERAL || type > MGL_LONG_REP || len == 0 || p + len > c.n;
-	if (!bad) {
-		if (type == MGL_LITERAL) bad = len != 1;
-		else {
-			const uint32_t* r = b.sp_state + (size_t)p * 8;
-			const uint32_t d0 = r[1], d1 = r[2], d2 = r[3], d3 = r[4];
-			uint32_t src = 0;
-			if (type == MGL_SHORT_REP) { bad = len != 1; src = d0; }
-			else {
-				bad = len < MGL_MIN_MATCH || len > MGL_MAX_MATCH || (type == MGL_LONG_REP && dist > 3u);
-				src = type == MGL_MATCH ? dist : (dist == 0 ? d0 : dist == 1 ? d1 : dist == 2 ? d2 : d3);
-			}
-			if (!bad) bad = src >= p || src >= c.dict_limit;
-			if (!bad) {
-				const uint8_t* a = c.data + p - src - 1u;
-				const uint8_t* z = c.data + p;
-				for (uint32_t i = 0; i < len; i++) if (a[i] != z[i]) { bad = true; break; }
-			}
+	bool bad = !mgl_pk_wellformed(type, dist, len) || len > c.n - p;
+	if (!bad && type != MGL_LITERAL) {
+		/* the builders walked a malformed entry as a literal and wrote no record for it: records are read for packets only */
+		const uint32_t* r = b.sp_state + (size_t)p * 8;
+		const uint32_t d0 = r[1], d1 = r[2], d2 = r[3], d3 = r[4];
+		const uint32_t src = type == MGL_MATCH ? dist : type == MGL_SHORT_REP ? d0 : (dist == 0 ? d0 : dist == 1 ? d1 : dist == 2 ? d2 : d3);
+		bad = src >= p || src >= c.dict_limit;
+		if (!bad) {
+			const uint8_t* a = c.data + p - src - 1u;
+			const uint8_t* z = c.data + p;
+			for (uint32_t i = 0; i < len; i++) if (a[i] != z[i]) { bad = true; break; }
 		}
 	}
 	if (bad) atomicOr(&ctl->error_flags, MGL_ERR_BAD_PACKET);

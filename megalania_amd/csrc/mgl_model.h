@@ -47,6 +47,20 @@ MGL_HD uint32_t mgl_pk_dist(mgl_pk p) { return (uint32_t)p; }
 #define MGL_PK_LITERAL ((uint64_t)1 << 32 | (uint64_t)MGL_LITERAL << 48)
 #define MGL_PK_SHORT_REP ((uint64_t)1 << 32 | (uint64_t)MGL_SHORT_REP << 48)
 
+/* "This slab entry is a packet": a known type, length 1 for LITERAL and SHORT_REP, a length the length coder has
+ * (MGL_MIN_MATCH..MGL_MAX_MATCH) for MATCH and LONG_REP, and a LONG_REP index that names a rep slot.  Every walk of a slab
+ * that the search did not make itself asks this, and that the packet ends inside the input, before it plans the entry:
+ * mgl_plan_length has no table for another length (len - 2 wraps below 2, and from 274 on the 8-bit tree of the high
+ * lengths runs into the contexts behind it), so nothing else may reach mgl_plan_packet.  Whether the packet reproduces
+ * the input is a separate question (k_validate, slab_is_valid).  Off-walk entries may hold anything. */
+MGL_HD int mgl_pk_wellformed(uint32_t type, uint32_t dist, uint32_t len)
+{
+	if (type == MGL_LITERAL || type == MGL_SHORT_REP) return len == 1u;
+	if (type == MGL_MATCH) return len >= MGL_MIN_MATCH && len <= MGL_MAX_MATCH;
+	if (type == MGL_LONG_REP) return len >= MGL_MIN_MATCH && len <= MGL_MAX_MATCH && dist <= 3u;
+	return 0;
+}
+
 /* Probability array layout (u16 units).  Same contexts as lzma_state.h:15-58; the fixed-size
  * groups come first and the literal coder last so that lc/lp only change the tail. */
 #define MGL_CS_IS_MATCH 0u    /* [12][16] */

@@ -66,6 +66,7 @@ __global__ void __launch_bounds__(64) k_opt_walk(DevCtx c, const mgl_pk* in, mgl
 			opt_resolve(st, type, dist, len);
 			if (lane == 0) out[pos] = mgl_pack(type, dist, len);
 		}
+		if (!mgl_pk_wellformed(type, dist, len)) break; /* only packets are planned (mgl_model.h): a resolved copy is one. Never taken */
 		uint32_t match_byte = 0, prev_byte = 0;
 		if (type == MGL_LITERAL) {
 			if (st.ctx_state >= 7 && st.dists[0] < pos) match_byte = c.data[pos - st.dists[0] - 1];

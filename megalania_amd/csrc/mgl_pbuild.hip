@@ -62,11 +62,11 @@ struct PBuild {
 	uint32_t force_fix; /* diagnostic: treat every warm-up as inconclusive (exercises pb_sim_fix) */
 };
 
-/* the validity rule of k_build: anything that is not a packet that fits is walked as a literal */
+/* the validity rule of k_build: anything that is not a packet (mgl_pk_wellformed) that fits is walked as a literal */
 __device__ __forceinline__ bool pb_decode(mgl_pk pk, uint32_t pos, uint32_t n, uint32_t& type, uint32_t& dist, uint32_t& len)
 {
 	type = mgl_pk_type(pk); len = mgl_pk_len(pk); dist = mgl_pk_dist(pk);
-	if (type < MGL_LITERAL || type > MGL_LONG_REP || len == 0 || pos + len > n) {
+	if (!mgl_pk_wellformed(type, dist, len) || len > n - pos) {
 		type = MGL_LITERAL; len = 1; dist = 0;
 		return false;
 	}

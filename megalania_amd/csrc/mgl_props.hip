@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(64) k_props_sweep(DevCtx c, const mgl_pk* slab
 		walk_window(w, c, slab, lane);
 		const mgl_pk pk = walk_slab_at(w, pos);
 		const uint32_t type = mgl_pk_type(pk), dist = mgl_pk_dist(pk), len = mgl_pk_len(pk);
-		if (type < MGL_LITERAL || type > MGL_LONG_REP || len == 0u || len > c.n - pos) break; /* the host validated the slab: never taken */
+		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) break; /* the walk of mgl_cost_slab refused such a slab: never taken */
 		uint32_t match_byte = 0, prev_byte = 0;
 		if (type == MGL_LITERAL) {
 			if (w.st.ctx_state >= 7u && w.st.dists[0] < pos) match_byte = c.data[pos - w.st.dists[0] - 1u];

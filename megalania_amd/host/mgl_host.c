@@ -249,7 +249,8 @@ static bool slab_is_valid(const uint8_t* data, size_t n, const mgl_packet* slab,
 		else if (p->type == MGL_LITERAL) { if (p->len != 1) why = "literal longer than one byte"; }
 		else if (p->type == MGL_SHORT_REP) {
 			if (p->len != 1) why = "short rep longer than one byte";
-			else if (w.dists[0] >= pos || data[pos] != data[pos - w.dists[0] - 1]) why = "short rep does not reproduce the input";
+			else if (w.dists[0] >= pos) why = "distance reaches before the start of the input";
+			else if (data[pos] != data[pos - w.dists[0] - 1]) why = "short rep does not reproduce the input";
 		} else {
 			if (p->len < MGL_MIN_MATCH || p->len > MGL_MAX_MATCH) why = "match length outside 2..273";
 			else if (p->type == MGL_LONG_REP && p->dist > 3) why = "rep index above 3";
