@@ -486,6 +486,10 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * clusters or a walk gave up (status 2 with a failure seen), 81 / 82 the batch accept's header and totals, 83 the chain index,
  * selector 84 one u32: the give-up sites of the in-place accepts seen since the last dump (MGL_GU_* bits of csrc/mgl_base2.h;
  * cleared by the dump and by key 6), 85 one u32: the chain pool's top.
+ * 26 / 27 (empty with MGL_NO_ORDER=1 or position targets): what the last targets launch left for the fused pick + walk launch --
+ * K bytes, 1 = the neighbour will pick, 0 = it takes a grow/shrink mutation; and K u32, every slice's neighbours in the order
+ * the launch takes them up (the picking ones first, ascending in j inside each class).  28: the two-launch form's pickstate
+ * records, 8 u32 per neighbour; word 7 = 1 where the pick half took the grow/shrink mutation (MGL_NO_FUSE=1 / MGL_F_PROFILE).
  * mgl_debug_set: key 0 = stop the neighbour kernels after a phase (tools/phase_cost.py), 50 =
  * stage timing in the accept path; key 1 = make the parallel builder redo every chain segment
  * serially (exercises its fallback); key 2 = shrink the first-pass change lists (a multiple of 8,
@@ -511,7 +515,9 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * key 7 = 1, 2 or the compiled MGL_BIG_WAVES (anything else: MGL_EINVAL): the wavefronts of a second-pass workgroup, which
  * share a neighbour's re-simulations; with 1 or 2 a neighbour's contexts take several trips (exercises that path).
  * key 8 = n: the next n crossovers (mgl_crossover, mgl_sa_cross_best and the crossing exchanges) find no room for their
- * buffers (MGL_ENOMEM; exercises mgl_sa_exchange_cross_all's fall-back). */
+ * buffers (MGL_ENOMEM; exercises mgl_sa_exchange_cross_all's fall-back).
+ * key 9 = pattern: overwrite the class hints (selector 26) with 0: all 0, 1: all 1, 2: alternating, anything else: random bytes
+ * from `pattern`, and make the order (selector 27) from them again -- the test of k_pick_order. */
 int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes);
 int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value);
 /* draw n of neighbour j at global step `step` (31-bit, like rand()); j = 0xFFFFFFFF is the

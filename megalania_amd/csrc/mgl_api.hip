@@ -151,6 +151,11 @@ struct mgl_sa {
 	bool batch_ok = false;
 	uint32_t* d_strat_tgt = nullptr;
 	uint32_t* d_strat_pre = nullptr; /* stratified targets: packets before every block of 4 096 positions */
+	/* made with the targets (launch_targets), for the fused launch: K bytes, 1 = the neighbour will pick, 0 = grow/shrink; and
+	 * K neighbour indices, every slice's picking neighbours in front of its others (k_pick_order).  Null: MGL_NO_ORDER=1,
+	 * position targets, no split form */
+	unsigned char* d_pick_hint = nullptr;
+	uint32_t* d_pick_order = nullptr;
 	bool select_small = false;    /* the previous bulk step had few acceptable neighbours: this one's selection runs as one launch */
 	uint32_t* h_bstat = nullptr;   /* pinned: the batch accept's status words, read back once per bulk step */
 	hipEvent_t ev_bstat = nullptr; /* behind that read-back's copy */
@@ -431,7 +436,12 @@ static void launch_targets(mgl_sa* sa, hipStream_t st, uint64_t step_override)
 	const uint32_t nw0 = sa->incremental ? sa->b2.nw0 : (sa->ctx.n + 63u) >> 6;
 	hipLaunchKernelGGL(k_rank_blocks, dim3(sa->ctx.strat_nblk), dim3(64), 0, st, onwalk, nw0, sa->d_strat_pre, sa->ctx.strat_nblk);
 	hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, st, sa->d_strat_pre, sa->ctx.strat_nblk);
-	hipLaunchKernelGGL(k_targets, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->d_strat_tgt);
+	hipLaunchKernelGGL(k_targets, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, sa->b2, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->d_strat_tgt,
+	                   sa->d_pick_hint);
+	if (sa->d_pick_order) {
+		const uint32_t slices = nbr_slices(sa);
+		hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, st, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
+	}
 }
 /* The next step's targets need the on-walk bitmap of the new base and nothing else: an accept has written it long before it is
  * through with chains and checkpoints, so they are worked out on the second stream beside the rest of the accept (30 us off
@@ -484,14 +494,14 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 		/* the first two thirds of the split form -- pick, then window walk -- of every slice, as one fused launch per slice (or as
 		 * two: MGL_NO_FUSE, MGL_F_PROFILE); slices alternate between the two streams, ev_rest[h] is recorded behind slice h's walk */
 		for (uint32_t h = 0; h < slices; h++) {
-			const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
+			const uint32_t j0 = mgl_slice_bound(K, h, slices), j1 = mgl_slice_bound(K, h + 1, slices);
 			hipStream_t st = (h & 1u) ? sa->stream2 : sa->stream;
 			if (sa->fuse && !sa->d_prof) {
 				/* pick and walk of a neighbour in one wavefront: no barrier on the slice's slowest pick in front of its walks.  Under
 				 * MGL_F_PROFILE the two halves run as two launches (below): the stage marks are the pick half's */
 				hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_PICKWALK>), dim3(j1 - j0), dim3(64), sa->fused_lds, st, sa->ctx,
 				                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->fused_lds, sa->d_todo, sa->d_counts,
-				                   (unsigned long long*)nullptr, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICKWALK>");
+				                   (unsigned long long*)nullptr, sa->big, sa->d_pickrec, j0, j1, (uint4*)sa->d_pick_order); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICKWALK>"); /* the order in the unused `pickstate` slot */
 				HIPCHK(hipEventRecord(sa->ev_rest[h], st));
 				continue;
 			}
@@ -507,7 +517,7 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 		}
 		HIPCHK(hipGetLastError());
 		for (uint32_t h = 0; h < slices; h++) {
-			const uint32_t j0 = (uint32_t)((uint64_t)K * h / slices), j1 = (uint32_t)((uint64_t)K * (h + 1) / slices);
+			const uint32_t j0 = mgl_slice_bound(K, h, slices), j1 = mgl_slice_bound(K, h + 1, slices);
 			/* the second half's re-simulation, several wavefronts per neighbour */
 			HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_rest[h], 0));
 			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 4 * (size_t)sa->time_sim_step + 2 * h), sa->stream3));
@@ -592,7 +602,7 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 	dfree(sa->big.ins_key); dfree(sa->big.rem_key); dfree(sa->big.ins_pos); dfree(sa->big.rem_pos); dfree(sa->big.uctx);
 	if (sa->h_bstat) (void)hipHostFree(sa->h_bstat);
 	if (sa->ev_bstat) (void)hipEventDestroy(sa->ev_bstat);
-	dfree(sa->big.cont); dfree(sa->d_traffic); dfree(sa->d_strat_pre); dfree(sa->d_strat_tgt);
+	dfree(sa->big.cont); dfree(sa->d_traffic); dfree(sa->d_strat_pre); dfree(sa->d_strat_tgt); dfree(sa->d_pick_hint); dfree(sa->d_pick_order);
 	{
 		BatchBuf& bt = sa->batch;
 		dfree(bt.hdr); dfree(bt.cl); dfree(bt.jpos); dfree(bt.jnew); dfree(bt.jold); dfree(bt.st_ikey); dfree(bt.st_rkey); dfree(bt.st_ipos);
@@ -1039,6 +1049,12 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		sa->ctx.strat_pre = sa->d_strat_pre;
 		HIPCHK(hipMalloc(&sa->d_strat_tgt, sizeof(uint32_t) * sa->cfg.neighbours_per_step));
 		sa->ctx.strat_tgt = sa->d_strat_tgt;
+		/* the fused launch takes up its picking neighbours first; MGL_NO_ORDER=1: in blockIdx order */
+		if (sa->incremental && sa->split_nbr && getenv("MGL_NO_ORDER") == nullptr) {
+			HIPCHK(hipMalloc(&sa->d_pick_hint, sa->cfg.neighbours_per_step));
+			HIPCHK(hipMemset(sa->d_pick_hint, 1, sa->cfg.neighbours_per_step));
+			HIPCHK(hipMalloc(&sa->d_pick_order, sizeof(uint32_t) * sa->cfg.neighbours_per_step));
+		}
 	}
 	sa->sqrt_thresh = ceil_sqrt_u64(sa->cfg.iters_per_epoch);
 	/* a bulk step costs a parallel rebuild (about 3 single steps at 100 KB, 6 at 10 MB, 20 at 100 MB) */
@@ -2542,12 +2558,15 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 25: src = sa->nbr.walked; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* and packets walked of the last costed neighbours */
 	case 22: src = sa->nbr.win2; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* soft ends | dep << 31 */
 	case 21: src = sa->nbr.win; sz = sizeof(uint32_t) * 2 * sa->cfg.neighbours_per_step; break; /* windows of the last costed neighbours */
+	case 26: src = sa->d_pick_hint; sz = src ? sa->cfg.neighbours_per_step : 0; break;                     /* class hints of the last targets made */
+	case 27: src = sa->d_pick_order; sz = src ? sizeof(uint32_t) * sa->cfg.neighbours_per_step : 0; break;  /* and the order made from them */
+	case 28: src = sa->d_pickstate; sz = src ? sizeof(uint4) * 2 * sa->cfg.neighbours_per_step : 0; break;  /* what the two-launch form's pick half left */
 	case 11: src = sa->pb.acc; sz = sa->pb.acc ? sizeof(unsigned long long) * 8 : 0; break; /* parallel builder totals */
 	default: return fail(MGL_EINVAL, "mgl_debug_dump: unknown selector");
 	}
 	*bytes = sz;
 	if (sz > cap_bytes) return fail(MGL_ERANGE, "mgl_debug_dump: buffer too small");
-	HIPCHK(hipMemcpy(out, src, sz, hipMemcpyDeviceToHost));
+	if (sz) HIPCHK(hipMemcpy(out, src, sz, hipMemcpyDeviceToHost));
 	if (what == 84) HIPCHK(hipMemset(sa->lim.why, 0, sizeof(uint32_t)));
 	return MGL_OK;
 }
@@ -2596,6 +2615,24 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 		return MGL_OK;
 	}
 	if (key == 8) { sa->force_xo_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` crossovers fail to allocate their buffers (MGL_ENOMEM) */
+	if (key == 9) { /* test of k_pick_order: overwrite the hint bytes (0: all 0, 1: all 1, 2: alternating, else: random from `value`) and make the order again */
+		if (!sa->d_pick_order) return fail(MGL_EINVAL, "mgl_debug_set: no launch order on this handle");
+		const uint32_t K = sa->cfg.neighbours_per_step, slices = nbr_slices(sa);
+		std::vector<unsigned char> h(K);
+		uint64_t x = value;
+		for (uint32_t j = 0; j < K; j++) {
+			x = x * 6364136223846793005ull + 1442695040888963407ull;
+			h[j] = value == 0 ? 0 : value == 1 ? 1 : value == 2 ? (unsigned char)(j & 1u) : (unsigned char)((x >> 40) % 3u); /* any non-zero byte is a picking neighbour */
+		}
+		HIPCHK(hipSetDevice(sa->device));
+		HIPCHK(hipStreamSynchronize(sa->stream));
+		HIPCHK(hipStreamSynchronize(sa->stream2));
+		HIPCHK(hipMemcpy(sa->d_pick_hint, h.data(), K, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, sa->stream, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipStreamSynchronize(sa->stream));
+		return MGL_OK;
+	}
 	if (key == 3) { sa->force_rollbacks = (uint32_t)value; return MGL_OK; } /* the next `value` bulk steps that take moves are taken back as if their parse had failed validation */
 	return fail(MGL_EINVAL, "mgl_debug_set: unknown key");
 }

@@ -1031,7 +1031,10 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		hand->m_first = uni64(m_first); hand->m_second = uni64(m_second); hand->rng_n = uni(rng.n);
 		hand->flags = (mutated ? MGL_HAND_MUTATED : 0u) | (second_set ? MGL_HAND_SECOND : 0u);
 	}
-	if (MODE == MGL_NBR_PICK && mutated) return; /* nothing to pick: the second half redoes the grow/shrink itself */
+	if (MODE == MGL_NBR_PICK && mutated) { /* nothing to pick: the second half redoes the grow/shrink itself */
+		if (!FUSED && lane == 0) reinterpret_cast<uint32_t*>(pickstate)[8u * j + 7u] = 1u; /* the decision, on record for the tests of the class hint (mgl_debug_dump 28) */
+		return;
+	}
 	/* where the pick's sources start and end depends on the target and the rep distances alone: searched for here, all
 	 * sources level by level, in front of the model load instead of source by source behind it */
 	TopkPlan plan;
@@ -1447,14 +1450,18 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_
 		 * tables are dead by then).  Each body's returns end that body alone: a neighbour whose pick body returned early
 		 * (grow/shrink, a diagnostic stop) still gets its walk body, which takes the same decision from the same values. */
 		static_assert(!BIG && !PROF, "the fused instance is a regular launch without stage marks");
+		/* which neighbour of the slice: the launch's order (k_pick_order: the picking neighbours first) travels in the `pickstate`
+		 * slot, which this instance has no other use for; null = blockIdx order */
+		const uint32_t* const order = reinterpret_cast<const uint32_t*>(pickstate);
+		const uint32_t unit = order != nullptr ? order[j_base + blockIdx.x] - j_base : blockIdx.x;
 		PickHand hand;
 		hand.target = 0; hand.rng_n = 0; hand.ctx_state = 0; hand.dists[0] = hand.dists[1] = hand.dists[2] = hand.dists[3] = 0;
 		hand.first = hand.second = hand.m_first = hand.m_second = 0; hand.flags = 0;
-		nbr2_one<false, MGL_NBR_PICK, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, pickstate, smem, T,
-		                                           blockIdx.x, lane, 0u, &hand);
+		nbr2_one<false, MGL_NBR_PICK, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, nullptr, smem, T,
+		                                           unit, lane, 0u, &hand);
 		wave_sync(); /* the walk body's journal and lists overwrite what the pick body's lanes read */
-		nbr2_one<false, MGL_NBR_REST, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, pickstate, smem, T,
-		                                           blockIdx.x, lane, 0u, &hand);
+		nbr2_one<false, MGL_NBR_REST, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, nullptr, smem, T,
+		                                           unit, lane, 0u, &hand);
 	} else if (BIG) {
 		/* wavefront 0 takes the workgroup's neighbours one at a time; the others help with their re-simulations */
 		if (wid != 0) { coop_helpers(c, b, big, prof_acc, smem, per_wave_bytes, T, lane, wid); return; }
@@ -1600,16 +1607,90 @@ __global__ void __launch_bounds__(1024) k_rank_scan(uint32_t* pre, uint32_t nblk
 	}
 }
 
+/* Will neighbour j pick, or does it take a grow/shrink mutation and go straight into its walk?  A copy of the rule at the head of
+ * nbr2_one's "mutate" stage (draw 1 of the neighbour's stream, the packets at the target and behind it, the rep distances
+ * there, two input bytes), kept out of nbr2_one so that the neighbour kernels compile as they did.  It only orders a launch
+ * (k_pick_order): a wrong answer costs time, never a result.  tests/test_gpu_pick_order.py holds the two together.  Every
+ * load is inside its buffer whatever the slab holds: pos < n, and base_state_at looks at positions below pos. */
+__device__ __forceinline__ bool nbr_will_pick(const DevCtx& c, const Base2& b, uint32_t pos, uint64_t key)
+{
+	if (pos >= c.n || pos + 1 >= c.n || (mgl_rng_draw(key, 1) % 2u) != 0) return true;
+	const mgl_pk first = b.slab[pos], second = b.slab[pos + 1];
+	const uint32_t ft = mgl_pk_type(first), flen = mgl_pk_len(first);
+	const uint32_t st = mgl_pk_type(second), slen = mgl_pk_len(second), sdist = mgl_pk_dist(second);
+	if ((ft == MGL_LONG_REP || ft == MGL_MATCH) && flen > 2) return false;
+	if ((ft == MGL_LITERAL || ft == MGL_SHORT_REP) && (st == MGL_MATCH || st == MGL_LONG_REP)) {
+		uint32_t d = sdist;
+		if (st == MGL_LONG_REP) { const mgl_wstate nb = base_state_at(b, pos); d = mgl_dist_at(&nb, sdist); }
+		const uint32_t rep_start = pos - d;
+		if (slen < MGL_MAX_MATCH && rep_start > 0 && rep_start <= pos && c.data[pos] == c.data[rep_start - 1]) return false;
+	}
+	return true;
+}
+
 /* the step's targets: one wavefront per neighbour (mgl_device.h:stratified_target; draw 0 of the neighbour's stream picks the
  * packet inside its slice).  A kernel of its own: in the pick kernel, sixteen wavefronts per CU, the same search was a
- * dozen dependent loads at the head of every wavefront's critical path */
-__global__ void __launch_bounds__(256) k_targets(DevCtx c, const uint64_t* onwalk, uint32_t nw0, const Control* ctl, uint64_t seed, uint64_t step_override,
-                                                 uint32_t K, uint32_t* tgt)
+ * dozen dependent loads at the head of every wavefront's critical path.  With `hint` (incremental engine) it also says which
+ * neighbours will pick: 1 = picks, 0 = grow/shrink.  Exact where the slab is final when this runs (behind k_apply_walk of a
+ * single step), a guess behind a batch accept. */
+__global__ void __launch_bounds__(256) k_targets(DevCtx c, Base2 b, const uint64_t* onwalk, uint32_t nw0, const Control* ctl, uint64_t seed, uint64_t step_override,
+                                                 uint32_t K, uint32_t* tgt, unsigned char* hint)
 {
 	const uint32_t j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
 	if (j >= K) return;
 	const uint64_t gstep = step_override != ~0ull ? step_override : ctl->gstep;
+	const uint64_t key = mgl_rng_key(seed, gstep, j);
 	/* packets on the walk: the last prefix sum (Control::packets says the same once the accept is through; this kernel may run beside it) */
-	const uint32_t t = stratified_target(onwalk, nw0, c.strat_pre, c.strat_nblk, c.strat_pre[c.strat_nblk], K, j, mgl_rng_draw(mgl_rng_key(seed, gstep, j), 0), lane);
+	const uint32_t t = stratified_target(onwalk, nw0, c.strat_pre, c.strat_nblk, c.strat_pre[c.strat_nblk], K, j, mgl_rng_draw(key, 0), lane);
 	if (lane == 0) tgt[j] = t;
+	if (hint != nullptr) {
+		const bool picks = nbr_will_pick(c, b, t, key); /* uniform: t is */
+		if (lane == 0) hint[j] = picks ? 1 : 0;
+	}
+}
+
+/* slice h of `slices` of a step's K neighbours is [mgl_slice_bound(K, h, slices), mgl_slice_bound(K, h + 1, slices)): the
+ * launches of launch_neighbours and the order below cut the step at the same places */
+__host__ __device__ __forceinline__ uint32_t mgl_slice_bound(uint32_t K, uint32_t h, uint32_t slices) { return (uint32_t)((uint64_t)K * h / slices); }
+
+/* of a flag per thread of a 1 024-thread workgroup: how many threads below this one have it set, and (*total) how many in all */
+__device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t* s_w, uint32_t* total)
+{
+	const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+	const unsigned long long m = __ballot(flag);
+	__syncthreads(); /* the previous use of s_w is read */
+	if (lane == 0) s_w[wid] = (uint32_t)__popcll(m);
+	__syncthreads();
+	uint32_t below = 0, all = 0;
+	for (uint32_t q = 0; q < 16u; q++) { const uint32_t v = s_w[q]; if (q < wid) below += v; all += v; }
+	*total = all;
+	return below + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+/* The order in which a fused launch takes up the neighbours of its slice: workgroup x evaluates order[j0 + x].  Workgroups
+ * start in blockIdx order; with the picking neighbours (hint != 0) in front, ascending in j, and the grow/shrink ones behind
+ * them, ascending too, the last slot round of a launch holds short walk-only wavefronts instead of picking ones seven times
+ * in ten.  (Measured on c3: all walk-only neighbours at the end beats half of them, evenly spread, which beats none: DESIGN.md
+ * section 5.)  One workgroup per slice; a permutation of [j0, j1) whatever the hint bytes hold. */
+__global__ void __launch_bounds__(1024) k_pick_order(const unsigned char* hint, uint32_t* order, uint32_t K, uint32_t slices)
+{
+	__shared__ uint32_t s_w[16];
+	const uint32_t j0 = mgl_slice_bound(K, blockIdx.x, slices), j1 = mgl_slice_bound(K, blockIdx.x + 1u, slices);
+	uint32_t picking = 0; /* of the slice: where its walk-only neighbours start */
+	for (uint32_t s = j0; s < j1; s += 1024u) {
+		const uint32_t j = s + threadIdx.x;
+		uint32_t t;
+		(void)block_rank(j < j1 && hint[j] != 0, s_w, &t);
+		picking += t;
+	}
+	uint32_t front_seen = 0, back_seen = 0;
+	for (uint32_t s = j0; s < j1; s += 1024u) {
+		const uint32_t j = s + threadIdx.x;
+		const bool in = j < j1, front = in && hint[j] != 0;
+		uint32_t tf;
+		const uint32_t rf = block_rank(front, s_w, &tf);
+		if (front) order[j0 + front_seen + rf] = j;
+		else if (in) order[j0 + picking + back_seen + (threadIdx.x - rf)] = j; /* the threads below an in-range thread are in range */
+		const uint32_t n_in = j1 - s < 1024u ? j1 - s : 1024u;
+		front_seen += tf; back_seen += n_in - tf;
+	}
 }
