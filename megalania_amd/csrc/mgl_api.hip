@@ -821,6 +821,12 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 		b.pool_cap = (uint32_t)(24 * n + (size_t)L.total * 272 + 4096);
 		/* chain index: one entry per context and block of the parallel builder (the builder's per-block counts are its source) */
 		b.sb_shift = n <= (1u << 20) ? 8u : n <= (1u << 23) ? 9u : MGL_PB_MAX_SHIFT;
+		/* MGL_SB_SHIFT (tests): 512- and 1 024-position blocks on small inputs.  Nothing outside 8..10 is taken: the builder's
+		 * LDS arrays hold MGL_PB_MAX_BLOCK positions, and a block is whole bitmap words (shift - 6) */
+		if (getenv("MGL_SB_SHIFT")) {
+			const int s = atoi(getenv("MGL_SB_SHIFT"));
+			if (s >= 8 && s <= (int)MGL_PB_MAX_SHIFT) b.sb_shift = (uint32_t)s;
+		}
 		b.nsb = (uint32_t)((n + (1u << b.sb_shift) - 1) >> b.sb_shift);
 		b.sb_stride = (b.nsb + 2u + 3u) & ~3u;
 		size_t bytes = 0;
@@ -2516,6 +2522,12 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 80: { /* host counters: batch accepts, batch accepts that fell back to the rebuild behind their commit, and those that left the
 	            * step to the rebuild before anything was touched */
 		const uint64_t v[3] = { sa->batch_accepts, sa->batch_fallbacks, sa->batch_early_giveups };
+		*bytes = sizeof v;
+		if (cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
+		return MGL_OK;
+	}
+	case 86: { /* the chain index's geometry as built: block shift (the size rule's, or MGL_SB_SHIFT's), blocks, words per row */
+		const uint32_t v[3] = { b.sb_shift, b.nsb, b.sb_stride };
 		*bytes = sizeof v;
 		if (cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
 		return MGL_OK;

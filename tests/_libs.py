@@ -63,6 +63,20 @@ def walk(slab: np.ndarray):
     return out
 
 
+def use_block_shift(monkeypatch, shift):
+    """MGL_SB_SHIFT for every handle created from here to the end of the test: 8, 9 or 10 (blocks of 256, 512 or 1 024
+    positions, for the parallel builder and the chain index alike), None = the library's size rule."""
+    if shift is None:
+        monkeypatch.delenv("MGL_SB_SHIFT", raising=False)
+    else:
+        monkeypatch.setenv("MGL_SB_SHIFT", str(shift))
+
+
+def block_shift(sa) -> int:
+    """the block shift the handle was created with (mgl_debug_dump selector 86: shift, blocks, index row stride)"""
+    return int(sa.debug_dump(86, np.uint32)[0])
+
+
 def canonical_base(sa, slab):
     """The incremental engine's base structures (a megalania_amd.binding.SA handle) in an offset-independent form."""
     n, total = sa.n, sa.nprobs
@@ -89,10 +103,10 @@ def canonical_base(sa, slab):
     st = sa.debug_dump(6, np.uint32).reshape(n, 8)[:, :5]
     ck = sa.debug_dump(7, np.uint16).reshape(-1, (total + 7) // 8 * 8)[:, :total]
     # the chain index is checked against the chains it indexes, here, whoever built or patched it: entry [c][b] = entries of
-    # context c's chain with a position below b << shift (the last column: the chain's length)
-    shift = 8 if n <= (1 << 20) else 9 if n <= (1 << 23) else 10
-    nsb = (n + (1 << shift) - 1) >> shift
-    stride = (nsb + 2 + 3) & ~3
+    # context c's chain with a position below b << shift (the last column: the chain's length).  Shift, block count and row
+    # stride are the ones the handle says it built with (the size rule's or MGL_SB_SHIFT's): the blocks must cover the input
+    shift, nsb, stride = (int(x) for x in sa.debug_dump(86, np.uint32))
+    assert nsb == (n + (1 << shift) - 1) >> shift and stride >= nsb + 1, (n, shift, nsb, stride)
     idx = sa.debug_dump(83, np.uint32).reshape(-1, stride)
     bounds = (np.arange(nsb + 1, dtype=np.int64) << shift)
     for c in range(total):

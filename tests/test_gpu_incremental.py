@@ -6,13 +6,27 @@ import lzma
 import numpy as np
 import pytest
 
-from _libs import Oracle, assert_same_base, canonical_base, literal_slab, walk
+from _libs import Oracle, assert_same_base, block_shift, canonical_base, literal_slab, use_block_shift, walk
 from conftest import slab_from_rle
 from megalania_amd import binding, corpus
 
 pytestmark = pytest.mark.gpu
 
 INF = 0xFFFFFFFF
+
+# The block shift (builder block = chain index granularity) the structure tests run at: the size rule's (8 at these sizes),
+# and the 512- and 1 024-position blocks of inputs above 1 MiB and 8 MiB through MGL_SB_SHIFT.  The golden inputs are 600 B
+# to 4 KB: one to four blocks at shift 10, so an input shorter than a block, nsb = 1 and a bitmap word range clipped by the
+# input's end come with them.
+SHIFTS = (None, 9, 10)
+
+
+def with_shifts(argnames, cases, ids=None):
+    """parametrize over cases x SHIFTS; a case at the size rule's shift keeps the id it had before there were shifts"""
+    ids = ids or ["-".join(str(v) for v in (c if isinstance(c, tuple) else (c,))) for c in cases]
+    return pytest.mark.parametrize(argnames + ",shift", [
+        pytest.param(*(c if isinstance(c, tuple) else (c,)), s, id=i if s is None else f"{i}-shift{s}")
+        for c, i in zip(cases, ids) for s in SHIFTS])
 
 
 def ref_to_product_ctx(r, lit):
@@ -93,11 +107,13 @@ def check_base(sa, o, slab, data):
 
 
 @pytest.mark.parametrize("serial_build", [False, True], ids=["parallel_build", "serial_build"])
-@pytest.mark.parametrize("name", ["lorem4k", "enwik3k", "reps", "zeros600"])
-def test_base_structures_match_oracle_trace(name, serial_build, golden, golden_input):
+@with_shifts("name", ["lorem4k", "enwik3k", "reps", "zeros600"])
+def test_base_structures_match_oracle_trace(name, shift, serial_build, golden, golden_input, monkeypatch):
     data = golden_input(name)
     n = len(data)
+    use_block_shift(monkeypatch, shift)
     sa = binding.SA(data, accept="single", neighbours_per_step=8, serial_build=serial_build)
+    assert shift is None or block_shift(sa) == shift
     o = Oracle(data)
     slabs = [literal_slab(n)]
     if name in golden["evolved_walks"]:
@@ -108,6 +124,7 @@ def test_base_structures_match_oracle_trace(name, serial_build, golden, golden_i
     for slab in slabs:
         sa.set_slab(slab.astype(binding.PACKET))
         check_base(sa, o, slab, data)
+        canonical_base(sa, slab)  # the chain index against the chains check_base has just checked
     sa.close()
 
 
@@ -135,14 +152,16 @@ def test_engines_agree_on_c2_neighbours():
     full.close()
 
 
-@pytest.mark.parametrize("name,K,steps", [("lorem4k", 64, 120), ("enwik3k", 96, 150), ("reps", 48, 120), ("zeros600", 32, 60)])
-def test_incremental_accept_equals_rebuild(name, K, steps, golden, golden_input):
+@with_shifts("name,K,steps", [("lorem4k", 64, 120), ("enwik3k", 96, 150), ("reps", 48, 120), ("zeros600", 32, 60)])
+def test_incremental_accept_equals_rebuild(name, K, steps, shift, golden, golden_input, monkeypatch):
     """After every accepted step the incrementally maintained base (bitmaps, special-state
     records, chains, dense checkpoints) is identical to one rebuilt from the slab."""
     data = golden_input(name)
+    use_block_shift(monkeypatch, shift)
     # a long epoch: sqrt(N) is large against i*i, so uphill moves (main.c:86) keep coming as well
     inc = binding.SA(data, accept="single", neighbours_per_step=K, seed=5, iters_per_epoch=10**7)
     ref = binding.SA(data, accept="single", neighbours_per_step=8, seed=5)
+    assert shift is None or block_shift(inc) == block_shift(ref) == shift
     o = Oracle(data, dict_limit=0x400000)
     accepted = 0
     for s in range(steps):
@@ -158,19 +177,21 @@ def test_incremental_accept_equals_rebuild(name, K, steps, golden, golden_input)
     ref.close()
 
 
-@pytest.mark.parametrize("name,K,steps,lcpb", [("lorem4k", 96, 80, {}), ("enwik3k", 128, 80, {}), ("reps", 64, 80, {}), ("zeros600", 32, 40, {}),
-                                               ("enwik3k", 128, 60, dict(lc=2, lp=1, pb=2))], ids=["lorem4k", "enwik3k", "reps", "zeros600", "enwik3k-lc2lp1pb2"])
-def test_batch_accept_equals_rebuild(name, K, steps, lcpb, golden, golden_input, monkeypatch):
+@with_shifts("name,K,steps,lcpb", [("lorem4k", 96, 80, {}), ("enwik3k", 128, 80, {}), ("reps", 64, 80, {}), ("zeros600", 32, 40, {}),
+                                   ("enwik3k", 128, 60, dict(lc=2, lp=1, pb=2))], ids=["lorem4k", "enwik3k", "reps", "zeros600", "enwik3k-lc2lp1pb2"])
+def test_batch_accept_equals_rebuild(name, K, steps, lcpb, shift, golden, golden_input, monkeypatch):
     """Bulk steps that take at most MGL_BATCH_MAX moves patch the base for all of them at once (mgl_kernels5.hip) instead of
     re-deriving it: after every such step bitmaps, special-state records, chains and dense checkpoints are identical to a
     rebuild from the slab, the cost is the oracle's walk of the slab, and a chain with the batch path switched off
     (MGL_NO_BATCH: every bulk step a rebuild) walks the same trajectory."""
     data = golden_input(name)
+    use_block_shift(monkeypatch, shift)
     inc = binding.SA(data, accept="bulk", neighbours_per_step=K, seed=5, iters_per_epoch=10**7, **lcpb)
     monkeypatch.setenv("MGL_NO_BATCH", "1")
     full = binding.SA(data, accept="bulk", neighbours_per_step=K, seed=5, iters_per_epoch=10**7, **lcpb)
     monkeypatch.delenv("MGL_NO_BATCH")
     ref = binding.SA(data, accept="single", neighbours_per_step=8, seed=5, **lcpb)
+    assert shift is None or block_shift(inc) == block_shift(full) == block_shift(ref) == shift
     o = Oracle(data, dict_limit=0x400000, **lcpb)
     moves = multi = 0
     for s in range(steps):
@@ -194,17 +215,20 @@ def test_batch_accept_equals_rebuild(name, K, steps, lcpb, golden, golden_input,
     inc.close(); full.close(); ref.close()
 
 
-def test_batch_accept_that_gives_up_falls_back_to_the_rebuild(monkeypatch):
+@pytest.mark.parametrize("shift", SHIFTS, ids=["rule", "shift9", "shift10"])
+def test_batch_accept_that_gives_up_falls_back_to_the_rebuild(shift, monkeypatch):
     """The batch accept's own fallback -- it has written journals and bitmaps, then a capacity is exceeded while the chains are
     rewritten -- is rare in real steps (tests/test_gpu_accept_giveups.py meets one, and takes every site of it with lowered
     capacities); mgl_debug_set key 5 forces it, here in its first form, at the top of the chain kernel.  The step must end exactly where the
     chain without the batch path ends (rebuild from the slab the commit left), and the next steps go on patching in place."""
     data = corpus.enwik_like(30000, 0x5151)
+    use_block_shift(monkeypatch, shift)
     a = binding.SA(data, accept="bulk", neighbours_per_step=256, seed=9, iters_per_epoch=10**7)
     monkeypatch.setenv("MGL_NO_BATCH", "1")
     b = binding.SA(data, accept="bulk", neighbours_per_step=256, seed=9, iters_per_epoch=10**7)
     monkeypatch.delenv("MGL_NO_BATCH")
     ref = binding.SA(data, accept="single", neighbours_per_step=8, seed=5)
+    assert shift is None or block_shift(a) == block_shift(b) == block_shift(ref) == shift
     for x in (a, b):
         x.run(12)
     a.debug_set(5, 3)
@@ -242,15 +266,17 @@ def test_full_size_c2_batch_path_vs_rebuild_path(monkeypatch):
     a.close(); b.close()
 
 
-@pytest.mark.parametrize("name,K", [("lorem4k", 64), ("enwik3k", 96)])
-def test_epoch_snapshots_equal_rebuild(name, K, golden, golden_input):
+@with_shifts("name,K", [("lorem4k", 64), ("enwik3k", 96)])
+def test_epoch_snapshots_equal_rebuild(name, K, shift, golden, golden_input, monkeypatch):
     """mgl_sa_begin_epoch restores the all-literal / best base structures from device copies;
     the chain must be indistinguishable from one that re-derives them from the slab
     (MGL_F_NO_SNAPSHOTS), across main.c:69-77's phase/epoch schedule."""
     data = golden_input(name)
     steps = (len(data) + K - 1) // K
+    use_block_shift(monkeypatch, shift)
     a = binding.SA(data, accept="single", neighbours_per_step=K, seed=11, iters_per_epoch=len(data))
     b = binding.SA(data, accept="single", neighbours_per_step=K, seed=11, iters_per_epoch=len(data), snapshots=False)
+    assert shift is None or block_shift(a) == block_shift(b) == shift
     o = Oracle(data, dict_limit=0x400000)
     for phase in range(3):
         for epoch in range(3):
@@ -313,12 +339,15 @@ def test_parallel_build_equals_serial_build(cfg, size, K, steps, accept):
     ser.close()
 
 
-def test_parallel_build_serial_segment_path():
+@pytest.mark.parametrize("shift", SHIFTS, ids=["rule", "shift9", "shift10"])
+def test_parallel_build_serial_segment_path(shift, monkeypatch):
     """pb_sim starts a chain segment from a warm-up that brackets the probability; pb_sim_fix redoes
     the segments whose bracket did not close.  That never happens on these inputs, so force it
     (mgl_debug_set key 1) and require the same structures and cost."""
     data, _ = corpus.config_input("c2", 60000)
+    use_block_shift(monkeypatch, shift)
     a = binding.SA(data, accept="single", neighbours_per_step=512, seed=9)
+    assert shift is None or block_shift(a) == shift
     a.run(30)
     cur, cost = a.current()
     want = canonical_base(a, cur)
