@@ -486,7 +486,9 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * clusters or a walk gave up (status 2 with a failure seen), 81 / 82 the batch accept's header and totals, 83 the chain index,
  * selector 84 one u32: the give-up sites of the in-place accepts seen since the last dump (MGL_GU_* bits of csrc/mgl_base2.h;
  * cleared by the dump and by key 6), 85 one u32: the chain pool's top, 86 three u32: the chain index's block shift (the size
- * rule's or MGL_SB_SHIFT's; the parallel builder's block is the same), its blocks and the words of an index row.
+ * rule's or MGL_SB_SHIFT's; the parallel builder's block is the same), its blocks and the words of an index row,
+ * 87 two u64 host counters, answered by every handle (the full-walk engine's too, like 21 and 22): the device allocations the
+ * handle holds right now and their total bytes as requested.
  * 26 / 27 (empty with MGL_NO_ORDER=1 or position targets): what the last targets launch left for the fused pick + walk launch --
  * K bytes, 1 = the neighbour will pick, 0 = it takes a grow/shrink mutation; and K u32, every slice's neighbours in the order
  * the launch takes them up (the picking ones first, ascending in j inside each class).  28: the two-launch form's pickstate

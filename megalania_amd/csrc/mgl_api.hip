@@ -15,6 +15,7 @@
 #include "mgl_props.hip"
 #include "mgl_crossover.hip"
 #include "../../include/megalania_hip.h"
+#include "mgl_owner.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -46,6 +47,28 @@ static int fail(int code, const std::string& msg)
 			return fail(MGL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
 	} while (0)
 
+#define TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0) /* an MGL_* code other than MGL_OK goes up */
+/* `bytes` of device memory from `own` at *ptr, every byte `fill` (-1: as it comes).  An allocation that does not fit is an
+ * MGL_EDEVICE error like any other failed runtime call -- or, for a caller that names `nomem`, MGL_ENOMEM with that message,
+ * and no error is left behind for the next launch check */
+static int dalloc(DevOwner& own, void** ptr, size_t bytes, int fill = -1, const char* nomem = nullptr)
+{
+	const hipError_t e = own.device(ptr, bytes);
+	if (e != hipSuccess && nomem) {
+		(void)hipGetLastError();
+		return fail(MGL_ENOMEM, nomem);
+	}
+	if (e != hipSuccess) return fail(MGL_EDEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+	if (fill >= 0) HIPCHK(hipMemset(*ptr, fill, bytes));
+	return MGL_OK;
+}
+/* the same for `count` elements of the pointer's type */
+template <class T>
+static int dnew(DevOwner& own, T*& ptr, size_t count, int fill = -1, const char* nomem = nullptr)
+{
+	return dalloc(own, (void**)&ptr, sizeof(T) * count, fill, nomem);
+}
+
 extern "C" const char* mgl_version(void) { return "megalania-hip 0.1 (gfx950)"; }
 extern "C" const char* mgl_last_error(void) { return g_err.c_str(); }
 extern "C" int mgl_device_count(void)
@@ -64,9 +87,22 @@ struct BaseMem {
 	Control* ctl;
 };
 
+/* the match index (mgl_index.hip) as the host builds it; DevCtx holds const views of the same arrays (fill_ctx_index) */
+struct MatchIndex {
+	uint32_t *bucket_off = nullptr, *bucket_pos = nullptr, *quad_pos = nullptr;
+	uint16_t *bucket_nx = nullptr, *quad_nx = nullptr;
+	/* exact-length orders D = 2..7; xpos[0] and xpos[2] alias bucket_pos / quad_pos, D = 2 has no rank / run */
+	uint32_t *xpos[6] = {}, *xrank[6] = {}, *xrun[6] = {};
+	uint8_t* xnxb[6] = {};
+	uint32_t *oct_pos = nullptr, *oct_rank = nullptr, *oct_run = nullptr;
+	uint32_t *hex_pos = nullptr, *hex_rank = nullptr, *hex_run = nullptr;
+	uint64_t *oct_nx8 = nullptr, *hex_nx8 = nullptr;
+};
+
 struct mgl_sa {
+	DevOwner own;            /* every device buffer, pinned buffer, event and stream of the handle: released when the handle is deleted */
 	int device;
-	hipStream_t stream;
+	hipStream_t stream = nullptr;
 	hipStream_t stream2;     /* second half of a step's neighbours: its kernels fill the other half's tails */
 	hipEvent_t ev_fork, ev_join;
 	hipEvent_t ev_tgt = nullptr, ev_tgt_go = nullptr; /* the next step's targets worked out beside the rest of this step's accept (launch_targets_ahead) */
@@ -80,19 +116,7 @@ struct mgl_sa {
 	uint64_t temperature = 0; /* mgl_sa_set_temperature: 0 = the reference's accept rule */
 	DevCtx ctx;
 	uint8_t* d_data;
-	uint32_t* d_bucket_off;
-	uint32_t* d_bucket_pos;
-	uint16_t* d_bucket_nx;
-	uint32_t* d_quad_pos;
-	uint16_t* d_quad_nx;
-	uint32_t *d_quad_rank = nullptr, *d_quad_run = nullptr;
-	uint32_t* d_xpos[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };  /* exact-length orders D = 2..7; [0] and [2] alias bucket_pos / quad_pos */
-	uint32_t* d_xrank[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-	uint32_t* d_xrun[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-	uint8_t* d_xnxb[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-	uint32_t *d_oct_pos = nullptr, *d_oct_rank = nullptr, *d_oct_run = nullptr;
-	uint32_t *d_hex_pos = nullptr, *d_hex_rank = nullptr, *d_hex_run = nullptr;
-	uint64_t *d_oct_nx8 = nullptr, *d_hex_nx8 = nullptr;
+	MatchIndex ix;
 	uint16_t* d_cost_tbl;
 	BaseMem base, scratch;
 	mgl_pk* d_best;
@@ -198,93 +222,78 @@ static uint64_t ceil_sqrt_u64(uint64_t x)
 	return r * r == x ? r : r + 1;
 }
 
-static void dfree(void* p) { if (p) (void)hipFree(p); }
-static void free_base(BaseMem& b)
-{
-	dfree(b.v.slab); dfree(b.v.onwalk); dfree(b.v.ckpt_probs); dfree(b.v.ckpt_hdr); dfree(b.ctl);
-	memset(&b, 0, sizeof b);
-}
-static hipError_t alloc_base(BaseMem& b, uint32_t n, uint32_t ckpt_elems)
+static int alloc_base(DevOwner& own, BaseMem& b, uint32_t n, uint32_t ckpt_elems)
 {
 	memset(&b, 0, sizeof b);
-	hipError_t e;
 	b.v.nckpt = (n + (1u << MGL_CKPT_SHIFT) - 1u) >> MGL_CKPT_SHIFT;
 	b.v.ckpt_elems = ckpt_elems;
-	if ((e = hipMalloc(&b.v.slab, sizeof(mgl_pk) * (size_t)n)) != hipSuccess) return e;
-	if ((e = hipMalloc(&b.v.onwalk, sizeof(uint64_t) * (((size_t)n + 63) / 64 + 1))) != hipSuccess) return e;
-	if ((e = hipMalloc(&b.v.ckpt_probs, sizeof(uint16_t) * (size_t)b.v.nckpt * ckpt_elems)) != hipSuccess) return e;
-	if ((e = hipMalloc(&b.v.ckpt_hdr, sizeof(CkptHdr) * (size_t)b.v.nckpt)) != hipSuccess) return e;
-	if ((e = hipMalloc(&b.ctl, sizeof(Control))) != hipSuccess) return e;
-	if ((e = hipMemset(b.v.onwalk, 0, sizeof(uint64_t) * (((size_t)n + 63) / 64 + 1))) != hipSuccess) return e;
-	return hipMemset(b.ctl, 0, sizeof(Control));
+	TRY(dnew(own, b.v.slab, n));
+	TRY(dnew(own, b.v.onwalk, ((size_t)n + 63) / 64 + 1, 0));
+	TRY(dnew(own, b.v.ckpt_probs, (size_t)b.v.nckpt * ckpt_elems));
+	TRY(dnew(own, b.v.ckpt_hdr, b.v.nckpt));
+	return dnew(own, b.ctl, 1, 0);
 }
 
-static size_t b2_pool_entries(const Base2& b) { return (size_t)b.pool_cap + 256; }
-/* device arrays of the incremental base; `own_slab`: also the slab and the on-walk bitmap */
-static int alloc_b2(Base2& b, size_t n, bool own_slab, bool init, size_t* bytes_out)
+/* One device array of a Base2: where its pointer lives, its bytes, the element size if it is one of the two chain pool arrays
+ * (4 ch_pos, 2 ch_ev, else 0: a snapshot copies a pool array up to the pool's top only), the byte a fresh base fills it with
+ * (-1: none), and what it adds to the total alloc_b2 reports (the pool arrays without their 256 entries of slack, the small
+ * arrays nothing). */
+struct B2Array {
+	void** ptr;
+	size_t bytes;
+	uint32_t pool_elem;
+	int fill;
+	size_t counted;
+};
+#define MGL_B2_ARRAYS 14u
+static_assert(MGL_B2_ARRAYS <= MGL_SNAP_SEGS, "a snapshot's plan holds a segment per array");
+/* the arrays of `b` for an input of n bytes, in the order of a snapshot's segments */
+static void b2_arrays(Base2& b, size_t n, B2Array a[MGL_B2_ARRAYS])
 {
+	const size_t pool = (size_t)b.pool_cap + 256, ck = sizeof(uint32_t) * b.ck_elems, sb = sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride;
+	uint32_t k = 0;
+	a[k++] = { (void**)&b.slab, sizeof(mgl_pk) * n, 0, -1, sizeof(mgl_pk) * n };
+	a[k++] = { (void**)&b.onwalk, sizeof(uint64_t) * ((n + 63) / 64 + 1), 0, -1, 0 };
+	a[k++] = { (void**)&b.sp0, sizeof(uint64_t) * (b.nw0 + 64), 0, 0, sizeof(uint64_t) * (b.nw0 + 64) };
+	a[k++] = { (void**)&b.sp1, sizeof(uint64_t) * (b.nw1 + 64), 0, 0, 0 };
+	a[k++] = { (void**)&b.sp2, sizeof(uint64_t) * (b.nw2 + 64), 0, 0, 0 };
+	a[k++] = { (void**)&b.sp_state, sizeof(uint32_t) * 8 * n, 0, -1, sizeof(uint32_t) * 8 * n };
+	a[k++] = { (void**)&b.ck_probs, sizeof(uint16_t) * (size_t)b.nck * b.ck_elems, 0, -1, sizeof(uint16_t) * (size_t)b.nck * b.ck_elems };
+	a[k++] = { (void**)&b.ch_off, ck, 0, -1, 0 };
+	a[k++] = { (void**)&b.ch_len, ck, 0, -1, 0 };
+	a[k++] = { (void**)&b.ch_cap, ck, 0, -1, 0 };
+	a[k++] = { (void**)&b.ch_pos, sizeof(uint32_t) * pool, 4, 0xFF, sizeof(uint32_t) * (size_t)b.pool_cap };
+	a[k++] = { (void**)&b.ch_ev, sizeof(uint16_t) * pool, 2, 0, sizeof(uint16_t) * (size_t)b.pool_cap };
+	a[k++] = { (void**)&b.pool_top, sizeof(uint32_t), 0, -1, 0 };
+	a[k++] = { (void**)&b.ch_sb, sb, 0, 0, sb };
+}
+/* device arrays of the incremental base, its geometry set; `own_slab`: also the slab and the on-walk bitmap (else they are the
+ * caller's); `init`: filled as a fresh base's */
+static int alloc_b2(DevOwner& own, Base2& b, size_t n, bool own_slab, bool init, size_t* bytes_out)
+{
+	B2Array a[MGL_B2_ARRAYS];
+	b2_arrays(b, n, a);
 	size_t bytes = 0;
-	if (own_slab) {
-		HIPCHK(hipMalloc(&b.slab, sizeof(mgl_pk) * n)); bytes += sizeof(mgl_pk) * n;
-		HIPCHK(hipMalloc(&b.onwalk, sizeof(uint64_t) * ((n + 63) / 64 + 1)));
-	}
-	HIPCHK(hipMalloc(&b.sp0, sizeof(uint64_t) * (b.nw0 + 64))); bytes += sizeof(uint64_t) * (b.nw0 + 64);
-	HIPCHK(hipMalloc(&b.sp1, sizeof(uint64_t) * (b.nw1 + 64)));
-	HIPCHK(hipMalloc(&b.sp2, sizeof(uint64_t) * (b.nw2 + 64)));
-	HIPCHK(hipMalloc(&b.sp_state, sizeof(uint32_t) * 8 * n)); bytes += sizeof(uint32_t) * 8 * n;
-	HIPCHK(hipMalloc(&b.ck_probs, sizeof(uint16_t) * (size_t)b.nck * b.ck_elems)); bytes += sizeof(uint16_t) * (size_t)b.nck * b.ck_elems;
-	HIPCHK(hipMalloc(&b.ch_off, sizeof(uint32_t) * b.ck_elems));
-	HIPCHK(hipMalloc(&b.ch_len, sizeof(uint32_t) * b.ck_elems));
-	HIPCHK(hipMalloc(&b.ch_cap, sizeof(uint32_t) * b.ck_elems));
-	HIPCHK(hipMalloc(&b.ch_pos, sizeof(uint32_t) * b2_pool_entries(b))); bytes += sizeof(uint32_t) * (size_t)b.pool_cap;
-	HIPCHK(hipMalloc(&b.ch_ev, sizeof(uint16_t) * b2_pool_entries(b))); bytes += sizeof(uint16_t) * (size_t)b.pool_cap;
-	HIPCHK(hipMalloc(&b.pool_top, sizeof(uint32_t)));
-	HIPCHK(hipMalloc(&b.ch_sb, sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride)); bytes += sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride;
-	if (init) {
-		HIPCHK(hipMemset(b.ch_sb, 0, sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride));
-		HIPCHK(hipMemset(b.sp0, 0, sizeof(uint64_t) * (b.nw0 + 64)));
-		HIPCHK(hipMemset(b.sp1, 0, sizeof(uint64_t) * (b.nw1 + 64)));
-		HIPCHK(hipMemset(b.sp2, 0, sizeof(uint64_t) * (b.nw2 + 64)));
-		HIPCHK(hipMemset(b.ch_pos, 0xFF, sizeof(uint32_t) * b2_pool_entries(b)));
-		HIPCHK(hipMemset(b.ch_ev, 0, sizeof(uint16_t) * b2_pool_entries(b)));
+	for (uint32_t k = own_slab ? 0u : 2u; k < MGL_B2_ARRAYS; k++) {
+		TRY(dalloc(own, a[k].ptr, a[k].bytes, init ? a[k].fill : -1));
+		bytes += a[k].counted;
 	}
 	if (bytes_out) *bytes_out = bytes;
 	return MGL_OK;
 }
-static void free_b2(Base2& b, bool own_slab)
-{
-	if (own_slab) { dfree(b.slab); dfree(b.onwalk); }
-	dfree(b.sp0); dfree(b.sp1); dfree(b.sp2); dfree(b.sp_state); dfree(b.ck_probs);
-	dfree(b.ch_off); dfree(b.ch_len); dfree(b.ch_cap); dfree(b.ch_pos); dfree(b.ch_ev); dfree(b.pool_top); dfree(b.ch_sb);
-	memset(&b, 0, sizeof b);
-}
 /* dir 0: base -> snapshot, dir 1: snapshot -> base; cond: only if this step found a new best */
 static int launch_snapshot(mgl_sa* sa, Base2& snap, uint32_t which, int dir, int cond)
 {
-	const Base2& from = dir == 0 ? sa->b2 : snap;
-	const Base2& to = dir == 0 ? snap : sa->b2;
-	const size_t n = sa->n;
+	Base2 from = dir == 0 ? sa->b2 : snap, to = dir == 0 ? snap : sa->b2;
+	B2Array src[MGL_B2_ARRAYS], dst[MGL_B2_ARRAYS];
+	b2_arrays(from, sa->n, src);
+	b2_arrays(to, sa->n, dst);
 	SnapPlan p;
 	memset(&p, 0, sizeof p);
-	uint32_t k = 0;
-	auto seg = [&](const void* s, void* d, size_t bytes, uint32_t pool_elem) {
-		p.seg[k].src = s; p.seg[k].dst = d; p.seg[k].bytes = bytes; p.seg[k].pool_elem = pool_elem; k++;
-	};
-	seg(from.slab, to.slab, sizeof(mgl_pk) * n, 0);
-	seg(from.onwalk, to.onwalk, sizeof(uint64_t) * ((n + 63) / 64 + 1), 0);
-	seg(from.sp0, to.sp0, sizeof(uint64_t) * (from.nw0 + 64), 0);
-	seg(from.sp1, to.sp1, sizeof(uint64_t) * (from.nw1 + 64), 0);
-	seg(from.sp2, to.sp2, sizeof(uint64_t) * (from.nw2 + 64), 0);
-	seg(from.sp_state, to.sp_state, sizeof(uint32_t) * 8 * n, 0);
-	seg(from.ck_probs, to.ck_probs, sizeof(uint16_t) * (size_t)from.nck * from.ck_elems, 0);
-	seg(from.ch_off, to.ch_off, sizeof(uint32_t) * from.ck_elems, 0);
-	seg(from.ch_len, to.ch_len, sizeof(uint32_t) * from.ck_elems, 0);
-	seg(from.ch_cap, to.ch_cap, sizeof(uint32_t) * from.ck_elems, 0);
-	seg(from.ch_pos, to.ch_pos, sizeof(uint32_t) * b2_pool_entries(from), 4);
-	seg(from.ch_ev, to.ch_ev, sizeof(uint16_t) * b2_pool_entries(from), 2);
-	seg(from.pool_top, to.pool_top, sizeof(uint32_t), 0);
-	seg(from.ch_sb, to.ch_sb, sizeof(uint32_t) * (size_t)from.ck_elems * from.sb_stride, 0);
-	p.nseg = k;
+	for (uint32_t k = 0; k < MGL_B2_ARRAYS; k++) {
+		p.seg[k].src = *src[k].ptr; p.seg[k].dst = *dst[k].ptr; p.seg[k].bytes = src[k].bytes; p.seg[k].pool_elem = src[k].pool_elem;
+	}
+	p.nseg = MGL_B2_ARRAYS;
 	p.src_pool_top = from.pool_top;
 	hipLaunchKernelGGL(k_snapshot, dim3(2048), dim3(256), 0, sa->stream, p, sa->base.ctl, sa->d_snap_meta + which, dir, cond);
 	HIPCHK(hipGetLastError());
@@ -413,15 +422,17 @@ static int launch_apply(mgl_sa* sa, uint64_t next_gstep = ~0ull)
 /* diagnostic switches of the launch path, read once */
 static const bool g_trace = getenv("MGL_TRACE") != nullptr, g_prof_big = getenv("MGL_PROF_BIG") != nullptr;
 #define NBR_TRACE(name) do { if (g_trace) { fprintf(stderr, "[mgl] %s\n", name); hipError_t e_ = hipDeviceSynchronize(); if (e_ != hipSuccess) fprintf(stderr, "[mgl] %s -> %s\n", name, hipGetErrorString(e_)); } } while (0)
-static hipEvent_t sim_event(mgl_sa* sa, size_t i)
+/* event i of a pool that grows on demand; the events are the handle's */
+static hipEvent_t pool_event(mgl_sa* sa, std::vector<hipEvent_t>& pool, size_t i)
 {
-	while (sa->ev_sim_pool.size() <= i) {
+	while (pool.size() <= i) {
 		hipEvent_t e = nullptr;
-		if (hipEventCreate(&e) != hipSuccess) return nullptr;
-		sa->ev_sim_pool.push_back(e);
+		if (sa->own.event(&e) != hipSuccess) return nullptr;
+		pool.push_back(e);
 	}
-	return sa->ev_sim_pool[i];
+	return pool[i];
 }
+static hipEvent_t sim_event(mgl_sa* sa, size_t i) { return pool_event(sa, sa->ev_sim_pool, i); }
 static uint32_t nbr_slices(const mgl_sa* sa)
 {
 	const uint32_t K = sa->cfg.neighbours_per_step;
@@ -583,483 +594,397 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 	if (!sa) return;
 	(void)hipSetDevice(sa->device);
 	if (sa->stream) (void)hipStreamSynchronize(sa->stream);
-	dfree(sa->d_data); dfree(sa->d_bucket_off); dfree(sa->d_bucket_pos); dfree(sa->d_bucket_nx); dfree(sa->d_quad_pos); dfree(sa->d_quad_nx); dfree(sa->d_cost_tbl);
-	dfree(sa->d_quad_rank); dfree(sa->d_quad_run); dfree(sa->d_oct_pos);
-	for (int i = 0; i < 6; i++) { if (i != 0 && i != 2) { dfree(sa->d_xpos[i]); dfree(sa->d_xrank[i]); dfree(sa->d_xrun[i]); } dfree(sa->d_xnxb[i]); } dfree(sa->d_oct_rank); dfree(sa->d_oct_run);
-	dfree(sa->d_hex_pos); dfree(sa->d_hex_rank); dfree(sa->d_hex_run); dfree(sa->d_oct_nx8); dfree(sa->d_hex_nx8);
-	free_base(sa->base); free_base(sa->scratch);
-	if (!sa->snapshots) dfree(sa->d_best); /* otherwise it is the best snapshot's slab */
-	dfree(sa->nbr.cost); dfree(sa->nbr.ndiffs); dfree(sa->nbr.walked); dfree(sa->nbr.win); dfree(sa->nbr.win2); dfree(sa->nbr.dpos);
-	dfree(sa->bulk.ckey); dfree(sa->bulk.cwin); dfree(sa->bulk.taken); dfree(sa->bulk.cstate); dfree(sa->bulk.cflags); dfree(sa->bulk.hdr);
-	dfree(sa->nbr.dold); dfree(sa->nbr.dnew);
-	dfree(sa->d_aos); dfree(sa->d_cum); dfree(sa->d_final_probs);
-	free_b2(sa->b2, false);
-	free_b2(sa->snap_lit, true); free_b2(sa->snap_best, true); dfree(sa->d_snap_meta);
-	dfree(sa->pb.exits); dfree(sa->pb.entry); dfree(sa->pb.gexits); dfree(sa->pb.gentry); dfree(sa->pb.gsum); dfree(sa->pb.ch_map); dfree(sa->pb.ch_vs); dfree(sa->pb.ch_pk); dfree(sa->pb.ch_state); dfree(sa->pb.tf_ctx); dfree(sa->pb.tf_dist); dfree(sa->pb.tf_pk);
-	dfree(sa->pb.st_in); dfree(sa->pb.hist); dfree(sa->pb.stage); dfree(sa->pb.stage_n); dfree(sa->pb.stage_over); dfree(sa->pb.acc); dfree(sa->pb.seg_off); dfree(sa->pb.unres);
-	dfree(sa->d_todo); dfree(sa->d_prof);
-	dfree(sa->big.sim_hdr); dfree(sa->big.sim_keys); dfree(sa->big.sim_pos);
-	dfree(sa->big.ins_key); dfree(sa->big.rem_key); dfree(sa->big.ins_pos); dfree(sa->big.rem_pos); dfree(sa->big.uctx);
-	if (sa->h_bstat) (void)hipHostFree(sa->h_bstat);
-	if (sa->ev_bstat) (void)hipEventDestroy(sa->ev_bstat);
-	dfree(sa->big.cont); dfree(sa->d_traffic); dfree(sa->d_strat_pre); dfree(sa->d_strat_tgt); dfree(sa->d_pick_hint); dfree(sa->d_pick_order);
-	{
-		BatchBuf& bt = sa->batch;
-		dfree(bt.hdr); dfree(bt.cl); dfree(bt.jpos); dfree(bt.jnew); dfree(bt.jold); dfree(bt.st_ikey); dfree(bt.st_rkey); dfree(bt.st_ipos);
-		dfree(bt.st_rpos); dfree(bt.ops); dfree(bt.ins_cl); dfree(bt.rem_cl); dfree(bt.acc); dfree(bt.runs);
-		dfree(bt.cnt_i); dfree(bt.cnt_r); dfree(bt.off_i); dfree(bt.off_r); dfree(bt.cur_i); dfree(bt.cur_r); dfree(bt.touched);
-		dfree(bt.bk_ipos); dfree(bt.bk_rpos); dfree(bt.bk_ibit); dfree(bt.bk_icl); dfree(bt.bk_rcl);
-	}
-	for (hipEvent_t e : sa->ev_sim_pool) if (e) (void)hipEventDestroy(e);
-	dfree(sa->d_todo2); dfree(sa->d_counts); dfree(sa->d_pickrec); dfree(sa->d_pickstate);
-	dfree(sa->lim.why); dfree(sa->ab.hdr); dfree(sa->ab.ins_key); dfree(sa->ab.rem_key); dfree(sa->ab.ins_pos); dfree(sa->ab.rem_pos);
-	dfree(sa->ab.tctx); dfree(sa->ab.scratch_pos); dfree(sa->ab.scratch_ev);
-	dfree(sa->ab.span_pos); dfree(sa->ab.span_ev); dfree(sa->ab.jobs_b); dfree(sa->ab.jobs_c);
-	dfree(sa->d_mf_off); dfree(sa->d_mf_src); dfree(sa->d_mf_len);
-	dfree(sa->d_topk_pk); dfree(sa->d_topk_cost); dfree(sa->d_small); dfree(sa->d_sub_offs); dfree(sa->d_sub_lens);
-	for (hipEvent_t e : sa->ev_pool) (void)hipEventDestroy(e);
-	if (sa->ev_begin) (void)hipEventDestroy(sa->ev_begin);
-	if (sa->ev_end) (void)hipEventDestroy(sa->ev_end);
-	if (sa->stream2) (void)hipStreamDestroy(sa->stream2);
-	if (sa->stream3) (void)hipStreamDestroy(sa->stream3);
-	for (auto& e : sa->ev_rest) if (e) (void)hipEventDestroy(e);
-	if (sa->ev_sim) (void)hipEventDestroy(sa->ev_sim);
-	if (sa->ev_val) (void)hipEventDestroy(sa->ev_val);
-	if (sa->ev_fork) (void)hipEventDestroy(sa->ev_fork);
-	if (sa->ev_tgt) (void)hipEventDestroy(sa->ev_tgt);
-	if (sa->ev_tgt_go) (void)hipEventDestroy(sa->ev_tgt_go);
-	if (sa->ev_join) (void)hipEventDestroy(sa->ev_join);
-	if (sa->stream) (void)hipStreamDestroy(sa->stream);
-	delete sa;
+	delete sa; /* sa->own releases everything the handle made */
 }
 
-static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
+/* ---- mgl_sa_create in stages: create_impl calls them in the order they stand in.  Everything is made through sa->own, so a
+ * stage that fails leaves nothing to undo: mgl_sa_create destroys the handle. */
+static int create_streams(mgl_sa* sa, size_t n)
 {
-	HIPCHK(hipSetDevice(sa->device));
-	HIPCHK(hipStreamCreate(&sa->stream));
-	HIPCHK(hipStreamCreate(&sa->stream2));
-	HIPCHK(hipEventCreateWithFlags(&sa->ev_fork, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&sa->ev_join, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&sa->ev_tgt, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&sa->ev_tgt_go, hipEventDisableTiming));
-	HIPCHK(hipStreamCreate(&sa->stream3));
-	for (auto& e : sa->ev_rest) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&sa->ev_sim, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&sa->ev_val, hipEventDisableTiming));
+	DevOwner& own = sa->own;
+	HIPCHK(own.stream(&sa->stream));
+	HIPCHK(own.stream(&sa->stream2));
+	for (hipEvent_t* e : { &sa->ev_fork, &sa->ev_join, &sa->ev_tgt, &sa->ev_tgt_go }) HIPCHK(own.event(e, hipEventDisableTiming));
+	HIPCHK(own.stream(&sa->stream3));
+	for (auto& e : sa->ev_rest) HIPCHK(own.event(&e, hipEventDisableTiming));
+	HIPCHK(own.event(&sa->ev_sim, hipEventDisableTiming));
+	HIPCHK(own.event(&sa->ev_val, hipEventDisableTiming));
 	/* measured: + 8 % on the 10 MB input, nothing on the 100 KB one (its kernels are too short to overlap) */
 	sa->halves = getenv("MGL_HALVES") ? (uint32_t)atoi(getenv("MGL_HALVES")) : (n > (1u << 20) ? 2u : 1u);
 	if (sa->halves < 1 || sa->halves > 8) sa->halves = 1;
-	HIPCHK(hipEventCreate(&sa->ev_begin));
-	HIPCHK(hipEventCreate(&sa->ev_end));
-	const mgl_layout L = mgl_make_layout(sa->props.lc, sa->props.lp, sa->props.pb);
-	const uint32_t ckpt_elems = (L.total + 7u) & ~7u;
+	HIPCHK(own.event(&sa->ev_begin));
+	HIPCHK(own.event(&sa->ev_end));
+	return MGL_OK;
+}
 
-	/* input, zero padded so that window loads past the end stay in bounds */
-	HIPCHK(hipMalloc(&sa->d_data, n + 128));
-	HIPCHK(hipMemset(sa->d_data, 0, n + 128));
-	HIPCHK(hipMemcpy(sa->d_data, data, n, hipMemcpyHostToDevice));
-
-	/* match index (substring_enumerator.c:26-47): positions bucketed by leading bigram, ascending
-	 * inside a bucket -- a stable two-pass counting sort on the device (mgl_index.hip) */
-	{
-		const uint32_t m = (uint32_t)(n - 1); /* positions that start a bigram */
-		HIPCHK(hipMalloc(&sa->d_bucket_off, sizeof(uint32_t) * 65537));
-		HIPCHK(hipMalloc(&sa->d_bucket_pos, sizeof(uint32_t) * (n ? n : 1)));
-		HIPCHK(hipMalloc(&sa->d_bucket_nx, sizeof(uint16_t) * (n ? n : 1)));
-		HIPCHK(hipMalloc(&sa->d_quad_pos, sizeof(uint32_t) * (n ? n : 1)));
-		HIPCHK(hipMalloc(&sa->d_quad_nx, sizeof(uint16_t) * (n ? n : 1)));
-		for (int i = 0; i < 6; i++) {
-			HIPCHK(hipMalloc(&sa->d_xnxb[i], n + 1));
-			HIPCHK(hipMemset(sa->d_xnxb[i], 0, n + 1));
-			if (i == 0 || i == 2) continue;
-			for (uint32_t** a : { &sa->d_xpos[i], &sa->d_xrank[i], &sa->d_xrun[i] }) {
-				HIPCHK(hipMalloc(a, sizeof(uint32_t) * (n + 1)));
-				HIPCHK(hipMemset(*a, 0, sizeof(uint32_t) * (n + 1)));
-			}
-		}
-		for (uint32_t** a : { &sa->d_quad_rank, &sa->d_quad_run, &sa->d_oct_pos, &sa->d_oct_rank, &sa->d_oct_run, &sa->d_hex_pos, &sa->d_hex_rank, &sa->d_hex_run }) {
-			HIPCHK(hipMalloc(a, sizeof(uint32_t) * (n + 1)));
-			HIPCHK(hipMemset(*a, 0, sizeof(uint32_t) * (n + 1)));
-		}
-		HIPCHK(hipMalloc(&sa->d_oct_nx8, sizeof(uint64_t) * (n + 1)));
-		HIPCHK(hipMalloc(&sa->d_hex_nx8, sizeof(uint64_t) * (n + 1)));
-		if (m == 0) HIPCHK(hipMemset(sa->d_bucket_off, 0, sizeof(uint32_t) * 65537));
-		else {
-			const uint32_t nblk = (m + MGL_IX_ITEMS - 1) / MGL_IX_ITEMS;
-			uint32_t *tmp = nullptr, *matrix = nullptr;
-			HIPCHK(hipMalloc(&tmp, sizeof(uint32_t) * m));
-			HIPCHK(hipMalloc(&matrix, sizeof(uint32_t) * 256 * (size_t)nblk));
-			/* bigram order: by data[p + 1], then data[p] */
-			for (int pass = 1; pass >= 0; pass--) {
-				const uint32_t* in = pass == 1 ? nullptr : tmp;
-				uint32_t* out = pass == 1 ? tmp : sa->d_bucket_pos;
-				hipLaunchKernelGGL(ix_count, dim3(nblk), dim3(64), 0, sa->stream, (const uint8_t*)sa->d_data, in, m, pass, matrix, nblk);
-				hipLaunchKernelGGL(ix_scan, dim3(1), dim3(1024), 0, sa->stream, matrix, 256u * nblk);
-				hipLaunchKernelGGL(ix_scatter, dim3(nblk), dim3(64), 0, sa->stream, (const uint8_t*)sa->d_data, in, out, m, pass,
-				                   (const uint32_t*)matrix, nblk);
-			}
-			hipLaunchKernelGGL(ix_offsets, dim3(m / 256 + 1), dim3(256), 0, sa->stream, (const uint8_t*)sa->d_data,
-			                   (const uint32_t*)sa->d_bucket_pos, m, sa->d_bucket_off);
-			hipLaunchKernelGGL(ix_next2, dim3(m / 256 + 1), dim3(256), 0, sa->stream, (const uint8_t*)sa->d_data,
-			                   (const uint32_t*)sa->d_bucket_pos, m, sa->d_bucket_nx, 0);
-			/* four-byte order: by data[p + 3], data[p + 2], data[p + 1], data[p] (ping-pong tmp <-> quad_pos) */
-			for (int pass = 3; pass >= 0; pass--) {
-				const uint32_t* in = pass == 3 ? nullptr : ((pass & 1) ? (const uint32_t*)sa->d_quad_pos : (const uint32_t*)tmp);
-				uint32_t* out = (pass & 1) ? tmp : sa->d_quad_pos;
-				hipLaunchKernelGGL(ix_count, dim3(nblk), dim3(64), 0, sa->stream, (const uint8_t*)sa->d_data, in, m, pass, matrix, nblk);
-				hipLaunchKernelGGL(ix_scan, dim3(1), dim3(1024), 0, sa->stream, matrix, 256u * nblk);
-				hipLaunchKernelGGL(ix_scatter, dim3(nblk), dim3(64), 0, sa->stream, (const uint8_t*)sa->d_data, in, out, m, pass,
-				                   (const uint32_t*)matrix, nblk);
-			}
-			hipLaunchKernelGGL(ix_next2, dim3(m / 256 + 1), dim3(256), 0, sa->stream, (const uint8_t*)sa->d_data,
-			                   (const uint32_t*)sa->d_quad_pos, m, sa->d_quad_nx, 1);
-			/* the eight- and sixteen-byte orders, and for all three deeper orders: rank, run starts, next bytes */
-			sa->d_xpos[0] = sa->d_bucket_pos; sa->d_xpos[2] = sa->d_quad_pos;
-			sa->d_xrank[2] = sa->d_quad_rank; sa->d_xrun[2] = sa->d_quad_run;
-			for (uint32_t D : { 3u, 5u, 6u, 7u, 8u, 16u }) {
-				uint32_t* dst = D == 8 ? sa->d_oct_pos : D == 16 ? sa->d_hex_pos : sa->d_xpos[D - 2];
-				for (int pass = (int)D - 1; pass >= 0; pass--) {
-					/* ping-pong so that the last pass (byte 0) lands in dst */
-					const uint32_t* in = pass == (int)D - 1 ? nullptr : ((pass & 1) ? (const uint32_t*)dst : (const uint32_t*)tmp);
-					uint32_t* out = (pass & 1) ? tmp : dst;
-					hipLaunchKernelGGL(ix_count, dim3(nblk), dim3(64), 0, sa->stream, (const uint8_t*)sa->d_data, in, m, pass, matrix, nblk);
-					hipLaunchKernelGGL(ix_scan, dim3(1), dim3(1024), 0, sa->stream, matrix, 256u * nblk);
-					hipLaunchKernelGGL(ix_scatter, dim3(nblk), dim3(64), 0, sa->stream, (const uint8_t*)sa->d_data, in, out, m, pass,
-					                   (const uint32_t*)matrix, nblk);
-				}
-			}
-			struct { const uint32_t* pos; uint32_t* rank; uint32_t* run; void* nx; uint32_t D, nxbytes; } lv[7] = {
-				{ sa->d_xpos[1], sa->d_xrank[1], sa->d_xrun[1], sa->d_xnxb[1], 3u, 1u },
-				{ sa->d_quad_pos, sa->d_quad_rank, sa->d_quad_run, sa->d_xnxb[2], 4u, 1u },
-				{ sa->d_xpos[3], sa->d_xrank[3], sa->d_xrun[3], sa->d_xnxb[3], 5u, 1u },
-				{ sa->d_xpos[4], sa->d_xrank[4], sa->d_xrun[4], sa->d_xnxb[4], 6u, 1u },
-				{ sa->d_xpos[5], sa->d_xrank[5], sa->d_xrun[5], sa->d_xnxb[5], 7u, 1u },
-				{ sa->d_oct_pos, sa->d_oct_rank, sa->d_oct_run, sa->d_oct_nx8, 8u, 8u },
-				{ sa->d_hex_pos, sa->d_hex_rank, sa->d_hex_run, sa->d_hex_nx8, 16u, 8u } };
-			hipLaunchKernelGGL(ix_next_byte, dim3(m / 256 + 1), dim3(256), 0, sa->stream, (const uint8_t*)sa->d_data, (const uint32_t*)sa->d_bucket_pos, m, sa->d_xnxb[0], 2u);
-			for (auto& l : lv) {
-				hipLaunchKernelGGL(ix_rank, dim3(m / 256 + 1), dim3(256), 0, sa->stream, l.pos, m, l.rank);
-				if (l.nxbytes == 1) hipLaunchKernelGGL(ix_next_byte, dim3(m / 256 + 1), dim3(256), 0, sa->stream, (const uint8_t*)sa->d_data, l.pos, m, (uint8_t*)l.nx, l.D);
-				else hipLaunchKernelGGL(ix_next_bytes, dim3(m / 256 + 1), dim3(256), 0, sa->stream, (const uint8_t*)sa->d_data, l.pos, m, l.nx, l.D, l.nxbytes);
-				hipLaunchKernelGGL(ix_heads, dim3(m / 256 + 1), dim3(256), 0, sa->stream, (const uint8_t*)sa->d_data, l.pos, m, l.D, l.run);
-				hipLaunchKernelGGL(ix_maxscan, dim3(1), dim3(1024), 0, sa->stream, l.run, m);
-			}
-			hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(sa->stream);
-			(void)hipFree(tmp); (void)hipFree(matrix);
-			HIPCHK(e1); HIPCHK(e2);
-		}
+static int alloc_match_index(mgl_sa* sa, size_t n)
+{
+	DevOwner& own = sa->own;
+	MatchIndex& ix = sa->ix;
+	TRY(dnew(own, ix.bucket_off, 65537));
+	TRY(dnew(own, ix.bucket_pos, n));
+	TRY(dnew(own, ix.bucket_nx, n));
+	TRY(dnew(own, ix.quad_pos, n));
+	TRY(dnew(own, ix.quad_nx, n));
+	ix.xpos[0] = ix.bucket_pos; ix.xpos[2] = ix.quad_pos; /* D = 2 and D = 4 are the bigram and the four-byte order */
+	for (int i = 0; i < 6; i++) {
+		TRY(dnew(own, ix.xnxb[i], n + 1, 0));
+		if (!ix.xpos[i]) TRY(dnew(own, ix.xpos[i], n + 1, 0));
+		if (i == 0) continue; /* the bucket bounds play the part of rank and run */
+		TRY(dnew(own, ix.xrank[i], n + 1, 0));
+		TRY(dnew(own, ix.xrun[i], n + 1, 0));
 	}
-	HIPCHK(hipMalloc(&sa->d_cost_tbl, sizeof(k_cost_table)));
-	HIPCHK(hipMemcpy(sa->d_cost_tbl, k_cost_table, sizeof(k_cost_table), hipMemcpyHostToDevice));
+	for (uint32_t** a : { &ix.oct_pos, &ix.oct_rank, &ix.oct_run, &ix.hex_pos, &ix.hex_rank, &ix.hex_run }) TRY(dnew(own, *a, n + 1, 0));
+	TRY(dnew(own, ix.oct_nx8, n + 1));
+	return dnew(own, ix.hex_nx8, n + 1);
+}
+/* match index (substring_enumerator.c:26-47): positions bucketed by leading bigram, ascending inside a bucket, and the
+ * deeper orders of the same positions -- stable counting sorts on the device (mgl_index.hip) */
+static int build_match_index(mgl_sa* sa, size_t n)
+{
+	TRY(alloc_match_index(sa, n));
+	const MatchIndex& ix = sa->ix;
+	const uint32_t m = (uint32_t)(n - 1); /* positions that start a bigram */
+	if (m == 0) {
+		HIPCHK(hipMemset(ix.bucket_off, 0, sizeof(uint32_t) * 65537));
+		return MGL_OK;
+	}
+	const uint8_t* data = sa->d_data;
+	hipStream_t st = sa->stream;
+	const uint32_t nblk = (m + MGL_IX_ITEMS - 1) / MGL_IX_ITEMS;
+	const dim3 per_pos(m / 256 + 1);
+	DevOwner scratch; /* gone when the index stands, and when a step fails */
+	uint32_t *tmp = nullptr, *matrix = nullptr;
+	TRY(dnew(scratch, tmp, m));
+	TRY(dnew(scratch, matrix, 256 * (size_t)nblk));
+	/* the positions ordered by their first D bytes, then by position, into dst: one count / scan / scatter pass per byte, the
+	 * last byte first.  The first pass reads no input (the positions in order); odd passes write tmp and even ones dst, so
+	 * that the last pass (byte 0) lands in dst */
+	auto radix_order = [&](uint32_t D, uint32_t* dst) {
+		for (int pass = (int)D - 1; pass >= 0; pass--) {
+			const uint32_t* in = pass == (int)D - 1 ? nullptr : ((pass & 1) ? (const uint32_t*)dst : (const uint32_t*)tmp);
+			uint32_t* out = (pass & 1) ? tmp : dst;
+			hipLaunchKernelGGL(ix_count, dim3(nblk), dim3(64), 0, st, data, in, m, pass, matrix, nblk);
+			hipLaunchKernelGGL(ix_scan, dim3(1), dim3(1024), 0, st, matrix, 256u * nblk);
+			hipLaunchKernelGGL(ix_scatter, dim3(nblk), dim3(64), 0, st, data, in, out, m, pass, (const uint32_t*)matrix, nblk);
+		}
+	};
+	/* of an order deeper than the bigram's: rank, the bytes that follow the prefix, run starts */
+	auto level = [&](const uint32_t* pos, uint32_t* rank, uint32_t* run, void* nx, uint32_t D, uint32_t nxbytes) {
+		hipLaunchKernelGGL(ix_rank, per_pos, dim3(256), 0, st, pos, m, rank);
+		if (nxbytes == 1) hipLaunchKernelGGL(ix_next_byte, per_pos, dim3(256), 0, st, data, pos, m, (uint8_t*)nx, D);
+		else hipLaunchKernelGGL(ix_next_bytes, per_pos, dim3(256), 0, st, data, pos, m, nx, D, nxbytes);
+		hipLaunchKernelGGL(ix_heads, per_pos, dim3(256), 0, st, data, pos, m, D, run);
+		hipLaunchKernelGGL(ix_maxscan, dim3(1), dim3(1024), 0, st, run, m);
+	};
+	radix_order(2, ix.bucket_pos); /* by data[p + 1], then data[p] */
+	hipLaunchKernelGGL(ix_offsets, per_pos, dim3(256), 0, st, data, (const uint32_t*)ix.bucket_pos, m, ix.bucket_off);
+	hipLaunchKernelGGL(ix_next2, per_pos, dim3(256), 0, st, data, (const uint32_t*)ix.bucket_pos, m, ix.bucket_nx, 0);
+	radix_order(4, ix.quad_pos);
+	hipLaunchKernelGGL(ix_next2, per_pos, dim3(256), 0, st, data, (const uint32_t*)ix.quad_pos, m, ix.quad_nx, 1);
+	for (uint32_t D : { 3u, 5u, 6u, 7u }) radix_order(D, ix.xpos[D - 2]);
+	radix_order(8, ix.oct_pos);
+	radix_order(16, ix.hex_pos);
+	hipLaunchKernelGGL(ix_next_byte, per_pos, dim3(256), 0, st, data, (const uint32_t*)ix.bucket_pos, m, ix.xnxb[0], 2u);
+	for (uint32_t i = 1; i < 6; i++) level(ix.xpos[i], ix.xrank[i], ix.xrun[i], ix.xnxb[i], i + 2u, 1u);
+	level(ix.oct_pos, ix.oct_rank, ix.oct_run, ix.oct_nx8, 8u, 8u);
+	level(ix.hex_pos, ix.hex_rank, ix.hex_run, ix.hex_nx8, 16u, 8u);
+	const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st); /* before the scratch goes */
+	HIPCHK(e1);
+	HIPCHK(e2);
+	return MGL_OK;
+}
+/* DevCtx's views of the index */
+static void fill_ctx_index(DevCtx& c, const MatchIndex& ix)
+{
+	c.bucket_off = ix.bucket_off; c.bucket_pos = ix.bucket_pos; c.bucket_nx = ix.bucket_nx; c.quad_pos = ix.quad_pos; c.quad_nx = ix.quad_nx;
+	for (int i = 0; i < 6; i++) { c.xpos[i] = ix.xpos[i]; c.xrank[i] = ix.xrank[i]; c.xrun[i] = ix.xrun[i]; c.xnxb[i] = ix.xnxb[i]; }
+	c.oct_pos = ix.oct_pos; c.oct_rank = ix.oct_rank; c.oct_run = ix.oct_run; c.oct_nx8 = ix.oct_nx8;
+	c.hex_pos = ix.hex_pos; c.hex_rank = ix.hex_rank; c.hex_run = ix.hex_run; c.hex_nx8 = ix.hex_nx8;
+}
 
-	sa->ctx.data = sa->d_data; sa->ctx.n = (uint32_t)n;
-	sa->ctx.bucket_off = sa->d_bucket_off; sa->ctx.bucket_pos = sa->d_bucket_pos; sa->ctx.bucket_nx = sa->d_bucket_nx; sa->ctx.quad_pos = sa->d_quad_pos; sa->ctx.quad_nx = sa->d_quad_nx;
-	for (int i = 0; i < 6; i++) { sa->ctx.xpos[i] = sa->d_xpos[i]; sa->ctx.xrank[i] = sa->d_xrank[i]; sa->ctx.xrun[i] = sa->d_xrun[i]; sa->ctx.xnxb[i] = sa->d_xnxb[i]; }
-	sa->ctx.oct_pos = sa->d_oct_pos; sa->ctx.oct_rank = sa->d_oct_rank; sa->ctx.oct_run = sa->d_oct_run; sa->ctx.oct_nx8 = sa->d_oct_nx8;
-	sa->ctx.hex_pos = sa->d_hex_pos; sa->ctx.hex_rank = sa->d_hex_rank; sa->ctx.hex_run = sa->d_hex_run; sa->ctx.hex_nx8 = sa->d_hex_nx8;
-	sa->ctx.cost_tbl = sa->d_cost_tbl; sa->ctx.L = L;
-	sa->ctx.dict_limit = sa->cfg.dict_limit; sa->ctx.max_scan = sa->cfg.max_bucket_scan; sa->ctx.top_k = sa->cfg.top_k;
-
-	HIPCHK(alloc_base(sa->base, (uint32_t)n, ckpt_elems));
-	HIPCHK(alloc_base(sa->scratch, (uint32_t)n, ckpt_elems));
-
+/* the two bases, the neighbours' outputs, the bulk selection's buffers and the staging areas of the API calls */
+static int alloc_search_buffers(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
+{
+	DevOwner& own = sa->own;
+	TRY(alloc_base(own, sa->base, (uint32_t)n, ckpt_elems));
+	TRY(alloc_base(own, sa->scratch, (uint32_t)n, ckpt_elems));
 	const size_t K = sa->cfg.neighbours_per_step;
-	HIPCHK(hipMalloc(&sa->nbr.cost, sizeof(uint64_t) * K));
-	HIPCHK(hipMalloc(&sa->nbr.ndiffs, sizeof(uint32_t) * K));
-	HIPCHK(hipMalloc(&sa->nbr.walked, sizeof(uint32_t) * K));
-	HIPCHK(hipMalloc(&sa->nbr.win, sizeof(uint32_t) * 2 * K));
-	HIPCHK(hipMemset(sa->nbr.win, 0xFF, sizeof(uint32_t) * 2 * K));
-	HIPCHK(hipMalloc(&sa->nbr.win2, sizeof(uint32_t) * K));
-	HIPCHK(hipMemset(sa->nbr.win2, 0xFF, sizeof(uint32_t) * K));
+	TRY(dnew(own, sa->nbr.cost, K));
+	TRY(dnew(own, sa->nbr.ndiffs, K));
+	TRY(dnew(own, sa->nbr.walked, K));
+	TRY(dnew(own, sa->nbr.win, 2 * K, 0xFF));
+	TRY(dnew(own, sa->nbr.win2, K, 0xFF));
 	memset(&sa->bulk, 0, sizeof sa->bulk);
-	HIPCHK(hipMalloc(&sa->bulk.ckey, sizeof(uint64_t) * K));
-	HIPCHK(hipMalloc(&sa->bulk.cwin, sizeof(uint4) * K));
-	HIPCHK(hipMalloc(&sa->bulk.taken, sizeof(uint32_t) * K));
-	HIPCHK(hipMalloc(&sa->bulk.cstate, 2u * (size_t)K));
-	HIPCHK(hipMalloc(&sa->bulk.cflags, sizeof(uint32_t) * (size_t)K));
-	HIPCHK(hipMemset(sa->bulk.cflags, 0, sizeof(uint32_t) * (size_t)K));
-	HIPCHK(hipMalloc(&sa->bulk.hdr, sizeof(unsigned long long) * 8));
-	{
-		const unsigned long long h0[8] = { 0, 0, 0, 0, 0, 0, ~0ull, 0 };
-		HIPCHK(hipMemcpy(sa->bulk.hdr, h0, sizeof h0, hipMemcpyHostToDevice));
-	}
-	HIPCHK(hipMalloc(&sa->nbr.dpos, sizeof(uint32_t) * K * MGL_MAX_DIFFS));
-	HIPCHK(hipMalloc(&sa->nbr.dold, sizeof(mgl_pk) * K * MGL_MAX_DIFFS));
-	HIPCHK(hipMalloc(&sa->nbr.dnew, sizeof(mgl_pk) * K * MGL_MAX_DIFFS));
-	HIPCHK(hipMalloc(&sa->d_aos, sizeof(mgl_packet) * n));
-	HIPCHK(hipMalloc(&sa->d_cum, sizeof(uint64_t) * n));
-	HIPCHK(hipMalloc(&sa->d_final_probs, sizeof(uint16_t) * ckpt_elems));
-	HIPCHK(hipMalloc(&sa->d_topk_pk, sizeof(mgl_pk) * 64));
-	HIPCHK(hipMalloc(&sa->d_topk_cost, sizeof(uint64_t) * 64));
-	HIPCHK(hipMalloc(&sa->d_small, sizeof(uint32_t) * 16));
+	TRY(dnew(own, sa->bulk.ckey, K));
+	TRY(dnew(own, sa->bulk.cwin, K));
+	TRY(dnew(own, sa->bulk.taken, K));
+	TRY(dnew(own, sa->bulk.cstate, 2 * K));
+	TRY(dnew(own, sa->bulk.cflags, K, 0));
+	TRY(dnew(own, sa->bulk.hdr, 8));
+	const unsigned long long h0[8] = { 0, 0, 0, 0, 0, 0, ~0ull, 0 };
+	HIPCHK(hipMemcpy(sa->bulk.hdr, h0, sizeof h0, hipMemcpyHostToDevice));
+	TRY(dnew(own, sa->nbr.dpos, K * MGL_MAX_DIFFS));
+	TRY(dnew(own, sa->nbr.dold, K * MGL_MAX_DIFFS));
+	TRY(dnew(own, sa->nbr.dnew, K * MGL_MAX_DIFFS));
+	TRY(dalloc(own, (void**)&sa->d_aos, sizeof(mgl_packet) * n));
+	TRY(dnew(own, sa->d_cum, n));
+	TRY(dnew(own, sa->d_final_probs, ckpt_elems));
+	TRY(dnew(own, sa->d_topk_pk, 64));
+	TRY(dnew(own, sa->d_topk_cost, 64));
+	TRY(dnew(own, sa->d_small, 16));
 	sa->sub_cap = 1u << 20;
-	HIPCHK(hipMalloc(&sa->d_sub_offs, sizeof(uint32_t) * sa->sub_cap));
-	HIPCHK(hipMalloc(&sa->d_sub_lens, sizeof(uint32_t) * sa->sub_cap));
+	TRY(dnew(own, sa->d_sub_offs, sa->sub_cap));
+	return dnew(own, sa->d_sub_lens, sa->sub_cap);
+}
 
-	/* LDS budget: 4 KiB cost table + per wave {probabilities, 2x272 length prices, journal} */
+/* the parallel builder's buffers (mgl_pbuild.hip), on the blocks of the chain index */
+static int alloc_pbuild(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
+{
+	DevOwner& own = sa->own;
+	PBuild& pb = sa->pb;
+	memset(&pb, 0, sizeof pb);
+	pb.shift = sa->b2.sb_shift; /* 256 / 512 / 1 024 positions per block up to 1 MiB / 8 MiB / above */
+	pb.nblk = (uint32_t)((n + (1u << pb.shift) - 1) >> pb.shift);
+	pb.ngrp = (pb.nblk + MGL_PB_GROUP - 1u) / MGL_PB_GROUP;
+	const size_t nblk = pb.nblk, nch = (nblk + MGL_PB_SCAN_CHUNK - 1u) / MGL_PB_SCAN_CHUNK;
+	TRY(dnew(own, pb.exits, nblk * MGL_PB_ENTRIES));
+	TRY(dnew(own, pb.entry, nblk + 1));
+	TRY(dnew(own, pb.gexits, (size_t)pb.ngrp * MGL_PB_ENTRIES));
+	TRY(dnew(own, pb.gentry, pb.ngrp));
+	TRY(dnew(own, pb.ch_map, nch));
+	TRY(dnew(own, pb.ch_vs, 8 * nch));
+	TRY(dnew(own, pb.ch_pk, nch));
+	TRY(dnew(own, pb.ch_state, 8 * nch));
+	TRY(dnew(own, pb.gsum, (size_t)((pb.nblk + MGL_PB_OFF_ROWS - 1u) / MGL_PB_OFF_ROWS) * ckpt_elems));
+	TRY(dnew(own, pb.tf_ctx, nblk));
+	TRY(dnew(own, pb.tf_dist, 8 * nblk));
+	TRY(dnew(own, pb.tf_pk, nblk));
+	TRY(dnew(own, pb.st_in, 8 * nblk));
+	TRY(dnew(own, pb.hist, nblk * ckpt_elems));
+	TRY(dnew(own, pb.stage, nblk * ((MGL_PB_STAGE_PER_POS << pb.shift) + 32u)));
+	TRY(dnew(own, pb.stage_n, nblk));
+	TRY(dnew(own, pb.stage_over, 1, 0));
+	TRY(dnew(own, pb.acc, 16, 0));
+	pb.seg_cap = sa->b2.pool_cap / MGL_PB_SEG + ckpt_elems + 64u;
+	TRY(dnew(own, pb.seg_off, ckpt_elems + 1));
+	return dnew(own, pb.unres, pb.seg_cap);
+}
+/* incremental engine: the geometry of its base (bitmaps, special-state records, dense checkpoints, event chains, chain index),
+ * the base, the parallel builder, the snapshots of the all-literal and the best slab */
+static int create_engine(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
+{
+	DevOwner& own = sa->own;
+	const size_t K = sa->cfg.neighbours_per_step;
+	Base2& b = sa->b2;
+	memset(&b, 0, sizeof b);
+	b.slab = sa->base.v.slab;
+	b.onwalk = sa->base.v.onwalk;
+	b.nw0 = (uint32_t)((n + 63) / 64);
+	b.nw1 = (b.nw0 + 63) / 64;
+	b.nw2 = (b.nw1 + 63) / 64;
+	b.nck = (uint32_t)((n + (1u << MGL_CK2_SHIFT) - 1) >> MGL_CK2_SHIFT);
+	b.ck_elems = ckpt_elems;
+	b.pool_cap = (uint32_t)(24 * n + (size_t)sa->ctx.L.total * 272 + 4096);
+	/* chain index: one entry per context and block of the parallel builder (the builder's per-block counts are its source) */
+	b.sb_shift = n <= (1u << 20) ? 8u : n <= (1u << 23) ? 9u : MGL_PB_MAX_SHIFT;
+	/* MGL_SB_SHIFT (tests): 512- and 1 024-position blocks on small inputs.  Nothing outside 8..10 is taken: the builder's
+	 * LDS arrays hold MGL_PB_MAX_BLOCK positions, and a block is whole bitmap words (shift - 6) */
+	if (getenv("MGL_SB_SHIFT")) {
+		const int s = atoi(getenv("MGL_SB_SHIFT"));
+		if (s >= 8 && s <= (int)MGL_PB_MAX_SHIFT) b.sb_shift = (uint32_t)s;
+	}
+	b.nsb = (uint32_t)((n + (1u << b.sb_shift) - 1) >> b.sb_shift);
+	b.sb_stride = (b.nsb + 2u + 3u) & ~3u;
+	TRY(alloc_b2(own, b, n, false, true, &sa->b2_bytes));
+	sa->parallel_build = !(sa->cfg.flags & MGL_F_SERIAL_BUILD);
+	if (sa->parallel_build) TRY(alloc_pbuild(sa, n, ckpt_elems));
+	sa->snapshots = !(sa->cfg.flags & MGL_F_NO_SNAPSHOTS);
+	if (sa->snapshots) {
+		for (Base2* s : { &sa->snap_lit, &sa->snap_best }) {
+			*s = b; /* the geometry; every array becomes the snapshot's own */
+			TRY(alloc_b2(own, *s, n, true, false, nullptr));
+		}
+		TRY(dnew(own, sa->d_snap_meta, 2, 0));
+		sa->d_best = sa->snap_best.slab; /* packets_best lives in the best snapshot */
+	}
+	if (sa->cfg.flags & MGL_F_PROFILE) TRY(dnew(own, sa->d_prof, 64 + 2 * K, 0));
+	return dnew(own, sa->d_todo, K + 1, 0);
+}
+
+/* the in-place accepts' buffers: single (ApplyBuf, mgl_kernels3.hip) and batch (BatchBuf, mgl_kernels5.hip), and their limits */
+static int alloc_accept_buffers(mgl_sa* sa)
+{
+	DevOwner& own = sa->own;
+	sa->incremental_apply = getenv("MGL_NO_INCREMENTAL_APPLY") == nullptr;
+	ApplyBuf& ab = sa->ab;
+	memset(&ab, 0, sizeof ab);
+	/* one workgroup per touched context plans the rewrite; the copies run as job lists */
+	sa->apply_blocks = 256;
+	ab.scratch_cap = sa->b2.pool_cap + 256u;
+	ab.span_cap = 1u << 22;
+	ab.job_cap = 1u << 20;
+	TRY(dnew(own, ab.hdr, 16, 0));
+	TRY(dnew(own, ab.ins_key, MGL_BATCH_ALLOC)); /* a single accept uses MGL_APPLY_CAP of each of these four */
+	TRY(dnew(own, ab.rem_key, MGL_BATCH_ALLOC));
+	TRY(dnew(own, ab.ins_pos, MGL_BATCH_ALLOC));
+	TRY(dnew(own, ab.rem_pos, MGL_BATCH_ALLOC));
+	TRY(dnew(own, ab.tctx, 16384));
+	TRY(dnew(own, ab.scratch_pos, ab.scratch_cap));
+	TRY(dnew(own, ab.scratch_ev, ab.scratch_cap));
+	TRY(dnew(own, ab.span_pos, ab.span_cap));
+	TRY(dnew(own, ab.span_ev, ab.span_cap));
+	TRY(dnew(own, ab.jobs_b, ab.job_cap));
+	TRY(dnew(own, ab.jobs_c, ab.job_cap));
+	BatchBuf& bt = sa->batch;
+	memset(&bt, 0, sizeof bt);
+	TRY(dnew(own, bt.hdr, 16, 0));
+	TRY(dnew(own, bt.cl, 8 * MGL_BATCH_MAX));
+	TRY(dnew(own, bt.jpos, MGL_BATCH_MAX * MGL_MAX_DIFFS));
+	TRY(dnew(own, bt.jnew, MGL_BATCH_MAX * MGL_MAX_DIFFS));
+	TRY(dnew(own, bt.jold, MGL_BATCH_MAX * MGL_MAX_DIFFS));
+	TRY(dnew(own, bt.st_ikey, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.st_rkey, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.st_ipos, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.st_rpos, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.ops, 2 * (size_t)MGL_BATCH_MAX * MGL_BATCH_OPCAP));
+	TRY(dnew(own, bt.ins_cl, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.rem_cl, MGL_BATCH_ALLOC));
+	bt.nctx = sa->ctx.L.total;
+	bt.runs_cap = 1u << 17;
+	TRY(dnew(own, bt.runs, 2 * (size_t)bt.runs_cap));
+	for (uint32_t** p : { &bt.cnt_i, &bt.cnt_r, &bt.off_i, &bt.off_r, &bt.cur_i, &bt.cur_r, &bt.touched }) TRY(dnew(own, *p, bt.nctx + 64u, 0));
+	TRY(dnew(own, bt.bk_ipos, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.bk_rpos, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.bk_ibit, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.bk_icl, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.bk_rcl, MGL_BATCH_ALLOC));
+	TRY(dnew(own, bt.acc, 4, 0));
+	HIPCHK(own.pinned((void**)&sa->h_bstat, sizeof(uint32_t) * 16));
+	HIPCHK(own.event(&sa->ev_bstat, hipEventDisableTiming));
+	sa->batch_ok = sa->incremental_apply && getenv("MGL_NO_BATCH") == nullptr;
+	uint32_t* why = nullptr;
+	TRY(dnew(own, why, 1, 0));
+	accept_limits_init(sa, why);
+	return MGL_OK;
+}
+
+/* what the neighbour evaluation keeps in global memory: the second pass's list areas, the hand-over between the halves of the
+ * split form, the re-simulation's lists and headers, the continuation records, the per-step counters */
+static int alloc_nbr_scratch(mgl_sa* sa, uint32_t ckpt_elems)
+{
+	DevOwner& own = sa->own;
+	const size_t K = sa->cfg.neighbours_per_step;
+	/* first-pass list size: a step of few neighbours leaves most of the LDS idle, and on repetitive inputs
+	 * (long matches everywhere) windows are long: give the lists the room */
+	sa->chg_cap = K <= 1024u ? 4u * MGL_CHG_CAP : (K <= 2048u ? 2u * MGL_CHG_CAP : MGL_CHG_CAP);
+	BigScratch& g = sa->big;
+	memset(&g, 0, sizeof g);
+	g.chg_cap = sa->chg_cap;
+	g.cap = MGL_BIG_CAP; g.uctx_cap = ckpt_elems; g.slots = (uint32_t)(K > 512 ? K : 512); /* every neighbour of a step may need one */
+	const size_t slots = g.slots;
+	TRY(dnew(own, g.ins_key, g.cap * slots));
+	TRY(dnew(own, g.rem_key, g.cap * slots));
+	TRY(dnew(own, g.ins_pos, g.cap * slots));
+	TRY(dnew(own, g.rem_pos, g.cap * slots));
+	TRY(dnew(own, g.uctx, g.uctx_cap * slots));
+	TRY(dnew(own, sa->d_todo2, K + 1, 0));
+	TRY(dnew(own, sa->d_counts, 16, 0)); /* [0..7] live, [8..15] the last finished step's */
+	g.todo_in = sa->d_todo; g.todo_in_count = sa->d_counts; g.spill_ctr = sa->d_counts + 2;
+	g.evcancel = getenv("MGL_NO_EVCANCEL") == nullptr ? 1u : 0u; /* the window walk lists a re-coded packet's changed events only; MGL_NO_EVCANCEL=1: all of them */
+	TRY(dnew(own, sa->d_pickrec, K));
+	TRY(dnew(own, sa->d_pickstate, 2 * K));
+	sa->split_nbr = getenv("MGL_NO_SPLIT") == nullptr;
+	if (sa->split_nbr) {
+		/* the second half's re-simulation as its own launch (k_sim): lists and headers per neighbour */
+		TRY(dnew(own, g.sim_hdr, K, 0xFF));
+		TRY(dnew(own, g.sim_keys, 2u * sa->chg_cap * K));
+		TRY(dnew(own, g.sim_pos, 2u * sa->chg_cap * K));
+		/* continuation records: the second half saves a walk that stops at a repair pick, the second pass resumes it */
+		if (getenv("MGL_NO_CONT") == nullptr) TRY(dnew(own, g.cont, MGL_CONT_WORDS * slots, 0));
+	}
+	return dnew(own, sa->d_traffic, 2, 0);
+}
+
+/* every dynamic LDS size, the wavefronts per workgroup of every neighbour launch, the kernels' LDS attributes, and the switches
+ * of the launch path.  LDS budget of the full-walk kernels: 4 KiB cost table + per wave {probabilities, 2x272 length prices,
+ * journal} */
+static int set_launch_geometry(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
+{
+	const uint32_t cu_lds = 160u * 1024u, pick_tbl = MGL_PICK_T_GLOBAL ? 0u : 4096u;
 	sa->per_wave_bytes = ckpt_elems * 2u + MGL_PRICE_WORDS * 4u + MGL_MAX_DIFFS * (8u + 8u + 4u);
 	sa->waves_per_block = 4;
-	while (sa->waves_per_block > 1 && 4096u + sa->waves_per_block * sa->per_wave_bytes > 160u * 1024u) sa->waves_per_block--;
+	while (sa->waves_per_block > 1 && 4096u + sa->waves_per_block * sa->per_wave_bytes > cu_lds) sa->waves_per_block--;
 	sa->nbr_lds = 4096u + sa->waves_per_block * sa->per_wave_bytes;
 	sa->walk_lds = 4096u + ckpt_elems * 2u + MGL_PRICE_WORDS * 4u;
 	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr_lds));
 	HIPCHK(hipFuncSetAttribute((const void*)k_rebuild, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->walk_lds));
 	HIPCHK(hipFuncSetAttribute((const void*)k_topk_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->walk_lds));
+	if (!sa->incremental) return MGL_OK;
 
-	/* incremental path: bitmaps, special-state records, dense checkpoints, event chains */
-	sa->incremental = !(sa->cfg.flags & MGL_F_FULLWALK);
-	if (sa->incremental) {
-		Base2& b = sa->b2;
-		memset(&b, 0, sizeof b);
-		b.slab = sa->base.v.slab;
-		b.onwalk = sa->base.v.onwalk;
-		b.nw0 = (uint32_t)(((size_t)n + 63) / 64);
-		b.nw1 = (b.nw0 + 63) / 64;
-		b.nw2 = (b.nw1 + 63) / 64;
-		b.nck = (uint32_t)(((size_t)n + (1u << MGL_CK2_SHIFT) - 1) >> MGL_CK2_SHIFT);
-		b.ck_elems = ckpt_elems;
-		b.pool_cap = (uint32_t)(24 * n + (size_t)L.total * 272 + 4096);
-		/* chain index: one entry per context and block of the parallel builder (the builder's per-block counts are its source) */
-		b.sb_shift = n <= (1u << 20) ? 8u : n <= (1u << 23) ? 9u : MGL_PB_MAX_SHIFT;
-		/* MGL_SB_SHIFT (tests): 512- and 1 024-position blocks on small inputs.  Nothing outside 8..10 is taken: the builder's
-		 * LDS arrays hold MGL_PB_MAX_BLOCK positions, and a block is whole bitmap words (shift - 6) */
-		if (getenv("MGL_SB_SHIFT")) {
-			const int s = atoi(getenv("MGL_SB_SHIFT"));
-			if (s >= 8 && s <= (int)MGL_PB_MAX_SHIFT) b.sb_shift = (uint32_t)s;
-		}
-		b.nsb = (uint32_t)((n + (1u << b.sb_shift) - 1) >> b.sb_shift);
-		b.sb_stride = (b.nsb + 2u + 3u) & ~3u;
-		size_t bytes = 0;
-		{
-			int rc = alloc_b2(b, n, false, true, &bytes);
-			if (rc) return rc;
-		}
-		sa->parallel_build = !(sa->cfg.flags & MGL_F_SERIAL_BUILD);
-		if (sa->parallel_build) {
-			PBuild& pb = sa->pb;
-			memset(&pb, 0, sizeof pb);
-			pb.shift = b.sb_shift; /* 256 / 512 / 1 024 positions per block up to 1 MiB / 8 MiB / above */
-			pb.nblk = (uint32_t)((n + (1u << pb.shift) - 1) >> pb.shift);
-			HIPCHK(hipMalloc(&pb.exits, sizeof(uint16_t) * (size_t)pb.nblk * MGL_PB_ENTRIES));
-			HIPCHK(hipMalloc(&pb.entry, sizeof(uint32_t) * ((size_t)pb.nblk + 1)));
-			pb.ngrp = (pb.nblk + MGL_PB_GROUP - 1u) / MGL_PB_GROUP;
-			HIPCHK(hipMalloc(&pb.gexits, sizeof(uint16_t) * (size_t)pb.ngrp * MGL_PB_ENTRIES));
-			HIPCHK(hipMalloc(&pb.gentry, sizeof(uint16_t) * (size_t)pb.ngrp));
-			{
-				const size_t nch = ((size_t)pb.nblk + MGL_PB_SCAN_CHUNK - 1u) / MGL_PB_SCAN_CHUNK;
-				HIPCHK(hipMalloc(&pb.ch_map, sizeof(uint64_t) * nch));
-				HIPCHK(hipMalloc(&pb.ch_vs, sizeof(uint32_t) * 8 * nch));
-				HIPCHK(hipMalloc(&pb.ch_pk, sizeof(uint32_t) * nch));
-				HIPCHK(hipMalloc(&pb.ch_state, sizeof(uint32_t) * 8 * nch));
-			}
-			HIPCHK(hipMalloc(&pb.gsum, sizeof(uint32_t) * (size_t)((pb.nblk + MGL_PB_OFF_ROWS - 1u) / MGL_PB_OFF_ROWS) * ckpt_elems));
-			HIPCHK(hipMalloc(&pb.tf_ctx, sizeof(uint64_t) * pb.nblk));
-			HIPCHK(hipMalloc(&pb.tf_dist, sizeof(uint32_t) * 8 * (size_t)pb.nblk));
-			HIPCHK(hipMalloc(&pb.tf_pk, sizeof(uint32_t) * pb.nblk));
-			HIPCHK(hipMalloc(&pb.st_in, sizeof(uint32_t) * 8 * (size_t)pb.nblk));
-			HIPCHK(hipMalloc(&pb.hist, sizeof(uint32_t) * (size_t)pb.nblk * ckpt_elems));
-			HIPCHK(hipMalloc(&pb.stage, sizeof(uint64_t) * (size_t)pb.nblk * ((MGL_PB_STAGE_PER_POS << pb.shift) + 32u)));
-			HIPCHK(hipMalloc(&pb.stage_n, sizeof(uint32_t) * (size_t)pb.nblk));
-			HIPCHK(hipMalloc(&pb.stage_over, sizeof(uint32_t)));
-			HIPCHK(hipMemset(pb.stage_over, 0, sizeof(uint32_t)));
-			HIPCHK(hipMalloc(&pb.acc, sizeof(unsigned long long) * 16));
-			HIPCHK(hipMemset(pb.acc, 0, sizeof(unsigned long long) * 16));
-			pb.seg_cap = b.pool_cap / MGL_PB_SEG + ckpt_elems + 64u;
-			HIPCHK(hipMalloc(&pb.seg_off, sizeof(uint32_t) * (ckpt_elems + 1)));
-			HIPCHK(hipMalloc(&pb.unres, pb.seg_cap));
-		}
-		sa->snapshots = !(sa->cfg.flags & MGL_F_NO_SNAPSHOTS);
-		if (sa->snapshots) {
-			for (Base2* s : { &sa->snap_lit, &sa->snap_best }) {
-				*s = b;
-				s->slab = nullptr; s->onwalk = nullptr; s->sp0 = s->sp1 = s->sp2 = nullptr; s->sp_state = nullptr;
-				s->ck_probs = nullptr; s->ch_off = s->ch_len = s->ch_cap = s->ch_pos = nullptr; s->ch_ev = nullptr;
-				s->pool_top = nullptr;
-				int rc = alloc_b2(*s, n, true, false, nullptr);
-				if (rc) return rc;
-			}
-			HIPCHK(hipMalloc(&sa->d_snap_meta, sizeof(SnapMeta) * 2));
-			HIPCHK(hipMemset(sa->d_snap_meta, 0, sizeof(SnapMeta) * 2));
-			sa->d_best = sa->snap_best.slab; /* packets_best lives in the best snapshot */
-		}
-		if (sa->cfg.flags & MGL_F_PROFILE) {
-			HIPCHK(hipMalloc(&sa->d_prof, sizeof(unsigned long long) * (64 + 2 * (size_t)K)));
-			HIPCHK(hipMemset(sa->d_prof, 0, sizeof(unsigned long long) * (64 + 2 * (size_t)K)));
-		}
-		HIPCHK(hipMalloc(&sa->d_todo, sizeof(uint32_t) * (K + 1)));
-		HIPCHK(hipMemset(sa->d_todo, 0, sizeof(uint32_t) * (K + 1)));
-		sa->b2_bytes = bytes;
-		sa->incremental_apply = getenv("MGL_NO_INCREMENTAL_APPLY") == nullptr;
-		{
-			ApplyBuf& ab = sa->ab;
-			memset(&ab, 0, sizeof ab);
-			/* one workgroup per touched context plans the rewrite; the copies run as job lists */
-			sa->apply_blocks = 256;
-			ab.scratch_cap = b.pool_cap + 256u;
-			ab.span_cap = 1u << 22;
-			ab.job_cap = 1u << 20;
-			HIPCHK(hipMalloc(&ab.hdr, sizeof(uint32_t) * 16));
-			HIPCHK(hipMemset(ab.hdr, 0, sizeof(uint32_t) * 16));
-			HIPCHK(hipMalloc(&ab.ins_key, sizeof(uint16_t) * MGL_BATCH_ALLOC)); /* a single accept uses MGL_APPLY_CAP of it */
-			HIPCHK(hipMalloc(&ab.rem_key, sizeof(uint16_t) * MGL_BATCH_ALLOC)); /* a single accept uses MGL_APPLY_CAP of it */
-			HIPCHK(hipMalloc(&ab.ins_pos, sizeof(uint32_t) * MGL_BATCH_ALLOC)); /* a single accept uses MGL_APPLY_CAP of it */
-			HIPCHK(hipMalloc(&ab.rem_pos, sizeof(uint32_t) * MGL_BATCH_ALLOC)); /* a single accept uses MGL_APPLY_CAP of it */
-			HIPCHK(hipMalloc(&ab.tctx, sizeof(uint16_t) * 16384));
-			HIPCHK(hipMalloc(&ab.scratch_pos, sizeof(uint32_t) * (size_t)ab.scratch_cap));
-			HIPCHK(hipMalloc(&ab.scratch_ev, sizeof(uint16_t) * (size_t)ab.scratch_cap));
-			HIPCHK(hipMalloc(&ab.span_pos, sizeof(uint32_t) * (size_t)ab.span_cap));
-			HIPCHK(hipMalloc(&ab.span_ev, sizeof(uint16_t) * (size_t)ab.span_cap));
-			HIPCHK(hipMalloc(&ab.jobs_b, sizeof(uint4) * (size_t)ab.job_cap));
-			HIPCHK(hipMalloc(&ab.jobs_c, sizeof(uint4) * (size_t)ab.job_cap));
-			BatchBuf& bt = sa->batch;
-			memset(&bt, 0, sizeof bt);
-			HIPCHK(hipMalloc(&bt.hdr, sizeof(uint32_t) * 16));
-			HIPCHK(hipMemset(bt.hdr, 0, sizeof(uint32_t) * 16));
-			HIPCHK(hipMalloc(&bt.cl, sizeof(uint32_t) * 8 * MGL_BATCH_MAX));
-			HIPCHK(hipMalloc(&bt.jpos, sizeof(uint32_t) * MGL_BATCH_MAX * MGL_MAX_DIFFS));
-			HIPCHK(hipMalloc(&bt.jnew, sizeof(mgl_pk) * MGL_BATCH_MAX * MGL_MAX_DIFFS));
-			HIPCHK(hipMalloc(&bt.jold, sizeof(mgl_pk) * MGL_BATCH_MAX * MGL_MAX_DIFFS));
-			HIPCHK(hipMalloc(&bt.st_ikey, sizeof(uint16_t) * MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.st_rkey, sizeof(uint16_t) * MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.st_ipos, sizeof(uint32_t) * MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.st_rpos, sizeof(uint32_t) * MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.ops, sizeof(uint4) * 2 * (size_t)MGL_BATCH_MAX * MGL_BATCH_OPCAP));
-			HIPCHK(hipMalloc(&bt.ins_cl, MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.rem_cl, MGL_BATCH_ALLOC));
-			bt.nctx = L.total;
-			bt.runs_cap = 1u << 17;
-			HIPCHK(hipMalloc(&bt.runs, sizeof(uint4) * 2 * (size_t)bt.runs_cap));
-			for (uint32_t** p : { &bt.cnt_i, &bt.cnt_r, &bt.off_i, &bt.off_r, &bt.cur_i, &bt.cur_r, &bt.touched }) {
-				HIPCHK(hipMalloc(p, sizeof(uint32_t) * (bt.nctx + 64u)));
-				HIPCHK(hipMemset(*p, 0, sizeof(uint32_t) * (bt.nctx + 64u)));
-			}
-			HIPCHK(hipMalloc(&bt.bk_ipos, sizeof(uint32_t) * MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.bk_rpos, sizeof(uint32_t) * MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.bk_ibit, sizeof(uint16_t) * MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.bk_icl, MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.bk_rcl, MGL_BATCH_ALLOC));
-			HIPCHK(hipMalloc(&bt.acc, sizeof(long long) * 4));
-			HIPCHK(hipMemset(bt.acc, 0, sizeof(long long) * 4));
-			HIPCHK(hipHostMalloc((void**)&sa->h_bstat, sizeof(uint32_t) * 16, hipHostMallocDefault));
-			HIPCHK(hipEventCreateWithFlags(&sa->ev_bstat, hipEventDisableTiming));
-			sa->batch_ok = sa->incremental_apply && getenv("MGL_NO_BATCH") == nullptr;
-			uint32_t* why = nullptr;
-			HIPCHK(hipMalloc(&why, sizeof(uint32_t)));
-			HIPCHK(hipMemset(why, 0, sizeof(uint32_t)));
-			accept_limits_init(sa, why);
+	/* journal + context bitmap + max(model + price tables, change lists + context list) */
+	const uint32_t fixed = MGL_MAX_DIFFS * (8u + 8u + 4u) + (((((sa->ctx.L.total + 31u) >> 5) + 3u) & ~3u) * 4u);
+	const uint32_t model = ckpt_elems * 2u + MGL_PRICE_WORDS * 4u;
+	const uint32_t lists = sa->chg_cap * (4u + 4u + 2u + 2u) + 2u * sa->chg_cap * 2u;
+	sa->per_wave2 = (fixed + (model > lists ? model : lists) + 15u) & ~15u;
+	sa->per_wave_pick = (model + 15u) & ~15u; /* no journal / bitmap in the pick half */
+	sa->per_wave_rest = (fixed + lists + 15u) & ~15u;
+	/* measured: one wavefront per workgroup wins although more would pack more waves into a CU's 160 KiB of LDS (LDS is
+	 * released per workgroup, and neighbour run times have a long tail) */
+	sa->waves_per_block2 = 1;
+	sa->nbr2_lds = 4096u + sa->waves_per_block2 * sa->per_wave2;
+	sa->build_lds = 4096u + ckpt_elems * 2u + ckpt_elems * 8u;
+	sa->fused_lds = pick_tbl + (sa->per_wave_pick > sa->per_wave_rest ? sa->per_wave_pick : sa->per_wave_rest);
+	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cu_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cu_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_REST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES)));
+	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICKWALK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->fused_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_sim<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+	HIPCHK(hipFuncSetAttribute((const void*)k_sim<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+	HIPCHK(hipFuncSetAttribute((const void*)k_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->build_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_build_end, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->build_lds));
 
-		}
-		{
-			/* journal + context bitmap + max(model + price tables, change lists + context list) */
-			const uint32_t fixed = MGL_MAX_DIFFS * (8u + 8u + 4u) + (((((L.total + 31u) >> 5) + 3u) & ~3u) * 4u) ;
-			const uint32_t model = ckpt_elems * 2u + MGL_PRICE_WORDS * 4u;
-			/* first-pass list size: a step of few neighbours leaves most of the LDS idle, and on repetitive inputs
-			 * (long matches everywhere) windows are long: give the lists the room */
-			sa->chg_cap = K <= 1024u ? 4u * MGL_CHG_CAP : (K <= 2048u ? 2u * MGL_CHG_CAP : MGL_CHG_CAP);
-			const uint32_t lists = sa->chg_cap * (4u + 4u + 2u + 2u) + 2u * sa->chg_cap * 2u;
-			sa->per_wave2 = (fixed + (model > lists ? model : lists) + 15u) & ~15u;
-			sa->per_wave_pick = (model + 15u) & ~15u; /* no journal / bitmap in the pick half */
-			sa->per_wave_rest = (fixed + lists + 15u) & ~15u;
-		}
-		{
-			BigScratch& g = sa->big;
-			memset(&g, 0, sizeof g);
-			g.chg_cap = sa->chg_cap;
-			g.cap = MGL_BIG_CAP; g.uctx_cap = ckpt_elems; g.slots = (uint32_t)(K > 512 ? K : 512); /* every neighbour of a step may need one */
-			HIPCHK(hipMalloc(&g.ins_key, sizeof(uint16_t) * (size_t)g.cap * g.slots));
-			HIPCHK(hipMalloc(&g.rem_key, sizeof(uint16_t) * (size_t)g.cap * g.slots));
-			HIPCHK(hipMalloc(&g.ins_pos, sizeof(uint32_t) * (size_t)g.cap * g.slots));
-			HIPCHK(hipMalloc(&g.rem_pos, sizeof(uint32_t) * (size_t)g.cap * g.slots));
-			HIPCHK(hipMalloc(&g.uctx, sizeof(uint16_t) * (size_t)g.uctx_cap * g.slots));
-			HIPCHK(hipMalloc(&sa->d_todo2, sizeof(uint32_t) * (K + 1)));
-			HIPCHK(hipMemset(sa->d_todo2, 0, sizeof(uint32_t) * (K + 1)));
-		}
-		/* waves per workgroup that packs the most waves into a CU's 160 KiB of LDS */
-		{
-			uint32_t best_w = 1, best_total = 0;
-			for (uint32_t w = 1; w <= 8; w++) {
-				const uint32_t bytes = 4096u + w * sa->per_wave2;
-				if (bytes > 160u * 1024u) break;
-				const uint32_t tot = (160u * 1024u / bytes) * w;
-				if (tot > best_total) { best_total = tot; best_w = w; }
-			}
-			(void)best_w; /* measured: one wavefront per workgroup wins although it packs fewer waves (LDS is
-			               * released per workgroup, and neighbour run times have a long tail) */
-			sa->waves_per_block2 = 1;
-		}
-		sa->nbr2_lds = 4096u + sa->waves_per_block2 * sa->per_wave2;
-		sa->build_lds = 4096u + ckpt_elems * 2u + ckpt_elems * 8u;
-		HIPCHK(hipMalloc(&sa->d_counts, sizeof(uint32_t) * 16)); /* [0..7] live, [8..15] the last finished step's */
-		HIPCHK(hipMemset(sa->d_counts, 0, sizeof(uint32_t) * 16));
-		sa->big.todo_in = sa->d_todo; sa->big.todo_in_count = sa->d_counts; sa->big.spill_ctr = sa->d_counts + 2;
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_REST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<true, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES)));
-		sa->fuse = getenv("MGL_NO_FUSE") == nullptr;
-		sa->big.evcancel = getenv("MGL_NO_EVCANCEL") == nullptr ? 1u : 0u; /* the window walk lists a re-coded packet's changed events only; MGL_NO_EVCANCEL=1: all of them */
-		sa->fused_lds = (MGL_PICK_T_GLOBAL ? 0u : 4096u) + (sa->per_wave_pick > sa->per_wave_rest ? sa->per_wave_pick : sa->per_wave_rest);
-		HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICKWALK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->fused_lds));
-		HIPCHK(hipMalloc(&sa->d_pickrec, sizeof(uint4) * K));
-		HIPCHK(hipMalloc(&sa->d_pickstate, sizeof(uint4) * 2 * K));
-		sa->split_nbr = getenv("MGL_NO_SPLIT") == nullptr;
-		if (sa->split_nbr) {
-			/* the second half's re-simulation as its own launch (k_sim): lists and headers per neighbour */
-			BigScratch& g = sa->big;
-			HIPCHK(hipMalloc(&g.sim_hdr, sizeof(uint4) * (size_t)K));
-			HIPCHK(hipMalloc(&g.sim_keys, sizeof(uint16_t) * 2u * sa->chg_cap * (size_t)K));
-			HIPCHK(hipMalloc(&g.sim_pos, sizeof(uint32_t) * 2u * sa->chg_cap * (size_t)K));
-			HIPCHK(hipMemset(g.sim_hdr, 0xFF, sizeof(uint4) * (size_t)K));
-			/* continuation records: the second half saves a walk that stops at a repair pick, the second pass resumes it */
-			if (getenv("MGL_NO_CONT") == nullptr) {
-				HIPCHK(hipMalloc(&g.cont, sizeof(uint32_t) * MGL_CONT_WORDS * (size_t)g.slots));
-				HIPCHK(hipMemset(g.cont, 0, sizeof(uint32_t) * MGL_CONT_WORDS * (size_t)g.slots));
-			}
-		}
-		if (getenv("MGL_SIMW")) { const int w = atoi(getenv("MGL_SIMW")); if (w == 1 || w == 2 || w == 4 || w == 8) sa->sim_waves = (uint32_t)w; }
-		sa->adaptive = sa->split_nbr && getenv("MGL_NO_ADAPT") == nullptr;
-		sa->form_single = !sa->split_nbr; /* one-kernel form only, or the split form until the device recommends otherwise */
-		/* eight pick wavefronts share a cost table per workgroup: 4 KiB + 8 x 9.3 KiB = 78 KiB, two
-		 * workgroups = 16 wavefronts per CU, so the 4 096 neighbours of a c2 step are all resident at
-		 * once (with two per workgroup 14 fit and the last 512 waited for a slot: 127 -> 108 us).
-		 * Above 1 MiB top-K run times vary too much for wavefronts to hold each other's LDS: one per
-		 * workgroup there (c3, first 200 steps: 3.04 ms per step against 3.26 with eight) */
-		sa->pick_waves = getenv("MGL_PICK_WAVES") ? (uint32_t)atoi(getenv("MGL_PICK_WAVES")) : 0u;
-		if (sa->pick_waves != 1 && sa->pick_waves != 2 && sa->pick_waves != 4 && sa->pick_waves != 8) sa->pick_waves = 0;
-		{
-			/* the workgroup size that puts most wavefronts on a CU's 160 KiB (larger models -- lc > 0 -- fit fewer) */
-			uint32_t best_w = 1, best_resident = 0;
-			for (uint32_t w = 1; w <= 8; w *= 2) {
-				const uint32_t bytes = (MGL_PICK_T_GLOBAL ? 0u : 4096u) + w * sa->per_wave_pick;
-				if (bytes > 160u * 1024u) break;
-				const uint32_t resident = (160u * 1024u / ((bytes + 1279u) / 1280u * 1280u)) * w;
-				if (resident > best_resident) { best_resident = resident; best_w = w; }
-			}
-			if (n > (1u << 20)) best_w = 1;
-			if (sa->pick_waves == 0 || (MGL_PICK_T_GLOBAL ? 0u : 4096u) + sa->pick_waves * sa->per_wave_pick > 160u * 1024u) sa->pick_waves = best_w;
-		}
-		HIPCHK(hipFuncSetAttribute((const void*)k_sim<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-		HIPCHK(hipFuncSetAttribute((const void*)k_sim<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-		HIPCHK(hipMalloc(&sa->d_traffic, sizeof(unsigned long long) * 2));
-		HIPCHK(hipMemset(sa->d_traffic, 0, sizeof(unsigned long long) * 2));
-		HIPCHK(hipFuncSetAttribute((const void*)k_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->build_lds));
-		HIPCHK(hipFuncSetAttribute((const void*)k_build_end, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->build_lds));
+	sa->fuse = getenv("MGL_NO_FUSE") == nullptr;
+	if (getenv("MGL_SIMW")) { const int w = atoi(getenv("MGL_SIMW")); if (w == 1 || w == 2 || w == 4 || w == 8) sa->sim_waves = (uint32_t)w; }
+	sa->adaptive = sa->split_nbr && getenv("MGL_NO_ADAPT") == nullptr;
+	sa->form_single = !sa->split_nbr; /* one-kernel form only, or the split form until the device recommends otherwise */
+	/* eight pick wavefronts share a cost table per workgroup: 4 KiB + 8 x 9.3 KiB = 78 KiB, two
+	 * workgroups = 16 wavefronts per CU, so the 4 096 neighbours of a c2 step are all resident at
+	 * once (with two per workgroup 14 fit and the last 512 waited for a slot: 127 -> 108 us).
+	 * Above 1 MiB top-K run times vary too much for wavefronts to hold each other's LDS: one per
+	 * workgroup there (c3, first 200 steps: 3.04 ms per step against 3.26 with eight) */
+	sa->pick_waves = getenv("MGL_PICK_WAVES") ? (uint32_t)atoi(getenv("MGL_PICK_WAVES")) : 0u;
+	if (sa->pick_waves != 1 && sa->pick_waves != 2 && sa->pick_waves != 4 && sa->pick_waves != 8) sa->pick_waves = 0;
+	/* the workgroup size that puts most wavefronts on a CU's 160 KiB (larger models -- lc > 0 -- fit fewer) */
+	uint32_t best_w = 1, best_resident = 0;
+	for (uint32_t w = 1; w <= 8; w *= 2) {
+		const uint32_t bytes = pick_tbl + w * sa->per_wave_pick;
+		if (bytes > cu_lds) break;
+		const uint32_t resident = (cu_lds / ((bytes + 1279u) / 1280u * 1280u)) * w;
+		if (resident > best_resident) { best_resident = resident; best_w = w; }
 	}
+	if (n > (1u << 20)) best_w = 1;
+	if (sa->pick_waves == 0 || pick_tbl + sa->pick_waves * sa->per_wave_pick > cu_lds) sa->pick_waves = best_w;
+	return MGL_OK;
+}
 
-	/* targets: stratified by packet ordinal (default), or position draws (MGL_F_POSITION_TARGETS) */
+/* targets: stratified by packet ordinal (default), or position draws (MGL_F_POSITION_TARGETS); and the decision's thresholds */
+static int create_targets(mgl_sa* sa, size_t n)
+{
+	DevOwner& own = sa->own;
+	const size_t K = sa->cfg.neighbours_per_step;
 	if (!(sa->cfg.flags & MGL_F_POSITION_TARGETS)) {
 		sa->ctx.strat_nblk = (uint32_t)((n + 4095u) / 4096u);
-		HIPCHK(hipMalloc(&sa->d_strat_pre, sizeof(uint32_t) * (sa->ctx.strat_nblk + 2u)));
-		HIPCHK(hipMemset(sa->d_strat_pre, 0, sizeof(uint32_t) * (sa->ctx.strat_nblk + 2u)));
+		TRY(dnew(own, sa->d_strat_pre, sa->ctx.strat_nblk + 2u, 0));
 		sa->ctx.strat_pre = sa->d_strat_pre;
-		HIPCHK(hipMalloc(&sa->d_strat_tgt, sizeof(uint32_t) * sa->cfg.neighbours_per_step));
+		TRY(dnew(own, sa->d_strat_tgt, K));
 		sa->ctx.strat_tgt = sa->d_strat_tgt;
 		/* the fused launch takes up its picking neighbours first; MGL_NO_ORDER=1: in blockIdx order */
 		if (sa->incremental && sa->split_nbr && getenv("MGL_NO_ORDER") == nullptr) {
-			HIPCHK(hipMalloc(&sa->d_pick_hint, sa->cfg.neighbours_per_step));
-			HIPCHK(hipMemset(sa->d_pick_hint, 1, sa->cfg.neighbours_per_step));
-			HIPCHK(hipMalloc(&sa->d_pick_order, sizeof(uint32_t) * sa->cfg.neighbours_per_step));
+			TRY(dnew(own, sa->d_pick_hint, K, 1));
+			TRY(dnew(own, sa->d_pick_order, K));
 		}
 	}
 	sa->sqrt_thresh = ceil_sqrt_u64(sa->cfg.iters_per_epoch);
@@ -1069,23 +994,52 @@ static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 	sa->bulk_threshold = getenv("MGL_BULK_THRESHOLD") ? (uint32_t)atoi(getenv("MGL_BULK_THRESHOLD"))
 	                     : sa->batch_ok ? 2u : (n <= (1u << 20) ? 16u : n <= (1u << 24) ? 32u : 128u);
 	if (sa->bulk_threshold == 0) sa->bulk_threshold = 1;
+	return MGL_OK;
+}
 
-	/* packet_slab_new: all-literal current and best slabs */
+/* packet_slab_new: all-literal current and best slabs, the base built on them and checked */
+static int first_build(mgl_sa* sa, size_t n)
+{
 	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->base.v.slab, sa->ctx.n);
-	if (!sa->d_best) HIPCHK(hipMalloc(&sa->d_best, sizeof(mgl_pk) * n));
+	if (!sa->d_best) TRY(dnew(sa->own, sa->d_best, n)); /* (with snapshots it is the best snapshot's slab) */
 	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->d_best, sa->ctx.n);
 	HIPCHK(hipGetLastError());
-	int rc = rebuild_base(sa, 0);
-	if (rc) return rc;
-	if (sa->incremental && sa->snapshots && (rc = launch_snapshot(sa, sa->snap_lit, 0, 0, 0))) return rc;
+	TRY(rebuild_base(sa, 0));
+	if (sa->incremental && sa->snapshots) TRY(launch_snapshot(sa, sa->snap_lit, 0, 0, 0));
 	HIPCHK(hipStreamSynchronize(sa->stream));
-	{
-		/* an input the structures were not sized for shows here, not steps later inside mgl_sa_run */
-		Control c0;
-		HIPCHK(hipMemcpy(&c0, sa->base.ctl, sizeof c0, hipMemcpyDeviceToHost));
-		if (c0.error_flags) return fail(MGL_EDEVICE, "mgl_sa_create: building the base structures of the all-literal slab failed");
-	}
+	/* an input the structures were not sized for shows here, not steps later inside mgl_sa_run */
+	Control c0;
+	HIPCHK(hipMemcpy(&c0, sa->base.ctl, sizeof c0, hipMemcpyDeviceToHost));
+	if (c0.error_flags) return fail(MGL_EDEVICE, "mgl_sa_create: building the base structures of the all-literal slab failed");
 	return MGL_OK;
+}
+
+static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
+{
+	HIPCHK(hipSetDevice(sa->device));
+	TRY(create_streams(sa, n));
+	const mgl_layout L = mgl_make_layout(sa->props.lc, sa->props.lp, sa->props.pb);
+	const uint32_t ckpt_elems = (L.total + 7u) & ~7u;
+	/* input, zero padded so that window loads past the end stay in bounds */
+	TRY(dnew(sa->own, sa->d_data, n + 128, 0));
+	HIPCHK(hipMemcpy(sa->d_data, data, n, hipMemcpyHostToDevice));
+	TRY(build_match_index(sa, n));
+	TRY(dnew(sa->own, sa->d_cost_tbl, 2048));
+	HIPCHK(hipMemcpy(sa->d_cost_tbl, k_cost_table, sizeof(k_cost_table), hipMemcpyHostToDevice));
+	sa->ctx.data = sa->d_data; sa->ctx.n = (uint32_t)n;
+	fill_ctx_index(sa->ctx, sa->ix);
+	sa->ctx.cost_tbl = sa->d_cost_tbl; sa->ctx.L = L;
+	sa->ctx.dict_limit = sa->cfg.dict_limit; sa->ctx.max_scan = sa->cfg.max_bucket_scan; sa->ctx.top_k = sa->cfg.top_k;
+	TRY(alloc_search_buffers(sa, n, ckpt_elems));
+	sa->incremental = !(sa->cfg.flags & MGL_F_FULLWALK);
+	if (sa->incremental) {
+		TRY(create_engine(sa, n, ckpt_elems));
+		TRY(alloc_accept_buffers(sa));
+		TRY(alloc_nbr_scratch(sa, ckpt_elems));
+	}
+	TRY(set_launch_geometry(sa, n, ckpt_elems));
+	TRY(create_targets(sa, n));
+	return first_build(sa, n);
 }
 
 extern "C" mgl_sa* mgl_sa_create(const uint8_t* data, size_t n, mgl_properties props, const mgl_sa_config* cfg)
@@ -1321,23 +1275,23 @@ static int scratch_walk(mgl_sa* sa, const mgl_packet* packets, bool want_cum, bo
 #define MGL_OPT_DEF_CAND 16u
 #define MGL_OPT_DEF_CHUNK 4096u
 struct OptBufs {
+	DevOwner own; /* the call's temporaries: gone with it */
 	uint32_t *counts = nullptr, *prices = nullptr, *entry = nullptr;
 	mgl_pk *back = nullptr, *dp = nullptr, *res = nullptr, *keep = nullptr;
 	unsigned long long* obj = nullptr;
-	~OptBufs() { dfree(counts); dfree(prices); dfree(entry); dfree(back); dfree(dp); dfree(res); dfree(keep); dfree(obj); }
 };
 static int opt_alloc(mgl_sa* sa, OptBufs& o, uint32_t chunk, bool seed)
 {
 	const size_t n = sa->n, total = sa->ctx.L.total, nch = (n + chunk - 1) / chunk;
-	HIPCHK(hipMalloc(&o.counts, sizeof(uint32_t) * 2 * total));
-	HIPCHK(hipMalloc(&o.prices, sizeof(uint32_t) * 2 * total));
-	HIPCHK(hipMalloc(&o.back, sizeof(mgl_pk) * (n + 1)));
-	HIPCHK(hipMalloc(&o.dp, sizeof(mgl_pk) * n));
-	HIPCHK(hipMalloc(&o.obj, sizeof(unsigned long long)));
+	TRY(dnew(o.own, o.counts, 2 * total));
+	TRY(dnew(o.own, o.prices, 2 * total));
+	TRY(dnew(o.own, o.back, n + 1));
+	TRY(dnew(o.own, o.dp, n));
+	TRY(dnew(o.own, o.obj, 1));
 	if (seed) {
-		HIPCHK(hipMalloc(&o.entry, sizeof(uint32_t) * 5 * nch));
-		HIPCHK(hipMalloc(&o.res, sizeof(mgl_pk) * n));
-		HIPCHK(hipMalloc(&o.keep, sizeof(mgl_pk) * n));
+		TRY(dnew(o.own, o.entry, 5 * nch));
+		TRY(dnew(o.own, o.res, n));
+		TRY(dnew(o.own, o.keep, n));
 	}
 	return MGL_OK;
 }
@@ -1353,30 +1307,25 @@ static int opt_prices(mgl_sa* sa, OptBufs& o, const mgl_pk* slab)
 }
 /* ---- the parses' match lists (mgl_matchfinder.hip) */
 struct MfTmp {
+	DevOwner own;
 	uint4* queue = nullptr;
 	uint32_t* qcount = nullptr;
 	hipEvent_t t0 = nullptr, t1 = nullptr;
-	~MfTmp()
-	{
-		dfree(queue); dfree(qcount);
-		if (t0) (void)hipEventDestroy(t0);
-		if (t1) (void)hipEventDestroy(t1);
-	}
 };
 /* the handle holds the lists of depth `depth` afterwards */
 static int mf_ensure(mgl_sa* sa, uint32_t depth)
 {
 	if (sa->mf_built == depth) return MGL_OK;
 	const uint32_t n = (uint32_t)sa->n;
-	dfree(sa->d_mf_off); dfree(sa->d_mf_src); dfree(sa->d_mf_len);
+	sa->own.release(sa->d_mf_off); sa->own.release(sa->d_mf_src); sa->own.release(sa->d_mf_len); /* another depth's */
 	sa->d_mf_off = nullptr; sa->d_mf_src = nullptr; sa->d_mf_len = nullptr;
 	sa->mf_built = 0; sa->mf_total = 0;
 	MfTmp t;
-	HIPCHK(hipMalloc(&sa->d_mf_off, sizeof(uint32_t) * ((size_t)n + 1)));
-	HIPCHK(hipMalloc(&t.queue, sizeof(uint4) * (size_t)n));
-	HIPCHK(hipMalloc(&t.qcount, sizeof(uint32_t)));
-	HIPCHK(hipEventCreate(&t.t0));
-	HIPCHK(hipEventCreate(&t.t1));
+	TRY(dnew(sa->own, sa->d_mf_off, (size_t)n + 1));
+	TRY(dnew(t.own, t.queue, n));
+	TRY(dnew(t.own, t.qcount, 1));
+	HIPCHK(t.own.event(&t.t0));
+	HIPCHK(t.own.event(&t.t1));
 	const dim3 g_direct(n / 256u + 1u); /* n + 1 lanes: off[n] */
 	HIPCHK(hipEventRecord(t.t0, sa->stream));
 	HIPCHK(hipMemsetAsync(t.qcount, 0, sizeof(uint32_t), sa->stream));
@@ -1393,8 +1342,8 @@ static int mf_ensure(mgl_sa* sa, uint32_t depth)
 	HIPCHK(hipMemcpyAsync(&total, sa->d_mf_off + n, sizeof total, hipMemcpyDeviceToHost, sa->stream));
 	HIPCHK(hipStreamSynchronize(sa->stream));
 	if ((uint64_t)total > (uint64_t)MGL_MF_MAX_ENTRIES * n) return fail(MGL_EDEVICE, "match finder: the list lengths do not add up");
-	HIPCHK(hipMalloc(&sa->d_mf_src, sizeof(uint32_t) * ((size_t)total + 1)));
-	HIPCHK(hipMalloc(&sa->d_mf_len, sizeof(uint16_t) * ((size_t)total + 1)));
+	TRY(dnew(sa->own, sa->d_mf_src, (size_t)total + 1));
+	TRY(dnew(sa->own, sa->d_mf_len, (size_t)total + 1));
 	hipLaunchKernelGGL(k_mf_direct<true>, g_direct, dim3(256), 0, sa->stream, sa->ctx, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len, t.queue, t.qcount);
 	if (queued) hipLaunchKernelGGL(k_mf_scan<true>, g_scan, dim3(256), 0, sa->stream, sa->ctx, depth, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len,
 	                               (const uint4*)t.queue, (const uint32_t*)t.qcount);
@@ -1516,8 +1465,8 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 	if ((rc = replace_current(sa, put_slab(sa, o.res), false, MGL_EDEVICE, who, &st.greedy_cost))) return rc;
 	if ((rc = opt_prices(sa, o, o.res))) return rc;
 	hipEvent_t t0, t1;
-	HIPCHK(hipEventCreate(&t0));
-	HIPCHK(hipEventCreate(&t1));
+	HIPCHK(o.own.event(&t0));
+	HIPCHK(o.own.event(&t1));
 	uint64_t best = ~0ull;
 	for (uint32_t p = 0; p < passes && rc == MGL_OK; p++) {
 		if (hipEventRecord(t0, sa->stream) != hipSuccess) { rc = fail(MGL_EDEVICE, "hipEventRecord"); break; }
@@ -1542,8 +1491,6 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 			HIPCHK(hipMemcpyAsync(o.keep, o.res, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
 		}
 	}
-	(void)hipEventDestroy(t0);
-	(void)hipEventDestroy(t1);
 	if (rc) return rc;
 	/* the cheapest pass stays current (the last one already is), validated */
 	if (st.best_pass + 1 != st.passes) rc = replace_current(sa, put_slab(sa, o.keep), true, MGL_EDEVICE, who, &best);
@@ -1581,13 +1528,7 @@ struct Parse {
 	float ms = 0;
 	uint32_t best_v = UINT32_MAX;
 	std::vector<mgl_optimal_stats> st;
-	~Parse()
-	{
-		dfree(snaps); dfree(entry); dfree(lists); dfree(start_idx); dfree(back); dfree(dp); dfree(res); dfree(keep);
-		dfree(obj); dfree(cost); dfree(tab);
-		for (hipEvent_t e : { t0, t1, call0, fork, join })
-			if (e) (void)hipEventDestroy(e);
-	}
+	DevOwner own; /* of the device buffers and events */
 };
 
 /* checks and defaults; a chunk or a segment longer than the input acts like one of its length */
@@ -1646,35 +1587,29 @@ static int parse_args(const mgl_sa* sa, Parse& P, uint32_t passes, uint32_t chun
 	return MGL_OK;
 }
 
-/* an allocation that does not fit is MGL_ENOMEM, and leaves no error behind for the next launch check */
-#define PARSE_ALLOC(ptr, bytes)                                                                              \
-	do {                                                                                                     \
-		if (hipMalloc(&(ptr), (bytes)) != hipSuccess) {                                                      \
-			(void)hipGetLastError();                                                                         \
-			return fail(MGL_ENOMEM, "adaptive parse: the per-variant buffers do not fit the device"); \
-		}                                                                                                    \
-	} while (0)
-
 /* The buffers, the frontier's lists if a variant asks for them, the tables on the device.  resolved: the passes' parses are
- * resolved (res; pass 0's greedy parses lie there first) and the best is kept (keep). */
+ * resolved (res; pass 0's greedy parses lie there first) and the best is kept (keep).  A buffer that does not fit is
+ * MGL_ENOMEM. */
 static int parse_alloc(mgl_sa* sa, Parse& P, bool resolved)
 {
+	static const char* nomem = "adaptive parse: the per-variant buffers do not fit the device";
 	const size_t n = sa->n, nv = P.nv;
-	if (P.nfront) { int rc = mf_ensure(sa, P.depth); if (rc) return rc; }
-	PARSE_ALLOC(P.snaps, sizeof(uint16_t) * P.snap_total);
-	PARSE_ALLOC(P.entry, sizeof(uint32_t) * 5 * P.nch * nv);
-	PARSE_ALLOC(P.back, sizeof(mgl_pk) * (n + 1) * nv);
-	PARSE_ALLOC(P.dp, sizeof(mgl_pk) * n * nv);
+	if (P.nfront) TRY(mf_ensure(sa, P.depth));
+	auto room = [&](auto*& ptr, size_t count) { return dnew(P.own, ptr, count, -1, nomem); };
+	TRY(room(P.snaps, P.snap_total));
+	TRY(room(P.entry, 5 * P.nch * nv));
+	TRY(room(P.back, (n + 1) * nv));
+	TRY(room(P.dp, n * nv));
 	if (resolved) {
-		PARSE_ALLOC(P.res, sizeof(mgl_pk) * n * nv);
-		PARSE_ALLOC(P.keep, sizeof(mgl_pk) * n);
+		TRY(room(P.res, n * nv));
+		TRY(room(P.keep, n));
 	}
-	PARSE_ALLOC(P.obj, sizeof(unsigned long long) * nv);
-	PARSE_ALLOC(P.cost, sizeof(uint64_t) * nv);
-	PARSE_ALLOC(P.tab, sizeof(AdpVariant) * nv);
-	PARSE_ALLOC(P.lists, sizeof(uint32_t) * nv);
-	PARSE_ALLOC(P.start_idx, sizeof(uint32_t) * nv);
-	for (hipEvent_t* e : { &P.t0, &P.t1, &P.call0, &P.fork, &P.join }) HIPCHK(hipEventCreate(e));
+	TRY(room(P.obj, nv));
+	TRY(room(P.cost, nv));
+	TRY(room(P.tab, nv));
+	TRY(room(P.lists, nv));
+	TRY(room(P.start_idx, nv));
+	for (hipEvent_t* e : { &P.t0, &P.t1, &P.call0, &P.fork, &P.join }) HIPCHK(P.own.event(e));
 	if (P.nnear) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_near));
 	if (P.nfront) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_front));
 	HIPCHK(hipEventRecord(P.call0, sa->stream));
@@ -1853,15 +1788,7 @@ extern "C" int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_
 	return MGL_OK;
 }
 
-static hipEvent_t pool_event(mgl_sa* sa, size_t i)
-{
-	while (sa->ev_pool.size() <= i) {
-		hipEvent_t e = nullptr;
-		if (hipEventCreate(&e) != hipSuccess) return nullptr;
-		sa->ev_pool.push_back(e);
-	}
-	return sa->ev_pool[i];
-}
+static hipEvent_t pool_event(mgl_sa* sa, size_t i) { return pool_event(sa, sa->ev_pool, i); }
 
 extern "C" int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_threshold)
 {
@@ -2238,13 +2165,13 @@ extern "C" int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_
 		slab = sa->scratch.v.slab;
 	}
 	struct Tmp {
+		DevOwner own;
 		uint64_t* d = nullptr;
 		hipEvent_t t0 = nullptr, t1 = nullptr;
-		~Tmp() { dfree(d); if (t0) (void)hipEventDestroy(t0); if (t1) (void)hipEventDestroy(t1); }
 	} tmp;
-	HIPCHK(hipMalloc(&tmp.d, sizeof(uint64_t) * MGL_PROPS_TRIPLES));
-	HIPCHK(hipEventCreate(&tmp.t0));
-	HIPCHK(hipEventCreate(&tmp.t1));
+	TRY(dnew(tmp.own, tmp.d, MGL_PROPS_TRIPLES));
+	HIPCHK(tmp.own.event(&tmp.t0));
+	HIPCHK(tmp.own.event(&tmp.t1));
 	HIPCHK(hipEventRecord(tmp.t0, sa->stream));
 	hipLaunchKernelGGL(k_props_sweep, dim3(MGL_PROPS_TRIPLES), dim3(64), 0, sa->stream, sa->ctx, slab, tmp.d);
 	HIPCHK(hipGetLastError());
@@ -2272,36 +2199,27 @@ struct XoBufs {
 	uint8_t* winner = nullptr;
 	XoCounters* cnt = nullptr;
 	hipEvent_t t0 = nullptr, t1 = nullptr;
-	~XoBufs()
-	{
-		dfree(slabs); dfree(child); dfree(cost); dfree(onwalk); dfree(joint); dfree(bound); dfree(state); dfree(last); dfree(winner); dfree(cnt);
-		if (t0) (void)hipEventDestroy(t0);
-		if (t1) (void)hipEventDestroy(t1);
-	}
+	DevOwner own;
 };
-#define XO_ALLOC(ptr, bytes)                                                                      \
-	do {                                                                                          \
-		if (hipMalloc(&(ptr), (bytes)) != hipSuccess) {                                           \
-			(void)hipGetLastError();                                                              \
-			return fail(MGL_ENOMEM, "crossover: the per-parent buffers do not fit the device"); \
-		}                                                                                         \
-	} while (0)
+/* a buffer that does not fit is MGL_ENOMEM (the crossing exchange of all chains falls back on it) */
 static int xo_alloc(mgl_sa* sa, XoBufs& x, uint32_t P)
 {
+	static const char* nomem = "crossover: the per-parent buffers do not fit the device";
 	const size_t n = sa->n, nw = n / 64 + 1;
-	if (sa->force_xo_nomem) { sa->force_xo_nomem--; return fail(MGL_ENOMEM, "crossover: the per-parent buffers do not fit the device"); }
-	XO_ALLOC(x.slabs, sizeof(mgl_pk) * n * P);
-	XO_ALLOC(x.cost, sizeof(uint64_t) * (n + 1) * P);
-	XO_ALLOC(x.state, sizeof(uint32_t) * 5 * n * P);
-	XO_ALLOC(x.onwalk, sizeof(uint64_t) * nw * P);
-	XO_ALLOC(x.child, sizeof(mgl_pk) * n);
-	XO_ALLOC(x.joint, sizeof(uint64_t) * nw);
-	XO_ALLOC(x.bound, sizeof(uint64_t) * nw);
-	XO_ALLOC(x.last, sizeof(uint32_t) * nw);
-	XO_ALLOC(x.winner, n + 1);
-	XO_ALLOC(x.cnt, sizeof(XoCounters));
-	HIPCHK(hipEventCreate(&x.t0));
-	HIPCHK(hipEventCreate(&x.t1));
+	if (sa->force_xo_nomem) { sa->force_xo_nomem--; return fail(MGL_ENOMEM, nomem); }
+	auto room = [&](auto*& ptr, size_t count) { return dnew(x.own, ptr, count, -1, nomem); };
+	TRY(room(x.slabs, n * P));
+	TRY(room(x.cost, (n + 1) * P));
+	TRY(room(x.state, 5 * n * P));
+	TRY(room(x.onwalk, nw * P));
+	TRY(room(x.child, n));
+	TRY(room(x.joint, nw));
+	TRY(room(x.bound, nw));
+	TRY(room(x.last, nw));
+	TRY(room(x.winner, n + 1));
+	TRY(room(x.cnt, 1));
+	HIPCHK(x.own.event(&x.t0));
+	HIPCHK(x.own.event(&x.t1));
 	return MGL_OK;
 }
 /* The P parents lie packed in x.slabs: walk them, cut, pick, scatter into x.child and cost the child.  A parent the walk
@@ -2500,6 +2418,12 @@ extern "C" int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs,
 extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes)
 {
 	if (!sa || !out || !bytes) return fail(MGL_EINVAL, "null argument");
+	if (what == 87) { /* host counters, on every handle: the device allocations the handle's owner holds, and their bytes as requested */
+		const uint64_t v[2] = { sa->own.live, sa->own.live_bytes };
+		*bytes = sizeof v;
+		if (cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
+		return MGL_OK;
+	}
 	if (!sa->incremental && what != 21 && what != 22) return fail(MGL_EINVAL, "mgl_debug_dump: handle runs the full-walk engine");
 	HIPCHK(hipSetDevice(sa->device));
 	HIPCHK(hipStreamSynchronize(sa->stream));
@@ -2549,22 +2473,22 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	case 14: src = sa->ab.hdr; sz = sa->ab.hdr ? sizeof(uint32_t) * 16 : 0; break; /* apply counters / stage cycles */
 	case 16: src = sa->base.ctl; sz = sizeof(Control); break; /* raw control block */
 	case 15: src = sa->d_pickrec; sz = sa->d_pickrec ? sizeof(uint4) * sa->cfg.neighbours_per_step : 0; break;
-	case 18: src = sa->d_quad_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 19: src = sa->d_quad_nx; sz = sizeof(uint16_t) * (sa->n - 1); break;
-	case 12: src = sa->d_bucket_off; sz = sizeof(uint32_t) * 65537; break;
-	case 13: src = sa->d_bucket_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 30: case 31: case 32: case 33: case 34: case 35: src = sa->d_xpos[what - 30]; sz = sizeof(uint32_t) * (sa->n - 1); break; /* exact-length orders D = what - 28 */
-	case 40: case 41: case 42: case 43: case 44: case 45: src = sa->d_xrank[what - 40]; sz = src ? sizeof(uint32_t) * (sa->n - 1) : 0; break;
-	case 50: case 51: case 52: case 53: case 54: case 55: src = sa->d_xrun[what - 50]; sz = src ? sizeof(uint32_t) * (sa->n - 1) : 0; break;
-	case 60: case 61: case 62: case 63: case 64: case 65: src = sa->d_xnxb[what - 60]; sz = sa->n - 1; break;
-	case 70: src = sa->d_oct_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 71: src = sa->d_oct_rank; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 72: src = sa->d_oct_run; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 73: src = sa->d_oct_nx8; sz = sizeof(uint64_t) * (sa->n - 1); break;
-	case 74: src = sa->d_hex_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 75: src = sa->d_hex_rank; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 76: src = sa->d_hex_run; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 77: src = sa->d_hex_nx8; sz = sizeof(uint64_t) * (sa->n - 1); break;
+	case 18: src = sa->ix.quad_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 19: src = sa->ix.quad_nx; sz = sizeof(uint16_t) * (sa->n - 1); break;
+	case 12: src = sa->ix.bucket_off; sz = sizeof(uint32_t) * 65537; break;
+	case 13: src = sa->ix.bucket_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 30: case 31: case 32: case 33: case 34: case 35: src = sa->ix.xpos[what - 30]; sz = sizeof(uint32_t) * (sa->n - 1); break; /* exact-length orders D = what - 28 */
+	case 40: case 41: case 42: case 43: case 44: case 45: src = sa->ix.xrank[what - 40]; sz = src ? sizeof(uint32_t) * (sa->n - 1) : 0; break;
+	case 50: case 51: case 52: case 53: case 54: case 55: src = sa->ix.xrun[what - 50]; sz = src ? sizeof(uint32_t) * (sa->n - 1) : 0; break;
+	case 60: case 61: case 62: case 63: case 64: case 65: src = sa->ix.xnxb[what - 60]; sz = sa->n - 1; break;
+	case 70: src = sa->ix.oct_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 71: src = sa->ix.oct_rank; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 72: src = sa->ix.oct_run; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 73: src = sa->ix.oct_nx8; sz = sizeof(uint64_t) * (sa->n - 1); break;
+	case 74: src = sa->ix.hex_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 75: src = sa->ix.hex_rank; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 76: src = sa->ix.hex_run; sz = sizeof(uint32_t) * (sa->n - 1); break;
+	case 77: src = sa->ix.hex_nx8; sz = sizeof(uint64_t) * (sa->n - 1); break;
 	case 23: src = sa->nbr.cost; sz = sizeof(uint64_t) * sa->cfg.neighbours_per_step; break;   /* costs, */
 	case 24: src = sa->nbr.ndiffs; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* journal lengths */
 	case 25: src = sa->nbr.walked; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* and packets walked of the last costed neighbours */

@@ -291,10 +291,10 @@ static int comm_allgather_u64(mgl_sa* sa, mgl_comm* comm, uint64_t mine, uint64_
 	}
 	if (!sa) return fail(MGL_EINVAL, "an RCCL all-gather needs a chain (stream)");
 	struct Tmp {
+		DevOwner own;
 		uint64_t* d = nullptr;
-		~Tmp() { dfree(d); }
 	} tmp;
-	HIPCHK(hipMalloc(&tmp.d, sizeof(uint64_t) * ((size_t)comm->world + 1u)));
+	TRY(dnew(tmp.own, tmp.d, (size_t)comm->world + 1u));
 	HIPCHK(hipMemcpyAsync(tmp.d, &mine, sizeof mine, hipMemcpyHostToDevice, sa->stream));
 	const int nrc = comm->all_gather(tmp.d, tmp.d + 1, 1, MGL_NCCL_UINT64, comm->comm, sa->stream);
 	if (nrc != 0) {
