@@ -1,6 +1,7 @@
 /*
- * mgl_api.hip -- the C ABI of include/megalania_hip.h over the kernels in mgl_kernels.hip.
- * Owns all device memory; one HIP stream per handle; no host thread is created.
+ * mgl_api.hip -- the C ABI of include/megalania_hip.h over the kernels in mgl_kernels*.hip and their neighbours.
+ * A handle's DevOwner (mgl_owner.h) owns its device memory, pinned buffers, events and its three HIP streams (StepQueues);
+ * no host thread is created.
  */
 #include "mgl_kernels.hip"
 #include "mgl_kernels2.hip"
@@ -27,11 +28,6 @@
 static const uint16_t k_cost_table[2048] = {
 #include "mgl_cost_table.inc"
 };
-
-/* A/B switch of the step's serial tail; 0 builds the form before it */
-#ifndef MGL_TAIL_EARLY
-#define MGL_TAIL_EARLY 1 /* the last resort queued in front of the join with the re-simulations; no fork wait on the third stream */
-#endif
 
 #define MGL_MAX_INPUT 176000000ull
 static thread_local std::string g_err;
@@ -99,16 +95,82 @@ struct MatchIndex {
 	uint64_t *oct_nx8 = nullptr, *hex_nx8 = nullptr;
 };
 
+/* The MGL_* environment variables a handle honours, read once per handle at the top of create_impl (read_env) and nowhere
+ * else: the creation stages read this.  (MGL_TRACE and MGL_PROF_BIG are the process's, MGL_COMM_TIMEOUT_S is the exchange's.) */
+struct EnvSwitches {
+	uint32_t halves;          /* MGL_HALVES: slices of a step's neighbours, 1..8 (any other value: 1); unset: 2 above 1 MiB of input, else 1 */
+	uint32_t sb_shift;        /* MGL_SB_SHIFT: log2 of the builder's block, 8..10 (any other value is ignored); 0 = the size rule of create_engine */
+	bool no_incremental_apply; /* MGL_NO_INCREMENTAL_APPLY: single steps rebuild the base instead of patching it (and no batch accept) */
+	bool no_batch;            /* MGL_NO_BATCH: bulk steps always rebuild */
+	bool no_evcancel;         /* MGL_NO_EVCANCEL: the window walk lists all events of a re-coded packet, not the changed ones only */
+	bool no_split;            /* MGL_NO_SPLIT: the one-kernel form only */
+	bool no_cont;             /* MGL_NO_CONT: no continuation records between the second half and the second pass */
+	bool no_fuse;             /* MGL_NO_FUSE: pick and walk of a slice as two launches */
+	uint32_t simw;            /* MGL_SIMW: wavefronts per neighbour of k_sim, 1, 2, 4 or 8 (any other value is ignored); 0 = MGL_SIM_WAVES */
+	bool no_adapt;            /* MGL_NO_ADAPT: the split form stays, whatever the device recommends */
+	uint32_t pick_waves;      /* MGL_PICK_WAVES: wavefronts per workgroup of the pick half, 1, 2, 4 or 8; 0 (unset, any other value) = the rule of set_launch_geometry */
+	bool no_order;            /* MGL_NO_ORDER: the fused launch takes its neighbours in blockIdx order */
+	uint32_t bulk_threshold;  /* MGL_BULK_THRESHOLD: improving neighbours per step above which a bulk step pays, at least 1 (0 is read as 1); 0 = unset: the rule of create_targets */
+};
+/* the three streams of a handle and the events that order a step's kernels across them */
+struct StepQueues {
+	hipStream_t stream = nullptr;  /* the main stream: everything that is not named below */
+	hipStream_t stream2 = nullptr; /* second half of a step's neighbours: its kernels fill the other half's tails */
+	hipStream_t stream3 = nullptr; /* the re-simulation kernels of the split form: beside the second pass, which only needs the walks */
+	hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+	hipEvent_t ev_tgt = nullptr, ev_tgt_go = nullptr; /* the next step's targets worked out beside the rest of this step's accept (launch_targets_ahead) */
+	hipEvent_t ev_rest[8] = {}, ev_sim = nullptr;
+	hipEvent_t ev_val = nullptr;   /* a bulk step's validation beside its build */
+	hipEvent_t ev_bstat = nullptr; /* behind the read-back copy of the batch accept's status words */
+};
+/* the next step's targets, made ahead on the second stream: none queued / queued and good for the next launch_neighbours /
+ * queued but the base went another way: to be made again */
+enum TgtAhead { TGT_NONE, TGT_READY, TGT_STALE };
+/* MGL_ACCEPT_AUTO's state: it switches between single and bulk steps block by block */
+struct AutoAccept {
+	bool bulk_now = true;          /* what the next block of steps runs as */
+	uint64_t bulk_hold = 0;        /* single steps left before bulk steps are tried again (their windows were too long) */
+	uint64_t blk_done = 0;         /* steps of the current block already run (a block carries over from one mgl_sa_run call to the next) */
+	uint64_t blk_imp0 = 0, blk_acc0 = 0; /* the device's improving / accepted counters when the current block began */
+	bool select_small = false;    /* the previous bulk step had few acceptable neighbours: this one's selection runs as one launch */
+	/* MGL_ACCEPT_AUTO starts over: a fresh block, bulk steps first (a new slab says nothing about the old one's windows) */
+	void reset() { bulk_now = true; bulk_hold = 0; blk_done = 0; select_small = false; }
+	void decide(bool was_bulk, uint64_t block, uint64_t improving, uint64_t taken, uint32_t bulk_threshold, bool batch_ok);
+};
+/* the form the regular neighbour launch runs as */
+struct LaunchForm {
+	bool split_nbr, adaptive; /* adaptive: the device recommends the split or the one-kernel form, the host adopts it block by block */
+	bool fuse;                /* the two halves as one launch (k_neighbours2<false, MGL_NBR_PICKWALK>); MGL_NO_FUSE=1: two launches */
+	bool form_single = false; /* the form the regular launch runs as right now */
+	uint32_t short_looks = 0; /* blocks of at most four steps still to come after a switch of the launch form */
+};
+/* diagnostic hooks of the tests (mgl_debug_set) */
+struct TestHooks {
+	uint32_t xo_nomem = 0;   /* key 8: the next so many crossovers find no room for their buffers */
+	uint32_t batch_fail = 0; /* key 5: the next so many batch accepts give up behind their commit */
+	uint32_t batch_late = 0; /* ... 0: before any chain is touched; n: once the n-th touched context has rewritten its chain's descriptors */
+	uint32_t rollbacks = 0;  /* key 3: treat the next so many bulk steps that took moves as failed validations */
+};
+/* MGL_F_TIMING brackets steps with events: every step of a short run, every fourth of a longer one (the ten event records of a
+ * timed step cost it 30 us at 10 MB), at most 512 of them.  A timed step has four slots on the main stream and, in the split
+ * form, two per slice for the k_sim launches of its first two slices on the stream they run on (the re-simulation kernel
+ * measured on its own: it is the path's dominant kernel).  The events are the handle's, made on demand (pool_event). */
+enum TimedSlot { T_NBR_BEGIN, T_NBR_END, T_ACCEPT_BEGIN, T_ACCEPT_END, T_SIM_BEGIN, T_SIM_END };
+struct StepTimer {
+	hipEvent_t ev_begin = nullptr, ev_end = nullptr; /* around the whole run */
+	std::vector<hipEvent_t> ev_pool, ev_sim_pool;    /* four per timed step each: the slots above / begin and end of slices 0 and 1 */
+	uint64_t stride = 1, timed = 0;  /* of the current run: every stride-th step is timed, `timed` of them in all */
+	int64_t step = -1;               /* >= 0: the current step's place among the timed ones */
+	bool sim = false;                /* ... and its k_sim launches are bracketed too (the split form runs) */
+	std::vector<uint8_t> sim_timed;  /* per timed step: how many of the regular k_sim launches carry events (0: none, the one-kernel form ran) */
+};
+
 struct mgl_sa {
 	DevOwner own;            /* every device buffer, pinned buffer, event and stream of the handle: released when the handle is deleted */
 	int device;
-	hipStream_t stream = nullptr;
-	hipStream_t stream2;     /* second half of a step's neighbours: its kernels fill the other half's tails */
-	hipEvent_t ev_fork, ev_join;
-	hipEvent_t ev_tgt = nullptr, ev_tgt_go = nullptr; /* the next step's targets worked out beside the rest of this step's accept (launch_targets_ahead) */
-	int tgt_ahead = 0;             /* 0 none, 1 queued and good for the next launch_neighbours, 2 queued but the base went another way: to be made again */
-	hipStream_t stream3 = nullptr;   /* the re-simulation kernels of the split form: beside the second pass, which only needs the walks */
-	hipEvent_t ev_rest[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }, ev_sim = nullptr;
+	EnvSwitches env;
+	StepQueues q;
+	TgtAhead tgt_ahead = TGT_NONE;
 	uint32_t halves;
 	uint32_t n;
 	mgl_properties props;
@@ -141,15 +203,13 @@ struct mgl_sa {
 	uint32_t big_waves = MGL_BIG_WAVES; /* wavefronts of a second-pass workgroup (mgl_debug_set key 7 lowers it for tests) */
 	uint32_t chg_cap = MGL_CHG_CAP; /* events per first-pass list */
 	uint32_t per_wave_pick, per_wave_rest, pick_waves; /* LDS per wavefront of the two halves of the split launch */
-	bool fuse;              /* the two halves as one launch (k_neighbours2<false, MGL_NBR_PICKWALK>); MGL_NO_FUSE=1: two launches */
 	uint32_t fused_lds;     /* its dynamic LDS: one wavefront, the larger of the two halves' areas */
 	size_t b2_bytes;
 	BigScratch big;
 	uint32_t* d_todo2;
 	uint4* d_pickstate;     /* 2 K: target, RNG position and walk state at the target (first half -> second half) */
 	uint4* d_pickrec;       /* K: picked packet, RNG position, ok flag (first half -> second half of the neighbour evaluation) */
-	bool split_nbr, adaptive; /* adaptive: the device recommends the split or the one-kernel form, the host adopts it block by block */
-	bool form_single = false; /* the form the regular launch runs as right now */
+	LaunchForm form;
 	uint32_t* d_counts;     /* [0] first-pass overflow count, [1] second-pass overflow count, [2] spill slots used, [3] repair picks, [4] unused, always zero, [5] event pairs the window walks cancelled */
 	ApplyBuf ab;
 	uint32_t apply_blocks;
@@ -160,16 +220,12 @@ struct mgl_sa {
 	SnapMeta* d_snap_meta; /* [0] literal, [1] best */
 	bool parallel_build;
 	PBuild pb;
-	hipEvent_t ev_begin, ev_end;
-	std::vector<hipEvent_t> ev_pool;
+	StepTimer timer;
 	/* the step's decision: single (one winner, incremental accept) or bulk (every window-best acceptable
 	 * neighbour, parallel rebuild); MGL_ACCEPT_AUTO switches between them block by block */
 	int accept_mode = MGL_ACCEPT_AUTO;
 	uint32_t bulk_threshold = 0;   /* improving neighbours per step above which a bulk step pays */
-	bool bulk_now = true;          /* AUTO: what the next block of steps runs as */
-	uint64_t bulk_hold = 0;        /* AUTO: single steps left before bulk steps are tried again (their windows were too long) */
-	uint64_t blk_done = 0;         /* AUTO: steps of the current block already run (a block carries over from one mgl_sa_run call to the next) */
-	uint64_t blk_imp0 = 0, blk_acc0 = 0; /* AUTO: the device's improving / accepted counters when the current block began */
+	AutoAccept autoacc;
 	BulkBuf bulk;
 	BatchBuf batch;               /* a bulk step that took few moves patches the base instead of rebuilding it (mgl_kernels5.hip) */
 	bool batch_ok = false;
@@ -180,28 +236,17 @@ struct mgl_sa {
 	 * position targets, no split form */
 	unsigned char* d_pick_hint = nullptr;
 	uint32_t* d_pick_order = nullptr;
-	bool select_small = false;    /* the previous bulk step had few acceptable neighbours: this one's selection runs as one launch */
 	uint32_t* h_bstat = nullptr;   /* pinned: the batch accept's status words, read back once per bulk step */
-	hipEvent_t ev_bstat = nullptr; /* behind that read-back's copy */
-	uint32_t force_xo_nomem = 0; /* diagnostic (mgl_debug_set key 8): the next so many crossovers find no room for their buffers */
-	uint32_t force_batch_fail = 0; /* diagnostic (mgl_debug_set key 5): the next so many batch accepts give up behind their commit */
-	uint32_t force_batch_late = 0; /* ... 0: before any chain is touched; n: once the n-th touched context has rewritten its chain's descriptors */
+	TestHooks force;
 	AcceptLimits lim, lim_max;     /* what the in-place accepts compare against (mgl_debug_set key 6 lowers them) and the compiled / allocated values */
 	uint64_t batch_early_giveups = 0; /* bulk steps that began a batch accept and left it before anything was touched (clusters or a walk gave up) */
 	uint64_t batch_accepts = 0, batch_fallbacks = 0; /* bulk steps whose moves were patched in / that went to the rebuild although a batch accept began */
 	std::vector<uint8_t> mode_log; /* per step of the last mgl_sa_run: 0 single, 1 bulk */
-	uint32_t force_rollbacks = 0;  /* diagnostic: treat the next so many bulk steps that took moves as failed validations */
 	uint64_t bulk_rollbacks = 0;   /* bulk steps whose combined parse failed validation and was taken back (never seen) */
 	bool best_unverified = false;  /* packets_best came from another chain: checked when an epoch starts from it */
 	uint32_t sim_waves = MGL_SIM_WAVES; /* wavefronts per neighbour in the regular re-simulation launch (MGL_SIMW: 1, 2, 4, 8) */
-	/* the re-simulation kernel measured on its own (it is the path's dominant kernel): HIP events around its launches on the
-	 * streams they run on (MGL_F_TIMING), and -- when switched on, mgl_debug_set key 4 -- the bytes of chain data it reads */
-	std::vector<hipEvent_t> ev_sim_pool;
-	int64_t time_sim_step = -1;     /* >= 0: the step whose k_sim launches are bracketed by events */
-	bool count_traffic = false;
+	bool count_traffic = false;     /* mgl_debug_set key 4: count the bytes of chain data the re-simulation kernel reads */
 	unsigned long long* d_traffic = nullptr; /* [0] bytes [1] spare */
-	uint32_t short_looks = 0;      /* blocks of at most four steps still to come after a switch of the launch form */
-	hipEvent_t ev_val = nullptr; /* a bulk step's validation beside its build */
 	/* the parses' match finder (mgl_sa_set_match_finder) and the lists of mgl_matchfinder.hip: made on first use, kept with
 	 * the depth they were made at, made again when another depth is asked for */
 	int mf_finder = MGL_MF_NEAREST;
@@ -295,18 +340,17 @@ static int launch_snapshot(mgl_sa* sa, Base2& snap, uint32_t which, int dir, int
 	}
 	p.nseg = MGL_B2_ARRAYS;
 	p.src_pool_top = from.pool_top;
-	hipLaunchKernelGGL(k_snapshot, dim3(2048), dim3(256), 0, sa->stream, p, sa->base.ctl, sa->d_snap_meta + which, dir, cond);
+	hipLaunchKernelGGL(k_snapshot, dim3(2048), dim3(256), 0, sa->q.stream, p, sa->base.ctl, sa->d_snap_meta + which, dir, cond);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
 
 static int launch_rebuild(mgl_sa* sa, BaseMem& b, int from_dirty, uint64_t* cum, uint16_t* final_probs)
 {
-	hipLaunchKernelGGL(k_rebuild, dim3(1), dim3(64), sa->walk_lds, sa->stream, sa->ctx, b.v, b.ctl, from_dirty, cum, final_probs);
+	hipLaunchKernelGGL(k_rebuild, dim3(1), dim3(64), sa->walk_lds, sa->q.stream, sa->ctx, b.v, b.ctl, from_dirty, cum, final_probs);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
-/* (re)derive everything that hangs off the current base slab */
 /* the base structures of the slab from scratch, block-parallel (mgl_pbuild.hip) */
 static int launch_pbuild(mgl_sa* sa, bool validate_beside = false)
 {
@@ -314,7 +358,7 @@ static int launch_pbuild(mgl_sa* sa, bool validate_beside = false)
 	Base2& b = sa->b2;
 	PBuild& pb = sa->pb;
 	Control* ctl = sa->base.ctl;
-	hipStream_t st = sa->stream;
+	hipStream_t st = sa->q.stream;
 	const uint32_t total = c.L.total;
 	hipLaunchKernelGGL(pb_exits, dim3(pb.nblk), dim3(320), 0, st, c, b, pb);
 	hipLaunchKernelGGL(pb_entries_group, dim3(pb.ngrp), dim3(320), MGL_PB_GROUP * MGL_PB_ENTRIES * 2u, st, pb);
@@ -333,10 +377,10 @@ static int launch_pbuild(mgl_sa* sa, bool validate_beside = false)
 	if (validate_beside) {
 		/* a bulk step's check of the new parse (every packet against the input) needs the bitmaps and the special-state
 		 * records, which exist from here on: it runs on the second stream beside the rest of the build */
-		HIPCHK(hipEventRecord(sa->ev_fork, st));
-		HIPCHK(hipStreamWaitEvent(sa->stream2, sa->ev_fork, 0));
-		hipLaunchKernelGGL(k_validate, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->stream2, sa->ctx, sa->b2, sa->base.ctl);
-		HIPCHK(hipEventRecord(sa->ev_val, sa->stream2));
+		HIPCHK(hipEventRecord(sa->q.ev_fork, st));
+		HIPCHK(hipStreamWaitEvent(sa->q.stream2, sa->q.ev_fork, 0));
+		hipLaunchKernelGGL(k_validate, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->q.stream2, sa->ctx, sa->b2, sa->base.ctl);
+		HIPCHK(hipEventRecord(sa->q.ev_val, sa->q.stream2));
 	}
 	{
 		const uint32_t og = (pb.nblk + MGL_PB_OFF_ROWS - 1u) / MGL_PB_OFF_ROWS;
@@ -351,7 +395,7 @@ static int launch_pbuild(mgl_sa* sa, bool validate_beside = false)
 	hipLaunchKernelGGL(pb_sim_fix, dim3((total + 63) / 64), dim3(64), 0, st, c, b, pb);
 	hipLaunchKernelGGL(pb_ckpt, dim3((b.ck_elems + 63) / 64, (b.nck + MGL_PB_CK_ROWS - 1) / MGL_PB_CK_ROWS), dim3(64), 0, st, c, b);
 	hipLaunchKernelGGL(pb_finish, dim3(1), dim3(64), 0, st, pb, ctl);
-	if (validate_beside) HIPCHK(hipStreamWaitEvent(st, sa->ev_val, 0));
+	if (validate_beside) HIPCHK(hipStreamWaitEvent(st, sa->q.ev_val, 0));
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -359,7 +403,7 @@ static int rebuild_base(mgl_sa* sa, int after_accept)
 {
 	if (!sa->incremental) return launch_rebuild(sa, sa->base, after_accept, nullptr, nullptr);
 	if (sa->parallel_build && !after_accept) return launch_pbuild(sa);
-	hipLaunchKernelGGL(k_build, dim3(1), dim3(64), sa->build_lds, sa->stream, sa->ctx, sa->b2, sa->base.ctl, after_accept);
+	hipLaunchKernelGGL(k_build, dim3(1), dim3(64), sa->build_lds, sa->q.stream, sa->ctx, sa->b2, sa->base.ctl, after_accept);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -367,7 +411,7 @@ static int rebuild_base(mgl_sa* sa, int after_accept)
 static int launch_validate(mgl_sa* sa)
 {
 	if (!sa->incremental) return MGL_OK;
-	hipLaunchKernelGGL(k_validate, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, sa->b2, sa->base.ctl);
+	hipLaunchKernelGGL(k_validate, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->q.stream, sa->ctx, sa->b2, sa->base.ctl);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -401,25 +445,21 @@ static int launch_apply(mgl_sa* sa, uint64_t next_gstep = ~0ull)
 {
 	/* the base is about to leave the best slab it still holds: keep a copy first (lazy: while every
 	 * accepted step is a new best no copy is ever taken) */
-	if (sa->snapshots) {
-		int rc = launch_snapshot(sa, sa->snap_best, 1, 0, 2);
-		if (rc) return rc;
-	}
-	hipLaunchKernelGGL(k_apply_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->nbr, sa->ab, sa->lim);
-	if (next_gstep != ~0ull) { int rc = launch_targets_ahead(sa, next_gstep); if (rc) return rc; } /* the bitmap is final from here on */
+	if (sa->snapshots) TRY(launch_snapshot(sa, sa->snap_best, 1, 0, 2));
+	hipLaunchKernelGGL(k_apply_walk, dim3(1), dim3(64), 0, sa->q.stream, sa->ctx, sa->b2, sa->base.ctl, sa->nbr, sa->ab, sa->lim);
+	if (next_gstep != ~0ull) TRY(launch_targets_ahead(sa, next_gstep)); /* the bitmap is final from here on */
 	if (!sa->snapshots)
-		hipLaunchKernelGGL(k_copy_best, dim3(256), dim3(256), 0, sa->stream, (const Control*)sa->base.ctl,
+		hipLaunchKernelGGL(k_copy_best, dim3(256), dim3(256), 0, sa->q.stream, (const Control*)sa->base.ctl,
 		                   (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n);
-	hipLaunchKernelGGL(k_apply_chains, dim3(sa->apply_blocks), dim3(MGL_APPLY_THREADS), 0, sa->stream, sa->ctx, accept_b2(sa), sa->base.ctl, accept_ab(sa), sa->lim);
-	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)nullptr);
-	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)nullptr);
-	hipLaunchKernelGGL(k_build_end, dim3(1), dim3(64), sa->build_lds, sa->stream, sa->ctx, sa->b2, sa->base.ctl, sa->snapshots ? 1 : 0, sa->d_counts, sa->adaptive ? 1 : 0, sa->form_single ? 1 : 0);
+	hipLaunchKernelGGL(k_apply_chains, dim3(sa->apply_blocks), dim3(MGL_APPLY_THREADS), 0, sa->q.stream, sa->ctx, accept_b2(sa), sa->base.ctl, accept_ab(sa), sa->lim);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->q.stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)nullptr);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->q.stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)nullptr);
+	hipLaunchKernelGGL(k_build_end, dim3(1), dim3(64), sa->build_lds, sa->q.stream, sa->ctx, sa->b2, sa->base.ctl, sa->snapshots ? 1 : 0, sa->d_counts, sa->form.adaptive ? 1 : 0, sa->form.form_single ? 1 : 0);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
-/* diagnostic (MGL_TRACE=1): name every launch of the neighbour evaluation on stderr and wait for the device after it, so that a
- * faulting kernel is the last one named */
-/* diagnostic switches of the launch path, read once */
+/* diagnostic switches of the launch path, read once.  MGL_TRACE=1: name every launch of the neighbour evaluation on stderr and wait
+ * for the device after it, so that a faulting kernel is the last one named */
 static const bool g_trace = getenv("MGL_TRACE") != nullptr, g_prof_big = getenv("MGL_PROF_BIG") != nullptr;
 #define NBR_TRACE(name) do { if (g_trace) { fprintf(stderr, "[mgl] %s\n", name); hipError_t e_ = hipDeviceSynchronize(); if (e_ != hipSuccess) fprintf(stderr, "[mgl] %s -> %s\n", name, hipGetErrorString(e_)); } } while (0)
 /* event i of a pool that grows on demand; the events are the handle's */
@@ -432,12 +472,17 @@ static hipEvent_t pool_event(mgl_sa* sa, std::vector<hipEvent_t>& pool, size_t i
 	}
 	return pool[i];
 }
-static hipEvent_t sim_event(mgl_sa* sa, size_t i) { return pool_event(sa, sa->ev_sim_pool, i); }
-static uint32_t nbr_slices(const mgl_sa* sa)
+/* slot `slot` of the current step (slice h's, for the two k_sim slots) on stream st, if the step is a timed one */
+static int mark(mgl_sa* sa, TimedSlot slot, hipStream_t st, uint32_t h = 0)
 {
-	const uint32_t K = sa->cfg.neighbours_per_step;
-	return (sa->halves >= 2 && K >= 1024) ? sa->halves : 1u;
+	StepTimer& t = sa->timer;
+	const bool sim = slot >= T_SIM_BEGIN;
+	if (t.step < 0 || (sim && (!t.sim || h >= 2))) return MGL_OK;
+	const size_t i = 4 * (size_t)t.step + (sim ? 2 * h + (slot - T_SIM_BEGIN) : slot);
+	HIPCHK(hipEventRecord(pool_event(sa, sim ? t.ev_sim_pool : t.ev_pool, i), st));
+	return MGL_OK;
 }
+static uint32_t nbr_slices(const mgl_sa* sa) { return (sa->halves >= 2 && sa->cfg.neighbours_per_step >= 1024) ? sa->halves : 1u; }
 /* stratified targets of a step: packets before every block of 4 096 positions of the current walk, their
  * prefix sums, then one wavefront per neighbour turns its ordinal into a position */
 static void launch_targets(mgl_sa* sa, hipStream_t st, uint64_t step_override)
@@ -456,136 +501,163 @@ static void launch_targets(mgl_sa* sa, hipStream_t st, uint64_t step_override)
 }
 /* The next step's targets need the on-walk bitmap of the new base and nothing else: an accept has written it long before it is
  * through with chains and checkpoints, so they are worked out on the second stream beside the rest of the accept (30 us off
- * every step).  Called right behind the launch that completes the bitmap; `next_gstep` is the step they are for. */
+ * every step).  Called right behind the launch that completes the bitmap; `next_gstep` is the step they are for.
+ * Records ev_tgt_go on the main stream, queues on the second stream behind it, records ev_tgt there. */
 static int launch_targets_ahead(mgl_sa* sa, uint64_t next_gstep)
 {
 	if (!sa->d_strat_pre || !sa->incremental) return MGL_OK;
-	HIPCHK(hipEventRecord(sa->ev_tgt_go, sa->stream));
-	HIPCHK(hipStreamWaitEvent(sa->stream2, sa->ev_tgt_go, 0));
-	launch_targets(sa, sa->stream2, next_gstep);
-	HIPCHK(hipEventRecord(sa->ev_tgt, sa->stream2));
+	HIPCHK(hipEventRecord(sa->q.ev_tgt_go, sa->q.stream));
+	HIPCHK(hipStreamWaitEvent(sa->q.stream2, sa->q.ev_tgt_go, 0));
+	launch_targets(sa, sa->q.stream2, next_gstep);
+	HIPCHK(hipEventRecord(sa->q.ev_tgt, sa->q.stream2));
 	HIPCHK(hipGetLastError());
-	sa->tgt_ahead = 1;
+	sa->tgt_ahead = TGT_READY;
+	return MGL_OK;
+}
+
+/* ---- a step's neighbour evaluation in stages: launch_neighbours calls them in the order they stand in. */
+/* the eight arguments every k_neighbours2 launch shares, written once */
+template <class Kern>
+static void launch_nbr2(mgl_sa* sa, Kern kern, uint32_t grid, uint32_t threads, uint32_t lds, hipStream_t st, uint64_t step_override, uint32_t per_wave,
+                        uint32_t* todo, uint32_t* todo_count, unsigned long long* prof, uint4* pickrec, uint32_t j0, uint32_t j1, uint4* pickstate)
+{
+	hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, sa->ctx, sa->b2, sa->base.ctl, sa->cfg.seed, step_override, sa->cfg.neighbours_per_step,
+	                   sa->nbr, per_wave, todo, todo_count, prof, sa->big, pickrec, j0, j1, pickstate);
+}
+/* The step's targets, on the main stream.  Waits for ev_tgt if targets were queued ahead; makes them here unless those are good. */
+static int nbr_targets(mgl_sa* sa, uint64_t step_override)
+{
+	if (!sa->d_strat_pre) return MGL_OK;
+	if (sa->tgt_ahead != TGT_NONE) HIPCHK(hipStreamWaitEvent(sa->q.stream, sa->q.ev_tgt, 0)); /* made beside the previous step's accept (or at least out of the buffers' way) */
+	if (sa->tgt_ahead != TGT_READY) launch_targets(sa, sa->q.stream, step_override);
+	sa->tgt_ahead = TGT_NONE;
+	return MGL_OK;
+}
+/* The full-walk kernel on the main stream; no waits, no records.  With `todo` it is the last resort of the incremental engine
+ * (a small grid strides over the list), without it the full-walk engine's whole evaluation. */
+static void nbr_fullwalk(mgl_sa* sa, uint64_t step_override, const uint32_t* todo, const uint32_t* todo_count)
+{
+	const uint32_t K = sa->cfg.neighbours_per_step, blocks = (K + sa->waves_per_block - 1) / sa->waves_per_block;
+	hipLaunchKernelGGL(k_neighbours, dim3(todo && blocks > 256u ? 256u : blocks), dim3(64 * sa->waves_per_block), sa->nbr_lds, sa->q.stream, sa->ctx, sa->base.v,
+	                   (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_bytes, todo, todo_count); NBR_TRACE("k_neighbours");
+}
+/* The first two thirds of the split form -- pick, then window walk -- of every slice, as one fused launch per slice (or as
+ * two: MGL_NO_FUSE, MGL_F_PROFILE).  Slices alternate between the main and the second stream.  Records ev_fork on the main
+ * stream, which the second stream waits for if there are two slices or more; records ev_rest[h] behind slice h's walk on
+ * its stream.  (The third stream needs no wait of its own for the fork: its first wait, ev_rest[0], is recorded on the main
+ * stream behind the fork, for any number of slices.) */
+static int nbr_pick_walk(mgl_sa* sa, uint64_t step_override, uint32_t slices)
+{
+	const uint32_t K = sa->cfg.neighbours_per_step;
+	HIPCHK(hipEventRecord(sa->q.ev_fork, sa->q.stream));
+	if (slices >= 2) HIPCHK(hipStreamWaitEvent(sa->q.stream2, sa->q.ev_fork, 0));
+	for (uint32_t h = 0; h < slices; h++) {
+		const uint32_t j0 = mgl_slice_bound(K, h, slices), j1 = mgl_slice_bound(K, h + 1, slices);
+		hipStream_t st = (h & 1u) ? sa->q.stream2 : sa->q.stream;
+		if (sa->form.fuse && !sa->d_prof) {
+			/* pick and walk of a neighbour in one wavefront: no barrier on the slice's slowest pick in front of its walks.  Under
+			 * MGL_F_PROFILE the two halves run as two launches (below): the stage marks are the pick half's */
+			launch_nbr2(sa, k_neighbours2<false, MGL_NBR_PICKWALK>, j1 - j0, 64, sa->fused_lds, st, step_override, sa->fused_lds, sa->d_todo, sa->d_counts,
+			            nullptr, sa->d_pickrec, j0, j1, (uint4*)sa->d_pick_order); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICKWALK>"); /* the order in the unused `pickstate` slot */
+		} else {
+			/* under MGL_F_PROFILE the instance that carries the stage marks (tools/pick_waves.py); normal runs hold none of them */
+			launch_nbr2(sa, sa->d_prof ? k_neighbours2<false, MGL_NBR_PICK, true> : k_neighbours2<false, MGL_NBR_PICK>, (j1 - j0 + sa->pick_waves - 1) / sa->pick_waves,
+			            64 * sa->pick_waves, sa->pick_waves * sa->per_wave_pick, st, step_override, sa->per_wave_pick, sa->d_todo, sa->d_counts, sa->d_prof,
+			            sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICK>");
+			launch_nbr2(sa, k_neighbours2<false, MGL_NBR_REST>, j1 - j0, 64, sa->per_wave_rest, st, step_override, sa->per_wave_rest, sa->d_todo, sa->d_counts,
+			            g_prof_big ? nullptr : sa->d_prof, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_REST>");
+		}
+		HIPCHK(hipEventRecord(sa->q.ev_rest[h], st));
+	}
+	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+/* The second half's re-simulation, several wavefronts per neighbour: slice h's k_sim on the third stream behind a wait for
+ * ev_rest[h], between its two timing slots (MGL_F_TIMING).  Records ev_sim behind the last one; then the main stream waits
+ * for the ev_rest of the odd slices (the walks of the other stream's slices). */
+static int nbr_sim(mgl_sa* sa, uint32_t slices)
+{
+	const uint32_t K = sa->cfg.neighbours_per_step;
+	const uint32_t sim_lds_regular = ((((sa->ctx.L.total + 31u) >> 5) + 3u) & ~3u) * 4u + sa->chg_cap * 16u;
+	hipStream_t st = sa->q.stream3;
+	for (uint32_t h = 0; h < slices; h++) {
+		const uint32_t j0 = mgl_slice_bound(K, h, slices), j1 = mgl_slice_bound(K, h + 1, slices);
+		HIPCHK(hipStreamWaitEvent(st, sa->q.ev_rest[h], 0));
+		TRY(mark(sa, T_SIM_BEGIN, st, h));
+		hipLaunchKernelGGL(sa->count_traffic ? k_sim<true> : k_sim<false>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, st, sa->ctx, sa->b2, sa->base.ctl, sa->nbr,
+		                   sa->big, j0, j1, sa->count_traffic ? sa->d_traffic : (unsigned long long*)nullptr); NBR_TRACE("k_sim");
+		TRY(mark(sa, T_SIM_END, st, h));
+	}
+	HIPCHK(hipEventRecord(sa->q.ev_sim, st));
+	for (uint32_t h = 1; h < slices; h += 2) HIPCHK(hipStreamWaitEvent(sa->q.stream, sa->q.ev_rest[h], 0));
+	return MGL_OK;
+}
+/* the one-kernel form, on the main stream; no waits, no records */
+static void nbr_one_kernel(mgl_sa* sa, uint64_t step_override)
+{
+	const uint32_t K = sa->cfg.neighbours_per_step, blocks2 = (K + sa->waves_per_block2 - 1) / sa->waves_per_block2;
+	launch_nbr2(sa, k_neighbours2<false, MGL_NBR_FULL>, blocks2, 64 * sa->waves_per_block2, sa->nbr2_lds, sa->q.stream, step_override, sa->per_wave2, sa->d_todo, sa->d_counts,
+	            sa->d_prof, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_FULL>");
+}
+/* The second pass, on the main stream behind whatever the regular form queued there; no records.  The few whose change lists
+ * overflowed LDS (or that need a second top-K pick): the whole evaluation in one kernel, lists in global scratch, a workgroup
+ * per neighbour -- one wavefront evaluates it, the others share its re-simulations */
+static void nbr_second_pass(mgl_sa* sa, uint64_t step_override, bool split_now)
+{
+	const uint32_t bigblocks = sa->big.slots < 1024u ? sa->big.slots : 1024u; /* the kernel strides over its list: none is dropped */
+	const uint32_t big_lds = 4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES; /* + a copy of both lists for the re-simulations, + the workgroup's command */
+	launch_nbr2(sa, k_neighbours2<true, MGL_NBR_FULL>, bigblocks, 64 * sa->big_waves, big_lds, sa->q.stream, step_override, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
+	            g_prof_big ? sa->d_prof : nullptr, split_now ? sa->d_pickrec : nullptr, 0u, sa->cfg.neighbours_per_step, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
+}
+/* Whatever overflowed even the second pass: exact full walk from byte 0.  It reads the second pass's list and writes the outputs
+ * of its own neighbours only, which k_sim never costs (their headers stay 0xFFFFFFFF): it is queued right behind the second
+ * pass, and the re-simulations join behind it -- the main stream waits for ev_sim. */
+static int nbr_last_resort(mgl_sa* sa, uint64_t step_override, bool split_now)
+{
+	nbr_fullwalk(sa, step_override, sa->d_todo2, sa->d_counts + 1);
+	if (split_now) HIPCHK(hipStreamWaitEvent(sa->q.stream, sa->q.ev_sim, 0));
+	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
 /* a step's neighbour evaluation: its targets, then on the incremental engine pick / walk slices on two streams, re-simulations
  * on a third, second pass, last resort */
 static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_counts = true)
 {
-	const uint32_t K = sa->cfg.neighbours_per_step;
-	if (sa->d_strat_pre) {
-		if (sa->tgt_ahead) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_tgt, 0)); /* made beside the previous step's accept (or at least out of the buffers' way) */
-		if (sa->tgt_ahead != 1) launch_targets(sa, sa->stream, step_override);
-		sa->tgt_ahead = 0;
-	}
+	TRY(nbr_targets(sa, step_override));
 	if (!sa->incremental) {
-		const uint32_t blocks = (K + sa->waves_per_block - 1) / sa->waves_per_block;
-		hipLaunchKernelGGL(k_neighbours, dim3(blocks), dim3(64 * sa->waves_per_block), sa->nbr_lds, sa->stream, sa->ctx, sa->base.v,
-		                   (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_bytes,
-		                   (const uint32_t*)nullptr, (const uint32_t*)nullptr); NBR_TRACE("k_neighbours");
+		nbr_fullwalk(sa, step_override, nullptr, nullptr);
 		HIPCHK(hipGetLastError());
 		return MGL_OK;
 	}
-	if (zero_counts) HIPCHK(hipMemsetAsync(sa->d_counts, 0, 8 * sizeof(uint32_t), sa->stream)); /* todo counts + spill slots; k_step_end clears them between steps */
-	const uint32_t blocks2 = (K + sa->waves_per_block2 - 1) / sa->waves_per_block2;
-	const bool split_now = sa->split_nbr && !sa->form_single;
-	const uint32_t sim_lds_regular = ((((sa->ctx.L.total + 31u) >> 5) + 3u) & ~3u) * 4u + sa->chg_cap * 16u;
+	if (zero_counts) HIPCHK(hipMemsetAsync(sa->d_counts, 0, 8 * sizeof(uint32_t), sa->q.stream)); /* todo counts + spill slots; k_step_end clears them between steps */
+	const bool split_now = sa->form.split_nbr && !sa->form.form_single;
 	if (split_now) {
 		/* the step's neighbours in slices on two streams: while the slowest wavefronts of one slice's kernel finish,
 		 * the other slice's kernels keep the CUs busy.  The re-simulation kernels run on a third stream: the second
 		 * pass below needs the walks, not the re-simulations, and its few long-running wavefronts overlap with them. */
 		const uint32_t slices = nbr_slices(sa);
-		HIPCHK(hipEventRecord(sa->ev_fork, sa->stream));
-		if (slices >= 2) HIPCHK(hipStreamWaitEvent(sa->stream2, sa->ev_fork, 0));
-#if !MGL_TAIL_EARLY
-		HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_fork, 0));
-#endif
-		/* (the third stream needs no wait of its own for the fork: its first wait, ev_rest[0], is recorded on the main stream
-		 * behind the fork, for any number of slices) */
-		/* the first two thirds of the split form -- pick, then window walk -- of every slice, as one fused launch per slice (or as
-		 * two: MGL_NO_FUSE, MGL_F_PROFILE); slices alternate between the two streams, ev_rest[h] is recorded behind slice h's walk */
-		for (uint32_t h = 0; h < slices; h++) {
-			const uint32_t j0 = mgl_slice_bound(K, h, slices), j1 = mgl_slice_bound(K, h + 1, slices);
-			hipStream_t st = (h & 1u) ? sa->stream2 : sa->stream;
-			if (sa->fuse && !sa->d_prof) {
-				/* pick and walk of a neighbour in one wavefront: no barrier on the slice's slowest pick in front of its walks.  Under
-				 * MGL_F_PROFILE the two halves run as two launches (below): the stage marks are the pick half's */
-				hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_PICKWALK>), dim3(j1 - j0), dim3(64), sa->fused_lds, st, sa->ctx,
-				                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->fused_lds, sa->d_todo, sa->d_counts,
-				                   (unsigned long long*)nullptr, sa->big, sa->d_pickrec, j0, j1, (uint4*)sa->d_pick_order); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICKWALK>"); /* the order in the unused `pickstate` slot */
-				HIPCHK(hipEventRecord(sa->ev_rest[h], st));
-				continue;
-			}
-			/* under MGL_F_PROFILE the instance that carries the stage marks (tools/pick_waves.py); normal runs hold none of them */
-			hipLaunchKernelGGL((sa->d_prof ? k_neighbours2<false, MGL_NBR_PICK, true> : k_neighbours2<false, MGL_NBR_PICK>), dim3((j1 - j0 + sa->pick_waves - 1) / sa->pick_waves), dim3(64 * sa->pick_waves),
-			                   (MGL_PICK_T_GLOBAL ? 0u : 4096u) + sa->pick_waves * sa->per_wave_pick, st, sa->ctx,
-			                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_pick, sa->d_todo, sa->d_counts,
-			                   sa->d_prof, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICK>");
-			hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_REST>), dim3(j1 - j0), dim3(64), sa->per_wave_rest, st, sa->ctx,
-			                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_rest, sa->d_todo, sa->d_counts,
-			                   g_prof_big ? (unsigned long long*)nullptr : sa->d_prof, sa->big, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_REST>");
-			HIPCHK(hipEventRecord(sa->ev_rest[h], st));
-		}
-		HIPCHK(hipGetLastError());
-		for (uint32_t h = 0; h < slices; h++) {
-			const uint32_t j0 = mgl_slice_bound(K, h, slices), j1 = mgl_slice_bound(K, h + 1, slices);
-			/* the second half's re-simulation, several wavefronts per neighbour */
-			HIPCHK(hipStreamWaitEvent(sa->stream3, sa->ev_rest[h], 0));
-			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 4 * (size_t)sa->time_sim_step + 2 * h), sa->stream3));
-			if (sa->count_traffic)
-				hipLaunchKernelGGL(k_sim<true>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, sa->stream3, sa->ctx, sa->b2, sa->base.ctl,
-				                   sa->nbr, sa->big, j0, j1, sa->d_traffic);
-			else
-				hipLaunchKernelGGL(k_sim<false>, dim3(j1 - j0), dim3(64 * sa->sim_waves), sim_lds_regular, sa->stream3, sa->ctx, sa->b2, sa->base.ctl,
-				                   sa->nbr, sa->big, j0, j1, (unsigned long long*)nullptr);
-			NBR_TRACE("k_sim");
-			if (sa->time_sim_step >= 0 && h < 2) HIPCHK(hipEventRecord(sim_event(sa, 4 * (size_t)sa->time_sim_step + 2 * h + 1), sa->stream3));
-		}
-		HIPCHK(hipEventRecord(sa->ev_sim, sa->stream3));
-		for (uint32_t h = 1; h < slices; h += 2) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_rest[h], 0)); /* the walks of the other stream's slices */
+		TRY(nbr_pick_walk(sa, step_override, slices));
+		TRY(nbr_sim(sa, slices));
+	} else {
+		nbr_one_kernel(sa, step_override);
 	}
-	if (!sa->split_nbr || sa->form_single) { /* the one-kernel form */
-		hipLaunchKernelGGL((k_neighbours2<false, MGL_NBR_FULL>), dim3(blocks2), dim3(64 * sa->waves_per_block2), sa->nbr2_lds, sa->stream, sa->ctx,
-		                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo, sa->d_counts,
-		                   sa->d_prof, sa->big, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_FULL>");
-	}
-	/* the few whose change lists overflowed LDS (or that need a second top-K pick): the whole evaluation in one kernel,
-	 * lists in global scratch, a workgroup per neighbour -- one wavefront evaluates it, the others share its re-simulations */
-	const uint32_t bigblocks = sa->big.slots < 1024u ? sa->big.slots : 1024u; /* the kernel strides over its list: none is dropped */
-	const uint32_t big_lds = 4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES; /* + a copy of both lists for the re-simulations, + the workgroup's command */
-	hipLaunchKernelGGL((k_neighbours2<true, MGL_NBR_FULL>), dim3(bigblocks), dim3(64 * sa->big_waves), big_lds, sa->stream, sa->ctx,
-	                   sa->b2, sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
-	                   g_prof_big ? sa->d_prof : (unsigned long long*)nullptr, sa->big, split_now ? sa->d_pickrec : (uint4*)nullptr, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
-#if !MGL_TAIL_EARLY
-	if (split_now) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_sim, 0));
-#endif
-	/* and whatever overflowed even that: exact full walk from byte 0 (a small grid strides over the list).  It reads the second
-	 * pass's list and writes the outputs of its own neighbours only, which k_sim never costs (their headers stay 0xFFFFFFFF):
-	 * it is queued right behind the second pass, and the re-simulations join behind it */
-	const uint32_t blocks = (K + sa->waves_per_block - 1) / sa->waves_per_block;
-	hipLaunchKernelGGL(k_neighbours, dim3(blocks < 256u ? blocks : 256u), dim3(64 * sa->waves_per_block), sa->nbr_lds, sa->stream, sa->ctx, sa->base.v,
-	                   (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->nbr, sa->per_wave_bytes,
-	                   (const uint32_t*)sa->d_todo2, (const uint32_t*)(sa->d_counts + 1)); NBR_TRACE("k_neighbours");
-#if MGL_TAIL_EARLY
-	if (split_now) HIPCHK(hipStreamWaitEvent(sa->stream, sa->ev_sim, 0));
-#endif
-	HIPCHK(hipGetLastError());
-	return MGL_OK;
+	nbr_second_pass(sa, step_override, split_now);
+	return nbr_last_resort(sa, step_override, split_now);
 }
 
 static int import_slab(mgl_sa* sa, const mgl_packet* packets, mgl_pk* d_slab)
 {
-	HIPCHK(hipMemcpyAsync(sa->d_aos, packets, sizeof(mgl_packet) * (size_t)sa->n, hipMemcpyHostToDevice, sa->stream));
-	hipLaunchKernelGGL(k_import, dim3(1024), dim3(256), 0, sa->stream, (const uint32_t*)sa->d_aos, d_slab, sa->n);
+	HIPCHK(hipMemcpyAsync(sa->d_aos, packets, sizeof(mgl_packet) * (size_t)sa->n, hipMemcpyHostToDevice, sa->q.stream));
+	hipLaunchKernelGGL(k_import, dim3(1024), dim3(256), 0, sa->q.stream, (const uint32_t*)sa->d_aos, d_slab, sa->n);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
 static int export_slab(mgl_sa* sa, const mgl_pk* d_slab, mgl_packet* packets)
 {
-	hipLaunchKernelGGL(k_export, dim3(1024), dim3(256), 0, sa->stream, d_slab, sa->d_aos, sa->n);
+	hipLaunchKernelGGL(k_export, dim3(1024), dim3(256), 0, sa->q.stream, d_slab, sa->d_aos, sa->n);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(packets, sa->d_aos, sizeof(mgl_packet) * (size_t)sa->n, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(packets, sa->d_aos, sizeof(mgl_packet) * (size_t)sa->n, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -593,27 +665,45 @@ extern "C" void mgl_sa_destroy(mgl_sa* sa)
 {
 	if (!sa) return;
 	(void)hipSetDevice(sa->device);
-	if (sa->stream) (void)hipStreamSynchronize(sa->stream);
+	if (sa->q.stream) (void)hipStreamSynchronize(sa->q.stream);
 	delete sa; /* sa->own releases everything the handle made */
 }
 
 /* ---- mgl_sa_create in stages: create_impl calls them in the order they stand in.  Everything is made through sa->own, so a
  * stage that fails leaves nothing to undo: mgl_sa_create destroys the handle. */
-static int create_streams(mgl_sa* sa, size_t n)
+/* every environment switch of a handle, for an input of n bytes (EnvSwitches says what each one is) */
+static void read_env(EnvSwitches& e, size_t n)
+{
+	const auto set = [](const char* name) { return getenv(name) != nullptr; };
+	const auto num = [](const char* name) { return getenv(name) ? atoi(getenv(name)) : 0; };
+	/* measured: + 8 % on the 10 MB input, nothing on the 100 KB one (its kernels are too short to overlap) */
+	e.halves = set("MGL_HALVES") ? (uint32_t)num("MGL_HALVES") : (n > (1u << 20) ? 2u : 1u);
+	if (e.halves < 1 || e.halves > 8) e.halves = 1;
+	/* (tests): 512- and 1 024-position blocks on small inputs.  Nothing outside 8..10 is taken: the builder's LDS arrays hold
+	 * MGL_PB_MAX_BLOCK positions, and a block is whole bitmap words (shift - 6) */
+	const int s = num("MGL_SB_SHIFT"), w = num("MGL_SIMW"), pw = num("MGL_PICK_WAVES");
+	e.sb_shift = s >= 8 && s <= (int)MGL_PB_MAX_SHIFT ? (uint32_t)s : 0u;
+	e.no_incremental_apply = set("MGL_NO_INCREMENTAL_APPLY"); e.no_batch = set("MGL_NO_BATCH"); e.no_evcancel = set("MGL_NO_EVCANCEL");
+	e.no_split = set("MGL_NO_SPLIT"); e.no_cont = set("MGL_NO_CONT"); e.no_fuse = set("MGL_NO_FUSE");
+	e.no_adapt = set("MGL_NO_ADAPT"); e.no_order = set("MGL_NO_ORDER");
+	e.simw = w == 1 || w == 2 || w == 4 || w == 8 ? (uint32_t)w : 0u;
+	e.pick_waves = pw == 1 || pw == 2 || pw == 4 || pw == 8 ? (uint32_t)pw : 0u;
+	e.bulk_threshold = set("MGL_BULK_THRESHOLD") ? (uint32_t)num("MGL_BULK_THRESHOLD") : 0u;
+	if (set("MGL_BULK_THRESHOLD") && e.bulk_threshold == 0) e.bulk_threshold = 1;
+}
+static int create_streams(mgl_sa* sa)
 {
 	DevOwner& own = sa->own;
-	HIPCHK(own.stream(&sa->stream));
-	HIPCHK(own.stream(&sa->stream2));
-	for (hipEvent_t* e : { &sa->ev_fork, &sa->ev_join, &sa->ev_tgt, &sa->ev_tgt_go }) HIPCHK(own.event(e, hipEventDisableTiming));
-	HIPCHK(own.stream(&sa->stream3));
-	for (auto& e : sa->ev_rest) HIPCHK(own.event(&e, hipEventDisableTiming));
-	HIPCHK(own.event(&sa->ev_sim, hipEventDisableTiming));
-	HIPCHK(own.event(&sa->ev_val, hipEventDisableTiming));
-	/* measured: + 8 % on the 10 MB input, nothing on the 100 KB one (its kernels are too short to overlap) */
-	sa->halves = getenv("MGL_HALVES") ? (uint32_t)atoi(getenv("MGL_HALVES")) : (n > (1u << 20) ? 2u : 1u);
-	if (sa->halves < 1 || sa->halves > 8) sa->halves = 1;
-	HIPCHK(own.event(&sa->ev_begin));
-	HIPCHK(own.event(&sa->ev_end));
+	HIPCHK(own.stream(&sa->q.stream));
+	HIPCHK(own.stream(&sa->q.stream2));
+	for (hipEvent_t* e : { &sa->q.ev_fork, &sa->q.ev_join, &sa->q.ev_tgt, &sa->q.ev_tgt_go }) HIPCHK(own.event(e, hipEventDisableTiming));
+	HIPCHK(own.stream(&sa->q.stream3));
+	for (auto& e : sa->q.ev_rest) HIPCHK(own.event(&e, hipEventDisableTiming));
+	HIPCHK(own.event(&sa->q.ev_sim, hipEventDisableTiming));
+	HIPCHK(own.event(&sa->q.ev_val, hipEventDisableTiming));
+	sa->halves = sa->env.halves;
+	HIPCHK(own.event(&sa->timer.ev_begin));
+	HIPCHK(own.event(&sa->timer.ev_end));
 	return MGL_OK;
 }
 
@@ -650,7 +740,7 @@ static int build_match_index(mgl_sa* sa, size_t n)
 		return MGL_OK;
 	}
 	const uint8_t* data = sa->d_data;
-	hipStream_t st = sa->stream;
+	hipStream_t st = sa->q.stream;
 	const uint32_t nblk = (m + MGL_IX_ITEMS - 1) / MGL_IX_ITEMS;
 	const dim3 per_pos(m / 256 + 1);
 	DevOwner scratch; /* gone when the index stands, and when a step fails */
@@ -788,12 +878,7 @@ static int create_engine(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 	b.pool_cap = (uint32_t)(24 * n + (size_t)sa->ctx.L.total * 272 + 4096);
 	/* chain index: one entry per context and block of the parallel builder (the builder's per-block counts are its source) */
 	b.sb_shift = n <= (1u << 20) ? 8u : n <= (1u << 23) ? 9u : MGL_PB_MAX_SHIFT;
-	/* MGL_SB_SHIFT (tests): 512- and 1 024-position blocks on small inputs.  Nothing outside 8..10 is taken: the builder's
-	 * LDS arrays hold MGL_PB_MAX_BLOCK positions, and a block is whole bitmap words (shift - 6) */
-	if (getenv("MGL_SB_SHIFT")) {
-		const int s = atoi(getenv("MGL_SB_SHIFT"));
-		if (s >= 8 && s <= (int)MGL_PB_MAX_SHIFT) b.sb_shift = (uint32_t)s;
-	}
+	if (sa->env.sb_shift) b.sb_shift = sa->env.sb_shift;
 	b.nsb = (uint32_t)((n + (1u << b.sb_shift) - 1) >> b.sb_shift);
 	b.sb_stride = (b.nsb + 2u + 3u) & ~3u;
 	TRY(alloc_b2(own, b, n, false, true, &sa->b2_bytes));
@@ -816,7 +901,7 @@ static int create_engine(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 static int alloc_accept_buffers(mgl_sa* sa)
 {
 	DevOwner& own = sa->own;
-	sa->incremental_apply = getenv("MGL_NO_INCREMENTAL_APPLY") == nullptr;
+	sa->incremental_apply = !sa->env.no_incremental_apply;
 	ApplyBuf& ab = sa->ab;
 	memset(&ab, 0, sizeof ab);
 	/* one workgroup per touched context plans the rewrite; the copies run as job lists */
@@ -861,8 +946,8 @@ static int alloc_accept_buffers(mgl_sa* sa)
 	TRY(dnew(own, bt.bk_rcl, MGL_BATCH_ALLOC));
 	TRY(dnew(own, bt.acc, 4, 0));
 	HIPCHK(own.pinned((void**)&sa->h_bstat, sizeof(uint32_t) * 16));
-	HIPCHK(own.event(&sa->ev_bstat, hipEventDisableTiming));
-	sa->batch_ok = sa->incremental_apply && getenv("MGL_NO_BATCH") == nullptr;
+	HIPCHK(own.event(&sa->q.ev_bstat, hipEventDisableTiming));
+	sa->batch_ok = sa->incremental_apply && !sa->env.no_batch;
 	uint32_t* why = nullptr;
 	TRY(dnew(own, why, 1, 0));
 	accept_limits_init(sa, why);
@@ -891,17 +976,17 @@ static int alloc_nbr_scratch(mgl_sa* sa, uint32_t ckpt_elems)
 	TRY(dnew(own, sa->d_todo2, K + 1, 0));
 	TRY(dnew(own, sa->d_counts, 16, 0)); /* [0..7] live, [8..15] the last finished step's */
 	g.todo_in = sa->d_todo; g.todo_in_count = sa->d_counts; g.spill_ctr = sa->d_counts + 2;
-	g.evcancel = getenv("MGL_NO_EVCANCEL") == nullptr ? 1u : 0u; /* the window walk lists a re-coded packet's changed events only; MGL_NO_EVCANCEL=1: all of them */
+	g.evcancel = sa->env.no_evcancel ? 0u : 1u; /* the window walk lists a re-coded packet's changed events only; MGL_NO_EVCANCEL=1: all of them */
 	TRY(dnew(own, sa->d_pickrec, K));
 	TRY(dnew(own, sa->d_pickstate, 2 * K));
-	sa->split_nbr = getenv("MGL_NO_SPLIT") == nullptr;
-	if (sa->split_nbr) {
+	sa->form.split_nbr = !sa->env.no_split;
+	if (sa->form.split_nbr) {
 		/* the second half's re-simulation as its own launch (k_sim): lists and headers per neighbour */
 		TRY(dnew(own, g.sim_hdr, K, 0xFF));
 		TRY(dnew(own, g.sim_keys, 2u * sa->chg_cap * K));
 		TRY(dnew(own, g.sim_pos, 2u * sa->chg_cap * K));
 		/* continuation records: the second half saves a walk that stops at a repair pick, the second pass resumes it */
-		if (getenv("MGL_NO_CONT") == nullptr) TRY(dnew(own, g.cont, MGL_CONT_WORDS * slots, 0));
+		if (!sa->env.no_cont) TRY(dnew(own, g.cont, MGL_CONT_WORDS * slots, 0));
 	}
 	return dnew(own, sa->d_traffic, 2, 0);
 }
@@ -911,7 +996,7 @@ static int alloc_nbr_scratch(mgl_sa* sa, uint32_t ckpt_elems)
  * journal} */
 static int set_launch_geometry(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 {
-	const uint32_t cu_lds = 160u * 1024u, pick_tbl = MGL_PICK_T_GLOBAL ? 0u : 4096u;
+	const uint32_t cu_lds = 160u * 1024u;
 	sa->per_wave_bytes = ckpt_elems * 2u + MGL_PRICE_WORDS * 4u + MGL_MAX_DIFFS * (8u + 8u + 4u);
 	sa->waves_per_block = 4;
 	while (sa->waves_per_block > 1 && 4096u + sa->waves_per_block * sa->per_wave_bytes > cu_lds) sa->waves_per_block--;
@@ -934,7 +1019,7 @@ static int set_launch_geometry(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 	sa->waves_per_block2 = 1;
 	sa->nbr2_lds = 4096u + sa->waves_per_block2 * sa->per_wave2;
 	sa->build_lds = 4096u + ckpt_elems * 2u + ckpt_elems * 8u;
-	sa->fused_lds = pick_tbl + (sa->per_wave_pick > sa->per_wave_rest ? sa->per_wave_pick : sa->per_wave_rest);
+	sa->fused_lds = (sa->per_wave_pick > sa->per_wave_rest ? sa->per_wave_pick : sa->per_wave_rest);
 	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_FULL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr2_lds));
 	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cu_lds));
 	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours2<false, MGL_NBR_PICK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cu_lds));
@@ -946,27 +1031,26 @@ static int set_launch_geometry(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 	HIPCHK(hipFuncSetAttribute((const void*)k_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->build_lds));
 	HIPCHK(hipFuncSetAttribute((const void*)k_build_end, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->build_lds));
 
-	sa->fuse = getenv("MGL_NO_FUSE") == nullptr;
-	if (getenv("MGL_SIMW")) { const int w = atoi(getenv("MGL_SIMW")); if (w == 1 || w == 2 || w == 4 || w == 8) sa->sim_waves = (uint32_t)w; }
-	sa->adaptive = sa->split_nbr && getenv("MGL_NO_ADAPT") == nullptr;
-	sa->form_single = !sa->split_nbr; /* one-kernel form only, or the split form until the device recommends otherwise */
+	sa->form.fuse = !sa->env.no_fuse;
+	if (sa->env.simw) sa->sim_waves = sa->env.simw;
+	sa->form.adaptive = sa->form.split_nbr && !sa->env.no_adapt;
+	sa->form.form_single = !sa->form.split_nbr; /* one-kernel form only, or the split form until the device recommends otherwise */
 	/* eight pick wavefronts share a cost table per workgroup: 4 KiB + 8 x 9.3 KiB = 78 KiB, two
 	 * workgroups = 16 wavefronts per CU, so the 4 096 neighbours of a c2 step are all resident at
 	 * once (with two per workgroup 14 fit and the last 512 waited for a slot: 127 -> 108 us).
 	 * Above 1 MiB top-K run times vary too much for wavefronts to hold each other's LDS: one per
 	 * workgroup there (c3, first 200 steps: 3.04 ms per step against 3.26 with eight) */
-	sa->pick_waves = getenv("MGL_PICK_WAVES") ? (uint32_t)atoi(getenv("MGL_PICK_WAVES")) : 0u;
-	if (sa->pick_waves != 1 && sa->pick_waves != 2 && sa->pick_waves != 4 && sa->pick_waves != 8) sa->pick_waves = 0;
+	sa->pick_waves = sa->env.pick_waves;
 	/* the workgroup size that puts most wavefronts on a CU's 160 KiB (larger models -- lc > 0 -- fit fewer) */
 	uint32_t best_w = 1, best_resident = 0;
 	for (uint32_t w = 1; w <= 8; w *= 2) {
-		const uint32_t bytes = pick_tbl + w * sa->per_wave_pick;
+		const uint32_t bytes = w * sa->per_wave_pick;
 		if (bytes > cu_lds) break;
 		const uint32_t resident = (cu_lds / ((bytes + 1279u) / 1280u * 1280u)) * w;
 		if (resident > best_resident) { best_resident = resident; best_w = w; }
 	}
 	if (n > (1u << 20)) best_w = 1;
-	if (sa->pick_waves == 0 || pick_tbl + sa->pick_waves * sa->per_wave_pick > cu_lds) sa->pick_waves = best_w;
+	if (sa->pick_waves == 0 || sa->pick_waves * sa->per_wave_pick > cu_lds) sa->pick_waves = best_w;
 	return MGL_OK;
 }
 
@@ -982,7 +1066,7 @@ static int create_targets(mgl_sa* sa, size_t n)
 		TRY(dnew(own, sa->d_strat_tgt, K));
 		sa->ctx.strat_tgt = sa->d_strat_tgt;
 		/* the fused launch takes up its picking neighbours first; MGL_NO_ORDER=1: in blockIdx order */
-		if (sa->incremental && sa->split_nbr && getenv("MGL_NO_ORDER") == nullptr) {
+		if (sa->incremental && sa->form.split_nbr && !sa->env.no_order) {
 			TRY(dnew(own, sa->d_pick_hint, K, 1));
 			TRY(dnew(own, sa->d_pick_order, K));
 		}
@@ -991,22 +1075,20 @@ static int create_targets(mgl_sa* sa, size_t n)
 	/* a bulk step costs a parallel rebuild (about 3 single steps at 100 KB, 6 at 10 MB, 20 at 100 MB) */
 	/* ... unless the step takes few moves: those are patched in at once (mgl_kernels5.hip) for about half a single step's time, so a bulk
 	 * step pays as soon as it can be expected to take two moves */
-	sa->bulk_threshold = getenv("MGL_BULK_THRESHOLD") ? (uint32_t)atoi(getenv("MGL_BULK_THRESHOLD"))
-	                     : sa->batch_ok ? 2u : (n <= (1u << 20) ? 16u : n <= (1u << 24) ? 32u : 128u);
-	if (sa->bulk_threshold == 0) sa->bulk_threshold = 1;
+	sa->bulk_threshold = sa->env.bulk_threshold ? sa->env.bulk_threshold : sa->batch_ok ? 2u : (n <= (1u << 20) ? 16u : n <= (1u << 24) ? 32u : 128u);
 	return MGL_OK;
 }
 
 /* packet_slab_new: all-literal current and best slabs, the base built on them and checked */
 static int first_build(mgl_sa* sa, size_t n)
 {
-	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->base.v.slab, sa->ctx.n);
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, sa->base.v.slab, sa->ctx.n);
 	if (!sa->d_best) TRY(dnew(sa->own, sa->d_best, n)); /* (with snapshots it is the best snapshot's slab) */
-	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->d_best, sa->ctx.n);
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, sa->d_best, sa->ctx.n);
 	HIPCHK(hipGetLastError());
 	TRY(rebuild_base(sa, 0));
 	if (sa->incremental && sa->snapshots) TRY(launch_snapshot(sa, sa->snap_lit, 0, 0, 0));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	/* an input the structures were not sized for shows here, not steps later inside mgl_sa_run */
 	Control c0;
 	HIPCHK(hipMemcpy(&c0, sa->base.ctl, sizeof c0, hipMemcpyDeviceToHost));
@@ -1017,7 +1099,8 @@ static int first_build(mgl_sa* sa, size_t n)
 static int create_impl(mgl_sa* sa, const uint8_t* data, size_t n)
 {
 	HIPCHK(hipSetDevice(sa->device));
-	TRY(create_streams(sa, n));
+	read_env(sa->env, n);
+	TRY(create_streams(sa));
 	const mgl_layout L = mgl_make_layout(sa->props.lc, sa->props.lp, sa->props.pb);
 	const uint32_t ckpt_elems = (L.total + 7u) & ~7u;
 	/* input, zero padded so that window loads past the end stay in bounds */
@@ -1072,14 +1155,14 @@ extern "C" mgl_sa* mgl_sa_create(const uint8_t* data, size_t n, mgl_properties p
 
 static int read_ctl(mgl_sa* sa, BaseMem& b, Control* out)
 {
-	HIPCHK(hipMemcpyAsync(out, b.ctl, sizeof(Control), hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(out, b.ctl, sizeof(Control), hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 static int write_ctl(mgl_sa* sa, BaseMem& b, const Control* in)
 {
-	HIPCHK(hipMemcpyAsync(b.ctl, in, sizeof(Control), hipMemcpyHostToDevice, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(b.ctl, in, sizeof(Control), hipMemcpyHostToDevice, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -1093,8 +1176,6 @@ static int keep_best_before_overwrite(mgl_sa* sa, Control& c)
 	return MGL_OK;
 }
 
-/* MGL_ACCEPT_AUTO starts over: a fresh block, bulk steps first (a new slab says nothing about the old one's windows) */
-static void auto_reset(mgl_sa* sa) { sa->bulk_now = true; sa->bulk_hold = 0; sa->blk_done = 0; sa->select_small = false; }
 
 /* The base has just been rebuilt on a new current slab: the walk's verdict on it, after checking every packet against the
  * input too if `validate`.  A slab that fails is `bad` in the name of `who`; *cost (nullable) = its exact cost. */
@@ -1117,19 +1198,19 @@ static int current_to_literal(mgl_sa* sa)
 	const bool snaps = sa->incremental && sa->snapshots;
 	if (snaps) {
 		SnapMeta meta;
-		HIPCHK(hipMemcpyAsync(&meta, sa->d_snap_meta, sizeof meta, hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipStreamSynchronize(sa->stream));
+		HIPCHK(hipMemcpyAsync(&meta, sa->d_snap_meta, sizeof meta, hipMemcpyDeviceToHost, sa->q.stream));
+		HIPCHK(hipStreamSynchronize(sa->q.stream));
 		if (meta.valid) {
 			if ((rc = launch_snapshot(sa, sa->snap_lit, 0u, 1, 0))) return rc;
-			HIPCHK(hipStreamSynchronize(sa->stream));
+			HIPCHK(hipStreamSynchronize(sa->q.stream));
 			return MGL_OK;
 		}
 	}
-	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->base.v.slab, sa->ctx.n);
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, sa->base.v.slab, sa->ctx.n);
 	HIPCHK(hipGetLastError());
 	if ((rc = rebuild_base(sa, 0))) return rc;
 	if (snaps && (rc = launch_snapshot(sa, sa->snap_lit, 0u, 0, 0))) return rc;
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -1147,12 +1228,12 @@ static int recover_from_refusal(mgl_sa* sa, bool forget_best)
 	if (forget_best) {
 		c.best_cost = 0; c.best_is_current = 0;
 		sa->best_unverified = false;
-		hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, sa->d_best, sa->ctx.n);
+		hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, sa->d_best, sa->ctx.n);
 		HIPCHK(hipGetLastError());
-		if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->stream));
+		if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->q.stream));
 	}
 	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
-	auto_reset(sa);
+	sa->autoacc.reset();
 	if ((rc = current_to_literal(sa))) return rc;
 	g_err = keep;
 	return MGL_OK;
@@ -1169,7 +1250,7 @@ static int replace_current(mgl_sa* sa, Put put, bool validate, int bad, const ch
 	int rc = read_ctl(sa, sa->base, &c);
 	if (rc) return rc;
 	if ((rc = keep_best_before_overwrite(sa, c))) return rc;
-	auto_reset(sa);
+	sa->autoacc.reset();
 	if ((rc = put())) return rc;
 	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
 	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
@@ -1185,7 +1266,7 @@ static int replace_current(mgl_sa* sa, Put put, bool validate, int bad, const ch
 static auto put_slab(mgl_sa* sa, const mgl_pk* slab)
 {
 	return [=]() -> int {
-		HIPCHK(hipMemcpyAsync(sa->base.v.slab, slab, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->stream));
+		HIPCHK(hipMemcpyAsync(sa->base.v.slab, slab, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
 		return MGL_OK;
 	};
 }
@@ -1205,21 +1286,21 @@ extern "C" int mgl_sa_begin_epoch(mgl_sa* sa, unsigned phase, int from_best)
 	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
 	/* MGL_ACCEPT_AUTO starts every epoch the same way, whatever the previous one left behind: a fresh block, bulk steps
 	 * first from the all-literal slab (thousands of improving neighbours), single steps first from the best slab */
-	auto_reset(sa);
-	sa->bulk_now = !from_best;
+	sa->autoacc.reset();
+	sa->autoacc.bulk_now = !from_best;
 	if (from_best && base_is_best) return MGL_OK; /* main.c:73-76 would copy packets_best over itself */
 	if (!from_best) return current_to_literal(sa);
 	if (snaps) {
 		SnapMeta meta;
-		HIPCHK(hipMemcpyAsync(&meta, sa->d_snap_meta + 1, sizeof meta, hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipStreamSynchronize(sa->stream));
+		HIPCHK(hipMemcpyAsync(&meta, sa->d_snap_meta + 1, sizeof meta, hipMemcpyDeviceToHost, sa->q.stream));
+		HIPCHK(hipStreamSynchronize(sa->q.stream));
 		if (meta.valid) {
 			if ((rc = launch_snapshot(sa, sa->snap_best, 1u, 1, 0))) return rc;
-			HIPCHK(hipStreamSynchronize(sa->stream));
+			HIPCHK(hipStreamSynchronize(sa->q.stream));
 			return MGL_OK;
 		}
 	}
-	HIPCHK(hipMemcpyAsync(sa->base.v.slab, sa->d_best, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(sa->base.v.slab, sa->d_best, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
 	if ((rc = rebuild_base(sa, 0))) return rc;
 	if (sa->best_unverified) {
 		/* a best slab that came from outside (another chain, mgl_sa_set_best) is checked here, where it first matters:
@@ -1230,14 +1311,14 @@ extern "C" int mgl_sa_begin_epoch(mgl_sa* sa, unsigned phase, int from_best)
 		if (v.error_flags || v.rebuild_cost != v.best_cost) {
 			(void)fail(MGL_EINVAL, "mgl_sa_begin_epoch: the adopted best slab is not a valid parse of the input at the cost it came with");
 			if ((rc = recover_from_refusal(sa, true))) return rc;
-			sa->bulk_now = true; /* the epoch starts from the all-literal slab after all */
+			sa->autoacc.bulk_now = true; /* the epoch starts from the all-literal slab after all */
 			return MGL_EINVAL;
 		}
 		sa->best_unverified = false;
 	}
 	/* the base now is the best slab's: keep it for the next epoch */
 	if (snaps && (rc = launch_snapshot(sa, sa->snap_best, 1u, 0, 0))) return rc;
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -1262,7 +1343,7 @@ extern "C" int mgl_sa_seed_greedy(mgl_sa* sa, uint32_t candidates)
 	if (candidates == 0) return fail(MGL_EINVAL, "mgl_sa_seed_greedy: candidates must be > 0");
 	HIPCHK(hipSetDevice(sa->device));
 	const auto put = [=]() -> int {
-		hipLaunchKernelGGL(k_greedy_seed, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, sa->base.v.slab, candidates);
+		hipLaunchKernelGGL(k_greedy_seed, dim3((sa->ctx.n + 255u) / 256u), dim3(256), 0, sa->q.stream, sa->ctx, sa->base.v.slab, candidates);
 		HIPCHK(hipGetLastError());
 		return MGL_OK;
 	};
@@ -1299,9 +1380,9 @@ static int opt_alloc(mgl_sa* sa, OptBufs& o, uint32_t chunk, bool seed)
 static int opt_prices(mgl_sa* sa, OptBufs& o, const mgl_pk* slab)
 {
 	const uint32_t total = sa->ctx.L.total;
-	HIPCHK(hipMemsetAsync(o.counts, 0, sizeof(uint32_t) * 2 * total, sa->stream));
-	hipLaunchKernelGGL(k_opt_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, slab, (mgl_pk*)nullptr, o.counts, 0, 1u, (uint32_t*)nullptr);
-	hipLaunchKernelGGL(k_opt_prices, dim3((total + 255) / 256), dim3(256), 0, sa->stream, (const uint32_t*)o.counts, sa->ctx.cost_tbl, total, o.prices);
+	HIPCHK(hipMemsetAsync(o.counts, 0, sizeof(uint32_t) * 2 * total, sa->q.stream));
+	hipLaunchKernelGGL(k_opt_walk, dim3(1), dim3(64), 0, sa->q.stream, sa->ctx, slab, (mgl_pk*)nullptr, o.counts, 0, 1u, (uint32_t*)nullptr);
+	hipLaunchKernelGGL(k_opt_prices, dim3((total + 255) / 256), dim3(256), 0, sa->q.stream, (const uint32_t*)o.counts, sa->ctx.cost_tbl, total, o.prices);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -1327,28 +1408,28 @@ static int mf_ensure(mgl_sa* sa, uint32_t depth)
 	HIPCHK(t.own.event(&t.t0));
 	HIPCHK(t.own.event(&t.t1));
 	const dim3 g_direct(n / 256u + 1u); /* n + 1 lanes: off[n] */
-	HIPCHK(hipEventRecord(t.t0, sa->stream));
-	HIPCHK(hipMemsetAsync(t.qcount, 0, sizeof(uint32_t), sa->stream));
-	hipLaunchKernelGGL(k_mf_direct<false>, g_direct, dim3(256), 0, sa->stream, sa->ctx, sa->d_mf_off, (uint32_t*)nullptr, (uint16_t*)nullptr, t.queue, t.qcount);
+	HIPCHK(hipEventRecord(t.t0, sa->q.stream));
+	HIPCHK(hipMemsetAsync(t.qcount, 0, sizeof(uint32_t), sa->q.stream));
+	hipLaunchKernelGGL(k_mf_direct<false>, g_direct, dim3(256), 0, sa->q.stream, sa->ctx, sa->d_mf_off, (uint32_t*)nullptr, (uint16_t*)nullptr, t.queue, t.qcount);
 	uint32_t queued = 0;
-	HIPCHK(hipMemcpyAsync(&queued, t.qcount, sizeof queued, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(&queued, t.qcount, sizeof queued, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	if (queued > n) return fail(MGL_EDEVICE, "match finder: the scan queue overran");
 	const dim3 g_scan((queued + 3u) / 4u);
-	if (queued) hipLaunchKernelGGL(k_mf_scan<false>, g_scan, dim3(256), 0, sa->stream, sa->ctx, depth, sa->d_mf_off, (uint32_t*)nullptr, (uint16_t*)nullptr,
+	if (queued) hipLaunchKernelGGL(k_mf_scan<false>, g_scan, dim3(256), 0, sa->q.stream, sa->ctx, depth, sa->d_mf_off, (uint32_t*)nullptr, (uint16_t*)nullptr,
 	                               (const uint4*)t.queue, (const uint32_t*)t.qcount);
-	hipLaunchKernelGGL(ix_scan, dim3(1), dim3(1024), 0, sa->stream, sa->d_mf_off, n + 1u);
+	hipLaunchKernelGGL(ix_scan, dim3(1), dim3(1024), 0, sa->q.stream, sa->d_mf_off, n + 1u);
 	uint32_t total = 0;
-	HIPCHK(hipMemcpyAsync(&total, sa->d_mf_off + n, sizeof total, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(&total, sa->d_mf_off + n, sizeof total, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	if ((uint64_t)total > (uint64_t)MGL_MF_MAX_ENTRIES * n) return fail(MGL_EDEVICE, "match finder: the list lengths do not add up");
 	TRY(dnew(sa->own, sa->d_mf_src, (size_t)total + 1));
 	TRY(dnew(sa->own, sa->d_mf_len, (size_t)total + 1));
-	hipLaunchKernelGGL(k_mf_direct<true>, g_direct, dim3(256), 0, sa->stream, sa->ctx, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len, t.queue, t.qcount);
-	if (queued) hipLaunchKernelGGL(k_mf_scan<true>, g_scan, dim3(256), 0, sa->stream, sa->ctx, depth, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len,
+	hipLaunchKernelGGL(k_mf_direct<true>, g_direct, dim3(256), 0, sa->q.stream, sa->ctx, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len, t.queue, t.qcount);
+	if (queued) hipLaunchKernelGGL(k_mf_scan<true>, g_scan, dim3(256), 0, sa->q.stream, sa->ctx, depth, sa->d_mf_off, sa->d_mf_src, sa->d_mf_len,
 	                               (const uint4*)t.queue, (const uint32_t*)t.qcount);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(t.t1, sa->stream));
+	HIPCHK(hipEventRecord(t.t1, sa->q.stream));
 	HIPCHK(hipEventSynchronize(t.t1));
 	float ms = 0;
 	HIPCHK(hipEventElapsedTime(&ms, t.t0, t.t1));
@@ -1378,10 +1459,10 @@ extern "C" int mgl_match_frontier(mgl_sa* sa, uint32_t depth, uint32_t* off_out,
 	if (count) *count = sa->mf_total;
 	if (gpu_ms) *gpu_ms = sa->mf_ms;
 	if (cap < sa->mf_total) return fail(MGL_ERANGE, "mgl_match_frontier: cap is below the number of entries");
-	if (off_out) HIPCHK(hipMemcpyAsync(off_out, sa->d_mf_off, sizeof(uint32_t) * ((size_t)sa->n + 1), hipMemcpyDeviceToHost, sa->stream));
-	if (src_out && sa->mf_total) HIPCHK(hipMemcpyAsync(src_out, sa->d_mf_src, sizeof(uint32_t) * sa->mf_total, hipMemcpyDeviceToHost, sa->stream));
-	if (len_out && sa->mf_total) HIPCHK(hipMemcpyAsync(len_out, sa->d_mf_len, sizeof(uint16_t) * sa->mf_total, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	if (off_out) HIPCHK(hipMemcpyAsync(off_out, sa->d_mf_off, sizeof(uint32_t) * ((size_t)sa->n + 1), hipMemcpyDeviceToHost, sa->q.stream));
+	if (src_out && sa->mf_total) HIPCHK(hipMemcpyAsync(src_out, sa->d_mf_src, sizeof(uint32_t) * sa->mf_total, hipMemcpyDeviceToHost, sa->q.stream));
+	if (len_out && sa->mf_total) HIPCHK(hipMemcpyAsync(len_out, sa->d_mf_len, sizeof(uint16_t) * sa->mf_total, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -1391,10 +1472,10 @@ static int opt_dp(mgl_sa* sa, OptBufs& o, const uint32_t* entry, uint32_t cand, 
 	const uint32_t nch = (uint32_t)((sa->n + chunk - 1) / chunk);
 	const bool mf = sa->mf_finder == MGL_MF_FRONTIER;
 	if (mf) { int rc = mf_ensure(sa, sa->mf_depth); if (rc) return rc; }
-	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.dp, (uint32_t)sa->n);
-	HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long), sa->stream));
-	if (mf) hipLaunchKernelGGL(k_opt_dp<true>, dim3(nch), dim3(64), 0, sa->stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj, mf_lists(sa));
-	else hipLaunchKernelGGL(k_opt_dp<false>, dim3(nch), dim3(64), 0, sa->stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj, MfLists{});
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, o.dp, (uint32_t)sa->n);
+	HIPCHK(hipMemsetAsync(o.obj, 0, sizeof(unsigned long long), sa->q.stream));
+	if (mf) hipLaunchKernelGGL(k_opt_dp<true>, dim3(nch), dim3(64), 0, sa->q.stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj, mf_lists(sa));
+	else hipLaunchKernelGGL(k_opt_dp<false>, dim3(nch), dim3(64), 0, sa->q.stream, sa->ctx, (const uint32_t*)o.prices, entry, chunk, cand, o.back, o.dp, o.obj, MfLists{});
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -1417,10 +1498,10 @@ extern "C" int mgl_optimal_pass(mgl_sa* sa, const uint32_t* prices, size_t npric
 	HIPCHK(hipSetDevice(sa->device));
 	OptBufs o;
 	if ((rc = opt_alloc(sa, o, chunk, false))) return rc;
-	HIPCHK(hipMemcpyAsync(o.prices, prices, sizeof(uint32_t) * nprices, hipMemcpyHostToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(o.prices, prices, sizeof(uint32_t) * nprices, hipMemcpyHostToDevice, sa->q.stream));
 	if ((rc = opt_dp(sa, o, nullptr, cand, chunk))) return rc;
 	unsigned long long obj = 0;
-	HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->q.stream));
 	if ((rc = export_slab(sa, o.dp, packets_out))) return rc;
 	if (objective) *objective = obj;
 	return MGL_OK;
@@ -1437,8 +1518,8 @@ extern "C" int mgl_optimal_prices(mgl_sa* sa, const mgl_packet* packets, uint32_
 	OptBufs o;
 	if ((rc = opt_alloc(sa, o, MGL_OPT_DEF_CHUNK, false))) return rc;
 	if ((rc = opt_prices(sa, o, sa->scratch.v.slab))) return rc;
-	HIPCHK(hipMemcpyAsync(prices_out, o.prices, sizeof(uint32_t) * 2 * sa->ctx.L.total, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(prices_out, o.prices, sizeof(uint32_t) * 2 * sa->ctx.L.total, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -1460,7 +1541,7 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 	const uint32_t n = (uint32_t)sa->n;
 	/* pass 0's prices: the greedy parse.  It and every pass's parse become the current slab in turn: the base's rebuild is
 	 * what costs them */
-	hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, o.res, cand);
+	hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->q.stream, sa->ctx, o.res, cand);
 	HIPCHK(hipGetLastError());
 	if ((rc = replace_current(sa, put_slab(sa, o.res), false, MGL_EDEVICE, who, &st.greedy_cost))) return rc;
 	if ((rc = opt_prices(sa, o, o.res))) return rc;
@@ -1469,18 +1550,18 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 	HIPCHK(o.own.event(&t1));
 	uint64_t best = ~0ull;
 	for (uint32_t p = 0; p < passes && rc == MGL_OK; p++) {
-		if (hipEventRecord(t0, sa->stream) != hipSuccess) { rc = fail(MGL_EDEVICE, "hipEventRecord"); break; }
+		if (hipEventRecord(t0, sa->q.stream) != hipSuccess) { rc = fail(MGL_EDEVICE, "hipEventRecord"); break; }
 		if ((rc = opt_dp(sa, o, p ? o.entry : nullptr, cand, chunk))) break;
-		hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, o.res, n);
-		HIPCHK(hipMemsetAsync(o.counts, 0, sizeof(uint32_t) * 2 * sa->ctx.L.total, sa->stream));
-		hipLaunchKernelGGL(k_opt_walk, dim3(1), dim3(64), 0, sa->stream, sa->ctx, (const mgl_pk*)o.dp, o.res, o.counts, 1, chunk, o.entry);
-		hipLaunchKernelGGL(k_opt_prices, dim3((sa->ctx.L.total + 255) / 256), dim3(256), 0, sa->stream, (const uint32_t*)o.counts, sa->ctx.cost_tbl,
+		hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, o.res, n);
+		HIPCHK(hipMemsetAsync(o.counts, 0, sizeof(uint32_t) * 2 * sa->ctx.L.total, sa->q.stream));
+		hipLaunchKernelGGL(k_opt_walk, dim3(1), dim3(64), 0, sa->q.stream, sa->ctx, (const mgl_pk*)o.dp, o.res, o.counts, 1, chunk, o.entry);
+		hipLaunchKernelGGL(k_opt_prices, dim3((sa->ctx.L.total + 255) / 256), dim3(256), 0, sa->q.stream, (const uint32_t*)o.counts, sa->ctx.cost_tbl,
 		                   sa->ctx.L.total, o.prices);
 		if ((rc = replace_current(sa, put_slab(sa, o.res), false, MGL_EDEVICE, who, &st.cost[p]))) break;
 		unsigned long long obj = 0;
-		HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->stream));
+		HIPCHK(hipMemcpyAsync(&obj, o.obj, sizeof obj, hipMemcpyDeviceToHost, sa->q.stream));
 		float ms = 0;
-		HIPCHK(hipEventRecord(t1, sa->stream));
+		HIPCHK(hipEventRecord(t1, sa->q.stream));
 		HIPCHK(hipEventSynchronize(t1));
 		st.objective[p] = obj;
 		HIPCHK(hipEventElapsedTime(&ms, t0, t1));
@@ -1488,7 +1569,7 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 		st.passes = p + 1;
 		if (st.cost[p] < best) {
 			best = st.cost[p]; st.best_pass = p;
-			HIPCHK(hipMemcpyAsync(o.keep, o.res, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
+			HIPCHK(hipMemcpyAsync(o.keep, o.res, sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->q.stream));
 		}
 	}
 	if (rc) return rc;
@@ -1496,7 +1577,7 @@ extern "C" int mgl_sa_seed_optimal(mgl_sa* sa, const mgl_optimal_config* cfg, mg
 	if (st.best_pass + 1 != st.passes) rc = replace_current(sa, put_slab(sa, o.keep), true, MGL_EDEVICE, who, &best);
 	else rc = check_current(sa, true, MGL_EDEVICE, who, nullptr);
 	if (rc) return rc;
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	if (stats) *stats = st;
 	return MGL_OK;
 }
@@ -1612,9 +1693,9 @@ static int parse_alloc(mgl_sa* sa, Parse& P, bool resolved)
 	for (hipEvent_t* e : { &P.t0, &P.t1, &P.call0, &P.fork, &P.join }) HIPCHK(P.own.event(e));
 	if (P.nnear) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_near));
 	if (P.nfront) HIPCHK(hipFuncSetAttribute((const void*)k_adp_dp_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_front));
-	HIPCHK(hipEventRecord(P.call0, sa->stream));
-	HIPCHK(hipMemcpyAsync(P.tab, P.h_tab, sizeof(AdpVariant) * nv, hipMemcpyHostToDevice, sa->stream));
-	HIPCHK(hipMemcpyAsync(P.lists, P.h_lists, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
+	HIPCHK(hipEventRecord(P.call0, sa->q.stream));
+	HIPCHK(hipMemcpyAsync(P.tab, P.h_tab, sizeof(AdpVariant) * nv, hipMemcpyHostToDevice, sa->q.stream));
+	HIPCHK(hipMemcpyAsync(P.lists, P.h_lists, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->q.stream));
 	return MGL_OK;
 }
 
@@ -1626,17 +1707,17 @@ static int parse_starts(mgl_sa* sa, Parse& P, const mgl_pk* given)
 	const uint32_t n = (uint32_t)sa->n, nv = P.nv;
 	uint32_t idx[MGL_SWEEP_MAX];
 	for (uint32_t v = 0; v < nv; v++) idx[v] = given ? 0u : P.cand_idx[v];
-	HIPCHK(hipMemcpyAsync(P.start_idx, idx, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(P.start_idx, idx, sizeof(uint32_t) * nv, hipMemcpyHostToDevice, sa->q.stream));
 	if (!given) {
 		for (uint32_t k = 0; k < P.ncand; k++) /* ncand <= nv slabs of res, which no pass has written yet */
-			hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->stream, sa->ctx, P.res + (size_t)k * n, P.cands[k]);
+			hipLaunchKernelGGL(k_greedy_seed, dim3((n + 255u) / 256u), dim3(256), 0, sa->q.stream, sa->ctx, P.res + (size_t)k * n, P.cands[k]);
 		given = P.res;
 	}
-	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)P.tab, given, (const uint32_t*)P.start_idx,
+	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(nv), dim3(64), 0, sa->q.stream, sa->ctx, (const AdpVariant*)P.tab, given, (const uint32_t*)P.start_idx,
 	                   (mgl_pk*)nullptr, 0, P.chunk, P.nch, P.entry, P.snaps, P.cost);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * nv, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	P.st.assign(nv, mgl_optimal_stats{});
 	for (uint32_t v = 0; v < nv; v++) {
 		P.st[v].greedy_cost = P.h_cost[v];
@@ -1653,22 +1734,22 @@ static int parse_dp(mgl_sa* sa, Parse& P)
 {
 	const size_t n = sa->n;
 	const bool both = P.nnear && P.nfront;
-	HIPCHK(hipEventRecord(P.t0, sa->stream));
-	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, P.dp, n * P.nv);
-	HIPCHK(hipMemsetAsync(P.obj, 0, sizeof(unsigned long long) * P.nv, sa->stream));
+	HIPCHK(hipEventRecord(P.t0, sa->q.stream));
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, P.dp, n * P.nv);
+	HIPCHK(hipMemsetAsync(P.obj, 0, sizeof(unsigned long long) * P.nv, sa->q.stream));
 	if (both) {
-		HIPCHK(hipEventRecord(P.fork, sa->stream));
-		HIPCHK(hipStreamWaitEvent(sa->stream2, P.fork, 0));
+		HIPCHK(hipEventRecord(P.fork, sa->q.stream));
+		HIPCHK(hipStreamWaitEvent(sa->q.stream2, P.fork, 0));
 	}
 	if (P.nfront)
-		hipLaunchKernelGGL(k_adp_dp_sweep<true>, dim3(P.nch, P.nfront), dim3(64), P.lds_front, both ? sa->stream2 : sa->stream, sa->ctx,
+		hipLaunchKernelGGL(k_adp_dp_sweep<true>, dim3(P.nch, P.nfront), dim3(64), P.lds_front, both ? sa->q.stream2 : sa->q.stream, sa->ctx,
 		                   (const AdpVariant*)P.tab, (const uint32_t*)P.lists + P.nnear, P.nch, (const uint32_t*)P.entry, (const uint16_t*)P.snaps, P.chunk,
 		                   P.back, P.dp, P.obj, mf_lists(sa));
-	if (both) HIPCHK(hipEventRecord(P.join, sa->stream2));
+	if (both) HIPCHK(hipEventRecord(P.join, sa->q.stream2));
 	if (P.nnear)
-		hipLaunchKernelGGL(k_adp_dp_sweep<false>, dim3(P.nch, P.nnear), dim3(64), P.lds_near, sa->stream, sa->ctx, (const AdpVariant*)P.tab,
+		hipLaunchKernelGGL(k_adp_dp_sweep<false>, dim3(P.nch, P.nnear), dim3(64), P.lds_near, sa->q.stream, sa->ctx, (const AdpVariant*)P.tab,
 		                   (const uint32_t*)P.lists, P.nch, (const uint32_t*)P.entry, (const uint16_t*)P.snaps, P.chunk, P.back, P.dp, P.obj, MfLists{});
-	if (both) HIPCHK(hipStreamWaitEvent(sa->stream, P.join, 0));
+	if (both) HIPCHK(hipStreamWaitEvent(sa->q.stream, P.join, 0));
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
 }
@@ -1678,13 +1759,13 @@ static int parse_dp(mgl_sa* sa, Parse& P)
 static int parse_resolve(mgl_sa* sa, Parse& P, bool snaps)
 {
 	const size_t n = sa->n;
-	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->stream, P.res, n * P.nv);
-	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(P.nv), dim3(64), 0, sa->stream, sa->ctx, (const AdpVariant*)P.tab, (const mgl_pk*)P.dp,
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, sa->q.stream, P.res, n * P.nv);
+	hipLaunchKernelGGL(k_adp_snap_sweep, dim3(P.nv), dim3(64), 0, sa->q.stream, sa->ctx, (const AdpVariant*)P.tab, (const mgl_pk*)P.dp,
 	                   (const uint32_t*)nullptr, P.res, 1, P.chunk, P.nch, P.entry, snaps ? P.snaps : (uint16_t*)nullptr, P.cost);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(P.h_obj, P.obj, sizeof(unsigned long long) * P.nv, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * P.nv, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipEventRecord(P.t1, sa->stream));
+	HIPCHK(hipMemcpyAsync(P.h_obj, P.obj, sizeof(unsigned long long) * P.nv, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * P.nv, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipEventRecord(P.t1, sa->q.stream));
 	HIPCHK(hipEventSynchronize(P.t1));
 	HIPCHK(hipEventElapsedTime(&P.ms, P.t0, P.t1));
 	return MGL_OK;
@@ -1703,7 +1784,7 @@ static int parse_keep(mgl_sa* sa, Parse& P, uint32_t p)
 		if (cost < P.best || (cost == P.best && P.best_v != UINT32_MAX && v < P.best_v)) { P.best = cost; P.best_v = keep_v = v; }
 	}
 	if (keep_v != UINT32_MAX)
-		HIPCHK(hipMemcpyAsync(P.keep, P.res + (size_t)keep_v * sa->n, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->stream));
+		HIPCHK(hipMemcpyAsync(P.keep, P.res + (size_t)keep_v * sa->n, sizeof(mgl_pk) * sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
 	return MGL_OK;
 }
 
@@ -1733,7 +1814,7 @@ static int sweep_run(mgl_sa* sa, const char* who, const mgl_parse_sweep_config* 
 		if ((rc = replace_current(sa, put_slab(sa, P.keep), true, MGL_EDEVICE, who, &built))) return rc;
 		if (built != P.best) return fail(MGL_EDEVICE, std::string(who) + ": the walk's cost of the seeded slab differs from the rebuild's");
 	}
-	HIPCHK(hipEventRecord(P.t1, sa->stream));
+	HIPCHK(hipEventRecord(P.t1, sa->q.stream));
 	HIPCHK(hipEventSynchronize(P.t1));
 	float call_ms = 0;
 	HIPCHK(hipEventElapsedTime(&call_ms, P.call0, P.t1));
@@ -1782,13 +1863,11 @@ extern "C" int mgl_adaptive_pass(mgl_sa* sa, const mgl_packet* parse_in, uint32_
 	if ((rc = parse_alloc(sa, P, false))) return rc;
 	if ((rc = parse_starts(sa, P, sa->scratch.v.slab))) return rc;
 	if ((rc = parse_dp(sa, P))) return rc;
-	HIPCHK(hipMemcpyAsync(P.h_obj, P.obj, sizeof(unsigned long long), hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipMemcpyAsync(P.h_obj, P.obj, sizeof(unsigned long long), hipMemcpyDeviceToHost, sa->q.stream));
 	if ((rc = export_slab(sa, P.dp, packets_out))) return rc;
 	if (objective) *objective = P.h_obj[0];
 	return MGL_OK;
 }
-
-static hipEvent_t pool_event(mgl_sa* sa, size_t i) { return pool_event(sa, sa->ev_pool, i); }
 
 extern "C" int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_threshold)
 {
@@ -1797,7 +1876,7 @@ extern "C" int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_thresh
 	if (mode == MGL_ACCEPT_BULK && !(sa->incremental && sa->parallel_build)) return fail(MGL_EINVAL, "mgl_sa_set_accept_mode: bulk steps need the incremental engine and its parallel builder");
 	sa->accept_mode = mode;
 	if (bulk_threshold) sa->bulk_threshold = bulk_threshold;
-	auto_reset(sa);
+	sa->autoacc.reset();
 	return MGL_OK;
 }
 extern "C" int mgl_sa_step_modes(mgl_sa* sa, uint8_t* modes_out, size_t cap, size_t* count)
@@ -1812,18 +1891,18 @@ extern "C" int mgl_sa_step_modes(mgl_sa* sa, uint8_t* modes_out, size_t cap, siz
  * step offers many improving neighbours AND their windows are short enough for several to be taken at once.
  * From the all-literal slab nothing resets the rep distances, so every window runs to the end of the file
  * and a bulk step takes one move like a single step, at three times the price: then single steps for a while. */
-static void auto_decide(mgl_sa* sa, bool was_bulk, uint64_t block, uint64_t improving, uint64_t taken)
+void AutoAccept::decide(bool was_bulk, uint64_t block, uint64_t improving, uint64_t taken, uint32_t bulk_threshold, bool batch_ok)
 {
-	const bool many = improving >= (uint64_t)sa->bulk_threshold * block;
+	const bool many = improving >= (uint64_t)bulk_threshold * block;
 	if (was_bulk) {
 		/* (a bulk step that takes one move is a single step at a higher price: from the all-literal slab, where no window
 		 * closes, or once improving neighbours have become rare) */
-		if (sa->batch_ok ? 2u * taken < 3u * block : taken < 4u * block) { sa->bulk_now = false; sa->bulk_hold = 48; }
-		else sa->bulk_now = many;
+		if (batch_ok ? 2u * taken < 3u * block : taken < 4u * block) { bulk_now = false; bulk_hold = 48; }
+		else bulk_now = many;
 		return;
 	}
-	sa->bulk_hold = sa->bulk_hold > block ? sa->bulk_hold - block : 0;
-	sa->bulk_now = many && sa->bulk_hold == 0;
+	bulk_hold = bulk_hold > block ? bulk_hold - block : 0;
+	bulk_now = many && bulk_hold == 0;
 }
 
 static DecideArgs decide_args(const mgl_sa* sa)
@@ -1837,114 +1916,251 @@ static DecideArgs decide_args(const mgl_sa* sa)
  * are queued before the host has read it (they then run beside the read-back), nullptr when the host knows the step is in */
 static void launch_bulk_close(mgl_sa* sa, const uint32_t* gate)
 {
-	hipLaunchKernelGGL(k_bulk_finish, dim3(1), dim3(64), 0, sa->stream, sa->base.ctl, sa->bulk, sa->snapshots ? 1 : 0,
+	hipLaunchKernelGGL(k_bulk_finish, dim3(1), dim3(64), 0, sa->q.stream, sa->base.ctl, sa->bulk, sa->snapshots ? 1 : 0,
 	                   sa->snapshots ? &sa->d_snap_meta[1].valid : (uint32_t*)nullptr, gate);
 	if (sa->snapshots) {
-		hipLaunchKernelGGL(k_bulk_keep_copy, dim3(1024), dim3(256), 0, sa->stream, (const Control*)sa->base.ctl, (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n, gate);
-		hipLaunchKernelGGL(k_bulk_keep_undo, dim3(64), dim3(256), 0, sa->stream, (const Control*)sa->base.ctl, sa->nbr, sa->bulk, sa->d_best, gate);
+		hipLaunchKernelGGL(k_bulk_keep_copy, dim3(1024), dim3(256), 0, sa->q.stream, (const Control*)sa->base.ctl, (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n, gate);
+		hipLaunchKernelGGL(k_bulk_keep_undo, dim3(64), dim3(256), 0, sa->q.stream, (const Control*)sa->base.ctl, sa->nbr, sa->bulk, sa->d_best, gate);
 	} else {
-		hipLaunchKernelGGL(k_bulk_copy_best, dim3(256), dim3(256), 0, sa->stream, (const Control*)sa->base.ctl, (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n, gate);
+		hipLaunchKernelGGL(k_bulk_copy_best, dim3(256), dim3(256), 0, sa->q.stream, (const Control*)sa->base.ctl, (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n, gate);
 	}
-	hipLaunchKernelGGL(k_bulk_reset, dim3(1), dim3(64), 0, sa->stream, sa->bulk, gate);
-	hipLaunchKernelGGL(k_bulk_step_end, dim3(1), dim3(64), 0, sa->stream, sa->base.ctl, sa->d_counts, sa->form_single ? 1 : 0, gate);
+	hipLaunchKernelGGL(k_bulk_reset, dim3(1), dim3(64), 0, sa->q.stream, sa->bulk, gate);
+	hipLaunchKernelGGL(k_bulk_step_end, dim3(1), dim3(64), 0, sa->q.stream, sa->base.ctl, sa->d_counts, sa->form.form_single ? 1 : 0, gate);
 }
-/* the tail of a bulk step: selection, journals into the slab, parallel rebuild, best-slab tracking */
-static int launch_bulk_tail(mgl_sa* sa, uint64_t next_gstep)
+/* ---- the tail of a bulk step in stages: launch_bulk_tail calls them in the order they stand in.  All on the main stream. */
+/* the selection: which of the step's acceptable neighbours are taken; no waits, no records */
+static int bulk_select(mgl_sa* sa)
 {
 	const uint32_t K = sa->cfg.neighbours_per_step;
 	const DecideArgs a = decide_args(sa);
 	const uint32_t blocks = (K + 255u) / 256u;
-	hipLaunchKernelGGL(k_bulk_prep, dim3(blocks), dim3(256), 0, sa->stream, sa->ctx, sa->base.ctl, sa->nbr, a, sa->bulk);
-	if (sa->select_small) {
-		hipLaunchKernelGGL(k_bulk_select_small, dim3(1), dim3(1024), 0, sa->stream, sa->base.ctl, sa->nbr, sa->bulk, K);
+	hipLaunchKernelGGL(k_bulk_prep, dim3(blocks), dim3(256), 0, sa->q.stream, sa->ctx, sa->base.ctl, sa->nbr, a, sa->bulk);
+	if (sa->autoacc.select_small) {
+		hipLaunchKernelGGL(k_bulk_select_small, dim3(1), dim3(1024), 0, sa->q.stream, sa->base.ctl, sa->nbr, sa->bulk, K);
 	} else for (uint32_t r = 0; r < MGL_BULK_ROUNDS; r++) {
-		hipLaunchKernelGGL(k_bulk_pairs, dim3(blocks, blocks), dim3(256), 0, sa->stream, sa->bulk, K, r);
-		hipLaunchKernelGGL(k_bulk_round, dim3(blocks), dim3(256), 0, sa->stream, sa->base.ctl, sa->nbr, sa->bulk, sa->base.v.slab, K, r);
+		hipLaunchKernelGGL(k_bulk_pairs, dim3(blocks, blocks), dim3(256), 0, sa->q.stream, sa->bulk, K, r);
+		hipLaunchKernelGGL(k_bulk_round, dim3(blocks), dim3(256), 0, sa->q.stream, sa->base.ctl, sa->nbr, sa->bulk, sa->base.v.slab, K, r);
 	}
-	hipLaunchKernelGGL(k_bulk_end, dim3(1), dim3(64), 0, sa->stream, sa->base.ctl, sa->bulk, a);
+	hipLaunchKernelGGL(k_bulk_end, dim3(1), dim3(64), 0, sa->q.stream, sa->base.ctl, sa->bulk, a);
 	HIPCHK(hipGetLastError());
-	int rc = MGL_OK;
-	/* A step that took few moves patches the base structures for all of them at once (mgl_kernels5.hip); every kernel of
-	 * that looks at the status word first, so a step that took none, or too many, passes through in a few microseconds. */
-	uint32_t bstat[8] = { 2u, 0, 0, 0, 0, 0, 0, 0 }; /* without the batch path: everything is the rebuild's */
-	bool closed = false; /* the closing kernels are queued (behind the batch accept's gate) and the gate is open */
-	if (sa->batch_ok && !sa->force_rollbacks) { /* (the rollback net hangs under the rebuild: while a test forces it, steps go that way) */
-		Base2& b = sa->b2;
-		if (sa->force_batch_fail) { /* hdr[9]: give up at the top of k_batch_chains; hdr[13] = n: behind the n-th context's rewrite */
-			const uint32_t early = sa->force_batch_late ? 0u : 1u, late = sa->force_batch_late;
-			HIPCHK(hipMemcpyAsync(sa->batch.hdr + 9, &early, sizeof early, hipMemcpyHostToDevice, sa->stream));
-			HIPCHK(hipMemcpyAsync(sa->batch.hdr + 13, &late, sizeof late, hipMemcpyHostToDevice, sa->stream));
-		}
-		const BatchBuf bt = accept_bt(sa);
-		const ApplyBuf ab = accept_ab(sa);
-		hipLaunchKernelGGL(k_batch_clusters, dim3(1), dim3(1024), 0, sa->stream, sa->ctx, (const Control*)sa->base.ctl, sa->nbr, sa->bulk, sa->batch, sa->lim);
-		hipLaunchKernelGGL(k_batch_walk, dim3(MGL_BATCH_MAX), dim3(64), 0, sa->stream, sa->ctx, b, sa->batch, sa->lim);
-		hipLaunchKernelGGL(k_batch_commit, dim3(MGL_BATCH_MAX), dim3(256), 0, sa->stream, sa->ctx, b, sa->base.ctl, sa->batch, sa->ab);
-		hipLaunchKernelGGL(pb_levels, dim3((b.nw0 + 255) / 256), dim3(256), 0, sa->stream, (const uint64_t*)b.sp0, b.sp1, b.nw0, b.nw1);
-		hipLaunchKernelGGL(pb_levels, dim3((b.nw1 + 255) / 256), dim3(256), 0, sa->stream, (const uint64_t*)b.sp1, b.sp2, b.nw1, b.nw2);
-		/* the bitmaps are the new base's from here on -- if the batch accept goes through, which the status read below says */
-		if (next_gstep != ~0ull && (rc = launch_targets_ahead(sa, next_gstep))) return rc;
-		hipLaunchKernelGGL(k_batch_scan, dim3(1), dim3(1024), 0, sa->stream, sa->batch, sa->ab);
-		hipLaunchKernelGGL(k_batch_fill, dim3(256), dim3(256), 0, sa->stream, sa->batch, sa->ab);
-		hipLaunchKernelGGL(k_batch_chains, dim3(MGL_BATCH_GRID), dim3(MGL_BATCH_THREADS), 0, sa->stream, sa->ctx, accept_b2(sa), sa->base.ctl, bt, ab, sa->lim);
-		hipLaunchKernelGGL(k_batch_ckpt, dim3(1024, 8), dim3(256), 0, sa->stream, b, (const Control*)sa->base.ctl, bt, ab);
-		hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, b, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)sa->batch.hdr);
-		hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->stream, b, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)sa->batch.hdr);
-		hipLaunchKernelGGL(k_batch_end, dim3(1), dim3(64), 0, sa->stream, sa->base.ctl, sa->batch);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(sa->h_bstat, sa->batch.hdr, sizeof bstat, hipMemcpyDeviceToHost, sa->stream)); /* pinned: no staging copy */
-		HIPCHK(hipEventRecord(sa->ev_bstat, sa->stream));
-		launch_bulk_close(sa, (const uint32_t*)sa->batch.hdr); /* behind the gate: they run while the host reads the status */
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventSynchronize(sa->ev_bstat));
-		memcpy(bstat, sa->h_bstat, sizeof bstat);
-		closed = bstat[0] == 3u || bstat[0] == 0u;
-		if (!closed && sa->tgt_ahead) sa->tgt_ahead = 2; /* the step goes to the rebuild (or was never committed): the targets are made again */
-		if (sa->force_batch_fail) {
-			const uint32_t zero = 0u;
-			HIPCHK(hipMemcpy(sa->batch.hdr + 9, &zero, sizeof zero, hipMemcpyHostToDevice));
-			HIPCHK(hipMemcpy(sa->batch.hdr + 13, &zero, sizeof zero, hipMemcpyHostToDevice));
-			/* a step that took nothing, or went to the rebuild anyway, does not count; a batch accept the hook was applied to does,
-			 * whether it gave up or (late form with n above the contexts that got that far) went through: the hook never stays
-			 * armed with a stale n */
-			if ((bstat[0] == 1u || bstat[0] == 3u) && --sa->force_batch_fail == 0) sa->force_batch_late = 0;
-		}
+	return MGL_OK;
+}
+/* A step that took few moves patches the base structures for all of them at once (mgl_kernels5.hip); every kernel of
+ * that looks at the status word first, so a step that took none, or too many, passes through in a few microseconds.
+ * Queues the batch accept (the next step's targets ahead behind its second pb_levels: launch_targets_ahead), the copy of
+ * the status words to pinned memory, ev_bstat behind it and the closing kernels behind the gate; waits for ev_bstat on the
+ * host.  bstat = the status words; *closed = the closing kernels are queued and the gate is open. */
+static int bulk_batch_accept(mgl_sa* sa, uint64_t next_gstep, uint32_t bstat[8], bool* closed)
+{
+	Base2& b = sa->b2;
+	hipStream_t st = sa->q.stream;
+	if (sa->force.batch_fail) { /* hdr[9]: give up at the top of k_batch_chains; hdr[13] = n: behind the n-th context's rewrite */
+		const uint32_t early = sa->force.batch_late ? 0u : 1u, late = sa->force.batch_late;
+		HIPCHK(hipMemcpyAsync(sa->batch.hdr + 9, &early, sizeof early, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(sa->batch.hdr + 13, &late, sizeof late, hipMemcpyHostToDevice, st));
 	}
-	if (sa->batch_ok) sa->select_small = bstat[7] <= 512u; /* this step's acceptable neighbours size the next step's selection */
-	if (bstat[0] == 3u) sa->batch_accepts++; /* the moves are in: structures patched, exact cost in Control::rebuild_cost, every rep packet of the new walk checked */
-	else if (bstat[0] != 0u) {
-		/* the rebuild's: the journals into the slab (unless the batch accept got as far as writing them: status 1 = it gave
-		 * up behind its commit), everything that hangs off the slab re-derived, the parse checked after the fact (soft window
-		 * ends rest on an argument about rep distances, not on a proof for every coincidence of values): every packet of
-		 * the new parse against the input; a parse that fails is taken back as a whole.  One small read-back per bulk
-		 * step (a bulk step of this kind is a rebuild: milliseconds) */
-		if (sa->batch_ok && bstat[0] == 1u) sa->batch_fallbacks++;
-		if (sa->batch_ok && bstat[0] == 2u && bstat[4]) sa->batch_early_giveups++; /* (status 2 without it: more moves than a batch accept handles) */
-		if (bstat[0] != 1u)
-			hipLaunchKernelGGL(k_bulk_write, dim3(64), dim3(256), 0, sa->stream, sa->base.ctl, sa->nbr, sa->bulk, sa->base.v.slab);
-		HIPCHK(hipGetLastError());
-		Control now;
-		if (sa->batch_ok && bstat[0] == 1u) { /* apply_failed was raised: not the rebuild's concern */
-			if ((rc = read_ctl(sa, sa->base, &now))) return rc;
-			now.apply_failed = 0;
-			if ((rc = write_ctl(sa, sa->base, &now))) return rc;
-		}
-		if ((rc = launch_pbuild(sa, sa->incremental))) return rc;
-		if ((rc = read_ctl(sa, sa->base, &now))) return rc;
-		if (sa->force_rollbacks && now.taken) { sa->force_rollbacks--; now.error_flags |= MGL_ERR_BAD_PACKET; } /* diagnostic (mgl_debug_set key 3): exercise the net */
-		if (now.error_flags & MGL_ERR_BAD_PACKET) {
-			hipLaunchKernelGGL(k_bulk_rollback, dim3(64), dim3(256), 0, sa->stream, sa->nbr, sa->bulk, sa->base.v.slab);
-			HIPCHK(hipGetLastError());
-			now.error_flags &= ~MGL_ERR_BAD_PACKET;
-			now.accepted -= now.taken;
-			now.taken = 0;
-			sa->bulk_rollbacks++;
-			if ((rc = write_ctl(sa, sa->base, &now))) return rc;
-			if ((rc = launch_pbuild(sa))) return rc;
-		}
+	const BatchBuf bt = accept_bt(sa);
+	const ApplyBuf ab = accept_ab(sa);
+	hipLaunchKernelGGL(k_batch_clusters, dim3(1), dim3(1024), 0, st, sa->ctx, (const Control*)sa->base.ctl, sa->nbr, sa->bulk, sa->batch, sa->lim);
+	hipLaunchKernelGGL(k_batch_walk, dim3(MGL_BATCH_MAX), dim3(64), 0, st, sa->ctx, b, sa->batch, sa->lim);
+	hipLaunchKernelGGL(k_batch_commit, dim3(MGL_BATCH_MAX), dim3(256), 0, st, sa->ctx, b, sa->base.ctl, sa->batch, sa->ab);
+	hipLaunchKernelGGL(pb_levels, dim3((b.nw0 + 255) / 256), dim3(256), 0, st, (const uint64_t*)b.sp0, b.sp1, b.nw0, b.nw1);
+	hipLaunchKernelGGL(pb_levels, dim3((b.nw1 + 255) / 256), dim3(256), 0, st, (const uint64_t*)b.sp1, b.sp2, b.nw1, b.nw2);
+	/* the bitmaps are the new base's from here on -- if the batch accept goes through, which the status read below says */
+	if (next_gstep != ~0ull) TRY(launch_targets_ahead(sa, next_gstep));
+	hipLaunchKernelGGL(k_batch_scan, dim3(1), dim3(1024), 0, st, sa->batch, sa->ab);
+	hipLaunchKernelGGL(k_batch_fill, dim3(256), dim3(256), 0, st, sa->batch, sa->ab);
+	hipLaunchKernelGGL(k_batch_chains, dim3(MGL_BATCH_GRID), dim3(MGL_BATCH_THREADS), 0, st, sa->ctx, accept_b2(sa), sa->base.ctl, bt, ab, sa->lim);
+	hipLaunchKernelGGL(k_batch_ckpt, dim3(1024, 8), dim3(256), 0, st, b, (const Control*)sa->base.ctl, bt, ab);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, st, b, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)sa->batch.hdr);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, st, b, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)sa->batch.hdr);
+	hipLaunchKernelGGL(k_batch_end, dim3(1), dim3(64), 0, st, sa->base.ctl, sa->batch);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(sa->h_bstat, sa->batch.hdr, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, st)); /* pinned: no staging copy */
+	HIPCHK(hipEventRecord(sa->q.ev_bstat, st));
+	launch_bulk_close(sa, (const uint32_t*)sa->batch.hdr); /* behind the gate: they run while the host reads the status */
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventSynchronize(sa->q.ev_bstat));
+	memcpy(bstat, sa->h_bstat, sizeof(uint32_t) * 8);
+	*closed = bstat[0] == MGL_BATCH_DONE || bstat[0] == MGL_BATCH_NONE;
+	if (!*closed && sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE; /* the step goes to the rebuild (or was never committed): the targets are made again */
+	if (sa->force.batch_fail) {
+		const uint32_t zero = 0u;
+		HIPCHK(hipMemcpy(sa->batch.hdr + 9, &zero, sizeof zero, hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(sa->batch.hdr + 13, &zero, sizeof zero, hipMemcpyHostToDevice));
+		/* a step that took nothing, or went to the rebuild anyway, does not count; a batch accept the hook was applied to does,
+		 * whether it gave up or (late form with n above the contexts that got that far) went through: the hook never stays
+		 * armed with a stale n */
+		if ((bstat[0] == MGL_BATCH_BEGAN || bstat[0] == MGL_BATCH_DONE) && --sa->force.batch_fail == 0) sa->force.batch_late = 0;
 	}
+	return MGL_OK;
+}
+/* The rebuild's: the journals into the slab (unless the batch accept got as far as writing them: MGL_BATCH_BEGAN = it gave
+ * up behind its commit), everything that hangs off the slab re-derived, the parse checked after the fact (soft window
+ * ends rest on an argument about rep distances, not on a proof for every coincidence of values): every packet of
+ * the new parse against the input; a parse that fails is taken back as a whole.  One small read-back per bulk
+ * step (a bulk step of this kind is a rebuild: milliseconds).  The validation runs on the second stream between ev_fork
+ * and ev_val (launch_pbuild); the host waits for the main stream at every read-back. */
+static int bulk_rebuild_checked(mgl_sa* sa, const uint32_t bstat[8])
+{
+	const bool gave_up_late = sa->batch_ok && bstat[0] == MGL_BATCH_BEGAN;
+	if (gave_up_late) sa->batch_fallbacks++;
+	if (sa->batch_ok && bstat[0] == MGL_BATCH_REBUILD && bstat[4]) sa->batch_early_giveups++; /* (MGL_BATCH_REBUILD without it: more moves than a batch accept handles) */
+	if (bstat[0] != MGL_BATCH_BEGAN)
+		hipLaunchKernelGGL(k_bulk_write, dim3(64), dim3(256), 0, sa->q.stream, sa->base.ctl, sa->nbr, sa->bulk, sa->base.v.slab);
+	HIPCHK(hipGetLastError());
+	Control now;
+	if (gave_up_late) { /* apply_failed was raised: not the rebuild's concern */
+		TRY(read_ctl(sa, sa->base, &now));
+		now.apply_failed = 0;
+		TRY(write_ctl(sa, sa->base, &now));
+	}
+	TRY(launch_pbuild(sa, sa->incremental));
+	TRY(read_ctl(sa, sa->base, &now));
+	if (sa->force.rollbacks && now.taken) { sa->force.rollbacks--; now.error_flags |= MGL_ERR_BAD_PACKET; } /* diagnostic (mgl_debug_set key 3): exercise the net */
+	if (!(now.error_flags & MGL_ERR_BAD_PACKET)) return MGL_OK;
+	hipLaunchKernelGGL(k_bulk_rollback, dim3(64), dim3(256), 0, sa->q.stream, sa->nbr, sa->bulk, sa->base.v.slab);
+	HIPCHK(hipGetLastError());
+	now.error_flags &= ~MGL_ERR_BAD_PACKET;
+	now.accepted -= now.taken;
+	now.taken = 0;
+	sa->bulk_rollbacks++;
+	TRY(write_ctl(sa, sa->base, &now));
+	return launch_pbuild(sa);
+}
+/* the tail of a bulk step: selection, journals into the slab, parallel rebuild, best-slab tracking */
+static int launch_bulk_tail(mgl_sa* sa, uint64_t next_gstep)
+{
+	TRY(bulk_select(sa));
+	uint32_t bstat[8] = { MGL_BATCH_REBUILD, 0, 0, 0, 0, 0, 0, 0 }; /* without the batch path: everything is the rebuild's */
+	bool closed = false;
+	/* (the rollback net hangs under the rebuild: while a test forces it, steps go that way) */
+	if (sa->batch_ok && !sa->force.rollbacks) TRY(bulk_batch_accept(sa, next_gstep, bstat, &closed));
+	if (sa->batch_ok) sa->autoacc.select_small = bstat[7] <= 512u; /* this step's acceptable neighbours size the next step's selection */
+	if (bstat[0] == MGL_BATCH_DONE) sa->batch_accepts++; /* the moves are in: structures patched, exact cost in Control::rebuild_cost, every rep packet of the new walk checked */
+	else if (bstat[0] != MGL_BATCH_NONE) TRY(bulk_rebuild_checked(sa, bstat));
 	if (!closed) launch_bulk_close(sa, nullptr);
 	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+
+/* ---- mgl_sa_run in stages */
+#define MGL_TIMED_STEPS_MAX 512u
+/* a run of `steps` steps begins: which of them carry events (StepTimer) */
+static void timer_begin_run(StepTimer& t, bool timing, uint64_t steps)
+{
+	t.stride = steps > 16 ? 4u : 1u;
+	const uint64_t n = (steps + t.stride - 1) / t.stride;
+	t.timed = timing ? (n < MGL_TIMED_STEPS_MAX ? n : MGL_TIMED_STEPS_MAX) : 0;
+	t.step = -1;
+	t.sim_timed.clear();
+}
+/* step s of the run begins; `slices` k_sim launches if its regular launch is the split form's, else 0 */
+static void timer_begin_step(StepTimer& t, uint64_t s, uint32_t slices)
+{
+	const bool timed = s % t.stride == 0 && s / t.stride < t.timed;
+	t.step = timed ? (int64_t)(s / t.stride) : -1;
+	t.sim = timed && slices != 0;
+	if (timed) t.sim_timed.push_back((uint8_t)(slices < 2u ? slices : 2u));
+}
+/* the run has been waited for: the elapsed times between its marks into stats */
+static int timer_add(const StepTimer& t, mgl_sa_stats* stats)
+{
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, t.ev_begin, t.ev_end));
+	stats->gpu_ms_total = ms;
+	for (size_t s = 0; s < t.timed && 4 * s + 3 < t.ev_pool.size(); s++) {
+		HIPCHK(hipEventElapsedTime(&ms, t.ev_pool[4 * s + T_NBR_BEGIN], t.ev_pool[4 * s + T_NBR_END]));
+		stats->gpu_ms_neighbours += ms;
+		HIPCHK(hipEventElapsedTime(&ms, t.ev_pool[4 * s + T_ACCEPT_BEGIN], t.ev_pool[4 * s + T_ACCEPT_END]));
+		stats->gpu_ms_rebuild += ms;
+	}
+	stats->neighbour_launches = t.timed;
+	for (size_t s = 0; s < t.timed && s < t.sim_timed.size(); s++)
+		for (uint32_t h = 0; h < t.sim_timed[s]; h++) { /* the regular launches: one per slice, at most two timed */
+			HIPCHK(hipEventElapsedTime(&ms, t.ev_sim_pool[4 * s + 2 * h], t.ev_sim_pool[4 * s + 2 * h + 1]));
+			stats->gpu_ms_sim += ms;
+			stats->sim_launches++;
+		}
+	return MGL_OK;
+}
+/* a step's neighbours between their two timing slots */
+static int run_neighbours(mgl_sa* sa, bool zero_counts)
+{
+	TRY(mark(sa, T_NBR_BEGIN, sa->q.stream));
+	TRY(launch_neighbours(sa, ~0ull, zero_counts));
+	return mark(sa, T_NBR_END, sa->q.stream);
+}
+/* One step by the single route: neighbours, the decision, then the in-place accept (launch_apply, which queues the targets of
+ * step next_gstep ahead) or -- MGL_NO_INCREMENTAL_APPLY, the full-walk engine -- best-slab copy, rebuild and lazy snapshot */
+static int step_single(mgl_sa* sa, bool first, uint64_t next_gstep)
+{
+	const bool inc_apply = sa->incremental && sa->incremental_apply;
+	TRY(run_neighbours(sa, first || !inc_apply));
+	hipLaunchKernelGGL(k_decide, dim3(1), dim3(1024), 0, sa->q.stream, sa->ctx, sa->base.v, sa->base.ctl, sa->nbr, decide_args(sa), inc_apply ? 0 : 1);
+	HIPCHK(hipGetLastError());
+	TRY(mark(sa, T_ACCEPT_BEGIN, sa->q.stream));
+	if (inc_apply) {
+		TRY(launch_apply(sa, next_gstep));
+	} else {
+		hipLaunchKernelGGL(k_copy_best, dim3(256), dim3(256), 0, sa->q.stream, (const Control*)sa->base.ctl,
+		                   (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n);
+		HIPCHK(hipGetLastError());
+		TRY(rebuild_base(sa, 1));
+		if (sa->incremental && sa->snapshots) TRY(launch_snapshot(sa, sa->snap_best, 1, 0, 1));
+	}
+	return mark(sa, T_ACCEPT_END, sa->q.stream);
+}
+/* one step by the bulk route: neighbours, then launch_bulk_tail */
+static int step_bulk(mgl_sa* sa, bool first, uint64_t next_gstep)
+{
+	TRY(run_neighbours(sa, first || !(sa->incremental && sa->incremental_apply)));
+	TRY(mark(sa, T_ACCEPT_BEGIN, sa->q.stream));
+	TRY(launch_bulk_tail(sa, next_gstep));
+	return mark(sa, T_ACCEPT_END, sa->q.stream);
+}
+/* How many steps run before the host looks at the device again.  Every block ends with one small read-back: AUTO needs the
+ * counters, and the form of the regular launch (split / one kernel) follows the device's recommendation from block to block.
+ * AUTO: a block is `full` = 16 single / 4 bulk steps wherever the calls' boundaries fall (blk_done steps of it are done). */
+static uint64_t block_length(const mgl_sa* sa, int mode, uint64_t full, uint64_t left)
+{
+	uint64_t block = mode == MGL_ACCEPT_AUTO ? full - sa->autoacc.blk_done : full;
+	if (sa->form.short_looks && block > 4u) block = 4u; /* a form was just switched (a trial, usually): look again soon, a trial of a form twice as slow should not last a whole block */
+	return block > left ? left : block;
+}
+/* the form the device recommends becomes the regular launch's */
+static void adopt_form(mgl_sa* sa, const Control& c)
+{
+	if (sa->form.adaptive && sa->form.form_single != (c.nbr_single != 0)) { sa->form.form_single = c.nbr_single != 0; sa->form.short_looks = 3; }
+}
+/* between two blocks, with the counters just read: the launch form, and AUTO's route for the next block if this one is over */
+static void end_block(mgl_sa* sa, const Control& now, bool bulk, uint64_t full, bool block_over)
+{
+	AutoAccept& au = sa->autoacc;
+	if (sa->form.short_looks) sa->form.short_looks--;
+	adopt_form(sa, now);
+	if (!block_over) return;
+	au.decide(bulk, full, now.imp_cands - au.blk_imp0, now.accepted - au.blk_acc0, sa->bulk_threshold, sa->batch_ok);
+	au.blk_done = 0; au.blk_imp0 = now.imp_cands; au.blk_acc0 = now.accepted;
+}
+/* what a run did, from the control block before and after it, the timed steps and the handle's own counters */
+static int fill_stats(mgl_sa* sa, const Control& before, const Control& after, uint64_t rollbacks_before, unsigned long long traffic_before, mgl_sa_stats* stats)
+{
+	memset(stats, 0, sizeof *stats);
+	stats->steps = after.gstep - before.gstep; stats->evaluations = after.evals - before.evals; stats->failed = after.failed - before.failed;
+	stats->accepted = after.accepted - before.accepted; stats->improved = after.improved - before.improved;
+	stats->packets_evaluated = after.packets_eval - before.packets_eval;
+	stats->current_cost = after.cur_cost; stats->best_cost = after.best_cost; stats->packets = after.packets;
+	TRY(timer_add(sa->timer, stats));
+	if (sa->count_traffic) {
+		unsigned long long now[2] = { 0, 0 };
+		HIPCHK(hipMemcpy(now, sa->d_traffic, sizeof now, hipMemcpyDeviceToHost));
+		stats->sim_bytes_counted = now[0] - traffic_before;
+	}
+	stats->full_rebuilds = after.full_rebuilds - before.full_rebuilds; stats->fallback_neighbours = after.fallback_nbrs - before.fallback_nbrs;
+	stats->second_pass_neighbours = after.big_nbrs - before.big_nbrs; stats->bulk_steps = after.bulk_steps - before.bulk_steps;
+	stats->dropped_neighbours = after.dropped - before.dropped; stats->improving_neighbours = after.imp_cands - before.imp_cands;
+	stats->bulk_rollbacks = sa->bulk_rollbacks - rollbacks_before; stats->bulk_double_writes = after.bulk_overlaps - before.bulk_overlaps;
 	return MGL_OK;
 }
 
@@ -1953,126 +2169,43 @@ extern "C" int mgl_sa_run(mgl_sa* sa, uint64_t steps, mgl_sa_stats* stats)
 	if (!sa) return fail(MGL_EINVAL, "null handle");
 	HIPCHK(hipSetDevice(sa->device));
 	Control before, after;
-	int rc = read_ctl(sa, sa->base, &before);
-	if (rc) return rc;
-	const bool timing = (sa->cfg.flags & MGL_F_TIMING) != 0;
-	/* MGL_F_TIMING brackets steps with events: every step of a short run, every fourth of a longer one (the ten event records of a
-	 * timed step cost it 30 us at 10 MB) */
-	const uint64_t t_stride = steps > 16 ? 4u : 1u;
-	const uint64_t timed_steps = timing ? ((steps + t_stride - 1) / t_stride < 512 ? (steps + t_stride - 1) / t_stride : 512) : 0;
-	const bool inc_apply = sa->incremental && sa->incremental_apply;
-	const DecideArgs dargs = decide_args(sa);
+	TRY(read_ctl(sa, sa->base, &before));
+	timer_begin_run(sa->timer, (sa->cfg.flags & MGL_F_TIMING) != 0, steps);
 	const int mode = (sa->incremental && sa->parallel_build) ? sa->accept_mode : MGL_ACCEPT_SINGLE; /* bulk steps rebuild with the parallel builder */
 	sa->mode_log.clear();
-	if (sa->tgt_ahead) sa->tgt_ahead = 2; /* (only behind a run that ended early: whatever was queued is not trusted) */
+	if (sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE; /* (only behind a run that ended early: whatever was queued is not trusted) */
 	const uint64_t rollbacks_before = sa->bulk_rollbacks;
-	std::vector<uint8_t> sim_timed; /* per timed step: how many of the regular k_sim launches carry events (0: none, the one-kernel form ran) */
 	unsigned long long traffic_before[2] = { 0, 0 };
 	if (sa->count_traffic) HIPCHK(hipMemcpy(traffic_before, sa->d_traffic, sizeof traffic_before, hipMemcpyDeviceToHost));
-	if (sa->blk_done == 0) { sa->blk_imp0 = before.imp_cands; sa->blk_acc0 = before.accepted; }
-	HIPCHK(hipEventRecord(sa->ev_begin, sa->stream));
+	AutoAccept& au = sa->autoacc;
+	if (au.blk_done == 0) { au.blk_imp0 = before.imp_cands; au.blk_acc0 = before.accepted; }
+	HIPCHK(hipEventRecord(sa->timer.ev_begin, sa->q.stream));
 	for (uint64_t s = 0; s < steps;) {
-		const bool bulk = mode == MGL_ACCEPT_BULK || (mode == MGL_ACCEPT_AUTO && sa->bulk_now);
-		/* AUTO looks at the device counters between blocks of steps (one small read-back per block) */
-		/* every block ends with one small read-back: AUTO needs the counters, and the form of the regular launch
-		 * (split / one kernel) follows the device's recommendation from block to block */
-		/* AUTO: a block is 16 single / 4 bulk steps wherever the calls' boundaries fall (blk_done steps of it are done) */
+		const bool bulk = mode == MGL_ACCEPT_BULK || (mode == MGL_ACCEPT_AUTO && au.bulk_now);
 		const uint64_t full = mode == MGL_ACCEPT_AUTO ? (bulk ? 4u : 16u) : 64u;
-		uint64_t block = mode == MGL_ACCEPT_AUTO ? full - sa->blk_done : full;
-		if (sa->short_looks && block > 4u) block = 4u; /* a form was just switched (a trial, usually): look again soon, a trial of a form twice as slow should not last a whole block */
-		if (block > steps - s) block = steps - s;
+		const uint64_t block = block_length(sa, mode, full, steps - s);
 		for (uint64_t e = s + block; s < e; s++) {
-			const bool t = s % t_stride == 0 && s / t_stride < timed_steps;
-			const uint64_t ti = s / t_stride; /* the step's place among the timed ones */
 			if (sa->mode_log.size() < (1u << 20)) sa->mode_log.push_back(bulk ? 1 : 0);
-			if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 0), sa->stream));
-			sa->time_sim_step = (t && sa->split_nbr && !sa->form_single) ? (int64_t)ti : -1;
-			if (t) sim_timed.push_back(sa->time_sim_step >= 0 ? (nbr_slices(sa) < 2u ? 1 : 2) : 0);
-			rc = launch_neighbours(sa, ~0ull, s == 0 || !inc_apply);
-			sa->time_sim_step = -1;
+			timer_begin_step(sa->timer, s, sa->form.split_nbr && !sa->form.form_single ? nbr_slices(sa) : 0u);
+			const uint64_t next_gstep = s + 1 < steps ? before.gstep + s + 1 : ~0ull;
+			const int rc = bulk ? step_bulk(sa, s == 0, next_gstep) : step_single(sa, s == 0, next_gstep);
+			sa->timer.step = -1; /* a launch_neighbours outside a run (mgl_neighbours) marks nothing */
 			if (rc) return rc;
-			if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 1), sa->stream));
-			if (bulk) {
-				if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 2), sa->stream));
-				if ((rc = launch_bulk_tail(sa, s + 1 < steps ? before.gstep + s + 1 : ~0ull))) return rc;
-				if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 3), sa->stream));
-				continue;
-			}
-			hipLaunchKernelGGL(k_decide, dim3(1), dim3(1024), 0, sa->stream, sa->ctx, sa->base.v, sa->base.ctl, sa->nbr, dargs, inc_apply ? 0 : 1);
-			HIPCHK(hipGetLastError());
-			if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 2), sa->stream));
-			if (inc_apply) {
-				if ((rc = launch_apply(sa, s + 1 < steps ? before.gstep + s + 1 : ~0ull))) return rc;
-			} else {
-				hipLaunchKernelGGL(k_copy_best, dim3(256), dim3(256), 0, sa->stream, (const Control*)sa->base.ctl,
-				                   (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n);
-				HIPCHK(hipGetLastError());
-				if ((rc = rebuild_base(sa, 1))) return rc;
-				if (sa->incremental && sa->snapshots && (rc = launch_snapshot(sa, sa->snap_best, 1, 0, 1))) return rc;
-			}
-			if (t) HIPCHK(hipEventRecord(pool_event(sa, 4 * ti + 3), sa->stream));
 		}
-		if (mode == MGL_ACCEPT_AUTO) sa->blk_done += block;
-		const bool block_over = mode == MGL_ACCEPT_AUTO && sa->blk_done == full;
-		if (block_over || (s < steps && sa->adaptive)) {
+		if (mode == MGL_ACCEPT_AUTO) au.blk_done += block;
+		const bool block_over = mode == MGL_ACCEPT_AUTO && au.blk_done == full;
+		if (block_over || (s < steps && sa->form.adaptive)) {
 			Control now;
-			if ((rc = read_ctl(sa, sa->base, &now))) return rc;
+			TRY(read_ctl(sa, sa->base, &now));
 			if (now.error_flags) break;
-			if (sa->short_looks) sa->short_looks--;
-			if (sa->adaptive && sa->form_single != (now.nbr_single != 0)) { sa->form_single = now.nbr_single != 0; sa->short_looks = 3; }
-			if (block_over) {
-				auto_decide(sa, bulk, full, now.imp_cands - sa->blk_imp0, now.accepted - sa->blk_acc0);
-				sa->blk_done = 0; sa->blk_imp0 = now.imp_cands; sa->blk_acc0 = now.accepted;
-			}
+			end_block(sa, now, bulk, full, block_over);
 		}
 	}
-	HIPCHK(hipEventRecord(sa->ev_end, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
-	if ((rc = read_ctl(sa, sa->base, &after))) return rc;
-	if (sa->adaptive && sa->form_single != (after.nbr_single != 0)) { sa->form_single = after.nbr_single != 0; sa->short_looks = 3; }
-	if (stats) {
-		memset(stats, 0, sizeof *stats);
-		stats->steps = after.gstep - before.gstep;
-		stats->evaluations = after.evals - before.evals;
-		stats->failed = after.failed - before.failed;
-		stats->accepted = after.accepted - before.accepted;
-		stats->improved = after.improved - before.improved;
-		stats->packets_evaluated = after.packets_eval - before.packets_eval;
-		stats->current_cost = after.cur_cost;
-		stats->best_cost = after.best_cost;
-		stats->packets = after.packets;
-		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, sa->ev_begin, sa->ev_end));
-		stats->gpu_ms_total = ms;
-		for (uint64_t s = 0; s < timed_steps; s++) {
-			HIPCHK(hipEventElapsedTime(&ms, sa->ev_pool[4 * s + 0], sa->ev_pool[4 * s + 1]));
-			stats->gpu_ms_neighbours += ms;
-			HIPCHK(hipEventElapsedTime(&ms, sa->ev_pool[4 * s + 2], sa->ev_pool[4 * s + 3]));
-			stats->gpu_ms_rebuild += ms;
-		}
-		stats->neighbour_launches = timed_steps;
-		for (uint64_t s = 0; s < timed_steps && s < sim_timed.size(); s++) {
-			if (!sim_timed[s]) continue;
-			for (uint32_t h = 0; h < sim_timed[s]; h++) { /* the regular launches: one per slice, at most two timed */
-				HIPCHK(hipEventElapsedTime(&ms, sa->ev_sim_pool[4 * s + 2 * h], sa->ev_sim_pool[4 * s + 2 * h + 1]));
-				stats->gpu_ms_sim += ms;
-				stats->sim_launches++;
-			}
-		}
-		if (sa->count_traffic) {
-			unsigned long long now[2] = { 0, 0 };
-			HIPCHK(hipMemcpy(now, sa->d_traffic, sizeof now, hipMemcpyDeviceToHost));
-			stats->sim_bytes_counted = now[0] - traffic_before[0];
-		}
-		stats->full_rebuilds = after.full_rebuilds - before.full_rebuilds;
-		stats->fallback_neighbours = after.fallback_nbrs - before.fallback_nbrs;
-		stats->second_pass_neighbours = after.big_nbrs - before.big_nbrs;
-		stats->bulk_steps = after.bulk_steps - before.bulk_steps;
-		stats->dropped_neighbours = after.dropped - before.dropped;
-		stats->improving_neighbours = after.imp_cands - before.imp_cands;
-		stats->bulk_rollbacks = sa->bulk_rollbacks - rollbacks_before;
-		stats->bulk_double_writes = after.bulk_overlaps - before.bulk_overlaps;
-	}
+	HIPCHK(hipEventRecord(sa->timer.ev_end, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	TRY(read_ctl(sa, sa->base, &after));
+	adopt_form(sa, after);
+	if (stats) TRY(fill_stats(sa, before, after, rollbacks_before, traffic_before[0], stats));
 	if (after.error_flags) {
 		char buf[96];
 		snprintf(buf, sizeof buf, "mgl_sa_run: device consistency check failed (flags 0x%x)", after.error_flags);
@@ -2109,7 +2242,7 @@ static int scratch_walk(mgl_sa* sa, const mgl_packet* packets, bool want_cum, bo
 {
 	int rc = import_slab(sa, packets, sa->scratch.v.slab);
 	if (rc) return rc;
-	HIPCHK(hipMemsetAsync(sa->scratch.ctl, 0, sizeof(Control), sa->stream));
+	HIPCHK(hipMemsetAsync(sa->scratch.ctl, 0, sizeof(Control), sa->q.stream));
 	if ((rc = launch_rebuild(sa, sa->scratch, 0, want_cum ? sa->d_cum : nullptr, want_probs ? sa->d_final_probs : nullptr))) return rc;
 	if ((rc = read_ctl(sa, sa->scratch, out))) return rc;
 	if (out->error_flags) return fail(MGL_EINVAL, "slab is not a valid parse of the input");
@@ -2124,8 +2257,8 @@ extern "C" int mgl_sa_set_best(mgl_sa* sa, const mgl_packet* packets, uint64_t p
 	int rc = scratch_walk(sa, packets, false, false, &c);
 	if (rc) return rc;
 	if (c.rebuild_cost != perplexity) return fail(MGL_EINVAL, "mgl_sa_set_best: perplexity does not match the slab");
-	HIPCHK(hipMemcpyAsync(sa->d_best, sa->scratch.v.slab, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
-	if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->stream));
+	HIPCHK(hipMemcpyAsync(sa->d_best, sa->scratch.v.slab, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
+	if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->q.stream));
 	if ((rc = read_ctl(sa, sa->base, &c))) return rc;
 	c.best_cost = perplexity;
 	c.best_is_current = 0;
@@ -2172,13 +2305,13 @@ extern "C" int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_
 	TRY(dnew(tmp.own, tmp.d, MGL_PROPS_TRIPLES));
 	HIPCHK(tmp.own.event(&tmp.t0));
 	HIPCHK(tmp.own.event(&tmp.t1));
-	HIPCHK(hipEventRecord(tmp.t0, sa->stream));
-	hipLaunchKernelGGL(k_props_sweep, dim3(MGL_PROPS_TRIPLES), dim3(64), 0, sa->stream, sa->ctx, slab, tmp.d);
+	HIPCHK(hipEventRecord(tmp.t0, sa->q.stream));
+	hipLaunchKernelGGL(k_props_sweep, dim3(MGL_PROPS_TRIPLES), dim3(64), 0, sa->q.stream, sa->ctx, slab, tmp.d);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(tmp.t1, sa->stream));
+	HIPCHK(hipEventRecord(tmp.t1, sa->q.stream));
 	uint64_t costs[MGL_PROPS_TRIPLES];
-	HIPCHK(hipMemcpyAsync(costs, tmp.d, sizeof costs, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(costs, tmp.d, sizeof costs, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	float ms = 0;
 	HIPCHK(hipEventElapsedTime(&ms, tmp.t0, tmp.t1));
 	if (gpu_ms) *gpu_ms = ms;
@@ -2206,7 +2339,7 @@ static int xo_alloc(mgl_sa* sa, XoBufs& x, uint32_t P)
 {
 	static const char* nomem = "crossover: the per-parent buffers do not fit the device";
 	const size_t n = sa->n, nw = n / 64 + 1;
-	if (sa->force_xo_nomem) { sa->force_xo_nomem--; return fail(MGL_ENOMEM, nomem); }
+	if (sa->force.xo_nomem) { sa->force.xo_nomem--; return fail(MGL_ENOMEM, nomem); }
 	auto room = [&](auto*& ptr, size_t count) { return dnew(x.own, ptr, count, -1, nomem); };
 	TRY(room(x.slabs, n * P));
 	TRY(room(x.cost, (n + 1) * P));
@@ -2228,7 +2361,7 @@ static int xo_run(mgl_sa* sa, XoBufs& x, uint32_t P, uint32_t grain, mgl_cross_s
 {
 	const uint32_t n = sa->n, nw = n / 64u + 1u, nblk = (n + 1u + 255u) / 256u;
 	if (grain == 0) grain = MGL_XO_DEF_GRAIN;
-	hipStream_t s = sa->stream;
+	hipStream_t s = sa->q.stream;
 	XoView v;
 	v.slab = x.slabs; v.cost = x.cost; v.state = x.state; v.onwalk = x.onwalk; v.nw = nw;
 	HIPCHK(hipEventRecord(x.t0, s));
@@ -2286,7 +2419,7 @@ extern "C" int mgl_crossover(mgl_sa* sa, const mgl_packet* const* parents, size_
 	if (rc) return rc;
 	for (size_t p = 0; p < nparents; p++) {
 		if ((rc = import_slab(sa, parents[p], x.slabs + p * (size_t)sa->n))) return rc;
-		HIPCHK(hipStreamSynchronize(sa->stream)); /* the staging area is reused */
+		HIPCHK(hipStreamSynchronize(sa->q.stream)); /* the staging area is reused */
 	}
 	mgl_cross_stats st;
 	if ((rc = xo_run(sa, x, (uint32_t)nparents, grain, &st))) return rc;
@@ -2299,11 +2432,11 @@ extern "C" int mgl_crossover(mgl_sa* sa, const mgl_packet* const* parents, size_
 static int slab_hash_device(mgl_sa* sa, const mgl_pk* slab, uint64_t* hash)
 {
 	unsigned long long* d_sum = (unsigned long long*)sa->d_topk_cost;
-	HIPCHK(hipMemsetAsync(d_sum, 0, sizeof *d_sum, sa->stream));
-	hipLaunchKernelGGL(k_slab_hash, dim3((sa->n + 255u) / 256u), dim3(256), 0, sa->stream, sa->n, slab, d_sum);
+	HIPCHK(hipMemsetAsync(d_sum, 0, sizeof *d_sum, sa->q.stream));
+	hipLaunchKernelGGL(k_slab_hash, dim3((sa->n + 255u) / 256u), dim3(256), 0, sa->q.stream, sa->n, slab, d_sum);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(hash, d_sum, sizeof *hash, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(hash, d_sum, sizeof *hash, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -2341,16 +2474,16 @@ extern "C" int mgl_top_k(mgl_sa* sa, const mgl_packet* packets, size_t position,
 	Control c;
 	int rc = scratch_walk(sa, packets, false, false, &c);
 	if (rc) return rc;
-	hipLaunchKernelGGL(k_topk_probe, dim3(1), dim3(64), sa->walk_lds, sa->stream, sa->ctx, sa->scratch.v, (uint32_t)position,
+	hipLaunchKernelGGL(k_topk_probe, dim3(1), dim3(64), sa->walk_lds, sa->q.stream, sa->ctx, sa->scratch.v, (uint32_t)position,
 	                   sa->d_topk_pk, sa->d_topk_cost, sa->d_small);
 	HIPCHK(hipGetLastError());
 	uint32_t cnt = 0;
 	mgl_pk pk[64];
 	uint64_t cs[64];
-	HIPCHK(hipMemcpyAsync(&cnt, sa->d_small, sizeof cnt, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipMemcpyAsync(pk, sa->d_topk_pk, sizeof pk, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipMemcpyAsync(cs, sa->d_topk_cost, sizeof cs, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(&cnt, sa->d_small, sizeof cnt, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipMemcpyAsync(pk, sa->d_topk_pk, sizeof pk, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipMemcpyAsync(cs, sa->d_topk_cost, sizeof cs, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	if (cnt == ~0u) return fail(MGL_ERANGE, "position is not on the slab's walk");
 	for (uint32_t i = 0; i < cnt; i++) {
 		out[i].type = (uint8_t)mgl_pk_type(pk[i]); out[i].dist = mgl_pk_dist(pk[i]); out[i].len = (uint16_t)mgl_pk_len(pk[i]);
@@ -2368,12 +2501,12 @@ extern "C" int mgl_substrings(mgl_sa* sa, size_t pos, size_t max_len, uint32_t* 
 	const uint32_t dcap = cap < sa->sub_cap ? (uint32_t)cap : sa->sub_cap;
 	DevCtx c = sa->ctx;
 	c.dict_limit = 0xFFFFFFFFu; /* the index query itself has no window (substring_enumerator.c:97 is a todo) */
-	hipLaunchKernelGGL(k_substrings, dim3(1), dim3(1), 0, sa->stream, c, (uint32_t)pos, (uint32_t)max_len, sa->d_sub_offs,
+	hipLaunchKernelGGL(k_substrings, dim3(1), dim3(1), 0, sa->q.stream, c, (uint32_t)pos, (uint32_t)max_len, sa->d_sub_offs,
 	                   sa->d_sub_lens, dcap, sa->d_small);
 	HIPCHK(hipGetLastError());
 	uint32_t cnt = 0;
-	HIPCHK(hipMemcpyAsync(&cnt, sa->d_small, sizeof cnt, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(&cnt, sa->d_small, sizeof cnt, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	const uint32_t take = cnt < dcap ? cnt : dcap;
 	if (offsets && take) HIPCHK(hipMemcpy(offsets, sa->d_sub_offs, sizeof(uint32_t) * take, hipMemcpyDeviceToHost));
 	if (lengths && take) HIPCHK(hipMemcpy(lengths, sa->d_sub_lens, sizeof(uint32_t) * take, hipMemcpyDeviceToHost));
@@ -2386,20 +2519,20 @@ extern "C" int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs,
 	if (!sa || !costs) return fail(MGL_EINVAL, "null argument");
 	HIPCHK(hipSetDevice(sa->device));
 	int rc = launch_neighbours(sa, global_step);
-	if (rc == MGL_OK && sa->d_counts) HIPCHK(hipMemcpyAsync(sa->d_counts + 8, sa->d_counts, sizeof(uint32_t) * 8, hipMemcpyDeviceToDevice, sa->stream));
+	if (rc == MGL_OK && sa->d_counts) HIPCHK(hipMemcpyAsync(sa->d_counts + 8, sa->d_counts, sizeof(uint32_t) * 8, hipMemcpyDeviceToDevice, sa->q.stream));
 	if (rc) return rc;
 	const size_t K = sa->cfg.neighbours_per_step;
-	HIPCHK(hipMemcpyAsync(costs, sa->nbr.cost, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipMemcpyAsync(costs, sa->nbr.cost, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, sa->q.stream));
 	std::vector<uint32_t> nd(K), dpos;
 	std::vector<mgl_pk> dold, dnew;
-	HIPCHK(hipMemcpyAsync(nd.data(), sa->nbr.ndiffs, sizeof(uint32_t) * K, hipMemcpyDeviceToHost, sa->stream));
+	HIPCHK(hipMemcpyAsync(nd.data(), sa->nbr.ndiffs, sizeof(uint32_t) * K, hipMemcpyDeviceToHost, sa->q.stream));
 	if (diffs) {
 		dpos.resize(K * MGL_MAX_DIFFS); dold.resize(K * MGL_MAX_DIFFS); dnew.resize(K * MGL_MAX_DIFFS);
-		HIPCHK(hipMemcpyAsync(dpos.data(), sa->nbr.dpos, sizeof(uint32_t) * dpos.size(), hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipMemcpyAsync(dold.data(), sa->nbr.dold, sizeof(mgl_pk) * dold.size(), hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipMemcpyAsync(dnew.data(), sa->nbr.dnew, sizeof(mgl_pk) * dnew.size(), hipMemcpyDeviceToHost, sa->stream));
+		HIPCHK(hipMemcpyAsync(dpos.data(), sa->nbr.dpos, sizeof(uint32_t) * dpos.size(), hipMemcpyDeviceToHost, sa->q.stream));
+		HIPCHK(hipMemcpyAsync(dold.data(), sa->nbr.dold, sizeof(mgl_pk) * dold.size(), hipMemcpyDeviceToHost, sa->q.stream));
+		HIPCHK(hipMemcpyAsync(dnew.data(), sa->nbr.dnew, sizeof(mgl_pk) * dnew.size(), hipMemcpyDeviceToHost, sa->q.stream));
 	}
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	for (size_t j = 0; j < K; j++) {
 		if (ndiffs) ndiffs[j] = nd[j];
 		if (!diffs) continue;
@@ -2426,7 +2559,7 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 	}
 	if (!sa->incremental && what != 21 && what != 22) return fail(MGL_EINVAL, "mgl_debug_dump: handle runs the full-walk engine");
 	HIPCHK(hipSetDevice(sa->device));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	const Base2& b = sa->b2;
 	const void* src = nullptr;
 	size_t sz = 0;
@@ -2511,9 +2644,9 @@ extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_b
 extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 {
 	if (sa && key == 5) { /* the next (low word) batch accepts give up behind their commit; high word 0: before a chain is touched, n: behind the n-th context's rewrite */
-		sa->force_batch_late = (uint32_t)(value >> 32);
-		sa->force_batch_fail = (uint32_t)value;
-		if (sa->force_batch_late && !sa->force_batch_fail) sa->force_batch_fail = 1;
+		sa->force.batch_late = (uint32_t)(value >> 32);
+		sa->force.batch_fail = (uint32_t)value;
+		if (sa->force.batch_late && !sa->force.batch_fail) sa->force.batch_fail = 1;
 		return MGL_OK;
 	}
 	if (sa && key == 6) { /* limit `id` of the in-place accepts := value (at most the compiled / allocated one); 0: all back to their defaults */
@@ -2521,7 +2654,7 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 		const uint64_t v = value >> 8;
 		if (!sa->incremental || !sa->lim.why) return fail(MGL_EINVAL, "mgl_debug_set: no in-place accept on this handle");
 		HIPCHK(hipSetDevice(sa->device));
-		HIPCHK(hipStreamSynchronize(sa->stream));
+		HIPCHK(hipStreamSynchronize(sa->q.stream));
 		if (id == 0) {
 			if (v) return fail(MGL_EINVAL, "mgl_debug_set: limit id 0 takes value 0 (restore the defaults)");
 			for (uint32_t i = 1; i < MGL_LIM_COUNT; i++) sa->lim.v[i] = i == MGL_LIM_SOFT_REACH ? 0u : sa->lim_max.v[i];
@@ -2550,7 +2683,7 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 		sa->big_waves = (uint32_t)value;
 		return MGL_OK;
 	}
-	if (key == 8) { sa->force_xo_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` crossovers fail to allocate their buffers (MGL_ENOMEM) */
+	if (key == 8) { sa->force.xo_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` crossovers fail to allocate their buffers (MGL_ENOMEM) */
 	if (key == 9) { /* test of k_pick_order: overwrite the hint bytes (0: all 0, 1: all 1, 2: alternating, else: random from `value`) and make the order again */
 		if (!sa->d_pick_order) return fail(MGL_EINVAL, "mgl_debug_set: no launch order on this handle");
 		const uint32_t K = sa->cfg.neighbours_per_step, slices = nbr_slices(sa);
@@ -2561,15 +2694,15 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 			h[j] = value == 0 ? 0 : value == 1 ? 1 : value == 2 ? (unsigned char)(j & 1u) : (unsigned char)((x >> 40) % 3u); /* any non-zero byte is a picking neighbour */
 		}
 		HIPCHK(hipSetDevice(sa->device));
-		HIPCHK(hipStreamSynchronize(sa->stream));
-		HIPCHK(hipStreamSynchronize(sa->stream2));
+		HIPCHK(hipStreamSynchronize(sa->q.stream));
+		HIPCHK(hipStreamSynchronize(sa->q.stream2));
 		HIPCHK(hipMemcpy(sa->d_pick_hint, h.data(), K, hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, sa->stream, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
+		hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, sa->q.stream, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipStreamSynchronize(sa->stream));
+		HIPCHK(hipStreamSynchronize(sa->q.stream));
 		return MGL_OK;
 	}
-	if (key == 3) { sa->force_rollbacks = (uint32_t)value; return MGL_OK; } /* the next `value` bulk steps that take moves are taken back as if their parse had failed validation */
+	if (key == 3) { sa->force.rollbacks = (uint32_t)value; return MGL_OK; } /* the next `value` bulk steps that take moves are taken back as if their parse had failed validation */
 	return fail(MGL_EINVAL, "mgl_debug_set: unknown key");
 }
 

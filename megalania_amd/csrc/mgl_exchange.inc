@@ -269,11 +269,11 @@ static int comm_min_u64(mgl_sa* sa, mgl_comm* comm, uint64_t mine, uint64_t* out
 	}
 	if (!sa) return fail(MGL_EINVAL, "an RCCL all-reduce needs a chain (device scratch, stream)");
 	uint64_t* d_key = (uint64_t*)sa->d_topk_cost; /* 64 u64 of scratch */
-	HIPCHK(hipMemcpyAsync(d_key, &mine, sizeof mine, hipMemcpyHostToDevice, sa->stream));
-	const int nrc = comm->all_reduce(d_key, d_key + 1, 1, MGL_NCCL_UINT64, MGL_NCCL_MIN, comm->comm, sa->stream);
+	HIPCHK(hipMemcpyAsync(d_key, &mine, sizeof mine, hipMemcpyHostToDevice, sa->q.stream));
+	const int nrc = comm->all_reduce(d_key, d_key + 1, 1, MGL_NCCL_UINT64, MGL_NCCL_MIN, comm->comm, sa->q.stream);
 	if (nrc != 0) return fail(MGL_EDEVICE, std::string("ncclAllReduce: ") + (comm->errstr ? comm->errstr(nrc) : "?"));
-	HIPCHK(hipMemcpyAsync(out, d_key + 1, sizeof *out, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(out, d_key + 1, sizeof *out, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 /* one u64 of every rank, in rank order, to every rank (`all`: world entries).  The host form reads every key that comm_min_u64
@@ -295,14 +295,14 @@ static int comm_allgather_u64(mgl_sa* sa, mgl_comm* comm, uint64_t mine, uint64_
 		uint64_t* d = nullptr;
 	} tmp;
 	TRY(dnew(tmp.own, tmp.d, (size_t)comm->world + 1u));
-	HIPCHK(hipMemcpyAsync(tmp.d, &mine, sizeof mine, hipMemcpyHostToDevice, sa->stream));
-	const int nrc = comm->all_gather(tmp.d, tmp.d + 1, 1, MGL_NCCL_UINT64, comm->comm, sa->stream);
+	HIPCHK(hipMemcpyAsync(tmp.d, &mine, sizeof mine, hipMemcpyHostToDevice, sa->q.stream));
+	const int nrc = comm->all_gather(tmp.d, tmp.d + 1, 1, MGL_NCCL_UINT64, comm->comm, sa->q.stream);
 	if (nrc != 0) {
-		(void)hipStreamSynchronize(sa->stream); /* the copy above reads a local and writes what tmp frees */
+		(void)hipStreamSynchronize(sa->q.stream); /* the copy above reads a local and writes what tmp frees */
 		return fail(MGL_EDEVICE, std::string("ncclAllGather: ") + (comm->errstr ? comm->errstr(nrc) : "?"));
 	}
-	HIPCHK(hipMemcpyAsync(all, tmp.d + 1, sizeof(uint64_t) * (size_t)comm->world, hipMemcpyDeviceToHost, sa->stream));
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipMemcpyAsync(all, tmp.d + 1, sizeof(uint64_t) * (size_t)comm->world, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 /* n packed packets from `send` on the root's device into `recv` on everybody else's */
@@ -316,18 +316,18 @@ static int comm_broadcast_slab(mgl_sa* sa, mgl_comm* comm, const mgl_pk* send, m
 			if (fstat(comm->fd, &sb) != 0 || ((size_t)sb.st_size < need && ftruncate(comm->fd, (off_t)need) != 0))
 				return fail(MGL_EDEVICE, "mgl_comm (shm): cannot grow the file to hold the slab");
 			if ((rc = shm_remap(comm, need)) != MGL_OK) return rc;
-			HIPCHK(hipMemcpyAsync(comm->map + MGL_SHM_HDR_BYTES, send, sizeof(mgl_pk) * n, hipMemcpyDeviceToHost, sa->stream));
-			HIPCHK(hipStreamSynchronize(sa->stream));
+			HIPCHK(hipMemcpyAsync(comm->map + MGL_SHM_HDR_BYTES, send, sizeof(mgl_pk) * n, hipMemcpyDeviceToHost, sa->q.stream));
+			HIPCHK(hipStreamSynchronize(sa->q.stream));
 		}
 		if ((rc = shm_barrier(comm)) != MGL_OK) return rc; /* the slab is in the file */
 		if (comm->rank != root) {
 			if ((rc = shm_remap(comm, need)) != MGL_OK) return rc;
-			HIPCHK(hipMemcpyAsync(recv, comm->map + MGL_SHM_HDR_BYTES, sizeof(mgl_pk) * n, hipMemcpyHostToDevice, sa->stream));
-			HIPCHK(hipStreamSynchronize(sa->stream));
+			HIPCHK(hipMemcpyAsync(recv, comm->map + MGL_SHM_HDR_BYTES, sizeof(mgl_pk) * n, hipMemcpyHostToDevice, sa->q.stream));
+			HIPCHK(hipStreamSynchronize(sa->q.stream));
 		}
 		return shm_barrier(comm); /* everybody has its copy: the area may be overwritten */
 	}
-	const int nrc = comm->broadcast(comm->rank == root ? (const void*)send : (const void*)recv, recv, n, MGL_NCCL_UINT64, root, comm->comm, sa->stream);
+	const int nrc = comm->broadcast(comm->rank == root ? (const void*)send : (const void*)recv, recv, n, MGL_NCCL_UINT64, root, comm->comm, sa->q.stream);
 	if (nrc != 0) return fail(MGL_EDEVICE, std::string("ncclBroadcast: ") + (comm->errstr ? comm->errstr(nrc) : "?"));
 	return MGL_OK;
 }
@@ -356,8 +356,8 @@ static const mgl_pk* best_slab_device(mgl_sa* sa, const Control& c)
 /* packets_best := the packed slab at `src` (device), claimed cost `cost` */
 static int adopt_best_device(mgl_sa* sa, const mgl_pk* src, uint64_t cost, Control& c)
 {
-	HIPCHK(hipMemcpyAsync(sa->d_best, src, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
-	if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->stream));
+	HIPCHK(hipMemcpyAsync(sa->d_best, src, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
+	if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->q.stream));
 	c.best_cost = cost;
 	c.best_is_current = 0;
 	sa->best_unverified = true;
@@ -377,7 +377,7 @@ static int broadcast_best_and_adopt(mgl_sa* sa, mgl_comm* comm, Control& c, int 
 		if (adopted) *adopted = true;
 		return adopt_best_device(sa, recv, wcost, c);
 	}
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	return MGL_OK;
 }
 
@@ -412,8 +412,8 @@ extern "C" int mgl_sa_best_packed(mgl_sa* sa, uint64_t* packed_out, uint64_t* pe
 	if (rc) return rc;
 	if (perplexity_out) *perplexity_out = c.best_cost;
 	if (packed_out) {
-		HIPCHK(hipMemcpyAsync(packed_out, best_slab_device(sa, c), sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToHost, sa->stream));
-		HIPCHK(hipStreamSynchronize(sa->stream));
+		HIPCHK(hipMemcpyAsync(packed_out, best_slab_device(sa, c), sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToHost, sa->q.stream));
+		HIPCHK(hipStreamSynchronize(sa->q.stream));
 	}
 	return MGL_OK;
 }
@@ -424,7 +424,7 @@ extern "C" int mgl_sa_adopt_best_packed(mgl_sa* sa, const uint64_t* packed, uint
 	Control c;
 	int rc = read_ctl(sa, sa->base, &c);
 	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(sa->scratch.v.slab, packed, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyHostToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(sa->scratch.v.slab, packed, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyHostToDevice, sa->q.stream));
 	return adopt_best_device(sa, sa->scratch.v.slab, perplexity, c);
 }
 
@@ -432,8 +432,8 @@ extern "C" int mgl_sa_adopt_best_packed(mgl_sa* sa, const uint64_t* packed, uint
 /* packets_best := the packed slab at `src` (device) at its exact cost; `unverified`: checked when an epoch starts from it */
 static int xo_set_best(mgl_sa* sa, const mgl_pk* src, uint64_t cost, Control& c, bool unverified)
 {
-	HIPCHK(hipMemcpyAsync(sa->d_best, src, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
-	if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->stream));
+	HIPCHK(hipMemcpyAsync(sa->d_best, src, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
+	if (sa->d_snap_meta) HIPCHK(hipMemsetAsync(sa->d_snap_meta + 1, 0, sizeof(SnapMeta), sa->q.stream));
 	c.best_cost = cost;
 	c.best_is_current = 0;
 	sa->best_unverified = unverified;
@@ -450,7 +450,7 @@ static int cross_best_scratch(mgl_sa* sa, uint32_t grain, bool from_peer /* or f
 	if (c.best_cost == 0) {
 		/* no best slab yet: the walk mgl_sa_set_best uses says what `other` costs */
 		Control w;
-		HIPCHK(hipMemsetAsync(sa->scratch.ctl, 0, sizeof(Control), sa->stream));
+		HIPCHK(hipMemsetAsync(sa->scratch.ctl, 0, sizeof(Control), sa->q.stream));
 		if ((rc = launch_rebuild(sa, sa->scratch, 0, nullptr, nullptr))) return rc;
 		if ((rc = read_ctl(sa, sa->scratch, &w))) return rc;
 		if (w.error_flags) return fail(MGL_EINVAL, "slab is not a valid parse of the input");
@@ -461,8 +461,8 @@ static int cross_best_scratch(mgl_sa* sa, uint32_t grain, bool from_peer /* or f
 	}
 	XoBufs x;
 	if ((rc = xo_alloc(sa, x, 2))) return rc;
-	HIPCHK(hipMemcpyAsync(x.slabs, best_slab_device(sa, c), sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
-	HIPCHK(hipMemcpyAsync(x.slabs + sa->n, other, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->stream));
+	HIPCHK(hipMemcpyAsync(x.slabs, best_slab_device(sa, c), sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
+	HIPCHK(hipMemcpyAsync(x.slabs + sa->n, other, sizeof(mgl_pk) * (size_t)sa->n, hipMemcpyDeviceToDevice, sa->q.stream));
 	if ((rc = xo_run(sa, x, 2, grain, st))) return rc;
 	const uint64_t own = st->parent_cost[0], oth = st->parent_cost[1];
 	if (st->child_cost < own && st->child_cost < oth) {
@@ -473,7 +473,7 @@ static int cross_best_scratch(mgl_sa* sa, uint32_t grain, bool from_peer /* or f
 		rc = xo_set_best(sa, other, oth, c, from_peer);
 	}
 	if (rc) return rc;
-	HIPCHK(hipStreamSynchronize(sa->stream)); /* the buffers go away with x */
+	HIPCHK(hipStreamSynchronize(sa->q.stream)); /* the buffers go away with x */
 	return MGL_OK;
 }
 
@@ -508,7 +508,7 @@ extern "C" int mgl_sa_exchange_cross(mgl_sa* sa, mgl_comm* comm, uint32_t grain,
 	if (winner_cost) *winner_cost = wcost == MGL_KEY_NONE ? 0 : wcost;
 	if (wcost == MGL_KEY_NONE || comm->world == 1) return MGL_OK;
 	if ((rc = comm_broadcast_slab(sa, comm, best_slab_device(sa, c), sa->scratch.v.slab, (size_t)sa->n, winner)) != MGL_OK) return rc;
-	HIPCHK(hipStreamSynchronize(sa->stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	if (winner == comm->rank) return MGL_OK;
 	/* every other rank crosses its own best slab with the one that has just landed in the scratch slab */
 	mgl_cross_stats st;
@@ -554,7 +554,7 @@ static int cross_all_parents(mgl_sa* sa, mgl_comm* comm, Control& c, uint32_t D,
 	for (uint32_t p = 0; p < D; p++) {
 		mgl_pk* slot = x.slabs + (size_t)p * n;
 		const int owner = (int)parent_rank[p];
-		if (owner == comm->rank) HIPCHK(hipMemcpyAsync(slot, best_slab_device(sa, c), sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->stream));
+		if (owner == comm->rank) HIPCHK(hipMemcpyAsync(slot, best_slab_device(sa, c), sizeof(mgl_pk) * n, hipMemcpyDeviceToDevice, sa->q.stream));
 		if ((rc = comm_broadcast_slab(sa, comm, slot, slot, n, owner)) != MGL_OK) return rc;
 	}
 	if ((rc = xo_run(sa, x, D, grain, st))) return rc;
@@ -570,7 +570,7 @@ static int cross_all_parents(mgl_sa* sa, mgl_comm* comm, Control& c, uint32_t D,
 		rc = xo_set_best(sa, x.slabs, cheapest, c, true);
 	}
 	if (rc) return rc;
-	HIPCHK(hipStreamSynchronize(sa->stream)); /* the buffers go away with x */
+	HIPCHK(hipStreamSynchronize(sa->q.stream)); /* the buffers go away with x */
 	return MGL_OK;
 }
 

@@ -184,9 +184,6 @@ __device__ __forceinline__ void pick_prof_mark(PickProf* p, uint32_t stage, uint
  * of one level are issued together and waited for once -- from the position and the rep distances alone: no model, no price.
  * So the pick half makes it before it loads the model, and its handful of round trips stand in front of the checkpoint
  * copy, not behind it.  All fields are wave-uniform (they live in SGPRs). */
-#ifndef MGL_PICK_BATCH
-#define MGL_PICK_BATCH 1 /* 0: the pick half and the probe set their sources up in place, as the one-kernel form does (A/B) */
-#endif
 struct TopkPlan {
 	uint32_t lo, hi;          /* the bigram bucket's entries inside the scan window */
 	uint32_t wmin;            /* a hit lies at a position >= wmin (below) */
@@ -1277,8 +1274,8 @@ __global__ void __launch_bounds__(64) k_topk_probe(DevCtx c, BaseView b, uint32_
 	walk_window(w, c, b.slab, lane);
 	TopK t;
 	TopkPlan plan;
-	if (MGL_PICK_BATCH) topk_plan_make(plan, c, w.st, lane);
-	topk_find<4, MGL_PICK_BATCH != 0>(t, c, w, probs, T, lencost, walk_slab_at(w, position), lane, &plan);
+	topk_plan_make(plan, c, w.st, lane);
+	topk_find<4, true>(t, c, w, probs, T, lencost, walk_slab_at(w, position), lane, &plan);
 	if (lane < t.count) {
 		const uint32_t o = t.count - 1 - lane; /* worst first */
 		out_pk[o] = topk_packet(t.key, position);

@@ -740,9 +740,6 @@ struct BigScratch {
  *                 same code on the same inputs, but no launch boundary -- and so no wait for the slice's slowest top-K
  *                 query -- between a neighbour's pick and its walk.  Not the phase machine as one kernel (246 VGPRs):
  *                 nothing but a handful of wave-uniform scalars (PickHand) lives across the top-K. */
-#ifndef MGL_PICK_T_GLOBAL
-#define MGL_PICK_T_GLOBAL 1 /* the pick half reads the 4 KiB cost table through the vector cache instead of keeping a copy in LDS: 16 instead of 11 wavefronts per CU at 10 MB (c3 neighbour kernels - 5 %), no change at 100 KB */
-#endif
 #ifndef MGL_REST_WAVES_PER_SIMD
 #define MGL_REST_WAVES_PER_SIMD 4
 #endif
@@ -880,7 +877,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	 * lists only start to fill once the mutated packet is known.  A repair that needs another
 	 * top-K pick while the lists are live is handed to the BIG pass, whose lists are in global
 	 * memory.  This keeps 11 instead of 8 wavefronts per CU. */
-	unsigned char* mine = smem + ((MODE == MGL_NBR_REST || (MODE == MGL_NBR_PICK && MGL_PICK_T_GLOBAL)) ? 0u : 4096u) + (size_t)wid * per_wave_bytes;
+	unsigned char* mine = smem + ((MODE == MGL_NBR_REST || MODE == MGL_NBR_PICK) ? 0u : 4096u) + (size_t)wid * per_wave_bytes;
 	Journal jn;
 	jn.old = (mgl_pk*)mine;
 	jn.neu = jn.old + MGL_MAX_DIFFS;
@@ -1040,7 +1037,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	TopkPlan plan;
 	if (MODE == MGL_NBR_PICK) {
 		if (PROF) pick_prof_mark(&pp, 0, lane);
-		if (MGL_PICK_BATCH) topk_plan_make(plan, c, nb, lane);
+		topk_plan_make(plan, c, nb, lane);
 		if (PROF) pick_prof_mark(&pp, 1, lane);
 	}
 	if (MODE == MGL_NBR_REST && c.diag_stop != 0 && c.diag_stop != 4 && c.diag_stop < 40) return; /* diagnostic stops of the first half */
@@ -1166,7 +1163,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 			walk_window(tw, c, b.slab, lane);
 			mgl_pk picked;
 			bool ok;
-			if constexpr (MODE == MGL_NBR_PICK) ok = pick_from_top_k<4, MGL_PICK_BATCH != 0, PROF>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked, &plan, &pp);
+			if constexpr (MODE == MGL_NBR_PICK) ok = pick_from_top_k<4, true, PROF>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked, &plan, &pp);
 			else ok = pick_from_top_k<1>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked);
 			if (MODE == MGL_NBR_PICK) {
 				if (lane == 0) pickrec[j] = make_uint4((uint32_t)picked, (uint32_t)(picked >> 32), rng.n, ok ? 1u : 0u); /* fused, too: the second pass restarts from it */
@@ -1438,8 +1435,10 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_
 	if (BIG && threadIdx.x == 0) { CoopCmd* cmd = coop_cmd(smem, per_wave_bytes); cmd->gen = 0; cmd->op = MGL_COOP_SIM; }
 	/* 4 KiB as 256 16-byte units (the table is hipMalloc-aligned, T sits at the start of the LDS block); the second
 	 * half of the split form prices nothing (its re-simulation is k_sim's) and has no table: 4 KiB less per workgroup */
-	if ((MODE == MGL_NBR_PICK || MODE == MGL_NBR_PICKWALK) && MGL_PICK_T_GLOBAL) {
-		T = const_cast<uint16_t*>(c.cost_tbl); /* read through the vector cache: 4 KiB less LDS per pick workgroup */
+	if (MODE == MGL_NBR_PICK || MODE == MGL_NBR_PICKWALK) {
+		/* the pick half reads the 4 KiB cost table through the vector cache instead of keeping a copy in LDS: 16 instead of 11
+		 * wavefronts per CU at 10 MB (c3 neighbour kernels - 5 %), no change at 100 KB */
+		T = const_cast<uint16_t*>(c.cost_tbl);
 	} else if (MODE != MGL_NBR_REST) {
 		for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) reinterpret_cast<uint4*>(T)[i] = reinterpret_cast<const uint4*>(c.cost_tbl)[i];
 		__syncthreads();

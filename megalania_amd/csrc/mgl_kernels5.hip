@@ -54,8 +54,13 @@
 #define MGL_BATCH_GAP 32u      /* events of a context further apart than this start a group of their own */
 #define MGL_BATCH_ALLOC (MGL_BATCH_MAX * MGL_BATCH_EVCAP) /* entries of the combined event lists (ApplyBuf lists are allocated this long) */
 
+/* BatchBuf::hdr[0], the batch accept's status: every kernel of it looks here first, the host reads it back once per bulk step */
+#define MGL_BATCH_NONE 0u    /* the step took no move: nothing to do */
+#define MGL_BATCH_BEGAN 1u   /* a batch accept is under way; read back by the host: it gave up behind its commit, the rebuild finishes the step */
+#define MGL_BATCH_REBUILD 2u /* left to the rebuild: more moves than a batch accept handles, or it gave up before anything was touched */
+#define MGL_BATCH_DONE 3u    /* the moves are in */
 struct BatchBuf {
-	uint32_t* hdr;      /* [0] status: 0 nothing to do, 1 batch accept, 2 left to the rebuild; [1] clusters; [2] inserted events,
+	uint32_t* hdr;      /* [0] status (MGL_BATCH_NONE / BEGAN / REBUILD / DONE); [1] clusters; [2] inserted events,
 	                     * [3] removed events (combined lists); [4] failure seen by a kernel (1 a walk gave up, 2 a walk met an invalid packet,
 	                     * 4 the clusters gave up); [5] journal entries; [6] touched contexts; [9] / [13] / [12] test hook (mgl_debug_set key 5):
 	                     * give up at the top of k_batch_chains / behind the [13]-th context's rewrite / contexts that got that far */
@@ -95,7 +100,7 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 	const uint32_t m = (uint32_t)bb.hdr[1];
 	if (tid == 0) {
 		s_bad = 0; s_ncl = 0;
-		bt.hdr[0] = m == 0 ? 0u : (m > MGL_BATCH_MAX ? 2u : 1u);
+		bt.hdr[0] = m == 0 ? MGL_BATCH_NONE : (m > MGL_BATCH_MAX ? MGL_BATCH_REBUILD : MGL_BATCH_BEGAN);
 		bt.hdr[1] = 0; bt.hdr[2] = 0; bt.hdr[3] = 0; bt.hdr[4] = 0; bt.hdr[5] = 0; bt.hdr[6] = 0;
 		bt.hdr[8] = 0; bt.hdr[12] = 0;
 		bt.hdr[7] = (uint32_t)bb.hdr[0]; /* acceptable neighbours of this step: the host sizes the next step's selection by it */
@@ -170,7 +175,7 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 	__syncthreads();
 	if (tid == 0) {
 		bt.hdr[1] = s_ncl; bt.hdr[5] = tot;
-		if (s_bad) { bt.hdr[0] = 2u; bt.hdr[4] = 4u; atomicOr(lim.why, s_bad); } /* nothing has been touched: the rebuild takes the step */
+		if (s_bad) { bt.hdr[0] = MGL_BATCH_REBUILD; bt.hdr[4] = 4u; atomicOr(lim.why, s_bad); } /* nothing has been touched: the rebuild takes the step */
 	}
 }
 
@@ -200,7 +205,7 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 {
 	__shared__ uint32_t s_jpos[MGL_BATCH_JCAP];
 	__shared__ mgl_pk s_jnew[MGL_BATCH_JCAP];
-	if (bt.hdr[0] != 1u) return;
+	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
 	const uint32_t cl = blockIdx.x, lane = threadIdx.x;
 	if (cl >= bt.hdr[1]) return;
 	const uint32_t j0 = bt.cl[cl * 8u], nd = bt.cl[cl * 8u + 1u];
@@ -373,8 +378,8 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 /* ------------------------------------------------------------------ commit: every walk has finished, nothing reads the old base any more */
 __global__ void __launch_bounds__(256) k_batch_commit(DevCtx c, Base2 b, Control* ctl, BatchBuf bt, ApplyBuf ab)
 {
-	if (bt.hdr[0] != 1u) return;
-	if (bt.hdr[4]) { if (blockIdx.x == 0 && threadIdx.x == 0) bt.hdr[0] = 2u; return; } /* a walk gave up: nothing has been touched, the rebuild takes the step */
+	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
+	if (bt.hdr[4]) { if (blockIdx.x == 0 && threadIdx.x == 0) bt.hdr[0] = MGL_BATCH_REBUILD; return; } /* a walk gave up: nothing has been touched, the rebuild takes the step */
 	const uint32_t cl = blockIdx.x, tid = threadIdx.x, ncl = bt.hdr[1];
 	if (cl >= ncl) return;
 	(void)c; (void)ctl;
@@ -425,7 +430,7 @@ __global__ void __launch_bounds__(256) k_batch_commit(DevCtx c, Base2 b, Control
 __global__ void __launch_bounds__(1024) k_batch_scan(BatchBuf bt, ApplyBuf ab)
 {
 	__shared__ uint32_t s_wi[16], s_wr[16], s_bi, s_br, s_nt;
-	if (bt.hdr[0] != 1u) return;
+	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
 	if (tid == 0) { s_bi = 0; s_br = 0; s_nt = 0; ab.hdr[4] = 0; ab.hdr[5] = 0; ab.hdr[6] = 0; ab.hdr[7] = 0; } /* + the job / span / scratch cursors of k_apply_jobs' lists */
 	__syncthreads();
@@ -452,7 +457,7 @@ __global__ void __launch_bounds__(1024) k_batch_scan(BatchBuf bt, ApplyBuf ab)
 /* every event of the combined lists into its context's bucket */
 __global__ void __launch_bounds__(256) k_batch_fill(BatchBuf bt, ApplyBuf ab)
 {
-	if (bt.hdr[0] != 1u) return;
+	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
 	const uint32_t n_ins = bt.hdr[2], n_rem = bt.hdr[3];
 	for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n_ins + n_rem; e += gridDim.x * blockDim.x) {
 		if (e < n_ins) {
@@ -745,7 +750,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 	__shared__ uint32_t s_hlist[MGL_BATCH_MAX], s_hspan[MGL_BATCH_MAX + 1], s_gat[MGL_BATCH_MAX], s_hjb[MGL_BATCH_MAX], s_hjc[MGL_BATCH_MAX], s_hscr[MGL_BATCH_MAX];
 	__shared__ int32_t s_hdelta[MGL_BATCH_MAX + 1]; /* length change accumulated up to and including head h */
 	__shared__ uint32_t s_ng, s_nh, s_fail, s_scr_base, s_job_b, s_job_c, s_newoff, s_newcap, s_newlen, s_maxd;
-	if (bt.hdr[0] != 1u || bt.hdr[4]) return;
+	if (bt.hdr[0] != MGL_BATCH_BEGAN || bt.hdr[4]) return;
 	if (bt.hdr[9]) { if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->apply_failed = 1; atomicOr(lim.why, MGL_GU_FORCED_EARLY); } return; } /* test hook (mgl_debug_set key 5): give up behind the commit */
 	/* one workgroup per touched context (k_batch_scan lists them: a tenth of the contexts on a step of fifteen moves), the
 	 * grid strides over the list */
@@ -1011,7 +1016,7 @@ __global__ void __launch_bounds__(256) k_batch_ckpt(Base2 b, const Control* ctl,
 {
 	__shared__ uint32_t s_pos[MGL_BATCH_CK_SPAN];
 	__shared__ uint16_t s_ev[MGL_BATCH_CK_SPAN];
-	if (bt.hdr[0] != 1u || bt.hdr[4] || ctl->apply_failed) return;
+	if (bt.hdr[0] != MGL_BATCH_BEGAN || bt.hdr[4] || ctl->apply_failed) return;
 	const uint32_t nruns = bt.hdr[8] < bt.runs_cap ? bt.hdr[8] : bt.runs_cap;
 	for (uint32_t ri = blockIdx.x; ri < nruns; ri += gridDim.x) {
 		const uint4 r0 = bt.runs[2u * ri], r1 = bt.runs[2u * ri + 1u];
@@ -1046,9 +1051,9 @@ __global__ void __launch_bounds__(256) k_batch_ckpt(Base2 b, const Control* ctl,
 __global__ void k_batch_end(Control* ctl, BatchBuf bt)
 {
 	if (threadIdx.x || blockIdx.x) return;
-	if (bt.hdr[0] != 1u || ctl->apply_failed) return;
+	if (bt.hdr[0] != MGL_BATCH_BEGAN || ctl->apply_failed) return;
 	const uint64_t base_cost = ctl->cur_cost ? ctl->cur_cost : ctl->rebuild_cost;
 	ctl->rebuild_cost = (uint64_t)((long long)base_cost + bt.acc[0] + bt.acc[1]);
 	ctl->packets = (uint64_t)((long long)ctl->packets + bt.acc[2]);
-	bt.hdr[0] = 3u; /* done */
+	bt.hdr[0] = MGL_BATCH_DONE;
 }
