@@ -21,8 +21,6 @@
  */
 #include "mgl_device.h"
 
-#define MGL_ADP_MAX_PROBS (MGL_OFF_LIT + (0x300u << 4) + 1u) /* 14 135 rounded up to an even count */
-
 /* u16 per snapshot: the model, padded to whole u32 words */
 __host__ __device__ static inline uint32_t adp_stride(const mgl_layout& L) { return (L.total + 1u) & ~1u; }
 
@@ -45,7 +43,7 @@ __global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const AdpVarian
                                                        int resolve, uint32_t chunk, uint32_t nch, uint32_t* entry, uint16_t* snaps, uint64_t* cost)
 {
 	__shared__ uint16_t T[2048];
-	__shared__ __align__(4) uint16_t probs[MGL_ADP_MAX_PROBS];
+	__shared__ __align__(4) uint16_t probs[MGL_MAX_PROBS];
 	const uint32_t lane = threadIdx.x, v = blockIdx.x;
 	const AdpVariant t = tab[v];
 	const mgl_layout L = adp_variant_layout(t);
@@ -62,8 +60,8 @@ __global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const AdpVarian
 	wave_sync();
 	while (st.pos < c.n) {
 		const uint32_t pos = st.pos;
-		walk_window(w, c, in, lane);
-		const mgl_pk pk = walk_slab_at(w, pos);
+		win_cover(w.win, c, in, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, pos);
 		uint32_t type = mgl_pk_type(pk), dist = mgl_pk_dist(pk), len = mgl_pk_len(pk);
 		if (len == 0 || len > c.n - pos) break; /* leaves the input: never taken (see below) */
 		if (snaps) {
@@ -85,22 +83,7 @@ __global__ void __launch_bounds__(64) k_adp_snap_sweep(DevCtx c, const AdpVarian
 		/* what is planned is a packet (mgl_model.h): a DP's copy is one once it is resolved (before that its distance is
 		 * absolute, whatever its type), a slab from outside has been through the walk of mgl_cost_slab.  Never taken. */
 		if (!mgl_pk_wellformed(type, dist, len)) break;
-		uint32_t match_byte = 0, prev_byte = 0;
-		if (type == MGL_LITERAL) {
-			if (st.ctx_state >= 7 && st.dists[0] < pos) match_byte = c.data[pos - st.dists[0] - 1];
-			if (L.lc > 0 && pos > 0) prev_byte = pos > w.wbase ? walk_byte_at(w, pos - 1u) : c.data[pos - 1];
-		}
-		mgl_plan pl;
-		mgl_plan_packet(&L, &st, type, dist, len, walk_byte_at(w, pos), match_byte, prev_byte, &pl);
-		if (lane < pl.nev) {
-			uint32_t ctx, bit;
-			mgl_plan_event(&pl, lane, &ctx, &bit); /* no slot occurs twice in one packet */
-			const uint32_t p = probs[ctx];
-			w.acc += T[bit ? 2048u - p : p];
-			probs[ctx] = (uint16_t)mgl_prob_update(p, bit);
-		}
-		if (lane == 0) w.acc += (uint64_t)pl.ndirect << 11;
-		mgl_advance(&st, type, dist, len);
+		walk_packet<true>(w, L, c.data, probs, T, type, dist, len, lane);
 		wave_sync();
 	}
 	const uint64_t total = wave_sum64(w.acc);
@@ -157,10 +140,7 @@ __global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant*
 		for (uint32_t k = lane; k < stride / 2u; k += 64u) dst[k] = src[k];
 	}
 	/* the anchor: position a, its exact walk state A (uniform) */
-	mgl_wstate A;
-	A.pos = s; A.ctx_state = entry[5u * m];
-	A.dists[0] = entry[5u * m + 1u]; A.dists[1] = entry[5u * m + 2u];
-	A.dists[2] = entry[5u * m + 3u]; A.dists[3] = entry[5u * m + 4u];
+	mgl_wstate A = state_from_words(entry + 5u * m, s);
 	uint64_t obj = 0;
 	__syncthreads();
 
@@ -189,13 +169,8 @@ __global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant*
 			const uint32_t dist = type == MGL_MATCH ? mgl_pk_dist(raw) - 1u : type == MGL_LONG_REP ? (uint32_t)(raw >> MGL_OPT_REP_SHIFT) & 3u : 0u;
 			if (len == 0u || len > e - pos) { pos = e; break; } /* the path is contiguous: never taken */
 			if (type == MGL_LONG_REP && lane == 0) out[pos] = raw & ((1ull << MGL_OPT_REP_SHIFT) - 1ull);
-			uint32_t match_byte = 0, prev_byte = 0;
-			if (type == MGL_LITERAL) {
-				if (A.ctx_state >= 7u && A.dists[0] < pos) match_byte = d[pos - A.dists[0] - 1u];
-				if (L.lc > 0u && pos > 0u) prev_byte = d[pos - 1u];
-			}
 			mgl_plan pl;
-			mgl_plan_packet(&L, &A, type, dist, len, d[pos], match_byte, prev_byte, &pl);
+			plan_at(L, d, A, type, dist, len, d[pos], pl); /* A.pos == pos */
 			if (lane < pl.nev) {
 				uint32_t ctx, bit;
 				mgl_plan_event(&pl, lane, &ctx, &bit); /* no slot occurs twice in one packet */

@@ -173,27 +173,25 @@ __device__ __forceinline__ uint32_t sp_find_next(const Base2& b, uint32_t x)
 	return (w << 6) + ctz64(b.sp0[w]);
 }
 
-/* n literal transitions of the ctx_state automaton (lzma_state.c:33-41); 3 reach 0 from anywhere */
-__device__ __forceinline__ uint32_t lit_steps(uint32_t s, uint32_t n)
+/* The state record of the special packet at pos: ctx_state and the four rep distances before it.  For lanes 0..7 only: the
+ * caller folds `lane < 8` into its own condition, so that the store needs no branch of its own.  The state comes by value:
+ * its five words are then plain values when the lane's choice is compiled, and the choice stays a chain of selects. */
+__device__ __forceinline__ void state_record_write(const Base2& b, uint32_t pos, const mgl_wstate st, uint32_t lane)
 {
-	if (n > 3) n = 3;
-	for (uint32_t i = 0; i < n; i++) s = mgl_next_ctx_state(s, MGL_LITERAL);
-	return s;
+	const uint32_t v = lane == 0 ? st.ctx_state : lane == 1 ? st.dists[0] : lane == 2 ? st.dists[1]
+	                 : lane == 3 ? st.dists[2] : lane == 4 ? st.dists[3] : 0u;
+	b.sp_state[(size_t)pos * 8 + lane] = v;
 }
 
 /* Walk state before the base packet that starts at x (x must be on the base walk). */
 __device__ __forceinline__ mgl_wstate base_state_at(const Base2& b, uint32_t x)
 {
-	mgl_wstate st;
-	st.pos = x; st.ctx_state = 0;
-	st.dists[0] = st.dists[1] = st.dists[2] = st.dists[3] = 0;
+	mgl_wstate st = state_initial();
+	st.pos = x;
 	if (x == 0) return st;
 	uint32_t s = sp_find_prev(b, x - 1);
 	if (s == MGL_POS_INF) return st; /* only literals so far: state 0, distances 0 */
-	const uint32_t* r = b.sp_state + (size_t)s * 8;
-	mgl_wstate t;
-	t.pos = s; t.ctx_state = r[0];
-	t.dists[0] = r[1]; t.dists[1] = r[2]; t.dists[2] = r[3]; t.dists[3] = r[4];
+	mgl_wstate t = state_from_words(b.sp_state + (size_t)s * 8, s);
 	const mgl_pk pk = b.slab[s];
 	mgl_advance(&t, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk));
 	st.ctx_state = lit_steps(t.ctx_state, x - t.pos);

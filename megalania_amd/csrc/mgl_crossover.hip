@@ -31,7 +31,6 @@
 #include "mgl_device.h"
 
 #define MGL_XO_PARENTS 8u
-#define MGL_XO_MAX_PROBS (MGL_OFF_LIT + (0x300u << 4) + 1u)
 
 /* device counters of one call */
 struct XoCounters {
@@ -53,7 +52,7 @@ struct XoView {
 __global__ void __launch_bounds__(64) k_xo_walk(DevCtx c, XoView v, XoCounters* cnt)
 {
 	__shared__ uint16_t T[2048];
-	__shared__ uint16_t probs[MGL_XO_MAX_PROBS];
+	__shared__ uint16_t probs[MGL_MAX_PROBS];
 	const uint32_t lane = threadIdx.x, p = blockIdx.x;
 	const mgl_pk* slab = v.slab + (size_t)p * c.n;
 	uint64_t* cost = v.cost + (size_t)p * ((size_t)c.n + 1u);
@@ -69,8 +68,8 @@ __global__ void __launch_bounds__(64) k_xo_walk(DevCtx c, XoView v, XoCounters* 
 	bool bad = false;
 	while (w.st.pos < c.n) {
 		const uint32_t pos = w.st.pos;
-		walk_window(w, c, slab, lane);
-		const mgl_pk pk = walk_slab_at(w, pos);
+		win_cover(w.win, c, slab, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, pos);
 		const uint32_t type = mgl_pk_type(pk), dist = mgl_pk_dist(pk), len = mgl_pk_len(pk);
 		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) { bad = true; break; }
 		const uint64_t before = wave_sum64(w.acc);
@@ -82,7 +81,7 @@ __global__ void __launch_bounds__(64) k_xo_walk(DevCtx c, XoView v, XoCounters* 
 		bits |= 1ull << (pos & 63u);
 		if (lane == 0) cost[pos] = before;
 		if (lane < 5u) state[(size_t)pos * 5u + lane] = lane == 0 ? w.st.ctx_state : mgl_dist_at(&w.st, lane - 1u);
-		walk_packet<true>(w, c, probs, T, type, dist, len, lane);
+		walk_packet<true>(w, c.L, c.data, probs, T, type, dist, len, lane);
 	}
 	const uint64_t total = wave_sum64(w.acc);
 	if (lane == 0) {

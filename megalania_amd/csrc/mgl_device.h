@@ -1,5 +1,5 @@
 /*
- * mgl_device.h -- device-side building blocks shared by the kernels in mgl_kernels.hip.
+ * mgl_device.h -- device-side building blocks shared by every kernel file of the library (mgl_api.hip includes them all as one translation unit).
  * gfx950 only: 64-lane wavefronts, probabilities and the bit-cost table in LDS.
  *
  * Conventions
@@ -201,51 +201,91 @@ __device__ __forceinline__ void wave_sync()
 }
 
 /* ------------------------------------------------------------------ the slab walk */
+
+/* the 64-position register window every walk reads the slab and the input through */
+struct Win { /* no padding in this order: a Walk handed to top-K by reference lives in scratch, and its size shows there */
+	uint32_t base; /* positions [base, base + 64) */
+	uint32_t byte;
+	mgl_pk pk;
+};
+__device__ __forceinline__ void win_reset(Win& w) { w.base = 0xFFFFFFFFu; w.pk = 0; w.byte = 0; }
+/* make the window cover pos */
+__device__ __forceinline__ void win_cover(Win& w, const DevCtx& c, const mgl_pk* slab, uint32_t pos, uint32_t lane)
+{
+	const uint32_t base = pos & ~63u;
+	if (base != w.base) {
+		const uint32_t p = base + lane;
+		w.pk = p < c.n ? slab[p] : 0;
+		w.byte = c.data[p < c.n ? p : c.n]; /* data has >= 64 bytes of zero padding */
+		w.base = base;
+	}
+}
+__device__ __forceinline__ mgl_pk win_pk(const Win& w, uint32_t pos) { return rdlane64(w.pk, pos - w.base); }
+__device__ __forceinline__ uint32_t win_byte(const Win& w, uint32_t pos) { return rdlane(w.byte, pos - w.base); }
+
+/* the LZMA initial state, at position 0 */
+__device__ __forceinline__ mgl_wstate state_initial()
+{
+	mgl_wstate st;
+	st.pos = 0; st.ctx_state = 0;
+	st.dists[0] = st.dists[1] = st.dists[2] = st.dists[3] = 0;
+	return st;
+}
+/* the state at pos from five stored words: ctx_state and the four rep distances */
+__device__ __forceinline__ mgl_wstate state_from_words(const uint32_t* s, uint32_t pos)
+{
+	mgl_wstate st;
+	st.pos = pos; st.ctx_state = s[0];
+	st.dists[0] = s[1]; st.dists[1] = s[2]; st.dists[2] = s[3]; st.dists[3] = s[4];
+	return st;
+}
+
 struct Walk {
 	mgl_wstate st;   /* uniform */
 	uint64_t acc;    /* per-lane partial perplexity */
-	uint32_t wbase;  /* window: positions [wbase, wbase+64) */
-	mgl_pk wpk;
-	uint32_t wbyte;
+	Win win;
 	uint32_t packets;
 };
 
 __device__ __forceinline__ void walk_reset(Walk& w)
 {
-	w.st.pos = 0; w.st.ctx_state = 0;
-	w.st.dists[0] = w.st.dists[1] = w.st.dists[2] = w.st.dists[3] = 0;
-	w.acc = 0; w.wbase = 0xFFFFFFFFu; w.wpk = 0; w.wbyte = 0; w.packets = 0;
+	w.st = state_initial();
+	w.acc = 0; win_reset(w.win); w.packets = 0;
 }
 
-/* make the window cover st.pos */
-__device__ __forceinline__ void walk_window(Walk& w, const DevCtx& c, const mgl_pk* slab, uint32_t lane)
+/* n literal transitions of the ctx_state automaton (lzma_state.c:33-41); 3 reach 0 from anywhere */
+__device__ __forceinline__ uint32_t lit_steps(uint32_t s, uint32_t n)
 {
-	uint32_t base = w.st.pos & ~63u;
-	if (base != w.wbase) {
-		uint32_t p = base + lane;
-		w.wpk = p < c.n ? slab[p] : 0;
-		w.wbyte = c.data[p < c.n ? p : c.n]; /* data has >= 64 bytes of zero padding */
-		w.wbase = base;
-	}
+	if (n > 3) n = 3;
+	for (uint32_t i = 0; i < n; i++) s = mgl_next_ctx_state(s, MGL_LITERAL);
+	return s;
 }
-__device__ __forceinline__ mgl_pk walk_slab_at(const Walk& w, uint32_t pos) { return rdlane64(w.wpk, pos - w.wbase); }
-__device__ __forceinline__ uint32_t walk_byte_at(const Walk& w, uint32_t pos) { return rdlane(w.wbyte, pos - w.wbase); }
 
-/* Cost one packet at the walk's position against the adaptive model in LDS and advance.
- * UPDATE=false leaves probabilities untouched (candidate costing) and does not advance. */
-template <bool UPDATE>
-__device__ __forceinline__ void walk_packet(Walk& w, const DevCtx& c, uint16_t* probs, const uint16_t* T,
-                                            uint32_t type, uint32_t dist, uint32_t len, uint32_t lane)
+/* the whole probability model under the largest layout (lc + lp = 4): 14 135 rounded up to an even count */
+#define MGL_MAX_PROBS (MGL_OFF_LIT + (0x300u << 4) + 1u)
+
+/* Plan the packet (type, dist, len) that starts at st.pos, whose first input byte is `byte`, under layout L: the one place
+ * that fetches a literal's match byte and previous byte. */
+__device__ __forceinline__ void plan_at(const mgl_layout& L, const uint8_t* data, const mgl_wstate& st, uint32_t type, uint32_t dist,
+                                        uint32_t len, uint32_t byte, mgl_plan& pl)
 {
-	uint32_t pos = w.st.pos;
-	uint32_t byte = walk_byte_at(w, pos);
 	uint32_t match_byte = 0, prev_byte = 0;
 	if (type == MGL_LITERAL) {
-		if (w.st.ctx_state >= 7 && w.st.dists[0] < pos) match_byte = c.data[pos - w.st.dists[0] - 1];
-		if (c.L.lc > 0 && pos > 0) prev_byte = c.data[pos - 1];
+		if (st.ctx_state >= 7 && st.dists[0] < st.pos) match_byte = data[st.pos - st.dists[0] - 1];
+		if (L.lc > 0 && st.pos > 0) prev_byte = data[st.pos - 1];
 	}
+	mgl_plan_packet(&L, &st, type, dist, len, byte, match_byte, prev_byte, &pl);
+}
+
+/* Cost one packet at the walk's position against the adaptive model in LDS (laid out by L) and advance.
+ * Lane e takes event slot e; no slot occurs twice in one packet, so the lanes' read-modify-writes do not meet.
+ * UPDATE=false leaves probabilities untouched (candidate costing) and does not advance. */
+template <bool UPDATE>
+__device__ __forceinline__ void walk_packet(Walk& w, const mgl_layout& L, const uint8_t* data, uint16_t* probs, const uint16_t* T,
+                                            uint32_t type, uint32_t dist, uint32_t len, uint32_t lane)
+{
 	mgl_plan pl;
-	mgl_plan_packet(&c.L, &w.st, type, dist, len, byte, match_byte, prev_byte, &pl);
+	plan_at(L, data, w.st, type, dist, len, win_byte(w.win, w.st.pos), pl);
 	if (lane < pl.nev) {
 		uint32_t ctx, bit;
 		mgl_plan_event(&pl, lane, &ctx, &bit);
@@ -258,4 +298,49 @@ __device__ __forceinline__ void walk_packet(Walk& w, const DevCtx& c, uint16_t* 
 		mgl_advance(&w.st, type, dist, len);
 		w.packets++;
 	}
+}
+
+/* ------------------------------------------------------------------ runs of plain literals
+ * Where a walk meets a run of plain literals (ctx_state < 7, so no match byte), up to seven of them are planned at once,
+ * nine lanes each (is_match + the eight bits of the literal tree: 7 x 9 = 63 lanes), instead of one per turn of the walk
+ * loop.  Uses only the slab / input window in registers.  What a caller does with its lane's event differs: the neighbour
+ * kernel and the two accept walks append it to a change list, the model replay and the parallel builder go through the
+ * run's packets one by one (the packets share contexts -- is_match and the top of the literal tree -- and probability
+ * updates and chain ranks have to stay in position order). */
+struct LitLane {
+	bool active;      /* this lane holds an event of the run ... */
+	uint32_t i, p;    /* ... of its literal i, at position p; the event's place in the run is `lane` itself (9 i + slot) */
+	uint32_t ctx, bit;
+};
+/* How many literals of the run that begins at offset o of the window to plan at once: the consecutive literals from there
+ * on (each one's successor is on the walk), cut at the window's edge, at `limit` and at seven.  0: fewer than two -- take
+ * the packet-at-a-time path.  The caller has checked that ctx_state < 7. */
+__device__ __forceinline__ uint32_t lit_run_take(bool lane_is_literal, uint32_t o, uint32_t limit)
+{
+	const unsigned long long lit = __ballot(lane_is_literal) >> o; /* window entries from the walk's position on */
+	uint32_t run = ~lit == 0ull ? 64u : (uint32_t)__ffsll((long long)~lit) - 1u;
+	run = run < 64u - o ? run : 64u - o;
+	run = run < limit ? run : limit;
+	return run < 2u ? 0u : run < 7u ? run : 7u;
+}
+/* Plan literals st.pos .. st.pos + take - 1 and hand each lane its event.  false: a literal's plan is not the 1 + 8 events
+ * assumed above (the caller takes the run one packet at a time).  Does not advance st. */
+__device__ __forceinline__ bool lit_run_plan(const DevCtx& c, const Win& win, const mgl_wstate& st, uint32_t take, uint32_t lane, LitLane& out)
+{
+	const uint32_t i = lane / 9u, p = st.pos + i;
+	out.active = i < take; out.i = i; out.p = p;
+	const uint32_t byte = (uint32_t)__shfl((int)win.byte, (int)((p - win.base) & 63u), 64);
+	uint32_t prev_byte = 0;
+	if (c.L.lc > 0) { /* the window's first position has its previous byte in the input only */
+		const uint32_t wprev = (uint32_t)__shfl((int)win.byte, (int)((p - 1u - win.base) & 63u), 64);
+		prev_byte = p == 0 ? 0u : (p - 1u >= win.base ? wprev : (uint32_t)c.data[p - 1u]);
+	}
+	mgl_wstate sv = st;
+	sv.pos = p; sv.ctx_state = lit_steps(st.ctx_state, i);
+	mgl_plan pl;
+	mgl_plan_packet(&c.L, &sv, MGL_LITERAL, 0, 1, byte, 0, prev_byte, &pl);
+	if (__ballot(out.active && pl.nev != 9u)) return false;
+	out.ctx = 0; out.bit = 0;
+	if (out.active) mgl_plan_event(&pl, lane - i * 9u, &out.ctx, &out.bit);
+	return true;
 }

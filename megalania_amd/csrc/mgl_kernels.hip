@@ -390,7 +390,7 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 	/* LITERAL and SHORT_REP, packet_enumerator.c:60-66 */
 	{
 		uint64_t cand = MGL_INVALID_COST;
-		uint32_t byte = walk_byte_at(w, pos);
+		uint32_t byte = win_byte(w.win, pos);
 		uint32_t rep_byte = (pos > 0 && w.st.dists[0] < pos) ? c.data[pos - w.st.dists[0] - 1] : 0x100u;
 		uint32_t prev_byte = (c.L.lc > 0 && pos > 0) ? c.data[pos - 1] : 0;
 		mgl_plan pl;
@@ -415,7 +415,7 @@ __device__ void topk_find(TopK& t, const DevCtx& c, const Walk& w, const uint16_
 	uint32_t lo, hi, bigram = 0;
 	if (BATCH) { lo = plan->lo; hi = plan->hi; }
 	else {
-		bigram = ((uint32_t)walk_byte_at(w, pos) << 8) | c.data[pos + 1];
+		bigram = ((uint32_t)win_byte(w.win, pos) << 8) | c.data[pos + 1];
 		lo = c.bucket_off[bigram];
 		const uint32_t end = c.bucket_off[bigram + 1];
 		hi = bucket_lower_bound(c.bucket_pos, lo, end, pos, lane); /* hits are < pos */
@@ -839,14 +839,14 @@ __global__ void __launch_bounds__(64) k_rebuild(DevCtx c, BaseView b, Control* c
 			word = pw; bits = 0;
 		}
 		bits |= 1ull << (pos & 63u);
-		walk_window(w, c, b.slab, lane);
-		const mgl_pk pk = walk_slab_at(w, pos);
+		win_cover(w.win, c, b.slab, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, pos);
 		uint32_t type = mgl_pk_type(pk), len = mgl_pk_len(pk), dist = mgl_pk_dist(pk);
 		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) { /* not a packet (mgl_model.h): cost as literal */
 			type = MGL_LITERAL; len = 1; dist = 0;
 			if (lane == 0) atomicOr(&ctl->error_flags, MGL_ERR_WALK_OVERRUN);
 		}
-		walk_packet<true>(w, c, probs, T, type, dist, len, lane);
+		walk_packet<true>(w, c.L, c.data, probs, T, type, dist, len, lane);
 		if (cum_out) {
 			uint64_t cum = base_cum + wave_sum64(w.acc);
 			if (lane == 0) cum_out[w.packets - 1] = cum;
@@ -940,13 +940,6 @@ __device__ __forceinline__ mgl_pk journal_or_base(const Journal& jn, const mgl_p
  * mutated one (the incremental kernel stops its two-pointer walk there).  The
  * full-walk engine has walked to the end of the file, so it finds the point afterwards from the
  * journal.  `st` = walk state at the target (uniform). */
-/* n literal transitions of the ctx_state automaton (3 reach 0 from anywhere) */
-__device__ __forceinline__ uint32_t lit_steps_(uint32_t s, uint32_t n)
-{
-	if (n > 3) n = 3;
-	for (uint32_t i = 0; i < n; i++) s = mgl_next_ctx_state(s, MGL_LITERAL);
-	return s;
-}
 struct WinInfo { uint32_t end, soft, n_ins, n_rem, walked; };
 /* events of one packet (mgl_plan_packet's nev: independent of the bytes) */
 __device__ __forceinline__ uint32_t packet_events(const DevCtx& c, const mgl_wstate& st, mgl_pk pk)
@@ -969,7 +962,7 @@ __device__ WinInfo window_end_from_journal(const DevCtx& c, const mgl_pk* slab, 
 				uint32_t sx = nb.pos;
 				while (sx < c.n && mgl_pk_type(uni64(slab[sx])) == MGL_LITERAL) sx++;
 				if (sx > nb.pos) {
-					const uint32_t cs = lit_steps_(nb.ctx_state, sx - nb.pos);
+					const uint32_t cs = lit_steps(nb.ctx_state, sx - nb.pos);
 					nb.pos = bs.pos = sx; nb.ctx_state = bs.ctx_state = cs;
 					count = 8;
 					continue;
@@ -1086,9 +1079,9 @@ __device__ void nbr_fullwalk_one(const DevCtx& c, const BaseView& b, const Contr
 	}
 	const uint32_t first_packet = w.packets;
 	while (w.st.pos < target) {
-		walk_window(w, c, b.slab, lane);
-		const mgl_pk pk = walk_slab_at(w, w.st.pos);
-		walk_packet<true>(w, c, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
+		win_cover(w.win, c, b.slab, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, w.st.pos);
+		walk_packet<true>(w, c.L, c.data, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
 	}
 	if (w.st.pos != target) { /* cannot happen for an on-walk target; fail safe */
 		if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = 0; out.win[2u * j] = target; out.win[2u * j + 1u] = MGL_WIN_NONE; }
@@ -1098,8 +1091,8 @@ __device__ void nbr_fullwalk_one(const DevCtx& c, const BaseView& b, const Contr
 
 	/* mutate, packet_slab_neighbour.c:119-152 */
 	const uint32_t pos = target;
-	walk_window(w, c, b.slab, lane);
-	const mgl_pk first = walk_slab_at(w, pos);
+	win_cover(w.win, c, b.slab, w.st.pos, lane);
+	const mgl_pk first = win_pk(w.win, pos);
 	mgl_pk m_first = first, m_second = 0;
 	bool second_set = false, mutated = false;
 	if (pos + 1 < c.n && (nbr_draw(rng) % 2u) == 0) {
@@ -1115,7 +1108,7 @@ __device__ void nbr_fullwalk_one(const DevCtx& c, const BaseView& b, const Contr
 		} else if ((ft == MGL_LITERAL || ft == MGL_SHORT_REP) && (st == MGL_MATCH || st == MGL_LONG_REP)) {
 			uint32_t rep_start = pos - (st == MGL_LONG_REP ? mgl_dist_at(&w.st, sdist) : sdist);
 			if (slen < MGL_MAX_MATCH && rep_start > 0 && rep_start <= pos &&
-			    walk_byte_at(w, pos) == c.data[rep_start - 1]) {
+			    win_byte(w.win, pos) == c.data[rep_start - 1]) {
 				m_first = mgl_pack(st, sdist, slen + 1);
 				journal_set(jn, pos, first, m_first, lane);
 				mutated = true;
@@ -1131,7 +1124,7 @@ __device__ void nbr_fullwalk_one(const DevCtx& c, const BaseView& b, const Contr
 		m_first = picked;
 		journal_set(jn, pos, first, m_first, lane);
 	}
-	walk_packet<true>(w, c, probs, T, mgl_pk_type(m_first), mgl_pk_dist(m_first), mgl_pk_len(m_first), lane); /* :169 */
+	walk_packet<true>(w, c.L, c.data, probs, T, mgl_pk_type(m_first), mgl_pk_dist(m_first), mgl_pk_len(m_first), lane); /* :169 */
 
 	/* repair_remaining_packets, packet_slab_neighbour.c:82-117 */
 	uint32_t count = 0, guard = 0, npicks = 0;
@@ -1139,13 +1132,13 @@ __device__ void nbr_fullwalk_one(const DevCtx& c, const BaseView& b, const Contr
 		if (++guard > c.n) break;
 		count++;
 		const uint32_t p = w.st.pos;
-		walk_window(w, c, b.slab, lane);
-		const mgl_pk old = (second_set && p == pos + 1) ? m_second : walk_slab_at(w, p);
+		win_cover(w.win, c, b.slab, w.st.pos, lane);
+		const mgl_pk old = (second_set && p == pos + 1) ? m_second : win_pk(w.win, p);
 		mgl_pk pk = old;
 		uint32_t type = mgl_pk_type(pk);
 		if (type == MGL_SHORT_REP || (type == MGL_LITERAL && count < 4)) {
 			/* for a LITERAL past the third packet the byte test cannot change anything (:91-97) */
-			const bool same = w.st.dists[0] < p && walk_byte_at(w, p) == c.data[p - w.st.dists[0] - 1];
+			const bool same = w.st.dists[0] < p && win_byte(w.win, p) == c.data[p - w.st.dists[0] - 1];
 			if (same) { if (count < 4) pk = MGL_PK_SHORT_REP; }
 			else pk = MGL_PK_LITERAL;
 		}
@@ -1167,7 +1160,7 @@ __device__ void nbr_fullwalk_one(const DevCtx& c, const BaseView& b, const Contr
 			const mgl_pk base_old = (second_set && p == pos + 1) ? uni64(b.slab[p]) : old;
 			journal_set(jn, p, base_old, pk, lane);
 		}
-		walk_packet<true>(w, c, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
+		walk_packet<true>(w, c.L, c.data, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
 	}
 
 	const uint64_t total = base_cum + wave_sum64(w.acc);
@@ -1267,15 +1260,15 @@ __global__ void __launch_bounds__(64) k_topk_probe(DevCtx c, BaseView b, uint32_
 	Walk w;
 	ckpt_load(b, c, position >> MGL_CKPT_SHIFT, probs, w, lane);
 	while (w.st.pos < position) {
-		walk_window(w, c, b.slab, lane);
-		const mgl_pk pk = walk_slab_at(w, w.st.pos);
-		walk_packet<true>(w, c, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
+		win_cover(w.win, c, b.slab, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, w.st.pos);
+		walk_packet<true>(w, c.L, c.data, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
 	}
-	walk_window(w, c, b.slab, lane);
+	win_cover(w.win, c, b.slab, w.st.pos, lane);
 	TopK t;
 	TopkPlan plan;
 	topk_plan_make(plan, c, w.st, lane);
-	topk_find<4, true>(t, c, w, probs, T, lencost, walk_slab_at(w, position), lane, &plan);
+	topk_find<4, true>(t, c, w, probs, T, lencost, win_pk(w.win, position), lane, &plan);
 	if (lane < t.count) {
 		const uint32_t o = t.count - 1 - lane; /* worst first */
 		out_pk[o] = topk_packet(t.key, position);

@@ -59,8 +59,8 @@ __device__ void build_body(const DevCtx& c, const Base2& b, Control* ctl, int ch
 		bitacc_move(on, b.onwalk, pos >> 6, lane);
 		bitacc_move(sp, b.sp0, pos >> 6, lane);
 		on.bits |= 1ull << (pos & 63u);
-		walk_window(w, c, b.slab, lane);
-		const mgl_pk pk = walk_slab_at(w, pos);
+		win_cover(w.win, c, b.slab, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, pos);
 		uint32_t type = mgl_pk_type(pk), len = mgl_pk_len(pk), dist = mgl_pk_dist(pk);
 		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) {
 			type = MGL_LITERAL; len = 1; dist = 0;
@@ -68,20 +68,10 @@ __device__ void build_body(const DevCtx& c, const Base2& b, Control* ctl, int ch
 		}
 		if (type != MGL_LITERAL) {
 			sp.bits |= 1ull << (pos & 63u);
-			if (lane < 8) {
-				const uint32_t v = lane == 0 ? w.st.ctx_state : lane == 1 ? w.st.dists[0] : lane == 2 ? w.st.dists[1]
-				                 : lane == 3 ? w.st.dists[2] : lane == 4 ? w.st.dists[3] : 0u;
-				b.sp_state[(size_t)pos * 8 + lane] = v;
-			}
-		}
-		const uint32_t byte = walk_byte_at(w, pos);
-		uint32_t match_byte = 0, prev_byte = 0;
-		if (type == MGL_LITERAL) {
-			if (w.st.ctx_state >= 7 && w.st.dists[0] < pos) match_byte = c.data[pos - w.st.dists[0] - 1];
-			if (c.L.lc > 0 && pos > 0) prev_byte = c.data[pos - 1];
+			if (lane < 8) state_record_write(b, pos, w.st, lane);
 		}
 		mgl_plan pl;
-		mgl_plan_packet(&c.L, &w.st, type, dist, len, byte, match_byte, prev_byte, &pl);
+		plan_at(c.L, c.data, w.st, type, dist, len, win_byte(w.win, pos), pl);
 		if (lane < pl.nev) {
 			uint32_t ctx, bit;
 			mgl_plan_event(&pl, lane, &ctx, &bit);
@@ -160,18 +150,12 @@ __device__ void build_body(const DevCtx& c, const Base2& b, Control* ctl, int ch
 			for (uint32_t i = lane; i < b.ck_elems / 2; i += 64) dst[i] = src[i];
 			next_ck++;
 		}
-		walk_window(w, c, b.slab, lane);
-		const mgl_pk pk = walk_slab_at(w, pos);
+		win_cover(w.win, c, b.slab, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, pos);
 		uint32_t type = mgl_pk_type(pk), len = mgl_pk_len(pk), dist = mgl_pk_dist(pk);
 		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) { type = MGL_LITERAL; len = 1; dist = 0; }
-		const uint32_t byte = walk_byte_at(w, pos);
-		uint32_t match_byte = 0, prev_byte = 0;
-		if (type == MGL_LITERAL) {
-			if (w.st.ctx_state >= 7 && w.st.dists[0] < pos) match_byte = c.data[pos - w.st.dists[0] - 1];
-			if (c.L.lc > 0 && pos > 0) prev_byte = c.data[pos - 1];
-		}
 		mgl_plan pl;
-		mgl_plan_packet(&c.L, &w.st, type, dist, len, byte, match_byte, prev_byte, &pl);
+		plan_at(c.L, c.data, w.st, type, dist, len, win_byte(w.win, pos), pl);
 		if (lane < pl.nev) {
 			uint32_t ctx, bit;
 			mgl_plan_event(&pl, lane, &ctx, &bit);
@@ -352,8 +336,8 @@ __device__ __forceinline__ uint32_t chain_list(Changes& ch, uint32_t lane, bool*
 	}
 	wave_sync();
 	uint32_t nu = 0;
-	for (uint32_t wbase = 0; wbase < ch.nbitwords; wbase += 64) {
-		const uint32_t word = wbase + lane < ch.nbitwords ? ch.ctxbits[wbase + lane] : 0u;
+	for (uint32_t w0 = 0; w0 < ch.nbitwords; w0 += 64) {
+		const uint32_t word = w0 + lane < ch.nbitwords ? ch.ctxbits[w0 + lane] : 0u;
 		const uint32_t cntl = (uint32_t)__popc(word);
 		uint32_t incl = cntl;
 		for (int o = 1; o < 64; o <<= 1) {
@@ -365,7 +349,7 @@ __device__ __forceinline__ uint32_t chain_list(Changes& ch, uint32_t lane, bool*
 		uint32_t at = nu + incl - cntl;
 		uint32_t wv = word;
 		while (wv) {
-			ch.uctx[at++] = (uint16_t)(((wbase + lane) << 5) + ((uint32_t)__ffs((int)wv) - 1u));
+			ch.uctx[at++] = (uint16_t)(((w0 + lane) << 5) + ((uint32_t)__ffs((int)wv) - 1u));
 			wv &= wv - 1u;
 		}
 		nu += chunk;
@@ -544,75 +528,24 @@ __device__ __forceinline__ void prof_mark(Prof& p, int phase, uint32_t lane)
 	p.t = __builtin_readcyclecounter();
 }
 
-struct Win {
-	uint32_t base;
-	mgl_pk pk;
-	uint32_t byte;
-};
-__device__ __forceinline__ void win_cover(Win& w, const DevCtx& c, const mgl_pk* slab, uint32_t pos, uint32_t lane)
-{
-	const uint32_t base = pos & ~63u;
-	if (base != w.base) {
-		const uint32_t p = base + lane;
-		w.pk = p < c.n ? slab[p] : 0;
-		w.byte = c.data[p < c.n ? p : c.n];
-		w.base = base;
-	}
-}
-__device__ __forceinline__ mgl_pk win_pk(const Win& w, uint32_t pos) { return rdlane64(w.pk, pos - w.base); }
-__device__ __forceinline__ uint32_t win_byte(const Win& w, uint32_t pos) { return rdlane(w.byte, pos - w.base); }
-
-__device__ __forceinline__ void plan_at(const DevCtx& c, const mgl_wstate& st, uint32_t type, uint32_t dist, uint32_t len,
-                                        uint32_t byte, mgl_plan& pl)
-{
-	uint32_t match_byte = 0, prev_byte = 0;
-	if (type == MGL_LITERAL) {
-		if (st.ctx_state >= 7 && st.dists[0] < st.pos) match_byte = c.data[st.pos - st.dists[0] - 1];
-		if (c.L.lc > 0 && st.pos > 0) prev_byte = c.data[st.pos - 1];
-	}
-	mgl_plan_packet(&c.L, &st, type, dist, len, byte, match_byte, prev_byte, &pl);
-}
-
 /* Base packets the neighbour's walk has passed over disappear, and under a freshly picked match
- * they are mostly a run of plain literals (ctx_state < 7, so no match byte): up to seven of them
- * are planned at once, nine lanes each (is_match + the eight literal bits), instead of one per
- * turn of the walk loop.  Uses only the slab / input window in registers.  Returns the number of
- * packets removed (0: not a plain-literal run of at least two -- take the packet-at-a-time path). */
+ * they are mostly a run of plain literals: their events go to the inserted (INS) or removed list
+ * seven packets at a time (lit_run_take / lit_run_plan, mgl_device.h).  Returns the number of
+ * packets taken (0: not a plain-literal run of at least two -- take the packet-at-a-time path). */
 template <bool INS>
 __device__ __forceinline__ uint32_t literal_run_events(const DevCtx& c, Changes& ch, const Win& win, mgl_wstate& st, uint32_t limit, uint32_t lane)
 {
 	if (st.ctx_state >= 7u) return 0;
-	const uint32_t o = st.pos - win.base;
-	const unsigned long long lit = __ballot(mgl_pk_type(win.pk) == MGL_LITERAL) >> o; /* window entries from st.pos on */
-	uint32_t run = (uint32_t)__ffsll((long long)~lit) - 1u; /* consecutive literals: each one's successor is on the walk */
-	if (~lit == 0ull) run = 64u;
-	run = run < 64u - o ? run : 64u - o;
-	run = run < limit ? run : limit;
-	if (run < 2u) return 0;
-	const uint32_t take = run < 7u ? run : 7u;
+	const uint32_t take = lit_run_take(mgl_pk_type(win.pk) == MGL_LITERAL, st.pos - win.base, limit);
+	if (!take) return 0;
 	uint32_t& n = INS ? ch.n_ins : ch.n_rem;
 	if (n + 9u * take > ch.cap || n + ch.n_cancel + 9u * take > MGL_BIG_CAP) { ch.overflow = true; ch.list_full = true; return take; }
-	const uint32_t i = lane / 9u, slot = lane - i * 9u;
-	const uint32_t p = st.pos + i;
-	const bool active = i < take;
-	const uint32_t byte = (uint32_t)__shfl((int)win.byte, (int)((p - win.base) & 63u), 64);
-	uint32_t prev_byte = 0;
-	if (c.L.lc > 0) {
-		const uint32_t wprev = (uint32_t)__shfl((int)win.byte, (int)((p - 1u - win.base) & 63u), 64);
-		prev_byte = p == 0 ? 0u : (p - 1u >= win.base ? wprev : (uint32_t)c.data[p - 1u]);
-	}
-	mgl_wstate sv = st;
-	sv.pos = p;
-	sv.ctx_state = lit_steps(st.ctx_state, i);
-	mgl_plan pl;
-	mgl_plan_packet(&c.L, &sv, MGL_LITERAL, 0, 1, byte, 0, prev_byte, &pl);
-	if (__ballot(active && pl.nev != 9u)) return 0; /* not the 1 + 8 events assumed above: one at a time */
-	if (active) {
-		uint32_t ctx, bit;
-		mgl_plan_event(&pl, slot, &ctx, &bit);
-		const uint32_t at = n + i * 9u + slot;
-		if (INS) { ch.ins_key[at] = (uint16_t)(ctx | (bit << 15)); ch.ins_pos[at] = p; }
-		else { ch.rem_key[at] = (uint16_t)ctx; ch.rem_pos[at] = p; }
+	LitLane ll;
+	if (!lit_run_plan(c, win, st, take, lane, ll)) return 0;
+	if (ll.active) {
+		const uint32_t at = n + lane;
+		if (INS) { ch.ins_key[at] = (uint16_t)(ll.ctx | (ll.bit << 15)); ch.ins_pos[at] = ll.p; }
+		else { ch.rem_key[at] = (uint16_t)ll.ctx; ch.rem_pos[at] = ll.p; }
 	}
 	n += 9u * take;
 	st.pos += take;
@@ -649,45 +582,25 @@ __device__ __forceinline__ void model_load_inl(const DevCtx& c, const Base2& b, 
 		walk_reset(w);
 		w.st = uni_state(base_state_at(b, start));
 		while (w.st.pos < y) {
-			walk_window(w, c, b.slab, lane);
+			win_cover(w.win, c, b.slab, w.st.pos, lane);
 			if (w.st.ctx_state < 7u) {
-				/* a run of plain literals: up to seven are planned at once, nine lanes each; their
-				 * probability updates are then applied packet by packet (the packets share contexts:
-				 * is_match and the top of the literal tree), which is all that has to stay in order */
-				const uint32_t o = w.st.pos - w.wbase;
-				const unsigned long long lit = __ballot(mgl_pk_type(w.wpk) == MGL_LITERAL) >> o;
-				uint32_t run = ~lit == 0ull ? 64u : (uint32_t)__ffsll((long long)~lit) - 1u;
-				run = run < 64u - o ? run : 64u - o;
-				run = run < y - w.st.pos ? run : y - w.st.pos;
-				if (run >= 2u) {
-					const uint32_t take = run < 7u ? run : 7u;
-					const uint32_t i = lane / 9u, slot = lane - i * 9u, p = w.st.pos + i;
-					const bool active = i < take;
-					const uint32_t byte = (uint32_t)__shfl((int)w.wbyte, (int)((p - w.wbase) & 63u), 64);
-					uint32_t prev_byte = 0;
-					if (c.L.lc > 0) {
-						const uint32_t wprev = (uint32_t)__shfl((int)w.wbyte, (int)((p - 1u - w.wbase) & 63u), 64);
-						prev_byte = p == 0 ? 0u : (p - 1u >= w.wbase ? wprev : (uint32_t)c.data[p - 1u]);
+				/* a run of plain literals (lit_run_plan): their probability updates are applied packet by packet
+				 * (the packets share contexts: is_match and the top of the literal tree), which is all that has
+				 * to stay in order */
+				const uint32_t take = lit_run_take(mgl_pk_type(w.win.pk) == MGL_LITERAL, w.st.pos - w.win.base, y - w.st.pos);
+				LitLane ll;
+				if (take && lit_run_plan(c, w.win, w.st, take, lane, ll)) {
+					for (uint32_t r = 0; r < take; r++) {
+						if (ll.active && ll.i == r) probs[ll.ctx] = (uint16_t)mgl_prob_update(probs[ll.ctx], ll.bit);
+						wave_sync();
 					}
-					mgl_wstate sv = w.st;
-					sv.pos = p; sv.ctx_state = lit_steps(w.st.ctx_state, i);
-					mgl_plan pl;
-					mgl_plan_packet(&c.L, &sv, MGL_LITERAL, 0, 1, byte, 0, prev_byte, &pl);
-					if (!__ballot(active && pl.nev != 9u)) {
-						uint32_t ctx = 0, bit = 0;
-						if (active) mgl_plan_event(&pl, slot, &ctx, &bit);
-						for (uint32_t r = 0; r < take; r++) {
-							if (active && i == r) probs[ctx] = (uint16_t)mgl_prob_update(probs[ctx], bit);
-							wave_sync();
-						}
-						w.st.pos += take; w.st.ctx_state = lit_steps(w.st.ctx_state, take);
-						w.packets += take;
-						continue;
-					}
+					w.st.pos += take; w.st.ctx_state = lit_steps(w.st.ctx_state, take);
+					w.packets += take;
+					continue;
 				}
 			}
-			const mgl_pk pk = walk_slab_at(w, w.st.pos);
-			walk_packet<true>(w, c, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
+			const mgl_pk pk = win_pk(w.win, w.st.pos);
+			walk_packet<true>(w, c.L, c.data, probs, T, mgl_pk_type(pk), mgl_pk_dist(pk), mgl_pk_len(pk), lane);
 		}
 		wave_sync();
 	}
@@ -979,7 +892,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	ch.diag = c.diag_stop;
 	const uint32_t pos = target;
 	mgl_wstate bs = nb;                               /* base's walk state */
-	Win win; win.base = 0xFFFFFFFFu; win.pk = 0; win.byte = 0;
+	Win win; win_reset(win);
 	Walk tw; /* scratch Walk for top-K (its window is the input window at the query position) */
 
 	/* ---- mutate, packet_slab_neighbour.c:119-152 */
@@ -1160,7 +1073,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 		}
 		if (MODE != MGL_NBR_REST && phase == P_TOPK) {
 			walk_from_state(tw, nb);
-			walk_window(tw, c, b.slab, lane);
+			win_cover(tw.win, c, b.slab, tw.st.pos, lane);
 			mgl_pk picked;
 			bool ok;
 			if constexpr (MODE == MGL_NBR_PICK) ok = pick_from_top_k<4, true, PROF>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked, &plan, &pp);
@@ -1246,7 +1159,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 									win_cover(win, c, b.slab, bs.pos, lane);
 									const mgl_pk bpk = win_pk(win, bs.pos);
 									mgl_plan bpl;
-									plan_at(c, bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk), win_byte(win, bs.pos), bpl);
+									plan_at(c.L, c.data, bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk), win_byte(win, bs.pos), bpl);
 									changes_add<false>(ch, bpl, bs.pos, lane);
 									mgl_advance(&bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk));
 								}
@@ -1338,7 +1251,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 							const mgl_pk bpk = win_pk(win, p);
 							const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
 							mgl_plan bpl;
-							plan_at(c, bs, btype, bdist, blen, win_byte(win, p), bpl);
+							plan_at(c.L, c.data, bs, btype, bdist, blen, win_byte(win, p), bpl);
 							bnev = bpl.nev; bndirect = bpl.ndirect;
 							if (lane < bnev) {
 								uint32_t cx, bt;
@@ -1348,7 +1261,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 							mgl_advance(&bs, btype, bdist, blen);
 						}
 						mgl_plan npl;
-						plan_at(c, nb, ntype, ndist, nlen, win_byte(win, p), npl);
+						plan_at(c.L, c.data, nb, ntype, ndist, nlen, win_byte(win, p), npl);
 						changes_add_pair(ch, bkey, bnev, bndirect, npl, p, lane, big.evcancel != 0);
 					}
 					mgl_advance(&nb, ntype, ndist, nlen);
@@ -1358,7 +1271,7 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 					if (literal_run_events<false>(c, ch, win, bs, (nb.pos < c.n ? nb.pos : c.n) - bs.pos, lane)) continue;
 					const mgl_pk bpk = win_pk(win, bs.pos);
 					mgl_plan bpl;
-					plan_at(c, bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk), win_byte(win, bs.pos), bpl);
+					plan_at(c.L, c.data, bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk), win_byte(win, bs.pos), bpl);
 					changes_add<false>(ch, bpl, bs.pos, lane);
 					mgl_advance(&bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk));
 				}

@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 	mgl_wstate nb = uni_state(base_state_at(b, t));
 	mgl_wstate bs = nb;
 	const unsigned long long tw1 = prof ? __builtin_readcyclecounter() : 0ull;
-	Win win; win.base = 0xFFFFFFFFu; win.pk = 0; win.byte = 0;
+	Win win; win_reset(win);
 	uint32_t n_ins = 0, n_rem = 0;
 	int32_t dpackets = 0;
 	uint32_t failed = 0; /* the give-up site's bit */
@@ -154,19 +154,15 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 			uint32_t btype = 0, bdist = 0, blen = 0;
 			if (paired) { btype = mgl_pk_type(old_at_p); bdist = mgl_pk_dist(old_at_p); blen = mgl_pk_len(old_at_p); }
 			if (!cancelled) {
-				plan_at(c, nb, ntype, ndist, nlen, win_byte(win, p), npl);
-				if (paired) plan_at(c, bs, btype, bdist, blen, win_byte(win, p), bpl);
+				plan_at(c.L, c.data, nb, ntype, ndist, nlen, win_byte(win, p), npl);
+				if (paired) plan_at(c.L, c.data, bs, btype, bdist, blen, win_byte(win, p), bpl);
 			}
 			/* base structures at p: on the new walk; special iff not a literal */
 			if (lane == 0) {
 				if (!paired) bit_write(b.onwalk, p, true);
 				special_write(b, p, ntype != MGL_LITERAL);
 			}
-			if (ntype != MGL_LITERAL && lane < 8) {
-				const uint32_t v = lane == 0 ? nb.ctx_state : lane == 1 ? nb.dists[0] : lane == 2 ? nb.dists[1]
-				                 : lane == 3 ? nb.dists[2] : lane == 4 ? nb.dists[3] : 0u;
-				b.sp_state[(size_t)p * 8 + lane] = v;
-			}
+			if (ntype != MGL_LITERAL && lane < 8) state_record_write(b, p, nb, lane);
 			if (!cancelled) {
 				if (n_ins + npl.nev > lim.v[MGL_LIM_APPLY_EVENTS] || (paired && n_rem + bpl.nev > lim.v[MGL_LIM_APPLY_EVENTS])) { failed = MGL_GU_APPLY_EVENTS; break; }
 				if (lane < npl.nev) {
@@ -196,35 +192,16 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 			const uint32_t q = bs.pos;
 			win_cover(win, c, b.slab, q, lane);
 			if (bs.ctx_state < 7u) {
-				/* a run of plain literals goes seven at a time, nine lanes each (as in the neighbour kernel) */
-				const uint32_t o = q - win.base;
-				const unsigned long long lit = __ballot(mgl_pk_type(win.pk) == MGL_LITERAL) >> o;
-				uint32_t run = ~lit == 0ull ? 64u : (uint32_t)__ffsll((long long)~lit) - 1u;
-				const uint32_t limit = (nb.pos < c.n ? nb.pos : c.n) - q;
-				run = run < 64u - o ? run : 64u - o;
-				run = run < limit ? run : limit;
-				if (run >= 2u) {
-					const uint32_t take = run < 7u ? run : 7u;
+				/* a run of plain literals goes seven at a time (lit_run_plan) */
+				const uint32_t take = lit_run_take(mgl_pk_type(win.pk) == MGL_LITERAL, q - win.base, (nb.pos < c.n ? nb.pos : c.n) - q);
+				if (take) {
 					if (n_rem + 9u * take > lim.v[MGL_LIM_APPLY_EVENTS]) { failed = MGL_GU_APPLY_EVENTS; break; }
-					const uint32_t i = lane / 9u, slot = lane - i * 9u, p = q + i;
-					const bool active = i < take;
-					const uint32_t byte = (uint32_t)__shfl((int)win.byte, (int)((p - win.base) & 63u), 64);
-					uint32_t prev_byte = 0;
-					if (c.L.lc > 0) {
-						const uint32_t wprev = (uint32_t)__shfl((int)win.byte, (int)((p - 1u - win.base) & 63u), 64);
-						prev_byte = p == 0 ? 0u : (p - 1u >= win.base ? wprev : (uint32_t)c.data[p - 1u]);
-					}
-					mgl_wstate sv = bs;
-					sv.pos = p; sv.ctx_state = lit_steps(bs.ctx_state, i);
-					mgl_plan pl;
-					mgl_plan_packet(&c.L, &sv, MGL_LITERAL, 0, 1, byte, 0, prev_byte, &pl);
-					if (!__ballot(active && pl.nev != 9u)) {
-						if (active) {
-							uint32_t ctx, bit;
-							mgl_plan_event(&pl, slot, &ctx, &bit);
-							ab.rem_key[n_rem + i * 9u + slot] = (uint16_t)ctx;
-							ab.rem_pos[n_rem + i * 9u + slot] = p;
-							atomicOr(&s_ctxbits[ctx >> 5], 1u << (ctx & 31u));
+					LitLane ll;
+					if (lit_run_plan(c, win, bs, take, lane, ll)) {
+						if (ll.active) {
+							ab.rem_key[n_rem + lane] = (uint16_t)ll.ctx;
+							ab.rem_pos[n_rem + lane] = ll.p;
+							atomicOr(&s_ctxbits[ll.ctx >> 5], 1u << (ll.ctx & 31u));
 						}
 						n_rem += 9u * take;
 						if (lane == 0) b.onwalk[q >> 6] &= ~(((take >= 64u ? ~0ull : ((1ull << take) - 1ull))) << (q & 63u)); /* literals are never special */
@@ -237,7 +214,7 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 			const mgl_pk bpk = win_pk(win, q);
 			const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
 			mgl_plan bpl;
-			plan_at(c, bs, btype, bdist, blen, win_byte(win, q), bpl);
+			plan_at(c.L, c.data, bs, btype, bdist, blen, win_byte(win, q), bpl);
 			if (n_rem + bpl.nev > lim.v[MGL_LIM_APPLY_EVENTS]) { failed = MGL_GU_APPLY_EVENTS; break; }
 			if (lane < bpl.nev) {
 				uint32_t ctx, bit;
@@ -258,8 +235,8 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 	if (lane < nd) b.slab[s_jpos[lane]] = s_jnew[lane];
 	/* touched contexts, ascending */
 	uint32_t nt = 0;
-	for (uint32_t wbase = 0; wbase < 512; wbase += 64) {
-		const uint32_t word = s_ctxbits[wbase + lane];
+	for (uint32_t w0 = 0; w0 < 512; w0 += 64) {
+		const uint32_t word = s_ctxbits[w0 + lane];
 		const uint32_t cntl = (uint32_t)__popc(word);
 		uint32_t incl = cntl;
 		for (int o = 1; o < 64; o <<= 1) {
@@ -270,7 +247,7 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 		uint32_t wv = word;
 		while (wv) {
 			const uint32_t bit = (uint32_t)__ffs((int)wv) - 1u;
-			ab.tctx[at++] = (uint16_t)(((wbase + lane) << 5) + bit);
+			ab.tctx[at++] = (uint16_t)(((w0 + lane) << 5) + bit);
 			wv &= wv - 1u;
 		}
 		nt += (uint32_t)__shfl((int)incl, 63, 64);

@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 
 	mgl_wstate nb = uni_state(base_state_at(b, t));
 	mgl_wstate bs = nb;
-	Win win; win.base = 0xFFFFFFFFu; win.pk = 0; win.byte = 0;
+	Win win; win_reset(win);
 	uint32_t n_ins = 0, n_rem = 0, nops = 0;
 	int32_t dpackets = 0;
 	long long ddirect = 0;
@@ -277,8 +277,8 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 			uint32_t btype = 0, bdist = 0, blen = 0;
 			if (paired) { btype = mgl_pk_type(old_at_p); bdist = mgl_pk_dist(old_at_p); blen = mgl_pk_len(old_at_p); }
 			if (!cancelled) {
-				plan_at(c, nb, ntype, ndist, nlen, win_byte(win, p), npl);
-				if (paired) plan_at(c, bs, btype, bdist, blen, win_byte(win, p), bpl);
+				plan_at(c.L, c.data, nb, ntype, ndist, nlen, win_byte(win, p), npl);
+				if (paired) plan_at(c.L, c.data, bs, btype, bdist, blen, win_byte(win, p), bpl);
 			}
 			/* p is on the new walk; special iff not a literal, with the state before it */
 			batch_op(bt, cl, nops, opcap, failed, p, (paired ? 0u : MGL_OP_ON) | (ntype != MGL_LITERAL ? MGL_OP_SPEC : MGL_OP_PLAIN), 1u, nb, lane);
@@ -311,35 +311,17 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 			const uint32_t q = bs.pos;
 			win_cover(win, c, b.slab, q, lane);
 			if (bs.ctx_state < 7u) {
-				const uint32_t o = q - win.base;
-				const unsigned long long lit = __ballot(mgl_pk_type(win.pk) == MGL_LITERAL) >> o;
-				uint32_t run = ~lit == 0ull ? 64u : (uint32_t)__ffsll((long long)~lit) - 1u;
 				uint32_t limit = nb.pos < c.n ? nb.pos : c.n;
 				limit = (limit < next_first ? limit : next_first) - q;
-				run = run < 64u - o ? run : 64u - o;
-				run = run < limit ? run : limit;
-				if (run >= 2u) {
-					const uint32_t take = run < 7u ? run : 7u;
+				const uint32_t take = lit_run_take(mgl_pk_type(win.pk) == MGL_LITERAL, q - win.base, limit);
+				if (take) {
 					if (n_rem + 9u * take > evcap) { failed = MGL_GU_WALK_EVENTS; break; }
-					const uint32_t i = lane / 9u, slot = lane - i * 9u, p = q + i;
-					const bool active = i < take;
-					const uint32_t byte = (uint32_t)__shfl((int)win.byte, (int)((p - win.base) & 63u), 64);
-					uint32_t prev_byte = 0;
-					if (c.L.lc > 0) {
-						const uint32_t wprev = (uint32_t)__shfl((int)win.byte, (int)((p - 1u - win.base) & 63u), 64);
-						prev_byte = p == 0 ? 0u : (p - 1u >= win.base ? wprev : (uint32_t)c.data[p - 1u]);
-					}
-					mgl_wstate sv = bs;
-					sv.pos = p; sv.ctx_state = lit_steps(bs.ctx_state, i);
-					mgl_plan pl;
-					mgl_plan_packet(&c.L, &sv, MGL_LITERAL, 0, 1, byte, 0, prev_byte, &pl);
-					if (!__ballot(active && pl.nev != 9u)) {
-						if (active) {
-							uint32_t ctx, bit;
-							mgl_plan_event(&pl, slot, &ctx, &bit);
-							rkey[n_rem + i * 9u + slot] = (uint16_t)ctx;
-							rpos[n_rem + i * 9u + slot] = p;
-								}
+					LitLane ll;
+					if (lit_run_plan(c, win, bs, take, lane, ll)) {
+						if (ll.active) {
+							rkey[n_rem + lane] = (uint16_t)ll.ctx;
+							rpos[n_rem + lane] = ll.p;
+						}
 						n_rem += 9u * take;
 						batch_op(bt, cl, nops, opcap, failed, q, MGL_OP_OFF, take, bs, lane);
 						dpackets -= (int32_t)take;
@@ -351,7 +333,7 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 			const mgl_pk bpk = win_pk(win, q);
 			const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
 			mgl_plan bpl;
-			plan_at(c, bs, btype, bdist, blen, win_byte(win, q), bpl);
+			plan_at(c.L, c.data, bs, btype, bdist, blen, win_byte(win, q), bpl);
 			if (n_rem + bpl.nev > evcap) { failed = MGL_GU_WALK_EVENTS; break; }
 			if (lane < bpl.nev) {
 				uint32_t ctx, bit;
@@ -649,10 +631,10 @@ __device__ __forceinline__ RunOut batch_run_wave(const uint32_t* cpos, const uin
 	}
 	r.k_start = k; r.lo = x0; r.uncoupled = 0; r.hi = MGL_POS_INF;
 	/* sixty-four chain entries, one per lane (entry `len` is the sentinel: position = infinity; nothing is read behind it) */
-	uint32_t wbase = 0xFFFFFFFFu, my_pos = MGL_POS_INF, my_ev = 0;
+	uint32_t cbase = 0xFFFFFFFFu, my_pos = MGL_POS_INF, my_ev = 0;
 	auto window = [&](uint32_t kk) {
-		if (wbase != 0xFFFFFFFFu && kk >= wbase && kk - wbase < 64u) return;
-		wbase = kk;
+		if (cbase != 0xFFFFFFFFu && kk >= cbase && kk - cbase < 64u) return;
+		cbase = kk;
 		const uint32_t idx = kk + lane;
 		my_pos = idx <= len ? cpos[idx] : MGL_POS_INF;
 		my_ev = idx <= len ? (uint32_t)cev[idx] : 0u;
@@ -664,10 +646,10 @@ __device__ __forceinline__ RunOut batch_run_wave(const uint32_t* cpos, const uin
 	uint32_t ns = 0;
 	for (;;) {
 		window(k);
-		const uint32_t off = uni(k - wbase);
+		const uint32_t off = uni(k - cbase);
 		const uint32_t nxt0 = ipos < rpos ? ipos : rpos;
 		/* the entries from k on that lie in front of the context's next change and of the sentinel: the tail's next stretch */
-		const unsigned long long okm = __ballot(lane >= off && wbase + lane < len && my_pos < nxt0) >> off;
+		const unsigned long long okm = __ballot(lane >= off && cbase + lane < len && my_pos < nxt0) >> off;
 		const uint32_t cnt = okm == ~0ull ? 64u - off : (uint32_t)__ffsll((long long)~okm) - 1u;
 		if (cnt > 0u) {
 			const uint32_t nxt_cl = nxt0 == MGL_POS_INF ? 0xFFFFu : (ipos <= rpos ? (uint32_t)s_icl[ii] : (uint32_t)s_rcl[ri]);

@@ -50,9 +50,7 @@ __global__ void __launch_bounds__(64) k_opt_walk(DevCtx c, const mgl_pk* in, mgl
                                                  uint32_t chunk, uint32_t* entry)
 {
 	const uint32_t lane = threadIdx.x;
-	mgl_wstate st;
-	st.pos = 0; st.ctx_state = 0;
-	st.dists[0] = st.dists[1] = st.dists[2] = st.dists[3] = 0;
+	mgl_wstate st = state_initial();
 	while (st.pos < c.n) {
 		const uint32_t pos = st.pos;
 		const mgl_pk pk = in[pos];
@@ -67,13 +65,8 @@ __global__ void __launch_bounds__(64) k_opt_walk(DevCtx c, const mgl_pk* in, mgl
 			if (lane == 0) out[pos] = mgl_pack(type, dist, len);
 		}
 		if (!mgl_pk_wellformed(type, dist, len)) break; /* only packets are planned (mgl_model.h): a resolved copy is one. Never taken */
-		uint32_t match_byte = 0, prev_byte = 0;
-		if (type == MGL_LITERAL) {
-			if (st.ctx_state >= 7 && st.dists[0] < pos) match_byte = c.data[pos - st.dists[0] - 1];
-			if (c.L.lc > 0 && pos > 0) prev_byte = c.data[pos - 1];
-		}
 		mgl_plan pl;
-		mgl_plan_packet(&c.L, &st, type, dist, len, c.data[pos], match_byte, prev_byte, &pl);
+		plan_at(c.L, c.data, st, type, dist, len, c.data[pos], pl);
 		if (lane < pl.nev) {
 			uint32_t ctx, bit;
 			mgl_plan_event(&pl, lane, &ctx, &bit);

@@ -391,72 +391,38 @@ __global__ void __launch_bounds__(64) pb_walk(DevCtx c, Base2 b, PBuild pb)
 	wave_sync();
 	Walk w;
 	walk_reset(w);
-	{
-		const uint32_t* s = pb.st_in + (size_t)blk * 8;
-		w.st.pos = pb.entry[blk];
-		w.st.ctx_state = s[0];
-		w.st.dists[0] = s[1]; w.st.dists[1] = s[2]; w.st.dists[2] = s[3]; w.st.dists[3] = s[4];
-	}
+	w.st = state_from_words(pb.st_in + (size_t)blk * 8, pb.entry[blk]);
 	const uint32_t end = ((blk + 1) << pb.shift) < c.n ? ((blk + 1) << pb.shift) : c.n;
 	uint32_t ndirect = 0;
 	while (w.st.pos < end) {
 		const uint32_t pos = w.st.pos;
-		walk_window(w, c, b.slab, lane);
+		win_cover(w.win, c, b.slab, w.st.pos, lane);
 		if (w.st.ctx_state < 7u) {
-			/* a run of plain literals: up to seven are planned at once, nine lanes each (is_match + the eight tree nodes);
-			 * their events take their ranks packet by packet, because the packets share contexts (is_match, the top
-			 * of the literal tree) and a chain is in position order -- the model replay of mgl_kernels2.hip does the same */
-			const uint32_t o = pos - w.wbase;
+			/* a run of plain literals (lit_run_plan): their events take their ranks packet by packet, because the packets
+			 * share contexts (is_match, the top of the literal tree) and a chain is in position order -- the model replay
+			 * of mgl_kernels2.hip does the same */
 			uint32_t lt, ld, ll;
-			const uint32_t myp = w.wbase + lane;
-			pb_decode(w.wpk, myp, c.n, lt, ld, ll);
-			const unsigned long long lit = __ballot(myp < c.n && lt == MGL_LITERAL) >> o;
-			uint32_t run = ~lit == 0ull ? 64u : (uint32_t)__ffsll((long long)~lit) - 1u;
-			run = run < 64u - o ? run : 64u - o;
-			run = run < end - pos ? run : end - pos;
-			if (run >= 2u) {
-				const uint32_t take = run < 7u ? run : 7u;
-				const uint32_t i = lane / 9u, slot = lane - i * 9u, p = pos + i;
-				const bool active = i < take;
-				const uint32_t byte = (uint32_t)__shfl((int)w.wbyte, (int)((p - w.wbase) & 63u), 64);
-				uint32_t prev_byte = 0;
-				if (c.L.lc > 0) {
-					const uint32_t wprev = (uint32_t)__shfl((int)w.wbyte, (int)((p - 1u - w.wbase) & 63u), 64);
-					prev_byte = p == 0 ? 0u : (p - 1u >= w.wbase ? wprev : (uint32_t)c.data[p - 1u]);
+			const uint32_t myp = w.win.base + lane;
+			pb_decode(w.win.pk, myp, c.n, lt, ld, ll);
+			const uint32_t take = lit_run_take(myp < c.n && lt == MGL_LITERAL, pos - w.win.base, end - pos);
+			LitLane e;
+			if (take && lit_run_plan(c, w.win, w.st, take, lane, e)) {
+				uint32_t k = 0;
+				for (uint32_t r = 0; r < take; r++) {
+					if (e.active && e.i == r) k = cnt[e.ctx]++;
+					wave_sync();
 				}
-				mgl_wstate sv = w.st;
-				sv.pos = p; sv.ctx_state = lit_steps(w.st.ctx_state, i);
-				mgl_plan pl;
-				mgl_plan_packet(&c.L, &sv, MGL_LITERAL, 0, 1, byte, 0, prev_byte, &pl);
-				if (!__ballot(active && pl.nev != 9u)) {
-					uint32_t ctx = 0, bit = 0, k = 0;
-					if (active) mgl_plan_event(&pl, slot, &ctx, &bit);
-					for (uint32_t r = 0; r < take; r++) {
-						if (active && i == r) k = cnt[ctx]++;
-						wave_sync();
-					}
-					if (active && nst + lane < cap) stage[nst + lane] = pb_stage_pack(p, ctx, bit, k);
-					nst += 9u * take;
-					w.st.pos += take; w.st.ctx_state = lit_steps(w.st.ctx_state, take);
-					continue;
-				}
+				if (e.active && nst + lane < cap) stage[nst + lane] = pb_stage_pack(e.p, e.ctx, e.bit, k);
+				nst += 9u * take;
+				w.st.pos += take; w.st.ctx_state = lit_steps(w.st.ctx_state, take);
+				continue;
 			}
 		}
 		uint32_t type, dist, len;
-		pb_decode(walk_slab_at(w, pos), pos, c.n, type, dist, len);
-		if (type != MGL_LITERAL && lane < 8) {
-			const uint32_t v = lane == 0 ? w.st.ctx_state : lane == 1 ? w.st.dists[0] : lane == 2 ? w.st.dists[1]
-			                 : lane == 3 ? w.st.dists[2] : lane == 4 ? w.st.dists[3] : 0u;
-			b.sp_state[(size_t)pos * 8 + lane] = v;
-		}
-		const uint32_t byte = walk_byte_at(w, pos);
-		uint32_t match_byte = 0, prev_byte = 0;
-		if (type == MGL_LITERAL) {
-			if (w.st.ctx_state >= 7 && w.st.dists[0] < pos) match_byte = c.data[pos - w.st.dists[0] - 1];
-			if (c.L.lc > 0 && pos > 0) prev_byte = c.data[pos - 1];
-		}
+		pb_decode(win_pk(w.win, pos), pos, c.n, type, dist, len);
+		if (type != MGL_LITERAL && lane < 8) state_record_write(b, pos, w.st, lane);
 		mgl_plan pl;
-		mgl_plan_packet(&c.L, &w.st, type, dist, len, byte, match_byte, prev_byte, &pl);
+		plan_at(c.L, c.data, w.st, type, dist, len, win_byte(w.win, pos), pl);
 		if (lane < pl.nev) {
 			uint32_t ctx, bit;
 			mgl_plan_event(&pl, lane, &ctx, &bit);

@@ -21,7 +21,6 @@
 #include "mgl_device.h"
 
 #define MGL_PROPS_NTRIPLES 75u
-#define MGL_PROPS_MAX_PROBS (MGL_OFF_LIT + (0x300u << 4) + 1u) /* 14 135 rounded up to an even count */
 
 /* triple number t of the canonical order */
 __host__ __device__ static inline mgl_layout mgl_props_triple(uint32_t t)
@@ -35,7 +34,7 @@ __host__ __device__ static inline mgl_layout mgl_props_triple(uint32_t t)
 __global__ void __launch_bounds__(64) k_props_sweep(DevCtx c, const mgl_pk* slab, uint64_t* cost_out)
 {
 	__shared__ uint16_t T[2048];
-	__shared__ uint16_t probs[MGL_PROPS_MAX_PROBS];
+	__shared__ uint16_t probs[MGL_MAX_PROBS];
 	const uint32_t lane = threadIdx.x;
 	const mgl_layout L = mgl_props_triple(blockIdx.x);
 	for (uint32_t i = lane; i < 2048u; i += 64u) T[i] = c.cost_tbl[i];
@@ -45,26 +44,11 @@ __global__ void __launch_bounds__(64) k_props_sweep(DevCtx c, const mgl_pk* slab
 	wave_sync();
 	while (w.st.pos < c.n) {
 		const uint32_t pos = w.st.pos;
-		walk_window(w, c, slab, lane);
-		const mgl_pk pk = walk_slab_at(w, pos);
+		win_cover(w.win, c, slab, w.st.pos, lane);
+		const mgl_pk pk = win_pk(w.win, pos);
 		const uint32_t type = mgl_pk_type(pk), dist = mgl_pk_dist(pk), len = mgl_pk_len(pk);
 		if (!mgl_pk_wellformed(type, dist, len) || len > c.n - pos) break; /* the walk of mgl_cost_slab refused such a slab: never taken */
-		uint32_t match_byte = 0, prev_byte = 0;
-		if (type == MGL_LITERAL) {
-			if (w.st.ctx_state >= 7u && w.st.dists[0] < pos) match_byte = c.data[pos - w.st.dists[0] - 1u];
-			if (L.lc > 0u && pos > 0u) prev_byte = pos > w.wbase ? walk_byte_at(w, pos - 1u) : c.data[pos - 1u];
-		}
-		mgl_plan pl;
-		mgl_plan_packet(&L, &w.st, type, dist, len, walk_byte_at(w, pos), match_byte, prev_byte, &pl);
-		if (lane < pl.nev) {
-			uint32_t ctx, bit;
-			mgl_plan_event(&pl, lane, &ctx, &bit);
-			const uint32_t p = probs[ctx];
-			w.acc += T[bit ? 2048u - p : p];
-			probs[ctx] = (uint16_t)mgl_prob_update(p, bit);
-		}
-		if (lane == 0) w.acc += (uint64_t)pl.ndirect << 11;
-		mgl_advance(&w.st, type, dist, len);
+		walk_packet<true>(w, L, c.data, probs, T, type, dist, len, lane);
 	}
 	const uint64_t total = wave_sum64(w.acc);
 	if (lane == 0) cost_out[blockIdx.x] = total;
