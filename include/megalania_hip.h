@@ -29,6 +29,9 @@
  *                     no reference counterpart (the reference runs one chain): several valid parses recombined region
  *                                    by region between the positions where their walks agree; the last one crosses the
  *                                    distinct best slabs of all chains (mgl_slab_hash, mgl_comm_allgather_u64 serve it)
+ *   mgl_sa_set_focus, mgl_sa_focus, mgl_focus_slice
+ *                     no reference counterpart (packet_slab_neighbour.c:162-163 draws its target over the whole slab): a
+ *                                    step's targets confined to a byte window, and the rule that hands every chain its slice
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -324,6 +327,28 @@ int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_threshold);
  * and mgl_sa_set_accept_mode start a fresh block whatever came before (bulk steps first, except single steps first
  * in an epoch that starts from the best slab). */
 int mgl_sa_step_modes(mgl_sa* sa, uint8_t* modes_out, size_t cap, size_t* count);
+/* Focus window (no reference counterpart: the reference draws its target over the whole slab, packet_slab_neighbour.c:162-163;
+ * DESIGN.md sections 4 and 9).  While a window [lo, hi) is set, in byte positions, the K neighbours of a step take their targets
+ * among the packets that start in [lo, hi) of the current walk: with a packet starts below lo and b below hi, neighbour j takes
+ * a packet of the j-th of K equal slices of the ordinals [a, b), by the rule of the default targets applied to b - a (with fewer
+ * than K packets in the window several neighbours share a target and differ by their streams).  Empty window -- no packet starts
+ * in [lo, hi), the window lies inside one packet: the packet that covers lo is the only target (a := a - 1).  A neighbour never
+ * writes below its target (packet_slab_neighbour.c:82-152 only move forward from it), so a search under a window leaves every
+ * slab entry below lo untouched, current and best; entries at and above hi may change (a repair runs until it re-joins).
+ * (0, 0) clears the window; (0, n) is a window and gives the trajectory of none.  Being byte positions, the window keeps its
+ * meaning while the walk changes; it stays set across mgl_sa_run, mgl_sa_begin_epoch, mgl_sa_set_slab, the seeds and the
+ * exchanges until it is changed, and mgl_neighbours honours it like mgl_sa_run, on both engines.  Slab, costs, RNG streams,
+ * MGL_ACCEPT_AUTO's block and mgl_sa_stats are untouched.  MGL_EINVAL, handle unchanged: lo >= hi other than (0, 0), hi > n, a
+ * handle created with MGL_F_POSITION_TARGETS (position draws have no ordinals to cut). */
+int mgl_sa_set_focus(mgl_sa* sa, uint64_t lo, uint64_t hi);
+/* The window in force (0, 0: none); packets (nullable) receives the b - a above on the current walk -- the walk's packets when
+ * no window is set, 1 for an empty window. */
+int mgl_sa_focus(mgl_sa* sa, uint64_t* lo, uint64_t* hi, uint64_t* packets);
+/* host arithmetic only, no device involved: the window of chain `rank` of `world` in exchange round `round`, [B_rank, B_rank+1)
+ * with, in even rounds, B_i = i n / world, and in odd rounds B_0 = 0, B_world = n, B_i = (2 i - 1) n / (2 world) between -- half
+ * a slice further down, so that no boundary stays where it was.  In every round the slices tile [0, n) without overlap and
+ * none is empty.  MGL_EINVAL: world == 0, rank >= world, n < 2 world. */
+int mgl_focus_slice(uint64_t n, uint32_t world, uint32_t rank, uint64_t round, uint64_t* lo, uint64_t* hi);
 /* Adopt a best slab found elsewhere (another chain / GPU): replaces best slab and best cost.
  * `perplexity` must be the slab's exact cost: the slab is walked on the device at once, which refuses (MGL_EINVAL, nothing
  * adopted) an entry that is no packet or does not fit, and a cost other than `perplexity`.  That walk does not look at the

@@ -39,6 +39,7 @@ HIP_SYMBOLS = [
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep", "mgl_parse_sweep_props",
     "mgl_crossover", "mgl_sa_cross_best", "mgl_sa_exchange_cross",
     "mgl_comm_allgather_u64", "mgl_slab_hash", "mgl_sa_exchange_cross_all",
+    "mgl_sa_set_focus", "mgl_sa_focus", "mgl_focus_slice",
 ]
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
@@ -245,6 +246,10 @@ def hip_lib():
         L.mgl_comm_allgather_u64.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.mgl_slab_hash.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.mgl_sa_exchange_cross_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(CrossAllStats)]
+        L.mgl_sa_set_focus.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        L.mgl_sa_focus.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mgl_focus_slice.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -284,6 +289,18 @@ def literal_slab(n: int) -> np.ndarray:
     s["type"] = LITERAL
     s["len"] = 1
     return s
+
+
+def focus_slice(n: int, world: int, rank: int, round: int):
+    """(lo, hi): the focus window of chain `rank` of `world` in exchange round `round` (mgl_focus_slice; no device needed).  The
+    slices of a round tile [0, n); odd rounds cut half a slice away from even rounds.  Raises MglError (rc -1) for
+    rank >= world, world == 0, n < 2 * world."""
+    L = hip_lib()
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    rc = L.mgl_focus_slice(n, world, rank, round, C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise MglError(f"rc={rc}: {L.mgl_last_error().decode()}", rc=rc)
+    return lo.value, hi.value
 
 
 def emit_stream(data: bytes, slab: np.ndarray, lc=0, lp=0, pb=0) -> bytes:
@@ -422,6 +439,17 @@ class SA:
         """ACCEPT_AUTO (default) / ACCEPT_SINGLE / ACCEPT_BULK, or the strings "auto" / "single" / "bulk"."""
         mode = {"auto": ACCEPT_AUTO, "single": ACCEPT_SINGLE, "bulk": ACCEPT_BULK}.get(mode, mode)
         self._chk(self.L.mgl_sa_set_accept_mode(self.h, mode, bulk_threshold))
+
+    def set_focus(self, lo: int, hi: int):
+        """The step's K targets among the packets that start in bytes [lo, hi) (mgl_sa_set_focus); (0, 0) clears the window.
+        Nothing below lo is written while it is set.  Stays until changed."""
+        self._chk(self.L.mgl_sa_set_focus(self.h, lo, hi))
+
+    def focus(self):
+        """(lo, hi, packets): the window in force ((0, 0): none) and the packets of the current walk it holds"""
+        lo, hi, pk = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.L.mgl_sa_focus(self.h, C.byref(lo), C.byref(hi), C.byref(pk)))
+        return lo.value, hi.value, pk.value
 
     def step_modes(self) -> np.ndarray:
         """per step of the last run(): 0 single, 1 bulk"""

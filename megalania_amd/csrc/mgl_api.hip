@@ -231,6 +231,8 @@ struct mgl_sa {
 	bool batch_ok = false;
 	uint32_t* d_strat_tgt = nullptr;
 	uint32_t* d_strat_pre = nullptr; /* stratified targets: packets before every block of 4 096 positions */
+	uint32_t focus_lo = 0, focus_hi = 0; /* mgl_sa_set_focus: the targets' byte window, hi = 0: none; handed to k_targets by every launch */
+	uint32_t* d_focus_cnt = nullptr; /* two words for mgl_sa_focus: first ordinal, packets */
 	/* made with the targets (launch_targets), for the fused launch: K bytes, 1 = the neighbour will pick, 0 = grow/shrink; and
 	 * K neighbour indices, every slice's picking neighbours in front of its others (k_pick_order).  Null: MGL_NO_ORDER=1,
 	 * position targets, no split form */
@@ -492,8 +494,8 @@ static void launch_targets(mgl_sa* sa, hipStream_t st, uint64_t step_override)
 	const uint32_t nw0 = sa->incremental ? sa->b2.nw0 : (sa->ctx.n + 63u) >> 6;
 	hipLaunchKernelGGL(k_rank_blocks, dim3(sa->ctx.strat_nblk), dim3(64), 0, st, onwalk, nw0, sa->d_strat_pre, sa->ctx.strat_nblk);
 	hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, st, sa->d_strat_pre, sa->ctx.strat_nblk);
-	hipLaunchKernelGGL(k_targets, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, sa->b2, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->d_strat_tgt,
-	                   sa->d_pick_hint);
+	hipLaunchKernelGGL(sa->focus_hi ? k_targets<true> : k_targets<false>, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, sa->b2, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->d_strat_tgt,
+	                   sa->d_pick_hint, sa->focus_lo, sa->focus_hi);
 	if (sa->d_pick_order) {
 		const uint32_t slices = nbr_slices(sa);
 		hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, st, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
@@ -1065,6 +1067,7 @@ static int create_targets(mgl_sa* sa, size_t n)
 		sa->ctx.strat_pre = sa->d_strat_pre;
 		TRY(dnew(own, sa->d_strat_tgt, K));
 		sa->ctx.strat_tgt = sa->d_strat_tgt;
+		TRY(dnew(own, sa->d_focus_cnt, 2, 0));
 		/* the fused launch takes up its picking neighbours first; MGL_NO_ORDER=1: in blockIdx order */
 		if (sa->incremental && sa->form.split_nbr && !sa->env.no_order) {
 			TRY(dnew(own, sa->d_pick_hint, K, 1));
@@ -1877,6 +1880,51 @@ extern "C" int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_thresh
 	sa->accept_mode = mode;
 	if (bulk_threshold) sa->bulk_threshold = bulk_threshold;
 	sa->autoacc.reset();
+	return MGL_OK;
+}
+/* The focus window: host state only.  Targets that were queued ahead under the old window are made again. */
+extern "C" int mgl_sa_set_focus(mgl_sa* sa, uint64_t lo, uint64_t hi)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	if (!sa->d_strat_pre) return fail(MGL_EINVAL, "mgl_sa_set_focus: position targets (MGL_F_POSITION_TARGETS) have no focus window");
+	if (hi > sa->n || (lo >= hi && (lo | hi) != 0)) return fail(MGL_EINVAL, "mgl_sa_set_focus: the window must be 0, 0 or lo < hi <= n");
+	sa->focus_lo = (uint32_t)lo; sa->focus_hi = (uint32_t)hi;
+	if (sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE;
+	return MGL_OK;
+}
+extern "C" int mgl_sa_focus(mgl_sa* sa, uint64_t* lo, uint64_t* hi, uint64_t* packets)
+{
+	if (!sa || !lo || !hi) return fail(MGL_EINVAL, "null argument");
+	*lo = sa->focus_lo; *hi = sa->focus_hi;
+	if (!packets) return MGL_OK;
+	if (!sa->d_strat_pre) return fail(MGL_EINVAL, "mgl_sa_focus: position targets (MGL_F_POSITION_TARGETS) count no packets");
+	HIPCHK(hipSetDevice(sa->device));
+	const uint64_t* onwalk = sa->incremental ? sa->b2.onwalk : sa->base.v.onwalk;
+	const uint32_t nw0 = sa->incremental ? sa->b2.nw0 : (sa->ctx.n + 63u) >> 6;
+	hipStream_t st = sa->q.stream;
+	HIPCHK(hipStreamSynchronize(sa->q.stream2)); /* targets queued ahead use the same prefix sums */
+	hipLaunchKernelGGL(k_rank_blocks, dim3(sa->ctx.strat_nblk), dim3(64), 0, st, onwalk, nw0, sa->d_strat_pre, sa->ctx.strat_nblk);
+	hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, st, sa->d_strat_pre, sa->ctx.strat_nblk);
+	hipLaunchKernelGGL(k_focus_count, dim3(1), dim3(64), 0, st, onwalk, nw0, (const uint32_t*)sa->d_strat_pre, sa->focus_lo, sa->focus_hi ? sa->focus_hi : sa->n, sa->d_focus_cnt);
+	HIPCHK(hipGetLastError());
+	uint32_t v[2] = { 0, 0 };
+	HIPCHK(hipMemcpyAsync(v, sa->d_focus_cnt, sizeof v, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	*packets = v[1];
+	return MGL_OK;
+}
+/* pure host arithmetic: chain `rank` of `world` gets slice [B_rank, B_rank+1) of [0, n); even rounds cut at i n / world, odd rounds
+ * half a slice further down, so that no boundary stays where it was */
+extern "C" int mgl_focus_slice(uint64_t n, uint32_t world, uint32_t rank, uint64_t round, uint64_t* lo, uint64_t* hi)
+{
+	if (!lo || !hi) return fail(MGL_EINVAL, "null argument");
+	if (world == 0 || rank >= world || n < 2ull * world) return fail(MGL_EINVAL, "mgl_focus_slice: needs rank < world and n >= 2 world");
+	auto bound = [&](uint64_t i) -> uint64_t {
+		if (i == 0) return 0;
+		if (i == world) return n;
+		return (round & 1u) ? (uint64_t)((unsigned __int128)(2 * i - 1) * n / (2ull * world)) : (uint64_t)((unsigned __int128)i * n / world);
+	};
+	*lo = bound(rank); *hi = bound(rank + 1ull);
 	return MGL_OK;
 }
 extern "C" int mgl_sa_step_modes(mgl_sa* sa, uint8_t* modes_out, size_t cap, size_t* count)

@@ -166,12 +166,14 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
  * under independent uniform draws (packet_slab_neighbour.c:162-163 draws an ordinal too), but the K targets of a step are
  * distinct and spread over the file, so that far fewer improving neighbours of one step overlap.  `pre[b]` = packets that
  * start before block b of 4 096 positions (k_rank_blocks / k_rank_scan, once per step).  Returns the target position. */
+/* `first` (0 without a focus window): the slices are cut from the P packets of ordinals [first, first + P), see focus_ordinals. */
 __device__ __forceinline__ uint32_t stratified_target(const uint64_t* onwalk, uint32_t nw0, const uint32_t* pre, uint32_t nblk,
-                                                      uint32_t P, uint32_t K, uint32_t j, uint32_t u, uint32_t lane)
+                                                      uint32_t first, uint32_t P, uint32_t K, uint32_t j, uint32_t u, uint32_t lane)
 {
 	const uint32_t lo_o = (uint32_t)((uint64_t)j * P / K), hi_o = (uint32_t)((uint64_t)(j + 1u) * P / K);
 	uint32_t ord = lo_o + (hi_o > lo_o ? u % (hi_o - lo_o) : 0u);
 	if (ord >= P) ord = P ? P - 1u : 0u;
+	ord += first;
 	uint32_t lo = 0, hi = nblk; /* pre[lo] <= ord < pre[hi] */
 	while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (pre[mid] <= ord) lo = mid; else hi = mid; }
 	const uint32_t rem = ord - pre[lo];
@@ -190,6 +192,28 @@ __device__ __forceinline__ uint32_t stratified_target(const uint64_t* onwalk, ui
 		tpos = ((lo * 64u + l) << 6) + (uint32_t)__ffsll((long long)wv) - 1u;
 	}
 	return uni(tpos);
+}
+/* packets of the walk that start below position x (x <= n): the prefix sum of x's block of 4 096 positions plus the popcounts of
+ * the block's bitmap words up to x's, that one masked below x.  One wavefront, one word per lane. */
+__device__ __forceinline__ uint32_t starts_below(const uint64_t* onwalk, uint32_t nw0, const uint32_t* pre, uint32_t x, uint32_t lane)
+{
+	const uint32_t blk = x >> 12, wx = x >> 6; /* x = n, a multiple of 4 096: blk = nblk, whose prefix sum is the walk's total, and no word counts */
+	const uint32_t w = blk * 64u + lane;
+	uint64_t word = (w < nw0 && w <= wx) ? onwalk[w] : 0ull;
+	if (w == wx) word &= (1ull << (x & 63u)) - 1ull;
+	return pre[blk] + (uint32_t)uni64(wave_sum64((uint64_t)__popcll(word)));
+}
+/* Focus window (mgl_sa_set_focus): the packets that start in [lo, hi), as ordinals [*first, *first + count) of the walk; a step's
+ * K slices are cut from these instead of from the whole walk.  A window inside one packet holds no start: it stands for the
+ * packet that covers lo (position 0 starts a packet, so one exists).  0 < hi <= n, lo < hi. */
+__device__ __forceinline__ uint32_t focus_ordinals(const uint64_t* onwalk, uint32_t nw0, const uint32_t* pre, uint32_t lo, uint32_t hi,
+                                                   uint32_t lane, uint32_t* first)
+{
+	uint32_t a = starts_below(onwalk, nw0, pre, lo, lane);
+	const uint32_t b = starts_below(onwalk, nw0, pre, hi, lane);
+	if (b == a) a -= 1u;
+	*first = a;
+	return b - a;
 }
 
 /* LDS written by some lanes of this wave is read by others: keep the compiler from moving

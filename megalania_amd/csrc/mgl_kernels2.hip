@@ -1544,21 +1544,34 @@ __device__ __forceinline__ bool nbr_will_pick(const DevCtx& c, const Base2& b, u
  * packet inside its slice).  A kernel of its own: in the pick kernel, sixteen wavefronts per CU, the same search was a
  * dozen dependent loads at the head of every wavefront's critical path.  With `hint` (incremental engine) it also says which
  * neighbours will pick: 1 = picks, 0 = grow/shrink.  Exact where the slab is final when this runs (behind k_apply_walk of a
- * single step), a guess behind a batch accept. */
+ * single step), a guess behind a batch accept.  FOCUS: the launch passes a focus window; without one the instantiation is the
+ * kernel as it was before there were windows (two unused arguments), so that a search without a window pays nothing. */
+template <bool FOCUS>
 __global__ void __launch_bounds__(256) k_targets(DevCtx c, Base2 b, const uint64_t* onwalk, uint32_t nw0, const Control* ctl, uint64_t seed, uint64_t step_override,
-                                                 uint32_t K, uint32_t* tgt, unsigned char* hint)
+                                                 uint32_t K, uint32_t* tgt, unsigned char* hint, uint32_t focus_lo, uint32_t focus_hi)
 {
 	const uint32_t j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
 	if (j >= K) return;
 	const uint64_t gstep = step_override != ~0ull ? step_override : ctl->gstep;
 	const uint64_t key = mgl_rng_key(seed, gstep, j);
-	/* packets on the walk: the last prefix sum (Control::packets says the same once the accept is through; this kernel may run beside it) */
-	const uint32_t t = stratified_target(onwalk, nw0, c.strat_pre, c.strat_nblk, c.strat_pre[c.strat_nblk], K, j, mgl_rng_draw(key, 0), lane);
+	/* packets on the walk: the last prefix sum (Control::packets says the same once the accept is through; this kernel may run beside it);
+	 * under a focus window (FOCUS: focus_hi != 0; kernel arguments: DevCtx stays as the neighbour kernels know it) the packets that start inside it */
+	uint32_t first = 0, P = c.strat_pre[c.strat_nblk];
+	if (FOCUS) P = focus_ordinals(onwalk, nw0, c.strat_pre, focus_lo, focus_hi, lane, &first);
+	const uint32_t t = stratified_target(onwalk, nw0, c.strat_pre, c.strat_nblk, first, P, K, j, mgl_rng_draw(key, 0), lane);
 	if (lane == 0) tgt[j] = t;
 	if (hint != nullptr) {
 		const bool picks = nbr_will_pick(c, b, t, key); /* uniform: t is */
 		if (lane == 0) hint[j] = picks ? 1 : 0;
 	}
+}
+/* what k_targets makes of a focus window on the current walk (mgl_sa_focus): out[0] = the first ordinal, out[1] = the packets.
+ * One wavefront, behind k_rank_blocks / k_rank_scan. */
+__global__ void __launch_bounds__(64) k_focus_count(const uint64_t* onwalk, uint32_t nw0, const uint32_t* pre, uint32_t focus_lo, uint32_t focus_hi, uint32_t* out)
+{
+	uint32_t first = 0;
+	const uint32_t count = focus_ordinals(onwalk, nw0, pre, focus_lo, focus_hi, threadIdx.x, &first);
+	if (threadIdx.x == 0) { out[0] = first; out[1] = count; }
 }
 
 /* slice h of `slices` of a step's K neighbours is [mgl_slice_bound(K, h, slices), mgl_slice_bound(K, h + 1, slices)): the

@@ -32,7 +32,7 @@ static void usage(const char* argv0)
 	        "          [--match-finder nearest|frontier [--mf-depth N]] [--parse-sweep [--parse-sweep-table]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]\n"
-	        "          [--exchange best|cross|cross-all [--cross-grain N]]] filename\n"
+	        "          [--exchange best|cross|cross-all [--cross-grain N]]] [--focus LO:HI|rank] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
 	        "  --save-slab  after every epoch, write the best packet slab (resumable checkpoint)\n"
 	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb, same filter)\n"
@@ -91,6 +91,11 @@ static void usage(const char* argv0)
 	        "               ones (the 8 cheapest at most) travel to every chain and all chains make the same child of them; it\n"
 	        "               becomes every chain's best slab if it is cheaper than the cheapest parent, which the dearer chains adopt\n"
 	        "               otherwise.  Every chain then holds a best slab of the same cost: no plain exchange follows\n"
+	        "  --focus LO:HI  the search takes its targets among the packets that start in bytes [LO, HI) of the input (LO < HI, HI at\n"
+	        "               most the file's size) and writes nothing below LO: refines one stretch, e.g. behind --seed-stream from a\n"
+	        "               stream whose input changed only there.  --focus rank (needs --chains N, N >= 2): before every epoch chain\n"
+	        "               R takes slice R of N of the input (mgl_focus_slice), shifted by half a slice every other epoch, so that\n"
+	        "               chains that leave an exchange with a common slab work on different stretches of it\n"
 	        "  --accept     what a step of K neighbours takes: the best acceptable one (single), every one that is\n"
 	        "               the best of its own window (bulk), or whichever pays (auto, default)\n", argv0);
 }
@@ -356,6 +361,8 @@ int main(int argc, char** argv)
 	bool format_xz = false, filter_given = false;
 	enum { FILTER_NONE, FILTER_X86, FILTER_AUTO } filter = FILTER_NONE;
 	uint32_t dict_size = 0;
+	bool focus_given = false, focus_rank = false;
+	unsigned long long focus_lo = 0, focus_hi = 0;
 	for (int i = 1; i < argc; i++) {
 		const char* a = argv[i];
 		const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -417,6 +424,22 @@ int main(int argc, char** argv)
 				return -1;
 			}
 			dict_size = (uint32_t)d;
+		}
+		else if (!strcmp(a, "--focus")) {
+			if (focus_given) { fprintf(stderr, "Error: --focus given twice\n"); usage(argv[0]); return -1; }
+			focus_given = true;
+			if (!strcmp(v, "rank")) focus_rank = true;
+			else {
+				char *e1 = NULL, *e2 = NULL;
+				const bool digits = v[0] >= '0' && v[0] <= '9';
+				focus_lo = strtoull(v, &e1, 0);
+				if (digits && e1 != v && *e1 == ':' && e1[1] >= '0' && e1[1] <= '9') focus_hi = strtoull(e1 + 1, &e2, 0);
+				if (!e2 || e2 == e1 + 1 || *e2 || focus_lo >= focus_hi) {
+					fprintf(stderr, "Error: --focus takes LO:HI, byte positions with LO < HI, or `rank`\n");
+					usage(argv[0]);
+					return -1;
+				}
+			}
 		}
 		else if (!strcmp(a, "-o")) out_path = v;
 		else if (!strcmp(a, "--save-slab")) save_path = v;
@@ -495,6 +518,11 @@ int main(int argc, char** argv)
 	}
 	if (filter == FILTER_AUTO && (seed_stream_path || load_path || chains > 1)) {
 		fprintf(stderr, "Error: --filter auto cannot be combined with --seed-stream, --load-slab or --chains above 1\n");
+		usage(argv[0]);
+		return -1;
+	}
+	if (focus_rank && chains < 2) {
+		fprintf(stderr, "Error: --focus rank needs --chains N with N at least 2\n");
 		usage(argv[0]);
 		return -1;
 	}
@@ -731,10 +759,17 @@ int main(int argc, char** argv)
 		        18 + cost / 16384.f, 18 + os.greedy_cost / 16384.f, mf);
 	}
 
+	if (focus_given && !focus_rank && mgl_sa_set_focus(sa, focus_lo, focus_hi) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 	unsigned long long steps_per_epoch = (file_size + cfg.neighbours_per_step - 1) / cfg.neighbours_per_step;
 	if (steps_override) steps_per_epoch = steps_override;
 	for (unsigned phase = 0; phase < phases; phase++) {
 		for (unsigned epoch = 0; epoch < epochs; epoch++) {
+			if (focus_rank) {
+				/* chain `rank`'s slice for this round; the rounds count the epochs of the whole run, which the chains share */
+				uint64_t lo = 0, hi = 0;
+				if (mgl_focus_slice(file_size, (uint32_t)chains, (uint32_t)rank, (uint64_t)phase * epochs + epoch, &lo, &hi) != MGL_OK ||
+				    mgl_sa_set_focus(sa, lo, hi) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
+			}
 			if (mgl_sa_begin_epoch(sa, phase, phase != 0 || resumed) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			if (greedy && phase == 0 && !resumed && mgl_sa_seed_greedy(sa, greedy) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }
 			if (seed.passes && phase == 0 && mgl_sa_set_slab(sa, optimal_slab) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); return -1; }

@@ -23,6 +23,18 @@ def pack_key(best_cost: int, rank: int) -> int:
     return (cost << 8) | (rank & 0xFF)
 
 
+def focus_chain(chain, rank: int, world: int, round: int):
+    """Give chain `rank` of `world` its stretch of the file for exchange round `round` (mgl_focus_slice + mgl_sa_set_focus):
+    the chain's targets lie in its slice until the next call, so chains that leave an exchange with a common best slab improve
+    different stretches of it and the next crossing has W disjoint pieces of work to collect.  Odd rounds cut half a slice
+    away from even rounds.  Returns the window (lo, hi)."""
+    from . import binding
+
+    lo, hi = binding.focus_slice(chain.n, world, rank, round)
+    chain.set_focus(lo, hi)
+    return lo, hi
+
+
 def exchange_best(chain, dist, device=None):
     """One exchange epoch over torch.distributed (any backend; the CPU tests use gloo).  `chain` offers
     best_cost(), best_packed() -> (u64 words, cost) and adopt_best_packed(words, cost).  The slab travels in
