@@ -266,3 +266,56 @@ __device__ __forceinline__ uint32_t chain_lower_bound(const uint32_t* pos, uint3
 	}
 	return lo + below;
 }
+
+/* ---- the chain rewrite of the in-place accepts (mgl_kernels3.hip, mgl_kernels5.hip).  An accept gives the step up to the rebuild: raise Control::apply_failed, name the site(s) */
+__device__ __forceinline__ void give_up(Control* ctl, const AcceptLimits& lim, uint32_t bits) { ctl->apply_failed = 1; atomicOr(lim.why, bits); }
+/* position of a context's first change: the smaller of its first inserted and first removed event (lists in position order, not both empty) */
+__device__ __forceinline__ uint32_t first_change(const uint32_t* ipos, uint32_t ni, const uint32_t* rpos, uint32_t nr) { return ((ni ? ipos[0] : MGL_POS_INF) < (nr ? rpos[0] : MGL_POS_INF)) ? ipos[0] : rpos[0]; }
+/* The chain index row of a context with events ipos[0..ni) (inserted) and rpos[0..nr) (removed): every block behind the first change has (inserted - removed
+ * events below it) more entries before it.  ATOMIC: added without waiting for the value (batch accept); else a plain read-modify-write (one workgroup per row either way). */
+template <bool ATOMIC>
+__device__ __forceinline__ void chain_index_patch(uint32_t* row, const Base2& b, const uint32_t* ipos, uint32_t ni, const uint32_t* rpos, uint32_t nr,
+                                                  uint32_t tid, uint32_t nthreads)
+{
+	const uint32_t first = first_change(ipos, ni, rpos, nr);
+	for (uint32_t blk = (first >> b.sb_shift) + 1u + tid; blk <= b.nsb; blk += nthreads) {
+		const uint32_t bound = blk == b.nsb ? MGL_POS_INF : blk << b.sb_shift;
+		uint32_t a = 0, z = ni;
+		while (a < z) { const uint32_t m = (a + z) >> 1; if (ipos[m] < bound) a = m + 1; else z = m; }
+		const uint32_t di = a;
+		a = 0; z = nr;
+		while (a < z) { const uint32_t m = (a + z) >> 1; if (rpos[m] < bound) a = m + 1; else z = m; }
+		if (di == a) continue;
+		if constexpr (ATOMIC) atomicAdd(&row[blk], di - a);
+		else row[blk] += di - a;
+	}
+}
+/* first packet start at or after checkpoint ck's boundary (new walk), or MGL_POS_INF */
+__device__ __forceinline__ uint32_t ckpt_boundary(const Base2& b, uint32_t ck)
+{
+	const uint32_t first = ck << MGL_CK2_SHIFT;
+	uint32_t w = first >> 6;
+	uint64_t keep = ~0ull << (first & 63u); /* the boundary may lie inside a bitmap word */
+	while (w < b.nw0) {
+		const uint64_t v = b.onwalk[w] & keep;
+		if (v) return (w << 6) + ctz64(v);
+		w++; keep = ~0ull;
+	}
+	return MGL_POS_INF;
+}
+/* the dense-checkpoint rows whose boundary can lie in (lo, hi] (it can lie behind a packet that starts up to 272 bytes before lo; hi = MGL_POS_INF: to the last row) */
+__device__ __forceinline__ void ckpt_rows(const Base2& b, uint32_t lo, uint32_t hi, uint32_t& ck_lo, uint32_t& ck_hi)
+{
+	ck_lo = (lo > MGL_MAX_MATCH ? lo - MGL_MAX_MATCH : 0u) >> MGL_CK2_SHIFT;
+	ck_hi = hi == MGL_POS_INF ? b.nck : ((hi >> MGL_CK2_SHIFT) + 1u < b.nck ? (hi >> MGL_CK2_SHIFT) + 1u : b.nck);
+}
+/* a context's probability before the first of the new entries [first, last) at or after P (end_p behind them all); pos(i) / ev(i): entry i, in LDS or global memory */
+template <class Pos, class Ev>
+__device__ __forceinline__ uint16_t span_prob_at(Pos pos, Ev ev, uint32_t first, uint32_t last, uint32_t P, uint32_t end_p)
+{
+	uint32_t a = first, z = last;
+	while (a < z) { const uint32_t mid = (a + z) >> 1; if (pos(mid) < P) a = mid + 1; else z = mid; }
+	return a < last ? (uint16_t)(ev(a) & 0x7FFu) : (uint16_t)end_p;
+}
+/* room for a chain of newlen entries that outgrew its slot and moves to the top of the pool: twice its size and a margin */
+__device__ __forceinline__ uint32_t chain_grow_cap(uint32_t newlen) { return (2u * (newlen + 1u) + 256u + 7u) & ~7u; }

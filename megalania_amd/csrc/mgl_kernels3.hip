@@ -262,22 +262,8 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 		}
 		ctl->packets = (uint64_t)((int64_t)ctl->packets + dpackets);
 		ctl->rebuild_cost = ctl->cur_cost; /* exact cost of the new base */
-		if (failed) { ctl->apply_failed = 1; atomicOr(lim.why, failed); }
+		if (failed) give_up(ctl, lim, failed);
 	}
-}
-
-/* first packet start at or after checkpoint ck's boundary (new walk), or MGL_POS_INF */
-__device__ __forceinline__ uint32_t ckpt_boundary(const Base2& b, uint32_t ck)
-{
-	const uint32_t first = ck << MGL_CK2_SHIFT;
-	uint32_t w = first >> 6;
-	uint64_t keep = ~0ull << (first & 63u); /* the boundary may lie inside a bitmap word */
-	while (w < b.nw0) {
-		const uint64_t v = b.onwalk[w] & keep;
-		if (v) return (w << 6) + ctz64(v);
-		w++; keep = ~0ull;
-	}
-	return MGL_POS_INF;
 }
 
 struct Piece {
@@ -349,32 +335,18 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 				__syncthreads();
 			}
 		}
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } continue; }
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); continue; }
 		APPLY_STAGE(0)
 
 		const uint32_t off = b.ch_off[cx], len = b.ch_len[cx], cap = b.ch_cap[cx];
 		uint32_t* cpos = b.ch_pos + off;
 		uint16_t* cev = b.ch_ev + off;
-		/* ---- 1b. the chain index: every block behind the first change has (inserted - removed events below it) more entries
-		 * before it (the lists are in position order) */
-		{
-			const uint32_t ni = s_ni, nr = s_nr;
-			const uint32_t first = ((ni ? s_ipos[0] : MGL_POS_INF) < (nr ? s_rpos[0] : MGL_POS_INF)) ? s_ipos[0] : s_rpos[0];
-			uint32_t* row = b.ch_sb + (size_t)cx * b.sb_stride;
-			for (uint32_t blk = (first >> b.sb_shift) + 1u + tid; blk <= b.nsb; blk += MGL_APPLY_THREADS) {
-				const uint32_t bound = blk == b.nsb ? MGL_POS_INF : blk << b.sb_shift;
-				uint32_t a = 0, z = ni;
-				while (a < z) { const uint32_t m = (a + z) >> 1; if (s_ipos[m] < bound) a = m + 1; else z = m; }
-				const uint32_t di = a;
-				a = 0; z = nr;
-				while (a < z) { const uint32_t m = (a + z) >> 1; if (s_rpos[m] < bound) a = m + 1; else z = m; }
-				if (di != a) row[blk] += di - a;
-			}
-		}
+		/* ---- 1b. the chain index row of this context (the lists are in position order) */
+		chain_index_patch<false>(b.ch_sb + (size_t)cx * b.sb_stride, b, s_ipos, s_ni, s_rpos, s_nr, tid, MGL_APPLY_THREADS);
 		/* ---- 2. re-simulate: new entries, pieces, checkpoint segments.  First the whole workgroup
 		 * finds the chain entry of the first change (1024-ary search) and stages the entries from
 		 * there on in LDS; then one thread walks them. */
-		const uint32_t x0 = ((s_ni ? s_ipos[0] : MGL_POS_INF) < (s_nr ? s_rpos[0] : MGL_POS_INF)) ? s_ipos[0] : s_rpos[0];
+		const uint32_t x0 = first_change(s_ipos, s_ni, s_rpos, s_nr);
 		if (tid == 0) { s_lo = 0; s_hi = len; }
 		__syncthreads();
 		for (;;) { /* invariant: entries before s_lo are < x0, entry s_hi is >= x0 (the sentinel is) */
@@ -515,7 +487,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 			uint32_t newoff = off, newcap = cap;
 			if (!fail && newlen + 1 > cap) {
 				/* the chain outgrew its slot: move it to fresh space at the top of the pool */
-				newcap = (2u * (newlen + 1u) + 256u + 7u) & ~7u;
+				newcap = chain_grow_cap(newlen);
 				newoff = 0;
 				if (lane == 0) newoff = atomicAdd(b.pool_top, newcap);
 				newoff = uni(newoff);
@@ -533,7 +505,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 #undef CEV
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } continue; }
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); continue; }
 		APPLY_STAGE(2)
 		const uint32_t k0 = s_k0, oldlen = s_oldlen, newlen = s_newlen, kk = s_k, ns = s_ns, np = s_npiece;
 		/* ---- 3. the rewrite as copy jobs.  Pass B saves the old entries [k0, len] (only [k0, k) when the
@@ -577,7 +549,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 			if (shift && ad > lim.v[MGL_LIM_APPLY_SHIFT]) s_fail |= MGL_GU_APPLY_SHIFT;
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } continue; }
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); continue; }
 		const uint32_t jb = s_job_b, jc = s_job_c, spb = s_span_base, scb = s_scr_base, noff = s_newoff;
 		for (uint32_t i = tid; i < ns; i += MGL_APPLY_THREADS) { ab.span_pos[spb + i] = s_span_pos[i]; ab.span_ev[spb + i] = s_span_ev[i]; }
 		if (tid == 0 && new_sentinel) { ab.span_pos[spb + ns] = MGL_POS_INF; ab.span_ev[spb + ns] = (uint16_t)(s_newtail & 0x7FFu); }
@@ -622,17 +594,13 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 		for (uint32_t sg = 0; sg < s_nseg; sg++) {
 			const uint32_t lo = s_seg_lo[sg], hi = s_seg_hi[sg];
 			const uint32_t first = s_seg_first[sg], last = s_seg_last[sg];
-			/* a boundary can lie behind a packet that starts up to 272 bytes before lo */
-			const uint32_t ck_lo = (lo > MGL_MAX_MATCH ? lo - MGL_MAX_MATCH : 0u) >> MGL_CK2_SHIFT;
-			const uint32_t ck_hi = hi == MGL_POS_INF ? b.nck : ((hi >> MGL_CK2_SHIFT) + 1u < b.nck ? (hi >> MGL_CK2_SHIFT) + 1u : b.nck);
+			uint32_t ck_lo, ck_hi;
+			ckpt_rows(b, lo, hi, ck_lo, ck_hi);
 			for (uint32_t ck = ck_lo + tid; ck < ck_hi; ck += MGL_APPLY_THREADS) {
 				const uint32_t P = ckpt_boundary(b, ck); /* MGL_POS_INF: behind the last packet = final model */
 				if (P <= lo || P > hi) continue;     /* value there is the old one */
-				/* probability before the first new event of this segment at or after P */
-				uint32_t a = first, z = last;
-				while (a < z) { const uint32_t mid = (a + z) >> 1; if (s_span_pos[mid] < P) a = mid + 1; else z = mid; }
-				const uint16_t v = a < last ? (uint16_t)(s_span_ev[a] & 0x7FFu) : s_seg_endp[sg];
-				b.ck_probs[(size_t)ck * b.ck_elems + cx] = v;
+				b.ck_probs[(size_t)ck * b.ck_elems + cx] = span_prob_at([&](uint32_t i) { return s_span_pos[i]; }, [&](uint32_t i) { return s_span_ev[i]; },
+				                                                        first, last, P, s_seg_endp[sg]);
 			}
 		}
 		__syncthreads();

@@ -17,7 +17,7 @@
  *   k_batch_commit    ops into the bitmaps (atomics: clusters share words) and state records, journals into the slab,
  *                     staged events into one list in position order.  The summary levels of the special bitmap are
  *                     re-derived afterwards (pb_levels).
- *   k_batch_ctxlist   the touched contexts, ascending.
+ *   k_batch_scan, k_batch_fill   the events bucketed by context, the touched contexts on a list.
  *   k_batch_chains    one workgroup per touched context.  Its events fall into groups (one per cluster that touches
  *                     it); a thread per group re-simulates from the group's first change until the probability re-joins
  *                     the old trajectory -- through the following groups when it has not re-joined by their first
@@ -108,7 +108,6 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 	}
 	if (m == 0 || m > MGL_BATCH_MAX) return;
 	for (uint32_t i = tid; i < bt.nctx; i += blockDim.x) { bt.cnt_i[i] = 0; bt.cnt_r[i] = 0; bt.cur_i[i] = 0; bt.cur_r[i] = 0; }
-	(void)ctl; (void)c;
 	if (tid < m) {
 		const uint32_t j = bb.taken[tid];
 		s_j[tid] = j; s_t[tid] = out.win[2u * j]; s_e[tid] = lim.v[MGL_LIM_SOFT_REACH] ? (out.win2[j] & 0x7FFFFFFFu) : out.win[2u * j + 1u]; s_nd[tid] = out.ndiffs[j];
@@ -364,7 +363,6 @@ __global__ void __launch_bounds__(256) k_batch_commit(DevCtx c, Base2 b, Control
 	if (bt.hdr[4]) { if (blockIdx.x == 0 && threadIdx.x == 0) bt.hdr[0] = MGL_BATCH_REBUILD; return; } /* a walk gave up: nothing has been touched, the rebuild takes the step */
 	const uint32_t cl = blockIdx.x, tid = threadIdx.x, ncl = bt.hdr[1];
 	if (cl >= ncl) return;
-	(void)c; (void)ctl;
 	/* this cluster's place in the combined lists: clusters are in position order */
 	uint32_t ioff = 0, roff = 0;
 	for (uint32_t q = 0; q < cl; q++) { ioff += bt.cl[q * 8u + 2u]; roff += bt.cl[q * 8u + 3u]; }
@@ -602,7 +600,6 @@ __device__ __forceinline__ RunOut batch_run(const uint32_t* cpos, const uint16_t
 	uint32_t lg = g;
 	while (s_gcl[lg] != last_cl) lg++;
 	r.last_group = lg;
-	(void)c_base;
 	return r;
 }
 
@@ -733,7 +730,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 	__shared__ int32_t s_hdelta[MGL_BATCH_MAX + 1]; /* length change accumulated up to and including head h */
 	__shared__ uint32_t s_ng, s_nh, s_fail, s_scr_base, s_job_b, s_job_c, s_newoff, s_newcap, s_newlen, s_maxd;
 	if (bt.hdr[0] != MGL_BATCH_BEGAN || bt.hdr[4]) return;
-	if (bt.hdr[9]) { if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->apply_failed = 1; atomicOr(lim.why, MGL_GU_FORCED_EARLY); } return; } /* test hook (mgl_debug_set key 5): give up behind the commit */
+	if (bt.hdr[9]) { if (blockIdx.x == 0 && threadIdx.x == 0) give_up(ctl, lim, MGL_GU_FORCED_EARLY); return; } /* test hook (mgl_debug_set key 5): give up behind the commit */
 	/* one workgroup per touched context (k_batch_scan lists them: a tenth of the contexts on a step of fifteen moves), the
 	 * grid strides over the list */
 	const uint32_t ntouched = bt.hdr[10];
@@ -743,7 +740,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 	for (uint32_t w = blockIdx.x; w < ntouched; w += gridDim.x) {
 		const uint32_t cx = bt.touched[w];
 		const uint32_t ni = bt.cnt_i[cx], nr = bt.cnt_r[cx];
-		if (ni > lim.v[MGL_LIM_BATCH_SUB] || nr > lim.v[MGL_LIM_BATCH_SUB]) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, MGL_GU_CH_SUB); } return; }
+		if (ni > lim.v[MGL_LIM_BATCH_SUB] || nr > lim.v[MGL_LIM_BATCH_SUB]) { if (tid == 0) give_up(ctl, lim, MGL_GU_CH_SUB); return; }
 		long long my_cost = 0; /* thread 0 sums the context's runs */
 		__syncthreads(); /* (the shared arrays are the previous context's until here) */
 		if (tid == 0) s_fail = 0;
@@ -788,9 +785,6 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 		const uint16_t* cev = b.ch_ev + off;
 		uint32_t* const sb_row = b.ch_sb + (size_t)cx * b.sb_stride;
 		const uint32_t sb_info = b.nsb | (b.sb_shift << 24);
-		/* ---- 2b. the chain index: every block behind the first change has (inserted - removed events below it) more entries
-		 * before it.  (The runs below search the OLD chain with the index: a row is patched by its own workgroup only, after
-		 * the runs have been planned ... so this happens at the very end, see step 8.) */
 		/* ---- 3. every group starts a run, writing its new entries into MGL_BATCH_RES entries of the span area taken for it
 		 * (most runs fit: a perturbed probability re-joins the old trajectory after about a hundred events; one that does not is
 		 * run again in step 5, into a place of its size) ... */
@@ -815,7 +809,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			else s_run[tid] = batch_run<true>(cpos, cev, len, T, s_ipos, s_ibit, s_icl, ni, s_rpos, s_rcl, nr, s_gi[tid], s_gr[tid], s_gcl, tid, ab.span_pos, ab.span_ev, at, res, sb_row, sb_info);
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); return; }
 		/* ---- 4. ... the ones that count begin where the previous one ended */
 		if (tid == 0) {
 			uint32_t nh = 0, maxd = 0;
@@ -837,7 +831,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			uint32_t newoff = off, newcap = cap;
 			uint32_t fail = maxd > lim.v[MGL_LIM_BATCH_SHIFT] ? MGL_GU_CH_SHIFT : 0u;
 			if (!fail && newlen + 1u > cap) { /* the chain outgrew its slot: fresh space at the top of the pool */
-				newcap = (2u * (newlen + 1u) + 256u + 7u) & ~7u;
+				newcap = chain_grow_cap(newlen);
 				newoff = atomicAdd(b.pool_top, newcap);
 				if (newoff + newcap > b.pool_cap) fail = MGL_GU_CH_POOL;
 			}
@@ -845,7 +839,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			s_fail = fail;
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); return; }
 		const uint32_t nh = s_nh, noff = s_newoff, maxd = s_maxd;
 		const bool moved = noff != off;
 		/* ---- 5. a run that counts and did not fit its place: again, into one of its size; the new sentinel behind a run that
@@ -882,7 +876,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			if (!s_fail && r0.uncoupled) { ab.span_pos[at + r0.ns] = MGL_POS_INF; ab.span_ev[at + r0.ns] = (uint16_t)r0.end_p; }
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); return; }
 		/* ---- 6. the rewrite as copy jobs.  Pieces in chain order: [prefix] run 0, stretch 0, run 1, stretch 1, ... ; stretch h
 		 * = old entries [k_end(h), k_start(h + 1)) (the last one runs to the sentinel, included) and moves by the length change
 		 * accumulated up to run h.  In place: a stretch that does not move is left alone; one that moves goes in chunks that
@@ -913,7 +907,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			if (s_scr_base + scr > ab.scratch_cap) s_fail |= MGL_GU_CH_SCRATCH;
 		}
 		__syncthreads();
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); return; }
 		{
 			const uint32_t jb0 = s_job_b, jc0 = s_job_c, scr0 = s_scr_base;
 			const uint32_t pre = moved ? (s_run[s_hlist[0]].k_start + MGL_JOB_CHUNK - 1u) / MGL_JOB_CHUNK : 0u; /* the prefix's jobs lead pass B's list */
@@ -924,7 +918,6 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 					ab.jobs_b[jb0 + ci] = make_uint4(off + at, noff + at, (k0 - at) < MGL_JOB_CHUNK ? (k0 - at) : MGL_JOB_CHUNK, MGL_SPACE_CHAIN | (MGL_SPACE_CHAIN << 8));
 				}
 			}
-			(void)pre;
 			for (uint32_t h = 0; h < nh; h++) {
 				const RunOut& r = s_run[s_hlist[h]];
 				const int32_t dprev = h ? s_hdelta[h - 1u] : 0;
@@ -962,21 +955,10 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 				if (bt.hdr[13] && atomicAdd(&bt.hdr[12], 1u) + 1u == bt.hdr[13]) s_fail = MGL_GU_FORCED_LATE;
 			}
 		}
-		/* ---- 6b. the chain index of this context (nothing searches the old chain any more) */
+		/* ---- 6b. the chain index of this context: the runs above searched the OLD chain with it, nothing does any more */
 		__syncthreads();
-		if (s_fail) { if (tid == 0) { ctl->apply_failed = 1; atomicOr(lim.why, s_fail); } return; }
-		{
-			const uint32_t first = ((ni ? s_ipos[0] : MGL_POS_INF) < (nr ? s_rpos[0] : MGL_POS_INF)) ? s_ipos[0] : s_rpos[0];
-			for (uint32_t blk = (first >> b.sb_shift) + 1u + tid; blk <= b.nsb; blk += blockDim.x) {
-				const uint32_t bound = blk == b.nsb ? MGL_POS_INF : blk << b.sb_shift;
-				uint32_t a = 0, z = ni;
-				while (a < z) { const uint32_t m = (a + z) >> 1; if (s_ipos[m] < bound) a = m + 1; else z = m; }
-				const uint32_t di = a;
-				a = 0; z = nr;
-				while (a < z) { const uint32_t m = (a + z) >> 1; if (s_rpos[m] < bound) a = m + 1; else z = m; }
-				if (di != a) atomicAdd(&sb_row[blk], di - a); /* (no value comes back: the thread does not wait for the row) */
-			}
-		}
+		if (s_fail) { if (tid == 0) give_up(ctl, lim, s_fail); return; }
+		chain_index_patch<true>(sb_row, b, s_ipos, ni, s_rpos, nr, tid, blockDim.x); /* (atomic: no value comes back, the thread does not wait for the row) */
 		/* ---- 7. the runs go on a list: k_batch_ckpt patches this context's value in the dense checkpoints along each of them
 		 * (a run of a rare context reaches over hundreds of kilobytes, thousands of rows: a job for more than one wavefront) */
 		__syncthreads();
@@ -986,7 +968,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			if (at < bt.runs_cap) {
 				bt.runs[2u * at] = make_uint4(cx, r.lo, r.hi, s_hspan[tid]);
 				bt.runs[2u * at + 1u] = make_uint4(r.ns, r.end_p, 0u, 0u);
-			} else { ctl->apply_failed = 1; atomicOr(lim.why, MGL_GU_CH_RUNS); }
+			} else give_up(ctl, lim, MGL_GU_CH_RUNS);
 		}
 		if (tid == 0 && my_cost) atomicAdd((unsigned long long*)&bt.acc[0], (unsigned long long)my_cost);
 	}
@@ -1007,9 +989,8 @@ __global__ void __launch_bounds__(256) k_batch_ckpt(Base2 b, const Control* ctl,
 		__syncthreads();
 		if (in_lds) for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) { s_pos[i] = ab.span_pos[first + i]; s_ev[i] = ab.span_ev[first + i]; }
 		__syncthreads();
-		/* a boundary can lie behind a packet that starts up to 272 bytes before lo */
-		const uint32_t ck_lo = (lo > MGL_MAX_MATCH ? lo - MGL_MAX_MATCH : 0u) >> MGL_CK2_SHIFT;
-		const uint32_t ck_hi = hi == MGL_POS_INF ? b.nck : ((hi >> MGL_CK2_SHIFT) + 1u < b.nck ? (hi >> MGL_CK2_SHIFT) + 1u : b.nck);
+		uint32_t ck_lo, ck_hi;
+		ckpt_rows(b, lo, hi, ck_lo, ck_hi);
 		/* blockIdx.y: the run's rows in gridDim.y slices (a run of a rare context reaches over thousands of rows) */
 		const uint32_t per = (ck_hi - ck_lo + gridDim.y - 1u) / gridDim.y;
 		const uint32_t my_lo = ck_lo + blockIdx.y * per, my_hi = (my_lo + per) < ck_hi ? (my_lo + per) : ck_hi;
@@ -1020,11 +1001,8 @@ __global__ void __launch_bounds__(256) k_batch_ckpt(Base2 b, const Control* ctl,
 			if ((ck << MGL_CK2_SHIFT) > last_pos && last_pos != MGL_POS_INF) { b.ck_probs[(size_t)ck * b.ck_elems + cx] = (uint16_t)end_p; continue; }
 			const uint32_t P = ckpt_boundary(b, ck); /* on the NEW walk (the bitmaps are committed); MGL_POS_INF: the final model */
 			if (P <= lo || P > hi) continue;      /* the value there is the old one */
-			/* probability before the first new entry of the run at or after P */
-			uint32_t a = 0, z = ns;
-			while (a < z) { const uint32_t mid = (a + z) >> 1; if ((in_lds ? s_pos[mid] : ab.span_pos[first + mid]) < P) a = mid + 1; else z = mid; }
-			const uint16_t v = a < ns ? (uint16_t)((in_lds ? s_ev[a] : ab.span_ev[first + a]) & 0x7FFu) : (uint16_t)end_p;
-			b.ck_probs[(size_t)ck * b.ck_elems + cx] = v;
+			b.ck_probs[(size_t)ck * b.ck_elems + cx] = span_prob_at([&](uint32_t i) __attribute__((always_inline)) { return in_lds ? s_pos[i] : ab.span_pos[first + i]; },
+			                                                        [&](uint32_t i) __attribute__((always_inline)) -> uint32_t { return in_lds ? s_ev[i] : ab.span_ev[first + i]; }, 0u, ns, P, end_p);
 		}
 	}
 }

@@ -45,6 +45,7 @@ class Chains:
         self.o = Oracle(data, dict_limit=0x400000, **props)
         self.step = 0
         self.gave_up = self.in_place = self.sites = 0
+        self.multi = 0   # steps that took two or more moves and did not give up
         self.a.giveup_sites(); self.t.giveup_sites()
 
     def close(self):
@@ -97,6 +98,7 @@ class Chains:
                 assert word & ~expect == 0, (what, "another site fired", site_names(word))
             self.gave_up += 1 if word else 0
             self.in_place += 1 if (sa_["accepted"] and not word) else 0
+            self.multi += 1 if (sa_["accepted"] >= 2 and not word) else 0
             self.sites |= word
             if word or (sa_["accepted"] and self.step % every == 0):
                 self.check_structures(what)
