@@ -25,6 +25,8 @@
  *   mgl_sa_destroy    main.c:107-108,121 the matching frees
  *   mgl_props_sweep   no reference counterpart (lc = lp = pb = 0 are fixed there, main.c:45): one parse costed
  *                                    under every supported lc/lp/pb at once
+ *   mgl_cost_map      no reference counterpart (perplexity_encoder.c:6-17 keeps one sum): the cost of a parse per byte,
+ *                                    per coder and per packet type
  *   mgl_crossover, mgl_sa_cross_best, mgl_sa_exchange_cross, mgl_sa_exchange_cross_all
  *                     no reference counterpart (the reference runs one chain): several valid parses recombined region
  *                                    by region between the positions where their walks agree; the last one crosses the
@@ -477,6 +479,35 @@ int mgl_cost_slab(mgl_sa* sa, const mgl_packet* packets, uint64_t* total,
 #define MGL_PROPS_TRIPLES 75
 typedef struct { mgl_properties props; uint64_t cost; } mgl_props_cost;
 int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_cost* out, size_t cap, size_t* count, double* gpu_ms);
+/* Where a parse spends its bits (no reference counterpart; DESIGN.md section 10, megalania_amd/csrc/mgl_costmap.hip): the
+ * exact cost of the slab per byte, per coder and per packet type, in the cost units of mgl_cost_slab (2048 per bit).
+ *   - A parity hook like its neighbours: slab, costs, RNG streams, the block state of MGL_ACCEPT_AUTO, the focus window and
+ *     mgl_sa_stats stay as they were.  Both engines (MGL_F_FULLWALK too).
+ *   - The slab is walked from byte 0 with the LZMA initial state and a fresh model under `props` (NULL: the handle's).  A
+ *     triple other than the handle's is allowed, exactly as in mgl_props_sweep; lc + lp > 4 or pb > 4 is MGL_EINVAL.
+ *     packets == NULL: the current slab.  Off-walk entries are never looked at.
+ *   - A slab that mgl_cost_slab refuses is refused with the same code, and nothing is written.
+ *   - map_out (nullable): n entries.  A packet of exact cost c and length L that starts at p gives byte p + k the value
+ *     c / L + (k < c % L ? 1 : 0): the entries of a packet sum to its cost, the whole map to report->total.  c < 2^20.
+ *   - report (nullable): see below.  A coded bit belongs to the class its probability context lies in (the ranges are those
+ *     of megalania_amd/csrc/mgl_model.h, L.total = MGL_OFF_LIT + (0x300 << (lc + lp))).
+ *   - Device memory: 8 bytes per input byte for the length of the call (a mark per position and the map), allocated and
+ *     freed by the call; MGL_ENOMEM, with the handle left usable, when they do not fit. */
+#define MGL_CC_KIND       0  /* is_match, is_rep, is_rep_g0/g1/g2, is_rep0_long: contexts [0, MGL_OFF_LEN) */
+#define MGL_CC_LITERAL    1  /* literal coder: contexts [MGL_OFF_LIT, L.total) */
+#define MGL_CC_LENGTH     2  /* match length coder: [MGL_OFF_LEN, MGL_OFF_REP_LEN) */
+#define MGL_CC_REP_LENGTH 3  /* rep length coder: [MGL_OFF_REP_LEN, MGL_OFF_DIST) */
+#define MGL_CC_DISTANCE   4  /* pos_slot, pos_coder, align: [MGL_OFF_DIST, MGL_OFF_LIT) */
+#define MGL_CC_DIRECT     5  /* direct bits: 2048 each, no context */
+#define MGL_CC_CLASSES    6
+typedef struct {
+	uint64_t total, packets;                 /* what mgl_cost_slab returns for the same slab (under `props`) */
+	uint64_t class_cost[MGL_CC_CLASSES];     /* sums to total */
+	uint64_t class_bits[MGL_CC_CLASSES];     /* coded bits (events; direct bits for MGL_CC_DIRECT) */
+	uint64_t type_cost[4], type_packets[4], type_bytes[4]; /* index = packet type - 1; costs sum to total, bytes to n */
+	double gpu_ms;                           /* device time of the call's kernels; 0 from the host form */
+} mgl_cost_report;
+int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_properties* props, uint32_t* map_out, mgl_cost_report* report);
 /* Final model state after costing `packets`: probabilities in the reference's struct order
  * (lzma_state.h:47-53: lit | len | rep_len | dist | ctx_state), ctx_state, rep distances. */
 int mgl_final_state(mgl_sa* sa, const mgl_packet* packets, uint16_t* probs_out, size_t probs_cap,
@@ -545,7 +576,8 @@ int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* 
  * key 8 = n: the next n crossovers (mgl_crossover, mgl_sa_cross_best and the crossing exchanges) find no room for their
  * buffers (MGL_ENOMEM; exercises mgl_sa_exchange_cross_all's fall-back).
  * key 9 = pattern: overwrite the class hints (selector 26) with 0: all 0, 1: all 1, 2: alternating, anything else: random bytes
- * from `pattern`, and make the order (selector 27) from them again -- the test of k_pick_order. */
+ * from `pattern`, and make the order (selector 27) from them again -- the test of k_pick_order.
+ * key 10 = n: the next n calls of mgl_cost_map find no room for their buffers (MGL_ENOMEM; the handle stays usable). */
 int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes);
 int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value);
 /* draw n of neighbour j at global step `step` (31-bit, like rand()); j = 0xFFFFFFFF is the

@@ -39,13 +39,13 @@ HIP_SYMBOLS = [
     "mgl_sa_best_packed", "mgl_sa_adopt_best_packed", "mgl_props_sweep", "mgl_parse_sweep_props",
     "mgl_crossover", "mgl_sa_cross_best", "mgl_sa_exchange_cross",
     "mgl_comm_allgather_u64", "mgl_slab_hash", "mgl_sa_exchange_cross_all",
-    "mgl_sa_set_focus", "mgl_sa_focus", "mgl_focus_slice",
+    "mgl_sa_set_focus", "mgl_sa_focus", "mgl_focus_slice", "mgl_cost_map",
 ]
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
     "mgl_range_encoder_new", "mgl_range_encoder_free", "mgl_perplexity_encoder_new", "mgl_file_output_new",
     "mgl_memory_output_new", "mgl_emit_stream", "mgl_stream_info_read", "mgl_stream_import",
-    "mgl_emit_stream_dict", "mgl_bcj_x86", "mgl_emit_xz", "mgl_stream_info_read_x",
+    "mgl_emit_stream_dict", "mgl_bcj_x86", "mgl_emit_xz", "mgl_stream_info_read_x", "mgl_host_cost_map",
 ]
 IMPORT_CLIP_WINDOW = 1
 IMPORT_X86 = 2
@@ -126,6 +126,25 @@ DEFAULT_SWEEP = [(f, 16, s, a) for f in (MF_NEAREST, MF_FRONTIER) for s in (64, 
 
 class PropsCost(C.Structure):
     _fields_ = [("props", Properties), ("cost", C.c_uint64)]
+
+
+# mgl_cost_report: the coders a coded bit can belong to (MGL_CC_*) and the packet types, in table order
+CC_KIND, CC_LITERAL, CC_LENGTH, CC_REP_LENGTH, CC_DISTANCE, CC_DIRECT = range(6)
+COST_CLASSES = ["kind", "literal", "length", "rep_length", "distance", "direct"]
+PACKET_TYPES = ["literal", "match", "short_rep", "long_rep"]
+
+
+class CostReport(C.Structure):
+    _fields_ = [("total", C.c_uint64), ("packets", C.c_uint64), ("class_cost", C.c_uint64 * 6), ("class_bits", C.c_uint64 * 6),
+                ("type_cost", C.c_uint64 * 4), ("type_packets", C.c_uint64 * 4), ("type_bytes", C.c_uint64 * 4),
+                ("gpu_ms", C.c_double)]
+
+    def asdict(self, device: bool):
+        d = dict(total=self.total, packets=self.packets, class_cost=list(self.class_cost), class_bits=list(self.class_bits),
+                 type_cost=list(self.type_cost), type_packets=list(self.type_packets), type_bytes=list(self.type_bytes))
+        if device:
+            d["gpu_ms"] = self.gpu_ms
+        return d
 
 
 XO_MAX_PARENTS = 8
@@ -250,6 +269,7 @@ def hip_lib():
         L.mgl_sa_focus.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mgl_focus_slice.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64)]
+        L.mgl_cost_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Properties), C.c_void_p, C.POINTER(CostReport)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -276,6 +296,7 @@ def host_lib():
         L.mgl_stream_info_read.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(StreamInfo)]
         L.mgl_stream_import.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                         C.c_void_p, C.POINTER(ImportStats)]
+        L.mgl_host_cost_map.argtypes = [C.c_void_p, C.c_size_t, Properties, C.c_void_p, C.c_void_p, C.POINTER(CostReport)]
         _host = L
     return _host
 
@@ -410,6 +431,24 @@ def stream_import(stream: bytes, data: bytes, window: int = 0x400000, clip: bool
     stats = {k: getattr(st, k) for k, _ in ImportStats._fields_ if k not in ("error", "error_pos", "long_reps")}
     stats["long_reps"] = list(st.long_reps)
     return slab, stats
+
+
+def host_cost_map(data: bytes, slab: np.ndarray, props=(0, 0, 0)):
+    """Where the parse `slab` of `data` spends its bits under props = (lc, lp, pb), on the host (C, mgl_host_cost_map; no
+    device needed): (uint32 map, one entry per input byte, summing to the total; report dict: total, packets, class_cost /
+    class_bits in COST_CLASSES order, type_cost / type_packets / type_bytes in PACKET_TYPES order).  The same integers as
+    SA.cost_map.  Raises MglError (rc -1) for a slab that is no valid parse of `data` or an unsupported triple."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    slab = np.ascontiguousarray(slab, dtype=PACKET)
+    if len(slab) != len(buf):
+        raise MglError("host_cost_map: the slab must have one entry per input byte", rc=-1)
+    out = np.zeros(len(buf), dtype=np.uint32)
+    rep = CostReport()
+    rc = L.mgl_host_cost_map(_ptr(buf), len(buf), Properties(*props), _ptr(slab), _ptr(out), C.byref(rep))
+    if rc != 0:
+        raise MglError(f"rc={rc}: mgl_host_cost_map failed (invalid slab or properties?)", rc=rc)
+    return out, rep.asdict(device=False)
 
 
 class SA:
@@ -715,6 +754,20 @@ class SA:
         assert cnt.value == len(PROPS_TRIPLES)
         assert [(e.props.lc, e.props.lp, e.props.pb) for e in out] == PROPS_TRIPLES
         return np.array([e.cost for e in out], dtype=np.uint64), ms.value
+
+    def cost_map(self, slab=None, props=None):
+        """Where `slab` (None: the current slab) spends its bits under props = (lc, lp, pb) (None: the handle's; another
+        triple is allowed, as in props_sweep) (mgl_cost_map; SA state untouched).  Returns (uint32 map, report dict) as
+        host_cost_map does, the report with gpu_ms, the device time of the call's kernels."""
+        if slab is not None:
+            slab = np.ascontiguousarray(slab, dtype=PACKET)
+            if len(slab) != self.n:
+                raise MglError("cost_map: the slab must have one entry per input byte", rc=-1)
+        pr = None if props is None else C.byref(Properties(*props))
+        out = np.zeros(self.n, dtype=np.uint32)
+        rep = CostReport()
+        self._chk(self.L.mgl_cost_map(self.h, _ptr(slab), pr, _ptr(out), C.byref(rep)))
+        return out, rep.asdict(device=True)
 
     def final_state(self, slab):
         slab = np.ascontiguousarray(slab, dtype=PACKET)

@@ -14,6 +14,7 @@
 #include "mgl_optimal.hip"
 #include "mgl_adaptive.hip"
 #include "mgl_props.hip"
+#include "mgl_costmap.hip"
 #include "mgl_crossover.hip"
 #include "../../include/megalania_hip.h"
 #include "mgl_owner.h"
@@ -147,6 +148,7 @@ struct LaunchForm {
 /* diagnostic hooks of the tests (mgl_debug_set) */
 struct TestHooks {
 	uint32_t xo_nomem = 0;   /* key 8: the next so many crossovers find no room for their buffers */
+	uint32_t cm_nomem = 0;   /* key 10: the next so many cost maps find no room for theirs */
 	uint32_t batch_fail = 0; /* key 5: the next so many batch accepts give up behind their commit */
 	uint32_t batch_late = 0; /* ... 0: before any chain is touched; n: once the n-th touched context has rewritten its chain's descriptors */
 	uint32_t rollbacks = 0;  /* key 3: treat the next so many bulk steps that took moves as failed validations */
@@ -2371,6 +2373,61 @@ extern "C" int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_
 	return MGL_OK;
 }
 
+/* Where a parse spends its bits (mgl_costmap.hip).  Validity as in mgl_props_sweep: the walk of mgl_cost_slab decides it for a
+ * caller's slab, and the current slab is read where it lies.  The call's two buffers -- a mark and a map entry per position,
+ * 8 bytes per input byte -- are its own and die with it. */
+extern "C" int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_properties* props, uint32_t* map_out, mgl_cost_report* report)
+{
+	static_assert(MGL_CC_CLASSES == MGL_CM_CLASSES, "header and kernel disagree on the number of classes");
+	static const char* nomem = "mgl_cost_map: the per-position buffers do not fit the device";
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	const mgl_properties pr = props ? *props : sa->props;
+	if ((uint32_t)pr.lc + pr.lp > 4u || pr.pb > 4u) return fail(MGL_EINVAL, "mgl_cost_map: supported properties are lc + lp <= 4, pb <= 4");
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* slab = sa->base.v.slab;
+	if (packets) {
+		Control c;
+		int rc = scratch_walk(sa, packets, false, false, &c);
+		if (rc) return rc;
+		slab = sa->scratch.v.slab;
+	}
+	struct Tmp {
+		DevOwner own;
+		uint32_t *mark = nullptr, *map = nullptr;
+		CostMapSums* sums = nullptr;
+		hipEvent_t t0 = nullptr, t1 = nullptr;
+	} tmp;
+	const size_t n = sa->n;
+	if (sa->force.cm_nomem) { sa->force.cm_nomem--; return fail(MGL_ENOMEM, nomem); }
+	TRY(dnew(tmp.own, tmp.mark, n, -1, nomem));
+	TRY(dnew(tmp.own, tmp.map, n, -1, nomem));
+	TRY(dnew(tmp.own, tmp.sums, 1, -1, nomem));
+	HIPCHK(tmp.own.event(&tmp.t0));
+	HIPCHK(tmp.own.event(&tmp.t1));
+	hipStream_t s = sa->q.stream;
+	HIPCHK(hipEventRecord(tmp.t0, s));
+	HIPCHK(hipMemsetAsync(tmp.mark, 0, sizeof(uint32_t) * n, s));
+	hipLaunchKernelGGL(k_costmap_walk, dim3(1), dim3(64), 0, s, sa->ctx, mgl_make_layout(pr.lc, pr.lp, pr.pb), slab, tmp.mark, tmp.sums);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(k_costmap_spread, dim3((sa->n + 255u) / 256u), dim3(256), 0, s, sa->n, (const uint32_t*)tmp.mark, tmp.map);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(tmp.t1, s));
+	CostMapSums h;
+	HIPCHK(hipMemcpyAsync(&h, tmp.sums, sizeof h, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (h.end_pos != sa->n) return fail(MGL_EDEVICE, "mgl_cost_map: the walk stopped inside the slab (device consistency check)");
+	if (map_out) HIPCHK(hipMemcpy(map_out, tmp.map, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+	if (report) {
+		float ms = 0;
+		HIPCHK(hipEventElapsedTime(&ms, tmp.t0, tmp.t1));
+		report->total = h.total; report->packets = h.packets;
+		for (uint32_t k = 0; k < MGL_CC_CLASSES; k++) { report->class_cost[k] = h.class_cost[k]; report->class_bits[k] = h.class_bits[k]; }
+		for (uint32_t t = 0; t < 4; t++) { report->type_cost[t] = h.type_cost[t]; report->type_packets[t] = h.type_packets[t]; report->type_bytes[t] = h.type_bytes[t]; }
+		report->gpu_ms = ms;
+	}
+	return MGL_OK;
+}
+
 /* ---- crossover of parses (mgl_crossover.hip) */
 #define MGL_XO_DEF_GRAIN 64u
 struct XoBufs {
@@ -2732,6 +2789,7 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 		return MGL_OK;
 	}
 	if (key == 8) { sa->force.xo_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` crossovers fail to allocate their buffers (MGL_ENOMEM) */
+	if (key == 10) { sa->force.cm_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` cost maps fail to allocate their buffers (MGL_ENOMEM) */
 	if (key == 9) { /* test of k_pick_order: overwrite the hint bytes (0: all 0, 1: all 1, 2: alternating, else: random from `value`) and make the order again */
 		if (!sa->d_pick_order) return fail(MGL_EINVAL, "mgl_debug_set: no launch order on this handle");
 		const uint32_t K = sa->cfg.neighbours_per_step, slices = nbr_slices(sa);

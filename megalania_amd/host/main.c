@@ -32,7 +32,8 @@ static void usage(const char* argv0)
 	        "          [--match-finder nearest|frontier [--mf-depth N]] [--parse-sweep [--parse-sweep-table]] [--temperature B]\n"
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]\n"
-	        "          [--exchange best|cross|cross-all [--cross-grain N]]] [--focus LO:HI|rank] filename\n"
+	        "          [--exchange best|cross|cross-all [--cross-grain N]]] [--focus LO:HI|rank]\n"
+	        "          [--cost-map FILE] [--cost-report] [--cost-bucket B] filename\n"
 	        "  -o           write the stream to a file instead of stdout\n"
 	        "  --save-slab  after every epoch, write the best packet slab (resumable checkpoint)\n"
 	        "  --load-slab  start from a slab written by --save-slab (same input, same lc/lp/pb, same filter)\n"
@@ -96,6 +97,15 @@ static void usage(const char* argv0)
 	        "               stream whose input changed only there.  --focus rank (needs --chains N, N >= 2): before every epoch chain\n"
 	        "               R takes slice R of N of the input (mgl_focus_slice), shifted by half a slice every other epoch, so that\n"
 	        "               chains that leave an exchange with a common slab work on different stretches of it\n"
+	        "  --cost-map FILE  where the emitted parse spends its bits (mgl_cost_map, under the run's final lc/lp/pb): FILE gets one\n"
+	        "               little-endian u32 per input byte, the byte's share of its packet's exact cost (2048 per bit); the values\n"
+	        "               sum to the parse's cost.  With --filter x86 the positions are those of the filtered bytes.  The emitted\n"
+	        "               stream is the same with and without this option and the next two; each may be given alone\n"
+	        "  --cost-report    print to stderr one line per coder and per packet type of the emitted parse:\n"
+	        "               `cost-class: NAME bits N cost X B share P %% exact C` (kind, literal, length, rep_length, distance, direct)\n"
+	        "               `cost-type: NAME packets N bytes M cost X B share P %% exact C` (literal, match, short_rep, long_rep)\n"
+	        "               behind `cost-report: total X B exact C packets N lc=.. lp=.. pb=.. T ms`; X = C / 16384\n"
+	        "  --cost-bucket B  print one line per B input bytes: `cost-bucket: offset O bytes N cost X B bpb R exact C`\n"
 	        "  --accept     what a step of K neighbours takes: the best acceptable one (single), every one that is\n"
 	        "               the best of its own window (bulk), or whichever pays (auto, default)\n", argv0);
 }
@@ -331,6 +341,52 @@ static int make_filter_seed(mgl_sa* sa, uint32_t greedy, seed_spec seed, mgl_pac
 	return rc != MGL_OK ? rc : mgl_sa_current(sa, parse, cost);
 }
 
+/* --cost-map / --cost-report / --cost-bucket: the slab the run emits, handed to mgl_cost_map explicitly under the run's
+ * final triple.  The line formats are fixed (README.md, "Cost map"); costs in bytes are cost / 16384, `exact` is the
+ * integer itself. */
+static bool report_costs(mgl_sa* sa, const mgl_packet* slab, size_t n, mgl_properties props, const char* map_path, bool tables,
+                         unsigned long long bucket)
+{
+	static const char* const class_name[MGL_CC_CLASSES] = { "kind", "literal", "length", "rep_length", "distance", "direct" };
+	static const char* const type_name[4] = { "literal", "match", "short_rep", "long_rep" };
+	const bool want_map = map_path || bucket;
+	uint32_t* map = want_map ? (uint32_t*)malloc(sizeof(uint32_t) * n) : NULL;
+	mgl_cost_report r;
+	if (want_map && !map) { fprintf(stderr, "Error: out of memory\n"); return false; }
+	if (mgl_cost_map(sa, slab, &props, map, &r) != MGL_OK) { fprintf(stderr, "Error: %s\n", mgl_last_error()); free(map); return false; }
+	if (map_path) {
+		/* n little-endian u32, one per byte the LZMA layer sees */
+		FILE* f = fopen(map_path, "wb");
+		bool ok = f != NULL;
+		for (size_t p = 0; ok && p < n; p++) {
+			const uint8_t le[4] = { (uint8_t)map[p], (uint8_t)(map[p] >> 8), (uint8_t)(map[p] >> 16), (uint8_t)(map[p] >> 24) };
+			ok = fwrite(le, 4, 1, f) == 1;
+		}
+		if (f && fclose(f) != 0) ok = false;
+		if (!ok) { fprintf(stderr, "Error: could not write %s\n", map_path); free(map); return false; }
+	}
+	const double total = r.total ? (double)r.total : 1.0;
+	if (tables) {
+		fprintf(stderr, "cost-report: total %.3f B exact %llu packets %llu lc=%u lp=%u pb=%u %.3f ms\n", r.total / 16384.0, (unsigned long long)r.total,
+		        (unsigned long long)r.packets, props.lc, props.lp, props.pb, r.gpu_ms);
+		for (unsigned k = 0; k < MGL_CC_CLASSES; k++)
+			fprintf(stderr, "cost-class: %s bits %llu cost %.3f B share %.2f %% exact %llu\n", class_name[k], (unsigned long long)r.class_bits[k],
+			        r.class_cost[k] / 16384.0, 100.0 * r.class_cost[k] / total, (unsigned long long)r.class_cost[k]);
+		for (unsigned t = 0; t < 4; t++)
+			fprintf(stderr, "cost-type: %s packets %llu bytes %llu cost %.3f B share %.2f %% exact %llu\n", type_name[t], (unsigned long long)r.type_packets[t],
+			        (unsigned long long)r.type_bytes[t], r.type_cost[t] / 16384.0, 100.0 * r.type_cost[t] / total, (unsigned long long)r.type_cost[t]);
+	}
+	for (size_t lo = 0, hi = 0; bucket && lo < n; lo = hi) {
+		hi = n - lo < bucket ? n : lo + (size_t)bucket;
+		uint64_t c = 0;
+		for (size_t p = lo; p < hi; p++) c += map[p];
+		fprintf(stderr, "cost-bucket: offset %zu bytes %zu cost %.3f B bpb %.4f exact %llu\n", lo, hi - lo, c / 16384.0, c / 2048.0 / (double)(hi - lo),
+		        (unsigned long long)c);
+	}
+	free(map);
+	return true;
+}
+
 int main(int argc, char** argv)
 {
 	mgl_sa_config cfg;
@@ -363,6 +419,9 @@ int main(int argc, char** argv)
 	uint32_t dict_size = 0;
 	bool focus_given = false, focus_rank = false;
 	unsigned long long focus_lo = 0, focus_hi = 0;
+	const char* cost_map_path = NULL;
+	bool cost_report = false;
+	unsigned long long cost_bucket = 0;
 	for (int i = 1; i < argc; i++) {
 		const char* a = argv[i];
 		const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -371,6 +430,7 @@ int main(int argc, char** argv)
 		if (!strcmp(a, "--props-table")) { props_table = true; continue; }
 		if (!strcmp(a, "--parse-sweep")) { parse_sweep = true; continue; }
 		if (!strcmp(a, "--parse-sweep-table")) { parse_sweep_table = true; continue; }
+		if (!strcmp(a, "--cost-report")) { cost_report = true; continue; }
 		if (!v) { usage(argv[0]); return -1; }
 		if (!strcmp(a, "--neighbours")) cfg.neighbours_per_step = (uint32_t)strtoul(v, NULL, 0);
 		else if (!strcmp(a, "--epochs")) epochs = (unsigned)strtoul(v, NULL, 0);
@@ -440,6 +500,12 @@ int main(int argc, char** argv)
 					return -1;
 				}
 			}
+		}
+		else if (!strcmp(a, "--cost-map")) cost_map_path = v;
+		else if (!strcmp(a, "--cost-bucket")) {
+			char* end = NULL;
+			cost_bucket = strtoull(v, &end, 0);
+			if (end == v || *end || !cost_bucket) { fprintf(stderr, "Error: --cost-bucket takes a number of bytes, at least 1\n"); usage(argv[0]); return -1; }
 		}
 		else if (!strcmp(a, "-o")) out_path = v;
 		else if (!strcmp(a, "--save-slab")) save_path = v;
@@ -838,6 +904,8 @@ int main(int argc, char** argv)
 		fprintf(stderr, "Error: could not fetch the best slab: %s\n", mgl_last_error());
 		return -1;
 	}
+	if (rank == 0 && (cost_map_path || cost_report || cost_bucket) &&
+	    !report_costs(sa, packets_best, file_size, props, cost_map_path, cost_report, cost_bucket)) return -1;
 	mgl_comm_destroy(comm);
 	mgl_sa_destroy(sa);
 	if (rank != 0) return 0; /* every chain holds the common best slab after the last exchange; rank 0 writes it */

@@ -32,7 +32,8 @@ void mgl_lzma_state_free(mgl_lzma_state* st)
 	st->probs = NULL;
 }
 
-void mgl_lzma_encode_packet(mgl_lzma_state* st, EncoderInterface* enc, mgl_packet packet)
+/* plan `packet` at the state's position: the one place that fetches a literal's match byte and previous byte */
+static void plan_packet_here(const mgl_lzma_state* st, mgl_packet packet, mgl_plan* plan)
 {
 	const uint32_t pos = st->walk.pos;
 	const uint32_t byte = st->data[pos];
@@ -41,8 +42,13 @@ void mgl_lzma_encode_packet(mgl_lzma_state* st, EncoderInterface* enc, mgl_packe
 		if (st->walk.ctx_state >= 7) match_byte = st->data[pos - st->walk.dists[0] - 1];
 		if (pos > 0) prev_byte = st->data[pos - 1];
 	}
+	mgl_plan_packet(&st->layout, &st->walk, packet.type, packet.dist, packet.len, byte, match_byte, prev_byte, plan);
+}
+
+void mgl_lzma_encode_packet(mgl_lzma_state* st, EncoderInterface* enc, mgl_packet packet)
+{
 	mgl_plan plan;
-	mgl_plan_packet(&st->layout, &st->walk, packet.type, packet.dist, packet.len, byte, match_byte, prev_byte, &plan);
+	plan_packet_here(st, packet, &plan);
 	for (uint32_t slot = 0; slot < plan.nev; slot++) {
 		if (plan.ndirect && slot == plan.direct_after) {
 			(*enc->encode_direct_bits)(enc, plan.direct_val, plan.ndirect);
@@ -295,6 +301,81 @@ bool mgl_emit_stream_dict(const uint8_t* data, size_t n, mgl_properties props, c
 bool mgl_emit_stream(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, OutputInterface* output)
 {
 	return mgl_emit_stream_dict(data, n, props, slab, MGL_DEFAULT_DICT, output);
+}
+
+/* ------------------------------------------------------------------ cost map (no reference equivalent)
+ *
+ * The perplexity backend with a memory: an EncoderInterface that knows which probability each bit it is handed belongs
+ * to.  The interface carries the probability's value, not its place, so the sink follows the packet's plan itself: the
+ * driver plans the packet it is about to hand to mgl_lzma_encode_packet (the same plan that call makes), and the k-th
+ * encode_bit of the packet is event slot k of that plan -- slot order is coding order -- whose context index is the
+ * probability's offset in mgl_lzma_state.probs.  The offset names the coder (the ranges of csrc/mgl_model.h). */
+typedef struct {
+	mgl_plan plan;
+	uint32_t slot;
+	uint64_t packet_cost;
+	uint64_t class_cost[MGL_CC_CLASSES], class_bits[MGL_CC_CLASSES];
+} mgl_costmap_sink;
+
+static unsigned costmap_class(uint32_t offset)
+{
+	return offset < MGL_OFF_LEN ? MGL_CC_KIND : offset < MGL_OFF_REP_LEN ? MGL_CC_LENGTH : offset < MGL_OFF_DIST ? MGL_CC_REP_LENGTH
+	     : offset < MGL_OFF_LIT ? MGL_CC_DISTANCE : MGL_CC_LITERAL;
+}
+static void costmap_encode_bit(EncoderInterface* enc, bool bit, Prob prob)
+{
+	mgl_costmap_sink* s = (mgl_costmap_sink*)enc->private_data;
+	uint32_t offset, planned_bit;
+	mgl_plan_event(&s->plan, s->slot++, &offset, &planned_bit);
+	const unsigned k = costmap_class(offset);
+	const uint64_t cost = k_bit_cost[bit ? 2048 - prob : prob];
+	s->class_cost[k] += cost;
+	s->class_bits[k] += 1;
+	s->packet_cost += cost;
+}
+static void costmap_encode_direct_bits(EncoderInterface* enc, unsigned bits, unsigned num_bits)
+{
+	mgl_costmap_sink* s = (mgl_costmap_sink*)enc->private_data;
+	(void)bits;
+	const uint64_t cost = (uint64_t)num_bits << MGL_NUM_BIT_MODEL_TOTAL_BITS;
+	s->class_cost[MGL_CC_DIRECT] += cost;
+	s->class_bits[MGL_CC_DIRECT] += num_bits;
+	s->packet_cost += cost;
+}
+
+int mgl_host_cost_map(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, uint32_t* map_out,
+                      mgl_cost_report* report)
+{
+	if (!data || !slab || n == 0 || n > 0xFFFFFFFFu) return MGL_EINVAL;
+	if (props.lc + props.lp > 4 || props.pb > 4) return MGL_EINVAL;
+	if (!slab_is_valid(data, n, slab, 0xFFFFFFFFu)) return MGL_EINVAL; /* a cost has no dictionary: any source inside the input */
+	mgl_lzma_state st;
+	if (!mgl_lzma_state_init(&st, data, n, props)) return MGL_ENOMEM;
+	mgl_costmap_sink sink;
+	memset(&sink, 0, sizeof sink);
+	EncoderInterface enc = { costmap_encode_bit, costmap_encode_direct_bits, &sink };
+	mgl_cost_report r;
+	memset(&r, 0, sizeof r);
+	while (st.walk.pos < n) {
+		const size_t pos = st.walk.pos;
+		const mgl_packet pk = slab[pos];
+		plan_packet_here(&st, pk, &sink.plan);
+		sink.slot = 0;
+		sink.packet_cost = 0;
+		mgl_lzma_encode_packet(&st, &enc, pk);
+		const uint64_t c = sink.packet_cost;
+		if (map_out)
+			for (uint32_t k = 0; k < pk.len; k++) map_out[pos + k] = (uint32_t)(c / pk.len + (k < c % pk.len ? 1u : 0u));
+		r.total += c;
+		r.packets++;
+		r.type_cost[pk.type - 1] += c;
+		r.type_packets[pk.type - 1]++;
+		r.type_bytes[pk.type - 1] += pk.len;
+	}
+	mgl_lzma_state_free(&st);
+	for (unsigned k = 0; k < MGL_CC_CLASSES; k++) { r.class_cost[k] = sink.class_cost[k]; r.class_bits[k] = sink.class_bits[k]; }
+	if (report) *report = r;
+	return MGL_OK;
 }
 
 /* ------------------------------------------------------------------ x86 BCJ filter (.xz filter id 0x04)

@@ -16,6 +16,7 @@
  *   mgl_stream_info_read / _import    (no reference equivalent: the reference has no decoder)
  *   mgl_emit_stream_dict              mgl_emit_stream with the dictionary size as a parameter
  *   mgl_bcj_x86 / mgl_emit_xz         (no reference equivalent: the .xz container and its x86 filter)
+ *   mgl_host_cost_map                 (no reference equivalent: perplexity_encoder.c's sum split per byte and per coder)
  *
  * Stream import reads the parse out of an existing LZMA-alone (.lzma) or .xz stream of the same
  * input, as a starting slab for the search (the best known parse of a file is usually the one
@@ -80,6 +81,15 @@ bool mgl_emit_stream(const uint8_t* data, size_t n, mgl_properties props, const 
 /* the same stream with `dict_size` (0 = 0x400000) as the header's dictionary and as the window the slab is checked against */
 bool mgl_emit_stream_dict(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, uint32_t dict_size,
                           OutputInterface* output);
+
+/* mgl_cost_map (include/megalania_hip.h) without a device: the same integers -- per-byte map (nullable, n entries), class
+ * and type tables (nullable; gpu_ms = 0) -- from the slab's walk under `props`, through an EncoderInterface that prices
+ * every bit from csrc/mgl_cost_table.inc and files it under the coder its probability belongs to.  MGL_EINVAL, with
+ * nothing written, for lc + lp > 4, pb > 4, n = 0 and for a slab that is not a valid parse of the input (the check of
+ * mgl_emit_stream with no dictionary limit: a message on stderr names the entry); MGL_ENOMEM when the model cannot be
+ * allocated. */
+int mgl_host_cost_map(const uint8_t* data, size_t n, mgl_properties props, const mgl_packet* slab, uint32_t* map_out,
+                      mgl_cost_report* report);
 
 /* The .xz x86 branch/call/jump filter (filter id 0x04, start offset 0) over the whole buffer, in place: the relative
  * targets of E8 / E9 become absolute ones (encode != 0) or relative ones again (encode == 0). */
