@@ -524,60 +524,151 @@ int mgl_substrings(mgl_sa* sa, size_t pos, size_t max_len, uint32_t* offsets, ui
  * generate.  diffs (nullable): diff_cap entries per neighbour, ndiffs[j] valid ones. */
 int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs, mgl_diff* diffs,
                    uint32_t* ndiffs, size_t diff_cap);
-/* Test / diagnostic hooks (no reference counterpart).  mgl_debug_dump: raw copy of one of the
- * incremental engine's device structures; *bytes receives the size even when the buffer is too
- * small.  Selectors: 0 chain offsets, 1 chain lengths, 2 chain positions, 3 chain events,
- * 4 on-walk bitmap, 5 special bitmap, 6 special-state records, 7 dense checkpoints, 8 chain
- * capacities, 9 phase-cycle counters (MGL_F_PROFILE), 10 per-step overflow / repair counters (sixteen u32: [0] second-pass list,
- * [1] last-resort list, [2] spill slots, [3] repair picks, [4] unused and zero, [5] event pairs the window walks of the costed neighbours left out of their
- * change lists (0 under MGL_NO_EVCANCEL=1), [6..7] unused and zero, of the last finished step or mgl_neighbours
- * call; then, as [8..15], the same eight slots live, which the end of a step leaves at zero),
- * 11 parallel-builder totals, 12 / 13 match index (bucket offsets / positions), 14 accept-path
- * counters, 15 pick records, 16 the control block, 21 the windows (target, end) of the last costed neighbours, 22 their soft ends | dep << 31,
- * 23 / 24 / 25 their costs (u64), journal lengths and packets walked,
- * 30-35 / 40-45 / 50-55 / 60-65 positions / ranks / run starts / next byte of the exact-length orders D = 2..7,
- * 70-73 and 74-77 positions, ranks, run starts, next eight bytes of the 8- and 16-byte orders, 80 three u64 host counters: bulk
- * steps whose moves were patched into the base structures at once (batch accept), those that began so and fell back to the
- * rebuild behind their commit (status 1), and those that left the step to the rebuild before anything was touched because the
- * clusters or a walk gave up (status 2 with a failure seen), 81 / 82 the batch accept's header and totals, 83 the chain index,
- * selector 84 one u32: the give-up sites of the in-place accepts seen since the last dump (MGL_GU_* bits of csrc/mgl_base2.h;
- * cleared by the dump and by key 6), 85 one u32: the chain pool's top, 86 three u32: the chain index's block shift (the size
- * rule's or MGL_SB_SHIFT's; the parallel builder's block is the same), its blocks and the words of an index row,
- * 87 two u64 host counters, answered by every handle (the full-walk engine's too, like 21 and 22): the device allocations the
- * handle holds right now and their total bytes as requested.
- * 26 / 27 (empty with MGL_NO_ORDER=1 or position targets): what the last targets launch left for the fused pick + walk launch --
- * K bytes, 1 = the neighbour will pick, 0 = it takes a grow/shrink mutation; and K u32, every slice's neighbours in the order
- * the launch takes them up (the picking ones first, ascending in j inside each class).  28: the two-launch form's pickstate
- * records, 8 u32 per neighbour; word 7 = 1 where the pick half took the grow/shrink mutation (MGL_NO_FUSE=1 / MGL_F_PROFILE).
- * mgl_debug_set: key 0 = stop the neighbour kernels after a phase (tools/phase_cost.py), 50 =
- * stage timing in the accept path; key 1 = make the parallel builder redo every chain segment
- * serially (exercises its fallback); key 2 = shrink the first-pass change lists (a multiple of 8,
- * at most the allocated size) so that neighbours overflow into the second pass (exercises it); key 3 = treat the
- * next so many bulk steps that took moves as failed validations (exercises the rollback); key 4 = 1 / 0: the
- * re-simulation kernel adds up the bytes it reads (mgl_sa_stats.sim_bytes_counted; a few percent slower); key 5 = n: the next
- * n batch accepts (bulk steps that patch few moves into the base structures) give up after they have written their journals
- * and bitmaps (exercises the fallback to the rebuild from there): at the top of the chain kernel, before any chain is touched.
- * Second form, value >> 32 = m > 0: the give-up comes once the m-th touched context has rewritten its chain's descriptors,
- * taken its pool space and queued its copy jobs -- behind a partial rewrite by other workgroups (a low word of 0 then counts as 1).
- * Every batch accept the hook is applied to counts against the low word, also one that goes through because fewer than m
- * contexts got that far (nothing gives up then); steps that take nothing or too many moves do not count.
- * key 6 = id | value << 8: limit `id` of the in-place accepts := value, so that a give-up's real comparison fires on an
- * ordinary input; a value above the compiled / allocated one is refused (MGL_EINVAL); id 0 with value 0 restores every default.
- * Single accept (mgl_kernels3.hip): 1 = inserted / removed events of the accepted neighbour, 2 = iterations of its walk,
- * 3 = events of one context, 4 = rewritten chain entries of one context, 5 = pieces / checkpoint segments of one context,
- * 6 = entries a chain's tail may shift by in place.  Both accepts: 7 = chain pool entries (a chain that outgrows its slot
- * finds the pool exhausted), 8 = copy jobs per list, 9 = span area entries, 10 = save area entries.  Batch accept
- * (mgl_kernels5.hip): 11 = journal entries of one cluster, 12 = staged events of one cluster, 13 = bitmap / state-record ops
- * of one cluster, 14 = iterations of a cluster's walk, 15 = events of one kind per context, 16 = entries a stretch may shift
- * by in place, 17 = runs on the checkpoint list, 18 = 1 / 0: clusters are split at the members' soft window ends instead of
- * their hard ends (a wrong rule on purpose: the boundary guard of the cluster walks must then send the step to the rebuild).
- * key 7 = 1, 2 or the compiled MGL_BIG_WAVES (anything else: MGL_EINVAL): the wavefronts of a second-pass workgroup, which
- * share a neighbour's re-simulations; with 1 or 2 a neighbour's contexts take several trips (exercises that path).
- * key 8 = n: the next n crossovers (mgl_crossover, mgl_sa_cross_best and the crossing exchanges) find no room for their
- * buffers (MGL_ENOMEM; exercises mgl_sa_exchange_cross_all's fall-back).
- * key 9 = pattern: overwrite the class hints (selector 26) with 0: all 0, 1: all 1, 2: alternating, anything else: random bytes
- * from `pattern`, and make the order (selector 27) from them again -- the test of k_pick_order.
- * key 10 = n: the next n calls of mgl_cost_map find no room for their buffers (MGL_ENOMEM; the handle stays usable). */
+/* Test / diagnostic hooks (no reference counterpart).  mgl_debug_dump: raw copy of one of the incremental engine's device
+ * structures; *bytes receives the size even when the buffer is too small (MGL_ERANGE).  A handle of the full-walk engine
+ * answers MGL_DUMP_WINDOWS, MGL_DUMP_SOFT_ENDS and MGL_DUMP_ALLOCATIONS only.  K = cfg.neighbours_per_step, n = the input's
+ * bytes.  The structs named are those of megalania_amd/csrc/mgl_words.h.  The numbers are the ABI: they never change. */
+enum mgl_dump_selector {
+	MGL_DUMP_CHAIN_OFF = 0,      /* u32 per context: chain offsets */
+	MGL_DUMP_CHAIN_LEN = 1,      /* u32 per context: chain lengths */
+	MGL_DUMP_CHAIN_POS = 2,      /* u32 per pool entry: chain positions */
+	MGL_DUMP_CHAIN_EV = 3,       /* u16 per pool entry: chain events */
+	MGL_DUMP_ONWALK = 4,         /* u64 words: on-walk bitmap */
+	MGL_DUMP_SPECIAL = 5,        /* u64 words: special bitmap */
+	MGL_DUMP_SPECIAL_STATE = 6,  /* 8 u32 per position: special-state records */
+	MGL_DUMP_CHECKPOINTS = 7,    /* u16: dense checkpoints */
+	MGL_DUMP_CHAIN_CAP = 8,      /* u32 per context: chain capacities */
+	MGL_DUMP_PHASE_CYCLES = 9,   /* u64, 64 + 2 K: phase-cycle counters (MGL_F_PROFILE; empty without) */
+	MGL_DUMP_STEP_COUNTS = 10,   /* StepCounts[2], per-step overflow / repair counters: those of the last finished step or mgl_neighbours
+	                              * call, then the live ones, which the end of a step leaves at zero */
+	MGL_DUMP_PBUILD_TOTALS = 11, /* PbAcc up to and including `redone` (8 u64): parallel-builder totals */
+	MGL_DUMP_BUCKET_OFF = 12,    /* u32, 65537: match index, bucket offsets */
+	MGL_DUMP_BUCKET_POS = 13,    /* u32, n - 1: match index, positions */
+	MGL_DUMP_APPLY_HDR = 14,     /* ApplyHdr: accept-path counters */
+	MGL_DUMP_PICK_RECORDS = 15,  /* 4 u32 per neighbour: pick records */
+	MGL_DUMP_CONTROL = 16,       /* bytes: the control block */
+	MGL_DUMP_QUAD_POS = 18,      /* u32, n - 1: positions of the 4-byte order */
+	MGL_DUMP_QUAD_NEXT = 19,     /* u16, n - 1: its next bytes */
+	MGL_DUMP_WINDOWS = 21,       /* 2 u32 per neighbour: the windows (target, end) of the last costed neighbours */
+	MGL_DUMP_SOFT_ENDS = 22,     /* u32 per neighbour: their soft ends | dep << 31 */
+	MGL_DUMP_COSTS = 23,         /* u64 per neighbour: their costs */
+	MGL_DUMP_JOURNAL_LENS = 24,  /* u32 per neighbour: journal lengths */
+	MGL_DUMP_WALKED = 25,        /* u32 per neighbour: packets walked */
+	MGL_DUMP_PICK_HINTS = 26,    /* K bytes (empty with MGL_NO_ORDER=1 or position targets): what the last targets launch left for the fused
+	                              * pick + walk launch: 1 = the neighbour will pick, 0 = it takes a grow/shrink mutation */
+	MGL_DUMP_PICK_ORDER = 27,    /* K u32 (empty likewise): every slice's neighbours in the order the launch takes them up (the picking ones
+	                              * first, ascending in j inside each class) */
+	MGL_DUMP_PICKSTATE = 28,     /* 8 u32 per neighbour: the two-launch form's pickstate records; word 7 = 1 where the pick half took the
+	                              * grow/shrink mutation (MGL_NO_FUSE=1 / MGL_F_PROFILE) */
+	/* the exact-length orders D = 2..7: selector = base + D - 2 */
+	MGL_DUMP_XPOS_BASE = 30,     /* u32, n - 1: positions */
+	MGL_DUMP_XRANK_BASE = 40,    /* u32, n - 1: ranks */
+	MGL_DUMP_XRUN_BASE = 50,     /* u32, n - 1: run starts */
+	MGL_DUMP_XNEXT_BASE = 60,    /* u8, n - 1: next byte */
+	MGL_DUMP_OCT_POS = 70,       /* u32, n - 1: the 8-byte order's positions, */
+	MGL_DUMP_OCT_RANK = 71,      /* u32: ranks, */
+	MGL_DUMP_OCT_RUN = 72,       /* u32: run starts */
+	MGL_DUMP_OCT_NEXT8 = 73,     /* u64: and next eight bytes */
+	MGL_DUMP_HEX_POS = 74,       /* the same four of the 16-byte order */
+	MGL_DUMP_HEX_RANK = 75,
+	MGL_DUMP_HEX_RUN = 76,
+	MGL_DUMP_HEX_NEXT8 = 77,
+	MGL_DUMP_BATCH_COUNTS = 80,  /* three u64 host counters: bulk steps whose moves were patched into the base structures at once (batch
+	                              * accept), those that began so and fell back to the rebuild behind their commit (status 1), and those that
+	                              * left the step to the rebuild before anything was touched because the clusters or a walk gave up (status 2
+	                              * with a failure seen) */
+	MGL_DUMP_BATCH_HDR = 81,     /* BatchHdr: the batch accept's header */
+	MGL_DUMP_BATCH_ACC = 82,     /* BatchAcc: and totals */
+	MGL_DUMP_CHAIN_INDEX = 83,   /* u32: the chain index, a row per context */
+	MGL_DUMP_GIVEUP_SITES = 84,  /* one u32: the give-up sites of the in-place accepts seen since the last dump (enum mgl_giveup_site;
+	                              * cleared by the dump and by MGL_KEY_LIMIT) */
+	MGL_DUMP_POOL_TOP = 85,      /* one u32: the chain pool's top */
+	MGL_DUMP_INDEX_GEOMETRY = 86, /* three u32: the chain index's block shift (the size rule's or MGL_SB_SHIFT's; the parallel builder's block is
+	                              * the same), its blocks and the words of an index row */
+	MGL_DUMP_ALLOCATIONS = 87    /* two u64 host counters, answered by every handle: the device allocations the handle holds right now and
+	                              * their total bytes as requested */
+};
+enum mgl_debug_key {
+	MGL_KEY_DIAG_STOP = 0,     /* stop the neighbour kernels after a phase (tools/phase_cost.py); 50 = stage timing in the accept path */
+	MGL_KEY_PBUILD_FIX = 1,    /* make the parallel builder redo every chain segment serially (exercises its fallback) */
+	MGL_KEY_LIST_CAP = 2,      /* shrink the first-pass change lists (a multiple of 8, at most the allocated size) so that neighbours
+	                            * overflow into the second pass (exercises it) */
+	MGL_KEY_ROLLBACKS = 3,     /* treat the next so many bulk steps that took moves as failed validations (exercises the rollback) */
+	MGL_KEY_COUNT_TRAFFIC = 4, /* 1 / 0: the re-simulation kernel adds up the bytes it reads (mgl_sa_stats.sim_bytes_counted; a few percent slower) */
+	MGL_KEY_BATCH_FAIL = 5,    /* n: the next n batch accepts (bulk steps that patch few moves into the base structures) give up after they
+	                            * have written their journals and bitmaps (exercises the fallback to the rebuild from there): at the top of
+	                            * the chain kernel, before any chain is touched.  Second form, value >> 32 = m > 0: the give-up comes once
+	                            * the m-th touched context has rewritten its chain's descriptors, taken its pool space and queued its copy
+	                            * jobs -- behind a partial rewrite by other workgroups (a low word of 0 then counts as 1).  Every batch
+	                            * accept the hook is applied to counts against the low word, also one that goes through because fewer
+	                            * than m contexts got that far (nothing gives up then); steps that take nothing or too many moves do not count */
+	MGL_KEY_LIMIT = 6,         /* id | value << 8: limit `id` (enum mgl_accept_limit) of the in-place accepts := value, so that a give-up's
+	                            * real comparison fires on an ordinary input; a value above the compiled / allocated one is refused
+	                            * (MGL_EINVAL); id 0 with value 0 restores every default */
+	MGL_KEY_BIG_WAVES = 7,     /* 1, 2 or the compiled MGL_BIG_WAVES (anything else: MGL_EINVAL): the wavefronts of a second-pass workgroup,
+	                            * which share a neighbour's re-simulations; with 1 or 2 a neighbour's contexts take several trips */
+	MGL_KEY_CROSS_NOMEM = 8,   /* n: the next n crossovers (mgl_crossover, mgl_sa_cross_best and the crossing exchanges) find no room for
+	                            * their buffers (MGL_ENOMEM; exercises mgl_sa_exchange_cross_all's fall-back) */
+	MGL_KEY_PICK_HINTS = 9,    /* pattern: overwrite the class hints (MGL_DUMP_PICK_HINTS) with 0: all 0, 1: all 1, 2: alternating, anything
+	                            * else: random bytes from `pattern`, and make the order (MGL_DUMP_PICK_ORDER) from them again -- the test
+	                            * of k_pick_order */
+	MGL_KEY_COSTMAP_NOMEM = 10 /* n: the next n calls of mgl_cost_map find no room for their buffers (MGL_ENOMEM; the handle stays usable) */
+};
+/* What the in-place accepts compare against before they give up (MGL_KEY_LIMIT).  1-6: the single accept (mgl_kernels3.hip);
+ * 7-10: both; 11-18: the batch accept (mgl_kernels5.hip). */
+enum mgl_accept_limit {
+	MGL_LIM_APPLY_EVENTS = 1,   /* inserted / removed events of the accepted neighbour */
+	MGL_LIM_APPLY_GUARD = 2,    /* iterations of its walk */
+	MGL_LIM_APPLY_SUB = 3,      /* events of one context */
+	MGL_LIM_APPLY_SPAN = 4,     /* rewritten chain entries of one context */
+	MGL_LIM_APPLY_PIECES = 5,   /* pieces / checkpoint segments of one context */
+	MGL_LIM_APPLY_SHIFT = 6,    /* entries a chain's tail may shift by in place */
+	MGL_LIM_POOL = 7,           /* chain pool entries (a chain that outgrows its slot finds the pool exhausted) */
+	MGL_LIM_JOBS = 8,           /* copy jobs per list */
+	MGL_LIM_SPAN_AREA = 9,      /* span area entries */
+	MGL_LIM_SCRATCH = 10,       /* save area entries */
+	MGL_LIM_BATCH_JOURNAL = 11, /* journal entries of one cluster */
+	MGL_LIM_BATCH_EVENTS = 12,  /* staged events of one cluster */
+	MGL_LIM_BATCH_OPS = 13,     /* bitmap / state-record ops of one cluster */
+	MGL_LIM_BATCH_GUARD = 14,   /* iterations of a cluster's walk */
+	MGL_LIM_BATCH_SUB = 15,     /* events of one kind per context */
+	MGL_LIM_BATCH_SHIFT = 16,   /* entries a stretch may shift by in place */
+	MGL_LIM_BATCH_RUNS = 17,    /* runs on the checkpoint list */
+	MGL_LIM_SOFT_REACH = 18,    /* 1 / 0: clusters are split at the members' soft window ends instead of their hard ends (a wrong rule on
+	                             * purpose: the boundary guard of the cluster walks must then send the step to the rebuild) */
+	MGL_LIM_COUNT = 19
+};
+/* Where an in-place accept gave up: the bits of MGL_DUMP_GIVEUP_SITES */
+enum mgl_giveup_site {
+	MGL_GU_APPLY_EVENTS = (1u << 0),    /* k_apply_walk: event lists */
+	MGL_GU_APPLY_GUARD = (1u << 1),     /* k_apply_walk: iteration guard */
+	MGL_GU_APPLY_SUB = (1u << 2),       /* k_apply_chains: events of one context */
+	MGL_GU_APPLY_SPAN = (1u << 3),      /* k_apply_chains: rewritten entries of one context */
+	MGL_GU_APPLY_PIECES = (1u << 4),    /* k_apply_chains: pieces / checkpoint segments */
+	MGL_GU_APPLY_POOL = (1u << 5),      /* k_apply_chains: chain pool exhausted */
+	MGL_GU_APPLY_JOBS = (1u << 6),      /* k_apply_chains: job lists */
+	MGL_GU_APPLY_SPAN_AREA = (1u << 7),
+	MGL_GU_APPLY_SCRATCH = (1u << 8),
+	MGL_GU_APPLY_SHIFT = (1u << 9),
+	MGL_GU_CL_JOURNAL = (1u << 10),     /* k_batch_clusters: a cluster's merged journal */
+	MGL_GU_CL_ORDER = (1u << 11),       /* k_batch_clusters: merged journal not strictly ascending */
+	MGL_GU_WALK_OPS = (1u << 12),       /* k_batch_walk */
+	MGL_GU_WALK_EVENTS = (1u << 13),
+	MGL_GU_WALK_GUARD = (1u << 14),
+	MGL_GU_WALK_INVALID = (1u << 15),   /* a packet or rep packet of the merged walk that does not code the input */
+	MGL_GU_WALK_OVERRUN = (1u << 16),   /* the merged walk had not re-joined the base at the next cluster's first entry */
+	MGL_GU_CH_SUB = (1u << 17),         /* k_batch_chains */
+	MGL_GU_CH_SPAN_AREA = (1u << 18),   /* step 3: the place every run gets to begin with */
+	MGL_GU_CH_SHIFT = (1u << 19),
+	MGL_GU_CH_POOL = (1u << 20),
+	MGL_GU_CH_JOBS = (1u << 21),
+	MGL_GU_CH_SCRATCH = (1u << 22),
+	MGL_GU_CH_RUNS = (1u << 23),
+	MGL_GU_FORCED_EARLY = (1u << 24),   /* MGL_KEY_BATCH_FAIL, low word */
+	MGL_GU_FORCED_LATE = (1u << 25),    /* MGL_KEY_BATCH_FAIL, high word */
+	MGL_GU_CH_SPAN_RERUN = (1u << 26)   /* k_batch_chains step 5: the span area, for a run that did not fit its first place (the chain has
+	                                     * its pool space by then) */
+};
 int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes);
 int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value);
 /* draw n of neighbour j at global step `step` (31-bit, like rand()); j = 0xFFFFFFFF is the

@@ -7,7 +7,9 @@ or finds no GPU, every entry point raises.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import os
+import re
 
 import numpy as np
 
@@ -60,6 +62,55 @@ def best_props(costs):
     assert len(costs) == len(PROPS_TRIPLES)
     return PROPS_TRIPLES[costs.index(min(costs))]
 CONTAINER_LZMA, CONTAINER_XZ = 1, 2
+
+
+def _header_enum(name: str, prefix: str):
+    """(NAME, value) of every enumerator of `enum name` in include/megalania_hip.h, the one place they are kept"""
+    text = open(os.path.join(HERE, "..", "include", "megalania_hip.h")).read()
+    body = re.search(r"enum %s \{(.*?)\n\};" % name, text, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    pairs = re.findall(r"\b%s([A-Z0-9_]+) = (?:(\d+)|\(1u << (\d+)\))" % prefix, body)
+    return [(n, int(v) if v else 1 << int(k)) for n, v, k in pairs]
+
+
+def _dump_members():
+    """an index family (X_BASE = b, the exact-length orders D = 2..7) becomes X_D2 .. X_D7 = b .. b + 5"""
+    for n, v in _header_enum("mgl_dump_selector", "MGL_DUMP_"):
+        if n.endswith("_BASE"):
+            yield from ((f"{n[:-5]}_D{d}", v + d - 2) for d in range(2, 8))
+        else:
+            yield n, v
+
+
+DUMP = enum.IntEnum("DUMP", list(_dump_members()))                               # mgl_debug_dump selectors
+KEY = enum.IntEnum("KEY", _header_enum("mgl_debug_key", "MGL_KEY_"))             # mgl_debug_set keys
+LIM = enum.IntEnum("LIM", [p for p in _header_enum("mgl_accept_limit", "MGL_LIM_") if p[0] != "COUNT"])  # limit ids of KEY.LIMIT
+GU = enum.IntFlag("GU", _header_enum("mgl_giveup_site", "MGL_GU_"))              # give-up sites, the bits of DUMP.GIVEUP_SITES
+
+# BatchHdr::status, from the #defines of csrc/mgl_words.h
+BATCH = enum.IntEnum("BATCH", [(n, int(v)) for n, v in re.findall(
+    r"#define MGL_BATCH_(NONE|BEGAN|REBUILD|DONE) (\d+)u", open(os.path.join(HERE, "csrc", "mgl_words.h")).read())])
+
+# csrc/mgl_words.h, field for field (tests/test_debug_words_cpu.py compares them with what the C compiler lays out)
+_u4 = lambda *names: np.dtype([(n, "u4") if isinstance(n, str) else n for n in names])
+BATCH_HDR = _u4("status", "clusters", "n_ins", "n_rem", "failed", "journal", "unused6", "acceptable", "runs", "force_early",
+                "touched", "unused11", "force_reached", "force_late", "unused14", "unused15")
+BATCH_ACC = np.dtype([(n, "i8") for n in ("cost", "direct", "packets", "pad")])
+APPLY_HDR = _u4("n_ins", "n_rem", "n_tctx", "first_pos", "jobs_b", "jobs_c", "span_used", "scratch_used", ("stage_cycles", "u4", 5),
+                "walk_cycles0", "walk_cycles1", "walk_cycles2")
+PB_ACC = np.dtype([("cost", "u8"), ("packets", "u8"), ("ctx_state", "u8"), ("dists", "u8", 4), ("redone", "u8"), ("left", "u8")])
+STEP_COUNTS = _u4("second_pass", "last_resort", "spill_slots", "repair_picks", "unused4", "cancelled", "unused6", "unused7")
+PICKSTATE = _u4(("state", "u4", 7), "mutated")  # word 7 = 1: the pick half took the grow/shrink mutation
+# element type of what each selector hands out; DUMP.PBUILD_TOTALS stops before PbAcc's last field
+DUMP_DTYPE = {d: np.dtype("u4") for d in DUMP}
+DUMP_DTYPE.update({
+    DUMP.CHAIN_EV: np.dtype("u2"), DUMP.ONWALK: np.dtype("u8"), DUMP.SPECIAL: np.dtype("u8"), DUMP.CHECKPOINTS: np.dtype("u2"),
+    DUMP.PHASE_CYCLES: np.dtype("u8"), DUMP.STEP_COUNTS: STEP_COUNTS, DUMP.PBUILD_TOTALS: np.dtype([(n, PB_ACC[n]) for n in PB_ACC.names if n != "left"]),
+    DUMP.APPLY_HDR: APPLY_HDR, DUMP.CONTROL: np.dtype("u1"), DUMP.QUAD_NEXT: np.dtype("u2"), DUMP.COSTS: np.dtype("u8"),
+    DUMP.PICK_HINTS: np.dtype("u1"), DUMP.PICKSTATE: PICKSTATE, DUMP.OCT_NEXT8: np.dtype("u8"), DUMP.HEX_NEXT8: np.dtype("u8"),
+    DUMP.BATCH_COUNTS: np.dtype("u8"), DUMP.BATCH_HDR: BATCH_HDR, DUMP.BATCH_ACC: BATCH_ACC, DUMP.ALLOCATIONS: np.dtype("u8"),
+    **{DUMP[f"XNEXT_D{d}"]: np.dtype("u1") for d in range(2, 8)},
+})
 
 
 class MglError(RuntimeError):
@@ -795,26 +846,29 @@ class SA:
 
     def batch_counters(self):
         """(bulk steps whose moves were patched into the base by the batch accept, bulk steps that began one and fell back to the rebuild)"""
-        v = self.debug_dump(80, np.uint64)
+        v = self.debug_dump(DUMP.BATCH_COUNTS)
         return int(v[0]), int(v[1])
 
     def batch_giveups(self) -> int:
         """bulk steps that began a batch accept and left the step to the rebuild before anything was touched (a cluster's journal
         or a walk gave up: status 2 with a failure seen)"""
-        return int(self.debug_dump(80, np.uint64)[2])
+        return int(self.debug_dump(DUMP.BATCH_COUNTS)[2])
 
     def giveup_sites(self) -> int:
-        """give-up sites of the in-place accepts seen since the last call (MGL_GU_* bits, csrc/mgl_base2.h); reading clears"""
-        return int(self.debug_dump(84, np.uint32)[0])
+        """give-up sites of the in-place accepts seen since the last call (GU bits); reading clears"""
+        return int(self.debug_dump(DUMP.GIVEUP_SITES)[0])
 
     def set_limit(self, limit_id: int, value: int):
-        """mgl_debug_set key 6: lower limit `limit_id` of the in-place accepts; set_limit(0, 0) restores every default"""
-        self.debug_set(6, limit_id | (value << 8))
+        """KEY.LIMIT: lower limit `limit_id` (LIM) of the in-place accepts; set_limit(0, 0) restores every default"""
+        self.debug_set(KEY.LIMIT, limit_id | (value << 8))
 
     def debug_set(self, key: int, value: int):
         self._chk(self.L.mgl_debug_set(self.h, key, value))
 
-    def debug_dump(self, what: int, dtype) -> np.ndarray:
+    def debug_dump(self, what: int, dtype=None) -> np.ndarray:
+        """one of the engine's structures (DUMP), as elements of `dtype` (default: the selector's own, DUMP_DTYPE)"""
+        if dtype is None:
+            dtype = DUMP_DTYPE[DUMP(what)]
         need = C.c_size_t(0)
         probe = np.zeros(1, dtype=np.uint8)
         self.L.mgl_debug_dump(self.h, what, _ptr(probe), 0, C.byref(need))

@@ -212,7 +212,7 @@ struct mgl_sa {
 	uint4* d_pickstate;     /* 2 K: target, RNG position and walk state at the target (first half -> second half) */
 	uint4* d_pickrec;       /* K: picked packet, RNG position, ok flag (first half -> second half of the neighbour evaluation) */
 	LaunchForm form;
-	uint32_t* d_counts;     /* [0] first-pass overflow count, [1] second-pass overflow count, [2] spill slots used, [3] repair picks, [4] unused, always zero, [5] event pairs the window walks cancelled */
+	StepCounts* d_counts;   /* [0] live, [1] the last finished step's */
 	ApplyBuf ab;
 	uint32_t apply_blocks;
 	bool incremental_apply;
@@ -240,7 +240,7 @@ struct mgl_sa {
 	 * position targets, no split form */
 	unsigned char* d_pick_hint = nullptr;
 	uint32_t* d_pick_order = nullptr;
-	uint32_t* h_bstat = nullptr;   /* pinned: the batch accept's status words, read back once per bulk step */
+	BatchHdr* h_bstat = nullptr;   /* pinned: the batch accept's status words, read back once per bulk step */
 	TestHooks force;
 	AcceptLimits lim, lim_max;     /* what the in-place accepts compare against (mgl_debug_set key 6 lowers them) and the compiled / allocated values */
 	uint64_t batch_early_giveups = 0; /* bulk steps that began a batch accept and left it before anything was touched (clusters or a walk gave up) */
@@ -456,8 +456,8 @@ static int launch_apply(mgl_sa* sa, uint64_t next_gstep = ~0ull)
 		hipLaunchKernelGGL(k_copy_best, dim3(256), dim3(256), 0, sa->q.stream, (const Control*)sa->base.ctl,
 		                   (const mgl_pk*)sa->base.v.slab, sa->d_best, sa->ctx.n);
 	hipLaunchKernelGGL(k_apply_chains, dim3(sa->apply_blocks), dim3(MGL_APPLY_THREADS), 0, sa->q.stream, sa->ctx, accept_b2(sa), sa->base.ctl, accept_ab(sa), sa->lim);
-	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->q.stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)nullptr);
-	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->q.stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)nullptr);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->q.stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 0, (const BatchHdr*)nullptr);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, sa->q.stream, sa->b2, (const Control*)sa->base.ctl, sa->ab, 1, (const BatchHdr*)nullptr);
 	hipLaunchKernelGGL(k_build_end, dim3(1), dim3(64), sa->build_lds, sa->q.stream, sa->ctx, sa->b2, sa->base.ctl, sa->snapshots ? 1 : 0, sa->d_counts, sa->form.adaptive ? 1 : 0, sa->form.form_single ? 1 : 0);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
@@ -561,14 +561,14 @@ static int nbr_pick_walk(mgl_sa* sa, uint64_t step_override, uint32_t slices)
 		if (sa->form.fuse && !sa->d_prof) {
 			/* pick and walk of a neighbour in one wavefront: no barrier on the slice's slowest pick in front of its walks.  Under
 			 * MGL_F_PROFILE the two halves run as two launches (below): the stage marks are the pick half's */
-			launch_nbr2(sa, k_neighbours2<false, MGL_NBR_PICKWALK>, j1 - j0, 64, sa->fused_lds, st, step_override, sa->fused_lds, sa->d_todo, sa->d_counts,
+			launch_nbr2(sa, k_neighbours2<false, MGL_NBR_PICKWALK>, j1 - j0, 64, sa->fused_lds, st, step_override, sa->fused_lds, sa->d_todo, &sa->d_counts[0].second_pass,
 			            nullptr, sa->d_pickrec, j0, j1, (uint4*)sa->d_pick_order); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICKWALK>"); /* the order in the unused `pickstate` slot */
 		} else {
 			/* under MGL_F_PROFILE the instance that carries the stage marks (tools/pick_waves.py); normal runs hold none of them */
 			launch_nbr2(sa, sa->d_prof ? k_neighbours2<false, MGL_NBR_PICK, true> : k_neighbours2<false, MGL_NBR_PICK>, (j1 - j0 + sa->pick_waves - 1) / sa->pick_waves,
-			            64 * sa->pick_waves, sa->pick_waves * sa->per_wave_pick, st, step_override, sa->per_wave_pick, sa->d_todo, sa->d_counts, sa->d_prof,
+			            64 * sa->pick_waves, sa->pick_waves * sa->per_wave_pick, st, step_override, sa->per_wave_pick, sa->d_todo, &sa->d_counts[0].second_pass, sa->d_prof,
 			            sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_PICK>");
-			launch_nbr2(sa, k_neighbours2<false, MGL_NBR_REST>, j1 - j0, 64, sa->per_wave_rest, st, step_override, sa->per_wave_rest, sa->d_todo, sa->d_counts,
+			launch_nbr2(sa, k_neighbours2<false, MGL_NBR_REST>, j1 - j0, 64, sa->per_wave_rest, st, step_override, sa->per_wave_rest, sa->d_todo, &sa->d_counts[0].second_pass,
 			            g_prof_big ? nullptr : sa->d_prof, sa->d_pickrec, j0, j1, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_REST>");
 		}
 		HIPCHK(hipEventRecord(sa->q.ev_rest[h], st));
@@ -600,7 +600,7 @@ static int nbr_sim(mgl_sa* sa, uint32_t slices)
 static void nbr_one_kernel(mgl_sa* sa, uint64_t step_override)
 {
 	const uint32_t K = sa->cfg.neighbours_per_step, blocks2 = (K + sa->waves_per_block2 - 1) / sa->waves_per_block2;
-	launch_nbr2(sa, k_neighbours2<false, MGL_NBR_FULL>, blocks2, 64 * sa->waves_per_block2, sa->nbr2_lds, sa->q.stream, step_override, sa->per_wave2, sa->d_todo, sa->d_counts,
+	launch_nbr2(sa, k_neighbours2<false, MGL_NBR_FULL>, blocks2, 64 * sa->waves_per_block2, sa->nbr2_lds, sa->q.stream, step_override, sa->per_wave2, sa->d_todo, &sa->d_counts[0].second_pass,
 	            sa->d_prof, sa->d_pickrec, 0u, K, sa->d_pickstate); NBR_TRACE("k_neighbours2<false, MGL_NBR_FULL>");
 }
 /* The second pass, on the main stream behind whatever the regular form queued there; no records.  The few whose change lists
@@ -610,7 +610,7 @@ static void nbr_second_pass(mgl_sa* sa, uint64_t step_override, bool split_now)
 {
 	const uint32_t bigblocks = sa->big.slots < 1024u ? sa->big.slots : 1024u; /* the kernel strides over its list: none is dropped */
 	const uint32_t big_lds = 4096u + sa->per_wave2 + 12u * MGL_BIG_CAP + MGL_COOP_BYTES; /* + a copy of both lists for the re-simulations, + the workgroup's command */
-	launch_nbr2(sa, k_neighbours2<true, MGL_NBR_FULL>, bigblocks, 64 * sa->big_waves, big_lds, sa->q.stream, step_override, sa->per_wave2, sa->d_todo2, sa->d_counts + 1,
+	launch_nbr2(sa, k_neighbours2<true, MGL_NBR_FULL>, bigblocks, 64 * sa->big_waves, big_lds, sa->q.stream, step_override, sa->per_wave2, sa->d_todo2, &sa->d_counts[0].last_resort,
 	            g_prof_big ? sa->d_prof : nullptr, split_now ? sa->d_pickrec : nullptr, 0u, sa->cfg.neighbours_per_step, sa->d_pickstate); NBR_TRACE("k_neighbours2<true, MGL_NBR_FULL>");
 }
 /* Whatever overflowed even the second pass: exact full walk from byte 0.  It reads the second pass's list and writes the outputs
@@ -618,7 +618,7 @@ static void nbr_second_pass(mgl_sa* sa, uint64_t step_override, bool split_now)
  * pass, and the re-simulations join behind it -- the main stream waits for ev_sim. */
 static int nbr_last_resort(mgl_sa* sa, uint64_t step_override, bool split_now)
 {
-	nbr_fullwalk(sa, step_override, sa->d_todo2, sa->d_counts + 1);
+	nbr_fullwalk(sa, step_override, sa->d_todo2, &sa->d_counts[0].last_resort);
 	if (split_now) HIPCHK(hipStreamWaitEvent(sa->q.stream, sa->q.ev_sim, 0));
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
@@ -633,7 +633,7 @@ static int launch_neighbours(mgl_sa* sa, uint64_t step_override, bool zero_count
 		HIPCHK(hipGetLastError());
 		return MGL_OK;
 	}
-	if (zero_counts) HIPCHK(hipMemsetAsync(sa->d_counts, 0, 8 * sizeof(uint32_t), sa->q.stream)); /* todo counts + spill slots; k_step_end clears them between steps */
+	if (zero_counts) HIPCHK(hipMemsetAsync(sa->d_counts, 0, sizeof(StepCounts), sa->q.stream)); /* todo counts + spill slots; k_step_end clears them between steps */
 	const bool split_now = sa->form.split_nbr && !sa->form.form_single;
 	if (split_now) {
 		/* the step's neighbours in slices on two streams: while the slowest wavefronts of one slice's kernel finish,
@@ -815,9 +815,10 @@ static int alloc_search_buffers(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 	TRY(dnew(own, sa->bulk.taken, K));
 	TRY(dnew(own, sa->bulk.cstate, 2 * K));
 	TRY(dnew(own, sa->bulk.cflags, K, 0));
-	TRY(dnew(own, sa->bulk.hdr, 8));
-	const unsigned long long h0[8] = { 0, 0, 0, 0, 0, 0, ~0ull, 0 };
-	HIPCHK(hipMemcpy(sa->bulk.hdr, h0, sizeof h0, hipMemcpyHostToDevice));
+	TRY(dnew(own, sa->bulk.hdr, 1));
+	BulkHdr h0 = {};
+	h0.min_key = ~0ull;
+	HIPCHK(hipMemcpy(sa->bulk.hdr, &h0, sizeof h0, hipMemcpyHostToDevice));
 	TRY(dnew(own, sa->nbr.dpos, K * MGL_MAX_DIFFS));
 	TRY(dnew(own, sa->nbr.dold, K * MGL_MAX_DIFFS));
 	TRY(dnew(own, sa->nbr.dnew, K * MGL_MAX_DIFFS));
@@ -859,7 +860,7 @@ static int alloc_pbuild(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 	TRY(dnew(own, pb.stage, nblk * ((MGL_PB_STAGE_PER_POS << pb.shift) + 32u)));
 	TRY(dnew(own, pb.stage_n, nblk));
 	TRY(dnew(own, pb.stage_over, 1, 0));
-	TRY(dnew(own, pb.acc, 16, 0));
+	TRY(dnew(own, pb.acc, 1, 0));
 	pb.seg_cap = sa->b2.pool_cap / MGL_PB_SEG + ckpt_elems + 64u;
 	TRY(dnew(own, pb.seg_off, ckpt_elems + 1));
 	return dnew(own, pb.unres, pb.seg_cap);
@@ -913,7 +914,7 @@ static int alloc_accept_buffers(mgl_sa* sa)
 	ab.scratch_cap = sa->b2.pool_cap + 256u;
 	ab.span_cap = 1u << 22;
 	ab.job_cap = 1u << 20;
-	TRY(dnew(own, ab.hdr, 16, 0));
+	TRY(dnew(own, ab.hdr, 1, 0));
 	TRY(dnew(own, ab.ins_key, MGL_BATCH_ALLOC)); /* a single accept uses MGL_APPLY_CAP of each of these four */
 	TRY(dnew(own, ab.rem_key, MGL_BATCH_ALLOC));
 	TRY(dnew(own, ab.ins_pos, MGL_BATCH_ALLOC));
@@ -927,8 +928,8 @@ static int alloc_accept_buffers(mgl_sa* sa)
 	TRY(dnew(own, ab.jobs_c, ab.job_cap));
 	BatchBuf& bt = sa->batch;
 	memset(&bt, 0, sizeof bt);
-	TRY(dnew(own, bt.hdr, 16, 0));
-	TRY(dnew(own, bt.cl, 8 * MGL_BATCH_MAX));
+	TRY(dnew(own, bt.hdr, 1, 0));
+	TRY(dnew(own, bt.cl, MGL_CL_WORDS * MGL_BATCH_MAX));
 	TRY(dnew(own, bt.jpos, MGL_BATCH_MAX * MGL_MAX_DIFFS));
 	TRY(dnew(own, bt.jnew, MGL_BATCH_MAX * MGL_MAX_DIFFS));
 	TRY(dnew(own, bt.jold, MGL_BATCH_MAX * MGL_MAX_DIFFS));
@@ -948,8 +949,8 @@ static int alloc_accept_buffers(mgl_sa* sa)
 	TRY(dnew(own, bt.bk_ibit, MGL_BATCH_ALLOC));
 	TRY(dnew(own, bt.bk_icl, MGL_BATCH_ALLOC));
 	TRY(dnew(own, bt.bk_rcl, MGL_BATCH_ALLOC));
-	TRY(dnew(own, bt.acc, 4, 0));
-	HIPCHK(own.pinned((void**)&sa->h_bstat, sizeof(uint32_t) * 16));
+	TRY(dnew(own, bt.acc, 1, 0));
+	HIPCHK(own.pinned((void**)&sa->h_bstat, sizeof(BatchHdr)));
 	HIPCHK(own.event(&sa->q.ev_bstat, hipEventDisableTiming));
 	sa->batch_ok = sa->incremental_apply && !sa->env.no_batch;
 	uint32_t* why = nullptr;
@@ -978,8 +979,8 @@ static int alloc_nbr_scratch(mgl_sa* sa, uint32_t ckpt_elems)
 	TRY(dnew(own, g.rem_pos, g.cap * slots));
 	TRY(dnew(own, g.uctx, g.uctx_cap * slots));
 	TRY(dnew(own, sa->d_todo2, K + 1, 0));
-	TRY(dnew(own, sa->d_counts, 16, 0)); /* [0..7] live, [8..15] the last finished step's */
-	g.todo_in = sa->d_todo; g.todo_in_count = sa->d_counts; g.spill_ctr = sa->d_counts + 2;
+	TRY(dnew(own, sa->d_counts, 2, 0));
+	g.todo_in = sa->d_todo; g.todo_in_count = &sa->d_counts[0].second_pass; g.spill_ctr = &sa->d_counts[0].spill_slots;
 	g.evcancel = sa->env.no_evcancel ? 0u : 1u; /* the window walk lists a re-coded packet's changed events only; MGL_NO_EVCANCEL=1: all of them */
 	TRY(dnew(own, sa->d_pickrec, K));
 	TRY(dnew(own, sa->d_pickstate, 2 * K));
@@ -1964,7 +1965,7 @@ static DecideArgs decide_args(const mgl_sa* sa)
 }
 /* what closes a bulk step: best-slab tracking, the step's counters.  `gate` = the batch accept's status word when these
  * are queued before the host has read it (they then run beside the read-back), nullptr when the host knows the step is in */
-static void launch_bulk_close(mgl_sa* sa, const uint32_t* gate)
+static void launch_bulk_close(mgl_sa* sa, const BatchHdr* gate)
 {
 	hipLaunchKernelGGL(k_bulk_finish, dim3(1), dim3(64), 0, sa->q.stream, sa->base.ctl, sa->bulk, sa->snapshots ? 1 : 0,
 	                   sa->snapshots ? &sa->d_snap_meta[1].valid : (uint32_t*)nullptr, gate);
@@ -2000,14 +2001,14 @@ static int bulk_select(mgl_sa* sa)
  * Queues the batch accept (the next step's targets ahead behind its second pb_levels: launch_targets_ahead), the copy of
  * the status words to pinned memory, ev_bstat behind it and the closing kernels behind the gate; waits for ev_bstat on the
  * host.  bstat = the status words; *closed = the closing kernels are queued and the gate is open. */
-static int bulk_batch_accept(mgl_sa* sa, uint64_t next_gstep, uint32_t bstat[8], bool* closed)
+static int bulk_batch_accept(mgl_sa* sa, uint64_t next_gstep, BatchHdr* bstat, bool* closed)
 {
 	Base2& b = sa->b2;
 	hipStream_t st = sa->q.stream;
-	if (sa->force.batch_fail) { /* hdr[9]: give up at the top of k_batch_chains; hdr[13] = n: behind the n-th context's rewrite */
+	if (sa->force.batch_fail) { /* give up at the top of k_batch_chains, or behind the n-th context's rewrite */
 		const uint32_t early = sa->force.batch_late ? 0u : 1u, late = sa->force.batch_late;
-		HIPCHK(hipMemcpyAsync(sa->batch.hdr + 9, &early, sizeof early, hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(sa->batch.hdr + 13, &late, sizeof late, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(&sa->batch.hdr->force_early, &early, sizeof early, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(&sa->batch.hdr->force_late, &late, sizeof late, hipMemcpyHostToDevice, st));
 	}
 	const BatchBuf bt = accept_bt(sa);
 	const ApplyBuf ab = accept_ab(sa);
@@ -2022,26 +2023,27 @@ static int bulk_batch_accept(mgl_sa* sa, uint64_t next_gstep, uint32_t bstat[8],
 	hipLaunchKernelGGL(k_batch_fill, dim3(256), dim3(256), 0, st, sa->batch, sa->ab);
 	hipLaunchKernelGGL(k_batch_chains, dim3(MGL_BATCH_GRID), dim3(MGL_BATCH_THREADS), 0, st, sa->ctx, accept_b2(sa), sa->base.ctl, bt, ab, sa->lim);
 	hipLaunchKernelGGL(k_batch_ckpt, dim3(1024, 8), dim3(256), 0, st, b, (const Control*)sa->base.ctl, bt, ab);
-	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, st, b, (const Control*)sa->base.ctl, sa->ab, 0, (const uint32_t*)sa->batch.hdr);
-	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, st, b, (const Control*)sa->base.ctl, sa->ab, 1, (const uint32_t*)sa->batch.hdr);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, st, b, (const Control*)sa->base.ctl, sa->ab, 0, (const BatchHdr*)sa->batch.hdr);
+	hipLaunchKernelGGL(k_apply_jobs, dim3(1024), dim3(256), 0, st, b, (const Control*)sa->base.ctl, sa->ab, 1, (const BatchHdr*)sa->batch.hdr);
 	hipLaunchKernelGGL(k_batch_end, dim3(1), dim3(64), 0, st, sa->base.ctl, sa->batch);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(sa->h_bstat, sa->batch.hdr, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, st)); /* pinned: no staging copy */
+	const size_t read_back = offsetof(BatchHdr, acceptable) + sizeof sa->h_bstat->acceptable; /* status .. acceptable */
+	HIPCHK(hipMemcpyAsync(sa->h_bstat, sa->batch.hdr, read_back, hipMemcpyDeviceToHost, st)); /* pinned: no staging copy */
 	HIPCHK(hipEventRecord(sa->q.ev_bstat, st));
-	launch_bulk_close(sa, (const uint32_t*)sa->batch.hdr); /* behind the gate: they run while the host reads the status */
+	launch_bulk_close(sa, (const BatchHdr*)sa->batch.hdr); /* behind the gate: they run while the host reads the status */
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventSynchronize(sa->q.ev_bstat));
-	memcpy(bstat, sa->h_bstat, sizeof(uint32_t) * 8);
-	*closed = bstat[0] == MGL_BATCH_DONE || bstat[0] == MGL_BATCH_NONE;
+	memcpy(bstat, sa->h_bstat, read_back);
+	*closed = bstat->status == MGL_BATCH_DONE || bstat->status == MGL_BATCH_NONE;
 	if (!*closed && sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE; /* the step goes to the rebuild (or was never committed): the targets are made again */
 	if (sa->force.batch_fail) {
 		const uint32_t zero = 0u;
-		HIPCHK(hipMemcpy(sa->batch.hdr + 9, &zero, sizeof zero, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(sa->batch.hdr + 13, &zero, sizeof zero, hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(&sa->batch.hdr->force_early, &zero, sizeof zero, hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(&sa->batch.hdr->force_late, &zero, sizeof zero, hipMemcpyHostToDevice));
 		/* a step that took nothing, or went to the rebuild anyway, does not count; a batch accept the hook was applied to does,
 		 * whether it gave up or (late form with n above the contexts that got that far) went through: the hook never stays
 		 * armed with a stale n */
-		if ((bstat[0] == MGL_BATCH_BEGAN || bstat[0] == MGL_BATCH_DONE) && --sa->force.batch_fail == 0) sa->force.batch_late = 0;
+		if ((bstat->status == MGL_BATCH_BEGAN || bstat->status == MGL_BATCH_DONE) && --sa->force.batch_fail == 0) sa->force.batch_late = 0;
 	}
 	return MGL_OK;
 }
@@ -2051,12 +2053,12 @@ static int bulk_batch_accept(mgl_sa* sa, uint64_t next_gstep, uint32_t bstat[8],
  * the new parse against the input; a parse that fails is taken back as a whole.  One small read-back per bulk
  * step (a bulk step of this kind is a rebuild: milliseconds).  The validation runs on the second stream between ev_fork
  * and ev_val (launch_pbuild); the host waits for the main stream at every read-back. */
-static int bulk_rebuild_checked(mgl_sa* sa, const uint32_t bstat[8])
+static int bulk_rebuild_checked(mgl_sa* sa, const BatchHdr& bstat)
 {
-	const bool gave_up_late = sa->batch_ok && bstat[0] == MGL_BATCH_BEGAN;
+	const bool gave_up_late = sa->batch_ok && bstat.status == MGL_BATCH_BEGAN;
 	if (gave_up_late) sa->batch_fallbacks++;
-	if (sa->batch_ok && bstat[0] == MGL_BATCH_REBUILD && bstat[4]) sa->batch_early_giveups++; /* (MGL_BATCH_REBUILD without it: more moves than a batch accept handles) */
-	if (bstat[0] != MGL_BATCH_BEGAN)
+	if (sa->batch_ok && bstat.status == MGL_BATCH_REBUILD && bstat.failed) sa->batch_early_giveups++; /* (MGL_BATCH_REBUILD without it: more moves than a batch accept handles) */
+	if (bstat.status != MGL_BATCH_BEGAN)
 		hipLaunchKernelGGL(k_bulk_write, dim3(64), dim3(256), 0, sa->q.stream, sa->base.ctl, sa->nbr, sa->bulk, sa->base.v.slab);
 	HIPCHK(hipGetLastError());
 	Control now;
@@ -2082,13 +2084,14 @@ static int bulk_rebuild_checked(mgl_sa* sa, const uint32_t bstat[8])
 static int launch_bulk_tail(mgl_sa* sa, uint64_t next_gstep)
 {
 	TRY(bulk_select(sa));
-	uint32_t bstat[8] = { MGL_BATCH_REBUILD, 0, 0, 0, 0, 0, 0, 0 }; /* without the batch path: everything is the rebuild's */
+	BatchHdr bstat = {};
+	bstat.status = MGL_BATCH_REBUILD; /* without the batch path: everything is the rebuild's */
 	bool closed = false;
 	/* (the rollback net hangs under the rebuild: while a test forces it, steps go that way) */
-	if (sa->batch_ok && !sa->force.rollbacks) TRY(bulk_batch_accept(sa, next_gstep, bstat, &closed));
-	if (sa->batch_ok) sa->autoacc.select_small = bstat[7] <= 512u; /* this step's acceptable neighbours size the next step's selection */
-	if (bstat[0] == MGL_BATCH_DONE) sa->batch_accepts++; /* the moves are in: structures patched, exact cost in Control::rebuild_cost, every rep packet of the new walk checked */
-	else if (bstat[0] != MGL_BATCH_NONE) TRY(bulk_rebuild_checked(sa, bstat));
+	if (sa->batch_ok && !sa->force.rollbacks) TRY(bulk_batch_accept(sa, next_gstep, &bstat, &closed));
+	if (sa->batch_ok) sa->autoacc.select_small = bstat.acceptable <= 512u; /* this step's acceptable neighbours size the next step's selection */
+	if (bstat.status == MGL_BATCH_DONE) sa->batch_accepts++; /* the moves are in: structures patched, exact cost in Control::rebuild_cost, every rep packet of the new walk checked */
+	else if (bstat.status != MGL_BATCH_NONE) TRY(bulk_rebuild_checked(sa, bstat));
 	if (!closed) launch_bulk_close(sa, nullptr);
 	HIPCHK(hipGetLastError());
 	return MGL_OK;
@@ -2624,7 +2627,7 @@ extern "C" int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs,
 	if (!sa || !costs) return fail(MGL_EINVAL, "null argument");
 	HIPCHK(hipSetDevice(sa->device));
 	int rc = launch_neighbours(sa, global_step);
-	if (rc == MGL_OK && sa->d_counts) HIPCHK(hipMemcpyAsync(sa->d_counts + 8, sa->d_counts, sizeof(uint32_t) * 8, hipMemcpyDeviceToDevice, sa->q.stream));
+	if (rc == MGL_OK && sa->d_counts) HIPCHK(hipMemcpyAsync(&sa->d_counts[1], &sa->d_counts[0], sizeof(StepCounts), hipMemcpyDeviceToDevice, sa->q.stream));
 	if (rc) return rc;
 	const size_t K = sa->cfg.neighbours_per_step;
 	HIPCHK(hipMemcpyAsync(costs, sa->nbr.cost, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, sa->q.stream));
@@ -2652,164 +2655,167 @@ extern "C" int mgl_neighbours(mgl_sa* sa, uint64_t global_step, uint64_t* costs,
 	return MGL_OK;
 }
 
-/* test hook: raw copies of the incremental path's base structures */
+/* mgl_debug_dump's answers that are host values, not device memory: a buffer too small gets the size and nothing else */
+static int dump_host(const void* v, size_t sz, void* out, size_t cap_bytes, size_t* bytes)
+{
+	*bytes = sz;
+	if (cap_bytes >= sz) memcpy(out, v, sz);
+	return MGL_OK;
+}
+/* test hook: raw copies of the incremental path's base structures (enum mgl_dump_selector) */
 extern "C" int mgl_debug_dump(mgl_sa* sa, uint32_t what, void* out, size_t cap_bytes, size_t* bytes)
 {
 	if (!sa || !out || !bytes) return fail(MGL_EINVAL, "null argument");
-	if (what == 87) { /* host counters, on every handle: the device allocations the handle's owner holds, and their bytes as requested */
+	if (what == MGL_DUMP_ALLOCATIONS) { /* on every handle */
 		const uint64_t v[2] = { sa->own.live, sa->own.live_bytes };
-		*bytes = sizeof v;
-		if (cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
-		return MGL_OK;
+		return dump_host(v, sizeof v, out, cap_bytes, bytes);
 	}
-	if (!sa->incremental && what != 21 && what != 22) return fail(MGL_EINVAL, "mgl_debug_dump: handle runs the full-walk engine");
+	if (!sa->incremental && what != MGL_DUMP_WINDOWS && what != MGL_DUMP_SOFT_ENDS) return fail(MGL_EINVAL, "mgl_debug_dump: handle runs the full-walk engine");
 	HIPCHK(hipSetDevice(sa->device));
 	HIPCHK(hipStreamSynchronize(sa->q.stream));
 	const Base2& b = sa->b2;
+	const MatchIndex& ix = sa->ix;
+	const size_t K = sa->cfg.neighbours_per_step, n1 = sa->n - 1;
 	const void* src = nullptr;
 	size_t sz = 0;
 	uint32_t top = 0;
 	if (sa->incremental) HIPCHK(hipMemcpy(&top, b.pool_top, sizeof top, hipMemcpyDeviceToHost));
 	switch (what) {
-	case 0: src = b.ch_off; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
-	case 1: src = b.ch_len; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
-	case 2: src = b.ch_pos; sz = sizeof(uint32_t) * (size_t)top; break;
-	case 3: src = b.ch_ev; sz = sizeof(uint16_t) * (size_t)top; break;
-	case 4: src = b.onwalk; sz = sizeof(uint64_t) * b.nw0; break;
-	case 5: src = b.sp0; sz = sizeof(uint64_t) * b.nw0; break;
-	case 6: src = b.sp_state; sz = sizeof(uint32_t) * 8 * (size_t)sa->n; break;
-	case 7: src = b.ck_probs; sz = sizeof(uint16_t) * (size_t)b.nck * b.ck_elems; break;
-	case 8: src = b.ch_cap; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
-	case 9: src = sa->d_prof; sz = sa->d_prof ? sizeof(unsigned long long) * (64 + 2 * (size_t)sa->cfg.neighbours_per_step) : 0; break;
-	case 80: { /* host counters: batch accepts, batch accepts that fell back to the rebuild behind their commit, and those that left the
-	            * step to the rebuild before anything was touched */
-		const uint64_t v[3] = { sa->batch_accepts, sa->batch_fallbacks, sa->batch_early_giveups };
-		*bytes = sizeof v;
-		if (cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
-		return MGL_OK;
-	}
-	case 86: { /* the chain index's geometry as built: block shift (the size rule's, or MGL_SB_SHIFT's), blocks, words per row */
-		const uint32_t v[3] = { b.sb_shift, b.nsb, b.sb_stride };
-		*bytes = sizeof v;
-		if (cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
-		return MGL_OK;
-	}
-	case 84: src = sa->lim.why; sz = sizeof(uint32_t); break; /* give-up sites seen since the last dump (cleared below) */
-	case 85: src = b.pool_top; sz = sizeof(uint32_t); break;
-	case 83: src = b.ch_sb; sz = sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride; break; /* the chain index, row per context, sb_stride words each */
-	case 81: src = sa->batch.hdr; sz = sizeof(uint32_t) * 16; break;
-	case 82: src = sa->batch.acc; sz = sizeof(long long) * 4; break;
-	case 10: { /* the per-step counters: [0..7] of the last finished step / mgl_neighbours call ([5]: event pairs the window walks of its costed neighbours left out of their change lists), [8..15] the live ones (zero between steps) */
-		uint32_t v[16];
+	case MGL_DUMP_CHAIN_OFF: src = b.ch_off; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
+	case MGL_DUMP_CHAIN_LEN: src = b.ch_len; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
+	case MGL_DUMP_CHAIN_POS: src = b.ch_pos; sz = sizeof(uint32_t) * (size_t)top; break;
+	case MGL_DUMP_CHAIN_EV: src = b.ch_ev; sz = sizeof(uint16_t) * (size_t)top; break;
+	case MGL_DUMP_ONWALK: src = b.onwalk; sz = sizeof(uint64_t) * b.nw0; break;
+	case MGL_DUMP_SPECIAL: src = b.sp0; sz = sizeof(uint64_t) * b.nw0; break;
+	case MGL_DUMP_SPECIAL_STATE: src = b.sp_state; sz = sizeof(uint32_t) * 8 * (size_t)sa->n; break;
+	case MGL_DUMP_CHECKPOINTS: src = b.ck_probs; sz = sizeof(uint16_t) * (size_t)b.nck * b.ck_elems; break;
+	case MGL_DUMP_CHAIN_CAP: src = b.ch_cap; sz = sizeof(uint32_t) * sa->ctx.L.total; break;
+	case MGL_DUMP_PHASE_CYCLES: src = sa->d_prof; sz = src ? sizeof(unsigned long long) * (64 + 2 * K) : 0; break;
+	case MGL_DUMP_STEP_COUNTS: { /* last, then live */
+		StepCounts v[2];
 		*bytes = sizeof v;
 		if (cap_bytes < sizeof v) return fail(MGL_ERANGE, "mgl_debug_dump: buffer too small");
-		HIPCHK(hipMemcpy(v, sa->d_counts + 8, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost));
-		HIPCHK(hipMemcpy(v + 8, sa->d_counts, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost));
-		memcpy(out, v, sizeof v);
-		return MGL_OK;
+		HIPCHK(hipMemcpy(&v[0], &sa->d_counts[1], sizeof(StepCounts), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(&v[1], &sa->d_counts[0], sizeof(StepCounts), hipMemcpyDeviceToHost));
+		return dump_host(v, sizeof v, out, cap_bytes, bytes);
 	}
-	case 14: src = sa->ab.hdr; sz = sa->ab.hdr ? sizeof(uint32_t) * 16 : 0; break; /* apply counters / stage cycles */
-	case 16: src = sa->base.ctl; sz = sizeof(Control); break; /* raw control block */
-	case 15: src = sa->d_pickrec; sz = sa->d_pickrec ? sizeof(uint4) * sa->cfg.neighbours_per_step : 0; break;
-	case 18: src = sa->ix.quad_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 19: src = sa->ix.quad_nx; sz = sizeof(uint16_t) * (sa->n - 1); break;
-	case 12: src = sa->ix.bucket_off; sz = sizeof(uint32_t) * 65537; break;
-	case 13: src = sa->ix.bucket_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 30: case 31: case 32: case 33: case 34: case 35: src = sa->ix.xpos[what - 30]; sz = sizeof(uint32_t) * (sa->n - 1); break; /* exact-length orders D = what - 28 */
-	case 40: case 41: case 42: case 43: case 44: case 45: src = sa->ix.xrank[what - 40]; sz = src ? sizeof(uint32_t) * (sa->n - 1) : 0; break;
-	case 50: case 51: case 52: case 53: case 54: case 55: src = sa->ix.xrun[what - 50]; sz = src ? sizeof(uint32_t) * (sa->n - 1) : 0; break;
-	case 60: case 61: case 62: case 63: case 64: case 65: src = sa->ix.xnxb[what - 60]; sz = sa->n - 1; break;
-	case 70: src = sa->ix.oct_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 71: src = sa->ix.oct_rank; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 72: src = sa->ix.oct_run; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 73: src = sa->ix.oct_nx8; sz = sizeof(uint64_t) * (sa->n - 1); break;
-	case 74: src = sa->ix.hex_pos; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 75: src = sa->ix.hex_rank; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 76: src = sa->ix.hex_run; sz = sizeof(uint32_t) * (sa->n - 1); break;
-	case 77: src = sa->ix.hex_nx8; sz = sizeof(uint64_t) * (sa->n - 1); break;
-	case 23: src = sa->nbr.cost; sz = sizeof(uint64_t) * sa->cfg.neighbours_per_step; break;   /* costs, */
-	case 24: src = sa->nbr.ndiffs; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* journal lengths */
-	case 25: src = sa->nbr.walked; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* and packets walked of the last costed neighbours */
-	case 22: src = sa->nbr.win2; sz = sizeof(uint32_t) * sa->cfg.neighbours_per_step; break; /* soft ends | dep << 31 */
-	case 21: src = sa->nbr.win; sz = sizeof(uint32_t) * 2 * sa->cfg.neighbours_per_step; break; /* windows of the last costed neighbours */
-	case 26: src = sa->d_pick_hint; sz = src ? sa->cfg.neighbours_per_step : 0; break;                     /* class hints of the last targets made */
-	case 27: src = sa->d_pick_order; sz = src ? sizeof(uint32_t) * sa->cfg.neighbours_per_step : 0; break;  /* and the order made from them */
-	case 28: src = sa->d_pickstate; sz = src ? sizeof(uint4) * 2 * sa->cfg.neighbours_per_step : 0; break;  /* what the two-launch form's pick half left */
-	case 11: src = sa->pb.acc; sz = sa->pb.acc ? sizeof(unsigned long long) * 8 : 0; break; /* parallel builder totals */
+	case MGL_DUMP_PBUILD_TOTALS: src = sa->pb.acc; sz = src ? offsetof(PbAcc, left) : 0; break;
+	case MGL_DUMP_BUCKET_OFF: src = ix.bucket_off; sz = sizeof(uint32_t) * 65537; break;
+	case MGL_DUMP_BUCKET_POS: src = ix.bucket_pos; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_APPLY_HDR: src = sa->ab.hdr; sz = src ? sizeof(ApplyHdr) : 0; break;
+	case MGL_DUMP_PICK_RECORDS: src = sa->d_pickrec; sz = src ? sizeof(uint4) * K : 0; break;
+	case MGL_DUMP_CONTROL: src = sa->base.ctl; sz = sizeof(Control); break;
+	case MGL_DUMP_QUAD_POS: src = ix.quad_pos; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_QUAD_NEXT: src = ix.quad_nx; sz = sizeof(uint16_t) * n1; break;
+	case MGL_DUMP_WINDOWS: src = sa->nbr.win; sz = sizeof(uint32_t) * 2 * K; break;
+	case MGL_DUMP_SOFT_ENDS: src = sa->nbr.win2; sz = sizeof(uint32_t) * K; break;
+	case MGL_DUMP_COSTS: src = sa->nbr.cost; sz = sizeof(uint64_t) * K; break;
+	case MGL_DUMP_JOURNAL_LENS: src = sa->nbr.ndiffs; sz = sizeof(uint32_t) * K; break;
+	case MGL_DUMP_WALKED: src = sa->nbr.walked; sz = sizeof(uint32_t) * K; break;
+	case MGL_DUMP_PICK_HINTS: src = sa->d_pick_hint; sz = src ? K : 0; break;
+	case MGL_DUMP_PICK_ORDER: src = sa->d_pick_order; sz = src ? sizeof(uint32_t) * K : 0; break;
+	case MGL_DUMP_PICKSTATE: src = sa->d_pickstate; sz = src ? sizeof(uint4) * 2 * K : 0; break;
+	case 30: case 31: case 32: case 33: case 34: case 35: src = ix.xpos[what - MGL_DUMP_XPOS_BASE]; sz = sizeof(uint32_t) * n1; break;
+	case 40: case 41: case 42: case 43: case 44: case 45: src = ix.xrank[what - MGL_DUMP_XRANK_BASE]; sz = src ? sizeof(uint32_t) * n1 : 0; break;
+	case 50: case 51: case 52: case 53: case 54: case 55: src = ix.xrun[what - MGL_DUMP_XRUN_BASE]; sz = src ? sizeof(uint32_t) * n1 : 0; break;
+	case 60: case 61: case 62: case 63: case 64: case 65: src = ix.xnxb[what - MGL_DUMP_XNEXT_BASE]; sz = n1; break;
+	case MGL_DUMP_OCT_POS: src = ix.oct_pos; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_OCT_RANK: src = ix.oct_rank; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_OCT_RUN: src = ix.oct_run; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_OCT_NEXT8: src = ix.oct_nx8; sz = sizeof(uint64_t) * n1; break;
+	case MGL_DUMP_HEX_POS: src = ix.hex_pos; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_HEX_RANK: src = ix.hex_rank; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_HEX_RUN: src = ix.hex_run; sz = sizeof(uint32_t) * n1; break;
+	case MGL_DUMP_HEX_NEXT8: src = ix.hex_nx8; sz = sizeof(uint64_t) * n1; break;
+	case MGL_DUMP_BATCH_COUNTS: {
+		const uint64_t v[3] = { sa->batch_accepts, sa->batch_fallbacks, sa->batch_early_giveups };
+		return dump_host(v, sizeof v, out, cap_bytes, bytes);
+	}
+	case MGL_DUMP_BATCH_HDR: src = sa->batch.hdr; sz = sizeof(BatchHdr); break;
+	case MGL_DUMP_BATCH_ACC: src = sa->batch.acc; sz = sizeof(BatchAcc); break;
+	case MGL_DUMP_CHAIN_INDEX: src = b.ch_sb; sz = sizeof(uint32_t) * (size_t)b.ck_elems * b.sb_stride; break;
+	case MGL_DUMP_GIVEUP_SITES: src = sa->lim.why; sz = sizeof(uint32_t); break; /* cleared below */
+	case MGL_DUMP_POOL_TOP: src = b.pool_top; sz = sizeof(uint32_t); break;
+	case MGL_DUMP_INDEX_GEOMETRY: {
+		const uint32_t v[3] = { b.sb_shift, b.nsb, b.sb_stride };
+		return dump_host(v, sizeof v, out, cap_bytes, bytes);
+	}
 	default: return fail(MGL_EINVAL, "mgl_debug_dump: unknown selector");
 	}
 	*bytes = sz;
 	if (sz > cap_bytes) return fail(MGL_ERANGE, "mgl_debug_dump: buffer too small");
 	if (sz) HIPCHK(hipMemcpy(out, src, sz, hipMemcpyDeviceToHost));
-	if (what == 84) HIPCHK(hipMemset(sa->lim.why, 0, sizeof(uint32_t)));
+	if (what == MGL_DUMP_GIVEUP_SITES) HIPCHK(hipMemset(sa->lim.why, 0, sizeof(uint32_t)));
 	return MGL_OK;
 }
 
-/* diagnostic knobs (tools/, tests/): key 0 = stop the neighbour kernel after phase `value`; key 1 = see below */
+/* MGL_KEY_LIMIT: limit `id` of the in-place accepts := v (at most the compiled / allocated one); id 0: all back to their defaults */
+static int set_limit(mgl_sa* sa, uint32_t id, uint64_t v)
+{
+	if (!sa->incremental || !sa->lim.why) return fail(MGL_EINVAL, "mgl_debug_set: no in-place accept on this handle");
+	HIPCHK(hipSetDevice(sa->device));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	if (id == 0) {
+		if (v) return fail(MGL_EINVAL, "mgl_debug_set: limit id 0 takes value 0 (restore the defaults)");
+		for (uint32_t i = 1; i < MGL_LIM_COUNT; i++) sa->lim.v[i] = i == MGL_LIM_SOFT_REACH ? 0u : sa->lim_max.v[i];
+	} else {
+		if (id >= MGL_LIM_COUNT || v > sa->lim_max.v[id]) return fail(MGL_EINVAL, "mgl_debug_set: unknown limit, or a value above the compiled / allocated one");
+		sa->lim.v[id] = (uint32_t)v;
+	}
+	HIPCHK(hipMemset(sa->lim.why, 0, sizeof(uint32_t)));
+	return MGL_OK;
+}
+/* MGL_KEY_PICK_HINTS, the test of k_pick_order: overwrite the hint bytes (0: all 0, 1: all 1, 2: alternating, else: random from `value`) and make the order again */
+static int set_pick_hints(mgl_sa* sa, uint64_t value)
+{
+	if (!sa->d_pick_order) return fail(MGL_EINVAL, "mgl_debug_set: no launch order on this handle");
+	const uint32_t K = sa->cfg.neighbours_per_step, slices = nbr_slices(sa);
+	std::vector<unsigned char> h(K);
+	uint64_t x = value;
+	for (uint32_t j = 0; j < K; j++) {
+		x = x * 6364136223846793005ull + 1442695040888963407ull;
+		h[j] = value == 0 ? 0 : value == 1 ? 1 : value == 2 ? (unsigned char)(j & 1u) : (unsigned char)((x >> 40) % 3u); /* any non-zero byte is a picking neighbour */
+	}
+	HIPCHK(hipSetDevice(sa->device));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream2));
+	HIPCHK(hipMemcpy(sa->d_pick_hint, h.data(), K, hipMemcpyHostToDevice));
+	hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, sa->q.stream, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	return MGL_OK;
+}
+/* diagnostic knobs (tools/, tests/): enum mgl_debug_key */
 extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 {
-	if (sa && key == 5) { /* the next (low word) batch accepts give up behind their commit; high word 0: before a chain is touched, n: behind the n-th context's rewrite */
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	switch (key) {
+	case MGL_KEY_DIAG_STOP: sa->ctx.diag_stop = (uint32_t)value; return MGL_OK;
+	case MGL_KEY_PBUILD_FIX: sa->pb.force_fix = (uint32_t)value; return MGL_OK;
+	case MGL_KEY_LIST_CAP: /* below what was allocated: pushes neighbours into the second pass */
+		if (value < 8 || value > sa->chg_cap || (value & 7u)) return fail(MGL_EINVAL, "mgl_debug_set: list capacity must be a multiple of 8 within the allocated one");
+		sa->big.chg_cap = (uint32_t)value;
+		return MGL_OK;
+	case MGL_KEY_ROLLBACKS: sa->force.rollbacks = (uint32_t)value; return MGL_OK;
+	case MGL_KEY_COUNT_TRAFFIC:
+		if (!sa->d_traffic) return fail(MGL_EINVAL, "mgl_debug_set: no split neighbour evaluation on this handle");
+		sa->count_traffic = value != 0;
+		return MGL_OK;
+	case MGL_KEY_BATCH_FAIL: /* low word: how many batch accepts; high word 0: before a chain is touched, n: behind the n-th context's rewrite */
 		sa->force.batch_late = (uint32_t)(value >> 32);
 		sa->force.batch_fail = (uint32_t)value;
 		if (sa->force.batch_late && !sa->force.batch_fail) sa->force.batch_fail = 1;
 		return MGL_OK;
-	}
-	if (sa && key == 6) { /* limit `id` of the in-place accepts := value (at most the compiled / allocated one); 0: all back to their defaults */
-		const uint32_t id = (uint32_t)(value & 0xFFu);
-		const uint64_t v = value >> 8;
-		if (!sa->incremental || !sa->lim.why) return fail(MGL_EINVAL, "mgl_debug_set: no in-place accept on this handle");
-		HIPCHK(hipSetDevice(sa->device));
-		HIPCHK(hipStreamSynchronize(sa->q.stream));
-		if (id == 0) {
-			if (v) return fail(MGL_EINVAL, "mgl_debug_set: limit id 0 takes value 0 (restore the defaults)");
-			for (uint32_t i = 1; i < MGL_LIM_COUNT; i++) sa->lim.v[i] = i == MGL_LIM_SOFT_REACH ? 0u : sa->lim_max.v[i];
-		} else {
-			if (id >= MGL_LIM_COUNT || v > sa->lim_max.v[id]) return fail(MGL_EINVAL, "mgl_debug_set: unknown limit, or a value above the compiled / allocated one");
-			sa->lim.v[id] = (uint32_t)v;
-		}
-		HIPCHK(hipMemset(sa->lim.why, 0, sizeof(uint32_t)));
-		return MGL_OK;
-	}
-	if (sa && key == 4) { /* count the bytes of chain data the re-simulation kernel reads (mgl_sa_stats.sim_bytes_counted) */
-		if (!sa->d_traffic) return fail(MGL_EINVAL, "mgl_debug_set: no split neighbour evaluation on this handle");
-		sa->count_traffic = value != 0;
-		return MGL_OK;
-	}
-	if (!sa) return fail(MGL_EINVAL, "null handle");
-	if (key == 0) { sa->ctx.diag_stop = (uint32_t)value; return MGL_OK; }
-	if (key == 1) { sa->pb.force_fix = (uint32_t)value; return MGL_OK; } /* parallel builder: redo every chain segment serially */
-	if (key == 2) { /* first-pass list capacity, below what was allocated: pushes neighbours into the second pass */
-		if (value < 8 || value > sa->chg_cap || (value & 7u)) return fail(MGL_EINVAL, "mgl_debug_set: list capacity must be a multiple of 8 within the allocated one");
-		sa->big.chg_cap = (uint32_t)value;
-		return MGL_OK;
-	}
-	if (key == 7) { /* wavefronts that share a second-pass neighbour's re-simulations: the block size of that launch and nothing else */
+	case MGL_KEY_LIMIT: return set_limit(sa, (uint32_t)(value & 0xFFu), value >> 8);
+	case MGL_KEY_BIG_WAVES: /* the block size of the second-pass launch and nothing else */
 		if (value != 1 && value != 2 && value != MGL_BIG_WAVES) return fail(MGL_EINVAL, "mgl_debug_set: 1, 2 or MGL_BIG_WAVES wavefronts");
 		sa->big_waves = (uint32_t)value;
 		return MGL_OK;
+	case MGL_KEY_CROSS_NOMEM: sa->force.xo_nomem = (uint32_t)value; return MGL_OK;
+	case MGL_KEY_PICK_HINTS: return set_pick_hints(sa, value);
+	case MGL_KEY_COSTMAP_NOMEM: sa->force.cm_nomem = (uint32_t)value; return MGL_OK;
+	default: return fail(MGL_EINVAL, "mgl_debug_set: unknown key");
 	}
-	if (key == 8) { sa->force.xo_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` crossovers fail to allocate their buffers (MGL_ENOMEM) */
-	if (key == 10) { sa->force.cm_nomem = (uint32_t)value; return MGL_OK; } /* the next `value` cost maps fail to allocate their buffers (MGL_ENOMEM) */
-	if (key == 9) { /* test of k_pick_order: overwrite the hint bytes (0: all 0, 1: all 1, 2: alternating, else: random from `value`) and make the order again */
-		if (!sa->d_pick_order) return fail(MGL_EINVAL, "mgl_debug_set: no launch order on this handle");
-		const uint32_t K = sa->cfg.neighbours_per_step, slices = nbr_slices(sa);
-		std::vector<unsigned char> h(K);
-		uint64_t x = value;
-		for (uint32_t j = 0; j < K; j++) {
-			x = x * 6364136223846793005ull + 1442695040888963407ull;
-			h[j] = value == 0 ? 0 : value == 1 ? 1 : value == 2 ? (unsigned char)(j & 1u) : (unsigned char)((x >> 40) % 3u); /* any non-zero byte is a picking neighbour */
-		}
-		HIPCHK(hipSetDevice(sa->device));
-		HIPCHK(hipStreamSynchronize(sa->q.stream));
-		HIPCHK(hipStreamSynchronize(sa->q.stream2));
-		HIPCHK(hipMemcpy(sa->d_pick_hint, h.data(), K, hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, sa->q.stream, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipStreamSynchronize(sa->q.stream));
-		return MGL_OK;
-	}
-	if (key == 3) { sa->force.rollbacks = (uint32_t)value; return MGL_OK; } /* the next `value` bulk steps that take moves are taken back as if their parse had failed validation */
-	return fail(MGL_EINVAL, "mgl_debug_set: unknown key");
 }
 
 #include "mgl_exchange.inc"

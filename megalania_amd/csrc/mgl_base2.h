@@ -21,6 +21,7 @@
  */
 #pragma once
 #include "mgl_device.h"
+#include "../../include/megalania_hip.h"
 
 #define MGL_CK2_SHIFT 6u
 #define MGL_POS_INF 0xFFFFFFFFu
@@ -59,63 +60,14 @@ struct Base2 {
 
 /* What the in-place accepts (mgl_kernels3.hip, mgl_kernels5.hip) compare against before they give up and leave the step to a
  * rebuild.  A kernel argument, by value: no load on any path.  The defaults are the compiled capacities (LDS arrays and
- * buffers keep those sizes); mgl_debug_set key 6 lowers a limit so that a test takes the real comparison on an ordinary
- * input (include/megalania_hip.h lists the ids).  Limits 7-10 and 17 are capacities that already travel in Base2 / ApplyBuf /
+ * buffers keep those sizes); mgl_debug_set MGL_KEY_LIMIT lowers a limit so that a test takes the real comparison on an ordinary
+ * input.  The ids (enum mgl_accept_limit) and the give-up sites (enum mgl_giveup_site) are include/megalania_hip.h's.  Limits 7-10 and 17 are capacities that already travel in Base2 / ApplyBuf /
  * BatchBuf: the host lowers the field of the copy it passes to the accept kernels.  `why`: every give-up ORs its site's bit
- * into this word, on the rare path only (mgl_debug_dump selector 84). */
-#define MGL_LIM_APPLY_EVENTS 1u   /* MGL_APPLY_CAP */
-#define MGL_LIM_APPLY_GUARD 2u    /* iterations of k_apply_walk */
-#define MGL_LIM_APPLY_SUB 3u      /* MGL_SUB_CAP */
-#define MGL_LIM_APPLY_SPAN 4u     /* MGL_SPAN_CAP */
-#define MGL_LIM_APPLY_PIECES 5u   /* MGL_PIECE_CAP */
-#define MGL_LIM_APPLY_SHIFT 6u    /* entries a chain's tail shifts by in place (MGL_SUB_CAP) */
-#define MGL_LIM_POOL 7u           /* Base2::pool_cap */
-#define MGL_LIM_JOBS 8u           /* ApplyBuf::job_cap */
-#define MGL_LIM_SPAN_AREA 9u      /* ApplyBuf::span_cap */
-#define MGL_LIM_SCRATCH 10u       /* ApplyBuf::scratch_cap */
-#define MGL_LIM_BATCH_JOURNAL 11u /* MGL_BATCH_JCAP */
-#define MGL_LIM_BATCH_EVENTS 12u  /* MGL_BATCH_EVCAP */
-#define MGL_LIM_BATCH_OPS 13u     /* MGL_BATCH_OPCAP */
-#define MGL_LIM_BATCH_GUARD 14u   /* iterations of k_batch_walk */
-#define MGL_LIM_BATCH_SUB 15u     /* MGL_BATCH_SUB */
-#define MGL_LIM_BATCH_SHIFT 16u   /* entries a stretch shifts by in place (2047: the job word's field) */
-#define MGL_LIM_BATCH_RUNS 17u    /* BatchBuf::runs_cap */
-#define MGL_LIM_SOFT_REACH 18u    /* 0 / 1: k_batch_clusters splits clusters at the members' soft ends (a wrong rule on purpose: the
-                                   * first cluster's walk then provably has not re-joined at the next one's first entry, and
-                                   * k_batch_walk's boundary guard must send the step to the rebuild) */
-#define MGL_LIM_COUNT 19u
+ * into this word, on the rare path only (MGL_DUMP_GIVEUP_SITES). */
 struct AcceptLimits {
 	uint32_t v[MGL_LIM_COUNT];
 	uint32_t* why;
 };
-/* give-up sites (bits of *AcceptLimits::why) */
-#define MGL_GU_APPLY_EVENTS (1u << 0)   /* k_apply_walk: event lists */
-#define MGL_GU_APPLY_GUARD (1u << 1)    /* k_apply_walk: iteration guard */
-#define MGL_GU_APPLY_SUB (1u << 2)      /* k_apply_chains: events of one context */
-#define MGL_GU_APPLY_SPAN (1u << 3)     /* k_apply_chains: rewritten entries of one context */
-#define MGL_GU_APPLY_PIECES (1u << 4)   /* k_apply_chains: pieces / checkpoint segments */
-#define MGL_GU_APPLY_POOL (1u << 5)     /* k_apply_chains: chain pool exhausted */
-#define MGL_GU_APPLY_JOBS (1u << 6)     /* k_apply_chains: job lists */
-#define MGL_GU_APPLY_SPAN_AREA (1u << 7)
-#define MGL_GU_APPLY_SCRATCH (1u << 8)
-#define MGL_GU_APPLY_SHIFT (1u << 9)
-#define MGL_GU_CL_JOURNAL (1u << 10)    /* k_batch_clusters: a cluster's merged journal */
-#define MGL_GU_CL_ORDER (1u << 11)      /* k_batch_clusters: merged journal not strictly ascending */
-#define MGL_GU_WALK_OPS (1u << 12)      /* k_batch_walk */
-#define MGL_GU_WALK_EVENTS (1u << 13)
-#define MGL_GU_WALK_GUARD (1u << 14)
-#define MGL_GU_WALK_INVALID (1u << 15)  /* a packet or rep packet of the merged walk that does not code the input */
-#define MGL_GU_WALK_OVERRUN (1u << 16)  /* the merged walk had not re-joined the base at the next cluster's first entry */
-#define MGL_GU_CH_SUB (1u << 17)        /* k_batch_chains */
-#define MGL_GU_CH_SPAN_AREA (1u << 18)   /* step 3: the place every run gets to begin with */
-#define MGL_GU_CH_SHIFT (1u << 19)
-#define MGL_GU_CH_POOL (1u << 20)
-#define MGL_GU_CH_JOBS (1u << 21)
-#define MGL_GU_CH_SCRATCH (1u << 22)
-#define MGL_GU_CH_RUNS (1u << 23)
-#define MGL_GU_FORCED_EARLY (1u << 24)  /* mgl_debug_set key 5, low word */
-#define MGL_GU_FORCED_LATE (1u << 25)   /* mgl_debug_set key 5, high word */
-#define MGL_GU_CH_SPAN_RERUN (1u << 26)  /* k_batch_chains step 5: the span area, for a run that did not fit its first place (the chain has its pool space by then) */
 
 __device__ __forceinline__ uint32_t ctz64(uint64_t v) { return (uint32_t)__ffsll((long long)v) - 1u; }
 __device__ __forceinline__ uint32_t msb64(uint64_t v) { return 63u - (uint32_t)__clzll((long long)v); }

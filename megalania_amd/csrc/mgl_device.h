@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mgl_model.h"
+#include "mgl_words.h"
 
 #define MGL_WAVE 64
 #define MGL_CKPT_SHIFT 10u          /* one prefix checkpoint per 1024 input bytes */

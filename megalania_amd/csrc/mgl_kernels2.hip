@@ -208,8 +208,8 @@ __global__ void __launch_bounds__(64) k_build(DevCtx c, Base2 b, Control* ctl, i
 }
 /* the tail of an incremental step in one launch: the fallback rebuild (only when k_apply_* gave
  * up) and then the step's bookkeeping (mgl_kernels3.hip) */
-__device__ void step_end_body(Control* ctl, int lazy_best, uint32_t* counts, int adaptive, int form_single);
-__global__ void __launch_bounds__(64) k_build_end(DevCtx c, Base2 b, Control* ctl, int lazy_best, uint32_t* counts, int adaptive, int form_single)
+__device__ void step_end_body(Control* ctl, int lazy_best, StepCounts* counts, int adaptive, int form_single);
+__global__ void __launch_bounds__(64) k_build_end(DevCtx c, Base2 b, Control* ctl, int lazy_best, StepCounts* counts, int adaptive, int form_single)
 {
 	build_body(c, b, ctl, 2);
 	__threadfence();

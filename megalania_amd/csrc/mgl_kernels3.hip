@@ -29,7 +29,7 @@
 #define MGL_APPLY_WIN 2048u
 
 struct ApplyBuf {
-	uint32_t* hdr;      /* [0] n_ins [1] n_rem [2] n_tctx [3] first journal position */
+	ApplyHdr* hdr;
 	uint16_t* ins_key;  /* ctx | bit << 15 */
 	uint32_t* ins_pos;
 	uint16_t* rem_key;
@@ -47,8 +47,6 @@ struct ApplyBuf {
 	uint4* jobs_c;
 	uint32_t job_cap;
 };
-/* hdr: [0] n_ins [1] n_rem [2] n_tctx [3] first journal position [4] jobs B [5] jobs C [6] span entries used
- * [7] scratch entries used */
 #define MGL_JOB_CHUNK 4096u
 #define MGL_SPACE_CHAIN 0u
 #define MGL_SPACE_SCRATCH 1u
@@ -253,12 +251,12 @@ __global__ void __launch_bounds__(64) k_apply_walk(DevCtx c, Base2 b, Control* c
 		nt += (uint32_t)__shfl((int)incl, 63, 64);
 	}
 	if (lane == 0) {
-		ab.hdr[0] = n_ins; ab.hdr[1] = n_rem; ab.hdr[2] = failed ? 0u : nt; ab.hdr[3] = t;
-		ab.hdr[4] = 0; ab.hdr[5] = 0; ab.hdr[6] = 0; ab.hdr[7] = 0;
+		ab.hdr->n_ins = n_ins; ab.hdr->n_rem = n_rem; ab.hdr->n_tctx = failed ? 0u : nt; ab.hdr->first_pos = t;
+		ab.hdr->jobs_b = 0; ab.hdr->jobs_c = 0; ab.hdr->span_used = 0; ab.hdr->scratch_used = 0;
 		if (prof) { /* diagnostic: cycles of [state lookup, walk, listing] and walk iterations of this accept */
 			const unsigned long long tw3 = __builtin_readcyclecounter();
-			ab.hdr[13] = (uint32_t)(tw1 - tw0); ab.hdr[14] = (uint32_t)(tw2 - tw1);
-			ab.hdr[15] = ((uint32_t)(tw3 - tw2) & 0xFFFFFu) | (guard << 20); /* hdr[8..12] belong to k_apply_chains' stages */
+			ab.hdr->walk_cycles0 = (uint32_t)(tw1 - tw0); ab.hdr->walk_cycles1 = (uint32_t)(tw2 - tw1);
+			ab.hdr->walk_cycles2 = ((uint32_t)(tw3 - tw2) & MGL_APPLY_CYCLES_MASK) | (guard << MGL_APPLY_GUARD_SHIFT);
 		}
 		ctl->packets = (uint64_t)((int64_t)ctl->packets + dpackets);
 		ctl->rebuild_cost = ctl->cur_cost; /* exact cost of the new base */
@@ -292,13 +290,13 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 	__shared__ uint32_t s_ni, s_nr, s_npiece, s_nseg, s_k0, s_newtail, s_oldlen, s_fail, s_newlen, s_newoff, s_newcap;
 	if (!ctl->accepted_flag || ctl->apply_failed) return;
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-	const uint32_t n_ins = ab.hdr[0], n_rem = ab.hdr[1], nt = ab.hdr[2];
+	const uint32_t n_ins = ab.hdr->n_ins, n_rem = ab.hdr->n_rem, nt = ab.hdr->n_tctx;
 
-	const bool prof = c.diag_stop == 50u; /* diagnostic: hdr[8..13] = slowest workgroup's cycles per stage */
+	const bool prof = c.diag_stop == 50u; /* diagnostic: ApplyHdr::stage_cycles = slowest workgroup's cycles per stage */
 	for (uint32_t ti = blockIdx.x; ti < nt; ti += gridDim.x) {
 		const uint32_t cx = ab.tctx[ti];
 		unsigned long long t0 = prof ? __builtin_readcyclecounter() : 0ull, t1;
-#define APPLY_STAGE(i_) if (prof && tid == 0) { t1 = __builtin_readcyclecounter(); atomicMax(&ab.hdr[8 + (i_)], (uint32_t)(t1 - t0)); t0 = t1; }
+#define APPLY_STAGE(i_) if (prof && tid == 0) { t1 = __builtin_readcyclecounter(); atomicMax(&ab.hdr->stage_cycles[i_], (uint32_t)(t1 - t0)); t0 = t1; }
 		__syncthreads();
 		if (tid == 0) { s_ni = 0; s_nr = 0; s_fail = 0; }
 		__syncthreads();
@@ -539,10 +537,10 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 		const uint32_t n_small = np - 1u; /* every piece but the tail (always the last one) */
 		const uint32_t scratch_need = small_count + n_sliver * ad;
 		if (tid == 0) {
-			s_job_b = atomicAdd(&ab.hdr[4], n_save + n_prefix + n_sliver);
-			s_job_c = atomicAdd(&ab.hdr[5], n_small + n_tail + (new_sentinel ? 1u : 0u));
-			s_span_base = atomicAdd(&ab.hdr[6], ns + 1u);
-			s_scr_base = atomicAdd(&ab.hdr[7], scratch_need);
+			s_job_b = atomicAdd(&ab.hdr->jobs_b, n_save + n_prefix + n_sliver);
+			s_job_c = atomicAdd(&ab.hdr->jobs_c, n_small + n_tail + (new_sentinel ? 1u : 0u));
+			s_span_base = atomicAdd(&ab.hdr->span_used, ns + 1u);
+			s_scr_base = atomicAdd(&ab.hdr->scratch_used, scratch_need);
 			if (s_job_b + n_save + n_prefix + n_sliver > ab.job_cap || s_job_c + n_small + n_tail + 1u > ab.job_cap) s_fail |= MGL_GU_APPLY_JOBS;
 			if (s_span_base + ns + 1u > ab.span_cap) s_fail |= MGL_GU_APPLY_SPAN_AREA;
 			if (s_scr_base + scratch_need > ab.scratch_cap) s_fail |= MGL_GU_APPLY_SCRATCH;
@@ -610,7 +608,7 @@ __global__ void __launch_bounds__(1024) k_apply_chains(DevCtx c, Base2 b, Contro
 }
 
 /* decide-only variant of the step's tail: flags for k_build's conditional run are reset there */
-__device__ void step_end_body(Control* ctl, int lazy_best, uint32_t* counts, int adaptive, int form_single)
+__device__ void step_end_body(Control* ctl, int lazy_best, StepCounts* counts, int adaptive, int form_single)
 {
 	if (threadIdx.x == 0 && blockIdx.x == 0) {
 		if (adaptive) {
@@ -622,7 +620,7 @@ __device__ void step_end_body(Control* ctl, int lazy_best, uint32_t* counts, int
 			const unsigned long long now = (unsigned long long)wall_clock64();
 			const unsigned long long dt64 = now - ctl->t_last;
 			const uint32_t cur = form_single ? 1u : 0u; /* the form the host launched this step */
-			const bool dirty = counts[0] != 0 || counts[3] != 0;
+			const bool dirty = counts[0].second_pass != 0 || counts[0].repair_picks != 0;
 			ctl->p_dirty = (uint32_t)((int32_t)ctl->p_dirty + (((dirty ? 65536 : 0) - (int32_t)ctl->p_dirty) >> 5));
 			if (ctl->t_last != 0 && ctl->mode_steps >= 1u && dt64 < 0x7FFFFFFFull) {
 				uint32_t* e = cur ? &ctl->ema_single : (dirty ? &ctl->ema_dirty : &ctl->ema_clean);
@@ -635,7 +633,7 @@ __device__ void step_end_body(Control* ctl, int lazy_best, uint32_t* counts, int
 			uint32_t want = cur;
 			if (ctl->probing) {
 				if (--ctl->probing == 0) want = 1u - cur; /* trial over: back, then decide below on fresh numbers */
-			} else if (cur == 0u && counts[0] > 128u) {
+			} else if (cur == 0u && counts[0].second_pass > 128u) {
 				want = 1u; /* a burst of repairs: hundreds of neighbours would go through the second pass */
 				ctl->p_dirty = ctl->p_dirty > 49152u ? ctl->p_dirty : 49152u;
 			} else if ((cur == 0u ? ctl->ema_single == 0 : (ctl->ema_clean == 0 && ctl->ema_dirty == 0)) ? ctl->mode_steps >= 8u : ctl->mode_steps >= 2048u) { /* a trial lasts until the host's next look, a block of steps */
@@ -658,13 +656,13 @@ __device__ void step_end_body(Control* ctl, int lazy_best, uint32_t* counts, int
 			else if (ctl->accepted_flag) ctl->best_is_current = 0;
 		}
 		ctl->accepted_flag = 0; ctl->apply_failed = 0;
-		/* the per-step counters ([0] second-pass list, [1] last-resort list, [2] spill slots, [3] repair picks, [4] unused, always zero,
-		 * [5] event pairs the window walks cancelled, [6..7] unused):
-		 * kept for diagnostics in [8..15], cleared for the next step (saves a memset launch) */
-		for (int i = 0; i < 8; i++) { counts[8 + i] = counts[i]; counts[i] = 0; }
+		/* the per-step counters: kept for diagnostics in counts[1], cleared for the next step (saves a memset launch).  Word by
+		 * word: a struct assignment allocates other registers, and this kernel's code is held equal to what it was */
+		uint32_t* live = &counts[0].second_pass; uint32_t* last = &counts[1].second_pass;
+		for (int i = 0; i < (int)(sizeof(StepCounts) / sizeof(uint32_t)); i++) { last[i] = live[i]; live[i] = 0; }
 	}
 }
-__global__ void k_step_end(Control* ctl, int lazy_best, uint32_t* counts, int adaptive, int form_single)
+__global__ void k_step_end(Control* ctl, int lazy_best, StepCounts* counts, int adaptive, int form_single)
 {
 	step_end_body(ctl, lazy_best, counts, adaptive, form_single);
 }
@@ -742,10 +740,10 @@ __global__ void __launch_bounds__(256) k_snapshot(SnapPlan p, Control* ctl, Snap
 #define MGL_SPACE_SHIFT2 4u /* job kind (batch accept, mgl_kernels5.hip): in-place shift of one chunk of a stretch, slivers saved at both ends */
 /* batch_hdr: nullptr for a single accept (runs when this step accepted a move), else the batch accept's header (runs while
  * its status is 1) */
-__global__ void __launch_bounds__(256) k_apply_jobs(Base2 b, const Control* ctl, ApplyBuf ab, int pass, const uint32_t* batch_hdr)
+__global__ void __launch_bounds__(256) k_apply_jobs(Base2 b, const Control* ctl, ApplyBuf ab, int pass, const BatchHdr* batch_hdr)
 {
-	if (batch_hdr ? (batch_hdr[0] != 1u || batch_hdr[4] != 0u || ctl->apply_failed) : (!ctl->accepted_flag || ctl->apply_failed)) return;
-	const uint32_t njobs = ab.hdr[pass == 0 ? 4 : 5];
+	if (batch_hdr ? (batch_hdr->status != MGL_BATCH_BEGAN || batch_hdr->failed != 0u || ctl->apply_failed) : (!ctl->accepted_flag || ctl->apply_failed)) return;
+	const uint32_t njobs = pass == 0 ? ab.hdr->jobs_b : ab.hdr->jobs_c;
 	const uint4* jobs = pass == 0 ? ab.jobs_b : ab.jobs_c;
 	for (uint32_t j = blockIdx.x; j < njobs; j += gridDim.x) {
 		const uint4 job = jobs[j];

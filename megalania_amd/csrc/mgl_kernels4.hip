@@ -136,7 +136,7 @@ struct BulkBuf {
 	uint32_t* taken;    /* K: neighbour indices taken this step */
 	uint8_t* cstate;    /* 2 x K: selection state per candidate (0 undecided, 1 taken, 2 rejected), one array per round parity */
 	uint32_t* cflags;   /* K: what k_bulk_pairs found for each candidate in the current round (zero between rounds) */
-	unsigned long long* hdr; /* [0] acceptable [1] taken [2] valid [3] walked [4] improving [5] dropped [6] smallest taken key */
+	BulkHdr* hdr;
 };
 
 __global__ void __launch_bounds__(256) k_bulk_prep(DevCtx c, Control* ctl, NbrOut out, DecideArgs a, BulkBuf bb)
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) k_bulk_prep(DevCtx c, Control* ctl, NbrOu
 	const unsigned long long m = __ballot(acc);
 	if (m) {
 		unsigned long long base = 0;
-		if (lane == (uint32_t)__ffsll((long long)m) - 1u) base = atomicAdd(&bb.hdr[0], (unsigned long long)__popcll(m));
+		if (lane == (uint32_t)__ffsll((long long)m) - 1u) base = atomicAdd(&bb.hdr->acceptable, (unsigned long long)__popcll(m));
 		base = (unsigned long long)shfl64(base, __ffsll((long long)m) - 1);
 		if (acc) {
 			const uint32_t at = (uint32_t)base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) k_bulk_prep(DevCtx c, Control* ctl, NbrOu
 	}
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		atomicAdd(&bb.hdr[2], s_cnt[0]); atomicAdd(&bb.hdr[3], s_cnt[1]); atomicAdd(&bb.hdr[4], s_cnt[2]); atomicAdd(&bb.hdr[5], s_cnt[3]);
+		atomicAdd(&bb.hdr->valid, s_cnt[0]); atomicAdd(&bb.hdr->walked, s_cnt[1]); atomicAdd(&bb.hdr->improving, s_cnt[2]); atomicAdd(&bb.hdr->dropped, s_cnt[3]);
 	}
 }
 
@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(256) k_bulk_pairs(BulkBuf bb, uint32_t K, uint
 	__shared__ uint64_t s_key[256];
 	__shared__ uint4 s_win[256];
 	__shared__ uint8_t s_st[256];
-	const uint32_t n = (uint32_t)bb.hdr[0];
+	const uint32_t n = (uint32_t)bb.hdr->acceptable;
 	if (blockIdx.x * 256u >= n || blockIdx.y * 256u >= n) return;
 	const uint8_t* st_in = bb.cstate + (size_t)(round & 1u) * K;
 	const uint32_t a = blockIdx.x * 256u + threadIdx.x;
@@ -228,7 +228,7 @@ __global__ void __launch_bounds__(256) k_bulk_pairs(BulkBuf bb, uint32_t K, uint
 /* second half: the verdicts of the round */
 __global__ void __launch_bounds__(256) k_bulk_round(Control* ctl, NbrOut out, BulkBuf bb, mgl_pk* slab, uint32_t K, uint32_t round)
 {
-	const uint32_t n = (uint32_t)bb.hdr[0];
+	const uint32_t n = (uint32_t)bb.hdr->acceptable;
 	const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
 	if (a >= n) return;
 	const uint8_t* st_in = bb.cstate + (size_t)(round & 1u) * K;
@@ -241,9 +241,9 @@ __global__ void __launch_bounds__(256) k_bulk_round(Control* ctl, NbrOut out, Bu
 	if (my != 0 || now != 1) return;
 	const uint64_t key = bb.ckey[a];
 	const uint32_t j = (uint32_t)(key & 0xFFFFFu);
-	const unsigned long long at = atomicAdd(&bb.hdr[1], 1ull);
+	const unsigned long long at = atomicAdd(&bb.hdr->taken, 1ull);
 	bb.taken[at] = j;
-	atomicMin(&bb.hdr[6], (unsigned long long)key);
+	atomicMin(&bb.hdr->min_key, (unsigned long long)key);
 	(void)ctl; (void)out; (void)slab;
 }
 /* The journals of the taken neighbours into the slab, for the rebuild (a batch accept writes them itself, mgl_kernels5.hip).
@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(256) k_bulk_round(Control* ctl, NbrOut out, Bu
  * counted (Control::bulk_overlaps, mgl_sa_stats.bulk_double_writes; the oracle counts the same thing). */
 __global__ void __launch_bounds__(256) k_bulk_write(Control* ctl, NbrOut out, BulkBuf bb, mgl_pk* slab)
 {
-	const uint32_t taken = (uint32_t)bb.hdr[1];
+	const uint32_t taken = (uint32_t)bb.hdr->taken;
 	for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < taken; t += gridDim.x * blockDim.x) {
 		const uint32_t j = bb.taken[t], nd = out.ndiffs[j];
 		for (uint32_t e = 0; e < nd; e++) {
@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(1024) k_bulk_select_small(Control* ctl, NbrOut
 	__shared__ uint64_t s_key[1024];
 	__shared__ uint4 s_win[1024];
 	__shared__ uint8_t s_st[1024];
-	const uint32_t n = (uint32_t)bb.hdr[0];
+	const uint32_t n = (uint32_t)bb.hdr->acceptable;
 	const uint32_t tid = threadIdx.x;
 	(void)ctl; (void)out;
 	/* states live in cstate[0 .. K) (previous round) and cstate[K .. 2K) (next round), as in the tiled form */
@@ -309,9 +309,9 @@ __global__ void __launch_bounds__(1024) k_bulk_select_small(Control* ctl, NbrOut
 				const uint8_t now = my ? my : ((f & 1u) ? (uint8_t)2 : ((f & 2u) ? (uint8_t)0 : (uint8_t)1));
 				st_out[a] = now;
 				if (my == 0 && now == 1) {
-					const unsigned long long at = atomicAdd(&bb.hdr[1], 1ull);
+					const unsigned long long at = atomicAdd(&bb.hdr->taken, 1ull);
 					bb.taken[at] = (uint32_t)(key & 0xFFFFFu);
-					atomicMin(&bb.hdr[6], (unsigned long long)key);
+					atomicMin(&bb.hdr->min_key, (unsigned long long)key);
 				}
 			}
 		}
@@ -325,12 +325,12 @@ __global__ void k_bulk_end(Control* ctl, BulkBuf bb, DecideArgs a)
 {
 	if (threadIdx.x || blockIdx.x) return;
 	const uint64_t base_cost = ctl->cur_cost ? ctl->cur_cost : ctl->rebuild_cost;
-	const uint32_t taken = (uint32_t)bb.hdr[1];
-	ctl->evals += bb.hdr[2];
-	ctl->failed += a.K - bb.hdr[2];
-	ctl->packets_eval += bb.hdr[3];
-	ctl->imp_cands += bb.hdr[4];
-	ctl->dropped += bb.hdr[5];
+	const uint32_t taken = (uint32_t)bb.hdr->taken;
+	ctl->evals += bb.hdr->valid;
+	ctl->failed += a.K - bb.hdr->valid;
+	ctl->packets_eval += bb.hdr->walked;
+	ctl->imp_cands += bb.hdr->improving;
+	ctl->dropped += bb.hdr->dropped;
 	ctl->gstep += 1;
 	ctl->iter += a.K;
 	ctl->accepted += taken;
@@ -351,8 +351,8 @@ __global__ void k_bulk_end(Control* ctl, BulkBuf bb, DecideArgs a)
 /* The kernels that close a bulk step take a gate: the batch accept's status word (mgl_kernels5.hip).  They are queued
  * behind the batch accept before the host has read that word, so that they run while it does: they go ahead when the
  * moves are in (3) or the step took none (0); a step that goes to the rebuild instead queues them again, ungated. */
-__device__ __forceinline__ bool gate_open(const uint32_t* gate) { return gate == nullptr || gate[0] == 3u || gate[0] == 0u; }
-__global__ void k_bulk_finish(Control* ctl, BulkBuf bb, int lazy_best, uint32_t* snap_best_valid, const uint32_t* gate)
+__device__ __forceinline__ bool gate_open(const BatchHdr* gate) { return gate == nullptr || gate->status == MGL_BATCH_DONE || gate->status == MGL_BATCH_NONE; }
+__global__ void k_bulk_finish(Control* ctl, BulkBuf bb, int lazy_best, uint32_t* snap_best_valid, const BatchHdr* gate)
 {
 	if (threadIdx.x || blockIdx.x || !gate_open(gate)) return;
 	const uint32_t taken = ctl->taken;
@@ -373,20 +373,20 @@ __global__ void k_bulk_finish(Control* ctl, BulkBuf bb, int lazy_best, uint32_t*
 		}
 	}
 	ctl->t_last = 0; /* a bulk step is not a sample for the split / one-kernel choice */
-	bb.hdr[0] = 0; bb.hdr[1] = taken; /* k_bulk_keep_undo still needs the count; cleared there */
-	bb.hdr[2] = bb.hdr[3] = bb.hdr[4] = bb.hdr[5] = 0; bb.hdr[6] = ~0ull;
+	bb.hdr->acceptable = 0; bb.hdr->taken = taken; /* k_bulk_keep_undo still needs the count; cleared there */
+	bb.hdr->valid = bb.hdr->walked = bb.hdr->improving = bb.hdr->dropped = 0; bb.hdr->min_key = ~0ull;
 }
 /* best slab := the slab before this step = the new slab ... */
-__global__ void __launch_bounds__(256) k_bulk_keep_copy(const Control* ctl, const mgl_pk* slab, mgl_pk* best, uint32_t n, const uint32_t* gate)
+__global__ void __launch_bounds__(256) k_bulk_keep_copy(const Control* ctl, const mgl_pk* slab, mgl_pk* best, uint32_t n, const BatchHdr* gate)
 {
 	if (!gate_open(gate) || !ctl->bulk_need_undo) return;
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) best[i] = slab[i];
 }
 /* ... with the taken journals undone */
-__global__ void __launch_bounds__(256) k_bulk_keep_undo(const Control* ctl, NbrOut out, BulkBuf bb, mgl_pk* best, const uint32_t* gate)
+__global__ void __launch_bounds__(256) k_bulk_keep_undo(const Control* ctl, NbrOut out, BulkBuf bb, mgl_pk* best, const BatchHdr* gate)
 {
 	if (!gate_open(gate)) return;
-	const uint32_t taken = (uint32_t)bb.hdr[1];
+	const uint32_t taken = (uint32_t)bb.hdr->taken;
 	if (ctl->bulk_need_undo) {
 		for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < taken; t += gridDim.x * blockDim.x) {
 			const uint32_t j = bb.taken[t], nd = out.ndiffs[j];
@@ -398,23 +398,23 @@ __global__ void __launch_bounds__(256) k_bulk_keep_undo(const Control* ctl, NbrO
  * taken journal is taken back */
 __global__ void __launch_bounds__(256) k_bulk_rollback(NbrOut out, BulkBuf bb, mgl_pk* slab)
 {
-	const uint32_t taken = (uint32_t)bb.hdr[1];
+	const uint32_t taken = (uint32_t)bb.hdr->taken;
 	for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < taken; t += gridDim.x * blockDim.x) {
 		const uint32_t j = bb.taken[t], nd = out.ndiffs[j];
 		for (uint32_t e = 0; e < nd; e++) slab[out.dpos[(size_t)j * MGL_MAX_DIFFS + e]] = out.dold[(size_t)j * MGL_MAX_DIFFS + e];
 	}
 }
-__global__ void k_bulk_reset(BulkBuf bb, const uint32_t* gate)
+__global__ void k_bulk_reset(BulkBuf bb, const BatchHdr* gate)
 {
-	if (threadIdx.x == 0 && blockIdx.x == 0 && gate_open(gate)) bb.hdr[1] = 0;
+	if (threadIdx.x == 0 && blockIdx.x == 0 && gate_open(gate)) bb.hdr->taken = 0;
 }
 /* the slab copy of a new best, for handles without snapshots (k_copy_best behind the gate) */
-__global__ void __launch_bounds__(256) k_bulk_copy_best(const Control* ctl, const mgl_pk* slab, mgl_pk* best, uint32_t n, const uint32_t* gate)
+__global__ void __launch_bounds__(256) k_bulk_copy_best(const Control* ctl, const mgl_pk* slab, mgl_pk* best, uint32_t n, const BatchHdr* gate)
 {
 	if (!gate_open(gate) || !ctl->copy_best_flag) return;
 	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) best[i] = slab[i];
 }
-__global__ void k_bulk_step_end(Control* ctl, uint32_t* counts, int form_single, const uint32_t* gate)
+__global__ void k_bulk_step_end(Control* ctl, StepCounts* counts, int form_single, const BatchHdr* gate)
 {
 	if (gate_open(gate)) step_end_body(ctl, 0, counts, 0, form_single);
 }

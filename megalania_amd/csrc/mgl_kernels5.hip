@@ -54,17 +54,9 @@
 #define MGL_BATCH_GAP 32u      /* events of a context further apart than this start a group of their own */
 #define MGL_BATCH_ALLOC (MGL_BATCH_MAX * MGL_BATCH_EVCAP) /* entries of the combined event lists (ApplyBuf lists are allocated this long) */
 
-/* BatchBuf::hdr[0], the batch accept's status: every kernel of it looks here first, the host reads it back once per bulk step */
-#define MGL_BATCH_NONE 0u    /* the step took no move: nothing to do */
-#define MGL_BATCH_BEGAN 1u   /* a batch accept is under way; read back by the host: it gave up behind its commit, the rebuild finishes the step */
-#define MGL_BATCH_REBUILD 2u /* left to the rebuild: more moves than a batch accept handles, or it gave up before anything was touched */
-#define MGL_BATCH_DONE 3u    /* the moves are in */
 struct BatchBuf {
-	uint32_t* hdr;      /* [0] status (MGL_BATCH_NONE / BEGAN / REBUILD / DONE); [1] clusters; [2] inserted events,
-	                     * [3] removed events (combined lists); [4] failure seen by a kernel (1 a walk gave up, 2 a walk met an invalid packet,
-	                     * 4 the clusters gave up); [5] journal entries; [6] touched contexts; [9] / [13] / [12] test hook (mgl_debug_set key 5):
-	                     * give up at the top of k_batch_chains / behind the [13]-th context's rewrite / contexts that got that far */
-	uint32_t* cl;       /* per cluster, 8 words: first journal entry, journal entries, staged inserted, staged removed, ops, -, -, - */
+	BatchHdr* hdr;      /* status, totals and the test hook's words (mgl_words.h) */
+	uint32_t* cl;       /* per cluster MGL_CL_WORDS words, MGL_CL_* */
 	uint32_t* jpos;     /* merged journals, cluster after cluster */
 	mgl_pk* jnew;
 	mgl_pk* jold;
@@ -76,14 +68,14 @@ struct BatchBuf {
 	uint32_t* cnt_i; uint32_t* cnt_r;   /* per context: events (counted by k_batch_commit) */
 	uint32_t* off_i; uint32_t* off_r;   /* exclusive scans */
 	uint32_t* cur_i; uint32_t* cur_r;   /* fill cursors */
-	uint32_t* touched;                  /* the contexts that have events (hdr[10] of them), listed by k_batch_scan */
+	uint32_t* touched;                  /* the contexts that have events (BatchHdr::touched of them), listed by k_batch_scan */
 	uint32_t* bk_ipos; uint16_t* bk_ibit; uint8_t* bk_icl; /* MGL_BATCH_ALLOC each */
 	uint32_t* bk_rpos; uint8_t* bk_rcl;
 	uint32_t nctx;      /* contexts (DevCtx::L.total) */
 	uint4* runs;        /* the runs that count, two words of four each: {context, lo, hi, first span entry} {entries, end probability, -, -}:
-	                     * k_batch_ckpt patches the dense checkpoints along them (hdr[8] = how many) */
+	                     * k_batch_ckpt patches the dense checkpoints along them (BatchHdr::runs of them) */
 	uint32_t runs_cap;
-	long long* acc;     /* [0] cost change summed by k_batch_chains [1] direct-bit cost change [2] packets on the walk, change */
+	BatchAcc* acc;
 };
 #define MGL_OP_ON 1u     /* position joins the walk */
 #define MGL_OP_OFF 2u    /* `count` positions from pos on leave the walk (they are not special any more either) */
@@ -97,14 +89,14 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 	__shared__ uint32_t s_joff[MGL_BATCH_MAX + 1], s_cl[MGL_BATCH_MAX * 2];
 	__shared__ uint32_t s_ncl, s_bad;
 	const uint32_t tid = threadIdx.x;
-	const uint32_t m = (uint32_t)bb.hdr[1];
+	const uint32_t m = (uint32_t)bb.hdr->taken;
 	if (tid == 0) {
 		s_bad = 0; s_ncl = 0;
-		bt.hdr[0] = m == 0 ? MGL_BATCH_NONE : (m > MGL_BATCH_MAX ? MGL_BATCH_REBUILD : MGL_BATCH_BEGAN);
-		bt.hdr[1] = 0; bt.hdr[2] = 0; bt.hdr[3] = 0; bt.hdr[4] = 0; bt.hdr[5] = 0; bt.hdr[6] = 0;
-		bt.hdr[8] = 0; bt.hdr[12] = 0;
-		bt.hdr[7] = (uint32_t)bb.hdr[0]; /* acceptable neighbours of this step: the host sizes the next step's selection by it */
-		bt.acc[0] = 0; bt.acc[1] = 0; bt.acc[2] = 0;
+		bt.hdr->status = m == 0 ? MGL_BATCH_NONE : (m > MGL_BATCH_MAX ? MGL_BATCH_REBUILD : MGL_BATCH_BEGAN);
+		bt.hdr->clusters = 0; bt.hdr->n_ins = 0; bt.hdr->n_rem = 0; bt.hdr->failed = 0; bt.hdr->journal = 0; bt.hdr->unused6 = 0;
+		bt.hdr->runs = 0; bt.hdr->force_reached = 0;
+		bt.hdr->acceptable = (uint32_t)bb.hdr->acceptable; /* acceptable neighbours of this step: the host sizes the next step's selection by it */
+		bt.acc->cost = 0; bt.acc->direct = 0; bt.acc->packets = 0;
 	}
 	if (m == 0 || m > MGL_BATCH_MAX) return;
 	for (uint32_t i = tid; i < bt.nctx; i += blockDim.x) { bt.cnt_i[i] = 0; bt.cnt_r[i] = 0; bt.cur_i[i] = 0; bt.cur_r[i] = 0; }
@@ -140,7 +132,7 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 		for (uint32_t q = 0; q < ncl; q++) if (s_cl[q * 2u + 1u] > lim.v[MGL_LIM_BATCH_JOURNAL]) s_bad = MGL_GU_CL_JOURNAL;
 	}
 	__syncthreads();
-	if (tid < s_ncl) { bt.cl[tid * 8u] = s_cl[tid * 2u]; bt.cl[tid * 8u + 1u] = s_cl[tid * 2u + 1u]; }
+	if (tid < s_ncl) { bt.cl[tid * MGL_CL_WORDS + MGL_CL_FIRST] = s_cl[tid * 2u]; bt.cl[tid * MGL_CL_WORDS + MGL_CL_ENTRIES] = s_cl[tid * 2u + 1u]; }
 	/* the merged journals: member after member (a member's entries all lie before the next member's target); one thread per
 	 * (member, entry) */
 	for (uint32_t x = tid; x < m * MGL_MAX_DIFFS; x += blockDim.x) {
@@ -173,8 +165,8 @@ __global__ void __launch_bounds__(1024) k_batch_clusters(DevCtx c, const Control
 	}
 	__syncthreads();
 	if (tid == 0) {
-		bt.hdr[1] = s_ncl; bt.hdr[5] = tot;
-		if (s_bad) { bt.hdr[0] = MGL_BATCH_REBUILD; bt.hdr[4] = 4u; atomicOr(lim.why, s_bad); } /* nothing has been touched: the rebuild takes the step */
+		bt.hdr->clusters = s_ncl; bt.hdr->journal = tot;
+		if (s_bad) { bt.hdr->status = MGL_BATCH_REBUILD; bt.hdr->failed = MGL_BATCH_FAIL_CLUSTERS; atomicOr(lim.why, s_bad); } /* nothing has been touched: the rebuild takes the step */
 	}
 }
 
@@ -204,16 +196,16 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 {
 	__shared__ uint32_t s_jpos[MGL_BATCH_JCAP];
 	__shared__ mgl_pk s_jnew[MGL_BATCH_JCAP];
-	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
+	if (bt.hdr->status != MGL_BATCH_BEGAN) return;
 	const uint32_t cl = blockIdx.x, lane = threadIdx.x;
-	if (cl >= bt.hdr[1]) return;
-	const uint32_t j0 = bt.cl[cl * 8u], nd = bt.cl[cl * 8u + 1u];
+	if (cl >= bt.hdr->clusters) return;
+	const uint32_t j0 = bt.cl[cl * MGL_CL_WORDS + MGL_CL_FIRST], nd = bt.cl[cl * MGL_CL_WORDS + MGL_CL_ENTRIES];
 	for (uint32_t i = lane; i < nd; i += 64) { s_jpos[i] = bt.jpos[j0 + i]; s_jnew[i] = bt.jnew[j0 + i]; }
 	wave_sync();
 	const uint32_t t = s_jpos[0], last_j = s_jpos[nd - 1];
 	/* the next cluster's walk starts at its first journal entry, from the OLD base's state there: this walk has to have re-joined
 	 * the base by then, and may not touch a packet of either walk at or behind it */
-	const uint32_t next_first = cl + 1u < bt.hdr[1] ? bt.jpos[j0 + nd] : MGL_POS_INF;
+	const uint32_t next_first = cl + 1u < bt.hdr->clusters ? bt.jpos[j0 + nd] : MGL_POS_INF;
 	const uint32_t evcap = lim.v[MGL_LIM_BATCH_EVENTS], opcap = lim.v[MGL_LIM_BATCH_OPS];
 	uint16_t* ikey = bt.st_ikey + (size_t)cl * MGL_BATCH_EVCAP; uint32_t* ipos = bt.st_ipos + (size_t)cl * MGL_BATCH_EVCAP;
 	uint16_t* rkey = bt.st_rkey + (size_t)cl * MGL_BATCH_EVCAP; uint32_t* rpos = bt.st_rpos + (size_t)cl * MGL_BATCH_EVCAP;
@@ -349,25 +341,25 @@ __global__ void __launch_bounds__(64) k_batch_walk(DevCtx c, Base2 b, BatchBuf b
 	}
 	wave_sync();
 	if (lane == 0) {
-		bt.cl[cl * 8u + 2u] = n_ins; bt.cl[cl * 8u + 3u] = n_rem; bt.cl[cl * 8u + 4u] = nops;
-		if (failed || invalid) { atomicOr(&bt.hdr[4], invalid ? 2u : 1u); atomicOr(lim.why, failed | (invalid ? MGL_GU_WALK_INVALID : 0u)); }
-		atomicAdd((unsigned long long*)&bt.acc[1], (unsigned long long)ddirect);
-		atomicAdd((unsigned long long*)&bt.acc[2], (unsigned long long)(long long)dpackets);
+		bt.cl[cl * MGL_CL_WORDS + MGL_CL_N_INS] = n_ins; bt.cl[cl * MGL_CL_WORDS + MGL_CL_N_REM] = n_rem; bt.cl[cl * MGL_CL_WORDS + MGL_CL_OPS] = nops;
+		if (failed || invalid) { atomicOr(&bt.hdr->failed, invalid ? MGL_BATCH_FAIL_INVALID : MGL_BATCH_FAIL_WALK); atomicOr(lim.why, failed | (invalid ? MGL_GU_WALK_INVALID : 0u)); }
+		atomicAdd((unsigned long long*)&bt.acc->direct, (unsigned long long)ddirect);
+		atomicAdd((unsigned long long*)&bt.acc->packets, (unsigned long long)(long long)dpackets);
 	}
 }
 
 /* ------------------------------------------------------------------ commit: every walk has finished, nothing reads the old base any more */
 __global__ void __launch_bounds__(256) k_batch_commit(DevCtx c, Base2 b, Control* ctl, BatchBuf bt, ApplyBuf ab)
 {
-	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
-	if (bt.hdr[4]) { if (blockIdx.x == 0 && threadIdx.x == 0) bt.hdr[0] = MGL_BATCH_REBUILD; return; } /* a walk gave up: nothing has been touched, the rebuild takes the step */
-	const uint32_t cl = blockIdx.x, tid = threadIdx.x, ncl = bt.hdr[1];
+	if (bt.hdr->status != MGL_BATCH_BEGAN) return;
+	if (bt.hdr->failed) { if (blockIdx.x == 0 && threadIdx.x == 0) bt.hdr->status = MGL_BATCH_REBUILD; return; } /* a walk gave up: nothing has been touched, the rebuild takes the step */
+	const uint32_t cl = blockIdx.x, tid = threadIdx.x, ncl = bt.hdr->clusters;
 	if (cl >= ncl) return;
 	/* this cluster's place in the combined lists: clusters are in position order */
 	uint32_t ioff = 0, roff = 0;
-	for (uint32_t q = 0; q < cl; q++) { ioff += bt.cl[q * 8u + 2u]; roff += bt.cl[q * 8u + 3u]; }
-	const uint32_t n_ins = bt.cl[cl * 8u + 2u], n_rem = bt.cl[cl * 8u + 3u], nops = bt.cl[cl * 8u + 4u];
-	if (cl == ncl - 1u && tid == 0) { bt.hdr[2] = ioff + n_ins; bt.hdr[3] = roff + n_rem; }
+	for (uint32_t q = 0; q < cl; q++) { ioff += bt.cl[q * MGL_CL_WORDS + MGL_CL_N_INS]; roff += bt.cl[q * MGL_CL_WORDS + MGL_CL_N_REM]; }
+	const uint32_t n_ins = bt.cl[cl * MGL_CL_WORDS + MGL_CL_N_INS], n_rem = bt.cl[cl * MGL_CL_WORDS + MGL_CL_N_REM], nops = bt.cl[cl * MGL_CL_WORDS + MGL_CL_OPS];
+	if (cl == ncl - 1u && tid == 0) { bt.hdr->n_ins = ioff + n_ins; bt.hdr->n_rem = roff + n_rem; }
 	const size_t sb = (size_t)cl * MGL_BATCH_EVCAP;
 	for (uint32_t e = tid; e < n_ins; e += blockDim.x) {
 		const uint16_t key = bt.st_ikey[sb + e];
@@ -402,7 +394,7 @@ __global__ void __launch_bounds__(256) k_batch_commit(DevCtx c, Base2 b, Control
 		}
 	}
 	/* the journal goes into the slab (main.c keeps the mutated slab on accept) */
-	const uint32_t j0 = bt.cl[cl * 8u], nd = bt.cl[cl * 8u + 1u];
+	const uint32_t j0 = bt.cl[cl * MGL_CL_WORDS + MGL_CL_FIRST], nd = bt.cl[cl * MGL_CL_WORDS + MGL_CL_ENTRIES];
 	for (uint32_t e = tid; e < nd; e += blockDim.x) b.slab[bt.jpos[j0 + e]] = bt.jnew[j0 + e];
 }
 
@@ -410,9 +402,9 @@ __global__ void __launch_bounds__(256) k_batch_commit(DevCtx c, Base2 b, Control
 __global__ void __launch_bounds__(1024) k_batch_scan(BatchBuf bt, ApplyBuf ab)
 {
 	__shared__ uint32_t s_wi[16], s_wr[16], s_bi, s_br, s_nt;
-	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
+	if (bt.hdr->status != MGL_BATCH_BEGAN) return;
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-	if (tid == 0) { s_bi = 0; s_br = 0; s_nt = 0; ab.hdr[4] = 0; ab.hdr[5] = 0; ab.hdr[6] = 0; ab.hdr[7] = 0; } /* + the job / span / scratch cursors of k_apply_jobs' lists */
+	if (tid == 0) { s_bi = 0; s_br = 0; s_nt = 0; ab.hdr->jobs_b = 0; ab.hdr->jobs_c = 0; ab.hdr->span_used = 0; ab.hdr->scratch_used = 0; } /* + the job / span / scratch cursors of k_apply_jobs' lists */
 	__syncthreads();
 	for (uint32_t base = 0; base < bt.nctx; base += blockDim.x) {
 		const uint32_t cx = base + tid;
@@ -432,13 +424,13 @@ __global__ void __launch_bounds__(1024) k_batch_scan(BatchBuf bt, ApplyBuf ab)
 		if (tid == blockDim.x - 1u) { s_bi = bi + ii; s_br = br + ir; }
 		__syncthreads();
 	}
-	if (tid == 0) bt.hdr[10] = s_nt;
+	if (tid == 0) bt.hdr->touched = s_nt;
 }
 /* every event of the combined lists into its context's bucket */
 __global__ void __launch_bounds__(256) k_batch_fill(BatchBuf bt, ApplyBuf ab)
 {
-	if (bt.hdr[0] != MGL_BATCH_BEGAN) return;
-	const uint32_t n_ins = bt.hdr[2], n_rem = bt.hdr[3];
+	if (bt.hdr->status != MGL_BATCH_BEGAN) return;
+	const uint32_t n_ins = bt.hdr->n_ins, n_rem = bt.hdr->n_rem;
 	for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n_ins + n_rem; e += gridDim.x * blockDim.x) {
 		if (e < n_ins) {
 			const uint32_t key = ab.ins_key[e], cx = key & 0x7FFFu;
@@ -729,11 +721,11 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 	__shared__ uint32_t s_hlist[MGL_BATCH_MAX], s_hspan[MGL_BATCH_MAX + 1], s_gat[MGL_BATCH_MAX], s_hjb[MGL_BATCH_MAX], s_hjc[MGL_BATCH_MAX], s_hscr[MGL_BATCH_MAX];
 	__shared__ int32_t s_hdelta[MGL_BATCH_MAX + 1]; /* length change accumulated up to and including head h */
 	__shared__ uint32_t s_ng, s_nh, s_fail, s_scr_base, s_job_b, s_job_c, s_newoff, s_newcap, s_newlen, s_maxd;
-	if (bt.hdr[0] != MGL_BATCH_BEGAN || bt.hdr[4]) return;
-	if (bt.hdr[9]) { if (blockIdx.x == 0 && threadIdx.x == 0) give_up(ctl, lim, MGL_GU_FORCED_EARLY); return; } /* test hook (mgl_debug_set key 5): give up behind the commit */
+	if (bt.hdr->status != MGL_BATCH_BEGAN || bt.hdr->failed) return;
+	if (bt.hdr->force_early) { if (blockIdx.x == 0 && threadIdx.x == 0) give_up(ctl, lim, MGL_GU_FORCED_EARLY); return; } /* test hook (mgl_debug_set key 5): give up behind the commit */
 	/* one workgroup per touched context (k_batch_scan lists them: a tenth of the contexts on a step of fifteen moves), the
 	 * grid strides over the list */
-	const uint32_t ntouched = bt.hdr[10];
+	const uint32_t ntouched = bt.hdr->touched;
 	if (blockIdx.x >= ntouched) return;
 	const uint32_t tid = threadIdx.x;
 	for (uint32_t i = tid; i < 256; i += blockDim.x) reinterpret_cast<uint4*>(T)[i] = reinterpret_cast<const uint4*>(c.cost_tbl)[i];
@@ -788,14 +780,14 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 		/* ---- 3. every group starts a run, writing its new entries into MGL_BATCH_RES entries of the span area taken for it
 		 * (most runs fit: a perturbed probability re-joins the old trajectory after about a hundred events; one that does not is
 		 * run again in step 5, into a place of its size) ... */
-		const uint32_t res = bt.hdr[1] <= MGL_BATCH_FEW ? MGL_BATCH_RES_FEW : MGL_BATCH_RES;
+		const uint32_t res = bt.hdr->clusters <= MGL_BATCH_FEW ? MGL_BATCH_RES_FEW : MGL_BATCH_RES;
 		/* few groups: a wavefront per run (batch_run_wave); many: a lane per run, all of them side by side */
 		const uint32_t lane = tid & 63u, wid = tid >> 6, nwaves = blockDim.x >> 6;
 		const bool by_wave = ng <= 3u * nwaves;
 		if (by_wave) {
 			for (uint32_t g = wid; g < ng; g += nwaves) {
 				uint32_t at = 0;
-				if (lane == 0) at = atomicAdd(&ab.hdr[6], res + 8u);
+				if (lane == 0) at = atomicAdd(&ab.hdr->span_used, res + 8u);
 				at = uni(at);
 				if (lane == 0) s_gat[g] = at;
 				if (at + res + 8u > ab.span_cap) { s_fail = MGL_GU_CH_SPAN_AREA; continue; }
@@ -803,7 +795,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 				if (lane == 0) s_run[g] = rr;
 			}
 		} else if (tid < ng) {
-			const uint32_t at = atomicAdd(&ab.hdr[6], res + 8u); /* (+ the spare entry the tail loop writes to instead of branching) */
+			const uint32_t at = atomicAdd(&ab.hdr->span_used, res + 8u); /* (+ the spare entry the tail loop writes to instead of branching) */
 			s_gat[tid] = at;
 			if (at + res + 8u > ab.span_cap) s_fail = MGL_GU_CH_SPAN_AREA;
 			else s_run[tid] = batch_run<true>(cpos, cev, len, T, s_ipos, s_ibit, s_icl, ni, s_rpos, s_rcl, nr, s_gi[tid], s_gr[tid], s_gcl, tid, ab.span_pos, ab.span_ev, at, res, sb_row, sb_info);
@@ -852,7 +844,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 				uint32_t at = s_hspan[h];
 				if (at == 0xFFFFFFFFu) {
 					at = 0;
-					if (lane == 0) at = atomicAdd(&ab.hdr[6], spn + 1u);
+					if (lane == 0) at = atomicAdd(&ab.hdr->span_used, spn + 1u);
 					at = uni(at);
 					if (at + spn + 1u > ab.span_cap) { s_fail = MGL_GU_CH_SPAN_RERUN; continue; }
 					if (lane == 0) s_hspan[h] = at;
@@ -866,7 +858,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 			const uint32_t spn = r0.ns + (r0.uncoupled ? 1u : 0u);
 			uint32_t at = s_hspan[tid];
 			if (at == 0xFFFFFFFFu) {
-				at = atomicAdd(&ab.hdr[6], spn + 1u);
+				at = atomicAdd(&ab.hdr->span_used, spn + 1u);
 				if (at + spn + 1u > ab.span_cap) s_fail = MGL_GU_CH_SPAN_RERUN;
 				else {
 					s_hspan[tid] = at;
@@ -900,9 +892,9 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 				jc += nchunks;
 				if (!moved) { jb += 2u * nchunks; scr += 2u * maxd * nchunks; }
 			}
-			s_job_b = atomicAdd(&ab.hdr[4], jb);
-			s_job_c = atomicAdd(&ab.hdr[5], jc);
-			s_scr_base = atomicAdd(&ab.hdr[7], scr);
+			s_job_b = atomicAdd(&ab.hdr->jobs_b, jb);
+			s_job_c = atomicAdd(&ab.hdr->jobs_c, jc);
+			s_scr_base = atomicAdd(&ab.hdr->scratch_used, scr);
 			if (s_job_b + jb > ab.job_cap || s_job_c + jc > ab.job_cap) s_fail |= MGL_GU_CH_JOBS;
 			if (s_scr_base + scr > ab.scratch_cap) s_fail |= MGL_GU_CH_SCRATCH;
 		}
@@ -952,7 +944,7 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 				/* test hook (mgl_debug_set key 5, high word = n): the n-th context to get this far gives up -- a give-up behind a
 				 * partial rewrite: other workgroups have rewritten their chains' descriptors, taken pool space, patched index rows
 				 * and queued jobs, and go on doing so */
-				if (bt.hdr[13] && atomicAdd(&bt.hdr[12], 1u) + 1u == bt.hdr[13]) s_fail = MGL_GU_FORCED_LATE;
+				if (bt.hdr->force_late && atomicAdd(&bt.hdr->force_reached, 1u) + 1u == bt.hdr->force_late) s_fail = MGL_GU_FORCED_LATE;
 			}
 		}
 		/* ---- 6b. the chain index of this context: the runs above searched the OLD chain with it, nothing does any more */
@@ -964,13 +956,13 @@ __global__ void __launch_bounds__(MGL_BATCH_THREADS) k_batch_chains(DevCtx c, Ba
 		__syncthreads();
 		if (tid < nh) {
 			const RunOut& r = s_run[s_hlist[tid]];
-			const uint32_t at = atomicAdd(&bt.hdr[8], 1u);
+			const uint32_t at = atomicAdd(&bt.hdr->runs, 1u);
 			if (at < bt.runs_cap) {
 				bt.runs[2u * at] = make_uint4(cx, r.lo, r.hi, s_hspan[tid]);
 				bt.runs[2u * at + 1u] = make_uint4(r.ns, r.end_p, 0u, 0u);
 			} else give_up(ctl, lim, MGL_GU_CH_RUNS);
 		}
-		if (tid == 0 && my_cost) atomicAdd((unsigned long long*)&bt.acc[0], (unsigned long long)my_cost);
+		if (tid == 0 && my_cost) atomicAdd((unsigned long long*)&bt.acc->cost, (unsigned long long)my_cost);
 	}
 }
 
@@ -980,8 +972,8 @@ __global__ void __launch_bounds__(256) k_batch_ckpt(Base2 b, const Control* ctl,
 {
 	__shared__ uint32_t s_pos[MGL_BATCH_CK_SPAN];
 	__shared__ uint16_t s_ev[MGL_BATCH_CK_SPAN];
-	if (bt.hdr[0] != MGL_BATCH_BEGAN || bt.hdr[4] || ctl->apply_failed) return;
-	const uint32_t nruns = bt.hdr[8] < bt.runs_cap ? bt.hdr[8] : bt.runs_cap;
+	if (bt.hdr->status != MGL_BATCH_BEGAN || bt.hdr->failed || ctl->apply_failed) return;
+	const uint32_t nruns = bt.hdr->runs < bt.runs_cap ? bt.hdr->runs : bt.runs_cap;
 	for (uint32_t ri = blockIdx.x; ri < nruns; ri += gridDim.x) {
 		const uint4 r0 = bt.runs[2u * ri], r1 = bt.runs[2u * ri + 1u];
 		const uint32_t cx = r0.x, lo = r0.y, hi = r0.z, first = r0.w, ns = r1.x, end_p = r1.y;
@@ -1011,9 +1003,9 @@ __global__ void __launch_bounds__(256) k_batch_ckpt(Base2 b, const Control* ctl,
 __global__ void k_batch_end(Control* ctl, BatchBuf bt)
 {
 	if (threadIdx.x || blockIdx.x) return;
-	if (bt.hdr[0] != MGL_BATCH_BEGAN || ctl->apply_failed) return;
+	if (bt.hdr->status != MGL_BATCH_BEGAN || ctl->apply_failed) return;
 	const uint64_t base_cost = ctl->cur_cost ? ctl->cur_cost : ctl->rebuild_cost;
-	ctl->rebuild_cost = (uint64_t)((long long)base_cost + bt.acc[0] + bt.acc[1]);
-	ctl->packets = (uint64_t)((long long)ctl->packets + bt.acc[2]);
-	bt.hdr[0] = MGL_BATCH_DONE;
+	ctl->rebuild_cost = (uint64_t)((long long)base_cost + bt.acc->cost + bt.acc->direct);
+	ctl->packets = (uint64_t)((long long)ctl->packets + bt.acc->packets);
+	bt.hdr->status = MGL_BATCH_DONE;
 }

@@ -55,7 +55,7 @@ struct PBuild {
 	uint64_t* stage;    /* nblk x (16 << shift + 32): the events pb_walk found, for pb_scatter */
 	uint32_t* stage_n;  /* nblk: how many */
 	uint32_t* stage_over; /* one word: a block outgrew its staging area (cannot happen; checked) */
-	unsigned long long* acc; /* [0] cost [1] packets [2] final ctx_state [3..6] final dists [7] segments pb_sim_fix redid [8] segments pb_sim left to it */
+	PbAcc* acc;
 	uint32_t* seg_off;  /* total + 1: first pb_sim segment of each context */
 	uint8_t* unres;     /* per segment: warm-up did not pin the probability, left to pb_sim_fix */
 	uint32_t seg_cap;
@@ -337,9 +337,9 @@ __global__ void __launch_bounds__(64) pb_scan(PBuild pb)
 	}
 	packets = wave_sum64(packets);
 	if (lane == 0) {
-		pb.acc[0] = 0;
-		pb.acc[1] = packets;
-		pb.acc[2] = cs; pb.acc[3] = d0; pb.acc[4] = d1; pb.acc[5] = d2; pb.acc[6] = d3; pb.acc[7] = 0; pb.acc[8] = 0;
+		pb.acc->cost = 0;
+		pb.acc->packets = packets;
+		pb.acc->ctx_state = cs; pb.acc->dists[0] = d0; pb.acc->dists[1] = d1; pb.acc->dists[2] = d2; pb.acc->dists[3] = d3; pb.acc->redone = 0; pb.acc->left = 0;
 	}
 }
 __global__ void __launch_bounds__(256) pb_scan_fill(PBuild pb)
@@ -438,7 +438,7 @@ __global__ void __launch_bounds__(64) pb_walk(DevCtx c, Base2 b, PBuild pb)
 	if (lane == 0) {
 		pb.stage_n[blk] = nst < cap ? nst : cap; /* (cap is never reached: see MGL_PB_STAGE_PER_POS) */
 		if (nst > cap) atomicOr(pb.stage_over, 1u);
-		if (ndirect) atomicAdd(&pb.acc[0], (unsigned long long)ndirect << 11);
+		if (ndirect) atomicAdd(&pb.acc->cost, (unsigned long long)ndirect << 11);
 	}
 }
 /* every staged event to its slot: chain offset of its context + events of that context in earlier blocks + its rank in the block */
@@ -618,19 +618,19 @@ __global__ void __launch_bounds__(64) pb_sim(DevCtx c, Base2 b, PBuild pb)
 			p = plo;
 		}
 		pb.unres[seg] = ok ? 0 : 1;
-		if (!ok) atomicAdd(&pb.acc[8], 1ull); /* pb_sim_fix returns at once when nothing is left to it (as good as always) */
+		if (!ok) atomicAdd(&pb.acc->left, 1ull); /* pb_sim_fix returns at once when nothing is left to it (as good as always) */
 		if (ok) {
 			pb_sim_range(ev, i0, i1, p, cost, T);
 			if (i1 == len) { ev[len] = (uint16_t)p; b.ch_pos[off + len] = MGL_POS_INF; }
 		}
 	}
 	cost = wave_sum64(cost);
-	if (threadIdx.x == 0 && cost) atomicAdd(&pb.acc[0], cost);
+	if (threadIdx.x == 0 && cost) atomicAdd(&pb.acc->cost, cost);
 }
 /* the segments pb_sim could not start: in chain order, from the entry before them */
 __global__ void __launch_bounds__(64) pb_sim_fix(DevCtx c, Base2 b, PBuild pb)
 {
-	if (pb.acc[8] == 0) return; /* every segment started exact */
+	if (pb.acc->left == 0) return; /* every segment started exact */
 	__shared__ uint16_t T[2048];
 	for (uint32_t i = threadIdx.x; i < 2048; i += 64) T[i] = c.cost_tbl[i];
 	__syncthreads();
@@ -653,8 +653,8 @@ __global__ void __launch_bounds__(64) pb_sim_fix(DevCtx c, Base2 b, PBuild pb)
 	}
 	cost = wave_sum64(cost);
 	redone = wave_sum64(redone);
-	if (threadIdx.x == 0 && cost) atomicAdd(&pb.acc[0], cost);
-	if (threadIdx.x == 0 && redone) atomicAdd(&pb.acc[7], redone);
+	if (threadIdx.x == 0 && cost) atomicAdd(&pb.acc->cost, cost);
+	if (threadIdx.x == 0 && redone) atomicAdd(&pb.acc->redone, redone);
 }
 
 /* dense checkpoints: row k = every context's probability before the first packet at or after
@@ -712,8 +712,8 @@ __global__ void pb_finish(PBuild pb, Control* ctl)
 {
 	if (threadIdx.x || blockIdx.x) return;
 	if (*pb.stage_over) atomicOr(&ctl->error_flags, MGL_ERR_WALK_OVERRUN); /* a block outgrew its staging area: cannot happen */
-	ctl->packets = pb.acc[1];
-	ctl->rebuild_cost = pb.acc[0];
-	ctl->final_ctx_state = (uint32_t)pb.acc[2];
-	for (int i = 0; i < 4; i++) ctl->final_dists[i] = (uint32_t)pb.acc[3 + i];
+	ctl->packets = pb.acc->packets;
+	ctl->rebuild_cost = pb.acc->cost;
+	ctl->final_ctx_state = (uint32_t)pb.acc->ctx_state;
+	for (int i = 0; i < 4; i++) ctl->final_dists[i] = (uint32_t)pb.acc->dists[i];
 }

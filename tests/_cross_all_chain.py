@@ -24,7 +24,7 @@ def chain(rank, world, path, nonce, jobs, out):
             if mine is not None:
                 sa.set_best(np.frombuffer(mine[0], dtype=binding.PACKET), mine[1])
             if job.get("nomem_rank") == rank and i == 0:
-                sa.debug_set(8, 1)  # this chain's next crossover finds no room for its buffers
+                sa.debug_set(binding.KEY.CROSS_NOMEM, 1)  # this chain's next crossover finds no room for its buffers
             cur0, cur0_cost = sa.current()
             st = multi_gpu.exchange_cross_all_native(sa, comm, grain)
             best, cost = sa.best()

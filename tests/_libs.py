@@ -8,6 +8,8 @@ import subprocess
 
 import numpy as np
 
+from megalania_amd.binding import DUMP
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.environ.get("MGL_ORACLE_SO") or os.path.join(ROOT, "oracle", "_build", "liboracle.so")  # the override: tests/test_sanitizers.py
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libmegalania_ref.so")
@@ -74,17 +76,17 @@ def use_block_shift(monkeypatch, shift):
 
 def block_shift(sa) -> int:
     """the block shift the handle was created with (mgl_debug_dump selector 86: shift, blocks, index row stride)"""
-    return int(sa.debug_dump(86, np.uint32)[0])
+    return int(sa.debug_dump(DUMP.INDEX_GEOMETRY)[0])
 
 
 def canonical_base(sa, slab):
     """The incremental engine's base structures (a megalania_amd.binding.SA handle) in an offset-independent form."""
     n, total = sa.n, sa.nprobs
-    off = sa.debug_dump(0, np.uint32)
-    ln = sa.debug_dump(1, np.uint32)
-    cap = sa.debug_dump(8, np.uint32)
-    cpos = sa.debug_dump(2, np.uint32)
-    cev = sa.debug_dump(3, np.uint16)
+    off = sa.debug_dump(DUMP.CHAIN_OFF)
+    ln = sa.debug_dump(DUMP.CHAIN_LEN)
+    cap = sa.debug_dump(DUMP.CHAIN_CAP)
+    cpos = sa.debug_dump(DUMP.CHAIN_POS)
+    cev = sa.debug_dump(DUMP.CHAIN_EV)
     chains = []
     for c in range(total):
         k, m = int(off[c]), int(ln[c])
@@ -92,22 +94,22 @@ def canonical_base(sa, slab):
         chains.append((cpos[k:k + m + 1].copy(), cev[k:k + m + 1].copy()))
     # every chain has its slot to itself, below the pool's top: a give-up that leaks or double-books pool space would pass every
     # comparison of contents until a later step writes through it
-    top = int(sa.debug_dump(85, np.uint32)[0])
+    top = int(sa.debug_dump(DUMP.POOL_TOP)[0])
     by_off = np.argsort(off[:total].astype(np.int64), kind="stable")
     o64, c64 = off[:total].astype(np.int64)[by_off], cap[:total].astype(np.int64)[by_off]
     clash = np.nonzero(o64[:-1] + c64[:-1] > o64[1:])[0]
     assert len(clash) == 0, ("chain slots overlap", [(int(by_off[i]), int(by_off[i + 1])) for i in clash[:5]])
     assert int((o64 + c64).max()) <= top, ("chain slot above the pool top", int(by_off[np.argmax(o64 + c64)]), top)
-    on = np.unpackbits(sa.debug_dump(4, np.uint64).view(np.uint8), bitorder="little")[:n].astype(bool)
-    sp = np.unpackbits(sa.debug_dump(5, np.uint64).view(np.uint8), bitorder="little")[:n].astype(bool)
-    st = sa.debug_dump(6, np.uint32).reshape(n, 8)[:, :5]
-    ck = sa.debug_dump(7, np.uint16).reshape(-1, (total + 7) // 8 * 8)[:, :total]
+    on = np.unpackbits(sa.debug_dump(DUMP.ONWALK).view(np.uint8), bitorder="little")[:n].astype(bool)
+    sp = np.unpackbits(sa.debug_dump(DUMP.SPECIAL).view(np.uint8), bitorder="little")[:n].astype(bool)
+    st = sa.debug_dump(DUMP.SPECIAL_STATE).reshape(n, 8)[:, :5]
+    ck = sa.debug_dump(DUMP.CHECKPOINTS).reshape(-1, (total + 7) // 8 * 8)[:, :total]
     # the chain index is checked against the chains it indexes, here, whoever built or patched it: entry [c][b] = entries of
     # context c's chain with a position below b << shift (the last column: the chain's length).  Shift, block count and row
     # stride are the ones the handle says it built with (the size rule's or MGL_SB_SHIFT's): the blocks must cover the input
-    shift, nsb, stride = (int(x) for x in sa.debug_dump(86, np.uint32))
+    shift, nsb, stride = (int(x) for x in sa.debug_dump(DUMP.INDEX_GEOMETRY))
     assert nsb == (n + (1 << shift) - 1) >> shift and stride >= nsb + 1, (n, shift, nsb, stride)
-    idx = sa.debug_dump(83, np.uint32).reshape(-1, stride)
+    idx = sa.debug_dump(DUMP.CHAIN_INDEX).reshape(-1, stride)
     bounds = (np.arange(nsb + 1, dtype=np.int64) << shift)
     for c in range(total):
         pos = chains[c][0][:-1].astype(np.int64)

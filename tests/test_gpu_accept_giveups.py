@@ -1,7 +1,7 @@
 """Every give-up path of the in-place accepts (mgl_kernels3.hip: a single accept; mgl_kernels5.hip: the moves of a bulk
-step) against the rebuild.  Both accepts leave the step to a rebuild whenever something does not fit; mgl_debug_set key 6
+step) against the rebuild.  Both accepts leave the step to a rebuild whenever something does not fit; mgl_debug_set's KEY.LIMIT
 lowers what a site compares against, so the real comparison fires on an ordinary input, and the give-up word
-(mgl_debug_dump selector 84) says which site fired.  Each case runs three chains with one seed: A with the limit lowered,
+(DUMP.GIVEUP_SITES) says which site fired.  Each case runs three chains with one seed: A with the limit lowered,
 B that never patches in place, T with the default limits (it may not give up on the same steps), and a handle R that only
 rebuilds from a slab.  DESIGN.md section 6 has the table of sites, limits and cases.  `-m gpu`."""
 import numpy as np
@@ -9,25 +9,17 @@ import pytest
 
 from _libs import Oracle, assert_same_base, canonical_base, literal_slab
 from megalania_amd import binding, corpus
+from megalania_amd.binding import GU, LIM
 
 pytestmark = pytest.mark.gpu
 
-# limit ids (include/megalania_hip.h, mgl_debug_set key 6) and give-up sites (csrc/mgl_base2.h)
-L_APPLY_EVENTS, L_APPLY_GUARD, L_APPLY_SUB, L_APPLY_SPAN, L_APPLY_PIECES, L_APPLY_SHIFT = 1, 2, 3, 4, 5, 6
-L_POOL, L_JOBS, L_SPAN_AREA, L_SCRATCH = 7, 8, 9, 10
-L_BATCH_JOURNAL, L_BATCH_EVENTS, L_BATCH_OPS, L_BATCH_GUARD, L_BATCH_SUB, L_BATCH_SHIFT, L_BATCH_RUNS, L_SOFT_REACH = 11, 12, 13, 14, 15, 16, 17, 18
-GU = {name: 1 << bit for bit, name in enumerate(
-    ["apply_events", "apply_guard", "apply_sub", "apply_span", "apply_pieces", "apply_pool", "apply_jobs", "apply_span_area",
-     "apply_scratch", "apply_shift", "cl_journal", "cl_order", "walk_ops", "walk_events", "walk_guard", "walk_invalid",
-     "walk_overrun", "ch_sub", "ch_span_area", "ch_shift", "ch_pool", "ch_jobs", "ch_scratch", "ch_runs", "forced_early",
-     "forced_late", "ch_span_rerun"])}
-EARLY = GU["cl_journal"] | GU["cl_order"] | GU["walk_ops"] | GU["walk_events"] | GU["walk_guard"] | GU["walk_invalid"] | GU["walk_overrun"]
+EARLY = GU.CL_JOURNAL | GU.CL_ORDER | GU.WALK_OPS | GU.WALK_EVENTS | GU.WALK_GUARD | GU.WALK_INVALID | GU.WALK_OVERRUN
 POOL_TOP = -1  # a case's value: the chain pool's top when the limit is set (nothing may take fresh pool space)
 PB2 = dict(lc=2, lp=1, pb=2)
 
 
 def site_names(word):
-    return [k for k, v in GU.items() if word & v]
+    return [g.name.lower() for g in GU if word & g]
 
 
 class Chains:
@@ -109,7 +101,7 @@ class Chains:
 
 def arm(ch, limit, value):
     if value == POOL_TOP:
-        value = int(ch.a.debug_dump(85, np.uint32)[0])
+        value = int(ch.a.debug_dump(binding.DUMP.POOL_TOP)[0])
     ch.a.set_limit(limit, value)
     ch.gave_up = ch.in_place = ch.sites = 0   # (what the warm-up did on its own is not the case's)
     return value
@@ -128,20 +120,20 @@ def inputs(name):
 # and 65-171 removed events, 50-62 touched contexts, 35-88 / 92-123 jobs, 359-4233 span and 326-4468 save entries).  The
 # comments: steps under the limit that gave up / that patched in place, on the MI355X run the values were fixed on.
 SINGLE = [
-    ("apply_events", L_APPLY_EVENTS, 140, "enwik6k", {}, 96, 20, 40),          # 10 / 30, first at step 20
-    ("apply_events", L_APPLY_EVENTS, 140, "enwik6k", PB2, 96, 20, 40),         # 8 / 32
-    ("apply_guard", L_APPLY_GUARD, 3, "enwik6k", {}, 96, 20, 30),              # 30 / 0: every accepted move walks more than three packets
-    ("apply_sub", L_APPLY_SUB, 8, "enwik6k", {}, 96, 20, 30),                  # 27 / 3
-    ("apply_span", L_APPLY_SPAN, 128, "enwik6k", {}, 96, 20, 40),              # 37 / 3
-    ("apply_pieces", L_APPLY_PIECES, 1, "enwik6k", {}, 96, 20, 40),            # 40 / 0: fires at the first re-join of any context (3 never fired in 40 steps: one move, one segment per context)
-    ("apply_shift", L_APPLY_SHIFT, 3, "enwik6k", {}, 96, 20, 40),              # 38 / 2
-    ("apply_pool", L_POOL, POOL_TOP, "enwik30k", {}, 256, 20, 900),            # 1 / 246: step 266, the first chain (an empty rep context, 264 entries of room) to outgrow its slot
-    ("apply_jobs", L_JOBS, 105, "enwik6k", {}, 96, 20, 40),                    # 21 / 19
-    ("apply_span_area", L_SPAN_AREA, 2800, "enwik6k", {}, 96, 20, 40),         # 12 / 28
-    ("apply_scratch", L_SCRATCH, 2900, "enwik6k", PB2, 96, 20, 40),            # 27 / 13
-    ("apply_scratch", L_SCRATCH, 2900, "enwik6k", {}, 96, 20, 40),
-    ("apply_span", L_APPLY_SPAN, 128, "enwik6k", PB2, 96, 20, 40),
-    ("apply_jobs", L_JOBS, 105, "enwik6k", PB2, 96, 20, 40),
+    ("apply_events", LIM.APPLY_EVENTS, 140, "enwik6k", {}, 96, 20, 40),          # 10 / 30, first at step 20
+    ("apply_events", LIM.APPLY_EVENTS, 140, "enwik6k", PB2, 96, 20, 40),         # 8 / 32
+    ("apply_guard", LIM.APPLY_GUARD, 3, "enwik6k", {}, 96, 20, 30),              # 30 / 0: every accepted move walks more than three packets
+    ("apply_sub", LIM.APPLY_SUB, 8, "enwik6k", {}, 96, 20, 30),                  # 27 / 3
+    ("apply_span", LIM.APPLY_SPAN, 128, "enwik6k", {}, 96, 20, 40),              # 37 / 3
+    ("apply_pieces", LIM.APPLY_PIECES, 1, "enwik6k", {}, 96, 20, 40),            # 40 / 0: fires at the first re-join of any context (3 never fired in 40 steps: one move, one segment per context)
+    ("apply_shift", LIM.APPLY_SHIFT, 3, "enwik6k", {}, 96, 20, 40),              # 38 / 2
+    ("apply_pool", LIM.POOL, POOL_TOP, "enwik30k", {}, 256, 20, 900),            # 1 / 246: step 266, the first chain (an empty rep context, 264 entries of room) to outgrow its slot
+    ("apply_jobs", LIM.JOBS, 105, "enwik6k", {}, 96, 20, 40),                    # 21 / 19
+    ("apply_span_area", LIM.SPAN_AREA, 2800, "enwik6k", {}, 96, 20, 40),         # 12 / 28
+    ("apply_scratch", LIM.SCRATCH, 2900, "enwik6k", PB2, 96, 20, 40),            # 27 / 13
+    ("apply_scratch", LIM.SCRATCH, 2900, "enwik6k", {}, 96, 20, 40),
+    ("apply_span", LIM.APPLY_SPAN, 128, "enwik6k", PB2, 96, 20, 40),
+    ("apply_jobs", LIM.JOBS, 105, "enwik6k", PB2, 96, 20, 40),
 ]
 
 
@@ -157,12 +149,12 @@ def test_single_accept_that_gives_up_equals_the_rebuild(site, limit, value, name
     arm(ch, limit, value)
     first = None
     for _ in range(steps):   # (a long run under the limit -- the pool case waits for a chain to outgrow its slot -- ends four steps behind the first give-up)
-        ch.run(1, expect=GU[site], every=4 if steps <= 100 else 64)
+        ch.run(1, expect=GU[site.upper()], every=4 if steps <= 100 else 64)
         if ch.gave_up and first is None:
             first = ch.step
         if steps > 100 and first is not None and ch.step - first >= 4:
             break
-    assert ch.gave_up >= 1 and ch.sites == GU[site], (site, ch.gave_up, ch.in_place, site_names(ch.sites))
+    assert ch.gave_up >= 1 and ch.sites == GU[site.upper()], (site, ch.gave_up, ch.in_place, site_names(ch.sites))
     ch.a.set_limit(0, 0)
     ch.in_place = 0
     ch.run(16, expect=None, every=2)
@@ -176,23 +168,23 @@ def test_single_accept_that_gives_up_equals_the_rebuild(site, limit, value, name
 # rewrite).  Not exercised, because no capacity reaches them: a merged journal that is not strictly ascending (cl_order) and a
 # packet or rep packet of a merged walk that does not code the input (walk_invalid) -- both would be bugs of the selection.
 BATCH = [
-    ("cl_journal", L_BATCH_JOURNAL, 2, "enwik30k", {}, 256, 9, 12, 10),        # 10 / 0, from step 12 on (the first under the limit)
-    ("walk_events", L_BATCH_EVENTS, 64, "enwik30k", {}, 256, 9, 12, 10),       # 10 / 0
-    ("walk_ops", L_BATCH_OPS, 8, "enwik30k", {}, 256, 9, 12, 10),              # 10 / 0
-    ("walk_guard", L_BATCH_GUARD, 4, "enwik30k", PB2, 256, 9, 12, 10),         # 10 / 0
-    ("ch_sub", L_BATCH_SUB, 8, "enwik30k", {}, 256, 9, 12, 10),                # 10 / 0
-    ("ch_shift", L_BATCH_SHIFT, 2, "enwik30k", {}, 256, 9, 12, 10),            # 10 / 0
-    ("ch_pool", L_POOL, POOL_TOP, "enwik30k", {}, 256, 9, 12, 16),             # 1 / 15: step 12 (the rebuild it falls back to lays the pool out afresh, below the limit)
-    ("ch_jobs", L_JOBS, 1750, "enwik30k", {}, 256, 9, 12, 10),                 # 9 / 1 (the default chain queues 1 580-1 900 jobs per list on these steps)
-    ("ch_span_area", L_SPAN_AREA, 4096, "enwik30k", PB2, 256, 9, 12, 10),      # 10 / 0
-    ("ch_span_area", L_SPAN_AREA, 4096, "enwik30k", {}, 256, 9, 12, 10),
+    ("cl_journal", LIM.BATCH_JOURNAL, 2, "enwik30k", {}, 256, 9, 12, 10),        # 10 / 0, from step 12 on (the first under the limit)
+    ("walk_events", LIM.BATCH_EVENTS, 64, "enwik30k", {}, 256, 9, 12, 10),       # 10 / 0
+    ("walk_ops", LIM.BATCH_OPS, 8, "enwik30k", {}, 256, 9, 12, 10),              # 10 / 0
+    ("walk_guard", LIM.BATCH_GUARD, 4, "enwik30k", PB2, 256, 9, 12, 10),         # 10 / 0
+    ("ch_sub", LIM.BATCH_SUB, 8, "enwik30k", {}, 256, 9, 12, 10),                # 10 / 0
+    ("ch_shift", LIM.BATCH_SHIFT, 2, "enwik30k", {}, 256, 9, 12, 10),            # 10 / 0
+    ("ch_pool", LIM.POOL, POOL_TOP, "enwik30k", {}, 256, 9, 12, 16),             # 1 / 15: step 12 (the rebuild it falls back to lays the pool out afresh, below the limit)
+    ("ch_jobs", LIM.JOBS, 1750, "enwik30k", {}, 256, 9, 12, 10),                 # 9 / 1 (the default chain queues 1 580-1 900 jobs per list on these steps)
+    ("ch_span_area", LIM.SPAN_AREA, 4096, "enwik30k", PB2, 256, 9, 12, 10),      # 10 / 0
+    ("ch_span_area", LIM.SPAN_AREA, 4096, "enwik30k", {}, 256, 9, 12, 10),
     # step 5's own comparison (a run that outgrew its first place is written again, after the chain got its pool space): the default
     # chain uses 640-750 K span entries on these steps, about 285 K of them first places (1 080 runs x 264) -- a capacity between the
     # two lets most first places through; workgroups interleave, so either of the two sites may be the one that fires on a step
-    ("ch_span_rerun", L_SPAN_AREA, 420000, "enwik30k", {}, 256, 9, 12, 10),
-    ("walk_guard", L_BATCH_GUARD, 4, "enwik30k", {}, 256, 9, 12, 10),
-    ("ch_scratch", L_SCRATCH, 64, "enwik30k", {}, 256, 9, 12, 10),             # 10 / 0
-    ("ch_runs", L_BATCH_RUNS, 1080, "enwik30k", {}, 256, 9, 12, 10),           # 8 / 2 (1 020-1 200 runs per step)
+    ("ch_span_rerun", LIM.SPAN_AREA, 420000, "enwik30k", {}, 256, 9, 12, 10),
+    ("walk_guard", LIM.BATCH_GUARD, 4, "enwik30k", {}, 256, 9, 12, 10),
+    ("ch_scratch", LIM.SCRATCH, 64, "enwik30k", {}, 256, 9, 12, 10),             # 10 / 0
+    ("ch_runs", LIM.BATCH_RUNS, 1080, "enwik30k", {}, 256, 9, 12, 10),           # 8 / 2 (1 020-1 200 runs per step)
 ]
 
 
@@ -206,9 +198,9 @@ def test_batch_accept_that_gives_up_equals_the_rebuild(site, limit, value, name,
     ch = Chains("bulk", inputs(name), K, seed, props, monkeypatch)
     ch.run(warm, expect=None, every=6)
     arm(ch, limit, value)
-    also = GU["ch_span_area"] if site == "ch_span_rerun" else 0
-    ch.run(steps, expect=GU[site] | also)
-    assert ch.gave_up >= 1 and ch.sites & ~also == GU[site], (site, ch.gave_up, ch.in_place, site_names(ch.sites))
+    also = GU.CH_SPAN_AREA if site == "ch_span_rerun" else 0
+    ch.run(steps, expect=GU[site.upper()] | also)
+    assert ch.gave_up >= 1 and ch.sites & ~also == GU[site.upper()], (site, ch.gave_up, ch.in_place, site_names(ch.sites))
     ch.a.set_limit(0, 0)
     ch.in_place = 0
     acc0 = ch.a.batch_counters()[0]
@@ -235,13 +227,13 @@ def test_forced_give_up_behind_a_partial_rewrite(which, props, monkeypatch):
         # contexts.  (T cannot be sent ahead instead: Chains.run keeps A, B and T in lockstep and compares them step by step.)
         probe = binding.SA(ch.data, accept="bulk", neighbours_per_step=256, seed=9, iters_per_epoch=10**7, **props)
         probe.run(ch.step + 1)
-        hdr = probe.debug_dump(81, np.uint32)
+        hdr = probe.debug_dump(binding.DUMP.BATCH_HDR)[0]
         probe.close()
-        touched = int(hdr[10])
-        assert hdr[0] == 3 and touched >= 4, ("the probed step was no batch accept", hdr[:11])
+        touched = int(hdr["touched"])
+        assert hdr["status"] == binding.BATCH.DONE and touched >= 4, ("the probed step was no batch accept", hdr)
         n = {"first": 1, "half": touched // 2, "all": touched, "early": 0}[which]
-        ch.a.debug_set(5, 1 | (n << 32))
-        want = GU["forced_early"] if which == "early" else GU["forced_late"]
+        ch.a.debug_set(binding.KEY.BATCH_FAIL, 1 | (n << 32))
+        want = GU.FORCED_EARLY if which == "early" else GU.FORCED_LATE
         words = ch.run(1, expect=want)
         assert words == [want], (which, rnd, n, touched, site_names(words[0]))
         ch.run(2, expect=None, every=1)
@@ -272,17 +264,17 @@ def test_cluster_boundary_guard(name, props, K, seed, warm, steps, ipe, monkeypa
         slab, best = literal_slab(n), literal_slab(n)
         ocur = obest = 0
     ch.run(warm, expect=None, every=6)   # (30 KB: the all-literal slab's first steps exceed a real capacity, see Chains.run)
-    arm(ch, L_SOFT_REACH, 1)
+    arm(ch, LIM.SOFT_REACH, 1)
     t_early0, a_early0 = ch.t.batch_giveups(), ch.a.batch_giveups()
     for s in range(steps):
-        word = ch.run(1, expect=GU["walk_overrun"], every=1)[0]
+        word = ch.run(1, expect=GU.WALK_OVERRUN, every=1)[0]
         if small:
             soft0 = ch.o.bulk_soft_overruns()
             res = ch.o.sa_batched(slab, best, ocur, obest, seed, K, 0, n, s, s + 1, iter0=s * K, modes=[1])
             ocur, obest = res["cur"], res["best"]
             assert ch.a.current()[1] == ocur, (name, s)
             assert bool(word) == (ch.o.bulk_soft_overruns() != soft0), (name, s, "guard fired", bool(word))
-    assert ch.gave_up >= 1 and ch.sites == GU["walk_overrun"]
+    assert ch.gave_up >= 1 and ch.sites == GU.WALK_OVERRUN
     assert ch.a.batch_giveups() - a_early0 == ch.gave_up and ch.a.batch_counters()[1] == 0
     assert ch.t.batch_giveups() == t_early0 and ch.t.batch_counters()[1] == 0   # knob off: no overrun, no status-2 give-up on these steps
     if small:
@@ -295,12 +287,12 @@ def test_cluster_boundary_guard(name, props, K, seed, warm, steps, ipe, monkeypa
 
 def test_key_6_refuses_what_it_cannot_honour():
     sa = binding.SA(corpus.lorem(2000), accept="single", neighbours_per_step=32, seed=3)
-    for bad in (L_APPLY_EVENTS | (8193 << 8), L_BATCH_SHIFT | (2048 << 8), L_SOFT_REACH | (2 << 8), 19, 0 | (1 << 8), 200 | (1 << 8)):
-        assert sa.L.mgl_debug_set(sa.h, 6, bad) != 0, bad
-    top = int(sa.debug_dump(85, np.uint32)[0])
-    assert sa.L.mgl_debug_set(sa.h, 6, L_POOL | ((1 << 40) << 8)) != 0
-    assert sa.L.mgl_debug_set(sa.h, 6, L_POOL | (top << 8)) == 0
-    assert sa.L.mgl_debug_set(sa.h, 6, 0) == 0
+    for bad in (LIM.APPLY_EVENTS | (8193 << 8), LIM.BATCH_SHIFT | (2048 << 8), LIM.SOFT_REACH | (2 << 8), len(LIM) + 1, 0 | (1 << 8), 200 | (1 << 8)):
+        assert sa.L.mgl_debug_set(sa.h, binding.KEY.LIMIT, bad) != 0, bad
+    top = int(sa.debug_dump(binding.DUMP.POOL_TOP)[0])
+    assert sa.L.mgl_debug_set(sa.h, binding.KEY.LIMIT, LIM.POOL | ((1 << 40) << 8)) != 0
+    assert sa.L.mgl_debug_set(sa.h, binding.KEY.LIMIT, LIM.POOL | (top << 8)) == 0
+    assert sa.L.mgl_debug_set(sa.h, binding.KEY.LIMIT, 0) == 0
     st = sa.run(20)
     assert st["accepted"] > 0 and st["full_rebuilds"] == 0 and sa.giveup_sites() == 0
     sa.close()

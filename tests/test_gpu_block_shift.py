@@ -196,5 +196,5 @@ def test_size_rule_picks_the_shift(size, shift, monkeypatch):
     data = prose(MIB + 1 if size <= MIB + 1 else 8 * MIB + 1)[:size]
     sa = binding.SA(data, accept="single", neighbours_per_step=8)
     nsb = (size + (1 << shift) - 1) >> shift
-    assert [int(x) for x in sa.debug_dump(86, np.uint32)] == [shift, nsb, (nsb + 2 + 3) & ~3]
+    assert [int(x) for x in sa.debug_dump(binding.DUMP.INDEX_GEOMETRY)] == [shift, nsb, (nsb + 2 + 3) & ~3]
     sa.close()

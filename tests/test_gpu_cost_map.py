@@ -22,7 +22,6 @@ pytestmark = pytest.mark.gpu
 MGL_EINVAL, MGL_ENOMEM = -1, -2
 EXTREME = 9 | lzma.PRESET_EXTREME
 FOREIGN = [(3, 0, 2), (0, 2, 2)]
-KEY_COSTMAP_NOMEM = 10
 
 
 def xz_parse(data, lc=0, lp=0, pb=0):
@@ -247,7 +246,7 @@ def test_refusals_equal_cost_slab_and_leave_the_handle_usable():
         rc, out, rep = _raw(sa, good, want_map=False)
         assert rc == 0 and (out == 0xA5A5A5A5).all() and binding.CostReport.from_buffer_copy(rep).total == want["total"]
         # no room for the call's buffers: MGL_ENOMEM once, then the same call goes through
-        sa.debug_set(KEY_COSTMAP_NOMEM, 1)
+        sa.debug_set(binding.KEY.COSTMAP_NOMEM, 1)
         rc, out, rep = _raw(sa, good)
         assert rc == MGL_ENOMEM and (out == 0xA5A5A5A5).all() and rep == untouched
         assert_device_equals_host(sa, data, good, None, "after ENOMEM")

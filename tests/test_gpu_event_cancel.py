@@ -3,7 +3,7 @@ packet and a base packet start at the same position and do not cancel whole, the
 same context, same bit -- stay off both change lists.  That is exact because a context occurs at most once in a packet's plan
 (the CPU test), and every cost, trajectory and drop decision below is compared with the oracle or the full-walk engine, which
 know nothing of it.  Costs are integer sums: every comparison is exact.  MGL_NO_EVCANCEL=1 restores the packet-level lists;
-mgl_debug_dump selector 10, slot [5], counts the cancelled pairs of the last step's (or mgl_neighbours call's) costed neighbours.
+mgl_debug_dump selector 10 (DUMP.STEP_COUNTS), field `cancelled`, counts the cancelled pairs of the last step's (or mgl_neighbours call's) costed neighbours.
 The GPU tests: `-m gpu`."""
 import lzma
 import os
@@ -16,7 +16,6 @@ from _libs import Oracle, literal_slab
 from conftest import slab_from_rle
 from megalania_amd import binding, corpus
 
-KEY_LIST_CAP, KEY_BIG_WAVES = 2, 7
 WIN_DROPPED = 0xFFFFFFFE  # csrc/mgl_device.h: MGL_WIN_DROPPED
 PROPS = [(0, 0, 0), (3, 0, 2), (0, 4, 4)]
 
@@ -93,9 +92,9 @@ def _oracle_costs(shape, props, step, data, cur, seed, K):
 def _set_big_waves(sa, waves):
     """waves = 0: the compiled MGL_BIG_WAVES (the one of 4 and 8 the library takes)"""
     if waves:
-        sa.debug_set(KEY_BIG_WAVES, waves)
+        sa.debug_set(binding.KEY.BIG_WAVES, waves)
         return
-    took = [w for w in (4, 8) if sa.L.mgl_debug_set(sa.h, KEY_BIG_WAVES, w) == 0]
+    took = [w for w in (4, 8) if sa.L.mgl_debug_set(sa.h, binding.KEY.BIG_WAVES, w) == 0]
     assert len(took) == 1, took
 
 
@@ -104,7 +103,7 @@ def _costs_vs_oracle(shape, data, K, seed, at_steps, start, cap, waves, props, s
     against the oracle's; returns (cancelled pairs over the mgl_neighbours calls, second-pass neighbours of the steps run)"""
     sa = binding.SA(data, accept="single", neighbours_per_step=K, seed=seed, **props, **kw)
     if cap:
-        sa.debug_set(KEY_LIST_CAP, cap)
+        sa.debug_set(binding.KEY.LIST_CAP, cap)
     _set_big_waves(sa, waves)
     if start is not None:
         sa.set_slab(start)
@@ -117,7 +116,7 @@ def _costs_vs_oracle(shape, data, K, seed, at_steps, start, cap, waves, props, s
         slab_rows, want = _oracle_costs(shape, props, step, data, cur, seed, K)
         assert rows(cur) == slab_rows, step
         got = sa.neighbours(step, want_diffs=False)[0]
-        n = int(sa.debug_dump(10, np.uint32)[5])
+        n = int(sa.debug_dump(binding.DUMP.STEP_COUNTS)[0]["cancelled"])
         print(f"{shape} step {step} cap {cap or 'allocated'} waves {waves or 'MGL_BIG_WAVES'} switch {'on' if switch_on else 'off'}: {n} cancelled pairs")
         pairs += n
         bad = np.nonzero(got != want)[0]
@@ -187,7 +186,7 @@ def test_two_slices_trajectory_vs_fullwalk(monkeypatch):
     ref.close()
     sa = binding.SA(data, accept="single", neighbours_per_step=1024)
     got = _steps(sa, 12)
-    pairs = int(sa.debug_dump(10, np.uint32)[5])
+    pairs = int(sa.debug_dump(binding.DUMP.STEP_COUNTS)[0]["cancelled"])
     sa.close()
     print(f"c2 20000 K=1024: final cost {got[1]}, {pairs} cancelled pairs in the last step")
     assert got == want
@@ -197,8 +196,8 @@ def test_two_slices_trajectory_vs_fullwalk(monkeypatch):
 # ---- 5. drop decisions
 def _statuses(sa, step):
     costs = sa.neighbours(step, want_diffs=False)[0]
-    win = sa.debug_dump(21, np.uint32).reshape(-1, 2)
-    pairs = int(sa.debug_dump(10, np.uint32)[5])
+    win = sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2)
+    pairs = int(sa.debug_dump(binding.DUMP.STEP_COUNTS)[0]["cancelled"])
     return [(1 if int(c) != binding.INVALID_COST else -1 if int(w) == WIN_DROPPED else 0, int(c)) for c, w in zip(costs, win[:, 1])], pairs
 
 

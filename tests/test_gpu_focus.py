@@ -78,7 +78,7 @@ def greedy_slab():
 
 
 def targets_of(sa):
-    return [int(t) for t in sa.debug_dump(21, np.uint32).reshape(-1, 2)[:, 0]]
+    return [int(t) for t in sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2)[:, 0]]
 
 
 # ---- 1. the target rule
@@ -170,8 +170,8 @@ def test_prefix_window_equals_the_oracle(case):
         outcomes = set()
         for step in (0, 11):
             costs, nd, diffs = sa.neighbours(step)
-            win = sa.debug_dump(21, np.uint32).reshape(-1, 2)
-            win2 = sa.debug_dump(22, np.uint32)
+            win = sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2)
+            win2 = sa.debug_dump(binding.DUMP.SOFT_ENDS)
             for j in range(K):
                 st, cost, od, w = o.neighbour_ex(slab, SEED, step, j, K=Ko)
                 outcomes.add(st)

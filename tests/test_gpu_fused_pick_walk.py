@@ -48,8 +48,8 @@ def _same_end(fused, split, what):
     (ba, bcost_a), (bb, bcost_b) = fused.best(), split.best()
     assert bcost_a == bcost_b and (ba == bb).all(), what
     # the last step's neighbours: cost, journal length, packets walked, window and soft window
-    for sel, dt in ((23, np.uint64), (24, np.uint32), (25, np.uint32), (21, np.uint32), (22, np.uint32)):
-        x, y = fused.debug_dump(sel, dt), split.debug_dump(sel, dt)
+    for sel in (binding.DUMP.COSTS, binding.DUMP.JOURNAL_LENS, binding.DUMP.WALKED, binding.DUMP.WINDOWS, binding.DUMP.SOFT_ENDS):
+        x, y = fused.debug_dump(sel), split.debug_dump(sel)
         assert len(x) == len(y) and (x == y).all(), (what, sel, np.nonzero(x != y)[0][:8])
 
 
@@ -91,7 +91,7 @@ def test_hand_over_to_second_pass(monkeypatch, variant):
     env = [("MGL_NO_CONT", "1")] if variant == "no_continuations" else []
     fused, split = _pair(monkeypatch, data, env=env, neighbours_per_step=1024, seed=79, accept="single")
     if variant == "small_lists":
-        fused.debug_set(2, 32); split.debug_set(2, 32)
+        fused.debug_set(binding.KEY.LIST_CAP, 32); split.debug_set(binding.KEY.LIST_CAP, 32)
     tot = _steps(fused, split, 12, variant)
     for t in tot:
         assert t["second_pass_neighbours"] > 0 and t["fallback_neighbours"] == 0, (variant, t)

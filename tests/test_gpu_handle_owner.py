@@ -28,7 +28,7 @@ def _sa(**kw):
 
 
 def _held(sa):
-    count, nbytes = sa.debug_dump(87, np.uint64).tolist()
+    count, nbytes = sa.debug_dump(binding.DUMP.ALLOCATIONS).tolist()
     return count, nbytes
 
 
@@ -96,7 +96,7 @@ def test_a_crossover_without_room_leaves_nothing_behind(seeded):
     sa = seeded
     held = _held(sa)
     cur, cost = sa.current()
-    sa.debug_set(8, 1)
+    sa.debug_set(binding.KEY.CROSS_NOMEM, 1)
     with pytest.raises(binding.MglError) as e:
         sa.crossover([literal_slab(N), cur])
     assert "do not fit the device" in str(e.value) and e.value.rc == -2  # MGL_ENOMEM

@@ -52,11 +52,11 @@ def check_base(sa, o, slab, data):
     total = sa.nprobs
     lit = total - 1847  # the literal coder: 0x300 << (lc + lp) probabilities, first in the reference's order, last in the product's
     ctx = ref_to_product_ctx(tr["ctx"], lit)
-    off = sa.debug_dump(0, np.uint32)
-    ln = sa.debug_dump(1, np.uint32)
-    cap = sa.debug_dump(8, np.uint32)
-    cpos = sa.debug_dump(2, np.uint32)
-    cev = sa.debug_dump(3, np.uint16)
+    off = sa.debug_dump(binding.DUMP.CHAIN_OFF)
+    ln = sa.debug_dump(binding.DUMP.CHAIN_LEN)
+    cap = sa.debug_dump(binding.DUMP.CHAIN_CAP)
+    cpos = sa.debug_dump(binding.DUMP.CHAIN_POS)
+    cev = sa.debug_dump(binding.DUMP.CHAIN_EV)
     ev = (tr["bit"].astype(np.uint16) << 15) | tr["prob"]
     fin = o.cost_slab(slab, want_probs=True)["probs"]
     fin_prod = np.empty(total, dtype=np.uint16)
@@ -76,20 +76,20 @@ def check_base(sa, o, slab, data):
     w = walk(slab)
     on = np.zeros(n, dtype=bool)
     on[w] = True
-    onw = sa.debug_dump(4, np.uint64)
+    onw = sa.debug_dump(binding.DUMP.ONWALK)
     got_on = np.unpackbits(onw.view(np.uint8), bitorder="little")[:n].astype(bool)
     assert (got_on == on).all()
     special = on & (slab["type"] != 1)
-    sp0 = sa.debug_dump(5, np.uint64)
+    sp0 = sa.debug_dump(binding.DUMP.SPECIAL)
     got_sp = np.unpackbits(sp0.view(np.uint8), bitorder="little")[:n].astype(bool)
     assert (got_sp == special).all()
     # state records before every special packet
-    st = sa.debug_dump(6, np.uint32).reshape(n, 8)
+    st = sa.debug_dump(binding.DUMP.SPECIAL_STATE).reshape(n, 8)
     pk_state = dict(zip((int(p) for p in tr["pk_pos"]), tr["pk_state"]))
     for p in np.nonzero(special)[0]:
         assert (st[p, :5] == pk_state[int(p)]).all(), p
     # dense checkpoints: model before the first packet at or after every `spacing`-th byte
-    ck = sa.debug_dump(7, np.uint16).reshape(-1, (total + 7) // 8 * 8)
+    ck = sa.debug_dump(binding.DUMP.CHECKPOINTS).reshape(-1, (total + 7) // 8 * 8)
     spacing = [s for s in (8, 16, 32, 64) if (n + s - 1) // s == ck.shape[0]]
     assert len(spacing) >= 1, (n, ck.shape)
     spacing = spacing[0]
@@ -231,7 +231,7 @@ def test_batch_accept_that_gives_up_falls_back_to_the_rebuild(shift, monkeypatch
     assert shift is None or block_shift(a) == block_shift(b) == block_shift(ref) == shift
     for x in (a, b):
         x.run(12)
-    a.debug_set(5, 3)
+    a.debug_set(binding.KEY.BATCH_FAIL, 3)
     for s in range(8):
         sa_, sb_ = a.run(1), b.run(1)
         assert sa_["current_cost"] == sb_["current_cost"] and sa_["accepted"] == sb_["accepted"] and sa_["bulk_rollbacks"] == 0, s
@@ -351,16 +351,16 @@ def test_parallel_build_serial_segment_path(shift, monkeypatch):
     a.run(30)
     cur, cost = a.current()
     want = canonical_base(a, cur)
-    a.L.mgl_debug_set(a.h, 1, 1)
+    a.L.mgl_debug_set(a.h, binding.KEY.PBUILD_FIX, 1)
     a.set_slab(cur)
-    acc = a.debug_dump(11, np.uint64)
-    assert int(acc[7]) > 10  # segments redone serially
+    acc = a.debug_dump(binding.DUMP.PBUILD_TOTALS)[0]
+    assert int(acc["redone"]) > 10  # segments redone serially
     cur2, cost2 = a.current()
     assert cost2 == cost and (cur2 == cur).all()
     assert_same_base(canonical_base(a, cur), want, "forced pb_sim_fix")
-    a.L.mgl_debug_set(a.h, 1, 0)
+    a.L.mgl_debug_set(a.h, binding.KEY.PBUILD_FIX, 0)
     a.set_slab(cur)
-    assert int(a.debug_dump(11, np.uint64)[7]) == 0
+    assert int(a.debug_dump(binding.DUMP.PBUILD_TOTALS)[0]["redone"]) == 0
     a.close()
 
 
@@ -405,7 +405,7 @@ def test_second_pass_takes_what_overflows_small_lists():
     for cap in (0, 16):
         sa = binding.SA(data, accept="single", neighbours_per_step=96, seed=5, iters_per_epoch=60)
         if cap:
-            assert sa.L.mgl_debug_set(sa.h, 2, cap) == 0
+            assert sa.L.mgl_debug_set(sa.h, binding.KEY.LIST_CAP, cap) == 0
         costs, second = [], 0
         for _ in range(40):
             st = sa.run(1)
@@ -413,7 +413,7 @@ def test_second_pass_takes_what_overflows_small_lists():
             second += st["second_pass_neighbours"]
         cur, cost = sa.current()
         runs.append((costs, cost, [tuple(int(x) for x in r) for r in zip(cur["type"], cur["dist"], cur["len"])], second))
-        assert sa.L.mgl_debug_set(sa.h, 2, 12) != 0  # not a multiple of 8
+        assert sa.L.mgl_debug_set(sa.h, binding.KEY.LIST_CAP, 12) != 0  # not a multiple of 8
         sa.close()
     assert runs[0][:3] == runs[1][:3]
     assert runs[1][3] > 2 * runs[0][3] and runs[1][3] > 40 * 96 // 2  # most of the 3 840 neighbours took the second pass
@@ -427,9 +427,9 @@ def test_counting_kernel_gives_the_same_trajectory_and_counts_bytes():
     a = binding.SA(data, accept="single", neighbours_per_step=2048, seed=7, timing=True)
     b = binding.SA(data, accept="single", neighbours_per_step=2048, seed=7, timing=True)
     a.run(30); b.run(30)
-    b.debug_set(4, 1)
+    b.debug_set(binding.KEY.COUNT_TRAFFIC, 1)
     sa_, sb_ = a.run(12), b.run(12)
-    b.debug_set(4, 0)
+    b.debug_set(binding.KEY.COUNT_TRAFFIC, 0)
     assert sa_["current_cost"] == sb_["current_cost"] and sa_["evaluations"] == sb_["evaluations"] and sa_["accepted"] == sb_["accepted"]
     assert sa_["sim_bytes_counted"] == 0
     if sb_["sim_launches"]:  # the split form ran (the device may have chosen the one-kernel form for some steps)

@@ -171,7 +171,7 @@ def test_every_neighbour_of_a_step_costs_what_the_oracle_says(props):
     sa = binding.SA(data, accept="single", neighbours_per_step=K, seed=seed, **props)
     sa.set_slab(P(slab))
     costs = sa.neighbours(step, want_diffs=False)[0]
-    win = sa.debug_dump(21, np.uint32).reshape(-1, 2)
+    win = sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2)
     sa.close()
     got = [(1 if int(c) != binding.INVALID_COST else -1 if int(w) == WIN_DROPPED else 0, int(c)) for c, w in zip(costs, win[:, 1])]
     o = Oracle(data, dict_limit=0x400000, **props)

@@ -238,8 +238,8 @@ def test_windows_and_drop_counter_vs_oracle():
         sa = binding.SA(data, accept="single", neighbours_per_step=K, seed=seed, fullwalk=fullwalk)
         sa.set_slab(P(slab))
         costs, nd, _ = sa.neighbours(777)
-        win = sa.debug_dump(21, np.uint32).reshape(-1, 2)
-        win2 = sa.debug_dump(22, np.uint32)
+        win = sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2)
+        win2 = sa.debug_dump(binding.DUMP.SOFT_ENDS)
         ndrop = 0
         for j in range(K):
             st, cost, diffs, w = o.neighbour_ex(slab, seed, 777, j, K=K)
@@ -416,8 +416,8 @@ def test_match_index_built_on_device(cfg, size):
     keys = (d[:-1] << 8) | d[1:]
     want_pos = np.argsort(keys, kind="stable").astype(np.uint32)
     want_off = np.searchsorted(keys[want_pos], np.arange(65537), side="left").astype(np.uint32)
-    got_off = sa.debug_dump(12, np.uint32)
-    got_pos = sa.debug_dump(13, np.uint32)
+    got_off = sa.debug_dump(binding.DUMP.BUCKET_OFF)
+    got_pos = sa.debug_dump(binding.DUMP.BUCKET_POS)
     assert (got_off == want_off).all()
     assert (got_pos == want_pos).all()
     # the second order of the same positions: by the four bytes at the position (zero padded), then by position
@@ -426,34 +426,35 @@ def test_match_index_built_on_device(cfg, size):
     idx = np.arange(m)
     key4 = (dp[idx] << 24) | (dp[idx + 1] << 16) | (dp[idx + 2] << 8) | dp[idx + 3]
     want_quad = np.argsort(key4, kind="stable").astype(np.uint32)
-    got_quad = sa.debug_dump(18, np.uint32)
-    got_qnx = sa.debug_dump(19, np.uint16)
+    got_quad = sa.debug_dump(binding.DUMP.QUAD_POS)
+    got_qnx = sa.debug_dump(binding.DUMP.QUAD_NEXT)
     assert (got_quad == want_quad).all()
     assert (got_qnx == (key4[want_quad] & 0xFFFF).astype(np.uint16)).all()
     # the deeper orders top-K scans by length (mgl_index.hip): positions by their first D bytes, then by position;
     # rank = inverse permutation; run start = first entry with the same D bytes; the byte(s) behind the prefix
     dp = np.concatenate([d, np.zeros(32, dtype=np.uint32)]).astype(np.uint8)
     # (D = 4 again, through the selectors top-K and the match finder read it by: its rank, run starts and next byte as well)
-    for D, sel in ((3, (31, 41, 51, 61)), (4, (32, 42, 52, 62)), (5, (33, 43, 53, 63)), (6, (34, 44, 54, 64)), (7, (35, 45, 55, 65)),
-                   (8, (70, 71, 72, 73)), (16, (74, 75, 76, 77))):
+    DUMP = binding.DUMP
+    for D, sel in [(D, [DUMP[f"{fam}_D{D}"] for fam in ("XPOS", "XRANK", "XRUN", "XNEXT")]) for D in range(3, 8)] + [
+            (8, (DUMP.OCT_POS, DUMP.OCT_RANK, DUMP.OCT_RUN, DUMP.OCT_NEXT8)), (16, (DUMP.HEX_POS, DUMP.HEX_RANK, DUMP.HEX_RUN, DUMP.HEX_NEXT8))]:
         cols = np.stack([dp[idx + k] for k in range(D)])           # D x m
         want = np.lexsort(cols[::-1]).astype(np.uint32)            # stable: ties keep position order
-        got = sa.debug_dump(sel[0], np.uint32)
+        got = sa.debug_dump(sel[0])
         assert (got == want).all(), D
-        rank = sa.debug_dump(sel[1], np.uint32)
+        rank = sa.debug_dump(sel[1])
         assert (rank[want] == np.arange(m, dtype=np.uint32)).all(), D
         keys = cols[:, want].T                                     # m x D, sorted
         head = np.ones(m, dtype=bool)
         head[1:] = (keys[1:] != keys[:-1]).any(axis=1)
         want_run = np.maximum.accumulate(np.where(head, np.arange(m), 0)).astype(np.uint32)
-        assert (sa.debug_dump(sel[2], np.uint32) == want_run).all(), D
+        assert (sa.debug_dump(sel[2]) == want_run).all(), D
         if D < 8:
-            assert (sa.debug_dump(sel[3], np.uint8) == dp[want + D]).all(), D
+            assert (sa.debug_dump(sel[3]) == dp[want + D]).all(), D
         else:
             nx = np.zeros(m, dtype=np.uint64)
             for k in range(8):
                 nx |= dp[want + D + k].astype(np.uint64) << np.uint64(8 * k)
-            assert (sa.debug_dump(sel[3], np.uint64) == nx).all(), D
+            assert (sa.debug_dump(sel[3]) == nx).all(), D
     sa.close()
 
 
@@ -557,7 +558,7 @@ def test_bulk_rollback_net_restores_the_step(golden_input):
     sa.run(3)
     before, cost_before = sa.current()
     best_before, bcost_before = sa.best()
-    assert sa.L.mgl_debug_set(sa.h, 3, 2) == 0
+    assert sa.L.mgl_debug_set(sa.h, binding.KEY.ROLLBACKS, 2) == 0
     st = sa.run(2)
     assert st["bulk_rollbacks"] == 2 and st["accepted"] == 0 and st["bulk_steps"] == 2 and st["evaluations"] > 0
     after, cost_after = sa.current()

@@ -39,7 +39,7 @@ def _pair(monkeypatch, data, env=(), **kw):
     monkeypatch.setenv("MGL_NO_ORDER", "1")
     plain = binding.SA(data, **kw)
     monkeypatch.delenv("MGL_NO_ORDER")
-    assert len(ordered.debug_dump(27, np.uint32)) == kw["neighbours_per_step"] and len(plain.debug_dump(27, np.uint32)) == 0
+    assert len(ordered.debug_dump(binding.DUMP.PICK_ORDER)) == kw["neighbours_per_step"] and len(plain.debug_dump(binding.DUMP.PICK_ORDER)) == 0
     return ordered, plain
 
 
@@ -49,7 +49,7 @@ def _slices(K, halves):
 
 
 def _check_order(chain, K, halves, what):
-    hint, order = chain.debug_dump(26, np.uint8), chain.debug_dump(27, np.uint32).astype(np.int64)
+    hint, order = chain.debug_dump(binding.DUMP.PICK_HINTS), chain.debug_dump(binding.DUMP.PICK_ORDER).astype(np.int64)
     assert len(hint) == K and len(order) == K
     for j0, j1 in _slices(K, halves):
         o = order[j0:j1]
@@ -63,7 +63,7 @@ def _check_order(chain, K, halves, what):
 
 def _check_adversarial(chain, K, halves, what):
     for pattern in (0, 1, 2, 0x9E3779B97F4A7C15, 12345):
-        chain.debug_set(9, pattern)
+        chain.debug_set(binding.KEY.PICK_HINTS, pattern)
         hint = _check_order(chain, K, halves, (what, pattern))
         if pattern == 0:
             assert not hint.any()
@@ -77,7 +77,7 @@ def _check_adversarial(chain, K, halves, what):
 
 def _decisions(chain, K):
     """what the two-launch form's pick half decided at the last step: 1 = grow/shrink"""
-    return chain.debug_dump(28, np.uint32).reshape(K, 8)[:, 7]
+    return chain.debug_dump(binding.DUMP.PICKSTATE)["mutated"]
 
 
 def _check_hint(monkeypatch, data, K, env=(), greedy=False, setup=None, auto_steps=0, **kw):
@@ -91,7 +91,7 @@ def _check_hint(monkeypatch, data, K, env=(), greedy=False, setup=None, auto_ste
     seen = 0
     for run in (1, 1, 1, 2, 2, 2):  # targets made at the head of the step, then beside the previous step's accept
         c.run(run)
-        hint, dec = c.debug_dump(26, np.uint8), _decisions(c, K)
+        hint, dec = c.debug_dump(binding.DUMP.PICK_HINTS), _decisions(c, K)
         assert set(np.unique(dec)) <= {0, 1}
         wrong = np.nonzero(hint != 1 - dec)[0]
         assert len(wrong) == 0, (run, len(wrong), wrong[:8])
@@ -101,7 +101,7 @@ def _check_hint(monkeypatch, data, K, env=(), greedy=False, setup=None, auto_ste
         bad = tot = 0
         for _ in range(auto_steps // 2):
             c.run(2)
-            hint, dec = c.debug_dump(26, np.uint8), _decisions(c, K)
+            hint, dec = c.debug_dump(binding.DUMP.PICK_HINTS), _decisions(c, K)
             bad += int(np.count_nonzero(hint != 1 - dec)); tot += K
         print(f"hint bytes that differ from the decision in auto steps: {bad} of {tot} ({100.0 * bad / tot:.2f} %)")
     c.close()
@@ -153,7 +153,7 @@ def test_hand_over_to_second_pass(monkeypatch):
     """c1's shape with first-pass lists of 32 events: hand-overs to the second pass and continuation records under the new mapping"""
     data, K = corpus.lorem(4096), 1024
     ordered, plain = _pair(monkeypatch, data, neighbours_per_step=K, seed=79, accept="single")
-    ordered.debug_set(2, 32); plain.debug_set(2, 32)
+    ordered.debug_set(binding.KEY.LIST_CAP, 32); plain.debug_set(binding.KEY.LIST_CAP, 32)
     tot = _steps(ordered, plain, 12, "small_lists")
     for t in tot:
         assert t["second_pass_neighbours"] > 0 and t["fallback_neighbours"] == 0, t
@@ -163,7 +163,7 @@ def test_hand_over_to_second_pass(monkeypatch):
 
 
 def test_hand_over_to_second_pass_hint(monkeypatch):
-    _check_hint(monkeypatch, corpus.lorem(4096), 1024, setup=lambda c: c.debug_set(2, 32), seed=79)
+    _check_hint(monkeypatch, corpus.lorem(4096), 1024, setup=lambda c: c.debug_set(binding.KEY.LIST_CAP, 32), seed=79)
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 65])
@@ -189,9 +189,9 @@ def test_position_targets(monkeypatch):
     monkeypatch.setenv("MGL_NO_FUSE", "1")
     split = binding.SA(data, **kw)
     monkeypatch.delenv("MGL_NO_FUSE")
-    assert len(fused.debug_dump(26, np.uint8)) == 0 and len(fused.debug_dump(27, np.uint32)) == 0
+    assert len(fused.debug_dump(binding.DUMP.PICK_HINTS)) == 0 and len(fused.debug_dump(binding.DUMP.PICK_ORDER)) == 0
     with pytest.raises(binding.MglError):
-        fused.debug_set(9, 0)
+        fused.debug_set(binding.KEY.PICK_HINTS, 0)
     fused.seed_greedy(); split.seed_greedy()
     _steps(fused, split, 8, "position")
     _same_end(fused, split, "position")

@@ -102,8 +102,8 @@ def test_every_neighbour_vs_oracle(name, alt, fullwalk):
     bad, got_rows, want_rows = [], [], []
     for step in rp.STEPS:
         costs, nd, diffs = sa.neighbours(step)
-        win = sa.debug_dump(21, np.uint32).reshape(-1, 2)
-        win2 = sa.debug_dump(22, np.uint32)
+        win = sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2)
+        win2 = sa.debug_dump(binding.DUMP.SOFT_ENDS)
         for j, (st, cost, od, w, reason) in enumerate(rp.oracle_neighbours(name, step, alt)):
             got_st = 1 if int(costs[j]) != binding.INVALID_COST else -1 if int(win[j, 1]) == WIN_DROPPED else 0
             got_rows.append((got_st, 0, 0, 0, reason))

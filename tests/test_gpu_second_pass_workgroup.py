@@ -12,15 +12,14 @@ from megalania_amd import binding, corpus
 
 pytestmark = pytest.mark.gpu
 
-KEY_LIST_CAP, KEY_BIG_WAVES = 2, 7
 
 
 def set_big_waves(sa, waves):
     """waves = 0 stands for the compiled MGL_BIG_WAVES (4 or 8: the one of the two the library takes); returns the number set"""
     if waves:
-        sa.debug_set(KEY_BIG_WAVES, waves)
+        sa.debug_set(binding.KEY.BIG_WAVES, waves)
         return waves
-    took = [w for w in (4, 8) if sa.L.mgl_debug_set(sa.h, KEY_BIG_WAVES, w) == 0]
+    took = [w for w in (4, 8) if sa.L.mgl_debug_set(sa.h, binding.KEY.BIG_WAVES, w) == 0]
     assert len(took) == 1, took
     return took[0]
 
@@ -33,7 +32,7 @@ def test_knob_takes_1_2_and_the_compiled_size_only():
     sa = binding.SA(corpus.lorem(600), accept="single", neighbours_per_step=8)
     full = set_big_waves(sa, 0)
     for w in range(0, 10):
-        assert (sa.L.mgl_debug_set(sa.h, KEY_BIG_WAVES, w) == 0) == (w in (1, 2, full)), w
+        assert (sa.L.mgl_debug_set(sa.h, binding.KEY.BIG_WAVES, w) == 0) == (w in (1, 2, full)), w
     sa.close()
 
 
@@ -59,7 +58,7 @@ def _four_engines(name, data, K, steps, start=None, **props):
                 costs.append(st["current_cost"])
                 second += st["second_pass_neighbours"]
                 if waves is not None:
-                    picks = max(picks, int(sa.debug_dump(10, np.uint32)[3]))  # the last step's repair picks
+                    picks = max(picks, int(sa.debug_dump(binding.DUMP.STEP_COUNTS)[0]["repair_picks"]))  # the last step's repair picks
             cur, cost = sa.current()
             print(f"{name} waves={waves}: second-pass neighbours {second}, most repair picks in a step {picks}, final cost {cost}")
             out[waves] = (costs, cost, rows(cur), second, picks)
@@ -124,7 +123,7 @@ def _long_lists_vs_oracle(waves, props, at_steps):
     data = corpus.lorem(3000)
     K, seed = 96, 5
     sa = binding.SA(data, accept="single", neighbours_per_step=K, seed=seed, iters_per_epoch=60, **props)
-    sa.debug_set(KEY_LIST_CAP, 16)  # first-pass lists of 16 events: most neighbours take the second pass
+    sa.debug_set(binding.KEY.LIST_CAP, 16)  # first-pass lists of 16 events: most neighbours take the second pass
     set_big_waves(sa, waves)
     done = second = 0
     for step in at_steps:

@@ -11,7 +11,6 @@ from megalania_amd import binding, corpus
 
 pytestmark = pytest.mark.gpu
 
-KEY_LIST_CAP = 2
 
 
 def rows(slab):
@@ -27,9 +26,9 @@ def liblzma_parse(data):
 def allocated_list_cap(sa):
     """the largest first-pass list capacity key 2 takes: the allocated one (capacities are multiples of 8)"""
     cap = 8
-    while sa.L.mgl_debug_set(sa.h, KEY_LIST_CAP, cap + 8) == 0:
+    while sa.L.mgl_debug_set(sa.h, binding.KEY.LIST_CAP, cap + 8) == 0:
         cap += 8
-    sa.debug_set(KEY_LIST_CAP, cap)
+    sa.debug_set(binding.KEY.LIST_CAP, cap)
     return cap
 
 
@@ -60,7 +59,7 @@ def _split_vs_fullwalk(name, data, K, steps, start, cap):
     sa = binding.SA(data, accept="single", neighbours_per_step=K)
     set_to = allocated_list_cap(sa)
     if cap:
-        sa.debug_set(KEY_LIST_CAP, cap)
+        sa.debug_set(binding.KEY.LIST_CAP, cap)
     costs, cost, slab, second, last = _steps(sa, steps, start)
     sa.close()
     print(f"{name} K={K} list capacity {cap or set_to}: second-pass neighbours {second} of {steps * K}, last-resort neighbours {last}, final cost {cost}")
@@ -121,10 +120,11 @@ def _epochs(data, K, steps, per_epoch, fullwalk, start):
         st = sa.run(1)
         out.append((st["current_cost"], st["best_cost"], st["accepted"], st["improved"]))
         if not fullwalk:
-            live = sa.debug_dump(10, np.uint32)
-            # the dump: [0..7] the finished step's counters ([4] has no user and stays zero), then, as [8..15], the live slots 0..7
-            # of the device's counter block, which the step's end must have cleared
-            assert len(live) == 16 and live[4] == 0 and not live[8:].any(), (s, live.tolist())
+            counts = sa.debug_dump(binding.DUMP.STEP_COUNTS)
+            last, live = counts[0], counts[1:]
+            # the dump: the finished step's counters (`unused4` has no user and stays zero), then the live ones of the device's
+            # counter block, which the step's end must have cleared
+            assert len(counts) == 2 and last["unused4"] == 0 and not live.view(np.uint32).any(), (s, counts)
     cur, cur_cost = sa.current()
     bst, best_cost = sa.best()
     sa.close()

@@ -126,13 +126,24 @@ def test_seeds_of_the_gpu_cluster_boundary_test(seed):
     assert o.bulk_cluster_overruns() == over0       # ... and none under the real rule
 
 
+def _header_enum_comments(header, name, prefix):
+    """{NAME: (value text, comment)} of `enum name` in the public header; a comment runs to the next enumerator"""
+    body = re.search(r"enum %s \{(.*?)\n\};" % name, header, re.S).group(1)
+    out = {}
+    for n, v, rest in re.findall(r"\b%s([A-Z0-9_]+) = (\(1u << \d+\)|[^,\s]+),?(.*?)(?=\n\t%s|\Z)" % (prefix, prefix), body, re.S):
+        out[n] = (v, " ".join(rest.replace("/*", " ").replace("*/", " ").replace(" * ", " ").split()))
+    return out
+
+
 def test_header_documents_the_limit_ids_of_key_6():
-    """include/megalania_hip.h lists every limit id mgl_debug_set key 6 takes, with the number csrc/mgl_base2.h gives it."""
+    """include/megalania_hip.h lists every limit id mgl_debug_set key 6 takes, with its number and what it limits, and the
+    give-up sites; csrc/mgl_base2.h uses the header's and defines none of its own."""
     base2 = open(os.path.join(ROOT, "megalania_amd", "csrc", "mgl_base2.h")).read()
     header = open(os.path.join(ROOT, "include", "megalania_hip.h")).read()
-    ids = {name: int(num) for name, num in re.findall(r"#define MGL_LIM_([A-Z_]+) (\d+)u", base2) if name != "COUNT"}
+    assert not re.search(r"#define MGL_(LIM|GU)_", base2) and "include/megalania_hip.h" in base2
+    lims = _header_enum_comments(header, "mgl_accept_limit", "MGL_LIM_")
+    ids = {name: int(v) for name, (v, _) in lims.items() if name != "COUNT"}
     assert len(ids) == 18 and sorted(ids.values()) == list(range(1, 19))
-    doc = " ".join(header[header.index("key 6 = id"):header.index("int mgl_debug_dump")].replace(" * ", " ").split())
     phrase = {"APPLY_EVENTS": "inserted / removed events of the accepted neighbour", "APPLY_GUARD": "iterations of its walk",
               "APPLY_SUB": "events of one context", "APPLY_SPAN": "rewritten chain entries of one context",
               "APPLY_PIECES": "pieces / checkpoint segments of one context", "APPLY_SHIFT": "entries a chain's tail may shift by in place",
@@ -143,7 +154,8 @@ def test_header_documents_the_limit_ids_of_key_6():
               "BATCH_RUNS": "runs on the checkpoint list", "SOFT_REACH": "1 / 0: clusters are split at the members' soft window ends"}
     assert set(phrase) == set(ids)
     for name, num in ids.items():
-        assert f" {num} = {phrase[name]}" in doc, (name, num)
-    assert "selector 84 one u32: the give-up sites of the in-place accepts" in " ".join(header.replace(" * ", " ").split())
-    sites = re.findall(r"#define MGL_GU_([A-Z_]+) \(1u << (\d+)\)", base2)
-    assert [int(b) for _, b in sites] == list(range(len(sites))) and len(sites) == 27
+        assert lims[name][1].startswith(phrase[name]), (name, num)
+    dumps = _header_enum_comments(header, "mgl_dump_selector", "MGL_DUMP_")
+    assert dumps["GIVEUP_SITES"][0] == "84" and dumps["GIVEUP_SITES"][1].startswith("one u32: the give-up sites of the in-place accepts")
+    sites = list(_header_enum_comments(header, "mgl_giveup_site", "MGL_GU_").values())
+    assert [v for v, _ in sites] == [f"(1u << {b})" for b in range(len(sites))] and len(sites) == 27

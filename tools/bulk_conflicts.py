@@ -34,8 +34,8 @@ if first > 1: sa.run(first - 1)
 for s in range(first, first + nsteps):
     cur = sa.current()[1]
     costs, _, _ = sa.neighbours(s - 1 + 0, want_diffs=False) if False else sa.neighbours(sa_step := (s - 1), want_diffs=False)
-    win = sa.debug_dump(21, np.uint32).reshape(-1, 2).astype(np.int64)
-    w2 = sa.debug_dump(22, np.uint32).astype(np.int64)
+    win = sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2).astype(np.int64)
+    w2 = sa.debug_dump(binding.DUMP.SOFT_ENDS).astype(np.int64)
     soft, dep = w2 & 0x7FFFFFFF, w2 >> 31
     ok = (costs != binding.INVALID_COST) & (costs < cur) & (win[:, 1] < 0xFFFFFFFE)
     idx = np.nonzero(ok)[0]

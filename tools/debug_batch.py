@@ -25,7 +25,7 @@ for s in range(steps):
     curf, costf = full.current()
     oc = o.cost_slab(cur.astype(literal_slab(1).dtype))["total"]
     same_slab = bool((cur == curf).all())
-    print(f"step {s}: accepted {st['accepted']}/{sf['accepted']} cost inc {cost} full {costf} oracle(inc slab) {oc} slab_same {same_slab} batch {inc.batch_counters()} hdr {inc.debug_dump(81, np.uint32)[:8]} acc {inc.debug_dump(82, np.int64)}", flush=True)
+    print(f"step {s}: accepted {st['accepted']}/{sf['accepted']} cost inc {cost} full {costf} oracle(inc slab) {oc} slab_same {same_slab} batch {inc.batch_counters()} hdr {inc.debug_dump(binding.DUMP.BATCH_HDR)[0]} acc {inc.debug_dump(binding.DUMP.BATCH_ACC)[0]}", flush=True)
     ref.set_slab(cur)
     a, b = canonical_base(inc, cur), canonical_base(ref, cur)
     for k in ("on", "sp"):

@@ -25,7 +25,7 @@ names = {1: "target + state_at", 2: "+ model_at (checkpoint + replay; split pick
 prev = 0.0
 stops = (4, 41, 42, 43, 0) if os.environ.get("MGL_SIM_ONLY") else (1, 2, 31, 32, 33, 34, 35, 36, 37, 39, 38, 3, 4, 41, 42, 43, 0)
 for stop in stops:
-    sa.L.mgl_debug_set(sa.h, 0, stop)
+    sa.L.mgl_debug_set(sa.h, binding.KEY.DIAG_STOP, stop)
     sa.run(2)
     st = sa.run(10)
     ms = st["gpu_ms_neighbours"] / 10

@@ -15,9 +15,9 @@ while done < 6000:
     p = sa.run(128); done += p["steps"]
     if p["bulk_steps"] == 0: break
 sa.set_accept_mode("single")
-base = sa.debug_dump(9, np.uint64).copy()
+base = sa.debug_dump(binding.DUMP.PHASE_CYCLES).copy()
 st = sa.run(16)
-p = sa.debug_dump(9, np.uint64)
+p = sa.debug_dump(binding.DUMP.PHASE_CYCLES)
 d = p[:32].astype(np.int64) - base[:32].astype(np.int64)
 names = ["state_at", "model_at", "top-K", "window walk", "chain_sim", "repair: model", "repair: overlay sim", "repair: top-K"]
 tot = float(d[:8].sum())

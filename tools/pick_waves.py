@@ -26,7 +26,7 @@ sa.run(8)
 
 
 def dump():
-    raw = sa.debug_dump(9, np.uint64)
+    raw = sa.debug_dump(binding.DUMP.PHASE_CYCLES)
     return raw[32 + K:64 + K].astype(np.float64), raw[64 + K:64 + 2 * K].copy()
 
 

@@ -14,10 +14,11 @@ sa.set_accept_mode("single")
 tot = np.zeros(4, dtype=np.int64)
 for s in range(20):
     sa.run(1)
-    tot += sa.debug_dump(10, np.uint32)[:4].astype(np.int64)
+    last = sa.debug_dump(binding.DUMP.STEP_COUNTS)[0]
+    tot += [int(last[f]) for f in ("second_pass", "last_resort", "spill_slots", "repair_picks")]
 print(cfg, "per step: second-pass list", tot[0] / 20, "last-resort list", tot[1] / 20, "spill slots", tot[2] / 20, "repair picks", tot[3] / 20)
 costs, nd, _ = sa.neighbours(10**6, want_diffs=False)
-win = sa.debug_dump(21, np.uint32).reshape(-1, 2)
+win = sa.debug_dump(binding.DUMP.WINDOWS).reshape(-1, 2)
 ok = costs != binding.INVALID_COST
 w = (win[ok, 1].astype(np.int64) - win[ok, 0].astype(np.int64))
 print("window bytes: mean %.0f p50 %.0f p90 %.0f p99 %.0f max %d" % (w.mean(), np.percentile(w, 50), np.percentile(w, 90), np.percentile(w, 99), w.max()))

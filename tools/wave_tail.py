@@ -19,7 +19,7 @@ sa.run(8)
 rows = []
 for rep in range(8):
     st = sa.run(1)
-    raw = sa.debug_dump(9, np.uint64)[32:32 + K].copy()
+    raw = sa.debug_dump(binding.DUMP.PHASE_CYCLES)[32:32 + K].copy()
     life = (raw & np.uint64(0xFFFFFFFFFF)).astype(np.float64)
     ev = ((raw >> np.uint64(40)) & np.uint64(0xFFF)).astype(np.int64)
     pk = ((raw >> np.uint64(52)) & np.uint64(0xFFF)).astype(np.int64)
