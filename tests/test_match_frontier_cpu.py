@@ -152,7 +152,9 @@ def test_a_budget_only_cuts_lists_short(name, data, dict_limit):
 
 def test_the_small_inputs_reach_every_path_of_the_scan():
     """what tests/test_gpu_match_frontier.py relies on: `runs` has a list of 49 entries and a position that examines 692
-    run entries (more than ten trips of a 64-lane wavefront), and the ELF slice has lists that a depth of 64 cuts short"""
+    run entries (more than ten trips of a 64-lane wavefront), and the ELF slice has lists that a depth of 64 cuts short.
+    What no natural input reaches (a list of 60, a budget that ends on a trip's edge, a source on the window's edge) is
+    planted: tests/_planted_frontier.py, tests/test_frontier_planted_cpu.py"""
     used = []
     full = frontier_rule(SMALL[3][1], 4096, stats=used)
     assert max(len(f) for f in full) == 49 and max(used) == 692
