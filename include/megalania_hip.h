@@ -34,6 +34,9 @@
  *   mgl_sa_set_focus, mgl_sa_focus, mgl_focus_slice
  *                     no reference counterpart (packet_slab_neighbour.c:162-163 draws its target over the whole slab): a
  *                                    step's targets confined to a byte window, and the rule that hands every chain its slice
+ *   mgl_sa_set_target_weights, mgl_sa_weight_targets_by_cost, mgl_sa_target_weights, mgl_weight_value
+ *                     no reference counterpart: a step's targets drawn in proportion to a weight per input byte, the
+ *                                    weights the caller's or the cost map of a slab
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -351,6 +354,35 @@ int mgl_sa_focus(mgl_sa* sa, uint64_t* lo, uint64_t* hi, uint64_t* packets);
  * a slice further down, so that no boundary stays where it was.  In every round the slices tile [0, n) without overlap and
  * none is empty.  MGL_EINVAL: world == 0, rank >= world, n < 2 world. */
 int mgl_focus_slice(uint64_t n, uint32_t world, uint32_t rank, uint64_t round, uint64_t* lo, uint64_t* hi);
+/* Target weights, the soft form of the focus window (no reference counterpart; DESIGN.md sections 4 and 10,
+ * megalania_amd/csrc/mgl_weights.hip).  While weights are set, the K neighbours of a step take their targets in proportion to a
+ * weight per input byte.  All of it is exact integer arithmetic:
+ *   - w[x], one uint32 per byte, S[x] = the sum of w below x (uint64); [lo, hi) = the focus window in force, [0, n) without one;
+ *     W = S[hi] - S[lo].  W == 0: the step's targets are those of the rule without weights (under the window, if one is set).
+ *   - Neighbour j draws v = a + (b > a ? u % (b - a) : 0) from slice [a, b) = [j W / K, (j + 1) W / K) of W, with
+ *     u = draw 0 << 31 | draw 0xFFFFFFFF of its stream (62 bits: a slice can be wider than one draw; mgl_weight_value).
+ *   - x is the byte of [lo, hi) with S[x] - S[lo] <= v < S[x + 1] - S[lo]; a byte of weight 0 is never drawn.
+ *   - The target is the start of the packet that covers x on the current walk.  Under a window that start may lie below lo:
+ *     then the first packet start inside [lo, hi) is the target, or, if the window holds none, the packet that covers lo (the
+ *     focus window's own empty case).  So a search under a window still leaves every slab entry below lo untouched.
+ * Being byte positions, the weights keep their meaning while the walk changes: they stay set across mgl_sa_run,
+ * mgl_sa_begin_epoch, mgl_sa_set_slab, the seeds and the exchanges until they are replaced or cleared, and mgl_neighbours
+ * honours them like mgl_sa_run, on both engines.  Slab, costs, RNG streams, MGL_ACCEPT_AUTO's block, the focus window and
+ * mgl_sa_stats are untouched by setting or clearing them.  Device memory: 4 n + n / 8 bytes, the handle's while weights are set
+ * (a prefix sum per 64 bytes, made once per call, never per step).
+ * NULL clears.  MGL_EINVAL, handle and weights in force unchanged: sum >= 2^44, a handle created with MGL_F_POSITION_TARGETS.
+ * MGL_ENOMEM, handle usable, no weights in force afterwards: the buffers (4 n + n / 8 bytes) do not fit. */
+int mgl_sa_set_target_weights(mgl_sa* sa, const uint32_t* weights /* n entries */);
+/* weights := cost map of `packets` (NULL: the current slab) under the handle's lc/lp/pb, + floor per byte; a slab that
+ * mgl_cost_map refuses is refused with its code and the weights in force stay.  total (nullable) = map total + floor * n.
+ * The map never leaves the device.  MGL_EINVAL also for floor > 2^32 - 1 - 2^20 (an entry would not fit) and a total >= 2^44;
+ * MGL_ENOMEM from the map's own buffers (8 n bytes for the length of the call) leaves the weights in force as they were.
+ * gpu_ms (nullable): device time of the map's two kernels. */
+int mgl_sa_weight_targets_by_cost(mgl_sa* sa, const mgl_packet* packets, uint32_t floor, uint64_t* total, double* gpu_ms);
+/* parity hook: weights_out (n entries, nullable), *total = S[n], *window = W under the focus in force; all 0 when none are set */
+int mgl_sa_target_weights(mgl_sa* sa, uint32_t* weights_out, uint64_t* total, uint64_t* window);
+/* host arithmetic only, no device: the value v neighbour j draws.  MGL_EINVAL: W == 0, W >= 2^44, K == 0, K > 2^20, j >= K, v NULL */
+int mgl_weight_value(uint64_t W, uint32_t K, uint32_t j, uint64_t seed, uint64_t step, uint64_t* v);
 /* Adopt a best slab found elsewhere (another chain / GPU): replaces best slab and best cost.
  * `perplexity` must be the slab's exact cost: the slab is walked on the device at once, which refuses (MGL_EINVAL, nothing
  * adopted) an entry that is no packet or does not fit, and a cost other than `perplexity`.  That walk does not look at the

@@ -42,6 +42,7 @@ HIP_SYMBOLS = [
     "mgl_crossover", "mgl_sa_cross_best", "mgl_sa_exchange_cross",
     "mgl_comm_allgather_u64", "mgl_slab_hash", "mgl_sa_exchange_cross_all",
     "mgl_sa_set_focus", "mgl_sa_focus", "mgl_focus_slice", "mgl_cost_map",
+    "mgl_sa_set_target_weights", "mgl_sa_weight_targets_by_cost", "mgl_sa_target_weights", "mgl_weight_value",
 ]
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
@@ -321,6 +322,10 @@ def hip_lib():
         L.mgl_focus_slice.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64)]
         L.mgl_cost_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Properties), C.c_void_p, C.POINTER(CostReport)]
+        L.mgl_sa_set_target_weights.argtypes = [C.c_void_p, C.c_void_p]
+        L.mgl_sa_weight_targets_by_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.mgl_sa_target_weights.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mgl_weight_value.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -373,6 +378,18 @@ def focus_slice(n: int, world: int, rank: int, round: int):
     if rc != 0:
         raise MglError(f"rc={rc}: {L.mgl_last_error().decode()}", rc=rc)
     return lo.value, hi.value
+
+
+def weight_value(W: int, K: int, j: int, seed: int, step: int) -> int:
+    """The value neighbour j of K draws from a window of weight W in step `step` under target weights (mgl_weight_value; no
+    device needed): uniform in slice [j W / K, (j + 1) W / K).  Raises MglError (rc -1) for W == 0, W >= 2^44, K == 0,
+    K > 2^20, j >= K."""
+    L = hip_lib()
+    v = C.c_uint64(0)
+    rc = L.mgl_weight_value(W, K, j, seed, step, C.byref(v))
+    if rc != 0:
+        raise MglError(f"rc={rc}: {L.mgl_last_error().decode()}", rc=rc)
+    return v.value
 
 
 def emit_stream(data: bytes, slab: np.ndarray, lc=0, lp=0, pb=0) -> bytes:
@@ -540,6 +557,34 @@ class SA:
         lo, hi, pk = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._chk(self.L.mgl_sa_focus(self.h, C.byref(lo), C.byref(hi), C.byref(pk)))
         return lo.value, hi.value, pk.value
+
+    def set_target_weights(self, weights):
+        """The step's K targets in proportion to weights[x], one uint32 per input byte (mgl_sa_set_target_weights); None clears.
+        Composes with the focus window; a window that weighs 0 falls back on the rule without weights.  Stays until changed."""
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.uint32)
+            if len(weights) != self.n:
+                raise MglError("set_target_weights: one weight per input byte", rc=-1)
+        self._chk(self.L.mgl_sa_set_target_weights(self.h, _ptr(weights)))
+
+    def weight_targets_by_cost(self, floor=0, slab=None):
+        """weights := the cost map of `slab` (None: the current slab) under the handle's lc/lp/pb, plus `floor` per byte, made on
+        the device (mgl_sa_weight_targets_by_cost).  Returns (total, gpu_ms): the map's total + floor * n and the map's device
+        time."""
+        if slab is not None:
+            slab = np.ascontiguousarray(slab, dtype=PACKET)
+            if len(slab) != self.n:
+                raise MglError("weight_targets_by_cost: the slab must have one entry per input byte", rc=-1)
+        total, ms = C.c_uint64(0), C.c_double(0)
+        self._chk(self.L.mgl_sa_weight_targets_by_cost(self.h, _ptr(slab), floor, C.byref(total), C.byref(ms)))
+        return total.value, ms.value
+
+    def target_weights(self):
+        """(uint32 weights, total, window): the weights in force (all 0: none), S[n], and W under the focus window in force"""
+        out = np.zeros(self.n, dtype=np.uint32)
+        total, window = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.L.mgl_sa_target_weights(self.h, _ptr(out), C.byref(total), C.byref(window)))
+        return out, total.value, window.value
 
     def step_modes(self) -> np.ndarray:
         """per step of the last run(): 0 single, 1 bulk"""

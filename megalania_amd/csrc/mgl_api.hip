@@ -16,6 +16,7 @@
 #include "mgl_props.hip"
 #include "mgl_costmap.hip"
 #include "mgl_crossover.hip"
+#include "mgl_weights.hip"
 #include "../../include/megalania_hip.h"
 #include "mgl_owner.h"
 
@@ -235,6 +236,13 @@ struct mgl_sa {
 	uint32_t* d_strat_pre = nullptr; /* stratified targets: packets before every block of 4 096 positions */
 	uint32_t focus_lo = 0, focus_hi = 0; /* mgl_sa_set_focus: the targets' byte window, hi = 0: none; handed to k_targets by every launch */
 	uint32_t* d_focus_cnt = nullptr; /* two words for mgl_sa_focus: first ordinal, packets */
+	/* mgl_sa_set_target_weights / mgl_sa_weight_targets_by_cost (mgl_weights.hip): n weights, their cell prefixes (cells + 1), and the
+	 * block totals of the scan with two words behind them for S[lo] and W.  All null: no weights.  wt_slo, wt_window: S[lo] and W of
+	 * the focus window in force, read back whenever weights or window change; handed to k_targets_weighted by every launch */
+	uint32_t* d_wt = nullptr;
+	uint64_t* d_wt_pre = nullptr;
+	uint64_t* d_wt_blk = nullptr;
+	uint64_t wt_total = 0, wt_slo = 0, wt_window = 0;
 	/* made with the targets (launch_targets), for the fused launch: K bytes, 1 = the neighbour will pick, 0 = grow/shrink; and
 	 * K neighbour indices, every slice's picking neighbours in front of its others (k_pick_order).  Null: MGL_NO_ORDER=1,
 	 * position targets, no split form */
@@ -494,10 +502,16 @@ static void launch_targets(mgl_sa* sa, hipStream_t st, uint64_t step_override)
 	const uint32_t K = sa->cfg.neighbours_per_step;
 	const uint64_t* onwalk = sa->incremental ? sa->b2.onwalk : sa->base.v.onwalk;
 	const uint32_t nw0 = sa->incremental ? sa->b2.nw0 : (sa->ctx.n + 63u) >> 6;
-	hipLaunchKernelGGL(k_rank_blocks, dim3(sa->ctx.strat_nblk), dim3(64), 0, st, onwalk, nw0, sa->d_strat_pre, sa->ctx.strat_nblk);
-	hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, st, sa->d_strat_pre, sa->ctx.strat_nblk);
-	hipLaunchKernelGGL(sa->focus_hi ? k_targets<true> : k_targets<false>, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, sa->b2, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->d_strat_tgt,
-	                   sa->d_pick_hint, sa->focus_lo, sa->focus_hi);
+	if (sa->d_wt && sa->wt_window) { /* weights in force and the window weighs something: the weighted rule (mgl_weights.hip), which counts no packets */
+		hipLaunchKernelGGL(k_targets_weighted, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, sa->b2, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K,
+		                   sa->d_strat_tgt, sa->d_pick_hint, sa->focus_lo, sa->focus_hi ? sa->focus_hi : sa->n, (const uint32_t*)sa->d_wt, (const uint64_t*)sa->d_wt_pre,
+		                   sa->wt_slo, sa->wt_window);
+	} else {
+		hipLaunchKernelGGL(k_rank_blocks, dim3(sa->ctx.strat_nblk), dim3(64), 0, st, onwalk, nw0, sa->d_strat_pre, sa->ctx.strat_nblk);
+		hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, st, sa->d_strat_pre, sa->ctx.strat_nblk);
+		hipLaunchKernelGGL(sa->focus_hi ? k_targets<true> : k_targets<false>, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, sa->b2, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K, sa->d_strat_tgt,
+		                   sa->d_pick_hint, sa->focus_lo, sa->focus_hi);
+	}
 	if (sa->d_pick_order) {
 		const uint32_t slices = nbr_slices(sa);
 		hipLaunchKernelGGL(k_pick_order, dim3(slices), dim3(1024), 0, st, (const unsigned char*)sa->d_pick_hint, sa->d_pick_order, K, slices);
@@ -1885,7 +1899,9 @@ extern "C" int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_thresh
 	sa->autoacc.reset();
 	return MGL_OK;
 }
-/* The focus window: host state only.  Targets that were queued ahead under the old window are made again. */
+static int weights_window(mgl_sa* sa);
+/* The focus window: host state only (with target weights in force, also what the window weighs).  Targets that were queued ahead
+ * under the old window are made again. */
 extern "C" int mgl_sa_set_focus(mgl_sa* sa, uint64_t lo, uint64_t hi)
 {
 	if (!sa) return fail(MGL_EINVAL, "null handle");
@@ -1893,6 +1909,10 @@ extern "C" int mgl_sa_set_focus(mgl_sa* sa, uint64_t lo, uint64_t hi)
 	if (hi > sa->n || (lo >= hi && (lo | hi) != 0)) return fail(MGL_EINVAL, "mgl_sa_set_focus: the window must be 0, 0 or lo < hi <= n");
 	sa->focus_lo = (uint32_t)lo; sa->focus_hi = (uint32_t)hi;
 	if (sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE;
+	if (sa->d_wt) { /* target weights in force: what the new window weighs (weights_window, below) */
+		HIPCHK(hipSetDevice(sa->device));
+		return weights_window(sa);
+	}
 	return MGL_OK;
 }
 extern "C" int mgl_sa_focus(mgl_sa* sa, uint64_t* lo, uint64_t* hi, uint64_t* packets)
@@ -2376,30 +2396,18 @@ extern "C" int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_
 	return MGL_OK;
 }
 
-/* Where a parse spends its bits (mgl_costmap.hip).  Validity as in mgl_props_sweep: the walk of mgl_cost_slab decides it for a
- * caller's slab, and the current slab is read where it lies.  The call's two buffers -- a mark and a map entry per position,
- * 8 bytes per input byte -- are its own and die with it. */
-extern "C" int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_properties* props, uint32_t* map_out, mgl_cost_report* report)
+/* the two kernels of the cost map over a valid slab that lies on the device; the map stays in tmp.map, on the device, for as
+ * long as the caller keeps `tmp` (mgl_cost_map copies it out, mgl_sa_weight_targets_by_cost makes weights of it there) */
+struct CostMapBufs {
+	DevOwner own;
+	uint32_t *mark = nullptr, *map = nullptr;
+	CostMapSums* sums = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+};
+static int cost_map_device(mgl_sa* sa, const mgl_pk* slab, const mgl_properties& pr, CostMapBufs& tmp, CostMapSums* sums, float* ms)
 {
-	static_assert(MGL_CC_CLASSES == MGL_CM_CLASSES, "header and kernel disagree on the number of classes");
 	static const char* nomem = "mgl_cost_map: the per-position buffers do not fit the device";
-	if (!sa) return fail(MGL_EINVAL, "null handle");
-	const mgl_properties pr = props ? *props : sa->props;
-	if ((uint32_t)pr.lc + pr.lp > 4u || pr.pb > 4u) return fail(MGL_EINVAL, "mgl_cost_map: supported properties are lc + lp <= 4, pb <= 4");
-	HIPCHK(hipSetDevice(sa->device));
-	const mgl_pk* slab = sa->base.v.slab;
-	if (packets) {
-		Control c;
-		int rc = scratch_walk(sa, packets, false, false, &c);
-		if (rc) return rc;
-		slab = sa->scratch.v.slab;
-	}
-	struct Tmp {
-		DevOwner own;
-		uint32_t *mark = nullptr, *map = nullptr;
-		CostMapSums* sums = nullptr;
-		hipEvent_t t0 = nullptr, t1 = nullptr;
-	} tmp;
+	CostMapSums& h = *sums;
 	const size_t n = sa->n;
 	if (sa->force.cm_nomem) { sa->force.cm_nomem--; return fail(MGL_ENOMEM, nomem); }
 	TRY(dnew(tmp.own, tmp.mark, n, -1, nomem));
@@ -2415,19 +2423,158 @@ extern "C" int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_pro
 	hipLaunchKernelGGL(k_costmap_spread, dim3((sa->n + 255u) / 256u), dim3(256), 0, s, sa->n, (const uint32_t*)tmp.mark, tmp.map);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(tmp.t1, s));
-	CostMapSums h;
 	HIPCHK(hipMemcpyAsync(&h, tmp.sums, sizeof h, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	if (h.end_pos != sa->n) return fail(MGL_EDEVICE, "mgl_cost_map: the walk stopped inside the slab (device consistency check)");
+	HIPCHK(hipEventElapsedTime(ms, tmp.t0, tmp.t1));
+	return MGL_OK;
+}
+/* Where a parse spends its bits (mgl_costmap.hip).  Validity as in mgl_props_sweep: the walk of mgl_cost_slab decides it for a
+ * caller's slab, and the current slab is read where it lies.  The call's two buffers -- a mark and a map entry per position,
+ * 8 bytes per input byte -- are its own and die with it. */
+extern "C" int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_properties* props, uint32_t* map_out, mgl_cost_report* report)
+{
+	static_assert(MGL_CC_CLASSES == MGL_CM_CLASSES, "header and kernel disagree on the number of classes");
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	const mgl_properties pr = props ? *props : sa->props;
+	if ((uint32_t)pr.lc + pr.lp > 4u || pr.pb > 4u) return fail(MGL_EINVAL, "mgl_cost_map: supported properties are lc + lp <= 4, pb <= 4");
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* slab = sa->base.v.slab;
+	if (packets) {
+		Control c;
+		int rc = scratch_walk(sa, packets, false, false, &c);
+		if (rc) return rc;
+		slab = sa->scratch.v.slab;
+	}
+	CostMapBufs tmp;
+	CostMapSums h;
+	float ms = 0;
+	TRY(cost_map_device(sa, slab, pr, tmp, &h, &ms));
+	const size_t n = sa->n;
 	if (map_out) HIPCHK(hipMemcpy(map_out, tmp.map, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
 	if (report) {
-		float ms = 0;
-		HIPCHK(hipEventElapsedTime(&ms, tmp.t0, tmp.t1));
 		report->total = h.total; report->packets = h.packets;
 		for (uint32_t k = 0; k < MGL_CC_CLASSES; k++) { report->class_cost[k] = h.class_cost[k]; report->class_bits[k] = h.class_bits[k]; }
 		for (uint32_t t = 0; t < 4; t++) { report->type_cost[t] = h.type_cost[t]; report->type_packets[t] = h.type_packets[t]; report->type_bytes[t] = h.type_bytes[t]; }
 		report->gpu_ms = ms;
 	}
+	return MGL_OK;
+}
+
+/* ---- cost-weighted targets (mgl_weights.hip) */
+static void weights_release(mgl_sa* sa)
+{
+	sa->own.release(sa->d_wt); sa->own.release(sa->d_wt_pre); sa->own.release(sa->d_wt_blk);
+	sa->d_wt = nullptr; sa->d_wt_pre = nullptr; sa->d_wt_blk = nullptr;
+	sa->wt_total = sa->wt_slo = sa->wt_window = 0;
+	if (sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE;
+}
+/* the handle's three buffers, kept from one set to the next; one that does not fit leaves the handle without weights */
+static int weights_alloc(mgl_sa* sa)
+{
+	static const char* nomem = "target weights: the buffers (4 n + n / 8 bytes) do not fit the device";
+	if (sa->d_wt) return MGL_OK;
+	int rc = dnew(sa->own, sa->d_wt, sa->n, -1, nomem);
+	if (!rc) rc = dnew(sa->own, sa->d_wt_pre, (size_t)wt_cells(sa->n) + 1u, -1, nomem);
+	if (!rc) rc = dnew(sa->own, sa->d_wt_blk, (size_t)wt_blocks(sa->n) + 2u, -1, nomem);
+	if (rc) weights_release(sa);
+	return rc;
+}
+/* S[lo] and W of the focus window in force, read back: one wavefront and one synchronisation per change of weights or window,
+ * none per step */
+static int weights_window(mgl_sa* sa)
+{
+	if (!sa->d_wt) return MGL_OK;
+	hipStream_t st = sa->q.stream;
+	uint64_t* out = sa->d_wt_blk + wt_blocks(sa->n);
+	hipLaunchKernelGGL(k_wt_window, dim3(1), dim3(64), 0, st, (const uint32_t*)sa->d_wt, (const uint64_t*)sa->d_wt_pre, sa->n, sa->focus_lo, sa->focus_hi ? sa->focus_hi : sa->n, out);
+	HIPCHK(hipGetLastError());
+	uint64_t v[2] = { 0, 0 };
+	HIPCHK(hipMemcpyAsync(v, out, sizeof v, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	sa->wt_slo = v[0]; sa->wt_window = v[1];
+	return MGL_OK;
+}
+/* the prefix structure over the weights in d_wt (the four launches of mgl_weights.hip), then the window.  Targets queued ahead
+ * were made under the old weights, and may still be reading them: the second stream is waited for before this is called. */
+static int weights_commit(mgl_sa* sa, uint64_t total)
+{
+	hipStream_t st = sa->q.stream;
+	const uint32_t n = sa->n, ncell = wt_cells(n), nblk = wt_blocks(n);
+	hipLaunchKernelGGL(k_wt_cells, dim3((ncell + 3u) / 4u), dim3(256), 0, st, (const uint32_t*)sa->d_wt, n, sa->d_wt_pre, ncell);
+	hipLaunchKernelGGL(k_wt_blocks, dim3(nblk), dim3(64), 0, st, sa->d_wt_pre, ncell, sa->d_wt_blk);
+	hipLaunchKernelGGL(k_wt_scan, dim3(1), dim3(64), 0, st, sa->d_wt_blk, nblk, sa->d_wt_pre, ncell);
+	hipLaunchKernelGGL(k_wt_add, dim3((ncell + 255u) / 256u), dim3(256), 0, st, sa->d_wt_pre, ncell, (const uint64_t*)sa->d_wt_blk);
+	HIPCHK(hipGetLastError());
+	sa->wt_total = total;
+	if (sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE;
+	return weights_window(sa);
+}
+static int weights_refuse(const mgl_sa* sa, const char* who)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	if (!sa->d_strat_pre) return fail(MGL_EINVAL, std::string(who) + ": position targets (MGL_F_POSITION_TARGETS) take no weights");
+	return MGL_OK;
+}
+extern "C" int mgl_sa_set_target_weights(mgl_sa* sa, const uint32_t* weights)
+{
+	TRY(weights_refuse(sa, "mgl_sa_set_target_weights"));
+	uint64_t total = 0;
+	if (weights) {
+		for (size_t x = 0; x < sa->n; x++) total += weights[x]; /* n < 2^28 entries below 2^32: no carry */
+		if (total >= MGL_WT_MAX_TOTAL) return fail(MGL_EINVAL, "mgl_sa_set_target_weights: the weights must sum to less than 2^44");
+	}
+	HIPCHK(hipSetDevice(sa->device));
+	HIPCHK(hipStreamSynchronize(sa->q.stream2));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	if (!weights) { weights_release(sa); return MGL_OK; }
+	TRY(weights_alloc(sa));
+	HIPCHK(hipMemcpyAsync(sa->d_wt, weights, sizeof(uint32_t) * (size_t)sa->n, hipMemcpyHostToDevice, sa->q.stream));
+	return weights_commit(sa, total);
+}
+extern "C" int mgl_sa_weight_targets_by_cost(mgl_sa* sa, const mgl_packet* packets, uint32_t floor, uint64_t* total, double* gpu_ms)
+{
+	TRY(weights_refuse(sa, "mgl_sa_weight_targets_by_cost"));
+	if (floor > 0xFFFFFFFFu - (1u << MGL_CM_COST_BITS)) return fail(MGL_EINVAL, "mgl_sa_weight_targets_by_cost: floor + a map entry must fit 32 bits");
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* slab = sa->base.v.slab;
+	if (packets) {
+		Control c;
+		TRY(scratch_walk(sa, packets, false, false, &c));
+		slab = sa->scratch.v.slab;
+	}
+	CostMapBufs tmp;
+	CostMapSums h;
+	float ms = 0;
+	TRY(cost_map_device(sa, slab, sa->props, tmp, &h, &ms)); /* MGL_ENOMEM here: the weights in force stay */
+	const uint64_t sum = h.total + (uint64_t)floor * sa->n; /* below 2^20 n + 2^32 n < 2^61 */
+	if (sum >= MGL_WT_MAX_TOTAL) return fail(MGL_EINVAL, "mgl_sa_weight_targets_by_cost: the weights must sum to less than 2^44");
+	HIPCHK(hipStreamSynchronize(sa->q.stream2));
+	TRY(weights_alloc(sa));
+	hipLaunchKernelGGL(k_wt_from_map, dim3((sa->n + 255u) / 256u), dim3(256), 0, sa->q.stream, sa->n, (const uint32_t*)tmp.map, floor, sa->d_wt);
+	HIPCHK(hipGetLastError());
+	TRY(weights_commit(sa, sum)); /* synchronises: the map is read before `tmp` dies */
+	if (total) *total = sum;
+	if (gpu_ms) *gpu_ms = ms;
+	return MGL_OK;
+}
+extern "C" int mgl_sa_target_weights(mgl_sa* sa, uint32_t* weights_out, uint64_t* total, uint64_t* window)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	if (total) *total = sa->wt_total;
+	if (window) *window = sa->wt_window;
+	if (!weights_out) return MGL_OK;
+	if (!sa->d_wt) { memset(weights_out, 0, sizeof(uint32_t) * (size_t)sa->n); return MGL_OK; }
+	HIPCHK(hipSetDevice(sa->device));
+	HIPCHK(hipMemcpyAsync(weights_out, sa->d_wt, sizeof(uint32_t) * (size_t)sa->n, hipMemcpyDeviceToHost, sa->q.stream));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	return MGL_OK;
+}
+extern "C" int mgl_weight_value(uint64_t W, uint32_t K, uint32_t j, uint64_t seed, uint64_t step, uint64_t* v)
+{
+	if (!v) return fail(MGL_EINVAL, "null argument");
+	if (W == 0 || W >= MGL_WT_MAX_TOTAL || K == 0 || K > MGL_WT_MAX_K || j >= K) return fail(MGL_EINVAL, "mgl_weight_value: needs 0 < W < 2^44 and j < K <= 2^20");
+	*v = weight_value(W, K, j, mgl_rng_key(seed, step, j));
 	return MGL_OK;
 }
 

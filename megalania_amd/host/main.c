@@ -91,6 +91,13 @@ static const char usage_options[] =
 	"               stream whose input changed only there.  --focus rank (needs --chains N, N >= 2): before every epoch chain\n"
 	"               R takes slice R of N of the input (mgl_focus_slice), shifted by half a slice every other epoch, so that\n"
 	"               chains that leave an exchange with a common slab work on different stretches of it\n"
+	"  --target-weights cost[:mean|:N] | file:PATH  the search draws a step's targets in proportion to a weight per input byte\n"
+	"               (mgl_sa_set_target_weights) instead of uniformly by packet; with --focus, inside the window.  cost: before\n"
+	"               every epoch's run the weights become the cost map of the slab the epoch starts from plus a floor per byte,\n"
+	"               made on the device: cost:mean (= cost) adds the mean cost of a byte, so that half the weight is uniform by\n"
+	"               byte and no stretch starves, cost:N adds N, cost:0 is the pure map.  file:PATH: one little-endian u32 per\n"
+	"               input byte, the format --cost-map writes (with --filter x86 per filtered byte), set once for the whole run;\n"
+	"               a file of another size is an error and nothing is written.  With --chains every chain has its own weights\n"
 	"  --cost-map FILE  where the emitted parse spends its bits (mgl_cost_map, under the run's final lc/lp/pb): FILE gets one\n"
 	"               little-endian u32 per input byte, the byte's share of its packet's exact cost (2048 per bit); the values\n"
 	"               sum to the parse's cost.  With --filter x86 the positions are those of the filtered bytes.  The emitted\n"
@@ -114,6 +121,7 @@ static void usage(const char* argv0)
 	        "          [--seed-stream file.lzma|file.xz [--clip-window]]\n"
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]\n"
 	        "          [--exchange best|cross|cross-all [--cross-grain N]]] [--focus LO:HI|rank]\n"
+	        "          [--target-weights cost[:mean|:N]|file:PATH]\n"
 	        "          [--cost-map FILE] [--cost-report] [--cost-bucket B] filename\n", argv0);
 	fputs(usage_options, stderr);
 }
@@ -125,6 +133,7 @@ typedef struct { uint32_t passes; bool adaptive; int finder; uint32_t mf_depth; 
 
 enum { FILTER_NONE, FILTER_X86, FILTER_AUTO };          /* in the order of --filter's words */
 enum { EXCHANGE_BEST, EXCHANGE_CROSS, EXCHANGE_ALL };   /* in the order of --exchange's words */
+enum { WEIGHTS_NONE, WEIGHTS_COST_MEAN, WEIGHTS_COST_FLOOR, WEIGHTS_FILE }; /* --target-weights */
 #define JOINT_MAX 4 /* --props-joint's candidates */
 
 /* everything the command line says, grouped as the usage text groups it */
@@ -152,9 +161,12 @@ typedef struct {
 	uint32_t exchange, cross_grain;
 	unsigned long long comm_nonce;
 	bool transport_shm, cross_grain_given;
-	/* focus, cost map */
+	/* focus, target weights, cost map */
 	unsigned long long focus_lo, focus_hi, cost_bucket;
 	bool focus_given, focus_rank, cost_report;
+	unsigned weights; /* WEIGHTS_* */
+	uint32_t weights_floor;
+	const char* weights_path;
 	/* files */
 	const char *filename, *out_path, *save_path, *load_path, *seed_stream_path, *comm_path, *cost_map_path;
 } cli_opts;
@@ -202,7 +214,24 @@ static const char* parse_focus(const char* v, cli_opts* o)
 	return NULL;
 }
 
-/* The last of a repeated option wins (--focus refuses a repeat), the last non-option argument is the file name. */
+/* --target-weights cost[:mean|:N] | file:PATH: the reason for a refusal, NULL for none */
+static const char* parse_target_weights(const char* v, cli_opts* o)
+{
+	static const char* const malformed = "--target-weights takes cost, cost:mean, cost:N (N from 0 to 4293918719) or file:PATH";
+	unsigned long long n = 0;
+	if (o->weights != WEIGHTS_NONE) return "--target-weights given twice";
+	if (!strcmp(v, "cost") || !strcmp(v, "cost:mean")) o->weights = WEIGHTS_COST_MEAN;
+	else if (!strncmp(v, "cost:", 5) && v[5] >= '0' && v[5] <= '9' && number(v + 5, &n) && n <= 0xFFFFFFFFull - (1u << 20)) {
+		o->weights = WEIGHTS_COST_FLOOR; /* a map entry is below 2^20: entry + N fits 32 bits */
+		o->weights_floor = (uint32_t)n;
+	} else if (!strncmp(v, "file:", 5) && v[5]) {
+		o->weights = WEIGHTS_FILE;
+		o->weights_path = v + 5;
+	} else return malformed;
+	return NULL;
+}
+
+/* The last of a repeated option wins (--focus and --target-weights refuse a repeat), the last non-option argument is the file name. */
 static int parse_args(int argc, char** argv, cli_opts* o)
 {
 	/* the reference's seed (main.c:68), top K (:49), props 0/0/0 (:45) and schedule (:66,69) */
@@ -260,6 +289,7 @@ static int parse_args(int argc, char** argv, cli_opts* o)
 		else if (!strcmp(a, "--exchange")) { bad = (w = word(v, "best", "cross", "cross-all")) < 0; o->exchange = w; }
 		else if (!strcmp(a, "--cross-grain")) { o->cross_grain = (uint32_t)strtoul(v, NULL, 0); o->cross_grain_given = true; }
 		else if (!strcmp(a, "--focus")) why = parse_focus(v, o);
+		else if (!strcmp(a, "--target-weights")) why = parse_target_weights(v, o);
 		else if (!strcmp(a, "--cost-map")) o->cost_map_path = v;
 		else if (!strcmp(a, "--cost-bucket")) { if (!number(v, &o->cost_bucket) || !o->cost_bucket) why = "--cost-bucket takes a number of bytes, at least 1"; }
 		else bad = true;
@@ -844,6 +874,43 @@ static int focus_slice(cli_run* r, uint64_t round)
 	return 0;
 }
 
+/* --target-weights file:PATH holds for the whole run: n little-endian u32, what --cost-map writes */
+static int load_target_weights(cli_run* r)
+{
+	const cli_opts* o = r->o;
+	const size_t n = r->file_size;
+	if (o->weights != WEIGHTS_FILE) return 0;
+	FILE* f = fopen(o->weights_path, "rb");
+	if (!f) return fail("could not open %s", o->weights_path);
+	uint32_t* w = (uint32_t*)malloc(sizeof(uint32_t) * n);
+	uint8_t le[4], extra;
+	bool ok = w != NULL;
+	size_t p = 0;
+	for (; ok && p < n && fread(le, 4, 1, f) == 1; p++) w[p] = (uint32_t)le[0] | (uint32_t)le[1] << 8 | (uint32_t)le[2] << 16 | (uint32_t)le[3] << 24;
+	const bool fits = ok && p == n && fread(&extra, 1, 1, f) == 0;
+	fclose(f);
+	if (!w) return fail("out of memory");
+	if (!fits) { free(w); return fail("%s does not hold %zu weights of 4 bytes, one per input byte", o->weights_path, n); }
+	const int rc = mgl_sa_set_target_weights(r->sa, w);
+	free(w);
+	return rc != MGL_OK ? lib_error() : 0;
+}
+
+/* --target-weights cost: the weights of the epoch that is about to run, from the slab it starts from */
+static int weigh_by_cost(cli_run* r)
+{
+	const cli_opts* o = r->o;
+	uint64_t cost = 0, total = 0;
+	double ms = 0;
+	if (o->weights != WEIGHTS_COST_MEAN && o->weights != WEIGHTS_COST_FLOOR) return 0;
+	/* the map's total is the slab's cost, so the mean cost of a byte is known before the map is made */
+	if (o->weights == WEIGHTS_COST_MEAN && mgl_sa_current(r->sa, NULL, &cost) != MGL_OK) return lib_error();
+	const uint32_t floor = o->weights == WEIGHTS_COST_MEAN ? (uint32_t)(cost / r->file_size) : o->weights_floor;
+	if (mgl_sa_weight_targets_by_cost(r->sa, NULL, floor, &total, &ms) != MGL_OK) return lib_error();
+	fprintf(stderr, "target-weights: cost map + %u per byte, total %llu, %.2f ms\n", floor, (unsigned long long)total, ms);
+	return 0;
+}
+
 /* the plain exchange: every chain adopts the cheapest best slab */
 static int exchange_best(cli_run* r)
 {
@@ -917,6 +984,7 @@ static int run_epochs(cli_run* r)
 			if (mgl_sa_begin_epoch(r->sa, phase, phase != 0 || r->resumed) != MGL_OK) return lib_error();
 			if (o->greedy && phase == 0 && !r->resumed && mgl_sa_seed_greedy(r->sa, o->greedy) != MGL_OK) return lib_error();
 			if (r->seed_filled && phase == 0 && mgl_sa_set_slab(r->sa, r->seed_slab) != MGL_OK) return lib_error();
+			if (weigh_by_cost(r)) return -1;
 			if (mgl_sa_run(r->sa, steps, &st) != MGL_OK) return lib_error();
 			fprintf(stderr, "current file size: %f\tbest: %f\tstep: %u\tepoch: %04u\t%.0f evals/s\n", bytes_f(st.current_cost), bytes_f(st.best_cost),
 			        phase + 1, epoch, st.gpu_ms_total > 0 ? st.evaluations / (st.gpu_ms_total * 1e-3) : 0.0);
@@ -1018,6 +1086,7 @@ int main(int argc, char** argv)
 	    seed_stream_as_best(&r) ||
 	    make_run_seed(&r) ||
 	    set_focus(&r) ||
+	    load_target_weights(&r) ||
 	    run_epochs(&r) ||
 	    final_exchange(&r) ||
 	    fetch_best(&r) ||
