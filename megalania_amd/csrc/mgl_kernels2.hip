@@ -617,29 +617,7 @@ __device__ __forceinline__ void walk_from_state(Walk& w, const mgl_wstate& st)
 	w.st = st;
 }
 
-/* BIG = false: the regular launch, change lists in LDS (MGL_CHG_CAP events each).
- * BIG = true: second chance for the few neighbours whose lists overflowed LDS: same code, lists
- * in a per-neighbour global scratch area (big.cap events each); what overflows even that goes
- * to the full-walk kernel. */
-struct BigScratch {
-	uint16_t* ins_key; uint32_t* ins_pos; uint16_t* rem_key; uint32_t* rem_pos; uint16_t* uctx;
-	uint32_t cap, uctx_cap, slots;
-	const uint32_t* todo_in; const uint32_t* todo_in_count;
-	uint32_t* spill_ctr; /* slots handed out to first-pass wavefronts that had to spill their lists */
-	/* re-simulation handed to k_sim (several wavefronts per neighbour): per neighbour a header
-	 * {n_ins, n_rem, direct lo, direct hi} (n_ins = ~0: nothing to do) and the two change lists */
-	uint32_t chg_cap; /* events per first-pass list (MGL_CHG_CAP, more when a step has few neighbours and LDS to spare) */
-	uint4* sim_hdr;
-	uint16_t* sim_keys; /* per neighbour: ins_key[chg_cap] | rem_key[chg_cap] */
-	uint32_t* sim_pos;  /* per neighbour: ins_pos[chg_cap] | rem_pos[chg_cap] */
-	/* continuation records, one per scratch slot (MGL_CONT_WORDS u32 each): a second-half wavefront whose repair needs a top-K pick
-	 * saves its walk here (state, journal; its change lists go to the slot's list area) and the second pass resumes it at the
-	 * pick instead of evaluating the neighbour again from its target.  nullptr: no continuations (restart, as before) */
-	uint32_t* cont;
-	uint32_t evcancel; /* the paired site of the window walk leaves events common to both packets out of the lists; 0 (MGL_NO_EVCANCEL=1): packet-level lists */
-};
-#define MGL_CONT_WORDS 368u       /* 48 header words | 64 journal positions | 64 old packets | 64 new packets */
-#define MGL_CONT_MAGIC 0x434F4E54u
+#include "mgl_nbr2.h" /* scratch slots and change-list helpers, NbrArgs / Nbr / NbrWalk, the continuation record, the fused hand, the outputs */
 /* MODE: the regular launch is split in two so that each half needs fewer registers and more
  * wavefronts fit a SIMD (top-K is the register hog):
  *   MGL_NBR_PICK  everything up to the mutated packet: target, walk state, and -- unless the
@@ -660,18 +638,6 @@ struct BigScratch {
 #define MGL_NBR_PICK 1
 #define MGL_NBR_REST 2
 #define MGL_NBR_PICKWALK 3
-/* what the pick body of the fused instance hands to its walk body, in place of `pickstate` and the read of `pickrec`: all
- * wave-uniform, so scalar registers */
-struct PickHand {
-	uint32_t target, rng_n;      /* rng_n: the RNG position behind the grow/shrink draw, or behind the pick */
-	uint32_t ctx_state, dists[4]; /* walk state at the target */
-	mgl_pk first, second;        /* the base's packets at the target and behind it (second: only with HAND_SECOND) */
-	mgl_pk m_first, m_second;    /* the mutated packet(s): grow/shrink, or the top-K pick */
-	uint32_t flags;
-};
-#define MGL_HAND_MUTATED 1u /* grow/shrink: no pick */
-#define MGL_HAND_SECOND 2u  /* ... that rewrote the packet behind the target too */
-#define MGL_HAND_OK 4u      /* the top-K pick found a candidate */
 /* ---- the second pass's re-simulations, by the whole workgroup
  *
  * A second-pass workgroup is MGL_BIG_WAVES wavefronts on one neighbour.  Wavefront 0 evaluates the neighbour (nbr2_one);
@@ -709,17 +675,18 @@ __device__ __forceinline__ void coop_share(const DevCtx& c, const Base2& b, cons
 {
 	const uint32_t slot = uni(cmd->slot), overlay = uni(cmd->overlay);
 	Changes cl;
+	changes_reset(cl);
 	cl.n_ins = uni(cmd->n_ins); cl.n_rem = uni(cmd->n_rem);
+	cl.ctxbits = nullptr; cl.nbitwords = 0; cl.dbg = dbg; cl.diag = c.diag_stop;
 	/* the lists sit in the slot's global scratch; a re-simulation scans them once per touched context, so it works on a copy
 	 * in LDS (behind wavefront 0's area: the second pass's launch reserves it) */
+	changes_use_slot(cl, big, slot);
+	const uint16_t* gik = cl.ins_key; const uint32_t* gip = cl.ins_pos;
+	const uint16_t* grk = cl.rem_key; const uint32_t* grp = cl.rem_pos;
 	uint32_t* cp = (uint32_t*)(smem + 4096u + per_wave_bytes);
 	cl.ins_pos = cp; cl.rem_pos = cp + MGL_BIG_CAP;
 	cl.ins_key = (uint16_t*)(cp + 2u * MGL_BIG_CAP); cl.rem_key = cl.ins_key + MGL_BIG_CAP;
-	cl.uctx = big.uctx + (size_t)slot * big.uctx_cap; cl.ctxbits = nullptr;
-	cl.cap = MGL_BIG_CAP; cl.uctx_cap = big.uctx_cap; cl.nbitwords = 0;
-	cl.direct = 0; cl.n_cancel = 0; cl.dbg = dbg; cl.diag = c.diag_stop; cl.overflow = false; cl.list_full = false;
-	const uint16_t* gik = big.ins_key + (size_t)slot * big.cap; const uint32_t* gip = big.ins_pos + (size_t)slot * big.cap;
-	const uint16_t* grk = big.rem_key + (size_t)slot * big.cap; const uint32_t* grp = big.rem_pos + (size_t)slot * big.cap;
+	cl.cap = MGL_BIG_CAP;
 	for (uint32_t e = threadIdx.x; e < cl.n_ins; e += blockDim.x) { cl.ins_pos[e] = gip[e]; cl.ins_key[e] = gik[e]; }
 	for (uint32_t e = threadIdx.x; e < cl.n_rem; e += blockDim.x) { cl.rem_pos[e] = grp[e]; cl.rem_key[e] = grk[e]; }
 	__syncthreads(); /* B */
@@ -763,99 +730,63 @@ __device__ __forceinline__ void coop_helpers(const DevCtx& c, const Base2& b, co
 		coop_share(c, b, big, dbg, smem, per_wave_bytes, T, cmd, lane, wid);
 	}
 }
-/* one neighbour, by the wavefront `wid` of its workgroup; `unit` = the neighbour's index in this launch's slice
- * (regular launch) or its slot in the second pass's list (BIG) */
-template <bool BIG, int MODE, bool PROF = false, bool FUSED = false>
-__device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Control* ctl, uint64_t seed,
-                                         uint64_t step_override, uint32_t K, const NbrOut& out, uint32_t per_wave_bytes,
-                                         uint32_t* todo, uint32_t* todo_count, unsigned long long* prof_acc,
-                                         const BigScratch& big, uint4* pickrec, uint32_t j_base, uint32_t j_end, uint4* pickstate,
-                                         unsigned char* smem, const uint16_t* T, uint32_t unit, uint32_t lane, uint32_t wid,
-                                         PickHand* hand = nullptr)
+
+/* ================================================================== one neighbour: nbr2_one and its stages */
+
+/* ---- the stages of nbr2_one, in its order */
+
+/* Reads the launch's LDS geometry.  Leaves the journal (empty), the bitmap, the model's and the price tables' place, and the lists'.
+ * LDS per wavefront: [journal | context bitmap | union].  The union holds EITHER the model + top-K price tables (while the
+ * mutation is chosen) OR the change lists (afterwards): the lists only start to fill once the mutated packet is known.  A
+ * repair that needs another top-K pick while the lists are live is handed to the BIG pass, whose lists are in global memory.
+ * This keeps 11 instead of 8 wavefronts per CU. */
+template <int MODE>
+__device__ __forceinline__ unsigned char* nbr_wave_area(const DevCtx& c, const NbrArgs& a, Nbr& n)
 {
-	static_assert(!FUSED || (!BIG && !PROF && (MODE == MGL_NBR_PICK || MODE == MGL_NBR_REST)), "the fused instance is the two halves of the regular launch");
-	uint32_t j = j_base + unit; /* [j_base, j_end): the slice of the step this launch covers */
-	uint32_t slot = 0;
-	const unsigned long long t_begin = prof_acc ? __builtin_readcyclecounter() : 0ull;
-	if (BIG) {
-		slot = unit;
-		const uint32_t nflag = *big.todo_in_count;
-		if (slot >= nflag) return;
-		j = uni(big.todo_in[slot]);
-		if (lane == 0) atomicAdd((unsigned long long*)&ctl->big_nbrs, 1ull); /* counted where the second pass takes it up */
-	}
-	if (j >= K || (!BIG && j >= j_end)) return;
-	/* LDS per wavefront: [journal | context bitmap | union].  The union holds EITHER the model +
-	 * top-K price tables (while the mutation is chosen) OR the change lists (afterwards): the
-	 * lists only start to fill once the mutated packet is known.  A repair that needs another
-	 * top-K pick while the lists are live is handed to the BIG pass, whose lists are in global
-	 * memory.  This keeps 11 instead of 8 wavefronts per CU. */
-	unsigned char* mine = smem + ((MODE == MGL_NBR_REST || MODE == MGL_NBR_PICK) ? 0u : 4096u) + (size_t)wid * per_wave_bytes;
-	Journal jn;
+	unsigned char* mine = a.smem + ((MODE == MGL_NBR_REST || MODE == MGL_NBR_PICK) ? 0u : 4096u) + (size_t)a.wid * a.per_wave_bytes;
+	Journal& jn = n.jn; Changes& ch = n.ch;
 	jn.old = (mgl_pk*)mine;
 	jn.neu = jn.old + MGL_MAX_DIFFS;
 	jn.pos = (uint32_t*)(jn.neu + MGL_MAX_DIFFS);
 	jn.count = 0; jn.overflow = false;
-	Changes ch;
 	ch.nbitwords = (c.L.total + 31u) >> 5;
 	ch.ctxbits = jn.pos + MGL_MAX_DIFFS;
 	/* the pick half never reads the journal or the bitmap: its wave area is the model + price tables alone */
 	unsigned char* uni_base = MODE == MGL_NBR_PICK ? mine : (unsigned char*)(ch.ctxbits + ((ch.nbitwords + 3u) & ~3u));
-	uint16_t* probs = (uint16_t*)uni_base;
-	uint32_t* lencost = (uint32_t*)(uni_base + (size_t)b.ck_elems * 2);
+	const uint32_t cap = a.big.chg_cap;
 	ch.ins_pos = (uint32_t*)uni_base;
-	ch.rem_pos = ch.ins_pos + big.chg_cap;
-	ch.ins_key = (uint16_t*)(ch.rem_pos + big.chg_cap);
-	ch.rem_key = ch.ins_key + big.chg_cap;
-	ch.uctx = ch.rem_key + big.chg_cap;
-	ch.cap = big.chg_cap; ch.uctx_cap = 2 * big.chg_cap;
-	if (BIG) {
-		if (slot >= big.slots) { /* more flagged neighbours than scratch slots: full walk */
-			if (lane == 0) { const uint32_t s2 = atomicAdd(todo_count, 1u); todo[s2] = j; }
-			return;
-		}
-		ch.ins_key = big.ins_key + (size_t)slot * big.cap; ch.ins_pos = big.ins_pos + (size_t)slot * big.cap;
-		ch.rem_key = big.rem_key + (size_t)slot * big.cap; ch.rem_pos = big.rem_pos + (size_t)slot * big.cap;
-		ch.uctx = big.uctx + (size_t)slot * big.uctx_cap;
-		ch.cap = big.cap; ch.uctx_cap = big.uctx_cap;
-	}
-	ch.n_ins = ch.n_rem = 0; ch.n_cancel = 0; ch.direct = 0; ch.overflow = false; ch.list_full = false;
-	bool too_many = false;
-	bool spilled = BIG;
+	ch.rem_pos = ch.ins_pos + cap;
+	ch.ins_key = (uint16_t*)(ch.rem_pos + cap);
+	ch.rem_key = ch.ins_key + cap;
+	ch.uctx = ch.rem_key + cap;
+	ch.cap = cap; ch.uctx_cap = 2 * cap;
+	return uni_base;
+}
 
-	const uint64_t gstep = step_override != ~0ull ? step_override : ctl->gstep;
-	NbrRng rng; rng.key = mgl_rng_key(seed, gstep, j); rng.n = 0;
-	/* second pass: a walk the second half saved at its repair pick (same neighbour, same slot) is taken up there */
-	uint32_t* const crec = (BIG && big.cont != nullptr) ? big.cont + (size_t)slot * MGL_CONT_WORDS : nullptr;
-	bool resumed = false;
-	if (BIG && crec != nullptr) resumed = uni(crec[0]) == MGL_CONT_MAGIC && uni(crec[1]) == j;
-
-	/* target (same rule as the full-walk path) and the walk state there; the second half of a split
-	 * launch takes both from the first half's record instead of drawing and searching again */
+/* Reads the step's targets or draws one; n.crec / n.resumed.  Leaves n.pos, the neighbour's walk state there (w.nb) and the RNG
+ * position.  Five sources: the pick body's hand (fused; with it comes n.first), the pick half's state record, a continuation
+ * record, the step's stratified targets, the neighbour's own draws (same rule as the full-walk path).  The pick half puts what it
+ * found on record for the walk half */
+template <bool BIG, int MODE, bool FUSED>
+__device__ __forceinline__ void nbr_target(const DevCtx& c, const Base2& b, const NbrArgs& a, uint32_t lane, Nbr& n, NbrWalk& w, NbrRng& rng, const PickHand* hand)
+{
+	const uint32_t j = n.j;
 	uint32_t target;
-	mgl_wstate nb; /* neighbour's walk state */
-	if (MODE == MGL_NBR_REST && lane == 0) big.sim_hdr[j] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+	mgl_wstate& nb = w.nb;
 	if (MODE == MGL_NBR_REST && FUSED) {
-		target = hand->target; rng.n = hand->rng_n;
-		nb.pos = target; nb.ctx_state = hand->ctx_state;
-		nb.dists[0] = hand->dists[0]; nb.dists[1] = hand->dists[1]; nb.dists[2] = hand->dists[2]; nb.dists[3] = hand->dists[3];
+		hand_take_target(hand, n, rng, nb);
+		return;
 	} else if (MODE == MGL_NBR_REST) {
-		const uint4 s0 = pickstate[2u * j], s1 = pickstate[2u * j + 1u];
+		const uint4 s0 = a.pickstate[2u * j], s1 = a.pickstate[2u * j + 1u];
 		target = s0.x; rng.n = s0.y;
 		nb.pos = target; nb.ctx_state = s0.z;
 		nb.dists[0] = s0.w; nb.dists[1] = s1.x; nb.dists[2] = s1.y; nb.dists[3] = s1.z;
-	} else if (BIG && resumed) {
-		target = uni(crec[2]);
-		nb.pos = uni(crec[3]); nb.ctx_state = uni(crec[4]);
-		nb.dists[0] = uni(crec[5]); nb.dists[1] = uni(crec[6]); nb.dists[2] = uni(crec[7]); nb.dists[3] = uni(crec[8]);
+	} else if (BIG && n.resumed) {
+		cont_resume_target(n.crec, &target, nb);
 	} else if (c.strat_pre != nullptr) {
 		target = uni(c.strat_tgt[j]); /* stratified_target(), worked out for the whole step by k_targets */
 		rng.n = 1;
 		nb = uni_state(base_state_at(b, target));
-		if (MODE == MGL_NBR_PICK && !FUSED && lane == 0) {
-			pickstate[2u * j] = make_uint4(target, rng.n, nb.ctx_state, nb.dists[0]);
-			pickstate[2u * j + 1u] = make_uint4(nb.dists[1], nb.dists[2], nb.dists[3], 0u);
-		}
 	} else {
 		uint32_t mydraw = lane < 32 ? mgl_rng_draw(rng.key, lane) % c.n : 0;
 		bool on = lane < 32 && ((b.onwalk[mydraw >> 6] >> (mydraw & 63u)) & 1ull);
@@ -873,76 +804,498 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 			target = uni(bits ? (wd << 6) + ctz64(bits) : 0u);
 		}
 		nb = uni_state(base_state_at(b, target));
-		if (MODE == MGL_NBR_PICK && !FUSED && lane == 0) {
-			pickstate[2u * j] = make_uint4(target, rng.n, nb.ctx_state, nb.dists[0]);
-			pickstate[2u * j + 1u] = make_uint4(nb.dists[1], nb.dists[2], nb.dists[3], 0u);
-		}
 	}
-	if (MODE == MGL_NBR_PICK && FUSED) {
-		hand->target = target; hand->ctx_state = nb.ctx_state;
-		hand->dists[0] = nb.dists[0]; hand->dists[1] = nb.dists[1]; hand->dists[2] = nb.dists[2]; hand->dists[3] = nb.dists[3];
+	if (MODE == MGL_NBR_PICK && !FUSED && lane == 0) { /* one of the last two sources */
+		a.pickstate[2u * j] = make_uint4(target, rng.n, nb.ctx_state, nb.dists[0]);
+		a.pickstate[2u * j + 1u] = make_uint4(nb.dists[1], nb.dists[2], nb.dists[3], 0u);
 	}
-	/* the pick half keeps its own stage clock (PickProf: stages behind the second half's lifetimes in the profile buffer) */
-	Prof prof;
-	prof_start(prof, MODE == MGL_NBR_PICK ? nullptr : prof_acc);
-	ch.dbg = MODE == MGL_NBR_PICK ? nullptr : prof_acc;
-	PickProf pp; /* PROF: the pick half's profiled instance, launched only under MGL_F_PROFILE */
-	pp.acc = PROF ? prof_acc + 32u + K : nullptr;
-	pp.t = t_begin;
-	ch.diag = c.diag_stop;
-	const uint32_t pos = target;
-	mgl_wstate bs = nb;                               /* base's walk state */
-	Win win; win_reset(win);
-	Walk tw; /* scratch Walk for top-K (its window is the input window at the query position) */
+	n.pos = target;
+}
 
-	/* ---- mutate, packet_slab_neighbour.c:119-152 */
-	mgl_pk first;
-	if (MODE == MGL_NBR_REST && FUSED) first = hand->first; /* the walk covers its window itself */
-	else { win_cover(win, c, b.slab, pos, lane); first = win_pk(win, pos); }
-	if (MODE == MGL_NBR_PICK && FUSED) hand->first = uni64(first);
-	mgl_pk m_first = first, m_second = 0;
-	bool second_set = false, mutated = false;
-	prof_mark(prof, 0, lane); /* state at target */
-	if (c.diag_stop == 1) { if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = first; } return; }
-	if (MODE == MGL_NBR_REST && FUSED) {
-		/* the pick body's grow/shrink decision: journalled here, not made again */
-		mutated = (hand->flags & MGL_HAND_MUTATED) != 0; second_set = (hand->flags & MGL_HAND_SECOND) != 0;
-		if (mutated) {
-			m_first = hand->m_first; m_second = hand->m_second;
-			journal_set(jn, pos, first, m_first, lane);
-			if (second_set) journal_set(jn, pos + 1, hand->second, m_second, lane);
-		}
-	} else if (!(BIG && resumed) && pos + 1 < c.n && (nbr_draw(rng) % 2u) == 0) {
+/* Reads the packets at the target and behind it, the state there, one draw.  Leaves n.mutated and, if set, n.m_first (and
+ * w.second_set, w.m_second), journalled except in the pick half; *second: the base's packet behind the target where the rule read
+ * and rewrote it.  mutate, packet_slab_neighbour.c:119-152.  nbr_will_pick, below, is the rule once more */
+template <int MODE>
+__device__ __forceinline__ void nbr_grow_shrink(const DevCtx& c, const Base2& b, uint32_t lane, Nbr& n, NbrWalk& w, NbrRng& rng, mgl_pk* second_out)
+{
+	const uint32_t pos = n.pos;
+	const mgl_pk first = n.first;
+	if (pos + 1 < c.n && (nbr_draw(rng) % 2u) == 0) {
 		const mgl_pk second = uni64(b.slab[pos + 1]);
 		const uint32_t ft = mgl_pk_type(first), flen = mgl_pk_len(first);
 		const uint32_t st = mgl_pk_type(second), slen = mgl_pk_len(second), sdist = mgl_pk_dist(second);
 		if ((ft == MGL_LONG_REP || ft == MGL_MATCH) && flen > 2) {
-			m_second = mgl_pack(ft, mgl_pk_dist(first), flen - 1);
-			m_first = MGL_PK_LITERAL;
-			if (MODE == MGL_NBR_PICK && FUSED) hand->second = uni64(second);
-			if (MODE != MGL_NBR_PICK) { journal_set(jn, pos, first, m_first, lane); journal_set(jn, pos + 1, second, m_second, lane); }
-			second_set = true; mutated = true;
+			w.m_second = mgl_pack(ft, mgl_pk_dist(first), flen - 1);
+			n.m_first = MGL_PK_LITERAL;
+			*second_out = second;
+			if (MODE != MGL_NBR_PICK) { journal_set(n.jn, pos, first, n.m_first, lane); journal_set(n.jn, pos + 1, second, w.m_second, lane); }
+			w.second_set = true; n.mutated = true;
 		} else if ((ft == MGL_LITERAL || ft == MGL_SHORT_REP) && (st == MGL_MATCH || st == MGL_LONG_REP)) {
+			const mgl_wstate nb = w.nb; /* a copy, here and in rep_taint_step: mgl_dist_at then chooses among four values, not among pointers into w, which would keep all of w in memory */
 			uint32_t rep_start = pos - (st == MGL_LONG_REP ? mgl_dist_at(&nb, sdist) : sdist);
-			if (slen < MGL_MAX_MATCH && rep_start > 0 && rep_start <= pos && win_byte(win, pos) == c.data[rep_start - 1]) {
-				m_first = mgl_pack(st, sdist, slen + 1);
-				if (MODE != MGL_NBR_PICK) journal_set(jn, pos, first, m_first, lane);
-				mutated = true;
+			if (slen < MGL_MAX_MATCH && rep_start > 0 && rep_start <= pos && win_byte(n.win, pos) == c.data[rep_start - 1]) {
+				n.m_first = mgl_pack(st, sdist, slen + 1);
+				if (MODE != MGL_NBR_PICK) journal_set(n.jn, pos, first, n.m_first, lane);
+				n.mutated = true;
 			}
 		}
 	}
-	/* ---- the rest runs as a small phase machine so that each big piece of code (model load,
-	 * chain re-simulation, top-K) exists exactly once in the kernel: the mutation's top-K pick and
-	 * a repair's top-K pick share one site, and so do the overlay re-simulation (model at a repair
-	 * position) and the final one.  Halves the code size and the register pressure. */
-	enum { P_MODEL, P_SIM, P_TOPK, P_WALK, P_OUT };
-	uint32_t phase = mutated ? P_WALK : P_MODEL;
-	if (MODE == MGL_NBR_PICK && FUSED) {
-		hand->m_first = uni64(m_first); hand->m_second = uni64(m_second); hand->rng_n = uni(rng.n);
-		hand->flags = (mutated ? MGL_HAND_MUTATED : 0u) | (second_set ? MGL_HAND_SECOND : 0u);
+}
+/* Will neighbour j pick, or does it take a grow/shrink mutation and go straight into its walk?  nbr_grow_shrink's rule a second
+ * time (draw 1 of the neighbour's stream, the packets at the target and behind it, the rep distances there, two input bytes), for
+ * k_targets.  There are two because one rule for both, with the distance look-up handed in, moved a neighbour kernel's row for the
+ * worse (the one-kernel form: 604 -> 620 B/lane of scratch): this one reads the slab and the state itself and only answers, the
+ * other works on what its wavefront holds and journals as it decides.
+ * It only orders a launch (k_pick_order): a wrong answer costs time, never a result.  tests/test_gpu_pick_order.py holds the two
+ * together.  Every load is inside its buffer whatever the slab holds: pos < n, and base_state_at looks at positions below pos. */
+__device__ __forceinline__ bool nbr_will_pick(const DevCtx& c, const Base2& b, uint32_t pos, uint64_t key)
+{
+	if (pos >= c.n || pos + 1 >= c.n || (mgl_rng_draw(key, 1) % 2u) != 0) return true;
+	const mgl_pk first = b.slab[pos], second = b.slab[pos + 1];
+	const uint32_t ft = mgl_pk_type(first), flen = mgl_pk_len(first);
+	const uint32_t st = mgl_pk_type(second), slen = mgl_pk_len(second), sdist = mgl_pk_dist(second);
+	if ((ft == MGL_LONG_REP || ft == MGL_MATCH) && flen > 2) return false;
+	if ((ft == MGL_LITERAL || ft == MGL_SHORT_REP) && (st == MGL_MATCH || st == MGL_LONG_REP)) {
+		uint32_t d = sdist;
+		if (st == MGL_LONG_REP) { const mgl_wstate nb = base_state_at(b, pos); d = mgl_dist_at(&nb, sdist); }
+		const uint32_t rep_start = pos - d;
+		if (slen < MGL_MAX_MATCH && rep_start > 0 && rep_start <= pos && c.data[pos] == c.data[rep_start - 1]) return false;
 	}
-	if (MODE == MGL_NBR_PICK && mutated) { /* nothing to pick: the second half redoes the grow/shrink itself */
-		if (!FUSED && lane == 0) reinterpret_cast<uint32_t*>(pickstate)[8u * j + 7u] = 1u; /* the decision, on record for the tests of the class hint (mgl_debug_dump 28) */
+	return true;
+}
+
+/* Reads the pick record (the pick half's, or the pick body's hand) of a neighbour without a grow/shrink.  Leaves the mutated packet
+ * journalled, the RNG position behind the pick, and the walk as the next phase -- or no candidate, and the end.  The second pass,
+ * too, takes the mutation's pick from the first half when there was one */
+template <int MODE, bool FUSED>
+__device__ __forceinline__ void nbr_take_pick(const NbrArgs& a, uint32_t lane, Nbr& n, NbrRng& rng, const PickHand* hand)
+{
+	const uint4 rec = (MODE == MGL_NBR_REST && FUSED) ? hand_take_pick(hand) : a.pickrec[n.j];
+	if (!(rec.w & 1u)) { n.generate_failed = true; n.phase = P_OUT; }
+	else {
+		n.m_first = (mgl_pk)rec.x | ((mgl_pk)rec.y << 32);
+		journal_set(n.jn, n.pos, n.first, n.m_first, lane);
+		rng.n = rec.z;
+		n.pick_is_mutation = false;
+		n.phase = P_WALK;
+	}
+}
+
+/* P_MODEL.  Reads w.pick_pos and the lists.  Leaves the base's adaptive model before the first base packet at or after pick_pos in
+ * probs (dense checkpoint + replay of < 64 bytes of base packets); live lists, which share the model's LDS, are moved to a global
+ * scratch slot first.  Next: P_SIM (overlay: the touched contexts' re-simulated values) when there are lists, else P_TOPK.
+ * Returns true where a diagnostic stop ends the neighbour */
+template <bool PROF, bool FUSED>
+__device__ __forceinline__ bool phase_model(const DevCtx& c, const Base2& b, const NbrArgs& a, uint32_t lane, const uint16_t* T, Nbr& n, const NbrWalk& w, uint16_t* probs, PickProf& pp)
+{
+	const BigScratch& big = a.big; Changes& ch = n.ch;
+	if ((ch.n_ins + ch.n_rem) != 0 && !n.spilled) {
+		uint32_t sl = 0;
+		if (lane == 0) sl = atomicAdd(big.spill_ctr, 1u);
+		sl = uni(sl);
+		if (sl >= big.slots) { ch.overflow = true; n.phase = P_OUT; return false; }
+		lists_copy_to_slot(ch, big, sl, lane);
+		__threadfence_block();
+		wave_sync();
+		changes_use_slot(ch, big, sl);
+		n.spilled = true;
+	}
+	if constexpr (FUSED) model_load_inl(c, b, probs, T, w.pick_pos, lane);
+	else model_load(c, b, probs, T, w.pick_pos, lane);
+	if (PROF) pick_prof_mark(&pp, 2, lane);
+	if (!n.pick_is_mutation) prof_mark(n.prof, 5, lane); /* repair: base model at the pick position */
+	if (n.pick_is_mutation) {
+		prof_mark(n.prof, 1, lane); /* model at target */
+		if (c.diag_stop == 2) { if (lane == 0) nbr_out_diag(a.out, n.j, probs[lane]); return true; }
+	}
+	/* ... with the touched contexts overridden by their re-simulated values */
+	if ((ch.n_ins + ch.n_rem) != 0) { n.sim_limit = w.pick_pos; n.sim_overlay = true; n.phase = P_SIM; }
+	else n.phase = P_TOPK;
+	return false;
+}
+
+/* P_SIM.  Reads the lists and the request (n.sim_limit, n.sim_overlay).  Three forms.  The walk half holds no re-simulation code: its
+ * lists go to k_sim, which puts several wavefronts on one neighbour's contexts and writes the cost, and it ends (P_OUT; journal and
+ * counters are written there).  The second pass re-simulates with its workgroup (coop_sim), the one-kernel form alone (chain_sim):
+ * an overlay leaves the model at a repair pick overridden (next: P_TOPK), the final one leaves n.delta (next: P_OUT) */
+template <bool BIG, int MODE>
+__device__ __forceinline__ void phase_sim(const DevCtx& c, const Base2& b, const NbrArgs& a, uint32_t lane, const uint16_t* T, Nbr& n, uint16_t* probs)
+{
+	const BigScratch& big = a.big; Changes& ch = n.ch;
+	const uint32_t j = n.j;
+	if (MODE == MGL_NBR_REST) {
+		uint16_t* gk = big.sim_keys + (size_t)j * (2u * big.chg_cap);
+		uint32_t* gp = big.sim_pos + (size_t)j * (2u * big.chg_cap);
+		lists_copy_out(ch, gk, gp, gk + big.chg_cap, gp + big.chg_cap, lane);
+		/* no fence: the consumer is a later launch on a stream that waits for this one */
+		if (lane == 0) big.sim_hdr[j] = make_uint4(ch.n_ins, ch.n_rem, (uint32_t)(uint64_t)ch.direct, (uint32_t)((uint64_t)ch.direct >> 32));
+		n.sim_deferred = true;
+		n.phase = P_OUT;
+		return;
+	}
+	int64_t r;
+	if (BIG) r = coop_sim(c, b, big, a.prof_acc, a.smem, a.per_wave_bytes, T, ch, n.slot, n.sim_limit, n.sim_overlay ? probs : nullptr, lane, &n.too_many);
+	else r = chain_sim(b, ch, T, n.sim_limit, n.sim_overlay ? probs : nullptr, lane, &n.too_many);
+	wave_sync();
+	if (n.too_many) { n.phase = P_OUT; return; }
+	if (n.sim_overlay) { prof_mark(n.prof, 6, lane); n.phase = P_TOPK; } /* repair: model overridden by the re-simulated values */
+	else { n.delta = r; prof_mark(n.prof, 4, lane); n.phase = P_OUT; }
+}
+
+/* P_TOPK.  Reads the model in probs and the request (n.pick_is_mutation: at the target against n.first; else w.pick_*).  The pick
+ * half records the pick and ends (returns true, as a diagnostic stop does).  Otherwise leaves the mutated packet journalled, or the
+ * repair's pick in w.picked_pk / w.have_pick; next: P_WALK -- or no candidate at the target, and P_OUT */
+template <int MODE, bool PROF, bool FUSED>
+__device__ __forceinline__ bool phase_topk(const DevCtx& c, const Base2& b, const NbrArgs& a, uint32_t lane, const uint16_t* T, Nbr& n, NbrWalk& w, NbrRng& rng, Walk& tw, uint16_t* probs, uint32_t* lencost, const TopkPlan& plan, PickProf& pp, PickHand* hand)
+{
+	const uint32_t j = n.j;
+	walk_from_state(tw, w.nb);
+	win_cover(tw.win, c, b.slab, tw.st.pos, lane);
+	mgl_pk picked;
+	bool ok;
+	if constexpr (MODE == MGL_NBR_PICK) ok = pick_from_top_k<4, true, PROF>(c, tw, probs, T, lencost, w.pick_inc, w.pick_best, rng, lane, &picked, &plan, &pp);
+	else {
+		/* a call, which is what the inliner made of it while the phases were one function: said here, so that the one-kernel form and
+		 * the second pass keep the registers, the scratch and the wavefronts per SIMD they had */
+		[[clang::noinline]] ok = pick_from_top_k<1>(c, tw, probs, T, lencost, w.pick_inc, w.pick_best, rng, lane, &picked);
+	}
+	if (MODE == MGL_NBR_PICK) {
+		if (lane == 0) a.pickrec[j] = make_uint4((uint32_t)picked, (uint32_t)(picked >> 32), rng.n, ok ? 1u : 0u); /* fused, too: the second pass restarts from it */
+		if (FUSED) hand_put_pick(hand, picked, rng, ok);
+		if (PROF) pick_prof_mark(&pp, 14, lane);
+		if (PROF && pp.acc && lane == 0) pp.acc[2u * MGL_PICK_STAGES + j] = __builtin_readcyclecounter() - n.t_begin; /* a picking wavefront's lifetime */
+		return true;
+	}
+	if (n.pick_is_mutation) {
+		if (!ok) { n.generate_failed = true; n.phase = P_OUT; return false; }
+		n.m_first = picked;
+		journal_set(n.jn, n.pos, n.first, n.m_first, lane);
+		n.pick_is_mutation = false;
+		prof_mark(n.prof, 2, lane); /* top-K */
+		if (c.diag_stop == 3 || (c.diag_stop >= 31 && c.diag_stop <= 39)) { if (lane == 0) nbr_out_diag(a.out, j, (uint32_t)n.m_first); return true; }
+	} else {
+		w.picked_pk = ok ? picked : w.pick_inc;
+		w.have_pick = true;
+		prof_mark(n.prof, 7, lane); /* repair: top-K */
+	}
+	n.win.base = 0xFFFFFFFFu;
+	n.phase = P_WALK;
+	return false;
+}
+
+/* ---- P_WALK's pieces */
+
+/* mgl_advance for a state inside NbrWalk, on a copy: mgl_advance chooses among the rep distances by pointer, and a pointer chosen
+ * among w's fields keeps all of w in memory (144 B/lane of scratch in every walking instance) */
+__device__ __forceinline__ void walk_advance(mgl_wstate& st, uint32_t type, uint32_t dist, uint32_t len)
+{
+	mgl_wstate s = st;
+	mgl_advance(&s, type, dist, len);
+	st = s;
+}
+
+/* the base packet at w.bs.pos goes away: its events to the removed list, the base's walk a packet on */
+__device__ __forceinline__ void base_packet_out(const DevCtx& c, const Base2& b, uint32_t lane, Nbr& n, NbrWalk& w)
+{
+	win_cover(n.win, c, b.slab, w.bs.pos, lane);
+	const mgl_pk bpk = win_pk(n.win, w.bs.pos);
+	mgl_plan bpl;
+	plan_at(c.L, c.data, w.bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk), win_byte(n.win, w.bs.pos), bpl);
+	changes_add<false>(n.ch, bpl, w.bs.pos, lane);
+	walk_advance(w.bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk));
+}
+
+enum { REPAIR_PACKET, REPAIR_STOP, REPAIR_SAVED };
+/* The repair rules of packet_slab_neighbour.c:82-117 for the neighbour's packet at p (not its first, not one back from a pick).
+ * Leaves the packet the base codes there for this neighbour (*old) and the packet it gets (*pk): REPAIR_PACKET.  A long rep that
+ * validates under no slot needs a top-K pick: the base's walk is caught up to p (the model at p needs every base packet that starts
+ * before p priced in) and the request left in w.pick_*; REPAIR_STOP, with *request_pick -- or with n.walk_long (too many picks)
+ * or an overflow.  The walk half holds no top-K code: with continuation records it saves the walk as it stands -- here, where
+ * everything is live anyway, so that the walk loop carries no value for it -- hands the neighbour to the second pass and ends,
+ * REPAIR_SAVED */
+template <bool BIG, int MODE>
+__device__ __forceinline__ uint32_t repair_packet(const DevCtx& c, const Base2& b, const NbrArgs& a, uint32_t lane, Nbr& n, NbrWalk& w, NbrRng& rng, Walk& tw, uint32_t p, mgl_pk* pk_out, mgl_pk* old_out, bool* request_pick)
+{
+	const BigScratch& big = a.big; Changes& ch = n.ch;
+	if (w.count < 8) w.count++;
+	const mgl_pk old = (w.second_set && p == n.pos + 1) ? w.m_second : win_pk(n.win, p);
+	mgl_pk pk = old;
+	*old_out = old;
+	uint32_t type = mgl_pk_type(pk);
+	if (type == MGL_SHORT_REP || (type == MGL_LITERAL && w.count < 4)) {
+		const bool same = w.nb.dists[0] < p && win_byte(n.win, p) == c.data[p - w.nb.dists[0] - 1];
+		if (same) { if (w.count < 4) pk = MGL_PK_SHORT_REP; }
+		else pk = MGL_PK_LITERAL;
+	}
+	type = mgl_pk_type(pk);
+	if (type == MGL_LONG_REP) {
+		const uint32_t len = mgl_pk_len(pk);
+		uint32_t idx = mgl_pk_dist(pk);
+		walk_from_state(tw, w.nb);
+		bool ok = long_rep_ok(c, tw, idx, len, lane);
+		for (uint32_t i = 0; i < 4 && !ok; i++) { idx = i; ok = long_rep_ok(c, tw, idx, len, lane); }
+		pk = mgl_pack(MGL_LONG_REP, idx, len);
+		if (!ok) {
+			if (++w.npicks > MGL_MAX_REPAIR_PICKS) { n.walk_long = true; return REPAIR_STOP; }
+			w.pick_best = (nbr_draw(rng) % 4u) == 0;
+			while (w.bs.pos < p && !ch.overflow) base_packet_out(c, b, lane, n, w);
+			if (ch.overflow) return REPAIR_STOP;
+			w.resume_old = old; w.pick_pos = p; w.pick_inc = pk;
+			if (MODE == MGL_NBR_REST && big.cont != nullptr) {
+				uint32_t slot2 = 0;
+				if (lane == 0) {
+					atomicAdd(big.spill_ctr + 1, 1u); /* repair picks this step */
+					slot2 = atomicAdd(a.todo_count, 1u);
+					a.todo[slot2] = n.j;
+					nbr_out_none(a.out, n.j, n.pos, 0, MGL_WIN_NONE);
+				}
+				slot2 = uni(slot2);
+				if (slot2 < big.slots) { /* else: no scratch slot, the second pass sends it on to the full walk */
+					lists_copy_to_slot(ch, big, slot2, lane);
+					cont_save(big.cont + (size_t)slot2 * MGL_CONT_WORDS, n.j, n.pos, w, rng, n.jn, ch, lane);
+				}
+				return REPAIR_SAVED;
+			}
+			*request_pick = true;
+			if (!BIG && lane == 0) atomicAdd(big.spill_ctr + 1, 1u); /* repair picks this step */
+			return REPAIR_STOP; /* -> P_MODEL, then back to the walk with w.have_pick */
+		}
+	}
+	*pk_out = pk;
+	return REPAIR_PACKET;
+}
+
+/* which rep distances the neighbour's packet pk at p reads and pushes: bit k of w.taint = distance k comes from before the window.
+ * A rep packet: the soft window reaches at least to behind it -- unless it is the base's own packet at this position reading a slot
+ * that holds the same distance in both walks (the move has no part in what it codes) */
+__device__ __forceinline__ void rep_taint_step(const Nbr& n, NbrWalk& w, uint32_t p, mgl_pk pk)
+{
+	const uint32_t ntype = mgl_pk_type(pk), ndist = mgl_pk_dist(pk);
+	if (ntype == MGL_SHORT_REP || ntype == MGL_LONG_REP) {
+		const uint32_t slot = ntype == MGL_SHORT_REP ? 0u : ndist;
+		const mgl_wstate nb = w.nb, bs = w.bs;
+		const bool same_read = bs.pos == p && win_pk(n.win, p) == pk && mgl_dist_at(&nb, slot) == mgl_dist_at(&bs, slot);
+		if (!same_read) w.wsoft = 0xFFFFFFFFu;
+		w.dep |= ntype == MGL_SHORT_REP ? (w.taint & 1u) : ((w.taint >> ndist) & 1u);
+	}
+	if (ntype == MGL_MATCH) w.taint = (w.taint << 1) & 0xFu;
+	else if (ntype == MGL_LONG_REP) w.taint = (w.taint & ~((2u << ndist) - 1u)) | ((w.taint & ((1u << ndist) - 1u)) << 1) | ((w.taint >> ndist) & 1u);
+}
+
+/* is pk at p the base's packet at the same position, coded identically (its events cancel whole)?  Which events a packet produces
+ * depends on the packet, ctx_state, the position and -- for a literal after a match -- the byte at rep distance 0; decided before
+ * anything is planned */
+__device__ __forceinline__ bool codes_identically(const DevCtx& c, const Nbr& n, const NbrWalk& w, uint32_t p, mgl_pk pk)
+{
+	bool cancelled = false;
+	if (w.bs.pos == p && win_pk(n.win, p) == pk && w.nb.ctx_state == w.bs.ctx_state) {
+		cancelled = true;
+		if (mgl_pk_type(pk) == MGL_LITERAL && w.nb.ctx_state >= 7) {
+			const uint32_t mn = w.nb.dists[0] < p ? c.data[p - w.nb.dists[0] - 1] : 0u;
+			const uint32_t mb = w.bs.dists[0] < p ? c.data[p - w.bs.dists[0] - 1] : 0u;
+			cancelled = mn == mb;
+		}
+	}
+	return cancelled;
+}
+
+/* P_WALK: the two-pointer walk over neighbour packets (w.nb) and base packets (w.bs) from where w stands, until both code
+ * identically again.  Leaves the lists, the journal and n.wend; next: P_SIM (the final re-simulation), P_MODEL (a repair's pick:
+ * back here with w.have_pick) or P_OUT (n.walk_long, an overflow).  Returns true where the neighbour has ended: its walk saved
+ * in a continuation record, or a diagnostic stop */
+template <bool BIG, int MODE>
+__device__ __forceinline__ bool phase_walk(const DevCtx& c, const Base2& b, const NbrArgs& a, uint32_t lane, Nbr& n, NbrWalk& w, NbrRng& rng, Walk& tw)
+{
+	Changes& ch = n.ch; Journal& jn = n.jn; Win& win = n.win;
+	bool request_pick = false;
+	while (w.nb.pos < c.n || w.bs.pos < c.n) {
+		if (ch.overflow || jn.overflow || n.too_many || ++w.guard > (BIG ? (1u << 20) : 4096u)) { ch.overflow = true; break; }
+		if (!w.first_packet && !w.have_pick && w.nb.pos == w.bs.pos && w.count >= 3) {
+			const bool same_ctx = w.nb.ctx_state == w.bs.ctx_state;
+			const bool same_d = w.nb.dists[0] == w.bs.dists[0] && w.nb.dists[1] == w.bs.dists[1] && w.nb.dists[2] == w.bs.dists[2] &&
+			                    w.nb.dists[3] == w.bs.dists[3];
+			if (same_ctx && w.wsoft == 0xFFFFFFFFu) w.wsoft = w.nb.pos;
+			if (same_ctx && same_d) break; /* the rest of the file is coded identically */
+			if (same_ctx && w.nb.ctx_state < 7) {
+				/* plain literals up to the next special packet code identically: skip them */
+				uint32_t sx = uni(sp_find_next(b, w.nb.pos));
+				if (sx == MGL_POS_INF || sx > c.n) sx = c.n;
+				if (sx > w.nb.pos) {
+					const uint32_t cs = lit_steps(w.nb.ctx_state, sx - w.nb.pos);
+					w.nb.pos = w.bs.pos = sx; w.nb.ctx_state = w.bs.ctx_state = cs;
+					w.count = 8;
+					continue;
+				}
+			}
+		}
+		if (w.walked > MGL_MAX_WALK && !w.have_pick) { n.walk_long = true; break; }
+		if ((w.have_pick || w.nb.pos <= w.bs.pos) && w.nb.pos < c.n) {
+			/* ---- next neighbour packet */
+			const uint32_t p = w.nb.pos;
+			win_cover(win, c, b.slab, p, lane);
+			mgl_pk pk, old = 0;
+			if (w.have_pick) {
+				pk = w.picked_pk; old = w.resume_old; w.have_pick = false; /* back from the top-K pick for this packet */
+			} else if (w.first_packet) {
+				pk = n.m_first; /* :169 the mutated packet is coded as is */
+			} else {
+				const uint32_t r = repair_packet<BIG, MODE>(c, b, a, lane, n, w, rng, tw, p, &pk, &old, &request_pick);
+				if (r == REPAIR_SAVED) return true;
+				if (r == REPAIR_STOP) break;
+			}
+			if (!w.first_packet && pk != old) {
+				const mgl_pk base_old = (w.second_set && p == n.pos + 1) ? uni64(b.slab[p]) : old;
+				journal_set(jn, p, base_old, pk, lane);
+				w.wsoft = 0xFFFFFFFFu; /* a changed packet (a SHORT_REP the repair turned into a literal, say): the soft window reaches behind it */
+			}
+			w.first_packet = false;
+			w.walked++;
+			const uint32_t ntype = mgl_pk_type(pk), ndist = mgl_pk_dist(pk), nlen = mgl_pk_len(pk);
+			rep_taint_step(n, w, p, pk);
+			if (codes_identically(c, n, w, p, pk)) {
+				walk_advance(w.bs, ntype, ndist, nlen);
+			} else {
+				/* of the base packet only a key per lane and two counts stay live while the neighbour's is planned */
+				uint32_t bkey = 0, bnev = 0, bndirect = 0;
+				if (w.bs.pos == p) {
+					const mgl_pk bpk = win_pk(win, p);
+					const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
+					mgl_plan bpl;
+					plan_at(c.L, c.data, w.bs, btype, bdist, blen, win_byte(win, p), bpl);
+					bnev = bpl.nev; bndirect = bpl.ndirect;
+					if (lane < bnev) {
+						uint32_t cx, bt;
+						mgl_plan_event(&bpl, lane, &cx, &bt);
+						bkey = cx | (bt << 15);
+					}
+					walk_advance(w.bs, btype, bdist, blen);
+				}
+				mgl_plan npl;
+				plan_at(c.L, c.data, w.nb, ntype, ndist, nlen, win_byte(win, p), npl);
+				changes_add_pair(ch, bkey, bnev, bndirect, npl, p, lane, a.big.evcancel != 0);
+			}
+			walk_advance(w.nb, ntype, ndist, nlen);
+		} else {
+			/* ---- a base packet the neighbour has already passed over: its events go away, a run of plain literals at a time */
+			win_cover(win, c, b.slab, w.bs.pos, lane);
+			if (literal_run_events<false>(c, ch, win, w.bs, (w.nb.pos < c.n ? w.nb.pos : c.n) - w.bs.pos, lane)) continue;
+			base_packet_out(c, b, lane, n, w);
+		}
+	}
+	if (n.walk_long) { n.phase = P_OUT; return false; }
+	if (request_pick) { prof_mark(n.prof, 3, lane); n.phase = P_MODEL; return false; }
+	prof_mark(n.prof, 3, lane); /* window walk */
+	if (c.diag_stop == 4) { if (lane == 0) nbr_out_diag(a.out, n.j, ch.n_ins + ch.n_rem); return true; }
+	if (ch.overflow || jn.overflow || n.too_many) { n.phase = P_OUT; return false; }
+	n.wend = w.nb.pos;
+	n.sim_limit = MGL_POS_INF; n.sim_overlay = false; n.phase = P_SIM;
+	return false;
+}
+
+/* The end of a neighbour that left the phases without a result.  Reads how they ended; returns false for the one that has a result */
+template <bool BIG>
+__device__ __forceinline__ bool nbr_out_unfinished(const NbrArgs& a, uint32_t lane, const Nbr& n, const NbrWalk& w)
+{
+	const uint32_t j = n.j;
+	if (n.generate_failed) { /* no candidate at the target (main.c:81-84 retries those) */
+		if (lane == 0) nbr_out_none(a.out, j, n.pos, 0, MGL_WIN_NONE);
+		return true;
+	}
+	if (n.jn.overflow) { /* same rule as the full-walk path and the oracle: dropped */
+		if (lane == 0) nbr_out_none(a.out, j, n.pos, w.walked, MGL_WIN_DROPPED);
+		return true;
+	}
+	if (n.walk_long || (n.ch.list_full && n.ch.cap == a.big.cap && !n.jn.overflow)) {
+		/* more inserted or removed events than the second pass's lists hold (MGL_BIG_CAP), or more than MGL_MAX_WALK packets
+		 * visited before the walks met again: dropped, like a neighbour with too long a journal; the oracle counts the same */
+		if (lane == 0) nbr_out_none(a.out, j, n.pos, w.walked, MGL_WIN_DROPPED);
+		return true;
+	}
+	if (n.ch.overflow || n.too_many) {
+		/* does not fit the change lists: hand it to the next pass (BIG, then the full-walk kernel) */
+		if (lane == 0) {
+			const uint32_t slot2 = atomicAdd(a.todo_count, 1u);
+			a.todo[slot2] = j;
+			if (BIG) atomicAdd((unsigned long long*)&a.ctl->fallback_nbrs, 1ull);
+			nbr_out_none(a.out, j, n.pos, 0, MGL_WIN_NONE);
+		}
+		return true;
+	}
+	return false;
+}
+
+/* one neighbour, by the wavefront a.wid of its workgroup; `unit` = the neighbour's index in this launch's slice
+ * (regular launch) or its slot in the second pass's list (BIG).  `hand`: the fused instance, whose two bodies are this function
+ * as the pick half and as the walk half */
+template <bool BIG, int MODE, bool PROF = false, bool FUSED = false>
+__device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, const NbrArgs& a, uint32_t lane, const uint16_t* T, uint32_t unit, PickHand* hand = nullptr)
+{
+	static_assert(!FUSED || (!BIG && !PROF && (MODE == MGL_NBR_PICK || MODE == MGL_NBR_REST)), "the fused instance is the two halves of the regular launch");
+	const BigScratch& big = a.big;
+	Nbr n; NbrWalk w; NbrRng rng;
+	/* ---- which neighbour: [j_base, j_end) is the slice of the step this launch covers */
+	n.j = a.j_base + unit; n.slot = 0;
+	n.t_begin = a.prof_acc ? __builtin_readcyclecounter() : 0ull;
+	if (BIG) {
+		n.slot = unit;
+		const uint32_t nflag = *big.todo_in_count;
+		if (n.slot >= nflag) return;
+		n.j = uni(big.todo_in[n.slot]);
+		if (lane == 0) atomicAdd((unsigned long long*)&a.ctl->big_nbrs, 1ull); /* counted where the second pass takes it up */
+	}
+	if (n.j >= a.K || (!BIG && n.j >= a.j_end)) return;
+	unsigned char* const uni_base = nbr_wave_area<MODE>(c, a, n);
+	uint16_t* const probs = (uint16_t*)uni_base;                                   /* the model */
+	uint32_t* const lencost = (uint32_t*)(uni_base + (size_t)b.ck_elems * 2); /* top-K's price tables */
+	if (BIG) {
+		if (n.slot >= big.slots) { /* more flagged neighbours than scratch slots: full walk */
+			if (lane == 0) { const uint32_t s2 = atomicAdd(a.todo_count, 1u); a.todo[s2] = n.j; }
+			return;
+		}
+		changes_use_slot(n.ch, big, n.slot);
+	}
+	changes_reset(n.ch);
+	n.too_many = false; n.spilled = BIG;
+	const uint64_t gstep = a.step_override != ~0ull ? a.step_override : a.ctl->gstep;
+	rng.key = mgl_rng_key(a.seed, gstep, n.j); rng.n = 0;
+	/* second pass: a walk the second half saved at its repair pick (same neighbour, same slot) is taken up there */
+	n.crec = (BIG && big.cont != nullptr) ? big.cont + (size_t)n.slot * MGL_CONT_WORDS : nullptr;
+	n.resumed = BIG && n.crec != nullptr && cont_holds(n.crec, n.j);
+
+	/* ---- the target, the state there and the base's packet */
+	if (MODE == MGL_NBR_REST && lane == 0) big.sim_hdr[n.j] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+	nbr_target<BIG, MODE, FUSED>(c, b, a, lane, n, w, rng, hand);
+	/* the pick half keeps its own stage clock (PickProf: stages behind the second half's lifetimes in the profile buffer) */
+	prof_start(n.prof, MODE == MGL_NBR_PICK ? nullptr : a.prof_acc);
+	n.ch.dbg = MODE == MGL_NBR_PICK ? nullptr : a.prof_acc;
+	PickProf pp; /* PROF: the pick half's profiled instance, launched only under MGL_F_PROFILE */
+	pp.acc = PROF ? a.prof_acc + 32u + a.K : nullptr;
+	pp.t = n.t_begin;
+	n.ch.diag = c.diag_stop;
+	w.bs = w.nb;
+	win_reset(n.win);
+	Walk tw; /* scratch Walk for top-K (its window is the input window at the query position) */
+	if (!(MODE == MGL_NBR_REST && FUSED)) { win_cover(n.win, c, b.slab, n.pos, lane); n.first = win_pk(n.win, n.pos); } /* from the hand: the walk covers its window itself */
+	if (MODE == MGL_NBR_PICK && FUSED) hand_put_target(hand, n, w.nb);
+	prof_mark(n.prof, 0, lane); /* state at target */
+	if (c.diag_stop == 1) { if (lane == 0) nbr_out_diag(a.out, n.j, (uint32_t)n.first); return; }
+
+	/* ---- the mutation: a grow/shrink, decided here, or a top-K pick (the phases) */
+	n.m_first = n.first; w.m_second = 0;
+	w.second_set = false; n.mutated = false;
+	mgl_pk second = 0; /* the base's packet behind the target, where a grow/shrink rewrote it */
+	if (MODE == MGL_NBR_REST && FUSED) {
+		/* the pick body's grow/shrink decision: journalled here, not made again */
+		hand_take_mutation(hand, n, w, &second);
+		if (n.mutated) {
+			journal_set(n.jn, n.pos, n.first, n.m_first, lane);
+			if (w.second_set) journal_set(n.jn, n.pos + 1, second, w.m_second, lane);
+		}
+	} else if (!(BIG && n.resumed)) nbr_grow_shrink<MODE>(c, b, lane, n, w, rng, &second);
+	n.phase = n.mutated ? P_WALK : P_MODEL;
+	if (MODE == MGL_NBR_PICK && FUSED) hand_put_mutation(hand, n, w, rng, second);
+	if (MODE == MGL_NBR_PICK && n.mutated) { /* nothing to pick: the second half redoes the grow/shrink itself */
+		if (!FUSED && lane == 0) reinterpret_cast<uint32_t*>(a.pickstate)[8u * n.j + 7u] = 1u; /* the decision, on record for the tests of the class hint (mgl_debug_dump 28) */
 		return;
 	}
 	/* where the pick's sources start and end depends on the target and the rep distances alone: searched for here, all
@@ -950,384 +1303,43 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, Contro
 	TopkPlan plan;
 	if (MODE == MGL_NBR_PICK) {
 		if (PROF) pick_prof_mark(&pp, 0, lane);
-		topk_plan_make(plan, c, nb, lane);
+		topk_plan_make(plan, c, w.nb, lane);
 		if (PROF) pick_prof_mark(&pp, 1, lane);
 	}
 	if (MODE == MGL_NBR_REST && c.diag_stop != 0 && c.diag_stop != 4 && c.diag_stop < 40) return; /* diagnostic stops of the first half */
-	/* pending top-K request */
-	bool pick_is_mutation = !mutated;
-	uint32_t pick_pos = pos;
-	mgl_pk pick_inc = first;
-	bool pick_best = false;
-	/* its result, handed back to the walk */
-	bool have_pick = false;
-	mgl_pk picked_pk = 0, resume_old = 0;
-	/* re-simulation request */
-	uint32_t sim_limit = MGL_POS_INF;
-	bool sim_overlay = false;
-	int64_t delta = 0;
-	bool generate_failed = false, sim_deferred = false, walk_long = false;
-	uint32_t npicks = 0; /* repair picks of this neighbour */
-	uint32_t count = 0;   /* repair packet counter of packet_slab_neighbour.c:84-86, saturating */
-	uint32_t walked = 0;
-	uint32_t wend = 0; /* where the two walks meet again: the end of this neighbour's window */
-	/* for the bulk step's selection: the first meeting point -- same byte, same ctx_state -- behind
-	 * the last rep packet the walk meets, and whether a rep packet of the neighbour reads a distance from before the window */
-	uint32_t wsoft = 0xFFFFFFFFu, taint = 0xFu, dep = 0u;
-	bool first_packet = true;
-	uint32_t guard = 0;
-	/* the second pass, too, takes the mutation's pick from the first half when there was one */
-	if (BIG && resumed) {
-		/* the saved walk: everything the loop below carries from one packet to the next */
-		bs.pos = uni(crec[9]); bs.ctx_state = uni(crec[10]);
-		bs.dists[0] = uni(crec[11]); bs.dists[1] = uni(crec[12]); bs.dists[2] = uni(crec[13]); bs.dists[3] = uni(crec[14]);
-		count = uni(crec[15]); walked = uni(crec[16]); npicks = uni(crec[17]); wsoft = uni(crec[18]); taint = uni(crec[19]); dep = uni(crec[20]);
-		rng.n = uni(crec[21]); guard = uni(crec[22]); jn.count = uni(crec[23]); ch.n_ins = uni(crec[24]); ch.n_rem = uni(crec[25]);
-		const uint32_t fl = uni(crec[26]);
-		pick_best = (fl & 1u) != 0; second_set = (fl & 2u) != 0;
-		pick_inc = (mgl_pk)uni(crec[28]) | ((mgl_pk)uni(crec[29]) << 32);
-		resume_old = (mgl_pk)uni(crec[30]) | ((mgl_pk)uni(crec[31]) << 32);
-		m_second = (mgl_pk)uni(crec[32]) | ((mgl_pk)uni(crec[33]) << 32);
-		ch.direct = (int64_t)((uint64_t)uni(crec[34]) | ((uint64_t)uni(crec[35]) << 32));
-		ch.n_cancel = uni(crec[36]); /* the resumed walk goes on counting events at packet level */
-		if (lane < jn.count) {
-			jn.pos[lane] = crec[48u + lane];
-			jn.old[lane] = reinterpret_cast<const mgl_pk*>(crec + 112u)[lane];
-			jn.neu[lane] = reinterpret_cast<const mgl_pk*>(crec + 240u)[lane];
-		}
-		wave_sync();
-		if (lane == 0) crec[0] = 0u; /* taken */
-		pick_pos = nb.pos;
-		mutated = true; pick_is_mutation = false; first_packet = false;
-		phase = P_MODEL;
-	}
-	if ((MODE == MGL_NBR_REST || (BIG && pickrec != nullptr)) && !mutated) { /* the host passes the pick records only when the split form ran */
-		const uint4 rec = (MODE == MGL_NBR_REST && FUSED) ? make_uint4((uint32_t)hand->m_first, (uint32_t)(hand->m_first >> 32), hand->rng_n, (hand->flags & MGL_HAND_OK) ? 1u : 0u)
-		                                                   : pickrec[j];
-		if (!(rec.w & 1u)) { generate_failed = true; phase = P_OUT; }
-		else {
-			m_first = (mgl_pk)rec.x | ((mgl_pk)rec.y << 32);
-			journal_set(jn, pos, first, m_first, lane);
-			rng.n = rec.z;
-			pick_is_mutation = false;
-			phase = P_WALK;
-		}
-	}
 
+	/* ---- the walk at its start: the pending pick is the mutation's; or the walk a continuation record holds, at its repair pick */
+	n.pick_is_mutation = !n.mutated;
+	w.pick_pos = n.pos; w.pick_inc = n.first; w.pick_best = false;
+	w.have_pick = false; w.picked_pk = 0; w.resume_old = 0;
+	w.count = 0; w.walked = 0; w.npicks = 0; w.guard = 0;
+	w.wsoft = 0xFFFFFFFFu; w.taint = 0xFu; w.dep = 0u;
+	w.first_packet = true;
+	n.sim_limit = MGL_POS_INF; n.sim_overlay = false; n.delta = 0;
+	n.generate_failed = false; n.sim_deferred = false; n.walk_long = false;
+	n.wend = 0;
+	if (BIG && n.resumed) {
+		cont_resume(n.crec, w, rng, n.jn, n.ch, lane);
+		n.mutated = true; n.pick_is_mutation = false;
+		n.phase = P_MODEL;
+	}
+	/* the host passes the pick records only when the split form ran */
+	if ((MODE == MGL_NBR_REST || (BIG && a.pickrec != nullptr)) && !n.mutated) nbr_take_pick<MODE, FUSED>(a, lane, n, rng, hand);
+
+	/* ---- the rest runs as a small phase machine so that each big piece of code (model load, chain re-simulation, top-K) exists
+	 * exactly once in the kernel: the mutation's top-K pick and a repair's top-K pick share one site, and so do the overlay
+	 * re-simulation (model at a repair position) and the final one.  Halves the code size and the register pressure. */
 	for (;;) {
-		if (MODE == MGL_NBR_REST && (phase == P_MODEL || phase == P_TOPK)) { ch.overflow = true; phase = P_OUT; continue; } /* repair pick without a continuation record: the next pass evaluates the neighbour again */
-		if (MODE != MGL_NBR_REST && phase == P_MODEL) {
-			/* the adaptive model the neighbour has at pick_pos: base model before the first base
-			 * packet at or after it (dense checkpoint + replay of < 64 bytes of base packets) ... */
-			if ((ch.n_ins + ch.n_rem) != 0 && !spilled) {
-				/* the model is about to overwrite the live lists (they share LDS): move the lists to a
-				 * global scratch slot and carry on from there */
-				uint32_t sl = 0;
-				if (lane == 0) sl = atomicAdd(big.spill_ctr, 1u);
-				sl = uni(sl);
-				if (sl >= big.slots) { ch.overflow = true; phase = P_OUT; continue; }
-				uint16_t* gik = big.ins_key + (size_t)sl * big.cap; uint32_t* gip = big.ins_pos + (size_t)sl * big.cap;
-				uint16_t* grk = big.rem_key + (size_t)sl * big.cap; uint32_t* grp = big.rem_pos + (size_t)sl * big.cap;
-				for (uint32_t i = lane; i < ch.n_ins; i += 64) { gik[i] = ch.ins_key[i]; gip[i] = ch.ins_pos[i]; }
-				for (uint32_t i = lane; i < ch.n_rem; i += 64) { grk[i] = ch.rem_key[i]; grp[i] = ch.rem_pos[i]; }
-				__threadfence_block();
-				wave_sync();
-				ch.ins_key = gik; ch.ins_pos = gip; ch.rem_key = grk; ch.rem_pos = grp;
-				ch.uctx = big.uctx + (size_t)sl * big.uctx_cap;
-				ch.cap = big.cap; ch.uctx_cap = big.uctx_cap;
-				spilled = true;
-			}
-			if constexpr (FUSED) model_load_inl(c, b, probs, T, pick_pos, lane);
-			else model_load(c, b, probs, T, pick_pos, lane);
-			if (PROF) pick_prof_mark(&pp, 2, lane);
-			if (!pick_is_mutation) prof_mark(prof, 5, lane); /* repair: base model at the pick position */
-			if (pick_is_mutation) {
-				prof_mark(prof, 1, lane); /* model at target */
-				if (c.diag_stop == 2) { if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = probs[lane]; } return; }
-			}
-			/* ... with the touched contexts overridden by their re-simulated values */
-			if ((ch.n_ins + ch.n_rem) != 0) { sim_limit = pick_pos; sim_overlay = true; phase = P_SIM; }
-			else phase = P_TOPK;
-		}
-		if (MODE == MGL_NBR_REST && phase == P_SIM) {
-			/* the second half ends here (always: it holds no re-simulation code of its own): the lists go to k_sim, which puts several wavefronts on the
-			 * contexts of one neighbour and writes the cost; journal and counters are written below */
-			uint16_t* gk = big.sim_keys + (size_t)j * (2u * big.chg_cap);
-			uint32_t* gp = big.sim_pos + (size_t)j * (2u * big.chg_cap);
-			for (uint32_t e = lane; e < ch.n_ins; e += 64) { gk[e] = ch.ins_key[e]; gp[e] = ch.ins_pos[e]; }
-			for (uint32_t e = lane; e < ch.n_rem; e += 64) { gk[big.chg_cap + e] = ch.rem_key[e]; gp[big.chg_cap + e] = ch.rem_pos[e]; }
-			/* no fence: the consumer is a later launch on a stream that waits for this one */
-			if (lane == 0) big.sim_hdr[j] = make_uint4(ch.n_ins, ch.n_rem, (uint32_t)(uint64_t)ch.direct, (uint32_t)((uint64_t)ch.direct >> 32));
-			sim_deferred = true;
-			phase = P_OUT;
-			continue;
-		}
-		if (MODE == MGL_NBR_FULL && phase == P_SIM) {
-			int64_t r;
-			if (BIG) r = coop_sim(c, b, big, prof_acc, smem, per_wave_bytes, T, ch, slot, sim_limit, sim_overlay ? probs : nullptr, lane, &too_many);
-			else r = chain_sim(b, ch, T, sim_limit, sim_overlay ? probs : nullptr, lane, &too_many);
-			wave_sync();
-			if (too_many) { phase = P_OUT; continue; }
-			if (sim_overlay) { prof_mark(prof, 6, lane); phase = P_TOPK; } /* repair: model overridden by the re-simulated values */
-			else { delta = r; prof_mark(prof, 4, lane); phase = P_OUT; }
-		}
-		if (MODE != MGL_NBR_REST && phase == P_TOPK) {
-			walk_from_state(tw, nb);
-			win_cover(tw.win, c, b.slab, tw.st.pos, lane);
-			mgl_pk picked;
-			bool ok;
-			if constexpr (MODE == MGL_NBR_PICK) ok = pick_from_top_k<4, true, PROF>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked, &plan, &pp);
-			else ok = pick_from_top_k<1>(c, tw, probs, T, lencost, pick_inc, pick_best, rng, lane, &picked);
-			if (MODE == MGL_NBR_PICK) {
-				if (lane == 0) pickrec[j] = make_uint4((uint32_t)picked, (uint32_t)(picked >> 32), rng.n, ok ? 1u : 0u); /* fused, too: the second pass restarts from it */
-				if (FUSED) { hand->m_first = uni64(picked); hand->rng_n = uni(rng.n); if (ok) hand->flags |= MGL_HAND_OK; }
-				if (PROF) pick_prof_mark(&pp, 14, lane);
-				if (PROF && pp.acc && lane == 0) pp.acc[2u * MGL_PICK_STAGES + j] = __builtin_readcyclecounter() - t_begin; /* a picking wavefront's lifetime */
-				return;
-			}
-			if (pick_is_mutation) {
-				if (!ok) { generate_failed = true; phase = P_OUT; continue; }
-				m_first = picked;
-				journal_set(jn, pos, first, m_first, lane);
-				pick_is_mutation = false;
-				prof_mark(prof, 2, lane); /* top-K */
-				if (c.diag_stop == 3 || (c.diag_stop >= 31 && c.diag_stop <= 39)) { if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = (uint32_t)m_first; } return; }
-			} else {
-				picked_pk = ok ? picked : pick_inc;
-				have_pick = true;
-				prof_mark(prof, 7, lane); /* repair: top-K */
-			}
-			win.base = 0xFFFFFFFFu;
-			phase = P_WALK;
-		}
-		if (MODE != MGL_NBR_PICK && phase == P_WALK) {
-			/* ---- two-pointer walk over neighbour packets (nb) and base packets (bs) */
-			bool request_pick = false;
-			while (nb.pos < c.n || bs.pos < c.n) {
-				if (ch.overflow || jn.overflow || too_many || ++guard > (BIG ? (1u << 20) : 4096u)) { ch.overflow = true; break; }
-				if (!first_packet && !have_pick && nb.pos == bs.pos && count >= 3) {
-					const bool same_ctx = nb.ctx_state == bs.ctx_state;
-					const bool same_d = nb.dists[0] == bs.dists[0] && nb.dists[1] == bs.dists[1] && nb.dists[2] == bs.dists[2] &&
-					                    nb.dists[3] == bs.dists[3];
-					if (same_ctx && wsoft == 0xFFFFFFFFu) wsoft = nb.pos;
-					if (same_ctx && same_d) break; /* the rest of the file is coded identically */
-					if (same_ctx && nb.ctx_state < 7) {
-						/* plain literals up to the next special packet code identically: skip them */
-						uint32_t sx = uni(sp_find_next(b, nb.pos));
-						if (sx == MGL_POS_INF || sx > c.n) sx = c.n;
-						if (sx > nb.pos) {
-							const uint32_t cs = lit_steps(nb.ctx_state, sx - nb.pos);
-							nb.pos = bs.pos = sx; nb.ctx_state = bs.ctx_state = cs;
-							count = 8;
-							continue;
-						}
-					}
-				}
-				if (walked > MGL_MAX_WALK && !have_pick) { walk_long = true; break; }
-				if ((have_pick || nb.pos <= bs.pos) && nb.pos < c.n) {
-					/* ---- next neighbour packet: repair rules of packet_slab_neighbour.c:82-117 */
-					const uint32_t p = nb.pos;
-					win_cover(win, c, b.slab, p, lane);
-					mgl_pk pk, old = 0;
-					if (have_pick) {
-						pk = picked_pk; old = resume_old; have_pick = false; /* back from the top-K pick for this packet */
-					} else if (first_packet) {
-						pk = m_first; /* :169 the mutated packet is coded as is */
-					} else {
-						if (count < 8) count++;
-						old = (second_set && p == pos + 1) ? m_second : win_pk(win, p);
-						pk = old;
-						uint32_t type = mgl_pk_type(pk);
-						if (type == MGL_SHORT_REP || (type == MGL_LITERAL && count < 4)) {
-							const bool same = nb.dists[0] < p && win_byte(win, p) == c.data[p - nb.dists[0] - 1];
-							if (same) { if (count < 4) pk = MGL_PK_SHORT_REP; }
-							else pk = MGL_PK_LITERAL;
-						}
-						type = mgl_pk_type(pk);
-						if (type == MGL_LONG_REP) {
-							const uint32_t len = mgl_pk_len(pk);
-							uint32_t idx = mgl_pk_dist(pk);
-							walk_from_state(tw, nb);
-							bool ok = long_rep_ok(c, tw, idx, len, lane);
-							for (uint32_t i = 0; i < 4 && !ok; i++) { idx = i; ok = long_rep_ok(c, tw, idx, len, lane); }
-							pk = mgl_pack(MGL_LONG_REP, idx, len);
-							if (!ok) {
-								if (++npicks > MGL_MAX_REPAIR_PICKS) { walk_long = true; break; }
-								pick_best = (nbr_draw(rng) % 4u) == 0;
-								/* the model at p needs every base packet that starts before p priced in */
-								while (bs.pos < p && !ch.overflow) {
-									win_cover(win, c, b.slab, bs.pos, lane);
-									const mgl_pk bpk = win_pk(win, bs.pos);
-									mgl_plan bpl;
-									plan_at(c.L, c.data, bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk), win_byte(win, bs.pos), bpl);
-									changes_add<false>(ch, bpl, bs.pos, lane);
-									mgl_advance(&bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk));
-								}
-								if (ch.overflow) break;
-								if (MODE == MGL_NBR_REST && big.cont != nullptr) {
-									/* the second half holds no top-K code: the walk as it stands goes to a continuation record (state, journal;
-									 * the change lists to the slot's list area) and the second pass takes it up at this pick.  Saved here, where
-									 * everything is live anyway, so that the walk loop carries no value for it */
-									uint32_t slot2 = 0;
-									if (lane == 0) {
-										atomicAdd(big.spill_ctr + 1, 1u); /* repair picks this step */
-										slot2 = atomicAdd(todo_count, 1u);
-										todo[slot2] = j;
-										out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = 0; out.win[2u * j] = pos; out.win[2u * j + 1u] = MGL_WIN_NONE;
-									}
-									slot2 = uni(slot2);
-									if (slot2 < big.slots) { /* else: no scratch slot, the second pass sends it on to the full walk */
-										uint16_t* gik = big.ins_key + (size_t)slot2 * big.cap; uint32_t* gip = big.ins_pos + (size_t)slot2 * big.cap;
-										uint16_t* grk = big.rem_key + (size_t)slot2 * big.cap; uint32_t* grp = big.rem_pos + (size_t)slot2 * big.cap;
-										for (uint32_t i = lane; i < ch.n_ins; i += 64) { gik[i] = ch.ins_key[i]; gip[i] = ch.ins_pos[i]; }
-										for (uint32_t i = lane; i < ch.n_rem; i += 64) { grk[i] = ch.rem_key[i]; grp[i] = ch.rem_pos[i]; }
-										uint32_t* rec = big.cont + (size_t)slot2 * MGL_CONT_WORDS;
-										if (lane < jn.count) {
-											rec[48u + lane] = jn.pos[lane];
-											reinterpret_cast<mgl_pk*>(rec + 112u)[lane] = jn.old[lane];
-											reinterpret_cast<mgl_pk*>(rec + 240u)[lane] = jn.neu[lane];
-										}
-										if (lane == 0) {
-											rec[1] = j; rec[2] = pos;
-											rec[3] = nb.pos; rec[4] = nb.ctx_state; rec[5] = nb.dists[0]; rec[6] = nb.dists[1]; rec[7] = nb.dists[2]; rec[8] = nb.dists[3];
-											rec[9] = bs.pos; rec[10] = bs.ctx_state; rec[11] = bs.dists[0]; rec[12] = bs.dists[1]; rec[13] = bs.dists[2]; rec[14] = bs.dists[3];
-											rec[15] = count; rec[16] = walked; rec[17] = npicks; rec[18] = wsoft; rec[19] = taint; rec[20] = dep;
-											rec[21] = rng.n; rec[22] = guard; rec[23] = jn.count; rec[24] = ch.n_ins; rec[25] = ch.n_rem;
-											rec[26] = (pick_best ? 1u : 0u) | (second_set ? 2u : 0u);
-											rec[28] = (uint32_t)pk; rec[29] = (uint32_t)(pk >> 32);       /* the incumbent of the pick */
-											rec[30] = (uint32_t)old; rec[31] = (uint32_t)(old >> 32);     /* the packet the repair found at p */
-											rec[32] = (uint32_t)m_second; rec[33] = (uint32_t)(m_second >> 32);
-											rec[34] = (uint32_t)(uint64_t)ch.direct; rec[35] = (uint32_t)((uint64_t)ch.direct >> 32);
-											rec[36] = ch.n_cancel;
-											rec[0] = MGL_CONT_MAGIC; /* the reader is a later launch */
-										}
-									}
-									return;
-								}
-								resume_old = old; pick_pos = p; pick_inc = pk;
-								request_pick = true;
-								if (!BIG && lane == 0) atomicAdd(big.spill_ctr + 1, 1u); /* repair picks this step */
-								break; /* -> P_MODEL, then back here with have_pick */
-							}
-						}
-					}
-					if (!first_packet && pk != old) {
-						const mgl_pk base_old = (second_set && p == pos + 1) ? uni64(b.slab[p]) : old;
-						journal_set(jn, p, base_old, pk, lane);
-						wsoft = 0xFFFFFFFFu; /* a changed packet (a SHORT_REP the repair turned into a literal, say): the soft window reaches behind it */
-					}
-					first_packet = false;
-					walked++;
-					const uint32_t ntype = mgl_pk_type(pk), ndist = mgl_pk_dist(pk), nlen = mgl_pk_len(pk);
-					/* which rep distances this packet reads / pushes: bit k of taint = distance k comes from before the window */
-					if (ntype == MGL_SHORT_REP || ntype == MGL_LONG_REP) {
-						/* a rep packet: the soft window reaches at least to behind it -- unless it is the base's own packet at this
-						 * position reading a slot that holds the same distance in both walks (the move has no part in what it codes) */
-						const uint32_t slot = ntype == MGL_SHORT_REP ? 0u : ndist;
-						const bool same_read = bs.pos == p && win_pk(win, p) == pk && mgl_dist_at(&nb, slot) == mgl_dist_at(&bs, slot);
-						if (!same_read) wsoft = 0xFFFFFFFFu;
-						dep |= ntype == MGL_SHORT_REP ? (taint & 1u) : ((taint >> ndist) & 1u);
-					}
-					if (ntype == MGL_MATCH) taint = (taint << 1) & 0xFu;
-					else if (ntype == MGL_LONG_REP) taint = (taint & ~((2u << ndist) - 1u)) | ((taint & ((1u << ndist) - 1u)) << 1) | ((taint >> ndist) & 1u);
-					/* the base packet at the same position: identical coding cancels.  Which events a
-					 * packet produces depends on the packet, ctx_state, the position and -- for a literal
-					 * after a match -- the byte at rep distance 0; decided before anything is planned */
-					bool cancelled = false;
-					if (bs.pos == p && win_pk(win, p) == pk && nb.ctx_state == bs.ctx_state) {
-						cancelled = true;
-						if (ntype == MGL_LITERAL && nb.ctx_state >= 7) {
-							const uint32_t mn = nb.dists[0] < p ? c.data[p - nb.dists[0] - 1] : 0u;
-							const uint32_t mb = bs.dists[0] < p ? c.data[p - bs.dists[0] - 1] : 0u;
-							cancelled = mn == mb;
-						}
-					}
-					if (cancelled) {
-						mgl_advance(&bs, ntype, ndist, nlen);
-					} else {
-						/* of the base packet only a key per lane and two counts stay live while the neighbour's is planned */
-						uint32_t bkey = 0, bnev = 0, bndirect = 0;
-						if (bs.pos == p) {
-							const mgl_pk bpk = win_pk(win, p);
-							const uint32_t btype = mgl_pk_type(bpk), bdist = mgl_pk_dist(bpk), blen = mgl_pk_len(bpk);
-							mgl_plan bpl;
-							plan_at(c.L, c.data, bs, btype, bdist, blen, win_byte(win, p), bpl);
-							bnev = bpl.nev; bndirect = bpl.ndirect;
-							if (lane < bnev) {
-								uint32_t cx, bt;
-								mgl_plan_event(&bpl, lane, &cx, &bt);
-								bkey = cx | (bt << 15);
-							}
-							mgl_advance(&bs, btype, bdist, blen);
-						}
-						mgl_plan npl;
-						plan_at(c.L, c.data, nb, ntype, ndist, nlen, win_byte(win, p), npl);
-						changes_add_pair(ch, bkey, bnev, bndirect, npl, p, lane, big.evcancel != 0);
-					}
-					mgl_advance(&nb, ntype, ndist, nlen);
-				} else {
-					/* ---- a base packet the neighbour has already passed over: its events go away */
-					win_cover(win, c, b.slab, bs.pos, lane);
-					if (literal_run_events<false>(c, ch, win, bs, (nb.pos < c.n ? nb.pos : c.n) - bs.pos, lane)) continue;
-					const mgl_pk bpk = win_pk(win, bs.pos);
-					mgl_plan bpl;
-					plan_at(c.L, c.data, bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk), win_byte(win, bs.pos), bpl);
-					changes_add<false>(ch, bpl, bs.pos, lane);
-					mgl_advance(&bs, mgl_pk_type(bpk), mgl_pk_dist(bpk), mgl_pk_len(bpk));
-				}
-			}
-			if (walk_long) { phase = P_OUT; continue; }
-			if (request_pick) { prof_mark(prof, 3, lane); phase = P_MODEL; continue; }
-			prof_mark(prof, 3, lane); /* window walk */
-			if (c.diag_stop == 4) { if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = ch.n_ins + ch.n_rem; } return; }
-			if (ch.overflow || jn.overflow || too_many) { phase = P_OUT; continue; }
-			wend = nb.pos;
-			sim_limit = MGL_POS_INF; sim_overlay = false; phase = P_SIM;
-			continue;
-		}
-		if (phase == P_OUT) break;
+		if (MODE == MGL_NBR_REST && (n.phase == P_MODEL || n.phase == P_TOPK)) { n.ch.overflow = true; n.phase = P_OUT; continue; } /* repair pick without a continuation record: the next pass evaluates the neighbour again */
+		if (MODE != MGL_NBR_REST && n.phase == P_MODEL) { if (phase_model<PROF, FUSED>(c, b, a, lane, T, n, w, probs, pp)) return; }
+		if (MODE != MGL_NBR_PICK && n.phase == P_SIM) { phase_sim<BIG, MODE>(c, b, a, lane, T, n, probs); }
+		if (MODE != MGL_NBR_REST && n.phase == P_TOPK) { if (phase_topk<MODE, PROF, FUSED>(c, b, a, lane, T, n, w, rng, tw, probs, lencost, plan, pp, hand)) return; }
+		if (MODE != MGL_NBR_PICK && n.phase == P_WALK) { if (phase_walk<BIG, MODE>(c, b, a, lane, n, w, rng, tw)) return; }
+		if (n.phase == P_OUT) break;
 	}
 
-	if (generate_failed) { /* no candidate at the target (main.c:81-84 retries those) */
-		if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = 0; out.win[2u * j] = pos; out.win[2u * j + 1u] = MGL_WIN_NONE; }
-		return;
-	}
-	if (jn.overflow) { /* same rule as the full-walk path and the oracle: dropped */
-		if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = walked; out.win[2u * j] = pos; out.win[2u * j + 1u] = MGL_WIN_DROPPED; }
-		return;
-	}
-	if (walk_long || (ch.list_full && ch.cap == big.cap && !jn.overflow)) {
-		/* more inserted or removed events than the second pass's lists hold (MGL_BIG_CAP), or more than MGL_MAX_WALK packets
-		 * visited before the walks met again: dropped, like a neighbour with too long a journal; the oracle counts the same */
-		if (lane == 0) { out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = walked; out.win[2u * j] = pos; out.win[2u * j + 1u] = MGL_WIN_DROPPED; }
-		return;
-	}
-	if (ch.overflow || too_many) {
-		/* does not fit the change lists: hand it to the next pass (BIG, then the full-walk kernel) */
-		if (lane == 0) {
-			const uint32_t slot2 = atomicAdd(todo_count, 1u);
-			todo[slot2] = j;
-			if (BIG) atomicAdd((unsigned long long*)&ctl->fallback_nbrs, 1ull);
-			out.cost[j] = MGL_INVALID_COST; out.ndiffs[j] = 0; out.walked[j] = 0; out.win[2u * j] = pos; out.win[2u * j + 1u] = MGL_WIN_NONE;
-		}
-		return;
-	}
-	if (lane == 0 && ch.n_cancel) atomicAdd(big.spill_ctr + 3, ch.n_cancel); /* event pairs cancelled in the neighbours this step finished */
-	const uint64_t total = (uint64_t)((int64_t)ctl->rebuild_cost + delta + ch.direct); /* rebuild_cost: exact cost of the base */
-	uint32_t nd = 0;
-	for (uint32_t i = 0; i < jn.count; i++) {
-		if (jn.old[i] == jn.neu[i]) continue;
-		if (lane == 0) {
-			out.dpos[(size_t)j * MGL_MAX_DIFFS + nd] = jn.pos[i];
-			out.dold[(size_t)j * MGL_MAX_DIFFS + nd] = jn.old[i];
-			out.dnew[(size_t)j * MGL_MAX_DIFFS + nd] = jn.neu[i];
-		}
-		nd++;
-	}
-	if (lane == 0) { if (!sim_deferred) out.cost[j] = total; out.ndiffs[j] = nd; out.walked[j] = walked; out.win[2u * j] = pos; out.win[2u * j + 1u] = wend; out.win2[j] = (wsoft < wend ? wsoft : wend) | (dep << 31); }
-	if (prof_acc && lane == 0) /* diagnostic: wave lifetime (40 bits) | change events (12 bits) | packets walked (12 bits) */
-		prof_acc[32 + j] = ((__builtin_readcyclecounter() - t_begin) & 0xFFFFFFFFFFull) |
-		                   ((unsigned long long)((ch.n_ins + ch.n_rem) & 0xFFFu) << 40) | ((unsigned long long)(walked & 0xFFFu) << 52);
+	if (nbr_out_unfinished<BIG>(a, lane, n, w)) return;
+	nbr_out_result(a, lane, n, w);
 }
 
 template <bool BIG, int MODE, bool PROF = false>
@@ -1357,6 +1369,11 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_
 		__syncthreads();
 	}
 	const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+	/* the fused instance has no stage marks, and its `pickstate` is the launch's order (below); the fused launch's wavefront and the
+	 * second pass's evaluating one are their workgroups' wavefront 0 */
+	constexpr bool FUSED = MODE == MGL_NBR_PICKWALK;
+	const NbrArgs a{ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, FUSED ? nullptr : prof_acc, big, pickrec, j_base, j_end,
+	                FUSED ? nullptr : pickstate, smem, (FUSED || BIG) ? 0u : wid};
 	if constexpr (MODE == MGL_NBR_PICKWALK) {
 		/* one wavefront per workgroup: the pick body, then the walk body on the same LDS area (the pick's model and price
 		 * tables are dead by then).  Each body's returns end that body alone: a neighbour whose pick body returned early
@@ -1369,22 +1386,19 @@ __global__ void __launch_bounds__((MODE == MGL_NBR_PICK ? 512 : (BIG ? 64 * MGL_
 		PickHand hand;
 		hand.target = 0; hand.rng_n = 0; hand.ctx_state = 0; hand.dists[0] = hand.dists[1] = hand.dists[2] = hand.dists[3] = 0;
 		hand.first = hand.second = hand.m_first = hand.m_second = 0; hand.flags = 0;
-		nbr2_one<false, MGL_NBR_PICK, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, nullptr, smem, T,
-		                                           unit, lane, 0u, &hand);
+		nbr2_one<false, MGL_NBR_PICK, false, true>(c, b, a, lane, T, unit, &hand);
 		wave_sync(); /* the walk body's journal and lists overwrite what the pick body's lanes read */
-		nbr2_one<false, MGL_NBR_REST, false, true>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, nullptr, big, pickrec, j_base, j_end, nullptr, smem, T,
-		                                           unit, lane, 0u, &hand);
+		nbr2_one<false, MGL_NBR_REST, false, true>(c, b, a, lane, T, unit, &hand);
 	} else if (BIG) {
 		/* wavefront 0 takes the workgroup's neighbours one at a time; the others help with their re-simulations */
 		if (wid != 0) { coop_helpers(c, b, big, prof_acc, smem, per_wave_bytes, T, lane, wid); return; }
 		const uint32_t n = *big.todo_in_count;
 		for (uint32_t unit = blockIdx.x; unit < n; unit += gridDim.x)
-			nbr2_one<BIG, MODE, PROF>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T, unit, lane, 0u);
+			nbr2_one<BIG, MODE, PROF>(c, b, a, lane, T, unit);
 		if (lane == 0) { CoopCmd* cmd = coop_cmd(smem, per_wave_bytes); cmd->op = MGL_COOP_EXIT; cmd->gen = cmd->gen + 1u; }
 		__syncthreads(); /* A, for the last time: the helpers leave */
 	} else {
-		nbr2_one<BIG, MODE, PROF>(c, b, ctl, seed, step_override, K, out, per_wave_bytes, todo, todo_count, prof_acc, big, pickrec, j_base, j_end, pickstate, smem, T,
-		                    blockIdx.x * waves + wid, lane, wid);
+		nbr2_one<BIG, MODE, PROF>(c, b, a, lane, T, blockIdx.x * waves + wid);
 	}
 }
 
@@ -1517,27 +1531,6 @@ __global__ void __launch_bounds__(1024) k_rank_scan(uint32_t* pre, uint32_t nblk
 		if (tid == blockDim.x - 1u) s_base = bsum + incl;
 		__syncthreads();
 	}
-}
-
-/* Will neighbour j pick, or does it take a grow/shrink mutation and go straight into its walk?  A copy of the rule at the head of
- * nbr2_one's "mutate" stage (draw 1 of the neighbour's stream, the packets at the target and behind it, the rep distances
- * there, two input bytes), kept out of nbr2_one so that the neighbour kernels compile as they did.  It only orders a launch
- * (k_pick_order): a wrong answer costs time, never a result.  tests/test_gpu_pick_order.py holds the two together.  Every
- * load is inside its buffer whatever the slab holds: pos < n, and base_state_at looks at positions below pos. */
-__device__ __forceinline__ bool nbr_will_pick(const DevCtx& c, const Base2& b, uint32_t pos, uint64_t key)
-{
-	if (pos >= c.n || pos + 1 >= c.n || (mgl_rng_draw(key, 1) % 2u) != 0) return true;
-	const mgl_pk first = b.slab[pos], second = b.slab[pos + 1];
-	const uint32_t ft = mgl_pk_type(first), flen = mgl_pk_len(first);
-	const uint32_t st = mgl_pk_type(second), slen = mgl_pk_len(second), sdist = mgl_pk_dist(second);
-	if ((ft == MGL_LONG_REP || ft == MGL_MATCH) && flen > 2) return false;
-	if ((ft == MGL_LITERAL || ft == MGL_SHORT_REP) && (st == MGL_MATCH || st == MGL_LONG_REP)) {
-		uint32_t d = sdist;
-		if (st == MGL_LONG_REP) { const mgl_wstate nb = base_state_at(b, pos); d = mgl_dist_at(&nb, sdist); }
-		const uint32_t rep_start = pos - d;
-		if (slen < MGL_MAX_MATCH && rep_start > 0 && rep_start <= pos && c.data[pos] == c.data[rep_start - 1]) return false;
-	}
-	return true;
 }
 
 /* the step's targets: one wavefront per neighbour (mgl_device.h:stratified_target; draw 0 of the neighbour's stream picks the
