@@ -37,6 +37,9 @@
  *   mgl_sa_set_target_weights, mgl_sa_weight_targets_by_cost, mgl_sa_target_weights, mgl_weight_value
  *                     no reference counterpart: a step's targets drawn in proportion to a weight per input byte, the
  *                                    weights the caller's or the cost map of a slab
+ *   mgl_cost_map_live, mgl_sa_set_live_weights, mgl_sa_live_weights
+ *                     no reference counterpart: the cost map of the current slab read off the engine's event chains instead
+ *                                    of walked, and target weights made again from it inside mgl_sa_run
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -383,6 +386,49 @@ int mgl_sa_weight_targets_by_cost(mgl_sa* sa, const mgl_packet* packets, uint32_
 int mgl_sa_target_weights(mgl_sa* sa, uint32_t* weights_out, uint64_t* total, uint64_t* window);
 /* host arithmetic only, no device: the value v neighbour j draws.  MGL_EINVAL: W == 0, W >= 2^44, K == 0, K > 2^20, j >= K, v NULL */
 int mgl_weight_value(uint64_t W, uint32_t K, uint32_t j, uint64_t seed, uint64_t step, uint64_t* v);
+/* Live target weights (no reference counterpart; DESIGN.md sections 4 and 10): the weights of
+ * mgl_sa_weight_targets_by_cost(sa, NULL, floor, ..) made again inside mgl_sa_run, from the live cost map (mgl_cost_map_live;
+ * the walk's map on the full-walk engine, the same integers).  The rule, with g = the handle's global step number (the steps
+ * run since the handle was made):
+ *   - When.  Before step g takes its targets the weights are refreshed if g % every == 0, or if the handle is stale: live
+ *     weights were just enabled, or the current slab was replaced from outside a run since the last refresh
+ *     (mgl_sa_begin_epoch, mgl_sa_set_slab, the seeds, an adopted re-parse).  Nothing else refreshes.  A refresh sets
+ *     w[x] = live map[x] + floor of the slab as it stands before step g -- floor the configured one, or with floor_mean
+ *     total / n of that very map, what mgl_sa_weight_targets_by_cost adds when handed total / n -- and makes the prefix sums
+ *     and the window's weight as every setting of weights does.  So a trajectory does not depend on how it is cut into
+ *     mgl_sa_run calls, and it is the trajectory of a caller who calls mgl_sa_weight_targets_by_cost before every such step.
+ *   - MGL_LW_SINGLE_ONLY.  A step takes its targets by the weights only if it goes the single route; a bulk-route step uses
+ *     the rule without weights and makes no refresh, and a refresh that falls due during bulk steps (the stale case
+ *     included) happens before the first single step after them.  Under MGL_ACCEPT_SINGLE the flag changes nothing, under
+ *     MGL_ACCEPT_BULK weights never apply, and under MGL_ACCEPT_AUTO they come on exactly when the device's own counters say
+ *     the slab has stopped offering bulk_threshold improving neighbours per step -- reproducible for the reason AUTO is.
+ *   - Sum.  A refresh whose weights sum to 2^44 or more leaves the steps up to the next refresh to the rule without weights
+ *     and counts in `skipped`; the run does not fail.
+ * mgl_neighbours honours the weights in force and never refreshes; mgl_sa_target_weights returns the last refresh's weights
+ * (all 0 before the first).  The focus window composes as with any weights (W == 0: the rule without weights; nothing below
+ * lo is written).  mgl_sa_set_target_weights and mgl_sa_weight_targets_by_cost turn live weights off (explicit weights
+ * replace them); enabling live weights replaces explicit ones.  Slab, costs, RNG streams, MGL_ACCEPT_AUTO's block, the focus
+ * window and mgl_sa_stats are untouched by enabling or disabling.  Device memory: the weights' 4 n + n / 8 bytes and 4 n for
+ * the map's marks, the handle's while live weights are on.  A refresh costs one read-back (the window's 16 bytes with the
+ * map's sums), as a block end costs one.
+ * cfg == NULL: off, weights cleared.  MGL_EINVAL, handle unchanged: every == 0, unknown flags, and without floor_mean a
+ * floor > 2^32 - 1 - 2^20 or floor * n >= 2^43; a handle created with MGL_F_POSITION_TARGETS.  MGL_ENOMEM: the buffers do not
+ * fit; the handle stays usable with no weights in force. */
+#define MGL_LW_SINGLE_ONLY 1u
+typedef struct {
+	uint32_t every;      /* steps between refreshes, >= 1 */
+	uint32_t floor;      /* added per byte; ignored with floor_mean */
+	uint32_t floor_mean; /* 1: floor = total / n of each refresh's map (what `cost:mean` adds) */
+	uint32_t flags;      /* MGL_LW_* */
+} mgl_live_weights_config;
+typedef struct {
+	uint64_t refreshes;  /* since enabled */
+	uint64_t skipped;    /* refreshes whose sum reached 2^44: that interval ran by the rule without weights */
+	uint64_t last_gstep, last_total; /* the last refresh: its step and its map's total */
+	double gpu_ms;       /* device time of all refreshes: map, weights, prefix sums */
+} mgl_live_weights_stats;
+int mgl_sa_set_live_weights(mgl_sa* sa, const mgl_live_weights_config* cfg /* NULL: off, weights cleared */);
+int mgl_sa_live_weights(mgl_sa* sa, mgl_live_weights_config* cfg_out, mgl_live_weights_stats* stats_out); /* every == 0: off */
 /* Adopt a best slab found elsewhere (another chain / GPU): replaces best slab and best cost.
  * `perplexity` must be the slab's exact cost: the slab is walked on the device at once, which refuses (MGL_EINVAL, nothing
  * adopted) an entry that is no packet or does not fit, and a cost other than `perplexity`.  That walk does not look at the
@@ -540,6 +586,20 @@ typedef struct {
 	double gpu_ms;                           /* device time of the call's kernels; 0 from the host form */
 } mgl_cost_report;
 int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_properties* props, uint32_t* map_out, mgl_cost_report* report);
+/* The cost map of the current slab without the walk (no reference counterpart; DESIGN.md section 10,
+ * megalania_amd/csrc/mgl_costmap_live.hip).  map_out (n entries, nullable) and every field of report (nullable) except gpu_ms
+ * equal, integer for integer, what mgl_cost_map(sa, NULL, NULL, map_out, report) returns at that moment: the current slab
+ * under the handle's own lc/lp/pb.  The incremental engine keeps every coded event of the current walk, with the
+ * probability before its update, in its event chains: an event's price is one table look-up and nothing is re-simulated,
+ * so the map is a data-parallel pass over the chains (milliseconds where the walk takes a second).  The chains exist under
+ * the handle's triple only: no foreign triple, no caller's slab.  A handle of the full-walk engine (MGL_F_FULLWALK) keeps
+ * no chains and is served by mgl_cost_map's walk, with the same integers.
+ *   - A parity hook: slab, costs, RNG streams, MGL_ACCEPT_AUTO's block, the focus window, the weights in force and
+ *     mgl_sa_stats stay as they were.
+ *   - Device memory as for mgl_cost_map, 8 bytes per input byte for the length of the call; MGL_ENOMEM, with the handle left
+ *     usable, when they do not fit (MGL_KEY_COSTMAP_NOMEM forces it here too).
+ *   - MGL_EDEVICE (device consistency check): the map's total is not the exact cost the control block holds. */
+int mgl_cost_map_live(mgl_sa* sa, uint32_t* map_out /* n, nullable */, mgl_cost_report* report /* nullable */);
 /* Final model state after costing `packets`: probabilities in the reference's struct order
  * (lzma_state.h:47-53: lit | len | rep_len | dist | ctx_state), ctx_state, rep distances. */
 int mgl_final_state(mgl_sa* sa, const mgl_packet* packets, uint16_t* probs_out, size_t probs_cap,
@@ -644,7 +704,7 @@ enum mgl_debug_key {
 	MGL_KEY_PICK_HINTS = 9,    /* pattern: overwrite the class hints (MGL_DUMP_PICK_HINTS) with 0: all 0, 1: all 1, 2: alternating, anything
 	                            * else: random bytes from `pattern`, and make the order (MGL_DUMP_PICK_ORDER) from them again -- the test
 	                            * of k_pick_order */
-	MGL_KEY_COSTMAP_NOMEM = 10 /* n: the next n calls of mgl_cost_map find no room for their buffers (MGL_ENOMEM; the handle stays usable) */
+	MGL_KEY_COSTMAP_NOMEM = 10 /* n: the next n calls of mgl_cost_map / mgl_cost_map_live find no room for their buffers (MGL_ENOMEM; the handle stays usable) */
 };
 /* What the in-place accepts compare against before they give up (MGL_KEY_LIMIT).  1-6: the single accept (mgl_kernels3.hip);
  * 7-10: both; 11-18: the batch accept (mgl_kernels5.hip). */

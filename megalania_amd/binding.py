@@ -43,7 +43,9 @@ HIP_SYMBOLS = [
     "mgl_comm_allgather_u64", "mgl_slab_hash", "mgl_sa_exchange_cross_all",
     "mgl_sa_set_focus", "mgl_sa_focus", "mgl_focus_slice", "mgl_cost_map",
     "mgl_sa_set_target_weights", "mgl_sa_weight_targets_by_cost", "mgl_sa_target_weights", "mgl_weight_value",
+    "mgl_cost_map_live", "mgl_sa_set_live_weights", "mgl_sa_live_weights",
 ]
+LW_SINGLE_ONLY = 1
 HOST_SYMBOLS = [
     "mgl_lzma_state_init", "mgl_lzma_state_free", "mgl_lzma_encode_packet", "mgl_lzma_encode_header",
     "mgl_range_encoder_new", "mgl_range_encoder_free", "mgl_perplexity_encoder_new", "mgl_file_output_new",
@@ -199,6 +201,15 @@ class CostReport(C.Structure):
         return d
 
 
+class LiveWeightsConfig(C.Structure):
+    _fields_ = [("every", C.c_uint32), ("floor", C.c_uint32), ("floor_mean", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LiveWeightsStats(C.Structure):
+    _fields_ = [("refreshes", C.c_uint64), ("skipped", C.c_uint64), ("last_gstep", C.c_uint64), ("last_total", C.c_uint64),
+                ("gpu_ms", C.c_double)]
+
+
 XO_MAX_PARENTS = 8
 
 
@@ -326,6 +337,9 @@ def hip_lib():
         L.mgl_sa_weight_targets_by_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.mgl_sa_target_weights.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mgl_weight_value.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.mgl_cost_map_live.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CostReport)]
+        L.mgl_sa_set_live_weights.argtypes = [C.c_void_p, C.POINTER(LiveWeightsConfig)]
+        L.mgl_sa_live_weights.argtypes = [C.c_void_p, C.POINTER(LiveWeightsConfig), C.POINTER(LiveWeightsStats)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -585,6 +599,24 @@ class SA:
         total, window = C.c_uint64(0), C.c_uint64(0)
         self._chk(self.L.mgl_sa_target_weights(self.h, _ptr(out), C.byref(total), C.byref(window)))
         return out, total.value, window.value
+
+    def set_live_weights(self, every, floor=0, floor_mean=False, single_only=False):
+        """Target weights made again from the live cost map before every step g with g % every == 0, and when the slab was
+        replaced from outside a run (mgl_sa_set_live_weights has the rule); every=None turns them off and clears the weights.
+        floor_mean: each refresh adds its map's total // n.  single_only: bulk-route steps neither use nor refresh them."""
+        if every is None:
+            self._chk(self.L.mgl_sa_set_live_weights(self.h, None))
+            return
+        cfg = LiveWeightsConfig(every, floor, int(bool(floor_mean)), LW_SINGLE_ONLY if single_only else 0)
+        self._chk(self.L.mgl_sa_set_live_weights(self.h, C.byref(cfg)))
+
+    def live_weights(self) -> dict:
+        """the live weights' configuration (every == 0: off) and what they did since they were enabled"""
+        cfg, st = LiveWeightsConfig(), LiveWeightsStats()
+        self._chk(self.L.mgl_sa_live_weights(self.h, C.byref(cfg), C.byref(st)))
+        return dict(every=cfg.every, floor=cfg.floor, floor_mean=bool(cfg.floor_mean), single_only=bool(cfg.flags & LW_SINGLE_ONLY),
+                    flags=cfg.flags, refreshes=st.refreshes, skipped=st.skipped, last_gstep=st.last_gstep, last_total=st.last_total,
+                    gpu_ms=st.gpu_ms)
 
     def step_modes(self) -> np.ndarray:
         """per step of the last run(): 0 single, 1 bulk"""
@@ -863,6 +895,14 @@ class SA:
         out = np.zeros(self.n, dtype=np.uint32)
         rep = CostReport()
         self._chk(self.L.mgl_cost_map(self.h, _ptr(slab), pr, _ptr(out), C.byref(rep)))
+        return out, rep.asdict(device=True)
+
+    def cost_map_live(self):
+        """cost_map() of the current slab under the handle's triple, read off the engine's event chains instead of walked
+        (mgl_cost_map_live; SA state untouched): the same integers, gpu_ms apart."""
+        out = np.zeros(self.n, dtype=np.uint32)
+        rep = CostReport()
+        self._chk(self.L.mgl_cost_map_live(self.h, _ptr(out), C.byref(rep)))
         return out, rep.asdict(device=True)
 
     def final_state(self, slab):

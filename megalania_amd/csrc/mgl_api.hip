@@ -15,6 +15,7 @@
 #include "mgl_adaptive.hip"
 #include "mgl_props.hip"
 #include "mgl_costmap.hip"
+#include "mgl_costmap_live.hip"
 #include "mgl_crossover.hip"
 #include "mgl_weights.hip"
 #include "../../include/megalania_hip.h"
@@ -146,6 +147,17 @@ struct LaunchForm {
 	bool form_single = false; /* the form the regular launch runs as right now */
 	uint32_t short_looks = 0; /* blocks of at most four steps still to come after a switch of the launch form */
 };
+/* mgl_sa_set_live_weights: the target weights made again from the live cost map (mgl_costmap_live.hip) inside mgl_sa_run.
+ * cfg.every == 0: off.  d_mark, d_sums: the refresh's own buffers beside the weights' three, the handle's while live weights are on */
+struct LiveWeights {
+	mgl_live_weights_config cfg = {};
+	mgl_live_weights_stats stats = {};
+	bool stale = false;            /* enabled, or the current slab replaced from outside a run, since the last refresh */
+	bool skip = false;             /* the last refresh's weights sum to 2^44 or more: launch_targets ignores them until the next one */
+	uint32_t* d_mark = nullptr;
+	CostMapSums* d_sums = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+};
 /* diagnostic hooks of the tests (mgl_debug_set) */
 struct TestHooks {
 	uint32_t xo_nomem = 0;   /* key 8: the next so many crossovers find no room for their buffers */
@@ -243,6 +255,8 @@ struct mgl_sa {
 	uint64_t* d_wt_pre = nullptr;
 	uint64_t* d_wt_blk = nullptr;
 	uint64_t wt_total = 0, wt_slo = 0, wt_window = 0;
+	bool wt_apply = true;          /* false only while a run's bulk-route steps pass under MGL_LW_SINGLE_ONLY: launch_targets then ignores the weights */
+	LiveWeights live;
 	/* made with the targets (launch_targets), for the fused launch: K bytes, 1 = the neighbour will pick, 0 = grow/shrink; and
 	 * K neighbour indices, every slice's picking neighbours in front of its others (k_pick_order).  Null: MGL_NO_ORDER=1,
 	 * position targets, no split form */
@@ -502,7 +516,7 @@ static void launch_targets(mgl_sa* sa, hipStream_t st, uint64_t step_override)
 	const uint32_t K = sa->cfg.neighbours_per_step;
 	const uint64_t* onwalk = sa->incremental ? sa->b2.onwalk : sa->base.v.onwalk;
 	const uint32_t nw0 = sa->incremental ? sa->b2.nw0 : (sa->ctx.n + 63u) >> 6;
-	if (sa->d_wt && sa->wt_window) { /* weights in force and the window weighs something: the weighted rule (mgl_weights.hip), which counts no packets */
+	if (sa->d_wt && sa->wt_window && sa->wt_apply && !sa->live.skip) { /* weights in force and the window weighs something: the weighted rule (mgl_weights.hip), which counts no packets */
 		hipLaunchKernelGGL(k_targets_weighted, dim3((K + 3u) / 4u), dim3(256), 0, st, sa->ctx, sa->b2, onwalk, nw0, (const Control*)sa->base.ctl, sa->cfg.seed, step_override, K,
 		                   sa->d_strat_tgt, sa->d_pick_hint, sa->focus_lo, sa->focus_hi ? sa->focus_hi : sa->n, (const uint32_t*)sa->d_wt, (const uint64_t*)sa->d_wt_pre,
 		                   sa->wt_slo, sa->wt_window);
@@ -1271,6 +1285,7 @@ static int replace_current(mgl_sa* sa, Put put, bool validate, int bad, const ch
 	if (rc) return rc;
 	if ((rc = keep_best_before_overwrite(sa, c))) return rc;
 	sa->autoacc.reset();
+	sa->live.stale = true; /* live weights: the next step refreshes them */
 	if ((rc = put())) return rc;
 	c.cur_cost = 0; c.accepted_flag = 0; c.copy_best_flag = 0; c.error_flags = 0;
 	if ((rc = write_ctl(sa, sa->base, &c))) return rc;
@@ -1299,6 +1314,7 @@ extern "C" int mgl_sa_begin_epoch(mgl_sa* sa, unsigned phase, int from_best)
 	int rc = read_ctl(sa, sa->base, &c);
 	if (rc) return rc;
 	if (from_best && c.best_cost == 0) from_best = 0; /* no best yet: packets_best is still the all-literal slab */
+	sa->live.stale = true; /* live weights: the next step refreshes them */
 	const bool snaps = sa->incremental && sa->snapshots;
 	const bool base_is_best = snaps && c.best_is_current;
 	if (!from_best && (rc = keep_best_before_overwrite(sa, c))) return rc;
@@ -1900,6 +1916,7 @@ extern "C" int mgl_sa_set_accept_mode(mgl_sa* sa, int mode, uint32_t bulk_thresh
 	return MGL_OK;
 }
 static int weights_window(mgl_sa* sa);
+static int live_refresh(mgl_sa* sa, uint64_t gstep);
 /* The focus window: host state only (with target weights in force, also what the window weighs).  Targets that were queued ahead
  * under the old window are made again. */
 extern "C" int mgl_sa_set_focus(mgl_sa* sa, uint64_t lo, uint64_t hi)
@@ -2164,6 +2181,24 @@ static int run_neighbours(mgl_sa* sa, bool zero_counts)
 	TRY(launch_neighbours(sa, ~0ull, zero_counts));
 	return mark(sa, T_NBR_END, sa->q.stream);
 }
+/* Live target weights, before step `gstep` of a run takes its targets (megalania_hip.h has the rule): under
+ * MGL_LW_SINGLE_ONLY a bulk-route step passes without weights and without a refresh; any other step refreshes if one is due
+ * or the handle is stale.  Targets queued ahead under the other setting are made again. */
+static int live_step(mgl_sa* sa, uint64_t gstep, bool bulk)
+{
+	LiveWeights& lw = sa->live;
+	const bool apply = !(bulk && (lw.cfg.flags & MGL_LW_SINGLE_ONLY));
+	if (apply != sa->wt_apply) {
+		sa->wt_apply = apply;
+		if (sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE;
+	}
+	if (!apply) {
+		if (gstep % lw.cfg.every == 0) lw.stale = true; /* due during bulk steps: before the first single step after them */
+		return MGL_OK;
+	}
+	if (lw.stale || gstep % lw.cfg.every == 0) return live_refresh(sa, gstep);
+	return MGL_OK;
+}
 /* One step by the single route: neighbours, the decision, then the in-place accept (launch_apply, which queues the targets of
  * step next_gstep ahead) or -- MGL_NO_INCREMENTAL_APPLY, the full-walk engine -- best-slab copy, rebuild and lazy snapshot */
 static int step_single(mgl_sa* sa, bool first, uint64_t next_gstep)
@@ -2259,6 +2294,7 @@ extern "C" int mgl_sa_run(mgl_sa* sa, uint64_t steps, mgl_sa_stats* stats)
 		const uint64_t block = block_length(sa, mode, full, steps - s);
 		for (uint64_t e = s + block; s < e; s++) {
 			if (sa->mode_log.size() < (1u << 20)) sa->mode_log.push_back(bulk ? 1 : 0);
+			if (sa->live.cfg.every) TRY(live_step(sa, before.gstep + s, bulk));
 			timer_begin_step(sa->timer, s, sa->form.split_nbr && !sa->form.form_single ? nbr_slices(sa) : 0u);
 			const uint64_t next_gstep = s + 1 < steps ? before.gstep + s + 1 : ~0ull;
 			const int rc = bulk ? step_bulk(sa, s == 0, next_gstep) : step_single(sa, s == 0, next_gstep);
@@ -2276,6 +2312,7 @@ extern "C" int mgl_sa_run(mgl_sa* sa, uint64_t steps, mgl_sa_stats* stats)
 	}
 	HIPCHK(hipEventRecord(sa->timer.ev_end, sa->q.stream));
 	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	sa->wt_apply = true; /* outside a run the weights in force hold (mgl_neighbours) */
 	TRY(read_ctl(sa, sa->base, &after));
 	adopt_form(sa, after);
 	if (stats) TRY(fill_stats(sa, before, after, rollbacks_before, traffic_before[0], stats));
@@ -2429,6 +2466,13 @@ static int cost_map_device(mgl_sa* sa, const mgl_pk* slab, const mgl_properties&
 	HIPCHK(hipEventElapsedTime(ms, tmp.t0, tmp.t1));
 	return MGL_OK;
 }
+static void cost_report_fill(mgl_cost_report* report, const CostMapSums& h, float ms)
+{
+	report->total = h.total; report->packets = h.packets;
+	for (uint32_t k = 0; k < MGL_CC_CLASSES; k++) { report->class_cost[k] = h.class_cost[k]; report->class_bits[k] = h.class_bits[k]; }
+	for (uint32_t t = 0; t < 4; t++) { report->type_cost[t] = h.type_cost[t]; report->type_packets[t] = h.type_packets[t]; report->type_bytes[t] = h.type_bytes[t]; }
+	report->gpu_ms = ms;
+}
 /* Where a parse spends its bits (mgl_costmap.hip).  Validity as in mgl_props_sweep: the walk of mgl_cost_slab decides it for a
  * caller's slab, and the current slab is read where it lies.  The call's two buffers -- a mark and a map entry per position,
  * 8 bytes per input byte -- are its own and die with it. */
@@ -2452,12 +2496,50 @@ extern "C" int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_pro
 	TRY(cost_map_device(sa, slab, pr, tmp, &h, &ms));
 	const size_t n = sa->n;
 	if (map_out) HIPCHK(hipMemcpy(map_out, tmp.map, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-	if (report) {
-		report->total = h.total; report->packets = h.packets;
-		for (uint32_t k = 0; k < MGL_CC_CLASSES; k++) { report->class_cost[k] = h.class_cost[k]; report->class_bits[k] = h.class_bits[k]; }
-		for (uint32_t t = 0; t < 4; t++) { report->type_cost[t] = h.type_cost[t]; report->type_packets[t] = h.type_packets[t]; report->type_bytes[t] = h.type_bytes[t]; }
-		report->gpu_ms = ms;
-	}
+	if (report) cost_report_fill(report, h, ms);
+	return MGL_OK;
+}
+/* the live map's kernel over the current base (incremental engine): zeroes the sums, leaves marks and sums on the device */
+static int launch_cost_map_live(mgl_sa* sa, uint32_t* mark, CostMapSums* sums)
+{
+	static_assert(MGL_CML_MAX_BLOCK == (1u << MGL_PB_MAX_SHIFT), "the live map's LDS marks hold the chain index's largest block");
+	hipStream_t s = sa->q.stream;
+	HIPCHK(hipMemsetAsync(sums, 0, sizeof *sums, s));
+	hipLaunchKernelGGL(k_cml_blocks, dim3(sa->b2.nsb < MGL_CML_GRID ? sa->b2.nsb : MGL_CML_GRID), dim3(MGL_CML_THREADS), 0, s, sa->ctx, sa->b2, mark, sums);
+	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+/* The cost map of the current slab from the event chains (mgl_costmap_live.hip): mgl_cost_map(sa, NULL, NULL, ..)'s integers
+ * without its walk.  The full-walk engine keeps no chains and is served by the walk. */
+extern "C" int mgl_cost_map_live(mgl_sa* sa, uint32_t* map_out, mgl_cost_report* report)
+{
+	static const char* nomem = "mgl_cost_map_live: the per-position buffers do not fit the device";
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	if (!sa->incremental) return mgl_cost_map(sa, nullptr, nullptr, map_out, report);
+	HIPCHK(hipSetDevice(sa->device));
+	if (sa->force.cm_nomem) { sa->force.cm_nomem--; return fail(MGL_ENOMEM, nomem); }
+	CostMapBufs tmp;
+	const size_t n = sa->n;
+	TRY(dnew(tmp.own, tmp.mark, n, -1, nomem));
+	TRY(dnew(tmp.own, tmp.map, n, -1, nomem));
+	TRY(dnew(tmp.own, tmp.sums, 1, -1, nomem));
+	HIPCHK(tmp.own.event(&tmp.t0));
+	HIPCHK(tmp.own.event(&tmp.t1));
+	hipStream_t s = sa->q.stream;
+	HIPCHK(hipEventRecord(tmp.t0, s));
+	TRY(launch_cost_map_live(sa, tmp.mark, tmp.sums));
+	hipLaunchKernelGGL(k_costmap_spread, dim3((sa->n + 255u) / 256u), dim3(256), 0, s, sa->n, (const uint32_t*)tmp.mark, tmp.map);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(tmp.t1, s));
+	CostMapSums h;
+	HIPCHK(hipMemcpyAsync(&h, tmp.sums, sizeof h, hipMemcpyDeviceToHost, s));
+	Control c;
+	TRY(read_ctl(sa, sa->base, &c));
+	if (h.total != c.rebuild_cost) return fail(MGL_EDEVICE, "mgl_cost_map_live: the chains' total is not the current cost (device consistency check)");
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, tmp.t0, tmp.t1));
+	if (map_out) HIPCHK(hipMemcpy(map_out, tmp.map, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+	if (report) cost_report_fill(report, h, ms);
 	return MGL_OK;
 }
 
@@ -2495,9 +2577,8 @@ static int weights_window(mgl_sa* sa)
 	sa->wt_slo = v[0]; sa->wt_window = v[1];
 	return MGL_OK;
 }
-/* the prefix structure over the weights in d_wt (the four launches of mgl_weights.hip), then the window.  Targets queued ahead
- * were made under the old weights, and may still be reading them: the second stream is waited for before this is called. */
-static int weights_commit(mgl_sa* sa, uint64_t total)
+/* the prefix structure over the weights in d_wt: the four launches of mgl_weights.hip, on the main stream */
+static int weights_prefix(mgl_sa* sa)
 {
 	hipStream_t st = sa->q.stream;
 	const uint32_t n = sa->n, ncell = wt_cells(n), nblk = wt_blocks(n);
@@ -2506,6 +2587,13 @@ static int weights_commit(mgl_sa* sa, uint64_t total)
 	hipLaunchKernelGGL(k_wt_scan, dim3(1), dim3(64), 0, st, sa->d_wt_blk, nblk, sa->d_wt_pre, ncell);
 	hipLaunchKernelGGL(k_wt_add, dim3((ncell + 255u) / 256u), dim3(256), 0, st, sa->d_wt_pre, ncell, (const uint64_t*)sa->d_wt_blk);
 	HIPCHK(hipGetLastError());
+	return MGL_OK;
+}
+/* the prefix structure, then the window.  Targets queued ahead were made under the old weights, and may still be reading them:
+ * the second stream is waited for before this is called. */
+static int weights_commit(mgl_sa* sa, uint64_t total)
+{
+	TRY(weights_prefix(sa));
 	sa->wt_total = total;
 	if (sa->tgt_ahead != TGT_NONE) sa->tgt_ahead = TGT_STALE;
 	return weights_window(sa);
@@ -2516,6 +2604,89 @@ static int weights_refuse(const mgl_sa* sa, const char* who)
 	if (!sa->d_strat_pre) return fail(MGL_EINVAL, std::string(who) + ": position targets (MGL_F_POSITION_TARGETS) take no weights");
 	return MGL_OK;
 }
+/* ---- live target weights (megalania_hip.h has the rule; mgl_costmap_live.hip the map) */
+/* live weights off: the refresh's buffers go, the weights' own stay for whoever set others */
+static void live_off(mgl_sa* sa)
+{
+	LiveWeights& lw = sa->live;
+	sa->own.release(lw.d_mark); sa->own.release(lw.d_sums); sa->own.release(lw.t0); sa->own.release(lw.t1);
+	lw = LiveWeights();
+}
+/* One refresh, before step `gstep` takes its targets and behind the previous step's accept on the main stream: the live map's
+ * marks (the serial walk's on the full-walk engine), w = map + floor straight into the weights, the prefix structure, the
+ * window.  One synchronisation: the window's words and the map's sums come back together. */
+static int live_refresh(mgl_sa* sa, uint64_t gstep)
+{
+	LiveWeights& lw = sa->live;
+	hipStream_t st = sa->q.stream;
+	const uint32_t n = sa->n;
+	/* targets queued ahead were made under the old weights and may still be reading them: the main stream waits for the second */
+	if (sa->tgt_ahead != TGT_NONE) { HIPCHK(hipStreamWaitEvent(st, sa->q.ev_tgt, 0)); sa->tgt_ahead = TGT_STALE; }
+	HIPCHK(hipEventRecord(lw.t0, st));
+	if (sa->incremental) {
+		TRY(launch_cost_map_live(sa, lw.d_mark, lw.d_sums));
+		hipLaunchKernelGGL(k_cml_check, dim3(1), dim3(1), 0, st, (const CostMapSums*)lw.d_sums, sa->base.ctl);
+	} else {
+		HIPCHK(hipMemsetAsync(lw.d_mark, 0, sizeof(uint32_t) * (size_t)n, st));
+		hipLaunchKernelGGL(k_costmap_walk, dim3(1), dim3(64), 0, st, sa->ctx, sa->ctx.L, (const mgl_pk*)sa->base.v.slab, lw.d_mark, lw.d_sums);
+	}
+	hipLaunchKernelGGL(k_cml_weights, dim3((n + 255u) / 256u), dim3(256), 0, st, n, (const uint32_t*)lw.d_mark, lw.cfg.floor, lw.cfg.floor_mean, (const CostMapSums*)lw.d_sums, sa->d_wt);
+	HIPCHK(hipGetLastError());
+	TRY(weights_prefix(sa));
+	HIPCHK(hipEventRecord(lw.t1, st));
+	CostMapSums h;
+	HIPCHK(hipMemcpyAsync(&h, lw.d_sums, sizeof h, hipMemcpyDeviceToHost, st));
+	TRY(weights_window(sa)); /* synchronises */
+	if (!sa->incremental && h.end_pos != n) return fail(MGL_EDEVICE, "live weights: the walk stopped inside the slab (device consistency check)");
+	const uint64_t floor = lw.cfg.floor_mean ? h.total / n : lw.cfg.floor;
+	sa->wt_total = h.total + floor * n;
+	lw.skip = sa->wt_total >= MGL_WT_MAX_TOTAL; /* this interval runs by the rule without weights */
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, lw.t0, lw.t1));
+	lw.stats.refreshes++; lw.stats.skipped += lw.skip ? 1u : 0u;
+	lw.stats.last_gstep = gstep; lw.stats.last_total = h.total; lw.stats.gpu_ms += ms;
+	lw.stale = false;
+	return MGL_OK;
+}
+extern "C" int mgl_sa_set_live_weights(mgl_sa* sa, const mgl_live_weights_config* cfg)
+{
+	static const char* nomem = "mgl_sa_set_live_weights: the buffers (8 n + n / 8 bytes) do not fit the device";
+	TRY(weights_refuse(sa, "mgl_sa_set_live_weights"));
+	if (cfg) {
+		if (cfg->every == 0) return fail(MGL_EINVAL, "mgl_sa_set_live_weights: every must be at least 1");
+		if (cfg->flags & ~MGL_LW_SINGLE_ONLY) return fail(MGL_EINVAL, "mgl_sa_set_live_weights: unknown flags");
+		if (!cfg->floor_mean && cfg->floor > 0xFFFFFFFFu - (1u << MGL_CM_COST_BITS)) return fail(MGL_EINVAL, "mgl_sa_set_live_weights: floor + a map entry must fit 32 bits");
+		if (!cfg->floor_mean && (uint64_t)cfg->floor * sa->n >= (MGL_WT_MAX_TOTAL >> 1)) return fail(MGL_EINVAL, "mgl_sa_set_live_weights: floor * n must stay below 2^43");
+	}
+	HIPCHK(hipSetDevice(sa->device));
+	HIPCHK(hipStreamSynchronize(sa->q.stream2));
+	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	live_off(sa);
+	weights_release(sa); /* explicit weights are replaced; none are in force until the first refresh */
+	if (!cfg) return MGL_OK;
+	LiveWeights& lw = sa->live;
+	int rc = weights_alloc(sa);
+	if (!rc) rc = dnew(sa->own, lw.d_mark, sa->n, -1, nomem);
+	if (!rc) rc = dnew(sa->own, lw.d_sums, 1, -1, nomem);
+	if (!rc && (sa->own.event(&lw.t0) != hipSuccess || sa->own.event(&lw.t1) != hipSuccess)) rc = fail(MGL_EDEVICE, "mgl_sa_set_live_weights: no event");
+	if (rc) { live_off(sa); weights_release(sa); return rc; }
+	/* until the first refresh the weights are all 0: the window weighs nothing, whoever asks (mgl_sa_set_focus, mgl_sa_target_weights) */
+	HIPCHK(hipMemsetAsync(sa->d_wt, 0, sizeof(uint32_t) * (size_t)sa->n, sa->q.stream));
+	HIPCHK(hipMemsetAsync(sa->d_wt_pre, 0, sizeof(uint64_t) * ((size_t)wt_cells(sa->n) + 1u), sa->q.stream));
+	lw.cfg = *cfg;
+	lw.cfg.floor_mean = cfg->floor_mean ? 1u : 0u;
+	if (lw.cfg.floor_mean) lw.cfg.floor = 0;
+	lw.stale = true;
+	return MGL_OK;
+}
+extern "C" int mgl_sa_live_weights(mgl_sa* sa, mgl_live_weights_config* cfg_out, mgl_live_weights_stats* stats_out)
+{
+	if (!sa) return fail(MGL_EINVAL, "null handle");
+	if (cfg_out) *cfg_out = sa->live.cfg;
+	if (stats_out) *stats_out = sa->live.stats;
+	return MGL_OK;
+}
+
 extern "C" int mgl_sa_set_target_weights(mgl_sa* sa, const uint32_t* weights)
 {
 	TRY(weights_refuse(sa, "mgl_sa_set_target_weights"));
@@ -2527,6 +2698,7 @@ extern "C" int mgl_sa_set_target_weights(mgl_sa* sa, const uint32_t* weights)
 	HIPCHK(hipSetDevice(sa->device));
 	HIPCHK(hipStreamSynchronize(sa->q.stream2));
 	HIPCHK(hipStreamSynchronize(sa->q.stream));
+	live_off(sa); /* explicit weights replace live ones */
 	if (!weights) { weights_release(sa); return MGL_OK; }
 	TRY(weights_alloc(sa));
 	HIPCHK(hipMemcpyAsync(sa->d_wt, weights, sizeof(uint32_t) * (size_t)sa->n, hipMemcpyHostToDevice, sa->q.stream));
@@ -2550,6 +2722,7 @@ extern "C" int mgl_sa_weight_targets_by_cost(mgl_sa* sa, const mgl_packet* packe
 	const uint64_t sum = h.total + (uint64_t)floor * sa->n; /* below 2^20 n + 2^32 n < 2^61 */
 	if (sum >= MGL_WT_MAX_TOTAL) return fail(MGL_EINVAL, "mgl_sa_weight_targets_by_cost: the weights must sum to less than 2^44");
 	HIPCHK(hipStreamSynchronize(sa->q.stream2));
+	live_off(sa); /* explicit weights replace live ones */
 	TRY(weights_alloc(sa));
 	hipLaunchKernelGGL(k_wt_from_map, dim3((sa->n + 255u) / 256u), dim3(256), 0, sa->q.stream, sa->n, (const uint32_t*)tmp.map, floor, sa->d_wt);
 	HIPCHK(hipGetLastError());

@@ -25,26 +25,7 @@
  * first).  The walk still stops at an entry that is no packet or runs off the end, and says where it stopped: a slab that
  * slipped through is reported, never read out of bounds or looped on.
  */
-#include "mgl_device.h"
-
-#define MGL_CM_CLASSES 6u      /* MGL_CC_*: kind, literal, length, rep length, distance, direct */
-#define MGL_CM_COST_BITS 20u   /* a mark: cost | len << 20 */
-/* at most MGL_MAX_EVENTS modelled bits of at most 22 528 (the table's largest entry) and 26 direct bits of 2 048 */
-static_assert(MGL_MAX_EVENTS * 22528u + 26u * 2048u < (1u << MGL_CM_COST_BITS), "a packet's cost must fit its mark");
-static_assert(MGL_MAX_MATCH < (1u << (32u - MGL_CM_COST_BITS)), "a packet's length must fit its mark");
-
-struct CostMapSums {
-	uint64_t total, packets;
-	uint64_t class_cost[MGL_CM_CLASSES], class_bits[MGL_CM_CLASSES];
-	uint64_t type_cost[4], type_packets[4], type_bytes[4];
-	uint32_t end_pos, pad; /* where the walk stopped: n for a slab the walk of mgl_cost_slab accepts */
-};
-
-/* the coder a context index belongs to, as an MGL_CC_* number (never MGL_CC_DIRECT: direct bits have no context) */
-__device__ __forceinline__ uint32_t costmap_class(uint32_t ctx)
-{
-	return ctx < MGL_OFF_LEN ? 0u : ctx < MGL_OFF_REP_LEN ? 2u : ctx < MGL_OFF_DIST ? 3u : ctx < MGL_OFF_LIT ? 4u : 1u;
-}
+#include "mgl_costmap.h"
 
 /* The sum of v over the wavefront (every lane active), wave-uniform.  This is the walk's one reduction per packet, so it
  * stays off the LDS crossbar that six __shfl_xor steps would cross: four row shifts inside the rows of 16 lanes (DPP

@@ -98,6 +98,13 @@ static const char usage_options[] =
 	"               byte and no stretch starves, cost:N adds N, cost:0 is the pure map.  file:PATH: one little-endian u32 per\n"
 	"               input byte, the format --cost-map writes (with --filter x86 per filtered byte), set once for the whole run;\n"
 	"               a file of another size is an error and nothing is written.  With --chains every chain has its own weights\n"
+	"  --live-weights R[:N|:mean][,single]  target weights that follow the search (mgl_sa_set_live_weights): before every R-th step\n"
+	"               of the handle, and before the first step of an epoch, the weights become the cost map of the slab as it\n"
+	"               stands plus a floor per byte -- N (default 0, the pure map) or, with mean, the map's mean --, read off the\n"
+	"               engine's event chains on the device.  ,single: only single-route steps use and refresh them, so that under\n"
+	"               --accept auto the weights come on once the slab has stopped offering improving neighbours in bulk.  One\n"
+	"               line per epoch on stderr: `live-weights: every R steps, floor F, refreshes M, skipped S, X ms` (the counts\n"
+	"               since the start).  Not together with --target-weights.  With --chains every chain has its own weights\n"
 	"  --cost-map FILE  where the emitted parse spends its bits (mgl_cost_map, under the run's final lc/lp/pb): FILE gets one\n"
 	"               little-endian u32 per input byte, the byte's share of its packet's exact cost (2048 per bit); the values\n"
 	"               sum to the parse's cost.  With --filter x86 the positions are those of the filtered bytes.  The emitted\n"
@@ -122,6 +129,7 @@ static void usage(const char* argv0)
 	        "          [--accept auto|single|bulk] [--chains N --rank R --comm-file PATH [--comm-nonce X] [--transport rccl|shm]\n"
 	        "          [--exchange best|cross|cross-all [--cross-grain N]]] [--focus LO:HI|rank]\n"
 	        "          [--target-weights cost[:mean|:N]|file:PATH]\n"
+	        "          [--live-weights R[:N|:mean][,single]]\n"
 	        "          [--cost-map FILE] [--cost-report] [--cost-bucket B] filename\n", argv0);
 	fputs(usage_options, stderr);
 }
@@ -167,6 +175,8 @@ typedef struct {
 	unsigned weights; /* WEIGHTS_* */
 	uint32_t weights_floor;
 	const char* weights_path;
+	bool live_given;
+	mgl_live_weights_config live; /* --live-weights */
 	/* files */
 	const char *filename, *out_path, *save_path, *load_path, *seed_stream_path, *comm_path, *cost_map_path;
 } cli_opts;
@@ -231,7 +241,30 @@ static const char* parse_target_weights(const char* v, cli_opts* o)
 	return NULL;
 }
 
-/* The last of a repeated option wins (--focus and --target-weights refuse a repeat), the last non-option argument is the file name. */
+/* --live-weights R[:N|:mean][,single]: the reason for a refusal, NULL for none */
+static const char* parse_live_weights(const char* v, cli_opts* o)
+{
+	static const char* const malformed = "--live-weights takes R, R:N, R:mean (R from 1, N from 0 to 4293918719), optionally followed by ,single";
+	char* end = NULL;
+	if (o->live_given) return "--live-weights given twice";
+	o->live_given = true;
+	if (v[0] < '0' || v[0] > '9') return malformed;
+	const unsigned long long every = strtoull(v, &end, 10);
+	if (every < 1 || every > 0xFFFFFFFFull) return malformed;
+	o->live = (mgl_live_weights_config){ .every = (uint32_t)every };
+	if (!strncmp(end, ":mean", 5)) { o->live.floor_mean = 1; end += 5; }
+	else if (*end == ':') {
+		if (end[1] < '0' || end[1] > '9') return malformed;
+		const unsigned long long n = strtoull(end + 1, &end, 10);
+		if (n > 0xFFFFFFFFull - (1u << 20)) return malformed; /* a map entry is below 2^20: entry + N fits 32 bits */
+		o->live.floor = (uint32_t)n;
+	}
+	if (!strcmp(end, ",single")) o->live.flags = MGL_LW_SINGLE_ONLY;
+	else if (*end) return malformed;
+	return NULL;
+}
+
+/* The last of a repeated option wins (--focus, --target-weights and --live-weights refuse a repeat), the last non-option argument is the file name. */
 static int parse_args(int argc, char** argv, cli_opts* o)
 {
 	/* the reference's seed (main.c:68), top K (:49), props 0/0/0 (:45) and schedule (:66,69) */
@@ -290,6 +323,7 @@ static int parse_args(int argc, char** argv, cli_opts* o)
 		else if (!strcmp(a, "--cross-grain")) { o->cross_grain = (uint32_t)strtoul(v, NULL, 0); o->cross_grain_given = true; }
 		else if (!strcmp(a, "--focus")) why = parse_focus(v, o);
 		else if (!strcmp(a, "--target-weights")) why = parse_target_weights(v, o);
+		else if (!strcmp(a, "--live-weights")) why = parse_live_weights(v, o);
 		else if (!strcmp(a, "--cost-map")) o->cost_map_path = v;
 		else if (!strcmp(a, "--cost-bucket")) { if (!number(v, &o->cost_bucket) || !o->cost_bucket) why = "--cost-bucket takes a number of bytes, at least 1"; }
 		else bad = true;
@@ -322,6 +356,7 @@ static int check_args(cli_opts* o)
 	if (o->filter != FILTER_NONE && !o->format_xz) return refuse(o, "--filter x86 / auto need --format xz: an .lzma stream has no place to declare a filter");
 	if (o->filter == FILTER_AUTO && (from_file || o->chains > 1)) return refuse(o, "--filter auto cannot be combined with --seed-stream, --load-slab or --chains above 1");
 	if (o->focus_rank && o->chains < 2) return refuse(o, "--focus rank needs --chains N with N at least 2");
+	if (o->live_given && o->weights != WEIGHTS_NONE) return refuse(o, "--live-weights and --target-weights exclude each other");
 	if (o->chains < 1 || o->rank < 0 || o->rank >= o->chains || (o->chains > 1 && !o->comm_path)) return refuse(o, NULL);
 
 	o->seed = (seed_spec){ o->adaptive ? o->adaptive : o->optimal, o->adaptive != 0, o->finder, o->mf_depth, o->parse_sweep, o->parse_sweep_table };
@@ -911,6 +946,26 @@ static int weigh_by_cost(cli_run* r)
 	return 0;
 }
 
+/* --live-weights: on before the first epoch, for the whole run */
+static int enable_live_weights(cli_run* r)
+{
+	if (!r->o->live_given) return 0;
+	return mgl_sa_set_live_weights(r->sa, &r->o->live) != MGL_OK ? lib_error() : 0;
+}
+
+/* --live-weights: what the refreshes did up to the end of this epoch's run */
+static int report_live_weights(cli_run* r)
+{
+	mgl_live_weights_stats st;
+	char floor[16] = "mean";
+	if (!r->o->live_given) return 0;
+	if (mgl_sa_live_weights(r->sa, NULL, &st) != MGL_OK) return lib_error();
+	if (!r->o->live.floor_mean) snprintf(floor, sizeof floor, "%u", r->o->live.floor);
+	fprintf(stderr, "live-weights: every %u steps, floor %s, refreshes %llu, skipped %llu, %.2f ms\n", r->o->live.every, floor,
+	        (unsigned long long)st.refreshes, (unsigned long long)st.skipped, st.gpu_ms);
+	return 0;
+}
+
 /* the plain exchange: every chain adopts the cheapest best slab */
 static int exchange_best(cli_run* r)
 {
@@ -988,7 +1043,7 @@ static int run_epochs(cli_run* r)
 			if (mgl_sa_run(r->sa, steps, &st) != MGL_OK) return lib_error();
 			fprintf(stderr, "current file size: %f\tbest: %f\tstep: %u\tepoch: %04u\t%.0f evals/s\n", bytes_f(st.current_cost), bytes_f(st.best_cost),
 			        phase + 1, epoch, st.gpu_ms_total > 0 ? st.evaluations / (st.gpu_ms_total * 1e-3) : 0.0);
-			if (exchange_and_report(r) || save_checkpoint(r, &st)) return -1;
+			if (report_live_weights(r) || exchange_and_report(r) || save_checkpoint(r, &st)) return -1;
 		}
 	}
 	return 0;
@@ -1087,6 +1142,7 @@ int main(int argc, char** argv)
 	    make_run_seed(&r) ||
 	    set_focus(&r) ||
 	    load_target_weights(&r) ||
+	    enable_live_weights(&r) ||
 	    run_epochs(&r) ||
 	    final_exchange(&r) ||
 	    fetch_best(&r) ||
