@@ -704,7 +704,9 @@ enum mgl_debug_key {
 	MGL_KEY_PICK_HINTS = 9,    /* pattern: overwrite the class hints (MGL_DUMP_PICK_HINTS) with 0: all 0, 1: all 1, 2: alternating, anything
 	                            * else: random bytes from `pattern`, and make the order (MGL_DUMP_PICK_ORDER) from them again -- the test
 	                            * of k_pick_order */
-	MGL_KEY_COSTMAP_NOMEM = 10 /* n: the next n calls of mgl_cost_map / mgl_cost_map_live find no room for their buffers (MGL_ENOMEM; the handle stays usable) */
+	MGL_KEY_COSTMAP_NOMEM = 10, /* n: the next n calls of mgl_cost_map / mgl_cost_map_live find no room for their buffers (MGL_ENOMEM; the handle stays usable) */
+	MGL_KEY_PROBE_FORM = 11    /* which form of the top-K search mgl_top_k probes: 0 (the default) the pick half's, batched set-up and four entries
+	                            * a lane; 1 the in-place form of the repair picks, the one-kernel form and the full-walk engine (anything else: MGL_EINVAL) */
 };
 /* What the in-place accepts compare against before they give up (MGL_KEY_LIMIT).  1-6: the single accept (mgl_kernels3.hip);
  * 7-10: both; 11-18: the batch accept (mgl_kernels5.hip). */

@@ -913,7 +913,10 @@ class SA:
         self._chk(self.L.mgl_final_state(self.h, _ptr(slab), _ptr(probs), self.nprobs, C.byref(cs), _ptr(dists)))
         return dict(probs=probs, ctx_state=cs.value, dists=dists)
 
-    def top_k(self, slab, position):
+    def top_k(self, slab, position, form=None):
+        """form: probe this form of the search from now on (KEY.PROBE_FORM: 0 batched set-up, 1 in place)"""
+        if form is not None:
+            self.debug_set(KEY.PROBE_FORM, form)
         slab = np.ascontiguousarray(slab, dtype=PACKET)
         out = np.zeros(64, dtype=PACKET)
         costs = np.zeros(64, dtype=np.uint64)

@@ -3,6 +3,7 @@
  * A handle's DevOwner (mgl_owner.h) owns its device memory, pinned buffers, events and its three HIP streams (StepQueues);
  * no host thread is created.
  */
+#include "mgl_topk.hip"
 #include "mgl_kernels.hip"
 #include "mgl_kernels2.hip"
 #include "mgl_kernels3.hip"
@@ -216,6 +217,7 @@ struct mgl_sa {
 	uint32_t* d_todo;       /* [0] = count, [1..K] = neighbour indices for the full-walk fallback */
 	uint32_t per_wave2, waves_per_block2, nbr2_lds, build_lds;
 	uint32_t big_waves = MGL_BIG_WAVES; /* wavefronts of a second-pass workgroup (mgl_debug_set key 7 lowers it for tests) */
+	uint32_t probe_form = 0;            /* the form of the top-K search mgl_top_k probes (MGL_KEY_PROBE_FORM) */
 	uint32_t chg_cap = MGL_CHG_CAP; /* events per first-pass list */
 	uint32_t per_wave_pick, per_wave_rest, pick_waves; /* LDS per wavefront of the two halves of the split launch */
 	uint32_t fused_lds;     /* its dynamic LDS: one wavefront, the larger of the two halves' areas */
@@ -1037,7 +1039,8 @@ static int set_launch_geometry(mgl_sa* sa, size_t n, uint32_t ckpt_elems)
 	sa->walk_lds = 4096u + ckpt_elems * 2u + MGL_PRICE_WORDS * 4u;
 	HIPCHK(hipFuncSetAttribute((const void*)k_neighbours, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->nbr_lds));
 	HIPCHK(hipFuncSetAttribute((const void*)k_rebuild, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->walk_lds));
-	HIPCHK(hipFuncSetAttribute((const void*)k_topk_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->walk_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_topk_probe<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->walk_lds));
+	HIPCHK(hipFuncSetAttribute((const void*)k_topk_probe<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sa->walk_lds));
 	if (!sa->incremental) return MGL_OK;
 
 	/* journal + context bitmap + max(model + price tables, change lists + context list) */
@@ -2902,7 +2905,8 @@ extern "C" int mgl_top_k(mgl_sa* sa, const mgl_packet* packets, size_t position,
 	Control c;
 	int rc = scratch_walk(sa, packets, false, false, &c);
 	if (rc) return rc;
-	hipLaunchKernelGGL(k_topk_probe, dim3(1), dim3(64), sa->walk_lds, sa->q.stream, sa->ctx, sa->scratch.v, (uint32_t)position,
+	const auto probe = sa->probe_form ? k_topk_probe<1> : k_topk_probe<0>;
+	hipLaunchKernelGGL(probe, dim3(1), dim3(64), sa->walk_lds, sa->q.stream, sa->ctx, sa->scratch.v, (uint32_t)position,
 	                   sa->d_topk_pk, sa->d_topk_cost, sa->d_small);
 	HIPCHK(hipGetLastError());
 	uint32_t cnt = 0;
@@ -3134,6 +3138,10 @@ extern "C" int mgl_debug_set(mgl_sa* sa, uint32_t key, uint64_t value)
 	case MGL_KEY_CROSS_NOMEM: sa->force.xo_nomem = (uint32_t)value; return MGL_OK;
 	case MGL_KEY_PICK_HINTS: return set_pick_hints(sa, value);
 	case MGL_KEY_COSTMAP_NOMEM: sa->force.cm_nomem = (uint32_t)value; return MGL_OK;
+	case MGL_KEY_PROBE_FORM:
+		if (value > 1) return fail(MGL_EINVAL, "mgl_debug_set: probe form 0 (batched) or 1 (in place)");
+		sa->probe_form = (uint32_t)value;
+		return MGL_OK;
 	default: return fail(MGL_EINVAL, "mgl_debug_set: unknown key");
 	}
 }

@@ -26,7 +26,29 @@
                             * given up and dropped: rep distances that no match ever flushes (long runs coded as rep matches) keep two
                             * walks apart for kilobytes; the oracle counts the same packets */
 #define MGL_MAX_TOPK 32u
-#define MGL_PRICE_WORDS 1072u         /* top-K price tables per wavefront (u32): 2x272 lengths, 4x64 slots, 128 tails, 16 align, 64 slot bounds, 64 suffix minima */
+#define MGL_PRICE_WORDS 1072u         /* top-K price tables per wavefront (u32): the layout below */
+/* The price tables of one top-K query (mgl_topk.hip), the way LZMA encoders price candidates (lzma_packet_encoder.c:42-104), in
+ * u32 words from the wavefront's table base.  Lengths 2..17 are priced when a query starts, 18.. (the 8-bit high tree) only
+ * when a match that long shows up. */
+enum PriceOff : uint32_t {
+	PT_LEN_MATCH = 0,                      /* match coder: price of length l at [l - 2], l = 2..273 */
+	PT_LEN_REP = PT_LEN_MATCH + 272u,      /* rep coder: the same */
+	PT_SLOT = PT_LEN_REP + 272u,           /* distance slot s in length context k (lengths 2, 3, 4, 5+) at [64 k + s] */
+	PT_TAIL = PT_SLOT + 4u * 64u,          /* reverse-tree tail of every distance below 128 */
+	PT_ALIGN = PT_TAIL + 128u,             /* the four align bits */
+	PT_LBSLOT = PT_ALIGN + 16u,            /* per slot: the least a distance of that slot costs in any length context (pruning bound) */
+	PT_SUFMIN = PT_LBSLOT + 64u,           /* [s] = the least of lbslot[s..63] */
+	PT_END = PT_SUFMIN + 64u
+};
+static_assert(PT_END == MGL_PRICE_WORDS, "the price tables' parts add up to MGL_PRICE_WORDS");
+struct PriceTab { uint32_t *len_m, *len_r, *slot, *tail, *align, *lbslot, *sufmin; };
+__device__ __forceinline__ PriceTab price_tab(uint32_t* base)
+{
+	PriceTab p;
+	p.len_m = base + PT_LEN_MATCH; p.len_r = base + PT_LEN_REP; p.slot = base + PT_SLOT; p.tail = base + PT_TAIL;
+	p.align = base + PT_ALIGN; p.lbslot = base + PT_LBSLOT; p.sufmin = base + PT_SUFMIN;
+	return p;
+}
 #define MGL_SEQ_MASK ((1ull << 44) - 1ull)
 #define MGL_INVALID_COST (~0ull)
 
@@ -369,3 +391,6 @@ __device__ __forceinline__ bool lit_run_plan(const DevCtx& c, const Win& win, co
 	if (out.active) mgl_plan_event(&pl, lane - i * 9u, &out.ctx, &out.bit);
 	return true;
 }
+/* model and walk state of prefix checkpoint ci into `probs` and `w`; returns the cost up to there (mgl_kernels.hip; the
+ * top-K probe of mgl_topk.hip, which stands in front of it, starts from one too) */
+__device__ __forceinline__ uint64_t ckpt_load(const BaseView& b, const DevCtx& c, uint32_t ci, uint16_t* probs, Walk& w, uint32_t lane);

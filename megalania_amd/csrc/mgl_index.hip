@@ -8,7 +8,7 @@
  * digit-major histogram matrix, and a scatter in which a wavefront ranks its 64 items among equal
  * digits with ballots, so equal keys keep their position order.  bucket_off is then read off the
  * sorted keys.  The dictionary window (dict_limit) is applied at query time by a search inside
- * the bucket (bucket_lower_bound, mgl_kernels.hip), so the index itself is window-independent.
+ * the bucket (bucket_lower_bound, mgl_topk.hip), so the index itself is window-independent.
  * A second order of the same positions -- by the four bytes at the position, then by position
  * (two more passes in front) -- groups, inside every bigram bucket, the entries that agree on
  * the next two bytes as well: a top-K query reads its >= 4-byte matches as one contiguous,

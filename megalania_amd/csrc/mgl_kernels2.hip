@@ -902,7 +902,7 @@ __device__ __forceinline__ bool phase_model(const DevCtx& c, const Base2& b, con
 	}
 	if constexpr (FUSED) model_load_inl(c, b, probs, T, w.pick_pos, lane);
 	else model_load(c, b, probs, T, w.pick_pos, lane);
-	if (PROF) pick_prof_mark(&pp, 2, lane);
+	if (PROF) pick_prof_mark(&pp, PS_MODEL, lane);
 	if (!n.pick_is_mutation) prof_mark(n.prof, 5, lane); /* repair: base model at the pick position */
 	if (n.pick_is_mutation) {
 		prof_mark(n.prof, 1, lane); /* model at target */
@@ -962,7 +962,7 @@ __device__ __forceinline__ bool phase_topk(const DevCtx& c, const Base2& b, cons
 	if (MODE == MGL_NBR_PICK) {
 		if (lane == 0) a.pickrec[j] = make_uint4((uint32_t)picked, (uint32_t)(picked >> 32), rng.n, ok ? 1u : 0u); /* fused, too: the second pass restarts from it */
 		if (FUSED) hand_put_pick(hand, picked, rng, ok);
-		if (PROF) pick_prof_mark(&pp, 14, lane);
+		if (PROF) pick_prof_mark(&pp, PS_DRAW, lane);
 		if (PROF && pp.acc && lane == 0) pp.acc[2u * MGL_PICK_STAGES + j] = __builtin_readcyclecounter() - n.t_begin; /* a picking wavefront's lifetime */
 		return true;
 	}
@@ -972,7 +972,7 @@ __device__ __forceinline__ bool phase_topk(const DevCtx& c, const Base2& b, cons
 		journal_set(n.jn, n.pos, n.first, n.m_first, lane);
 		n.pick_is_mutation = false;
 		prof_mark(n.prof, 2, lane); /* top-K */
-		if (c.diag_stop == 3 || (c.diag_stop >= 31 && c.diag_stop <= 39)) { if (lane == 0) nbr_out_diag(a.out, j, (uint32_t)n.m_first); return true; }
+		if (c.diag_stop == 3 || (c.diag_stop >= TS_FIRST && c.diag_stop <= TS_LAST)) { if (lane == 0) nbr_out_diag(a.out, j, (uint32_t)n.m_first); return true; }
 	} else {
 		w.picked_pk = ok ? picked : w.pick_inc;
 		w.have_pick = true;
@@ -1302,9 +1302,9 @@ __device__ __forceinline__ void nbr2_one(const DevCtx& c, const Base2& b, const 
 	 * sources level by level, in front of the model load instead of source by source behind it */
 	TopkPlan plan;
 	if (MODE == MGL_NBR_PICK) {
-		if (PROF) pick_prof_mark(&pp, 0, lane);
+		if (PROF) pick_prof_mark(&pp, PS_TARGET, lane);
 		topk_plan_make(plan, c, w.nb, lane);
-		if (PROF) pick_prof_mark(&pp, 1, lane);
+		if (PROF) pick_prof_mark(&pp, PS_PLAN, lane);
 	}
 	if (MODE == MGL_NBR_REST && c.diag_stop != 0 && c.diag_stop != 4 && c.diag_stop < 40) return; /* diagnostic stops of the first half */
 

@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(64) k_wt_window(const uint32_t* w, const uint6
 /* The value v neighbour j of K draws from W (0 < W < 2^44, K <= 2^20, so (j + 1) W fits 64 bits): uniform inside slice j of K
  * equal slices of W.  A slice can be wider than one 31-bit draw (K = 1 and a 10 MB cost map: W is about 2^38), so two draws
  * of the neighbour's stream make 62 bits: draw 0, the neighbour's target draw of the ordinal rule, and draw 0xFFFFFFFF.
- * No neighbour stream reaches that index: the streams count up from 0 one draw at a time (nbr_draw, mgl_kernels.hip; rng.n
+ * No neighbour stream reaches that index: the streams count up from 0 one draw at a time (nbr_draw, mgl_topk.hip; rng.n
  * starts at 1 or at most 32 behind the target, mgl_kernels.hip:nbr_fullwalk_one and mgl_kernels2.hip:nbr2_one) through the mutation's
  * one draw and the picks' ten draws a turn (nine in pick_from_top_k, one for pick_best), and a neighbour's repair loop ends at
  * its guard: 4 096 or 2^20 turns in nbr2_one, n <= MGL_MAX_INPUT turns in nbr_fullwalk_one -- below 1.8e9 < 2^31 draws in all.  (The

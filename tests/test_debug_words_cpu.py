@@ -74,7 +74,7 @@ def test_binding_dtypes_have_the_compiled_layout(tmp_path):
 def test_enums_are_the_frozen_numbers():
     assert [(m.name, int(m)) for m in binding.LIM] == [(m.name, i + 1) for i, m in enumerate(binding.LIM)] and len(binding.LIM) == 18
     assert [(m.name.lower(), int(m)) for m in binding.GU] == [(name, 1 << bit) for bit, name in enumerate(SITES)] and len(SITES) == 27
-    assert [int(m) for m in binding.KEY] == list(range(11))
+    assert [int(m) for m in binding.KEY] == list(range(12)) and binding.KEY.PROBE_FORM == 11
     assert sorted(int(m) for m in binding.DUMP) == DUMP_VALUES
     assert [int(m) for m in binding.BATCH] == [0, 1, 2, 3]
     for e in (binding.DUMP, binding.KEY, binding.LIM, binding.GU, binding.BATCH):

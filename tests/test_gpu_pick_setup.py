@@ -1,8 +1,10 @@
-"""The batched set-up of the top-K sources (topk_plan_make: the mgl_top_k probe and the split pick) against the
-oracle, aimed at what only a batched search can get wrong: lower bounds that take two and three 64-ary levels with
-the window floor inside a run of thousands of entries, orders whose runs differ in length at one position, the scan
-cap (where the runs are searched for the first position the cap leaves, not for the window floor), and the split
-pick itself, whose plan is made in front of the model load.  All comparisons are exact.  `-m gpu`."""
+"""The set-up of the top-K sources against the oracle, in both forms: batched (topk_plan_make: probe form 0,
+topk_find<4, true>, and the split pick) and in place (source_range without a plan: probe form 1, topk_find<1>, and
+the one-kernel form).  Aimed at what a search for the sources' bounds can get wrong: lower bounds that take two
+and three 64-ary levels with the window floor inside a run of thousands of entries, orders whose runs differ in
+length at one position, the scan cap (where the runs are searched for the first position the cap leaves, not for
+the window floor), and the split pick itself, whose plan is made in front of the model load.  All comparisons are
+exact.  `-m gpu`."""
 import numpy as np
 import pytest
 
@@ -77,11 +79,14 @@ def probe_positions(w, n, D, count, seed):
 
 
 def same_as_oracle(sa, o, slab, ps, k=20, what=()):
+    """both probe forms against one oracle answer per position; the handle is left on the default form"""
     dslab = P(slab)
     for p in ps:
-        pk, costs = sa.top_k(dslab, p)
         opk, ocosts = o.top_k(slab, p, mode=1, k=k)
-        assert (as_list(pk), [int(c) for c in costs]) == (as_list(opk), [int(c) for c in ocosts]), (what, p)
+        want = (as_list(opk), [int(c) for c in ocosts])
+        for form in (1, 0):
+            pk, costs = sa.top_k(dslab, p, form=form)
+            assert (as_list(pk), [int(c) for c in costs]) == want, (what, p, form)
 
 
 @pytest.mark.parametrize("D", WINDOWS, ids=lambda D: f"D{D}")
@@ -111,6 +116,28 @@ def test_probe_with_the_floor_inside_long_runs(name, D):
             three += cut and len(offs) > 4096  # a run of more than 64 * 64 entries: a third
     assert total >= 80, total
     assert two >= 3 and three >= 1, (two, three)
+    sa.close()
+
+
+def test_probe_form_key():
+    """MGL_KEY_PROBE_FORM takes 0 and 1 and refuses 2 (the form stays what it was); a handle switched 1 -> 0 answers
+    as one that never left 0."""
+    data, slabs = case("ab_lorem")
+    _, slab, w = slabs[1]
+    dslab = P(slab)
+    ps = probe_positions(w, len(data), 5000, 12, seed=5)
+    sa = binding.SA(data, neighbours_per_step=8, dict_limit=5000)
+    fresh = [sa.top_k(dslab, p) for p in ps]
+    sa.debug_set(binding.KEY.PROBE_FORM, 1)
+    with pytest.raises(binding.MglError) as e:
+        sa.debug_set(binding.KEY.PROBE_FORM, 2)
+    assert e.value.rc == -1  # MGL_EINVAL
+    in_place = [sa.top_k(dslab, p) for p in ps]
+    sa.debug_set(binding.KEY.PROBE_FORM, 0)
+    again = [sa.top_k(dslab, p) for p in ps]
+    for a, b, c in zip(fresh, in_place, again):
+        assert as_list(a[0]) == as_list(c[0]) == as_list(b[0]) and a[1].tolist() == c[1].tolist() == b[1].tolist()
+    assert any(len(a[0]) == 20 for a in fresh)
     sa.close()
 
 

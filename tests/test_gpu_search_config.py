@@ -1,8 +1,9 @@
 """The device's top-K search against the oracle across the settings of mgl_sa_config that change what it returns:
 top_k (1..32), the dictionary window (dict_limit) and the bucket scan cap (max_bucket_scan).  Every other GPU test
 runs at top_k 20 with a window larger than its input; here the window cuts through the inputs, at its edge
-(copies planted at distance D - 1 and D) and at the production size of 4 MiB.  Both instantiations of topk_find
-are reached: the mgl_top_k probe and the split pick (W = 4), the full-walk engine and the one-kernel form (W = 1).
+(copies planted at distance D - 1 and D) and at the production size of 4 MiB.  Both forms of topk_find
+(mgl_topk.hip) are reached, each directly and through an engine: the batched W = 4 form by probe form 0 and the
+split pick, the in-place W = 1 form by probe form 1, the full-walk engine and the one-kernel form.
 The oracle's own handling of these settings is pinned by a brute force in tests/test_oracle_search_config.py.
 `-m gpu`."""
 import lzma
@@ -79,8 +80,9 @@ def check_window_edge(pk_near, pk_far, D, M, o_unwindowed, near):
 
 @pytest.mark.parametrize("setting", GRID, ids=[_sid(s) for s in GRID])
 def test_top_k_probe_vs_oracle_across_settings(setting):
-    """(a) mgl_top_k (topk_find<4>) == Oracle.top_k(mode=1, k): packets and costs, at every position of the planted
-    copies +-2 and about 200 walk positions per input."""
+    """(a) mgl_top_k in both probe forms (topk_find<4, true> with a plan, topk_find<1> in place) == one answer of
+    Oracle.top_k(mode=1, k): packets and costs, at every position of the planted copies +-2 and about 200 walk
+    positions per input."""
     k, D, M = setting
     rng = np.random.default_rng(k * 1000003 + (D or 0) * 101 + M)
     calls, t_dev = 0, 0.0
@@ -95,13 +97,14 @@ def test_top_k_probe_vs_oracle_across_settings(setting):
                         | {p for p in planted if p in on})
             dslab = P(slab)
             for p in ps:
-                t0 = time.perf_counter()
-                pk, costs = sa.top_k(dslab, p)
-                t_dev += time.perf_counter() - t0
-                calls += 1
                 opk, ocosts = o.top_k(slab, p, mode=1, k=k)
                 assert len(opk) <= k
-                assert (as_list(pk), [int(c) for c in costs]) == (as_list(opk), [int(c) for c in ocosts]), (name, kind, p)
+                for form in (1, 0):  # the handle is left on the default form
+                    t0 = time.perf_counter()
+                    pk, costs = sa.top_k(dslab, p, form=form)
+                    t_dev += time.perf_counter() - t0
+                    calls += 1
+                    assert (as_list(pk), [int(c) for c in costs]) == (as_list(opk), [int(c) for c in ocosts]), (name, kind, p, form)
             if kind == "literal" and len(case) == 5 and name == f"edge{D}":
                 near, far = case[3], case[4]
                 check_window_edge(sa.top_k(dslab, near)[0], sa.top_k(dslab, far)[0], D, M, Oracle(data), near)
@@ -129,7 +132,7 @@ NB_ENGINES = ["split", "one_kernel", "fullwalk"]
 @pytest.mark.parametrize("setting", NB_SETTINGS, ids=[_sid(s) for s in NB_SETTINGS])
 def test_neighbours_vs_oracle_across_settings(setting, engine, monkeypatch):
     """(b) every neighbour of a step == the oracle, cost and journal, from the literal slab and from a slab the
-    device evolved under the same settings; split pick (topk_find<4>), one-kernel form and full walk (<1>)."""
+    device evolved under the same settings; split pick (topk_find<4, true>), one-kernel form and full walk (topk_find<1>)."""
     k, D, M = setting
     if engine == "one_kernel":
         monkeypatch.setenv("MGL_NO_SPLIT", "1")

@@ -20,7 +20,7 @@ while prepare != 0 and done < (prepare if prepare > 0 else 6000):
 print(f"{cfg}: after {done} steps, {p['packets'] if prepare else '?'} packets")
 sa.set_accept_mode("single")
 names = {1: "target + state_at", 2: "+ model_at (checkpoint + replay; split pick: includes the plan, the set-up of all top-K sources)", 31: "  top-K: price tables", 32: "  top-K: + literal/short-rep", 33: "  top-K: + bucket bounds (split pick: set-up done, the plan is made before the model load)",
-         34: "  top-K: + runs of the deeper orders (split pick: as 33)", 35: "  top-K: + rep pass", 36: "  top-K: + 16-byte run", 37: "  top-K: + 8-byte run", 38: "  top-K: + 4-byte run", 39: "  top-K: all sources, short ones filter only",
+         34: "  top-K: + the window's first position (split pick: as 33)", 35: "  top-K: + rep pass, bounds of the two long runs", 36: "  top-K: + 16-byte run", 37: "  top-K: + 8-byte run", 38: "  top-K: + exact-length sources D = 7..4", 39: "  top-K: all sources, short ones filter only",
          3: "+ top-K complete / mutate", 4: "+ window walk", 41: "  re-simulation: distinct contexts listed", 42: "  re-simulation: + chain search, first chunk", 43: "  re-simulation: + merge part", 0: "+ chain_sim (everything)"}
 prev = 0.0
 stops = (4, 41, 42, 43, 0) if os.environ.get("MGL_SIM_ONLY") else (1, 2, 31, 32, 33, 34, 35, 36, 37, 39, 38, 3, 4, 41, 42, 43, 0)

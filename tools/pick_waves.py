@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: where a picking wavefront of the pick half (k_neighbours2<false, MGL_NBR_PICK>) spends its cycles on an
 evolved slab (MGL_F_PROFILE): the lifetime percentiles of the wavefronts that pick, and each stage's share of the
-summed lifetime.  The stages are those of PickProf (mgl_kernels.hip).
+summed lifetime.  The stages are enum PickStage (mgl_topk.hip).
    python tools/pick_waves.py c3 [single steps measured]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
