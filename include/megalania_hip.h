@@ -40,6 +40,9 @@
  *   mgl_cost_map_live, mgl_sa_set_live_weights, mgl_sa_live_weights
  *                     no reference counterpart: the cost map of the current slab read off the engine's event chains instead
  *                                    of walked, and target weights made again from it inside mgl_sa_run
+ *   mgl_segment_cuts, mgl_props_sweep_spans, mgl_segment_partition, mgl_sa_segment_props
+ *                     no reference counterpart: a parse cut into segments that each start from an LZMA2 state reset under
+ *                                    their own lc/lp/pb, every candidate segment costed under every triple at once
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -600,6 +603,50 @@ int mgl_cost_map(mgl_sa* sa, const mgl_packet* packets, const mgl_properties* pr
  *     usable, when they do not fit (MGL_KEY_COSTMAP_NOMEM forces it here too).
  *   - MGL_EDEVICE (device consistency check): the map's total is not the exact cost the control block holds. */
 int mgl_cost_map_live(mgl_sa* sa, uint32_t* map_out /* n, nullable */, mgl_cost_report* report /* nullable */);
+/* Segment props (no reference counterpart; DESIGN.md section 10, megalania_amd/csrc/mgl_segments.hip): a parse cut into
+ * segments, each coded from an LZMA2 state reset under its own lc/lp/pb, the dictionary running through.  All of it is exact
+ * integer arithmetic, in the cost units of mgl_cost_slab.
+ *   - Segment [lo, hi), lo and hi packet starts of the slab's walk (hi may be n): its coder starts at lo with a fresh model
+ *     under its triple, ctx_state 0 and rep distances (0, 0, 0, 0).  Copies may reach below lo; literal contexts use the
+ *     absolute position and the real previous byte.
+ *   - Re-expression.  The slab's rep packets name slots of the rep stack t of the slab's own walk from byte 0; the segment
+ *     has its own stack r.  In walk order: LITERAL and MATCH stay.  SHORT_REP, D = t[0]: stays if r[0] == D, else LITERAL.
+ *     LONG_REP i of length L, D = t[i]: stays if r[i] == D, else LONG_REP j for the least j with r[j] == D, else
+ *     MATCH(D, L).  Then t advances by the original packet, r and the segment's ctx_state by the re-expressed one.
+ *   - cost(lo, hi, T) = the sum of the exact bit costs of the re-expressed packets that start in [lo, hi).  With lo = 0
+ *     nothing is re-expressed, and cost(0, n, T) is mgl_props_sweep's entry for T.
+ *   - Cuts c_0 = 0 < c_1 < .. < c_m = n, all packet starts, m <= 16 (ncuts = m + 1 <= MGL_SEG_MAX_CUTS).  Span (i, j), i < j,
+ *     is [c_i, c_j) and has index s(i, j) = i m - i (i - 1) / 2 + (j - i - 1); there are m (m + 1) / 2 spans.
+ *   - The grain rule (mgl_segment_cuts): g' = max(grain, ceil(n / 16)); the candidates k g', k >= 1, below n, each moved to
+ *     the first packet start at or above it; candidates that meet there, or at n, count once.  grain 0 = 65536.
+ *   - The partition (mgl_segment_partition): best[0] = 0, best[j] = min over i < j of best[i] + min_T cost[s(i, j)][T] +
+ *     (i > 0 ? overhead : 0), i ascending and only a strictly smaller value replacing the current one, triple ties to the
+ *     first in mgl_props_sweep's order.  MGL_SEG_OVERHEAD is the .xz writer's bound for one further chunk: 6 header bytes
+ *     with the props byte and at most 5 flush bytes. */
+#define MGL_SEG_MAX_CUTS 17
+#define MGL_SEG_MAX_SPANS 136
+#define MGL_SEG_OVERHEAD (11ull * 16384ull)
+typedef struct { uint64_t lo, hi; mgl_properties props; uint64_t cost; } mgl_segment;
+/* The cuts of the grain rule on the walk of `packets` (NULL: the current slab; a caller's slab is validated like
+ * mgl_props_sweep's).  cuts_out: cap entries, c_0 .. c_m; *ncuts = m + 1.  cap < *ncuts: MGL_ERANGE with *ncuts set. */
+int mgl_segment_cuts(mgl_sa* sa, const mgl_packet* packets, uint64_t grain, uint64_t* cuts_out, size_t cap, size_t* ncuts);
+/* Parity hook (the search state is untouched): cost_out[s * 75 + T] = cost(span s, triple T of mgl_props_sweep's order),
+ * every span walked by its own wavefront.  *count = 75 m (m + 1) / 2; cap < *count: MGL_ERANGE with *count set.
+ * The slab is validated by the walk mgl_props_sweep uses and refused as there.  MGL_EINVAL: cuts not strictly ascending
+ * from 0 to n, fewer than 2 or more than MGL_SEG_MAX_CUTS.  MGL_ERANGE: a cut that is no packet start.  The call's buffers
+ * are its own and die with it; MGL_ENOMEM leaves the handle usable.  gpu_ms (nullable): device time of the two kernels. */
+int mgl_props_sweep_spans(mgl_sa* sa, const mgl_packet* packets, const uint64_t* cuts, size_t ncuts, uint64_t* cost_out, size_t cap,
+                          size_t* count, double* gpu_ms);
+/* Host arithmetic only, no device involved: the partition above over a table of mgl_props_sweep_spans.  segs_out: room for
+ * ncuts - 1 segments; *nseg of them are written, in ascending order, tiling [0, n); *total (nullable) = best[m], the sum of
+ * the segments' costs plus (*nseg - 1) overhead.  MGL_EINVAL: a null argument, ncuts outside 2..MGL_SEG_MAX_CUTS. */
+int mgl_segment_partition(const uint64_t* cost, size_t ncuts, const uint64_t* cuts, uint64_t overhead, mgl_segment* segs_out, size_t* nseg,
+                          uint64_t* total);
+/* The three above in a row, with MGL_SEG_OVERHEAD: the cheapest segmentation of `packets` (NULL: the current slab) over the
+ * grain's cuts.  segs_out: cap entries (MGL_SEG_MAX_CUTS - 1 always suffice; fewer than needed: MGL_ERANGE with *nseg set).
+ * *single_best (nullable) = min_T cost[s(0, m)][T], the best one triple does; *total <= *single_best. */
+int mgl_sa_segment_props(mgl_sa* sa, const mgl_packet* packets, uint64_t grain, mgl_segment* segs_out, size_t cap, size_t* nseg,
+                         uint64_t* total, uint64_t* single_best, double* gpu_ms);
 /* Final model state after costing `packets`: probabilities in the reference's struct order
  * (lzma_state.h:47-53: lit | len | rep_len | dist | ctx_state), ctx_state, rep distances. */
 int mgl_final_state(mgl_sa* sa, const mgl_packet* packets, uint16_t* probs_out, size_t probs_cap,

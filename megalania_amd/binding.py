@@ -44,6 +44,7 @@ HIP_SYMBOLS = [
     "mgl_sa_set_focus", "mgl_sa_focus", "mgl_focus_slice", "mgl_cost_map",
     "mgl_sa_set_target_weights", "mgl_sa_weight_targets_by_cost", "mgl_sa_target_weights", "mgl_weight_value",
     "mgl_cost_map_live", "mgl_sa_set_live_weights", "mgl_sa_live_weights",
+    "mgl_segment_cuts", "mgl_props_sweep_spans", "mgl_segment_partition", "mgl_sa_segment_props",
 ]
 LW_SINGLE_ONLY = 1
 HOST_SYMBOLS = [
@@ -51,7 +52,17 @@ HOST_SYMBOLS = [
     "mgl_range_encoder_new", "mgl_range_encoder_free", "mgl_perplexity_encoder_new", "mgl_file_output_new",
     "mgl_memory_output_new", "mgl_emit_stream", "mgl_stream_info_read", "mgl_stream_import",
     "mgl_emit_stream_dict", "mgl_bcj_x86", "mgl_emit_xz", "mgl_stream_info_read_x", "mgl_host_cost_map",
+    "mgl_host_segment_cost", "mgl_host_segment_packets", "mgl_emit_xz_segments",
 ]
+# segment props (include/megalania_hip.h): most cuts, the .xz writer's bound for one further chunk in cost units, default grain
+SEG_MAX_CUTS = 17
+SEG_OVERHEAD = 11 * 16384
+SEG_DEFAULT_GRAIN = 65536
+
+
+def span_index(i: int, j: int, m: int) -> int:
+    """row of span (i, j), i < j <= m, in a props_sweep_spans table over m + 1 cuts"""
+    return i * m - i * (i - 1) // 2 + (j - i - 1)
 IMPORT_CLIP_WINDOW = 1
 IMPORT_X86 = 2
 FILTER_NONE, FILTER_X86 = 0, 4
@@ -201,6 +212,21 @@ class CostReport(C.Structure):
         return d
 
 
+class Segment(C.Structure):
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_uint64), ("props", Properties), ("cost", C.c_uint64)]
+
+    def asdict(self):
+        return dict(lo=self.lo, hi=self.hi, props=(self.props.lc, self.props.lp, self.props.pb), cost=self.cost)
+
+
+def _segments(segs):
+    """dicts (lo, hi, props[, cost]) or Segment instances as a C array"""
+    arr = (Segment * max(len(segs), 1))()
+    for k, s in enumerate(segs):
+        arr[k] = s if isinstance(s, Segment) else Segment(s["lo"], s["hi"], Properties(*s["props"]), s.get("cost", 0))
+    return arr
+
+
 class LiveWeightsConfig(C.Structure):
     _fields_ = [("every", C.c_uint32), ("floor", C.c_uint32), ("floor_mean", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -340,6 +366,14 @@ def hip_lib():
         L.mgl_cost_map_live.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CostReport)]
         L.mgl_sa_set_live_weights.argtypes = [C.c_void_p, C.POINTER(LiveWeightsConfig)]
         L.mgl_sa_live_weights.argtypes = [C.c_void_p, C.POINTER(LiveWeightsConfig), C.POINTER(LiveWeightsStats)]
+        L.mgl_segment_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.mgl_props_sweep_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
+        L.mgl_segment_partition.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.POINTER(Segment),
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+        L.mgl_sa_segment_props.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Segment), C.c_size_t,
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_double)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -367,6 +401,13 @@ def host_lib():
         L.mgl_stream_import.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                         C.c_void_p, C.POINTER(ImportStats)]
         L.mgl_host_cost_map.argtypes = [C.c_void_p, C.c_size_t, Properties, C.c_void_p, C.c_void_p, C.POINTER(CostReport)]
+        L.mgl_host_segment_cost.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, Properties,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mgl_host_segment_packets.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                               C.c_size_t, C.POINTER(C.c_size_t)]
+        L.mgl_emit_xz_segments.restype = C.c_bool
+        L.mgl_emit_xz_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Segment), C.c_size_t,
+                                           C.POINTER(XzOptions), C.POINTER(OutputInterface)]
         _host = L
     return _host
 
@@ -531,6 +572,81 @@ def host_cost_map(data: bytes, slab: np.ndarray, props=(0, 0, 0)):
     if rc != 0:
         raise MglError(f"rc={rc}: mgl_host_cost_map failed (invalid slab or properties?)", rc=rc)
     return out, rep.asdict(device=False)
+
+
+def host_segment_cost(data: bytes, slab: np.ndarray, lo: int, hi: int, props=(0, 0, 0)):
+    """(cost, reexpressed): the exact cost of the packets of `slab` that start in [lo, hi), coded from an LZMA2 state reset at
+    lo under props -- fresh model, ctx_state 0, reps 0, rep packets re-expressed against that stack -- and how many packets
+    the re-expression changed (host C, mgl_host_segment_cost; no device needed).  Raises MglError (rc -1) for a slab that is
+    no valid parse, a bad triple, or lo / hi off the walk."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    slab = np.ascontiguousarray(slab, dtype=PACKET)
+    if len(slab) != len(buf):
+        raise MglError("host_segment_cost: the slab must have one entry per input byte", rc=-1)
+    cost, changed = C.c_uint64(0), C.c_uint64(0)
+    rc = L.mgl_host_segment_cost(_ptr(buf), len(buf), _ptr(slab), lo, hi, Properties(*props), C.byref(cost), C.byref(changed))
+    if rc != 0:
+        raise MglError(f"rc={rc}: mgl_host_segment_cost failed (invalid slab, properties or segment?)", rc=rc)
+    return cost.value, changed.value
+
+
+def host_segment_packets(data: bytes, slab: np.ndarray, lo: int, hi: int) -> np.ndarray:
+    """The re-expressed packets of segment [lo, hi) in walk order (host C, mgl_host_segment_packets)."""
+    L = host_lib()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    slab = np.ascontiguousarray(slab, dtype=PACKET)
+    if len(slab) != len(buf):
+        raise MglError("host_segment_packets: the slab must have one entry per input byte", rc=-1)
+    out = np.zeros(max(hi - lo, 1), dtype=PACKET)
+    cnt = C.c_size_t(0)
+    rc = L.mgl_host_segment_packets(_ptr(buf), len(buf), _ptr(slab), lo, hi, _ptr(out), len(out), C.byref(cnt))
+    if rc != 0:
+        raise MglError(f"rc={rc}: mgl_host_segment_packets failed (invalid slab or segment?)", rc=rc)
+    return out[: cnt.value].copy()
+
+
+def emit_xz_segments(original: bytes, coded: bytes, slab: np.ndarray, segments, filter=0, dict_size=0, check=1) -> bytes:
+    """emit_xz with a triple per segment (host C, mgl_emit_xz_segments): `segments` is a list of dicts lo, hi, props that tile
+    [0, n) at packet starts; every segment after the first opens with an LZMA2 chunk that resets the state and sets its
+    props.  Raises MglError when the writer refuses (invalid slab, option, or segments that do not tile)."""
+    L = host_lib()
+    org = np.frombuffer(bytes(original), dtype=np.uint8)
+    cod = np.frombuffer(bytes(coded), dtype=np.uint8)
+    if len(org) != len(cod):
+        raise MglError("emit_xz_segments: original and coded differ in length", rc=-1)
+    cap = 2 * len(org) + (len(org) >> 10) * 16 + 1024 + 16 * len(segments)
+    out = np.zeros(cap, dtype=np.uint8)
+    sink = MemorySink(out.ctypes.data, cap, 0)
+    oi = OutputInterface()
+    L.mgl_memory_output_new(C.byref(oi), C.byref(sink))
+    slab = np.ascontiguousarray(slab, dtype=PACKET)
+    if len(slab) != len(org):
+        raise MglError("emit_xz_segments: the slab must have one entry per input byte", rc=-1)
+    opt = XzOptions(filter, dict_size, check)
+    if not L.mgl_emit_xz_segments(_ptr(org), _ptr(cod), len(org), _ptr(slab), _segments(segments), len(segments), C.byref(opt),
+                                  C.byref(oi)):
+        raise MglError("mgl_emit_xz_segments failed (invalid slab, option or segments?)")
+    assert sink.len <= cap
+    return out[: sink.len].tobytes()
+
+
+def segment_partition(cost, cuts, overhead=SEG_OVERHEAD):
+    """(segments, total): the cheapest way to tile [0, n) with spans of `cuts`, each under its cheapest triple, `overhead` per
+    segment after the first (mgl_segment_partition; host arithmetic, no device needed).  cost: the table of
+    SA.props_sweep_spans, shape (spans, 75).  Segments are dicts lo, hi, props, cost in ascending order."""
+    L = hip_lib()
+    cost = np.ascontiguousarray(cost, dtype=np.uint64).reshape(-1)
+    cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+    m = len(cuts) - 1
+    if not 1 <= m < SEG_MAX_CUTS or len(cost) != m * (m + 1) // 2 * len(PROPS_TRIPLES):
+        raise MglError("segment_partition: 2..17 cuts and 75 costs per span", rc=-1)
+    segs = (Segment * m)()
+    nseg, total = C.c_size_t(0), C.c_uint64(0)
+    rc = L.mgl_segment_partition(_ptr(cost), len(cuts), _ptr(cuts), overhead, segs, C.byref(nseg), C.byref(total))
+    if rc != 0:
+        raise MglError(f"rc={rc}: {L.mgl_last_error().decode()}", rc=rc)
+    return [segs[k].asdict() for k in range(nseg.value)], total.value
 
 
 class SA:
@@ -882,6 +998,51 @@ class SA:
         assert cnt.value == len(PROPS_TRIPLES)
         assert [(e.props.lc, e.props.lp, e.props.pb) for e in out] == PROPS_TRIPLES
         return np.array([e.cost for e in out], dtype=np.uint64), ms.value
+
+    def _own_slab(self, slab, who):
+        if slab is None:
+            return None
+        slab = np.ascontiguousarray(slab, dtype=PACKET)
+        if len(slab) != self.n:
+            raise MglError(f"{who}: the slab must have one entry per input byte", rc=-1)
+        return slab
+
+    def segment_cuts(self, grain=0, slab=None):
+        """The cut points of the grain rule on the walk of `slab` (None: the current slab): 0, then every multiple of
+        max(grain, ceil(n / 16)) below n moved up to the next packet start, then n (mgl_segment_cuts; grain 0 = 65536)."""
+        slab = self._own_slab(slab, "segment_cuts")
+        out = np.zeros(SEG_MAX_CUTS, dtype=np.uint64)
+        cnt = C.c_size_t(0)
+        self._chk(self.L.mgl_segment_cuts(self.h, _ptr(slab), grain, _ptr(out), len(out), C.byref(cnt)))
+        return [int(c) for c in out[: cnt.value]]
+
+    def props_sweep_spans(self, cuts, slab=None):
+        """Exact cost of every span [cuts[i], cuts[j]) of `slab` (None: the current slab), coded from a state reset at its
+        start, under every triple of PROPS_TRIPLES (mgl_props_sweep_spans; SA state untouched).  Returns (uint64 table of
+        shape (spans, 75), row span_index(i, j, len(cuts) - 1); device ms)."""
+        slab = self._own_slab(slab, "props_sweep_spans")
+        cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+        m = max(len(cuts) - 1, 0)
+        spans = m * (m + 1) // 2 if len(cuts) <= SEG_MAX_CUTS else 0
+        out = np.zeros(max(spans, 1) * len(PROPS_TRIPLES), dtype=np.uint64)
+        cnt, ms = C.c_size_t(0), C.c_double(0)
+        self._chk(self.L.mgl_props_sweep_spans(self.h, _ptr(slab), _ptr(cuts), len(cuts), _ptr(out), len(out), C.byref(cnt),
+                                               C.byref(ms)))
+        assert cnt.value == spans * len(PROPS_TRIPLES)
+        return out[: cnt.value].reshape(spans, len(PROPS_TRIPLES)).copy(), ms.value
+
+    def segment_props(self, grain=0, slab=None):
+        """The cheapest segmentation of `slab` (None: the current slab) over the grain's cuts, every segment under its own
+        triple behind an LZMA2 state reset (mgl_sa_segment_props).  Returns dict(segments=[lo, hi, props, cost ...], total,
+        single_best, gpu_ms): total = the segments' costs + SEG_OVERHEAD per segment after the first, never above
+        single_best, the cost under the best one triple."""
+        slab = self._own_slab(slab, "segment_props")
+        segs = (Segment * (SEG_MAX_CUTS - 1))()
+        nseg, total, single, ms = C.c_size_t(0), C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+        self._chk(self.L.mgl_sa_segment_props(self.h, _ptr(slab), grain, segs, len(segs), C.byref(nseg), C.byref(total),
+                                              C.byref(single), C.byref(ms)))
+        return dict(segments=[segs[k].asdict() for k in range(nseg.value)], total=total.value, single_best=single.value,
+                    gpu_ms=ms.value)
 
     def cost_map(self, slab=None, props=None):
         """Where `slab` (None: the current slab) spends its bits under props = (lc, lp, pb) (None: the handle's; another

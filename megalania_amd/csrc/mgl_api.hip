@@ -15,6 +15,7 @@
 #include "mgl_optimal.hip"
 #include "mgl_adaptive.hip"
 #include "mgl_props.hip"
+#include "mgl_segments.hip"
 #include "mgl_costmap.hip"
 #include "mgl_costmap_live.hip"
 #include "mgl_crossover.hip"
@@ -26,6 +27,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -2433,6 +2435,196 @@ extern "C" int mgl_props_sweep(mgl_sa* sa, const mgl_packet* packets, mgl_props_
 		out[t].props.lc = (uint8_t)L.lc; out[t].props.lp = (uint8_t)L.lp; out[t].props.pb = (uint8_t)L.pb;
 		out[t].cost = costs[t];
 	}
+	return MGL_OK;
+}
+
+/* ---- segment props (mgl_segments.hip; include/megalania_hip.h, "Segment props", has the definitions) ---- */
+
+static size_t seg_span_index(size_t i, size_t j, size_t m) { return i * m - i * (i - 1) / 2 + (j - i - 1); }
+
+/* the grain rule over a host copy of a valid slab; cuts holds MGL_SEG_MAX_CUTS entries.  0: an entry of length 0 on the walk */
+static size_t seg_cuts_host(const mgl_packet* p, uint64_t n, uint64_t grain, uint64_t* cuts)
+{
+	const uint64_t leaf = (n + 15) / 16, g = grain ? grain : 65536, step = g > leaf ? g : leaf;
+	size_t k = 0;
+	uint64_t pos = 0;
+	cuts[k++] = 0;
+	for (uint64_t cand = step; cand < n; cand += step) { /* at most 15 candidates: 16 step >= n */
+		while (pos < cand) {
+			if (!p[pos].len) return 0;
+			pos += p[pos].len;
+		}
+		if (pos >= n) break;
+		if (pos != cuts[k - 1]) cuts[k++] = pos;
+	}
+	cuts[k++] = n;
+	return k;
+}
+
+/* the slab a call works on, validated if it is the caller's: on the device (*d_slab) and, if asked for, on the host */
+static int seg_take_slab(mgl_sa* sa, const mgl_packet* packets, const mgl_pk** d_slab, std::vector<mgl_packet>* host)
+{
+	*d_slab = sa->base.v.slab;
+	if (packets) {
+		Control c;
+		TRY(scratch_walk(sa, packets, false, false, &c));
+		*d_slab = sa->scratch.v.slab;
+	}
+	if (host) {
+		host->resize(sa->n);
+		if (packets) memcpy(host->data(), packets, sizeof(mgl_packet) * (size_t)sa->n);
+		else TRY(export_slab(sa, sa->base.v.slab, host->data()));
+	}
+	return MGL_OK;
+}
+
+extern "C" int mgl_segment_cuts(mgl_sa* sa, const mgl_packet* packets, uint64_t grain, uint64_t* cuts_out, size_t cap, size_t* ncuts)
+{
+	if (!sa || !cuts_out || !ncuts) return fail(MGL_EINVAL, "null argument");
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* d_slab;
+	std::vector<mgl_packet> host;
+	TRY(seg_take_slab(sa, packets, &d_slab, &host));
+	uint64_t cuts[MGL_SEG_MAX_CUTS];
+	const size_t k = seg_cuts_host(host.data(), sa->n, grain, cuts);
+	if (!k) return fail(MGL_EINVAL, "slab is not a valid parse of the input");
+	*ncuts = k;
+	if (cap < k) return fail(MGL_ERANGE, "mgl_segment_cuts: cuts_out is too small");
+	memcpy(cuts_out, cuts, sizeof(uint64_t) * k);
+	return MGL_OK;
+}
+
+/* the two kernels over a valid slab that lies on the device */
+static int seg_sweep_device(mgl_sa* sa, const mgl_pk* slab, const uint64_t* cuts, size_t ncuts, uint64_t* cost_out, float* ms)
+{
+	static const char* nomem = "mgl_props_sweep_spans: the call's buffers do not fit the device";
+	const uint32_t m = (uint32_t)ncuts - 1u, spans = m * (m + 1u) / 2u;
+	/* launch order: longest span first, ties in index order */
+	uint32_t h_cuts[MGL_SEG_MAX_CUTS], h_order[MGL_SEG_MAX_SPANS];
+	for (size_t k = 0; k < ncuts; k++) h_cuts[k] = (uint32_t)cuts[k];
+	uint32_t q = 0;
+	for (uint32_t i = 0; i < m; i++)
+		for (uint32_t j = i + 1; j <= m; j++) h_order[q++] = i | j << 8;
+	std::stable_sort(h_order, h_order + spans, [&](uint32_t a, uint32_t b) {
+		return h_cuts[a >> 8] - h_cuts[a & 0xFFu] > h_cuts[b >> 8] - h_cuts[b & 0xFFu];
+	});
+	struct Tmp {
+		DevOwner own;
+		uint32_t *cuts = nullptr, *order = nullptr, *starts = nullptr;
+		uint64_t* cost = nullptr;
+		hipEvent_t t0 = nullptr, t1 = nullptr;
+	} tmp;
+	TRY(dnew(tmp.own, tmp.cuts, MGL_SEG_MAX_CUTS, -1, nomem));
+	TRY(dnew(tmp.own, tmp.order, MGL_SEG_MAX_SPANS, -1, nomem));
+	TRY(dnew(tmp.own, tmp.starts, MGL_SEG_MAX_CUTS * MGL_SEG_START_WORDS, -1, nomem));
+	TRY(dnew(tmp.own, tmp.cost, (size_t)spans * MGL_PROPS_TRIPLES, -1, nomem));
+	HIPCHK(tmp.own.event(&tmp.t0));
+	HIPCHK(tmp.own.event(&tmp.t1));
+	hipStream_t s = sa->q.stream;
+	HIPCHK(hipMemcpyAsync(tmp.cuts, h_cuts, sizeof(uint32_t) * ncuts, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(tmp.order, h_order, sizeof(uint32_t) * spans, hipMemcpyHostToDevice, s));
+	HIPCHK(hipEventRecord(tmp.t0, s));
+	hipLaunchKernelGGL(k_seg_starts, dim3(1), dim3(64), 0, s, sa->ctx, slab, (const uint32_t*)tmp.cuts, (uint32_t)ncuts, tmp.starts);
+	HIPCHK(hipGetLastError());
+	/* the sweep follows at once: from a cut that is no packet start its walks are bounded nonsense, thrown away below */
+	hipLaunchKernelGGL(k_props_spans, dim3(spans * MGL_PROPS_TRIPLES), dim3(64), 0, s, sa->ctx, slab, (const uint32_t*)tmp.cuts, m,
+	                   (const uint32_t*)tmp.starts, (const uint32_t*)tmp.order, tmp.cost);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(tmp.t1, s));
+	uint32_t h_starts[MGL_SEG_MAX_CUTS * MGL_SEG_START_WORDS];
+	std::vector<uint64_t> h_cost((size_t)spans * MGL_PROPS_TRIPLES);
+	HIPCHK(hipMemcpyAsync(h_starts, tmp.starts, sizeof(uint32_t) * ncuts * MGL_SEG_START_WORDS, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(h_cost.data(), tmp.cost, sizeof(uint64_t) * h_cost.size(), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (size_t k = 0; k < ncuts; k++)
+		if (!h_starts[k * MGL_SEG_START_WORDS]) return fail(MGL_ERANGE, "mgl_props_sweep_spans: cut " + std::to_string(cuts[k]) + " is not a packet start of the walk");
+	HIPCHK(hipEventElapsedTime(ms, tmp.t0, tmp.t1));
+	memcpy(cost_out, h_cost.data(), sizeof(uint64_t) * h_cost.size());
+	return MGL_OK;
+}
+
+static int seg_check_cuts(const mgl_sa* sa, const uint64_t* cuts, size_t ncuts)
+{
+	bool ok = ncuts >= 2 && ncuts <= MGL_SEG_MAX_CUTS && cuts[0] == 0 && cuts[ncuts - 1] == sa->n;
+	for (size_t k = 1; ok && k < ncuts; k++) ok = cuts[k] > cuts[k - 1];
+	return ok ? MGL_OK : fail(MGL_EINVAL, "mgl_props_sweep_spans: between 2 and 17 cuts, strictly ascending from 0 to n");
+}
+
+extern "C" int mgl_props_sweep_spans(mgl_sa* sa, const mgl_packet* packets, const uint64_t* cuts, size_t ncuts, uint64_t* cost_out, size_t cap,
+                                     size_t* count, double* gpu_ms)
+{
+	static_assert(MGL_SEG_MAX_SPANS == (MGL_SEG_MAX_CUTS - 1) * MGL_SEG_MAX_CUTS / 2, "spans of the most cuts");
+	if (!sa || !cuts || !cost_out) return fail(MGL_EINVAL, "null argument");
+	TRY(seg_check_cuts(sa, cuts, ncuts));
+	const size_t m = ncuts - 1, need = m * (m + 1) / 2 * MGL_PROPS_TRIPLES;
+	if (count) *count = need;
+	if (cap < need) return fail(MGL_ERANGE, "mgl_props_sweep_spans: cost_out holds fewer than 75 entries per span");
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* slab;
+	TRY(seg_take_slab(sa, packets, &slab, nullptr));
+	float ms = 0;
+	TRY(seg_sweep_device(sa, slab, cuts, ncuts, cost_out, &ms));
+	if (gpu_ms) *gpu_ms = ms;
+	return MGL_OK;
+}
+
+extern "C" int mgl_segment_partition(const uint64_t* cost, size_t ncuts, const uint64_t* cuts, uint64_t overhead, mgl_segment* segs_out, size_t* nseg,
+                                     uint64_t* total)
+{
+	if (!cost || !cuts || !segs_out || !nseg) return fail(MGL_EINVAL, "null argument");
+	if (ncuts < 2 || ncuts > MGL_SEG_MAX_CUTS) return fail(MGL_EINVAL, "mgl_segment_partition: between 2 and 17 cuts");
+	const size_t m = ncuts - 1;
+	uint64_t best[MGL_SEG_MAX_CUTS];
+	size_t from[MGL_SEG_MAX_CUTS], triple[MGL_SEG_MAX_CUTS];
+	best[0] = 0;
+	for (size_t j = 1; j <= m; j++) {
+		bool have = false;
+		for (size_t i = 0; i < j; i++) {
+			const uint64_t* row = cost + seg_span_index(i, j, m) * MGL_PROPS_TRIPLES;
+			size_t arg = 0;
+			for (size_t t = 1; t < MGL_PROPS_TRIPLES; t++)
+				if (row[t] < row[arg]) arg = t;
+			const uint64_t v = best[i] + row[arg] + (i ? overhead : 0);
+			if (!have || v < best[j]) { best[j] = v; from[j] = i; triple[j] = arg; have = true; }
+		}
+	}
+	size_t k = 0;
+	for (size_t j = m; j; j = from[j]) k++;
+	*nseg = k;
+	for (size_t j = m; j; j = from[j]) {
+		const mgl_layout L = mgl_props_triple((uint32_t)triple[j]);
+		mgl_segment& sg = segs_out[--k];
+		sg.lo = cuts[from[j]]; sg.hi = cuts[j];
+		sg.props.lc = (uint8_t)L.lc; sg.props.lp = (uint8_t)L.lp; sg.props.pb = (uint8_t)L.pb;
+		sg.cost = cost[seg_span_index(from[j], j, m) * MGL_PROPS_TRIPLES + triple[j]];
+	}
+	if (total) *total = best[m];
+	return MGL_OK;
+}
+
+extern "C" int mgl_sa_segment_props(mgl_sa* sa, const mgl_packet* packets, uint64_t grain, mgl_segment* segs_out, size_t cap, size_t* nseg,
+                                    uint64_t* total, uint64_t* single_best, double* gpu_ms)
+{
+	if (!sa || !segs_out || !nseg) return fail(MGL_EINVAL, "null argument");
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* slab;
+	std::vector<mgl_packet> host;
+	TRY(seg_take_slab(sa, packets, &slab, &host));
+	uint64_t cuts[MGL_SEG_MAX_CUTS];
+	const size_t ncuts = seg_cuts_host(host.data(), sa->n, grain, cuts);
+	if (!ncuts) return fail(MGL_EINVAL, "slab is not a valid parse of the input");
+	const size_t m = ncuts - 1;
+	std::vector<uint64_t> cost(m * (m + 1) / 2 * MGL_PROPS_TRIPLES);
+	float ms = 0;
+	TRY(seg_sweep_device(sa, slab, cuts, ncuts, cost.data(), &ms));
+	if (gpu_ms) *gpu_ms = ms;
+	mgl_segment segs[MGL_SEG_MAX_CUTS];
+	size_t k = 0;
+	TRY(mgl_segment_partition(cost.data(), ncuts, cuts, MGL_SEG_OVERHEAD, segs, &k, total));
+	if (single_best) *single_best = *std::min_element(cost.begin() + seg_span_index(0, m, m) * MGL_PROPS_TRIPLES, cost.begin() + (seg_span_index(0, m, m) + 1) * MGL_PROPS_TRIPLES);
+	*nseg = k;
+	if (cap < k) return fail(MGL_ERANGE, "mgl_sa_segment_props: segs_out is too small");
+	memcpy(segs_out, segs, sizeof(mgl_segment) * k);
 	return MGL_OK;
 }
 

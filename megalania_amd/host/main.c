@@ -114,6 +114,16 @@ static const char usage_options[] =
 	"               `cost-type: NAME packets N bytes M cost X B share P % exact C` (literal, match, short_rep, long_rep)\n"
 	"               behind `cost-report: total X B exact C packets N lc=.. lp=.. pb=.. T ms`; X = C / 16384\n"
 	"  --cost-bucket B  print one line per B input bytes: `cost-bucket: offset O bytes N cost X B bpb R exact C`\n"
+	"  --segment-props GRAIN|auto  with --format xz: after the search the best parse is cut at about every GRAIN bytes (auto =\n"
+	"               65536; at most 16 leaves, so at least a sixteenth of the input each), every run of leaves is costed from an\n"
+	"               LZMA2 state reset under all 75 lc/lp/pb at once (mgl_props_sweep_spans) and the stream is written in the\n"
+	"               cheapest segments (mgl_segment_partition, 11 bytes charged per further segment), each behind a chunk that\n"
+	"               resets the state and sets its triple; the dictionary runs through.  Never larger in exact cost than the\n"
+	"               stream under the best single triple.  Two kinds of lines on stderr:\n"
+	"               `segment-props: grain G cuts C spans S single lc=.. lp=.. pb=.. X B exact C segmented X B exact C segments M T ms`\n"
+	"               `segment: offset O bytes N lc=.. lp=.. pb=.. cost X B exact C reexpressed R` (X = C / 16384; R = rep packets\n"
+	"               named again against the segment's own rep stack).  Not with --cost-map, --cost-report or --cost-bucket,\n"
+	"               which describe a stream under one triple\n"
 	"  --accept     what a step of K neighbours takes: the best acceptable one (single), every one that is\n"
 	"               the best of its own window (bulk), or whichever pays (auto, default)\n";
 
@@ -130,7 +140,7 @@ static void usage(const char* argv0)
 	        "          [--exchange best|cross|cross-all [--cross-grain N]]] [--focus LO:HI|rank]\n"
 	        "          [--target-weights cost[:mean|:N]|file:PATH]\n"
 	        "          [--live-weights R[:N|:mean][,single]]\n"
-	        "          [--cost-map FILE] [--cost-report] [--cost-bucket B] filename\n", argv0);
+	        "          [--cost-map FILE] [--cost-report] [--cost-bucket B] [--segment-props GRAIN|auto] filename\n", argv0);
 	fputs(usage_options, stderr);
 }
 
@@ -164,6 +174,9 @@ typedef struct {
 	/* format, filter */
 	uint32_t filter, dict_size;
 	bool format_xz, filter_given;
+	/* --segment-props: the grain, 0 for auto */
+	bool segment_props;
+	unsigned long long segment_grain;
 	/* chains, exchange */
 	int chains, rank;
 	uint32_t exchange, cross_grain;
@@ -325,6 +338,12 @@ static int parse_args(int argc, char** argv, cli_opts* o)
 		else if (!strcmp(a, "--target-weights")) why = parse_target_weights(v, o);
 		else if (!strcmp(a, "--live-weights")) why = parse_live_weights(v, o);
 		else if (!strcmp(a, "--cost-map")) o->cost_map_path = v;
+		else if (!strcmp(a, "--segment-props")) {
+			o->segment_props = true;
+			o->segment_grain = 0;
+			if (strcmp(v, "auto") != 0 && (v[0] < '0' || v[0] > '9' || !number(v, &o->segment_grain) || !o->segment_grain))
+				why = "--segment-props takes a number of bytes, at least 1, or auto";
+		}
 		else if (!strcmp(a, "--cost-bucket")) { if (!number(v, &o->cost_bucket) || !o->cost_bucket) why = "--cost-bucket takes a number of bytes, at least 1"; }
 		else bad = true;
 		if (bad || why) return refuse(o, why);
@@ -355,6 +374,9 @@ static int check_args(cli_opts* o)
 	if (o->cross_grain_given && o->exchange == EXCHANGE_BEST) return refuse(o, "--cross-grain needs --exchange cross or --exchange cross-all");
 	if (o->filter != FILTER_NONE && !o->format_xz) return refuse(o, "--filter x86 / auto need --format xz: an .lzma stream has no place to declare a filter");
 	if (o->filter == FILTER_AUTO && (from_file || o->chains > 1)) return refuse(o, "--filter auto cannot be combined with --seed-stream, --load-slab or --chains above 1");
+	if (o->segment_props && !o->format_xz) return refuse(o, "--segment-props needs --format xz: an .lzma stream cannot reset its state or change lc/lp/pb");
+	if (o->segment_props && (o->cost_map_path || o->cost_report || o->cost_bucket))
+		return refuse(o, "--segment-props cannot be combined with --cost-map, --cost-report or --cost-bucket: they describe a stream under one triple");
 	if (o->focus_rank && o->chains < 2) return refuse(o, "--focus rank needs --chains N with N at least 2");
 	if (o->live_given && o->weights != WEIGHTS_NONE) return refuse(o, "--live-weights and --target-weights exclude each other");
 	if (o->chains < 1 || o->rank < 0 || o->rank >= o->chains || (o->chains > 1 && !o->comm_path)) return refuse(o, NULL);
@@ -392,6 +414,9 @@ typedef struct {
 	bool resumed; /* a best slab was loaded: every epoch starts from it */
 	uint8_t* seed_stream;
 	size_t seed_stream_len;
+	/* --segment-props: the segments the stream is written in */
+	mgl_segment segs[MGL_SEG_MAX_CUTS];
+	size_t nseg;
 } cli_run;
 
 /* every error of the run: one `Error:` line on stderr, exit status 255; nothing is freed on the way out */
@@ -1104,6 +1129,48 @@ static int report_costs(cli_run* r)
 	return 0;
 }
 
+/* --segment-props, on rank 0: the slab the run emits is cut by the grain rule, every span costed under every triple from a
+ * state reset, and the cheapest tiling kept for write_stream -- the three calls mgl_sa_segment_props makes, made here one by one
+ * because the `single` figure wants the triple of the table's whole-file row, not only its cost.  The handle's own triple plays
+ * no part.  Each segment is walked once more on the host, for the count of re-expressed packets and as a check of the device's
+ * figure.  The line formats are fixed (README.md, "Segment props"). */
+static int choose_segments(cli_run* r)
+{
+	const cli_opts* o = r->o;
+	if (!o->segment_props || o->rank != 0) return 0;
+	uint64_t cuts[MGL_SEG_MAX_CUTS], total = 0;
+	size_t ncuts = 0, count = 0;
+	double ms = 0;
+	if (mgl_segment_cuts(r->sa, r->packets_best, o->segment_grain, cuts, MGL_SEG_MAX_CUTS, &ncuts) != MGL_OK) return lib_error();
+	const size_t m = ncuts - 1, spans = m * (m + 1) / 2;
+	uint64_t* tab = (uint64_t*)malloc(sizeof(uint64_t) * spans * MGL_PROPS_TRIPLES);
+	if (!tab) return fail("out of memory");
+	if (mgl_props_sweep_spans(r->sa, r->packets_best, cuts, ncuts, tab, spans * MGL_PROPS_TRIPLES, &count, &ms) != MGL_OK ||
+	    mgl_segment_partition(tab, ncuts, cuts, MGL_SEG_OVERHEAD, r->segs, &r->nseg, &total) != MGL_OK) return lib_error();
+	/* span (0, m) is row m - 1; the triples come in the order lc, lp, pb */
+	const uint64_t* whole = tab + (m - 1) * MGL_PROPS_TRIPLES;
+	mgl_properties single = { 0, 0, 0 };
+	size_t arg = 0, t = 0;
+	for (unsigned lc = 0; lc <= 4; lc++)
+		for (unsigned lp = 0; lp + lc <= 4; lp++)
+			for (unsigned pb = 0; pb <= 4; pb++, t++)
+				if (whole[t] < whole[arg] || t == 0) { arg = t; single = (mgl_properties){ (uint8_t)lc, (uint8_t)lp, (uint8_t)pb }; }
+	fprintf(stderr, "segment-props: grain %llu cuts %zu spans %zu single lc=%u lp=%u pb=%u %.3f B exact %llu segmented %.3f B exact %llu segments %zu %.3f ms\n",
+	        o->segment_grain ? o->segment_grain : 65536ull, ncuts, spans, single.lc, single.lp, single.pb, whole[arg] / 16384.0,
+	        (unsigned long long)whole[arg], total / 16384.0, (unsigned long long)total, r->nseg, ms);
+	free(tab);
+	for (size_t k = 0; k < r->nseg; k++) {
+		const mgl_segment* sg = &r->segs[k];
+		uint64_t cost = 0, changed = 0;
+		if (mgl_host_segment_cost(r->file_data, r->file_size, r->packets_best, sg->lo, sg->hi, sg->props, &cost, &changed) != MGL_OK || cost != sg->cost)
+			return fail("segment at %llu: the host walk does not confirm the device's cost %llu", (unsigned long long)sg->lo, (unsigned long long)sg->cost);
+		fprintf(stderr, "segment: offset %llu bytes %llu lc=%u lp=%u pb=%u cost %.3f B exact %llu reexpressed %llu\n", (unsigned long long)sg->lo,
+		        (unsigned long long)(sg->hi - sg->lo), sg->props.lc, sg->props.lp, sg->props.pb, sg->cost / 16384.0, (unsigned long long)sg->cost,
+		        (unsigned long long)changed);
+	}
+	return 0;
+}
+
 static int write_stream(cli_run* r)
 {
 	const cli_opts* o = r->o;
@@ -1113,7 +1180,8 @@ static int write_stream(cli_run* r)
 	mgl_file_output_new(&output, out);
 	if (o->format_xz) {
 		const mgl_xz_options xo = { r->filter == FILTER_X86 ? 4u : 0u, o->dict_size, 1 };
-		if (!mgl_emit_xz(r->orig_data, r->file_data, r->file_size, r->props, r->packets_best, &xo, &output)) return -1;
+		if (o->segment_props ? !mgl_emit_xz_segments(r->orig_data, r->file_data, r->file_size, r->packets_best, r->segs, r->nseg, &xo, &output)
+		                     : !mgl_emit_xz(r->orig_data, r->file_data, r->file_size, r->props, r->packets_best, &xo, &output)) return -1;
 	} else if (o->dict_size) {
 		if (!mgl_emit_stream_dict(r->file_data, r->file_size, r->props, r->packets_best, o->dict_size, &output)) return -1;
 	} else if (!mgl_emit_stream(r->file_data, r->file_size, r->props, r->packets_best, &output)) return -1;
@@ -1146,7 +1214,8 @@ int main(int argc, char** argv)
 	    run_epochs(&r) ||
 	    final_exchange(&r) ||
 	    fetch_best(&r) ||
-	    report_costs(&r)) return -1;
+	    report_costs(&r) ||
+	    choose_segments(&r)) return -1;
 	mgl_comm_destroy(r.comm);
 	mgl_sa_destroy(r.sa);
 	if (o.rank != 0) return 0; /* every chain holds the common best slab after the last exchange; rank 0 writes it */

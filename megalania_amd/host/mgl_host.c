@@ -378,6 +378,90 @@ int mgl_host_cost_map(const uint8_t* data, size_t n, mgl_properties props, const
 	return MGL_OK;
 }
 
+/* ------------------------------------------------------------------ segments (no reference equivalent)
+ *
+ * A segment's coder starts from an LZMA2 state reset in the middle of the slab's walk: fresh model, ctx_state 0, rep
+ * distances (0, 0, 0, 0), the dictionary untouched.  The slab's rep packets name slots of the rep stack of the slab's own
+ * walk from byte 0 (`t`); the segment has its own (`r`), so each packet is named again in r's terms
+ * (include/megalania_hip.h, "Segment props", has the rule).  The copy itself never changes, so what was valid stays valid. */
+
+static bool props_ok(mgl_properties p) { return p.lc + p.lp <= 4 && p.pb <= 4; }
+
+/* the packet at t's position as the walk with rep stack r codes it */
+static mgl_packet seg_reexpress(const mgl_wstate* t, const mgl_wstate* r, mgl_packet pk)
+{
+	if (pk.type == MGL_SHORT_REP) {
+		if (r->dists[0] != t->dists[0]) pk.type = MGL_LITERAL;
+	} else if (pk.type == MGL_LONG_REP) {
+		const uint32_t d = mgl_dist_at(t, pk.dist);
+		if (mgl_dist_at(r, pk.dist) != d) {
+			uint32_t j = 0;
+			while (j < 4 && r->dists[j] != d) j++;
+			if (j < 4) pk.dist = j;
+			else { pk.type = MGL_MATCH; pk.dist = d; }
+		}
+	}
+	return pk;
+}
+
+static bool same_packet(mgl_packet a, mgl_packet b) { return a.type == b.type && a.dist == b.dist && a.len == b.len; }
+
+/* the slab's own walk from byte 0 up to `to`; false when `to` is no packet start (the slab is a valid parse) */
+static bool seg_true_walk(const mgl_packet* slab, uint64_t to, mgl_wstate* t)
+{
+	memset(t, 0, sizeof *t);
+	while (t->pos < to) mgl_advance(t, slab[t->pos].type, slab[t->pos].dist, slab[t->pos].len);
+	return t->pos == to;
+}
+
+/* The segment [lo, hi) through `enc` under `props`, or, with out != NULL, its re-expressed packets into out[0 .. cap). */
+static int seg_walk(const uint8_t* data, size_t n, const mgl_packet* slab, uint64_t lo, uint64_t hi, mgl_properties props,
+                    EncoderInterface* enc, mgl_packet* out, size_t cap, size_t* count, uint64_t* reexpressed)
+{
+	if (!data || !slab || n == 0 || n > 0xFFFFFFFFu || lo > hi || hi > n || !props_ok(props)) return MGL_EINVAL;
+	if (!slab_is_valid(data, n, slab, 0xFFFFFFFFu)) return MGL_EINVAL;
+	mgl_wstate t;
+	if (!seg_true_walk(slab, lo, &t)) return MGL_EINVAL;
+	mgl_lzma_state st;
+	if (!mgl_lzma_state_init(&st, data, n, props)) return MGL_ENOMEM;
+	st.walk.pos = (uint32_t)lo;
+	size_t k = 0;
+	uint64_t changed = 0;
+	while (t.pos < hi) {
+		const mgl_packet pk = slab[t.pos], q = seg_reexpress(&t, &st.walk, pk);
+		if (!same_packet(pk, q)) changed++;
+		if (out && k < cap) out[k] = q;
+		k++;
+		if (enc) mgl_lzma_encode_packet(&st, enc, q);
+		else mgl_advance(&st.walk, q.type, q.dist, q.len);
+		mgl_advance(&t, pk.type, pk.dist, pk.len);
+	}
+	mgl_lzma_state_free(&st);
+	if (t.pos != hi) return MGL_EINVAL;
+	if (count) *count = k;
+	if (reexpressed) *reexpressed = changed;
+	return out && k > cap ? MGL_ERANGE : MGL_OK;
+}
+
+int mgl_host_segment_cost(const uint8_t* data, size_t n, const mgl_packet* slab, uint64_t lo, uint64_t hi, mgl_properties props,
+                          uint64_t* cost, uint64_t* reexpressed)
+{
+	uint64_t sum = 0;
+	EncoderInterface enc;
+	mgl_perplexity_encoder_new(&enc, &sum);
+	const int rc = seg_walk(data, n, slab, lo, hi, props, &enc, NULL, 0, NULL, reexpressed);
+	if (rc == MGL_OK && cost) *cost = sum;
+	return rc;
+}
+
+int mgl_host_segment_packets(const uint8_t* data, size_t n, const mgl_packet* slab, uint64_t lo, uint64_t hi, mgl_packet* out,
+                             size_t cap, size_t* count)
+{
+	const mgl_properties none = { 0, 0, 0 };
+	if (!out && cap) return MGL_EINVAL;
+	return seg_walk(data, n, slab, lo, hi, none, NULL, out, cap, count, NULL);
+}
+
 /* ------------------------------------------------------------------ x86 BCJ filter (.xz filter id 0x04)
  *
  * The relative 32-bit target behind an E8 (call) or E9 (jmp) opcode becomes an absolute one, so that calls of one
@@ -484,25 +568,29 @@ static bool xz_write(OutputInterface* output, const void* p, size_t n, bool* fai
 	return true;
 }
 
-bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_properties props, const mgl_packet* slab,
-                 const mgl_xz_options* opt, OutputInterface* output)
+/* The writer behind mgl_emit_xz (one segment, [0, n)) and mgl_emit_xz_segments; `who` names the caller in the messages.
+ * Segment k > 0 opens with a chunk that resets the state and sets its properties; its packets are re-expressed against the
+ * rep stack that starts there (seg_reexpress; the identity in segment 0). */
+static bool emit_xz_core(const char* who, const uint8_t* original, const uint8_t* coded, size_t n, const mgl_packet* slab,
+                         const mgl_segment* segs, size_t nseg, const mgl_xz_options* opt, OutputInterface* output)
 {
 	static const mgl_xz_options k_defaults = { 0, 0, 0 };
 	if (!opt) opt = &k_defaults;
 	if ((opt->filter != 0 && opt->filter != 4) || opt->check > 1) {
-		fprintf(stderr, "Error: mgl_emit_xz: filter must be 0 or 4 and check 0 or 1\n");
+		fprintf(stderr, "Error: %s: filter must be 0 or 4 and check 0 or 1\n", who);
 		return false;
 	}
-	if (props.lc > 4 || props.lp > 4 || props.pb > 4 || props.lc + props.lp > 4) {
-		fprintf(stderr, "Error: mgl_emit_xz: LZMA2 needs lc + lp <= 4 and pb <= 4\n");
-		return false;
-	}
+	for (size_t k = 0; k < nseg; k++)
+		if (segs[k].props.lc > 4 || segs[k].props.lp > 4 || segs[k].props.pb > 4 || segs[k].props.lc + segs[k].props.lp > 4) {
+			fprintf(stderr, "Error: %s: LZMA2 needs lc + lp <= 4 and pb <= 4\n", who);
+			return false;
+		}
 	if (n && (!original || !coded || !slab)) {
-		fprintf(stderr, "Error: mgl_emit_xz: null argument\n");
+		fprintf(stderr, "Error: %s: null argument\n", who);
 		return false;
 	}
 	if (opt->filter == 0 && coded != original && n && memcmp(coded, original, n) != 0) {
-		fprintf(stderr, "Error: mgl_emit_xz: without a filter the coded bytes are the original ones\n");
+		fprintf(stderr, "Error: %s: without a filter the coded bytes are the original ones\n", who);
 		return false;
 	}
 	const uint32_t want = opt->dict_size ? opt->dict_size : MGL_DEFAULT_DICT;
@@ -510,6 +598,15 @@ bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_pr
 	while (dict_byte < 40 && xz_dict_of_byte(dict_byte) < (want < 4096 ? 4096 : want)) dict_byte++;
 	const uint32_t window = dict_byte == 40 ? 0xFFFFFFFFu : (uint32_t)xz_dict_of_byte(dict_byte);
 	if (!slab_is_valid(coded, n, slab, window)) return false;
+	/* the segments tile [0, n) and every one starts at a packet start of the walk */
+	for (size_t k = 0; n && k < nseg; k++) {
+		mgl_wstate at;
+		if (segs[k].lo != (k ? segs[k - 1].hi : 0) || segs[k].hi <= segs[k].lo || segs[k].hi > n || (k + 1 == nseg && segs[k].hi != n) ||
+		    !seg_true_walk(slab, segs[k].lo, &at)) {
+			fprintf(stderr, "Error: %s: segment %zu does not continue the tiling of the input at a packet start\n", who, k);
+			return false;
+		}
+	}
 
 	bool failed = false;
 	uint8_t hdr[32];
@@ -535,11 +632,24 @@ bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_pr
 		unpadded = hsize;
 
 		mgl_lzma_state st;
+		mgl_properties props = segs[0].props;
 		if (!mgl_lzma_state_init(&st, coded, n, props)) return false;
 		uint8_t* cbuf = (uint8_t*)malloc(XZ_CHUNK_CSIZE_MAX);
-		if (!cbuf) { fprintf(stderr, "Error: could not allocate memory in mgl_emit_xz\n"); mgl_lzma_state_free(&st); return false; }
-		bool first = true;
+		if (!cbuf) { fprintf(stderr, "Error: could not allocate memory in %s\n", who); mgl_lzma_state_free(&st); return false; }
+		bool first = true, reset = false;
+		size_t seg = 0;
+		mgl_wstate tw; /* the slab's own walk, whose rep stack the slab's rep packets name */
+		memset(&tw, 0, sizeof tw);
 		while (st.walk.pos < n) {
+			if (st.walk.pos == segs[seg].hi) {
+				/* the next segment: a fresh model under its triple, ctx_state 0, reps 0; the position runs on */
+				props = segs[++seg].props;
+				mgl_lzma_state_free(&st);
+				if (!mgl_lzma_state_init(&st, coded, n, props)) { free(cbuf); return false; }
+				st.walk.pos = tw.pos;
+				reset = true;
+			}
+			const size_t seg_end = (size_t)segs[seg].hi;
 			/* one chunk: a fresh range coder over a memory sink; model and rep stack carry on */
 			mgl_memory_sink sink = { cbuf, XZ_CHUNK_CSIZE_MAX, 0 };
 			OutputInterface mem;
@@ -549,28 +659,30 @@ bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_pr
 			const size_t start = st.walk.pos;
 			do {
 				/* the first packet of a chunk always fits: 5 + 70 bytes, at most 273 bytes of input */
-				mgl_lzma_encode_packet(&st, &enc, slab[st.walk.pos]);
-			} while (st.walk.pos < n && st.walk.pos - start + slab[st.walk.pos].len <= XZ_CHUNK_USIZE_MAX &&
+				const mgl_packet pk = slab[st.walk.pos];
+				mgl_lzma_encode_packet(&st, &enc, seg_reexpress(&tw, &st.walk, pk));
+				mgl_advance(&tw, pk.type, pk.dist, pk.len);
+			} while (st.walk.pos < seg_end && st.walk.pos - start + slab[st.walk.pos].len <= XZ_CHUNK_USIZE_MAX &&
 			         rc_bytes_if_flushed(&enc, &sink) + XZ_PACKET_MAX_BYTES <= XZ_CHUNK_CSIZE_MAX);
 			mgl_range_encoder_free(&enc);
 			const size_t usize = st.walk.pos - start, csize = sink.len;
 			if (csize > XZ_CHUNK_CSIZE_MAX || usize > XZ_CHUNK_USIZE_MAX) { /* the bound above rules this out */
-				fprintf(stderr, "Error: mgl_emit_xz: an LZMA2 chunk came out at %zu bytes for %zu\n", csize, usize);
+				fprintf(stderr, "Error: %s: an LZMA2 chunk came out at %zu bytes for %zu\n", who, csize, usize);
 				free(cbuf);
 				mgl_lzma_state_free(&st);
 				return false;
 			}
 			size_t c = 0;
-			hdr[c++] = (uint8_t)((first ? 0xE0 : 0x80) | ((usize - 1) >> 16));
+			hdr[c++] = (uint8_t)((first ? 0xE0 : reset ? 0xC0 : 0x80) | ((usize - 1) >> 16));
 			hdr[c++] = (uint8_t)((usize - 1) >> 8);
 			hdr[c++] = (uint8_t)(usize - 1);
 			hdr[c++] = (uint8_t)((csize - 1) >> 8);
 			hdr[c++] = (uint8_t)(csize - 1);
-			if (first) hdr[c++] = (uint8_t)((props.pb * 5 + props.lp) * 9 + props.lc);
+			if (first || reset) hdr[c++] = (uint8_t)((props.pb * 5 + props.lp) * 9 + props.lc);
 			xz_write(output, hdr, c, &failed);
 			xz_write(output, cbuf, csize, &failed);
 			unpadded += c + csize;
-			first = false;
+			first = reset = false;
 		}
 		free(cbuf);
 		mgl_lzma_state_free(&st);
@@ -605,6 +717,23 @@ bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_pr
 	hdr[11] = 'Z';
 	xz_write(output, hdr, 12, &failed);
 	return true;
+}
+
+bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_properties props, const mgl_packet* slab,
+                 const mgl_xz_options* opt, OutputInterface* output)
+{
+	const mgl_segment whole = { 0, n, props, 0 };
+	return emit_xz_core("mgl_emit_xz", original, coded, n, slab, &whole, 1, opt, output);
+}
+
+bool mgl_emit_xz_segments(const uint8_t* original, const uint8_t* coded, size_t n, const mgl_packet* slab, const mgl_segment* segs,
+                          size_t nseg, const mgl_xz_options* opt, OutputInterface* output)
+{
+	if (n ? (!segs || nseg == 0) : nseg != 0) {
+		fprintf(stderr, "Error: mgl_emit_xz_segments: the segments do not tile the input\n");
+		return false;
+	}
+	return emit_xz_core("mgl_emit_xz_segments", original, coded, n, slab, segs, nseg, opt, output);
 }
 
 /* ------------------------------------------------------------------ stream import

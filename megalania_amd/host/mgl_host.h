@@ -17,6 +17,8 @@
  *   mgl_emit_stream_dict              mgl_emit_stream with the dictionary size as a parameter
  *   mgl_bcj_x86 / mgl_emit_xz         (no reference equivalent: the .xz container and its x86 filter)
  *   mgl_host_cost_map                 (no reference equivalent: perplexity_encoder.c's sum split per byte and per coder)
+ *   mgl_host_segment_cost / _packets, mgl_emit_xz_segments  (no reference equivalent: a parse coded in segments, each behind
+ *                                     an LZMA2 state reset under its own lc/lp/pb)
  *
  * Stream import reads the parse out of an existing LZMA-alone (.lzma) or .xz stream of the same
  * input, as a starting slab for the search (the best known parse of a file is usually the one
@@ -108,6 +110,27 @@ typedef struct {
  * false (with a message on stderr) on a bad slab or option. */
 bool mgl_emit_xz(const uint8_t* original, const uint8_t* coded, size_t n, mgl_properties props, const mgl_packet* slab,
                  const mgl_xz_options* opt, OutputInterface* output);
+
+/* Segment props on the host (include/megalania_hip.h, "Segment props", has the definitions; one re-expression routine
+ * serves all three).
+ * mgl_host_segment_cost: *cost (nullable) = cost(lo, hi, props), the segment's re-expressed packets through the perplexity
+ * encoder from a fresh model; *reexpressed (nullable) = how many of them differ from the slab's.  lo == hi costs 0.
+ * MGL_EINVAL: lc + lp > 4 or pb > 4, n = 0, a slab that is not a valid parse (mgl_host_cost_map's check), lo > hi, hi > n,
+ * lo or hi not a packet start of the walk.  MGL_ENOMEM when the model cannot be allocated.
+ * mgl_host_segment_packets: the same walk without a model; out (nullable, cap entries) receives the re-expressed packets
+ * in walk order, *count their number; MGL_ERANGE, with *count set, when out is too small. */
+int mgl_host_segment_cost(const uint8_t* data, size_t n, const mgl_packet* slab, uint64_t lo, uint64_t hi, mgl_properties props,
+                          uint64_t* cost, uint64_t* reexpressed);
+int mgl_host_segment_packets(const uint8_t* data, size_t n, const mgl_packet* slab, uint64_t lo, uint64_t hi, mgl_packet* out,
+                             size_t cap, size_t* count);
+/* mgl_emit_xz with a triple per segment: still one stream of one block and one dictionary.  segs[0 .. nseg) tile [0, n) in
+ * ascending order, every lo a packet start of the slab's walk (`cost` is not looked at).  The first chunk is 0xE0 as in
+ * mgl_emit_xz; the first chunk of every later segment is 0xC0 -- state reset and that segment's props byte, also where the
+ * triple repeats --; all others are 0x80.  A chunk never crosses a segment's end and a packet is never split; the
+ * chunk-size rules are mgl_emit_xz's.  One segment writes mgl_emit_xz's bytes.  n = 0 (with nseg = 0) writes the empty
+ * stream.  false (with a message on stderr) as mgl_emit_xz, and when the segments do not tile [0, n) at packet starts. */
+bool mgl_emit_xz_segments(const uint8_t* original, const uint8_t* coded, size_t n, const mgl_packet* slab, const mgl_segment* segs,
+                          size_t nseg, const mgl_xz_options* opt, OutputInterface* output);
 
 typedef struct {
 	int container;            /* 1 LZMA-alone (.lzma), 2 .xz */
