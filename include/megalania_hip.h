@@ -43,6 +43,9 @@
  *   mgl_segment_cuts, mgl_props_sweep_spans, mgl_segment_partition, mgl_sa_segment_props
  *                     no reference counterpart: a parse cut into segments that each start from an LZMA2 state reset under
  *                                    their own lc/lp/pb, every candidate segment costed under every triple at once
+ *   mgl_segment_reparse
+ *                     no reference counterpart: the adaptive parse made again inside every segment, from its reset and
+ *                                    under its own triple
  *
  * Error convention: the reference returns NULL / -1 / false and prints to stderr
  * (packet_slab.c:18-27, memory_mapper.c:12-31); here constructors return NULL and
@@ -647,6 +650,46 @@ int mgl_segment_partition(const uint64_t* cost, size_t ncuts, const uint64_t* cu
  * *single_best (nullable) = min_T cost[s(0, m)][T], the best one triple does; *total <= *single_best. */
 int mgl_sa_segment_props(mgl_sa* sa, const mgl_packet* packets, uint64_t grain, mgl_segment* segs_out, size_t cap, size_t* nseg,
                          uint64_t* total, uint64_t* single_best, double* gpu_ms);
+/* Segment re-parse (no reference counterpart; DESIGN.md section 10, megalania_amd/csrc/mgl_segparse.hip): the adaptive parse
+ * of mgl_sa_seed_adaptive run again inside every segment, for the coder that will code it -- from the state reset at the
+ * segment's start and under the segment's own triple -- instead of for the one triple and the one running model the slab
+ * was made under.  Exact integers in mgl_cost_slab's units throughout.
+ *   - Input: a valid slab (`packets`, NULL: the current slab), nseg segments that tile [0, n) at packet starts (what
+ *     mgl_emit_xz_segments accepts), and mgl_adaptive_config's settings with their defaults; from_current must be 0.  The
+ *     handle's match finder and depth apply as for mgl_sa_seed_adaptive.
+ *   - Per segment s = [lo, hi) under its triple T_s, independently of the others.  Chunk m is [lo + m chunk,
+ *     min(lo + (m + 1) chunk, hi)): the grid starts at lo.  Pass 0's chunk starts and model snapshots come from the walk of
+ *     the segment's own packets from the reset, re-expressed as under "Segment props" above (a chunk start inside a packet
+ *     takes the LZMA initial state and the model before that packet, as in mgl_sa_seed_adaptive); that walk's cost is
+ *     start_cost = cost(lo, hi, T_s).  Pass p runs mgl_sa_seed_adaptive's shortest path over every chunk with prices under
+ *     T_s's layout; an edge ends at its chunk's end at the latest, so no packet crosses hi, while MATCH sources are absolute
+ *     positions bounded by the dictionary only: copies reach below lo.  The pass's copies are then walked from the reset,
+ *     resolved against the segment coder's own rep stack and costed exactly (pass_cost[p]); that walk leaves pass p + 1's
+ *     starts.  objective[p] as in mgl_optimal_stats.  The cheapest pass is taken if it costs strictly less than start_cost,
+ *     ties to the lower pass; otherwise the segment keeps its packets and best_pass is UINT32_MAX.
+ *   - Join.  A slab's rep packets name the rep stack of the walk from byte 0, so the result is assembled as copies and
+ *     resolved once: one walk from 0 takes per segment the input's packets, their distances made absolute through the
+ *     input's own stack, or the taken pass's copies, and names each against the output's running stack (distance found in
+ *     the stack: SHORT_REP for length 1, else LONG_REP of the least such slot; otherwise LITERAL for length 1, else MATCH).
+ *     The output is an ordinary valid slab with the same segments at packet starts; final_cost = cost(lo, hi, T_s) of it.
+ *     A packet that uses the distance-1 rep a reset leaves in the coder's stack can come out of the join as a MATCH or a
+ *     LITERAL where the whole-file stack lacks that distance; final_cost then differs from pass_cost[best_pass] by that
+ *     packet, and by nothing else.
+ *   - Guard.  Unless the sum of final_cost is strictly below the sum of start_cost the call hands back the input slab:
+ *     *taken = 0, final_cost = start_cost and best_pass = UINT32_MAX for every segment.  The result never costs more. */
+typedef struct {
+	uint32_t passes, best_pass;             /* best_pass UINT32_MAX: the input's packets were kept */
+	uint64_t start_cost, final_cost;
+	uint64_t pass_cost[MGL_OPT_MAX_PASSES], objective[MGL_OPT_MAX_PASSES];
+} mgl_segment_parse_stats;
+/* packets_out: n entries.  segs_out: nseg entries, the same lo, hi and props with cost = final_cost.  stats: nseg entries,
+ * nullable; taken and gpu_ms (device time of the call) nullable.  The search state is untouched; the call's buffers (about
+ * 40 bytes per input byte) are its own and die with it, MGL_ENOMEM leaves the handle usable.  MGL_EINVAL: a null argument,
+ * nseg outside 1..16, segments that do not tile [0, n) in ascending order, a triple outside lc + lp <= 4, pb <= 4, whatever
+ * mgl_sa_seed_adaptive refuses of the settings, from_current != 0.  MGL_ERANGE: an invalid slab, or a segment boundary that
+ * is no packet start.  mgl_emit_xz_segments(packets_out, segs_out) codes the result. */
+int mgl_segment_reparse(mgl_sa* sa, const mgl_packet* packets, const mgl_segment* segs, size_t nseg, const mgl_adaptive_config* cfg,
+                        mgl_packet* packets_out, mgl_segment* segs_out, mgl_segment_parse_stats* stats, int* taken, double* gpu_ms);
 /* Final model state after costing `packets`: probabilities in the reference's struct order
  * (lzma_state.h:47-53: lit | len | rep_len | dist | ctx_state), ctx_state, rep distances. */
 int mgl_final_state(mgl_sa* sa, const mgl_packet* packets, uint16_t* probs_out, size_t probs_cap,

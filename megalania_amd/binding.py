@@ -45,6 +45,7 @@ HIP_SYMBOLS = [
     "mgl_sa_set_target_weights", "mgl_sa_weight_targets_by_cost", "mgl_sa_target_weights", "mgl_weight_value",
     "mgl_cost_map_live", "mgl_sa_set_live_weights", "mgl_sa_live_weights",
     "mgl_segment_cuts", "mgl_props_sweep_spans", "mgl_segment_partition", "mgl_sa_segment_props",
+    "mgl_segment_reparse",
 ]
 LW_SINGLE_ONLY = 1
 HOST_SYMBOLS = [
@@ -219,6 +220,16 @@ class Segment(C.Structure):
         return dict(lo=self.lo, hi=self.hi, props=(self.props.lc, self.props.lp, self.props.pb), cost=self.cost)
 
 
+class SegmentParseStats(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("best_pass", C.c_uint32), ("start_cost", C.c_uint64), ("final_cost", C.c_uint64),
+                ("pass_cost", C.c_uint64 * OPT_MAX_PASSES), ("objective", C.c_uint64 * OPT_MAX_PASSES)]
+
+    def asdict(self):
+        k = self.passes
+        return dict(passes=k, best_pass=None if self.best_pass == 0xFFFFFFFF else self.best_pass, start_cost=self.start_cost,
+                    final_cost=self.final_cost, pass_cost=list(self.pass_cost[:k]), objective=list(self.objective[:k]))
+
+
 def _segments(segs):
     """dicts (lo, hi, props[, cost]) or Segment instances as a C array"""
     arr = (Segment * max(len(segs), 1))()
@@ -374,6 +385,9 @@ def hip_lib():
         L.mgl_sa_segment_props.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(Segment), C.c_size_t,
                                            C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_double)]
+        L.mgl_segment_reparse.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Segment), C.c_size_t, C.POINTER(AdaptiveConfig),
+                                          C.c_void_p, C.POINTER(Segment), C.POINTER(SegmentParseStats), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_double)]
         L.mgl_rng_draw_at.restype = C.c_uint32
         L.mgl_rng_draw_at.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
         _hip = L
@@ -1043,6 +1057,27 @@ class SA:
                                               C.byref(single), C.byref(ms)))
         return dict(segments=[segs[k].asdict() for k in range(nseg.value)], total=total.value, single_best=single.value,
                     gpu_ms=ms.value)
+
+    def segment_reparse(self, segs, slab=None, passes: int = 0, cand: int = 0, chunk: int = 0, segment: int = 0, ahead: int = 0,
+                        from_current: bool = False):
+        """The adaptive parse made again inside every segment of `segs` (dicts lo, hi, props that tile the input at packet
+        starts of `slab`; None: the current slab), each from its LZMA2 state reset and under its own triple
+        (mgl_segment_reparse; SA state untouched; the settings are seed_adaptive's, from_current is refused).  Returns
+        (slab, segs, stats, taken, gpu_ms): the joined slab and the same segments with cost = final_cost -- what
+        emit_xz_segments takes --, per segment dict(passes, best_pass (None: its packets were kept), start_cost, final_cost,
+        pass_cost, objective), and whether the result is the joined slab (True) or the input handed back because the
+        join did not cost less (False)."""
+        slab = self._own_slab(slab, "segment_reparse")
+        nseg = len(segs)
+        out = np.zeros(self.n, dtype=PACKET)
+        segs_out = (Segment * max(nseg, 1))()
+        st = (SegmentParseStats * max(nseg, 1))()
+        taken, ms = C.c_int(0), C.c_double(0)
+        cfg = AdaptiveConfig(passes, cand, chunk, segment, ahead, int(from_current))
+        self._chk(self.L.mgl_segment_reparse(self.h, _ptr(slab), _segments(segs), nseg, C.byref(cfg), _ptr(out), segs_out, st,
+                                             C.byref(taken), C.byref(ms)))
+        return (out, [segs_out[k].asdict() for k in range(nseg)], [st[k].asdict() for k in range(nseg)], bool(taken.value),
+                ms.value)
 
     def cost_map(self, slab=None, props=None):
         """Where `slab` (None: the current slab) spends its bits under props = (lc, lp, pb) (None: the handle's; another

@@ -12,7 +12,8 @@
  *                     initial state, costs it exactly, and leaves the walk state and a copy of the model at every chunk
  *                     start; when resolving it resolves the DP's copies on the way, as k_opt_walk does
  *   k_adp_dp_sweep    one workgroup (one wavefront) per chunk and variant: the forward shortest path, segment by segment
- *                     (the instance <true> reads its MATCH sources from the lists of mgl_matchfinder.hip, as k_opt_dp<true>)
+ *                     (the instance <true> reads its MATCH sources from the lists of mgl_matchfinder.hip, as k_opt_dp<true>);
+ *                     its body, adp_dp_chunk, is shared with the per-segment parse of mgl_segparse.hip
  *
  * A variant carries its own lc/lp/pb (mgl_parse_sweep_props): the bodies take the probability layout as an argument,
  * nothing else of a parse depends on it.
@@ -102,45 +103,35 @@ struct AdpLivePrices {
 
 extern __shared__ __align__(4) uint16_t adp_model[]; /* the chunk's model: adp_stride(L) u16, sized at launch (a sweep: its largest) */
 
-/* Workgroup (m, y) runs chunk m = [s, e) of variant v = list[y], one of the variants of this instance's finder, with that
- * variant's settings and layout from `tab` and on its slice of entry, snaps, back, out and objective.  The DP of
- * mgl_optimal.hip runs over the nodes a..end of one segment at a time, an edge ending at `end` at the latest, with prices
- * read from the model M in LDS, which stays frozen while a segment's DP runs.  Lane 0 then reads the path off the back
- * pointers into out[] (entries that start before the commit horizon only), and the wavefront walks those entries forward
- * from the anchor: lane e applies event e of each to M, under the exact state of the path.  Where that walk ends is the
- * next anchor.
+/* The shortest path of one chunk [s, e) under the live model, by one workgroup of one wavefront: settings and layout are the
+ * caller's, `start` holds the five words of the chunk's walk state and `snap` its model (adp_stride(L) u16), S, T and M are
+ * the workgroup's LDS.  The DP of mgl_optimal.hip runs over the nodes a..end of one segment at a time, an edge ending at `end`
+ * at the latest, with prices read from the model M in LDS, which stays frozen while a segment's DP runs.  Lane 0 then reads
+ * the path off the back pointers into out[] (entries that start before the commit horizon only), and the wavefront walks
+ * those entries forward from the anchor: lane e applies event e of each to M, under the exact state of the path.  Where that
+ * walk ends is the next anchor.  The sum of what the segments committed is added to *objective.
  *
- * back[] and out[] are read and written by lane 0 alone (what the other lanes need of an entry is broadcast).  Until it is
- * committed, an entry of out[] keeps a LONG_REP's rep index above the type byte (MGL_OPT_REP_SHIFT). */
+ * back[] and out[] are indexed by absolute position (back: nodes s + 1 .. e, out: [s, e)) and are read and written by lane 0
+ * alone (what the other lanes need of an entry is broadcast).  Until it is committed, an entry of out[] keeps a LONG_REP's rep
+ * index above the type byte (MGL_OPT_REP_SHIFT).  k_adp_dp_sweep below and k_segp_dp (mgl_segparse.hip) are its callers. */
 template <bool MF>
-__global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant* tab, const uint32_t* list, uint32_t nch, const uint32_t* entry,
-                                                     const uint16_t* snaps, uint32_t chunk, mgl_pk* back, mgl_pk* out,
-                                                     unsigned long long* objective, MfLists mf)
+__device__ __forceinline__ void adp_dp_chunk(OptLds& S, uint16_t* T, uint16_t* M, const DevCtx& c, const mgl_layout& L, uint32_t cand,
+                                             uint32_t segment, uint32_t ahead, uint32_t s, uint32_t e, const uint32_t* start,
+                                             const uint16_t* snap, mgl_pk* back, mgl_pk* out, unsigned long long* objective, const MfLists& mf)
 {
-	__shared__ OptLds S;
-	__shared__ uint16_t T[2048];
-	uint16_t* M = adp_model;
-
-	const uint32_t lane = threadIdx.x, m = blockIdx.x, v = list[blockIdx.y];
-	const AdpVariant t = tab[v];
-	const mgl_layout L = adp_variant_layout(t);
-	const uint32_t cand = t.cand, segment = t.segment, ahead = t.ahead;
-	const uint32_t s = m * chunk;
-	const uint32_t e = (s + chunk) < c.n ? (s + chunk) : c.n;
+	const uint32_t lane = threadIdx.x;
 	const uint8_t* d = c.data;
 	const uint32_t stride = adp_stride(L);
-	entry += (size_t)v * 5u * nch; snaps += t.snap_off;
-	back += (size_t)v * ((size_t)c.n + 1u); out += (size_t)v * c.n;
 	const AdpLivePrices price{ M, T };
 
 	for (uint32_t k = lane; k < 2048u; k += 64u) T[k] = c.cost_tbl[k];
 	{
-		const uint32_t* src = (const uint32_t*)(snaps + (size_t)m * stride);
+		const uint32_t* src = (const uint32_t*)snap;
 		uint32_t* dst = (uint32_t*)M;
 		for (uint32_t k = lane; k < stride / 2u; k += 64u) dst[k] = src[k];
 	}
 	/* the anchor: position a, its exact walk state A (uniform) */
-	mgl_wstate A = state_from_words(entry + 5u * m, s);
+	mgl_wstate A = state_from_words(start, s);
 	uint64_t obj = 0;
 	__syncthreads();
 
@@ -184,5 +175,26 @@ __global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant*
 		a = pos;
 		__syncthreads();
 	}
-	if (lane == 0) atomicAdd(objective + v, (unsigned long long)obj);
+	if (lane == 0) atomicAdd(objective, (unsigned long long)obj);
+}
+
+/* Workgroup (m, y) runs chunk m = [s, e) of variant v = list[y], one of the variants of this instance's finder, with that
+ * variant's settings and layout from `tab` and on its slice of entry, snaps, back, out and objective: adp_dp_chunk above. */
+template <bool MF>
+__global__ void __launch_bounds__(64) k_adp_dp_sweep(DevCtx c, const AdpVariant* tab, const uint32_t* list, uint32_t nch, const uint32_t* entry,
+                                                     const uint16_t* snaps, uint32_t chunk, mgl_pk* back, mgl_pk* out,
+                                                     unsigned long long* objective, MfLists mf)
+{
+	__shared__ OptLds S;
+	__shared__ uint16_t T[2048];
+	uint16_t* M = adp_model;
+
+	const uint32_t m = blockIdx.x, v = list[blockIdx.y];
+	const AdpVariant t = tab[v];
+	const mgl_layout L = adp_variant_layout(t);
+	const uint32_t s = m * chunk;
+	const uint32_t e = (s + chunk) < c.n ? (s + chunk) : c.n;
+	adp_dp_chunk<MF>(S, T, M, c, L, t.cand, t.segment, t.ahead, s, e, entry + ((size_t)v * nch + m) * 5u,
+	                 snaps + t.snap_off + (size_t)m * adp_stride(L), back + (size_t)v * ((size_t)c.n + 1u), out + (size_t)v * c.n,
+	                 objective + v, mf);
 }

@@ -16,6 +16,7 @@
 #include "mgl_adaptive.hip"
 #include "mgl_props.hip"
 #include "mgl_segments.hip"
+#include "mgl_segparse.hip"
 #include "mgl_costmap.hip"
 #include "mgl_costmap_live.hip"
 #include "mgl_crossover.hip"
@@ -2625,6 +2626,227 @@ extern "C" int mgl_sa_segment_props(mgl_sa* sa, const mgl_packet* packets, uint6
 	*nseg = k;
 	if (cap < k) return fail(MGL_ERANGE, "mgl_sa_segment_props: segs_out is too small");
 	memcpy(segs_out, segs, sizeof(mgl_segment) * k);
+	return MGL_OK;
+}
+
+/* ---- segment re-parse (mgl_segparse.hip; include/megalania_hip.h, "Segment re-parse", has the rule): the stages of
+ * mgl_segment_reparse, in the order they stand in.  One SegParse is one call: its buffers die with it. */
+#define MGL_SEGP_MAX (MGL_SEG_MAX_CUTS - 1)
+struct SegParse {
+	/* settings (segp_args) */
+	uint32_t nseg = 0, passes = 0, chunk = 0, maxch = 0, totch = 0, lds = 0;
+	size_t snap_total = 0;
+	SegVariant h_tab[MGL_SEGP_MAX];
+	uint32_t h_cuts[MGL_SEG_MAX_CUTS];
+	/* device buffers and events (segp_alloc) */
+	SegVariant* tab = nullptr;
+	uint32_t *cuts = nullptr, *starts = nullptr, *entry = nullptr, *take = nullptr, *done = nullptr;
+	uint16_t* snaps = nullptr;
+	mgl_pk *back = nullptr, *dp = nullptr, *keep = nullptr, *out = nullptr;
+	unsigned long long* obj = nullptr;
+	uint64_t* cost = nullptr;
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	/* the last walk's costs and the last DP's objectives, per segment */
+	uint64_t h_cost[MGL_SEGP_MAX];
+	unsigned long long h_obj[MGL_SEGP_MAX];
+	DevOwner own;
+};
+
+/* argument checks; per segment its place, triple, settings after the defaults and clamps, its chunks and its snapshots */
+static int segp_args(const mgl_sa* sa, SegParse& P, const mgl_segment* segs, size_t nseg, const mgl_adaptive_config* cfg)
+{
+	if (nseg < 1 || nseg > MGL_SEGP_MAX) return fail(MGL_EINVAL, "mgl_segment_reparse: between 1 and 16 segments");
+	for (size_t k = 0; k < nseg; k++) {
+		if (segs[k].lo != (k ? segs[k - 1].hi : 0) || segs[k].hi <= segs[k].lo || segs[k].hi > sa->n)
+			return fail(MGL_EINVAL, "mgl_segment_reparse: the segments must tile [0, n) in ascending order");
+		if ((uint32_t)segs[k].props.lc + segs[k].props.lp > 4u || segs[k].props.pb > 4u)
+			return fail(MGL_EINVAL, "mgl_segment_reparse: supported properties are lc + lp <= 4, pb <= 4");
+	}
+	if (segs[nseg - 1].hi != sa->n) return fail(MGL_EINVAL, "mgl_segment_reparse: the segments must tile [0, n) in ascending order");
+	if (cfg && cfg->from_current) return fail(MGL_EINVAL, "mgl_segment_reparse: from_current must be 0 (the slab is the packets argument)");
+	P.nseg = (uint32_t)nseg;
+	P.passes = cfg && cfg->passes ? cfg->passes : MGL_OPT_DEF_PASSES;
+	if (P.passes > MGL_OPT_MAX_PASSES) return fail(MGL_EINVAL, "adaptive parse: at most 16 passes");
+	uint32_t cand = cfg && cfg->cand ? cfg->cand : MGL_OPT_DEF_CAND, segment = cfg ? cfg->segment : 0u, ahead = cfg ? cfg->ahead : 0u;
+	P.chunk = cfg && cfg->chunk ? cfg->chunk : MGL_OPT_DEF_CHUNK;
+	TRY(adp_args(sa, cand, P.chunk, segment, ahead, false));
+	for (uint32_t v = 0; v < P.nseg; v++) {
+		SegVariant& t = P.h_tab[v];
+		t.lo = (uint32_t)segs[v].lo; t.hi = (uint32_t)segs[v].hi;
+		t.props = adp_pack_props(segs[v].props.lc, segs[v].props.lp, segs[v].props.pb);
+		t.cand = cand; t.segment = segment; t.ahead = ahead;
+		t.nch = (t.hi - t.lo + P.chunk - 1u) / P.chunk;
+		t.ch_off = P.totch; t.snap_off = P.snap_total;
+		const uint32_t stride = adp_stride(mgl_make_layout(segs[v].props.lc, segs[v].props.lp, segs[v].props.pb));
+		P.totch += t.nch;
+		P.snap_total += (size_t)t.nch * stride;
+		if (t.nch > P.maxch) P.maxch = t.nch;
+		if (stride * (uint32_t)sizeof(uint16_t) > P.lds) P.lds = stride * (uint32_t)sizeof(uint16_t);
+		P.h_cuts[v] = t.lo;
+	}
+	P.h_cuts[P.nseg] = (uint32_t)sa->n;
+	return MGL_OK;
+}
+
+static int segp_alloc(mgl_sa* sa, SegParse& P)
+{
+	static const char* nomem = "mgl_segment_reparse: the call's buffers do not fit the device";
+	const size_t n = sa->n;
+	auto room = [&](auto*& ptr, size_t count) { return dnew(P.own, ptr, count, -1, nomem); };
+	TRY(room(P.tab, MGL_SEGP_MAX));
+	TRY(room(P.cuts, MGL_SEG_MAX_CUTS));
+	TRY(room(P.starts, MGL_SEG_MAX_CUTS * MGL_SEG_START_WORDS));
+	TRY(room(P.take, MGL_SEGP_MAX));
+	TRY(room(P.done, 1));
+	TRY(room(P.obj, MGL_SEGP_MAX));
+	TRY(room(P.cost, MGL_SEGP_MAX));
+	TRY(dnew(P.own, P.entry, 5 * (size_t)P.totch, 0, nomem)); /* a walk that stops early leaves the LZMA initial state behind it */
+	TRY(room(P.snaps, P.snap_total));
+	TRY(room(P.back, n + 1));
+	TRY(room(P.dp, n));
+	TRY(room(P.keep, n));
+	TRY(room(P.out, n));
+	HIPCHK(P.own.event(&P.t0));
+	HIPCHK(P.own.event(&P.t1));
+	if (sa->mf_finder == MGL_MF_FRONTIER) HIPCHK(hipFuncSetAttribute((const void*)k_segp_dp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+	else HIPCHK(hipFuncSetAttribute((const void*)k_segp_dp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+	HIPCHK(hipMemcpyAsync(P.tab, P.h_tab, sizeof(SegVariant) * P.nseg, hipMemcpyHostToDevice, sa->q.stream));
+	HIPCHK(hipMemcpyAsync(P.cuts, P.h_cuts, sizeof(uint32_t) * (P.nseg + 1u), hipMemcpyHostToDevice, sa->q.stream));
+	return MGL_OK;
+}
+
+/* The walk of `slab` (a valid parse on the device) segment by segment from the resets: h_cost holds cost(lo, hi, T_s) of
+ * every segment afterwards; `snaps`: the walk leaves the chunk starts and the model snapshots as well.  MGL_ERANGE (or
+ * `bad`) where a segment boundary is no packet start of the slab. */
+static int segp_slab_walk(mgl_sa* sa, SegParse& P, const mgl_pk* slab, bool snaps, int bad)
+{
+	hipStream_t s = sa->q.stream;
+	const uint32_t ncuts = P.nseg + 1u;
+	hipLaunchKernelGGL(k_seg_starts, dim3(1), dim3(64), 0, s, sa->ctx, slab, (const uint32_t*)P.cuts, ncuts, P.starts);
+	hipLaunchKernelGGL(k_segp_walk, dim3(P.nseg), dim3(64), 0, s, sa->ctx, (const SegVariant*)P.tab, slab, 0, P.chunk, (const uint32_t*)P.starts,
+	                   P.entry, snaps ? P.snaps : (uint16_t*)nullptr, P.cost);
+	HIPCHK(hipGetLastError());
+	uint32_t h_starts[MGL_SEG_MAX_CUTS * MGL_SEG_START_WORDS];
+	HIPCHK(hipMemcpyAsync(h_starts, P.starts, sizeof(uint32_t) * ncuts * MGL_SEG_START_WORDS, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * P.nseg, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (uint32_t k = 0; k < ncuts; k++)
+		if (!h_starts[k * MGL_SEG_START_WORDS])
+			return fail(bad, "mgl_segment_reparse: segment boundary " + std::to_string(P.h_cuts[k]) + " is not a packet start of the walk");
+	return MGL_OK;
+}
+
+/* One pass: the DP of every chunk of every segment from the starts in entry / snaps into dp, then the walk that resolves
+ * the copies against each segment coder's own state, costs them exactly and leaves the next pass's starts */
+static int segp_pass(mgl_sa* sa, SegParse& P, bool snaps)
+{
+	hipStream_t s = sa->q.stream;
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, s, P.dp, (size_t)sa->n);
+	HIPCHK(hipMemsetAsync(P.obj, 0, sizeof(unsigned long long) * P.nseg, s));
+	if (sa->mf_finder == MGL_MF_FRONTIER)
+		hipLaunchKernelGGL(k_segp_dp<true>, dim3(P.maxch, P.nseg), dim3(64), P.lds, s, sa->ctx, (const SegVariant*)P.tab, (const uint32_t*)P.entry,
+		                   (const uint16_t*)P.snaps, P.chunk, P.back, P.dp, P.obj, mf_lists(sa));
+	else
+		hipLaunchKernelGGL(k_segp_dp<false>, dim3(P.maxch, P.nseg), dim3(64), P.lds, s, sa->ctx, (const SegVariant*)P.tab, (const uint32_t*)P.entry,
+		                   (const uint16_t*)P.snaps, P.chunk, P.back, P.dp, P.obj, MfLists{});
+	hipLaunchKernelGGL(k_segp_walk, dim3(P.nseg), dim3(64), 0, s, sa->ctx, (const SegVariant*)P.tab, (const mgl_pk*)P.dp, 1, P.chunk,
+	                   (const uint32_t*)nullptr, P.entry, snaps ? P.snaps : (uint16_t*)nullptr, P.cost);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(P.h_obj, P.obj, sizeof(unsigned long long) * P.nseg, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(P.h_cost, P.cost, sizeof(uint64_t) * P.nseg, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return MGL_OK;
+}
+
+/* The join: out = per segment the input's packets or the kept DP copies, resolved in one walk from byte 0; then the cost of
+ * every segment of it, as pass 0's starts were made */
+static int segp_join(mgl_sa* sa, SegParse& P, const mgl_pk* slab, const uint32_t* h_take)
+{
+	hipStream_t s = sa->q.stream;
+	HIPCHK(hipMemcpyAsync(P.take, h_take, sizeof(uint32_t) * P.nseg, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(k_fill_literal, dim3(1024), dim3(256), 0, s, P.out, (size_t)sa->n);
+	/* starts still holds the input's true stacks at the cuts (segp_slab_walk) */
+	hipLaunchKernelGGL(k_segp_join, dim3(1), dim3(64), 0, s, sa->ctx, (const SegVariant*)P.tab, P.nseg, (const uint32_t*)P.take, slab,
+	                   (const mgl_pk*)P.keep, (const uint32_t*)P.starts, P.out, P.done);
+	HIPCHK(hipGetLastError());
+	uint32_t done = 0;
+	HIPCHK(hipMemcpyAsync(&done, P.done, sizeof done, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (done != sa->n) return fail(MGL_EDEVICE, "mgl_segment_reparse: the join's walk stopped at " + std::to_string(done));
+	return segp_slab_walk(sa, P, P.out, false, MGL_EDEVICE);
+}
+
+extern "C" int mgl_segment_reparse(mgl_sa* sa, const mgl_packet* packets, const mgl_segment* segs, size_t nseg, const mgl_adaptive_config* cfg,
+                                   mgl_packet* packets_out, mgl_segment* segs_out, mgl_segment_parse_stats* stats, int* taken, double* gpu_ms)
+{
+	if (!sa || !segs || !packets_out || !segs_out) return fail(MGL_EINVAL, "null argument");
+	SegParse P;
+	TRY(segp_args(sa, P, segs, nseg, cfg));
+	HIPCHK(hipSetDevice(sa->device));
+	const mgl_pk* slab = sa->base.v.slab;
+	std::vector<mgl_packet> host(sa->n);
+	if (packets) {
+		Control c;
+		if (scratch_walk(sa, packets, false, false, &c)) return fail(MGL_ERANGE, "mgl_segment_reparse: packets is not a valid parse of the input");
+		slab = sa->scratch.v.slab;
+		memcpy(host.data(), packets, sizeof(mgl_packet) * (size_t)sa->n);
+	} else TRY(export_slab(sa, slab, host.data()));
+	if (sa->mf_finder == MGL_MF_FRONTIER) TRY(mf_ensure(sa, sa->mf_depth));
+	TRY(segp_alloc(sa, P));
+	HIPCHK(hipEventRecord(P.t0, sa->q.stream));
+
+	mgl_segment_parse_stats st[MGL_SEGP_MAX];
+	memset(st, 0, sizeof st);
+	uint64_t best[MGL_SEGP_MAX], sum_start = 0, sum_final = 0;
+	uint32_t take[MGL_SEGP_MAX], any = 0;
+	TRY(segp_slab_walk(sa, P, slab, true, MGL_ERANGE));
+	for (uint32_t v = 0; v < P.nseg; v++) {
+		st[v].passes = P.passes; st[v].best_pass = UINT32_MAX;
+		st[v].start_cost = st[v].final_cost = best[v] = P.h_cost[v];
+		sum_start += P.h_cost[v];
+	}
+	for (uint32_t p = 0; p < P.passes; p++) {
+		TRY(segp_pass(sa, P, p + 1 < P.passes));
+		for (uint32_t v = 0; v < P.nseg; v++) {
+			st[v].pass_cost[p] = P.h_cost[v]; st[v].objective[p] = P.h_obj[v];
+			if (P.h_cost[v] >= best[v]) continue;
+			best[v] = P.h_cost[v]; st[v].best_pass = p;
+			const SegVariant& t = P.h_tab[v];
+			HIPCHK(hipMemcpyAsync(P.keep + t.lo, P.dp + t.lo, sizeof(mgl_pk) * (t.hi - t.lo), hipMemcpyDeviceToDevice, sa->q.stream));
+		}
+	}
+	for (uint32_t v = 0; v < P.nseg; v++) any |= take[v] = st[v].best_pass != UINT32_MAX;
+
+	/* the guard: the joined slab is handed out only where its segments cost less than the input's, in total */
+	int took = 0;
+	if (any) {
+		TRY(segp_join(sa, P, slab, take));
+		for (uint32_t v = 0; v < P.nseg; v++) sum_final += P.h_cost[v];
+		took = sum_final < sum_start;
+	}
+	if (took) {
+		for (uint32_t v = 0; v < P.nseg; v++) st[v].final_cost = P.h_cost[v];
+		TRY(export_slab(sa, P.out, packets_out));
+	} else {
+		for (uint32_t v = 0; v < P.nseg; v++) st[v].best_pass = UINT32_MAX;
+		memcpy(packets_out, host.data(), sizeof(mgl_packet) * (size_t)sa->n);
+	}
+	HIPCHK(hipEventRecord(P.t1, sa->q.stream));
+	HIPCHK(hipEventSynchronize(P.t1));
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, P.t0, P.t1));
+	if (took) {
+		/* device consistency check: what is handed out is a valid parse of the input */
+		Control c;
+		if (scratch_walk(sa, packets_out, false, false, &c)) return fail(MGL_EDEVICE, "mgl_segment_reparse: the joined slab is not a valid parse of the input");
+	}
+	for (uint32_t v = 0; v < P.nseg; v++) {
+		segs_out[v] = segs[v];
+		segs_out[v].cost = st[v].final_cost;
+	}
+	if (stats) memcpy(stats, st, sizeof(mgl_segment_parse_stats) * P.nseg);
+	if (taken) *taken = took;
+	if (gpu_ms) *gpu_ms = ms;
 	return MGL_OK;
 }
 

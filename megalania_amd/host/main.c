@@ -124,6 +124,13 @@ static const char usage_options[] =
 	"               `segment: offset O bytes N lc=.. lp=.. pb=.. cost X B exact C reexpressed R` (X = C / 16384; R = rep packets\n"
 	"               named again against the segment's own rep stack).  Not with --cost-map, --cost-report or --cost-bucket,\n"
 	"               which describe a stream under one triple\n"
+	"  --segment-reparse P  with --segment-props: the chosen segments are parsed again, each for the coder that codes it -- P\n"
+	"               (1..16) passes of the adaptive parse from the state reset at the segment's start, under the segment's own\n"
+	"               triple, copies still reaching below the cut (mgl_segment_reparse; --match-finder / --mf-depth apply).  A\n"
+	"               segment keeps its packets unless a pass costs less, and the whole result is dropped unless it costs less in\n"
+	"               total, so the stream never grows.  One round; lines on stderr:\n"
+	"               `segment-reparse: passes P segments M reparsed R taken 0|1 was X B exact C now X B exact C T ms`\n"
+	"               `segment-parse: offset O bytes N lc=.. lp=.. pb=.. start X B exact C best X B exact C pass p|- final X B exact C`\n"
 	"  --accept     what a step of K neighbours takes: the best acceptable one (single), every one that is\n"
 	"               the best of its own window (bulk), or whichever pays (auto, default)\n";
 
@@ -140,7 +147,7 @@ static void usage(const char* argv0)
 	        "          [--exchange best|cross|cross-all [--cross-grain N]]] [--focus LO:HI|rank]\n"
 	        "          [--target-weights cost[:mean|:N]|file:PATH]\n"
 	        "          [--live-weights R[:N|:mean][,single]]\n"
-	        "          [--cost-map FILE] [--cost-report] [--cost-bucket B] [--segment-props GRAIN|auto] filename\n", argv0);
+	        "          [--cost-map FILE] [--cost-report] [--cost-bucket B] [--segment-reparse P] [--segment-props GRAIN|auto] filename\n", argv0);
 	fputs(usage_options, stderr);
 }
 
@@ -177,6 +184,8 @@ typedef struct {
 	/* --segment-props: the grain, 0 for auto */
 	bool segment_props;
 	unsigned long long segment_grain;
+	uint32_t segment_reparse; /* --segment-reparse: the passes, 0 for none */
+	bool segment_reparse_given;
 	/* chains, exchange */
 	int chains, rank;
 	uint32_t exchange, cross_grain;
@@ -344,6 +353,10 @@ static int parse_args(int argc, char** argv, cli_opts* o)
 			if (strcmp(v, "auto") != 0 && (v[0] < '0' || v[0] > '9' || !number(v, &o->segment_grain) || !o->segment_grain))
 				why = "--segment-props takes a number of bytes, at least 1, or auto";
 		}
+		else if (!strcmp(a, "--segment-reparse")) {
+			o->segment_reparse_given = true;
+			if (v[0] < '0' || v[0] > '9' || !count_in(v, 1, MGL_OPT_MAX_PASSES, &o->segment_reparse)) why = "--segment-reparse takes a number of passes from 1 to 16";
+		}
 		else if (!strcmp(a, "--cost-bucket")) { if (!number(v, &o->cost_bucket) || !o->cost_bucket) why = "--cost-bucket takes a number of bytes, at least 1"; }
 		else bad = true;
 		if (bad || why) return refuse(o, why);
@@ -362,7 +375,7 @@ static int check_args(cli_opts* o)
 	if (o->optimal && (o->greedy || from_file)) return refuse(o, "--optimal-seed cannot be combined with --greedy-seed, --seed-stream or --load-slab");
 	if (o->adaptive && (o->optimal || o->greedy || from_file))
 		return refuse(o, "--adaptive-seed cannot be combined with --optimal-seed, --greedy-seed, --seed-stream or --load-slab");
-	if ((o->finder_given || o->mf_depth) && !(o->optimal || o->adaptive || o->props_auto))
+	if ((o->finder_given || o->mf_depth) && !(o->optimal || o->adaptive || o->props_auto || o->segment_reparse_given))
 		return refuse(o, "--match-finder / --mf-depth need --optimal-seed, --adaptive-seed or --props auto");
 	if ((o->parse_sweep && !o->adaptive) || (o->parse_sweep_table && !o->parse_sweep)) return refuse(o, NULL);
 	if (o->parse_sweep && o->finder_given) return refuse(o, "--parse-sweep runs both match finders; --match-finder cannot be combined with it");
@@ -377,6 +390,7 @@ static int check_args(cli_opts* o)
 	if (o->segment_props && !o->format_xz) return refuse(o, "--segment-props needs --format xz: an .lzma stream cannot reset its state or change lc/lp/pb");
 	if (o->segment_props && (o->cost_map_path || o->cost_report || o->cost_bucket))
 		return refuse(o, "--segment-props cannot be combined with --cost-map, --cost-report or --cost-bucket: they describe a stream under one triple");
+	if (o->segment_reparse_given && !o->segment_props) return refuse(o, "--segment-reparse needs --segment-props: it parses the segments that option chooses");
 	if (o->focus_rank && o->chains < 2) return refuse(o, "--focus rank needs --chains N with N at least 2");
 	if (o->live_given && o->weights != WEIGHTS_NONE) return refuse(o, "--live-weights and --target-weights exclude each other");
 	if (o->chains < 1 || o->rank < 0 || o->rank >= o->chains || (o->chains > 1 && !o->comm_path)) return refuse(o, NULL);
@@ -1171,6 +1185,54 @@ static int choose_segments(cli_run* r)
 	return 0;
 }
 
+/* --segment-reparse, behind choose_segments: the best slab and the chosen segments go through mgl_segment_reparse once, under
+ * the run's match finder; what comes back is what write_stream codes.  Every segment of the returned slab is walked once more
+ * on the host, as choose_segments does.  The line formats are fixed (README.md, "Segment re-parse"). */
+static int reparse_segments(cli_run* r)
+{
+	const cli_opts* o = r->o;
+	if (!o->segment_reparse || o->rank != 0) return 0;
+	const size_t n = r->file_size, nseg = r->nseg;
+	mgl_packet* out = (mgl_packet*)malloc(sizeof(mgl_packet) * n);
+	mgl_segment segs[MGL_SEG_MAX_CUTS];
+	mgl_segment_parse_stats st[MGL_SEG_MAX_CUTS];
+	const mgl_adaptive_config ac = { o->segment_reparse, 0, 0, 0, 0, 0 };
+	int taken = 0;
+	double ms = 0;
+	if (!out) return fail("out of memory");
+	if (mgl_sa_set_match_finder(r->sa, (int)o->finder, o->mf_depth) != MGL_OK ||
+	    mgl_segment_reparse(r->sa, r->packets_best, r->segs, nseg, &ac, out, segs, st, &taken, &ms) != MGL_OK) return lib_error();
+	uint64_t was = 0, now = 0;
+	size_t reparsed = 0;
+	for (size_t k = 0; k < nseg; k++) {
+		uint64_t cost = 0, changed = 0;
+		if (mgl_host_segment_cost(r->file_data, n, out, segs[k].lo, segs[k].hi, segs[k].props, &cost, &changed) != MGL_OK || cost != segs[k].cost)
+			return fail("segment at %llu: the host walk does not confirm the device's cost %llu of the re-parse", (unsigned long long)segs[k].lo,
+			            (unsigned long long)segs[k].cost);
+		was += st[k].start_cost + (k ? MGL_SEG_OVERHEAD : 0);
+		now += st[k].final_cost + (k ? MGL_SEG_OVERHEAD : 0);
+		reparsed += st[k].best_pass != UINT32_MAX;
+	}
+	fprintf(stderr, "segment-reparse: passes %u segments %zu reparsed %zu taken %d was %.3f B exact %llu now %.3f B exact %llu %.3f ms\n", o->segment_reparse,
+	        nseg, reparsed, taken, was / 16384.0, (unsigned long long)was, now / 16384.0, (unsigned long long)now, ms);
+	for (size_t k = 0; k < nseg; k++) {
+		const mgl_segment_parse_stats* s = &st[k];
+		uint64_t best = s->start_cost;
+		char pass[16] = "-";
+		for (uint32_t p = 0; p < s->passes; p++)
+			if (s->pass_cost[p] < best) best = s->pass_cost[p];
+		if (s->best_pass != UINT32_MAX) snprintf(pass, sizeof pass, "%u", s->best_pass);
+		fprintf(stderr, "segment-parse: offset %llu bytes %llu lc=%u lp=%u pb=%u start %.3f B exact %llu best %.3f B exact %llu pass %s final %.3f B exact %llu\n",
+		        (unsigned long long)segs[k].lo, (unsigned long long)(segs[k].hi - segs[k].lo), segs[k].props.lc, segs[k].props.lp, segs[k].props.pb,
+		        s->start_cost / 16384.0, (unsigned long long)s->start_cost, best / 16384.0, (unsigned long long)best, pass, s->final_cost / 16384.0,
+		        (unsigned long long)s->final_cost);
+	}
+	memcpy(r->packets_best, out, sizeof(mgl_packet) * n);
+	memcpy(r->segs, segs, sizeof(mgl_segment) * nseg);
+	free(out);
+	return 0;
+}
+
 static int write_stream(cli_run* r)
 {
 	const cli_opts* o = r->o;
@@ -1215,7 +1277,8 @@ int main(int argc, char** argv)
 	    final_exchange(&r) ||
 	    fetch_best(&r) ||
 	    report_costs(&r) ||
-	    choose_segments(&r)) return -1;
+	    choose_segments(&r) ||
+	    reparse_segments(&r)) return -1;
 	mgl_comm_destroy(r.comm);
 	mgl_sa_destroy(r.sa);
 	if (o.rank != 0) return 0; /* every chain holds the common best slab after the last exchange; rank 0 writes it */
